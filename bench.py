@@ -7,7 +7,7 @@ scan plan -> ADC list scan -> top-1 select) over one batch of queries that is al
 Default workload = the shape BASELINE.json's metric is quoted on ("SIFT1B PQ16 nprobe=32"): synthetic
 1B x 128-d, the reference's 993 127 centroids, PQ16, at the paper operating point (nprobe, max_codes, efSearch) =
 (32, 10000, 80) (reference examples/run_sift1b.sh:37-43), batch 10 k.  It fits ONE GPU (26 GB).  SIFT1B-shaped
-synthetic data: see tests/synth.py.  The same JSON line carries `secondary` results for configs[1] (100M, 2^17
+synthetic data: see tests/synth.py.  With --full the same JSON line carries `secondary` results for configs[1] (100M, 2^17
 centroids) and configs[2] (the 1B corpus at (64, 30000, 100)).
 
 N > 1: the SAME 1B corpus, its inverted lists sharded list-wise over the N ranks by an owner table
@@ -21,7 +21,7 @@ labels MAX-all-reduced.
   --list-shards S  (default N): the N ranks as N / S replica groups of S list shards each; a group holds the whole
                      corpus, serves its own S x 10 k batch, and its collectives stay inside the group.  S = N -- ONE copy
                      of the 1B-vector code array sharded across the N GPUs, the layout BASELINE.json's north_star names --
-                     is what `value` reports.  The same line carries `replica_groups`: the same job as 2 groups x N/2
+                     is what `value` reports.  With --full the same line carries `replica_groups`: the same job as 2 groups x N/2
                      shards (a 1B x PQ16 index is 26 GB of a GPU's 288, and list sharding replicates per-(query, shard)
                      work: DESIGN.md 7), measured in the same run on the same ranks.
 
@@ -30,6 +30,11 @@ imports torch, loads the library or touches the GPU in any way -- runs `python -
 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process, which
 prints rank 0's JSON line on the inherited stdout, and exits with its code.  Under an external launcher (WORLD_SIZE set)
 the process is a rank and runs as before.
+
+A plain run does only what the headline needs: set-up, warm-up, the --steps timed steps (`value`, `ms_per_step`, the scan
+`roofline` from the events of those steps) and, with --dump-outputs DIR, the last timed step's results as .npy files.
+Everything else -- per-stage times, sustained / one-part / pipelined / host-pointer rates, the replica layout, the walk
+roofline, the CPU baseline with parity and float order, and the secondary workloads -- runs only with --full.
 
 Prints ONE JSON line on rank 0.
 """
@@ -283,6 +288,14 @@ def main():
                     help="batches in flight for the extra 'pipelined' figure (1 GPU only; 1 = skip it)")
     ap.add_argument("--sustain-s", type=float, default=1.2, help="length of the extra sustained measurement, seconds")
     ap.add_argument("--dump", default=None, help="write rank 0's labels/distances of the last step to this .npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller (rank 0's batch) as DIR/distances.npy "
+                         "(float32) and DIR/labels.npy (float64, exact for ids < 2^53), both of shape (batch, k=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-stage times, the sustained run, the "
+                         "one-part and pipelined forms, the host-pointer rate, the replica layout (N > 1), the walk "
+                         "roofline, the CPU baseline with parity and float order, and the secondary workloads.  Without "
+                         "it a run sets up, warms up, times --steps steps and prints the headline line")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -329,7 +342,7 @@ def main():
     if world % S:
         raise SystemExit("--list-shards %d does not divide --gpus %d" % (S, world))
     R = world // S
-    S2 = world // 2 if (world > 1 and world % 2 == 0 and S == world and not args.no_replica_layout) else 0
+    S2 = world // 2 if (args.full and world > 1 and world % 2 == 0 and S == world and not args.no_replica_layout) else 0
 
     def make_group(shards):
         """This rank's process group in the layout of `shards` list shards per replica group (None = the world)."""
@@ -410,26 +423,30 @@ def main():
         return tot
 
     stage = stage_sum()
-    n_aux = 10
-    for h_ in prof_handles:
-        h_.set_profiling(1)
-        h_.reset_stage_ms()
-    timed_steps(torch, step, barrier, n_aux)
-    stage_all = stage_sum()
+    ncodes, nsegs = (sharded or g).last_scan_counts()  # per step, this shard (both parts of a two-part sharded step)
+    # what the last timed step returned to its caller (--dump-outputs, --dump, and the parity legs of --full)
+    out_dist, out_lab = d_dist.cpu().numpy(), d_lab.cpu().numpy()
+    lab_gpu = out_lab[:, 0].copy()
+    dist_gpu = out_dist[:, 0].copy()
+    n_aux, n_sus, t_sus, sus_same = 10, 0, 0.0, None
+    if args.full:
+        for h_ in prof_handles:
+            h_.set_profiling(1)
+            h_.reset_stage_ms()
+        timed_steps(torch, step, barrier, n_aux)
+        stage_all = stage_sum()
+        for name_, (ms_, n_) in stage_all.items():  # small stages: per step from the extra steps, scaled to the region
+            if name_ != "scan":
+                stage[name_] = (ms_ / n_aux * args.steps, int(round(n_ / n_aux * args.steps)))
     for h_ in prof_handles:
         h_.set_profiling(False)
-    for name_, (ms_, n_) in stage_all.items():  # small stages: per step from the extra steps, scaled to the region
-        if name_ != "scan":
-            stage[name_] = (ms_ / n_aux * args.steps, int(round(n_ / n_aux * args.steps)))
-    ncodes, nsegs = (sharded or g).last_scan_counts()  # per step, this shard (both parts of a two-part sharded step)
-    lab_gpu = d_lab.cpu().numpy()[:, 0].copy()
-    dist_gpu = d_dist.cpu().numpy()[:, 0].copy()
 
     # the same step sustained for >= 1 s (the K-step region above is tens of milliseconds: too short for the clocks
     # and the driver's SMI sampler to mean anything); stage events off, results must not change
-    n_sus = max(args.steps, int(math.ceil(args.sustain_s / max(1e-6, elapsed / args.steps))))
-    t_sus = timed_steps(torch, step, barrier, n_sus) if args.sustain_s > 0 else 0.0
-    sus_same = bool((d_lab.cpu().numpy()[:, 0] == lab_gpu).all())
+    if args.full:
+        n_sus = max(args.steps, int(math.ceil(args.sustain_s / max(1e-6, elapsed / args.steps))))
+        t_sus = timed_steps(torch, step, barrier, n_sus) if args.sustain_s > 0 else 0.0
+        sus_same = bool((d_lab.cpu().numpy()[:, 0] == lab_gpu).all())
 
     # N > 1: the same job as 2 replica groups x N/2 list shards, on the same ranks in the same run (`replica_groups`,
     # reported beside `value`, never as it): another upload of the same tables, graph and byte stream
@@ -472,7 +489,7 @@ def main():
     # the host-pointer entry point of the C ABI (queries in, distances and labels out over PCIe): SURVEY 8d's
     # end-to-end figure; never `value` (the contract wants inputs resident in HBM), reported beside it
     host_qps = None
-    if world == 1:
+    if args.full and world == 1:
         g.search(queries, 1, nprobe, max_codes, efSearch=ef, do_pruning=grouping)
         t_h = time.perf_counter()
         for _ in range(3):
@@ -486,7 +503,7 @@ def main():
     one_part = None
     parts_used = g.last_batch_parts() if world == 1 else (nq, 0)
     split_active = world == 1 and nq >= 8192 and os.environ.get("IVFHNSW_SPLIT", "") != "0" and not args.no_split
-    if split_active and not args.no_one_part:
+    if args.full and split_active and not args.no_one_part:
         g.set_batch_split(0)
         sp_d, sp_l = torch.empty_like(d_dist), torch.empty_like(d_lab)
         for _ in range(3):
@@ -523,7 +540,7 @@ def main():
     # view of the index (ivfhnsw_gpu_create_view: same tables, own workspace).  The walk is ALU-bound and ends in a
     # tail of partly filled SIMDs, the scan is HBM-bound: batches in flight overlap the two.
     pipe = None
-    if world == 1 and args.in_flight > 1:
+    if args.full and world == 1 and args.in_flight > 1:
         ctxs = [(g, torch.cuda.current_stream(), d_dist, d_lab)]
         for _ in range(args.in_flight - 1):
             v = g.view()
@@ -562,6 +579,14 @@ def main():
 
     if rank == 0 and args.dump:
         np.savez(args.dump, labels=lab_gpu, dist=dist_gpu)
+    if rank == 0 and args.dump_outputs:
+        rows = np.arange(len(out_lab))
+        cap = (64_000_000 - 4096) // 12   # 4 + 8 bytes per query: past 64 MB, a fixed seeded sample of the queries
+        if len(rows) > cap:
+            rows = np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "distances.npy"), out_dist[rows].astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "labels.npy"), out_lab[rows].astype(np.float64))
     out = None
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -600,37 +625,40 @@ def main():
                 "sharding": sharding, "replica_groups": R, "list_shards": S,
             },
             "value_is": "device-resident rate (queries and results in HBM, bench contract); SURVEY 8d's end-to-end "
-                        "figure incl. H2D/D2H is host_pointer_queries_per_s",
-            "sustained": {"steps": n_sus, "seconds": round(t_sus, 3),
-                          "queries_per_s": round(nq_job * n_sus / t_sus, 1) if t_sus > 0 else None,
-                          "results_unchanged": sus_same},
+                        "figure incl. H2D/D2H is host_pointer_queries_per_s (--full)",
             "roofline": scan_roofline(g, M, stage, traffic, args.steps),
-            "roofline_lds": pmc_lds(args.workload) if single else None,
-            # the kernel most of the step is spent in.  frac = its own HBM-side bytes (PMC) over its launch time, as a
-            # fraction of the HBM peak; the reference's dist_calc accounting (dist_evals x 4d bytes, rows
-            # the kernel's exact rejection filter mostly does not read) is reported separately by the cpu_baseline leg
-            "roofline_walk": {
-                "bound": "hbm, random kilobyte pieces (DESIGN.md 3.2: at 993 127 nodes the walk runs near the rate HBM serves them; on cache-resident graphs its instruction stream binds)", "kernel": "hnsw_walk_kernel",
-                "shape": "the whole batch in one launch (one_part): the default path's two walk launches overlap each other",
-                "traffic_calibration": "FETCH_SIZE x 2 + WRITE_SIZE; the x 2 measured on the walk's own access shapes "
-                                       "(profiles/r03_fetch_calibration.md: 2.000 for link rows, byte rows and float rows alike)",
-                "avg_launch_ms": round(walk_avg_ms, 4), "traffic": walk_traffic, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "traffic_gbps": walk_gbps, "frac": None if walk_gbps is None else round(walk_gbps / HBM_PEAK_GBPS, 4),
-            },
-            "stage_ms_per_step": {k: round(v[0] / max(1, args.steps), 4) for k, v in stage.items()},
-            "stage_note": "sums of launch durations per step; with the batch split the two parts' launches OVERLAP, so the sum "
-                          "exceeds the step (one_part.stage_ms_per_step has the one-launch-per-kernel shape).  scan: HIP "
-                          "events over the timed region; the other stages: %d extra steps with every stage bracketed (six "
-                          "event pairs per step cost 2.3 %% of it)" % n_aux,
-            "host_pointer_queries_per_s": None if host_qps is None else round(host_qps, 1),
-            "pipelined": pipe,
             "batch_split": {"parts": 2 if split_active else 1, "part_queries": list(parts_used) if split_active else None,
                             "note": "a plain ivfhnsw_gpu_search_dev call of >= 8192 queries runs as two uneven parts on two "
                                     "streams (default since ABI 9; IVFHNSW_SPLIT=0 = one part): `value`, `roofline` "
                                     "(17 B x ALL codes of the step over the SUMMED scan-launch time) and the stage "
                                     "times are this default path's"},
-            "one_part": one_part,
         }
+        if args.full:
+            out.update({
+                "sustained": {"steps": n_sus, "seconds": round(t_sus, 3),
+                              "queries_per_s": round(nq_job * n_sus / t_sus, 1) if t_sus > 0 else None,
+                              "results_unchanged": sus_same},
+                "roofline_lds": pmc_lds(args.workload) if single else None,
+                # the kernel most of the step is spent in.  frac = its own HBM-side bytes (PMC) over its launch time, as a
+                # fraction of the HBM peak; the reference's dist_calc accounting (dist_evals x 4d bytes, rows
+                # the kernel's exact rejection filter mostly does not read) is reported separately by the cpu_baseline leg
+                "roofline_walk": {
+                    "bound": "hbm, random kilobyte pieces (DESIGN.md 3.2: at 993 127 nodes the walk runs near the rate HBM serves them; on cache-resident graphs its instruction stream binds)", "kernel": "hnsw_walk_kernel",
+                    "shape": "the whole batch in one launch (one_part): the default path's two walk launches overlap each other",
+                    "traffic_calibration": "FETCH_SIZE x 2 + WRITE_SIZE; the x 2 measured on the walk's own access shapes "
+                                           "(profiles/r03_fetch_calibration.md: 2.000 for link rows, byte rows and float rows alike)",
+                    "avg_launch_ms": round(walk_avg_ms, 4), "traffic": walk_traffic, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "traffic_gbps": walk_gbps, "frac": None if walk_gbps is None else round(walk_gbps / HBM_PEAK_GBPS, 4),
+                },
+                "stage_ms_per_step": {k: round(v[0] / max(1, args.steps), 4) for k, v in stage.items()},
+                "stage_note": "sums of launch durations per step; with the batch split the two parts' launches OVERLAP, so the sum "
+                              "exceeds the step (one_part.stage_ms_per_step has the one-launch-per-kernel shape).  scan: HIP "
+                              "events over the timed region; the other stages: %d extra steps with every stage bracketed (six "
+                              "event pairs per step cost 2.3 %% of it)" % n_aux,
+                "host_pointer_queries_per_s": None if host_qps is None else round(host_qps, 1),
+                "pipelined": pipe,
+                "one_part": one_part,
+            })
         if replica is not None:
             out["replica_groups"] = replica
         if world > 1:
@@ -639,7 +667,7 @@ def main():
                                     "max_over_mean": round(float(nc_max.item()) / max(1.0, ncodes_all / world), 4)}
 
         ox = None
-        if world == 1 and args.scale == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.scale == 1 and not args.no_cpu_baseline:
             # the oracle (a port of the reference's CPU path) on the same corpus, bounded sample of the same batch
             from oracle import orc
             t0 = time.time()
@@ -712,7 +740,7 @@ def main():
 
         # secondary results in the same line: configs[2]'s operating point on the same corpus, configs[1], the metric's
         # shape on CLUSTERED centroids, and a recall-bearing index built by the library's own pipeline
-        if single and args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
+        if args.full and single and args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
             out["secondary"] = []
             try:
                 nthr = min(16, len(os.sched_getaffinity(0)))

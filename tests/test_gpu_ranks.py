@@ -46,18 +46,18 @@ def test_sharded_searcher_two_ranks_on_the_gpu(tmp_path):
 
 def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` from a bare shell, gloo ranks on the one GPU: ONE JSON line with n_gpus 2, the
-    single-copy layout (1 group x 2 list shards) as `value`, the 2 x 1 replica layout beside it, and rank 0's results
-    equal to the one-rank run of the same batch."""
+    single-copy layout (1 group x 2 list shards) as `value`, the 2 x 1 replica layout beside it (--full), and rank 0's
+    results equal to the one-rank run of the same batch, whose --dump-outputs files hold the same last step."""
     w = "synthetic-10M-pq16-nc16384-nprobe32"
     common = ["--steps", "3", "--warmup", "1", "--sustain-s", "0", "--workload", w, "--no-cpu-baseline", "--no-secondary"]
     env = _env()
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "20000", "--in-flight", "1",
-                          "--no-split", "--dump", str(tmp_path / "one.npz")] + common, env=env, capture_output=True, text=True,
-                         timeout=900, cwd=ROOT)
+                          "--no-split", "--dump", str(tmp_path / "one.npz"), "--dump-outputs", str(tmp_path / "one_out")] + common,
+                         env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-3000:]
     env["IVFHNSW_BENCH_BACKEND"] = "gloo"
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump", str(tmp_path / "two.npz")]
-                         + common, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
+                          "--dump", str(tmp_path / "two.npz")] + common, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert two.returncode == 0, two.stderr[-3000:]
     lines = [ln for ln in two.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, two.stdout[-2000:]
@@ -67,3 +67,6 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert out["replica_groups"]["groups"] == 2 and out["replica_groups"]["list_shards_per_group"] == 1
     a, b = np.load(tmp_path / "one.npz"), np.load(tmp_path / "two.npz")
     assert np.array_equal(a["labels"], b["labels"]) and np.array_equal(a["dist"].view(np.uint32), b["dist"].view(np.uint32))
+    dd, dl = np.load(tmp_path / "one_out" / "distances.npy"), np.load(tmp_path / "one_out" / "labels.npy")
+    assert dd.dtype == np.float32 and dl.dtype == np.float64 and dd.shape == dl.shape == (20000, 1)
+    assert np.array_equal(dd[:, 0].view(np.uint32), a["dist"].view(np.uint32)) and np.array_equal(dl[:, 0], a["labels"])

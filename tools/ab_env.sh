@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 VAR=$1; VALS=$2; shift; shift
 O=gpurun_out/abenv; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-secondary --in-flight 1 --sustain-s 0.5"
+B="python3 bench.py --full --no-cpu-baseline --no-secondary --in-flight 1 --sustain-s 0.5"
 for w in ${@:-synthetic-1B-pq16-nc993127-nprobe32}; do
   for v in $VALS; do
     env $VAR=$v timeout -k 10 300 $B --workload $w > $O/$w.$VAR$v.json 2> $O/$w.$VAR$v.err || echo "FAILED $w $VAR=$v"

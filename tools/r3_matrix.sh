@@ -2,7 +2,7 @@
 # round 3: the step's stages on {iid, clustered} tables x {plain k-NN graph, insertion-loop graph}, IVFADC and Grouping
 cd "$(dirname "$0")/.."
 O=gpurun_out/r3_matrix; mkdir -p $O
-B="python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --in-flight 1 --sustain-s 0"
+B="python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --in-flight 1 --sustain-s 0"
 run() { # name, env..., workload
   n=$1; shift; w=$1; shift
   env "$@" timeout -k 10 400 $B --workload $w > $O/$n.json 2> $O/$n.err || echo "FAILED $n"
