@@ -142,8 +142,10 @@ typedef struct ivfhnsw_search_params {
     size_t max_codes;
     size_t efSearch;
     int do_pruning;
-    int heap_order; /* k > 1 only: 0 = results ascending by (distance, scan position); 1 = exactly the array
-                       faiss's max-heap leaves behind (IndexIVF_HNSW.cpp:265,285-288), slot 0 = current worst */
+    int heap_order; /* k > 1 only: 0 = results ascending by (distance, scan position), k <= 1024; 1 = exactly the
+                       array faiss's max-heap leaves behind (IndexIVF_HNSW.cpp:265,285-288), slot 0 = current worst,
+                       for any k and any number of admitted codes (with out_keys: k <= 1024 and the 8192-entry
+                       candidate stream of ivfhnsw_gpu_last_stream_dev) */
 } ivfhnsw_search_params;
 
 /* IndexIVF_HNSW::search / IndexIVF_HNSW_Grouping::search (IndexIVF_HNSW.cpp:234-296,
@@ -159,7 +161,10 @@ typedef struct ivfhnsw_search_params {
  * output.  For k > 1 the same set is returned either ascending by (distance, scan position)
  * (params->heap_order = 0) or, with heap_order = 1, in exactly the heap-array order the reference leaves: the
  * device replays faiss's pop/push over a superset of the admitted codes in scan order, which yields the same
- * heap because a code that fails `dist < distances[0]` leaves the heap untouched. */
+ * heap because a code that fails `dist < distances[0]` leaves the heap untouched.  k > 1024 is accepted in heap
+ * order only; a query whose candidate stream outgrows 8192 entries is recomputed without one, so heap order has no
+ * bound on k or on the admitted codes here (the heap moves to global memory when it does not fit in LDS beside the
+ * query's table: exact, but slow). */
 int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
                        const float *coarse_dists, const ivfhnsw_search_params *params, float *distances,
                        int64_t *labels);

@@ -142,7 +142,7 @@ struct ivfhnsw_gpu {
     void *visited_zero_ptr = nullptr; // ... of this allocation
     size_t visited_zero_bytes = 0;
     DevBuf w_xq, w_luts, w_segs, w_lpos, w_hdr, w_keys, w_cid, w_cd, w_qsd, w_totals, w_visited, w_status, w_stream,
-        w_slen, w_counter, w_tail, w_redo;
+        w_slen, w_counter, w_tail, w_redo, w_hredo, w_heap;
     int opt_scan_pipe = -1;      // ivfhnsw_gpu_set_option "scan_pipe"
     bool lat_defer_redo = false; // host-pointer small batches: the latency walk flags a tie overflow, the call repeats itself
     bool latency_off = false;    // ... on the throughput walk
@@ -408,7 +408,8 @@ int ivfhnsw_gpu_create(int device, ivfhnsw_gpu **out)
     }
     h->own_stream = true;
     h->split_pm = split_permille_env();
-    // [0] status bits, [1] the walk's query counter, [2] queries on the redo list, [3] the redo launch's counter, [4] its exit count
+    // [0] status bits, [1] the walk's query counter, [2] queries on the redo list, [3] the redo launch's counter, [4] its exit count,
+    // [5] heap-order queries whose candidate stream overflowed (heap_scan_kernel redoes them), [6] that launch's exit count
     if (h->w_status.ensure(8 * sizeof(uint32_t)) || hipMemset(h->w_status.p, 0, 8 * sizeof(uint32_t)) != hipSuccess) {
         ivfhnsw_gpu_destroy(h);
         return fail(IVFHNSW_ERR_HIP, "cannot allocate the device status word");
@@ -441,7 +442,7 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
     DevBuf *all[] = {&h->goff, &h->loff, &h->cnorm, &h->pqc, &h->ntab, &h->opq_at, &h->codes, &h->ncodes, &h->ids,
                      &h->g_alpha, &h->g_nn, &h->g_sizes, &h->g_inter, &h->q_counts, &h->q_links, &h->q_vectors, &h->q_qrows, &h->q_nbrows, &h->q_nbnorms, &h->q_fat, &h->q_links_c, &h->e_pqc, &h->e_ntab, &h->e_a, &h->e_at, &h->e_x, &h->e_idx, &h->e_dist, &h->e_res, &h->e_tmp, &h->e_codes, &h->e_ncodes, &h->cg_q, &h->cg_cidx, &h->cg_ids, &h->cg_dists, &h->gc_nn, &h->cg_cvn, &h->cg_tab, &h->cg_tab2, &h->cg_off, &h->cg_alpha2, &h->cg_sub,
                      &h->w_xq, &h->w_luts, &h->w_segs, &h->w_lpos, &h->w_hdr, &h->w_keys, &h->w_cid, &h->w_cd,
-                     &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len};
+                     &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len};
     for (auto *b : all)
         b->release();
     h->p_in.release();
@@ -1509,8 +1510,9 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
     if (nq > 0 && (!d_queries || !d_distances || !d_labels))
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
-    if (k > 1024)
-        return fail(IVFHNSW_ERR_INVALID, "k %zu > 1024 unsupported", k);
+    // k > 1024 only in heap order on the labels path: heap_scan_kernel, no stream
+    if (k > 1024 && (!p->heap_order || d_out_keys))
+        return fail(IVFHNSW_ERR_INVALID, "k %zu > 1024 unsupported (only heap_order = 1 without out_keys)", k);
     if (nq > 0x7fffffffull / (k > p->nprobe ? k : p->nprobe))
         return fail(IVFHNSW_ERR_INVALID, "nq too large");
     if (h->has_group && !h->has_graph)
@@ -1524,13 +1526,16 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
 
     const int d = h->t.d, M = h->t.M, nprobe = (int)p->nprobe;
     const int max_seg = h->has_group ? nprobe * h->g.nsubc : nprobe;
+    // k > 1024: the heap-order scan only (no top-k keys, no stream); the plan kernels reset one key per query
+    const bool heap_big = k > 1024;
+    const int plan_k = heap_big ? 1 : (int)k;
     if ((rc = h->w_segs.ensure(nq * (size_t)max_seg * sizeof(Seg))))
         return rc;
     if ((rc = h->w_lpos.ensure(nq * (size_t)max_seg * sizeof(uint32_t))))
         return rc;
     if ((rc = h->w_hdr.ensure(nq * sizeof(PlanHdr))))
         return rc;
-    if ((rc = h->w_keys.ensure(nq * k * sizeof(uint64_t))))
+    if ((rc = h->w_keys.ensure(nq * (size_t)plan_k * sizeof(uint64_t))))
         return rc;
     if ((rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
@@ -1622,7 +1627,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
         StageScope sc(h, IVFHNSW_STAGE_LUT); // plan + tables: one kernel, accounted as the table stage
         HIP_TRY(launch_plan_lut(h->stream, h->t, xq, cid, cd, (int)nq, nprobe, p->max_codes, h->w_segs.as<Seg>(),
                                 h->w_lpos.as<uint32_t>(), h->w_hdr.as<PlanHdr>(), max_seg, h->w_keys.as<uint64_t>(),
-                                (int)k, h->w_luts.as<float>()));
+                                plan_k, h->w_luts.as<float>()));
     } else {
         StageScope sc(h, IVFHNSW_STAGE_PLAN);
         if (h->has_group) {
@@ -1631,18 +1636,39 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
                 return rc;
             HIP_TRY(launch_plan_grouping(h->stream, h->t, h->g, h->gr, xq, cid, cd, (int)nq, nprobe, p->max_codes,
                                          p->do_pruning, h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                         h->w_hdr.as<PlanHdr>(), max_seg, h->w_keys.as<uint64_t>(), (int)k,
+                                         h->w_hdr.as<PlanHdr>(), max_seg, h->w_keys.as<uint64_t>(), plan_k,
                                          h->w_qsd.as<float>()));
         } else {
             HIP_TRY(launch_plan_ivf(h->stream, h->t, cid, cd, (int)nq, nprobe, p->max_codes, h->w_segs.as<Seg>(),
                                     h->w_lpos.as<uint32_t>(), h->w_hdr.as<PlanHdr>(), max_seg,
-                                    h->w_keys.as<uint64_t>(), (int)k));
+                                    h->w_keys.as<uint64_t>(), plan_k));
         }
     }
     // 4. table (IndexIVF_HNSW.cpp:262)
     if (!pipe && !plan_lut) {
         StageScope sc(h, IVFHNSW_STAGE_LUT);
         HIP_TRY(launch_lut(h->stream, h->t, xq, h->w_luts.as<float>(), (int)nq, h->w_hdr.as<PlanHdr>()));
+    }
+    // heap_scan_kernel's global-tier heaps (k beyond what fits in LDS beside the table) and its redo list
+    float *heap_ws = nullptr;
+    if (heap && !d_out_keys) {
+        if ((rc = h->w_heap.ensure(heap_scan_ws_bytes(M, (int)k, (int)nq))))
+            return rc;
+        heap_ws = h->w_heap.as<float>();
+    }
+    if (heap_big) {
+        // 5-6. scan and heap replay in one kernel, every query of the batch (IndexIVF_HNSW.cpp:282-289)
+        {
+            StageScope sc(h, IVFHNSW_STAGE_SCAN);
+            HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
+                                     h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, nullptr, nullptr, heap_ws,
+                                     d_distances, d_labels));
+        }
+        h->last_scan_kernel = "heap_scan_kernel";
+        h->last_nq = (int)nq;
+        h->last_max_seg = max_seg;
+        h->last_stream = false; // no candidate stream exists
+        return IVFHNSW_OK;
     }
     // 5. scan (IndexIVF_HNSW.cpp:282-289)
     bool scan_selected = false;
@@ -1652,6 +1678,8 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
         if ((rc = h->w_stream.ensure(nq * (size_t)kHeapStreamCap * sizeof(uint64_t))))
             return rc;
         if ((rc = h->w_slen.ensure(nq * sizeof(uint32_t))))
+            return rc;
+        if (!d_out_keys && (rc = h->w_hredo.ensure(nq * sizeof(uint32_t))))
             return rc;
     }
     {
@@ -1674,11 +1702,19 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
     // 6. select
     if (!scan_selected) {
         StageScope sc(h, IVFHNSW_STAGE_SELECT);
-        if (heap && !d_out_keys)
+        if (heap && !d_out_keys) {
+            // a query whose stream overflowed goes on the redo list instead of failing the batch; heap_scan_kernel redoes
+            // it from the plan and the table.  Fixed grid, count read on the device: no host synchronisation, and an
+            // empty list costs one launch that exits at once (its last workgroup re-zeroes w_status[5..6])
+            uint32_t *redo_hdr = h->w_status.as<uint32_t>() + 5;
             HIP_TRY(launch_heap_replay(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), max_seg,
                                        h->w_stream.as<uint64_t>(), h->w_slen.as<uint32_t>(), kHeapStreamCap, (int)nq,
-                                       (int)k, d_distances, d_labels, status_word(h), nullptr));
-        else
+                                       (int)k, d_distances, d_labels, status_word(h), nullptr, redo_hdr,
+                                       h->w_hredo.as<uint32_t>()));
+            HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
+                                     h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, redo_hdr,
+                                     h->w_hredo.as<uint32_t>(), heap_ws, d_distances, d_labels));
+        } else
             HIP_TRY(launch_select(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), max_seg,
                                   h->w_keys.as<uint64_t>(), (int)nq, (int)k, d_distances, d_labels, d_out_keys));
     }
@@ -2217,7 +2253,7 @@ int ivfhnsw_gpu_memory_bytes(ivfhnsw_gpu *h, uint64_t *bytes)
     const DevBuf *all[] = {&h->goff, &h->loff, &h->cnorm, &h->pqc, &h->ntab, &h->opq_at, &h->codes, &h->ncodes,
                            &h->ids, &h->g_alpha, &h->g_nn, &h->g_sizes, &h->g_inter, &h->q_counts, &h->q_links,
                            &h->q_vectors, &h->q_qrows, &h->q_nbrows, &h->q_nbnorms, &h->q_fat, &h->q_links_c, &h->e_pqc, &h->e_ntab, &h->e_a, &h->e_at, &h->e_x, &h->e_idx, &h->e_dist, &h->e_res, &h->e_tmp, &h->e_codes, &h->e_ncodes, &h->cg_q, &h->cg_cidx, &h->cg_ids, &h->cg_dists, &h->gc_nn, &h->cg_cvn, &h->cg_tab, &h->cg_tab2, &h->cg_off, &h->cg_alpha2, &h->cg_sub, &h->w_xq, &h->w_luts, &h->w_segs, &h->w_lpos, &h->w_hdr, &h->w_keys,
-                           &h->w_cid, &h->w_cd, &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd,
+                           &h->w_cid, &h->w_cd, &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd,
                            &h->s_dist, &h->s_lab};
     uint64_t s = 0;
     for (auto *b : all)

@@ -434,4 +434,44 @@ template <int CS> __device__ __forceinline__ float code_sum(const float *s_lut, 
         return r.sum;
 }
 
+// faiss Heap.h semantics on a 1-based binary max-heap of k values (0-based arrays val / ids), values compared only:
+// the replay of IndexIVF_HNSW.cpp:285-288 (kernels_topk.hip heap_replay_kernel, kernels_heap.hip heap_scan_kernel)
+template <typename ID>
+__device__ __forceinline__ void heap_replace_top(int k, float *val, ID *ids, float nv, ID nid)
+{
+    // maxheap_pop followed by maxheap_push, as the reference calls them
+    float *v = val - 1;
+    ID *id = ids - 1;
+    {
+        const float last = v[k];
+        int hole = 1;
+        for (;;) {
+            const int l = hole * 2, r = l + 1;
+            if (l > k)
+                break;
+            const int big = (r == k + 1 || v[l] > v[r]) ? l : r;
+            if (last > v[big])
+                break;
+            v[hole] = v[big];
+            id[hole] = id[big];
+            hole = big;
+        }
+        v[hole] = v[k];
+        id[hole] = id[k];
+    }
+    {
+        int hole = k;
+        while (hole > 1) {
+            const int parent = hole / 2;
+            if (!(nv > v[parent]))
+                break;
+            v[hole] = v[parent];
+            id[hole] = id[parent];
+            hole = parent;
+        }
+        v[hole] = nv;
+        id[hole] = nid;
+    }
+}
+
 } // namespace ivfhnsw_gpu_impl

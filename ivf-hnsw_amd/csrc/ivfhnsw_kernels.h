@@ -157,7 +157,18 @@ const char *last_scan_kernel_name(); // the kernel the calling thread's last lau
 hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
                               const uint64_t *stream, const uint32_t *stream_len, uint32_t stream_cap, int nq, int k,
                               float *dist, int64_t *labels, uint32_t *status,
-                              int64_t *out_keys = nullptr); // non-null: the heap array as signed keys, no labels (sharded)
+                              int64_t *out_keys = nullptr, // non-null: the heap array as signed keys, no labels (sharded)
+                              // non-null (labels path only): a query whose stream overflowed is appended to redo_list
+                              // (redo_hdr[0] counts them) instead of raising kStatusTopkStreamOverflow
+                              uint32_t *redo_hdr = nullptr, uint32_t *redo_list = nullptr);
+// k > 1 in faiss heap-array order straight from the plan and the tables, no stream and no bound on k or on the admitted
+// codes (kernels_heap.hip).  redo_list null: every query of the batch; else the redo_hdr[0] queries listed by
+// launch_heap_replay, and the launch's last workgroup re-zeroes redo_hdr[0..1].  heap_ws: heap_scan_ws_bytes of scratch.
+bool heap_scan_lds_tier(int code_size, int k);
+size_t heap_scan_ws_bytes(int code_size, int k, int nq);
+hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
+                            const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
+                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels);
 // keys -> (distance, label) through the plan; also emits signed-orderable keys when out_keys != null
 hipError_t launch_select(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
                          const uint64_t *keys, int nq, int k, float *dist, int64_t *labels, int64_t *out_keys);

@@ -1,0 +1,275 @@
+// k > 1 in faiss heap-array order with no bound on k and none on the codes the heap admits (IndexIVF_HNSW.cpp:265,
+// 285-288).  heap_scan_kernel scores a query's codes straight from the plan and the table the search has built, with the
+// arithmetic of scan_topk_kernel (kernels_topk.hip), and replays the reference's pop/push over them itself: no candidate
+// stream, so no stream cap.
+//
+// Exactness is the argument above heap_replay_kernel: a code that fails dist < distances[0] leaves the heap untouched, and
+// a root read earlier in the scan is never below the current root.  So the codes of a chunk that pass dist < root, with
+// root read when the chunk starts, are a superset of the codes the heap admits from that chunk, in scan order, and
+// replaying them (strict '<' against the CURRENT root, values only) leaves the reference's heap array bit for bit.
+//
+// One 256-thread workgroup per query.  The heap is (value, scan position) pairs; labels are resolved for the k survivors
+// at the end.  Two tiers, chosen per launch from k and the code size (heap_scan_lds_tier):
+//   LDS     the heap beside the table and the chunk buffer (8 k bytes; k <~ 16 500 at PQ16, <~ 2 200 at code size 128)
+//   global  the heap in a per-workgroup slot of a global workspace: exact but slow, every level of a sift is a round
+//           trip to L2 (~200 cycles instead of ~50 for a dependent ds_read)
+#include "ivfhnsw_kernels.h"
+#include "device_common.h"
+
+#include <float.h>
+
+namespace ivfhnsw_gpu_impl {
+
+constexpr int HS_U = 4;                // codes per thread per chunk
+constexpr int HS_CHUNK = 256 * HS_U;   // codes scored between two replays
+constexpr int HS_SEGCAP = 256;         // plan segments staged in LDS at a time
+constexpr int HS_GRID_MAX = 1024;      // workgroups per launch (the launch walks its queries with a grid stride)
+constexpr size_t HS_WS_MAX = 512ull << 20; // global tier: bound on the heap workspace (grid x 8 k bytes)
+constexpr size_t HS_LDS = 160 * 1024;      // LDS of one workgroup on gfx950
+// static LDS of the kernel (norm table, segments, chunk buffer, counts) with room for alignment
+constexpr size_t HS_STATIC_LDS = 256 * 4 + HS_SEGCAP * sizeof(Seg) + (HS_SEGCAP + 1) * 4 + HS_CHUNK * 8 + HS_U * 4 * 4 + 512;
+
+template <int CS, bool LDS_HEAP>
+__global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float *__restrict__ luts,
+                                                        const Seg *__restrict__ segs, const uint32_t *__restrict__ lpos,
+                                                        const PlanHdr *__restrict__ hdr, int max_seg, int nq, int k,
+                                                        uint32_t *__restrict__ redo_hdr,
+                                                        const uint32_t *__restrict__ redo_list, float *__restrict__ heap_ws,
+                                                        float *__restrict__ dist, long long *__restrict__ labels)
+{
+    // dynamic LDS: the query's table [csz][256], then (LDS tier) the heap's values [k] and scan positions [k]
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+    __shared__ float s_norm[256];
+    __shared__ __attribute__((aligned(16))) Seg s_seg[HS_SEGCAP];
+    __shared__ uint32_t s_lpos[HS_SEGCAP + 1];
+    __shared__ float s_cd[HS_CHUNK];    // the chunk's candidates in scan order: value ...
+    __shared__ uint32_t s_cp[HS_CHUNK]; // ... and scan position
+    __shared__ uint32_t s_wcnt[HS_U][4];
+
+    const int tid = threadIdx.x;
+    const int csz = CS > 0 ? CS : t.M;
+    float *s_lut = s_dyn;
+    float *val = LDS_HEAP ? s_dyn + (size_t)csz * 256 : heap_ws + (size_t)blockIdx.x * 2 * k;
+    uint32_t *hpos = reinterpret_cast<uint32_t *>(val + k);
+    s_norm[tid] = t.norm_table[tid];
+    // redo form: the queries heap_replay_kernel listed (the count is stable until the last workgroup below clears it)
+    const uint32_t n = redo_list ? redo_hdr[0] : (uint32_t)nq;
+
+    for (uint32_t item = blockIdx.x; item < n; item += gridDim.x) {
+        const int q = redo_list ? (int)redo_list[item] : (int)item;
+        const PlanHdr h = hdr[q];
+        __syncthreads(); // the previous query's label pass is done with the heap
+        for (int j = tid; j < k; j += 256) { // maxheap_heapify
+            val[j] = FLT_MAX;
+            hpos[j] = 0xffffffffu;
+        }
+        if (h.total) {
+            const float4 *src = reinterpret_cast<const float4 *>(luts + (size_t)q * csz * 256);
+            float4 *dst = reinterpret_cast<float4 *>(s_lut);
+            for (int i = tid; i < csz * 64; i += 256)
+                dst[i] = src[i];
+        }
+        const Seg *sq = segs + (size_t)q * max_seg;
+        const uint32_t *lq = lpos + (size_t)q * max_seg;
+        const uint32_t nseg = h.total ? h.nseg : 0u;
+        for (uint32_t cs = 0; cs < nseg; cs += HS_SEGCAP) {
+            const uint32_t cn = min((uint32_t)HS_SEGCAP, nseg - cs);
+            __syncthreads();
+            for (uint32_t i = tid; i < cn; i += 256) {
+                s_seg[i] = sq[cs + i];
+                s_lpos[i] = lq[cs + i];
+            }
+            const uint32_t ch = (cs + cn == nseg) ? h.total : lq[cs + cn];
+            if (tid == 0)
+                s_lpos[cn] = ch;
+            __syncthreads();
+            const uint32_t cl = s_lpos[0];
+            // the segment this lane is inside, kept in registers (positions only grow)
+            uint32_t s = 0, seg_lo = 0, seg_hi = 0, seg_start = 0, seg_vpos = 0;
+            float seg_ct = 0.f;
+            for (uint32_t base = cl; base < ch; base += HS_CHUNK) {
+                const float root = val[0]; // the heap is at rest here (barrier behind the last replay)
+                CodeRegs<CS> w[HS_U];
+                uint32_t nbv[HS_U], vp[HS_U];
+                float ct[HS_U], dn[HS_U];
+                bool ok[HS_U], pass[HS_U];
+#pragma unroll
+                for (int u = 0; u < HS_U; u++) {
+                    const uint32_t p = base + u * 256 + tid;
+                    ok[u] = p < ch;
+                    if (ok[u]) {
+                        if (p >= seg_hi) {
+                            uint32_t a = s, b = cn - 1;
+                            while (a < b) {
+                                const uint32_t mid = (a + b) >> 1;
+                                if (s_lpos[mid + 1] > p)
+                                    b = mid;
+                                else
+                                    a = mid + 1;
+                            }
+                            s = a;
+                            const Seg sg = s_seg[s];
+                            seg_lo = s_lpos[s];
+                            seg_hi = seg_lo + sg.len;
+                            seg_start = sg.start;
+                            seg_vpos = sg.vpos;
+                            seg_ct = sg.cterm;
+                        }
+                        const uint32_t off = p - seg_lo;
+                        const uint32_t gi = seg_start + off;
+                        code_fetch<CS>(t.codes, gi, t.M, s_lut, w[u]);
+                        nbv[u] = t.norm_codes[gi];
+                        vp[u] = seg_vpos + off;
+                        ct[u] = seg_ct;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < HS_U; u++) {
+                    pass[u] = false;
+                    dn[u] = 0.f;
+                    if (ok[u]) {
+                        // scan_topk_kernel's arithmetic, term for term
+                        const float sum = code_sum<CS>(s_lut, w[u]);
+                        const float tt = __fadd_rn(ct[u], s_norm[nbv[u]]);
+                        const float d = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                        if (d < FLT_MAX) {
+                            dn[u] = __fadd_rn(d, 0.0f);
+                            pass[u] = dn[u] < root;
+                        }
+                    }
+                }
+                // compact the candidates in scan order (unroll step, then wave, then lane)
+                unsigned long long bal[HS_U];
+#pragma unroll
+                for (int u = 0; u < HS_U; u++) {
+                    bal[u] = __ballot(pass[u]);
+                    if ((tid & 63) == 0)
+                        s_wcnt[u][tid >> 6] = (uint32_t)__popcll(bal[u]);
+                }
+                __syncthreads();
+                uint32_t total = 0, mine[HS_U];
+#pragma unroll
+                for (int u = 0; u < HS_U; u++) {
+                    mine[u] = total;
+#pragma unroll
+                    for (int w2 = 0; w2 < 4; w2++) {
+                        const uint32_t c = s_wcnt[u][w2];
+                        if (w2 < (tid >> 6))
+                            mine[u] += c;
+                        total += c;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < HS_U; u++)
+                    if (pass[u]) {
+                        const uint32_t i = mine[u] + (uint32_t)__popcll(bal[u] & ((1ull << (tid & 63)) - 1ull));
+                        s_cd[i] = dn[u];
+                        s_cp[i] = vp[u];
+                    }
+                __syncthreads();
+                if (tid == 0)
+                    for (uint32_t i = 0; i < total; i++) {
+                        const float d = s_cd[i];
+                        if (d < val[0])
+                            heap_replace_top<uint32_t>(k, val, hpos, d, s_cp[i]);
+                    }
+                __syncthreads();
+            }
+        }
+        __syncthreads();
+        // labels of the survivors (segments ascend in vpos)
+        float *out_d = dist + (size_t)q * k;
+        long long *out_l = labels + (size_t)q * k;
+        for (int j = tid; j < k; j += 256) {
+            const uint32_t vpos = hpos[j];
+            long long lab = -1;
+            if (vpos != 0xffffffffu && h.nseg) {
+                uint32_t a = 0, b = h.nseg - 1;
+                while (a < b) {
+                    const uint32_t mid = (a + b + 1) >> 1;
+                    if (sq[mid].vpos <= vpos)
+                        a = mid;
+                    else
+                        b = mid - 1;
+                }
+                const Seg sg = sq[a];
+                lab = (long long)t.ids[sg.start + (vpos - sg.vpos)];
+            }
+            out_d[j] = val[j];
+            out_l[j] = lab;
+        }
+    }
+    if (redo_list) {
+        // the last workgroup out leaves the list's header zero for the next search (no memset on the stream)
+        __syncthreads();
+        if (tid == 0) {
+            __threadfence();
+            if (atomicAdd(&redo_hdr[1], 1u) == gridDim.x - 1) {
+                redo_hdr[0] = 0;
+                redo_hdr[1] = 0;
+            }
+        }
+    }
+}
+
+bool heap_scan_lds_tier(int code_size, int k)
+{
+    return HS_STATIC_LDS + (size_t)code_size * 1024 + (size_t)8 * k <= HS_LDS;
+}
+
+static int heap_scan_grid(int code_size, int k, int nq)
+{
+    size_t g = std::min<size_t>((size_t)nq, HS_GRID_MAX);
+    if (!heap_scan_lds_tier(code_size, k))
+        g = std::min(g, HS_WS_MAX / ((size_t)8 * k));
+    return (int)std::max<size_t>(g, 1);
+}
+
+size_t heap_scan_ws_bytes(int code_size, int k, int nq)
+{
+    return heap_scan_lds_tier(code_size, k) ? 0 : (size_t)heap_scan_grid(code_size, k, nq) * 8 * k;
+}
+
+template <int CS, bool LDS_HEAP>
+static hipError_t launch_heap_scan_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
+                                      const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k,
+                                      uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist,
+                                      int64_t *labels)
+{
+    auto *kern = heap_scan_kernel<CS, LDS_HEAP>;
+    const size_t shm = (size_t)t.M * 1024 + (LDS_HEAP ? (size_t)8 * k : 0);
+    static DynLdsState attr_set;
+    if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)heap_scan_grid(t.M, k, nq)), dim3(256), shm, s, t, luts, segs, lpos, hdr,
+                       max_seg, nq, k, redo_hdr, redo_list, heap_ws, dist, reinterpret_cast<long long *>(labels));
+    return hipGetLastError();
+}
+
+hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
+                            const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
+                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (k < 1 || t.M % 4 || (size_t)t.M * 1024 > kScanDynLdsMax || (redo_list && !redo_hdr))
+        return hipErrorInvalidValue;
+    const bool lds = heap_scan_lds_tier(t.M, k);
+    if (!lds && !heap_ws)
+        return hipErrorInvalidValue;
+#define IVFHNSW_HEAP_SCAN(CS)                                                                                         \
+    return lds ? launch_heap_scan_cs<CS, true>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,     \
+                                               heap_ws, dist, labels)                                                 \
+               : launch_heap_scan_cs<CS, false>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,    \
+                                                heap_ws, dist, labels)
+    switch (t.M) {
+    case 4: IVFHNSW_HEAP_SCAN(4);
+    case 8: IVFHNSW_HEAP_SCAN(8);
+    case 16: IVFHNSW_HEAP_SCAN(16);
+    case 32: IVFHNSW_HEAP_SCAN(32);
+    default: IVFHNSW_HEAP_SCAN(0); // any other multiple of 4: the run-time form
+    }
+#undef IVFHNSW_HEAP_SCAN
+}
+
+} // namespace ivfhnsw_gpu_impl

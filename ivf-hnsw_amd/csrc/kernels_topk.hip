@@ -245,43 +245,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
 // the candidate stream above is such a superset (its filter threshold is never below the heap's current
 // maximum).  One thread per query; faiss Heap.h semantics (1-based binary max-heap on values only).
 // ---------------------------------------------------------------------------------------------
-template <typename ID>
-__device__ __forceinline__ void heap_replace_top(int k, float *val, ID *ids, float nv, ID nid)
-{
-    // maxheap_pop followed by maxheap_push, as the reference calls them
-    float *v = val - 1;
-    ID *id = ids - 1;
-    {
-        const float last = v[k];
-        int hole = 1;
-        for (;;) {
-            const int l = hole * 2, r = l + 1;
-            if (l > k)
-                break;
-            const int big = (r == k + 1 || v[l] > v[r]) ? l : r;
-            if (last > v[big])
-                break;
-            v[hole] = v[big];
-            id[hole] = id[big];
-            hole = big;
-        }
-        v[hole] = v[k];
-        id[hole] = id[k];
-    }
-    {
-        int hole = k;
-        while (hole > 1) {
-            const int parent = hole / 2;
-            if (!(nv > v[parent]))
-                break;
-            v[hole] = v[parent];
-            id[hole] = id[parent];
-            hole = parent;
-        }
-        v[hole] = nv;
-        id[hole] = nid;
-    }
-}
+// (heap_replace_top, faiss's maxheap_pop + maxheap_push: device_common.h)
 
 // One wavefront per query (four per workgroup).  The heap lives in LDS as (value, scan position); the stream is
 // read 64 keys at a time by all lanes, keys that cannot pass (not below the heap's maximum at the start of the
@@ -293,7 +257,8 @@ __global__ __launch_bounds__(256) void heap_replay_kernel(IvfTables t, const Seg
                                                           const uint32_t *__restrict__ stream_len, uint32_t stream_cap,
                                                           int nq, int k, float *__restrict__ dist,
                                                           long long *__restrict__ labels, uint32_t *__restrict__ status,
-                                                          long long *__restrict__ out_keys)
+                                                          long long *__restrict__ out_keys, uint32_t *__restrict__ redo_hdr,
+                                                          uint32_t *__restrict__ redo_list)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -311,6 +276,13 @@ __global__ __launch_bounds__(256) void heap_replay_kernel(IvfTables t, const Seg
     long long *out_l = labels + (size_t)q * k;
     long long *out_k = out_keys ? out_keys + (size_t)q * k : nullptr;
     if (len > stream_cap) {
+        if (redo_list) {
+            // the stream was truncated: heap_scan_kernel (kernels_heap.hip) redoes this query from the plan and the
+            // table, and writes its row
+            if (lane == 0)
+                redo_list[atomicAdd(&redo_hdr[0], 1u)] = (uint32_t)q;
+            return;
+        }
         if (lane == 0)
             atomicOr(status, kStatusTopkStreamOverflow);
         for (int j = lane; j < k; j += 64) {
@@ -382,13 +354,15 @@ __global__ __launch_bounds__(256) void heap_replay_kernel(IvfTables t, const Seg
 
 hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
                               const uint64_t *stream, const uint32_t *stream_len, uint32_t stream_cap, int nq, int k,
-                              float *dist, int64_t *labels, uint32_t *status, int64_t *out_keys)
+                              float *dist, int64_t *labels, uint32_t *status, int64_t *out_keys, uint32_t *redo_hdr,
+                              uint32_t *redo_list)
 {
     if (nq == 0)
         return hipSuccess;
     hipLaunchKernelGGL(heap_replay_kernel, dim3((nq + 3) / 4), dim3(256), (size_t)4 * 2 * k * sizeof(float), s, t, segs, hdr, max_seg,
                        reinterpret_cast<const unsigned long long *>(stream), stream_len, stream_cap, nq, k, dist,
-                       reinterpret_cast<long long *>(labels), status, reinterpret_cast<long long *>(out_keys));
+                       reinterpret_cast<long long *>(labels), status, reinterpret_cast<long long *>(out_keys), redo_hdr,
+                       redo_list);
     return hipGetLastError();
 }
 

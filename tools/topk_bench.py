@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """k > 1 throughput of the search path on the bench corpus (configs[1] shape): both result orders
 (heap_order 0 = ascending, 1 = the array faiss's max-heap leaves).  Host-pointer API, so PCIe is included.
-usage: python tools/topk_bench.py [--ks 1,10,100]"""
+--heap-big: the heap-order cases beyond the candidate stream (heap_scan_kernel, kernels_heap.hip) instead -- k = 1000
+with max_codes 100000 (streams overflow and are redone), k = 4096 (LDS heap) and k = 17000 (global heap at PQ16), on
+fewer queries (the results are nq x k).
+usage: python tools/topk_bench.py [--ks 1,10,100] [--heap-big]"""
 import argparse
 import os
 import sys
@@ -17,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="1,10,100")
+    ap.add_argument("--heap-big", action="store_true")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -32,6 +36,17 @@ def main():
     g = pkg.GpuIndex(0)
     g.upload_ivf_synthetic(d, M, tb["offsets"], cn, tb["pq_centroids"], tb["norm_table"], 1241)
     g.upload_quantizer(counts, links, tb["centroids"], 0)
+    if args.heap_big:
+        for k, mc, n in ((1000, 100000, 2000), (4096, max_codes, 2000), (17000, max_codes, 200)):
+            q = queries[:n]
+            g.search(q, k, nprobe, mc, efSearch=ef, heap_order=True)
+            t0 = time.perf_counter()
+            for _ in range(3):
+                g.search(q, k, nprobe, mc, efSearch=ef, heap_order=True)
+            t = (time.perf_counter() - t0) / 3
+            print("heap_order=1 k=%d max_codes=%d nq=%d: %.2f ms = %.4f M q/s" % (k, mc, n, t * 1e3, n / t / 1e6),
+                  flush=True)
+        return
     for k in [int(x) for x in args.ks.split(",")]:
         for heap in (False, True):
             if k == 1 and heap:
