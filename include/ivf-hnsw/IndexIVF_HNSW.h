@@ -5,7 +5,8 @@
 // C ABI of <ivfhnsw_hip.h> (HNSW walk, PQ table, ADC scan and top-k all on the device).  There is no CPU search
 // path: without a gfx950 device search() throws.
 //
-// Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device().
+// Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
+// release_base(), searchDisk_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
 
@@ -114,6 +115,17 @@ public:
     /// Extension: call after mutating ids/codes/norm_codes/pq/... behind the class's back.
     void invalidate_device() { device_dirty_ = true; }
 
+    /// Extension: the raw uint8 base vectors of a .bvecs file (the rows searchDisk reads, utils.cpp:98-105) into HBM,
+    /// streamed in chunks of at most 256 MB with every record's dim header checked.  searchDisk / searchDisk_batch with
+    /// the same path then re-rank on the device.  release_base() frees the copy.
+    void upload_base(const char *path_base);
+    void release_base();
+    /// Extension: searchDisk for nq queries (IndexIVF_HNSW_Grouping.cpp:365-395): search_batch for kc candidates
+    /// (kc = 0: k, exactly nq searchDisk calls; larger: "search more, keep k"), then the k best by exact distance
+    /// against the base rows -- on the device when upload_base() loaded path_base and kc <= 4096, else from the file.
+    void searchDisk_batch(size_t nq, size_t k, const float *x, float *distances, long *labels, const char *path_base,
+                          size_t kc = 0);
+
 protected:
     std::vector<float> precomputed_table;
     float pq_L2sqr(const uint8_t *code);
@@ -142,6 +154,11 @@ protected:
                        size_t nprobe_, size_t max_codes_, bool pruning, float *distances, long *labels);
     void upload_graph_to(ivfhnsw_gpu *handle);
     virtual bool shards_need_graph() const { return false; } ///< Grouping: sub-centroid distances on every shard
+    /// searchDisk's second half: cand [nq*kc] (-1 = empty) re-ranked by exact distance against path_base, k kept
+    void rerank_candidates(size_t nq, size_t kc, const float *x, const long *cand, size_t k, float *distances,
+                           long *labels, const char *path_base);
+    bool device_base_for(const char *path_base);
+    int load_base(const char *path_base);
 
 private:
     void reconstruct(size_t n, float *x, const float *decoded_residuals, const idx_t *keys);

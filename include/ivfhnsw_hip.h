@@ -237,6 +237,36 @@ int ivfhnsw_gpu_rotate_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, fl
 int ivfhnsw_gpu_coarse(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t k, size_t efSearch,
                        uint32_t *ids, float *dists);
 
+/* ---- exact re-rank against the raw base vectors (IndexIVF_HNSW_Grouping::searchDisk) ------------------------------
+ *
+ * The raw base vectors the reference's searchDisk reads (utils.cpp:98-105: .bvecs records, uint32 dim + d bytes).
+ * first == 0 (re)allocates n*d bytes, zero-filled, and frees any previous store; every call copies rows
+ * [first, first+count): row r is read at rows + r*row_stride (row_stride >= d; d + 4 takes a .bvecs file image as it
+ * is, `rows` pointing past the first record's 4-byte header).  n == 0 frees the store.  Needs d % 16 == 0,
+ * 16 <= d <= 512 (fvec_L2sqr ignores a tail beyond 16*(d/16), utils.cpp:22-52) and n < 2^32; a later call whose n or d
+ * differs from the store's: IVFHNSW_ERR_INVALID.  A failed allocation: IVFHNSW_ERR_NOMEM and no store.  Views see the
+ * parent's store; ivfhnsw_gpu_memory_bytes counts it.  Synchronous: `rows` may be reused when the call returns.
+ * upload_base_dev: the same with the rows already in HBM (device pointer). */
+int ivfhnsw_gpu_upload_base(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const uint8_t *rows,
+                            size_t row_stride);
+int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const uint8_t *d_rows,
+                                size_t row_stride);
+
+/* searchDisk's exact re-rank for nq queries (IndexIVF_HNSW_Grouping.cpp:365-395): d_cand[nq*kc] are labels a search
+ * returned (-1 = empty), queries are unrotated (getL2Distance compares the raw query with the raw base row,
+ * utils.cpp:98-137); writes the k best by (exact distance, label) ascending, [nq*k], padded with FLT_MAX / -1 when fewer
+ * than k candidates are valid (IndexIVF_HNSW_Grouping.cpp:384-394).  Distance = fvec_L2sqr (utils.cpp:22-52) bit for
+ * bit; duplicate labels stay duplicates; a label >= n counts as empty.  The reference sorts by `cmp` (utils.cpp:193-201),
+ * which treats distances within 0.001 as equal: the same order whenever no two different distances of a query lie that
+ * close, always so for integer-valued queries.  1 <= k <= kc <= 4096, else IVFHNSW_ERR_INVALID; no
+ * store: IVFHNSW_ERR_STATE.  Device pointers, asynchronous on the handle's stream (ordered after a search_dev on the same
+ * stream). */
+int ivfhnsw_gpu_rerank_dev(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *d_queries, const int64_t *d_cand,
+                           size_t k, float *d_distances, int64_t *d_labels);
+/* host pointers, synchronous; a candidate label outside [-1, n) -> IVFHNSW_ERR_INVALID, nothing written */
+int ivfhnsw_gpu_rerank(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *queries, const int64_t *cand,
+                       size_t k, float *distances, int64_t *labels);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 /* ---- construction side: what IndexIVF_HNSW::add_batch computes before it appends --------

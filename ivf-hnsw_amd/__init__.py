@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_last_stream_dev", "ivfhnsw_gpu_replay_stream_dev", "ivfhnsw_gpu_pq_train", "ivfhnsw_gpu_xty",
     "ivfhnsw_gpu_prepare_latency", "ivfhnsw_gpu_set_batch_split", "ivfhnsw_gpu_last_batch_parts", "ivfhnsw_gpu_search_keys", "ivfhnsw_gpu_resolve_keys", "ivfhnsw_gpu_last_stream",
     "ivfhnsw_gpu_device_count", "ivfhnsw_gpu_knn", "ivfhnsw_gpu_knn_dev", "ivfhnsw_gpu_build_graph", "ivfhnsw_gpu_set_option", "ivfhnsw_gpu_search_sharded",
+    "ivfhnsw_gpu_upload_base", "ivfhnsw_gpu_upload_base_dev", "ivfhnsw_gpu_rerank_dev", "ivfhnsw_gpu_rerank",
 )
 
 
@@ -119,6 +120,12 @@ def lib():
         L.ivfhnsw_gpu_prepare_latency.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_set_batch_split.argtypes = [C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_last_batch_parts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_upload_base.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                              C.c_size_t]
+        L.ivfhnsw_gpu_upload_base_dev.argtypes = L.ivfhnsw_gpu_upload_base.argtypes
+        L.ivfhnsw_gpu_rerank_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_rerank.argtypes = L.ivfhnsw_gpu_rerank_dev.argtypes
         L.ivfhnsw_gpu_last_scan_kernel.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_last_scan_kernel.restype = C.c_char_p
         _lib = L
@@ -171,6 +178,7 @@ class GpuIndex:
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
+        self._device = device
         _check(lib().ivfhnsw_gpu_create(device, C.byref(self._h)))
         self.d = self.nc = self.code_size = 0
 
@@ -181,6 +189,7 @@ class GpuIndex:
         v._h = C.c_void_p()
         _check(lib().ivfhnsw_gpu_create_view(self._h, C.byref(v._h)))
         v.d, v.nc, v.code_size = self.d, self.nc, self.code_size
+        v._device = self._device
         v._parent = self
         return v
 
@@ -422,6 +431,89 @@ class GpuIndex:
 
     def set_stream(self, stream_ptr):
         _check(lib().ivfhnsw_gpu_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    # ---- exact re-rank (IndexIVF_HNSW_Grouping::searchDisk) --------------------------------------------------------
+    def upload_base(self, rows_u8, n=None, first=0, row_stride=None):
+        """Rows [first, first + count) of the uint8 base store (ivfhnsw_gpu_upload_base).  rows_u8: [count, d] uint8 whose
+        rows may lie row_stride bytes apart (default: its own row stride; raw[:, 4:] of a [count, d + 4] .bvecs image
+        is taken as it is).  n: rows of the whole store (default first + count); first == 0 (re)allocates it."""
+        a = np.asarray(rows_u8)
+        assert a.dtype == np.uint8 and a.ndim == 2, "rows_u8: a 2-D uint8 array [count, d]"
+        count, d = a.shape
+        stride = a.strides[0] if row_stride is None else row_stride
+        assert count == 0 or (a.strides[1] == 1 and (count == 1 or a.strides[0] == stride)), \
+            "rows must be contiguous inside a row and row_stride apart"
+        n = first + count if n is None else n
+        _check(lib().ivfhnsw_gpu_upload_base(self._h, n, d, first, count, C.c_void_p(a.ctypes.data) if count else None,
+                                             max(stride, d)))
+        self.base_n, self.base_d = n, d
+
+    def upload_base_dev(self, n, d, first, count, d_rows, row_stride=None):
+        """The same from HBM (a torch CUDA uint8 tensor or a device address); synchronous."""
+        _check(lib().ivfhnsw_gpu_upload_base_dev(self._h, n, d, first, count, _devptr(d_rows),
+                                                 d if row_stride is None else row_stride))
+        self.base_n, self.base_d = n, d
+
+    def upload_base_bvecs(self, path, chunk_rows=1 << 20):
+        """Stream a .bvecs file (records: int32 dim + dim bytes) into the base store in chunks of chunk_rows records;
+        every record's dim header is checked."""
+        with open(path, "rb") as f:
+            d = int(np.frombuffer(f.read(4), np.int32)[0])
+            rec = d + 4
+            size = os.fstat(f.fileno()).st_size
+            if d <= 0 or size % rec:
+                raise ValueError("%s: not a .bvecs file of dimension %d" % (path, d))
+            n = size // rec
+            f.seek(0)
+            for first in range(0, n, chunk_rows):
+                m = min(chunk_rows, n - first)
+                raw = np.frombuffer(f.read(m * rec), np.uint8).reshape(m, rec)
+                dims = raw[:, :4].copy().view(np.int32)[:, 0]
+                if (dims != d).any():
+                    bad = int(np.nonzero(dims != d)[0][0])
+                    raise ValueError("%s: record %d has dimension %d, expected %d" % (path, first + bad, dims[bad], d))
+                self.upload_base(raw[:, 4:], n=n, first=first, row_stride=rec)
+        return n, d
+
+    def rerank(self, queries, cand, k):
+        """Host arrays: the k best of every query's candidate labels ([nq, kc] int64, -1 = empty) by (exact L2 against
+        the base store, label): (distances f32 [nq, k], labels i64 [nq, k])."""
+        c = _np(cand, np.int64)
+        c = c.reshape(c.shape[0] if c.ndim > 1 else 1, -1)
+        nq, kc = c.shape
+        q = _np(queries, np.float32).reshape(nq, -1)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_rerank(self._h, nq, kc, _ptr(q), _ptr(c), k, _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def rerank_dev(self, nq, kc, d_queries, d_cand, k, d_distances, d_labels):
+        """Device buffers (torch CUDA tensors), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_rerank_dev(self._h, nq, kc, _devptr(d_queries), _devptr(d_cand), k, _devptr(d_distances),
+                                            _devptr(d_labels)))
+
+    def search_rerank(self, queries, k, kc, nprobe, max_codes, efSearch=0, do_pruning=False, coarse_ids=None,
+                      coarse_dists=None):
+        """searchDisk for a batch: search_dev for kc candidates (ascending, heap_order 0), then rerank_dev on the same
+        stream, with no host round trip in between.  Host arrays in and out: (distances [nq, k], labels [nq, k])."""
+        import torch
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        dev = torch.device("cuda", self._device)
+        tq = torch.from_numpy(q).to(dev)
+        tcid = None if coarse_ids is None else torch.from_numpy(_np(coarse_ids, np.uint32).reshape(nq, nprobe).view(np.int32)).to(dev)
+        tcd = None if coarse_dists is None else torch.from_numpy(_np(coarse_dists, np.float32).reshape(nq, nprobe)).to(dev)
+        cd = torch.empty((nq, kc), dtype=torch.float32, device=dev)
+        cl = torch.empty((nq, kc), dtype=torch.int64, device=dev)
+        od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)  # the copies above ran on torch's stream, the library runs on the handle's
+        self.search_dev(nq, kc, tq, cd, cl, nprobe, max_codes, d_coarse_ids=tcid, d_coarse_dists=tcd, efSearch=efSearch,
+                        do_pruning=do_pruning)
+        self.rerank_dev(nq, kc, tq, cl, k, od, ol)
+        self.sync()
+        return od.cpu().numpy(), ol.cpu().numpy()
 
     # ---- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on):

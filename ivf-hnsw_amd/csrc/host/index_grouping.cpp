@@ -82,24 +82,13 @@ void IndexIVF_HNSW_Grouping::search(size_t k, const float *x, float *distances, 
 void IndexIVF_HNSW_Grouping::searchDisk(size_t k, const float *query, float *distances, long *labels,
                                         const char *path_base)
 {
-    // ANN search, then exact re-ranking of its k results against the base file (the reference reads 2k results
-    // out of a k-sized search, IndexIVF_HNSW_Grouping.cpp:368-383; this re-ranks the k that exist)
+    // ANN search, then exact re-ranking of its k results against the base rows (the reference reads 2k results
+    // out of a k-sized search, IndexIVF_HNSW_Grouping.cpp:368-383; this re-ranks the k that exist): on the device when it
+    // holds path_base (upload_base, or IVFHNSW_RERANK=device), else from the file as the reference does
     std::vector<float> d0(k);
     std::vector<long> l0(k);
     search(k, query, d0.data(), l0.data());
-    std::vector<SearchInfo_t> ranked;
-    for (size_t i = 0; i < k; i++)
-        if (l0[i] >= 0) {
-            SearchInfo_t s;
-            s.label = l0[i];
-            s.distance = getL2Distance(query, path_base, d, l0[i], base_vec);
-            ranked.push_back(s);
-        }
-    std::sort(ranked.begin(), ranked.end(), cmp);
-    for (size_t i = 0; i < k; i++) {
-        distances[i] = i < ranked.size() ? ranked[i].distance : FLT_MAX;
-        labels[i] = i < ranked.size() ? ranked[i].label : -1;
-    }
+    rerank_candidates(1, k, query, l0.data(), k, distances, labels, path_base);
 }
 
 void IndexIVF_HNSW_Grouping::write(const char *path_index, bool do_trunc)

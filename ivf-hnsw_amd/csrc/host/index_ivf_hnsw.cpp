@@ -8,10 +8,14 @@
 #include <ivfhnsw_hip.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 
 namespace ivfhnsw {
 
@@ -20,6 +24,32 @@ namespace {
 [[noreturn]] void gpu_fail(const char *what)
 {
     throw std::runtime_error(std::string(what) + ": " + ivfhnsw_gpu_last_error());
+}
+
+// What searchDisk's device re-rank knows about an index: the .bvecs file its device holds ("" = none) and whether
+// IVFHNSW_RERANK=device already tried to load one.  Kept beside the object, not in it: drivers compiled against an
+// earlier IndexIVF_HNSW.h allocate the object with that header's size, so the class layout must not grow.
+struct BaseState {
+    std::string path;
+    bool auto_tried = false;
+};
+std::mutex g_base_mu;
+std::unordered_map<const void *, BaseState> g_base;
+
+BaseState base_state(const void *ix)
+{
+    std::lock_guard<std::mutex> lk(g_base_mu);
+    auto it = g_base.find(ix);
+    return it == g_base.end() ? BaseState() : it->second;
+}
+
+void set_base_state(const void *ix, const BaseState &st)
+{
+    std::lock_guard<std::mutex> lk(g_base_mu);
+    if (st.path.empty() && !st.auto_tried)
+        g_base.erase(ix);
+    else
+        g_base[ix] = st;
 }
 
 } // namespace
@@ -44,6 +74,7 @@ IndexIVF_HNSW::IndexIVF_HNSW(size_t dim, size_t ncentroids, size_t bytes_per_cod
 
 IndexIVF_HNSW::~IndexIVF_HNSW()
 {
+    set_base_state(this, BaseState());
     for (ivfhnsw_gpu *sh : shards_)
         ivfhnsw_gpu_destroy(sh);
     if (gpu_)
@@ -457,6 +488,140 @@ void IndexIVF_HNSW::search_batch(size_t nq, size_t k, const float *x, float *dis
 {
     ensure_device();
     device_search(nq, k, x, nullptr, nullptr, nprobe, max_codes, false, distances, labels);
+}
+
+// ------------------------------------------------------------------------------------------ searchDisk's re-rank
+// The base file in HBM (ivfhnsw_gpu_upload_base): records of uint32 dim + d bytes (utils.cpp:98-105), read in chunks of
+// at most 256 MB and handed over as the file image, rows d + 4 bytes apart.  Returns the library's status; file errors
+// throw.
+int IndexIVF_HNSW::load_base(const char *path_base)
+{
+    if (!gpu_ && ivfhnsw_gpu_create(0, &gpu_))
+        gpu_fail("ivfhnsw_gpu_create");
+    FILE *f = fopen(path_base, "rb");
+    if (!f)
+        throw std::runtime_error(std::string("IndexIVF_HNSW::upload_base: cannot open ") + path_base);
+    const size_t rec = sizeof(uint32_t) + d;
+    fseek(f, 0, SEEK_END);
+    const long size = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (size < 0 || (size_t)size % rec) {
+        fclose(f);
+        throw std::runtime_error(std::string("IndexIVF_HNSW::upload_base: size of ") + path_base +
+                                 " is not a multiple of the record size 4 + d");
+    }
+    const size_t n = (size_t)size / rec, chunk = std::max<size_t>(1, ((size_t)256 << 20) / rec);
+    std::vector<uint8_t> buf(std::min(chunk, n) * rec + 1);
+    BaseState st = base_state(this);
+    st.path.clear();
+    set_base_state(this, st);
+    int rc = IVFHNSW_OK;
+    for (size_t first = 0; first < n && rc == IVFHNSW_OK; first += chunk) {
+        const size_t m = std::min(chunk, n - first);
+        if (fread(buf.data(), rec, m, f) != m) {
+            fclose(f);
+            throw std::runtime_error(std::string("IndexIVF_HNSW::upload_base: short read of ") + path_base);
+        }
+        for (size_t r = 0; r < m; r++) {
+            uint32_t dim;
+            std::memcpy(&dim, buf.data() + r * rec, sizeof(dim));
+            if (dim != d) {
+                fclose(f);
+                ivfhnsw_gpu_upload_base(gpu_, 0, d, 0, 0, nullptr, d); // no half-loaded store
+                throw std::runtime_error(std::string("IndexIVF_HNSW::upload_base: record ") + std::to_string(first + r) +
+                                         " of " + path_base + " has dimension " + std::to_string(dim) + ", not " +
+                                         std::to_string(d));
+            }
+        }
+        rc = ivfhnsw_gpu_upload_base(gpu_, n, d, first, m, buf.data() + sizeof(uint32_t), rec);
+    }
+    fclose(f);
+    if (rc == IVFHNSW_OK && n) {
+        st.path = path_base;
+        set_base_state(this, st);
+    }
+    return rc;
+}
+
+void IndexIVF_HNSW::upload_base(const char *path_base)
+{
+    if (load_base(path_base) != IVFHNSW_OK)
+        gpu_fail("ivfhnsw_gpu_upload_base");
+}
+
+void IndexIVF_HNSW::release_base()
+{
+    BaseState st = base_state(this);
+    st.path.clear();
+    set_base_state(this, st);
+    if (gpu_ && ivfhnsw_gpu_upload_base(gpu_, 0, d, 0, 0, nullptr, d))
+        gpu_fail("ivfhnsw_gpu_upload_base");
+}
+
+// Does the device hold path_base?  With IVFHNSW_RERANK=device the first call loads it; a store that does not fit in
+// HBM (or a d the device form does not take) leaves the host loop in charge.
+bool IndexIVF_HNSW::device_base_for(const char *path_base)
+{
+    BaseState st = base_state(this);
+    if (!st.path.empty())
+        return st.path == path_base;
+    static const bool auto_load = [] {
+        const char *e = getenv("IVFHNSW_RERANK");
+        return e && std::string(e) == "device";
+    }();
+    if (!auto_load || st.auto_tried)
+        return false;
+    st.auto_tried = true;
+    set_base_state(this, st);
+    const int rc = load_base(path_base);
+    if (rc == IVFHNSW_OK)
+        return true;
+    if (rc != IVFHNSW_ERR_NOMEM && rc != IVFHNSW_ERR_INVALID)
+        gpu_fail("ivfhnsw_gpu_upload_base");
+    std::fprintf(stderr, "IVFHNSW_RERANK=device: %s not loaded (%s); searchDisk re-ranks from the file\n", path_base,
+                 ivfhnsw_gpu_last_error());
+    return false;
+}
+
+void IndexIVF_HNSW::rerank_candidates(size_t nq, size_t kc, const float *x, const long *cand, size_t k, float *distances,
+                                      long *labels, const char *path_base)
+{
+    if (kc <= 4096 && device_base_for(path_base)) {
+        if (ivfhnsw_gpu_rerank(gpu_, nq, kc, x, reinterpret_cast<const int64_t *>(cand), k, distances,
+                               reinterpret_cast<int64_t *>(labels)))
+            gpu_fail("ivfhnsw_gpu_rerank");
+        return;
+    }
+    // the reference's loop (IndexIVF_HNSW_Grouping.cpp:375-394): one read of the base file per result, cmp's order
+    std::vector<SearchInfo_t> ranked;
+    for (size_t q = 0; q < nq; q++) {
+        ranked.clear();
+        for (size_t i = 0; i < kc; i++)
+            if (cand[q * kc + i] >= 0) {
+                SearchInfo_t s;
+                s.label = cand[q * kc + i];
+                s.distance = getL2Distance(x + q * d, path_base, d, cand[q * kc + i], base_vec);
+                ranked.push_back(s);
+            }
+        std::sort(ranked.begin(), ranked.end(), cmp);
+        for (size_t i = 0; i < k; i++) {
+            distances[q * k + i] = i < ranked.size() ? ranked[i].distance : FLT_MAX;
+            labels[q * k + i] = i < ranked.size() ? ranked[i].label : -1;
+        }
+    }
+}
+
+void IndexIVF_HNSW::searchDisk_batch(size_t nq, size_t k, const float *x, float *distances, long *labels,
+                                     const char *path_base, size_t kc)
+{
+    if (kc == 0)
+        kc = k;
+    if (k == 0 || kc < k)
+        throw std::invalid_argument("IndexIVF_HNSW::searchDisk_batch: needs 1 <= k <= kc");
+    std::vector<float> dc(nq * kc);
+    std::vector<long> lc(nq * kc);
+    search_batch(nq, kc, x, dc.data(), lc.data());
+    rerank_candidates(nq, kc, x, lc.data(), k, distances, labels, path_base);
 }
 
 void IndexIVF_HNSW::search(size_t k, const float *x, float *distances, long *labels)

@@ -242,6 +242,12 @@ hipError_t launch_fill_bytes(hipStream_t s, uint8_t *dst, size_t nbytes, uint64_
 hipError_t launch_fill_iota(hipStream_t s, uint32_t *dst, size_t n, uint32_t first);
 hipError_t launch_fill_lists(hipStream_t s, const IvfTables &t, uint8_t *codes, uint8_t *norm_codes, uint32_t *ids,
                              uint64_t seed_codes, uint64_t seed_norms);
+// exact re-rank against the uint8 base store (kernels_rerank.hip): rows [count] at src_stride -> the store's layout at dst;
+// then for nq queries the k best of kc candidate labels by (exact distance, label), empty slots FLT_MAX / -1
+hipError_t launch_rerank_permute(hipStream_t s, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t count, int d);
+size_t rerank_lds_bytes(int kc, int d);
+hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
+                         const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels);
 // sum of PlanHdr.total / nseg over the batch into out[0], out[1]
 hipError_t launch_plan_totals(hipStream_t s, const PlanHdr *hdr, int nq, unsigned long long *out);
 
