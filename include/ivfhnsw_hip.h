@@ -323,6 +323,32 @@ int ivfhnsw_gpu_pq_train(ivfhnsw_gpu *h, size_t n, size_t d, size_t M, const flo
                          uint8_t *out_assign);
 int ivfhnsw_gpu_xty(ivfhnsw_gpu *h, size_t n, size_t d, const float *X, const float *Y, float *C);
 
+/* ivfhnsw_gpu_kmeans: exact Lloyd k-means of the IVF coarse centroids, the input the reference never learns (its
+ * drivers read it as -path_centroids and hand it to IndexIVF_HNSW::build_quantizer, IndexIVF_HNSW.cpp:34-66; the
+ * README points to downloaded files).  x [n][d] (host); centroids [nc][d] (host) are the seeds in and the result out;
+ * out_assign (nullable) [n]: the last iteration's assignment; out_obj (nullable, host) [niter]: each iteration's
+ * objective.  One iteration, exactly:
+ *   1. assign[i], dist[i] = the k = 1 result of ivfhnsw_gpu_knn (IVFHNSW_KNN_ALL) of x against the current centroids:
+ *      (norm(x) + norm(c)) - 2 * dot with fmaf-chain norms and dots, ties to the lower id;
+ *   2. obj[t] = sum of dist[i] in double (order free);
+ *   3. every cluster with cnt > 0: component j = S / (float)cnt rounded once, S the float sum of the members' component
+ *      j in ascending point index from 0.0f (lloyd_update_kernel's rule); an empty cluster keeps its row;
+ *   4. empty clusters ci, ascending (faiss's split_clusters, its random pick made deterministic): cj = the cluster with
+ *      the largest current count, ties to the lower id (counts changed by earlier splits of this iteration count);
+ *      row ci = row cj; then for even j c[ci][j] *= 1 + EPS and c[cj][j] *= 1 - EPS, for odd j the other way round
+ *      (EPS = 1/1024, float); cnt[ci] = cnt[cj] / 2, cnt[cj] -= cnt[ci].  The pairs are applied in that order.
+ * Limits: 1 <= nc <= n < 2^31, d a multiple of 4 with d <= 128 (knn's).  niter = 0 returns the seeds unchanged and
+ * writes nothing else.  Anything else, or a NULL x / centroids, returns IVFHNSW_ERR_INVALID and touches no buffer.
+ * A point with no finite distance (NaN / inf input) returns IVFHNSW_ERR_STATE.  Needs no upload, and leaves the index
+ * the handle holds as it was.
+ * ivfhnsw_gpu_kmeans_dev: the same on device pointers (16-byte aligned) on the handle's stream; out_obj stays host
+ * memory.  Synchronises once per iteration (the counts come to the host, where the splits are chosen) and returns when
+ * it is done. */
+int ivfhnsw_gpu_kmeans(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const float *x, size_t niter, float *centroids,
+                       uint32_t *out_assign, double *out_obj);
+int ivfhnsw_gpu_kmeans_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const float *d_x, size_t niter, float *d_centroids,
+                           uint32_t *d_out_assign, double *out_obj);
+
 /* ---- exact nearest-neighbour tables and graph construction -------------------------------------
  *
  * ivfhnsw_gpu_knn: for each of nq query rows the k nearest of nx base rows by brute force on the matrix cores -- the exact

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_prepare_latency", "ivfhnsw_gpu_set_batch_split", "ivfhnsw_gpu_last_batch_parts", "ivfhnsw_gpu_search_keys", "ivfhnsw_gpu_resolve_keys", "ivfhnsw_gpu_last_stream",
     "ivfhnsw_gpu_device_count", "ivfhnsw_gpu_knn", "ivfhnsw_gpu_knn_dev", "ivfhnsw_gpu_build_graph", "ivfhnsw_gpu_set_option", "ivfhnsw_gpu_search_sharded",
     "ivfhnsw_gpu_upload_base", "ivfhnsw_gpu_upload_base_dev", "ivfhnsw_gpu_rerank_dev", "ivfhnsw_gpu_rerank",
+    "ivfhnsw_gpu_kmeans", "ivfhnsw_gpu_kmeans_dev",
 )
 
 
@@ -108,6 +109,9 @@ def lib():
         L.ivfhnsw_gpu_pq_train.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_xty.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_kmeans.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_kmeans_dev.argtypes = L.ivfhnsw_gpu_kmeans.argtypes
         L.ivfhnsw_gpu_knn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_build_graph.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
@@ -388,6 +392,25 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_xty(self._h, n, d, _ptr(X), _ptr(Y), _ptr(out)))
         return out
 
+    def kmeans(self, x, centroids, niter):
+        """niter exact Lloyd iterations of the coarse centroids (ivfhnsw_gpu_kmeans): x [n, d], seeds [nc, d] ->
+        (centroids f32 [nc, d], assign u32 [n] of the last iteration, obj f64 [niter])."""
+        x = _np(x, np.float32)
+        n, d = x.shape
+        c = _np(centroids, np.float32).reshape(-1, d).copy()
+        a = np.zeros(n, np.uint32)
+        obj = np.zeros(niter, np.float64)
+        _check(lib().ivfhnsw_gpu_kmeans(self._h, n, d, c.shape[0], _ptr(x), niter, _ptr(c), _ptr(a), _ptr(obj)))
+        return c, a, obj
+
+    def kmeans_dev(self, n, d, nc, d_x, niter, d_centroids, d_assign=None):
+        """The same on device buffers (torch CUDA tensors; d_centroids updated in place, d_assign [n] u32/i32 or None);
+        returns obj f64 [niter] (host)."""
+        obj = np.zeros(niter, np.float64)
+        _check(lib().ivfhnsw_gpu_kmeans_dev(self._h, n, d, nc, _devptr(d_x), niter, _devptr(d_centroids),
+                                            _devptr(d_assign), _ptr(obj)))
+        return obj
+
     KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2
 
     def knn(self, base, k, queries=None, mode=None):
@@ -457,21 +480,13 @@ class GpuIndex:
     def upload_base_bvecs(self, path, chunk_rows=1 << 20):
         """Stream a .bvecs file (records: int32 dim + dim bytes) into the base store in chunks of chunk_rows records;
         every record's dim header is checked."""
+        n, d = xvecs_shape(path, 1)
+        rec = d + 4
         with open(path, "rb") as f:
-            d = int(np.frombuffer(f.read(4), np.int32)[0])
-            rec = d + 4
-            size = os.fstat(f.fileno()).st_size
-            if d <= 0 or size % rec:
-                raise ValueError("%s: not a .bvecs file of dimension %d" % (path, d))
-            n = size // rec
-            f.seek(0)
             for first in range(0, n, chunk_rows):
                 m = min(chunk_rows, n - first)
                 raw = np.frombuffer(f.read(m * rec), np.uint8).reshape(m, rec)
-                dims = raw[:, :4].copy().view(np.int32)[:, 0]
-                if (dims != d).any():
-                    bad = int(np.nonzero(dims != d)[0][0])
-                    raise ValueError("%s: record %d has dimension %d, expected %d" % (path, first + bad, dims[bad], d))
+                _check_dims(path, raw[:, :4].copy().view(np.int32)[:, 0], d, first)
                 self.upload_base(raw[:, 4:], n=n, first=first, row_stride=rec)
         return n, d
 
@@ -543,3 +558,76 @@ class GpuIndex:
         a = C.c_uint64()
         _check(lib().ivfhnsw_gpu_memory_bytes(self._h, C.byref(a)))
         return a.value
+
+
+# ---- .bvecs / .fvecs files (utils.h readXvec: records of an int32 dim and dim elements) -------------------------------
+def xvecs_shape(path, itemsize):
+    """(n, d) of a .bvecs (itemsize 1) / .fvecs (4) file, from its first header and its size."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(4)
+    d = int(np.frombuffer(head, np.int32)[0]) if len(head) == 4 else 0
+    if d <= 0 or size % (4 + d * itemsize):
+        raise ValueError("%s: not a %s file of dimension %d" % (path, ".bvecs" if itemsize == 1 else ".fvecs", d))
+    return size // (4 + d * itemsize), d
+
+
+def _check_dims(path, dims, d, first=0, rows=None):
+    if (dims != d).any():
+        bad = int(np.nonzero(dims != d)[0][0])
+        rec = first + bad if rows is None else int(rows[bad])
+        raise ValueError("%s: record %d has dimension %d, expected %d" % (path, rec, dims[bad], d))
+
+
+def open_xvecs(path):
+    """Memory-map a .bvecs (uint8) or .fvecs (float32) file: rows [n, d], a read-only view; only the rows a caller
+    indexes are read.  read_xvecs checks the dim headers of the rows it returns."""
+    itemsize = 1 if path.endswith(".bvecs") else 4
+    n, d = xvecs_shape(path, itemsize)
+    rec = np.dtype([("dim", "<i4"), ("v", np.uint8 if itemsize == 1 else "<f4", (d,))])
+    return np.memmap(path, dtype=rec, mode="r", shape=(n,))
+
+
+def read_xvecs(path, rows=None):
+    """Rows (all, or the sorted index array `rows`) of a .bvecs / .fvecs file, every record's dim header checked."""
+    mm = open_xvecs(path)
+    d = mm.dtype["v"].shape[0]
+    recs = mm if rows is None else mm[np.asarray(rows)]
+    _check_dims(path, np.asarray(recs["dim"]), d, rows=rows)
+    return np.ascontiguousarray(recs["v"])
+
+
+def write_fvecs(path, x):
+    """x [n, d] as a .fvecs file: what build_quantizer (IndexIVF_HNSW.cpp:34-66) reads as the centroids."""
+    x = np.ascontiguousarray(x, np.float32)
+    n, d = x.shape
+    rec = np.empty(n, np.dtype([("dim", "<i4"), ("v", "<f4", (d,))]))
+    rec["dim"] = d
+    rec["v"] = x
+    rec.tofile(path)
+
+
+# ---- coarse centroids -------------------------------------------------------------------------------------------------
+def learn_centroids(x, nc, niter=10, seed=1234, max_points_per_centroid=256, device=0):
+    """nc coarse centroids of x [n, d] (uint8 or float; a memory map is read only where sampled) by exact Lloyd k-means
+    on the device (ivfhnsw_gpu_kmeans): at most nc * max_points_per_centroid rows, drawn without replacement (faiss's
+    rule), in file order; seeds = nc distinct rows of that sample; both draws from numpy.random.default_rng(seed).
+    Returns (centroids f32 [nc, d], obj f64 [niter])."""
+    n = len(x)
+    if not 1 <= nc <= n:
+        raise ValueError("need 1 <= nc <= n (nc %d, n %d)" % (nc, n))
+    rng = np.random.default_rng(seed)
+    cap = nc * max_points_per_centroid
+    if n > cap:
+        pick = np.sort(rng.choice(n, size=cap, replace=False))
+        xs = np.asarray(x[pick], np.float32)
+    else:
+        xs = np.asarray(x, np.float32)
+    xs = np.ascontiguousarray(xs)
+    seeds = xs[rng.choice(len(xs), size=nc, replace=False)]
+    g = GpuIndex(device)
+    try:
+        c, _, obj = g.kmeans(xs, seeds, niter)
+    finally:
+        g.close()
+    return c, obj

@@ -125,6 +125,8 @@ struct ivfhnsw_gpu {
     DevBuf e_pqc, e_ntab, e_a, e_at, e_x, e_idx, e_dist, e_res, e_tmp, e_codes, e_ncodes;
     DevBuf t_x, t_y, t_cb, t_assign, t_part, t_c; // training (pq_train, xty)
     DevBuf k_q, k_x, k_qn, k_xn, k_part, k_ids, k_dists; // exact neighbour tables (ivfhnsw_gpu_knn)
+    DevBuf km_x, km_c, km_assign, km_dist, km_cnt, km_start, km_ids, km_ids2, km_hist, km_part, km_status,
+        km_pairs; // coarse k-means (ivfhnsw_gpu_kmeans)
     DevBuf cg_q, cg_cidx, cg_ids, cg_dists, gc_nn, cg_cvn, cg_tab, cg_tab2, cg_off, cg_alpha2, cg_sub; // add_group
     size_t e_d = 0, e_M = 0;
     bool e_opq = false, has_codebooks = false;
@@ -449,7 +451,9 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
     DevBuf *all[] = {&h->goff, &h->loff, &h->cnorm, &h->pqc, &h->ntab, &h->opq_at, &h->codes, &h->ncodes, &h->ids,
                      &h->g_alpha, &h->g_nn, &h->g_sizes, &h->g_inter, &h->q_counts, &h->q_links, &h->q_vectors, &h->q_qrows, &h->q_nbrows, &h->q_nbnorms, &h->q_fat, &h->q_links_c, &h->e_pqc, &h->e_ntab, &h->e_a, &h->e_at, &h->e_x, &h->e_idx, &h->e_dist, &h->e_res, &h->e_tmp, &h->e_codes, &h->e_ncodes, &h->cg_q, &h->cg_cidx, &h->cg_ids, &h->cg_dists, &h->gc_nn, &h->cg_cvn, &h->cg_tab, &h->cg_tab2, &h->cg_off, &h->cg_alpha2, &h->cg_sub,
                      &h->w_xq, &h->w_luts, &h->w_segs, &h->w_lpos, &h->w_hdr, &h->w_keys, &h->w_cid, &h->w_cd,
-                     &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab};
+                     &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab,
+                     &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2, &h->km_hist,
+                     &h->km_part, &h->km_status, &h->km_pairs};
     for (auto *b : all)
         b->release();
     h->p_in.release();
@@ -1343,6 +1347,157 @@ int ivfhnsw_gpu_knn(ivfhnsw_gpu *h, size_t nq, size_t nx, size_t d, const float 
     HIP_TRY(hipMemcpy(out_ids, h->k_ids.p, nq * k * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_dists)
         HIP_TRY(hipMemcpy(out_dists, h->k_dists.p, nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
+extern "C++" {
+namespace {
+
+int kmeans_check(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const void *x, const void *c)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (d < 4 || d > 128 || (d & 3))
+        return fail(IVFHNSW_ERR_INVALID, "kmeans: d %zu must be a multiple of 4, at most 128", d);
+    if (nc < 1 || nc > n || n > 0x7fffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "kmeans: need 1 <= nc <= n < 2^31 (n %zu, nc %zu)", n, nc);
+    if (!x || !c)
+        return fail(IVFHNSW_ERR_INVALID, "kmeans: null buffer");
+    return IVFHNSW_OK;
+}
+
+// faiss's split_clusters with the random choice replaced: every empty cluster ci, ascending, takes the cluster cj with
+// the largest CURRENT count (ties to the lower id); cnt[ci] = cnt[cj] / 2, cnt[cj] -= cnt[ci].  n >= nc keeps a count
+// >= 2 in the heap while a cluster is empty, so ci never stays empty.  Heap entries are (count, ~id); an entry whose
+// count is no longer the cluster's is stale (a split only lowers cj's count) and is dropped when it surfaces.
+void kmeans_pick_splits(std::vector<uint32_t> &cnt, std::vector<uint32_t> &pairs)
+{
+    pairs.clear();
+    std::vector<std::pair<uint32_t, uint32_t>> heap;
+    for (size_t c = 0; c < cnt.size(); c++)
+        if (cnt[c])
+            heap.emplace_back(cnt[c], ~(uint32_t)c);
+    if (heap.size() == cnt.size())
+        return;
+    std::make_heap(heap.begin(), heap.end());
+    for (size_t ci = 0; ci < cnt.size(); ci++) {
+        if (cnt[ci])
+            continue;
+        uint32_t cj;
+        for (;;) {
+            std::pop_heap(heap.begin(), heap.end());
+            const auto top = heap.back();
+            heap.pop_back();
+            cj = ~top.second;
+            if (top.first == cnt[cj])
+                break;
+        }
+        cnt[ci] = cnt[cj] / 2;
+        cnt[cj] -= cnt[ci];
+        pairs.push_back((uint32_t)ci);
+        pairs.push_back(cj);
+        heap.emplace_back(cnt[cj], ~cj);
+        std::push_heap(heap.begin(), heap.end());
+        heap.emplace_back(cnt[ci], ~(uint32_t)ci);
+        std::push_heap(heap.begin(), heap.end());
+    }
+}
+
+// niter Lloyd iterations on device buffers: assign (knn k = 1), objective, counts, stable member lists,
+// means, splits.  One synchronisation per iteration: the counts and the objective's partial sums come to the host.
+int kmeans_run(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const float *d_x, size_t niter, float *d_c,
+               uint32_t *d_out_assign, double *out_obj) try
+{
+    const size_t nblocks = (n + kKmeansTile - 1) / kKmeansTile;
+    int rc;
+    if ((rc = h->km_assign.ensure(n * sizeof(uint32_t))) || (rc = h->km_dist.ensure(n * sizeof(float))) ||
+        (rc = h->km_ids.ensure(n * sizeof(uint32_t))) || (rc = h->km_ids2.ensure(n * sizeof(uint32_t))) ||
+        (rc = h->km_cnt.ensure(nc * sizeof(uint32_t))) || (rc = h->km_start.ensure(nc * sizeof(uint32_t))) ||
+        (rc = h->km_hist.ensure(256 * nblocks * sizeof(uint32_t))) || (rc = h->km_part.ensure(nblocks * sizeof(double))) ||
+        (rc = h->km_status.ensure(sizeof(uint32_t))) || (rc = h->km_pairs.ensure(2 * nc * sizeof(uint32_t))))
+        return rc;
+    int key_bits = 0;
+    while (key_bits < 32 && ((nc - 1) >> key_bits))
+        key_bits++;
+    uint32_t *assign = h->km_assign.as<uint32_t>(), *cnt = h->km_cnt.as<uint32_t>();
+    std::vector<uint32_t> hcnt(nc), pairs;
+    std::vector<double> hpart(nblocks);
+    uint32_t status = 0;
+    for (size_t it = 0; it < niter; it++) {
+        if ((rc = ivfhnsw_gpu_knn_dev(h, n, nc, d, d_x, d_c, 1, IVFHNSW_KNN_ALL, assign, h->km_dist.as<float>())))
+            return rc;
+        HIP_TRY(hipMemsetAsync(cnt, 0, nc * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipMemsetAsync(h->km_status.p, 0, sizeof(uint32_t), h->stream));
+        HIP_TRY(launch_kmeans_count(h->stream, assign, h->km_dist.as<float>(), n, (uint32_t)nc, cnt,
+                                    h->km_part.as<double>(), h->km_status.as<uint32_t>()));
+        HIP_TRY(launch_scan_u32(h->stream, cnt, h->km_start.as<uint32_t>(), nc));
+        uint32_t *members = nullptr;
+        HIP_TRY(launch_sort_by_key(h->stream, assign, n, key_bits, h->km_ids.as<uint32_t>(), h->km_ids2.as<uint32_t>(),
+                                   h->km_hist.as<uint32_t>(), &members));
+        HIP_TRY(launch_kmeans_means(h->stream, d_x, n, members, h->km_start.as<uint32_t>(), cnt, d_c, nc, (int)d));
+        HIP_TRY(hipMemcpyAsync(hcnt.data(), cnt, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(hpart.data(), h->km_part.p, nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&status, h->km_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (status)
+            return fail(IVFHNSW_ERR_STATE, "kmeans: a point has no finite distance to any centroid (NaN or inf input)");
+        if (out_obj) {
+            double obj = 0.0;
+            for (double p : hpart)
+                obj += p;
+            out_obj[it] = obj;
+        }
+        kmeans_pick_splits(hcnt, pairs);
+        if (!pairs.empty()) {
+            // pageable source: the copy has completed when the next iteration's synchronisation returns, before `pairs`
+            // is rewritten
+            HIP_TRY(hipMemcpyAsync(h->km_pairs.p, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                   h->stream));
+            HIP_TRY(launch_kmeans_split(h->stream, d_c, h->km_pairs.as<uint32_t>(), pairs.size() / 2, (int)d));
+        }
+    }
+    if (d_out_assign)
+        HIP_TRY(hipMemcpyAsync(d_out_assign, assign, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+} catch (const std::bad_alloc &) {
+    return fail(IVFHNSW_ERR_NOMEM, "kmeans: host allocation failed");
+}
+
+} // namespace
+} // extern "C++"
+
+int ivfhnsw_gpu_kmeans_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const float *d_x, size_t niter, float *d_centroids,
+                           uint32_t *d_out_assign, double *out_obj)
+{
+    int rc = kmeans_check(h, n, d, nc, d_x, d_centroids);
+    if (rc)
+        return rc;
+    if (((uintptr_t)d_x | (uintptr_t)d_centroids) & 15)
+        return fail(IVFHNSW_ERR_INVALID, "kmeans_dev: x and centroids must be 16-byte aligned");
+    if (niter == 0)
+        return IVFHNSW_OK;
+    return kmeans_run(h, n, d, nc, d_x, niter, d_centroids, d_out_assign, out_obj);
+}
+
+int ivfhnsw_gpu_kmeans(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const float *x, size_t niter, float *centroids,
+                       uint32_t *out_assign, double *out_obj)
+{
+    int rc = kmeans_check(h, n, d, nc, x, centroids);
+    if (rc)
+        return rc;
+    if (niter == 0)
+        return IVFHNSW_OK;
+    if ((rc = h->km_x.ensure(n * d * sizeof(float))) || (rc = h->km_c.ensure(nc * d * sizeof(float))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->km_x.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->km_c.p, centroids, nc * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if ((rc = kmeans_run(h, n, d, nc, h->km_x.as<float>(), niter, h->km_c.as<float>(), nullptr, out_obj)))
+        return rc;
+    HIP_TRY(hipMemcpy(centroids, h->km_c.p, nc * d * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_assign)
+        HIP_TRY(hipMemcpy(out_assign, h->km_assign.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return IVFHNSW_OK;
 }
 
@@ -2399,7 +2554,9 @@ int ivfhnsw_gpu_memory_bytes(ivfhnsw_gpu *h, uint64_t *bytes)
                            &h->ids, &h->g_alpha, &h->g_nn, &h->g_sizes, &h->g_inter, &h->q_counts, &h->q_links,
                            &h->q_vectors, &h->q_qrows, &h->q_nbrows, &h->q_nbnorms, &h->q_fat, &h->q_links_c, &h->e_pqc, &h->e_ntab, &h->e_a, &h->e_at, &h->e_x, &h->e_idx, &h->e_dist, &h->e_res, &h->e_tmp, &h->e_codes, &h->e_ncodes, &h->cg_q, &h->cg_cidx, &h->cg_ids, &h->cg_dists, &h->gc_nn, &h->cg_cvn, &h->cg_tab, &h->cg_tab2, &h->cg_off, &h->cg_alpha2, &h->cg_sub, &h->w_xq, &h->w_luts, &h->w_segs, &h->w_lpos, &h->w_hdr, &h->w_keys,
                            &h->w_cid, &h->w_cd, &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd,
-                           &h->s_dist, &h->s_lab, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab};
+                           &h->s_dist, &h->s_lab, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab,
+                           &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2,
+                           &h->km_hist, &h->km_part, &h->km_status, &h->km_pairs};
     uint64_t s = 0;
     for (auto *b : all)
         s += b->bytes;

@@ -217,6 +217,18 @@ hipError_t launch_norm_codes(hipStream_t s, const float *rec, const float *ntab,
 constexpr int kXtyChunk = 2048;
 hipError_t launch_lloyd_update(hipStream_t s, const float *x, const uint8_t *assign, float *cb, size_t n, int d, int M);
 hipError_t launch_xty(hipStream_t s, const float *X, const float *Y, float *partials, float *C, size_t n, int d);
+// Lloyd k-means of the coarse centroids (kernels_kmeans.hip): counts + objective partials per tile of kKmeansTile points,
+// an exclusive scan, a stable sort of the point ids by cluster (LSD radix, 8 bits per pass; *sorted = ids_a or ids_b),
+// the means in member order and the in-order split of empty clusters.  hist: [256][ceil(n / kKmeansTile)].
+constexpr int kKmeansTile = 4096;
+hipError_t launch_kmeans_count(hipStream_t s, const uint32_t *assign, const float *dist, size_t n, uint32_t nc,
+                               uint32_t *cnt, double *part, uint32_t *status);
+hipError_t launch_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, size_t len);
+hipError_t launch_sort_by_key(hipStream_t s, const uint32_t *keys, size_t n, int key_bits, uint32_t *ids_a, uint32_t *ids_b,
+                              uint32_t *hist, uint32_t **sorted);
+hipError_t launch_kmeans_means(hipStream_t s, const float *x, size_t n, const uint32_t *members, const uint32_t *start,
+                               const uint32_t *cnt, float *c, size_t nc, int d);
+hipError_t launch_kmeans_split(hipStream_t s, float *c, const uint32_t *pairs, size_t npairs, int d);
 // exact k-nearest-neighbour tables on the matrix cores (kernels_knn.hip); part = [nsplit][nq][k] u64 workspace
 int knn_splits_for(size_t nq, size_t nx);
 hipError_t launch_knn_norms(hipStream_t s, const float *x, float *out, size_t n, int d);
