@@ -133,6 +133,8 @@ protected:
     ivfhnsw_gpu *gpu_;
     bool device_dirty_;
     void ensure_device();
+    /// the device copy is what ensure_device would upload (add_batch then appends to it in place)
+    bool device_current();
     void device_upload_common();
     /// construction side: graph (once per quantizer state) and code books (every call) for ivfhnsw_gpu_encode
     void ensure_encoder();

@@ -92,6 +92,42 @@ int ivfhnsw_gpu_upload_ivf(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *desc);
  * exactly the bytes and ids its lists have in the unsharded corpus. */
 int ivfhnsw_gpu_upload_ivf_synthetic(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *desc, uint64_t seed);
 
+/* ---- appends to the device lists -------------------------------------------------------------
+ *
+ * IndexIVF_HNSW::add_batch appends code i to the END of list idx[i], in input order (IndexIVF_HNSW.cpp:122-131): the
+ * lists only grow at their ends.  ivfhnsw_gpu_append_ivf does that to the lists the handle holds, in HBM, without a
+ * second upload: code i (ids[i], codes[i*code_size ..], norm_codes[i]) goes to the end of list list_idx[i]; codes of
+ * one list keep ascending i.  After any sequence of appends the handle's arrays (offsets, local offsets, codes, norm
+ * codes, ids, n_local) are byte for byte what upload_ivf of the concatenated lists holds, so searches (labels,
+ * distance bits, the max_codes cut, last_scan_counts) are those of that upload.
+ *   Sharded handles (shard_world > 1): pass every shard the whole batch.  Each updates the global offsets and keeps
+ *   the codes of the lists it owns (the ownership recorded at upload).
+ *   Errors leave the tables exactly as they were: list_idx[i] >= nc or n_local + n >= 2^32 - 1 -> IVFHNSW_ERR_INVALID;
+ *   allocation failure -> IVFHNSW_ERR_NOMEM; before upload_ivf, on a view, or on a handle with grouping tables (a
+ *   second add_group is no append, IndexIVF_HNSW_Grouping.cpp:43-157) -> IVFHNSW_ERR_STATE.  n = 0 does nothing.
+ *   The new arrays are built beside the old ones and swapped in: the peak is twice the list bytes.  The graph and
+ *   the latency walk's records are not touched.  Like an upload, an append must not run while views of the handle
+ *   exist (ivfhnsw_gpu_create_view): they keep the old arrays, which the append frees.  A view created afterwards
+ *   sees the new lists.
+ * ivfhnsw_gpu_append_ivf_dev: the same on device pointers (list_idx, ids and codes 4-byte aligned) on the handle's
+ *   stream; the ids are checked on the device before anything changes.  Returns when the append is done.
+ * ivfhnsw_gpu_add: ivfhnsw_gpu_encode followed by the append, the codes never leaving HBM.  Needs upload_codebooks,
+ *   upload_quantizer and upload_ivf; code books whose d or code_size differ from the index, or OPQ in one and not
+ *   the other -> IVFHNSW_ERR_INVALID, checked before anything is encoded.  ids [n] are the labels of the new codes;
+ *   out_idx [n], out_codes [n*code_size], out_norm_codes [n] (each nullable) receive what encode would return.
+ * ivfhnsw_gpu_add_dev: the same on device pointers.
+ * ivfhnsw_gpu_download_ivf: the handle's global offsets [nc+1] and its local ids [n_local], codes
+ *   [n_local*code_size], norm codes [n_local] (each nullable), in the layout upload_ivf takes. */
+int ivfhnsw_gpu_append_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *ids, const uint8_t *codes,
+                           const uint8_t *norm_codes);
+int ivfhnsw_gpu_append_ivf_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_ids,
+                               const uint8_t *d_codes, const uint8_t *d_norm_codes);
+int ivfhnsw_gpu_add(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *precomputed_idx, size_t efSearch,
+                    const uint32_t *ids, uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes);
+int ivfhnsw_gpu_add_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32_t *d_precomputed_idx, size_t efSearch,
+                        const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes);
+int ivfhnsw_gpu_download_ivf(ivfhnsw_gpu *h, uint64_t *offsets, uint32_t *ids, uint8_t *codes, uint8_t *norm_codes);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */

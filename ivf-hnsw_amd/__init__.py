@@ -30,7 +30,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_prepare_latency", "ivfhnsw_gpu_set_batch_split", "ivfhnsw_gpu_last_batch_parts", "ivfhnsw_gpu_search_keys", "ivfhnsw_gpu_resolve_keys", "ivfhnsw_gpu_last_stream",
     "ivfhnsw_gpu_device_count", "ivfhnsw_gpu_knn", "ivfhnsw_gpu_knn_dev", "ivfhnsw_gpu_build_graph", "ivfhnsw_gpu_set_option", "ivfhnsw_gpu_search_sharded",
     "ivfhnsw_gpu_upload_base", "ivfhnsw_gpu_upload_base_dev", "ivfhnsw_gpu_rerank_dev", "ivfhnsw_gpu_rerank",
-    "ivfhnsw_gpu_kmeans", "ivfhnsw_gpu_kmeans_dev",
+    "ivfhnsw_gpu_kmeans", "ivfhnsw_gpu_kmeans_dev", "ivfhnsw_gpu_append_ivf", "ivfhnsw_gpu_append_ivf_dev",
+    "ivfhnsw_gpu_add", "ivfhnsw_gpu_add_dev", "ivfhnsw_gpu_download_ivf",
 )
 
 
@@ -112,6 +113,11 @@ def lib():
         L.ivfhnsw_gpu_kmeans.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_kmeans_dev.argtypes = L.ivfhnsw_gpu_kmeans.argtypes
+        L.ivfhnsw_gpu_append_ivf.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
+        L.ivfhnsw_gpu_append_ivf_dev.argtypes = L.ivfhnsw_gpu_append_ivf.argtypes
+        L.ivfhnsw_gpu_add.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
+        L.ivfhnsw_gpu_add_dev.argtypes = L.ivfhnsw_gpu_add.argtypes
+        L.ivfhnsw_gpu_download_ivf.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.ivfhnsw_gpu_knn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_build_graph.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
@@ -195,6 +201,7 @@ class GpuIndex:
         v.d, v.nc, v.code_size = self.d, self.nc, self.code_size
         v._device = self._device
         v._parent = self
+        v._shard = getattr(self, "_shard", (0, 1, None))
         return v
 
     def close(self):
@@ -231,6 +238,7 @@ class GpuIndex:
                        _ptr(keep["norm_table"]), _ptr(keep["opq_A"]), shard_rank, shard_world,
                        _ptr(keep["list_owner"]))
         self.d, self.nc, self.code_size = d, nc, code_size
+        self._shard = (shard_rank, shard_world, keep["list_owner"])
         return desc, keep
 
     def upload_ivf(self, d, code_size, offsets, ids, codes, norm_codes, centroid_norms, pq_centroids, norm_table,
@@ -244,6 +252,60 @@ class GpuIndex:
         desc, keep = self._desc(d, code_size, offsets, centroid_norms, pq_centroids, norm_table, opq_A, None, None,
                                 None, shard_rank, shard_world, list_owner)
         _check(lib().ivfhnsw_gpu_upload_ivf_synthetic(self._h, C.byref(desc), seed))
+
+    # ---- appends (ivfhnsw_gpu_append_ivf / ivfhnsw_gpu_add) -------------------------------------
+    def append_ivf(self, list_idx, ids, codes, norm_codes):
+        """Append code i to the end of list list_idx[i] (IndexIVF_HNSW.cpp:122-131) in HBM; host arrays."""
+        li = _np(list_idx, np.uint32).ravel()
+        n = li.size
+        i = _np(ids, np.uint32).ravel()
+        c = _np(codes, np.uint8).reshape(n, -1) if n else np.zeros((0, self.code_size), np.uint8)
+        nc = _np(norm_codes, np.uint8).ravel()
+        assert i.size == n and nc.size == n and (not self.code_size or c.shape[1] == self.code_size)
+        _check(lib().ivfhnsw_gpu_append_ivf(self._h, n, _ptr(li), _ptr(i), _ptr(c), _ptr(nc)))
+
+    def append_ivf_dev(self, n, d_list_idx, d_ids, d_codes, d_norm_codes):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_append_ivf_dev(self._h, n, _devptr(d_list_idx), _devptr(d_ids), _devptr(d_codes),
+                                                _devptr(d_norm_codes)))
+
+    def add(self, x, ids, precomputed_idx=None, efSearch=0):
+        """encode + append_ivf without the codes leaving HBM: returns (idx, codes, norm_codes) as encode does."""
+        x = _np(x, np.float32)
+        x = x.reshape(-1, x.shape[-1])
+        n = x.shape[0]
+        i = _np(ids, np.uint32).ravel()
+        assert i.size == n
+        pidx = None if precomputed_idx is None else _np(precomputed_idx, np.uint32)
+        idx = np.empty(n, np.uint32)
+        codes = np.empty((n, self.code_size), np.uint8)
+        ncodes = np.empty(n, np.uint8)
+        _check(lib().ivfhnsw_gpu_add(self._h, n, _ptr(x), _ptr(pidx), efSearch, _ptr(i), _ptr(idx), _ptr(codes),
+                                     _ptr(ncodes)))
+        return idx, codes, ncodes
+
+    def add_dev(self, n, d_x, d_ids, d_precomputed_idx=None, efSearch=0, d_out_idx=None, d_out_codes=None,
+                d_out_norm_codes=None):
+        """add on device buffers (outputs optional)."""
+        _check(lib().ivfhnsw_gpu_add_dev(self._h, n, _devptr(d_x), _devptr(d_precomputed_idx), efSearch, _devptr(d_ids),
+                                         _devptr(d_out_idx), _devptr(d_out_codes), _devptr(d_out_norm_codes)))
+
+    def download_ivf(self):
+        """(offsets u64 [nc+1], ids u32 [n_local], codes u8 [n_local, code_size], norm_codes u8 [n_local]) as the
+        handle holds them: this shard's lists only, in the layout upload_ivf takes."""
+        off = np.empty(self.nc + 1, np.uint64)
+        _check(lib().ivfhnsw_gpu_download_ivf(self._h, _ptr(off), None, None, None))
+        rank, world, owner = getattr(self, "_shard", (0, 1, None))
+        lens = np.diff(off)
+        if world > 1:
+            own = (owner if owner is not None else np.arange(self.nc) % world) == rank
+            lens = lens[own]
+        n = int(lens.sum())
+        ids = np.empty(n, np.uint32)
+        codes = np.empty((n, self.code_size), np.uint8)
+        ncodes = np.empty(n, np.uint8)
+        _check(lib().ivfhnsw_gpu_download_ivf(self._h, None, _ptr(ids), _ptr(codes), _ptr(ncodes)))
+        return off, ids, codes, ncodes
 
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)

@@ -133,6 +133,8 @@ struct ivfhnsw_gpu {
     // the raw uint8 base vectors of searchDisk's re-rank (ivfhnsw_gpu_upload_base), each row permuted for the quad that
     // scores it (kernels_rerank.hip); a view reads its parent's
     DevBuf base_rows, base_stage;
+    DevBuf ap_idx, ap_ids, ap_codes, ap_ncodes, ap_cnt, ap_own, ap_part, ap_status, ap_perm, ap_perm2, ap_hist,
+        ap_tiles; // appends (ivfhnsw_gpu_append_ivf, ivfhnsw_gpu_add)
     uint64_t base_n = 0;
     size_t base_d = 0;
     ivfhnsw_gpu *parent = nullptr;
@@ -453,7 +455,8 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
                      &h->w_xq, &h->w_luts, &h->w_segs, &h->w_lpos, &h->w_hdr, &h->w_keys, &h->w_cid, &h->w_cd,
                      &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab,
                      &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2, &h->km_hist,
-                     &h->km_part, &h->km_status, &h->km_pairs};
+                     &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes, &h->ap_ncodes, &h->ap_cnt,
+                     &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2, &h->ap_hist, &h->ap_tiles};
     for (auto *b : all)
         b->release();
     h->p_in.release();
@@ -1498,6 +1501,262 @@ int ivfhnsw_gpu_kmeans(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const floa
     HIP_TRY(hipMemcpy(centroids, h->km_c.p, nc * d * sizeof(float), hipMemcpyDeviceToHost));
     if (out_assign)
         HIP_TRY(hipMemcpy(out_assign, h->km_assign.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// appends to the lists the handle holds: the new CSR is built beside the old one and swapped in
+static int append_state(ivfhnsw_gpu *h, const char *who)
+{
+    if (h && h->is_view)
+        return fail(IVFHNSW_ERR_STATE, "%s: appends go to the handle that holds the tables, not to a view of it", who);
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_ivf", who);
+    if (h->has_group)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle holds grouping tables, whose lists have no append", who);
+    return IVFHNSW_OK;
+}
+
+static int append_size(ivfhnsw_gpu *h, size_t n, const char *who)
+{
+    if (n >= 0xffffffffull || h->n_local + n >= 0xffffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "%s: %llu + %zu codes reach 2^32 - 1 on one shard", who,
+                    (unsigned long long)h->n_local, n);
+    return IVFHNSW_OK;
+}
+
+// the batch's staging in HBM: list ids, ids, codes, norm codes of n rows
+static int append_stage(ivfhnsw_gpu *h, size_t n)
+{
+    int rc;
+    if ((rc = h->ap_idx.ensure(n * sizeof(uint32_t))) || (rc = h->ap_ids.ensure(n * sizeof(uint32_t))) ||
+        (rc = h->ap_codes.ensure(n * h->t.M)) || (rc = h->ap_ncodes.ensure(n)))
+        return rc;
+    return IVFHNSW_OK;
+}
+
+// d_idx [n] (every id < nc is checked here, on the device, before anything changes), d_ids [n], d_codes [n][M] (dword
+// aligned), d_ncodes [n]: device memory, read on the handle's stream.  Returns with the stream drained; on any error
+// the handle's tables are the ones it had.
+static int append_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const uint32_t *d_ids, const uint8_t *d_codes,
+                       const uint8_t *d_ncodes)
+{
+    const size_t nc = h->t.nc, len = nc + 1;
+    int rc;
+    if ((rc = h->ap_cnt.ensure(len * sizeof(uint32_t))) || (rc = h->ap_own.ensure(len * sizeof(uint32_t))) ||
+        (rc = h->ap_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) || (rc = h->ap_status.ensure(sizeof(uint32_t))))
+        return rc;
+    uint32_t *cnt = h->ap_cnt.as<uint32_t>(), *own = h->ap_own.as<uint32_t>(), *status = h->ap_status.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(cnt, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_append_count(h->stream, d_idx, n, (uint32_t)nc, cnt, status));
+    HIP_TRY(launch_append_tables(h->stream, h->t, cnt, own, h->ap_part.as<uint32_t>()));
+    uint32_t st = 0, total = 0;
+    HIP_TRY(hipMemcpyAsync(&st, status, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&total, own + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (st)
+        return fail(IVFHNSW_ERR_INVALID, "append: a list id is >= nc = %zu", nc);
+    const uint64_t n_local2 = total;
+    const size_t nblocks = (n + kKmeansTile - 1) / kKmeansTile;
+    if ((rc = h->ap_perm.ensure(n * sizeof(uint32_t))) || (rc = h->ap_perm2.ensure(n * sizeof(uint32_t))) ||
+        (rc = h->ap_hist.ensure(256 * nblocks * sizeof(uint32_t))) ||
+        (rc = h->ap_tiles.ensure((n_local2 / kAppendTileRows + 2) * sizeof(uint32_t))))
+        return rc;
+    // the new arrays first: the old ones stay the handle's until the new ones are complete
+    DevBuf goff2, loff2, codes2, ncodes2, ids2;
+    DevBuf *fresh[] = {&goff2, &loff2, &codes2, &ncodes2, &ids2};
+    auto drop = [&] {
+        for (auto *b : fresh)
+            b->release();
+    };
+    if ((rc = goff2.ensure(len * sizeof(uint64_t))) || (rc = loff2.ensure(nc * sizeof(uint32_t))) ||
+        (rc = codes2.ensure(n_local2 * h->t.M)) || (rc = ncodes2.ensure(n_local2)) ||
+        (rc = ids2.ensure(n_local2 * sizeof(uint32_t)))) {
+        drop();
+        return rc;
+    }
+    int key_bits = 1;
+    while (key_bits < 32 && (nc - 1) >> key_bits)
+        key_bits++;
+    uint32_t *perm = nullptr;
+    const uint32_t *nstart = cnt, *lstart = own; // scanned in place by launch_append_tables
+    hipError_t e = launch_sort_by_key(h->stream, d_idx, n, key_bits, h->ap_perm.as<uint32_t>(), h->ap_perm2.as<uint32_t>(),
+                                      h->ap_hist.as<uint32_t>(), &perm);
+    if (e == hipSuccess)
+        e = launch_append_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), goff2.as<uint64_t>(),
+                                loff2.as<uint32_t>(), codes2.as<uint8_t>(), ncodes2.as<uint8_t>(), ids2.as<uint32_t>(), n_local2);
+    if (e == hipSuccess)
+        e = launch_append_scatter(h->stream, h->t, perm, d_idx, n, nstart, lstart, d_codes, d_ncodes, d_ids,
+                                  codes2.as<uint8_t>(), ncodes2.as<uint8_t>(), ids2.as<uint32_t>());
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        drop();
+        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append: %s", hipGetErrorString(e));
+    }
+    std::swap(h->goff, goff2);
+    std::swap(h->loff, loff2);
+    std::swap(h->codes, codes2);
+    std::swap(h->ncodes, ncodes2);
+    std::swap(h->ids, ids2);
+    drop(); // the old arrays
+    h->t.goff = h->goff.as<uint64_t>();
+    h->t.loff = h->loff.as<uint32_t>();
+    h->t.codes = h->codes.as<uint8_t>();
+    h->t.norm_codes = h->ncodes.as<uint8_t>();
+    h->t.ids = h->ids.as<uint32_t>();
+    h->n_local = n_local2;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_append_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *ids, const uint8_t *codes,
+                           const uint8_t *norm_codes)
+{
+    int rc = append_state(h, "append_ivf");
+    if (rc || n == 0)
+        return rc;
+    if (!list_idx || !ids || !codes || !norm_codes)
+        return fail(IVFHNSW_ERR_INVALID, "append_ivf: null buffer");
+    if ((rc = append_size(h, n, "append_ivf")))
+        return rc;
+    for (size_t i = 0; i < n; i++)
+        if (list_idx[i] >= h->t.nc)
+            return fail(IVFHNSW_ERR_INVALID, "append_ivf: list_idx[%zu] = %u, nc = %u", i, list_idx[i], h->t.nc);
+    if ((rc = append_stage(h, n)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->ap_idx.p, list_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_codes.p, codes, n * h->t.M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ncodes.p, norm_codes, n, hipMemcpyHostToDevice, h->stream));
+    return append_core(h, n, h->ap_idx.as<uint32_t>(), h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(),
+                       h->ap_ncodes.as<uint8_t>());
+}
+
+int ivfhnsw_gpu_append_ivf_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_ids,
+                               const uint8_t *d_codes, const uint8_t *d_norm_codes)
+{
+    int rc = append_state(h, "append_ivf_dev");
+    if (rc || n == 0)
+        return rc;
+    if (!d_list_idx || !d_ids || !d_codes || !d_norm_codes)
+        return fail(IVFHNSW_ERR_INVALID, "append_ivf_dev: null buffer");
+    if (((uintptr_t)d_list_idx | (uintptr_t)d_ids | (uintptr_t)d_codes) & 3)
+        return fail(IVFHNSW_ERR_INVALID, "append_ivf_dev: list_idx, ids and codes must be 4-byte aligned");
+    if ((rc = append_size(h, n, "append_ivf_dev")))
+        return rc;
+    return append_core(h, n, d_list_idx, d_ids, d_codes, d_norm_codes);
+}
+
+// encode (as ivfhnsw_gpu_encode, chunk by chunk) into the staging, then one append
+static int add_impl(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *pidx, size_t efSearch, const uint32_t *ids,
+                    uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes, bool dev, const char *who)
+{
+    int rc = append_state(h, who);
+    if (rc)
+        return rc;
+    if (!h->has_codebooks || !h->has_graph)
+        return fail(IVFHNSW_ERR_STATE, "%s needs upload_codebooks and upload_quantizer", who);
+    if (h->gr.n != h->t.nc || h->gr.d != h->t.d)
+        return fail(IVFHNSW_ERR_STATE, "%s: the quantizer holds %u x %d, the index %u lists of d = %d", who, h->gr.n,
+                    h->gr.d, h->t.nc, h->t.d);
+    if (h->e_d != (size_t)h->t.d || h->e_M != (size_t)h->t.M || h->e_opq != (h->t.opq_At != nullptr))
+        return fail(IVFHNSW_ERR_INVALID, "%s: code books (d %zu, code_size %zu, %s OPQ) do not match the index (d %d, "
+                    "code_size %d, %s OPQ)", who, h->e_d, h->e_M, h->e_opq ? "with" : "no", h->t.d, h->t.M,
+                    h->t.opq_At ? "with" : "no");
+    if (n == 0)
+        return IVFHNSW_OK;
+    if (!x || !ids)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null buffer", who);
+    if (!pidx && efSearch == 0)
+        return fail(IVFHNSW_ERR_INVALID, "%s: efSearch 0 (assign runs searchKnn(x, 1))", who);
+    if ((rc = append_size(h, n, who)))
+        return rc;
+    if ((rc = append_stage(h, n)))
+        return rc;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    uint32_t *sidx = h->ap_idx.as<uint32_t>();
+    if (pidx) {
+        if (!dev) {
+            for (size_t i = 0; i < n; i++)
+                if (pidx[i] >= h->t.nc)
+                    return fail(IVFHNSW_ERR_INVALID, "%s: precomputed_idx[%zu] = %u out of range", who, i, pidx[i]);
+        }
+        HIP_TRY(hipMemcpyAsync(sidx, pidx, n * sizeof(uint32_t), in, h->stream));
+        if (dev) { // before the encoder reads a centroid row by it
+            if ((rc = h->ap_status.ensure(sizeof(uint32_t))))
+                return rc;
+            uint32_t st = 0;
+            HIP_TRY(hipMemsetAsync(h->ap_status.p, 0, sizeof(uint32_t), h->stream));
+            HIP_TRY(launch_append_count(h->stream, sidx, n, h->t.nc, nullptr, h->ap_status.as<uint32_t>()));
+            HIP_TRY(hipMemcpyAsync(&st, h->ap_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (st)
+                return fail(IVFHNSW_ERR_INVALID, "%s: a precomputed_idx is >= nc = %u", who, h->t.nc);
+        }
+    }
+    const size_t d = h->e_d, M = h->e_M;
+    const size_t kChunk = (size_t)1 << 18;
+    for (size_t i0 = 0; i0 < n; i0 += kChunk) {
+        const size_t m = std::min(kChunk, n - i0);
+        if ((rc = h->e_x.ensure(m * d * sizeof(float))) || (rc = h->e_res.ensure(m * d * sizeof(float))) ||
+            (rc = h->e_tmp.ensure(m * d * sizeof(float))) || (rc = h->e_dist.ensure(m * sizeof(float))) ||
+            (rc = h->e_codes.ensure(m * M)) || (rc = h->e_ncodes.ensure(m)))
+            return rc;
+        float *dx = h->e_x.as<float>();
+        HIP_TRY(hipMemcpyAsync(dx, x + i0 * d, m * d * sizeof(float), in, h->stream));
+        if (!pidx && (rc = ivfhnsw_gpu_coarse_dev(h, m, dx, 1, efSearch, sidx + i0, h->e_dist.as<float>())))
+            return rc;
+        if ((rc = encode_rows(h, m, dx, h->gr.vectors, sidx + i0)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(h->ap_codes.as<uint8_t>() + i0 * M, h->e_codes.p, m * M, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->ap_ncodes.as<uint8_t>() + i0, h->e_ncodes.p, m, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if ((rc = check_status(h)))
+            return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), in, h->stream));
+    if (out_codes)
+        HIP_TRY(hipMemcpyAsync(out_codes, h->ap_codes.p, n * M, out, h->stream));
+    if (out_norm_codes)
+        HIP_TRY(hipMemcpyAsync(out_norm_codes, h->ap_ncodes.p, n, out, h->stream));
+    if (out_idx)
+        HIP_TRY(hipMemcpyAsync(out_idx, sidx, n * sizeof(uint32_t), out, h->stream));
+    return append_core(h, n, sidx, h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>());
+}
+
+int ivfhnsw_gpu_add(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *precomputed_idx, size_t efSearch,
+                    const uint32_t *ids, uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes)
+{
+    return add_impl(h, n, x, precomputed_idx, efSearch, ids, out_idx, out_codes, out_norm_codes, false, "add");
+}
+
+int ivfhnsw_gpu_add_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32_t *d_precomputed_idx, size_t efSearch,
+                        const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes)
+{
+    return add_impl(h, n, d_x, d_precomputed_idx, efSearch, d_ids, d_out_idx, d_out_codes, d_out_norm_codes, true, "add_dev");
+}
+
+int ivfhnsw_gpu_download_ivf(ivfhnsw_gpu *h, uint64_t *offsets, uint32_t *ids, uint8_t *codes, uint8_t *norm_codes)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "download_ivf before upload_ivf");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (offsets)
+        HIP_TRY(hipMemcpy(offsets, h->t.goff, ((size_t)h->t.nc + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (ids && h->n_local)
+        HIP_TRY(hipMemcpy(ids, h->t.ids, h->n_local * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (codes && h->n_local)
+        HIP_TRY(hipMemcpy(codes, h->t.codes, h->n_local * h->t.M, hipMemcpyDeviceToHost));
+    if (norm_codes && h->n_local)
+        HIP_TRY(hipMemcpy(norm_codes, h->t.norm_codes, h->n_local, hipMemcpyDeviceToHost));
     return IVFHNSW_OK;
 }
 
@@ -2556,7 +2815,9 @@ int ivfhnsw_gpu_memory_bytes(ivfhnsw_gpu *h, uint64_t *bytes)
                            &h->w_cid, &h->w_cd, &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd,
                            &h->s_dist, &h->s_lab, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab,
                            &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2,
-                           &h->km_hist, &h->km_part, &h->km_status, &h->km_pairs};
+                           &h->km_hist, &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes,
+                           &h->ap_ncodes, &h->ap_cnt, &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2,
+                           &h->ap_hist, &h->ap_tiles};
     uint64_t s = 0;
     for (auto *b : all)
         s += b->bytes;

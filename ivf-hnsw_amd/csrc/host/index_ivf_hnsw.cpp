@@ -4,6 +4,7 @@
 // (IndexIVF_HNSW.cpp:637-663,758-779); the construction side (add_batch, train_pq) is a plain host
 // implementation kept only so that the drivers' cold-start path works at small scale.
 #include <ivf-hnsw/IndexIVF_HNSW.h>
+#include <ivf-hnsw/IndexIVF_HNSW_Grouping.h>
 
 #include <ivfhnsw_hip.h>
 
@@ -159,6 +160,12 @@ void IndexIVF_HNSW::ensure_latency_walk()
 
 void IndexIVF_HNSW::ensure_device()
 {
+    if (!device_current())
+        sync_to_device();
+}
+
+bool IndexIVF_HNSW::device_current()
+{
     // The list total is the fingerprint that catches a driver appending to the public lists behind the class's back;
     // summing a million list sizes per call would cost more than the search itself (one query per call at 993 127
     // centroids), so beyond 2^16 lists the class relies on its own dirty flags (add_batch, read, invalidate_device()).
@@ -168,9 +175,8 @@ void IndexIVF_HNSW::ensure_device()
         for (size_t c = 0; c < nc; c++)
             total += ids[c].size();
     }
-    if (!gpu_ || device_dirty_ || up_pq_ != pq || up_norm_pq_ != norm_pq || up_opq_ != opq_matrix ||
-        up_quantizer_ != quantizer || up_total_ != total || up_do_opq_ != do_opq)
-        sync_to_device();
+    return gpu_ && !device_dirty_ && up_pq_ == pq && up_norm_pq_ == norm_pq && up_opq_ == opq_matrix &&
+           up_quantizer_ == quantizer && up_total_ == total && up_do_opq_ == do_opq;
 }
 
 void IndexIVF_HNSW::device_upload_common()
@@ -731,15 +737,28 @@ void IndexIVF_HNSW::add_batch(size_t n, const float *x, const idx_t *xids, const
     ensure_encoder();
     std::vector<idx_t> idx(n);
     std::vector<uint8_t> xcodes(n * code_size), ncodes(n);
-    if (ivfhnsw_gpu_encode(gpu_, n, x, precomputed_idx, quantizer->efSearch, idx.data(), xcodes.data(), ncodes.data()))
+    // A device copy that is current (one handle, no grouping tables, nothing ensure_device would re-upload) takes the
+    // batch in place: ivfhnsw_gpu_add appends the codes to the lists in HBM, and neither the lists nor
+    // the graph go up again.  Every other case -- the first build before any search included -- marks the copy stale.
+    const bool in_place = nshards() == 1 && !dynamic_cast<const IndexIVF_HNSW_Grouping *>(this) && device_current();
+    if (in_place) {
+        if (ivfhnsw_gpu_add(gpu_, n, x, precomputed_idx, quantizer->efSearch, xids, idx.data(), xcodes.data(),
+                            ncodes.data()))
+            gpu_fail("ivfhnsw_gpu_add");
+    } else if (ivfhnsw_gpu_encode(gpu_, n, x, precomputed_idx, quantizer->efSearch, idx.data(), xcodes.data(),
+                                  ncodes.data())) {
         gpu_fail("ivfhnsw_gpu_encode");
+    }
     for (size_t i = 0; i < n; i++) {
         const idx_t key = idx[i];
         ids[key].push_back(xids[i]);
         codes[key].insert(codes[key].end(), xcodes.begin() + i * code_size, xcodes.begin() + (i + 1) * code_size);
         norm_codes[key].push_back(ncodes[i]);
     }
-    device_dirty_ = true;
+    if (in_place)
+        up_total_ += n;
+    else
+        device_dirty_ = true;
 }
 
 void IndexIVF_HNSW::add_batch2(size_t, const float *, const idx_t *, const idx_t *, uint64_t *, char *)

@@ -260,6 +260,21 @@ hipError_t launch_rerank_permute(hipStream_t s, const uint8_t *src, size_t src_s
 size_t rerank_lds_bytes(int kc, int d);
 hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
                          const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels);
+// appends to the inverted lists (kernels_append.hip).  count: cnt[idx[i]] += 1 (cnt may be null: check
+// only), an id >= nc raises *status.  tables: own[c] = old length + cnt[c] of the owned lists, then cnt and own ([nc + 1]
+// each, slot nc zero) become their exclusive scans nstart / lstart in place; part: append_scan_parts(nc + 1) words.
+// merge: goff2 / loff2 and the old rows into the new arrays (tile_first: n_local2 / kAppendTileRows + 2 words).
+// scatter: the batch's rows (perm = the ids sorted by list, stably) to the ends of their lists; runs after merge.
+constexpr int kAppendTileRows = 2048;
+size_t append_scan_parts(size_t len);
+hipError_t launch_append_count(hipStream_t s, const uint32_t *idx, size_t n, uint32_t nc, uint32_t *cnt, uint32_t *status);
+hipError_t launch_append_tables(hipStream_t s, const IvfTables &t, uint32_t *cnt, uint32_t *own, uint32_t *part);
+hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
+                               uint32_t *ids2, uint64_t n_local2);
+hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
+                                 const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
+                                 const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2);
 // sum of PlanHdr.total / nseg over the batch into out[0], out[1]
 hipError_t launch_plan_totals(hipStream_t s, const PlanHdr *hdr, int nq, unsigned long long *out);
 

@@ -1,0 +1,325 @@
+// Appending codes to the inverted lists a handle holds (ivfhnsw_gpu_append_ivf).  The reference's
+// add_batch appends code i to the end of list idx[i], in input order (IndexIVF_HNSW.cpp:122-131); the lists only grow
+// at their ends, so the new CSR is the old one with every list stretched.  One out-of-place merge builds it:
+//   count    cnt[c] = new codes of list c (global atomics); an id >= nc raises *status and is not counted
+//   lens     own[c] = old length + cnt[c] for the lists this shard owns (loff[c] != kNotOwned), 0 otherwise
+//   scan     nstart = exclusive scan of cnt, lstart = exclusive scan of own (both [nc + 1]; lstart[nc] = the new n_local)
+//   offsets  goff'[c] = goff[c] + nstart[c]; loff'[c] = lstart[c] for owned lists, kNotOwned for the others
+//   merge    old row r of list c moves to r + (lstart[c] - loff[c]): a destination-tiled copy.  Each workgroup reads the
+//            first list of its tile (tile_first, one binary search per tile) and finds every row's list within the
+//            tile's range; the rows are then copied as 16-byte groups (codes, ids) and 4-byte groups (norm codes).
+//            The tile's new rows get whatever the group held; the scatter below overwrites them
+//   scatter  new code p of the stably sorted batch (launch_sort_by_key, kernels_kmeans.hip) goes to
+//            lstart[c] + old_len[c] + (p - nstart[c])
+// code_size is any multiple of 4, so a row is a whole number q of dwords but not always of 16-byte groups: every
+// address here is dword aligned, and the merge's destination groups are 16-byte aligned (a tile is 2048 rows).
+#include "ivfhnsw_kernels.h"
+#include "device_common.h"
+
+namespace ivfhnsw_gpu_impl {
+
+namespace {
+
+constexpr uint32_t kSkip = 0xffffffffu; // a tile row with no old source row (a new code, or past the end)
+constexpr int kScanChunk = 4096;        // elements per workgroup of the three-phase scan
+
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes, dword aligned
+
+__global__ __launch_bounds__(256) void append_count_kernel(const uint32_t *__restrict__ idx, size_t n, uint32_t nc,
+                                                           uint32_t *__restrict__ cnt, uint32_t *__restrict__ status)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t c = idx[i];
+    if (c >= nc)
+        *status = 1u;
+    else if (cnt)
+        atomicAdd(cnt + c, 1u);
+}
+
+// own[c] for c < nc (own[nc] = 0, the scan's total slot)
+__global__ __launch_bounds__(256) void append_lens_kernel(const uint64_t *__restrict__ goff, const uint32_t *__restrict__ loff,
+                                                          const uint32_t *__restrict__ cnt, uint32_t *__restrict__ own,
+                                                          uint32_t nc)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > nc)
+        return;
+    own[c] = (c < nc && loff[c] != kNotOwned) ? (uint32_t)(goff[c + 1] - goff[c]) + cnt[c] : 0u;
+}
+
+// exclusive scan of [len] in chunks of kScanChunk: part[b] = sum of chunk b, then (part scanned) each chunk in place.
+// blockIdx.y picks the array (a or b), so both scans share the launches.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w, uint32_t &total)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(inc, o);
+        if (lane >= o)
+            inc += y;
+    }
+    if (lane == 63)
+        s_w[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < wave; w++)
+        base += s_w[w];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(256) void scan_reduce_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
+                                                          size_t len, uint32_t *__restrict__ part, uint32_t nblk)
+{
+    __shared__ uint32_t s_w[4];
+    const uint32_t *x = blockIdx.y ? b : a;
+    const size_t i0 = (size_t)blockIdx.x * kScanChunk;
+    uint32_t acc = 0;
+    for (int r = 0; r < kScanChunk / 256; r++) {
+        const size_t i = i0 + (size_t)r * 256 + threadIdx.x;
+        if (i < len)
+            acc += x[i];
+    }
+    uint32_t total;
+    (void)block_excl_scan(acc, s_w, total);
+    if (threadIdx.x == 0)
+        part[(size_t)blockIdx.y * nblk + blockIdx.x] = total;
+}
+
+// each thread owns 16 consecutive elements of the chunk
+__global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t *__restrict__ a, uint32_t *__restrict__ b, size_t len,
+                                                         const uint32_t *__restrict__ part, uint32_t nblk)
+{
+    __shared__ uint32_t s_w[4];
+    uint32_t *x = blockIdx.y ? b : a;
+    const size_t i0 = (size_t)blockIdx.x * kScanChunk + (size_t)threadIdx.x * 16;
+    uint32_t v[16], s = 0;
+#pragma unroll
+    for (int u = 0; u < 16; u++) {
+        v[u] = i0 + u < len ? x[i0 + u] : 0u;
+        s += v[u];
+    }
+    uint32_t total;
+    uint32_t run = part[(size_t)blockIdx.y * nblk + blockIdx.x] + block_excl_scan(s, s_w, total);
+#pragma unroll
+    for (int u = 0; u < 16; u++) {
+        if (i0 + u < len)
+            x[i0 + u] = run;
+        run += v[u];
+    }
+}
+
+__global__ __launch_bounds__(256) void append_offsets_kernel(const uint64_t *__restrict__ goff, const uint32_t *__restrict__ loff,
+                                                             const uint32_t *__restrict__ nstart, const uint32_t *__restrict__ lstart,
+                                                             uint64_t *__restrict__ goff2, uint32_t *__restrict__ loff2, uint32_t nc)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > nc)
+        return;
+    goff2[c] = goff[c] + nstart[c];
+    if (c < nc)
+        loff2[c] = loff[c] == kNotOwned ? kNotOwned : lstart[c];
+}
+
+// the largest c in [lo, hi] with lstart[c] <= r (lstart[lo] <= r holds)
+__device__ __forceinline__ uint32_t list_of_row(const uint32_t *__restrict__ lstart, uint32_t lo, uint32_t hi, uint32_t r)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (lstart[mid] <= r)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// tile_first[b] = the list holding row b * kAppendTileRows of the new local arrays; tile_first[ntiles] = nc - 1
+__global__ __launch_bounds__(256) void append_tiles_kernel(const uint32_t *__restrict__ lstart, uint32_t nc, uint32_t ntiles,
+                                                           uint32_t *__restrict__ tile_first)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b > ntiles)
+        return;
+    tile_first[b] = b == ntiles ? nc - 1 : list_of_row(lstart, 0, nc - 1, b * (uint32_t)kAppendTileRows);
+}
+
+// dst dwords [0, ndw) of the tile from src dword s_src[row] * q + k; 16-byte groups, a group whose four source dwords
+// are consecutive is one dword-aligned 16-byte load
+__device__ __forceinline__ void copy_tile_dwords(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, const uint32_t *s_src,
+                                                 uint32_t ndw, uint32_t q)
+{
+    for (uint32_t e = threadIdx.x * 4; e < ndw; e += 1024) {
+        uint32_t j = e / q, k = e - j * q;
+        size_t s[4];
+        bool ok[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t sr = e + u < ndw ? s_src[j] : kSkip;
+            ok[u] = sr != kSkip;
+            s[u] = (size_t)(ok[u] ? sr : 0u) * q + k;
+            if (++k == q) {
+                k = 0;
+                j++;
+            }
+        }
+        uint32_t v[4];
+        if (ok[0] && ok[1] && ok[2] && ok[3] && s[1] == s[0] + 1 && s[2] == s[0] + 2 && s[3] == s[0] + 3) {
+            const u32x4_a4 w = *reinterpret_cast<const u32x4_a4 *>(src + s[0]);
+            v[0] = w.x;
+            v[1] = w.y;
+            v[2] = w.z;
+            v[3] = w.w;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                v[u] = ok[u] ? src[s[u]] : 0u;
+        }
+        if (e + 4 <= ndw) {
+            *reinterpret_cast<uint4 *>(dst + e) = make_uint4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (e + u < ndw)
+                    dst[e + u] = v[u];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void append_merge_kernel(const uint64_t *__restrict__ goff, const uint32_t *__restrict__ loff,
+                                                           const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ tile_first,
+                                                           const uint32_t *__restrict__ codes, const uint8_t *__restrict__ ncodes,
+                                                           const uint32_t *__restrict__ ids, uint32_t *__restrict__ codes2,
+                                                           uint8_t *__restrict__ ncodes2, uint32_t *__restrict__ ids2,
+                                                           uint32_t n_local2, uint32_t q)
+{
+    __shared__ uint32_t s_src[kAppendTileRows];
+    const uint32_t r0 = blockIdx.x * (uint32_t)kAppendTileRows;
+    const uint32_t rows = min((uint32_t)kAppendTileRows, n_local2 - r0);
+    const uint32_t lo = tile_first[blockIdx.x], hi = tile_first[blockIdx.x + 1];
+    for (uint32_t j = threadIdx.x; j < rows; j += 256) {
+        const uint32_t r = r0 + j;
+        const uint32_t c = list_of_row(lstart, lo, hi, r);
+        const uint32_t off = r - lstart[c];
+        s_src[j] = off < (uint32_t)(goff[c + 1] - goff[c]) ? loff[c] + off : kSkip;
+    }
+    __syncthreads();
+    copy_tile_dwords(codes, codes2 + (size_t)r0 * q, s_src, rows * q, q);
+    copy_tile_dwords(ids, ids2 + r0, s_src, rows, 1u);
+    // norm codes: one byte per row, four rows per dword store
+    for (uint32_t e = threadIdx.x * 4; e < rows; e += 1024) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t sr = e + u < rows ? s_src[e + u] : kSkip;
+            w |= (uint32_t)(sr != kSkip ? ncodes[sr] : 0u) << (8 * u);
+        }
+        if (e + 4 <= rows) {
+            *reinterpret_cast<uint32_t *>(ncodes2 + r0 + e) = w;
+        } else {
+            for (uint32_t u = 0; e + u < rows; u++)
+                ncodes2[r0 + e + u] = (uint8_t)(w >> (8 * u));
+        }
+    }
+}
+
+// one thread per dword of the new codes, in sorted order: code p of the sorted batch is input row perm[p]
+__global__ __launch_bounds__(256) void append_scatter_kernel(const uint32_t *__restrict__ perm, const uint32_t *__restrict__ idx,
+                                                             const uint32_t *__restrict__ nstart, const uint32_t *__restrict__ loff,
+                                                             const uint64_t *__restrict__ goff, const uint32_t *__restrict__ lstart,
+                                                             const uint32_t *__restrict__ new_codes, const uint8_t *__restrict__ new_norm,
+                                                             const uint32_t *__restrict__ new_ids, uint32_t *__restrict__ codes2,
+                                                             uint8_t *__restrict__ ncodes2, uint32_t *__restrict__ ids2, size_t n,
+                                                             uint32_t q)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * q)
+        return;
+    const size_t p = e / q;
+    const uint32_t k = (uint32_t)(e - p * q);
+    const uint32_t i = perm[p];
+    const uint32_t c = idx[i];
+    if (loff[c] == kNotOwned)
+        return;
+    const size_t row = (size_t)lstart[c] + (goff[c + 1] - goff[c]) + (p - nstart[c]);
+    codes2[row * q + k] = new_codes[(size_t)i * q + k];
+    if (k == 0) {
+        ids2[row] = new_ids[i];
+        ncodes2[row] = new_norm[i];
+    }
+}
+
+inline unsigned blocks_of(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
+
+} // namespace
+
+size_t append_scan_parts(size_t len) { return 2 * ((len + kScanChunk - 1) / kScanChunk); }
+
+hipError_t launch_append_count(hipStream_t s, const uint32_t *idx, size_t n, uint32_t nc, uint32_t *cnt, uint32_t *status)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(append_count_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, idx, n, nc, cnt, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_append_tables(hipStream_t s, const IvfTables &t, uint32_t *cnt, uint32_t *own, uint32_t *part)
+{
+    const size_t len = (size_t)t.nc + 1;
+    hipLaunchKernelGGL(append_lens_kernel, dim3(blocks_of(len, 256)), dim3(256), 0, s, t.goff, t.loff, cnt, own, t.nc);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    const uint32_t nblk = (uint32_t)blocks_of(len, kScanChunk);
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nblk, 2), dim3(256), 0, s, cnt, own, len, part, nblk);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_scan_u32(s, part, part, nblk); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_scan_u32(s, part + nblk, part + nblk, nblk); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk, 2), dim3(256), 0, s, cnt, own, len, part, nblk);
+    return hipGetLastError();
+}
+
+hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
+                               uint32_t *ids2, uint64_t n_local2)
+{
+    const size_t len = (size_t)t.nc + 1;
+    hipLaunchKernelGGL(append_offsets_kernel, dim3(blocks_of(len, 256)), dim3(256), 0, s, t.goff, t.loff, nstart, lstart,
+                       goff2, loff2, t.nc);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (n_local2 == 0)
+        return hipSuccess;
+    if (n_local2 >= 0xffffffffull || t.M % 4)
+        return hipErrorInvalidValue;
+    const uint32_t ntiles = (uint32_t)blocks_of(n_local2, kAppendTileRows);
+    hipLaunchKernelGGL(append_tiles_kernel, dim3(blocks_of((size_t)ntiles + 1, 256)), dim3(256), 0, s, lstart, t.nc, ntiles,
+                       tile_first);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(append_merge_kernel, dim3(ntiles), dim3(256), 0, s, t.goff, t.loff, lstart, tile_first,
+                       reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(codes2),
+                       ncodes2, ids2, (uint32_t)n_local2, (uint32_t)(t.M / 4));
+    return hipGetLastError();
+}
+
+hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
+                                 const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
+                                 const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2)
+{
+    if (n == 0)
+        return hipSuccess;
+    const uint32_t q = (uint32_t)(t.M / 4);
+    hipLaunchKernelGGL(append_scatter_kernel, dim3(blocks_of(n * q, 256)), dim3(256), 0, s, perm, idx, nstart, t.loff,
+                       t.goff, lstart, reinterpret_cast<const uint32_t *>(codes), norm_codes, ids,
+                       reinterpret_cast<uint32_t *>(codes2), ncodes2, ids2, n, q);
+    return hipGetLastError();
+}
+
+} // namespace ivfhnsw_gpu_impl
