@@ -6,7 +6,7 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch().
+// release_base(), searchDisk_batch(), remove_ids().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
 
@@ -93,6 +93,10 @@ public:
     virtual void search_batch(size_t nq, size_t k, const float *x, float *distances, long *labels);
 
     virtual void add_batch(size_t n, const float *x, const idx_t *xids, const idx_t *precomputed_idx = nullptr);
+    /// Extension: remove every code whose id is one of xids[0..n) from the lists (and their sub-groups); returns how many.
+    /// With the device copy current (one handle) the lists shrink in HBM as well (ivfhnsw_gpu_remove_ids); otherwise the
+    /// next search uploads them again.
+    size_t remove_ids(size_t n, const idx_t *xids);
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

@@ -128,6 +128,39 @@ int ivfhnsw_gpu_add_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32
                         const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes);
 int ivfhnsw_gpu_download_ivf(ivfhnsw_gpu *h, uint64_t *offsets, uint32_t *ids, uint8_t *codes, uint8_t *norm_codes);
 
+/* ---- removals from the device lists ------------------------------------------------------------
+ *
+ * faiss's remove_ids for the lists the handle holds, in HBM, without a second upload.  ivfhnsw_gpu_remove_ids removes
+ * every code whose id equals one of labels[0..n) from every list that holds one; the codes that remain keep their order
+ * in each list.  Any uint32 label is accepted (0xffffffff included); repeated labels count once, labels that match
+ * nothing are ignored.  After the call the handle's arrays (offsets, local offsets, codes, norm codes, ids, n_local)
+ * are byte for byte what upload_ivf of the remaining lists holds, so searches (labels, distance bits, the max_codes
+ * cut, last_scan_counts) are those of that upload.  On a handle with grouping tables each sub-group loses the codes it
+ * held: the sub-group sizes are those upload_grouping would get with each size reduced by its removed codes, and what
+ * upload_grouping derives from the sizes (the plan's dedupe choice) follows them; alphas, neighbour ids and
+ * inter-centroid distances do not change.
+ *   n_removed (nullable) receives the number of codes removed, removed_per_list (nullable, [nc]) the number per list.
+ *   Errors leave the tables exactly as they were: null labels with n > 0 -> IVFHNSW_ERR_INVALID; allocation failure
+ *   (host or device) -> IVFHNSW_ERR_NOMEM; before upload_ivf, on a view, or on a sharded handle (shard_world > 1: a
+ *   shard cannot update the global offsets of lists other shards own) -> IVFHNSW_ERR_STATE.  n = 0, or labels that
+ *   match nothing: 0 removed, nothing reallocated.
+ *   Synchronous on the handle's stream, like an append.  Like an upload, a removal must not run while views of the
+ *   handle exist; the handle's own two-part batches pick up the new lists.  A removal ends the validity of the last
+ *   search's plan and candidate stream (resolve_keys*, last_stream*).  The graph and the latency walk's records are
+ *   not touched.
+ *   Memory: the new lists are built beside the old ones and swapped in (the peak is twice the list bytes), plus a
+ *   bitmap of the labels over [0, max label] (max label / 8 bytes, at most 512 MB), a removal mask of one bit per code
+ *   (n_local / 8 bytes), the labels' staging (4 n bytes, host form) and [nc] counts; the handle keeps these buffers for
+ *   the next call until it is destroyed.
+ * ivfhnsw_gpu_remove_ids_dev: the same on device pointers (d_labels 4-byte aligned, d_removed_per_list [nc] nullable),
+ *   on the handle's stream; returns when the new arrays are in place.
+ * ivfhnsw_gpu_download_grouping: the sub-group sizes the handle holds, [nc*nsubc] as upload_grouping takes them; no
+ *   grouping tables -> IVFHNSW_ERR_STATE. */
+int ivfhnsw_gpu_remove_ids(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, uint64_t *n_removed, uint32_t *removed_per_list);
+int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint64_t *n_removed,
+                               uint32_t *d_removed_per_list);
+int ivfhnsw_gpu_download_grouping(ivfhnsw_gpu *h, uint32_t *subgroup_sizes);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */

@@ -31,7 +31,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_device_count", "ivfhnsw_gpu_knn", "ivfhnsw_gpu_knn_dev", "ivfhnsw_gpu_build_graph", "ivfhnsw_gpu_set_option", "ivfhnsw_gpu_search_sharded",
     "ivfhnsw_gpu_upload_base", "ivfhnsw_gpu_upload_base_dev", "ivfhnsw_gpu_rerank_dev", "ivfhnsw_gpu_rerank",
     "ivfhnsw_gpu_kmeans", "ivfhnsw_gpu_kmeans_dev", "ivfhnsw_gpu_append_ivf", "ivfhnsw_gpu_append_ivf_dev",
-    "ivfhnsw_gpu_add", "ivfhnsw_gpu_add_dev", "ivfhnsw_gpu_download_ivf",
+    "ivfhnsw_gpu_add", "ivfhnsw_gpu_add_dev", "ivfhnsw_gpu_download_ivf", "ivfhnsw_gpu_remove_ids",
+    "ivfhnsw_gpu_remove_ids_dev", "ivfhnsw_gpu_download_grouping",
 )
 
 
@@ -118,6 +119,9 @@ def lib():
         L.ivfhnsw_gpu_add.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
         L.ivfhnsw_gpu_add_dev.argtypes = L.ivfhnsw_gpu_add.argtypes
         L.ivfhnsw_gpu_download_ivf.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        L.ivfhnsw_gpu_remove_ids.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+        L.ivfhnsw_gpu_remove_ids_dev.argtypes = L.ivfhnsw_gpu_remove_ids.argtypes
+        L.ivfhnsw_gpu_download_grouping.argtypes = [C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_knn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_build_graph.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
@@ -202,6 +206,7 @@ class GpuIndex:
         v._device = self._device
         v._parent = self
         v._shard = getattr(self, "_shard", (0, 1, None))
+        v._nsubc = getattr(self, "_nsubc", 0)
         return v
 
     def close(self):
@@ -307,6 +312,22 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_download_ivf(self._h, None, _ptr(ids), _ptr(codes), _ptr(ncodes)))
         return off, ids, codes, ncodes
 
+    # ---- removals (ivfhnsw_gpu_remove_ids) -------------------------------------------------------
+    def remove_ids(self, labels):
+        """Remove every code whose id is one of `labels` from the lists in HBM (faiss remove_ids): returns (n_removed,
+        removed_per_list uint32 [nc])."""
+        lab = _np(labels, np.uint32).ravel()
+        nr = C.c_uint64(0)
+        per = np.zeros(self.nc, np.uint32)
+        _check(lib().ivfhnsw_gpu_remove_ids(self._h, lab.size, _ptr(lab) if lab.size else None, C.byref(nr), _ptr(per)))
+        return int(nr.value), per
+
+    def remove_ids_dev(self, n, d_labels, d_removed_per_list=None):
+        """The same on device buffers (torch CUDA tensors or raw addresses); returns n_removed."""
+        nr = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_remove_ids_dev(self._h, n, _devptr(d_labels), C.byref(nr), _devptr(d_removed_per_list)))
+        return int(nr.value)
+
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)
         n = _np(nn_centroid_idxs, np.uint32)
@@ -314,6 +335,13 @@ class GpuIndex:
         i = _np(inter_centroid_dists, np.float32)
         assert a.size == self.nc and n.size == s.size == i.size == self.nc * nsubc
         _check(lib().ivfhnsw_gpu_upload_grouping(self._h, nsubc, _ptr(a), _ptr(n), _ptr(s), _ptr(i)))
+        self._nsubc = nsubc
+
+    def download_grouping(self):
+        """The sub-group sizes the handle holds, uint32 [nc, nsubc] as upload_grouping takes them."""
+        out = np.empty((self.nc, getattr(self, "_nsubc", 0)), np.uint32)
+        _check(lib().ivfhnsw_gpu_download_grouping(self._h, _ptr(out) if out.size else None))
+        return out
 
     def upload_quantizer(self, link_counts, links, vectors, enterpoint=0):
         c = _np(link_counts, np.uint8)

@@ -135,6 +135,7 @@ struct ivfhnsw_gpu {
     DevBuf base_rows, base_stage;
     DevBuf ap_idx, ap_ids, ap_codes, ap_ncodes, ap_cnt, ap_own, ap_part, ap_status, ap_perm, ap_perm2, ap_hist,
         ap_tiles; // appends (ivfhnsw_gpu_append_ivf, ivfhnsw_gpu_add)
+    DevBuf rm_labels, rm_bits, rm_mask, rm_keep, rm_rem, rm_out, rm_part, rm_status, rm_sizes; // removals (ivfhnsw_gpu_remove_ids)
     uint64_t base_n = 0;
     size_t base_d = 0;
     ivfhnsw_gpu *parent = nullptr;
@@ -456,7 +457,9 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
                      &h->w_qsd, &h->w_totals, &h->w_visited, &h->w_status, &h->w_stream, &h->w_slen, &h->w_counter, &h->w_tail, &h->w_redo, &h->w_hredo, &h->w_heap, &h->k_q, &h->k_x, &h->k_qn, &h->k_xn, &h->k_part, &h->k_ids, &h->k_dists, &h->t_x, &h->t_y, &h->t_cb, &h->t_assign, &h->t_part, &h->t_c, &h->s_q, &h->s_cid, &h->s_cd, &h->s_dist, &h->s_lab, &h->s_keys, &h->s_len, &h->base_rows, &h->base_stage, &h->r_q, &h->r_cand, &h->r_dist, &h->r_lab,
                      &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2, &h->km_hist,
                      &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes, &h->ap_ncodes, &h->ap_cnt,
-                     &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2, &h->ap_hist, &h->ap_tiles};
+                     &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2, &h->ap_hist, &h->ap_tiles,
+                     &h->rm_labels, &h->rm_bits, &h->rm_mask, &h->rm_keep, &h->rm_rem, &h->rm_out, &h->rm_part, &h->rm_status,
+                     &h->rm_sizes};
     for (auto *b : all)
         b->release();
     h->p_in.release();
@@ -585,6 +588,33 @@ try {
     return fail(IVFHNSW_ERR_NOMEM, "ivfhnsw_gpu_upload_ivf_synthetic: host allocation failed");
 }
 
+// How much do the neighbour lists of groups a query probes together overlap?  Sampled: a group and its 15 nearest
+// neighbour groups stand for a query's probes; the share of DISTINCT ids in their 16 lists.  Clustered centroids
+// (k-means of real descriptors): ~0.1-0.3, the plan's hash set saves most row gathers; iid synthetic: ~0.7, it costs
+// more than it saves (measured).  Tables [nc * nsubc]; upload_grouping and remove_ids set g.dedupe by it.
+static int grouping_dedupe(size_t nc, size_t nsubc, const uint32_t *subgroup_sizes, const uint32_t *nn_centroid_idxs)
+{
+    const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
+    double distinct = 0, total = 0;
+    std::vector<uint32_t> ids;
+    for (size_t c = 0; c < nc; c += step) {
+        ids.clear();
+        auto add_list = [&](size_t cc) {
+            for (size_t j = 0; j < nsubc; j++)
+                if (subgroup_sizes[cc * nsubc + j])
+                    ids.push_back(nn_centroid_idxs[cc * nsubc + j]);
+        };
+        add_list(c);
+        for (size_t j = 0; j < take; j++)
+            if (nn_centroid_idxs[c * nsubc + j] < nc)
+                add_list(nn_centroid_idxs[c * nsubc + j]);
+        total += (double)ids.size();
+        std::sort(ids.begin(), ids.end());
+        distinct += (double)(std::unique(ids.begin(), ids.end()) - ids.begin());
+    }
+    return (total > 0 && distinct / total < 0.55) ? 1 : 0;
+}
+
 int ivfhnsw_gpu_upload_grouping(ivfhnsw_gpu *h, size_t nsubc, const float *alphas, const uint32_t *nn_centroid_idxs,
                                 const uint32_t *subgroup_sizes, const float *inter_centroid_dists)
 try {
@@ -627,31 +657,7 @@ try {
     h->g.nn_idx = h->g_nn.as<uint32_t>();
     h->g.sub_sizes = h->g_sizes.as<uint32_t>();
     h->g.inter_dists = h->g_inter.as<float>();
-    // How much do the neighbour lists of groups a query probes together overlap?  Sampled: a group and its 15 nearest
-    // neighbour groups stand for a query's probes; the share of DISTINCT ids in their 16 lists.  Clustered centroids
-    // (k-means of real descriptors): ~0.1-0.3, the plan's hash set saves most row gathers; iid synthetic: ~0.7, it costs
-    // more than it saves (measured).
-    {
-        const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
-        double distinct = 0, total = 0;
-        std::vector<uint32_t> ids;
-        for (size_t c = 0; c < nc; c += step) {
-            ids.clear();
-            auto add_list = [&](size_t cc) {
-                for (size_t j = 0; j < nsubc; j++)
-                    if (subgroup_sizes[cc * nsubc + j])
-                        ids.push_back(nn_centroid_idxs[cc * nsubc + j]);
-            };
-            add_list(c);
-            for (size_t j = 0; j < take; j++)
-                if (nn_centroid_idxs[c * nsubc + j] < nc)
-                    add_list(nn_centroid_idxs[c * nsubc + j]);
-            total += (double)ids.size();
-            std::sort(ids.begin(), ids.end());
-            distinct += (double)(std::unique(ids.begin(), ids.end()) - ids.begin());
-        }
-        h->g.dedupe = (total > 0 && distinct / total < 0.55) ? 1 : 0;
-    }
+    h->g.dedupe = grouping_dedupe(nc, nsubc, subgroup_sizes, nn_centroid_idxs);
     h->has_group = true;
     return IVFHNSW_OK;
 } catch (const std::bad_alloc &) {
@@ -1760,6 +1766,189 @@ int ivfhnsw_gpu_download_ivf(ivfhnsw_gpu *h, uint64_t *offsets, uint32_t *ids, u
     return IVFHNSW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// removals by label: a stable compaction of the lists into fresh arrays, swapped in when complete
+static int remove_state(ivfhnsw_gpu *h, const char *who)
+{
+    if (h && h->is_view)
+        return fail(IVFHNSW_ERR_STATE, "%s: removals go to the handle that holds the tables, not to a view of it", who);
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_ivf", who);
+    if (h->t.shard_world > 1)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; a shard cannot update the global offsets of the "
+                    "lists other shards own, so sharded handles have no removal", who, h->t.shard_rank, h->t.shard_world);
+    return IVFHNSW_OK;
+}
+
+// d_labels [n] (device memory, n > 0, max_label = their maximum), read on the handle's stream.  rem_out [nc] (device,
+// nullable) receives the codes removed per list.  Returns with the stream drained; on any error the handle's tables are
+// the ones it had.  Nothing removed: no table is reallocated.
+static int remove_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t max_label, uint64_t *n_removed,
+                       uint32_t *rem_out)
+try {
+    const size_t nc = h->t.nc, len = nc + 1;
+    const uint64_t n_local = h->n_local;
+    const size_t ntiles = (size_t)((n_local + kRemoveTileRows - 1) / kRemoveTileRows);
+    const bool grp = h->has_group;
+    const size_t nsub = grp ? nc * (size_t)h->g.nsubc : 0;
+    int rc;
+    if ((rc = h->rm_bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))) ||
+        (rc = h->rm_mask.ensure(std::max<size_t>(ntiles, 1) * (kRemoveTileRows / 64) * sizeof(uint64_t))) ||
+        (rc = h->rm_keep.ensure((ntiles + 1) * sizeof(uint32_t))) || (rc = h->rm_rem.ensure(len * sizeof(uint32_t))) ||
+        (rc = h->rm_part.ensure(append_scan_parts(std::max(len, ntiles + 1)) * sizeof(uint32_t))) ||
+        (rc = h->rm_sizes.ensure(nsub * sizeof(uint32_t))))
+        return rc;
+    uint32_t *keep = h->rm_keep.as<uint32_t>(), *rem = h->rm_rem.as<uint32_t>(), *part = h->rm_part.as<uint32_t>();
+    unsigned long long *mask = h->rm_mask.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(keep + ntiles, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_remove_mark(h->stream, h->t, n_local, d_labels, n, max_label, h->rm_bits.as<uint32_t>(), mask, keep));
+    HIP_TRY(launch_remove_counts(h->stream, h->t, mask, grp ? h->g.sub_sizes : nullptr, h->rm_sizes.as<uint32_t>(),
+                                 grp ? h->g.nsubc : 0, rem, rem_out));
+    HIP_TRY(launch_scan_excl_u32(h->stream, rem, len, part));
+    HIP_TRY(launch_scan_excl_u32(h->stream, keep, ntiles + 1, part));
+    uint32_t removed = 0, kept = 0;
+    HIP_TRY(hipMemcpyAsync(&removed, rem + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&kept, keep + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((uint64_t)removed + kept != n_local)
+        return fail(IVFHNSW_ERR_HIP, "remove_ids: %u removed + %u kept != %llu codes", removed, kept,
+                    (unsigned long long)n_local);
+    *n_removed = removed;
+    if (removed == 0)
+        return IVFHNSW_OK;
+    const uint64_t n_local2 = kept;
+    // the new arrays first: the old ones stay the handle's until the new ones are complete
+    DevBuf goff2, loff2, codes2, ncodes2, ids2;
+    DevBuf *fresh[] = {&goff2, &loff2, &codes2, &ncodes2, &ids2};
+    auto drop = [&] {
+        for (auto *b : fresh)
+            b->release();
+    };
+    if ((rc = goff2.ensure(len * sizeof(uint64_t))) || (rc = loff2.ensure(nc * sizeof(uint32_t))) ||
+        (rc = codes2.ensure(n_local2 * h->t.M)) || (rc = ncodes2.ensure(n_local2)) ||
+        (rc = ids2.ensure(n_local2 * sizeof(uint32_t)))) {
+        drop();
+        return rc;
+    }
+    hipError_t e = launch_remove_compact(h->stream, h->t, n_local, mask, rem, keep, goff2.as<uint64_t>(), loff2.as<uint32_t>(),
+                                         codes2.as<uint8_t>(), ncodes2.as<uint8_t>(), ids2.as<uint32_t>(), n_local2);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->stream);
+    // Grouping: the choice upload_grouping derives from the sizes follows the new ones
+    int dedupe = h->g.dedupe;
+    if (e == hipSuccess && grp) {
+        std::vector<uint32_t> sizes(nsub), nn(nsub);
+        e = hipMemcpy(sizes.data(), h->rm_sizes.p, nsub * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(nn.data(), h->g.nn_idx, nsub * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            dedupe = grouping_dedupe(nc, (size_t)h->g.nsubc, sizes.data(), nn.data());
+    }
+    if (e != hipSuccess) {
+        drop();
+        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "remove_ids: %s", hipGetErrorString(e));
+    }
+    std::swap(h->goff, goff2);
+    std::swap(h->loff, loff2);
+    std::swap(h->codes, codes2);
+    std::swap(h->ncodes, ncodes2);
+    std::swap(h->ids, ids2);
+    drop(); // the old arrays
+    h->t.goff = h->goff.as<uint64_t>();
+    h->t.loff = h->loff.as<uint32_t>();
+    h->t.codes = h->codes.as<uint8_t>();
+    h->t.norm_codes = h->ncodes.as<uint8_t>();
+    h->t.ids = h->ids.as<uint32_t>();
+    h->n_local = n_local2;
+    if (grp) { // the staging that holds the new sizes becomes the table; the old table the next call's staging
+        std::swap(h->g_sizes, h->rm_sizes);
+        h->g.sub_sizes = h->g_sizes.as<uint32_t>();
+        h->g.dedupe = dedupe;
+    }
+    return IVFHNSW_OK;
+} catch (const std::bad_alloc &) {
+    return fail(IVFHNSW_ERR_NOMEM, "remove_ids: host allocation failed");
+}
+
+int ivfhnsw_gpu_remove_ids(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, uint64_t *n_removed, uint32_t *removed_per_list)
+{
+    int rc = remove_state(h, "remove_ids");
+    if (rc)
+        return rc;
+    if (n && !labels)
+        return fail(IVFHNSW_ERR_INVALID, "remove_ids: null labels");
+    if (n_removed)
+        *n_removed = 0;
+    if (removed_per_list)
+        memset(removed_per_list, 0, (size_t)h->t.nc * sizeof(uint32_t));
+    if (n == 0 || h->n_local == 0)
+        return IVFHNSW_OK;
+    uint32_t mx = 0;
+    for (size_t i = 0; i < n; i++)
+        mx = std::max(mx, labels[i]);
+    if ((rc = h->rm_labels.ensure(n * sizeof(uint32_t))) ||
+        (removed_per_list && (rc = h->rm_out.ensure((size_t)h->t.nc * sizeof(uint32_t)))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->rm_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    uint64_t removed = 0;
+    if ((rc = remove_core(h, n, h->rm_labels.as<uint32_t>(), mx, &removed, removed_per_list ? h->rm_out.as<uint32_t>() : nullptr)))
+        return rc;
+    if (removed_per_list && removed)
+        HIP_TRY(hipMemcpy(removed_per_list, h->rm_out.p, (size_t)h->t.nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_removed)
+        *n_removed = removed;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint64_t *n_removed,
+                               uint32_t *d_removed_per_list)
+{
+    int rc = remove_state(h, "remove_ids_dev");
+    if (rc)
+        return rc;
+    if (n && !d_labels)
+        return fail(IVFHNSW_ERR_INVALID, "remove_ids_dev: null labels");
+    if (n_removed)
+        *n_removed = 0;
+    if (n == 0 || h->n_local == 0) {
+        if (d_removed_per_list) {
+            HIP_TRY(hipMemsetAsync(d_removed_per_list, 0, (size_t)h->t.nc * sizeof(uint32_t), h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        return IVFHNSW_OK;
+    }
+    if ((rc = h->rm_status.ensure(sizeof(uint32_t))))
+        return rc;
+    uint32_t mx = 0;
+    HIP_TRY(hipMemsetAsync(h->rm_status.p, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->rm_status.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(&mx, h->rm_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    uint64_t removed = 0;
+    if ((rc = remove_core(h, n, d_labels, mx, &removed, d_removed_per_list)))
+        return rc;
+    if (n_removed)
+        *n_removed = removed;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_download_grouping(ivfhnsw_gpu *h, uint32_t *subgroup_sizes)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_group)
+        return fail(IVFHNSW_ERR_STATE, "download_grouping: the handle holds no grouping tables");
+    if (!subgroup_sizes)
+        return fail(IVFHNSW_ERR_INVALID, "download_grouping: null buffer");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(subgroup_sizes, h->g.sub_sizes, (size_t)h->t.nc * h->g.nsubc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
 static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
                             const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
                             int64_t *d_labels, int64_t *d_out_keys);
@@ -2817,7 +3006,8 @@ int ivfhnsw_gpu_memory_bytes(ivfhnsw_gpu *h, uint64_t *bytes)
                            &h->km_x, &h->km_c, &h->km_assign, &h->km_dist, &h->km_cnt, &h->km_start, &h->km_ids, &h->km_ids2,
                            &h->km_hist, &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes,
                            &h->ap_ncodes, &h->ap_cnt, &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2,
-                           &h->ap_hist, &h->ap_tiles};
+                           &h->ap_hist, &h->ap_tiles, &h->rm_labels, &h->rm_bits, &h->rm_mask, &h->rm_keep, &h->rm_rem,
+                           &h->rm_out, &h->rm_part, &h->rm_status, &h->rm_sizes};
     uint64_t s = 0;
     for (auto *b : all)
         s += b->bytes;

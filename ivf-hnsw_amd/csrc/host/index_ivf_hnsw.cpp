@@ -761,6 +761,72 @@ void IndexIVF_HNSW::add_batch(size_t n, const float *x, const idx_t *xids, const
         device_dirty_ = true;
 }
 
+size_t IndexIVF_HNSW::remove_ids(size_t n, const idx_t *xids)
+{
+    // A current device copy (one handle, nothing ensure_device would re-upload) shrinks in place: ivfhnsw_gpu_remove_ids
+    // compacts the lists in HBM and reports the codes it removed per list, so only those host lists are
+    // filtered.  Every other case filters every list on the host and marks the copy stale.
+    if (n == 0)
+        return 0;
+    auto *grouping = dynamic_cast<IndexIVF_HNSW_Grouping *>(this);
+    const bool in_place = nshards() == 1 && device_current();
+    std::vector<uint32_t> per_list;
+    uint64_t dev_removed = 0;
+    if (in_place) {
+        per_list.assign(nc, 0);
+        if (ivfhnsw_gpu_remove_ids(gpu_, n, xids, &dev_removed, per_list.data()))
+            gpu_fail("ivfhnsw_gpu_remove_ids");
+    }
+    std::vector<idx_t> labels(xids, xids + n);
+    std::sort(labels.begin(), labels.end());
+    labels.erase(std::unique(labels.begin(), labels.end()), labels.end());
+    size_t removed = 0;
+    for (size_t c = 0; c < nc; c++) {
+        if (in_place && per_list[c] == 0)
+            continue;
+        std::vector<idx_t> &lid = ids[c];
+        std::vector<uint8_t> &lcode = codes[c], &lnorm = norm_codes[c];
+        // the list's rows sub-group by sub-group (one group of the whole list without Grouping tables)
+        std::vector<idx_t> whole(1, (idx_t)lid.size());
+        std::vector<idx_t> &groups = grouping && !grouping->subgroup_sizes[c].empty() ? grouping->subgroup_sizes[c] : whole;
+        size_t r = 0, w = 0;
+        for (idx_t &size : groups) {
+            const size_t end = r + size;
+            for (; r < end; r++) {
+                if (std::binary_search(labels.begin(), labels.end(), lid[r])) {
+                    size--;
+                    continue;
+                }
+                lid[w] = lid[r];
+                std::copy(lcode.begin() + r * code_size, lcode.begin() + (r + 1) * code_size, lcode.begin() + w * code_size);
+                lnorm[w] = lnorm[r];
+                w++;
+            }
+        }
+        if (r != lid.size())
+            throw std::runtime_error("IndexIVF_HNSW::remove_ids: the sub-group sizes of list " + std::to_string(c) +
+                                     " do not add up to its length");
+        const size_t gone = r - w;
+        if (in_place && gone != per_list[c])
+            throw std::runtime_error("IndexIVF_HNSW::remove_ids: list " + std::to_string(c) + " lost " +
+                                     std::to_string(gone) + " codes on the host, " + std::to_string(per_list[c]) +
+                                     " on the device");
+        lid.resize(w);
+        lcode.resize(w * code_size);
+        lnorm.resize(w);
+        removed += gone;
+    }
+    if (in_place) {
+        if (removed != dev_removed)
+            throw std::runtime_error("IndexIVF_HNSW::remove_ids: " + std::to_string(removed) + " codes removed on the host, " +
+                                     std::to_string(dev_removed) + " on the device");
+        up_total_ -= removed;
+    } else if (removed) {
+        device_dirty_ = true;
+    }
+    return removed;
+}
+
 void IndexIVF_HNSW::add_batch2(size_t, const float *, const idx_t *, const idx_t *, uint64_t *, char *)
 {
     throw std::runtime_error("IndexIVF_HNSW::add_batch2: the ORCV vendor format is out of scope (SURVEY.md 2, row 9)");

@@ -275,6 +275,23 @@ hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t
 hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
                                  const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
                                  const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2);
+// exclusive scan of a [len] in place with the scan above; part: append_scan_parts(len) words
+hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part);
+// removal by label from an unsharded handle (kernels_remove.hip).  max: atomicMax of the labels into
+// *out.  mark: bits ((max_label / 32 + 1) words) = the label set, then mask [ceil(n_local / kRemoveTileRows) *
+// kRemoveTileRows / 64] (bit r = row r is removed) and keep [one per tile] = rows each tile keeps.  counts: rem [nc + 1]
+// (slot nc zero) = codes removed per list, also into rem_out when non-null; sizes != null (Grouping): sizes2 [nc * nsubc]
+// = the sub-group sizes after the removal.  compact, after rem and keep are scanned (rscan, kscan): goff2 / loff2 and the
+// surviving rows, in order, into the new arrays of n_local2 rows.
+constexpr int kRemoveTileRows = 2048;
+hipError_t launch_remove_max(hipStream_t s, const uint32_t *labels, size_t n, uint32_t *out);
+hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *labels, size_t n,
+                              uint32_t max_label, uint32_t *bits, unsigned long long *mask, uint32_t *keep);
+hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigned long long *mask, const uint32_t *sizes,
+                                uint32_t *sizes2, int nsubc, uint32_t *rem, uint32_t *rem_out);
+hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
+                                 const uint32_t *rscan, const uint32_t *kscan, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2,
+                                 uint8_t *ncodes2, uint32_t *ids2, uint64_t n_local2);
 // sum of PlanHdr.total / nseg over the batch into out[0], out[1]
 hipError_t launch_plan_totals(hipStream_t s, const PlanHdr *hdr, int nq, unsigned long long *out);
 

@@ -285,6 +285,20 @@ hipError_t launch_append_tables(hipStream_t s, const IvfTables &t, uint32_t *cnt
     return hipGetLastError();
 }
 
+hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part)
+{
+    if (len == 0)
+        return hipSuccess;
+    const uint32_t nblk = (uint32_t)blocks_of(len, kScanChunk);
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nblk, 1), dim3(256), 0, s, a, nullptr, len, part, nblk);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_scan_u32(s, part, part, nblk); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk, 1), dim3(256), 0, s, a, nullptr, len, part, nblk);
+    return hipGetLastError();
+}
+
 hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
                                uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
                                uint32_t *ids2, uint64_t n_local2)
