@@ -118,6 +118,9 @@ public:
     virtual void sync_to_device();
     /// Extension: call after mutating ids/codes/norm_codes/pq/... behind the class's back.
     void invalidate_device() { device_dirty_ = true; }
+    /// Extension: how often the lists, tables and code books went to the device as a whole (sync_to_device and the
+    /// lazy form of it); in-place additions and table re-sends do not count.
+    size_t device_full_uploads() const;
 
     /// Extension: the raw uint8 base vectors of a .bvecs file (the rows searchDisk reads, utils.cpp:98-105) into HBM,
     /// streamed in chunks of at most 256 MB with every record's dim header checked.  searchDisk / searchDisk_batch with
@@ -140,6 +143,15 @@ protected:
     /// the device copy is what ensure_device would upload (add_batch then appends to it in place)
     bool device_current();
     void device_upload_common();
+    /// The finer state beside device_dirty_: the lists on the device are current, but a table pass (compute_centroid_norms,
+    /// compute_inter_centroid_dists) changed values; ensure_device re-sends only those tables.
+    /// (Kept beside the object, like the re-rank state: the class layout must not grow.)
+    enum { kTableNorms = 1, kTableGrouping = 2 };
+    unsigned tables_dirty() const;
+    void mark_tables_dirty(unsigned which);
+    void sync_tables_to_device();
+    /// n codes went into the device lists in place (add_batch, Grouping::add_group): the fingerprint follows
+    void device_took(size_t n) { up_total_ += n; }
     /// construction side: graph (once per quantizer state) and code books (every call) for ivfhnsw_gpu_encode
     void ensure_encoder();
     void upload_graph();

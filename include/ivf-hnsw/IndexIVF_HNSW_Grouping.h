@@ -39,6 +39,8 @@ public:
     void dump_inter_centroid_dists(char *path);
 
     void sync_to_device() override;
+    /// Extension: the four grouping tables alone to the lists the device already holds (ivfhnsw_gpu_upload_grouping)
+    void upload_grouping_tables();
 
 protected:
     bool shards_need_graph() const override { return true; } // sub-centroid distances (Grouping.cpp:248,314) on every shard

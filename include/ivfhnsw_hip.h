@@ -103,8 +103,9 @@ int ivfhnsw_gpu_upload_ivf_synthetic(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *des
  *   Sharded handles (shard_world > 1): pass every shard the whole batch.  Each updates the global offsets and keeps
  *   the codes of the lists it owns (the ownership recorded at upload).
  *   Errors leave the tables exactly as they were: list_idx[i] >= nc or n_local + n >= 2^32 - 1 -> IVFHNSW_ERR_INVALID;
- *   allocation failure -> IVFHNSW_ERR_NOMEM; before upload_ivf, on a view, or on a handle with grouping tables (a
- *   second add_group is no append, IndexIVF_HNSW_Grouping.cpp:43-157) -> IVFHNSW_ERR_STATE.  n = 0 does nothing.
+ *   allocation failure -> IVFHNSW_ERR_NOMEM; before upload_ivf, on a view, or on a handle with grouping tables (its
+ *   lists grow inside, by ivfhnsw_gpu_append_grouping / ivfhnsw_gpu_add_groups below) -> IVFHNSW_ERR_STATE.  n = 0 does
+ *   nothing.
  *   The new arrays are built beside the old ones and swapped in: the peak is twice the list bytes.  The graph and
  *   the latency walk's records are not touched.  Like an upload, an append must not run while views of the handle
  *   exist (ivfhnsw_gpu_create_view): they keep the old arrays, which the append frees.  A view created afterwards
@@ -160,6 +161,64 @@ int ivfhnsw_gpu_remove_ids(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, uin
 int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint64_t *n_removed,
                                uint32_t *d_removed_per_list);
 int ivfhnsw_gpu_download_grouping(ivfhnsw_gpu *h, uint32_t *subgroup_sizes);
+
+/* ---- additions to a Grouping index on the device -----------------------------------------------
+ *
+ * IndexIVF_HNSW_Grouping::add_group lays a group out as nsubc sub-groups end to end (IndexIVF_HNSW_Grouping.cpp:
+ * 127-155), so a Grouping list grows at the end of each of its sub-groups, not only at its own end.
+ * ivfhnsw_gpu_append_grouping does that to the lists the handle holds, in HBM: code i (ids[i], codes[i*code_size ..],
+ * norm_codes[i]) goes to the end of sub-group sub_idx[i] of list list_idx[i]; codes of one sub-group keep ascending i;
+ * codes already there keep their order; alpha, neighbours and inter-centroid distances of the group do not change.
+ * After any sequence of calls the handle's arrays (offsets, local offsets, codes, norm codes, ids, n_local, sub-group
+ * sizes, and the dedupe choice upload_grouping derives from them) are byte for byte what upload_ivf + upload_grouping
+ * of the merged lists hold, so searches (labels, distance bits, the max_codes cut, pruning decisions,
+ * last_scan_counts) are those of that upload.
+ * ivfhnsw_gpu_add_groups is add_group (:43-157) for groups that hold no codes (never added, or emptied by
+ * ivfhnsw_gpu_remove_ids; the vector-add driver's flow, tests/test_ivfhnsw_grouping_sift1b_vector_add.cpp):
+ * ivfhnsw_gpu_encode_groups on the same arguments with the handle's nsubc, then for every group with points its
+ * nn_centroid_idxs row, its alpha, its inter-centroid-distance row and its codes (sub-group by sub-group, arrival
+ * order inside each, :127-155) are installed, the codes never leaving HBM between the encode and the install.  A group
+ * with zero points gets its neighbour row and nothing else (:63-64).  ids [offsets[ngroups]] are the labels of the
+ * points.  inter_centroid_dists NULL: the rows are computed on the device as compute_inter_centroid_dists does
+ * (:620-631); non-NULL ([ngroups*nsubc]): the caller's rows are stored as given.  out_nn_centroid_idxs
+ * [ngroups*nsubc], out_alphas [ngroups] (an empty group keeps the caller's value), out_subcentroid_idxs [n], out_codes
+ * [n*code_size] and out_norm_codes [n] (nullable) receive what encode_groups returns.
+ *   Sharded handles (shard_world > 1): pass every shard the whole batch.  Each updates the global offsets and the
+ *   (replicated) grouping tables and keeps the codes of the lists it owns.
+ *   Errors are found before anything is written and leave every table exactly as it was: list_idx[i] >= nc,
+ *   sub_idx[i] >= nsubc, centroid_idx[g] >= nc, the same centroid twice in one add_groups call, n_local + n >=
+ *   2^32 - 1, code books that do not match the index -> IVFHNSW_ERR_INVALID; an add_groups centroid whose list already
+ *   holds codes (with or without points of its own in the call) -> IVFHNSW_ERR_STATE, the message naming the list;
+ *   before upload_ivf, on a view, or on a handle WITHOUT grouping tables -> IVFHNSW_ERR_STATE; allocation failure ->
+ *   IVFHNSW_ERR_NOMEM.  n = 0 / ngroups = 0 does nothing.  (An error of the encode itself -- efSearch < nsubc + 1, a
+ *   walk that finds fewer than nsubc + 1 centroids -- also leaves the tables; the out_* arrays may be partly written.)
+ *   Views, streams, memory, validity: as for ivfhnsw_gpu_append_ivf (no views alive during the call; synchronous on the
+ *   handle's stream; new arrays built beside the old ones and swapped in, peak twice the list bytes, plus three
+ *   [nc*nsubc] uint32 work tables the handle keeps) and as for ivfhnsw_gpu_remove_ids (the last search's plan and
+ *   candidate stream stop being valid; the graph and the latency walk's records are not touched).
+ * The _dev forms: the same on device pointers (4-byte aligned; offsets 8-byte; else IVFHNSW_ERR_INVALID) on the handle's
+ *   stream; the ids are checked on the device and a status word read before anything changes.  add_groups_dev reads d_centroid_idx and
+ *   d_offsets back first (they steer the chunking of the encode).
+ * ivfhnsw_gpu_download_grouping_tables: alphas [nc], nn_centroid_idxs, subgroup_sizes, inter_centroid_dists
+ *   [nc*nsubc each] as the handle holds them (each nullable); no grouping tables -> IVFHNSW_ERR_STATE.
+ * ivfhnsw_gpu_upload_centroid_norms: replaces the [nc] centroid norms upload_ivf's descriptor brought
+ *   (IndexIVF_HNSW::compute_centroid_norms, IndexIVF_HNSW.cpp:930-935) and nothing else; before upload_ivf or on a
+ *   view -> IVFHNSW_ERR_STATE. */
+int ivfhnsw_gpu_append_grouping(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *sub_idx,
+                                const uint32_t *ids, const uint8_t *codes, const uint8_t *norm_codes);
+int ivfhnsw_gpu_append_grouping_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_sub_idx,
+                                    const uint32_t *d_ids, const uint8_t *d_codes, const uint8_t *d_norm_codes);
+int ivfhnsw_gpu_add_groups(ivfhnsw_gpu *h, size_t ngroups, const uint32_t *centroid_idx, const uint64_t *offsets, const float *x,
+                           size_t efSearch, const uint32_t *ids, const float *inter_centroid_dists,
+                           uint32_t *out_nn_centroid_idxs, float *out_alphas, uint32_t *out_subcentroid_idxs, uint8_t *out_codes,
+                           uint8_t *out_norm_codes);
+int ivfhnsw_gpu_add_groups_dev(ivfhnsw_gpu *h, size_t ngroups, const uint32_t *d_centroid_idx, const uint64_t *d_offsets,
+                               const float *d_x, size_t efSearch, const uint32_t *d_ids, const float *d_inter_centroid_dists,
+                               uint32_t *d_out_nn_centroid_idxs, float *d_out_alphas, uint32_t *d_out_subcentroid_idxs,
+                               uint8_t *d_out_codes, uint8_t *d_out_norm_codes);
+int ivfhnsw_gpu_download_grouping_tables(ivfhnsw_gpu *h, float *alphas, uint32_t *nn_centroid_idxs, uint32_t *subgroup_sizes,
+                                         float *inter_centroid_dists);
+int ivfhnsw_gpu_upload_centroid_norms(ivfhnsw_gpu *h, const float *centroid_norms);
 
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty

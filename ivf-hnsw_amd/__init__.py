@@ -32,7 +32,9 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_upload_base", "ivfhnsw_gpu_upload_base_dev", "ivfhnsw_gpu_rerank_dev", "ivfhnsw_gpu_rerank",
     "ivfhnsw_gpu_kmeans", "ivfhnsw_gpu_kmeans_dev", "ivfhnsw_gpu_append_ivf", "ivfhnsw_gpu_append_ivf_dev",
     "ivfhnsw_gpu_add", "ivfhnsw_gpu_add_dev", "ivfhnsw_gpu_download_ivf", "ivfhnsw_gpu_remove_ids",
-    "ivfhnsw_gpu_remove_ids_dev", "ivfhnsw_gpu_download_grouping",
+    "ivfhnsw_gpu_remove_ids_dev", "ivfhnsw_gpu_download_grouping", "ivfhnsw_gpu_append_grouping",
+    "ivfhnsw_gpu_append_grouping_dev", "ivfhnsw_gpu_add_groups", "ivfhnsw_gpu_add_groups_dev",
+    "ivfhnsw_gpu_download_grouping_tables", "ivfhnsw_gpu_upload_centroid_norms",
 )
 
 
@@ -122,6 +124,13 @@ def lib():
         L.ivfhnsw_gpu_remove_ids.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
         L.ivfhnsw_gpu_remove_ids_dev.argtypes = L.ivfhnsw_gpu_remove_ids.argtypes
         L.ivfhnsw_gpu_download_grouping.argtypes = [C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_append_grouping.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+        L.ivfhnsw_gpu_append_grouping_dev.argtypes = L.ivfhnsw_gpu_append_grouping.argtypes
+        L.ivfhnsw_gpu_add_groups.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + \
+            [C.c_void_p] * 7
+        L.ivfhnsw_gpu_add_groups_dev.argtypes = L.ivfhnsw_gpu_add_groups.argtypes
+        L.ivfhnsw_gpu_download_grouping_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        L.ivfhnsw_gpu_upload_centroid_norms.argtypes = [C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_knn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_build_graph.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
@@ -342,6 +351,76 @@ class GpuIndex:
         out = np.empty((self.nc, getattr(self, "_nsubc", 0)), np.uint32)
         _check(lib().ivfhnsw_gpu_download_grouping(self._h, _ptr(out) if out.size else None))
         return out
+
+    # ---- additions to a Grouping index (ivfhnsw_gpu_append_grouping / ivfhnsw_gpu_add_groups) ----
+    def append_grouping(self, list_idx, sub_idx, ids, codes, norm_codes):
+        """Put code i at the end of sub-group sub_idx[i] of list list_idx[i] (IndexIVF_HNSW_Grouping.cpp:127-155) in HBM;
+        host arrays."""
+        li = _np(list_idx, np.uint32).ravel()
+        n = li.size
+        si = _np(sub_idx, np.uint32).ravel()
+        i = _np(ids, np.uint32).ravel()
+        c = _np(codes, np.uint8).reshape(n, -1) if n else np.zeros((0, self.code_size), np.uint8)
+        nc = _np(norm_codes, np.uint8).ravel()
+        assert si.size == n and i.size == n and nc.size == n and (not self.code_size or c.shape[1] == self.code_size)
+        _check(lib().ivfhnsw_gpu_append_grouping(self._h, n, _ptr(li), _ptr(si), _ptr(i), _ptr(c), _ptr(nc)))
+
+    def append_grouping_dev(self, n, d_list_idx, d_sub_idx, d_ids, d_codes, d_norm_codes):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_append_grouping_dev(self._h, n, _devptr(d_list_idx), _devptr(d_sub_idx), _devptr(d_ids),
+                                                     _devptr(d_codes), _devptr(d_norm_codes)))
+
+    def add_groups(self, centroid_idx, offsets, x, ids, efSearch, inter_centroid_dists=None, alphas_in=None):
+        """add_group for groups that hold no codes: encode_groups + the install of rows and codes in HBM.  Returns what
+        encode_groups does: (nn_centroid_idxs [G, nsubc], alphas [G], subcentroid_idxs [n], codes [n, M], norm_codes [n]).
+        inter_centroid_dists None: the rows are computed on the device; [G, nsubc]: stored as given."""
+        cidx = _np(centroid_idx, np.uint32).ravel()
+        off = _np(offsets, np.uint64).ravel()
+        G = cidx.size
+        nsubc = getattr(self, "_nsubc", 0)
+        x = _np(x, np.float32)
+        x = x.reshape(-1, x.shape[-1]) if x.size else x.reshape(0, 1)
+        n = int(off[-1]) if off.size else 0
+        i = _np(ids, np.uint32).ravel()
+        assert off.size == G + 1 and i.size == n and x.shape[0] == n
+        icd = None if inter_centroid_dists is None else _np(inter_centroid_dists, np.float32)
+        assert icd is None or icd.size == G * nsubc
+        nn = np.empty((G, nsubc), np.uint32)
+        alphas = np.zeros(G, np.float32) if alphas_in is None else _np(alphas_in, np.float32).copy()
+        sub = np.empty(n, np.uint32)
+        codes = np.empty((n, self.code_size), np.uint8)
+        ncodes = np.empty(n, np.uint8)
+        _check(lib().ivfhnsw_gpu_add_groups(self._h, G, _ptr(cidx), _ptr(off), _ptr(x), efSearch, _ptr(i), _ptr(icd),
+                                            _ptr(nn), _ptr(alphas), _ptr(sub), _ptr(codes), _ptr(ncodes)))
+        return nn, alphas, sub, codes, ncodes
+
+    def add_groups_dev(self, ngroups, d_centroid_idx, d_offsets, d_x, d_ids, efSearch, d_out_nn_centroid_idxs, d_out_alphas,
+                       d_out_subcentroid_idxs, d_out_codes, d_out_norm_codes=None, d_inter_centroid_dists=None):
+        """add_groups on device buffers (d_offsets uint64 [ngroups + 1]; d_out_norm_codes optional)."""
+        _check(lib().ivfhnsw_gpu_add_groups_dev(self._h, ngroups, _devptr(d_centroid_idx), _devptr(d_offsets), _devptr(d_x),
+                                                efSearch, _devptr(d_ids), _devptr(d_inter_centroid_dists),
+                                                _devptr(d_out_nn_centroid_idxs), _devptr(d_out_alphas),
+                                                _devptr(d_out_subcentroid_idxs), _devptr(d_out_codes),
+                                                _devptr(d_out_norm_codes)))
+
+    def download_grouping_tables(self):
+        """(alphas f32 [nc], nn_centroid_idxs u32 [nc, nsubc], subgroup_sizes u32 [nc, nsubc], inter_centroid_dists f32
+        [nc, nsubc]) as the handle holds them."""
+        nsubc = getattr(self, "_nsubc", 0)
+        a = np.empty(self.nc, np.float32)
+        nn = np.empty((self.nc, nsubc), np.uint32)
+        sz = np.empty((self.nc, nsubc), np.uint32)
+        icd = np.empty((self.nc, nsubc), np.float32)
+        has = nsubc > 0
+        _check(lib().ivfhnsw_gpu_download_grouping_tables(self._h, _ptr(a), _ptr(nn) if has else None,
+                                                          _ptr(sz) if has else None, _ptr(icd) if has else None))
+        return a, nn, sz, icd
+
+    def upload_centroid_norms(self, centroid_norms):
+        """Replace the [nc] centroid norms upload_ivf brought (compute_centroid_norms) and nothing else."""
+        cn = _np(centroid_norms, np.float32).ravel()
+        assert cn.size == self.nc
+        _check(lib().ivfhnsw_gpu_upload_centroid_norms(self._h, _ptr(cn)))
 
     def upload_quantizer(self, link_counts, links, vectors, enterpoint=0):
         c = _np(link_counts, np.uint8)

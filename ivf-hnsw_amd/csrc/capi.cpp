@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 using namespace ivfhnsw_gpu_impl;
@@ -135,6 +136,8 @@ struct ivfhnsw_gpu {
     DevBuf base_rows, base_stage;
     DevBuf ap_idx, ap_ids, ap_codes, ap_ncodes, ap_cnt, ap_own, ap_part, ap_status, ap_perm, ap_perm2, ap_hist,
         ap_tiles; // appends (ivfhnsw_gpu_append_ivf, ivfhnsw_gpu_add)
+    DevBuf gp_sub, gp_sizes, gp_pre_old, gp_pre_new, gp_rows, gp_gather, ga_cidx, ga_off, ga_nn, ga_alpha, ga_inter,
+        ga_status; // additions to a Grouping index (ivfhnsw_gpu_append_grouping, ivfhnsw_gpu_add_groups)
     DevBuf rm_labels, rm_bits, rm_mask, rm_keep, rm_rem, rm_out, rm_part, rm_status, rm_sizes; // removals (ivfhnsw_gpu_remove_ids)
     uint64_t base_n = 0;
     size_t base_d = 0;
@@ -358,6 +361,46 @@ int upload_tables(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *d, std::vector<uint32_
     return IVFHNSW_OK;
 }
 
+// The dedupe choice of a Grouping index (see grouping_dedupe below) over row accessors, so that a caller holding only the
+// sampled rows can ask the same question.
+// sizes_row(c) / nn_row(c): row c of the two tables (only the sampled groups' rows and their neighbours' are asked for)
+template <class SizesRow, class NnRow>
+int grouping_dedupe_rows(size_t nc, size_t nsubc, SizesRow sizes_row, NnRow nn_row)
+{
+    const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
+    double distinct = 0, total = 0;
+    // distinct ids of a sample by the sample's number stamped on the id (ids of non-empty sub-groups are < nc, checked at
+    // upload; any other id is counted by sort + unique): sorting every sample cost about 15 ms per call at nsubc 64, DESIGN.md 3.12
+    std::vector<uint32_t> seen(nc, 0), odd;
+    uint32_t stamp = 0;
+    for (size_t c = 0; c < nc; c += step) {
+        odd.clear();
+        stamp++;
+        auto add_list = [&](size_t cc) {
+            const uint32_t *sz = sizes_row(cc), *nn = nn_row(cc);
+            for (size_t j = 0; j < nsubc; j++) {
+                if (!sz[j])
+                    continue;
+                total += 1.0;
+                if (nn[j] >= nc) {
+                    odd.push_back(nn[j]);
+                } else if (seen[nn[j]] != stamp) {
+                    seen[nn[j]] = stamp;
+                    distinct += 1.0;
+                }
+            }
+        };
+        add_list(c);
+        const uint32_t *nn_c = nn_row(c);
+        for (size_t j = 0; j < take; j++)
+            if (nn_c[j] < nc)
+                add_list(nn_c[j]);
+        std::sort(odd.begin(), odd.end());
+        distinct += (double)(std::unique(odd.begin(), odd.end()) - odd.begin());
+    }
+    return (total > 0 && distinct / total < 0.55) ? 1 : 0;
+}
+
 } // namespace
 
 // for the library's other translation units (graph_build.cpp): record a failure the way every entry point does
@@ -459,7 +502,8 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
                      &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes, &h->ap_ncodes, &h->ap_cnt,
                      &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2, &h->ap_hist, &h->ap_tiles,
                      &h->rm_labels, &h->rm_bits, &h->rm_mask, &h->rm_keep, &h->rm_rem, &h->rm_out, &h->rm_part, &h->rm_status,
-                     &h->rm_sizes};
+                     &h->rm_sizes, &h->gp_sub, &h->gp_sizes, &h->gp_pre_old, &h->gp_pre_new, &h->gp_rows,
+                     &h->gp_gather, &h->ga_cidx, &h->ga_off, &h->ga_nn, &h->ga_alpha, &h->ga_inter, &h->ga_status};
     for (auto *b : all)
         b->release();
     h->p_in.release();
@@ -594,25 +638,8 @@ try {
 // more than it saves (measured).  Tables [nc * nsubc]; upload_grouping and remove_ids set g.dedupe by it.
 static int grouping_dedupe(size_t nc, size_t nsubc, const uint32_t *subgroup_sizes, const uint32_t *nn_centroid_idxs)
 {
-    const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
-    double distinct = 0, total = 0;
-    std::vector<uint32_t> ids;
-    for (size_t c = 0; c < nc; c += step) {
-        ids.clear();
-        auto add_list = [&](size_t cc) {
-            for (size_t j = 0; j < nsubc; j++)
-                if (subgroup_sizes[cc * nsubc + j])
-                    ids.push_back(nn_centroid_idxs[cc * nsubc + j]);
-        };
-        add_list(c);
-        for (size_t j = 0; j < take; j++)
-            if (nn_centroid_idxs[c * nsubc + j] < nc)
-                add_list(nn_centroid_idxs[c * nsubc + j]);
-        total += (double)ids.size();
-        std::sort(ids.begin(), ids.end());
-        distinct += (double)(std::unique(ids.begin(), ids.end()) - ids.begin());
-    }
-    return (total > 0 && distinct / total < 0.55) ? 1 : 0;
+    return grouping_dedupe_rows(nc, nsubc, [&](size_t c) { return subgroup_sizes + c * nsubc; },
+                                [&](size_t c) { return nn_centroid_idxs + c * nsubc; });
 }
 
 int ivfhnsw_gpu_upload_grouping(ivfhnsw_gpu *h, size_t nsubc, const float *alphas, const uint32_t *nn_centroid_idxs,
@@ -1120,11 +1147,14 @@ int ivfhnsw_gpu_encode(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t 
     return IVFHNSW_OK;
 }
 
-int ivfhnsw_gpu_encode_groups(ivfhnsw_gpu *h, size_t ngroups, size_t nsubc, const uint32_t *centroid_idx,
+// centroid_idx and offsets are host arrays; dev: x and the out_* arrays are device pointers.  stage (add_groups): every
+// chunk's list ids, sub-group ids, codes and norm codes also go to the append staging (ap_idx, gp_sub, ap_codes, ap_ncodes)
+// and the groups' neighbour rows and alphas to ga_nn / ga_alpha, all sized by the caller.
+static int encode_groups_impl(ivfhnsw_gpu *h, size_t ngroups, size_t nsubc, const uint32_t *centroid_idx,
                               const uint64_t *offsets, const float *x, size_t efSearch, uint32_t *out_nn_centroid_idxs,
                               float *out_alphas, uint32_t *out_subcentroid_idxs, uint8_t *out_codes,
-                              uint8_t *out_norm_codes)
-try {
+                              uint8_t *out_norm_codes, bool dev, bool stage)
+{
     int rc = bind(h);
     if (rc)
         return rc;
@@ -1151,8 +1181,10 @@ try {
         if (centroid_idx[g] >= h->gr.n)
             return fail(IVFHNSW_ERR_INVALID, "centroid_idx[%zu] = %u out of range", g, centroid_idx[g]);
     }
-    if (n_total && (!x || !out_subcentroid_idxs || !out_codes || !out_norm_codes))
+    if (n_total && (!x || !out_subcentroid_idxs || !out_codes || (!out_norm_codes && !stage)))
         return fail(IVFHNSW_ERR_INVALID, "null buffer");
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     // chunks of whole groups: at most 2^18 points (one oversized group goes alone) and 4096 groups
     const size_t kMaxPoints = (size_t)1 << 18, kMaxGroups = 4096;
     std::vector<uint32_t> ids, nn;
@@ -1194,7 +1226,13 @@ try {
                 nn[g * nsubc + s] = ids[g * k + s + 1];
                 cvn[g * nsubc + s] = dists[g * k + s + 1];
             }
-        std::memcpy(out_nn_centroid_idxs + g0 * nsubc, nn.data(), G * nsubc * sizeof(uint32_t));
+        if (dev)
+            HIP_TRY(hipMemcpy(out_nn_centroid_idxs + g0 * nsubc, nn.data(), G * nsubc * sizeof(uint32_t), hipMemcpyHostToDevice));
+        else
+            std::memcpy(out_nn_centroid_idxs + g0 * nsubc, nn.data(), G * nsubc * sizeof(uint32_t));
+        if (stage)
+            HIP_TRY(hipMemcpy(h->ga_nn.as<uint32_t>() + g0 * nsubc, nn.data(), G * nsubc * sizeof(uint32_t),
+                              hipMemcpyHostToDevice));
         if (m == 0) { // only empty groups: alpha stays what the caller has (Grouping.cpp:63-64)
             g0 = g1;
             continue;
@@ -1208,7 +1246,7 @@ try {
             (rc = h->e_ncodes.ensure(m)) || (rc = h->cg_sub.ensure(m * sizeof(uint32_t))))
             return rc;
         float *dx = h->e_x.as<float>();
-        HIP_TRY(hipMemcpyAsync(dx, x + p0 * d, m * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dx, x + p0 * d, m * d * sizeof(float), in, h->stream));
         HIP_TRY(hipMemcpyAsync(h->gc_nn.p, nn.data(), G * nsubc * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(h->cg_cvn.p, cvn.data(), G * nsubc * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(h->cg_off.p, off.data(), (G + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
@@ -1230,16 +1268,39 @@ try {
         // alphas: only groups with points are written (an empty group keeps the caller's value)
         std::vector<float> al(G);
         HIP_TRY(hipMemcpyAsync(al.data(), h->cg_alpha2.p, G * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(out_subcentroid_idxs + p0, h->cg_sub.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(out_codes + p0 * M, h->e_codes.p, m * M, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(out_norm_codes + p0, h->e_ncodes.p, m, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(out_subcentroid_idxs + p0, h->cg_sub.p, m * sizeof(uint32_t), out, h->stream));
+        HIP_TRY(hipMemcpyAsync(out_codes + p0 * M, h->e_codes.p, m * M, out, h->stream));
+        if (out_norm_codes)
+            HIP_TRY(hipMemcpyAsync(out_norm_codes + p0, h->e_ncodes.p, m, out, h->stream));
+        if (stage) { // the codes stay in HBM on their way into the lists
+            HIP_TRY(launch_groups_point_lists(h->stream, doff, cidx, G, h->ap_idx.as<uint32_t>() + p0));
+            HIP_TRY(hipMemcpyAsync(h->gp_sub.as<uint32_t>() + p0, h->cg_sub.p, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->ap_codes.as<uint8_t>() + p0 * M, h->e_codes.p, m * M, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->ap_ncodes.as<uint8_t>() + p0, h->e_ncodes.p, m, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->ga_alpha.as<float>() + g0, h->cg_alpha2.p, G * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        }
         HIP_TRY(hipStreamSynchronize(h->stream));
+        std::vector<float> cur(G); // an empty group keeps the caller's alpha
+        if (dev)
+            HIP_TRY(hipMemcpy(cur.data(), out_alphas + g0, G * sizeof(float), hipMemcpyDeviceToHost));
+        float *dst = dev ? cur.data() : out_alphas + g0;
         for (size_t g = 0; g < G; g++)
             if (off[g + 1] > off[g])
-                out_alphas[g0 + g] = al[g];
+                dst[g] = al[g];
+        if (dev)
+            HIP_TRY(hipMemcpy(out_alphas + g0, cur.data(), G * sizeof(float), hipMemcpyHostToDevice));
         g0 = g1;
     }
     return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_encode_groups(ivfhnsw_gpu *h, size_t ngroups, size_t nsubc, const uint32_t *centroid_idx,
+                              const uint64_t *offsets, const float *x, size_t efSearch, uint32_t *out_nn_centroid_idxs,
+                              float *out_alphas, uint32_t *out_subcentroid_idxs, uint8_t *out_codes,
+                              uint8_t *out_norm_codes)
+try {
+    return encode_groups_impl(h, ngroups, nsubc, centroid_idx, offsets, x, efSearch, out_nn_centroid_idxs, out_alphas,
+                              out_subcentroid_idxs, out_codes, out_norm_codes, false, false);
 } catch (const std::bad_alloc &) {
     return fail(IVFHNSW_ERR_NOMEM, "ivfhnsw_gpu_encode_groups: host allocation failed");
 }
@@ -1745,6 +1806,404 @@ int ivfhnsw_gpu_add_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32
                         const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes)
 {
     return add_impl(h, n, d_x, d_precomputed_idx, efSearch, d_ids, d_out_idx, d_out_codes, d_out_norm_codes, true, "add_dev");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// additions to a Grouping index: codes at the ends of sub-groups, and whole groups into empty lists
+static int grouping_append_state(ivfhnsw_gpu *h, const char *who)
+{
+    if (h && h->is_view)
+        return fail(IVFHNSW_ERR_STATE, "%s: appends go to the handle that holds the tables, not to a view of it", who);
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_ivf", who);
+    if (!h->has_group)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle holds no grouping tables (IVFADC lists grow by append_ivf)", who);
+    return IVFHNSW_OK;
+}
+
+// the device buffers grouping_dedupe_dev can need, sized for its largest sample, so that it allocates nothing itself
+static int grouping_dedupe_reserve(ivfhnsw_gpu *h)
+{
+    const size_t nc = h->t.nc, nsubc = (size_t)h->g.nsubc;
+    const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
+    const size_t rows = ((nc + step - 1) / step) * (1 + take);
+    int rc;
+    if ((rc = h->gp_rows.ensure(rows * sizeof(uint32_t))) || (rc = h->gp_gather.ensure(2 * rows * nsubc * sizeof(uint32_t))))
+        return rc;
+    return IVFHNSW_OK;
+}
+
+// grouping_dedupe on the tables in HBM: only the rows it samples (about 512 groups and 15 neighbours of each) come to
+// the host, not the two [nc * nsubc] tables
+static int grouping_dedupe_dev(ivfhnsw_gpu *h, const uint32_t *d_sizes, const uint32_t *d_nn, int *dedupe)
+{
+    const size_t nc = h->t.nc, nsubc = (size_t)h->g.nsubc;
+    const size_t take = std::min<size_t>(15, nsubc), step = std::max<size_t>(1, nc / 512);
+    std::vector<uint32_t> want, szs, nns;
+    std::unordered_map<uint32_t, size_t> at;
+    int rc;
+    auto fetch = [&](size_t first) -> int { // rows want[first ..] of both tables behind the ones already here
+        const size_t m = want.size() - first;
+        if (m == 0)
+            return IVFHNSW_OK;
+        if ((rc = h->gp_rows.ensure(m * sizeof(uint32_t))) || (rc = h->gp_gather.ensure(2 * m * nsubc * sizeof(uint32_t))))
+            return rc;
+        uint32_t *g = h->gp_gather.as<uint32_t>();
+        HIP_TRY(hipMemcpyAsync(h->gp_rows.p, want.data() + first, m * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(launch_gather_rows(h->stream, d_sizes, h->gp_rows.as<uint32_t>(), m, (uint32_t)nsubc, g));
+        HIP_TRY(launch_gather_rows(h->stream, d_nn, h->gp_rows.as<uint32_t>(), m, (uint32_t)nsubc, g + m * nsubc));
+        szs.resize(want.size() * nsubc);
+        nns.resize(want.size() * nsubc);
+        HIP_TRY(hipMemcpyAsync(szs.data() + first * nsubc, g, m * nsubc * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(nns.data() + first * nsubc, g + m * nsubc, m * nsubc * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return IVFHNSW_OK;
+    };
+    auto need = [&](uint32_t c) {
+        if (at.emplace(c, want.size()).second)
+            want.push_back(c);
+    };
+    for (size_t c = 0; c < nc; c += step)
+        need((uint32_t)c);
+    if ((rc = fetch(0)))
+        return rc;
+    const size_t sampled = want.size();
+    for (size_t i = 0; i < sampled; i++)
+        for (size_t j = 0; j < take; j++)
+            if (nns[i * nsubc + j] < nc)
+                need(nns[i * nsubc + j]);
+    if ((rc = fetch(sampled)))
+        return rc;
+    *dedupe = grouping_dedupe_rows(nc, nsubc, [&](size_t c) { return szs.data() + at.at((uint32_t)c) * nsubc; },
+                                   [&](size_t c) { return nns.data() + at.at((uint32_t)c) * nsubc; });
+    return IVFHNSW_OK;
+}
+
+// the table rows add_groups installs with its codes: ga_cidx / ga_off / ga_nn / ga_alpha hold them, inter null = computed
+struct GroupRows {
+    size_t ngroups;
+    const float *d_inter;
+};
+
+// d_list / d_sub [n] (checked here, on the device, before anything changes), d_ids [n], d_codes [n][M] (dword aligned),
+// d_ncodes [n]: device memory, read on the handle's stream.  rows: the groups whose table rows go in with the batch (n may
+// be 0 then).  Returns with the stream drained.  Bad ids and every device allocation (the dedupe sample's included) come
+// before the first table row is written, so those errors leave the handle's tables the ones it had; behind that point
+// only a failing launch or copy (a lost device) can stop the call.
+static int grouping_append_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list, const uint32_t *d_sub,
+                                const uint32_t *d_ids, const uint8_t *d_codes, const uint8_t *d_ncodes, const GroupRows *rows)
+try {
+    const size_t nc = h->t.nc, len = nc + 1, nsubc = (size_t)h->g.nsubc, nsub = nc * nsubc;
+    int rc;
+    auto write_rows = [&]() -> hipError_t {
+        if (!rows)
+            return hipSuccess;
+        return launch_groups_rows(h->stream, h->ga_cidx.as<uint32_t>(), h->ga_off.as<unsigned long long>(),
+                                  h->ga_nn.as<uint32_t>(), h->ga_alpha.as<float>(), rows->d_inter, h->gr.vectors, h->t.d,
+                                  (uint32_t)nsubc, rows->ngroups, h->g_nn.as<uint32_t>(), h->g_alpha.as<float>(),
+                                  h->g_inter.as<float>());
+    };
+    int dedupe = h->g.dedupe;
+    if ((rc = grouping_dedupe_reserve(h)))
+        return rc;
+    if (n == 0) { // neighbour rows of empty groups only
+        HIP_TRY(write_rows());
+        if ((rc = grouping_dedupe_dev(h, h->g.sub_sizes, h->g.nn_idx, &dedupe)))
+            return rc;
+        h->g.dedupe = dedupe;
+        return IVFHNSW_OK;
+    }
+    if ((rc = h->ap_cnt.ensure(len * sizeof(uint32_t))) || (rc = h->ap_own.ensure(len * sizeof(uint32_t))) ||
+        (rc = h->ap_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) || (rc = h->ap_status.ensure(sizeof(uint32_t))) ||
+        (rc = h->gp_sizes.ensure(nsub * sizeof(uint32_t))))
+        return rc;
+    uint32_t *cnt = h->ap_cnt.as<uint32_t>(), *own = h->ap_own.as<uint32_t>(), *status = h->ap_status.as<uint32_t>();
+    uint32_t *sizes2 = h->gp_sizes.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(cnt, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemcpyAsync(sizes2, h->g.sub_sizes, nsub * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(launch_grouping_count(h->stream, d_list, d_sub, n, (uint32_t)nc, (uint32_t)nsubc, cnt, sizes2, status));
+    HIP_TRY(launch_append_tables(h->stream, h->t, cnt, own, h->ap_part.as<uint32_t>()));
+    uint32_t st = 0, total = 0;
+    HIP_TRY(hipMemcpyAsync(&st, status, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&total, own + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (st)
+        return fail(IVFHNSW_ERR_INVALID, "append_grouping: a list id is >= nc = %zu or a sub-group id >= nsubc = %zu", nc, nsubc);
+    const uint64_t n_local2 = total;
+    const size_t nblocks = (n + kKmeansTile - 1) / kKmeansTile;
+    if ((rc = h->ap_perm.ensure(n * sizeof(uint32_t))) || (rc = h->ap_perm2.ensure(n * sizeof(uint32_t))) ||
+        (rc = h->ap_hist.ensure(256 * nblocks * sizeof(uint32_t))) ||
+        (rc = h->ap_tiles.ensure((n_local2 / kAppendTileRows + 2) * sizeof(uint32_t))) ||
+        (rc = h->gp_pre_old.ensure(nsub * sizeof(uint32_t))) || (rc = h->gp_pre_new.ensure(nsub * sizeof(uint32_t))))
+        return rc;
+    // the new arrays first: the old ones stay the handle's until the new ones are complete
+    DevBuf goff2, loff2, codes2, ncodes2, ids2;
+    DevBuf *fresh[] = {&goff2, &loff2, &codes2, &ncodes2, &ids2};
+    auto drop = [&] {
+        for (auto *b : fresh)
+            b->release();
+    };
+    if ((rc = goff2.ensure(len * sizeof(uint64_t))) || (rc = loff2.ensure(nc * sizeof(uint32_t))) ||
+        (rc = codes2.ensure(n_local2 * h->t.M)) || (rc = ncodes2.ensure(n_local2)) ||
+        (rc = ids2.ensure(n_local2 * sizeof(uint32_t)))) {
+        drop();
+        return rc;
+    }
+    auto bits_of = [](size_t top) {
+        int b = 1;
+        while (b < 32 && top >> b)
+            b++;
+        return b;
+    };
+    // stable order by (list, sub-group): by sub-group first, then from that order by list
+    uint32_t *perm = nullptr;
+    const uint32_t *nstart = cnt, *lstart = own; // scanned in place by launch_append_tables
+    const uint32_t *pre_old = h->gp_pre_old.as<uint32_t>(), *pre_new = h->gp_pre_new.as<uint32_t>();
+    uint32_t *pa = h->ap_perm.as<uint32_t>(), *pb = h->ap_perm2.as<uint32_t>(), *hist = h->ap_hist.as<uint32_t>();
+    hipError_t e = write_rows();
+    if (e == hipSuccess)
+        e = launch_sort_by_key(h->stream, d_sub, n, bits_of(nsubc - 1), pa, pb, hist, &perm);
+    if (e == hipSuccess)
+        e = launch_sort_by_key_from(h->stream, d_list, n, bits_of(nc - 1), perm, pa, pb, hist, &perm);
+    if (e == hipSuccess)
+        e = launch_append_layout(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), goff2.as<uint64_t>(),
+                                 loff2.as<uint32_t>(), n_local2);
+    if (e == hipSuccess)
+        e = launch_grouping_prefix(h->stream, nstart, h->g.sub_sizes, sizes2, h->gp_pre_old.as<uint32_t>(),
+                                   h->gp_pre_new.as<uint32_t>(), (uint32_t)nc, (uint32_t)nsubc);
+    if (e == hipSuccess)
+        e = launch_grouping_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), pre_old, pre_new,
+                                  (uint32_t)nsubc, codes2.as<uint8_t>(), ncodes2.as<uint8_t>(), ids2.as<uint32_t>(), n_local2);
+    if (e == hipSuccess)
+        e = launch_grouping_scatter(h->stream, h->t, perm, d_list, d_sub, n, nstart, lstart, h->g.sub_sizes, pre_old,
+                                    (uint32_t)nsubc, d_codes, d_ncodes, d_ids, codes2.as<uint8_t>(), ncodes2.as<uint8_t>(),
+                                    ids2.as<uint32_t>());
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        drop();
+        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append_grouping: %s", hipGetErrorString(e));
+    }
+    // the choice upload_grouping derives from the sizes and the neighbour rows follows the new ones
+    if ((rc = grouping_dedupe_dev(h, sizes2, h->g.nn_idx, &dedupe))) {
+        drop();
+        return rc;
+    }
+    std::swap(h->goff, goff2);
+    std::swap(h->loff, loff2);
+    std::swap(h->codes, codes2);
+    std::swap(h->ncodes, ncodes2);
+    std::swap(h->ids, ids2);
+    drop(); // the old arrays
+    h->t.goff = h->goff.as<uint64_t>();
+    h->t.loff = h->loff.as<uint32_t>();
+    h->t.codes = h->codes.as<uint8_t>();
+    h->t.norm_codes = h->ncodes.as<uint8_t>();
+    h->t.ids = h->ids.as<uint32_t>();
+    h->n_local = n_local2;
+    std::swap(h->g_sizes, h->gp_sizes); // the staging that holds the new sizes becomes the table
+    h->g.sub_sizes = h->g_sizes.as<uint32_t>();
+    h->g.dedupe = dedupe;
+    return IVFHNSW_OK;
+} catch (const std::bad_alloc &) {
+    return fail(IVFHNSW_ERR_NOMEM, "append_grouping: host allocation failed");
+}
+
+int ivfhnsw_gpu_append_grouping(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *sub_idx,
+                                const uint32_t *ids, const uint8_t *codes, const uint8_t *norm_codes)
+{
+    int rc = grouping_append_state(h, "append_grouping");
+    if (rc || n == 0)
+        return rc;
+    if (!list_idx || !sub_idx || !ids || !codes || !norm_codes)
+        return fail(IVFHNSW_ERR_INVALID, "append_grouping: null buffer");
+    if ((rc = append_size(h, n, "append_grouping")))
+        return rc;
+    for (size_t i = 0; i < n; i++)
+        if (list_idx[i] >= h->t.nc || sub_idx[i] >= (uint32_t)h->g.nsubc)
+            return fail(IVFHNSW_ERR_INVALID, "append_grouping: (list_idx, sub_idx)[%zu] = (%u, %u), nc = %u, nsubc = %d", i,
+                        list_idx[i], sub_idx[i], h->t.nc, h->g.nsubc);
+    if ((rc = append_stage(h, n)) || (rc = h->gp_sub.ensure(n * sizeof(uint32_t))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->ap_idx.p, list_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->gp_sub.p, sub_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_codes.p, codes, n * h->t.M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ncodes.p, norm_codes, n, hipMemcpyHostToDevice, h->stream));
+    return grouping_append_core(h, n, h->ap_idx.as<uint32_t>(), h->gp_sub.as<uint32_t>(), h->ap_ids.as<uint32_t>(),
+                                h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>(), nullptr);
+}
+
+int ivfhnsw_gpu_append_grouping_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_sub_idx,
+                                    const uint32_t *d_ids, const uint8_t *d_codes, const uint8_t *d_norm_codes)
+{
+    int rc = grouping_append_state(h, "append_grouping_dev");
+    if (rc || n == 0)
+        return rc;
+    if (!d_list_idx || !d_sub_idx || !d_ids || !d_codes || !d_norm_codes)
+        return fail(IVFHNSW_ERR_INVALID, "append_grouping_dev: null buffer");
+    if (((uintptr_t)d_list_idx | (uintptr_t)d_sub_idx | (uintptr_t)d_ids | (uintptr_t)d_codes) & 3)
+        return fail(IVFHNSW_ERR_INVALID, "append_grouping_dev: list_idx, sub_idx, ids and codes must be 4-byte aligned");
+    if ((rc = append_size(h, n, "append_grouping_dev")))
+        return rc;
+    return grouping_append_core(h, n, d_list_idx, d_sub_idx, d_ids, d_codes, d_norm_codes, nullptr);
+}
+
+// encode_groups into the staging, the checks that need the handle's lists, then one append with the groups' table rows
+static int add_groups_impl(ivfhnsw_gpu *h, size_t ngroups, const uint32_t *centroid_idx_in, const uint64_t *offsets_in,
+                           const float *x, size_t efSearch, const uint32_t *ids, const float *inter, uint32_t *out_nn,
+                           float *out_alphas, uint32_t *out_sub, uint8_t *out_codes, uint8_t *out_norm_codes, bool dev,
+                           const char *who)
+try {
+    int rc = grouping_append_state(h, who);
+    if (rc)
+        return rc;
+    if (!h->has_codebooks || !h->has_graph)
+        return fail(IVFHNSW_ERR_STATE, "%s needs upload_codebooks and upload_quantizer", who);
+    if (h->gr.n != h->t.nc || h->gr.d != h->t.d)
+        return fail(IVFHNSW_ERR_STATE, "%s: the quantizer holds %u x %d, the index %u lists of d = %d", who, h->gr.n,
+                    h->gr.d, h->t.nc, h->t.d);
+    if (h->e_d != (size_t)h->t.d || h->e_M != (size_t)h->t.M || h->e_opq != (h->t.opq_At != nullptr))
+        return fail(IVFHNSW_ERR_INVALID, "%s: code books (d %zu, code_size %zu, %s OPQ) do not match the index (d %d, "
+                    "code_size %d, %s OPQ)", who, h->e_d, h->e_M, h->e_opq ? "with" : "no", h->t.d, h->t.M,
+                    h->t.opq_At ? "with" : "no");
+    if (ngroups == 0)
+        return IVFHNSW_OK;
+    if (!centroid_idx_in || !offsets_in || !out_nn || !out_alphas)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null buffer", who);
+    const size_t nc = h->t.nc, nsubc = (size_t)h->g.nsubc;
+    // the groups' ids and point offsets steer the chunking on the host: the _dev form brings them over first
+    std::vector<uint32_t> cidx_h;
+    std::vector<uint64_t> off_h;
+    const uint32_t *centroid_idx = centroid_idx_in;
+    const uint64_t *offsets = offsets_in;
+    if (dev) {
+        if (((uintptr_t)centroid_idx_in | (uintptr_t)x | (uintptr_t)ids | (uintptr_t)inter | (uintptr_t)out_nn |
+             (uintptr_t)out_alphas | (uintptr_t)out_sub | (uintptr_t)out_codes) & 3 || (uintptr_t)offsets_in & 7)
+            return fail(IVFHNSW_ERR_INVALID, "%s: device pointers must be 4-byte aligned (offsets 8-byte)", who);
+        cidx_h.resize(ngroups);
+        off_h.resize(ngroups + 1);
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(cidx_h.data(), centroid_idx_in, ngroups * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(off_h.data(), offsets_in, (ngroups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        centroid_idx = cidx_h.data();
+        offsets = off_h.data();
+    }
+    if (offsets[0] != 0)
+        return fail(IVFHNSW_ERR_INVALID, "%s: offsets[0] must be 0", who);
+    for (size_t g = 0; g < ngroups; g++) {
+        if (offsets[g + 1] < offsets[g])
+            return fail(IVFHNSW_ERR_INVALID, "%s: offsets not monotone at group %zu", who, g);
+        if (centroid_idx[g] >= nc)
+            return fail(IVFHNSW_ERR_INVALID, "%s: centroid_idx[%zu] = %u, nc = %zu", who, g, centroid_idx[g], nc);
+    }
+    {
+        std::vector<uint32_t> sorted(centroid_idx, centroid_idx + ngroups);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end())
+            return fail(IVFHNSW_ERR_INVALID, "%s: centroid %u appears twice in one call", who, *dup);
+    }
+    const size_t n = offsets[ngroups];
+    if (n && (!ids || !x))
+        return fail(IVFHNSW_ERR_INVALID, "%s: null buffer", who);
+    if ((rc = append_size(h, n, who)))
+        return rc;
+    if ((rc = h->ga_cidx.ensure(ngroups * sizeof(uint32_t))) || (rc = h->ga_off.ensure((ngroups + 1) * sizeof(uint64_t))) ||
+        (rc = h->ga_nn.ensure(ngroups * nsubc * sizeof(uint32_t))) || (rc = h->ga_alpha.ensure(ngroups * sizeof(float))) ||
+        (rc = h->ga_status.ensure(sizeof(uint32_t))) || (rc = append_stage(h, n)) || (rc = h->gp_sub.ensure(n * sizeof(uint32_t))) ||
+        (inter && !dev && (rc = h->ga_inter.ensure(ngroups * nsubc * sizeof(float)))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->ga_cidx.p, centroid_idx, ngroups * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ga_off.p, offsets, (ngroups + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    // a group that holds codes cannot be added to: its alpha and neighbours would be overwritten under them
+    uint32_t first = 0xffffffffu;
+    HIP_TRY(hipMemsetAsync(h->ga_status.p, 0xff, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_groups_empty(h->stream, h->t.goff, h->ga_cidx.as<uint32_t>(), ngroups, (uint32_t)nc, h->ga_status.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(&first, h->ga_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (first != 0xffffffffu)
+        return fail(IVFHNSW_ERR_STATE, "%s: list %u (group %u of the call) already holds codes; a second add_group on a "
+                    "centroid has no counterpart in a search (remove its ids first)", who, centroid_idx[first], first);
+    const float *d_inter = nullptr;
+    if (inter && dev) {
+        d_inter = inter;
+    } else if (inter) {
+        HIP_TRY(hipMemcpyAsync(h->ga_inter.p, inter, ngroups * nsubc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        d_inter = h->ga_inter.as<float>();
+    }
+    if ((rc = encode_groups_impl(h, ngroups, nsubc, centroid_idx, offsets, x, efSearch, out_nn, out_alphas, out_sub, out_codes,
+                                 out_norm_codes, dev, true)))
+        return rc;
+    if (n)
+        HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               h->stream));
+    const GroupRows rows{ngroups, d_inter};
+    return grouping_append_core(h, n, h->ap_idx.as<uint32_t>(), h->gp_sub.as<uint32_t>(), h->ap_ids.as<uint32_t>(),
+                                h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>(), &rows);
+} catch (const std::bad_alloc &) {
+    return fail(IVFHNSW_ERR_NOMEM, "%s: host allocation failed", who);
+}
+
+int ivfhnsw_gpu_add_groups(ivfhnsw_gpu *h, size_t ngroups, const uint32_t *centroid_idx, const uint64_t *offsets, const float *x,
+                           size_t efSearch, const uint32_t *ids, const float *inter_centroid_dists,
+                           uint32_t *out_nn_centroid_idxs, float *out_alphas, uint32_t *out_subcentroid_idxs, uint8_t *out_codes,
+                           uint8_t *out_norm_codes)
+{
+    return add_groups_impl(h, ngroups, centroid_idx, offsets, x, efSearch, ids, inter_centroid_dists, out_nn_centroid_idxs,
+                           out_alphas, out_subcentroid_idxs, out_codes, out_norm_codes, false, "add_groups");
+}
+
+int ivfhnsw_gpu_add_groups_dev(ivfhnsw_gpu *h, size_t ngroups, const uint32_t *d_centroid_idx, const uint64_t *d_offsets,
+                               const float *d_x, size_t efSearch, const uint32_t *d_ids, const float *d_inter_centroid_dists,
+                               uint32_t *d_out_nn_centroid_idxs, float *d_out_alphas, uint32_t *d_out_subcentroid_idxs,
+                               uint8_t *d_out_codes, uint8_t *d_out_norm_codes)
+{
+    return add_groups_impl(h, ngroups, d_centroid_idx, d_offsets, d_x, efSearch, d_ids, d_inter_centroid_dists,
+                           d_out_nn_centroid_idxs, d_out_alphas, d_out_subcentroid_idxs, d_out_codes, d_out_norm_codes, true,
+                           "add_groups_dev");
+}
+
+int ivfhnsw_gpu_download_grouping_tables(ivfhnsw_gpu *h, float *alphas, uint32_t *nn_centroid_idxs, uint32_t *subgroup_sizes,
+                                         float *inter_centroid_dists)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_group)
+        return fail(IVFHNSW_ERR_STATE, "download_grouping_tables: the handle holds no grouping tables");
+    const size_t nc = h->t.nc, nsub = nc * (size_t)h->g.nsubc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (alphas)
+        HIP_TRY(hipMemcpy(alphas, h->g.alphas, nc * sizeof(float), hipMemcpyDeviceToHost));
+    if (nn_centroid_idxs)
+        HIP_TRY(hipMemcpy(nn_centroid_idxs, h->g.nn_idx, nsub * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (subgroup_sizes)
+        HIP_TRY(hipMemcpy(subgroup_sizes, h->g.sub_sizes, nsub * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (inter_centroid_dists)
+        HIP_TRY(hipMemcpy(inter_centroid_dists, h->g.inter_dists, nsub * sizeof(float), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_upload_centroid_norms(ivfhnsw_gpu *h, const float *centroid_norms)
+{
+    if (h && h->is_view)
+        return fail(IVFHNSW_ERR_STATE, "uploads go to the handle that holds the tables, not to a view of it");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "upload_centroid_norms before upload_ivf");
+    if (!centroid_norms)
+        return fail(IVFHNSW_ERR_INVALID, "upload_centroid_norms: null buffer");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->cnorm.p, centroid_norms, (size_t)h->t.nc * sizeof(float), hipMemcpyHostToDevice));
+    return IVFHNSW_OK;
 }
 
 int ivfhnsw_gpu_download_ivf(ivfhnsw_gpu *h, uint64_t *offsets, uint32_t *ids, uint8_t *codes, uint8_t *norm_codes)
@@ -3007,7 +3466,8 @@ int ivfhnsw_gpu_memory_bytes(ivfhnsw_gpu *h, uint64_t *bytes)
                            &h->km_hist, &h->km_part, &h->km_status, &h->km_pairs, &h->ap_idx, &h->ap_ids, &h->ap_codes,
                            &h->ap_ncodes, &h->ap_cnt, &h->ap_own, &h->ap_part, &h->ap_status, &h->ap_perm, &h->ap_perm2,
                            &h->ap_hist, &h->ap_tiles, &h->rm_labels, &h->rm_bits, &h->rm_mask, &h->rm_keep, &h->rm_rem,
-                           &h->rm_out, &h->rm_part, &h->rm_status, &h->rm_sizes};
+                           &h->rm_out, &h->rm_part, &h->rm_status, &h->rm_sizes, &h->gp_sub, &h->gp_sizes, &h->gp_pre_old, &h->gp_pre_new, &h->gp_rows,
+                           &h->gp_gather, &h->ga_cidx, &h->ga_off, &h->ga_nn, &h->ga_alpha, &h->ga_inter, &h->ga_status};
     uint64_t s = 0;
     for (auto *b : all)
         s += b->bytes;

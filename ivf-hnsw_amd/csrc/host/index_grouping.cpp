@@ -44,6 +44,12 @@ IndexIVF_HNSW_Grouping::IndexIVF_HNSW_Grouping(size_t dim, size_t ncentroids, si
 void IndexIVF_HNSW_Grouping::sync_to_device()
 {
     device_upload_common();
+    upload_grouping_tables();
+    device_dirty_ = false;
+}
+
+void IndexIVF_HNSW_Grouping::upload_grouping_tables()
+{
     // [nc][nsubc] row-major tables; groups without codes have empty vectors on the host -> zero rows
     std::vector<float> icd(nc * nsubc, 0.f);
     std::vector<uint32_t> nn(nc * nsubc, 0), sz(nc * nsubc, 0);
@@ -59,7 +65,6 @@ void IndexIVF_HNSW_Grouping::sync_to_device()
     for (size_t r = 0; r < nshards(); r++)
         if (ivfhnsw_gpu_upload_grouping(shard(r), nsubc, alphas.data(), nn.data(), sz.data(), icd.data()))
             throw std::runtime_error(std::string("ivfhnsw_gpu_upload_grouping: ") + ivfhnsw_gpu_last_error());
-    device_dirty_ = false;
 }
 
 void IndexIVF_HNSW_Grouping::search_batch(size_t nq, size_t k, const float *x, float *distances, long *labels)
@@ -151,13 +156,26 @@ void IndexIVF_HNSW_Grouping::read(const char *path_index)
 
 void IndexIVF_HNSW_Grouping::compute_inter_centroid_dists()
 {
+    // lists current on the device: a pass that changed no bit of what the device holds (a row the host did not have
+    // went up as zeros) dirties nothing, one that did re-sends the grouping tables alone
+    const bool current = device_current();
+    bool changed = false;
     for (size_t i = 0; i < nc; i++) {
-        inter_centroid_dists[i].resize(nsubc);
+        if (inter_centroid_dists[i].size() != nsubc)
+            inter_centroid_dists[i].assign(nsubc, 0.f);
+        if (nn_centroid_idxs[i].size() != nsubc)
+            continue; // a group add_group has not seen yet has no neighbours to measure: its row stays
         const float *c = quantizer->getDataByInternalId((idx_t)i);
-        for (size_t s = 0; s < nsubc; s++)
-            inter_centroid_dists[i][s] = fvec_L2sqr(quantizer->getDataByInternalId(nn_centroid_idxs[i][s]), c, d);
+        for (size_t s = 0; s < nsubc; s++) {
+            const float v = fvec_L2sqr(quantizer->getDataByInternalId(nn_centroid_idxs[i][s]), c, d);
+            changed |= std::memcmp(&v, &inter_centroid_dists[i][s], sizeof(float)) != 0;
+            inter_centroid_dists[i][s] = v;
+        }
     }
-    device_dirty_ = true;
+    if (!current)
+        device_dirty_ = true;
+    else if (changed)
+        mark_tables_dirty(kTableGrouping);
 }
 
 void IndexIVF_HNSW_Grouping::dump_inter_centroid_dists(char *path)
@@ -185,9 +203,25 @@ void IndexIVF_HNSW_Grouping::add_group(size_t centroid_idx, size_t group_size, c
     std::vector<idx_t> sub(group_size);
     std::vector<uint8_t> xcodes(group_size * code_size), xnorm(group_size);
     float alpha = alphas[centroid_idx];
-    if (ivfhnsw_gpu_encode_groups(gpu_, 1, nsubc, &cidx, off, data, quantizer->efSearch,
-                                  nn_centroid_idxs[centroid_idx].data(), &alpha, sub.data(), xcodes.data(), xnorm.data()))
+    // A device copy that is current (one handle, nothing ensure_device would re-upload) takes a group that holds no codes
+    // in place: ivfhnsw_gpu_add_groups installs its rows and codes in HBM.  The inter-centroid row is
+    // the one sync_to_device would upload, so both ways give the same bits whenever the caller computes the real one.
+    // Every other case -- the first build, several shards, a second add_group on a centroid -- marks the copy stale.
+    const bool in_place = nshards() == 1 && subgroup_sizes[centroid_idx].empty() && ids[centroid_idx].empty() &&
+                          device_current();
+    if (in_place) {
+        std::vector<float> icd(nsubc, 0.f);
+        if (inter_centroid_dists[centroid_idx].size() == nsubc)
+            icd = inter_centroid_dists[centroid_idx];
+        std::vector<uint32_t> labels(idxs, idxs + group_size);
+        if (ivfhnsw_gpu_add_groups(gpu_, 1, &cidx, off, data, quantizer->efSearch, labels.data(), icd.data(),
+                                   nn_centroid_idxs[centroid_idx].data(), &alpha, sub.data(), xcodes.data(), xnorm.data()))
+            throw std::runtime_error(std::string("ivfhnsw_gpu_add_groups: ") + ivfhnsw_gpu_last_error());
+    } else if (ivfhnsw_gpu_encode_groups(gpu_, 1, nsubc, &cidx, off, data, quantizer->efSearch,
+                                         nn_centroid_idxs[centroid_idx].data(), &alpha, sub.data(), xcodes.data(),
+                                         xnorm.data())) {
         throw std::runtime_error(std::string("ivfhnsw_gpu_encode_groups: ") + ivfhnsw_gpu_last_error());
+    }
     if (group_size == 0)
         return; // :63-64: neighbours recorded, nothing else
     alphas[centroid_idx] = alpha;
@@ -203,7 +237,10 @@ void IndexIVF_HNSW_Grouping::add_group(size_t centroid_idx, size_t group_size, c
             norm_codes[centroid_idx].push_back(xnorm[i]);
         }
     }
-    device_dirty_ = true;
+    if (in_place)
+        device_took(group_size);
+    else
+        device_dirty_ = true;
 }
 
 // train_pq (Grouping.cpp:486-618): residuals against the SUB-centroids of a training sample, then the two code

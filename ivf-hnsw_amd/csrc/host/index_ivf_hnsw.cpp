@@ -53,7 +53,36 @@ void set_base_state(const void *ix, const BaseState &st)
         g_base[ix] = st;
 }
 
+// The finer device state of an index, beside the object for the same reason: which tables a pass
+// changed while the lists on the device stayed current, and how often everything went up as a whole.
+struct DeviceSide {
+    unsigned tables_dirty = 0;
+    size_t full_uploads = 0;
+};
+std::mutex g_side_mu;
+std::unordered_map<const void *, DeviceSide> g_side;
+
 } // namespace
+
+unsigned IndexIVF_HNSW::tables_dirty() const
+{
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    auto it = g_side.find(this);
+    return it == g_side.end() ? 0u : it->second.tables_dirty;
+}
+
+void IndexIVF_HNSW::mark_tables_dirty(unsigned which)
+{
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    g_side[this].tables_dirty |= which;
+}
+
+size_t IndexIVF_HNSW::device_full_uploads() const
+{
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    auto it = g_side.find(this);
+    return it == g_side.end() ? 0 : it->second.full_uploads;
+}
 
 IndexIVF_HNSW::IndexIVF_HNSW(size_t dim, size_t ncentroids, size_t bytes_per_code, size_t nbits_per_idx,
                              size_t max_group_size)
@@ -76,6 +105,10 @@ IndexIVF_HNSW::IndexIVF_HNSW(size_t dim, size_t ncentroids, size_t bytes_per_cod
 IndexIVF_HNSW::~IndexIVF_HNSW()
 {
     set_base_state(this, BaseState());
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        g_side.erase(this);
+    }
     for (ivfhnsw_gpu *sh : shards_)
         ivfhnsw_gpu_destroy(sh);
     if (gpu_)
@@ -162,6 +195,22 @@ void IndexIVF_HNSW::ensure_device()
 {
     if (!device_current())
         sync_to_device();
+    else if (tables_dirty())
+        sync_tables_to_device();
+}
+
+void IndexIVF_HNSW::sync_tables_to_device()
+{
+    const unsigned which = tables_dirty();
+    if (which & kTableGrouping)
+        if (auto *grp = dynamic_cast<IndexIVF_HNSW_Grouping *>(this))
+            grp->upload_grouping_tables(); // legal on the lists already there; the lists and the graph stay
+    if (which & kTableNorms)
+        for (size_t r = 0; r < nshards(); r++)
+            if (ivfhnsw_gpu_upload_centroid_norms(shard(r), centroid_norms.data()))
+                gpu_fail("ivfhnsw_gpu_upload_centroid_norms");
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    g_side[this].tables_dirty = 0;
 }
 
 bool IndexIVF_HNSW::device_current()
@@ -262,6 +311,10 @@ void IndexIVF_HNSW::device_upload_common()
     up_quantizer_ = quantizer;
     up_total_ = total;
     up_do_opq_ = do_opq;
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    DeviceSide &side = g_side[this];
+    side.tables_dirty = 0;
+    side.full_uploads++;
 }
 
 void IndexIVF_HNSW::upload_graph()
@@ -929,9 +982,18 @@ void IndexIVF_HNSW::read(const char *path_index)
 
 void IndexIVF_HNSW::compute_centroid_norms()
 {
-    for (size_t i = 0; i < nc; i++)
-        centroid_norms[i] = faiss::fvec_norm_L2sqr(quantizer->getDataByInternalId((idx_t)i), d);
-    device_dirty_ = true;
+    // lists current on the device: a pass that changed no bit dirties nothing, one that did re-sends the norms alone
+    const bool current = device_current();
+    bool changed = false;
+    for (size_t i = 0; i < nc; i++) {
+        const float v = faiss::fvec_norm_L2sqr(quantizer->getDataByInternalId((idx_t)i), d);
+        changed |= std::memcmp(&v, &centroid_norms[i], sizeof(float)) != 0;
+        centroid_norms[i] = v;
+    }
+    if (!current)
+        device_dirty_ = true;
+    else if (changed)
+        mark_tables_dirty(kTableNorms);
 }
 
 void IndexIVF_HNSW::rotate_quantizer()

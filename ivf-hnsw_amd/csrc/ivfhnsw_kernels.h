@@ -226,6 +226,10 @@ hipError_t launch_kmeans_count(hipStream_t s, const uint32_t *assign, const floa
 hipError_t launch_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, size_t len);
 hipError_t launch_sort_by_key(hipStream_t s, const uint32_t *keys, size_t n, int key_bits, uint32_t *ids_a, uint32_t *ids_b,
                               uint32_t *hist, uint32_t **sorted);
+// the same sort applied to the permutation `start` (ids_a, ids_b or null = the identity): sorting by a minor key and
+// then, from its result, by a major key gives the stable order by (major, minor)
+hipError_t launch_sort_by_key_from(hipStream_t s, const uint32_t *keys, size_t n, int key_bits, const uint32_t *start,
+                                   uint32_t *ids_a, uint32_t *ids_b, uint32_t *hist, uint32_t **sorted);
 hipError_t launch_kmeans_means(hipStream_t s, const float *x, size_t n, const uint32_t *members, const uint32_t *start,
                                const uint32_t *cnt, float *c, size_t nc, int d);
 hipError_t launch_kmeans_split(hipStream_t s, float *c, const uint32_t *pairs, size_t npairs, int d);
@@ -275,6 +279,9 @@ hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t
 hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
                                  const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
                                  const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2);
+// the first half of merge alone (goff2 / loff2 and tile_first), for a caller with a merge kernel of its own
+hipError_t launch_append_layout(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                                uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint64_t n_local2);
 // exclusive scan of a [len] in place with the scan above; part: append_scan_parts(len) words
 hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part);
 // removal by label from an unsharded handle (kernels_remove.hip).  max: atomicMax of the labels into
@@ -292,6 +299,36 @@ hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigne
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
                                  const uint32_t *rscan, const uint32_t *kscan, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2,
                                  uint8_t *ncodes2, uint32_t *ids2, uint64_t n_local2);
+// additions to a Grouping index (kernels_add_groups.hip).  count: cnt[list] += 1 and sizes2[list][sub] += 1
+// (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  prefix, after launch_append_tables:
+// pre_old / pre_new [nc * nsubc] = exclusive prefix sums of sizes / sizes2 inside every list the batch touches.  merge,
+// after launch_append_layout: the old rows into the new arrays.  scatter: the batch's rows (perm = the ids sorted stably by
+// (list, sub-group)) behind the old rows of their sub-groups; runs after merge.
+hipError_t launch_grouping_count(hipStream_t s, const uint32_t *list_idx, const uint32_t *sub_idx, size_t n, uint32_t nc,
+                                 uint32_t nsubc, uint32_t *cnt, uint32_t *sizes2, uint32_t *status);
+hipError_t launch_grouping_prefix(hipStream_t s, const uint32_t *nstart, const uint32_t *sizes, const uint32_t *sizes2,
+                                  uint32_t *pre_old, uint32_t *pre_new, uint32_t nc, uint32_t nsubc);
+hipError_t launch_grouping_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                                 const uint32_t *tile_first, const uint32_t *pre_old,
+                                 const uint32_t *pre_new, uint32_t nsubc, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2,
+                                 uint64_t n_local2);
+hipError_t launch_grouping_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx,
+                                   const uint32_t *sub_idx, size_t n, const uint32_t *nstart, const uint32_t *lstart,
+                                   const uint32_t *sizes, const uint32_t *pre_old, uint32_t nsubc, const uint8_t *codes,
+                                   const uint8_t *norm_codes, const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2,
+                                   uint32_t *ids2);
+// add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
+// the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --
+// for groups with points); out[i] = table[rows[i]] for rows of nsubc words
+hipError_t launch_groups_empty(hipStream_t s, const uint64_t *goff, const uint32_t *cidx, size_t ngroups, uint32_t nc,
+                               uint32_t *status);
+hipError_t launch_groups_point_lists(hipStream_t s, const unsigned long long *off, const uint32_t *cidx, size_t G,
+                                     uint32_t *list_idx);
+hipError_t launch_groups_rows(hipStream_t s, const uint32_t *cidx, const unsigned long long *off, const uint32_t *nn_src,
+                              const float *alpha_src, const float *inter_src, const float *vectors, int d, uint32_t nsubc,
+                              size_t G, uint32_t *nn_dst, float *alpha_dst, float *inter_dst);
+hipError_t launch_gather_rows(hipStream_t s, const uint32_t *table, const uint32_t *rows, size_t nrows, uint32_t nsubc,
+                              uint32_t *out);
 // sum of PlanHdr.total / nseg over the batch into out[0], out[1]
 hipError_t launch_plan_totals(hipStream_t s, const PlanHdr *hdr, int nq, unsigned long long *out);
 

@@ -15,15 +15,13 @@
 // address here is dword aligned, and the merge's destination groups are 16-byte aligned (a tile is 2048 rows).
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
+#include "append_tile.h"
 
 namespace ivfhnsw_gpu_impl {
 
 namespace {
 
-constexpr uint32_t kSkip = 0xffffffffu; // a tile row with no old source row (a new code, or past the end)
 constexpr int kScanChunk = 4096;        // elements per workgroup of the three-phase scan
-
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes, dword aligned
 
 __global__ __launch_bounds__(256) void append_count_kernel(const uint32_t *__restrict__ idx, size_t n, uint32_t nc,
                                                            uint32_t *__restrict__ cnt, uint32_t *__restrict__ status)
@@ -125,19 +123,6 @@ __global__ __launch_bounds__(256) void append_offsets_kernel(const uint64_t *__r
         loff2[c] = loff[c] == kNotOwned ? kNotOwned : lstart[c];
 }
 
-// the largest c in [lo, hi] with lstart[c] <= r (lstart[lo] <= r holds)
-__device__ __forceinline__ uint32_t list_of_row(const uint32_t *__restrict__ lstart, uint32_t lo, uint32_t hi, uint32_t r)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (lstart[mid] <= r)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 // tile_first[b] = the list holding row b * kAppendTileRows of the new local arrays; tile_first[ntiles] = nc - 1
 __global__ __launch_bounds__(256) void append_tiles_kernel(const uint32_t *__restrict__ lstart, uint32_t nc, uint32_t ntiles,
                                                            uint32_t *__restrict__ tile_first)
@@ -146,48 +131,6 @@ __global__ __launch_bounds__(256) void append_tiles_kernel(const uint32_t *__res
     if (b > ntiles)
         return;
     tile_first[b] = b == ntiles ? nc - 1 : list_of_row(lstart, 0, nc - 1, b * (uint32_t)kAppendTileRows);
-}
-
-// dst dwords [0, ndw) of the tile from src dword s_src[row] * q + k; 16-byte groups, a group whose four source dwords
-// are consecutive is one dword-aligned 16-byte load
-__device__ __forceinline__ void copy_tile_dwords(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, const uint32_t *s_src,
-                                                 uint32_t ndw, uint32_t q)
-{
-    for (uint32_t e = threadIdx.x * 4; e < ndw; e += 1024) {
-        uint32_t j = e / q, k = e - j * q;
-        size_t s[4];
-        bool ok[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t sr = e + u < ndw ? s_src[j] : kSkip;
-            ok[u] = sr != kSkip;
-            s[u] = (size_t)(ok[u] ? sr : 0u) * q + k;
-            if (++k == q) {
-                k = 0;
-                j++;
-            }
-        }
-        uint32_t v[4];
-        if (ok[0] && ok[1] && ok[2] && ok[3] && s[1] == s[0] + 1 && s[2] == s[0] + 2 && s[3] == s[0] + 3) {
-            const u32x4_a4 w = *reinterpret_cast<const u32x4_a4 *>(src + s[0]);
-            v[0] = w.x;
-            v[1] = w.y;
-            v[2] = w.z;
-            v[3] = w.w;
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                v[u] = ok[u] ? src[s[u]] : 0u;
-        }
-        if (e + 4 <= ndw) {
-            *reinterpret_cast<uint4 *>(dst + e) = make_uint4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (e + u < ndw)
-                    dst[e + u] = v[u];
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void append_merge_kernel(const uint64_t *__restrict__ goff, const uint32_t *__restrict__ loff,
@@ -210,21 +153,7 @@ __global__ __launch_bounds__(256) void append_merge_kernel(const uint64_t *__res
     __syncthreads();
     copy_tile_dwords(codes, codes2 + (size_t)r0 * q, s_src, rows * q, q);
     copy_tile_dwords(ids, ids2 + r0, s_src, rows, 1u);
-    // norm codes: one byte per row, four rows per dword store
-    for (uint32_t e = threadIdx.x * 4; e < rows; e += 1024) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t sr = e + u < rows ? s_src[e + u] : kSkip;
-            w |= (uint32_t)(sr != kSkip ? ncodes[sr] : 0u) << (8 * u);
-        }
-        if (e + 4 <= rows) {
-            *reinterpret_cast<uint32_t *>(ncodes2 + r0 + e) = w;
-        } else {
-            for (uint32_t u = 0; e + u < rows; u++)
-                ncodes2[r0 + e + u] = (uint8_t)(w >> (8 * u));
-        }
-    }
+    copy_tile_norm_codes(ncodes, ncodes2, s_src, r0, rows);
 }
 
 // one thread per dword of the new codes, in sorted order: code p of the sorted batch is input row perm[p]
@@ -299,9 +228,8 @@ hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
-                               uint32_t *ids2, uint64_t n_local2)
+hipError_t launch_append_layout(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                                uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint64_t n_local2)
 {
     const size_t len = (size_t)t.nc + 1;
     hipLaunchKernelGGL(append_offsets_kernel, dim3(blocks_of(len, 256)), dim3(256), 0, s, t.goff, t.loff, nstart, lstart,
@@ -315,8 +243,18 @@ hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t
     const uint32_t ntiles = (uint32_t)blocks_of(n_local2, kAppendTileRows);
     hipLaunchKernelGGL(append_tiles_kernel, dim3(blocks_of((size_t)ntiles + 1, 256)), dim3(256), 0, s, lstart, t.nc, ntiles,
                        tile_first);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+    return hipGetLastError();
+}
+
+hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
+                               uint32_t *ids2, uint64_t n_local2)
+{
+    if (hipError_t e = launch_append_layout(s, t, nstart, lstart, tile_first, goff2, loff2, n_local2); e != hipSuccess)
         return e;
+    if (n_local2 == 0)
+        return hipSuccess;
+    const uint32_t ntiles = (uint32_t)blocks_of(n_local2, kAppendTileRows);
     hipLaunchKernelGGL(append_merge_kernel, dim3(ntiles), dim3(256), 0, s, t.goff, t.loff, lstart, tile_first,
                        reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(codes2),
                        ncodes2, ids2, (uint32_t)n_local2, (uint32_t)(t.M / 4));

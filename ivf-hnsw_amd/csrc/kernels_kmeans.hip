@@ -247,10 +247,16 @@ hipError_t launch_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, siz
 hipError_t launch_sort_by_key(hipStream_t s, const uint32_t *keys, size_t n, int key_bits, uint32_t *ids_a, uint32_t *ids_b,
                               uint32_t *hist, uint32_t **sorted)
 {
+    return launch_sort_by_key_from(s, keys, n, key_bits, nullptr, ids_a, ids_b, hist, sorted);
+}
+
+hipError_t launch_sort_by_key_from(hipStream_t s, const uint32_t *keys, size_t n, int key_bits, const uint32_t *start,
+                                   uint32_t *ids_a, uint32_t *ids_b, uint32_t *hist, uint32_t **sorted)
+{
     const size_t nblocks = (n + kKmeansTile - 1) / kKmeansTile;
     const int passes = key_bits <= 8 ? 1 : (key_bits + 7) / 8;
-    const uint32_t *in = nullptr; // pass 0 reads the identity permutation
-    uint32_t *out = ids_a;
+    const uint32_t *in = start; // null: pass 0 reads the identity permutation
+    uint32_t *out = start == ids_a ? ids_b : ids_a;
     for (int p = 0; p < passes; p++) {
         hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, keys, in, n, 8 * p, hist,
                            (uint32_t)nblocks);
