@@ -1,0 +1,274 @@
+// What the sources of the C ABI (capi_*.cpp) share: error reporting, the growing device / pinned buffers, the handle
+// itself with the one list of its device buffers, and the host helpers more than one subject needs.  Private to the
+// library: not installed, nothing outside csrc/ includes it.  The ABI functions take their C linkage from their
+// declarations in ivfhnsw_hip.h.
+#pragma once
+#include "../../include/ivfhnsw_hip.h"
+#include "ivfhnsw_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace ivfhnsw_gpu_impl {
+
+// records the message ivfhnsw_gpu_last_error returns on this thread; returns code (capi_handle.cpp)
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(expr)                                                                                        \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess)                                                                                \
+            return fail(e_ == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "%s: %s (%s:%d)",   \
+                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                   \
+    } while (0)
+
+// A device allocation that only ever grows.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need)
+    {
+        if (need <= bytes)
+            return IVFHNSW_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, need ? need : 1));
+        bytes = need;
+        return IVFHNSW_OK;
+    }
+    void release()
+    {
+        if (p)
+            (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Pinned, device-visible host memory that only ever grows (the small-batch entry point reads queries and writes
+// results through it: no staging copies on the latency path).
+struct HostBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need)
+    {
+        if (need <= bytes)
+            return IVFHNSW_OK;
+        release();
+        HIP_TRY(hipHostMalloc(&p, need ? need : 1, hipHostMallocDefault));
+        bytes = need;
+        return IVFHNSW_OK;
+    }
+    void release()
+    {
+        if (p)
+            (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+struct StageEvent {
+    int stage;
+    hipEvent_t a, b;
+};
+
+} // namespace ivfhnsw_gpu_impl
+
+using namespace ivfhnsw_gpu_impl;
+
+// Every device buffer of the handle, named ONCE: this list is the handle's DevBuf members, what ivfhnsw_gpu_destroy
+// frees and what ivfhnsw_gpu_memory_bytes sums (ivfhnsw_gpu::for_each_devbuf).  A new feature adds its buffers here and
+// nowhere else.  The pinned HostBufs p_in / p_out are not in it: they are not HBM.
+#define IVFHNSW_GPU_DEVBUFS(X) \
+    X(goff) X(loff) X(cnorm) X(pqc) X(ntab) X(opq_at) X(codes) X(ncodes) X(ids) /* index tables */ \
+    X(g_alpha) X(g_nn) X(g_sizes) X(g_inter) /* Grouping tables */ \
+    X(q_counts) X(q_links) X(q_vectors) X(q_qrows) X(q_nbrows) X(q_nbnorms) X(q_fat) X(q_links_c) /* quantizer */ \
+    X(e_pqc) X(e_ntab) X(e_a) X(e_at) X(e_x) X(e_idx) X(e_dist) X(e_res) X(e_tmp) X(e_codes) X(e_ncodes) /* code books, encode */ \
+    X(t_x) X(t_y) X(t_cb) X(t_assign) X(t_part) X(t_c) /* pq_train, xty */ \
+    X(k_q) X(k_x) X(k_qn) X(k_xn) X(k_part) X(k_ids) X(k_dists) /* knn */ \
+    X(km_x) X(km_c) X(km_assign) X(km_dist) X(km_cnt) X(km_start) X(km_ids) X(km_ids2) X(km_hist) X(km_part) X(km_status) X(km_pairs) /* kmeans */ \
+    X(cg_q) X(cg_cidx) X(cg_ids) X(cg_dists) X(gc_nn) X(cg_cvn) X(cg_tab) X(cg_tab2) X(cg_off) X(cg_alpha2) X(cg_sub) /* add_group */ \
+    X(base_rows) X(base_stage) /* uint8 base of the re-rank, rows permuted (kernels_rerank.hip); a view reads its parent's */ \
+    X(r_q) X(r_cand) X(r_dist) X(r_lab) /* staging of the host-pointer re-rank */ \
+    X(ap_idx) X(ap_ids) X(ap_codes) X(ap_ncodes) X(ap_cnt) X(ap_own) X(ap_part) X(ap_status) X(ap_perm) X(ap_perm2) X(ap_hist) X(ap_tiles) /* append_ivf, add */ \
+    X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
+    X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
+    X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_counter) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
+    X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
+
+struct ivfhnsw_gpu {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    bool is_view = false; // ivfhnsw_gpu_create_view: tables belong to the parent, workspace and stream are its own
+
+#define IVFHNSW_X(name) DevBuf name;
+    IVFHNSW_GPU_DEVBUFS(IVFHNSW_X)
+#undef IVFHNSW_X
+    template <class F> void for_each_devbuf(F &&f)
+    {
+#define IVFHNSW_X(name) f(name);
+        IVFHNSW_GPU_DEVBUFS(IVFHNSW_X)
+#undef IVFHNSW_X
+    }
+    HostBuf p_in, p_out; // pinned: small batches of the host-pointer entry point
+
+    IvfTables t{};
+    bool has_ivf = false;
+    uint64_t n_local = 0;
+    GroupTables g{};
+    bool has_group = false;
+    GraphTables gr{};
+    bool has_graph = false;
+    size_t e_d = 0, e_M = 0;
+    bool e_opq = false, has_codebooks = false;
+    uint64_t base_n = 0;
+    size_t base_d = 0;
+    ivfhnsw_gpu *parent = nullptr;
+
+    // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
+    ivfhnsw_gpu *split_view = nullptr;
+    hipEvent_t split_fork = nullptr, split_join = nullptr;
+    bool last_split = false;
+    uint32_t *status_shared = nullptr; // the internal split view raises its status bits in the PARENT's word (no merge launch)
+    size_t last_parts[2] = {0, 0}; // queries in the two parts of the last search_dev call (second 0 = one part)
+    int split_pm = 0; // permille of a large batch in its first part; 0 = one part (ivfhnsw_gpu_set_batch_split)
+    bool walk_counters_clean = true;  // w_status[1..4] are zero (ivfhnsw_gpu_create clears them, the redo launch's last wavefront restores it)
+    bool visited_zero = false;        // every byte of w_visited is zero (the walk's overflow bitmaps, kernels_hnsw.hip)
+    void *visited_zero_ptr = nullptr; // ... of this allocation
+    size_t visited_zero_bytes = 0;
+    int opt_scan_pipe = -1;      // ivfhnsw_gpu_set_option "scan_pipe"
+    bool lat_defer_redo = false; // host-pointer small batches: the latency walk flags a tie overflow, the call repeats itself
+    bool latency_off = false;    // ... on the throughput walk
+
+    int last_nq = 0, last_max_seg = 0;
+    const char *last_scan_kernel = "";
+    uint32_t *tail_status_out = nullptr; // pinned word the tail kernel copies the status into (host-pointer path)
+    bool tail_wrote_status = false;
+    uint64_t *walk_zero_keys = nullptr; // the tail kernel's meeting words, cleared by the latency walk when it runs
+    uint32_t *walk_zero_done = nullptr;
+    bool walk_zeroed = false;
+    bool last_stream = false; // the last search left a candidate stream (k > 1, heap_order)
+
+    int profiling = 0; // 0 off, 1 every stage, 2 only the scan (an event pair costs ~7 us of stream time)
+    std::vector<StageEvent> pending;
+    std::vector<hipEvent_t> pool;
+    double stage_ms[IVFHNSW_STAGE_COUNT] = {0};
+    uint64_t stage_n[IVFHNSW_STAGE_COUNT] = {0};
+};
+
+namespace ivfhnsw_gpu_impl {
+
+// ---- capi_handle.cpp
+int bind(ivfhnsw_gpu *h);
+int upload(DevBuf &b, const void *src, size_t bytes);
+hipEvent_t take_event(ivfhnsw_gpu *h);
+int drain_events(ivfhnsw_gpu *h);
+// After a stream sync: did any kernel flag something it could not represent?
+int check_status(ivfhnsw_gpu *h);
+
+// the word the kernels of this handle raise status bits in
+inline uint32_t *status_word(ivfhnsw_gpu *h) { return h->status_shared ? h->status_shared : h->w_status.as<uint32_t>(); }
+
+// a view reads its parent's tables: what create_view copies once and a split batch before every call (uploads and
+// in-place updates since the view's creation included)
+void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent);
+
+// The opening of every call that changes the tables a handle holds: not through a view, the device bound and, with
+// need_ivf, lists present ("<who> before upload_ivf").  Each caller adds its own further conditions behind it.
+enum TableChange { kUploads, kAppends, kRemovals }; // kUploads: the message carries no "<who>: "
+int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool need_ivf);
+
+// h->t's pointers to the five list arrays and n_local follow the handle's buffers
+void point_at_lists(ivfhnsw_gpu *h, uint64_t n_local);
+
+// The five arrays that make up the resident lists, built BESIDE the handle's: an in-place update fills a fresh set and
+// installs it when it is complete and the stream has drained, so that on any error the handle's tables are the ones it
+// had.  The destructor frees what was not installed -- after install, the handle's previous arrays.
+struct ListArrays {
+    DevBuf goff, loff, codes, ncodes, ids;
+    ListArrays() = default;
+    ListArrays(const ListArrays &) = delete;
+    ListArrays &operator=(const ListArrays &) = delete;
+    ~ListArrays() { release(); }
+    int allocate(size_t nc, uint64_t n_local, size_t M)
+    {
+        int rc;
+        if ((rc = goff.ensure((nc + 1) * sizeof(uint64_t))) || (rc = loff.ensure(nc * sizeof(uint32_t))) ||
+            (rc = codes.ensure(n_local * M)) || (rc = ncodes.ensure(n_local)) || (rc = ids.ensure(n_local * sizeof(uint32_t))))
+            return rc;
+        return IVFHNSW_OK;
+    }
+    void release()
+    {
+        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids})
+            b->release();
+    }
+    void install(ivfhnsw_gpu *h, uint64_t n_local)
+    {
+        std::swap(h->goff, goff);
+        std::swap(h->loff, loff);
+        std::swap(h->codes, codes);
+        std::swap(h->ncodes, ncodes);
+        std::swap(h->ids, ids);
+        release(); // the old arrays
+        point_at_lists(h, n_local);
+    }
+};
+
+struct StageScope {
+    ivfhnsw_gpu *h;
+    StageEvent ev{};
+    bool on;
+    StageScope(ivfhnsw_gpu *h_, int stage)
+        : h(h_), on(h_->profiling == 1 || (h_->profiling == 2 && stage == IVFHNSW_STAGE_SCAN))
+    {
+        if (!on)
+            return;
+        ev.stage = stage;
+        ev.a = take_event(h);
+        ev.b = take_event(h);
+        (void)hipEventRecord(ev.a, h->stream);
+    }
+    ~StageScope()
+    {
+        if (!on)
+            return;
+        (void)hipEventRecord(ev.b, h->stream);
+        h->pending.push_back(ev);
+    }
+};
+
+// candidate-stream entries per query kept for the heap-order replay (k > 1)
+constexpr uint32_t kHeapStreamCap = 8192;
+
+constexpr int kSplitAuto = 1000; // the first part's share follows the call's walk : table + plan + scan estimate
+
+// Batches beyond kMaxBatch queries are processed in slices so that the per-batch workspace (16 KB of table per
+// query at PQ16, plus the plan) stays bounded; the multi-GPU resolve step needs the whole plan, so it is limited
+// to one slice.
+constexpr size_t kMaxBatchAll = 1 << 17;
+
+// ---- capi_upload.cpp
+int grouping_dedupe_reserve(ivfhnsw_gpu *h);
+int grouping_dedupe_dev(ivfhnsw_gpu *h, const uint32_t *d_sizes, const uint32_t *d_nn, int *dedupe);
+
+// ---- capi_build.cpp
+int encode_rows(ivfhnsw_gpu *h, size_t m, float *dx, const float *table, const uint32_t *rows);
+int encode_groups_impl(ivfhnsw_gpu *h, size_t ngroups, size_t nsubc, const uint32_t *centroid_idx,
+                       const uint64_t *offsets, const float *x, size_t efSearch, uint32_t *out_nn_centroid_idxs,
+                       float *out_alphas, uint32_t *out_subcentroid_idxs, uint8_t *out_codes, uint8_t *out_norm_codes,
+                       bool dev, bool stage);
+
+} // namespace ivfhnsw_gpu_impl

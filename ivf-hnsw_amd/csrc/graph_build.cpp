@@ -22,7 +22,7 @@
 #include <thread>
 #include <vector>
 
-int ivfhnsw_gpu_fail_msg(int code, const char *msg); // capi.cpp
+int ivfhnsw_gpu_fail_msg(int code, const char *msg); // capi_handle.cpp
 
 namespace {
 

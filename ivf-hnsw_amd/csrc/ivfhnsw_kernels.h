@@ -1,5 +1,5 @@
 // Device-side data layout and kernel launchers of the gfx950 IVFADC search path.
-// Host code (capi.cpp) sees only the launch_* functions; kernels live in kernels_*.hip.
+// Host code (capi_*.cpp) sees only the launch_* functions; kernels live in kernels_*.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -202,7 +202,7 @@ hipError_t launch_coarse_latency(hipStream_t s, const GraphTables &g, const floa
                                  uint64_t *zero_keys = nullptr, uint32_t *zero_done = nullptr, // [nq] words to clear
                                  uint32_t *redo_hdr = nullptr, uint32_t *redo_list = nullptr); // zeroed header: see launch_coarse
 // bits of the device status word
-constexpr uint32_t kStatusHnswTieOverflow = 1u; // latency walk on the synchronous host-pointer path only: the call repeats itself (capi.cpp)
+constexpr uint32_t kStatusHnswTieOverflow = 1u; // latency walk on the synchronous host-pointer path only: the call repeats itself (capi_search.cpp)
 constexpr uint32_t kStatusTopkStreamOverflow = 2u;
 // synthetic corpus: uniform bytes from a counter hash; ids = running index
 // construction side (kernels_encode.hip): IndexIVF_HNSW.cpp:75-121

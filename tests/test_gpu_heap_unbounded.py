@@ -14,7 +14,7 @@ import synth
 
 pytestmark = pytest.mark.gpu
 
-CAP = 8192  # candidate-stream entries per query of the heap-order replay (capi.cpp kHeapStreamCap)
+CAP = 8192  # candidate-stream entries per query of the heap-order replay (capi_internal.h kHeapStreamCap)
 FLT_MAX = np.float32(3.4028234663852886e38)
 
 

@@ -301,6 +301,57 @@ def test_search_sharded_entry_point(gpu, pkg, grouping):
             assert np.array_equal(np.sort(lab, 1), np.sort(ref_l, 1)) and (np.diff(dist, axis=1) >= 0).all()
 
 
+def test_memory_bytes_counts_the_key_staging(gpu, pkg):
+    """ivfhnsw_gpu_memory_bytes is every device buffer the handle holds, the keys a host-pointer shard search stages
+    (ivfhnsw_gpu_search_keys) included.  Two handles with the same shard run the same search, one on host pointers and one
+    on device pointers: the per-batch workspace is the same, so what the first holds beyond the second is exactly its
+    staging -- queries, coarse ids and distances, distances, labels and the keys."""
+    import ctypes as C
+    import torch
+    c = corpus(seed=11, nc=256, d=128, M=16, n_base=30000, nq=128)
+    nprobe, max_codes, ef, k, world = 16, 2500, 40, 1, 2
+    ox = synth.oracle_index(c)
+    ox.set_params(nprobe, max_codes, ef)
+    _, _, cid, cd, _ = ox.search_batch(c["queries"], k=k)
+    q = np.ascontiguousarray(c["queries"], np.float32)
+    cid = np.ascontiguousarray(cid, np.uint32)
+    cd = np.ascontiguousarray(cd, np.float32)
+    nq, d = q.shape
+    ids, codes, ncodes = _shard_arrays(c, 0, world)
+    grown = []
+    for host in (True, False):
+        g = gpu()
+        g.upload_ivf(c["d"], c["code_size"], c["offsets"], ids, codes, ncodes, c["centroid_norms"], c["pq_centroids"],
+                     c["norm_table"], shard_rank=0, shard_world=world)
+        held = g.memory_bytes()
+        if host:
+            keys = np.empty((nq, k), np.int64)
+            p = pkg.SearchParams(nprobe, max_codes, 0, 0, 0)
+
+            def call():
+                rc = pkg.lib().ivfhnsw_gpu_search_keys(
+                    g._h, C.c_size_t(nq), C.c_size_t(k), C.c_void_p(q.ctypes.data), C.c_void_p(cid.ctypes.data),
+                    C.c_void_p(cd.ctypes.data), C.byref(p), C.c_void_p(keys.ctypes.data))
+                assert rc == 0, pkg.lib().ivfhnsw_gpu_last_error()
+            call()
+            grown.append(g.memory_bytes() - held)
+            call()  # the same shape again: nothing grows
+            assert g.memory_bytes() - held == grown[0]
+        else:
+            dev = torch.device("cuda", 0)
+            dd = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            ll = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            kk = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            g.search_dev(nq, k, torch.from_numpy(q).to(dev), dd, ll, nprobe, max_codes,
+                         d_coarse_ids=torch.from_numpy(cid.astype(np.int32)).to(dev), d_coarse_dists=torch.from_numpy(cd).to(dev),
+                         d_out_keys=kk)
+            g.sync()
+            grown.append(g.memory_bytes() - held)
+            assert np.array_equal(kk.cpu().numpy(), keys)  # the same search
+    staging = nq * d * 4 + 2 * nq * nprobe * 4 + nq * k * 4 + nq * k * 8 + nq * k * 8
+    assert grown[0] - grown[1] == staging
+
+
 def test_search_sharded_makes_the_rccl_calls(tmp_path):
     """A single shard with IVFHNSW_SHARDS_RCCL=1: ncclCommInitAll over one device and the two all-reduces (int64 MIN of the
     keys, MAX of the labels) are EXECUTED -- dtype, reduction, in-place buffers, group calls -- with results checked; what one
