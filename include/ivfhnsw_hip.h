@@ -260,7 +260,10 @@ int ivfhnsw_gpu_last_batch_parts(ivfhnsw_gpu *h, uint64_t *first, uint64_t *seco
  *   "scan_pipe"  -1 (default) the library chooses, 0 never, 1 wherever the shape allows: table + scan of a list shard as
  *                ONE software-pipelined kernel (kernels_scan3.hip) instead of two kernels.  A caller that runs a sharded
  *                step as two overlapping parts (ShardedSearcher) turns it off: the pipelined form holds most of a CU's
- *                LDS and cannot run beside the other part's walk. */
+ *                LDS and cannot run beside the other part's walk.
+ *   "exact_splits"  -1 (default) the library chooses from (nq, n); 1..64: exact_search cuts the store's rows into that many
+ *                column splits whose partial tables are merged.  The results are the same for every value; the key exists so
+ *                that the split and merge path can be exercised on a small store.  Other values: IVFHNSW_ERR_INVALID. */
 int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value);
 
 /* The search-time knobs the drivers set as public members (IndexIVF_HNSW.h:61-62, hnswalg.h:69,
@@ -394,6 +397,25 @@ int ivfhnsw_gpu_rerank_dev(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *d_
 /* host pointers, synchronous; a candidate label outside [-1, n) -> IVFHNSW_ERR_INVALID, nothing written */
 int ivfhnsw_gpu_rerank(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *queries, const int64_t *cand,
                        size_t k, float *distances, int64_t *labels);
+
+/* ---- exact brute-force search of the base store (the drivers' ground truth, -path_gt) ---------------------------------
+ *
+ * For each of nq queries the k rows of the base store (upload_base) nearest by exact squared L2, sum (q[j] - x[j])^2 in
+ * integers, ascending by (distance, label), [nq*k], padded with FLT_MAX / -1 when the store has fewer than k rows.
+ * Queries are uint8, d bytes each (the store's d), row_stride bytes apart (row_stride >= d; d + 4 takes a .bvecs query
+ * file image as it is, `queries` pointing past the first record's header).  For d <= 256 the distance is at most
+ * 256 * 255^2 < 2^24, so every partial sum of fvec_L2sqr (utils.cpp:22-52) is an exactly representable integer and the
+ * float written is bit for bit what ivfhnsw_gpu_rerank returns for the same queries as floats with every row a
+ * candidate; a store with d > 256: IVFHNSW_ERR_INVALID.  1 <= k <= 100, null buffers with nq > 0, row_stride < d:
+ * IVFHNSW_ERR_INVALID; no store: IVFHNSW_ERR_STATE; nq = 0 does nothing; nq is unbounded (processed in chunks).  A view
+ * searches its parent's store.  Neither form touches the index, the plan of the last search or its candidate stream; the
+ * workspace belongs to the handle and ivfhnsw_gpu_memory_bytes counts it.
+ * exact_search: host pointers, synchronous.  exact_search_dev: device pointers of any alignment, asynchronous on the
+ * handle's stream (ordered after an upload_base_dev or search_dev on the same stream). */
+int ivfhnsw_gpu_exact_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                             float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                 float *d_distances, int64_t *d_labels);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

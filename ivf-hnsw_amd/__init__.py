@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_remove_ids_dev", "ivfhnsw_gpu_download_grouping", "ivfhnsw_gpu_append_grouping",
     "ivfhnsw_gpu_append_grouping_dev", "ivfhnsw_gpu_add_groups", "ivfhnsw_gpu_add_groups_dev",
     "ivfhnsw_gpu_download_grouping_tables", "ivfhnsw_gpu_upload_centroid_norms",
+    "ivfhnsw_gpu_exact_search", "ivfhnsw_gpu_exact_search_dev",
 )
 
 
@@ -149,6 +150,9 @@ def lib():
         L.ivfhnsw_gpu_rerank_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_rerank.argtypes = L.ivfhnsw_gpu_rerank_dev.argtypes
+        L.ivfhnsw_gpu_exact_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                               C.c_void_p]
+        L.ivfhnsw_gpu_exact_search_dev.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
         L.ivfhnsw_gpu_last_scan_kernel.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_last_scan_kernel.restype = C.c_char_p
         _lib = L
@@ -646,10 +650,14 @@ class GpuIndex:
                                                  d if row_stride is None else row_stride))
         self.base_n, self.base_d = n, d
 
-    def upload_base_bvecs(self, path, chunk_rows=1 << 20):
-        """Stream a .bvecs file (records: int32 dim + dim bytes) into the base store in chunks of chunk_rows records;
-        every record's dim header is checked."""
+    def upload_base_bvecs(self, path, chunk_rows=1 << 20, rows=None):
+        """Stream a .bvecs file (records: int32 dim + dim bytes) into the base store in chunks of chunk_rows records
+        (rows: only the file's first `rows` records); every record's dim header is checked."""
         n, d = xvecs_shape(path, 1)
+        if rows is not None:
+            if not 1 <= rows <= n:
+                raise ValueError("%s holds %d records, asked for the first %d" % (path, n, rows))
+            n = rows
         rec = d + 4
         with open(path, "rb") as f:
             for first in range(0, n, chunk_rows):
@@ -698,6 +706,28 @@ class GpuIndex:
         self.rerank_dev(nq, kc, tq, cl, k, od, ol)
         self.sync()
         return od.cpu().numpy(), ol.cpu().numpy()
+
+    # ---- exact brute-force search of the base store (ground truth) -------------------------------------------------
+    def exact_search(self, queries_u8, k):
+        """The k rows of the base store nearest to every query by exact integer squared L2 (ivfhnsw_gpu_exact_search):
+        queries_u8 [nq, d] uint8 whose rows may lie a row stride apart (raw[:, 4:] of a .bvecs image is taken as it is).
+        Returns (distances f32 [nq, k], labels i64 [nq, k]) ascending by (distance, label), padded FLT_MAX / -1."""
+        a = np.asarray(queries_u8)
+        assert a.dtype == np.uint8 and a.ndim == 2, "queries_u8: a 2-D uint8 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 1 and (nq == 1 or a.strides[0] >= d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] if nq > 1 else d
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k, _ptr(dist),
+                                              _ptr(lab)))
+        return dist, lab
+
+    def exact_search_dev(self, nq, d_queries, row_stride, k, d_distances, d_labels):
+        """The same on device buffers (torch CUDA tensors or raw addresses), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_distances),
+                                                  _devptr(d_labels)))
 
     # ---- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on):

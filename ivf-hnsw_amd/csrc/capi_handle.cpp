@@ -281,6 +281,12 @@ int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value)
         h->opt_scan_pipe = (int)value;
         return IVFHNSW_OK;
     }
+    if (!strcmp(key, "exact_splits")) {
+        if (value != -1 && (value < 1 || value > 64))
+            return fail(IVFHNSW_ERR_INVALID, "set_option exact_splits: %ld is neither -1 nor in 1..64", value);
+        h->opt_exact_splits = (int)value;
+        return IVFHNSW_OK;
+    }
     return fail(IVFHNSW_ERR_INVALID, "set_option: unknown key '%s'", key);
 }
 

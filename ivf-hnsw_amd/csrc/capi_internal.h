@@ -101,6 +101,7 @@ using namespace ivfhnsw_gpu_impl;
     X(cg_q) X(cg_cidx) X(cg_ids) X(cg_dists) X(gc_nn) X(cg_cvn) X(cg_tab) X(cg_tab2) X(cg_off) X(cg_alpha2) X(cg_sub) /* add_group */ \
     X(base_rows) X(base_stage) /* uint8 base of the re-rank, rows permuted (kernels_rerank.hip); a view reads its parent's */ \
     X(r_q) X(r_cand) X(r_dist) X(r_lab) /* staging of the host-pointer re-rank */ \
+    X(ex_q) X(ex_part) X(ex_raw) X(ex_dist) X(ex_lab) /* exact_search: permuted queries, per-split partial tables; staging of the host form */ \
     X(ap_idx) X(ap_ids) X(ap_codes) X(ap_ncodes) X(ap_cnt) X(ap_own) X(ap_part) X(ap_status) X(ap_perm) X(ap_perm2) X(ap_hist) X(ap_tiles) /* append_ivf, add */ \
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
@@ -149,6 +150,7 @@ struct ivfhnsw_gpu {
     void *visited_zero_ptr = nullptr; // ... of this allocation
     size_t visited_zero_bytes = 0;
     int opt_scan_pipe = -1;      // ivfhnsw_gpu_set_option "scan_pipe"
+    int opt_exact_splits = -1;   // ... "exact_splits"
     bool lat_defer_redo = false; // host-pointer small batches: the latency walk flags a tie overflow, the call repeats itself
     bool latency_off = false;    // ... on the throughput walk
 

@@ -264,6 +264,13 @@ hipError_t launch_rerank_permute(hipStream_t s, const uint8_t *src, size_t src_s
 size_t rerank_lds_bytes(int kc, int d);
 hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
                          const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels);
+// exact brute-force search of the store on the int8 matrix cores (kernels_exact.hip).  Qp: [nq][d] queries
+// in the store's byte order (launch_rerank_permute), d % 16 == 0, d <= 256, 1 <= k <= 100; part: [nsplit][nq][k] u64
+// workspace; writes the k nearest rows of every query ascending by (distance, label), padded with FLT_MAX / -1
+int exact_rows_per_block(int k);
+int exact_splits_for(size_t nq, size_t nx, int k);
+hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
+                               int nsplit, unsigned long long *part, float *dists, int64_t *labels);
 // appends to the inverted lists (kernels_append.hip).  count: cnt[idx[i]] += 1 (cnt may be null: check
 // only), an id >= nc raises *status.  tables: own[c] = old length + cnt[c] of the owned lists, then cnt and own ([nc + 1]
 // each, slot nc zero) become their exclusive scans nstart / lstart in place; part: append_scan_parts(nc + 1) words.

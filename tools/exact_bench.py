@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Times the exact brute-force search of the uint8 base store (ivfhnsw_gpu_exact_search_dev, kernels_exact.hip).
+
+  1. n = 10 M x 128 (the shape the float path can also run): exact_search_dev against ivfhnsw_gpu_knn_dev on the same rows
+     converted to float, same queries, k = 1 and k = 10; the labels must be equal (knn's fmaf chains are exact on these
+     integers too, and both break ties to the lower id).
+  2. The 10^9 x 128 store, filled on the device in ~1 GB torch chunks through upload_base_dev (the rows never exist on the
+     host): 10 000 queries at k = 1 and k = 100.
+Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
+work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
+tile, the bytes per second all tiles stream together.
+usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
+                                   [--no-big] [--no-small] [--out result.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.abspath(os.path.dirname(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def fill_store(g, torch, dev, n, d, seed, keep=False):
+    """n x d random bytes into the base store in chunks of ~1 GB; keep: also return them as one tensor."""
+    chunk_rows = min(n, (1 << 30) // d)
+    buf = torch.empty((chunk_rows, d), dtype=torch.uint8, device=dev)
+    kept = torch.empty((n, d), dtype=torch.uint8, device=dev) if keep else None
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(seed)
+    t0 = time.time()
+    for first in range(0, n, chunk_rows):
+        m = min(chunk_rows, n - first)
+        buf.random_(0, 256, generator=gen)
+        if keep:
+            kept[first:first + m] = buf[:m]
+        torch.cuda.synchronize(dev)
+        g.upload_base_dev(n, d, first, m, buf)
+    del buf
+    log("[exact_bench] %d x %d base store on the device: %.1fs, %.1f GB held" % (n, d, time.time() - t0, g.memory_bytes() / 1e9))
+    return kept
+
+
+def timed(torch, dev, fn, warmup, reps, what):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize(dev)
+    ts = []
+    for i in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(dev)
+        ts.append(time.perf_counter() - t0)
+        log("[exact_bench] %s rep %d: %.4f s" % (what, i, ts[-1]))
+    return statistics.median(ts), ts
+
+
+def figures(name, n, d, nq, k, t, ts, rows_per_tile=None):
+    r = {"what": name, "rows": n, "d": d, "nq": nq, "k": k, "seconds": round(t, 5), "reps": [round(x, 5) for x in ts],
+         "TOPs": round(2.0 * nq * n * d / t / 1e12, 2), "store_TB_per_s_per_pass": round(n * d / t / 1e12, 4)}
+    if rows_per_tile:  # every query tile streams the whole store: what the caches deliver to the CUs
+        r["query_tiles"] = -(-nq // rows_per_tile)
+        r["streamed_TB_per_s"] = round(r["query_tiles"] * n * d / t / 1e12, 3)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000_000)
+    ap.add_argument("--small-rows", type=int, default=10_000_000)
+    ap.add_argument("--d", type=int, default=128)
+    ap.add_argument("--nq", type=int, default=10000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--no-big", action="store_true")
+    ap.add_argument("--no-small", action="store_true")
+    ap.add_argument("--out", default=None, help="write the whole result as JSON here")
+    args = ap.parse_args()
+    import torch
+    import __graft_entry__ as ge
+    pkg = ge.load_pkg()
+    dev = torch.device("cuda", 0)
+    g = pkg.GpuIndex(0)
+    g.set_stream(torch.cuda.current_stream(dev).cuda_stream)  # one stream: torch's synchronize covers the library's work
+    d, nq = args.d, args.nq
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(4321)
+    q = torch.empty((nq, d), dtype=torch.uint8, device=dev).random_(0, 256, generator=gen)
+    result = {"device": torch.cuda.get_device_name(dev), "rows": []}
+
+    def exact(n, k, name):
+        od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        t, ts = timed(torch, dev, lambda: g.exact_search_dev(nq, q, d, k, od, ol), args.warmup, args.reps,
+                      "%s exact k=%d" % (name, k))
+        r = figures("exact_search_dev", n, d, nq, k, t, ts, 128 if k <= 32 else 64)  # kernels_exact.hip's strips
+        result["rows"].append(r)
+        print(json.dumps(r), flush=True)
+        return r, ol
+
+    if not args.no_small:
+        n = args.small_rows
+        rows = fill_store(g, torch, dev, n, d, 99, keep=True)
+        xf = rows.to(torch.float32)
+        del rows
+        qf = q.to(torch.float32)
+        for k in (1, 10):
+            r, ol = exact(n, k, "%d rows" % n)
+            ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            t, ts = timed(torch, dev, lambda: g.knn_dev(nq, n, d, qf, xf, k, ids, dist), args.warmup, args.reps,
+                          "%d rows knn k=%d" % (n, k))
+            rk = figures("knn_dev (f32 MFMA)", n, d, nq, k, t, ts)
+            rk["labels_equal"] = bool(torch.equal(ids.to(torch.int64) & 0xffffffff, ol))
+            rk["exact_speedup"] = round(t / r["seconds"], 2)
+            result["rows"].append(rk)
+            print(json.dumps(rk), flush=True)
+            assert rk["labels_equal"], "exact_search and knn disagree"
+        del xf, qf
+        torch.cuda.empty_cache()
+    if not args.no_big:
+        n = args.rows
+        fill_store(g, torch, dev, n, d, 99)
+        for k in (1, 100):
+            exact(n, k, "%d rows" % n)
+    g.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
