@@ -529,11 +529,26 @@ int ivfhnsw_gpu_knn_dev(ivfhnsw_gpu *h, size_t nq, size_t nx, size_t d, const fl
  * fstdistfunc, :326-357), the links stored farthest first (:153-170), and mutuallyConnectNewElement's reverse links in
  * insertion order -- appended while the neighbour has room, else the neighbour's maxM + 1 candidates shrunk by the same
  * heuristic (:171-209).  Because the candidates no longer depend on the graph, node t's final list is a fold over the
- * later nodes that chose t, in their order: every node is processed independently (host threads), and the result is
- * exactly what the serial loop would leave.  vectors [n][d] host; out_counts [n] (the 1-byte link count of
- * hnswalg.cpp:25); out_links [n][maxM].  M <= maxM <= 64, ncand <= 80, n < 2^32. */
+ * later nodes that chose t, in their order: every node is processed independently, and the result is exactly what the
+ * serial loop would leave.  All of it runs on the device (kernels_graph.hip): the forward heuristic and the fold take one
+ * node per wavefront, the reverse lists are a stable sort of the forward links; the library starts no host thread.
+ * vectors [n][d] host; out_counts [n] (the 1-byte link count of hnswalg.cpp:25); out_links [n][maxM], zero from each
+ * node's count on.  1 <= M <= maxM <= 64, M <= ncand <= 80, d a multiple of 16 with d <= 128, n < 2^31 and n * M < 2^32;
+ * anything else, or a NULL argument, returns IVFHNSW_ERR_INVALID and touches no buffer.  n <= 1 writes zeros.
+ * ivfhnsw_gpu_build_graph_dev: the same on device pointers (d_vectors 16-byte aligned as for kmeans_dev, d_out_links
+ * 4-byte aligned, else IVFHNSW_ERR_INVALID), the one deviation from hnswalg.cpp:110-225 being the same: exact candidates.
+ * Asynchronous on the handle's stream, as knn_dev: it reads nothing back (the reverse lists are bounded by n * M entries)
+ * and does not synchronise; d_vectors is only read.  Needs no upload, and leaves the index, the last search's plan and
+ * the candidate stream as they were; its workspace (the n x ncand table, n x M forward links and three arrays of that
+ * size for the sort) stays on the handle and counts in ivfhnsw_gpu_memory_bytes.  The host-pointer form is an upload,
+ * this call and a download.
+ * ivfhnsw_gpu_last_graph_longest_reverse: the longest reverse list (later nodes that chose one node) the handle's last
+ * build_graph[_dev] met, 0 before any; synchronises the stream. */
 int ivfhnsw_gpu_build_graph(ivfhnsw_gpu *h, size_t n, size_t d, const float *vectors, size_t M, size_t maxM, size_t ncand,
                             uint8_t *out_counts, uint32_t *out_links);
+int ivfhnsw_gpu_build_graph_dev(ivfhnsw_gpu *h, size_t n, size_t d, const float *d_vectors, size_t M, size_t maxM,
+                                size_t ncand, uint8_t *d_out_counts, uint32_t *d_out_links);
+int ivfhnsw_gpu_last_graph_longest_reverse(ivfhnsw_gpu *h, uint64_t *out);
 
 enum ivfhnsw_stage {
     IVFHNSW_STAGE_OPQ = 0,    /* opq_matrix->apply, IndexIVF_HNSW.cpp:240 */

@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_append_grouping_dev", "ivfhnsw_gpu_add_groups", "ivfhnsw_gpu_add_groups_dev",
     "ivfhnsw_gpu_download_grouping_tables", "ivfhnsw_gpu_upload_centroid_norms",
     "ivfhnsw_gpu_exact_search", "ivfhnsw_gpu_exact_search_dev",
+    "ivfhnsw_gpu_build_graph_dev", "ivfhnsw_gpu_last_graph_longest_reverse",
 )
 
 
@@ -136,6 +137,8 @@ def lib():
                                       C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_build_graph.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_build_graph_dev.argtypes = L.ivfhnsw_gpu_build_graph.argtypes
+        L.ivfhnsw_gpu_last_graph_longest_reverse.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_knn_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_int, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -617,6 +620,18 @@ class GpuIndex:
         links = np.zeros((n, maxM), np.uint32)
         _check(lib().ivfhnsw_gpu_build_graph(self._h, n, d, _ptr(v), M, maxM, ncand, _ptr(counts), _ptr(links)))
         return counts, links
+
+    def build_graph_dev(self, n, d, d_vectors, M, maxM, ncand, d_counts, d_links):
+        """The same on device buffers (torch CUDA tensors: d_vectors f32 [n, d], d_counts u8 [n], d_links u32/i32
+        [n, maxM]), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_build_graph_dev(self._h, n, d, _devptr(d_vectors), M, maxM, ncand, _devptr(d_counts),
+                                                 _devptr(d_links)))
+
+    def last_graph_longest_reverse(self):
+        """The longest reverse list (later nodes that chose one node) of the last build_graph[_dev]."""
+        v = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_last_graph_longest_reverse(self._h, C.byref(v)))
+        return v.value
 
     def set_option(self, key, value):
         """Library options (ivfhnsw_gpu_set_option), e.g. ("scan_pipe", 0)."""

@@ -390,6 +390,26 @@ int ivfhnsw_gpu_knn(ivfhnsw_gpu *h, size_t nq, size_t nx, size_t d, const float 
 
 namespace {
 
+// what both forms of build_graph refuse, before either touches a buffer (vectors / counts / links: host or device)
+int build_graph_check(ivfhnsw_gpu *h, size_t n, size_t d, const void *vectors, size_t M, size_t maxM, size_t ncand,
+                      const void *counts, const void *links)
+{
+    if (!h || !vectors || !counts || !links)
+        return fail(IVFHNSW_ERR_INVALID, "build_graph: null argument");
+    if (M < 1 || M > maxM || maxM > 64 || ncand < M || ncand > 80 || n >= 0xffffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "build_graph: need 1 <= M <= maxM <= 64, M <= ncand <= 80, n < 2^32");
+    if (d % 16 != 0)
+        return fail(IVFHNSW_ERR_INVALID, "build_graph: d must be a multiple of 16 (the reference's distance "
+                                         "ignores the dims beyond one, hnswalg.cpp:330; so does upload_quantizer)");
+    if (n > 1 && (d < 16 || d > 128))
+        return fail(IVFHNSW_ERR_INVALID, "knn: d %zu must be a multiple of 4, at most 128", d);
+    if (n > 0x7fffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "knn: too many rows");
+    if (n * M > 0xffffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "build_graph: n * M must stay below 2^32 (the reverse lists are indexed by 32 bits)");
+    return IVFHNSW_OK;
+}
+
 int kmeans_check(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const void *x, const void *c)
 {
     int rc = bind(h);
@@ -534,5 +554,92 @@ int ivfhnsw_gpu_kmeans(ivfhnsw_gpu *h, size_t n, size_t d, size_t nc, const floa
     HIP_TRY(hipMemcpy(centroids, h->km_c.p, nc * d * sizeof(float), hipMemcpyDeviceToHost));
     if (out_assign)
         HIP_TRY(hipMemcpy(out_assign, h->km_assign.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_build_graph_dev(ivfhnsw_gpu *h, size_t n, size_t d, const float *d_vectors, size_t M, size_t maxM,
+                                size_t ncand, uint8_t *d_out_counts, uint32_t *d_out_links)
+{
+    int rc = build_graph_check(h, n, d, d_vectors, M, maxM, ncand, d_out_counts, d_out_links);
+    if (rc)
+        return rc;
+    if (((uintptr_t)d_vectors & 15) || ((uintptr_t)d_out_links & 3))
+        return fail(IVFHNSW_ERR_INVALID, "build_graph_dev: vectors must be 16-byte aligned, links 4-byte aligned");
+    if ((rc = bind(h)))
+        return rc;
+    if (n == 0)
+        return IVFHNSW_OK;
+    HIP_TRY(hipMemsetAsync(d_out_counts, 0, n, h->stream));
+    HIP_TRY(hipMemsetAsync(d_out_links, 0, n * maxM * sizeof(uint32_t), h->stream));
+    if (n == 1)
+        return IVFHNSW_OK;
+    const size_t nslots = n * M, nblocks = (nslots + kKmeansTile - 1) / kKmeansTile;
+    if ((rc = h->gb_table.ensure(n * ncand * sizeof(uint32_t))) || (rc = h->gb_fwd.ensure(nslots * sizeof(uint32_t))) ||
+        (rc = h->gb_fcnt.ensure(n)) || (rc = h->gb_deg.ensure((n + 1) * sizeof(uint32_t))) ||
+        (rc = h->gb_roff.ensure((n + 1) * sizeof(uint32_t))) || (rc = h->gb_ids.ensure(nslots * sizeof(uint32_t))) ||
+        (rc = h->gb_ids2.ensure(nslots * sizeof(uint32_t))) || (rc = h->gb_hist.ensure(256 * nblocks * sizeof(uint32_t))) ||
+        (rc = h->gb_stat.ensure(sizeof(uint32_t))))
+        return rc;
+    uint32_t *table = h->gb_table.as<uint32_t>(), *fwd = h->gb_fwd.as<uint32_t>(), *deg = h->gb_deg.as<uint32_t>();
+    // the exact candidates: row c against rows 0..c-1
+    if ((rc = ivfhnsw_gpu_knn_dev(h, n, n, d, d_vectors, d_vectors, ncand, IVFHNSW_KNN_EARLIER, table, nullptr)))
+        return rc;
+    // A. forward links, and how many later nodes chose each node
+    HIP_TRY(hipMemsetAsync(deg, 0, (n + 1) * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->gb_stat.p, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_graph_forward(h->stream, d_vectors, table, n, (int)d, (int)M, (int)ncand, fwd, h->gb_fcnt.as<uint8_t>(), deg));
+    // B. reverse lists: the link slots c * M + i sorted stably by the node they name (an empty slot names n, behind every
+    // node), so that node t's run lists the nodes that chose it ascending -- the order the serial loop meets them in
+    HIP_TRY(launch_scan_u32(h->stream, deg, h->gb_roff.as<uint32_t>(), n + 1));
+    int key_bits = 1;
+    while (key_bits < 32 && (n >> key_bits))
+        key_bits++;
+    uint32_t *pairs = nullptr;
+    HIP_TRY(launch_sort_by_key(h->stream, fwd, nslots, key_bits, h->gb_ids.as<uint32_t>(), h->gb_ids2.as<uint32_t>(),
+                               h->gb_hist.as<uint32_t>(), &pairs));
+    // C. every node's own insertion, then the later nodes that chose it, in their order
+    HIP_TRY(launch_graph_fold(h->stream, d_vectors, fwd, h->gb_fcnt.as<uint8_t>(), h->gb_roff.as<uint32_t>(), pairs, n, (int)d,
+                              (int)M, (int)maxM, d_out_counts, d_out_links, h->gb_stat.as<uint32_t>()));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_build_graph(ivfhnsw_gpu *h, size_t n, size_t d, const float *vectors, size_t M, size_t maxM, size_t ncand,
+                            uint8_t *out_counts, uint32_t *out_links)
+{
+    int rc = build_graph_check(h, n, d, vectors, M, maxM, ncand, out_counts, out_links);
+    if (rc)
+        return rc;
+    if (n <= 1) {
+        std::memset(out_counts, 0, n);
+        std::memset(out_links, 0, n * maxM * sizeof(uint32_t));
+        return IVFHNSW_OK;
+    }
+    if ((rc = bind(h)))
+        return rc;
+    if ((rc = upload(h->k_x, vectors, n * d * sizeof(float))) || (rc = h->gb_counts.ensure(n)) ||
+        (rc = h->gb_links.ensure(n * maxM * sizeof(uint32_t))))
+        return rc;
+    if ((rc = ivfhnsw_gpu_build_graph_dev(h, n, d, h->k_x.as<float>(), M, maxM, ncand, h->gb_counts.as<uint8_t>(),
+                                          h->gb_links.as<uint32_t>())))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out_counts, h->gb_counts.p, n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_links, h->gb_links.p, n * maxM * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_last_graph_longest_reverse(ivfhnsw_gpu *h, uint64_t *out)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!out)
+        return fail(IVFHNSW_ERR_INVALID, "null argument");
+    uint32_t v = 0;
+    if (h->gb_stat.p) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(&v, h->gb_stat.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    *out = v;
     return IVFHNSW_OK;
 }

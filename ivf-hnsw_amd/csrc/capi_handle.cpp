@@ -118,9 +118,6 @@ void point_at_lists(ivfhnsw_gpu *h, uint64_t n_local)
 
 } // namespace ivfhnsw_gpu_impl
 
-// for the library's other translation units (graph_build.cpp): record a failure the way every entry point does
-int ivfhnsw_gpu_fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
-
 const char *ivfhnsw_gpu_last_error(void) { return g_last_error.c_str(); }
 
 int ivfhnsw_gpu_abi_version(void) { return 9; }

@@ -98,6 +98,7 @@ using namespace ivfhnsw_gpu_impl;
     X(t_x) X(t_y) X(t_cb) X(t_assign) X(t_part) X(t_c) /* pq_train, xty */ \
     X(k_q) X(k_x) X(k_qn) X(k_xn) X(k_part) X(k_ids) X(k_dists) /* knn */ \
     X(km_x) X(km_c) X(km_assign) X(km_dist) X(km_cnt) X(km_start) X(km_ids) X(km_ids2) X(km_hist) X(km_part) X(km_status) X(km_pairs) /* kmeans */ \
+    X(gb_table) X(gb_fwd) X(gb_fcnt) X(gb_deg) X(gb_roff) X(gb_ids) X(gb_ids2) X(gb_hist) X(gb_stat) X(gb_counts) X(gb_links) /* build_graph */ \
     X(cg_q) X(cg_cidx) X(cg_ids) X(cg_dists) X(gc_nn) X(cg_cvn) X(cg_tab) X(cg_tab2) X(cg_off) X(cg_alpha2) X(cg_sub) /* add_group */ \
     X(base_rows) X(base_stage) /* uint8 base of the re-rank, rows permuted (kernels_rerank.hip); a view reads its parent's */ \
     X(r_q) X(r_cand) X(r_dist) X(r_lab) /* staging of the host-pointer re-rank */ \

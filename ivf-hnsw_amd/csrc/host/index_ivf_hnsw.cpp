@@ -137,12 +137,14 @@ void IndexIVF_HNSW::build_quantizer(const char *path_data, const char *path_info
     // IVFHNSW_BUILD=device: the insertion loop for all centroids at once on the device (ivfhnsw_gpu_build_graph: exact
     // candidates on the matrix cores, then this very heuristic and connect step per node) -- seconds for a million
     // centroids where the serial loop below takes hours (README.md:65 of the reference); the default keeps the serial
-    // loop, whose graph equals the reference's link for link.
+    // loop, whose graph equals the reference's link for link.  The device-built graph does NOT: its candidates are the
+    // exact nearest earlier centroids, not the results of the reference's greedy search of the graph built so far.  A d
+    // the device form does not take (no multiple of 16, as the reference's distance reads it) stays on the serial loop.
     static const bool on_device = [] {
         const char *e = getenv("IVFHNSW_BUILD");
         return e && std::string(e) == "device";
     }();
-    if (on_device && nc > 1 && d % 4 == 0 && d <= 128 && 2 * M_ <= 64) {
+    if (on_device && nc > 1 && d % 16 == 0 && d <= 128 && 2 * M_ <= 64) {
         std::vector<float> all(nc * d);
         for (size_t i = 0; i < nc; i++)
             readXvec<float>(input, all.data() + i * d, d);

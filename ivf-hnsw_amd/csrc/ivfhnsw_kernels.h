@@ -238,6 +238,18 @@ int knn_splits_for(size_t nq, size_t nx);
 hipError_t launch_knn_norms(hipStream_t s, const float *x, float *out, size_t n, int d);
 hipError_t launch_knn(hipStream_t s, const float *Q, const float *X, const float *qn, const float *xn, size_t nq, size_t nx,
                       int d, int k, int mode, int nsplit, unsigned long long *part, uint32_t *ids, float *dists); // mode: IVFHNSW_KNN_*
+// the insertion loop behind the neighbour table (kernels_graph.hip).  forward: node c's links out of row c
+// of the IVFHNSW_KNN_EARLIER table into fwd [n][M] (slots beyond fcnt[c] hold n) and deg[t] += 1 for every link to t
+// (deg [n + 1] zeroed before).  fold: pairs = the slots 0 .. n * M - 1 of fwd sorted stably by their content, roff
+// [n + 1] = the exclusive scan of deg; writes counts [n], links [n][maxM] and the longest reverse list into *longest
+// (zeroed before).
+size_t graph_forward_lds_bytes(int d, int ncand);
+size_t graph_fold_lds_bytes(int d, int maxM);
+hipError_t launch_graph_forward(hipStream_t s, const float *x, const uint32_t *table, size_t n, int d, int M, int ncand,
+                                uint32_t *fwd, uint8_t *fcnt, uint32_t *deg);
+hipError_t launch_graph_fold(hipStream_t s, const float *x, const uint32_t *fwd, const uint8_t *fcnt, const uint32_t *roff,
+                             const uint32_t *pairs, size_t n, int d, int M, int maxM, uint8_t *counts, uint32_t *links,
+                             uint32_t *longest);
 // Grouping construction (IndexIVF_HNSW_Grouping.cpp:43-157)
 hipError_t launch_group_table(hipStream_t s, int mode, const float *vectors, const uint32_t *centroid_idx,
                               const uint32_t *nn, const float *alphas, const float *cv_in, float *out, size_t ngroups,
