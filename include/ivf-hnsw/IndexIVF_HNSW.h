@@ -6,7 +6,7 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch(), remove_ids().
+// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
 
@@ -97,6 +97,14 @@ public:
     /// With the device copy current (one handle) the lists shrink in HBM as well (ivfhnsw_gpu_remove_ids); otherwise the
     /// next search uploads them again.
     size_t remove_ids(size_t n, const idx_t *xids);
+    /// Extension: faiss's IDSelector.  Every search entry point (search, search_batch, search2, searchDisk,
+    /// searchDisk_batch) returns only codes whose id is one of xids[0..n) -- with deny, only codes whose id is none of
+    /// them -- as if every other code failed `dist < distances[0]`; unfilled slots hold FLT_MAX / -1.  The set is kept
+    /// on the host (beside the object: the class layout does not grow) and installed on the device copy whenever that is
+    /// made or remade, at once if it is current (ivfhnsw_gpu_set_filter).  write() is unaffected.
+    /// Throws with IVFHNSW_SHARDS > 1 (sharded handles have no filter).
+    void set_id_filter(size_t n, const idx_t *xids, bool deny = false);
+    void clear_id_filter();
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

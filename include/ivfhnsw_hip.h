@@ -220,6 +220,41 @@ int ivfhnsw_gpu_download_grouping_tables(ivfhnsw_gpu *h, float *alphas, uint32_t
                                          float *inter_centroid_dists);
 int ivfhnsw_gpu_upload_centroid_norms(ivfhnsw_gpu *h, const float *centroid_norms);
 
+/* Label filter: faiss's IDSelector for the lists the handle holds.  A handle holds no filter or one: a
+ * set of uint32 labels and a mode.  IVFHNSW_FILTER_ALLOW: only rows whose id is in the set pass; IVFHNSW_FILTER_DENY:
+ * rows whose id is in the set do not pass (soft deletes, without the compaction of ivfhnsw_gpu_remove_ids).  With a
+ * filter installed every search on the handle (search, search_dev, search_keys / out_keys; unsharded handles) behaves as
+ * the reference's would if a non-passing code failed `dist < distances[0]`: the same lists and sub-groups are visited in
+ * the same order, max_codes and Grouping's pruning count every stored code, ivfhnsw_gpu_last_scan_counts and the scan
+ * positions in keys and candidate streams are those of the unfiltered call (resolve_keys, last_stream and replay_stream
+ * work unchanged); results hold passing labels only, unfilled slots FLT_MAX / -1, and heap_order = 1 leaves the heap
+ * array faiss would leave had it seen only the passing codes (any k).  ivfhnsw_gpu_last_scan_kernel reports the
+ * filtered launch as the unfiltered name with "+filter" appended; small batches run plan, table and scan instead of the
+ * one-launch tail.  Without a filter nothing changes: the same kernels, the same bits.
+ *   Any label value is accepted (0xffffffff included); repeated labels count once; labels that match nothing are
+ *   ignored; an empty allow set passes nothing, an empty deny set everything.
+ * ivfhnsw_gpu_set_filter replaces an earlier filter; the new one is built beside it, so any error leaves the earlier
+ *   filter in force.  Synchronous; ~1 bit per label value up to the largest label (<= 512 MB) plus 1 bit per resident
+ *   row stay allocated, both counted by ivfhnsw_gpu_memory_bytes.  ivfhnsw_gpu_set_filter_dev: d_labels in device memory
+ *   (4-byte aligned), read on the handle's stream; returns with that stream drained.
+ * ivfhnsw_gpu_clear_filter: no filter afterwards; succeeds on a handle that has none.  ivfhnsw_gpu_upload_ivf clears it.
+ * After a successful append_ivf, add, remove_ids, append_grouping or add_groups (host or _dev form) the filter holds for
+ *   the updated lists (rows are judged again from the kept label set); an update that fails leaves tables and filter
+ *   as they were.
+ * Views: set_filter / clear_filter on a view -> IVFHNSW_ERR_STATE.  A view filters with what its parent held when the
+ *   view was created (the internal view of split batches: at every call); replacing or clearing the parent's filter
+ *   while a view of it is in use is, like an update of the tables, the caller's to avoid.
+ * ivfhnsw_gpu_filter_info: *mode = the installed mode or -1; *rows_passing = resident rows that pass (all of them
+ *   without a filter); *rows_total = resident rows.  Each pointer nullable.
+ * Errors: before upload_ivf, on a view, on a handle with shard_world > 1 -> IVFHNSW_ERR_STATE; null labels with n > 0
+ *   or an unknown mode -> IVFHNSW_ERR_INVALID; a failed allocation -> IVFHNSW_ERR_NOMEM. */
+#define IVFHNSW_FILTER_ALLOW 0
+#define IVFHNSW_FILTER_DENY 1
+int ivfhnsw_gpu_set_filter(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int mode);
+int ivfhnsw_gpu_set_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int mode);
+int ivfhnsw_gpu_clear_filter(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IVFHNSW_HIP_LIB") or os.path.join(_HERE, "libivfhnsw_hip.so")  # override: A/B runs of two builds
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
+FILTER_ALLOW, FILTER_DENY = 0, 1
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
 # every symbol include/ivfhnsw_hip.h declares
@@ -37,6 +38,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_download_grouping_tables", "ivfhnsw_gpu_upload_centroid_norms",
     "ivfhnsw_gpu_exact_search", "ivfhnsw_gpu_exact_search_dev",
     "ivfhnsw_gpu_build_graph_dev", "ivfhnsw_gpu_last_graph_longest_reverse",
+    "ivfhnsw_gpu_set_filter", "ivfhnsw_gpu_set_filter_dev", "ivfhnsw_gpu_clear_filter", "ivfhnsw_gpu_filter_info",
 )
 
 
@@ -156,6 +158,10 @@ def lib():
         L.ivfhnsw_gpu_exact_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                C.c_void_p]
         L.ivfhnsw_gpu_exact_search_dev.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
+        L.ivfhnsw_gpu_set_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_set_filter_dev.argtypes = L.ivfhnsw_gpu_set_filter.argtypes
+        L.ivfhnsw_gpu_clear_filter.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_last_scan_kernel.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_last_scan_kernel.restype = C.c_char_p
         _lib = L
@@ -343,6 +349,26 @@ class GpuIndex:
         nr = C.c_uint64(0)
         _check(lib().ivfhnsw_gpu_remove_ids_dev(self._h, n, _devptr(d_labels), C.byref(nr), _devptr(d_removed_per_list)))
         return int(nr.value)
+
+    # ---- label filter (ivfhnsw_gpu_set_filter) ---------------------------------------------------
+    def set_filter(self, labels, deny=False):
+        """Searches return only rows whose id is in `labels` (deny=True: is not in them); replaces an earlier filter."""
+        lab = _np(labels, np.uint32).ravel()
+        _check(lib().ivfhnsw_gpu_set_filter(self._h, lab.size, _ptr(lab) if lab.size else None,
+                                            FILTER_DENY if deny else FILTER_ALLOW))
+
+    def set_filter_dev(self, n, d_labels, deny=False):
+        """The same on a device buffer (torch CUDA tensor or raw address)."""
+        _check(lib().ivfhnsw_gpu_set_filter_dev(self._h, n, _devptr(d_labels), FILTER_DENY if deny else FILTER_ALLOW))
+
+    def clear_filter(self):
+        _check(lib().ivfhnsw_gpu_clear_filter(self._h))
+
+    def filter_info(self):
+        """(mode or -1, rows_passing, rows_total)."""
+        m, a, b = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_filter_info(self._h, C.byref(m), C.byref(a), C.byref(b)))
+        return int(m.value), int(a.value), int(b.value)
 
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)

@@ -89,6 +89,9 @@ void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent)
     view->has_group = parent->has_group;
     view->gr = parent->gr;
     view->has_graph = parent->has_graph;
+    view->filter_mode = parent->filter_mode; // the view filters as its parent does at this moment
+    view->fmask = parent->fmask;
+    view->f_pass = parent->f_pass;
 }
 
 int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool need_ivf)

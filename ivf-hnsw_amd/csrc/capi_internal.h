@@ -106,6 +106,7 @@ using namespace ivfhnsw_gpu_impl;
     X(ap_idx) X(ap_ids) X(ap_codes) X(ap_ncodes) X(ap_cnt) X(ap_own) X(ap_part) X(ap_status) X(ap_perm) X(ap_perm2) X(ap_hist) X(ap_tiles) /* append_ivf, add */ \
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
+    X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_counter) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
 
@@ -138,6 +139,15 @@ struct ivfhnsw_gpu {
     uint64_t base_n = 0;
     size_t base_d = 0;
     ivfhnsw_gpu *parent = nullptr;
+
+    // the label filter (capi_filter.cpp).  filter_mode -1 = none.  fmask is what the scans read: the
+    // handle's own f_mask, on a view the mask its parent held when follow_parent ran.  f_bits holds the label set over
+    // [0, f_max_label] (f_has_bits false = the empty set) so that an update can judge the rows of its new arrays.
+    int filter_mode = -1;
+    const uint32_t *fmask = nullptr;
+    bool f_has_bits = false;
+    uint32_t f_max_label = 0;
+    uint64_t f_pass = 0;
 
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
@@ -196,11 +206,19 @@ int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool n
 // h->t's pointers to the five list arrays and n_local follow the handle's buffers
 void point_at_lists(ivfhnsw_gpu *h, uint64_t n_local);
 
+// ---- capi_filter.cpp
+// The pass mask of h's filter over ids [n_local] into mask (allocated here) and the rows that pass into *pass.  Returns
+// with the stream drained; the handle is not touched.
+int filter_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &mask, uint64_t *pass);
+void filter_drop(ivfhnsw_gpu *h); // the handle holds no filter afterwards (buffers released)
+
 // The five arrays that make up the resident lists, built BESIDE the handle's: an in-place update fills a fresh set and
 // installs it when it is complete and the stream has drained, so that on any error the handle's tables are the ones it
 // had.  The destructor frees what was not installed -- after install, the handle's previous arrays.
 struct ListArrays {
     DevBuf goff, loff, codes, ncodes, ids;
+    DevBuf fmask; // the handle's filter judged over the new ids (mark_filter); installed with them
+    uint64_t fpass = 0;
     ListArrays() = default;
     ListArrays(const ListArrays &) = delete;
     ListArrays &operator=(const ListArrays &) = delete;
@@ -213,13 +231,26 @@ struct ListArrays {
             return rc;
         return IVFHNSW_OK;
     }
+    // The one place an update re-marks the filter: rows move and new rows must be judged.  Called when the new ids are
+    // complete and BEFORE install, so that a failure here leaves tables and filter as they were.  No filter: nothing.
+    int mark_filter(ivfhnsw_gpu *h, uint64_t n_local)
+    {
+        if (h->filter_mode < 0)
+            return IVFHNSW_OK;
+        return filter_mark_rows(h, ids.as<uint32_t>(), n_local, fmask, &fpass);
+    }
     void release()
     {
-        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids})
+        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask})
             b->release();
     }
     void install(ivfhnsw_gpu *h, uint64_t n_local)
     {
+        if (h->filter_mode >= 0) {
+            std::swap(h->f_mask, fmask);
+            h->fmask = h->f_mask.as<uint32_t>();
+            h->f_pass = fpass;
+        }
         std::swap(h->goff, goff);
         std::swap(h->loff, loff);
         std::swap(h->codes, codes);

@@ -305,8 +305,11 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
         const char *e = getenv("IVFHNSW_TAIL_MAX_NQ");
         return (e && *e) ? (size_t)atol(e) : (size_t)8;
     }();
+    // a label filter: plan, table and the filtered form of the ordinary scan; the one-launch tail and the
+    // pipelined scan have no filtered form
+    const uint32_t *fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
     const bool use_tail =
-        !h->has_group && nq <= tail_max_nq && !d_out_keys && ivf_tail_supported(h->t, nprobe, (int)k);
+        !h->has_group && nq <= tail_max_nq && !d_out_keys && !fmask && ivf_tail_supported(h->t, nprobe, (int)k);
     const size_t tail_kbytes = nq * sizeof(uint64_t);
     h->walk_zeroed = false;
     h->walk_zero_keys = nullptr;
@@ -359,7 +362,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
     if (k == 1 && nq < 1024)
         nsplit = (int)std::min<size_t>(32, (2048 + nq - 1) / nq);
     // list shards: table and scan in one software-pipelined kernel, the table never leaves the chip (kernels_scan3.hip)
-    const bool pipe = k == 1 && !h->has_group && !heap && h->opt_scan_pipe != 0 &&
+    const bool pipe = k == 1 && !h->has_group && !heap && !fmask && h->opt_scan_pipe != 0 &&
                       scan_pipe_supported(h->t, max_seg, (int)nq, nsplit, h->n_local > 0, h->opt_scan_pipe == 1);
     // one GPU, IVFADC: plan and tables are independent of each other and go in ONE launch (kernels_search.hip
     // plan_lut_kernel; IVFHNSW_PLAN_LUT=0 keeps them apart)
@@ -412,9 +415,9 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
             StageScope sc(h, IVFHNSW_STAGE_SCAN);
             HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
                                      h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, nullptr, nullptr, heap_ws,
-                                     d_distances, d_labels));
+                                     d_distances, d_labels, fmask));
         }
-        h->last_scan_kernel = "heap_scan_kernel";
+        h->last_scan_kernel = fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel";
         h->last_nq = (int)nq;
         h->last_max_seg = max_seg;
         h->last_stream = false; // no candidate stream exists
@@ -445,7 +448,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
                                 h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, nsplit, h->w_keys.as<uint64_t>(),
                                 heap ? h->w_stream.as<uint64_t>() : nullptr, heap ? h->w_slen.as<uint32_t>() : nullptr,
                                 heap ? kHeapStreamCap : 0, seg_hint, want_sel ? d_distances : nullptr,
-                                want_sel ? d_labels : nullptr, &scan_selected));
+                                want_sel ? d_labels : nullptr, &scan_selected, fmask));
             h->last_scan_kernel = last_scan_kernel_name();
         }
     }
@@ -463,7 +466,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
                                        h->w_hredo.as<uint32_t>()));
             HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
                                      h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, redo_hdr,
-                                     h->w_hredo.as<uint32_t>(), heap_ws, d_distances, d_labels));
+                                     h->w_hredo.as<uint32_t>(), heap_ws, d_distances, d_labels, fmask));
         } else
             HIP_TRY(launch_select(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), max_seg,
                                   h->w_keys.as<uint64_t>(), (int)nq, (int)k, d_distances, d_labels, d_out_keys));

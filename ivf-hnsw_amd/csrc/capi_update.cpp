@@ -118,6 +118,8 @@ static int append_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const ui
         e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append: %s", hipGetErrorString(e));
+    if ((rc = fresh.mark_filter(h, n_local2)))
+        return rc;
     fresh.install(h, n_local2);
     return IVFHNSW_OK;
 }
@@ -347,7 +349,7 @@ try {
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append_grouping: %s", hipGetErrorString(e));
     // the choice upload_grouping derives from the sizes and the neighbour rows follows the new ones
-    if ((rc = grouping_dedupe_dev(h, sizes2, h->g.nn_idx, &dedupe)))
+    if ((rc = grouping_dedupe_dev(h, sizes2, h->g.nn_idx, &dedupe)) || (rc = fresh.mark_filter(h, n_local2)))
         return rc;
     fresh.install(h, n_local2);
     std::swap(h->g_sizes, h->gp_sizes); // the staging that holds the new sizes becomes the table
@@ -569,6 +571,8 @@ try {
     // Grouping: the choice upload_grouping derives from the sizes follows the new ones
     int dedupe = h->g.dedupe;
     if (grp && (rc = grouping_dedupe_dev(h, h->rm_sizes.as<uint32_t>(), h->g.nn_idx, &dedupe)))
+        return rc;
+    if ((rc = fresh.mark_filter(h, n_local2)))
         return rc;
     fresh.install(h, n_local2);
     if (grp) { // the staging that holds the new sizes becomes the table; the old table the next call's staging

@@ -42,6 +42,7 @@ int upload_tables(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *d, bool need_lists, ui
     if (rc)
         return rc;
     h->has_ivf = false;
+    filter_drop(h); // a filter belongs to the lists it was marked over
     std::vector<uint32_t> loff(d->nc, kNotOwned);
     n_local = 0;
     for (size_t c = 0; c < d->nc; c++) {

@@ -474,4 +474,11 @@ __device__ __forceinline__ void heap_replace_top(int k, float *val, ID *ids, flo
     }
 }
 
+// The pass mask of a label filter as the OPTIONAL last argument of a scan kernel: the kernels end in a
+// parameter pack that is empty (the unfiltered instantiation: its arguments and its code are what they were before the
+// filter existed) or holds the mask, bit r = local row r passes.  A lane loads the 32-bit word of its row beside the
+// row's norm code, so both waits fall together; the lanes of a wavefront read consecutive rows and share one or two words.
+__device__ __forceinline__ const uint32_t *filter_mask() { return nullptr; }
+__device__ __forceinline__ const uint32_t *filter_mask(const uint32_t *m) { return m; }
+
 } // namespace ivfhnsw_gpu_impl

@@ -58,11 +58,73 @@ void set_base_state(const void *ix, const BaseState &st)
 struct DeviceSide {
     unsigned tables_dirty = 0;
     size_t full_uploads = 0;
+    // set_id_filter: the label set, installed on the handle whenever the device copy is made or remade
+    bool has_filter = false, filter_deny = false;
+    std::vector<uint32_t> filter_labels;
 };
 std::mutex g_side_mu;
 std::unordered_map<const void *, DeviceSide> g_side;
 
+size_t shards_wanted() // IVFHNSW_SHARDS=N: N handles, shard r on device r % (devices of the node), lists c % N == r
+{
+    static const size_t n = [] {
+        const char *e = getenv("IVFHNSW_SHARDS");
+        const long v = (e && *e) ? atol(e) : 1;
+        return (size_t)(v < 1 ? 1 : v > 64 ? 64 : v);
+    }();
+    return n;
+}
+
+// the index's label filter onto its handle (upload_ivf has cleared whatever the handle held)
+void install_id_filter(const void *ix, ivfhnsw_gpu *h)
+{
+    bool has = false, deny = false;
+    std::vector<uint32_t> labels;
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(ix);
+        if (it != g_side.end() && it->second.has_filter) {
+            has = true;
+            deny = it->second.filter_deny;
+            labels = it->second.filter_labels;
+        }
+    }
+    if (has && ivfhnsw_gpu_set_filter(h, labels.size(), labels.data(), deny ? IVFHNSW_FILTER_DENY : IVFHNSW_FILTER_ALLOW))
+        gpu_fail("ivfhnsw_gpu_set_filter");
+}
+
 } // namespace
+
+void IndexIVF_HNSW::set_id_filter(size_t n, const idx_t *xids, bool deny)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_filter: IVFHNSW_SHARDS > 1, and sharded handles have no label filter");
+    if (n && !xids)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_filter: null ids");
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        DeviceSide &side = g_side[this];
+        side.has_filter = true;
+        side.filter_deny = deny;
+        side.filter_labels.assign(xids, xids + n);
+    }
+    if (gpu_ && device_current()) // otherwise the next search's upload installs it
+        install_id_filter(this, gpu_);
+}
+
+void IndexIVF_HNSW::clear_id_filter()
+{
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(this);
+        if (it != g_side.end()) {
+            it->second.has_filter = false;
+            std::vector<uint32_t>().swap(it->second.filter_labels);
+        }
+    }
+    if (gpu_ && ivfhnsw_gpu_clear_filter(gpu_))
+        gpu_fail("ivfhnsw_gpu_clear_filter");
+}
 
 unsigned IndexIVF_HNSW::tables_dirty() const
 {
@@ -240,12 +302,7 @@ void IndexIVF_HNSW::device_upload_common()
         throw std::runtime_error("IndexIVF_HNSW: do_opq is set but opq_matrix is null");
     if (pq->centroids.size() != 256 * d || norm_pq->centroids.size() != 256)
         throw std::runtime_error("IndexIVF_HNSW: pq / norm_pq have unexpected shapes");
-    // IVFHNSW_SHARDS=N: N handles, shard r on device r % (devices of the node), lists c % N == r
-    static const size_t want_shards = [] {
-        const char *e = getenv("IVFHNSW_SHARDS");
-        const long v = (e && *e) ? atol(e) : 1;
-        return (size_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-    }();
+    const size_t want_shards = shards_wanted();
     if (nshards() != want_shards) {
         for (ivfhnsw_gpu *sh : shards_)
             ivfhnsw_gpu_destroy(sh);
@@ -313,6 +370,8 @@ void IndexIVF_HNSW::device_upload_common()
     up_quantizer_ = quantizer;
     up_total_ = total;
     up_do_opq_ = do_opq;
+    if (world == 1)
+        install_id_filter(this, gpu_); // upload_ivf dropped the handle's
     std::lock_guard<std::mutex> lk(g_side_mu);
     DeviceSide &side = g_side[this];
     side.tables_dirty = 0;

@@ -142,7 +142,9 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
                        int seg_len_hint = 0,
                        // k = 1: let the scan resolve the winner's label itself where one workgroup sees the whole query;
                        // *did_select tells whether it did (else launch_select has to run)
-                       float *sel_dist = nullptr, int64_t *sel_labels = nullptr, bool *did_select = nullptr); // expected codes per plan segment (0 = unknown): picks the scan form
+                       float *sel_dist = nullptr, int64_t *sel_labels = nullptr, bool *did_select = nullptr, // expected codes per plan segment (0 = unknown): picks the scan form
+                       // non-null: the filtered form of the chosen kernel; bit r = local row r passes (launch_filter_mark)
+                       const uint32_t *fmask = nullptr);
 // table + scan pipelined over queries, for list shards (kernels_scan3.hip)
 bool scan_pipe_supported(const IvfTables &t, int max_seg, int nq, int nsplit, bool has_codes, bool forced = false);
 hipError_t launch_scan_pipe(hipStream_t s, const IvfTables &t, const float *xq, const Seg *segs, const uint32_t *lpos,
@@ -168,7 +170,8 @@ bool heap_scan_lds_tier(int code_size, int k);
 size_t heap_scan_ws_bytes(int code_size, int k, int nq);
 hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
                             const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
-                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels);
+                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
+                            const uint32_t *fmask = nullptr); // non-null: the filtered form, as launch_scan
 // keys -> (distance, label) through the plan; also emits signed-orderable keys when out_keys != null
 hipError_t launch_select(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
                          const uint64_t *keys, int nq, int k, float *dist, int64_t *labels, int64_t *out_keys);
@@ -318,6 +321,14 @@ hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigne
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
                                  const uint32_t *rscan, const uint32_t *kscan, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2,
                                  uint8_t *ncodes2, uint32_t *ids2, uint64_t n_local2);
+// the label bitmap alone, for a caller that keeps it (the search filter below): bits [max_label / 32 + 1 words] zeroed, then
+// the bit of every label set
+hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits);
+// search filter (kernels_filter.hip): mask [ceil(n_local / 64)] words, bit r = row r passes: its id is in the
+// label bitmap (bits null = the empty set), or with deny is not; rows at or beyond n_local are 0.  *count (zeroed here) = the
+// rows that pass.
+hipError_t launch_filter_mark(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
+                              int deny, unsigned long long *mask, unsigned long long *count);
 // additions to a Grouping index (kernels_add_groups.hip).  count: cnt[list] += 1 and sizes2[list][sub] += 1
 // (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  prefix, after launch_append_tables:
 // pre_old / pre_new [nc * nsubc] = exclusive prefix sums of sizes / sizes2 inside every list the batch touches.  merge,

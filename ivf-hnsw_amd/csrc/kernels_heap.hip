@@ -29,14 +29,19 @@ constexpr size_t HS_LDS = 160 * 1024;      // LDS of one workgroup on gfx950
 // static LDS of the kernel (norm table, segments, chunk buffer, counts) with room for alignment
 constexpr size_t HS_STATIC_LDS = 256 * 4 + HS_SEGCAP * sizeof(Seg) + (HS_SEGCAP + 1) * 4 + HS_CHUNK * 8 + HS_U * 4 * 4 + 512;
 
-template <int CS, bool LDS_HEAP>
+// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear never reaches
+// the heap.
+template <int CS, bool LDS_HEAP, class... Mask>
 __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float *__restrict__ luts,
                                                         const Seg *__restrict__ segs, const uint32_t *__restrict__ lpos,
                                                         const PlanHdr *__restrict__ hdr, int max_seg, int nq, int k,
                                                         uint32_t *__restrict__ redo_hdr,
                                                         const uint32_t *__restrict__ redo_list, float *__restrict__ heap_ws,
-                                                        float *__restrict__ dist, long long *__restrict__ labels)
+                                                        float *__restrict__ dist, long long *__restrict__ labels,
+                                                        Mask... fmask_arg)
 {
+    constexpr bool FILT = sizeof...(Mask) != 0;
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     // dynamic LDS: the query's table [csz][256], then (LDS tier) the heap's values [k] and scan positions [k]
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     __shared__ float s_norm[256];
@@ -91,6 +96,7 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                 const float root = val[0]; // the heap is at rest here (barrier behind the last replay)
                 CodeRegs<CS> w[HS_U];
                 uint32_t nbv[HS_U], vp[HS_U];
+                [[maybe_unused]] uint32_t fw[HS_U], fb[HS_U];
                 float ct[HS_U], dn[HS_U];
                 bool ok[HS_U], pass[HS_U];
 #pragma unroll
@@ -119,6 +125,10 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                         const uint32_t gi = seg_start + off;
                         code_fetch<CS>(t.codes, gi, t.M, s_lut, w[u]);
                         nbv[u] = t.norm_codes[gi];
+                        if constexpr (FILT) {
+                            fw[u] = fmask[gi >> 5];
+                            fb[u] = gi & 31u;
+                        }
                         vp[u] = seg_vpos + off;
                         ct[u] = seg_ct;
                     }
@@ -127,6 +137,8 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                 for (int u = 0; u < HS_U; u++) {
                     pass[u] = false;
                     dn[u] = 0.f;
+                    if constexpr (FILT)
+                        ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
                     if (ok[u]) {
                         // scan_topk_kernel's arithmetic, term for term
                         const float sum = code_sum<CS>(s_lut, w[u]);
@@ -234,10 +246,19 @@ template <int CS, bool LDS_HEAP>
 static hipError_t launch_heap_scan_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
                                       const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k,
                                       uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist,
-                                      int64_t *labels)
+                                      int64_t *labels, const uint32_t *fmask)
 {
-    auto *kern = heap_scan_kernel<CS, LDS_HEAP>;
     const size_t shm = (size_t)t.M * 1024 + (LDS_HEAP ? (size_t)8 * k : 0);
+    if (fmask) {
+        auto *fkern = heap_scan_kernel<CS, LDS_HEAP, const uint32_t *>;
+        static DynLdsState fattr_set;
+        if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(fkern, dim3((unsigned)heap_scan_grid(t.M, k, nq)), dim3(256), shm, s, t, luts, segs, lpos, hdr,
+                           max_seg, nq, k, redo_hdr, redo_list, heap_ws, dist, reinterpret_cast<long long *>(labels), fmask);
+        return hipGetLastError();
+    }
+    auto *kern = heap_scan_kernel<CS, LDS_HEAP>;
     static DynLdsState attr_set;
     if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
         return e;
@@ -248,7 +269,7 @@ static hipError_t launch_heap_scan_cs(hipStream_t s, const IvfTables &t, const f
 
 hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
                             const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
-                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels)
+                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels, const uint32_t *fmask)
 {
     if (nq == 0)
         return hipSuccess;
@@ -259,9 +280,9 @@ hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts
         return hipErrorInvalidValue;
 #define IVFHNSW_HEAP_SCAN(CS)                                                                                         \
     return lds ? launch_heap_scan_cs<CS, true>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,     \
-                                               heap_ws, dist, labels)                                                 \
+                                               heap_ws, dist, labels, fmask)                                          \
                : launch_heap_scan_cs<CS, false>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,    \
-                                                heap_ws, dist, labels)
+                                                heap_ws, dist, labels, fmask)
     switch (t.M) {
     case 4: IVFHNSW_HEAP_SCAN(4);
     case 8: IVFHNSW_HEAP_SCAN(8);

@@ -281,15 +281,22 @@ hipError_t launch_remove_max(hipStream_t s, const uint32_t *labels, size_t n, ui
     return hipGetLastError();
 }
 
+hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits)
+{
+    if (hipError_t e = hipMemsetAsync(bits, 0, ((size_t)max_label / 32 + 1) * sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(remove_bits_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, labels, n, bits);
+    return hipGetLastError();
+}
+
 hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *labels, size_t n,
                               uint32_t max_label, uint32_t *bits, unsigned long long *mask, uint32_t *keep)
 {
     if (n == 0 || n_local == 0)
         return hipSuccess;
-    if (hipError_t e = hipMemsetAsync(bits, 0, ((size_t)max_label / 32 + 1) * sizeof(uint32_t), s); e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(remove_bits_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, labels, n, bits);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+    if (hipError_t e = launch_remove_bits(s, labels, n, max_label, bits); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(remove_mark_kernel, dim3(blocks_of(n_local, kRemoveTileRows)), dim3(256), 0, s, t.ids, n_local, bits,
                        max_label, mask, keep);

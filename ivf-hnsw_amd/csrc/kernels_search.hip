@@ -386,7 +386,8 @@ __device__ __forceinline__ void sel_write(const SelOut &so, int q, unsigned long
     so.labels[q] = lb;
 }
 
-template <int CS, int SEGCAP, int U, int THREADS>
+// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear forms no key.
+template <int CS, int SEGCAP, int U, int THREADS, class... Mask>
 __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restrict__ codes,
                                                           const uint8_t *__restrict__ norm_codes,
                                                           const float *__restrict__ luts,
@@ -394,8 +395,11 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
                                                           const Seg *__restrict__ segs,
                                                           const uint32_t *__restrict__ lpos,
                                                           const PlanHdr *__restrict__ hdr, int max_seg, int nsplit,
-                                                          unsigned long long *__restrict__ keys, int cs_rt, SelOut so)
+                                                          unsigned long long *__restrict__ keys, int cs_rt, SelOut so,
+                                                          Mask... fmask_arg)
 {
+    constexpr bool FILT = sizeof...(Mask) != 0;
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     // CS == 0: run-time code size cs_rt, table in dynamic LDS (code sizes without an instantiation of their own)
     __shared__ __attribute__((aligned(16))) float s_lut_fixed[(CS > 0 ? CS : 1) * 256];
     extern __shared__ __attribute__((aligned(16))) float s_lut_dyn[];
@@ -462,6 +466,7 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
         for (uint32_t base = b0; base < b1; base += THREADS * U) {
             CodeRegs<CS> w[U];
             uint32_t nb[U], vp[U];
+            [[maybe_unused]] uint32_t fw[U], fb[U];
             float ct[U];
             bool ok[U];
 #pragma unroll
@@ -507,12 +512,18 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
                     const uint32_t gi = seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
                     nb[u] = norm_codes[gi];
+                    if constexpr (FILT) {
+                        fw[u] = fmask[gi >> 5];
+                        fb[u] = gi & 31u;
+                    }
                     vp[u] = seg_vpos + off;
                     ct[u] = seg_ct;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
+                if constexpr (FILT)
+                    ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
                 if (ok[u]) {
                     float sum;
                     if constexpr (CS > 0)
@@ -563,7 +574,7 @@ constexpr int BM_SEGCAP = 256;
 constexpr int BM_SPANCAP = 8192;
 constexpr int BM_SPANW = BM_SPANCAP / 64;
 
-template <int CS, int U>
+template <int CS, int U, class... Mask> // Mask: see scan_k1_kernel
 __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__restrict__ codes,
                                                              const uint8_t *__restrict__ norm_codes,
                                                              const float *__restrict__ luts,
@@ -571,8 +582,11 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                                                              const Seg *__restrict__ segs,
                                                              const uint32_t *__restrict__ lpos,
                                                              const PlanHdr *__restrict__ hdr, int max_seg, int nsplit,
-                                                             unsigned long long *__restrict__ keys, SelOut so)
+                                                             unsigned long long *__restrict__ keys, SelOut so,
+                                                             Mask... fmask_arg)
 {
+    constexpr bool FILT = sizeof...(Mask) != 0;
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     __shared__ __attribute__((aligned(16))) float s_lut[CS * 256];
     __shared__ float s_norm[256];
     __shared__ __attribute__((aligned(16))) Seg s_seg[BM_SEGCAP];
@@ -675,6 +689,7 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
             for (uint32_t rbase = (b0 - cl) & ~63u; rbase < b1 - cl; rbase += 256 * U) {
                 CodeRegs<CS> w[U];
                 uint32_t nb[U], vp[U];
+                [[maybe_unused]] uint32_t fw[U], fb[U];
                 float ct[U];
                 bool ok[U];
 #pragma unroll
@@ -697,6 +712,10 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                             const uint32_t gi = sg.start + off;
                             code_fetch<CS>(codes, gi, CS, s_lut, w[u]);
                             nb[u] = norm_codes[gi];
+                            if constexpr (FILT) {
+                                fw[u] = fmask[gi >> 5];
+                                fb[u] = gi & 31u;
+                            }
                             vp[u] = sg.vpos + off;
                             ct[u] = sg.cterm;
                         }
@@ -704,6 +723,8 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
+                    if constexpr (FILT)
+                        ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
                     if (ok[u]) {
                         const float sum = code_sum<CS>(s_lut, w[u]);
                         const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
@@ -745,7 +766,7 @@ const char *last_scan_kernel_name() { return g_scan_kernel_name; }
 template <int CS>
 static hipError_t launch_scan_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
                                  const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int nsplit,
-                                 uint64_t *keys, int seg_len_hint, SelOut so, bool *did_select)
+                                 uint64_t *keys, int seg_len_hint, SelOut so, bool *did_select, const uint32_t *fmask)
 {
     if (nsplit != 1)
         so.ids = nullptr; // several workgroups per query meet in an atomic: nobody knows the winner
@@ -753,17 +774,25 @@ static hipError_t launch_scan_cs(hipStream_t s, const IvfTables &t, const float 
     auto *k64 = reinterpret_cast<unsigned long long *>(keys);
     // plans of short segments (Grouping sub-groups, ~16 codes): the bitmap form; whole lists: the position form
     if (seg_len_hint > 0 && seg_len_hint <= 48) {
-        g_scan_kernel_name = "scan_k1_bitmap_kernel";
-        hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts, t.norm_table,
-                           segs, lpos, hdr, max_seg, nsplit, k64, so);
+        g_scan_kernel_name = fmask ? "scan_k1_bitmap_kernel+filter" : "scan_k1_bitmap_kernel";
+        if (fmask)
+            hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4, const uint32_t *>), grid, dim3(256), 0, s, t.codes, t.norm_codes,
+                               luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, so, fmask);
+        else
+            hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts, t.norm_table,
+                               segs, lpos, hdr, max_seg, nsplit, k64, so);
         if (did_select)
             *did_select = so.ids != nullptr;
         return hipGetLastError();
     }
 #define IVFHNSW_SCAN(SEGCAP)                                                                                        \
-    hipLaunchKernelGGL((scan_k1_kernel<CS, SEGCAP, 4, 256>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts,    \
-                       t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, t.M, so)
-    g_scan_kernel_name = "scan_k1_kernel";
+    if (fmask)                                                                                                      \
+        hipLaunchKernelGGL((scan_k1_kernel<CS, SEGCAP, 4, 256, const uint32_t *>), grid, dim3(256), 0, s, t.codes,  \
+                           t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, t.M, so, fmask); \
+    else                                                                                                            \
+        hipLaunchKernelGGL((scan_k1_kernel<CS, SEGCAP, 4, 256>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts, \
+                           t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, t.M, so)
+    g_scan_kernel_name = fmask ? "scan_k1_kernel+filter" : "scan_k1_kernel";
     if (max_seg <= 64) {
         IVFHNSW_SCAN(64);
     } else if (max_seg <= 256) {
@@ -781,12 +810,12 @@ static hipError_t launch_scan_cs(hipStream_t s, const IvfTables &t, const float 
 
 hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
                             const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k, uint64_t *keys,
-                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap);
+                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap, const uint32_t *fmask);
 
 hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
                        const PlanHdr *hdr, int max_seg, int nq, int k, int nsplit, uint64_t *keys, uint64_t *stream,
                        uint32_t *stream_len, uint32_t stream_cap, int seg_len_hint, float *sel_dist, int64_t *sel_labels,
-                       bool *did_select)
+                       bool *did_select, const uint32_t *fmask)
 {
     if (did_select)
         *did_select = false;
@@ -797,19 +826,30 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
     if (nq == 0)
         return hipSuccess;
     if (k != 1) {
-        g_scan_kernel_name = "scan_topk_kernel";
-        return launch_scan_topk(s, t, luts, segs, lpos, hdr, max_seg, nq, k, keys, stream, stream_len, stream_cap);
+        g_scan_kernel_name = fmask ? "scan_topk_kernel+filter" : "scan_topk_kernel";
+        return launch_scan_topk(s, t, luts, segs, lpos, hdr, max_seg, nq, k, keys, stream, stream_len, stream_cap, fmask);
     }
     switch (t.M) {
-    case 4: return launch_scan_cs<4>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select);
-    case 8: return launch_scan_cs<8>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select);
-    case 16: return launch_scan_cs<16>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select);
-    case 32: return launch_scan_cs<32>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select);
+    case 4: return launch_scan_cs<4>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
+    case 8: return launch_scan_cs<8>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
+    case 16: return launch_scan_cs<16>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
+    case 32: return launch_scan_cs<32>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
     default: {
         // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS
         const size_t shm = (size_t)t.M * 1024;
         if (t.M % 4 || shm > kScanDynLdsMax)
             return hipErrorInvalidValue;
+        if (fmask) {
+            g_scan_kernel_name = "scan_k1_kernel (run-time code size)+filter";
+            auto *fkern = scan_k1_kernel<0, 256, 2, 256, const uint32_t *>;
+            static DynLdsState fattr_set;
+            if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
+                return e;
+            hipLaunchKernelGGL(fkern, dim3((unsigned)nq * nsplit), dim3(256), shm, s, t.codes, t.norm_codes, luts, t.norm_table,
+                               segs, lpos, hdr, max_seg, nsplit, reinterpret_cast<unsigned long long *>(keys), t.M,
+                               SelOut{nullptr, nullptr, nullptr}, fmask);
+            return hipGetLastError();
+        }
         g_scan_kernel_name = "scan_k1_kernel (run-time code size)";
         auto *kern = scan_k1_kernel<0, 256, 2, 256>;
         static DynLdsState attr_set;

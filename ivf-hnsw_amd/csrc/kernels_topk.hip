@@ -42,7 +42,9 @@ __device__ __forceinline__ void bitonic_sort_n(unsigned long long *buf, int n, i
     }
 }
 
-template <int CS>
+// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear forms no key, so
+// it enters neither the sort buffer nor the candidate stream.
+template <int CS, class... Mask>
 __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restrict__ codes,
                                                         const uint8_t *__restrict__ norm_codes,
                                                         const float *__restrict__ luts,
@@ -52,8 +54,10 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                                                         unsigned long long *__restrict__ keys,
                                                         unsigned long long *__restrict__ stream,
                                                         uint32_t *__restrict__ stream_len, uint32_t stream_cap,
-                                                        int cs_rt)
+                                                        int cs_rt, Mask... fmask_arg)
 {
+    constexpr bool FILT = sizeof...(Mask) != 0;
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     // CS == 0: run-time code size cs_rt, table in dynamic LDS (see scan_k1_kernel)
     __shared__ __attribute__((aligned(16))) float s_lut_fixed[(CS > 0 ? CS : 1) * 256];
     extern __shared__ __attribute__((aligned(16))) float s_lut_dyn[];
@@ -144,6 +148,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
             bool pass[TK_U];
             CodeRegs<CS> w[TK_U];
             uint32_t nbv[TK_U], vp[TK_U];
+            [[maybe_unused]] uint32_t fw[TK_U], fb[TK_U];
             float ct[TK_U];
             bool ok[TK_U];
 #pragma unroll
@@ -172,6 +177,10 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                     const uint32_t gi = seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
                     nbv[u] = norm_codes[gi];
+                    if constexpr (FILT) {
+                        fw[u] = fmask[gi >> 5];
+                        fb[u] = gi & 31u;
+                    }
                     vp[u] = seg_vpos + off;
                     ct[u] = seg_ct;
                 }
@@ -180,6 +189,8 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
             for (int u = 0; u < TK_U; u++) {
                 pass[u] = false;
                 key[u] = 0;
+                if constexpr (FILT)
+                    ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
                 if (ok[u]) {
                     const float sum = code_sum<CS>(s_lut, w[u]);
                     const float tt = __fadd_rn(ct[u], s_norm[nbv[u]]);
@@ -368,15 +379,21 @@ hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs
 
 hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
                             const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k, uint64_t *keys,
-                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap)
+                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap, const uint32_t *fmask)
 {
     if (k < 1 || k > TK_KCAP)
         return hipErrorInvalidValue;
     dim3 grid((unsigned)nq), block(256);
     auto *k64 = reinterpret_cast<unsigned long long *>(keys);
 #define IVFHNSW_TOPK(CS)                                                                                              \
-    hipLaunchKernelGGL((scan_topk_kernel<CS>), grid, block, 0, s, t.codes, t.norm_codes, luts, t.norm_table, segs, lpos, \
-                       hdr, max_seg, k, k64, reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M)
+    if (fmask)                                                                                                        \
+        hipLaunchKernelGGL((scan_topk_kernel<CS, const uint32_t *>), grid, block, 0, s, t.codes, t.norm_codes, luts,  \
+                           t.norm_table, segs, lpos, hdr, max_seg, k, k64,                                            \
+                           reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M, fmask);       \
+    else                                                                                                              \
+        hipLaunchKernelGGL((scan_topk_kernel<CS>), grid, block, 0, s, t.codes, t.norm_codes, luts, t.norm_table, segs, \
+                           lpos, hdr, max_seg, k, k64, reinterpret_cast<unsigned long long *>(stream), stream_len,    \
+                           stream_cap, t.M)
     switch (t.M) {
     case 4: IVFHNSW_TOPK(4); break;
     case 8: IVFHNSW_TOPK(8); break;
@@ -386,6 +403,15 @@ hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts
         const size_t shm = (size_t)t.M * 1024;
         if (t.M % 4 || shm > kScanDynLdsMax)
             return hipErrorInvalidValue;
+        if (fmask) {
+            auto *fkern = scan_topk_kernel<0, const uint32_t *>;
+            static DynLdsState fattr_set;
+            if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
+                return e;
+            hipLaunchKernelGGL(fkern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg,
+                               k, k64, reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M, fmask);
+            break;
+        }
         auto *kern = scan_topk_kernel<0>;
         static DynLdsState attr_set;
         if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
