@@ -67,10 +67,10 @@ int drain_events(ivfhnsw_gpu *h)
 int check_status(ivfhnsw_gpu *h)
 {
     uint32_t st = 0;
-    HIP_TRY(hipMemcpy(&st, h->w_status.p, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, &status_words(h)->bits, sizeof(st), hipMemcpyDeviceToHost));
     if (!st)
         return IVFHNSW_OK;
-    HIP_TRY(hipMemset(h->w_status.p, 0, sizeof(st)));
+    HIP_TRY(hipMemset(&status_words(h)->bits, 0, sizeof(st)));
     if (st & kStatusHnswTieOverflow)
         return fail(IVFHNSW_ERR_STATE, "HNSW walk: more than 64 candidates tie exactly with the efSearch-th "
                                        "distance; results of this batch are invalid");
@@ -174,9 +174,7 @@ int ivfhnsw_gpu_create(int device, ivfhnsw_gpu **out)
     }
     h->own_stream = true;
     h->split_pm = split_permille_env();
-    // [0] status bits, [1] the walk's query counter, [2] queries on the redo list, [3] the redo launch's counter, [4] its exit count,
-    // [5] heap-order queries whose candidate stream overflowed (heap_scan_kernel redoes them), [6] that launch's exit count
-    if (h->w_status.ensure(8 * sizeof(uint32_t)) || hipMemset(h->w_status.p, 0, 8 * sizeof(uint32_t)) != hipSuccess) {
+    if (h->w_status.ensure(sizeof(StatusWords)) || hipMemset(h->w_status.p, 0, sizeof(StatusWords)) != hipSuccess) {
         ivfhnsw_gpu_destroy(h);
         return fail(IVFHNSW_ERR_HIP, "cannot allocate the device status word");
     }

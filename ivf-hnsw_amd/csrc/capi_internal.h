@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <new>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -83,6 +84,35 @@ struct StageEvent {
     hipEvent_t a, b;
 };
 
+// The handle's w_status buffer.  check_status reads `bits`; the rest are counters that live on the device between
+// launches and that the launch which used them leaves zero.  The launchers take the address of a member and reach its
+// neighbours from there, hence the asserts.
+struct StatusWords {
+    uint32_t bits;            // kStatus* (ivfhnsw_kernels.h)
+    uint32_t walk_next;       // the walk's query counter (launch_coarse: next_query, followed by the redo header)
+    uint32_t redo_len;        // the walk's redo header: queries on the redo list,
+    uint32_t redo_next;       // ... the redo launch's counter,
+    uint32_t redo_exits;      // ... its exit count
+    uint32_t heap_redo_len;   // heap-order queries whose candidate stream overflowed (heap_scan_kernel redoes them),
+    uint32_t heap_redo_exits; // ... that launch's exit count
+    uint32_t pad;
+};
+static_assert(offsetof(StatusWords, redo_len) == offsetof(StatusWords, walk_next) + 4 &&
+                  offsetof(StatusWords, redo_next) == offsetof(StatusWords, walk_next) + 8 &&
+                  offsetof(StatusWords, redo_exits) == offsetof(StatusWords, walk_next) + 12,
+              "launch_coarse: next_query is followed by the three words of the redo header");
+static_assert(offsetof(StatusWords, heap_redo_exits) == offsetof(StatusWords, heap_redo_len) + 4, "launch_heap_scan: redo_hdr[0..1]");
+static_assert(offsetof(StatusWords, bits) == 0 && sizeof(StatusWords) == 8 * sizeof(uint32_t), "8 words, bits first");
+
+// What the host knows about the walk's scratch between calls (walk_scratch, capi_search.cpp; the launchers update the
+// two flags through the pointers they take).
+struct WalkScratch {
+    bool zero = false;          // every byte of w_visited is zero (the walk's overflow bitmaps, kernels_hnsw.hip)
+    void *zero_ptr = nullptr;   // ... of this allocation
+    size_t zero_bytes = 0;
+    bool counters_clean = true; // StatusWords walk_next .. redo_exits are zero (ivfhnsw_gpu_create clears them, the redo launch's last wavefront restores it)
+};
+
 } // namespace ivfhnsw_gpu_impl
 
 using namespace ivfhnsw_gpu_impl;
@@ -107,7 +137,7 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
-    X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_counter) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
+    X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
 
 struct ivfhnsw_gpu {
@@ -156,23 +186,14 @@ struct ivfhnsw_gpu {
     uint32_t *status_shared = nullptr; // the internal split view raises its status bits in the PARENT's word (no merge launch)
     size_t last_parts[2] = {0, 0}; // queries in the two parts of the last search_dev call (second 0 = one part)
     int split_pm = 0; // permille of a large batch in its first part; 0 = one part (ivfhnsw_gpu_set_batch_split)
-    bool walk_counters_clean = true;  // w_status[1..4] are zero (ivfhnsw_gpu_create clears them, the redo launch's last wavefront restores it)
-    bool visited_zero = false;        // every byte of w_visited is zero (the walk's overflow bitmaps, kernels_hnsw.hip)
-    void *visited_zero_ptr = nullptr; // ... of this allocation
-    size_t visited_zero_bytes = 0;
-    int opt_scan_pipe = -1;      // ivfhnsw_gpu_set_option "scan_pipe"
-    int opt_exact_splits = -1;   // ... "exact_splits"
-    bool lat_defer_redo = false; // host-pointer small batches: the latency walk flags a tie overflow, the call repeats itself
-    bool latency_off = false;    // ... on the throughput walk
+    WalkScratch walk;
+    int opt_scan_pipe = -1;    // ivfhnsw_gpu_set_option "scan_pipe"
+    int opt_exact_splits = -1; // ... "exact_splits"
 
+    // the plan the last search_dev chunk left (remember_plan, capi_search.cpp)
     int last_nq = 0, last_max_seg = 0;
     const char *last_scan_kernel = "";
-    uint32_t *tail_status_out = nullptr; // pinned word the tail kernel copies the status into (host-pointer path)
-    bool tail_wrote_status = false;
-    uint64_t *walk_zero_keys = nullptr; // the tail kernel's meeting words, cleared by the latency walk when it runs
-    uint32_t *walk_zero_done = nullptr;
-    bool walk_zeroed = false;
-    bool last_stream = false; // the last search left a candidate stream (k > 1, heap_order)
+    bool last_stream = false; // ... and a candidate stream (k > 1, heap_order)
 
     int profiling = 0; // 0 off, 1 every stage, 2 only the scan (an event pair costs ~7 us of stream time)
     std::vector<StageEvent> pending;
@@ -192,7 +213,8 @@ int drain_events(ivfhnsw_gpu *h);
 int check_status(ivfhnsw_gpu *h);
 
 // the word the kernels of this handle raise status bits in
-inline uint32_t *status_word(ivfhnsw_gpu *h) { return h->status_shared ? h->status_shared : h->w_status.as<uint32_t>(); }
+inline StatusWords *status_words(ivfhnsw_gpu *h) { return h->w_status.as<StatusWords>(); }
+inline uint32_t *status_word(ivfhnsw_gpu *h) { return h->status_shared ? h->status_shared : &status_words(h)->bits; }
 
 // a view reads its parent's tables: what create_view copies once and a split batch before every call (uploads and
 // in-place updates since the view's creation included)

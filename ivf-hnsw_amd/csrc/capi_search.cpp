@@ -1,8 +1,75 @@
 // The batched search pipeline (rotate -> coarse -> table -> plan -> scan -> select) and its host-pointer entry points.
 #include "capi_internal.h"
 
-int ivfhnsw_gpu_coarse_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t nprobe, size_t efSearch,
-                           uint32_t *d_coarse_ids, float *d_coarse_dists)
+// What one search call asks of the stages below it; the default is a plain search_dev / coarse_dev call.
+struct SearchCall {
+    uint32_t *status_out = nullptr; // in: pinned word the tail kernel copies the status into (host-pointer path)
+    bool defer_redo = false;        // in: the latency walk only flags a tie overflow, the caller repeats the call ...
+    bool no_latency = false;        // in: ... with this set, on the throughput walk
+    bool wrote_status = false;      // out: the tail kernel wrote *status_out
+};
+
+// The tail kernel's per-query meeting words, which the latency walk clears on its way when it runs.
+struct WalkClear {
+    uint64_t *keys = nullptr; // in
+    uint32_t *done = nullptr; // in
+    bool cleared = false;     // out
+};
+
+// a size from the environment, def when unset or empty; every caller reads its knob once per process
+static size_t env_size(const char *name, size_t def)
+{
+    const char *e = getenv(name);
+    return (e && *e) ? (size_t)atol(e) : def;
+}
+
+// what ivfhnsw_gpu_search, ivfhnsw_gpu_search_keys and every chunk of search_dev check first, behind bind
+static int search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, size_t k)
+{
+    if (!h->has_ivf)
+        return fail(IVFHNSW_ERR_STATE, "search before upload_ivf");
+    if (!p || p->nprobe == 0 || k == 0)
+        return fail(IVFHNSW_ERR_INVALID, "nprobe and k must be positive");
+    return IVFHNSW_OK;
+}
+
+// The host-pointer entry points: a staging buffer of `bytes` filled from host memory, and one copied back to it, on the
+// handle's stream.
+static int stage_in(ivfhnsw_gpu *h, DevBuf &b, const void *src, size_t bytes)
+{
+    int rc = b.ensure(bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    return IVFHNSW_OK;
+}
+
+static int stage_out(ivfhnsw_gpu *h, void *dst, const DevBuf &b, size_t bytes)
+{
+    HIP_TRY(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    return IVFHNSW_OK;
+}
+
+// Scratch of the walk (h->walk) for nslots queries in flight, `words` of bitmap each: first half the visited bitmaps
+// (the LDS set's overflow store), second half the tail bitmaps of the redo form (walk_set.h TailSpill) -- always at the
+// middle of the ALLOCATION, so that no launch's visited area ever overlaps them; both halves zero between launches
+static int walk_scratch(ivfhnsw_gpu *h, size_t words, size_t nslots, size_t nq, uint32_t **tails)
+{
+    int rc = h->w_visited.ensure(words * sizeof(uint32_t) * std::max<size_t>(nslots, 64) * 2);
+    if (rc)
+        return rc;
+    if (h->w_visited.p != h->walk.zero_ptr || h->w_visited.bytes != h->walk.zero_bytes) {
+        HIP_TRY(hipMemsetAsync(h->w_visited.p, 0, h->w_visited.bytes, h->stream)); // (re)allocated: contents unknown
+        h->walk.zero = true;
+        h->walk.zero_ptr = h->w_visited.p;
+        h->walk.zero_bytes = h->w_visited.bytes;
+    }
+    *tails = reinterpret_cast<uint32_t *>(h->w_visited.as<char>() + h->w_visited.bytes / 2);
+    return h->w_redo.ensure(nq * sizeof(uint32_t));
+}
+
+static int coarse_dev_impl(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t nprobe, size_t efSearch,
+                           uint32_t *d_coarse_ids, float *d_coarse_dists, const SearchCall &call, WalkClear &meet)
 {
     int rc = bind(h);
     if (rc)
@@ -22,57 +89,42 @@ int ivfhnsw_gpu_coarse_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, si
     const size_t words = ((((size_t)h->gr.n + 31) / 32) + 3) & ~(size_t)3;
     StageScope sc(h, IVFHNSW_STAGE_COARSE);
     // few queries (the reference's drivers: one per call): a workgroup per query on the fat graph, when it was prepared
-    static const size_t lat_max_nq = [] {
-        const char *e = getenv("IVFHNSW_LATENCY_MAX_NQ");
-        return (e && *e) ? (size_t)atol(e) : (size_t)256;
-    }();
-    // scratch of the walk: first half the visited bitmaps (the LDS set's overflow store), second half the tail bitmaps
-    // of the redo form (walk_set.h TailSpill) -- always at the middle of the ALLOCATION, so that no launch's visited area
-    // ever overlaps them; both halves zero between launches
-    auto walk_scratch = [&](size_t nslots, uint32_t **tails) -> int {
-        int r = h->w_visited.ensure(words * sizeof(uint32_t) * std::max<size_t>(nslots, 64) * 2);
-        if (r)
-            return r;
-        if (h->w_visited.p != h->visited_zero_ptr || h->w_visited.bytes != h->visited_zero_bytes) {
-            HIP_TRY(hipMemsetAsync(h->w_visited.p, 0, h->w_visited.bytes, h->stream)); // (re)allocated: contents unknown
-            h->visited_zero = true;
-            h->visited_zero_ptr = h->w_visited.p;
-            h->visited_zero_bytes = h->w_visited.bytes;
-        }
-        *tails = reinterpret_cast<uint32_t *>(h->w_visited.as<char>() + h->w_visited.bytes / 2);
-        return h->w_redo.ensure(nq * sizeof(uint32_t));
-    };
+    static const size_t lat_max_nq = env_size("IVFHNSW_LATENCY_MAX_NQ", 256);
+    StatusWords *st = status_words(h);
     uint32_t *tails = nullptr;
-    if (!h->latency_off && nq <= lat_max_nq && coarse_latency_supported(h->gr, (int)efSearch)) {
-        uint32_t *hdr = h->w_status.as<uint32_t>() + 2;
-        const bool defer = h->lat_defer_redo; // the caller synchronises and reads the status word itself
+    if (!call.no_latency && nq <= lat_max_nq && coarse_latency_supported(h->gr, (int)efSearch)) {
+        uint32_t *hdr = &st->redo_len;
+        const bool defer = call.defer_redo; // the caller synchronises and reads the status word itself
         if (!defer) {
-            if ((rc = walk_scratch(64, &tails)))
+            if ((rc = walk_scratch(h, words, 64, nq, &tails)))
                 return rc;
             HIP_TRY(hipMemsetAsync(hdr, 0, 3 * sizeof(uint32_t), h->stream)); // length, counter, exit count
         }
         HIP_TRY(launch_coarse_latency(h->stream, h->gr, d_queries, (int)nq, (int)nprobe, (int)efSearch, d_coarse_ids,
-                                      d_coarse_dists, status_word(h), h->walk_zero_keys, h->walk_zero_done,
-                                      defer ? nullptr : hdr, defer ? nullptr : h->w_redo.as<uint32_t>()));
-        h->walk_zeroed = h->walk_zero_keys != nullptr;
-        h->walk_zero_keys = nullptr; // consumed: set by search_dev right before the call, never carried over
-        h->walk_zero_done = nullptr;
+                                      d_coarse_dists, status_word(h), meet.keys, meet.done, defer ? nullptr : hdr,
+                                      defer ? nullptr : h->w_redo.as<uint32_t>()));
+        meet.cleared = meet.keys != nullptr;
         if (!defer)
             HIP_TRY(launch_coarse_redo(h->stream, h->gr, d_queries, (int)nq, (int)nprobe, (int)efSearch, d_coarse_ids,
                                        d_coarse_dists, h->w_visited.as<uint32_t>(), words, status_word(h), hdr,
                                        h->w_redo.as<uint32_t>(), tails, 64));
         return IVFHNSW_OK;
     }
-    {
-        const int nslots = (int)std::min<size_t>(nq, (size_t)coarse_slots_for((int)efSearch));
-        if ((rc = walk_scratch((size_t)nslots, &tails)))
-            return rc;
-        HIP_TRY(launch_coarse(h->stream, h->gr, d_queries, (int)nq, (int)nprobe, (int)efSearch, d_coarse_ids,
-                              d_coarse_dists, h->w_visited.as<uint32_t>(), words, nslots, status_word(h),
-                              h->w_status.as<uint32_t>() + 1, h->w_visited.bytes / 2, &h->visited_zero,
-                              h->w_redo.as<uint32_t>(), tails, 64, &h->walk_counters_clean));
-    }
+    const int nslots = (int)std::min<size_t>(nq, (size_t)coarse_slots_for((int)efSearch));
+    if ((rc = walk_scratch(h, words, (size_t)nslots, nq, &tails)))
+        return rc;
+    HIP_TRY(launch_coarse(h->stream, h->gr, d_queries, (int)nq, (int)nprobe, (int)efSearch, d_coarse_ids, d_coarse_dists,
+                          h->w_visited.as<uint32_t>(), words, nslots, status_word(h), &st->walk_next,
+                          h->w_visited.bytes / 2, &h->walk.zero, h->w_redo.as<uint32_t>(), tails, 64,
+                          &h->walk.counters_clean));
     return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_coarse_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t nprobe, size_t efSearch,
+                           uint32_t *d_coarse_ids, float *d_coarse_dists)
+{
+    WalkClear meet;
+    return coarse_dev_impl(h, nq, d_queries, nprobe, efSearch, d_coarse_ids, d_coarse_dists, SearchCall(), meet);
 }
 
 int ivfhnsw_gpu_rotate_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, float *d_out)
@@ -108,25 +160,34 @@ int ivfhnsw_gpu_coarse(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t k
     if (!queries || !ids || !dists || k == 0)
         return fail(IVFHNSW_ERR_INVALID, "null buffer or k == 0");
     const size_t d = h->gr.d;
-    if ((rc = h->s_q.ensure(nq * d * sizeof(float))))
+    if ((rc = h->s_cid.ensure(nq * k * sizeof(uint32_t))) || (rc = h->s_cd.ensure(nq * k * sizeof(float))) ||
+        (rc = stage_in(h, h->s_q, queries, nq * d * sizeof(float))) ||
+        (rc = ivfhnsw_gpu_coarse_dev(h, nq, h->s_q.as<float>(), k, efSearch, h->s_cid.as<uint32_t>(), h->s_cd.as<float>())) ||
+        (rc = stage_out(h, ids, h->s_cid, nq * k * sizeof(uint32_t))) ||
+        (rc = stage_out(h, dists, h->s_cd, nq * k * sizeof(float))))
         return rc;
-    if ((rc = h->s_cid.ensure(nq * k * sizeof(uint32_t))))
-        return rc;
-    if ((rc = h->s_cd.ensure(nq * k * sizeof(float))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(h->s_q.p, queries, nq * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ivfhnsw_gpu_coarse_dev(h, nq, h->s_q.as<float>(), k, efSearch, h->s_cid.as<uint32_t>(),
-                                     h->s_cd.as<float>())))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ids, h->s_cid.p, nq * k * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(dists, h->s_cd.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return check_status(h);
 }
 
-static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
-                            const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
-                            int64_t *d_labels, int64_t *d_out_keys);
+// The arguments of ivfhnsw_gpu_search_dev, handed down as one.
+struct SearchArgs {
+    size_t nq, k;
+    const float *d_queries;
+    const uint32_t *d_coarse_ids;
+    const float *d_coarse_dists;
+    const ivfhnsw_search_params *p;
+    float *d_distances;
+    int64_t *d_labels, *d_out_keys;
+    SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
+    {
+        return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
+                d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k, d_labels + q0 * k,
+                d_out_keys};
+    }
+};
+
+static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call);
 
 // One large batch as TWO uneven parts on two streams.  The walk's resident wavefronts pull queries from a counter, so a
 // launch ends with a tail of partly idle CUs (10 000 queries on 4096 slots: 2.44 "rounds"), and the scan can only start
@@ -165,9 +226,9 @@ static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params
     return (int)std::min(900.0, std::max(400.0, share * 1000.0 + 0.5));
 }
 
-static int search_dev_split(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const ivfhnsw_search_params *p,
-                            float *d_distances, int64_t *d_labels)
+static int search_dev_split(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call)
 {
+    const size_t nq = a.nq;
     int rc = bind(h);
     if (rc)
         return rc;
@@ -181,21 +242,18 @@ static int search_dev_split(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
     // the view follows the handle's tables (uploads since its creation included)
     follow_parent(v, h);
     v->profiling = h->profiling;
-    v->status_shared = h->w_status.as<uint32_t>();
+    v->status_shared = &status_words(h)->bits;
     // the second part: ~22 % of the batch, in whole "rounds" of the scan's resident workgroups (8 per CU x 256 CUs): its
     // scan runs alone at the end of the step, and 2200 workgroups on 2048 slots would take two rounds for one
     const size_t round_wgs = 2048;
-    const int pm = h->split_pm == kSplitAuto ? auto_split_permille(h, p) : h->split_pm;
+    const int pm = h->split_pm == kSplitAuto ? auto_split_permille(h, a.p) : h->split_pm;
     size_t n2 = ((nq * (size_t)(1000 - pm) / 1000 + round_wgs / 2) / round_wgs) * round_wgs;
     n2 = std::max(round_wgs, std::min(n2, nq / 2));
     const size_t n1 = nq - n2;
-    const size_t d = (size_t)h->t.d;
     HIP_TRY(hipEventRecord(h->split_fork, h->stream));
     HIP_TRY(hipStreamWaitEvent(v->stream, h->split_fork, 0));
-    rc = search_dev_chunk(h, n1, k, d_queries, nullptr, nullptr, p, d_distances, d_labels, nullptr);
-    int rc2 = rc ? rc
-                 : search_dev_chunk(v, nq - n1, k, d_queries + n1 * d, nullptr, nullptr, p, d_distances + n1 * k,
-                                    d_labels + n1 * k, nullptr);
+    rc = search_dev_chunk(h, a.slice(0, n1, (size_t)h->t.d), call);
+    int rc2 = rc ? rc : search_dev_chunk(v, a.slice(n1, n2, (size_t)h->t.d), call);
     // (whatever the second part flags it raises in the handle's own status word: v->status_shared)
     // the join itself, always (the fork was recorded)
     (void)hipSetDevice(h->device);
@@ -207,274 +265,299 @@ static int search_dev_split(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_
     return rc2;
 }
 
-static int search_dev_part(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
-                           const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
-                           int64_t *d_labels, int64_t *d_out_keys)
+static int search_dev_part(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call)
 {
     if (h) {
         h->last_split = false;
-        h->last_parts[0] = nq;
+        h->last_parts[0] = a.nq;
         h->last_parts[1] = 0;
     }
-    const bool split = h && p && !h->is_view && h->split_pm > 0 && nq >= kSplitMinNq && !d_coarse_ids &&
-                       !d_out_keys && !(p->heap_order && k > 1) && h->has_ivf && h->has_graph && p->nprobe > 0 && k > 0 &&
-                       k <= 1024 && d_queries && d_distances && d_labels;
-    if (split)
-        return search_dev_split(h, nq, k, d_queries, p, d_distances, d_labels);
-    return search_dev_chunk(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
+    const bool split = h && a.p && !h->is_view && h->split_pm > 0 && a.nq >= kSplitMinNq && !a.d_coarse_ids &&
+                       !a.d_out_keys && !(a.p->heap_order && a.k > 1) && h->has_ivf && h->has_graph && a.p->nprobe > 0 &&
+                       a.k > 0 && a.k <= 1024 && a.d_queries && a.d_distances && a.d_labels;
+    return split ? search_dev_split(h, a, call) : search_dev_chunk(h, a, call);
 }
 
-int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
-                           const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
-                           int64_t *d_labels, int64_t *d_out_keys)
+static int search_dev_impl(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call)
 {
-    const size_t kMaxBatch = (p && p->heap_order && k > 1) ? kMaxBatchAll / 8 : kMaxBatchAll;
-    if (nq <= kMaxBatch || !h || !p)
-        return search_dev_part(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
-    if (d_out_keys)
+    const size_t kMaxBatch = (a.p && a.p->heap_order && a.k > 1) ? kMaxBatchAll / 8 : kMaxBatchAll;
+    if (a.nq <= kMaxBatch || !h || !a.p)
+        return search_dev_part(h, a, call);
+    if (a.d_out_keys)
         return fail(IVFHNSW_ERR_INVALID, "sharded search (out_keys) is limited to %zu queries per call", kMaxBatch);
-    const size_t d = (size_t)h->t.d;
-    for (size_t q0 = 0; q0 < nq; q0 += kMaxBatch) {
-        const size_t n = std::min(kMaxBatch, nq - q0);
-        int rc = search_dev_part(h, n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
-                                 d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k,
-                                 d_labels + q0 * k, nullptr);
+    for (size_t q0 = 0; q0 < a.nq; q0 += kMaxBatch) {
+        int rc = search_dev_part(h, a.slice(q0, std::min(kMaxBatch, a.nq - q0), (size_t)h->t.d), call);
         if (rc)
             return rc;
     }
     return IVFHNSW_OK;
 }
 
-static int search_dev_chunk(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
-                            const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
-                            int64_t *d_labels, int64_t *d_out_keys)
+int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                           const float *d_coarse_dists, const ivfhnsw_search_params *p, float *d_distances,
+                           int64_t *d_labels, int64_t *d_out_keys)
+{
+    SearchCall call;
+    return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
+}
+
+// One chunk on its way through the stages below: its arguments, and what a stage leaves for the later ones.
+struct Chunk : SearchArgs {
+    int nprobe, max_seg, plan_k;    // chunk_workspace
+    bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
+    const uint32_t *fmask;          // a label filter
+    const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
+    const uint32_t *cid;
+    const float *cd;
+    bool use_tail;                  // ... everything behind them in one launch (chunk_tail),
+    WalkClear meet;                 // ... whose meeting words the walk may have cleared
+    int nsplit;                     // chunk_plan_table: workgroups per query,
+    bool heap, pipe;                // ... heap order with a stream, table and scan in one pipelined kernel
+};
+
+static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_stream, const char *kernel_name)
+{
+    h->last_scan_kernel = kernel_name;
+    h->last_nq = (int)nq;
+    h->last_max_seg = max_seg;
+    h->last_stream = has_stream;
+}
+
+static int chunk_checks(ivfhnsw_gpu *h, const Chunk &c)
 {
     int rc = bind(h);
-    if (rc)
+    if (rc || (rc = search_args_guard(h, c.p, c.k)))
         return rc;
-    if (!h->has_ivf)
-        return fail(IVFHNSW_ERR_STATE, "search before upload_ivf");
-    if (!p || p->nprobe == 0 || k == 0)
-        return fail(IVFHNSW_ERR_INVALID, "nprobe and k must be positive");
-    if ((d_coarse_ids == nullptr) != (d_coarse_dists == nullptr))
+    if ((c.d_coarse_ids == nullptr) != (c.d_coarse_dists == nullptr))
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
-    if (nq > 0 && (!d_queries || !d_distances || !d_labels))
+    if (c.nq > 0 && (!c.d_queries || !c.d_distances || !c.d_labels))
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
     // k > 1024 only in heap order on the labels path: heap_scan_kernel, no stream
-    if (k > 1024 && (!p->heap_order || d_out_keys))
-        return fail(IVFHNSW_ERR_INVALID, "k %zu > 1024 unsupported (only heap_order = 1 without out_keys)", k);
-    if (nq > 0x7fffffffull / (k > p->nprobe ? k : p->nprobe))
+    if (c.k > 1024 && (!c.p->heap_order || c.d_out_keys))
+        return fail(IVFHNSW_ERR_INVALID, "k %zu > 1024 unsupported (only heap_order = 1 without out_keys)", c.k);
+    if (c.nq > 0x7fffffffull / (c.k > c.p->nprobe ? c.k : c.p->nprobe))
         return fail(IVFHNSW_ERR_INVALID, "nq too large");
     if (h->has_group && !h->has_graph)
         return fail(IVFHNSW_ERR_STATE, "Grouping search needs upload_quantizer (sub-centroid distances)");
     if (h->has_graph && (h->gr.d != h->t.d || h->gr.n != h->t.nc))
         return fail(IVFHNSW_ERR_STATE, "quantizer (%u x %d) does not match the index (%u x %d)", h->gr.n, h->gr.d,
                     h->t.nc, h->t.d);
-    h->last_nq = 0;
-    if (nq == 0)
-        return IVFHNSW_OK;
+    return IVFHNSW_OK;
+}
 
-    const int d = h->t.d, M = h->t.M, nprobe = (int)p->nprobe;
-    const int max_seg = h->has_group ? nprobe * h->g.nsubc : nprobe;
-    // k > 1024: the heap-order scan only (no top-k keys, no stream); the plan kernels reset one key per query
-    const bool heap_big = k > 1024;
-    const int plan_k = heap_big ? 1 : (int)k;
-    if ((rc = h->w_segs.ensure(nq * (size_t)max_seg * sizeof(Seg))))
+static int chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
+{
+    c.nprobe = (int)c.p->nprobe;
+    c.max_seg = h->has_group ? c.nprobe * h->g.nsubc : c.nprobe;
+    c.heap_big = c.k > 1024;
+    c.plan_k = c.heap_big ? 1 : (int)c.k; // the plan kernels reset one key per query
+    c.fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
+    int rc;
+    if ((rc = h->w_segs.ensure(c.nq * (size_t)c.max_seg * sizeof(Seg))) ||
+        (rc = h->w_lpos.ensure(c.nq * (size_t)c.max_seg * sizeof(uint32_t))) ||
+        (rc = h->w_hdr.ensure(c.nq * sizeof(PlanHdr))) ||
+        (rc = h->w_keys.ensure(c.nq * (size_t)c.plan_k * sizeof(uint64_t))) ||
+        (rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
-    if ((rc = h->w_lpos.ensure(nq * (size_t)max_seg * sizeof(uint32_t))))
-        return rc;
-    if ((rc = h->w_hdr.ensure(nq * sizeof(PlanHdr))))
-        return rc;
-    if ((rc = h->w_keys.ensure(nq * (size_t)plan_k * sizeof(uint64_t))))
-        return rc;
-    if ((rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
-        return rc;
+    return IVFHNSW_OK;
+}
 
-    // 1. rotate (IndexIVF_HNSW.cpp:240)
-    const float *xq = d_queries;
+// 1. rotate (IndexIVF_HNSW.cpp:240), 2. coarse (IndexIVF_HNSW.cpp:248-259)
+static int chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call)
+{
+    const size_t nq = c.nq;
+    int rc;
+    c.xq = c.d_queries;
     if (h->t.opq_At) {
-        if ((rc = h->w_xq.ensure(nq * (size_t)d * sizeof(float))))
+        if ((rc = h->w_xq.ensure(nq * (size_t)h->t.d * sizeof(float))))
             return rc;
         StageScope sc(h, IVFHNSW_STAGE_OPQ);
-        HIP_TRY(launch_opq(h->stream, h->t.opq_At, d_queries, h->w_xq.as<float>(), (int)nq, d));
-        xq = h->w_xq.as<float>();
+        HIP_TRY(launch_opq(h->stream, h->t.opq_At, c.d_queries, h->w_xq.as<float>(), (int)nq, h->t.d));
+        c.xq = h->w_xq.as<float>();
     }
     // small IVFADC batches: everything behind the coarse stage in one launch (kernels_tail.hip); its per-query
-    // meeting words are cleared by the latency walk when that runs, by a memset otherwise
-    static const size_t tail_max_nq = [] {
-        const char *e = getenv("IVFHNSW_TAIL_MAX_NQ");
-        return (e && *e) ? (size_t)atol(e) : (size_t)8;
-    }();
-    // a label filter: plan, table and the filtered form of the ordinary scan; the one-launch tail and the
-    // pipelined scan have no filtered form
-    const uint32_t *fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
-    const bool use_tail =
-        !h->has_group && nq <= tail_max_nq && !d_out_keys && !fmask && ivf_tail_supported(h->t, nprobe, (int)k);
-    const size_t tail_kbytes = nq * sizeof(uint64_t);
-    h->walk_zeroed = false;
-    h->walk_zero_keys = nullptr;
-    h->walk_zero_done = nullptr;
-    if (use_tail) {
-        if ((rc = h->w_tail.ensure(tail_kbytes + nq * sizeof(uint32_t))))
+    // meeting words are cleared by the latency walk when that runs, by a memset otherwise.  The one-launch tail and the
+    // pipelined scan have no filtered form.
+    static const size_t tail_max_nq = env_size("IVFHNSW_TAIL_MAX_NQ", 8);
+    c.use_tail = !h->has_group && nq <= tail_max_nq && !c.d_out_keys && !c.fmask &&
+                 ivf_tail_supported(h->t, c.nprobe, (int)c.k);
+    if (c.use_tail) {
+        if ((rc = h->w_tail.ensure(nq * (sizeof(uint64_t) + sizeof(uint32_t)))))
             return rc;
-        h->walk_zero_keys = h->w_tail.as<uint64_t>();
-        h->walk_zero_done = reinterpret_cast<uint32_t *>(h->w_tail.as<char>() + tail_kbytes);
+        c.meet.keys = h->w_tail.as<uint64_t>();
+        c.meet.done = reinterpret_cast<uint32_t *>(c.meet.keys + nq);
     }
-    // 2. coarse (IndexIVF_HNSW.cpp:248-259)
-    const uint32_t *cid = d_coarse_ids;
-    const float *cd = d_coarse_dists;
-    if (!cid) {
-        if ((rc = h->w_cid.ensure(nq * (size_t)nprobe * sizeof(uint32_t))))
+    c.cid = c.d_coarse_ids;
+    c.cd = c.d_coarse_dists;
+    if (!c.cid) {
+        if ((rc = h->w_cid.ensure(nq * (size_t)c.nprobe * sizeof(uint32_t))) ||
+            (rc = h->w_cd.ensure(nq * (size_t)c.nprobe * sizeof(float))) ||
+            (rc = coarse_dev_impl(h, nq, c.xq, c.p->nprobe, c.p->efSearch, h->w_cid.as<uint32_t>(), h->w_cd.as<float>(),
+                                  call, c.meet)))
             return rc;
-        if ((rc = h->w_cd.ensure(nq * (size_t)nprobe * sizeof(float))))
-            return rc;
-        if ((rc = ivfhnsw_gpu_coarse_dev(h, nq, xq, p->nprobe, p->efSearch, h->w_cid.as<uint32_t>(),
-                                         h->w_cd.as<float>())))
-            return rc;
-        cid = h->w_cid.as<uint32_t>();
-        cd = h->w_cd.as<float>();
+        c.cid = h->w_cid.as<uint32_t>();
+        c.cd = h->w_cd.as<float>();
     }
-    h->tail_wrote_status = false;
-    h->walk_zero_keys = nullptr;
-    h->walk_zero_done = nullptr;
-    if (use_tail) {
-        const int nsplit = (int)std::min<size_t>(32, (2048 + nq - 1) / nq);
-        StageScope sc(h, IVFHNSW_STAGE_SCAN);
-        if (!h->walk_zeroed)
-            HIP_TRY(hipMemsetAsync(h->w_tail.p, 0, tail_kbytes + nq * sizeof(uint32_t), h->stream));
-        HIP_TRY(launch_ivf_tail(h->stream, h->t, xq, cid, cd, (int)nq, nprobe, p->max_codes, nsplit,
-                                h->w_tail.as<uint64_t>(), reinterpret_cast<uint32_t *>(h->w_tail.as<char>() + tail_kbytes),
-                                h->w_hdr.as<PlanHdr>(), d_distances, d_labels, status_word(h),
-                                h->tail_status_out));
-        h->tail_wrote_status = h->tail_status_out != nullptr;
-        h->last_scan_kernel = "ivf_tail_kernel";
-        h->last_nq = (int)nq;
-        h->last_max_seg = max_seg;
-        h->last_stream = false;
-        return IVFHNSW_OK;
-    }
-    // a plan segment is a list (IVFADC) or a sub-group (Grouping): the mean length decides the scan form
-    const uint64_t nseg_all = (uint64_t)h->t.nc * (h->has_group ? (uint64_t)h->g.nsubc : 1);
-    const int seg_hint = (int)std::min<uint64_t>(1u << 20, nseg_all ? (h->n_local * h->t.shard_world) / nseg_all : 0);
-    const bool heap = p->heap_order && k > 1;
+    return IVFHNSW_OK;
+}
+
+static int chunk_tail(ivfhnsw_gpu *h, const Chunk &c, SearchCall &call)
+{
+    const size_t nq = c.nq;
+    const int nsplit = (int)std::min<size_t>(32, (2048 + nq - 1) / nq);
+    StageScope sc(h, IVFHNSW_STAGE_SCAN);
+    if (!c.meet.cleared)
+        HIP_TRY(hipMemsetAsync(c.meet.keys, 0, nq * (sizeof(uint64_t) + sizeof(uint32_t)), h->stream));
+    HIP_TRY(launch_ivf_tail(h->stream, h->t, c.xq, c.cid, c.cd, (int)nq, c.nprobe, c.p->max_codes, nsplit, c.meet.keys,
+                            c.meet.done, h->w_hdr.as<PlanHdr>(), c.d_distances, c.d_labels, status_word(h),
+                            call.status_out));
+    call.wrote_status = call.status_out != nullptr;
+    remember_plan(h, nq, c.max_seg, false, "ivf_tail_kernel");
+    return IVFHNSW_OK;
+}
+
+// 3. plan (IndexIVF_HNSW.cpp:267-292 / IndexIVF_HNSW_Grouping.cpp:222-353), 4. table (IndexIVF_HNSW.cpp:262)
+static int chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
+{
+    const int nq = (int)c.nq, max_seg = c.max_seg;
+    const ivfhnsw_search_params *p = c.p;
+    int rc;
+    c.heap = p->heap_order && c.k > 1;
     // small batches: split each query over several workgroups so the chip still fills
-    int nsplit = 1;
-    if (k == 1 && nq < 1024)
-        nsplit = (int)std::min<size_t>(32, (2048 + nq - 1) / nq);
+    c.nsplit = (c.k == 1 && c.nq < 1024) ? (int)std::min<size_t>(32, (2048 + c.nq - 1) / c.nq) : 1;
     // list shards: table and scan in one software-pipelined kernel, the table never leaves the chip (kernels_scan3.hip)
-    const bool pipe = k == 1 && !h->has_group && !heap && !fmask && h->opt_scan_pipe != 0 &&
-                      scan_pipe_supported(h->t, max_seg, (int)nq, nsplit, h->n_local > 0, h->opt_scan_pipe == 1);
+    c.pipe = c.k == 1 && !h->has_group && !c.heap && !c.fmask && h->opt_scan_pipe != 0 &&
+             scan_pipe_supported(h->t, max_seg, nq, c.nsplit, h->n_local > 0, h->opt_scan_pipe == 1);
     // one GPU, IVFADC: plan and tables are independent of each other and go in ONE launch (kernels_search.hip
     // plan_lut_kernel; IVFHNSW_PLAN_LUT=0 keeps them apart)
-    static const bool plan_lut_on = [] {
-        const char *e = getenv("IVFHNSW_PLAN_LUT");
-        return !(e && *e && atoi(e) == 0);
-    }();
+    static const bool plan_lut_on = env_size("IVFHNSW_PLAN_LUT", 1) != 0;
     const int ds = h->t.dsub;
-    const bool plan_lut = plan_lut_on && !h->has_group && !pipe && h->t.shard_world == 1 &&
+    const bool plan_lut = plan_lut_on && !h->has_group && !c.pipe && h->t.shard_world == 1 &&
                           (ds == 4 || ds == 6 || ds == 8 || ds == 12 || ds == 16);
-    if (!pipe && (rc = h->w_luts.ensure(nq * (size_t)M * 256 * sizeof(float))))
+    if (!c.pipe && (rc = h->w_luts.ensure(c.nq * (size_t)h->t.M * 256 * sizeof(float))))
         return rc;
-    // 3. plan (IndexIVF_HNSW.cpp:267-292 / IndexIVF_HNSW_Grouping.cpp:222-353)
+    Seg *segs = h->w_segs.as<Seg>();
+    uint32_t *lpos = h->w_lpos.as<uint32_t>();
+    PlanHdr *hdr = h->w_hdr.as<PlanHdr>();
+    uint64_t *keys = h->w_keys.as<uint64_t>();
     if (plan_lut) {
         StageScope sc(h, IVFHNSW_STAGE_LUT); // plan + tables: one kernel, accounted as the table stage
-        HIP_TRY(launch_plan_lut(h->stream, h->t, xq, cid, cd, (int)nq, nprobe, p->max_codes, h->w_segs.as<Seg>(),
-                                h->w_lpos.as<uint32_t>(), h->w_hdr.as<PlanHdr>(), max_seg, h->w_keys.as<uint64_t>(),
-                                plan_k, h->w_luts.as<float>()));
-    } else {
+        HIP_TRY(launch_plan_lut(h->stream, h->t, c.xq, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
+                                keys, c.plan_k, h->w_luts.as<float>()));
+        return IVFHNSW_OK;
+    }
+    {
         StageScope sc(h, IVFHNSW_STAGE_PLAN);
         if (h->has_group) {
             // per query: pass-1 values and sub-centroid distances of every (row, sub-group) the plan touches
-            if ((rc = h->w_qsd.ensure(nq * (size_t)max_seg * 2 * sizeof(float))))
+            if ((rc = h->w_qsd.ensure(c.nq * (size_t)max_seg * 2 * sizeof(float))))
                 return rc;
-            HIP_TRY(launch_plan_grouping(h->stream, h->t, h->g, h->gr, xq, cid, cd, (int)nq, nprobe, p->max_codes,
-                                         p->do_pruning, h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                         h->w_hdr.as<PlanHdr>(), max_seg, h->w_keys.as<uint64_t>(), plan_k,
-                                         h->w_qsd.as<float>()));
+            HIP_TRY(launch_plan_grouping(h->stream, h->t, h->g, h->gr, c.xq, c.cid, c.cd, nq, c.nprobe, p->max_codes,
+                                         p->do_pruning, segs, lpos, hdr, max_seg, keys, c.plan_k, h->w_qsd.as<float>()));
         } else {
-            HIP_TRY(launch_plan_ivf(h->stream, h->t, cid, cd, (int)nq, nprobe, p->max_codes, h->w_segs.as<Seg>(),
-                                    h->w_lpos.as<uint32_t>(), h->w_hdr.as<PlanHdr>(), max_seg,
-                                    h->w_keys.as<uint64_t>(), plan_k));
+            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
+                                    keys, c.plan_k));
         }
     }
-    // 4. table (IndexIVF_HNSW.cpp:262)
-    if (!pipe && !plan_lut) {
+    if (!c.pipe) {
         StageScope sc(h, IVFHNSW_STAGE_LUT);
-        HIP_TRY(launch_lut(h->stream, h->t, xq, h->w_luts.as<float>(), (int)nq, h->w_hdr.as<PlanHdr>()));
+        HIP_TRY(launch_lut(h->stream, h->t, c.xq, h->w_luts.as<float>(), nq, hdr));
     }
+    return IVFHNSW_OK;
+}
+
+// 5. scan (IndexIVF_HNSW.cpp:282-289), 6. select
+static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
+{
+    const int nq = (int)c.nq, k = (int)c.k, max_seg = c.max_seg;
+    const bool heap = c.heap, replay_here = c.heap && !c.d_out_keys;
+    float *luts = h->w_luts.as<float>();
+    Seg *segs = h->w_segs.as<Seg>();
+    uint32_t *lpos = h->w_lpos.as<uint32_t>();
+    PlanHdr *hdr = h->w_hdr.as<PlanHdr>();
+    int rc;
     // heap_scan_kernel's global-tier heaps (k beyond what fits in LDS beside the table) and its redo list
     float *heap_ws = nullptr;
-    if (heap && !d_out_keys) {
-        if ((rc = h->w_heap.ensure(heap_scan_ws_bytes(M, (int)k, (int)nq))))
+    if (replay_here) {
+        if ((rc = h->w_heap.ensure(heap_scan_ws_bytes(h->t.M, k, nq))))
             return rc;
         heap_ws = h->w_heap.as<float>();
     }
-    if (heap_big) {
-        // 5-6. scan and heap replay in one kernel, every query of the batch (IndexIVF_HNSW.cpp:282-289)
+    if (c.heap_big) {
+        // scan and heap replay in one kernel, every query of the batch; no candidate stream exists
         {
             StageScope sc(h, IVFHNSW_STAGE_SCAN);
-            HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                     h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, nullptr, nullptr, heap_ws,
-                                     d_distances, d_labels, fmask));
+            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, nullptr, nullptr, heap_ws,
+                                     c.d_distances, c.d_labels, c.fmask));
         }
-        h->last_scan_kernel = fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel";
-        h->last_nq = (int)nq;
-        h->last_max_seg = max_seg;
-        h->last_stream = false; // no candidate stream exists
+        remember_plan(h, c.nq, max_seg, false, c.fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel");
         return IVFHNSW_OK;
     }
-    // 5. scan (IndexIVF_HNSW.cpp:282-289)
-    bool scan_selected = false;
     if (heap) {
         // with out_keys (sharded search) the replay is the caller's: it merges the shards' candidate streams in scan
         // order first (ivfhnsw_gpu_last_stream_dev, ivfhnsw_gpu_replay_stream_dev)
-        if ((rc = h->w_stream.ensure(nq * (size_t)kHeapStreamCap * sizeof(uint64_t))))
-            return rc;
-        if ((rc = h->w_slen.ensure(nq * sizeof(uint32_t))))
-            return rc;
-        if (!d_out_keys && (rc = h->w_hredo.ensure(nq * sizeof(uint32_t))))
+        if ((rc = h->w_stream.ensure(c.nq * (size_t)kHeapStreamCap * sizeof(uint64_t))) ||
+            (rc = h->w_slen.ensure(c.nq * sizeof(uint32_t))) ||
+            (replay_here && (rc = h->w_hredo.ensure(c.nq * sizeof(uint32_t)))))
             return rc;
     }
+    bool scan_selected = false;
+    const char *kernel_name = "scan_pipe_kernel";
     {
         StageScope sc(h, IVFHNSW_STAGE_SCAN);
-        if (pipe) {
-            HIP_TRY(launch_scan_pipe(h->stream, h->t, xq, h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                     h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, h->w_keys.as<uint64_t>()));
-            h->last_scan_kernel = "scan_pipe_kernel";
+        if (c.pipe) {
+            HIP_TRY(launch_scan_pipe(h->stream, h->t, c.xq, segs, lpos, hdr, max_seg, nq, h->w_keys.as<uint64_t>()));
         } else {
+            // a plan segment is a list (IVFADC) or a sub-group (Grouping): the mean length decides the scan form
+            const uint64_t nseg_all = (uint64_t)h->t.nc * (h->has_group ? (uint64_t)h->g.nsubc : 1);
+            const int seg_hint =
+                (int)std::min<uint64_t>(1u << 20, nseg_all ? (h->n_local * h->t.shard_world) / nseg_all : 0);
             // k = 1 without out_keys: the scan writes distance and label itself where it can (no select launch)
-            const bool want_sel = k == 1 && !d_out_keys && !heap;
-            HIP_TRY(launch_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, nsplit, h->w_keys.as<uint64_t>(),
+            const bool want_sel = k == 1 && !c.d_out_keys && !heap;
+            HIP_TRY(launch_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, c.nsplit, h->w_keys.as<uint64_t>(),
                                 heap ? h->w_stream.as<uint64_t>() : nullptr, heap ? h->w_slen.as<uint32_t>() : nullptr,
-                                heap ? kHeapStreamCap : 0, seg_hint, want_sel ? d_distances : nullptr,
-                                want_sel ? d_labels : nullptr, &scan_selected, fmask));
-            h->last_scan_kernel = last_scan_kernel_name();
+                                heap ? kHeapStreamCap : 0, seg_hint, want_sel ? c.d_distances : nullptr,
+                                want_sel ? c.d_labels : nullptr, &scan_selected, c.fmask));
+            kernel_name = last_scan_kernel_name();
         }
     }
-    // 6. select
     if (!scan_selected) {
         StageScope sc(h, IVFHNSW_STAGE_SELECT);
-        if (heap && !d_out_keys) {
+        if (replay_here) {
             // a query whose stream overflowed goes on the redo list instead of failing the batch; heap_scan_kernel redoes
             // it from the plan and the table.  Fixed grid, count read on the device: no host synchronisation, and an
-            // empty list costs one launch that exits at once (its last workgroup re-zeroes w_status[5..6])
-            uint32_t *redo_hdr = h->w_status.as<uint32_t>() + 5;
-            HIP_TRY(launch_heap_replay(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), max_seg,
-                                       h->w_stream.as<uint64_t>(), h->w_slen.as<uint32_t>(), kHeapStreamCap, (int)nq,
-                                       (int)k, d_distances, d_labels, status_word(h), nullptr, redo_hdr,
-                                       h->w_hredo.as<uint32_t>()));
-            HIP_TRY(launch_heap_scan(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                     h->w_hdr.as<PlanHdr>(), max_seg, (int)nq, (int)k, redo_hdr,
-                                     h->w_hredo.as<uint32_t>(), heap_ws, d_distances, d_labels, fmask));
+            // empty list costs one launch that exits at once (its last workgroup re-zeroes the two heap_redo words)
+            uint32_t *redo_hdr = &status_words(h)->heap_redo_len;
+            HIP_TRY(launch_heap_replay(h->stream, h->t, segs, hdr, max_seg, h->w_stream.as<uint64_t>(),
+                                       h->w_slen.as<uint32_t>(), kHeapStreamCap, nq, k, c.d_distances, c.d_labels,
+                                       status_word(h), nullptr, redo_hdr, h->w_hredo.as<uint32_t>()));
+            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr,
+                                     h->w_hredo.as<uint32_t>(), heap_ws, c.d_distances, c.d_labels, c.fmask));
         } else
-            HIP_TRY(launch_select(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), max_seg,
-                                  h->w_keys.as<uint64_t>(), (int)nq, (int)k, d_distances, d_labels, d_out_keys));
+            HIP_TRY(launch_select(h->stream, h->t, segs, hdr, max_seg, h->w_keys.as<uint64_t>(), nq, k, c.d_distances,
+                                  c.d_labels, c.d_out_keys));
     }
-    h->last_nq = (int)nq;
-    h->last_max_seg = max_seg;
-    h->last_stream = heap;
+    remember_plan(h, c.nq, max_seg, heap, kernel_name);
     return IVFHNSW_OK;
+}
+
+static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call)
+{
+    Chunk c{a};
+    int rc = chunk_checks(h, c);
+    if (rc)
+        return rc;
+    h->last_nq = 0;
+    call.wrote_status = false;
+    if (c.nq == 0)
+        return IVFHNSW_OK;
+    if ((rc = chunk_workspace(h, c)) || (rc = chunk_coarse(h, c, call)))
+        return rc;
+    if (c.use_tail)
+        return chunk_tail(h, c, call);
+    if ((rc = chunk_plan_table(h, c)))
+        return rc;
+    return chunk_scan_select(h, c);
 }
 
 int ivfhnsw_gpu_resolve_keys_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const int64_t *d_keys, float *d_distances,
@@ -534,29 +617,20 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
                        const float *coarse_dists, const ivfhnsw_search_params *p, float *distances, int64_t *labels)
 {
     int rc = bind(h);
-    if (rc)
+    if (rc || (rc = search_args_guard(h, p, k)))
         return rc;
-    if (!h->has_ivf)
-        return fail(IVFHNSW_ERR_STATE, "search before upload_ivf");
-    if (!p || p->nprobe == 0 || k == 0)
-        return fail(IVFHNSW_ERR_INVALID, "nprobe and k must be positive");
     if (nq == 0)
         return IVFHNSW_OK;
     if (!queries || !distances || !labels)
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
     if ((coarse_ids == nullptr) != (coarse_dists == nullptr))
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
-    const size_t d = h->t.d;
+    const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
     // Small batches -- the reference's drivers pass ONE query per call (tests/test_ivfhnsw_sift1b.cpp:193-208) -- go
     // through pinned host memory the kernels read and write directly: no staging copies, one synchronisation.  Layout
     // of the two blocks: in = queries | coarse ids | coarse dists; out = distances | labels | status word.
-    static const size_t pinned_max_nq = [] {
-        const char *e = getenv("IVFHNSW_PINNED_MAX_NQ");
-        return (e && *e) ? (size_t)atol(e) : (size_t)256;
-    }();
+    static const size_t pinned_max_nq = env_size("IVFHNSW_PINNED_MAX_NQ", 256);
     if (nq <= pinned_max_nq) {
-        const size_t np = p->nprobe;
-        const size_t in_q = nq * d * sizeof(float), in_c = coarse_ids ? nq * np * sizeof(uint32_t) : 0;
         const size_t out_d = (nq * k * sizeof(float) + 7) & ~(size_t)7, out_l = nq * k * sizeof(int64_t);
         if ((rc = h->p_in.ensure(in_q + 2 * in_c)) || (rc = h->p_out.ensure(out_d + out_l + 8)))
             return rc;
@@ -567,28 +641,26 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
             memcpy(pin + in_q + in_c, coarse_dists, in_c);
         }
         uint32_t *pst = reinterpret_cast<uint32_t *>(pout + out_d + out_l);
+        uint32_t *bits = &status_words(h)->bits;
         // The latency walk keeps at most 64 exact ties at the efSearch boundary.  This call synchronises anyway, so instead
         // of a redo launch behind every one-query call the walk only raises a status bit, and the call repeats itself once
         // on the throughput walk, whose redo form has no such limit (hnswalg.cpp:67-68,93 has none either).
         for (int attempt = 0; attempt < 2; attempt++) {
-            h->tail_status_out = pst;
-            h->lat_defer_redo = attempt == 0;
-            h->latency_off = attempt == 1;
-            rc = ivfhnsw_gpu_search_dev(h, nq, k, reinterpret_cast<const float *>(pin),
-                                        coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
-                                        coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
-                                        reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr);
-            h->tail_status_out = nullptr;
-            h->lat_defer_redo = false;
-            h->latency_off = false;
+            SearchCall call{pst, attempt == 0, attempt == 1};
+            rc = search_dev_impl(h,
+                                 {nq, k, reinterpret_cast<const float *>(pin),
+                                  coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
+                                  coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
+                                  reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr},
+                                 call);
             if (rc)
                 return rc;
-            if (!h->tail_wrote_status)
-                HIP_TRY(hipMemcpyAsync(pst, h->w_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            if (!call.wrote_status)
+                HIP_TRY(hipMemcpyAsync(pst, bits, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
             if (attempt == 0 && (*pst & kStatusHnswTieOverflow)) {
                 *pst &= ~kStatusHnswTieOverflow;
-                HIP_TRY(hipMemcpy(h->w_status.p, pst, sizeof(uint32_t), hipMemcpyHostToDevice)); // bit consumed
+                HIP_TRY(hipMemcpy(bits, pst, sizeof(uint32_t), hipMemcpyHostToDevice)); // bit consumed
                 continue;
             }
             break;
@@ -597,30 +669,15 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
         memcpy(labels, pout + out_d, out_l);
         return *pst ? check_status(h) : IVFHNSW_OK;
     }
-    if ((rc = h->s_q.ensure(nq * d * sizeof(float))))
+    if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
+        (rc = stage_in(h, h->s_q, queries, in_q)) ||
+        (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
+        (rc = ivfhnsw_gpu_search_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
+                                     coarse_ids ? h->s_cd.as<float>() : nullptr, p, h->s_dist.as<float>(),
+                                     h->s_lab.as<int64_t>(), nullptr)) ||
+        (rc = stage_out(h, distances, h->s_dist, nq * k * sizeof(float))) ||
+        (rc = stage_out(h, labels, h->s_lab, nq * k * sizeof(int64_t))))
         return rc;
-    if ((rc = h->s_dist.ensure(nq * k * sizeof(float))))
-        return rc;
-    if ((rc = h->s_lab.ensure(nq * k * sizeof(int64_t))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(h->s_q.p, queries, nq * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (coarse_ids) {
-        if ((rc = h->s_cid.ensure(nq * p->nprobe * sizeof(uint32_t))))
-            return rc;
-        if ((rc = h->s_cd.ensure(nq * p->nprobe * sizeof(float))))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(h->s_cid.p, coarse_ids, nq * p->nprobe * sizeof(uint32_t), hipMemcpyHostToDevice,
-                               h->stream));
-        HIP_TRY(hipMemcpyAsync(h->s_cd.p, coarse_dists, nq * p->nprobe * sizeof(float), hipMemcpyHostToDevice,
-                               h->stream));
-    }
-    rc = ivfhnsw_gpu_search_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                                coarse_ids ? h->s_cd.as<float>() : nullptr, p, h->s_dist.as<float>(),
-                                h->s_lab.as<int64_t>(), nullptr);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(distances, h->s_dist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(labels, h->s_lab.p, nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return check_status(h);
 }
@@ -629,28 +686,21 @@ int ivfhnsw_gpu_search_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const float *qu
                             const float *coarse_dists, const ivfhnsw_search_params *p, int64_t *keys)
 {
     int rc = bind(h);
-    if (rc)
+    if (rc || (rc = search_args_guard(h, p, k)))
         return rc;
-    if (!h->has_ivf)
-        return fail(IVFHNSW_ERR_STATE, "search before upload_ivf");
-    if (!p || p->nprobe == 0 || k == 0)
-        return fail(IVFHNSW_ERR_INVALID, "nprobe and k must be positive");
     if (nq == 0)
         return IVFHNSW_OK;
     if (!queries || !keys || !coarse_ids || !coarse_dists)
         return fail(IVFHNSW_ERR_INVALID, "null buffer (a shard is searched with the coarse stage supplied)");
     const size_t d = h->t.d, np = p->nprobe;
-    if ((rc = h->s_q.ensure(nq * d * sizeof(float))) || (rc = h->s_dist.ensure(nq * k * sizeof(float))) ||
-        (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) || (rc = h->s_keys.ensure(nq * k * sizeof(int64_t))) ||
-        (rc = h->s_cid.ensure(nq * np * sizeof(uint32_t))) || (rc = h->s_cd.ensure(nq * np * sizeof(float))))
+    if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
+        (rc = h->s_keys.ensure(nq * k * sizeof(int64_t))) || (rc = stage_in(h, h->s_q, queries, nq * d * sizeof(float))) ||
+        (rc = stage_in(h, h->s_cid, coarse_ids, nq * np * sizeof(uint32_t))) ||
+        (rc = stage_in(h, h->s_cd, coarse_dists, nq * np * sizeof(float))) ||
+        (rc = ivfhnsw_gpu_search_dev(h, nq, k, h->s_q.as<float>(), h->s_cid.as<uint32_t>(), h->s_cd.as<float>(), p,
+                                     h->s_dist.as<float>(), h->s_lab.as<int64_t>(), h->s_keys.as<int64_t>())) ||
+        (rc = stage_out(h, keys, h->s_keys, nq * k * sizeof(int64_t))))
         return rc;
-    HIP_TRY(hipMemcpyAsync(h->s_q.p, queries, nq * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->s_cid.p, coarse_ids, nq * np * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->s_cd.p, coarse_dists, nq * np * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ivfhnsw_gpu_search_dev(h, nq, k, h->s_q.as<float>(), h->s_cid.as<uint32_t>(), h->s_cd.as<float>(), p,
-                                     h->s_dist.as<float>(), h->s_lab.as<int64_t>(), h->s_keys.as<int64_t>())))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(keys, h->s_keys.p, nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return check_status(h);
 }
@@ -664,14 +714,12 @@ int ivfhnsw_gpu_resolve_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const int64_t 
         return IVFHNSW_OK;
     if (!keys || !distances || !labels)
         return fail(IVFHNSW_ERR_INVALID, "null buffer");
-    if ((rc = h->s_keys.ensure(nq * k * sizeof(int64_t))) || (rc = h->s_dist.ensure(nq * k * sizeof(float))) ||
-        (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))))
+    if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
+        (rc = stage_in(h, h->s_keys, keys, nq * k * sizeof(int64_t))) ||
+        (rc = ivfhnsw_gpu_resolve_keys_dev(h, nq, k, h->s_keys.as<int64_t>(), h->s_dist.as<float>(), h->s_lab.as<int64_t>())) ||
+        (rc = stage_out(h, distances, h->s_dist, nq * k * sizeof(float))) ||
+        (rc = stage_out(h, labels, h->s_lab, nq * k * sizeof(int64_t))))
         return rc;
-    HIP_TRY(hipMemcpyAsync(h->s_keys.p, keys, nq * k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ivfhnsw_gpu_resolve_keys_dev(h, nq, k, h->s_keys.as<int64_t>(), h->s_dist.as<float>(), h->s_lab.as<int64_t>())))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(distances, h->s_dist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(labels, h->s_lab.p, nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return IVFHNSW_OK;
 }
@@ -681,20 +729,14 @@ int ivfhnsw_gpu_last_stream(ivfhnsw_gpu *h, size_t nq, size_t len_cap, uint64_t 
     int rc = bind(h);
     if (rc)
         return rc;
-    if (lens) {
-        if ((rc = h->s_len.ensure(nq * sizeof(uint32_t))))
-            return rc;
-        if ((rc = ivfhnsw_gpu_last_stream_dev(h, nq, 0, nullptr, h->s_len.as<uint32_t>(), stream_cap)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(lens, h->s_len.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (keys) {
-        if ((rc = h->s_keys.ensure(nq * len_cap * sizeof(uint64_t))))
-            return rc;
-        if ((rc = ivfhnsw_gpu_last_stream_dev(h, nq, len_cap, h->s_keys.as<uint64_t>(), nullptr, stream_cap)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(keys, h->s_keys.p, nq * len_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    }
+    if (lens && ((rc = h->s_len.ensure(nq * sizeof(uint32_t))) ||
+                 (rc = ivfhnsw_gpu_last_stream_dev(h, nq, 0, nullptr, h->s_len.as<uint32_t>(), stream_cap)) ||
+                 (rc = stage_out(h, lens, h->s_len, nq * sizeof(uint32_t)))))
+        return rc;
+    if (keys && ((rc = h->s_keys.ensure(nq * len_cap * sizeof(uint64_t))) ||
+                 (rc = ivfhnsw_gpu_last_stream_dev(h, nq, len_cap, h->s_keys.as<uint64_t>(), nullptr, stream_cap)) ||
+                 (rc = stage_out(h, keys, h->s_keys, nq * len_cap * sizeof(uint64_t)))))
+        return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return IVFHNSW_OK;
 }
