@@ -6,7 +6,7 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter().
+// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), range_search().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
 
@@ -91,6 +91,13 @@ public:
 
     /// Extension: nq queries in one device pass (what the hardware is for).
     virtual void search_batch(size_t nq, size_t k, const float *x, float *distances, long *labels);
+    /// Extension: faiss's range_search for nq queries (ivfhnsw_gpu_range_search).  Every code that
+    /// search_batch would score (this object's nprobe, max_codes, quantizer->efSearch; on an IndexIVF_HNSW_Grouping its
+    /// sub-groups and do_pruning; set_id_filter honoured) with dist < radius, strictly: query q's results are entries
+    /// [lims[q], lims[q + 1]) of distances and labels, in the order the scan loop meets them; lims has nq + 1 entries.
+    /// Non-virtual (the class layout and vtable are those of the other extensions).  Throws with IVFHNSW_SHARDS > 1.
+    void range_search(size_t nq, const float *x, float radius, std::vector<size_t> &lims, std::vector<float> &distances,
+                      std::vector<long> &labels);
 
     virtual void add_batch(size_t n, const float *x, const idx_t *xids, const idx_t *precomputed_idx = nullptr);
     /// Extension: remove every code whose id is one of xids[0..n) from the lists (and their sub-groups); returns how many.

@@ -387,6 +387,49 @@ int ivfhnsw_gpu_search_sharded(ivfhnsw_gpu *const *shards, size_t nshards, size_
                                const uint32_t *coarse_ids, const float *coarse_dists, const ivfhnsw_search_params *params,
                                float *distances, int64_t *labels);
 
+/* ---- range search ---------------------------------------------------------------------------------
+ *
+ * faiss's range_search (Index::range_search / RangeSearchResult: lims, distances, labels) for the lists the handle
+ * holds: everything closer than the radius instead of the best k.  The candidates of a query are the codes the loop of
+ * IndexIVF_HNSW.cpp:282-289 (Grouping: IndexIVF_HNSW_Grouping.cpp:321-333) meets, i.e. the codes ivfhnsw_gpu_search of the
+ * same call would score: the same rotation, coarse stage (the walk, or coarse_ids / coarse_dists with 0xffffffff slots
+ * skipped), probe order, max_codes rule, sub-groups and pruning decisions, and the label filter when one is installed
+ * (a filtered row is never returned; max_codes and pruning count every stored code).  A candidate is returned iff
+ * dist < radius -- strict, as faiss compares for L2; a NaN distance fails -- with dist bit for bit what
+ * ivfhnsw_gpu_search returns for that code.  The results of one query stand in ascending scan position, the order in
+ * which that loop meets them.  No cap per query, nothing truncated, nothing padded; radius = +inf returns every scored
+ * code with a finite distance.
+ *   lims [nq + 1]: lims[0] = 0, query q's results are entries [lims[q], lims[q + 1]) of distances (float) and labels
+ *   (int64); *total = lims[nq].  The results stay in HBM the handle owns until its next range search, upload_ivf or
+ *   destroy (a view holds its own); ivfhnsw_gpu_memory_bytes counts them (12 bytes per result, kept at their largest
+ *   size so far, plus 4 bytes per (query, slice) of the count).
+ *   params: nprobe, max_codes, efSearch and do_pruning as in ivfhnsw_gpu_search; heap_order is ignored.
+ *   Both forms return when the results are complete, and synchronise the handle's stream ONCE between their two passes:
+ *   the host has to size the result buffers from the count (as ivfhnsw_gpu_kmeans_dev reads its objective per
+ *   iteration).  ivfhnsw_gpu_last_scan_counts reports what the k-search of the same arguments reports,
+ *   ivfhnsw_gpu_last_scan_kernel the range kernel's name ("+filter" appended on a filtered launch).  A range search ends
+ *   the validity of the last search's plan and candidate stream (resolve_keys*, last_stream*), as a removal does.
+ *   Limits: a batch whose results number 2^32 or more -> IVFHNSW_ERR_INVALID with a message (nothing is returned: split
+ *   the batch or lower the radius); at most 131 072 queries per call.
+ *   Errors leave earlier range results as they were: NaN radius, NULL queries, NULL lims or total with nq > 0 ->
+ *   IVFHNSW_ERR_INVALID; whatever ivfhnsw_gpu_search_dev refuses for the same params -> that call's status; before
+ *   upload_ivf, or on a handle with shard_world > 1 (range search over the key protocol is not built) ->
+ *   IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM.  nq = 0: lims[0] = 0, *total = 0, success.
+ * ivfhnsw_gpu_range_search: host pointers.  ivfhnsw_gpu_range_search_dev: device pointers (d_lims 8-byte aligned), *total on
+ *   the host.
+ * ivfhnsw_gpu_range_results: copies entries [first, first + count) to host buffers (either may be NULL); first + count
+ *   beyond the total -> IVFHNSW_ERR_INVALID; count = 0 succeeds.  ivfhnsw_gpu_range_results_dev: the device pointers
+ *   themselves (NULL when the total is 0) and the total, each output nullable.  Either before any range search on the
+ *   handle -> IVFHNSW_ERR_STATE. */
+int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                             const float *coarse_dists, const ivfhnsw_search_params *params, float radius,
+                             uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                 const float *d_coarse_dists, const ivfhnsw_search_params *params, float radius,
+                                 uint64_t *d_lims, uint64_t *total);
+int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
+int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
+
 /* The coarse stage alone (HierarchicalNSW::searchKnn, hnswalg.cpp:227-234, plus the unload loop of
  * IndexIVF_HNSW.cpp:249-259): device pointers, [nq*nprobe] outputs, nearest first.  Queries must
  * already be rotated when OPQ is on. */

@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_search", "ivfhnsw_gpu_exact_search_dev",
     "ivfhnsw_gpu_build_graph_dev", "ivfhnsw_gpu_last_graph_longest_reverse",
     "ivfhnsw_gpu_set_filter", "ivfhnsw_gpu_set_filter_dev", "ivfhnsw_gpu_clear_filter", "ivfhnsw_gpu_filter_info",
+    "ivfhnsw_gpu_range_search", "ivfhnsw_gpu_range_search_dev", "ivfhnsw_gpu_range_results", "ivfhnsw_gpu_range_results_dev",
 )
 
 
@@ -162,6 +163,12 @@ def lib():
         L.ivfhnsw_gpu_set_filter_dev.argtypes = L.ivfhnsw_gpu_set_filter.argtypes
         L.ivfhnsw_gpu_clear_filter.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
+        L.ivfhnsw_gpu_range_results.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_range_results_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_last_scan_kernel.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_last_scan_kernel.restype = C.c_char_p
         _lib = L
@@ -504,6 +511,49 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_search_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
                                             _devptr(d_coarse_dists), C.byref(p), _devptr(d_distances),
                                             _devptr(d_labels), _devptr(d_out_keys)))
+
+    # ---- range search (ivfhnsw_gpu_range_search) ---------------------------------------------------
+    def range_search(self, queries, radius, nprobe, max_codes, efSearch=0, do_pruning=False, coarse_ids=None,
+                     coarse_dists=None):
+        """Every code the k-search of the same arguments would score with dist < radius (strict), per query in scan
+        order: (lims u64 [nq + 1], distances f32 [total], labels i64 [total]); query q owns [lims[q], lims[q + 1])."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search(self._h, nq, _ptr(q) if nq else None, _ptr(cid), _ptr(cd), C.byref(p),
+                                              C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def range_search_dev(self, nq, d_queries, radius, d_lims, nprobe, max_codes, efSearch=0, do_pruning=False,
+                         d_coarse_ids=None, d_coarse_dists=None):
+        """The same on device buffers (d_lims: [nq + 1] 64-bit words); returns when the results are complete, with their
+        number.  They stay in the handle's memory: range_results_dev() / range_results()."""
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                  _devptr(d_coarse_dists), C.byref(p), C.c_float(radius), _devptr(d_lims),
+                                                  C.byref(total)))
+        return int(total.value)
+
+    def range_results(self, first, count):
+        """Entries [first, first + count) of the last range search's results: (distances f32, labels i64)."""
+        dist = np.empty(count, np.float32)
+        lab = np.empty(count, np.int64)
+        _check(lib().ivfhnsw_gpu_range_results(self._h, first, count, _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def range_results_dev(self):
+        """(distance pointer, label pointer, total) of the last range search's results in the handle's memory (raw device
+        addresses, 0 when the total is 0), valid until this handle's next range search, upload_ivf or close."""
+        pd, pl, total = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_range_results_dev(self._h, C.byref(pd), C.byref(pl), C.byref(total)))
+        return pd.value or 0, pl.value or 0, int(total.value)
 
     def resolve_keys_dev(self, nq, k, d_keys, d_distances, d_labels):
         _check(lib().ivfhnsw_gpu_resolve_keys_dev(self._h, nq, k, _devptr(d_keys), _devptr(d_distances),

@@ -138,6 +138,7 @@ using namespace ivfhnsw_gpu_impl;
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
+    X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
 
 struct ivfhnsw_gpu {
@@ -194,6 +195,11 @@ struct ivfhnsw_gpu {
     int last_nq = 0, last_max_seg = 0;
     const char *last_scan_kernel = "";
     bool last_stream = false; // ... and a candidate stream (k > 1, heap_order)
+    bool last_range = false;  // ... left by a range search: it serves last_scan_counts, not resolve_keys
+
+    // the results of the last range search (capi_range.cpp): rg_total entries of rg_dist / rg_lab
+    bool rg_valid = false;
+    uint64_t rg_total = 0;
 
     int profiling = 0; // 0 off, 1 every stage, 2 only the scan (an event pair costs ~7 us of stream time)
     std::vector<StageEvent> pending;
@@ -315,6 +321,65 @@ constexpr int kSplitAuto = 1000; // the first part's share follows the call's wa
 // query at PQ16, plus the plan) stays bounded; the multi-GPU resolve step needs the whole plan, so it is limited
 // to one slice.
 constexpr size_t kMaxBatchAll = 1 << 17;
+
+// ---- capi_search.cpp: the stages of one search_dev chunk that range search (capi_range.cpp) runs as well
+// What one search call asks of the stages below it; the default is a plain search_dev / coarse_dev call.
+struct SearchCall {
+    uint32_t *status_out = nullptr; // in: pinned word the tail kernel copies the status into (host-pointer path)
+    bool defer_redo = false;        // in: the latency walk only flags a tie overflow, the caller repeats the call ...
+    bool no_latency = false;        // in: ... with this set, on the throughput walk
+    bool wrote_status = false;      // out: the tail kernel wrote *status_out
+};
+
+// The tail kernel's per-query meeting words, which the latency walk clears on its way when it runs.
+struct WalkClear {
+    uint64_t *keys = nullptr; // in
+    uint32_t *done = nullptr; // in
+    bool cleared = false;     // out
+};
+
+// The arguments of ivfhnsw_gpu_search_dev, handed down as one.
+struct SearchArgs {
+    size_t nq, k;
+    const float *d_queries;
+    const uint32_t *d_coarse_ids;
+    const float *d_coarse_dists;
+    const ivfhnsw_search_params *p;
+    float *d_distances;
+    int64_t *d_labels, *d_out_keys;
+    SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
+    {
+        return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
+                d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k, d_labels + q0 * k,
+                d_out_keys};
+    }
+};
+
+// One chunk on its way through the stages below: its arguments, and what a stage leaves for the later ones.
+struct Chunk : SearchArgs {
+    int nprobe, max_seg, plan_k;    // chunk_workspace
+    bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
+    const uint32_t *fmask;          // a label filter
+    const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
+    const uint32_t *cid;
+    const float *cd;
+    bool use_tail;                  // ... everything behind them in one launch (chunk_tail),
+    WalkClear meet;                 // ... whose meeting words the walk may have cleared
+    int nsplit;                     // chunk_plan_table: workgroups per query,
+    bool heap, pipe;                // ... heap order with a stream, table and scan in one pipelined kernel
+};
+
+int search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, size_t k);
+int stage_in(ivfhnsw_gpu *h, DevBuf &b, const void *src, size_t bytes);
+int stage_out(ivfhnsw_gpu *h, void *dst, const DevBuf &b, size_t bytes);
+// results = false: a caller without d_distances / d_labels of [nq][k] (range search sizes its own output)
+int chunk_checks(ivfhnsw_gpu *h, const Chunk &c, bool results = true);
+int chunk_workspace(ivfhnsw_gpu *h, Chunk &c);
+int chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call);
+int chunk_plan_table(ivfhnsw_gpu *h, Chunk &c);
+
+// ---- capi_range.cpp
+void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)
 
 // ---- capi_upload.cpp
 int grouping_dedupe_reserve(ivfhnsw_gpu *h);

@@ -1,21 +1,6 @@
 // The batched search pipeline (rotate -> coarse -> table -> plan -> scan -> select) and its host-pointer entry points.
 #include "capi_internal.h"
 
-// What one search call asks of the stages below it; the default is a plain search_dev / coarse_dev call.
-struct SearchCall {
-    uint32_t *status_out = nullptr; // in: pinned word the tail kernel copies the status into (host-pointer path)
-    bool defer_redo = false;        // in: the latency walk only flags a tie overflow, the caller repeats the call ...
-    bool no_latency = false;        // in: ... with this set, on the throughput walk
-    bool wrote_status = false;      // out: the tail kernel wrote *status_out
-};
-
-// The tail kernel's per-query meeting words, which the latency walk clears on its way when it runs.
-struct WalkClear {
-    uint64_t *keys = nullptr; // in
-    uint32_t *done = nullptr; // in
-    bool cleared = false;     // out
-};
-
 // a size from the environment, def when unset or empty; every caller reads its knob once per process
 static size_t env_size(const char *name, size_t def)
 {
@@ -24,7 +9,7 @@ static size_t env_size(const char *name, size_t def)
 }
 
 // what ivfhnsw_gpu_search, ivfhnsw_gpu_search_keys and every chunk of search_dev check first, behind bind
-static int search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, size_t k)
+int ivfhnsw_gpu_impl::search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, size_t k)
 {
     if (!h->has_ivf)
         return fail(IVFHNSW_ERR_STATE, "search before upload_ivf");
@@ -35,7 +20,7 @@ static int search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *
 
 // The host-pointer entry points: a staging buffer of `bytes` filled from host memory, and one copied back to it, on the
 // handle's stream.
-static int stage_in(ivfhnsw_gpu *h, DevBuf &b, const void *src, size_t bytes)
+int ivfhnsw_gpu_impl::stage_in(ivfhnsw_gpu *h, DevBuf &b, const void *src, size_t bytes)
 {
     int rc = b.ensure(bytes);
     if (rc)
@@ -44,7 +29,7 @@ static int stage_in(ivfhnsw_gpu *h, DevBuf &b, const void *src, size_t bytes)
     return IVFHNSW_OK;
 }
 
-static int stage_out(ivfhnsw_gpu *h, void *dst, const DevBuf &b, size_t bytes)
+int ivfhnsw_gpu_impl::stage_out(ivfhnsw_gpu *h, void *dst, const DevBuf &b, size_t bytes)
 {
     HIP_TRY(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, h->stream));
     return IVFHNSW_OK;
@@ -170,23 +155,6 @@ int ivfhnsw_gpu_coarse(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t k
     return check_status(h);
 }
 
-// The arguments of ivfhnsw_gpu_search_dev, handed down as one.
-struct SearchArgs {
-    size_t nq, k;
-    const float *d_queries;
-    const uint32_t *d_coarse_ids;
-    const float *d_coarse_dists;
-    const ivfhnsw_search_params *p;
-    float *d_distances;
-    int64_t *d_labels, *d_out_keys;
-    SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
-    {
-        return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
-                d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k, d_labels + q0 * k,
-                d_out_keys};
-    }
-};
-
 static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call);
 
 // One large batch as TWO uneven parts on two streams.  The walk's resident wavefronts pull queries from a counter, so a
@@ -301,20 +269,6 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
 }
 
-// One chunk on its way through the stages below: its arguments, and what a stage leaves for the later ones.
-struct Chunk : SearchArgs {
-    int nprobe, max_seg, plan_k;    // chunk_workspace
-    bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
-    const uint32_t *fmask;          // a label filter
-    const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
-    const uint32_t *cid;
-    const float *cd;
-    bool use_tail;                  // ... everything behind them in one launch (chunk_tail),
-    WalkClear meet;                 // ... whose meeting words the walk may have cleared
-    int nsplit;                     // chunk_plan_table: workgroups per query,
-    bool heap, pipe;                // ... heap order with a stream, table and scan in one pipelined kernel
-};
-
 static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_stream, const char *kernel_name)
 {
     h->last_scan_kernel = kernel_name;
@@ -323,14 +277,14 @@ static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_strea
     h->last_stream = has_stream;
 }
 
-static int chunk_checks(ivfhnsw_gpu *h, const Chunk &c)
+int ivfhnsw_gpu_impl::chunk_checks(ivfhnsw_gpu *h, const Chunk &c, bool results)
 {
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, c.p, c.k)))
         return rc;
     if ((c.d_coarse_ids == nullptr) != (c.d_coarse_dists == nullptr))
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
-    if (c.nq > 0 && (!c.d_queries || !c.d_distances || !c.d_labels))
+    if (c.nq > 0 && (!c.d_queries || (results && (!c.d_distances || !c.d_labels))))
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
     // k > 1024 only in heap order on the labels path: heap_scan_kernel, no stream
     if (c.k > 1024 && (!c.p->heap_order || c.d_out_keys))
@@ -345,7 +299,7 @@ static int chunk_checks(ivfhnsw_gpu *h, const Chunk &c)
     return IVFHNSW_OK;
 }
 
-static int chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
+int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
 {
     c.nprobe = (int)c.p->nprobe;
     c.max_seg = h->has_group ? c.nprobe * h->g.nsubc : c.nprobe;
@@ -363,7 +317,7 @@ static int chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
 }
 
 // 1. rotate (IndexIVF_HNSW.cpp:240), 2. coarse (IndexIVF_HNSW.cpp:248-259)
-static int chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call)
+int ivfhnsw_gpu_impl::chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call)
 {
     const size_t nq = c.nq;
     int rc;
@@ -417,7 +371,7 @@ static int chunk_tail(ivfhnsw_gpu *h, const Chunk &c, SearchCall &call)
 }
 
 // 3. plan (IndexIVF_HNSW.cpp:267-292 / IndexIVF_HNSW_Grouping.cpp:222-353), 4. table (IndexIVF_HNSW.cpp:262)
-static int chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
+int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
 {
     const int nq = (int)c.nq, max_seg = c.max_seg;
     const ivfhnsw_search_params *p = c.p;
@@ -548,6 +502,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &cal
     if (rc)
         return rc;
     h->last_nq = 0;
+    h->last_range = false;
     call.wrote_status = false;
     if (c.nq == 0)
         return IVFHNSW_OK;
@@ -566,7 +521,7 @@ int ivfhnsw_gpu_resolve_keys_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const int6
     int rc = bind(h);
     if (rc)
         return rc;
-    if (!h->has_ivf || h->last_nq == 0 || (size_t)h->last_nq != nq)
+    if (!h->has_ivf || h->last_nq == 0 || (size_t)h->last_nq != nq || h->last_range)
         return fail(IVFHNSW_ERR_STATE, "resolve_keys needs the plan of a preceding search_dev with the same nq");
     StageScope sc(h, IVFHNSW_STAGE_SELECT);
     HIP_TRY(launch_resolve(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), h->last_max_seg, d_keys,

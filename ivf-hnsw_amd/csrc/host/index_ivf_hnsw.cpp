@@ -610,6 +610,30 @@ void IndexIVF_HNSW::search_batch(size_t nq, size_t k, const float *x, float *dis
     device_search(nq, k, x, nullptr, nullptr, nprobe, max_codes, false, distances, labels);
 }
 
+void IndexIVF_HNSW::range_search(size_t nq, const float *x, float radius, std::vector<size_t> &lims,
+                                 std::vector<float> &distances, std::vector<long> &labels)
+{
+    static_assert(sizeof(long) == sizeof(int64_t) && sizeof(size_t) == sizeof(uint64_t), "LP64 expected");
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::range_search: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
+    ensure_device();
+    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
+    ivfhnsw_search_params p;
+    p.nprobe = nprobe;
+    p.max_codes = max_codes;
+    p.efSearch = quantizer->efSearch;
+    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
+    p.heap_order = 0;
+    lims.assign(nq + 1, 0);
+    uint64_t total = 0;
+    if (ivfhnsw_gpu_range_search(gpu_, nq, x, nullptr, nullptr, &p, radius, reinterpret_cast<uint64_t *>(lims.data()), &total))
+        gpu_fail("ivfhnsw_gpu_range_search");
+    distances.resize(total);
+    labels.resize(total);
+    if (ivfhnsw_gpu_range_results(gpu_, 0, total, distances.data(), reinterpret_cast<int64_t *>(labels.data())))
+        gpu_fail("ivfhnsw_gpu_range_results");
+}
+
 // ------------------------------------------------------------------------------------------ searchDisk's re-rank
 // The base file in HBM (ivfhnsw_gpu_upload_base): records of uint32 dim + d bytes (utils.cpp:98-105), read in chunks of
 // at most 256 MB and handed over as the file image, rows d + 4 bytes apart.  Returns the library's status; file errors

@@ -172,6 +172,17 @@ hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts
                             const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
                             const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
                             const uint32_t *fmask = nullptr); // non-null: the filtered form, as launch_scan
+// range search (kernels_range.hip): the scan's plan, table and filter mask as launch_scan takes them, every
+// query cut into nsplit slices.  count: slices [nq * nsplit + 1] (zeroed here) = the codes with dist < radius in every
+// slice, *total (device, zeroed here) their 64-bit sum, *kernel_name the form that ran.  After launch_scan_excl_u32 over
+// slices: lims [nq + 1] = every query's first place, and fill writes hit r of a slice at bases[slice] + r, in scan order.
+hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
+                              const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
+                              uint32_t *slices, unsigned long long *total, const uint32_t *fmask, const char **kernel_name);
+hipError_t launch_range_lims(hipStream_t s, const uint32_t *bases, int nq, int nsplit, uint64_t *lims);
+hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
+                             const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
+                             const uint32_t *bases, float *dist, int64_t *labels, const uint32_t *fmask);
 // keys -> (distance, label) through the plan; also emits signed-orderable keys when out_keys != null
 hipError_t launch_select(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
                          const uint64_t *keys, int nq, int k, float *dist, int64_t *labels, int64_t *out_keys);
