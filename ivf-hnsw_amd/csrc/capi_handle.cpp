@@ -197,6 +197,13 @@ int ivfhnsw_gpu_destroy(ivfhnsw_gpu *h)
         (void)hipEventDestroy(h->split_fork);
     if (h->split_join)
         (void)hipEventDestroy(h->split_join);
+    if (h->early_stream) { // (joined into h->stream by every call that used it)
+        (void)hipStreamSynchronize(h->early_stream);
+        (void)hipStreamDestroy(h->early_stream);
+    }
+    for (hipEvent_t e : {h->early_ready[0], h->early_ready[1], h->early_done[0], h->early_done[1]})
+        if (e)
+            (void)hipEventDestroy(e);
     for (auto &ev : h->pending) {
         (void)hipEventDestroy(ev.a);
         (void)hipEventDestroy(ev.b);

@@ -183,6 +183,11 @@ struct ivfhnsw_gpu {
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
     hipEvent_t split_fork = nullptr, split_join = nullptr;
+    // ... and both parts' ADC tables are built beside the walks on a stream of the lowest priority (search_dev_split)
+    hipStream_t early_stream = nullptr;
+    hipEvent_t early_ready[2] = {nullptr, nullptr}; // per part: its rotated queries are there (OPQ only)
+    hipEvent_t early_done[2] = {nullptr, nullptr};  // per part: its tables are written
+    bool early_failed = false;                      // the stream could not be created: today's launches, not tried again
     bool last_split = false;
     uint32_t *status_shared = nullptr; // the internal split view raises its status bits in the PARENT's word (no merge launch)
     size_t last_parts[2] = {0, 0}; // queries in the two parts of the last search_dev call (second 0 = one part)
@@ -291,23 +296,24 @@ struct ListArrays {
 
 struct StageScope {
     ivfhnsw_gpu *h;
+    hipStream_t s; // the handle's stream, or the one the stage's launches really go to (a split call's early tables)
     StageEvent ev{};
     bool on;
-    StageScope(ivfhnsw_gpu *h_, int stage)
-        : h(h_), on(h_->profiling == 1 || (h_->profiling == 2 && stage == IVFHNSW_STAGE_SCAN))
+    StageScope(ivfhnsw_gpu *h_, int stage, hipStream_t s_ = nullptr)
+        : h(h_), s(s_ ? s_ : h_->stream), on(h_->profiling == 1 || (h_->profiling == 2 && stage == IVFHNSW_STAGE_SCAN))
     {
         if (!on)
             return;
         ev.stage = stage;
         ev.a = take_event(h);
         ev.b = take_event(h);
-        (void)hipEventRecord(ev.a, h->stream);
+        (void)hipEventRecord(ev.a, s);
     }
     ~StageScope()
     {
         if (!on)
             return;
-        (void)hipEventRecord(ev.b, h->stream);
+        (void)hipEventRecord(ev.b, s);
         h->pending.push_back(ev);
     }
 };
@@ -324,11 +330,19 @@ constexpr size_t kMaxBatchAll = 1 << 17;
 
 // ---- capi_search.cpp: the stages of one search_dev chunk that range search (capi_range.cpp) runs as well
 // What one search call asks of the stages below it; the default is a plain search_dev / coarse_dev call.
+// One part of a split call builds its ADC tables early: on `stream`, beside the walks, instead of behind its own walk.
+struct EarlyTables {
+    hipStream_t stream; // the handle's helper stream; it already waits for the call's fork
+    hipEvent_t ready;   // recorded behind the part's rotation (OPQ), which the tables are built from
+    hipEvent_t done;    // recorded behind the table launch; the part's scan waits for it
+};
+
 struct SearchCall {
     uint32_t *status_out = nullptr; // in: pinned word the tail kernel copies the status into (host-pointer path)
     bool defer_redo = false;        // in: the latency walk only flags a tie overflow, the caller repeats the call ...
     bool no_latency = false;        // in: ... with this set, on the throughput walk
     bool wrote_status = false;      // out: the tail kernel wrote *status_out
+    const EarlyTables *early = nullptr; // in: the part of a split call that is running (search_dev_split), else null
 };
 
 // The tail kernel's per-query meeting words, which the latency walk clears on its way when it runs.
@@ -367,6 +381,7 @@ struct Chunk : SearchArgs {
     WalkClear meet;                 // ... whose meeting words the walk may have cleared
     int nsplit;                     // chunk_plan_table: workgroups per query,
     bool heap, pipe;                // ... heap order with a stream, table and scan in one pipelined kernel
+    const EarlyTables *early;       // search_dev_chunk: a split call's part (SearchCall::early); null everywhere else
 };
 
 int search_args_guard(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, size_t k);

@@ -157,6 +157,15 @@ int ivfhnsw_gpu_coarse(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t k
 
 static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call);
 
+// one GPU, IVFADC: plan and tables are independent of each other and go in ONE launch (kernels_search.hip
+// plan_lut_kernel; IVFHNSW_PLAN_LUT=0 keeps them apart) -- unless the table is left to the pipelined scan
+static bool plan_lut_shape(const ivfhnsw_gpu *h)
+{
+    static const bool plan_lut_on = env_size("IVFHNSW_PLAN_LUT", 1) != 0;
+    const int ds = h->t.dsub;
+    return plan_lut_on && !h->has_group && h->t.shard_world == 1 && (ds == 4 || ds == 6 || ds == 8 || ds == 12 || ds == 16);
+}
+
 // One large batch as TWO uneven parts on two streams.  The walk's resident wavefronts pull queries from a counter, so a
 // launch ends with a tail of partly idle CUs (10 000 queries on 4096 slots: 2.44 "rounds"), and the scan can only start
 // when the last query has been walked.  Here the first ~78 % of the batch run on the handle's stream and the rest on an
@@ -171,6 +180,12 @@ static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &cal
 // HBM peak where the one-launch form reads 0.62 (bench.py reports both).  Not for sharded calls (their resolve step
 // needs one plan), heap-order k > 1 (one candidate stream), given coarse results (no walk to overlap) or batches below
 // two rounds of the walk.
+// Since round 4 a THIRD stream builds both parts' ADC tables while the walks run, where the second walk leaves resident
+// slots for that (early_tables_wanted): each part's chain behind its walk is then redo, plan, scan.  Kernel trace of a step
+// at (32, 10000, 80), before -> after, us from the first walk's start: walks end 1172 / 1486 -> 1210 / 1478, scans start
+// 1252 / 1550 -> 1243 / 1518, chains end 1558 / 1635 -> 1542 / 1605; the table kernels ran from 22 to 1125 (first part, its
+// workgroups entering as walk wavefronts leave) and 1132 to 1174 (second part).  The join covers the third stream through
+// the chains: each waits for its tables in front of its scan.
 static const size_t kSplitMinNq = 8192;
 
 // The first part's share when nobody fixed it.  The second part's walk fills the tail of the first part's, the first part's
@@ -178,20 +193,68 @@ static const size_t kSplitMinNq = 8192;
 // second walk and the first scan take equally long, share = W / (W + S).  W and S per query from the call's own parameters,
 // with rates measured at the 1B shapes on one MI355X: the walk 1.7 ns per unit of efSearch (1.37 / 1.63 /
 // 2.56 ms per 10 k queries at 80 / 100 / 130), the scan (M + 1) bytes per code at 5 TB/s over the codes the max_codes rule
-// lets through, the table 5 ns, the Grouping plan ~90 ns and its scan at 0.8 of the rate.  Measured against fixed shares:
+// lets through, the table 5 ns (nothing where it is built early, beside the walks), the Grouping plan ~90 ns and its scan
+// at 0.8 of the rate.  Measured against fixed shares:
 // (32, 10000, 80) 0.79 -> the 2048-query second part that measured best; (64, 30000, 100) 0.63 -> 4096, 3.97 -> 4.18 M
 // queries/s; Grouping + pruning 0.49 -> 4096, 3.35 -> 3.44 M.  The estimate only has to land on the right multiple of 2048.
-static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p)
+static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params *p, bool early_tables)
 {
     const double walk = 1.7 * (double)p->efSearch;
     const double nc = (double)std::max<uint32_t>(h->t.nc, 1u);
     const double list = (double)h->n_local / nc;
     const double codes = std::min((double)p->nprobe * list, (double)p->max_codes + 0.5 * list);
-    double scan = codes * (double)(h->t.M + 1) / 5000.0 + 5.0;
+    double scan = codes * (double)(h->t.M + 1) / 5000.0 + (early_tables ? 0.0 : 5.0); // early tables are on neither chain
     if (h->has_group)
         scan = scan / 0.8 + 90.0;
     const double share = walk / (walk + scan);
     return (int)std::min(900.0, std::max(400.0, share * 1000.0 + 0.5));
+}
+
+// Early tables (IVFHNSW_EARLY_LUT=0 = the launches of round 3): where a part would build plan and tables in one launch
+// behind its walk (chunk_plan_table), the tables of BOTH parts are built on a third stream while the walks run.  lut_body
+// reads only the (rotated) queries and the code book, and from the first walk's last round on resident slots stand empty:
+// the 16 KB per query written there are off both chains, each of which then runs plan, scan.  Measured, alternating on one
+// box (profiles/r04_early_tables.md): (32, 10000, 80) 1.652 -> 1.617 ms per step.  Only where the second part's walk leaves
+// such slots, i.e. has fewer queries than the walk has resident wavefronts (search_dev_split): at (64, 30000, 100) its 4096
+// queries take every slot the first walk frees, the table workgroups compete with them, and the step measured 0.6 %
+// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter or a table that the
+// pipelined scan builds itself.
+static bool early_tables_wanted(const ivfhnsw_gpu *h, const SearchArgs &a)
+{
+    static const bool on = env_size("IVFHNSW_EARLY_LUT", 1) != 0;
+    if (!on || !plan_lut_shape(h) || h->filter_mode >= 0)
+        return false;
+    const bool may_pipe = a.k == 1 && h->opt_scan_pipe != 0 &&
+                          scan_pipe_supported(h->t, (int)a.p->nprobe, (int)a.nq, 1, h->n_local > 0, h->opt_scan_pipe == 1);
+    return !may_pipe;
+}
+
+// The helper stream and its events, once per handle.  The stream has the lowest priority, so that a walk's wavefronts win
+// a freed slot ahead of table workgroups.  (The view's stream at the highest priority on top of that changed nothing at
+// (32, 10000, 80) -- 1.6145 / 1.6129 / 1.6154 ms with both, this one, neither -- and took a tenth off the first scan's
+// rate at (64, 30000, 100): not done.)  false = not available: the launches of round 3.
+static bool early_setup(ivfhnsw_gpu *h)
+{
+    if (h->early_stream)
+        return true;
+    if (h->early_failed)
+        return false;
+    int least = 0, greatest = 0;
+    hipStream_t s = nullptr;
+    bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
+              hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++)
+        ok = hipEventCreateWithFlags(&h->early_ready[i], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&h->early_done[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (s)
+            (void)hipStreamDestroy(s);
+        h->early_failed = true; // (events that were created go with the handle)
+        return false;
+    }
+    h->early_stream = s;
+    return true;
 }
 
 static int search_dev_split(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &call)
@@ -213,18 +276,40 @@ static int search_dev_split(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &cal
     v->status_shared = &status_words(h)->bits;
     // the second part: ~22 % of the batch, in whole "rounds" of the scan's resident workgroups (8 per CU x 256 CUs): its
     // scan runs alone at the end of the step, and 2200 workgroups on 2048 slots would take two rounds for one
+    // (with early tables too: second parts of 1024 / 1536 / 2048 / 2560 queries, the short ones scanned by two workgroups
+    // per query, gave 1.675 / 1.640 / 1.613 / 1.631 ms per step at (32, 10000, 80))
     const size_t round_wgs = 2048;
-    const int pm = h->split_pm == kSplitAuto ? auto_split_permille(h, a.p) : h->split_pm;
-    size_t n2 = ((nq * (size_t)(1000 - pm) / 1000 + round_wgs / 2) / round_wgs) * round_wgs;
-    n2 = std::max(round_wgs, std::min(n2, nq / 2));
-    const size_t n1 = nq - n2;
+    auto second_part = [&](bool early_tables) {
+        const int pm = h->split_pm == kSplitAuto ? auto_split_permille(h, a.p, early_tables) : h->split_pm;
+        const size_t n = ((nq * (size_t)(1000 - pm) / 1000 + round_wgs / 2) / round_wgs) * round_wgs;
+        return std::max(round_wgs, std::min(n, nq / 2));
+    };
+    // early tables where the second walk leaves resident slots to build them in (early_tables_wanted)
+    const bool early = early_tables_wanted(h, a) && second_part(true) < (size_t)coarse_slots_for((int)a.p->efSearch) &&
+                       early_setup(h);
+    const size_t n2 = second_part(early), n1 = nq - n2;
     HIP_TRY(hipEventRecord(h->split_fork, h->stream));
     HIP_TRY(hipStreamWaitEvent(v->stream, h->split_fork, 0));
+    EarlyTables part[2];
+    if (early) {
+        HIP_TRY(hipStreamWaitEvent(h->early_stream, h->split_fork, 0));
+        for (int i = 0; i < 2; i++)
+            part[i] = {h->early_stream, h->early_ready[i], h->early_done[i]};
+    }
+    call.early = early ? &part[0] : nullptr;
     rc = search_dev_chunk(h, a.slice(0, n1, (size_t)h->t.d), call);
+    call.early = early ? &part[1] : nullptr;
     int rc2 = rc ? rc : search_dev_chunk(v, a.slice(n1, n2, (size_t)h->t.d), call);
+    call.early = nullptr;
     // (whatever the second part flags it raises in the handle's own status word: v->status_shared)
     // the join itself, always (the fork was recorded)
     (void)hipSetDevice(h->device);
+    if (early && rc2) {
+        // a part failed on its way: its table launch may be out with no scan waiting for it.  (Otherwise each chain waits
+        // for its tables in front of its scan, and the second part's are the last thing the helper stream was given.)
+        HIP_TRY(hipEventRecord(h->early_done[1], h->early_stream));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->early_done[1], 0));
+    }
     HIP_TRY(hipEventRecord(h->split_join, v->stream));
     HIP_TRY(hipStreamWaitEvent(h->stream, h->split_join, 0));
     h->last_split = rc2 == 0;
@@ -325,9 +410,15 @@ int ivfhnsw_gpu_impl::chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &c
     if (h->t.opq_At) {
         if ((rc = h->w_xq.ensure(nq * (size_t)h->t.d * sizeof(float))))
             return rc;
-        StageScope sc(h, IVFHNSW_STAGE_OPQ);
-        HIP_TRY(launch_opq(h->stream, h->t.opq_At, c.d_queries, h->w_xq.as<float>(), (int)nq, h->t.d));
+        {
+            StageScope sc(h, IVFHNSW_STAGE_OPQ);
+            HIP_TRY(launch_opq(h->stream, h->t.opq_At, c.d_queries, h->w_xq.as<float>(), (int)nq, h->t.d));
+        }
         c.xq = h->w_xq.as<float>();
+        if (call.early) { // a split call's part: its tables are built from these, beside the walk that is launched next
+            HIP_TRY(hipEventRecord(call.early->ready, h->stream));
+            HIP_TRY(hipStreamWaitEvent(call.early->stream, call.early->ready, 0));
+        }
     }
     // small IVFADC batches: everything behind the coarse stage in one launch (kernels_tail.hip); its per-query
     // meeting words are cleared by the latency walk when that runs, by a memset otherwise.  The one-launch tail and the
@@ -382,18 +473,33 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
     // list shards: table and scan in one software-pipelined kernel, the table never leaves the chip (kernels_scan3.hip)
     c.pipe = c.k == 1 && !h->has_group && !c.heap && !c.fmask && h->opt_scan_pipe != 0 &&
              scan_pipe_supported(h->t, max_seg, nq, c.nsplit, h->n_local > 0, h->opt_scan_pipe == 1);
-    // one GPU, IVFADC: plan and tables are independent of each other and go in ONE launch (kernels_search.hip
-    // plan_lut_kernel; IVFHNSW_PLAN_LUT=0 keeps them apart)
-    static const bool plan_lut_on = env_size("IVFHNSW_PLAN_LUT", 1) != 0;
-    const int ds = h->t.dsub;
-    const bool plan_lut = plan_lut_on && !h->has_group && !c.pipe && h->t.shard_world == 1 &&
-                          (ds == 4 || ds == 6 || ds == 8 || ds == 12 || ds == 16);
+    const bool plan_lut = !c.pipe && plan_lut_shape(h);
     if (!c.pipe && (rc = h->w_luts.ensure(c.nq * (size_t)h->t.M * 256 * sizeof(float))))
         return rc;
     Seg *segs = h->w_segs.as<Seg>();
     uint32_t *lpos = h->w_lpos.as<uint32_t>();
     PlanHdr *hdr = h->w_hdr.as<PlanHdr>();
     uint64_t *keys = h->w_keys.as<uint64_t>();
+    if (plan_lut && c.early) {
+        // A split call's part: the tables need only the (rotated) queries, so they are built on the helper stream, into
+        // this part's own w_luts, while the walks run -- launched here, behind the walk in host order, so that the walk's
+        // wavefronts are on the chip first and the table workgroups (lowest priority) take slots that walks have left.
+        // This stream then runs the plan alone and meets the tables in front of the scan.  (The wait in front of the plan
+        // instead: 1.6037 against 1.6072 ms per step, inside the run-to-run spread.)
+        const EarlyTables &e = *c.early;
+        {
+            StageScope sc(h, IVFHNSW_STAGE_LUT, e.stream);
+            HIP_TRY(launch_lut(e.stream, h->t, c.xq, h->w_luts.as<float>(), nq, nullptr));
+        }
+        HIP_TRY(hipEventRecord(e.done, e.stream));
+        {
+            StageScope sc(h, IVFHNSW_STAGE_PLAN);
+            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
+                                    keys, c.plan_k));
+        }
+        HIP_TRY(hipStreamWaitEvent(h->stream, e.done, 0));
+        return IVFHNSW_OK;
+    }
     if (plan_lut) {
         StageScope sc(h, IVFHNSW_STAGE_LUT); // plan + tables: one kernel, accounted as the table stage
         HIP_TRY(launch_plan_lut(h->stream, h->t, c.xq, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
@@ -506,6 +612,7 @@ static int search_dev_chunk(ivfhnsw_gpu *h, const SearchArgs &a, SearchCall &cal
     call.wrote_status = false;
     if (c.nq == 0)
         return IVFHNSW_OK;
+    c.early = call.early;
     if ((rc = chunk_workspace(h, c)) || (rc = chunk_coarse(h, c, call)))
         return rc;
     if (c.use_tail)
