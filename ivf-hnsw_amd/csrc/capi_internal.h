@@ -227,6 +227,12 @@ int check_status(ivfhnsw_gpu *h);
 inline StatusWords *status_words(ivfhnsw_gpu *h) { return h->w_status.as<StatusWords>(); }
 inline uint32_t *status_word(ivfhnsw_gpu *h) { return h->status_shared ? h->status_shared : &status_words(h)->bits; }
 
+// the scan plan in the handle's workspace, as the launchers take it
+inline PlanView plan_of(const ivfhnsw_gpu *h, int max_seg, size_t nq)
+{
+    return {h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(), h->w_hdr.as<PlanHdr>(), max_seg, (int)nq};
+}
+
 // a view reads its parent's tables: what create_view copies once and a split batch before every call (uploads and
 // in-place updates since the view's creation included)
 void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent);
@@ -263,6 +269,10 @@ struct ListArrays {
             (rc = codes.ensure(n_local * M)) || (rc = ncodes.ensure(n_local)) || (rc = ids.ensure(n_local * sizeof(uint32_t))))
             return rc;
         return IVFHNSW_OK;
+    }
+    NewLists view(uint64_t n_local) const // what the update launchers fill
+    {
+        return {goff.as<uint64_t>(), loff.as<uint32_t>(), codes.as<uint8_t>(), ncodes.as<uint8_t>(), ids.as<uint32_t>(), n_local};
     }
     // The one place an update re-marks the filter: rows move and new rows must be judged.  Called when the new ids are
     // complete and BEFORE install, so that a failure here leaves tables and filter as they were.  No filter: nothing.

@@ -42,9 +42,8 @@ static int range_fill_pass(ivfhnsw_gpu *h, const Chunk &c, int seg_hint, float r
     HIP_TRY(launch_range_lims(h->stream, h->rg_slices.as<uint32_t>(), (int)c.nq, c.nsplit, d_lims));
     if (total) {
         StageScope sc(h, IVFHNSW_STAGE_SELECT); // the fill pass is accounted as the select stage, the count pass as the scan
-        HIP_TRY(launch_range_fill(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                  h->w_hdr.as<PlanHdr>(), c.max_seg, (int)c.nq, c.nsplit, seg_hint, radius,
-                                  h->rg_slices.as<uint32_t>(), dist, labels, c.fmask));
+        HIP_TRY(launch_range_fill(h->stream, h->t, h->w_luts.as<float>(), plan_of(h, c.max_seg, c.nq), c.nsplit, seg_hint,
+                                  radius, h->rg_slices.as<uint32_t>(), dist, labels, c.fmask));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     return check_status(h);
@@ -98,9 +97,8 @@ int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queri
     const char *kernel_name = "";
     {
         StageScope sc(h, IVFHNSW_STAGE_SCAN);
-        HIP_TRY(launch_range_count(h->stream, h->t, h->w_luts.as<float>(), h->w_segs.as<Seg>(), h->w_lpos.as<uint32_t>(),
-                                   h->w_hdr.as<PlanHdr>(), c.max_seg, (int)nq, c.nsplit, seg_hint, radius, slices, d_total,
-                                   c.fmask, &kernel_name));
+        HIP_TRY(launch_range_count(h->stream, h->t, h->w_luts.as<float>(), plan_of(h, c.max_seg, nq), c.nsplit, seg_hint,
+                                   radius, slices, d_total, c.fmask, &kernel_name));
     }
     HIP_TRY(launch_scan_excl_u32(h->stream, slices, len, h->rg_part.as<uint32_t>()));
     // the one synchronisation between the passes: the host sizes the results from the count

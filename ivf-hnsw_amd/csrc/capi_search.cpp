@@ -476,9 +476,7 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
     const bool plan_lut = !c.pipe && plan_lut_shape(h);
     if (!c.pipe && (rc = h->w_luts.ensure(c.nq * (size_t)h->t.M * 256 * sizeof(float))))
         return rc;
-    Seg *segs = h->w_segs.as<Seg>();
-    uint32_t *lpos = h->w_lpos.as<uint32_t>();
-    PlanHdr *hdr = h->w_hdr.as<PlanHdr>();
+    const PlanView plan = plan_of(h, max_seg, c.nq);
     uint64_t *keys = h->w_keys.as<uint64_t>();
     if (plan_lut && c.early) {
         // A split call's part: the tables need only the (rotated) queries, so they are built on the helper stream, into
@@ -494,16 +492,15 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
         HIP_TRY(hipEventRecord(e.done, e.stream));
         {
             StageScope sc(h, IVFHNSW_STAGE_PLAN);
-            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
-                                    keys, c.plan_k));
+            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, c.nprobe, p->max_codes, plan, keys, c.plan_k));
         }
         HIP_TRY(hipStreamWaitEvent(h->stream, e.done, 0));
         return IVFHNSW_OK;
     }
     if (plan_lut) {
         StageScope sc(h, IVFHNSW_STAGE_LUT); // plan + tables: one kernel, accounted as the table stage
-        HIP_TRY(launch_plan_lut(h->stream, h->t, c.xq, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
-                                keys, c.plan_k, h->w_luts.as<float>()));
+        HIP_TRY(launch_plan_lut(h->stream, h->t, c.xq, c.cid, c.cd, c.nprobe, p->max_codes, plan, keys, c.plan_k,
+                                h->w_luts.as<float>()));
         return IVFHNSW_OK;
     }
     {
@@ -512,16 +509,15 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
             // per query: pass-1 values and sub-centroid distances of every (row, sub-group) the plan touches
             if ((rc = h->w_qsd.ensure(c.nq * (size_t)max_seg * 2 * sizeof(float))))
                 return rc;
-            HIP_TRY(launch_plan_grouping(h->stream, h->t, h->g, h->gr, c.xq, c.cid, c.cd, nq, c.nprobe, p->max_codes,
-                                         p->do_pruning, segs, lpos, hdr, max_seg, keys, c.plan_k, h->w_qsd.as<float>()));
+            HIP_TRY(launch_plan_grouping(h->stream, h->t, h->g, h->gr, c.xq, c.cid, c.cd, c.nprobe, p->max_codes,
+                                         p->do_pruning, plan, keys, c.plan_k, h->w_qsd.as<float>()));
         } else {
-            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, nq, c.nprobe, p->max_codes, segs, lpos, hdr, max_seg,
-                                    keys, c.plan_k));
+            HIP_TRY(launch_plan_ivf(h->stream, h->t, c.cid, c.cd, c.nprobe, p->max_codes, plan, keys, c.plan_k));
         }
     }
     if (!c.pipe) {
         StageScope sc(h, IVFHNSW_STAGE_LUT);
-        HIP_TRY(launch_lut(h->stream, h->t, c.xq, h->w_luts.as<float>(), nq, hdr));
+        HIP_TRY(launch_lut(h->stream, h->t, c.xq, h->w_luts.as<float>(), nq, plan.hdr));
     }
     return IVFHNSW_OK;
 }
@@ -529,17 +525,15 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
 // 5. scan (IndexIVF_HNSW.cpp:282-289), 6. select
 static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
 {
-    const int nq = (int)c.nq, k = (int)c.k, max_seg = c.max_seg;
+    const int k = (int)c.k;
     const bool heap = c.heap, replay_here = c.heap && !c.d_out_keys;
     float *luts = h->w_luts.as<float>();
-    Seg *segs = h->w_segs.as<Seg>();
-    uint32_t *lpos = h->w_lpos.as<uint32_t>();
-    PlanHdr *hdr = h->w_hdr.as<PlanHdr>();
+    const PlanView plan = plan_of(h, c.max_seg, c.nq);
     int rc;
     // heap_scan_kernel's global-tier heaps (k beyond what fits in LDS beside the table) and its redo list
     float *heap_ws = nullptr;
     if (replay_here) {
-        if ((rc = h->w_heap.ensure(heap_scan_ws_bytes(h->t.M, k, nq))))
+        if ((rc = h->w_heap.ensure(heap_scan_ws_bytes(h->t.M, k, plan.nq))))
             return rc;
         heap_ws = h->w_heap.as<float>();
     }
@@ -547,10 +541,10 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
         // scan and heap replay in one kernel, every query of the batch; no candidate stream exists
         {
             StageScope sc(h, IVFHNSW_STAGE_SCAN);
-            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, nullptr, nullptr, heap_ws,
-                                     c.d_distances, c.d_labels, c.fmask));
+            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, nullptr, nullptr, heap_ws, c.d_distances, c.d_labels,
+                                     c.fmask));
         }
-        remember_plan(h, c.nq, max_seg, false, c.fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel");
+        remember_plan(h, c.nq, c.max_seg, false, c.fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel");
         return IVFHNSW_OK;
     }
     if (heap) {
@@ -566,19 +560,24 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
     {
         StageScope sc(h, IVFHNSW_STAGE_SCAN);
         if (c.pipe) {
-            HIP_TRY(launch_scan_pipe(h->stream, h->t, c.xq, segs, lpos, hdr, max_seg, nq, h->w_keys.as<uint64_t>()));
+            HIP_TRY(launch_scan_pipe(h->stream, h->t, c.xq, plan, h->w_keys.as<uint64_t>()));
         } else {
             // a plan segment is a list (IVFADC) or a sub-group (Grouping): the mean length decides the scan form
             const uint64_t nseg_all = (uint64_t)h->t.nc * (h->has_group ? (uint64_t)h->g.nsubc : 1);
             const int seg_hint =
                 (int)std::min<uint64_t>(1u << 20, nseg_all ? (h->n_local * h->t.shard_world) / nseg_all : 0);
-            // k = 1 without out_keys: the scan writes distance and label itself where it can (no select launch)
-            const bool want_sel = k == 1 && !c.d_out_keys && !heap;
-            HIP_TRY(launch_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, c.nsplit, h->w_keys.as<uint64_t>(),
-                                heap ? h->w_stream.as<uint64_t>() : nullptr, heap ? h->w_slen.as<uint32_t>() : nullptr,
-                                heap ? kHeapStreamCap : 0, seg_hint, want_sel ? c.d_distances : nullptr,
-                                want_sel ? c.d_labels : nullptr, &scan_selected, c.fmask));
-            kernel_name = last_scan_kernel_name();
+            ScanOut out;
+            if (heap) {
+                out.stream = h->w_stream.as<uint64_t>();
+                out.stream_len = h->w_slen.as<uint32_t>();
+                out.stream_cap = kHeapStreamCap;
+            } else if (k == 1 && !c.d_out_keys) {
+                // k = 1 without out_keys: the scan writes distance and label itself where it can (no select launch)
+                out.sel_dist = c.d_distances;
+                out.sel_labels = c.d_labels;
+            }
+            HIP_TRY(launch_scan(h->stream, h->t, luts, plan, k, c.nsplit, h->w_keys.as<uint64_t>(), seg_hint, c.fmask, out,
+                                &scan_selected, &kernel_name));
         }
     }
     if (!scan_selected) {
@@ -588,16 +587,16 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
             // it from the plan and the table.  Fixed grid, count read on the device: no host synchronisation, and an
             // empty list costs one launch that exits at once (its last workgroup re-zeroes the two heap_redo words)
             uint32_t *redo_hdr = &status_words(h)->heap_redo_len;
-            HIP_TRY(launch_heap_replay(h->stream, h->t, segs, hdr, max_seg, h->w_stream.as<uint64_t>(),
-                                       h->w_slen.as<uint32_t>(), kHeapStreamCap, nq, k, c.d_distances, c.d_labels,
-                                       status_word(h), nullptr, redo_hdr, h->w_hredo.as<uint32_t>()));
-            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr,
-                                     h->w_hredo.as<uint32_t>(), heap_ws, c.d_distances, c.d_labels, c.fmask));
+            HIP_TRY(launch_heap_replay(h->stream, h->t, plan, h->w_stream.as<uint64_t>(), h->w_slen.as<uint32_t>(),
+                                       kHeapStreamCap, k, c.d_distances, c.d_labels, status_word(h), nullptr, redo_hdr,
+                                       h->w_hredo.as<uint32_t>()));
+            HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, redo_hdr, h->w_hredo.as<uint32_t>(), heap_ws,
+                                     c.d_distances, c.d_labels, c.fmask));
         } else
-            HIP_TRY(launch_select(h->stream, h->t, segs, hdr, max_seg, h->w_keys.as<uint64_t>(), nq, k, c.d_distances,
-                                  c.d_labels, c.d_out_keys));
+            HIP_TRY(launch_select(h->stream, h->t, plan, h->w_keys.as<uint64_t>(), k, c.d_distances, c.d_labels,
+                                  c.d_out_keys));
     }
-    remember_plan(h, c.nq, max_seg, heap, kernel_name);
+    remember_plan(h, c.nq, c.max_seg, heap, kernel_name);
     return IVFHNSW_OK;
 }
 
@@ -631,8 +630,7 @@ int ivfhnsw_gpu_resolve_keys_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const int6
     if (!h->has_ivf || h->last_nq == 0 || (size_t)h->last_nq != nq || h->last_range)
         return fail(IVFHNSW_ERR_STATE, "resolve_keys needs the plan of a preceding search_dev with the same nq");
     StageScope sc(h, IVFHNSW_STAGE_SELECT);
-    HIP_TRY(launch_resolve(h->stream, h->t, h->w_segs.as<Seg>(), h->w_hdr.as<PlanHdr>(), h->last_max_seg, d_keys,
-                           (int)nq, (int)k, d_distances, d_labels));
+    HIP_TRY(launch_resolve(h->stream, h->t, plan_of(h, h->last_max_seg, nq), d_keys, (int)k, d_distances, d_labels));
     return IVFHNSW_OK;
 }
 
@@ -670,8 +668,9 @@ int ivfhnsw_gpu_replay_stream_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const uin
     if (!d_stream || !d_len || !d_out_keys || k == 0 || k > 1024 || nq > 0x7fffffffull / k)
         return fail(IVFHNSW_ERR_INVALID, "bad replay_stream arguments (k %zu)", k);
     StageScope sc(h, IVFHNSW_STAGE_SELECT);
-    HIP_TRY(launch_heap_replay(h->stream, h->t, nullptr, nullptr, 0, d_stream, d_len, cap, (int)nq, (int)k, nullptr,
-                               nullptr, status_word(h), d_out_keys));
+    // no plan: with out_keys the replay resolves no labels
+    HIP_TRY(launch_heap_replay(h->stream, h->t, PlanView{nullptr, nullptr, nullptr, 0, (int)nq}, d_stream, d_len, cap, (int)k,
+                               nullptr, nullptr, status_word(h), d_out_keys));
     return IVFHNSW_OK;
 }
 

@@ -108,12 +108,10 @@ static int append_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const ui
     hipError_t e = launch_sort_by_key(h->stream, d_idx, n, bits_of(nc - 1), h->ap_perm.as<uint32_t>(),
                                       h->ap_perm2.as<uint32_t>(), h->ap_hist.as<uint32_t>(), &perm);
     if (e == hipSuccess)
-        e = launch_append_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), fresh.goff.as<uint64_t>(),
-                                fresh.loff.as<uint32_t>(), fresh.codes.as<uint8_t>(), fresh.ncodes.as<uint8_t>(),
-                                fresh.ids.as<uint32_t>(), n_local2);
+        e = launch_append_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), fresh.view(n_local2));
     if (e == hipSuccess)
         e = launch_append_scatter(h->stream, h->t, perm, d_idx, n, nstart, lstart, d_codes, d_ncodes, d_ids,
-                                  fresh.codes.as<uint8_t>(), fresh.ncodes.as<uint8_t>(), fresh.ids.as<uint32_t>());
+                                  fresh.view(n_local2));
     if (e == hipSuccess)
         e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess)
@@ -320,8 +318,7 @@ try {
     ListArrays fresh;
     if ((rc = fresh.allocate(nc, n_local2, h->t.M)))
         return rc;
-    uint8_t *codes2 = fresh.codes.as<uint8_t>(), *ncodes2 = fresh.ncodes.as<uint8_t>();
-    uint32_t *ids2 = fresh.ids.as<uint32_t>();
+    const NewLists nl = fresh.view(n_local2);
     // stable order by (list, sub-group): by sub-group first, then from that order by list
     uint32_t *perm = nullptr;
     const uint32_t *nstart = h->ap_cnt.as<uint32_t>(), *lstart = h->ap_own.as<uint32_t>(); // scanned in place by launch_append_tables
@@ -333,17 +330,16 @@ try {
     if (e == hipSuccess)
         e = launch_sort_by_key_from(h->stream, d_list, n, bits_of(nc - 1), perm, pa, pb, hist, &perm);
     if (e == hipSuccess)
-        e = launch_append_layout(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), fresh.goff.as<uint64_t>(),
-                                 fresh.loff.as<uint32_t>(), n_local2);
+        e = launch_append_layout(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), nl);
     if (e == hipSuccess)
         e = launch_grouping_prefix(h->stream, nstart, h->g.sub_sizes, sizes2, h->gp_pre_old.as<uint32_t>(),
                                    h->gp_pre_new.as<uint32_t>(), (uint32_t)nc, (uint32_t)nsubc);
     if (e == hipSuccess)
         e = launch_grouping_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), pre_old, pre_new,
-                                  (uint32_t)nsubc, codes2, ncodes2, ids2, n_local2);
+                                  (uint32_t)nsubc, nl);
     if (e == hipSuccess)
         e = launch_grouping_scatter(h->stream, h->t, perm, d_list, d_sub, n, nstart, lstart, h->g.sub_sizes, pre_old,
-                                    (uint32_t)nsubc, d_codes, d_ncodes, d_ids, codes2, ncodes2, ids2);
+                                    (uint32_t)nsubc, d_codes, d_ncodes, d_ids, nl);
     if (e == hipSuccess)
         e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess)
@@ -561,9 +557,7 @@ try {
     ListArrays fresh;
     if ((rc = fresh.allocate(nc, n_local2, h->t.M)) || (grp && (rc = grouping_dedupe_reserve(h))))
         return rc;
-    hipError_t e = launch_remove_compact(h->stream, h->t, n_local, mask, rem, keep, fresh.goff.as<uint64_t>(),
-                                         fresh.loff.as<uint32_t>(), fresh.codes.as<uint8_t>(), fresh.ncodes.as<uint8_t>(),
-                                         fresh.ids.as<uint32_t>(), n_local2);
+    hipError_t e = launch_remove_compact(h->stream, h->t, n_local, mask, rem, keep, fresh.view(n_local2));
     if (e == hipSuccess)
         e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess)

@@ -6,6 +6,8 @@
 #include <mutex>
 #include <stdint.h>
 
+#include "scan_dispatch.h"
+
 namespace ivfhnsw_gpu_impl {
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, DEVICE): a process that drives several GPUs
@@ -32,7 +34,25 @@ inline hipError_t raise_dyn_lds(const void *kern, size_t bytes, DynLdsState &st)
     }
     return hipSuccess;
 }
-
+// what a launcher calls before a launch with `bytes` of dynamic LDS: every kernel KERN has a state of its own
+template <auto KERN> hipError_t dyn_lds(size_t bytes)
+{
+    static DynLdsState st;
+    return raise_dyn_lds((const void *)KERN, bytes, st);
+}
+// The dynamic LDS of a scan kernel KERN of code size CS: none for a compiled size, whose table is static LDS; for the
+// run-time form (CS == 0) M KB, raised here, and hipErrorInvalidValue for an M it cannot take.
+template <int CS, auto KERN> hipError_t scan_table_lds(int M, size_t *bytes)
+{
+    *bytes = 0;
+    if constexpr (CS == 0) {
+        if (!runtime_code_size_ok(M))
+            return hipErrorInvalidValue;
+        *bytes = (size_t)M * 1024;
+        return dyn_lds<KERN>(*bytes);
+    }
+    return hipSuccess;
+}
 
 // One scored (sub)list of one query: the unit of the scan plan.
 // start  : index of the first code inside this shard's flat code array
@@ -53,6 +73,27 @@ struct __attribute__((aligned(8))) PlanHdr {
     uint32_t total;
 };
 
+// The scan plan of one batch as the launchers take it: segs / lpos [nq][max_seg] (lpos: a segment's first position in the
+// query's flat array of owned codes), hdr [nq].  The launchers unpack it into their kernels' arguments; one that does not
+// read lpos ignores it.
+struct PlanView {
+    Seg *segs;
+    uint32_t *lpos;
+    PlanHdr *hdr;
+    int max_seg;
+    int nq;
+};
+
+// The arrays of the resident lists that an in-place update fills beside the handle's (ListArrays::view, capi_internal.h):
+// goff [nc + 1], loff [nc], and n_local rows of codes / ncodes / ids.
+struct NewLists {
+    uint64_t *goff;
+    uint32_t *loff;
+    uint8_t *codes, *ncodes;
+    uint32_t *ids;
+    uint64_t n_local;
+};
+
 // Packed result key: (orderable(dist) << 32) | vpos.  Unsigned order of the key is the order of
 // (dist, scan position): strict '<' of IndexIVF_HNSW.cpp:285 == "smallest key wins".
 constexpr uint32_t kOrdFltMax = 0x7f7fffffu | 0x80000000u; // orderable(FLT_MAX)
@@ -60,9 +101,6 @@ constexpr uint64_t kKeyInit = (uint64_t)kOrdFltMax << 32;  // accept iff key < k
 constexpr uint64_t kSignFlip = 0x8000000000000000ull;      // keys leave the library as signed-orderable int64
 
 constexpr uint32_t kNotOwned = 0xffffffffu;
-// dynamic LDS the run-time-code-size scan kernels may ask for (1 KB per code byte; the rest of the 160 KB holds
-// the plan chunk, the norm table and the top-k buffers)
-constexpr size_t kScanDynLdsMax = 128 * 1024;
 
 struct IvfTables {
     int d, M, dsub;             // M == code_size
@@ -123,42 +161,47 @@ hipError_t launch_opq(hipStream_t s, const float *At, const float *x, float *y, 
 // hdr (optional): queries whose plan is empty on this shard get no table
 hipError_t launch_lut(hipStream_t s, const IvfTables &t, const float *xq, float *luts, int nq, const PlanHdr *hdr = nullptr);
 // probe order + max_codes rule (IndexIVF_HNSW.cpp:267-292); also resets keys[nq*k] to kKeyInit
-hipError_t launch_plan_ivf(hipStream_t s, const IvfTables &t, const uint32_t *coarse_ids,
-                           const float *coarse_dists, int nq, int nprobe, uint64_t max_codes, Seg *segs,
-                           uint32_t *lpos, PlanHdr *hdr, int max_seg, uint64_t *keys, int k);
+hipError_t launch_plan_ivf(hipStream_t s, const IvfTables &t, const uint32_t *coarse_ids, const float *coarse_dists,
+                           int nprobe, uint64_t max_codes, const PlanView &p, uint64_t *keys, int k);
 // plan_ivf + lut in one launch (one GPU; hipErrorInvalidValue for a dsub without an instantiation)
 hipError_t launch_plan_lut(hipStream_t s, const IvfTables &t, const float *xq, const uint32_t *coarse_ids,
-                           const float *coarse_dists, int nq, int nprobe, uint64_t max_codes, Seg *segs, uint32_t *lpos,
-                           PlanHdr *hdr, int max_seg, uint64_t *keys, int k, float *luts);
+                           const float *coarse_dists, int nprobe, uint64_t max_codes, const PlanView &p, uint64_t *keys,
+                           int k, float *luts);
 // Grouping: sub-centroid distances, pruning threshold, pass-2 plan (IndexIVF_HNSW_Grouping.cpp:222-353)
 hipError_t launch_plan_grouping(hipStream_t s, const IvfTables &t, const GroupTables &g, const GraphTables &gr,
-                                const float *xq, const uint32_t *coarse_ids, const float *coarse_dists, int nq,
-                                int nprobe, uint64_t max_codes, int do_pruning, Seg *segs, uint32_t *lpos,
-                                PlanHdr *hdr, int max_seg, uint64_t *keys, int k, float *qsd_scratch);
+                                const float *xq, const uint32_t *coarse_ids, const float *coarse_dists, int nprobe,
+                                uint64_t max_codes, int do_pruning, const PlanView &p, uint64_t *keys, int k,
+                                float *qsd_scratch);
+// What launch_scan writes besides the keys, each part optional.
+struct ScanOut {
+    // k > 1: the candidate stream of the heap-order replay, stream_cap entries per query
+    uint64_t *stream = nullptr;
+    uint32_t *stream_len = nullptr;
+    uint32_t stream_cap = 0;
+    // k = 1: the scan resolves the winner's label itself where one workgroup sees the whole query
+    float *sel_dist = nullptr;
+    int64_t *sel_labels = nullptr;
+};
 // the ADC loop (IndexIVF_HNSW.cpp:282-289 / IndexIVF_HNSW_Grouping.cpp:321-333)
-hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                       const PlanHdr *hdr, int max_seg, int nq, int k, int nsplit, uint64_t *keys,
-                       uint64_t *stream = nullptr, uint32_t *stream_len = nullptr, uint32_t stream_cap = 0,
-                       int seg_len_hint = 0,
-                       // k = 1: let the scan resolve the winner's label itself where one workgroup sees the whole query;
-                       // *did_select tells whether it did (else launch_select has to run)
-                       float *sel_dist = nullptr, int64_t *sel_labels = nullptr, bool *did_select = nullptr, // expected codes per plan segment (0 = unknown): picks the scan form
-                       // non-null: the filtered form of the chosen kernel; bit r = local row r passes (launch_filter_mark)
-                       const uint32_t *fmask = nullptr);
+// seg_len_hint: expected codes per plan segment (0 = unknown), picks the scan form
+// fmask non-null: the filtered form of the chosen kernel; bit r = local row r passes (launch_filter_mark)
+// *did_select: the scan wrote out.sel_dist / sel_labels (else launch_select has to run); *kernel_name: the form that ran,
+// "" when nothing was launched; either may be null
+hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, int nsplit,
+                       uint64_t *keys, int seg_len_hint, const uint32_t *fmask, const ScanOut &out, bool *did_select,
+                       const char **kernel_name);
 // table + scan pipelined over queries, for list shards (kernels_scan3.hip)
 bool scan_pipe_supported(const IvfTables &t, int max_seg, int nq, int nsplit, bool has_codes, bool forced = false);
-hipError_t launch_scan_pipe(hipStream_t s, const IvfTables &t, const float *xq, const Seg *segs, const uint32_t *lpos,
-                            const PlanHdr *hdr, int max_seg, int nq, uint64_t *keys);
+hipError_t launch_scan_pipe(hipStream_t s, const IvfTables &t, const float *xq, const PlanView &p, uint64_t *keys);
 // plan + table + scan + select of a small IVFADC batch in one launch (kernels_tail.hip); keys_inv [nq] and done [nq] zeroed
 bool ivf_tail_supported(const IvfTables &t, int nprobe, int k);
 hipError_t launch_ivf_tail(hipStream_t s, const IvfTables &t, const float *xq, const uint32_t *cid, const float *cd,
                            int nq, int nprobe, uint64_t max_codes, int nsplit, uint64_t *keys_inv, uint32_t *done,
                            PlanHdr *hdr, float *dist, int64_t *labels, const uint32_t *status_word, uint32_t *status_out);
-const char *last_scan_kernel_name(); // the kernel the calling thread's last launch_scan chose
 // k > 1 in faiss heap-array order: sequential replay of the top-k kernel's candidate stream
-hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                              const uint64_t *stream, const uint32_t *stream_len, uint32_t stream_cap, int nq, int k,
-                              float *dist, int64_t *labels, uint32_t *status,
+hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const PlanView &p, const uint64_t *stream,
+                              const uint32_t *stream_len, uint32_t stream_cap, int k, float *dist, int64_t *labels,
+                              uint32_t *status,
                               int64_t *out_keys = nullptr, // non-null: the heap array as signed keys, no labels (sharded)
                               // non-null (labels path only): a query whose stream overflowed is appended to redo_list
                               // (redo_hdr[0] counts them) instead of raising kStatusTopkStreamOverflow
@@ -168,27 +211,26 @@ hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs
 // launch_heap_replay, and the launch's last workgroup re-zeroes redo_hdr[0..1].  heap_ws: heap_scan_ws_bytes of scratch.
 bool heap_scan_lds_tier(int code_size, int k);
 size_t heap_scan_ws_bytes(int code_size, int k, int nq);
-hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                            const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
-                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
+hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k,
+                            uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
                             const uint32_t *fmask = nullptr); // non-null: the filtered form, as launch_scan
 // range search (kernels_range.hip): the scan's plan, table and filter mask as launch_scan takes them, every
 // query cut into nsplit slices.  count: slices [nq * nsplit + 1] (zeroed here) = the codes with dist < radius in every
 // slice, *total (device, zeroed here) their 64-bit sum, *kernel_name the form that ran.  After launch_scan_excl_u32 over
 // slices: lims [nq + 1] = every query's first place, and fill writes hit r of a slice at bases[slice] + r, in scan order.
-hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                              const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
-                              uint32_t *slices, unsigned long long *total, const uint32_t *fmask, const char **kernel_name);
+hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
+                              int seg_len_hint, float radius, uint32_t *slices, unsigned long long *total,
+                              const uint32_t *fmask, const char **kernel_name);
 hipError_t launch_range_lims(hipStream_t s, const uint32_t *bases, int nq, int nsplit, uint64_t *lims);
-hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                             const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
-                             const uint32_t *bases, float *dist, int64_t *labels, const uint32_t *fmask);
+hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
+                             int seg_len_hint, float radius, const uint32_t *bases, float *dist, int64_t *labels,
+                             const uint32_t *fmask);
 // keys -> (distance, label) through the plan; also emits signed-orderable keys when out_keys != null
-hipError_t launch_select(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                         const uint64_t *keys, int nq, int k, float *dist, int64_t *labels, int64_t *out_keys);
+hipError_t launch_select(hipStream_t s, const IvfTables &t, const PlanView &p, const uint64_t *keys, int k, float *dist,
+                         int64_t *labels, int64_t *out_keys);
 // same, reading signed-orderable keys (after a cross-shard MIN)
-hipError_t launch_resolve(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                          const int64_t *skeys, int nq, int k, float *dist, int64_t *labels);
+hipError_t launch_resolve(hipStream_t s, const IvfTables &t, const PlanView &p, const int64_t *skeys, int k, float *dist,
+                          int64_t *labels);
 // HNSW walk, one wavefront per query (hnswalg.cpp:48-109,227-234)
 hipError_t launch_coarse(hipStream_t s, const GraphTables &g, const float *xq, int nq, int nprobe, int ef,
                          uint32_t *coarse_ids, float *coarse_dists, uint32_t *visited_scratch,
@@ -300,29 +342,28 @@ hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *
 // appends to the inverted lists (kernels_append.hip).  count: cnt[idx[i]] += 1 (cnt may be null: check
 // only), an id >= nc raises *status.  tables: own[c] = old length + cnt[c] of the owned lists, then cnt and own ([nc + 1]
 // each, slot nc zero) become their exclusive scans nstart / lstart in place; part: append_scan_parts(nc + 1) words.
-// merge: goff2 / loff2 and the old rows into the new arrays (tile_first: n_local2 / kAppendTileRows + 2 words).
+// merge: nl.goff / nl.loff and the old rows into the new arrays nl (tile_first: nl.n_local / kAppendTileRows + 2 words).
 // scatter: the batch's rows (perm = the ids sorted by list, stably) to the ends of their lists; runs after merge.
 constexpr int kAppendTileRows = 2048;
 size_t append_scan_parts(size_t len);
 hipError_t launch_append_count(hipStream_t s, const uint32_t *idx, size_t n, uint32_t nc, uint32_t *cnt, uint32_t *status);
 hipError_t launch_append_tables(hipStream_t s, const IvfTables &t, uint32_t *cnt, uint32_t *own, uint32_t *part);
 hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
-                               uint32_t *ids2, uint64_t n_local2);
+                               uint32_t *tile_first, const NewLists &nl);
 hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
                                  const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
-                                 const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2);
-// the first half of merge alone (goff2 / loff2 and tile_first), for a caller with a merge kernel of its own
+                                 const uint32_t *ids, const NewLists &nl);
+// the first half of merge alone (nl.goff / nl.loff and tile_first), for a caller with a merge kernel of its own
 hipError_t launch_append_layout(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                                uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint64_t n_local2);
+                                uint32_t *tile_first, const NewLists &nl);
 // exclusive scan of a [len] in place with the scan above; part: append_scan_parts(len) words
 hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part);
 // removal by label from an unsharded handle (kernels_remove.hip).  max: atomicMax of the labels into
 // *out.  mark: bits ((max_label / 32 + 1) words) = the label set, then mask [ceil(n_local / kRemoveTileRows) *
 // kRemoveTileRows / 64] (bit r = row r is removed) and keep [one per tile] = rows each tile keeps.  counts: rem [nc + 1]
 // (slot nc zero) = codes removed per list, also into rem_out when non-null; sizes != null (Grouping): sizes2 [nc * nsubc]
-// = the sub-group sizes after the removal.  compact, after rem and keep are scanned (rscan, kscan): goff2 / loff2 and the
-// surviving rows, in order, into the new arrays of n_local2 rows.
+// = the sub-group sizes after the removal.  compact, after rem and keep are scanned (rscan, kscan): nl.goff / nl.loff and the
+// surviving rows, in order, into the new arrays nl.
 constexpr int kRemoveTileRows = 2048;
 hipError_t launch_remove_max(hipStream_t s, const uint32_t *labels, size_t n, uint32_t *out);
 hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *labels, size_t n,
@@ -330,8 +371,7 @@ hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_loca
 hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigned long long *mask, const uint32_t *sizes,
                                 uint32_t *sizes2, int nsubc, uint32_t *rem, uint32_t *rem_out);
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
-                                 const uint32_t *rscan, const uint32_t *kscan, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2,
-                                 uint8_t *ncodes2, uint32_t *ids2, uint64_t n_local2);
+                                 const uint32_t *rscan, const uint32_t *kscan, const NewLists &nl);
 // the label bitmap alone, for a caller that keeps it (the search filter below): bits [max_label / 32 + 1 words] zeroed, then
 // the bit of every label set
 hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits);
@@ -350,14 +390,12 @@ hipError_t launch_grouping_count(hipStream_t s, const uint32_t *list_idx, const 
 hipError_t launch_grouping_prefix(hipStream_t s, const uint32_t *nstart, const uint32_t *sizes, const uint32_t *sizes2,
                                   uint32_t *pre_old, uint32_t *pre_new, uint32_t nc, uint32_t nsubc);
 hipError_t launch_grouping_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                                 const uint32_t *tile_first, const uint32_t *pre_old,
-                                 const uint32_t *pre_new, uint32_t nsubc, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2,
-                                 uint64_t n_local2);
+                                 const uint32_t *tile_first, const uint32_t *pre_old, const uint32_t *pre_new,
+                                 uint32_t nsubc, const NewLists &nl);
 hipError_t launch_grouping_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx,
                                    const uint32_t *sub_idx, size_t n, const uint32_t *nstart, const uint32_t *lstart,
                                    const uint32_t *sizes, const uint32_t *pre_old, uint32_t nsubc, const uint8_t *codes,
-                                   const uint8_t *norm_codes, const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2,
-                                   uint32_t *ids2);
+                                   const uint8_t *norm_codes, const uint32_t *ids, const NewLists &nl);
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --
 // for groups with points); out[i] = table[rows[i]] for rows of nsubc words

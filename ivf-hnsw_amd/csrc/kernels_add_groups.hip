@@ -253,33 +253,31 @@ hipError_t launch_grouping_prefix(hipStream_t s, const uint32_t *nstart, const u
 }
 
 hipError_t launch_grouping_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                                 const uint32_t *tile_first, const uint32_t *pre_old,
-                                 const uint32_t *pre_new, uint32_t nsubc, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2,
-                                 uint64_t n_local2)
+                                 const uint32_t *tile_first, const uint32_t *pre_old, const uint32_t *pre_new,
+                                 uint32_t nsubc, const NewLists &nl)
 {
-    if (n_local2 == 0)
+    if (nl.n_local == 0)
         return hipSuccess;
-    if (n_local2 >= 0xffffffffull || t.M % 4 || nsubc == 0)
+    if (nl.n_local >= 0xffffffffull || t.M % 4 || nsubc == 0)
         return hipErrorInvalidValue;
-    const uint32_t ntiles = blocks_of(n_local2, kAppendTileRows);
+    const uint32_t ntiles = blocks_of(nl.n_local, kAppendTileRows);
     hipLaunchKernelGGL(grouping_merge_kernel, dim3(ntiles), dim3(256), 0, s, t.goff, t.loff, nstart, lstart, tile_first,
                        pre_old, pre_new, nsubc, reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids,
-                       reinterpret_cast<uint32_t *>(codes2), ncodes2, ids2, (uint32_t)n_local2, (uint32_t)(t.M / 4));
+                       reinterpret_cast<uint32_t *>(nl.codes), nl.ncodes, nl.ids, (uint32_t)nl.n_local, (uint32_t)(t.M / 4));
     return hipGetLastError();
 }
 
 hipError_t launch_grouping_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx,
                                    const uint32_t *sub_idx, size_t n, const uint32_t *nstart, const uint32_t *lstart,
                                    const uint32_t *sizes, const uint32_t *pre_old, uint32_t nsubc, const uint8_t *codes,
-                                   const uint8_t *norm_codes, const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2,
-                                   uint32_t *ids2)
+                                   const uint8_t *norm_codes, const uint32_t *ids, const NewLists &nl)
 {
     if (n == 0)
         return hipSuccess;
     const uint32_t q = (uint32_t)(t.M / 4);
     hipLaunchKernelGGL(grouping_scatter_kernel, dim3(blocks_of(n * q, 256)), dim3(256), 0, s, perm, list_idx, sub_idx, nstart,
                        t.loff, lstart, sizes, pre_old, nsubc, reinterpret_cast<const uint32_t *>(codes), norm_codes, ids,
-                       reinterpret_cast<uint32_t *>(codes2), ncodes2, ids2, n, q);
+                       reinterpret_cast<uint32_t *>(nl.codes), nl.ncodes, nl.ids, n, q);
     return hipGetLastError();
 }
 

@@ -229,48 +229,47 @@ hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t
 }
 
 hipError_t launch_append_layout(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                                uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint64_t n_local2)
+                                uint32_t *tile_first, const NewLists &nl)
 {
     const size_t len = (size_t)t.nc + 1;
     hipLaunchKernelGGL(append_offsets_kernel, dim3(blocks_of(len, 256)), dim3(256), 0, s, t.goff, t.loff, nstart, lstart,
-                       goff2, loff2, t.nc);
+                       nl.goff, nl.loff, t.nc);
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
-    if (n_local2 == 0)
+    if (nl.n_local == 0)
         return hipSuccess;
-    if (n_local2 >= 0xffffffffull || t.M % 4)
+    if (nl.n_local >= 0xffffffffull || t.M % 4)
         return hipErrorInvalidValue;
-    const uint32_t ntiles = (uint32_t)blocks_of(n_local2, kAppendTileRows);
+    const uint32_t ntiles = (uint32_t)blocks_of(nl.n_local, kAppendTileRows);
     hipLaunchKernelGGL(append_tiles_kernel, dim3(blocks_of((size_t)ntiles + 1, 256)), dim3(256), 0, s, lstart, t.nc, ntiles,
                        tile_first);
     return hipGetLastError();
 }
 
 hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                               uint32_t *tile_first, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2, uint8_t *ncodes2,
-                               uint32_t *ids2, uint64_t n_local2)
+                               uint32_t *tile_first, const NewLists &nl)
 {
-    if (hipError_t e = launch_append_layout(s, t, nstart, lstart, tile_first, goff2, loff2, n_local2); e != hipSuccess)
+    if (hipError_t e = launch_append_layout(s, t, nstart, lstart, tile_first, nl); e != hipSuccess)
         return e;
-    if (n_local2 == 0)
+    if (nl.n_local == 0)
         return hipSuccess;
-    const uint32_t ntiles = (uint32_t)blocks_of(n_local2, kAppendTileRows);
+    const uint32_t ntiles = (uint32_t)blocks_of(nl.n_local, kAppendTileRows);
     hipLaunchKernelGGL(append_merge_kernel, dim3(ntiles), dim3(256), 0, s, t.goff, t.loff, lstart, tile_first,
-                       reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(codes2),
-                       ncodes2, ids2, (uint32_t)n_local2, (uint32_t)(t.M / 4));
+                       reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(nl.codes),
+                       nl.ncodes, nl.ids, (uint32_t)nl.n_local, (uint32_t)(t.M / 4));
     return hipGetLastError();
 }
 
 hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
                                  const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
-                                 const uint32_t *ids, uint8_t *codes2, uint8_t *ncodes2, uint32_t *ids2)
+                                 const uint32_t *ids, const NewLists &nl)
 {
     if (n == 0)
         return hipSuccess;
     const uint32_t q = (uint32_t)(t.M / 4);
     hipLaunchKernelGGL(append_scatter_kernel, dim3(blocks_of(n * q, 256)), dim3(256), 0, s, perm, idx, nstart, t.loff,
                        t.goff, lstart, reinterpret_cast<const uint32_t *>(codes), norm_codes, ids,
-                       reinterpret_cast<uint32_t *>(codes2), ncodes2, ids2, n, q);
+                       reinterpret_cast<uint32_t *>(nl.codes), nl.ncodes, nl.ids, n, q);
     return hipGetLastError();
 }
 

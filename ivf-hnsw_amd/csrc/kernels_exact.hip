@@ -256,9 +256,8 @@ hipError_t launch_exact_t(hipStream_t s, const uint8_t *Qp, const uint8_t *X, in
                           size_t cols_per_split, unsigned long long *part)
 {
     const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(int));
-    auto *kern = exact_mfma_kernel<NS, CAP, WAVES>;
-    static DynLdsState attr_set;
-    if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
+    constexpr auto kern = exact_mfma_kernel<NS, CAP, WAVES>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
         return e;
     // query tile is the fast index, column split the slow one: the tiles that run together stream the same columns
     hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 32 * WAVES - 1) / (32 * WAVES)), (unsigned)nsplit), dim3(64 * WAVES), shm,

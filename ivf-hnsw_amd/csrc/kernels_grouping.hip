@@ -718,10 +718,11 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
 }
 
 hipError_t launch_plan_grouping(hipStream_t s, const IvfTables &t, const GroupTables &g, const GraphTables &gr,
-                                const float *xq, const uint32_t *coarse_ids, const float *coarse_dists, int nq,
-                                int nprobe, uint64_t max_codes, int do_pruning, Seg *segs, uint32_t *lpos,
-                                PlanHdr *hdr, int max_seg, uint64_t *keys, int k, float *scratch)
+                                const float *xq, const uint32_t *coarse_ids, const float *coarse_dists, int nprobe,
+                                uint64_t max_codes, int do_pruning, const PlanView &p, uint64_t *keys, int k,
+                                float *scratch)
 {
+    const auto [segs, lpos, hdr, max_seg, nq] = p;
     if (nq == 0)
         return hipSuccess;
     // IVFHNSW_PLAN_GROUP4=0: the one-wavefront-per-query form (A/B runs)

@@ -242,55 +242,33 @@ size_t heap_scan_ws_bytes(int code_size, int k, int nq)
     return heap_scan_lds_tier(code_size, k) ? 0 : (size_t)heap_scan_grid(code_size, k, nq) * 8 * k;
 }
 
-template <int CS, bool LDS_HEAP>
-static hipError_t launch_heap_scan_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
-                                      const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k,
-                                      uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist,
-                                      int64_t *labels, const uint32_t *fmask)
+hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k,
+                            uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
+                            const uint32_t *fmask)
 {
-    const size_t shm = (size_t)t.M * 1024 + (LDS_HEAP ? (size_t)8 * k : 0);
-    if (fmask) {
-        auto *fkern = heap_scan_kernel<CS, LDS_HEAP, const uint32_t *>;
-        static DynLdsState fattr_set;
-        if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(fkern, dim3((unsigned)heap_scan_grid(t.M, k, nq)), dim3(256), shm, s, t, luts, segs, lpos, hdr,
-                           max_seg, nq, k, redo_hdr, redo_list, heap_ws, dist, reinterpret_cast<long long *>(labels), fmask);
-        return hipGetLastError();
-    }
-    auto *kern = heap_scan_kernel<CS, LDS_HEAP>;
-    static DynLdsState attr_set;
-    if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)heap_scan_grid(t.M, k, nq)), dim3(256), shm, s, t, luts, segs, lpos, hdr,
-                       max_seg, nq, k, redo_hdr, redo_list, heap_ws, dist, reinterpret_cast<long long *>(labels));
-    return hipGetLastError();
-}
-
-hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                            const PlanHdr *hdr, int max_seg, int nq, int k, uint32_t *redo_hdr,
-                            const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels, const uint32_t *fmask)
-{
-    if (nq == 0)
+    if (p.nq == 0)
         return hipSuccess;
-    if (k < 1 || t.M % 4 || (size_t)t.M * 1024 > kScanDynLdsMax || (redo_list && !redo_hdr))
+    if (k < 1 || !runtime_code_size_ok(t.M) || (redo_list && !redo_hdr))
         return hipErrorInvalidValue;
     const bool lds = heap_scan_lds_tier(t.M, k);
     if (!lds && !heap_ws)
         return hipErrorInvalidValue;
-#define IVFHNSW_HEAP_SCAN(CS)                                                                                         \
-    return lds ? launch_heap_scan_cs<CS, true>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,     \
-                                               heap_ws, dist, labels, fmask)                                          \
-               : launch_heap_scan_cs<CS, false>(s, t, luts, segs, lpos, hdr, max_seg, nq, k, redo_hdr, redo_list,    \
-                                                heap_ws, dist, labels, fmask)
-    switch (t.M) {
-    case 4: IVFHNSW_HEAP_SCAN(4);
-    case 8: IVFHNSW_HEAP_SCAN(8);
-    case 16: IVFHNSW_HEAP_SCAN(16);
-    case 32: IVFHNSW_HEAP_SCAN(32);
-    default: IVFHNSW_HEAP_SCAN(0); // any other multiple of 4: the run-time form
-    }
-#undef IVFHNSW_HEAP_SCAN
+    // table and (LDS tier) heap are dynamic LDS at every code size; 0 = any other multiple of 4, the run-time form
+    const size_t shm = (size_t)t.M * 1024 + (lds ? (size_t)8 * k : 0);
+    const dim3 grid((unsigned)heap_scan_grid(t.M, k, p.nq)), block(256);
+    return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
+        return with_mask(fmask, [&](auto... m) {
+            auto launch = [&](auto lds_heap) -> hipError_t {
+                constexpr auto kern = heap_scan_kernel<decltype(cs)::value, decltype(lds_heap)::value, decltype(m)...>;
+                if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
+                    return e;
+                hipLaunchKernelGGL(kern, grid, block, shm, s, t, luts, p.segs, p.lpos, p.hdr, p.max_seg, p.nq, k, redo_hdr,
+                                   redo_list, heap_ws, dist, reinterpret_cast<long long *>(labels), m...);
+                return hipGetLastError();
+            };
+            return lds ? launch(std::true_type()) : launch(std::false_type());
+        });
+    });
 }
 
 } // namespace ivfhnsw_gpu_impl

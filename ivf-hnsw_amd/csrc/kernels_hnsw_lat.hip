@@ -600,8 +600,9 @@ hipError_t launch_coarse_latency(hipStream_t s, const GraphTables &g, const floa
 #define IVFHNSW_LAT(N, J)                                                                                             \
     do {                                                                                                              \
         auto *kern = stamps ? hnsw_walk_lat_kernel<N, J, true> : hnsw_walk_lat_kernel<N, J, false>;                   \
-        static DynLdsState attr[2];                                                                                   \
-        if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr[stamps ? 1 : 0]); e != hipSuccess)             \
+        if (hipError_t e = stamps ? dyn_lds<hnsw_walk_lat_kernel<N, J, true>>(shm)                                    \
+                                  : dyn_lds<hnsw_walk_lat_kernel<N, J, false>>(shm);                                  \
+            e != hipSuccess)                                                                                          \
             return e;                                                                                                 \
         hipLaunchKernelGGL(kern, dim3(nq), dim3(LAT_THREADS), shm, s, g, xq, nq, nprobe, ef, coarse_ids, coarse_dists, \
                            status, diag, zero_keys, zero_done, redo_hdr, redo_list);                                                                                   \

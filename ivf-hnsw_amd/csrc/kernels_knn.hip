@@ -297,9 +297,8 @@ hipError_t launch_knn_t(hipStream_t s, const float *Q, const float *X, const flo
 {
     const size_t shm = (size_t)(2 * D2 * 32 + 32) * sizeof(float) + (size_t)4 * 32 * CAP * sizeof(unsigned long long) +
                        128 * sizeof(uint32_t) + 128 * sizeof(float);
-    auto *kern = knn_mfma_kernel<D2, CAP>;
-    static DynLdsState attr_set;
-    if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
+    constexpr auto kern = knn_mfma_kernel<D2, CAP>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 127) / 128), (unsigned)nsplit), dim3(256), shm, s, Q, X, qn, xn, nq, nx, d,
                        k, mode, cols_per_split, part);

@@ -444,93 +444,56 @@ __global__ void range_total_kernel(const uint32_t *__restrict__ counts, size_t l
         atomicAdd(out, t);
 }
 
-template <auto KERN> hipError_t range_dyn_lds(size_t shm)
-{
-    static DynLdsState st;
-    return raise_dyn_lds((const void *)KERN, shm, st);
-}
-
-template <int CS, bool FILL>
-hipError_t range_launch_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                           const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
-                           uint32_t *slices, RangeOut out, const uint32_t *fmask, const char **name)
-{
-    const dim3 grid((unsigned)nq * nsplit), block(RG_THREADS);
-    if constexpr (CS > 0) {
-        // plans of short segments (Grouping sub-groups): the bitmap form; whole lists: the position form
-        if (seg_len_hint > 0 && seg_len_hint <= 48) {
-            *name = fmask ? "range_scan_bitmap_kernel+filter" : "range_scan_bitmap_kernel";
-            if (fmask)
-                hipLaunchKernelGGL((range_scan_bitmap_kernel<CS, 4, FILL, const uint32_t *>), grid, block, 0, s, t.codes,
-                                   t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, radius, slices, out, fmask);
-            else
-                hipLaunchKernelGGL((range_scan_bitmap_kernel<CS, 4, FILL>), grid, block, 0, s, t.codes, t.norm_codes, luts,
-                                   t.norm_table, segs, lpos, hdr, max_seg, nsplit, radius, slices, out);
-            return hipGetLastError();
-        }
-        *name = fmask ? "range_scan_kernel+filter" : "range_scan_kernel";
-        if (fmask)
-            hipLaunchKernelGGL((range_scan_kernel<CS, 4, FILL, const uint32_t *>), grid, block, 0, s, t.codes, t.norm_codes,
-                               luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, t.M, radius, slices, out, fmask);
-        else
-            hipLaunchKernelGGL((range_scan_kernel<CS, 4, FILL>), grid, block, 0, s, t.codes, t.norm_codes, luts,
-                               t.norm_table, segs, lpos, hdr, max_seg, nsplit, t.M, radius, slices, out);
-        return hipGetLastError();
-    } else {
-        // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS
-        const size_t shm = (size_t)t.M * 1024;
-        if (t.M % 4 || shm > kScanDynLdsMax)
-            return hipErrorInvalidValue;
-        *name = fmask ? "range_scan_kernel (run-time code size)+filter" : "range_scan_kernel (run-time code size)";
-        if (fmask) {
-            if (hipError_t e = range_dyn_lds<range_scan_kernel<0, 2, FILL, const uint32_t *>>(shm); e != hipSuccess)
-                return e;
-            hipLaunchKernelGGL((range_scan_kernel<0, 2, FILL, const uint32_t *>), grid, block, shm, s, t.codes, t.norm_codes,
-                               luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, t.M, radius, slices, out, fmask);
-        } else {
-            if (hipError_t e = range_dyn_lds<range_scan_kernel<0, 2, FILL>>(shm); e != hipSuccess)
-                return e;
-            hipLaunchKernelGGL((range_scan_kernel<0, 2, FILL>), grid, block, shm, s, t.codes, t.norm_codes, luts,
-                               t.norm_table, segs, lpos, hdr, max_seg, nsplit, t.M, radius, slices, out);
-        }
-        return hipGetLastError();
-    }
-}
-
 template <bool FILL>
-hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                        const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius, uint32_t *slices,
-                        RangeOut out, const uint32_t *fmask, const char **name)
+hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit, int seg_len_hint,
+                        float radius, uint32_t *slices, RangeOut out, const uint32_t *fmask, const char **name)
 {
-#define IVFHNSW_RANGE(CS) \
-    return range_launch_cs<CS, FILL>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, seg_len_hint, radius, slices, out, fmask, name)
-    switch (t.M) {
-    case 4: IVFHNSW_RANGE(4);
-    case 8: IVFHNSW_RANGE(8);
-    case 16: IVFHNSW_RANGE(16);
-    case 32: IVFHNSW_RANGE(32);
-    default: IVFHNSW_RANGE(0);
-    }
-#undef IVFHNSW_RANGE
+    const dim3 grid((unsigned)p.nq * nsplit), block(RG_THREADS);
+    return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
+        return with_mask(fmask, [&](auto... m) -> hipError_t {
+            constexpr int CS = decltype(cs)::value;
+            constexpr bool FILT = sizeof...(m) != 0;
+            if constexpr (CS > 0) {
+                // plans of short segments (Grouping sub-groups): the bitmap form; whole lists: the position form
+                if (seg_len_hint > 0 && seg_len_hint <= 48) {
+                    *name = FILT ? "range_scan_bitmap_kernel+filter" : "range_scan_bitmap_kernel";
+                    hipLaunchKernelGGL((range_scan_bitmap_kernel<CS, 4, FILL, decltype(m)...>), grid, block, 0, s, t.codes,
+                                       t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, radius, slices,
+                                       out, m...);
+                    return hipGetLastError();
+                }
+            }
+            // a compiled size unrolls by 4; any other multiple of 4 (IndexIVF_HNSW.cpp:805) is the run-time form, by 2
+            constexpr auto kern = range_scan_kernel<CS, (CS > 0 ? 4 : 2), FILL, decltype(m)...>;
+            size_t shm;
+            if (hipError_t e = scan_table_lds<CS, kern>(t.M, &shm); e != hipSuccess)
+                return e;
+            *name = CS > 0 ? (FILT ? "range_scan_kernel+filter" : "range_scan_kernel")
+                           : (FILT ? "range_scan_kernel (run-time code size)+filter" : "range_scan_kernel (run-time code size)");
+            hipLaunchKernelGGL(kern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr,
+                               p.max_seg, nsplit, t.M, radius, slices, out, m...);
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace
 
-hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                              const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
-                              uint32_t *slices, unsigned long long *total, const uint32_t *fmask, const char **kernel_name)
+hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
+                              int seg_len_hint, float radius, uint32_t *slices, unsigned long long *total,
+                              const uint32_t *fmask, const char **kernel_name)
 {
-    const char *name = "";
-    const size_t len = (size_t)nq * nsplit + 1;
+    const char *unused_name;
+    kernel_name = kernel_name ? kernel_name : &unused_name; // may be null
+    *kernel_name = "";
+    const size_t len = (size_t)p.nq * nsplit + 1;
     hipError_t e = hipMemsetAsync(slices, 0, len * sizeof(uint32_t), s);
     if (e == hipSuccess)
         e = hipMemsetAsync(total, 0, sizeof(unsigned long long), s);
-    if (e != hipSuccess || nq == 0)
+    if (e != hipSuccess || p.nq == 0)
         return e;
-    e = range_launch<false>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, seg_len_hint, radius, slices,
-                            RangeOut{nullptr, nullptr, nullptr}, fmask, &name);
-    if (kernel_name)
-        *kernel_name = name;
+    e = range_launch<false>(s, t, luts, p, nsplit, seg_len_hint, radius, slices, RangeOut{nullptr, nullptr, nullptr}, fmask,
+                            kernel_name);
     if (e != hipSuccess)
         return e;
     const unsigned grid = (unsigned)std::min<size_t>((len + 255) / 256, 1024);
@@ -545,16 +508,15 @@ hipError_t launch_range_lims(hipStream_t s, const uint32_t *bases, int nq, int n
     return hipGetLastError();
 }
 
-hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                             const PlanHdr *hdr, int max_seg, int nq, int nsplit, int seg_len_hint, float radius,
-                             const uint32_t *bases, float *dist, int64_t *labels, const uint32_t *fmask)
+hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
+                             int seg_len_hint, float radius, const uint32_t *bases, float *dist, int64_t *labels,
+                             const uint32_t *fmask)
 {
-    if (nq == 0)
+    if (p.nq == 0)
         return hipSuccess;
     const char *name = "";
-    return range_launch<true>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, seg_len_hint, radius,
-                              const_cast<uint32_t *>(bases), RangeOut{t.ids, dist, reinterpret_cast<long long *>(labels)},
-                              fmask, &name);
+    return range_launch<true>(s, t, luts, p, nsplit, seg_len_hint, radius, const_cast<uint32_t *>(bases),
+                              RangeOut{t.ids, dist, reinterpret_cast<long long *>(labels)}, fmask, &name);
 }
 
 } // namespace ivfhnsw_gpu_impl

@@ -312,20 +312,19 @@ hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigne
 }
 
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
-                                 const uint32_t *rscan, const uint32_t *kscan, uint64_t *goff2, uint32_t *loff2, uint8_t *codes2,
-                                 uint8_t *ncodes2, uint32_t *ids2, uint64_t n_local2)
+                                 const uint32_t *rscan, const uint32_t *kscan, const NewLists &nl)
 {
     hipLaunchKernelGGL(remove_offsets_kernel, dim3(blocks_of((size_t)t.nc + 1, 256)), dim3(256), 0, s, t.goff, t.loff, rscan,
-                       goff2, loff2, t.nc);
+                       nl.goff, nl.loff, t.nc);
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
-    if (n_local2 == 0)
+    if (nl.n_local == 0)
         return hipSuccess;
     if (t.M % 4)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(remove_compact_kernel, dim3(blocks_of(n_local, kRemoveTileRows)), dim3(256), 0, s, mask, kscan, n_local,
-                       reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(codes2),
-                       ncodes2, ids2, (uint32_t)(t.M / 4));
+                       reinterpret_cast<const uint32_t *>(t.codes), t.norm_codes, t.ids, reinterpret_cast<uint32_t *>(nl.codes),
+                       nl.ncodes, nl.ids, (uint32_t)(t.M / 4));
     return hipGetLastError();
 }
 

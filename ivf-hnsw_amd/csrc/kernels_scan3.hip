@@ -373,9 +373,9 @@ bool scan_pipe_supported(const IvfTables &t, int max_seg, int nq, int nsplit, bo
     return knob == 1 || forced || t.shard_world >= 8;
 }
 
-hipError_t launch_scan_pipe(hipStream_t s, const IvfTables &t, const float *xq, const Seg *segs, const uint32_t *lpos,
-                            const PlanHdr *hdr, int max_seg, int nq, uint64_t *keys)
+hipError_t launch_scan_pipe(hipStream_t s, const IvfTables &t, const float *xq, const PlanView &p, uint64_t *keys)
 {
+    const auto [segs, lpos, hdr, max_seg, nq] = p;
     if (nq == 0)
         return hipSuccess;
     static const int resident = [] {

@@ -279,9 +279,10 @@ __global__ __launch_bounds__(256) void plan_lut_kernel(IvfTables t, const uint32
 }
 
 hipError_t launch_plan_lut(hipStream_t s, const IvfTables &t, const float *xq, const uint32_t *coarse_ids,
-                           const float *coarse_dists, int nq, int nprobe, uint64_t max_codes, Seg *segs, uint32_t *lpos,
-                           PlanHdr *hdr, int max_seg, uint64_t *keys, int k, float *luts)
+                           const float *coarse_dists, int nprobe, uint64_t max_codes, const PlanView &p, uint64_t *keys,
+                           int k, float *luts)
 {
+    const auto [segs, lpos, hdr, max_seg, nq] = p;
     if (nq == 0)
         return hipSuccess;
     const int plan_blocks = (nq + 3) / 4, lut_blocks = (nq + LUT_QB - 1) / LUT_QB;
@@ -304,9 +305,9 @@ hipError_t launch_plan_lut(hipStream_t s, const IvfTables &t, const float *xq, c
 }
 
 hipError_t launch_plan_ivf(hipStream_t s, const IvfTables &t, const uint32_t *coarse_ids, const float *coarse_dists,
-                           int nq, int nprobe, uint64_t max_codes, Seg *segs, uint32_t *lpos, PlanHdr *hdr,
-                           int max_seg, uint64_t *keys, int k)
+                           int nprobe, uint64_t max_codes, const PlanView &p, uint64_t *keys, int k)
 {
+    const auto [segs, lpos, hdr, max_seg, nq] = p;
     if (nq == 0)
         return hipSuccess;
     hipLaunchKernelGGL(plan_ivf_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, t, coarse_ids, coarse_dists, nq,
@@ -759,107 +760,68 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
     }
 }
 
-// which scan kernel the last launch_scan of this thread chose (reported by bench.py next to its roofline)
-static thread_local const char *g_scan_kernel_name = "";
-const char *last_scan_kernel_name() { return g_scan_kernel_name; }
+hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, uint64_t *keys,
+                            const ScanOut &out, const uint32_t *fmask);
 
-template <int CS>
-static hipError_t launch_scan_cs(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
-                                 const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int nsplit,
-                                 uint64_t *keys, int seg_len_hint, SelOut so, bool *did_select, const uint32_t *fmask)
+hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, int nsplit,
+                       uint64_t *keys, int seg_len_hint, const uint32_t *fmask, const ScanOut &out, bool *did_select,
+                       const char **kernel_name)
 {
-    if (nsplit != 1)
-        so.ids = nullptr; // several workgroups per query meet in an atomic: nobody knows the winner
-    dim3 grid((unsigned)nq * nsplit);
-    auto *k64 = reinterpret_cast<unsigned long long *>(keys);
-    // plans of short segments (Grouping sub-groups, ~16 codes): the bitmap form; whole lists: the position form
-    if (seg_len_hint > 0 && seg_len_hint <= 48) {
-        g_scan_kernel_name = fmask ? "scan_k1_bitmap_kernel+filter" : "scan_k1_bitmap_kernel";
-        if (fmask)
-            hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4, const uint32_t *>), grid, dim3(256), 0, s, t.codes, t.norm_codes,
-                               luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, so, fmask);
-        else
-            hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts, t.norm_table,
-                               segs, lpos, hdr, max_seg, nsplit, k64, so);
-        if (did_select)
-            *did_select = so.ids != nullptr;
-        return hipGetLastError();
-    }
-#define IVFHNSW_SCAN(SEGCAP)                                                                                        \
-    if (fmask)                                                                                                      \
-        hipLaunchKernelGGL((scan_k1_kernel<CS, SEGCAP, 4, 256, const uint32_t *>), grid, dim3(256), 0, s, t.codes,  \
-                           t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, t.M, so, fmask); \
-    else                                                                                                            \
-        hipLaunchKernelGGL((scan_k1_kernel<CS, SEGCAP, 4, 256>), grid, dim3(256), 0, s, t.codes, t.norm_codes, luts, \
-                           t.norm_table, segs, lpos, hdr, max_seg, nsplit, k64, t.M, so)
-    g_scan_kernel_name = fmask ? "scan_k1_kernel+filter" : "scan_k1_kernel";
-    if (max_seg <= 64) {
-        IVFHNSW_SCAN(64);
-    } else if (max_seg <= 256) {
-        // nprobe 65..256 (the DEEP1B preset probes 128 lists): a 5 KB plan instead of 20 KB keeps 7 workgroups
-        // per CU resident instead of 4
-        IVFHNSW_SCAN(256);
-    } else {
-        IVFHNSW_SCAN(1024);
-    }
-#undef IVFHNSW_SCAN
-    if (did_select)
-        *did_select = so.ids != nullptr;
-    return hipGetLastError();
-}
-
-hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
-                            const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k, uint64_t *keys,
-                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap, const uint32_t *fmask);
-
-hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs, const uint32_t *lpos,
-                       const PlanHdr *hdr, int max_seg, int nq, int k, int nsplit, uint64_t *keys, uint64_t *stream,
-                       uint32_t *stream_len, uint32_t stream_cap, int seg_len_hint, float *sel_dist, int64_t *sel_labels,
-                       bool *did_select, const uint32_t *fmask)
-{
-    if (did_select)
-        *did_select = false;
-    SelOut so;
-    so.ids = (k == 1 && sel_dist && sel_labels) ? t.ids : nullptr;
-    so.dist = sel_dist;
-    so.labels = reinterpret_cast<long long *>(sel_labels);
-    if (nq == 0)
+    bool unused_sel;
+    const char *unused_name;
+    did_select = did_select ? did_select : &unused_sel; // both out-arguments may be null
+    kernel_name = kernel_name ? kernel_name : &unused_name;
+    *did_select = false;
+    *kernel_name = "";
+    if (p.nq == 0)
         return hipSuccess;
     if (k != 1) {
-        g_scan_kernel_name = fmask ? "scan_topk_kernel+filter" : "scan_topk_kernel";
-        return launch_scan_topk(s, t, luts, segs, lpos, hdr, max_seg, nq, k, keys, stream, stream_len, stream_cap, fmask);
+        *kernel_name = fmask ? "scan_topk_kernel+filter" : "scan_topk_kernel";
+        return launch_scan_topk(s, t, luts, p, k, keys, out, fmask);
     }
-    switch (t.M) {
-    case 4: return launch_scan_cs<4>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
-    case 8: return launch_scan_cs<8>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
-    case 16: return launch_scan_cs<16>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
-    case 32: return launch_scan_cs<32>(s, t, luts, segs, lpos, hdr, max_seg, nq, nsplit, keys, seg_len_hint, so, did_select, fmask);
-    default: {
-        // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS
-        const size_t shm = (size_t)t.M * 1024;
-        if (t.M % 4 || shm > kScanDynLdsMax)
-            return hipErrorInvalidValue;
-        if (fmask) {
-            g_scan_kernel_name = "scan_k1_kernel (run-time code size)+filter";
-            auto *fkern = scan_k1_kernel<0, 256, 2, 256, const uint32_t *>;
-            static DynLdsState fattr_set;
-            if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
-                return e;
-            hipLaunchKernelGGL(fkern, dim3((unsigned)nq * nsplit), dim3(256), shm, s, t.codes, t.norm_codes, luts, t.norm_table,
-                               segs, lpos, hdr, max_seg, nsplit, reinterpret_cast<unsigned long long *>(keys), t.M,
-                               SelOut{nullptr, nullptr, nullptr}, fmask);
-            return hipGetLastError();
-        }
-        g_scan_kernel_name = "scan_k1_kernel (run-time code size)";
-        auto *kern = scan_k1_kernel<0, 256, 2, 256>;
-        static DynLdsState attr_set;
-        if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nq * nsplit), dim3(256), shm, s, t.codes, t.norm_codes, luts, t.norm_table,
-                           segs, lpos, hdr, max_seg, nsplit, reinterpret_cast<unsigned long long *>(keys), t.M, SelOut{nullptr, nullptr, nullptr});
-        return hipGetLastError();
-    }
-    }
+    // several workgroups per query meet in an atomic: nobody knows the winner
+    const bool sel = out.sel_dist && out.sel_labels && nsplit == 1;
+    const SelOut so{sel ? t.ids : nullptr, out.sel_dist, reinterpret_cast<long long *>(out.sel_labels)};
+    const dim3 grid((unsigned)p.nq * nsplit), block(256);
+    auto *k64 = reinterpret_cast<unsigned long long *>(keys);
+    return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
+        return with_mask(fmask, [&](auto... m) -> hipError_t {
+            constexpr int CS = decltype(cs)::value;
+            constexpr bool FILT = sizeof...(m) != 0;
+            // the position form: a compiled size unrolls by 4 and stages as many segments as the plan's width asks for
+            auto position = [&](auto segcap, auto unroll, const SelOut &so_) -> hipError_t {
+                constexpr auto kern = scan_k1_kernel<CS, decltype(segcap)::value, decltype(unroll)::value, 256, decltype(m)...>;
+                size_t shm;
+                if (hipError_t e = scan_table_lds<CS, kern>(t.M, &shm); e != hipSuccess)
+                    return e;
+                hipLaunchKernelGGL(kern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr,
+                                   p.max_seg, nsplit, k64, t.M, so_, m...);
+                *did_select = so_.ids != nullptr;
+                return hipGetLastError();
+            };
+            if constexpr (CS == 0) {
+                // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS, keys only
+                *kernel_name = FILT ? "scan_k1_kernel (run-time code size)+filter" : "scan_k1_kernel (run-time code size)";
+                return position(int_c<256>(), int_c<2>(), SelOut{nullptr, nullptr, nullptr});
+            } else if (seg_len_hint > 0 && seg_len_hint <= 48) {
+                // plans of short segments (Grouping sub-groups, ~16 codes): the bitmap form; whole lists: the position form
+                *kernel_name = FILT ? "scan_k1_bitmap_kernel+filter" : "scan_k1_bitmap_kernel";
+                hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4, decltype(m)...>), grid, block, 0, s, t.codes, t.norm_codes, luts,
+                                   t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, k64, so, m...);
+                *did_select = so.ids != nullptr;
+                return hipGetLastError();
+            } else {
+                *kernel_name = FILT ? "scan_k1_kernel+filter" : "scan_k1_kernel";
+                if (p.max_seg <= 64)
+                    return position(int_c<64>(), int_c<4>(), so);
+                // nprobe 65..256 (the DEEP1B preset probes 128 lists): a 5 KB plan instead of 20 KB keeps 7 workgroups
+                // per CU resident instead of 4
+                if (p.max_seg <= 256)
+                    return position(int_c<256>(), int_c<4>(), so);
+                return position(int_c<1024>(), int_c<4>(), so);
+            }
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -912,26 +874,26 @@ __global__ void select_kernel(IvfTables t, const Seg *__restrict__ segs, const P
         out_keys[i] = (long long)(key ^ kSignFlip);
 }
 
-hipError_t launch_select(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                         const uint64_t *keys, int nq, int k, float *dist, int64_t *labels, int64_t *out_keys)
+hipError_t launch_select(hipStream_t s, const IvfTables &t, const PlanView &p, const uint64_t *keys, int k, float *dist,
+                         int64_t *labels, int64_t *out_keys)
 {
-    const size_t n = (size_t)nq * k;
+    const size_t n = (size_t)p.nq * k;
     if (n == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, segs, hdr, max_seg,
-                       reinterpret_cast<const unsigned long long *>(keys), nq, k, dist,
+    hipLaunchKernelGGL(select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, p.segs, p.hdr, p.max_seg,
+                       reinterpret_cast<const unsigned long long *>(keys), p.nq, k, dist,
                        reinterpret_cast<long long *>(labels), reinterpret_cast<long long *>(out_keys), 0);
     return hipGetLastError();
 }
 
-hipError_t launch_resolve(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                          const int64_t *skeys, int nq, int k, float *dist, int64_t *labels)
+hipError_t launch_resolve(hipStream_t s, const IvfTables &t, const PlanView &p, const int64_t *skeys, int k, float *dist,
+                          int64_t *labels)
 {
-    const size_t n = (size_t)nq * k;
+    const size_t n = (size_t)p.nq * k;
     if (n == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, segs, hdr, max_seg,
-                       reinterpret_cast<const unsigned long long *>(skeys), nq, k, dist,
+    hipLaunchKernelGGL(select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, p.segs, p.hdr, p.max_seg,
+                       reinterpret_cast<const unsigned long long *>(skeys), p.nq, k, dist,
                        reinterpret_cast<long long *>(labels), (long long *)nullptr, 1);
     return hipGetLastError();
 }

@@ -363,66 +363,36 @@ __global__ __launch_bounds__(256) void heap_replay_kernel(IvfTables t, const Seg
     }
 }
 
-hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const Seg *segs, const PlanHdr *hdr, int max_seg,
-                              const uint64_t *stream, const uint32_t *stream_len, uint32_t stream_cap, int nq, int k,
-                              float *dist, int64_t *labels, uint32_t *status, int64_t *out_keys, uint32_t *redo_hdr,
-                              uint32_t *redo_list)
+hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const PlanView &p, const uint64_t *stream,
+                              const uint32_t *stream_len, uint32_t stream_cap, int k, float *dist, int64_t *labels,
+                              uint32_t *status, int64_t *out_keys, uint32_t *redo_hdr, uint32_t *redo_list)
 {
-    if (nq == 0)
+    if (p.nq == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(heap_replay_kernel, dim3((nq + 3) / 4), dim3(256), (size_t)4 * 2 * k * sizeof(float), s, t, segs, hdr, max_seg,
-                       reinterpret_cast<const unsigned long long *>(stream), stream_len, stream_cap, nq, k, dist,
+    hipLaunchKernelGGL(heap_replay_kernel, dim3((p.nq + 3) / 4), dim3(256), (size_t)4 * 2 * k * sizeof(float), s, t, p.segs, p.hdr,
+                       p.max_seg, reinterpret_cast<const unsigned long long *>(stream), stream_len, stream_cap, p.nq, k, dist,
                        reinterpret_cast<long long *>(labels), status, reinterpret_cast<long long *>(out_keys), redo_hdr,
                        redo_list);
     return hipGetLastError();
 }
 
-hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const Seg *segs,
-                            const uint32_t *lpos, const PlanHdr *hdr, int max_seg, int nq, int k, uint64_t *keys,
-                            uint64_t *stream, uint32_t *stream_len, uint32_t stream_cap, const uint32_t *fmask)
+hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, uint64_t *keys,
+                            const ScanOut &out, const uint32_t *fmask)
 {
     if (k < 1 || k > TK_KCAP)
         return hipErrorInvalidValue;
-    dim3 grid((unsigned)nq), block(256);
-    auto *k64 = reinterpret_cast<unsigned long long *>(keys);
-#define IVFHNSW_TOPK(CS)                                                                                              \
-    if (fmask)                                                                                                        \
-        hipLaunchKernelGGL((scan_topk_kernel<CS, const uint32_t *>), grid, block, 0, s, t.codes, t.norm_codes, luts,  \
-                           t.norm_table, segs, lpos, hdr, max_seg, k, k64,                                            \
-                           reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M, fmask);       \
-    else                                                                                                              \
-        hipLaunchKernelGGL((scan_topk_kernel<CS>), grid, block, 0, s, t.codes, t.norm_codes, luts, t.norm_table, segs, \
-                           lpos, hdr, max_seg, k, k64, reinterpret_cast<unsigned long long *>(stream), stream_len,    \
-                           stream_cap, t.M)
-    switch (t.M) {
-    case 4: IVFHNSW_TOPK(4); break;
-    case 8: IVFHNSW_TOPK(8); break;
-    case 16: IVFHNSW_TOPK(16); break;
-    case 32: IVFHNSW_TOPK(32); break;
-    default: {
-        const size_t shm = (size_t)t.M * 1024;
-        if (t.M % 4 || shm > kScanDynLdsMax)
-            return hipErrorInvalidValue;
-        if (fmask) {
-            auto *fkern = scan_topk_kernel<0, const uint32_t *>;
-            static DynLdsState fattr_set;
-            if (hipError_t e = raise_dyn_lds((const void *)fkern, shm, fattr_set); e != hipSuccess)
+    return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
+        return with_mask(fmask, [&](auto... m) -> hipError_t {
+            constexpr auto kern = scan_topk_kernel<decltype(cs)::value, decltype(m)...>;
+            size_t shm;
+            if (hipError_t e = scan_table_lds<decltype(cs)::value, kern>(t.M, &shm); e != hipSuccess)
                 return e;
-            hipLaunchKernelGGL(fkern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg,
-                               k, k64, reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M, fmask);
-            break;
-        }
-        auto *kern = scan_topk_kernel<0>;
-        static DynLdsState attr_set;
-        if (hipError_t e = raise_dyn_lds((const void *)kern, shm, attr_set); e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(kern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, segs, lpos, hdr, max_seg, k,
-                           k64, reinterpret_cast<unsigned long long *>(stream), stream_len, stream_cap, t.M);
-        break;
-    }
-    }
-#undef IVFHNSW_TOPK
-    return hipGetLastError();
+            hipLaunchKernelGGL(kern, dim3((unsigned)p.nq), dim3(256), shm, s, t.codes, t.norm_codes, luts, t.norm_table, p.segs,
+                               p.lpos, p.hdr, p.max_seg, k, reinterpret_cast<unsigned long long *>(keys),
+                               reinterpret_cast<unsigned long long *>(out.stream), out.stream_len, out.stream_cap, t.M, m...);
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace ivfhnsw_gpu_impl
