@@ -6,7 +6,8 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), range_search().
+// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), range_search(),
+// reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
 
@@ -98,6 +99,18 @@ public:
     /// Non-virtual (the class layout and vtable are those of the other extensions).  Throws with IVFHNSW_SHARDS > 1.
     void range_search(size_t nq, const float *x, float radius, std::vector<size_t> &lims, std::vector<float> &distances,
                       std::vector<long> &labels);
+
+    /// Extension: faiss's reconstruct by id (ivfhnsw_gpu_reconstruct): x[i*d ..] = the vector the index
+    /// stores for labels[i] -- anchor + decoded code, in the ORIGINAL space (with OPQ: rotated back) -- taken from the
+    /// device copy; the lowest row of a label several codes bear; a label no code bears gives d NaNs (0x7fc00000).
+    /// On an IndexIVF_HNSW_Grouping the anchor is the code's sub-centroid.  Non-virtual, like range_search.  Throws
+    /// with IVFHNSW_SHARDS > 1.
+    void reconstruct_labels(size_t n, const idx_t *labels, float *x);
+    /// Extension: faiss's search_and_reconstruct (ivfhnsw_gpu_search_reconstruct): search() / search_batch() and, in
+    /// recons[(q*k + j)*d ..], the stored vector of result j of query q -- of the code that won, not of the first code
+    /// bearing its label; unfilled slots are d NaNs.  Non-virtual.  Throws with IVFHNSW_SHARDS > 1.
+    void search_and_reconstruct(size_t k, const float *x, float *distances, long *labels, float *recons);
+    void search_and_reconstruct_batch(size_t nq, size_t k, const float *x, float *distances, long *labels, float *recons);
 
     virtual void add_batch(size_t n, const float *x, const idx_t *xids, const idx_t *precomputed_idx = nullptr);
     /// Extension: remove every code whose id is one of xids[0..n) from the lists (and their sub-groups); returns how many.

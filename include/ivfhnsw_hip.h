@@ -430,6 +430,68 @@ int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queri
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 
+/* ---- reconstruction of stored vectors ------------------------------------------------------------
+ *
+ * faiss's reconstruct / reconstruct_n / search_and_reconstruct and the label -> row lookup of its direct map, for the
+ * lists the handle holds, without a download.  Read-only: tables, filter and range results stay as they are, and the
+ * label filter plays no part (these calls address stored rows).
+ *   Resident row r = position r of the handle's ids / codes / norm_codes arrays, in ivfhnsw_gpu_download_ivf order; list
+ *   c is rows [offsets[c], offsets[c + 1]).  Rows stay valid until the next upload, append, add, remove or add_groups.
+ *   Anchor of a row: with V the vectors given to ivfhnsw_gpu_upload_quantizer (with OPQ: the rotated centroids), V[c]
+ *   for a row of list c; on a Grouping index, for a row of sub-group s of list c (s follows from the row's place in the
+ *   list and subgroup_sizes[c]), cv = V[nn[c][s]] + (-1.f * V[c]), anchor = V[c] + alpha[c] * cv
+ *   (IndexIVF_HNSW_Grouping.cpp:70-87).  Each step one float operation, nothing contracted.
+ *   IVFHNSW_RECON_ROTATED: y[j] = anchor[j] + pq_centroids[m][code[m]][j - m * dsub], m = j / dsub; one add.
+ *   IVFHNSW_RECON_ORIGINAL: without OPQ the same bits; with OPQ x[i] = sum over k of A[k][i] * y[k] as the k-ordered
+ *   fmaf chain from 0.0f (transform_transpose), bit for bit what ivfhnsw_gpu_rotate_dev returns for y on a handle whose
+ *   opq_A is the transpose of this one's.  NOT the reference's c + A^T * dec (IndexIVF_HNSW.cpp:106-113): a served handle
+ *   holds only the rotated centroids, so the centroid goes through the float rotation and back; the two agree to the
+ *   rounding of a d-term float sum (DESIGN.md 3.16 records the measured bound).
+ *   Empty slot (row -1, a label that no row bears, an unfilled search result): d floats of bit pattern 0x7fc00000.
+ * locate: rows[i] = the lowest resident row whose id equals labels[i], or -1; counts[i] (nullable) = the resident rows
+ *   bearing that label.  Any label value (0xffffffff included); repeated labels in the request get the same answer each;
+ *   n = 0 does nothing.  One pass over the ids against a bitmap of the labels (as ivfhnsw_gpu_remove_ids marks; at most
+ *   512 MB), hits looked up in the sorted request.  The host form is synchronous; locate_dev (labels and counts 4-byte
+ *   aligned, rows 8-byte) runs on the handle's stream and returns with it drained.  At most 2^31 - 1 labels per call.
+ * reconstruct_rows: out [n][d] = the vectors of rows[0..n); row -1 is an empty slot.  Host form: a row outside
+ *   [-1, n_local) -> IVFHNSW_ERR_INVALID and nothing written.  reconstruct_rows_dev (rows 8-byte aligned): such a row is
+ *   an empty slot; asynchronous on the handle's stream.
+ * reconstruct: locate followed by reconstruct_rows of the lowest row of every label; a label without a row gives an
+ *   empty slot and counts in *n_missing (nullable).  reconstruct_dev returns with the stream drained when n_missing is
+ *   given.
+ * search_reconstruct: distances and labels bit for bit those of ivfhnsw_gpu_search / search_dev with the same arguments
+ *   (filter, Grouping, pruning, heap_order as there); rows [nq*k] (nullable) = the resident row every result came from,
+ *   -1 for an unfilled slot; recons [nq*k][d] = that row's reconstruction -- the winning row, not the first row bearing
+ *   the label.  Runs search_dev with out_keys, so what that refuses is refused here with its status (heap_order with
+ *   k > 1024), and with heap_order = 1 a query whose candidate stream outgrows 8192 entries is an IVFHNSW_ERR_STATE at
+ *   the next synchronisation instead of being recomputed; large batches run in one part.  search_reconstruct_dev is
+ *   asynchronous on the handle's stream.
+ * Errors, all forms: before upload_ivf, the reconstructing forms before upload_quantizer or with a quantizer whose n or d
+ *   differ from the index's nc or d, a handle with shard_world > 1 (a shard holds only its own lists) ->
+ *   IVFHNSW_ERR_STATE; an unknown space, NULL buffers with n > 0, a misaligned device pointer -> IVFHNSW_ERR_INVALID; a
+ *   failed allocation -> IVFHNSW_ERR_NOMEM.  Views are allowed: they read the parent's tables, the workspace is the
+ *   view's.
+ * Memory (kept on the handle, counted by ivfhnsw_gpu_memory_bytes): locate 20 bytes per label, the bitmap, 1 KB per 4096
+ *   labels and, host form, 4 + 8 + 4 bytes per label of staging; reconstruction with OPQ in ORIGINAL space 4 d bytes per
+ *   row of a chunk of 2^18 rows, host forms as much again for the output and 8 bytes per row; search_reconstruct 8 or 16
+ *   bytes per result besides the search's own workspace. */
+#define IVFHNSW_RECON_ORIGINAL 0
+#define IVFHNSW_RECON_ROTATED 1
+int ivfhnsw_gpu_locate(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int64_t *rows, uint32_t *counts);
+int ivfhnsw_gpu_locate_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int64_t *d_rows, uint32_t *d_counts);
+int ivfhnsw_gpu_reconstruct_rows(ivfhnsw_gpu *h, size_t n, const int64_t *rows, int space, float *out);
+int ivfhnsw_gpu_reconstruct_rows_dev(ivfhnsw_gpu *h, size_t n, const int64_t *d_rows, int space, float *d_out);
+int ivfhnsw_gpu_reconstruct(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int space, float *out, uint64_t *n_missing);
+int ivfhnsw_gpu_reconstruct_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int space, float *d_out,
+                                uint64_t *n_missing);
+int ivfhnsw_gpu_search_reconstruct(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                                   const float *coarse_dists, const ivfhnsw_search_params *params, int space,
+                                   float *distances, int64_t *labels, int64_t *rows, float *recons);
+int ivfhnsw_gpu_search_reconstruct_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries,
+                                       const uint32_t *d_coarse_ids, const float *d_coarse_dists,
+                                       const ivfhnsw_search_params *params, int space, float *d_distances,
+                                       int64_t *d_labels, int64_t *d_rows, float *d_recons);
+
 /* The coarse stage alone (HierarchicalNSW::searchKnn, hnswalg.cpp:227-234, plus the unload loop of
  * IndexIVF_HNSW.cpp:249-259): device pointers, [nq*nprobe] outputs, nearest first.  Queries must
  * already be rotated when OPQ is on. */

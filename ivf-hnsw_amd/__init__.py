@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("IVFHNSW_HIP_LIB") or os.path.join(_HERE, "libivfhnsw_
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
 FILTER_ALLOW, FILTER_DENY = 0, 1
+RECON_ORIGINAL, RECON_ROTATED = 0, 1
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
 # every symbol include/ivfhnsw_hip.h declares
@@ -40,6 +41,9 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_build_graph_dev", "ivfhnsw_gpu_last_graph_longest_reverse",
     "ivfhnsw_gpu_set_filter", "ivfhnsw_gpu_set_filter_dev", "ivfhnsw_gpu_clear_filter", "ivfhnsw_gpu_filter_info",
     "ivfhnsw_gpu_range_search", "ivfhnsw_gpu_range_search_dev", "ivfhnsw_gpu_range_results", "ivfhnsw_gpu_range_results_dev",
+    "ivfhnsw_gpu_locate", "ivfhnsw_gpu_locate_dev", "ivfhnsw_gpu_reconstruct_rows", "ivfhnsw_gpu_reconstruct_rows_dev",
+    "ivfhnsw_gpu_reconstruct", "ivfhnsw_gpu_reconstruct_dev", "ivfhnsw_gpu_search_reconstruct",
+    "ivfhnsw_gpu_search_reconstruct_dev",
 )
 
 
@@ -169,6 +173,16 @@ def lib():
         L.ivfhnsw_gpu_range_results.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_range_results_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_locate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_locate_dev.argtypes = L.ivfhnsw_gpu_locate.argtypes
+        L.ivfhnsw_gpu_reconstruct_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+        L.ivfhnsw_gpu_reconstruct_rows_dev.argtypes = L.ivfhnsw_gpu_reconstruct_rows.argtypes
+        L.ivfhnsw_gpu_reconstruct.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_reconstruct_dev.argtypes = L.ivfhnsw_gpu_reconstruct.argtypes
+        L.ivfhnsw_gpu_search_reconstruct.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.ivfhnsw_gpu_search_reconstruct_dev.argtypes = L.ivfhnsw_gpu_search_reconstruct.argtypes
         L.ivfhnsw_gpu_last_scan_kernel.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_last_scan_kernel.restype = C.c_char_p
         _lib = L
@@ -511,6 +525,81 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_search_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
                                             _devptr(d_coarse_dists), C.byref(p), _devptr(d_distances),
                                             _devptr(d_labels), _devptr(d_out_keys)))
+
+    # ---- reconstruction of stored vectors (ivfhnsw_gpu_reconstruct*) ---------------------------------
+    def locate(self, labels):
+        """(rows int64 [n], counts uint32 [n]): the lowest resident row bearing each label (-1 = none) and how many rows
+        bear it.  Resident row r = position r of download_ivf()'s ids / codes / norm_codes."""
+        lab = _np(labels, np.uint32).ravel()
+        rows = np.empty(lab.size, np.int64)
+        counts = np.empty(lab.size, np.uint32)
+        _check(lib().ivfhnsw_gpu_locate(self._h, lab.size, _ptr(lab) if lab.size else None, _ptr(rows), _ptr(counts)))
+        return rows, counts
+
+    def locate_dev(self, n, d_labels, d_rows, d_counts=None):
+        """The same on device buffers (torch CUDA tensors or raw addresses); returns with the stream drained."""
+        _check(lib().ivfhnsw_gpu_locate_dev(self._h, n, _devptr(d_labels), _devptr(d_rows), _devptr(d_counts)))
+
+    def reconstruct_rows(self, rows, space=RECON_ORIGINAL):
+        """float32 [n, d]: the stored vectors of the resident rows (-1 = an empty slot: NaN 0x7fc00000)."""
+        r = _np(rows, np.int64).ravel()
+        out = np.empty((r.size, self.d), np.float32)
+        _check(lib().ivfhnsw_gpu_reconstruct_rows(self._h, r.size, _ptr(r) if r.size else None, space, _ptr(out)))
+        return out
+
+    def reconstruct_rows_dev(self, n, d_rows, d_out, space=RECON_ORIGINAL):
+        """The same on device buffers, asynchronous on the handle's stream; a row outside [0, n_local) is an empty slot."""
+        _check(lib().ivfhnsw_gpu_reconstruct_rows_dev(self._h, n, _devptr(d_rows), space, _devptr(d_out)))
+
+    def reconstruct_list(self, c, space=RECON_ORIGINAL):
+        """The vectors of list c, rows offsets[c] .. offsets[c + 1] (faiss reconstruct_n over one list)."""
+        off = np.empty(self.nc + 1, np.uint64)
+        _check(lib().ivfhnsw_gpu_download_ivf(self._h, _ptr(off), None, None, None))
+        return self.reconstruct_rows(np.arange(int(off[c]), int(off[c + 1]), dtype=np.int64), space)
+
+    def reconstruct(self, labels, space=RECON_ORIGINAL):
+        """(float32 [n, d], n_missing): the vector stored for each label (its lowest row); a label no row bears gives an
+        empty slot and counts in n_missing (faiss reconstruct by id)."""
+        lab = _np(labels, np.uint32).ravel()
+        out = np.empty((lab.size, self.d), np.float32)
+        miss = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_reconstruct(self._h, lab.size, _ptr(lab) if lab.size else None, space, _ptr(out),
+                                             C.byref(miss)))
+        return out, int(miss.value)
+
+    def reconstruct_dev(self, n, d_labels, d_out, space=RECON_ORIGINAL, count_missing=True):
+        """The same on device buffers; returns n_missing (None, and no wait for the stream, with count_missing=False)."""
+        miss = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_reconstruct_dev(self._h, n, _devptr(d_labels), space, _devptr(d_out),
+                                                 C.byref(miss) if count_missing else None))
+        return int(miss.value) if count_missing else None
+
+    def search_reconstruct(self, queries, k, nprobe, max_codes, coarse_ids=None, coarse_dists=None, efSearch=0,
+                           do_pruning=False, heap_order=False, space=RECON_ORIGINAL):
+        """search() plus, for every result, the resident row it came from and that row's vector (faiss
+        search_and_reconstruct): (distances [nq, k], labels [nq, k], rows int64 [nq, k], recons float32 [nq, k, d])."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        rows = np.empty((nq, k), np.int64)
+        rec = np.empty((nq, k, q.shape[1]), np.float32)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_reconstruct(self._h, nq, k, _ptr(q), _ptr(cid), _ptr(cd), C.byref(p), space,
+                                                    _ptr(dist), _ptr(lab), _ptr(rows), _ptr(rec)))
+        return dist, lab, rows, rec
+
+    def search_reconstruct_dev(self, nq, k, d_queries, d_distances, d_labels, d_recons, nprobe, max_codes, d_rows=None,
+                               d_coarse_ids=None, d_coarse_dists=None, efSearch=0, do_pruning=False, heap_order=False,
+                               space=RECON_ORIGINAL):
+        """The same on device buffers, asynchronous on the handle's stream."""
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_reconstruct_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                        _devptr(d_coarse_dists), C.byref(p), space, _devptr(d_distances),
+                                                        _devptr(d_labels), _devptr(d_rows), _devptr(d_recons)))
 
     # ---- range search (ivfhnsw_gpu_range_search, DESIGN.md 3.15) ---------------------------------------------------
     def range_search(self, queries, radius, nprobe, max_codes, efSearch=0, do_pruning=False, coarse_ids=None,

@@ -83,6 +83,7 @@ int check_status(ivfhnsw_gpu *h)
 void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent)
 {
     view->t = parent->t;
+    view->opq_A = parent->opq_A;
     view->has_ivf = parent->has_ivf;
     view->n_local = parent->n_local;
     view->g = parent->g;

@@ -121,7 +121,7 @@ using namespace ivfhnsw_gpu_impl;
 // frees and what ivfhnsw_gpu_memory_bytes sums (ivfhnsw_gpu::for_each_devbuf).  A new feature adds its buffers here and
 // nowhere else.  The pinned HostBufs p_in / p_out are not in it: they are not HBM.
 #define IVFHNSW_GPU_DEVBUFS(X) \
-    X(goff) X(loff) X(cnorm) X(pqc) X(ntab) X(opq_at) X(codes) X(ncodes) X(ids) /* index tables */ \
+    X(goff) X(loff) X(cnorm) X(pqc) X(ntab) X(opq_at) X(opq_a) X(codes) X(ncodes) X(ids) /* index tables */ \
     X(g_alpha) X(g_nn) X(g_sizes) X(g_inter) /* Grouping tables */ \
     X(q_counts) X(q_links) X(q_vectors) X(q_qrows) X(q_nbrows) X(q_nbnorms) X(q_fat) X(q_links_c) /* quantizer */ \
     X(e_pqc) X(e_ntab) X(e_a) X(e_at) X(e_x) X(e_idx) X(e_dist) X(e_res) X(e_tmp) X(e_codes) X(e_ncodes) /* code books, encode */ \
@@ -139,6 +139,8 @@ using namespace ivfhnsw_gpu_impl;
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
+    X(lc_bits) X(lc_labels) X(lc_sorted) X(lc_perm) X(lc_perm2) X(lc_hist) X(lc_lo) X(lc_cnt) X(lc_rows) X(lc_counts) X(lc_scalar) /* locate: label bitmap, the sorted request, answers, staging */ \
+    X(rc_rows) X(rc_y) X(rc_out) X(sr_keys) X(sr_rows) /* reconstruct: staged rows, the ROTATED chunk of an OPQ call, host-form output; search_reconstruct's keys and rows */ \
     X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
 
 struct ivfhnsw_gpu {
@@ -159,6 +161,7 @@ struct ivfhnsw_gpu {
     HostBuf p_in, p_out; // pinned: small batches of the host-pointer entry point
 
     IvfTables t{};
+    const float *opq_A = nullptr; // the OPQ matrix as uploaded, row major (t.opq_At is its transpose): reconstruct's way back
     bool has_ivf = false;
     uint64_t n_local = 0;
     GroupTables g{};

@@ -76,8 +76,11 @@ int upload_tables(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *d, bool need_lists, ui
                 at[k * d->d + i] = d->opq_A[i * d->d + k];
         if ((rc = upload(h->opq_at, at.data(), at.size() * sizeof(float))))
             return rc;
+        if ((rc = upload(h->opq_a, d->opq_A, at.size() * sizeof(float)))) // as given: ORIGINAL-space reconstruction (capi_recon.cpp)
+            return rc;
     } else {
         h->opq_at.release();
+        h->opq_a.release();
     }
     IvfTables &t = h->t;
     t.d = (int)d->d;
@@ -90,6 +93,7 @@ int upload_tables(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *d, bool need_lists, ui
     t.pq_centroids = h->pqc.as<float>();
     t.norm_table = h->ntab.as<float>();
     t.opq_At = d->opq_A ? h->opq_at.as<float>() : nullptr;
+    h->opq_A = d->opq_A ? h->opq_a.as<float>() : nullptr;
     t.shard_rank = d->shard_rank;
     t.shard_world = d->shard_world;
     return IVFHNSW_OK;

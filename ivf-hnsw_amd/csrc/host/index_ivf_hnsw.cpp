@@ -634,6 +634,39 @@ void IndexIVF_HNSW::range_search(size_t nq, const float *x, float radius, std::v
         gpu_fail("ivfhnsw_gpu_range_results");
 }
 
+void IndexIVF_HNSW::reconstruct_labels(size_t n, const idx_t *labels, float *x)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::reconstruct_labels: IVFHNSW_SHARDS > 1, and a shard holds only its own lists");
+    ensure_device();
+    if (ivfhnsw_gpu_reconstruct(gpu_, n, labels, IVFHNSW_RECON_ORIGINAL, x, nullptr))
+        gpu_fail("ivfhnsw_gpu_reconstruct");
+}
+
+void IndexIVF_HNSW::search_and_reconstruct(size_t k, const float *x, float *distances, long *labels, float *recons)
+{
+    search_and_reconstruct_batch(1, k, x, distances, labels, recons);
+}
+
+void IndexIVF_HNSW::search_and_reconstruct_batch(size_t nq, size_t k, const float *x, float *distances, long *labels,
+                                                 float *recons)
+{
+    static_assert(sizeof(long) == sizeof(int64_t), "LP64 expected");
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::search_and_reconstruct_batch: IVFHNSW_SHARDS > 1, and a shard holds only its own lists");
+    ensure_device();
+    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
+    ivfhnsw_search_params p;
+    p.nprobe = nprobe;
+    p.max_codes = max_codes;
+    p.efSearch = quantizer->efSearch;
+    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
+    p.heap_order = 1; // as search_batch: the array faiss's max-heap leaves
+    if (ivfhnsw_gpu_search_reconstruct(gpu_, nq, k, x, nullptr, nullptr, &p, IVFHNSW_RECON_ORIGINAL, distances,
+                                       reinterpret_cast<int64_t *>(labels), nullptr, recons))
+        gpu_fail("ivfhnsw_gpu_search_reconstruct");
+}
+
 // ------------------------------------------------------------------------------------------ searchDisk's re-rank
 // The base file in HBM (ivfhnsw_gpu_upload_base): records of uint32 dim + d bytes (utils.cpp:98-105), read in chunks of
 // at most 256 MB and handed over as the file image, rows d + 4 bytes apart.  Returns the library's status; file errors

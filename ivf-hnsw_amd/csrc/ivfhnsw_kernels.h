@@ -408,6 +408,26 @@ hipError_t launch_groups_rows(hipStream_t s, const uint32_t *cidx, const unsigne
                               size_t G, uint32_t *nn_dst, float *alpha_dst, float *inter_dst);
 hipError_t launch_gather_rows(hipStream_t s, const uint32_t *table, const uint32_t *rows, size_t nrows, uint32_t nsubc,
                               uint32_t *out);
+// reconstruction of stored rows (kernels_recon.hip), unsharded handles.  rows: out [n][d] = the ROTATED-
+// space vector of resident row rows[i] (anchor + decoded code, one add per component; V = the quantizer's vectors, g null
+// = IVFADC); a row outside [0, n_local) is an empty slot: d floats of kReconEmptyBits.  refill: the empty slots of out
+// once more (behind launch_opq, which has no rule for them).  resolve_rows: signed result keys of the plan p ->
+// the resident row each came from, -1 for an unfilled slot.
+constexpr uint32_t kReconEmptyBits = 0x7fc00000u;
+hipError_t launch_recon_rows(hipStream_t s, const IvfTables &t, const GroupTables *g, const float *V, uint64_t n_local,
+                             const int64_t *rows, size_t n, float *out);
+hipError_t launch_recon_refill(hipStream_t s, uint64_t n_local, const int64_t *rows, size_t n, int d, float *out);
+hipError_t launch_resolve_rows(hipStream_t s, const PlanView &p, const int64_t *skeys, int k, int64_t *rows);
+// locate (same file): hit, one pass over ids [n_local]: an id whose bit is set in bits ([0, max_label]) is looked up in
+// sorted [n] (the request's labels ascending, repeats allowed) and its FIRST place p gets lo[p] = min(lo[p], row),
+// cnt[p] += 1 (lo 0xffffffff, cnt 0 before).  gather: sorted[j] = labels[perm[j]].  scatter: request perm[j] receives the
+// answer of the first place of its label: rows (-1 = none) and counts (nullable); *missing (nullable, zeroed before) +=
+// the requests without a row.
+hipError_t launch_locate_gather(hipStream_t s, const uint32_t *labels, const uint32_t *perm, size_t n, uint32_t *sorted);
+hipError_t launch_locate_hit(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
+                             const uint32_t *sorted, size_t n, uint32_t *lo, uint32_t *cnt);
+hipError_t launch_locate_scatter(hipStream_t s, const uint32_t *sorted, const uint32_t *perm, size_t n, const uint32_t *lo,
+                                 const uint32_t *cnt, int64_t *rows, uint32_t *counts, unsigned long long *missing);
 // sum of PlanHdr.total / nseg over the batch into out[0], out[1]
 hipError_t launch_plan_totals(hipStream_t s, const PlanHdr *hdr, int nq, unsigned long long *out);
 
