@@ -322,6 +322,29 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
     return (uint32_t)x;
 }
 
+// the same over 64-bit values (code counts of a plan), by __shfl_up
+__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o = __shfl_up(v, off, 64);
+        if (lane >= off)
+            v += o;
+    }
+    return v;
+}
+
+// minimum over the wavefront, left in every lane (packed keys: the reference's strict-'<' first-wins top-1)
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        uint64_t o = __shfl_xor((unsigned long long)v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // order-preserving map f32 -> u32 (and back) for packed (distance, scan position) keys
 __device__ __forceinline__ uint32_t f32_orderable(float f)
 {

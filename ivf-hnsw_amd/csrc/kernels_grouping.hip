@@ -228,17 +228,6 @@ __device__ __forceinline__ void wave_lds_order()
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
-__device__ __forceinline__ unsigned long long incl_scan_u64(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += o;
-    }
-    return v;
-}
-
 // DEDUPE (round 3): phase A evaluates every DISTINCT neighbour centroid of the query once.  The reference caches
 // ||x - y_N||^2 per query (query_centroid_dists, Grouping.cpp:244-250, 311-316) because the probed groups' neighbour lists
 // overlap: on clustered centroids -- a query's probes are each other's neighbours -- the ~1350 (row, sub-group) pairs of a
@@ -323,7 +312,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
                 gs = t.goff[c + 1] - t.goff[c];
             const bool ne = gs != 0;
             const unsigned long long m = __ballot(ne);
-            const unsigned long long incl = incl_scan_u64(gs, lane) + cum;
+            const unsigned long long incl = wave_incl_scan_u64(gs, lane) + cum;
             const int upto = nrows + __popcll(m & ((2ull << lane) - 1ull)); // rows up to and including this lane's
             if (ne) {
                 s_rowp[upto - 1] = i;

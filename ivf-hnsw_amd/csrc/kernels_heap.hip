@@ -1,7 +1,7 @@
 // k > 1 in faiss heap-array order with no bound on k and none on the codes the heap admits (IndexIVF_HNSW.cpp:265,
-// 285-288).  heap_scan_kernel scores a query's codes straight from the plan and the table the search has built, with the
-// arithmetic of scan_topk_kernel (kernels_topk.hip), and replays the reference's pop/push over them itself: no candidate
-// stream, so no stream cap.
+// 285-288).  heap_scan_kernel scores a query's codes straight from the plan and the table the search has built, by the
+// steps of scan_topk_kernel (kernels_topk.hip, scan_steps.h), and replays the reference's pop/push over them itself: no
+// candidate stream, so no stream cap.
 //
 // Exactness is the argument above heap_replay_kernel: a code that fails dist < distances[0] leaves the heap untouched, and
 // a root read earlier in the scan is never below the current root.  So the codes of a chunk that pass dist < root, with
@@ -13,8 +13,7 @@
 //   LDS     the heap beside the table and the chunk buffer (8 k bytes; k <~ 16 500 at PQ16, <~ 2 200 at code size 128)
 //   global  the heap in a per-workgroup slot of a global workspace: exact but slow, every level of a sift is a round
 //           trip to L2 (~200 cycles instead of ~50 for a dependent ds_read)
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 
@@ -79,19 +78,12 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
         const uint32_t nseg = h.total ? h.nseg : 0u;
         for (uint32_t cs = 0; cs < nseg; cs += HS_SEGCAP) {
             const uint32_t cn = min((uint32_t)HS_SEGCAP, nseg - cs);
+            const uint32_t ch = plan_chunk_end(lq, cs, cn, nseg, h.total);
             __syncthreads();
-            for (uint32_t i = tid; i < cn; i += 256) {
-                s_seg[i] = sq[cs + i];
-                s_lpos[i] = lq[cs + i];
-            }
-            const uint32_t ch = (cs + cn == nseg) ? h.total : lq[cs + cn];
-            if (tid == 0)
-                s_lpos[cn] = ch;
+            stage_plan_chunk<256>(sq, lq, cs, cn, ch, s_seg, s_lpos, tid);
             __syncthreads();
             const uint32_t cl = s_lpos[0];
-            // the segment this lane is inside, kept in registers (positions only grow)
-            uint32_t s = 0, seg_lo = 0, seg_hi = 0, seg_start = 0, seg_vpos = 0;
-            float seg_ct = 0.f;
+            SegCursor c;
             for (uint32_t base = cl; base < ch; base += HS_CHUNK) {
                 const float root = val[0]; // the heap is at rest here (barrier behind the last replay)
                 CodeRegs<CS> w[HS_U];
@@ -104,33 +96,15 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                     const uint32_t p = base + u * 256 + tid;
                     ok[u] = p < ch;
                     if (ok[u]) {
-                        if (p >= seg_hi) {
-                            uint32_t a = s, b = cn - 1;
-                            while (a < b) {
-                                const uint32_t mid = (a + b) >> 1;
-                                if (s_lpos[mid + 1] > p)
-                                    b = mid;
-                                else
-                                    a = mid + 1;
-                            }
-                            s = a;
-                            const Seg sg = s_seg[s];
-                            seg_lo = s_lpos[s];
-                            seg_hi = seg_lo + sg.len;
-                            seg_start = sg.start;
-                            seg_vpos = sg.vpos;
-                            seg_ct = sg.cterm;
-                        }
-                        const uint32_t off = p - seg_lo;
-                        const uint32_t gi = seg_start + off;
+                        c.seek<SeekHalves>(p, s_lpos, s_seg, cn);
+                        const uint32_t off = p - c.seg_lo;
+                        const uint32_t gi = c.seg_start + off;
                         code_fetch<CS>(t.codes, gi, t.M, s_lut, w[u]);
-                        nbv[u] = t.norm_codes[gi];
-                        if constexpr (FILT) {
-                            fw[u] = fmask[gi >> 5];
+                        load_norm_filter<FILT>(t.norm_codes, fmask, gi, nbv[u], fw[u]);
+                        if constexpr (FILT)
                             fb[u] = gi & 31u;
-                        }
-                        vp[u] = seg_vpos + off;
-                        ct[u] = seg_ct;
+                        vp[u] = c.seg_vpos + off;
+                        ct[u] = c.seg_ct;
                     }
                 }
 #pragma unroll
@@ -138,14 +112,12 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                     pass[u] = false;
                     dn[u] = 0.f;
                     if constexpr (FILT)
-                        ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
+                        ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
                     if (ok[u]) {
-                        // scan_topk_kernel's arithmetic, term for term
                         const float sum = code_sum<CS>(s_lut, w[u]);
-                        const float tt = __fadd_rn(ct[u], s_norm[nbv[u]]);
-                        const float d = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                        const float d = adc_distance(ct[u], s_norm[nbv[u]], sum);
                         if (d < FLT_MAX) {
-                            dn[u] = __fadd_rn(d, 0.0f);
+                            dn[u] = adc_value(d);
                             pass[u] = dn[u] < root;
                         }
                     }

@@ -1,15 +1,14 @@
 // gfx950 kernels of range search: every scored code with dist < radius, in scan order.
 //
-// The scan of kernels_search.hip keeps a minimum; this one keeps hits.  Plan, table and filter mask are consumed exactly
-// as scan_k1_kernel / scan_k1_bitmap_kernel consume them, and the distance is formed by the same intrinsics in the same
-// order, so a returned distance is bit for bit what the k-search returns for that code.  Two passes over the same
+// The scan of kernels_search.hip keeps a minimum; this one keeps hits.  Plan, table and filter mask are consumed by the
+// steps scan_k1_kernel / scan_k1_bitmap_kernel consume them by (scan_steps.h), and the distance is adc_distance, so a
+// returned distance is bit for bit what the k-search returns for that code.  Two passes over the same
 // (query, slice) grid: COUNT leaves the hits of every slice, a prefix over them gives every slice its place in the
 // output, FILL scores the slice again and writes hit number r of the slice at base + r.  A slice without hits ends the
 // fill pass before it stages its table.
 //
 // Float contract as in kernels_search.hip: explicit round-to-nearest intrinsics, built with -ffp-contract=off.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 #include <algorithm>
@@ -19,34 +18,13 @@ namespace ivfhnsw_gpu_impl {
 namespace {
 
 constexpr int RG_THREADS = 256;
-constexpr int RG_SEGCAP = 256;                // plan segments staged at a time (position form)
-constexpr int RG_BM_SEGCAP = 256;             // ... and in the bitmap form, whose chunk also spans at most
-constexpr int RG_BM_SPANCAP = 8192;           // ... this many positions
-constexpr int RG_BM_SPANW = RG_BM_SPANCAP / 64;
+constexpr int RG_SEGCAP = 256; // plan segments staged at a time (position form)
 
 struct RangeOut {
     const uint32_t *ids;
     float *dist;
     long long *labels;
 };
-
-// the ADC sum of one code, m = 0..CS-1 in order (IndexIVF_HNSW.cpp:802-814); byte-offset table addressing as the k = 1
-// scan's adc_sum_lds, the run-time form's sum was taken while the code was read (code_fetch)
-template <int CS> __device__ __forceinline__ float range_code_sum(const float *s_lut, const CodeRegs<CS> &r)
-{
-    if constexpr (CS > 0) {
-        float sum = 0.0f;
-        const char *base = reinterpret_cast<const char *>(s_lut);
-#pragma unroll
-        for (int m = 0; m < CS; m++) {
-            const uint32_t e = (r.w[m >> 2] >> ((m & 3) * 8)) & 0xffu;
-            sum = __fadd_rn(sum, *reinterpret_cast<const float *>(base + m * 1024 + (e << 2)));
-        }
-        return sum;
-    } else {
-        return r.sum;
-    }
-}
 
 // What a workgroup does with the hits of one tile: U rows of RG_THREADS consecutive positions, row u before row u + 1,
 // lane t of a row before lane t + 1 -- position order.
@@ -105,21 +83,7 @@ __device__ __forceinline__ void range_finish(uint32_t *slices, uint32_t run, int
     }
 }
 
-// The table of query q into LDS, global -> LDS directly (global_load_lds_dwordx4: wave-uniform LDS base + lane * 16), and
-// the norm table; the caller's next __syncthreads waits for both.
-__device__ __forceinline__ void range_stage_tables(const float *luts, const float *norm_table, int q, int csz, float *s_lut,
-                                                   float *s_norm, int tid)
-{
-    const float4 *src = reinterpret_cast<const float4 *>(luts + (size_t)q * csz * 256);
-    const int lane = tid & 63;
-    for (int i = tid; i < csz * 64; i += RG_THREADS)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
-                                         (__attribute__((address_space(3))) void *)(reinterpret_cast<float4 *>(s_lut) + (i - lane)),
-                                         16, 0, 0);
-    s_norm[tid] = norm_table[tid];
-}
-
-// Position form (whole inverted lists): the slicing, the plan chunks and the per-lane segment cache of scan_k1_kernel.
+// Position form (whole inverted lists): scan_slice, stage_plan_chunk and a SegCursor, as scan_k1_kernel.
 // CS == 0: run-time code size cs_rt, table in dynamic LDS.  Mask: empty, or the pass mask of a label filter.
 template <int CS, int U, bool FILL, class... Mask>
 __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *__restrict__ codes,
@@ -149,11 +113,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
     const PlanHdr h = hdr[q];
     if (h.total == 0)
         return;
-    // this slice of the query's virtual code array, in multiples of the block width
-    uint32_t per = (h.total + nsplit - 1) / nsplit;
-    per = (per + (RG_THREADS - 1)) & ~(uint32_t)(RG_THREADS - 1);
-    const uint32_t lo = min((uint32_t)split * per, h.total);
-    const uint32_t hi = min(lo + per, h.total);
+    const auto [lo, hi] = scan_slice(h.total, nsplit, split, RG_THREADS);
     if (lo >= hi)
         return;
     uint32_t out_base = 0;
@@ -162,7 +122,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
         if (slices[blockIdx.x + 1] == out_base) // the count pass found nothing here
             return;
     }
-    range_stage_tables(luts, norm_table, q, csz, s_lut, s_norm, tid);
+    stage_table_dma<RG_THREADS>(luts, q, csz, s_lut, tid);
+    s_norm[tid] = norm_table[tid];
 
     const Seg *sq = segs + (size_t)q * max_seg;
     const uint32_t *lq = lpos + (size_t)q * max_seg;
@@ -171,26 +132,17 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
 
     for (uint32_t cs = 0; cs < h.nseg; cs += RG_SEGCAP) {
         const uint32_t cn = min((uint32_t)RG_SEGCAP, h.nseg - cs);
-        const uint32_t ch = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
+        const uint32_t ch = plan_chunk_end(lq, cs, cn, h.nseg, h.total);
         if (ch <= lo) // block-uniform: the chunk ends before this slice
             continue;
         if (lq[cs] >= hi)
             break;
         __syncthreads(); // previous chunk fully consumed (and the tables staged, first time)
-        for (uint32_t i = tid; i < cn; i += RG_THREADS) {
-            s_seg[i] = sq[cs + i];
-            s_lpos[i] = lq[cs + i];
-        }
-        if (tid == 0)
-            s_lpos[cn] = ch;
+        stage_plan_chunk<RG_THREADS>(sq, lq, cs, cn, ch, s_seg, s_lpos, tid);
         __syncthreads();
         const uint32_t cl = s_lpos[0];
         const uint32_t b0 = max(cl, lo), b1 = min(ch, hi);
-        // the segment this lane is inside, in registers: positions only grow, the LDS plan is searched again only when a
-        // position runs past the segment's end
-        uint32_t s = 0;
-        uint32_t seg_lo = 0, seg_hi = 0, seg_start = 0;
-        float seg_ct = 0.f;
+        SegCursor c;
         for (uint32_t base = b0; base < b1; base += RG_THREADS * U) {
             CodeRegs<CS> w[U];
             uint32_t nb[U], gi[U];
@@ -203,52 +155,24 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
                 ok[u] = p < b1;
                 gi[u] = 0;
                 if (ok[u]) {
-                    if (p >= seg_hi) {
-                        // first s with s_lpos[s + 1] > p, searched in [s, cn): two steps forward, then by halves
-                        uint32_t a = s, b = cn - 1;
-                        if (a < b && s_lpos[a + 1] <= p) {
-                            a++;
-                            if (a < b && s_lpos[a + 1] <= p)
-                                a++;
-                            else
-                                b = a;
-                        } else {
-                            b = a;
-                        }
-                        while (a < b) {
-                            const uint32_t mid = (a + b) >> 1;
-                            if (s_lpos[mid + 1] > p)
-                                b = mid;
-                            else
-                                a = mid + 1;
-                        }
-                        s = a;
-                        const Seg sg = s_seg[s];
-                        seg_lo = s_lpos[s];
-                        seg_hi = seg_lo + sg.len;
-                        seg_start = sg.start;
-                        seg_ct = sg.cterm;
-                    }
-                    gi[u] = seg_start + (p - seg_lo);
+                    c.seek<SeekStep2Halves>(p, s_lpos, s_seg, cn);
+                    gi[u] = c.seg_start + (p - c.seg_lo);
                     code_fetch<CS>(codes, gi[u], cs_rt, s_lut, w[u]);
-                    nb[u] = norm_codes[gi[u]];
-                    if constexpr (FILT)
-                        fw[u] = fmask[gi[u] >> 5];
-                    ct[u] = seg_ct;
+                    load_norm_filter<FILT>(norm_codes, fmask, gi[u], nb[u], fw[u]);
+                    ct[u] = c.seg_ct;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if constexpr (FILT)
-                    ok[u] = ok[u] && ((fw[u] >> (gi[u] & 31u)) & 1u);
+                    ok[u] = ok[u] && filter_pass(fw[u], gi[u] & 31u);
                 hit[u] = false;
                 dv[u] = 0.f;
                 if (ok[u]) {
-                    const float sum = range_code_sum<CS>(s_lut, w[u]);
-                    const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
-                    const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                    const float sum = code_sum_lds<CS>(s_lut, w[u]);
+                    const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
                     hit[u] = dist < radius; // strict, and false for a NaN distance
-                    dv[u] = __fadd_rn(dist, 0.0f);
+                    dv[u] = adc_value(dist);
                 }
             }
             range_tile<U, FILL>(hit, dv, gi, s_wcnt, buf, run, out_base, out, lane, wave);
@@ -258,8 +182,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
 }
 
 // Short-segment form (Grouping sub-groups of ~10-16 codes): positions are dealt to lanes one code each and the segment of
-// a position comes from a bitmap of segment starts plus the starts before every 64-position word, as in
-// scan_k1_bitmap_kernel -- one broadcast LDS read and two v_mbcnt instead of a search per position, and no idle lanes.
+// a position comes from a bitmap of segment starts plus the starts before every 64-position word (scan_steps.h
+// BitmapChunk, as scan_k1_bitmap_kernel) -- one broadcast LDS read and two v_mbcnt instead of a search per position.
 template <int CS, int U, bool FILL, class... Mask>
 __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uint8_t *__restrict__ codes,
                                                                        const uint8_t *__restrict__ norm_codes,
@@ -275,10 +199,10 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
     [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     __shared__ __attribute__((aligned(16))) float s_lut[CS * 256];
     __shared__ float s_norm[256];
-    __shared__ __attribute__((aligned(16))) Seg s_seg[RG_BM_SEGCAP];
-    __shared__ uint32_t s_lpos[RG_BM_SEGCAP + 1];
-    __shared__ unsigned long long s_mask[RG_BM_SPANW];
-    __shared__ uint32_t s_pref[RG_BM_SPANW];
+    __shared__ __attribute__((aligned(16))) Seg s_seg[kBmSegCap];
+    __shared__ uint32_t s_lpos[kBmSegCap + 1];
+    __shared__ unsigned long long s_mask[kBmSpanWords];
+    __shared__ uint32_t s_pref[kBmSpanWords];
     __shared__ uint32_t s_wtot[RG_THREADS / 64];
     __shared__ uint32_t s_wcnt[2][U][RG_THREADS / 64];
 
@@ -288,10 +212,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
     const PlanHdr h = hdr[q];
     if (h.total == 0)
         return;
-    uint32_t per = (h.total + nsplit - 1) / nsplit;
-    per = (per + 255u) & ~255u;
-    const uint32_t lo = min((uint32_t)split * per, h.total);
-    const uint32_t hi = min(lo + per, h.total);
+    const auto [lo, hi] = scan_slice(h.total, nsplit, split, RG_THREADS);
     if (lo >= hi)
         return;
     uint32_t out_base = 0;
@@ -300,75 +221,22 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
         if (slices[blockIdx.x + 1] == out_base)
             return;
     }
-    range_stage_tables(luts, norm_table, q, CS, s_lut, s_norm, tid);
+    stage_table_dma<RG_THREADS>(luts, q, CS, s_lut, tid);
+    s_norm[tid] = norm_table[tid];
 
     const Seg *sq = segs + (size_t)q * max_seg;
     const uint32_t *lq = lpos + (size_t)q * max_seg;
     uint32_t run = 0;
     int buf = 0;
 
-    // first segment of this slice: the last one starting at or before lo
-    uint32_t cs = 0;
-    if (lo > 0) {
-        uint32_t a = 0, b = h.nseg - 1;
-        while (a < b) {
-            const uint32_t mid = (a + b + 1) >> 1;
-            if (lq[mid] <= lo)
-                a = mid;
-            else
-                b = mid - 1;
-        }
-        cs = a;
-    }
+    uint32_t cs = first_segment(lq, h.nseg, lo);
     while (cs < h.nseg) {
         const uint32_t cl = lq[cs];
         if (cl >= hi)
             break;
-        // as many segments as fit the plan buffer AND the bitmap's span; one oversized segment goes alone
-        uint32_t cn = min((uint32_t)RG_BM_SEGCAP, h.nseg - cs);
-        {
-            const uint32_t end_all = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-            if (end_all - cl > (uint32_t)RG_BM_SPANCAP) {
-                uint32_t a = 1, b = cn > 1 ? cn - 1 : 1; // largest count whose end stays inside the span (or 1)
-                while (a < b) {
-                    const uint32_t mid = (a + b + 1) >> 1;
-                    if (lq[cs + mid] - cl <= (uint32_t)RG_BM_SPANCAP)
-                        a = mid;
-                    else
-                        b = mid - 1;
-                }
-                cn = a;
-            }
-        }
-        const uint32_t ch = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-        const bool single = ch - cl > (uint32_t)RG_BM_SPANCAP; // cn == 1: every position belongs to segment 0
-        const uint32_t nwords = single ? 0u : (ch - cl + 63) >> 6;
-        __syncthreads(); // previous chunk fully consumed (and the tables staged, first time)
-        for (uint32_t i = tid; i < cn; i += RG_THREADS) {
-            s_seg[i] = sq[cs + i];
-            s_lpos[i] = lq[cs + i];
-        }
-        if (tid < (int)nwords)
-            s_mask[tid] = 0ull;
-        __syncthreads();
-        if (!single) {
-            uint32_t *m32 = reinterpret_cast<uint32_t *>(s_mask);
-            for (uint32_t i = tid; i < cn; i += RG_THREADS) {
-                const uint32_t r = s_lpos[i] - cl;
-                atomicOr(&m32[r >> 5], 1u << (r & 31));
-            }
-            __syncthreads();
-            // starts before every word (at most 128 words: waves 0 and 1 scan, two totals)
-            const uint32_t cnt = tid < (int)nwords ? (uint32_t)__popcll(s_mask[tid]) : 0u;
-            const uint32_t inc = wave_incl_scan(cnt, lane);
-            if (lane == 63)
-                s_wtot[wave] = inc;
-            __syncthreads();
-            if (tid < (int)nwords)
-                s_pref[tid] = (wave ? s_wtot[0] : 0u) + inc - cnt;
-            __syncthreads();
-        }
-        const uint32_t b0 = max(cl, lo), b1 = min(ch, hi);
+        const BitmapChunk bc =
+            stage_bitmap_chunk<RG_THREADS>(sq, lq, cs, h.nseg, h.total, s_seg, s_lpos, s_mask, s_pref, s_wtot, tid);
+        const uint32_t b0 = max(cl, lo), b1 = min(bc.ch, hi);
         if (b0 < b1) {
             for (uint32_t rbase = (b0 - cl) & ~63u; rbase < b1 - cl; rbase += RG_THREADS * U) {
                 CodeRegs<CS> w[U];
@@ -382,22 +250,14 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
                     const uint32_t p = cl + r;
                     ok[u] = p >= b0 && p < b1;
                     gi[u] = 0;
-                    const uint32_t wi = __builtin_amdgcn_readfirstlane(r >> 6);
+                    const uint32_t wi = BitmapChunk::word_of(r);
                     if (wi * 64u < b1 - cl) { // wave-uniform
-                        uint32_t sgi = 0;
-                        if (!single) {
-                            const unsigned long long mw = s_mask[wi];
-                            const uint32_t below =
-                                __builtin_amdgcn_mbcnt_hi((uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
-                            sgi = s_pref[wi] + below + (uint32_t)((mw >> lane) & 1ull) - 1u;
-                        }
+                        const uint32_t sgi = bc.segment_of(wi, lane);
                         if (ok[u]) {
                             const Seg sg = s_seg[sgi];
                             gi[u] = sg.start + (p - s_lpos[sgi]);
                             code_fetch<CS>(codes, gi[u], CS, s_lut, w[u]);
-                            nb[u] = norm_codes[gi[u]];
-                            if constexpr (FILT)
-                                fw[u] = fmask[gi[u] >> 5];
+                            load_norm_filter<FILT>(norm_codes, fmask, gi[u], nb[u], fw[u]);
                             ct[u] = sg.cterm;
                         }
                     }
@@ -405,21 +265,20 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     if constexpr (FILT)
-                        ok[u] = ok[u] && ((fw[u] >> (gi[u] & 31u)) & 1u);
+                        ok[u] = ok[u] && filter_pass(fw[u], gi[u] & 31u);
                     hit[u] = false;
                     dv[u] = 0.f;
                     if (ok[u]) {
-                        const float sum = range_code_sum<CS>(s_lut, w[u]);
-                        const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
-                        const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                        const float sum = code_sum_lds<CS>(s_lut, w[u]);
+                        const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
                         hit[u] = dist < radius;
-                        dv[u] = __fadd_rn(dist, 0.0f);
+                        dv[u] = adc_value(dist);
                     }
                 }
                 range_tile<U, FILL>(hit, dv, gi, s_wcnt, buf, run, out_base, out, lane, wave);
             }
         }
-        cs += cn;
+        cs += bc.cn;
     }
     range_finish<FILL>(slices, run, lane);
 }

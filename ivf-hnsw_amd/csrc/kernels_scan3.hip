@@ -15,12 +15,11 @@
 // Every global load is consumed one full iteration after it was issued, there is ONE barrier per query (hand-written:
 // __syncthreads() would drain the loads in flight, guide 5.3), and the per-wave minima meet in LDS, one wavefront
 // writing the query's key an iteration later.  Same arithmetic in the same order as lut_kernel /
-// scan_k1_kernel (ip_sse_order, adc_sum, the packed (distance, scan position) key), so the same bits.
+// scan_k1_kernel (ip_sse_order, adc_sum, adc_distance / adc_key of scan_steps.h), so the same bits.
 //
 // Buffers: tables x2, plan and query x3 (item j's plan is still read by the slower wavefronts' extra passes while a
 // faster one already stores item j+2's).  ~37 KB of LDS and ~120 VGPRs per 512-thread workgroup: two per CU.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 #include <stdio.h>
@@ -37,16 +36,6 @@ __device__ __forceinline__ void pipe_barrier()
 {
     // LDS traffic drained, global loads left in flight
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ unsigned long long pipe_wave_min(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
 }
 
 template <int CS, int U>
@@ -124,10 +113,9 @@ __device__ __forceinline__ unsigned long long pipe_score(const PipeRegs<CS, U> &
             const Seg sg = s_seg[s];
             const uint32_t vp = sg.vpos + (base + u * PT + tid - s_lpos[s]);
             const float sum = adc_sum<CS>(s_lut, r.w[u]);
-            const float tt = __fadd_rn(sg.cterm, s_norm[r.nb[u]]);
-            const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+            const float dist = adc_distance(sg.cterm, s_norm[r.nb[u]], sum);
             if (dist < FLT_MAX) { // also rejects NaN, as 'dist < distances[0]' does
-                const unsigned long long key = ((unsigned long long)f32_orderable(__fadd_rn(dist, 0.0f)) << 32) | vp;
+                const unsigned long long key = adc_key(dist, vp);
                 best = key < best ? key : best;
             }
         }
@@ -313,7 +301,7 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 pipe_touch<CS, U>(regs);
                 best = pipe_score<CS, U>(regs, s_lut[j & 1], s_norm, s_seg[b0], s_lpos[b0], total, base, tid, best);
             }
-            best = pipe_wave_min(best);
+            best = wave_min_u64(best);
         }
         // the wavefronts' minima meet in LDS; wave 3 writes the query's key an iteration later (no atomic, and no
         // store whose completion a later wait of THIS iteration would sit on)

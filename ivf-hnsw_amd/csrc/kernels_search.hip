@@ -4,8 +4,7 @@
 // Float contract (see DESIGN.md "Numerics"): every arithmetic step is an explicit round-to-nearest
 // intrinsic in the order the reference's source evaluates it; this file is built with
 // -ffp-contract=off so nothing else gets fused either.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 #include <stdlib.h>
@@ -178,17 +177,6 @@ hipError_t launch_lut(hipStream_t s, const IvfTables &t, const float *xq, float 
 // the list that makes ncode >= max_codes.  Depends only on coarse results and list sizes, never on
 // codes, so it is computed up front and the scan itself is order-free.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += o;
-    }
-    return v;
-}
-
 // One wavefront per query, lanes over the probes (chunks of 64): list sizes in parallel, the max_codes prefix
 // rule by a wave scan -- list i is scored iff fewer than max_codes codes precede it in probe order.
 __device__ __forceinline__ void plan_ivf_body(int bid, const IvfTables &t, const uint32_t *__restrict__ cid,
@@ -327,32 +315,9 @@ hipError_t launch_plan_ivf(hipStream_t s, const IvfTables &t, const uint32_t *co
 // Per code: CS LDS gathers summed in m order, dist = (cterm + norm) - 2*sum, packed into a
 // (distance, scan position) key; the wave/block minimum is the reference's strict-'<' first-wins top-1.
 // Bound: HBM read of CS+1 bytes per code; the CS LDS gathers per code run at about the same rate
-// (random bank conflicts), see DESIGN.md.
+// (random bank conflicts), see DESIGN.md.  The steps shared with the other scan kernels: scan_steps.h.  (Replicating the
+// table over disjoint LDS banks was built and measured in round 1 -- no gain, DESIGN.md 3.1 -- and removed in round 3.)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        uint64_t o = __shfl_xor((unsigned long long)v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-// The ADC sum of one code from the query's table in LDS, m = 0..CS-1 in order (IndexIVF_HNSW.cpp:802-814).  (Replicating
-// the table over disjoint LDS banks was built and measured in round 1 -- no gain, DESIGN.md 3.1 -- and removed in round 3.)
-template <int CS>
-__device__ __forceinline__ float adc_sum_lds(const float *s_lut, const uint32_t (&w)[CS > 0 ? CS / 4 : 1])
-{
-    float sum = 0.0f;
-    const char *base = reinterpret_cast<const char *>(s_lut);
-#pragma unroll
-    for (int m = 0; m < CS; m++) {
-        const uint32_t e = (w[m >> 2] >> ((m & 3) * 8)) & 0xffu;
-        sum = __fadd_rn(sum, *reinterpret_cast<const float *>(base + m * 1024 + (e << 2)));
-    }
-    return sum;
-}
 
 // The winner's label resolved by the scan itself (k = 1, one workgroup per query, results wanted as distance + label):
 // select_kernel would re-read the key and the plan for 9 us and a launch.  ids == nullptr: keys only, as before.
@@ -420,50 +385,29 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
             sel_write(so, q, kKeyInit, nullptr, 0);
         return;
     }
-    // this split's slice of the virtual code array, in multiples of the block width
-    uint32_t per = (h.total + nsplit - 1) / nsplit;
-    per = (per + (THREADS - 1)) & ~(uint32_t)(THREADS - 1);
-    const uint32_t lo = min((uint32_t)split * per, h.total);
-    const uint32_t hi = min(lo + per, h.total);
+    const auto [lo, hi] = scan_slice(h.total, nsplit, split, THREADS);
     if (lo >= hi)
         return;
 
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(luts + (size_t)q * csz * 256);
-        // global -> LDS directly (global_load_lds_dwordx4: wave-uniform LDS base + lane * 16): the table never
-        // passes through VGPRs, and a ds_write_b128 costs the LDS pipe 13 cycles where the DMA's write costs 4
-        // -- the scan is bound by that pipe
-        const int lane = tid & 63;
-        for (int i = tid; i < csz * 64; i += THREADS)
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(src + i),
-                (__attribute__((address_space(3))) void *)(reinterpret_cast<float4 *>(s_lut) + (i - lane)), 16, 0, 0);
-        for (int i = tid; i < 256; i += THREADS)
-            s_norm[i] = norm_table[i];
-    }
+    stage_table_dma<THREADS>(luts, q, csz, s_lut, tid);
+    for (int i = tid; i < 256; i += THREADS)
+        s_norm[i] = norm_table[i];
 
     const Seg *sq = segs + (size_t)q * max_seg;
     const uint32_t *lq = lpos + (size_t)q * max_seg;
     unsigned long long best = kKeyInit;
+    // whole lists, at most 64 of them: the next position is in this list or the next one
+    using Seek = std::conditional_t<SEGCAP <= 64, SeekLinear, SeekStep2Halves>;
 
     for (uint32_t cs = 0; cs < h.nseg; cs += SEGCAP) {
         const uint32_t cn = min((uint32_t)SEGCAP, h.nseg - cs);
+        const uint32_t ch = plan_chunk_end(lq, cs, cn, h.nseg, h.total);
         __syncthreads(); // previous chunk fully consumed (and LUT staged, first time)
-        for (uint32_t i = tid; i < cn; i += THREADS) {
-            s_seg[i] = sq[cs + i];
-            s_lpos[i] = lq[cs + i];
-        }
-        const uint32_t ch = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-        if (tid == 0)
-            s_lpos[cn] = ch;
+        stage_plan_chunk<THREADS>(sq, lq, cs, cn, ch, s_seg, s_lpos, tid);
         __syncthreads();
         const uint32_t cl = s_lpos[0];
         const uint32_t b0 = max(cl, lo), b1 = min(ch, hi);
-        // the segment this lane is currently inside, kept in registers: positions only grow, so the LDS plan is
-        // consulted again only when a position runs past the segment's end
-        uint32_t s = 0;
-        uint32_t seg_lo = 0, seg_hi = 0, seg_start = 0, seg_vpos = 0;
-        float seg_ct = 0.f;
+        SegCursor c;
         for (uint32_t base = b0; base < b1; base += THREADS * U) {
             CodeRegs<CS> w[U];
             uint32_t nb[U], vp[U];
@@ -475,67 +419,26 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
                 const uint32_t p = base + u * THREADS + tid;
                 ok[u] = p < b1;
                 if (ok[u]) {
-                    if (p >= seg_hi) {
-                        if constexpr (SEGCAP <= 64) {
-                            while (p >= s_lpos[s + 1])
-                                s++;
-                        } else {
-                            // first s with s_lpos[s+1] > p, searched in (s, cn).  Inverted lists are about as long
-                            // as the block's stride (1024 positions), so the segment is usually the next one or the
-                            // one after: two steps forward before the binary search (which sub-group plans need).
-                            uint32_t a = s, b = cn - 1;
-                            if (a < b && s_lpos[a + 1] <= p) {
-                                a++;
-                                if (a < b && s_lpos[a + 1] <= p)
-                                    a++;
-                                else
-                                    b = a;
-                            } else {
-                                b = a;
-                            }
-                            while (a < b) {
-                                const uint32_t mid = (a + b) >> 1;
-                                if (s_lpos[mid + 1] > p)
-                                    b = mid;
-                                else
-                                    a = mid + 1;
-                            }
-                            s = a;
-                        }
-                        const Seg sg = s_seg[s];
-                        seg_lo = s_lpos[s];
-                        seg_hi = seg_lo + sg.len;
-                        seg_start = sg.start;
-                        seg_vpos = sg.vpos;
-                        seg_ct = sg.cterm;
-                    }
-                    const uint32_t off = p - seg_lo;
-                    const uint32_t gi = seg_start + off;
+                    c.seek<Seek>(p, s_lpos, s_seg, cn);
+                    const uint32_t off = p - c.seg_lo;
+                    const uint32_t gi = c.seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
-                    nb[u] = norm_codes[gi];
-                    if constexpr (FILT) {
-                        fw[u] = fmask[gi >> 5];
+                    load_norm_filter<FILT>(norm_codes, fmask, gi, nb[u], fw[u]);
+                    if constexpr (FILT)
                         fb[u] = gi & 31u;
-                    }
-                    vp[u] = seg_vpos + off;
-                    ct[u] = seg_ct;
+                    vp[u] = c.seg_vpos + off;
+                    ct[u] = c.seg_ct;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if constexpr (FILT)
-                    ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
+                    ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
                 if (ok[u]) {
-                    float sum;
-                    if constexpr (CS > 0)
-                        sum = adc_sum_lds<CS>(s_lut, w[u].w);
-                    else
-                        sum = w[u].sum;
-                    const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
-                    const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                    const float sum = code_sum_lds<CS>(s_lut, w[u]);
+                    const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
                     if (dist < FLT_MAX) { // also rejects NaN, as 'dist < distances[0]' does
-                        const unsigned long long key =
-                            ((unsigned long long)f32_orderable(__fadd_rn(dist, 0.0f)) << 32) | vp[u];
+                        const unsigned long long key = adc_key(dist, vp[u]);
                         best = key < best ? key : best;
                     }
                 }
@@ -567,14 +470,8 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
 // segment (round 1's scan_k1_short_kernel, tools/experiments/) leaves half the lanes idle -- and the scan is bound by
 // LDS instruction issue, so idle lanes cost as much as busy ones.  Here positions are dealt to lanes one code each
 // AND the segment comes from a bitmap: one bit per position of the plan chunk, set where a segment starts, plus the
-// number of starts before every 64-position word.  A wavefront's 64 positions share a word, so
-//     segment = pref[word] + popcount(mask[word] & lanes_up_to_mine) - 1
-// is one broadcast LDS read and two v_mbcnt.  Chunks of <= 256 segments and <= 8192 positions: 23 KB of LDS per
-// workgroup, six workgroups per CU.
-constexpr int BM_SEGCAP = 256;
-constexpr int BM_SPANCAP = 8192;
-constexpr int BM_SPANW = BM_SPANCAP / 64;
-
+// number of starts before every 64-position word (scan_steps.h BitmapChunk).  Chunks of <= 256 segments and <= 8192
+// positions: 23 KB of LDS per workgroup, six workgroups per CU.
 template <int CS, int U, class... Mask> // Mask: see scan_k1_kernel
 __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__restrict__ codes,
                                                              const uint8_t *__restrict__ norm_codes,
@@ -590,10 +487,10 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
     [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
     __shared__ __attribute__((aligned(16))) float s_lut[CS * 256];
     __shared__ float s_norm[256];
-    __shared__ __attribute__((aligned(16))) Seg s_seg[BM_SEGCAP];
-    __shared__ uint32_t s_lpos[BM_SEGCAP + 1];
-    __shared__ unsigned long long s_mask[BM_SPANW];
-    __shared__ uint32_t s_pref[BM_SPANW];
+    __shared__ __attribute__((aligned(16))) Seg s_seg[kBmSegCap];
+    __shared__ uint32_t s_lpos[kBmSegCap + 1];
+    __shared__ unsigned long long s_mask[kBmSpanWords];
+    __shared__ uint32_t s_pref[kBmSpanWords];
     __shared__ uint32_t s_wtot[4];
     __shared__ unsigned long long s_red[4];
 
@@ -606,86 +503,22 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
             sel_write(so, q, kKeyInit, nullptr, 0);
         return;
     }
-    uint32_t per = (h.total + nsplit - 1) / nsplit;
-    per = (per + 255u) & ~255u;
-    const uint32_t lo = min((uint32_t)split * per, h.total);
-    const uint32_t hi = min(lo + per, h.total);
+    const auto [lo, hi] = scan_slice(h.total, nsplit, split, 256);
     if (lo >= hi)
         return;
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(luts + (size_t)q * CS * 256);
-        for (int i = tid; i < CS * 64; i += 256) // global -> LDS directly (see scan_k1_kernel)
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(src + i),
-                (__attribute__((address_space(3))) void *)(reinterpret_cast<float4 *>(s_lut) + (i - lane)), 16, 0, 0);
-        s_norm[tid] = norm_table[tid];
-    }
+    stage_table_dma<256>(luts, q, CS, s_lut, tid);
+    s_norm[tid] = norm_table[tid];
     const Seg *sq = segs + (size_t)q * max_seg;
     const uint32_t *lq = lpos + (size_t)q * max_seg;
     unsigned long long best = kKeyInit;
 
-    // first segment of this split: the last one starting at or before lo
-    uint32_t cs = 0;
-    if (lo > 0) {
-        uint32_t a = 0, b = h.nseg - 1;
-        while (a < b) {
-            const uint32_t mid = (a + b + 1) >> 1;
-            if (lq[mid] <= lo)
-                a = mid;
-            else
-                b = mid - 1;
-        }
-        cs = a;
-    }
+    uint32_t cs = first_segment(lq, h.nseg, lo);
     while (cs < h.nseg) {
         const uint32_t cl = lq[cs];
         if (cl >= hi)
             break;
-        // as many segments as fit the plan buffer AND the bitmap's span; one oversized segment goes alone
-        uint32_t cn = min((uint32_t)BM_SEGCAP, h.nseg - cs);
-        {
-            const uint32_t end_all = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-            if (end_all - cl > (uint32_t)BM_SPANCAP) {
-                uint32_t a = 1, b = cn > 1 ? cn - 1 : 1; // largest count whose end stays inside the span (or 1)
-                while (a < b) {
-                    const uint32_t mid = (a + b + 1) >> 1;
-                    if (lq[cs + mid] - cl <= (uint32_t)BM_SPANCAP)
-                        a = mid;
-                    else
-                        b = mid - 1;
-                }
-                cn = a;
-            }
-        }
-        const uint32_t ch = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-        const bool single = ch - cl > (uint32_t)BM_SPANCAP; // cn == 1: every position belongs to segment 0
-        const uint32_t nwords = single ? 0u : (ch - cl + 63) >> 6;
-        __syncthreads(); // previous chunk fully consumed (and the table staged, first time)
-        for (uint32_t i = tid; i < cn; i += 256) {
-            s_seg[i] = sq[cs + i];
-            s_lpos[i] = lq[cs + i];
-        }
-        if (tid < (int)nwords)
-            s_mask[tid] = 0ull;
-        __syncthreads();
-        if (!single) {
-            uint32_t *m32 = reinterpret_cast<uint32_t *>(s_mask);
-            for (uint32_t i = tid; i < cn; i += 256) {
-                const uint32_t r = s_lpos[i] - cl;
-                atomicOr(&m32[r >> 5], 1u << (r & 31));
-            }
-            __syncthreads();
-            // starts before every word (at most 128 words: waves 0 and 1 scan, two totals)
-            const uint32_t cnt = tid < (int)nwords ? (uint32_t)__popcll(s_mask[tid]) : 0u;
-            const uint32_t inc = wave_incl_scan(cnt, lane);
-            if (lane == 63)
-                s_wtot[wave] = inc;
-            __syncthreads();
-            if (tid < (int)nwords)
-                s_pref[tid] = (wave ? s_wtot[0] : 0u) + inc - cnt;
-            __syncthreads();
-        }
-        const uint32_t b0 = max(cl, lo), b1 = min(ch, hi);
+        const BitmapChunk bc = stage_bitmap_chunk<256>(sq, lq, cs, h.nseg, h.total, s_seg, s_lpos, s_mask, s_pref, s_wtot, tid);
+        const uint32_t b0 = max(cl, lo), b1 = min(bc.ch, hi);
         if (b0 < b1) {
             for (uint32_t rbase = (b0 - cl) & ~63u; rbase < b1 - cl; rbase += 256 * U) {
                 CodeRegs<CS> w[U];
@@ -698,25 +531,17 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                     const uint32_t r = rbase + u * 256 + tid;
                     const uint32_t p = cl + r;
                     ok[u] = p >= b0 && p < b1;
-                    const uint32_t wi = __builtin_amdgcn_readfirstlane(r >> 6);
+                    const uint32_t wi = BitmapChunk::word_of(r);
                     if (wi * 64u < b1 - cl) { // wave-uniform
-                        uint32_t sgi = 0;
-                        if (!single) {
-                            const unsigned long long mw = s_mask[wi];
-                            const uint32_t below =
-                                __builtin_amdgcn_mbcnt_hi((uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
-                            sgi = s_pref[wi] + below + (uint32_t)((mw >> lane) & 1ull) - 1u;
-                        }
+                        const uint32_t sgi = bc.segment_of(wi, lane);
                         if (ok[u]) {
                             const Seg sg = s_seg[sgi];
                             const uint32_t off = p - s_lpos[sgi];
                             const uint32_t gi = sg.start + off;
                             code_fetch<CS>(codes, gi, CS, s_lut, w[u]);
-                            nb[u] = norm_codes[gi];
-                            if constexpr (FILT) {
-                                fw[u] = fmask[gi >> 5];
+                            load_norm_filter<FILT>(norm_codes, fmask, gi, nb[u], fw[u]);
+                            if constexpr (FILT)
                                 fb[u] = gi & 31u;
-                            }
                             vp[u] = sg.vpos + off;
                             ct[u] = sg.cterm;
                         }
@@ -725,21 +550,19 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     if constexpr (FILT)
-                        ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
+                        ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
                     if (ok[u]) {
                         const float sum = code_sum<CS>(s_lut, w[u]);
-                        const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
-                        const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                        const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
                         if (dist < FLT_MAX) {
-                            const unsigned long long key =
-                                ((unsigned long long)f32_orderable(__fadd_rn(dist, 0.0f)) << 32) | vp[u];
+                            const unsigned long long key = adc_key(dist, vp[u]);
                             best = key < best ? key : best;
                         }
                     }
                 }
             }
         }
-        cs += cn;
+        cs += bc.cn;
     }
     best = wave_min_u64(best);
     if (lane == 0)

@@ -11,35 +11,13 @@
 //
 // keys_inv[q] holds the bitwise complement of the best key (atomicMax; 0 = nothing yet, so a plain memset initialises
 // it), done[q] counts finished workgroups of query q.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 
 namespace ivfhnsw_gpu_impl {
 
 namespace {
-
-__device__ __forceinline__ unsigned long long tail_wave_min(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long tail_wave_scan(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += o;
-    }
-    return v;
-}
 
 template <int CS, int DSUB, int U>
 __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float *__restrict__ xq,
@@ -76,14 +54,14 @@ __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float 
         unsigned long long n = 0;
         if (ok)
             n = t.goff[c + 1] - t.goff[c];
-        const unsigned long long incl = tail_wave_scan(n, lane);
+        const unsigned long long incl = wave_incl_scan_u64(n, lane);
         const unsigned long long excl = incl - n;
         // the check follows the scoring (IndexIVF_HNSW.cpp:290-292): the first non-empty list is always scored
         const bool take = n != 0 && (excl < max_codes || excl == 0);
         const uint32_t lo_c = take ? t.loff[c] : kNotOwned;
         const bool owned = lo_c != kNotOwned;
         const unsigned long long om = __ballot(owned);
-        const unsigned long long own_incl = tail_wave_scan(owned ? n : 0ull, lane);
+        const unsigned long long own_incl = wave_incl_scan_u64(owned ? n : 0ull, lane);
         if (owned) {
             const uint32_t r = (uint32_t)__popcll(om & ((1ull << lane) - 1ull));
             Seg sg;
@@ -112,10 +90,7 @@ __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float 
     const uint32_t total = s_lpos[nseg];
 
     unsigned long long best = kKeyInit;
-    uint32_t per = (total + nsplit - 1) / nsplit;
-    per = (per + 255u) & ~255u;
-    const uint32_t lo = min((uint32_t)split * per, total);
-    const uint32_t hi = min(lo + per, total);
+    const auto [lo, hi] = scan_slice(total, nsplit, split, 256);
     if (lo < hi) { // block-uniform
         // ---- table: thread c builds tab[m][c] for every m (lut_kernel's arithmetic; the code book comes from L2)
         {
@@ -141,9 +116,8 @@ __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float 
             }
         }
         __syncthreads();
-        // ---- scan of [lo, hi) (scan_k1_kernel's loop, one plan chunk)
-        uint32_t s = 0, seg_lo = 0, seg_hi = 0, seg_start = 0, seg_vpos = 0;
-        float seg_ct = 0.f;
+        // ---- scan of [lo, hi): one plan chunk, walked as scan_k1_kernel walks it (scan_steps.h)
+        SegCursor c;
         for (uint32_t base = lo; base < hi; base += 256 * U) {
             uint32_t w[U][CS / 4];
             uint32_t nb[U], vp[U];
@@ -154,40 +128,29 @@ __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float 
                 const uint32_t p = base + u * 256 + tid;
                 ok[u] = p < hi;
                 if (ok[u]) {
-                    if (p >= seg_hi) {
-                        while (p >= s_lpos[s + 1])
-                            s++;
-                        const Seg sg = s_seg[s];
-                        seg_lo = s_lpos[s];
-                        seg_hi = seg_lo + sg.len;
-                        seg_start = sg.start;
-                        seg_vpos = sg.vpos;
-                        seg_ct = sg.cterm;
-                    }
-                    const uint32_t off = p - seg_lo;
-                    const uint32_t gi = seg_start + off;
+                    c.seek<SeekLinear>(p, s_lpos, s_seg, nseg);
+                    const uint32_t off = p - c.seg_lo;
+                    const uint32_t gi = c.seg_start + off;
                     load_code_words<CS>(t.codes, gi, w[u]);
                     nb[u] = t.norm_codes[gi];
-                    vp[u] = seg_vpos + off;
-                    ct[u] = seg_ct;
+                    vp[u] = c.seg_vpos + off;
+                    ct[u] = c.seg_ct;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if (ok[u]) {
                     const float sum = adc_sum<CS>(s_lut, w[u]);
-                    const float tt = __fadd_rn(ct[u], s_norm[nb[u]]);
-                    const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                    const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
                     if (dist < FLT_MAX) {
-                        const unsigned long long key =
-                            ((unsigned long long)f32_orderable(__fadd_rn(dist, 0.0f)) << 32) | vp[u];
+                        const unsigned long long key = adc_key(dist, vp[u]);
                         best = key < best ? key : best;
                     }
                 }
             }
         }
     }
-    best = tail_wave_min(best);
+    best = wave_min_u64(best);
     if (lane == 0)
         s_red[wave] = best;
     __syncthreads();

@@ -1,4 +1,4 @@
-// ADC list scan for k > 1: same arithmetic as scan_k1_kernel (kernels_search.hip), but the k smallest
+// ADC list scan for k > 1: scan_k1_kernel's steps (kernels_search.hip, scan_steps.h), but the k smallest
 // (distance, scan position) keys are kept per query.
 //
 // faiss's max-heap admits a code iff dist < current k-th best (IndexIVF_HNSW.cpp:285-288); the final
@@ -10,8 +10,7 @@
 // One 256-thread workgroup per query.  Threads push keys below the running threshold T into an LDS
 // buffer; when it fills, the buffer and the current top are bitonic-sorted together and T tightens, so
 // after the first few hundred codes almost nothing passes the filter.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "scan_steps.h"
 
 #include <float.h>
 
@@ -126,19 +125,12 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
 
     for (uint32_t cs = 0; cs < h.nseg; cs += TK_SEGCAP) {
         const uint32_t cn = min((uint32_t)TK_SEGCAP, h.nseg - cs);
+        const uint32_t ch = plan_chunk_end(lq, cs, cn, h.nseg, h.total);
         __syncthreads();
-        for (uint32_t i = tid; i < cn; i += 256) {
-            s_seg[i] = sq[cs + i];
-            s_lpos[i] = lq[cs + i];
-        }
-        const uint32_t ch = (cs + cn == h.nseg) ? h.total : lq[cs + cn];
-        if (tid == 0)
-            s_lpos[cn] = ch;
+        stage_plan_chunk<256>(sq, lq, cs, cn, ch, s_seg, s_lpos, tid);
         __syncthreads();
         const uint32_t cl = s_lpos[0];
-        // the segment this lane is inside, kept in registers (positions only grow)
-        uint32_t s = 0, seg_lo = 0, seg_hi = 0, seg_start = 0, seg_vpos = 0;
-        float seg_ct = 0.f;
+        SegCursor c;
         for (uint32_t base = cl; base < ch; iter++) {
             // no threshold yet (every code passes): take a quarter iteration and sort 512 entries instead of 2048
             if ((ncand && T == kKeyInit) || ncand + k + 256 * TK_U > TK_N)
@@ -156,33 +148,15 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                 const uint32_t p = base + u * 256 + tid;
                 ok[u] = u < u_now && p < ch;
                 if (ok[u]) {
-                    if (p >= seg_hi) {
-                        uint32_t a = s, b = cn - 1;
-                        while (a < b) {
-                            const uint32_t mid = (a + b) >> 1;
-                            if (s_lpos[mid + 1] > p)
-                                b = mid;
-                            else
-                                a = mid + 1;
-                        }
-                        s = a;
-                        const Seg sg = s_seg[s];
-                        seg_lo = s_lpos[s];
-                        seg_hi = seg_lo + sg.len;
-                        seg_start = sg.start;
-                        seg_vpos = sg.vpos;
-                        seg_ct = sg.cterm;
-                    }
-                    const uint32_t off = p - seg_lo;
-                    const uint32_t gi = seg_start + off;
+                    c.seek<SeekHalves>(p, s_lpos, s_seg, cn);
+                    const uint32_t off = p - c.seg_lo;
+                    const uint32_t gi = c.seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
-                    nbv[u] = norm_codes[gi];
-                    if constexpr (FILT) {
-                        fw[u] = fmask[gi >> 5];
+                    load_norm_filter<FILT>(norm_codes, fmask, gi, nbv[u], fw[u]);
+                    if constexpr (FILT)
                         fb[u] = gi & 31u;
-                    }
-                    vp[u] = seg_vpos + off;
-                    ct[u] = seg_ct;
+                    vp[u] = c.seg_vpos + off;
+                    ct[u] = c.seg_ct;
                 }
             }
 #pragma unroll
@@ -190,13 +164,12 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                 pass[u] = false;
                 key[u] = 0;
                 if constexpr (FILT)
-                    ok[u] = ok[u] && ((fw[u] >> fb[u]) & 1u);
+                    ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
                 if (ok[u]) {
                     const float sum = code_sum<CS>(s_lut, w[u]);
-                    const float tt = __fadd_rn(ct[u], s_norm[nbv[u]]);
-                    const float dist = __fsub_rn(tt, __fmul_rn(2.0f, sum));
+                    const float dist = adc_distance(ct[u], s_norm[nbv[u]], sum);
                     if (dist < FLT_MAX) {
-                        key[u] = ((unsigned long long)f32_orderable(__fadd_rn(dist, 0.0f)) << 32) | vp[u];
+                        key[u] = adc_key(dist, vp[u]);
                         pass[u] = key[u] < T;
                     }
                 }
