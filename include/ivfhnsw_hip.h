@@ -298,7 +298,11 @@ int ivfhnsw_gpu_last_batch_parts(ivfhnsw_gpu *h, uint64_t *first, uint64_t *seco
  *                LDS and cannot run beside the other part's walk.
  *   "exact_splits"  -1 (default) the library chooses from (nq, n); 1..64: exact_search cuts the store's rows into that many
  *                column splits whose partial tables are merged.  The results are the same for every value; the key exists so
- *                that the split and merge path can be exercised on a small store.  Other values: IVFHNSW_ERR_INVALID. */
+ *                that the split and merge path can be exercised on a small store.  Other values: IVFHNSW_ERR_INVALID.
+ *                exact_range_search cuts the store the same way (its slices of a query follow each other in label order).
+ *   "exact_range_map"  -1 (default) or 1: exact_range_search's first pass leaves a map of the tiles in which anything
+ *                passed and its second pass visits only those; 0: the second pass sweeps the whole store again.  The
+ *                results are the same; the key exists so that both can be measured and compared. */
 int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value);
 
 /* The search-time knobs the drivers set as public members (IndexIVF_HNSW.h:61-62, hnswalg.h:69,
@@ -556,6 +560,48 @@ int ivfhnsw_gpu_exact_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, 
                              float *distances, int64_t *labels);
 int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
                                  float *d_distances, int64_t *d_labels);
+
+/* ---- exact range search of the base store ----------------------------------------------------------
+ *
+ * Every row of the base store (upload_base) within a radius of each of nq queries: the true answer to the question
+ * ivfhnsw_gpu_range_search answers approximately, in its layout (lims, distances, labels).  Queries as for exact_search:
+ * uint8, the store's d bytes each, row_stride >= d bytes apart (d + 4 takes a .bvecs image as it is).
+ *   Row j is returned for query q iff (float)dist(q, j) < radius, dist the integer sum (q[i] - x[i])^2 -- strict, as
+ *   range_search and faiss compare for L2.  The distance written is that integer as a float, bit for bit what exact_search
+ *   and rerank write for the pair (d <= 256: below 2^24, exact).  Every row of the store is a candidate, the zero rows of
+ *   a chunk that was never uploaded included.  The radius becomes an int32 threshold on the host, dist < thr: thr = 0 when
+ *   !(radius > 0) (0, negatives, -inf: all-zero lims without a sweep), INT_MAX when radius > 2^24 (+inf), else
+ *   (int)ceilf(radius) -- for integer dist < 2^24 exactly the float comparison.
+ *   The results of one query stand in ASCENDING LABEL.  lims [nq + 1]: lims[0] = 0, query q owns entries
+ *   [lims[q], lims[q + 1]) of distances (float) and labels (int64); *total = lims[nq].  No cap, nothing truncated or padded.
+ *   The results stay in HBM the handle owns, apart from the IVF range search's (neither call disturbs the other's), until
+ *   the handle's next exact range search or destroy: upload_base, exact_search and every index call leave them alone.  A
+ *   view searches its parent's store and holds its own results.  The buffers keep their largest size so far.
+ *   Memory (ivfhnsw_gpu_memory_bytes counts all of it): 12 bytes per result; 4 bytes per (query, column split) of the
+ *   count; nq * d bytes of queries; and the tile map the first pass leaves for the second, one bit per (32 queries, 32
+ *   rows) = nq * n / 8192 bytes, coarsened by powers of two until it is at most 1/16 of the store's n * d bytes (on a tiny
+ *   store: 4 bytes per (32 queries, column split)).
+ *   Both forms return when the results are complete, and synchronise the handle's stream ONCE between their two passes
+ *   (the host sizes the results from the count, as range_search does).  With ivfhnsw_gpu_set_profiling the count pass is
+ *   accounted as the scan stage and the fill pass as the select stage, as range_search accounts its own.
+ *   Limits: at most 131 072 queries per call; 2^32 or more results in one call -> IVFHNSW_ERR_INVALID with a message,
+ *   found after the count pass and before anything is allocated.
+ *   Errors leave earlier results as they were: no store -> IVFHNSW_ERR_STATE; a store with d > 256, a NaN radius, NULL
+ *   queries, lims or total with nq > 0, row_stride < d, more than 131 072 queries -> IVFHNSW_ERR_INVALID; a failed
+ *   allocation -> IVFHNSW_ERR_NOMEM.  nq = 0: lims[0] = 0 (when lims is given), *total = 0, success.
+ *   The options "exact_splits" and "exact_range_map" (ivfhnsw_gpu_set_option) apply; the results do not depend on them.
+ * exact_range_search: host pointers.  exact_range_search_dev: device pointers (queries of any alignment, d_lims 8-byte
+ *   aligned), *total on the host; ordered behind an upload_base_dev on the handle's stream.
+ * exact_range_results[_dev]: as range_results[_dev], for these buffers: entries [first, first + count) to host buffers
+ *   (either may be NULL; first + count beyond the total -> IVFHNSW_ERR_INVALID; count = 0 succeeds), or the device
+ *   pointers themselves (NULL when the total is 0) and the total, each output nullable.  Either before any exact range
+ *   search on the handle -> IVFHNSW_ERR_STATE. */
+int ivfhnsw_gpu_exact_range_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, float radius,
+                                   uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, float radius,
+                                       uint64_t *d_lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

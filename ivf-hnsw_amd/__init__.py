@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_locate", "ivfhnsw_gpu_locate_dev", "ivfhnsw_gpu_reconstruct_rows", "ivfhnsw_gpu_reconstruct_rows_dev",
     "ivfhnsw_gpu_reconstruct", "ivfhnsw_gpu_reconstruct_dev", "ivfhnsw_gpu_search_reconstruct",
     "ivfhnsw_gpu_search_reconstruct_dev",
+    "ivfhnsw_gpu_exact_range_search", "ivfhnsw_gpu_exact_range_search_dev", "ivfhnsw_gpu_exact_range_results",
+    "ivfhnsw_gpu_exact_range_results_dev",
 )
 
 
@@ -163,6 +165,12 @@ def lib():
         L.ivfhnsw_gpu_exact_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                C.c_void_p]
         L.ivfhnsw_gpu_exact_search_dev.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
+        L.ivfhnsw_gpu_exact_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p,
+                                                     C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_exact_range_search_dev.argtypes = L.ivfhnsw_gpu_exact_range_search.argtypes
+        L.ivfhnsw_gpu_exact_range_results.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_exact_range_results_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                          C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_set_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_set_filter_dev.argtypes = L.ivfhnsw_gpu_set_filter.argtypes
         L.ivfhnsw_gpu_clear_filter.argtypes = [C.c_void_p]
@@ -908,6 +916,46 @@ class GpuIndex:
         """The same on device buffers (torch CUDA tensors or raw addresses), asynchronous on the handle's stream."""
         _check(lib().ivfhnsw_gpu_exact_search_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_distances),
                                                   _devptr(d_labels)))
+
+    # ---- exact range search of the base store (ivfhnsw_gpu_exact_range_search, DESIGN.md 3.17) ----------------------
+    def exact_range_search(self, queries_u8, radius):
+        """Every row of the base store with float(exact integer squared L2) < radius (strict), per query in ascending
+        label: (lims u64 [nq + 1], distances f32 [total], labels i64 [total]); query q owns [lims[q], lims[q + 1]).
+        queries_u8 [nq, d] uint8 whose rows may lie a row stride apart, as exact_search takes them."""
+        a = np.asarray(queries_u8)
+        assert a.dtype == np.uint8 and a.ndim == 2, "queries_u8: a 2-D uint8 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 1 and (nq == 1 or a.strides[0] >= d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] if nq > 1 else d
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                    C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_dev(self, nq, d_queries, row_stride, radius, d_lims):
+        """The same on device buffers (d_lims: [nq + 1] 64-bit words); returns when the results are complete, with their
+        number.  They stay in the handle's memory: exact_range_results_dev() / exact_range_results()."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_dev(self._h, nq, _devptr(d_queries), row_stride, C.c_float(radius),
+                                                        _devptr(d_lims), C.byref(total)))
+        return int(total.value)
+
+    def exact_range_results(self, first, count):
+        """Entries [first, first + count) of the last exact range search's results: (distances f32, labels i64)."""
+        dist = np.empty(count, np.float32)
+        lab = np.empty(count, np.int64)
+        _check(lib().ivfhnsw_gpu_exact_range_results(self._h, first, count, _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_range_results_dev(self):
+        """(distance pointer, label pointer, total) of the last exact range search's results in the handle's memory (raw
+        device addresses, 0 when the total is 0), valid until this handle's next exact range search or close."""
+        pd, pl, total = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_results_dev(self._h, C.byref(pd), C.byref(pl), C.byref(total)))
+        return pd.value or 0, pl.value or 0, int(total.value)
 
     # ---- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on):

@@ -1,5 +1,7 @@
 #include "capi_internal.h"
 
+#include <climits>
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Exact brute-force search of the uint8 base store (kernels_exact.hip): the ground truth the drivers
 // read as -path_gt (tests/test_ivfhnsw_sift1b.cpp:173-215), computed from the store upload_base left in HBM.
@@ -69,7 +71,227 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
     return IVFHNSW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Exact range search: count -> prefix -> (one synchronisation: the host sizes the results) -> fill, both
+// passes the sweep of exact_mfma_kernel with a fixed gate (exact_range_kernel).
+
+// (float)dist < radius for an integer 0 <= dist < 2^24, as an int32 threshold: dist < thr
+int exact_range_threshold(float radius)
+{
+    if (!(radius > 0.f))
+        return 0;
+    if (radius > 16777216.f)
+        return INT_MAX;
+    return (int)ceilf(radius);
+}
+
+// what both forms check before they touch anything
+int exact_range_guard(ivfhnsw_gpu *h, size_t nq, const void *queries, size_t row_stride, float radius, const void *lims,
+                      const void *total)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    if (!b->base_n)
+        return fail(IVFHNSW_ERR_STATE, "exact_range_search before upload_base");
+    if (b->base_d > 256)
+        return fail(IVFHNSW_ERR_INVALID,
+                    "exact_range_search on a store of dimension %zu: beyond d = 256 the squared distance can exceed 2^24 and "
+                    "is no longer the exact float fvec_L2sqr returns",
+                    (size_t)b->base_d);
+    if (std::isnan(radius))
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: the radius is NaN");
+    if (nq == 0)
+        return IVFHNSW_OK;
+    if (!queries || !lims || !total)
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: null queries, lims or total");
+    if (row_stride < b->base_d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, (size_t)b->base_d);
+    if (nq > kMaxBatchAll)
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_search is limited to %zu queries per call", kMaxBatchAll);
+    return IVFHNSW_OK;
+}
+
+// The tile map's granularity: one bit per 2^shift tiles of (32 queries, 32 rows), the finest whose map stays within a
+// sixteenth of the store -- or, on a store too small for that, the one word per (32 queries, split) that is the least.
+int exact_range_map_shift(size_t nq, size_t n, size_t d, int nsplit, size_t *bytes)
+{
+    const size_t strips = (nq + 31) / 32;
+    int shift = 0;
+    for (;; shift++) {
+        const size_t words = (size_t)exact_range_map_words(n, nsplit, shift);
+        *bytes = strips * nsplit * words * sizeof(uint32_t);
+        if (*bytes <= n * d / 16 || words == 1 || shift == kExactRangeMaxShift)
+            return shift;
+    }
+}
+
+// the sweep of one form over every chunk of the call's queries (h->ex_q: all of them, permuted)
+int exact_range_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, bool fill, size_t nq, int thr, int nsplit, int map_shift, float *dist,
+                     int64_t *labels, size_t out_cap)
+{
+    const size_t d = b->base_d;
+    StageScope sc(h, fill ? IVFHNSW_STAGE_SELECT : IVFHNSW_STAGE_SCAN); // accounted as range_search accounts its passes
+    for (size_t q0 = 0; q0 < nq; q0 += kExactChunk) // (kExactChunk % 128 == 0: a chunk starts a workgroup's strip)
+        HIP_TRY(launch_exact_range(h->stream, fill, h->ex_q.as<uint8_t>() + q0 * d, b->base_rows.as<uint8_t>(),
+                                   std::min(kExactChunk, nq - q0), q0, b->base_n, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
+                                   h->xr_tot.as<unsigned long long>(), h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr,
+                                   map_shift, dist, labels, out_cap));
+    return IVFHNSW_OK;
+}
+
+// device pointers, the arguments checked (nq > 0)
+int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, float radius, uint64_t *d_lims,
+                    uint64_t *total)
+{
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    const size_t d = b->base_d, n = b->base_n;
+    const int thr = exact_range_threshold(radius);
+    int rc;
+    if (thr == 0) { // nothing is below it: no sweep
+        HIP_TRY(hipMemsetAsync(d_lims, 0, (nq + 1) * sizeof(uint64_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->xr_valid = true;
+        h->xr_total = 0;
+        *total = 0;
+        return IVFHNSW_OK;
+    }
+    const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_splits_for(std::min(nq, kExactChunk), n, 1);
+    const size_t len = nq * (size_t)nsplit + 1;
+    size_t map_bytes = 0;
+    const int map_shift = exact_range_map_shift(nq, n, d, nsplit, &map_bytes);
+    if ((rc = h->ex_q.ensure(nq * d)) || (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) ||
+        (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
+        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))))
+        return rc;
+    HIP_TRY(launch_rerank_permute(h->stream, d_queries, row_stride, h->ex_q.as<uint8_t>(), nq, (int)d));
+    HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
+    if ((rc = exact_range_pass(h, b, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0)))
+        return rc;
+    HIP_TRY(launch_scan_excl_u32(h->stream, h->xr_slices.as<uint32_t>(), len, h->xr_part.as<uint32_t>()));
+    // the one synchronisation between the passes: the host sizes the results from the count
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, h->xr_tot.p, sizeof(tot), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (tot >= (1ull << 32))
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: %llu results in one call, the limit is 2^32 - 1 (use a smaller "
+                                         "radius or fewer queries per call)", tot);
+    // results: in the buffers the handle holds when they are large enough, else in new ones swapped in when they are full
+    DevBuf nd, nl;
+    const bool grow = tot * sizeof(float) > h->xr_dist.bytes || tot * sizeof(int64_t) > h->xr_lab.bytes;
+    if (grow && ((rc = nd.ensure(tot * sizeof(float))) || (rc = nl.ensure(tot * sizeof(int64_t))))) {
+        nd.release();
+        nl.release();
+        return rc;
+    }
+    auto fill = [&]() -> int {
+        HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
+        if (tot)
+            if (int e = exact_range_pass(h, b, true, nq, thr, nsplit, map_shift, grow ? nd.as<float>() : h->xr_dist.as<float>(),
+                                         grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), (size_t)tot))
+                return e;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return IVFHNSW_OK;
+    };
+    if ((rc = fill())) {
+        nd.release();
+        nl.release();
+        return rc;
+    }
+    if (grow) {
+        std::swap(h->xr_dist, nd);
+        std::swap(h->xr_lab, nl);
+        nd.release();
+        nl.release();
+    }
+    h->xr_valid = true;
+    h->xr_total = tot;
+    *total = tot;
+    return IVFHNSW_OK;
+}
+
 } // namespace
+
+int ivfhnsw_gpu_exact_range_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, float radius,
+                                       uint64_t *d_lims, uint64_t *total)
+{
+    int rc = exact_range_guard(h, nq, d_queries, row_stride, radius, d_lims, total);
+    if (rc)
+        return rc;
+    if (nq == 0) {
+        if (d_lims) {
+            HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        if (total)
+            *total = 0;
+        h->xr_valid = true;
+        h->xr_total = 0;
+        return IVFHNSW_OK;
+    }
+    return exact_range_dev(h, nq, d_queries, row_stride, radius, d_lims, total);
+}
+
+int ivfhnsw_gpu_exact_range_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, float radius,
+                                   uint64_t *lims, uint64_t *total)
+{
+    int rc = exact_range_guard(h, nq, queries, row_stride, radius, lims, total);
+    if (rc)
+        return rc;
+    if (nq == 0) {
+        if (lims)
+            lims[0] = 0;
+        return ivfhnsw_gpu_exact_range_search_dev(h, 0, nullptr, row_stride, radius, nullptr, total);
+    }
+    const size_t d = (h->parent ? h->parent : h)->base_d;
+    if ((rc = h->ex_raw.ensure(nq * d)) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d, queries, row_stride, d, nq, hipMemcpyHostToDevice, h->stream));
+    if ((rc = exact_range_dev(h, nq, h->ex_raw.as<uint8_t>(), d, radius, h->xr_lims.as<uint64_t>(), total)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_exact_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->xr_valid)
+        return fail(IVFHNSW_ERR_STATE, "exact_range_results before an exact range search on this handle");
+    if (first > h->xr_total || count > h->xr_total - first)
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_results: [%llu, %llu + %llu) is beyond the %llu results held",
+                    (unsigned long long)first, (unsigned long long)first, (unsigned long long)count,
+                    (unsigned long long)h->xr_total);
+    if (count == 0)
+        return IVFHNSW_OK;
+    if (distances)
+        HIP_TRY(hipMemcpyAsync(distances, h->xr_dist.as<float>() + first, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (labels)
+        HIP_TRY(hipMemcpyAsync(labels, h->xr_lab.as<int64_t>() + first, count * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_exact_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!h->xr_valid)
+        return fail(IVFHNSW_ERR_STATE, "exact_range_results_dev before an exact range search on this handle");
+    if (d_distances)
+        *d_distances = h->xr_total ? h->xr_dist.as<float>() : nullptr;
+    if (d_labels)
+        *d_labels = h->xr_total ? h->xr_lab.as<int64_t>() : nullptr;
+    if (total)
+        *total = h->xr_total;
+    return IVFHNSW_OK;
+}
 
 int ivfhnsw_gpu_exact_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
                              float *distances, int64_t *labels)

@@ -139,6 +139,7 @@ using namespace ivfhnsw_gpu_impl;
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
+    X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
     X(lc_bits) X(lc_labels) X(lc_sorted) X(lc_perm) X(lc_perm2) X(lc_hist) X(lc_lo) X(lc_cnt) X(lc_rows) X(lc_counts) X(lc_scalar) /* locate: label bitmap, the sorted request, answers, staging */ \
     X(rc_rows) X(rc_y) X(rc_out) X(sr_keys) X(sr_rows) /* reconstruct: staged rows, the ROTATED chunk of an OPQ call, host-form output; search_reconstruct's keys and rows */ \
     X(s_q) X(s_cid) X(s_cd) X(s_dist) X(s_lab) X(s_keys) X(s_len) /* staging of the host-pointer entry points */
@@ -198,6 +199,7 @@ struct ivfhnsw_gpu {
     WalkScratch walk;
     int opt_scan_pipe = -1;    // ivfhnsw_gpu_set_option "scan_pipe"
     int opt_exact_splits = -1; // ... "exact_splits"
+    int opt_exact_range_map = -1; // ... "exact_range_map"
 
     // the plan the last search_dev chunk left (remember_plan, capi_search.cpp)
     int last_nq = 0, last_max_seg = 0;
@@ -208,6 +210,9 @@ struct ivfhnsw_gpu {
     // the results of the last range search (capi_range.cpp): rg_total entries of rg_dist / rg_lab
     bool rg_valid = false;
     uint64_t rg_total = 0;
+    // ... and of the last exact range search (capi_exact.cpp): xr_total entries of xr_dist / xr_lab
+    bool xr_valid = false;
+    uint64_t xr_total = 0;
 
     int profiling = 0; // 0 off, 1 every stage, 2 only the scan (an event pair costs ~7 us of stream time)
     std::vector<StageEvent> pending;

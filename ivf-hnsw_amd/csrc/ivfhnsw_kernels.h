@@ -339,6 +339,18 @@ int exact_rows_per_block(int k);
 int exact_splits_for(size_t nq, size_t nx, int k);
 hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
                                int nsplit, unsigned long long *part, float *dists, int64_t *labels);
+// exact range search (kernels_exact.hip): the same sweep with the fixed gate dist < thr (int32, thr >= 0),
+// one launch for the nq queries Qp [nq][d] (permuted) that are queries [q_off, q_off + nq) of the call, q_off % 32 == 0.
+// count (fill = false): slices[(q_off + q) * nsplit + split] = the rows of the split that pass, *total (device) += their
+// 64-bit sum; neither is zeroed here.  fill: slices holds the exclusive scan of the counts (launch_scan_excl_u32); hit r of
+// a slice goes to dist / labels [bases[slice] + r], ascending label; nothing is written at or beyond out_cap.
+// map (nullable; then every tile is visited): [ceil(total queries / 32)][nsplit][exact_range_map_words] words, one bit
+// per 2^map_shift tiles of 32 columns; the count form writes every word the fill form of the same arguments reads.
+constexpr int kExactRangeMaxShift = 20;
+int exact_range_map_words(size_t nx, int nsplit, int map_shift);
+hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
+                              int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
+                              int map_shift, float *dist, int64_t *labels, size_t out_cap);
 // appends to the inverted lists (kernels_append.hip).  count: cnt[idx[i]] += 1 (cnt may be null: check
 // only), an id >= nc raises *status.  tables: own[c] = old length + cnt[c] of the owned lists, then cnt and own ([nc + 1]
 // each, slot nc zero) become their exclusive scans nstart / lstart in place; part: append_scan_parts(nc + 1) words.

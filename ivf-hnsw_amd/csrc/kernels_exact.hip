@@ -23,6 +23,9 @@
 // distances the lower label wins by the strict '<' alone.  The common tile (no candidate in any of the wave's 32 x 32
 // distances) costs two vector instructions per accumulator register: 2 acc - |x'|^2 > |q'|^2 - threshold.
 // LDS bounds the strip: 4 waves (128 rows) up to k = 32, 2 waves (64 rows) of 136 keys per row up to k = 100.
+//
+// The exact range search (ivfhnsw_gpu_exact_range_search) is the same sweep with a fixed gate and no
+// selection: exact_range_kernel, below the k-search.
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 
@@ -265,7 +268,215 @@ hipError_t launch_exact_t(hipStream_t s, const uint8_t *Qp, const uint8_t *X, in
     return hipGetLastError();
 }
 
+// Exact range search (ivfhnsw_gpu_exact_range_search): the sweep above with a fixed gate, dist < thr, in
+// two forms.  Nothing is selected, so there is no LDS at all: a lane keeps the counters of its 16 accumulator rows in
+// registers (the 32 lanes of a half hold the same values, a half's ballot is uniform across it), and the strip is always
+// 4 waves.  Rows beyond nq get a gate nothing passes.
+//   count (FILL = false): cnt[r] += popcount of the row's half of the ballot; at the end of the split
+//       slices[(q_off + row) * nsplit + split] = cnt -- query major, split minor, so that the exclusive prefix over the
+//       array puts a query's results in ascending label -- and *total += the wave's sum (64 bit).
+//   fill (FILL = true): cnt[r] starts at the prefix of the row's slice and is the row's cursor; a passing lane writes
+//       (dist, col) at cnt[r] + popcount of the lower passing lanes of its half.  Columns of a tile are lane & 31: ballot
+//       order is label order.
+// The tile map (map != null): the count form records per wave ONE BIT per 2^map_shift tiles of its split -- did any lane
+// pass in them -- 32 bits to a word, stored by one lane when the word is complete; map[((q_off + r0) / 32 * nsplit + split)
+// * map_words + word].  The fill form visits only tiles whose bit is set, still in order, so the cursors stay right; a
+// tile it skips is neither loaded nor multiplied.  Every word the fill form reads the count form wrote (the same tiles).
+template <int NS, bool FILL>
+__global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restrict__ Qp, const uint8_t *__restrict__ X, int nq,
+                                                          size_t nx, int d, int thr, size_t cols_per_split, size_t q_off,
+                                                          uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
+                                                          uint32_t *__restrict__ map, int map_shift, int map_words,
+                                                          float *__restrict__ out_d, long long *__restrict__ out_l,
+                                                          size_t out_cap)
+{
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const int r0 = blockIdx.x * 128 + wave * 32;
+    if (r0 >= nq)
+        return; // no barrier anywhere below
+    const int nsplit = gridDim.y, split = blockIdx.y;
+    const size_t c_begin = (size_t)split * cols_per_split < nx ? (size_t)split * cols_per_split : nx;
+    const size_t c_end = c_begin + cols_per_split < nx ? c_begin + cols_per_split : nx;
+    const uint32_t ntiles = (uint32_t)((c_end - c_begin + 31) >> 5);
+
+    const bool tail_in = 32 * (NS - 1) + 16 * kk < d;
+    auto load_row = [&](const uint8_t *row, i32x4 (&w)[NS]) {
+#pragma unroll
+        for (int s = 0; s < NS; s++)
+            w[s] = *reinterpret_cast<const i32x4 *>(row + (s < NS - 1 || tail_in ? 32 * s + 16 * kk : 0));
+    };
+    auto to_i8 = [&](const i32x4 (&raw)[NS], i32x4 (&w)[NS]) {
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const i32x4 zero = {0, 0, 0, 0};
+            w[s] = s < NS - 1 || tail_in ? raw[s] ^ (int)0x80808080 : zero;
+        }
+    };
+
+    i32x4 a[NS], cur[NS], nxt[NS];
+    load_row(Qp + (size_t)min(r0 + m, nq - 1) * d, nxt);
+    to_i8(nxt, a);
+    int qn = 0;
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+        qn = exact_sq4(a[s], qn);
+    qn += __shfl_xor(qn, 32);
+    // dist < thr  <=>  2 dot - |x'|^2 > |q'|^2 - thr = gate, set once (|q'|^2 <= 2^22: no overflow for any thr >= 0)
+    int qn_r[16], gate[16];
+    uint32_t cnt[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
+        qn_r[r] = __shfl(qn, row);
+        gate[r] = r0 + row < nq ? qn_r[r] - thr : INT_MAX;
+        cnt[r] = FILL && r0 + row < nq ? slices[(q_off + r0 + row) * nsplit + split] : 0u;
+    }
+
+    uint32_t *mw = map ? map + ((((q_off + r0) >> 5) * nsplit + split) * (size_t)map_words) : nullptr;
+    // the first tile at or after t that is to be visited (ntiles: none)
+    auto next_tile = [&](uint32_t t) -> uint32_t {
+        if (!FILL || !mw)
+            return t < ntiles ? t : ntiles;
+        while (t < ntiles) {
+            const uint32_t g = t >> map_shift;
+            const uint32_t w = __builtin_amdgcn_readfirstlane(mw[g >> 5]) >> (g & 31);
+            if (w & 1u)
+                return t;
+            t = (w ? g + (uint32_t)__ffs((int)w) - 1u : (g | 31u) + 1u) << map_shift; // the next set bit, or the next word
+        }
+        return ntiles;
+    };
+    // a column at or beyond c_end is not read (the lane reads the split's first row and drops it)
+    auto fetch = [&](uint32_t t) {
+        const size_t c = c_begin + ((size_t)t << 5) + m;
+        load_row(X + (c < c_end ? c : c_begin) * (size_t)d, nxt);
+    };
+    uint32_t t = next_tile(0), bits = 0;
+    if (t < ntiles)
+        fetch(t);
+    while (t < ntiles) {
+        const size_t col = c_begin + ((size_t)t << 5) + m;
+        const bool col_ok = col < c_end;
+        to_i8(nxt, cur);
+        const uint32_t tn = next_tile(t + 1);
+        if (tn < ntiles)
+            fetch(tn); // in flight behind this tile's MFMAs
+        i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        int xn = 0;
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], cur[s], acc, 0, 0, 0);
+            xn = exact_sq4(cur[s], xn);
+        }
+        xn += __shfl_xor(xn, 32);
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            any |= (acc[r] << 1) - xn > gate[r];
+        const bool hit = __ballot(any && col_ok) != 0; // wave-uniform
+        if (hit) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const bool pass = col_ok && (acc[r] << 1) - xn > gate[r];
+                const unsigned long long mask = __ballot(pass);
+                const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
+                if (FILL) {
+                    const size_t o = (size_t)cnt[r] + __popc(half & ((1u << m) - 1u));
+                    if (pass && o < out_cap) { // (o < out_cap always: the count form counted this very lane)
+                        out_d[o] = (float)(qn_r[r] + xn - 2 * acc[r]);
+                        out_l[o] = (long long)col;
+                    }
+                }
+                cnt[r] += __popc(half);
+            }
+        }
+        if (!FILL && mw) {
+            const uint32_t g = t >> map_shift;
+            bits |= hit ? 1u << (g & 31) : 0u;
+            if (tn >= ntiles || (tn >> map_shift) >> 5 != g >> 5) { // the word is complete
+                if (lane == 0)
+                    mw[g >> 5] = bits;
+                bits = 0;
+            }
+        }
+        t = tn;
+    }
+    if (!FILL) {
+        unsigned long long sum = 0;
+        if (m == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
+                if (r0 + row < nq)
+                    slices[(q_off + r0 + row) * nsplit + split] = cnt[r];
+                sum += cnt[r];
+            }
+        }
+        sum += __shfl_xor(sum, 32);
+        if (lane == 0 && sum)
+            atomicAdd(total, sum);
+    }
+}
+
+template <int NS>
+hipError_t launch_exact_range_t(hipStream_t s, bool fill, dim3 grid, const uint8_t *Qp, const uint8_t *X, int nq, size_t nx, int d,
+                                int thr, size_t cps, size_t q_off, uint32_t *slices, unsigned long long *total, uint32_t *map,
+                                int map_shift, int map_words, float *out_d, long long *out_l, size_t out_cap)
+{
+    if (fill)
+        hipLaunchKernelGGL((exact_range_kernel<NS, true>), grid, dim3(256), 0, s, Qp, X, nq, nx, d, thr, cps, q_off, slices, total,
+                           map, map_shift, map_words, out_d, out_l, out_cap);
+    else
+        hipLaunchKernelGGL((exact_range_kernel<NS, false>), grid, dim3(256), 0, s, Qp, X, nq, nx, d, thr, cps, q_off, slices, total,
+                           map, map_shift, map_words, out_d, out_l, out_cap);
+    return hipGetLastError();
+}
+
 } // namespace
+
+static size_t exact_range_cols_per_split(size_t nx, int nsplit)
+{
+    size_t cps = (nx + nsplit - 1) / nsplit;
+    cps = (cps + 31) & ~(size_t)31;
+    return cps ? cps : 32;
+}
+
+int exact_range_map_words(size_t nx, int nsplit, int map_shift)
+{
+    const size_t tiles = exact_range_cols_per_split(nx, nsplit) / 32;
+    const size_t bits = (tiles + ((size_t)1 << map_shift) - 1) >> map_shift;
+    return (int)((bits + 31) / 32);
+}
+
+hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
+                              int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
+                              int map_shift, float *dist, int64_t *labels, size_t out_cap)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || thr < 0 || nq > 0x7fffffffull || nx >= 0xffffffffull || nsplit < 1 || nsplit > 64 ||
+        (q_off & 31) || map_shift < 0 || map_shift > kExactRangeMaxShift)
+        return hipErrorInvalidValue;
+    const size_t cps = exact_range_cols_per_split(nx, nsplit);
+    const int words = exact_range_map_words(nx, nsplit, map_shift);
+    // query tile is the fast index, column split the slow one, as in launch_exact_t
+    const dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nsplit);
+    long long *lab = reinterpret_cast<long long *>(labels);
+#define IVFHNSW_EXACT_RANGE(NS) \
+    launch_exact_range_t<NS>(s, fill, grid, Qp, X, (int)nq, nx, d, thr, cps, q_off, slices, total, map, map_shift, words, dist, lab, out_cap)
+    switch ((d + 31) / 32) {
+    case 1: return IVFHNSW_EXACT_RANGE(1);
+    case 2: return IVFHNSW_EXACT_RANGE(2);
+    case 3: return IVFHNSW_EXACT_RANGE(3);
+    case 4: return IVFHNSW_EXACT_RANGE(4);
+    case 5: return IVFHNSW_EXACT_RANGE(5);
+    case 6: return IVFHNSW_EXACT_RANGE(6);
+    case 7: return IVFHNSW_EXACT_RANGE(7);
+    default: return IVFHNSW_EXACT_RANGE(8);
+    }
+#undef IVFHNSW_EXACT_RANGE
+}
 
 int exact_rows_per_block(int k) { return k <= 32 ? 128 : 64; }
 

@@ -6,11 +6,17 @@
      integers too, and both break ties to the lower id).
   2. The 10^9 x 128 store, filled on the device in ~1 GB torch chunks through upload_base_dev (the rows never exist on the
      host): 10 000 queries at k = 1 and k = 100.
+  3. On both stores the exact RANGE search (ivfhnsw_gpu_exact_range_search_dev) beside exact_search at
+     k = 1 -- one sweep of the unchanged kernel, the yardstick: radius 0 (the call itself), the median k = 10 and k = 100
+     distances of the exact_search above (about 10 and 100 rows per query), the radius one such step further (about
+     1 000), and on the small store the median distance with --dense-nq queries (the total stays below 2^32).  Every
+     radius with the tile map and without it ("exact_range_map" 1 / 0): seconds of the whole call, of the count pass
+     and of the fill pass (HIP events, set_profiling), results, and the ratios to the k = 1 sweep.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
-                                   [--no-big] [--no-small] [--out result.json]"""
+                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--dense-nq 512] [--out result.json]"""
 import argparse
 import json
 import os
@@ -79,6 +85,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-big", action="store_true")
     ap.add_argument("--no-small", action="store_true")
+    ap.add_argument("--no-knn", action="store_true", help="skip the float knn comparison on the small store")
+    ap.add_argument("--no-range", action="store_true", help="skip the exact range search legs")
+    ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
     import torch
@@ -101,33 +110,82 @@ def main():
         r = figures("exact_search_dev", n, d, nq, k, t, ts, 128 if k <= 32 else 64)  # kernels_exact.hip's strips
         result["rows"].append(r)
         print(json.dumps(r), flush=True)
-        return r, ol
+        return r, ol, od
+
+    lims = torch.empty((nq + 1,), dtype=torch.int64, device=dev)
+
+    def range_legs(n, name, k1_seconds, d10, d100, dense_radius=None):
+        """The exact range search at each radius, with and without the tile map, against the k = 1 sweep."""
+        r10, r100 = float(d10.median()), float(d100.median())
+        legs = [("0", 0.0, nq), ("k=10 distance", r10, nq), ("k=100 distance", r100, nq),
+                ("one step beyond", 2 * r100 - r10, nq)]
+        if dense_radius is not None:
+            legs.append(("median distance", dense_radius, min(nq, args.dense_nq)))
+        g.set_profiling(True)
+        for what, radius, m in legs:
+            for use_map in (1, 0):
+                g.set_option("exact_range_map", use_map)
+                total = [0]
+
+                def call():
+                    total[0] = g.exact_range_search_dev(m, q, d, radius, lims)
+                for _ in range(args.warmup):
+                    call()
+                g.reset_stage_ms()
+                t, ts = timed(torch, dev, call, 0, args.reps, "%s range '%s' map=%d" % (name, what, use_map))
+                st = g.stage_ms()
+                r = {"what": "exact_range_search_dev", "rows": n, "d": d, "nq": m, "radius": what, "radius_value": radius,
+                     "tile_map": bool(use_map), "results": total[0], "results_per_query": round(total[0] / m, 2),
+                     "seconds": round(t, 5), "reps": [round(x, 5) for x in ts],
+                     "count_pass_s": round(st["scan"][0] / 1e3 / max(1, args.reps), 5),
+                     "fill_pass_s": round(st["select"][0] / 1e3 / max(1, args.reps), 5),
+                     "k1_sweep_s": round(k1_seconds * m / nq, 5)}
+                for key in ("seconds", "count_pass_s", "fill_pass_s"):
+                    r[key.replace("_s", "").replace("seconds", "total") + "_over_k1"] = round(r[key] / r["k1_sweep_s"], 3)
+                result["rows"].append(r)
+                print(json.dumps(r), flush=True)
+                if radius == 0.0:
+                    break  # no sweep, no map
+        g.set_profiling(False)
+        g.set_option("exact_range_map", -1)
+
+    def yardstick_and_range(n, dense_radius=None):
+        name = "%d rows" % n
+        r1, _, _ = exact(n, 1, name)
+        _, _, od100 = exact(n, 100, name)
+        if not args.no_range:
+            range_legs(n, name, r1["seconds"], od100[:, 9], od100[:, 99], dense_radius)
 
     if not args.no_small:
         n = args.small_rows
         rows = fill_store(g, torch, dev, n, d, 99, keep=True)
-        xf = rows.to(torch.float32)
+        # the median distance of the store, from a sample: the dense radius
+        sample = (q[:32].to(torch.float32)[:, None, :] - rows[:20_000].to(torch.float32)[None, :, :]).square_().sum(-1)
+        dense_radius = float(sample.median())
+        del sample
+        if not args.no_knn:
+            xf = rows.to(torch.float32)
+            qf = q.to(torch.float32)
+            for k in (1, 10):
+                r, ol, _ = exact(n, k, "%d rows" % n)
+                ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+                dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                t, ts = timed(torch, dev, lambda: g.knn_dev(nq, n, d, qf, xf, k, ids, dist), args.warmup, args.reps,
+                              "%d rows knn k=%d" % (n, k))
+                rk = figures("knn_dev (f32 MFMA)", n, d, nq, k, t, ts)
+                rk["labels_equal"] = bool(torch.equal(ids.to(torch.int64) & 0xffffffff, ol))
+                rk["exact_speedup"] = round(t / r["seconds"], 2)
+                result["rows"].append(rk)
+                print(json.dumps(rk), flush=True)
+                assert rk["labels_equal"], "exact_search and knn disagree"
+            del xf, qf
         del rows
-        qf = q.to(torch.float32)
-        for k in (1, 10):
-            r, ol = exact(n, k, "%d rows" % n)
-            ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
-            dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
-            t, ts = timed(torch, dev, lambda: g.knn_dev(nq, n, d, qf, xf, k, ids, dist), args.warmup, args.reps,
-                          "%d rows knn k=%d" % (n, k))
-            rk = figures("knn_dev (f32 MFMA)", n, d, nq, k, t, ts)
-            rk["labels_equal"] = bool(torch.equal(ids.to(torch.int64) & 0xffffffff, ol))
-            rk["exact_speedup"] = round(t / r["seconds"], 2)
-            result["rows"].append(rk)
-            print(json.dumps(rk), flush=True)
-            assert rk["labels_equal"], "exact_search and knn disagree"
-        del xf, qf
         torch.cuda.empty_cache()
+        yardstick_and_range(n, dense_radius)
     if not args.no_big:
         n = args.rows
         fill_store(g, torch, dev, n, d, 99)
-        for k in (1, 100):
-            exact(n, k, "%d rows" % n)
+        yardstick_and_range(n)
     g.close()
     if args.out:
         with open(args.out, "w") as f:

@@ -6,7 +6,12 @@ Streams a .bvecs base into the device's base store (upload_base_bvecs), runs the
 per query one int32 k followed by k labels, nearest first, ties to the lower label.  Labels are the reference's idx_t
 (uint32): a label >= 2^31 is stored as its 32-bit pattern; a slot beyond the base's rows (k > rows) holds 0xffffffff.
 
-usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N]"""
+With --radius R the exact RANGE search runs instead (ivfhnsw_gpu_exact_range_search): --out is then an .npz holding lims
+(uint64 [nq + 1]), labels (int64) and distances (float32) -- query q owns entries [lims[q], lims[q + 1]), every base row
+with distance < R in ascending label -- and radius; --k is ignored.  read_range reads it back.
+
+usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N]
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N]"""
 import argparse
 import os
 import sys
@@ -45,6 +50,26 @@ def read_ivecs(path):
     return rec[:, 1:].astype(np.int64)
 
 
+def write_range(path, lims, distances, labels, radius):
+    """The result of an exact range search as an .npz (written to exactly `path`)."""
+    with open(path, "wb") as f:
+        np.savez(f, lims=np.asarray(lims, np.uint64), labels=np.asarray(labels, np.int64),
+                 distances=np.asarray(distances, np.float32), radius=np.float32(radius))
+
+
+def read_range(path):
+    """(lims uint64 [nq + 1], distances float32 [total], labels int64 [total], radius) of a file --radius wrote; lims is
+    checked against the arrays."""
+    with np.load(path) as z:
+        lims, dist, lab, radius = z["lims"], z["distances"], z["labels"], float(z["radius"])
+    if lims.dtype != np.uint64 or dist.dtype != np.float32 or lab.dtype != np.int64:
+        raise ValueError("%s: lims / distances / labels are not uint64 / float32 / int64" % path)
+    if lims.ndim != 1 or lims.size < 1 or lims[0] != 0 or (np.diff(lims.astype(np.int64)) < 0).any() or \
+            dist.shape != (int(lims[-1]),) or lab.shape != dist.shape:
+        raise ValueError("%s: lims does not describe the %d distances and %d labels" % (path, dist.size, lab.size))
+    return lims, dist, lab, radius
+
+
 def read_bvecs_image(path):
     """(image uint8 [n, d + 4], d) of a .bvecs file, every record's dim header checked; image[:, 4:] are the rows, d + 4
     bytes apart, as exact_search and upload_base take them."""
@@ -76,11 +101,26 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
     return lab
 
 
+def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20):
+    """(lims, distances, labels) of every base row within the radius of every query, ascending label per query."""
+    img, dq = read_bvecs_image(query_path)
+    g = pkg.GpuIndex(device)
+    try:
+        n, d = g.upload_base_bvecs(base_path, chunk_rows=chunk_rows, rows=rows)
+        if d != dq:
+            raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        return g.exact_range_search(img[:, 4:], radius)
+    finally:
+        g.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--base", required=True)
     ap.add_argument("--queries", required=True)
     ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--radius", type=float, default=None,
+                    help="range mode: every row with distance < RADIUS; --out is an .npz, --k is ignored")
     ap.add_argument("--out", required=True)
     ap.add_argument("--rows", type=int, default=None, help="only the base file's first N records")
     ap.add_argument("--device", type=int, default=0)
@@ -88,6 +128,11 @@ def main(argv=None):
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
+    if args.radius is not None:
+        lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device)
+        write_range(args.out, lims, dist, lab, args.radius)
+        print("%s: %d queries, %d rows within %g" % (args.out, lims.size - 1, lab.size, args.radius))
+        return
     lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device)
     write_ivecs(args.out, lab)
     print("%s: %d queries x %d labels" % (args.out, lab.shape[0], lab.shape[1]))

@@ -7,7 +7,11 @@
   and all of the scored codes are returned.  Per radius: wall milliseconds per call (the call returns when the results
   are complete), in a second loop with set_profiling the time of the count pass (accounted as the scan stage) and of
   the fill pass (the select stage), results per second, and the bytes the handle holds.
-usage: python tools/range_bench.py [--workload NAME] [--nq 10000] [--reps 10]"""
+  --recall instead: on the small SIFT-like uint8 corpus of tests/rerank_ref.uint8_recall_corpus, the IVF range search
+  against the exact one (ivfhnsw_gpu_exact_range_search) at radii taken as quantiles of the exact 10th
+  neighbour's distance: recall |IVF range & exact range| / |exact range| and precision |IVF range & exact range| /
+  |IVF range| of the label sets (the ADC distance is an approximation: neither is 1), and the mean results per query.
+usage: python tools/range_bench.py [--workload NAME] [--nq 10000] [--reps 10] [--recall]"""
 import argparse
 import json
 import os
@@ -25,17 +29,52 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def recall(pkg, quantiles=(0.1, 0.5, 0.9)):
+    import rerank_ref
+    c = rerank_ref.uint8_recall_corpus(pkg, seed=77)
+    g = pkg.GpuIndex(0)
+    g.upload_ivf(c["d"], c["code_size"], c["offsets"], c["ids"], c["codes"], c["norm_codes"], c["centroid_norms"],
+                 c["pq_centroids"], c["norm_table"])
+    g.upload_quantizer(c["counts"], c["links"], c["centroids"], 0)
+    g.upload_base(c["base"])
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)  # integer-valued, 0..255
+    nq, n = len(q8), len(c["base"])
+    kd, _ = g.exact_search(q8, 10)
+    rows = []
+    for x in quantiles:
+        r = float(np.quantile(kd[:, 9], x, method="lower"))
+        el, _, elab = g.exact_range_search(q8, r)
+        ekeys = np.repeat(np.arange(nq, dtype=np.int64), np.diff(el.astype(np.int64))) * n + elab
+        for nprobe, max_codes, ef in ((16, 10000, 64), (32, 20000, 80)):
+            il, _, ilab = g.range_search(qf, r, nprobe, max_codes, efSearch=ef)
+            ikeys = np.unique(np.repeat(np.arange(nq, dtype=np.int64), np.diff(il.astype(np.int64))) * n + ilab)
+            both = np.intersect1d(ikeys, ekeys, assume_unique=True).size
+            row = {"quantile_of_10th_neighbour": x, "radius": r, "nprobe": nprobe, "max_codes": max_codes, "efSearch": ef,
+                   "exact_per_query": ekeys.size / nq, "ivf_per_query": ikeys.size / nq,
+                   "recall": both / max(1, ekeys.size), "precision": both / max(1, ikeys.size)}
+            rows.append(row)
+            log("[range_bench] radius %.0f (q%.2f) nprobe %d: exact %.2f / query, ivf %.2f / query, recall %.4f, precision %.4f"
+                % (r, x, nprobe, row["exact_per_query"], row["ivf_per_query"], row["recall"], row["precision"]))
+    g.close()
+    return {"corpus": "uint8_recall_corpus(seed=77)", "rows": n, "nq": nq, "range_recall": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="synthetic-1B-pq16-nc993127-nprobe32")
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--recall", action="store_true", help="recall and precision against the exact range search instead")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
+    pkg = ge.load_pkg()
+    if args.recall:
+        print(json.dumps(recall(pkg)))
+        return
     import bench
     import synth
-    pkg = ge.load_pkg()
     dev = torch.device("cuda", 0)
     c = bench.Corpus(pkg, synth, args.workload, 1234, dev, 0)
     g = c.g
