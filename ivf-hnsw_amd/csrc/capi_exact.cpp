@@ -12,29 +12,43 @@ namespace {
 constexpr size_t kExactChunk = 16384;
 constexpr size_t kExactPartBytes = (size_t)256 << 20;
 
-int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k, float *distances,
-               int64_t *labels, bool on_device)
+// What every exact call checks before it touches anything, in this order: the handle; the store (*b: a view searches its
+// parent's); the call's own arguments (arg_check() returns their error, or 0); and, when there are queries, the buffers
+// (any_null, with the call's text) and the row stride.  nq == 0 passes: the caller returns what its empty call returns.
+template <class ArgCheck>
+int exact_guard(ivfhnsw_gpu *h, const char *name, size_t nq, size_t row_stride, bool any_null, const char *null_text,
+                ArgCheck arg_check, const ivfhnsw_gpu **b)
 {
     int rc = bind(h);
     if (rc)
         return rc;
-    const ivfhnsw_gpu *b = h->parent ? h->parent : h; // a view searches its parent's store
-    if (!b->base_n)
-        return fail(IVFHNSW_ERR_STATE, "exact_search before upload_base");
-    const size_t d = b->base_d, n = b->base_n;
+    *b = h->parent ? h->parent : h;
+    if (!(*b)->base_n)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_base", name);
+    const size_t d = (*b)->base_d;
     if (d > 256)
         return fail(IVFHNSW_ERR_INVALID,
-                    "exact_search on a store of dimension %zu: beyond d = 256 the squared distance can exceed 2^24 and is no "
-                    "longer the exact float fvec_L2sqr returns",
-                    d);
-    if (k < 1 || k > 100)
-        return fail(IVFHNSW_ERR_INVALID, "exact_search needs 1 <= k <= 100 (k %zu)", k);
-    if (nq == 0)
-        return IVFHNSW_OK;
-    if (!queries || !distances || !labels)
-        return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
+                    "%s on a store of dimension %zu: beyond d = 256 the squared distance can exceed 2^24 and is no longer the "
+                    "exact float fvec_L2sqr returns",
+                    name, d);
+    if ((rc = arg_check()) || nq == 0)
+        return rc;
+    if (any_null)
+        return fail(IVFHNSW_ERR_INVALID, "%s", null_text);
     if (row_stride < d)
         return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    return IVFHNSW_OK;
+}
+
+int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k, float *distances,
+               int64_t *labels, bool on_device)
+{
+    const ivfhnsw_gpu *b;
+    auto k_check = [&] { return k < 1 || k > 100 ? fail(IVFHNSW_ERR_INVALID, "exact_search needs 1 <= k <= 100 (k %zu)", k) : 0; };
+    int rc = exact_guard(h, "exact_search", nq, row_stride, !queries || !distances || !labels, "null query/result buffer", k_check, &b);
+    if (rc || nq == 0)
+        return rc;
+    const size_t d = b->base_d, n = b->base_n;
 
     const size_t first = std::min(nq, kExactChunk);
     const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_splits_for(first, n, (int)k);
@@ -89,27 +103,28 @@ int exact_range_threshold(float radius)
 int exact_range_guard(ivfhnsw_gpu *h, size_t nq, const void *queries, size_t row_stride, float radius, const void *lims,
                       const void *total)
 {
-    int rc = bind(h);
-    if (rc)
-        return rc;
-    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
-    if (!b->base_n)
-        return fail(IVFHNSW_ERR_STATE, "exact_range_search before upload_base");
-    if (b->base_d > 256)
-        return fail(IVFHNSW_ERR_INVALID,
-                    "exact_range_search on a store of dimension %zu: beyond d = 256 the squared distance can exceed 2^24 and "
-                    "is no longer the exact float fvec_L2sqr returns",
-                    (size_t)b->base_d);
-    if (std::isnan(radius))
-        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: the radius is NaN");
-    if (nq == 0)
-        return IVFHNSW_OK;
-    if (!queries || !lims || !total)
-        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: null queries, lims or total");
-    if (row_stride < b->base_d)
-        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, (size_t)b->base_d);
-    if (nq > kMaxBatchAll)
+    const ivfhnsw_gpu *b;
+    auto radius_check = [&] { return std::isnan(radius) ? fail(IVFHNSW_ERR_INVALID, "exact_range_search: the radius is NaN") : 0; };
+    const int rc = exact_guard(h, "exact_range_search", nq, row_stride, !queries || !lims || !total,
+                               "exact_range_search: null queries, lims or total", radius_check, &b);
+    if (rc == IVFHNSW_OK && nq > kMaxBatchAll)
         return fail(IVFHNSW_ERR_INVALID, "exact_range_search is limited to %zu queries per call", kMaxBatchAll);
+    return rc;
+}
+
+// a call without queries: lims is the one entry 0 (on the host or on the device), and no results are held
+int exact_range_none(ivfhnsw_gpu *h, uint64_t *lims, uint64_t *d_lims, uint64_t *total)
+{
+    if (lims)
+        lims[0] = 0;
+    if (d_lims) {
+        HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    if (total)
+        *total = 0;
+    h->xr_valid = true;
+    h->xr_total = 0;
     return IVFHNSW_OK;
 }
 
@@ -220,17 +235,8 @@ int ivfhnsw_gpu_exact_range_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t 
     int rc = exact_range_guard(h, nq, d_queries, row_stride, radius, d_lims, total);
     if (rc)
         return rc;
-    if (nq == 0) {
-        if (d_lims) {
-            HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-        if (total)
-            *total = 0;
-        h->xr_valid = true;
-        h->xr_total = 0;
-        return IVFHNSW_OK;
-    }
+    if (nq == 0)
+        return exact_range_none(h, nullptr, d_lims, total);
     return exact_range_dev(h, nq, d_queries, row_stride, radius, d_lims, total);
 }
 
@@ -240,11 +246,8 @@ int ivfhnsw_gpu_exact_range_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *que
     int rc = exact_range_guard(h, nq, queries, row_stride, radius, lims, total);
     if (rc)
         return rc;
-    if (nq == 0) {
-        if (lims)
-            lims[0] = 0;
-        return ivfhnsw_gpu_exact_range_search_dev(h, 0, nullptr, row_stride, radius, nullptr, total);
-    }
+    if (nq == 0)
+        return exact_range_none(h, lims, nullptr, total);
     const size_t d = (h->parent ? h->parent : h)->base_d;
     if ((rc = h->ex_raw.ensure(nq * d)) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))))
         return rc;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "scan_dispatch.h"
+#include "sweep_plan_math.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -290,7 +291,7 @@ hipError_t launch_kmeans_means(hipStream_t s, const float *x, size_t n, const ui
                                const uint32_t *cnt, float *c, size_t nc, int d);
 hipError_t launch_kmeans_split(hipStream_t s, float *c, const uint32_t *pairs, size_t npairs, int d);
 // exact k-nearest-neighbour tables on the matrix cores (kernels_knn.hip); part = [nsplit][nq][k] u64 workspace
-int knn_splits_for(size_t nq, size_t nx);
+inline int knn_splits_for(size_t nq, size_t nx) { return sweep_splits_for(nq, nx, 128); } // nx >= 1
 hipError_t launch_knn_norms(hipStream_t s, const float *x, float *out, size_t n, int d);
 hipError_t launch_knn(hipStream_t s, const float *Q, const float *X, const float *qn, const float *xn, size_t nq, size_t nx,
                       int d, int k, int mode, int nsplit, unsigned long long *part, uint32_t *ids, float *dists); // mode: IVFHNSW_KNN_*
@@ -335,8 +336,8 @@ hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, 
 // exact brute-force search of the store on the int8 matrix cores (kernels_exact.hip).  Qp: [nq][d] queries
 // in the store's byte order (launch_rerank_permute), d % 16 == 0, d <= 256, 1 <= k <= 100; part: [nsplit][nq][k] u64
 // workspace; writes the k nearest rows of every query ascending by (distance, label), padded with FLT_MAX / -1
-int exact_rows_per_block(int k);
-int exact_splits_for(size_t nq, size_t nx, int k);
+inline int exact_rows_per_block(int k) { return k <= 32 ? 128 : 64; }
+inline int exact_splits_for(size_t nq, size_t nx, int k) { return sweep_splits_for(nq, nx, exact_rows_per_block(k)); }
 hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
                                int nsplit, unsigned long long *part, float *dists, int64_t *labels);
 // exact range search (kernels_exact.hip): the same sweep with the fixed gate dist < thr (int32, thr >= 0),
@@ -347,7 +348,7 @@ hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *
 // map (nullable; then every tile is visited): [ceil(total queries / 32)][nsplit][exact_range_map_words] words, one bit
 // per 2^map_shift tiles of 32 columns; the count form writes every word the fill form of the same arguments reads.
 constexpr int kExactRangeMaxShift = 20;
-int exact_range_map_words(size_t nx, int nsplit, int map_shift);
+inline int exact_range_map_words(size_t nx, int nsplit, int map_shift) { return sweep_map_words(nx, nsplit, map_shift); }
 hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
                               int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
                               int map_shift, float *dist, int64_t *labels, size_t out_cap);

@@ -21,14 +21,10 @@
 // tiles of 32 columns through LDS, stored k-major ([k][32 columns]: the staging writes and the operand-B reads of a
 // half-wave both touch 32 consecutive words, no bank conflicts); the next tile's global loads are in flight in
 // registers behind the current tile's d/2 MFMAs (one LDS tile, so that with k <= 16 two workgroups fit a CU and fill
-// each other's barriers).  Selection: every lane holds the running k-th distance of its 16 rows;
-// a candidate below it (rare after the first tiles) is appended to the row's LDS buffer, placed by a ballot; a row whose
-// buffer could overflow in the next tile is compacted by its wave (rank of every key among the row's keys: keys are
-// unique, id in the low word).  Columns arrive in increasing id order, so among equal distances the earlier id wins by
-// the strict '<' alone.  Few query rows (ground truth for 10 k queries): the columns are split over blockIdx.y and the
-// partial tables merged by knn_merge_kernel.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+// each other's barriers).  Selection is sweep_steps.h's (row_append, rows_compact, rows_write_out), shared with
+// kernels_exact.hip; here the key is (orderable distance, id).  Few query rows (ground truth for 10 k queries): the
+// columns are split over blockIdx.y and the partial tables merged by knn_merge_kernel (sweep_merge).
+#include "sweep_steps.h"
 
 #include <float.h>
 
@@ -37,8 +33,6 @@ namespace ivfhnsw_gpu_impl {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr unsigned long long kKnnKeyNone = ~0ull;
 
 __global__ __launch_bounds__(256) void knn_norms_kernel(const float *__restrict__ x, float *__restrict__ out, size_t n, int d,
                                                         int ld)
@@ -98,8 +92,7 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(const float *__restric
     float qn_r[16], thr[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
-        qn_r[r] = qn[min(r0 + row, nq - 1)];
+        qn_r[r] = qn[min(r0 + mfma32_row(r, kk), nq - 1)];
         thr[r] = FLT_MAX;
     }
     if (lane < 32) {
@@ -166,129 +159,40 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(const float *__restric
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const float dist = __fsub_rn(__fadd_rn(qn_r[r], xnc), __fmul_rn(2.0f, acc[r]));
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
+            const int row = mfma32_row(r, kk);
             const bool pass = col_ok && dist < thr[r] && (mode == 0 || (mode == 1 ? (long long)col != (long long)(r0 + row)
                                                                                    : (long long)col < (long long)(r0 + row)));
             const unsigned long long mask = __ballot(pass);
             if (mask) { // wave-uniform: rare once the thresholds have settled
-                const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
-                const uint32_t base = cnt[row];
-                if (pass)
-                    buf[(size_t)row * CAP + base + __popc(half & ((1u << m) - 1u))] =
-                        ((unsigned long long)f32_orderable(dist) << 32) | (uint32_t)col;
-                if (m == 0 && half)
-                    cnt[row] = base + __popc(half);
+                row_append<CAP>(buf, cnt, row, pass, mask, dist, (uint32_t)col, m, kk);
                 any_new = true;
             }
         }
         if (any_new) {
-            // rows that could overflow in the next tile (32 more entries at most): keep their k smallest
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long need = __ballot(lane < 32 && cnt[lane] > (uint32_t)(CAP - 32));
-            while (need) {
-                const int row = __ffsll((long long)need) - 1;
-                need &= need - 1;
-                const int n = (int)cnt[row];
-                unsigned long long *rb = buf + (size_t)row * CAP;
-                // two keys per lane; rank = number of smaller keys (all distinct)
-                const unsigned long long k0 = lane < n ? rb[lane] : kKnnKeyNone;
-                const unsigned long long k1 = lane + 64 < n ? rb[lane + 64] : kKnnKeyNone;
-                int rk0 = 0, rk1 = 0;
-                for (int i = 0; i < n; i++) {
-                    const unsigned long long v = rb[i];
-                    rk0 += v < k0 ? 1 : 0;
-                    rk1 += v < k1 ? 1 : 0;
-                }
-                __builtin_amdgcn_wave_barrier();
-                if (lane < n && rk0 < k)
-                    rb[rk0] = k0;
-                if (lane + 64 < n && rk1 < k)
-                    rb[rk1] = k1;
-                if (lane == 0)
-                    cnt[row] = (uint32_t)min(n, k);
-                __builtin_amdgcn_wave_barrier();
-                if (lane == 0 && n >= k)
-                    thr_s[row] = orderable_f32((uint32_t)(rb[k - 1] >> 32));
-            }
-            __builtin_amdgcn_wave_barrier();
+            rows_compact<CAP>(buf, cnt, thr_s, k, lane);
 #pragma unroll
             for (int r = 0; r < 16; r++)
-                thr[r] = thr_s[(r & 3) + 8 * (r >> 2) + 4 * kk];
+                thr[r] = thr_s[mfma32_row(r, kk)];
         }
     }
 
-    // final order of every row, then out: [split][nq][k] keys ascending, kKnnKeyNone beyond what was found
-    for (int row = 0; row < 32; row++) {
-        const int n = (int)cnt[row];
-        unsigned long long *rb = buf + (size_t)row * CAP;
-        const unsigned long long k0 = lane < n ? rb[lane] : kKnnKeyNone;
-        const unsigned long long k1 = lane + 64 < n ? rb[lane + 64] : kKnnKeyNone;
-        int rk0 = 0, rk1 = 0;
-        for (int i = 0; i < n; i++) {
-            const unsigned long long v = rb[i];
-            rk0 += v < k0 ? 1 : 0;
-            rk1 += v < k1 ? 1 : 0;
-        }
-        if (r0 + row < nq) {
-            unsigned long long *o = out_keys + ((size_t)blockIdx.y * nq + (r0 + row)) * (size_t)k;
-            if (lane < n && rk0 < k)
-                o[rk0] = k0;
-            if (lane + 64 < n && rk1 < k)
-                o[rk1] = k1;
-            for (int i = n + lane; i < k; i += 64)
-                o[i] = kKnnKeyNone;
-        }
-    }
+    // out: [split][nq][k] keys
+    rows_write_out<CAP>(buf, cnt, k, lane, nq - r0, out_keys, (size_t)blockIdx.y * nq + r0);
 }
 
-// one wavefront per query: the k smallest of the splits' sorted partial tables (keys distinct: ids differ)
 __global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long *__restrict__ part, int nsplit, int nq,
                                                        int k, uint32_t *__restrict__ ids, float *__restrict__ dists)
 {
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const int total = nsplit * k;
-    for (int i = lane; i < total; i += 64) {
-        const int s = i / k, j = i - s * k;
-        const unsigned long long key = part[((size_t)s * nq + q) * k + j];
-        if (key == kKnnKeyNone)
-            continue;
-        int rank = 0;
-        for (int t = 0; t < nsplit; t++) {
-            // keys of split t below `key`: the lists are sorted, binary search
-            const unsigned long long *p = part + ((size_t)t * nq + q) * k;
-            int lo = 0, hi = k;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (p[mid] < key)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            rank += lo;
-        }
-        if (rank < k) {
-            ids[(size_t)q * k + rank] = (uint32_t)key;
-            dists[(size_t)q * k + rank] = orderable_f32((uint32_t)(key >> 32));
-        }
-    }
-    // slots nothing reached: fewer than k candidates exist
-    int found = 0;
-    for (int t = 0; t < nsplit; t++) {
-        const unsigned long long *p = part + ((size_t)t * nq + q) * k;
-        int lo = 0, hi = k;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (p[mid] != kKnnKeyNone)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        found += lo;
-    }
-    for (int i = min(found, k) + lane; i < k; i += 64) {
-        ids[(size_t)q * k + i] = 0xffffffffu;
-        dists[(size_t)q * k + i] = FLT_MAX;
-    }
+    sweep_merge(
+        part, nsplit, nq, k,
+        [&](size_t o, unsigned long long key) {
+            ids[o] = (uint32_t)key;
+            dists[o] = orderable_f32((uint32_t)(key >> 32));
+        },
+        [&](size_t o) {
+            ids[o] = 0xffffffffu;
+            dists[o] = FLT_MAX;
+        });
 }
 
 template <int D2, int CAP>
@@ -307,17 +211,6 @@ hipError_t launch_knn_t(hipStream_t s, const float *Q, const float *X, const flo
 
 } // namespace
 
-int knn_splits_for(size_t nq, size_t nx)
-{
-    // enough workgroups for two per CU; a split never shorter than 4096 columns
-    const size_t row_blocks = (nq + 127) / 128;
-    size_t s = (512 + row_blocks - 1) / row_blocks;
-    const size_t max_s = (nx + 4095) / 4096;
-    s = s < 1 ? 1 : s;
-    s = s > max_s ? max_s : s;
-    return (int)(s > 64 ? 64 : s);
-}
-
 hipError_t launch_knn_norms(hipStream_t s, const float *x, float *out, size_t n, int d)
 {
     if (n == 0)
@@ -334,8 +227,7 @@ hipError_t launch_knn(hipStream_t s, const float *Q, const float *X, const float
         return hipSuccess;
     if (d < 4 || d > 128 || (d & 3) || k > 80 || nq > 0x7fffffffull || nx > 0xffffffffull || nsplit < 1 || mode < 0 || mode > 2)
         return hipErrorInvalidValue;
-    size_t cps = (nx + nsplit - 1) / nsplit;
-    cps = (cps + 31) & ~(size_t)31;
+    const size_t cps = sweep_cols_per_split(nx, nsplit);
     hipError_t e;
     const int d2 = (d + 1) / 2;
 #define IVFHNSW_KNN(D2)                                                                                                \

@@ -5,6 +5,7 @@
 // intrinsic in the order the reference's source evaluates it; this file is built with
 // -ffp-contract=off so nothing else gets fused either.
 #include "scan_steps.h"
+#include "sweep_steps.h"
 
 #include <float.h>
 #include <stdlib.h>
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void opq_mfma_kernel(const float *__restrict__
         }
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * kk; // C/D layout of the 32x32 MFMA
+            const int row = mfma32_row(r, kk);
             if (q0 + row < nq)
                 y[(size_t)(q0 + row) * d + i0 + m] = acc[r];
         }

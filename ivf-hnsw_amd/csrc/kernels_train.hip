@@ -9,8 +9,7 @@
 // X^T Y contracts over the n training points (n = 65 536 at faiss's default): that one is a true dense
 // contraction and runs on v_mfma_f32_32x32x2_f32, whose accumulation is a k-ordered fmaf chain -- a defined order
 // the oracle restates (orc_xty).
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "sweep_steps.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(64) void xty_mfma_kernel(const float *__restrict__ 
     float *p = P + (size_t)blockIdx.z * d * d;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * kk; // C/D layout of the 32x32 MFMA
+        const int row = mfma32_row(r, kk);
         p[(size_t)(a0 + row) * d + b0 + m] = acc[r];
     }
 }

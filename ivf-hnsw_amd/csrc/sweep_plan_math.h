@@ -1,0 +1,59 @@
+// The host arithmetic the brute-force MFMA sweeps share (knn_mfma_kernel, exact_mfma_kernel, exact_range_kernel;
+// DESIGN.md 1b): how the columns are cut into splits, how many splits a call takes, the size of the range search's tile
+// map, and the one dispatch on a row's length.  One copy; the device steps are in sweep_steps.h.  No HIP in here:
+// tests/cpp/sweep_plan_tool.cpp checks it on the host against the formulas it replaced.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "scan_dispatch.h"
+
+namespace ivfhnsw_gpu_impl {
+
+// Columns per split: equal shares rounded up to the 32 columns of a tile, never none (an empty store still gets a
+// split, whose kernels find c_begin >= c_end and read nothing).
+inline size_t sweep_cols_per_split(size_t nx, int nsplit)
+{
+    size_t cps = (nx + nsplit - 1) / nsplit;
+    cps = (cps + 31) & ~(size_t)31;
+    return cps ? cps : 32;
+}
+
+// Splits of a call whose workgroups own rows_per_block query rows each:
+// enough workgroups for two per CU; a split never shorter than 4096 columns
+inline int sweep_splits_for(size_t nq, size_t nx, int rows_per_block)
+{
+    const size_t rpb = (size_t)rows_per_block;
+    const size_t row_blocks = (nq + rpb - 1) / rpb;
+    size_t s = (512 + row_blocks - 1) / row_blocks;
+    const size_t max_s = (nx + 4095) / 4096;
+    s = s > max_s ? max_s : s;
+    s = s < 1 ? 1 : s;
+    return (int)(s > 64 ? 64 : s);
+}
+
+// Words of the range search's tile map per (32 queries, split): one bit per 2^map_shift tiles, 32 bits to a word.
+inline int sweep_map_words(size_t nx, int nsplit, int map_shift)
+{
+    const size_t tiles = sweep_cols_per_split(nx, nsplit) / 32;
+    const size_t bits = (tiles + ((size_t)1 << map_shift) - 1) >> map_shift;
+    return (int)((bits + 31) / 32);
+}
+
+// f(int_c<NS>()) for NS = ceil(d / 32) = 1 .. 8, the steps of 32 bytes a row of the uint8 store is read in (d <= 256)
+template <class F> auto by_row_steps(int d, F &&f)
+{
+    switch ((d + 31) / 32) {
+    case 1: return f(int_c<1>());
+    case 2: return f(int_c<2>());
+    case 3: return f(int_c<3>());
+    case 4: return f(int_c<4>());
+    case 5: return f(int_c<5>());
+    case 6: return f(int_c<6>());
+    case 7: return f(int_c<7>());
+    default: return f(int_c<8>());
+    }
+}
+
+} // namespace ivfhnsw_gpu_impl

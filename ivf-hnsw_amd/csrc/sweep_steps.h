@@ -1,0 +1,254 @@
+// The steps the brute-force MFMA sweeps share, one copy each: the C/D row map, the selection of a row's k
+// smallest keys through its LDS buffer (knn_mfma_kernel, exact_mfma_kernel), the int8 strip that reads the uint8 store
+// (exact_mfma_kernel, exact_range_kernel) and the merge of the splits' partial tables.  Control flow -- which tile comes
+// next, what a tile without a candidate costs, what is done with a distance that passes -- stays in the kernels.  Host
+// arithmetic (columns per split, split count): sweep_plan_math.h.
+#pragma once
+
+#include "ivfhnsw_kernels.h"
+#include "device_common.h"
+
+namespace ivfhnsw_gpu_impl {
+
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// a slot of a key table nothing was found for
+constexpr unsigned long long kSweepKeyNone = ~0ull;
+
+// C/D layout of the 32x32 MFMA: col = lane & 31, and accumulator register r of a lane with kk = lane >> 5 is row
+__device__ __forceinline__ int mfma32_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Selection.  Every lane holds the running k-th distance of its 16 rows; a candidate below it (rare after the first
+// tiles) goes to the row's LDS buffer, placed by a ballot; a row whose buffer could overflow in the next tile is
+// compacted by its wave by rank (keys are unique: the column in the low word).  Columns arrive in increasing order, so
+// among equal distances the lower column wins by the strict '<' alone.
+// A wave's arrays: buf [32][CAP] keys, cnt [32] keys held, thr_s [32] the k-th distance (the type's maximum until a row
+// holds k keys).  CAP = keys of a row's buffer; a row is compacted when it holds more than CAP - 32.
+
+// A distance as the high word of a key, and back as the threshold its kernel compares distances with: float distances
+// in their order-preserving form, the exact search's integers as they are.  Chosen by type at compile time: only a lane
+// that appends, and the one lane that finds a row's k-th key, convert, which costs no register -- keeping the high word
+// in LDS and converting on reload would be 16 conversions per lane after every tile with a candidate.
+__device__ __forceinline__ uint32_t key_hi(float dist) { return f32_orderable(dist); }
+__device__ __forceinline__ uint32_t key_hi(int dist) { return (uint32_t)dist; }
+__device__ __forceinline__ void key_threshold(uint32_t hi, float &thr) { thr = orderable_f32(hi); }
+__device__ __forceinline__ void key_threshold(uint32_t hi, int &thr) { thr = (int)hi; }
+
+// The lanes of `row` that pass (mask = their ballot, not empty: the test is the kernel's, wave-uniform) append their
+// (dist, col) keys in lane order = column order.
+template <int CAP, class D>
+__device__ __forceinline__ void row_append(unsigned long long *buf, uint32_t *cnt, int row, bool pass, unsigned long long mask,
+                                           D dist, uint32_t col, int m, int kk)
+{
+    const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
+    const uint32_t base = cnt[row];
+    if (pass)
+        buf[(size_t)row * CAP + base + __popc(half & ((1u << m) - 1u))] = ((unsigned long long)key_hi(dist) << 32) | col;
+    if (m == 0 && half)
+        cnt[row] = base + __popc(half);
+}
+
+// rank of up to NK keys per lane among the n keys of a row buffer (the number of smaller keys: all distinct), the k
+// smallest written to dst in order
+template <int NK>
+__device__ __forceinline__ void rank_row(const unsigned long long *rb, int n, int k, int lane, unsigned long long *dst,
+                                         bool in_place)
+{
+    unsigned long long key[NK];
+    int rk[NK];
+#pragma unroll
+    for (int u = 0; u < NK; u++) {
+        key[u] = lane + 64 * u < n ? rb[lane + 64 * u] : kSweepKeyNone;
+        rk[u] = 0;
+    }
+    for (int i = 0; i < n; i++) {
+        const unsigned long long v = rb[i];
+#pragma unroll
+        for (int u = 0; u < NK; u++)
+            rk[u] += v < key[u] ? 1 : 0;
+    }
+    if (in_place)
+        __builtin_amdgcn_wave_barrier(); // every lane has read the buffer before any lane rewrites it
+#pragma unroll
+    for (int u = 0; u < NK; u++)
+        if (lane + 64 * u < n && rk[u] < k)
+            dst[rk[u]] = key[u];
+}
+
+// rows that could overflow in the next tile (32 more entries at most): keep their k smallest
+template <int CAP, class T>
+__device__ __forceinline__ void rows_compact(unsigned long long *buf, uint32_t *cnt, T *thr_s, int k, int lane)
+{
+    __builtin_amdgcn_wave_barrier();
+    unsigned long long need = __ballot(lane < 32 && cnt[lane] > (uint32_t)(CAP - 32));
+    while (need) {
+        const int row = __ffsll((long long)need) - 1;
+        need &= need - 1;
+        const int n = (int)cnt[row];
+        unsigned long long *rb = buf + (size_t)row * CAP;
+        rank_row<(CAP + 63) / 64>(rb, n, k, lane, rb, true);
+        if (lane == 0)
+            cnt[row] = (uint32_t)min(n, k);
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0 && n >= k)
+            key_threshold((uint32_t)(rb[k - 1] >> 32), thr_s[row]);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// final order of the wave's first nrows rows (the others are beyond nq), then out: row i to out[(first + i) * k ..],
+// k keys ascending, kSweepKeyNone beyond what was found
+template <int CAP>
+__device__ __forceinline__ void rows_write_out(const unsigned long long *buf, const uint32_t *cnt, int k, int lane, int nrows,
+                                               unsigned long long *out, size_t first)
+{
+    __builtin_amdgcn_wave_barrier();
+    for (int row = 0; row < min(nrows, 32); row++) {
+        const int n = (int)cnt[row];
+        unsigned long long *o = out + (first + row) * (size_t)k;
+        rank_row<(CAP + 63) / 64>(buf + (size_t)row * CAP, n, k, lane, o, false);
+        for (int i = n + lane; i < k; i += 64)
+            o[i] = kSweepKeyNone;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The int8 strip.  A wave owns 32 query rows for the whole sweep (operand A: NS = ceil(d / 32) steps of 16 bytes per
+// lane, in registers) and takes the columns 32 at a time.  Lane l loads bytes [32 s + 16 (l >> 5), + 16) of row
+// c0 + (l & 31) for step s straight from the store -- the row norm comes from the same registers (v_dot4_i32_i8), so
+// nothing is staged in LDS and the waves never meet at a barrier; the next tile's loads are in flight behind the
+// current tile's MFMAs.  Rows are [.][d] bytes, 16-byte aligned, d % 16 == 0.
+
+__device__ __forceinline__ int i8_sq4(const i32x4 &w, int acc)
+{
+    acc = __builtin_amdgcn_sdot4(w.x, w.x, acc, false);
+    acc = __builtin_amdgcn_sdot4(w.y, w.y, acc, false);
+    acc = __builtin_amdgcn_sdot4(w.z, w.z, acc, false);
+    return __builtin_amdgcn_sdot4(w.w, w.w, acc, false);
+}
+
+// dist < thr  <=>  2 dot - |x'|^2 > |q'|^2 - thr = gate: what a tile costs per accumulator register when nothing passes
+__device__ __forceinline__ bool i8_gate_pass(int acc_r, int xn, int gate_r) { return (acc_r << 1) - xn > gate_r; }
+
+template <int NS> struct I8Strip {
+    i32x4 a[NS], cur[NS], nxt[NS]; // operand A; the tile being multiplied; the raw bytes of the tile in flight
+    int qn_r[16];                  // |q'|^2 of the 16 rows whose dot products this lane holds (mfma32_row)
+    int m, kk;
+    bool tail_in;
+
+    // the 16 bytes of step s this lane owns.  Only the upper half of the last step can lie at or beyond byte d of the row
+    // (d % 32 == 16): there the lane reads the row's first piece again, without a branch, and to_i8 replaces it by zeros
+    // -- the upper half of the last step is zero in both operands and is never read (it would lie in the next row, or
+    // past the store's end).
+    __device__ __forceinline__ void load_row(const uint8_t *row, i32x4 (&w)[NS]) const
+    {
+#pragma unroll
+        for (int s = 0; s < NS; s++)
+            w[s] = *reinterpret_cast<const i32x4 *>(row + (s < NS - 1 || tail_in ? 32 * s + 16 * kk : 0));
+    }
+    // The XOR to i8 waits until the bytes are used, so that a tile's loads stay in flight behind the tile before it.
+    __device__ __forceinline__ void to_i8(const i32x4 (&raw)[NS], i32x4 (&w)[NS]) const
+    {
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const i32x4 zero = {0, 0, 0, 0};
+            w[s] = s < NS - 1 || tail_in ? raw[s] ^ (int)0x80808080 : zero;
+        }
+    }
+
+    // operand A and the norms of the wave's 32 query rows [r0, r0 + 32) of Qp [nq][d] (rows beyond nq repeat the last)
+    __device__ __forceinline__ void setup(const uint8_t *Qp, int r0, int lane, int nq, int d)
+    {
+        m = lane & 31, kk = lane >> 5;
+        tail_in = 32 * (NS - 1) + 16 * kk < d;
+        load_row(Qp + (size_t)min(r0 + m, nq - 1) * d, nxt);
+        to_i8(nxt, a);
+        int qn = 0;
+#pragma unroll
+        for (int s = 0; s < NS; s++)
+            qn = i8_sq4(a[s], qn);
+        qn += __shfl_xor(qn, 32);
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            qn_r[r] = __shfl(qn, mfma32_row(r, kk));
+    }
+
+    // start the loads of the tile whose first column is c0, of the split's columns [c_begin, c_end) of X [.][d]:
+    // a column at or beyond c_end is not read (the lane reads the split's first row and drops it)
+    __device__ __forceinline__ void fetch(const uint8_t *X, size_t c0, size_t c_begin, size_t c_end, int d)
+    {
+        const size_t c = c0 + m;
+        load_row(X + (c < c_end ? c : c_begin) * (size_t)d, nxt);
+    }
+    // the fetched tile becomes the current one; call before the next fetch
+    __device__ __forceinline__ void take() { to_i8(nxt, cur); }
+
+    // the current tile: acc[r] = q'.x' of row mfma32_row(r, kk) and the lane's column, xn = |x'|^2 of that column
+    __device__ __forceinline__ void product(i32x16 &acc, int &xn) const
+    {
+        acc = i32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        xn = 0;
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], cur[s], acc, 0, 0, 0);
+            xn = i8_sq4(cur[s], xn);
+        }
+        xn += __shfl_xor(xn, 32);
+    }
+    // does any of the lane's 16 distances pass its row's gate
+    __device__ __forceinline__ bool any_pass(const i32x16 &acc, int xn, const int (&gate)[16]) const
+    {
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            any |= i8_gate_pass(acc[r], xn, gate[r]); // all terms far inside int32
+        return any;
+    }
+    __device__ __forceinline__ int dist(const i32x16 &acc, int xn, int r) const { return qn_r[r] + xn - 2 * acc[r]; }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The merge of a split call, one wavefront per query: the k smallest of the splits' sorted partial tables part
+// [nsplit][nq][k] (keys distinct: the low words differ).  A key's rank is the number of keys below it, summed over the
+// tables; put(slot, key) stores a result, pad(slot) fills a slot nothing reached.
+template <class Put, class Pad>
+__device__ __forceinline__ void sweep_merge(const unsigned long long *__restrict__ part, int nsplit, int nq, int k, Put put,
+                                            Pad pad)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int total = nsplit * k;
+    int found = 0;
+    for (int i = lane; i < total; i += 64) {
+        const int s = i / k, j = i - s * k;
+        const unsigned long long key = part[((size_t)s * nq + q) * k + j];
+        if (key == kSweepKeyNone)
+            continue;
+        found++;
+        int rank = 0;
+        for (int t = 0; t < nsplit; t++) {
+            // keys of split t below `key`: the lists are sorted, binary search
+            const unsigned long long *p = part + ((size_t)t * nq + q) * k;
+            int lo = 0, hi = k;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (p[mid] < key)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < k)
+            put((size_t)q * k + rank, key);
+    }
+    // slots nothing reached: fewer than k candidates exist
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        found += __shfl_xor(found, o);
+    for (int i = min(found, k) + lane; i < k; i += 64)
+        pad((size_t)q * k + i);
+}
+
+} // namespace ivfhnsw_gpu_impl
