@@ -6,8 +6,7 @@
 // 311-316); the cached value is a pure function of (query, centroid) -- the HNSW walk and fvec_L2sqr are
 // the same arithmetic (utils.cpp:22-52 == hnswalg.cpp:326-357) -- so it is simply evaluated where needed.
 // Sequential float sums (the threshold, Grouping.cpp:253) keep the reference's (probe, sub-group) order.
-#include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "plan_steps.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -55,58 +54,28 @@ __global__ __launch_bounds__(64) void plan_grouping_kernel(IvfTables t, GroupTab
             const unsigned long long gs = t.goff[c + 1] - t.goff[c];
             if (gs == 0)
                 continue;
-            const float alpha = g.alphas[c];
-            const float oma = __fsub_rn(1.0f, alpha);
-            const float term1 = __fmul_rn(oma, qd[i]);
+            const GroupTerms gt = group_terms(g.alphas[c], qd[i]);
             for (int s0 = 0; s0 < nsubc; s0 += 64) {
                 const int subc = s0 + lane;
                 bool active = false;
-                float v = 0.f, qn = 0.f;
+                float v = 0.f;
                 uint32_t nn = 0;
                 if (subc < nsubc && g.sub_sizes[(size_t)c * nsubc + subc] != 0) {
                     active = true;
                     nn = g.nn_idx[(size_t)c * nsubc + subc];
                 }
-                // distances of the active sub-groups' neighbour centroids: a quad of lanes per row, 16 rows per
-                // pass, results handed back to the owning lane through LDS
-                {
-                    const unsigned long long am = __ballot(active);
-                    const int na = __popcll(am);
-                    for (int base = 0; base < na; base += 16) {
-                        const int r = base + (lane >> 2);
-                        const int src = r < na ? nth_set_bit(am, r) : 0;
-                        const uint32_t nnq = (uint32_t)__shfl((int)nn, src, 64);
-                        float dq = 0.f;
-                        if (r < na)
-                            dq = l2_ref_order_quad(gr.vectors + (size_t)nnq * t.d, s_q, t.d, lane & 3);
-                        if (r < na && (lane & 3) == 0)
-                            s_dist[src] = dq;
-                    }
-                    __syncthreads();
-                    if (active)
-                        qn = s_dist[lane];
-                    __syncthreads();
-                }
-                if (active) {
-                    const float a = __fmul_rn(oma, g.inter_dists[(size_t)c * nsubc + subc]);
-                    const float b = __fsub_rn(a, qn);
-                    v = __fsub_rn(term1, __fmul_rn(alpha, b)); // Grouping.cpp:251-252
-                }
+                const float qn = gather_quads<false>(active, __ballot(active), nn, 0.f, gr.vectors, s_q, t.d, s_dist, lane);
+                if (active)
+                    v = group_pass1_value(gt, g.inter_dists[(size_t)c * nsubc + subc], qn);
                 if (subc < nsubc) {
                     qsd[(size_t)row * nsubc + subc] = v; // value-initialised 0.0 where inactive (:228)
                     qnv[(size_t)row * nsubc + subc] = qn;
                 }
-                unsigned long long m = __ballot(active);
-                nsubgroups += __popcll(m);
-                while (m) { // threshold += qsd[subc], in sub-group order (:253)
-                    const int j = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    threshold = __fadd_rn(threshold, __shfl(v, j, 64));
-                }
+                threshold_add_active(threshold, nsubgroups, active, v);
             }
             ncode += gs;
             row++;
-            if (ncode >= 2 * max_codes)
+            if (plan_pass1_ends(ncode, max_codes))
                 break;
         }
         p1_rows = row;
@@ -115,8 +84,7 @@ __global__ __launch_bounds__(64) void plan_grouping_kernel(IvfTables t, GroupTab
     __syncthreads();
 
     // ---- pass 2 (Grouping.cpp:283-353)
-    unsigned long long ncode = 0; // codes scored so far == scan position of the next one
-    uint32_t ns = 0, nl = 0;
+    PlanCursor cur;
     int row = 0;
     Seg *sq = segs + (size_t)q * max_seg;
     uint32_t *lq = lpos + (size_t)q * max_seg;
@@ -127,11 +95,8 @@ __global__ __launch_bounds__(64) void plan_grouping_kernel(IvfTables t, GroupTab
         const unsigned long long gs = t.goff[c + 1] - t.goff[c];
         if (gs == 0)
             continue;
-        const float alpha = g.alphas[c];
-        const float oma = __fsub_rn(1.0f, alpha);
-        const float term1 = __fmul_rn(oma, __fsub_rn(qd[i], t.centroid_norms[c]));
+        const GroupTerms gt = group_terms(g.alphas[c], ivf_cterm(qd[i], t.centroid_norms[c]));
         const uint32_t lo_c = t.loff[c];
-        const bool owned = lo_c != kNotOwned;
         uint32_t list_off = 0; // codes of this list before the current chunk of sub-groups
         for (int s0 = 0; s0 < nsubc; s0 += 64) {
             const int subc = s0 + lane;
@@ -151,63 +116,21 @@ __global__ __launch_bounds__(64) void plan_grouping_kernel(IvfTables t, GroupTab
             const bool need = scanned && !(do_pruning && row < p1_rows);
             if (scanned && !need)
                 qn2 = qnv[(size_t)row * nsubc + subc];
-            {
-                const uint32_t nn = scanned ? g.nn_idx[(size_t)c * nsubc + subc] : 0u;
-                const unsigned long long am = __ballot(need);
-                const int na = __popcll(am);
-                if (na) {
-                    for (int base = 0; base < na; base += 16) {
-                        const int r = base + (lane >> 2);
-                        const int src = r < na ? nth_set_bit(am, r) : 0;
-                        const uint32_t nnq = (uint32_t)__shfl((int)nn, src, 64);
-                        float dq = 0.f;
-                        if (r < na)
-                            dq = l2_ref_order_quad(gr.vectors + (size_t)nnq * t.d, s_q, t.d, lane & 3);
-                        if (r < na && (lane & 3) == 0)
-                            s_dist[src] = dq;
-                    }
-                    __syncthreads();
-                    if (need)
-                        qn2 = s_dist[lane];
-                    __syncthreads();
-                }
-                if (scanned) {
-                    const float term2 = __fmul_rn(alpha, __fsub_rn(qn2, t.centroid_norms[nn])); // :318
-                    cterm = __fadd_rn(term1, term2);
-                }
-            }
-            const uint32_t in_sz = wave_incl_scan(sz, lane);
-            const uint32_t in_sc = wave_incl_scan(scanned ? sz : 0u, lane);
-            const unsigned long long m = __ballot(scanned);
-            const uint32_t rank_sc = __popcll(m & ((1ull << lane) - 1ull));
-            if (scanned && owned) {
-                Seg sg;
-                sg.start = lo_c + list_off + (in_sz - sz);
-                sg.len = sz;
-                sg.vpos = (uint32_t)ncode + (in_sc - sz);
-                sg.cterm = cterm;
-                sq[ns + rank_sc] = sg;
-                lq[ns + rank_sc] = nl + (in_sc - sz);
-            }
-            const uint32_t tot_sz = __shfl(in_sz, 63, 64), tot_sc = __shfl(in_sc, 63, 64);
-            list_off += tot_sz;
-            ncode += tot_sc;
-            if (owned) {
-                ns += (uint32_t)__popcll(m);
-                nl += tot_sc;
-            }
+            const uint32_t nn = scanned ? g.nn_idx[(size_t)c * nsubc + subc] : 0u;
+            const unsigned long long am = __ballot(need);
+            if (am)
+                qn2 = gather_quads<false>(need, am, nn, qn2, gr.vectors, s_q, t.d, s_dist, lane);
+            if (scanned)
+                cterm = group_cterm(gt, qn2, t.centroid_norms[nn]);
+            list_off += emit_segments(cur, scanned, sz, cterm, lo_c, list_off, sq, lq, lane);
         }
-        if (ncode >= max_codes)
+        if (plan_pass2_ends(cur.ncode, max_codes))
             break;
         if (do_pruning)
             row++;
     }
-    if (lane == 0) {
-        PlanHdr h;
-        h.nseg = ns;
-        h.total = nl;
-        hdr[q] = h;
-    }
+    if (lane == 0)
+        store_plan_hdr(&hdr[q], cur.ns, cur.nl);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -222,12 +145,6 @@ __global__ __launch_bounds__(64) void plan_grouping_kernel(IvfTables t, GroupTab
 // pass 2 -- bookkeeping over the probes in order -- runs on wavefront 0 as before, reading the distances (phase C).
 // Same arithmetic on the same operands in the same order wherever order matters: same bits.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_lds_order()
-{
-    // LDS operations of one wavefront execute in order; this only stops hipcc from moving them across each other
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // DEDUPE (round 3): phase A evaluates every DISTINCT neighbour centroid of the query once.  The reference caches
 // ||x - y_N||^2 per query (query_centroid_dists, Grouping.cpp:244-250, 311-316) because the probed groups' neighbour lists
 // overlap: on clustered centroids -- a query's probes are each other's neighbours -- the ~1350 (row, sub-group) pairs of a
@@ -235,12 +152,6 @@ __device__ __forceinline__ void wave_lds_order()
 // The four wavefronts enter the pairs' centroid ids into an LDS hash set (compare-and-swap, linear probing), compact the
 // occupied slots, evaluate those rows by lane quads, and every pair reads its value back: the same function of (query,
 // centroid), the same bits.  Chosen per index at upload from the overlap of its neighbour lists (GroupTables::dedupe).
-constexpr int GH_SLOTS = 2048;
-constexpr int GH_PROBES = 48;
-constexpr uint32_t GH_EMPTY = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t gh_hash(uint32_t id) { return (id * 2654435761u) >> 21; } // 11 bits
-
 template <bool DEDUPE>
 __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupTables g, GraphTables gr,
                                                             const float *__restrict__ xq,
@@ -263,7 +174,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             st_t = now;
         }
     };
-    extern __shared__ __attribute__((aligned(16))) float s_q[]; // query[d] | dist[4][64] | probe of row[nprobe]
+    extern __shared__ __attribute__((aligned(16))) float s_q[]; // laid out by plan4_lds (plan_math.h)
     __shared__ int s_p1, s_ra, s_nrows;
     __shared__ uint32_t h_key[DEDUPE ? GH_SLOTS : 1];
     __shared__ float h_val[DEDUPE ? GH_SLOTS : 1];
@@ -271,18 +182,16 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
     __shared__ int h_n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x;
-    float *s_dist = s_q + t.d + wave * 64;
-    int *s_rowp = reinterpret_cast<int *>(s_q + t.d + 256);
-    // per row (a non-empty probed group, in probe order), staged once so that wavefront 0's serial passes read LDS
-    // instead of walking a chain of dependent global loads per row: centroid, list size, alpha, ||c||^2, first local
-    // code, coarse distance, active sub-groups
-    uint32_t *s_rc = reinterpret_cast<uint32_t *>(s_rowp + nprobe);
-    uint32_t *s_rgs = s_rc + nprobe;
-    float *s_ral = reinterpret_cast<float *>(s_rgs + nprobe);
-    float *s_rcn = s_ral + nprobe;
-    uint32_t *s_rlo = reinterpret_cast<uint32_t *>(s_rcn + nprobe);
-    float *s_rqd = reinterpret_cast<float *>(s_rlo + nprobe);
-    uint32_t *s_rna = reinterpret_cast<uint32_t *>(s_rqd + nprobe);
+    const Plan4Lds lds = plan4_lds(t.d, nprobe);
+    float *s_dist = s_q + lds.dist + wave * 64;
+    int *s_rowp = reinterpret_cast<int *>(s_q + lds.row(kRowProbe));
+    uint32_t *s_rc = reinterpret_cast<uint32_t *>(s_q + lds.row(kRowCentroid));
+    uint32_t *s_rgs = reinterpret_cast<uint32_t *>(s_q + lds.row(kRowSize));
+    float *s_ral = s_q + lds.row(kRowAlpha);
+    float *s_rcn = s_q + lds.row(kRowNorm);
+    uint32_t *s_rlo = reinterpret_cast<uint32_t *>(s_q + lds.row(kRowFirstCode));
+    float *s_rqd = s_q + lds.row(kRowCoarseDist);
+    uint32_t *s_rna = reinterpret_cast<uint32_t *>(s_q + lds.row(kRowActive));
     const int nsubc = g.nsubc;
     for (int j = tid; j < k; j += 256)
         keys[(size_t)q * k + j] = kKeyInit;
@@ -319,8 +228,8 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
                 s_rc[upto - 1] = c;
                 s_rgs[upto - 1] = (uint32_t)gs;
             }
-            const unsigned long long h1 = __ballot(ne && incl >= 2 * max_codes);
-            const unsigned long long h2 = __ballot(ne && incl >= max_codes);
+            const unsigned long long h1 = __ballot(ne && plan_pass1_ends(incl, max_codes));
+            const unsigned long long h2 = __ballot(ne && plan_pass2_ends(incl, max_codes));
             if (p1 < 0 && h1)
                 p1 = __shfl(upto, __ffsll((long long)h1) - 1, 64);
             if (r2 < 0 && h2)
@@ -353,16 +262,8 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             const uint32_t c = s_rc[r];
             for (int s0 = 0; s0 < nsubc; s0 += 64) {
                 const int subc = s0 + lane;
-                if (subc < nsubc && g.sub_sizes[(size_t)c * nsubc + subc] != 0) {
-                    const uint32_t nn = g.nn_idx[(size_t)c * nsubc + subc];
-                    uint32_t slot = gh_hash(nn);
-                    for (int pr = 0; pr < GH_PROBES; pr++) {
-                        const uint32_t old = atomicCAS(&h_key[slot], GH_EMPTY, nn);
-                        if (old == GH_EMPTY || old == nn)
-                            break;
-                        slot = (slot + 1) & (GH_SLOTS - 1);
-                    }
-                }
+                if (subc < nsubc && g.sub_sizes[(size_t)c * nsubc + subc] != 0)
+                    gh_find<true>(h_key, g.nn_idx[(size_t)c * nsubc + subc]);
             }
         }
         __syncthreads();
@@ -389,9 +290,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
     for (int r = wave; r < ra; r += 4) {
         const int i = s_rowp[r];
         const uint32_t c = qc[i];
-        const float alpha = g.alphas[c];
-        const float oma = __fsub_rn(1.0f, alpha);
-        const float term1 = __fmul_rn(oma, qd[i]);
+        const GroupTerms gt = group_terms(g.alphas[c], qd[i]);
         for (int s0 = 0; s0 < nsubc; s0 += 64) {
             const int subc = s0 + lane;
             bool active = false;
@@ -404,45 +303,18 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             bool direct = active; // this pair's row is gathered here (always, without DEDUPE)
             if constexpr (DEDUPE) {
                 if (active) {
-                    uint32_t slot = gh_hash(nn);
-                    for (int pr = 0; pr < GH_PROBES; pr++) {
-                        const uint32_t kk = h_key[slot];
-                        if (kk == nn) {
-                            qn = h_val[slot];
-                            direct = false;
-                            break;
-                        }
-                        if (kk == GH_EMPTY)
-                            break;
-                        slot = (slot + 1) & (GH_SLOTS - 1);
+                    const int slot = gh_find<false>(h_key, nn);
+                    if (slot >= 0) {
+                        qn = h_val[slot];
+                        direct = false;
                     }
                 }
             }
-            {
-                const unsigned long long am = __ballot(direct);
-                const int na = __popcll(am);
-                for (int base = 0; base < na; base += 16) {
-                    const int rr = base + (lane >> 2);
-                    const int src = rr < na ? nth_set_bit(am, rr) : 0;
-                    const uint32_t nnq = (uint32_t)__shfl((int)nn, src, 64);
-                    float dq = 0.f;
-                    if (rr < na)
-                        dq = l2_ref_order_quad_batched(gr.vectors + (size_t)nnq * t.d, s_q, t.d, lane & 3);
-                    if (rr < na && (lane & 3) == 0)
-                        s_dist[src] = dq;
-                }
-                if (na) {
-                    wave_lds_order();
-                    if (direct)
-                        qn = s_dist[lane];
-                    wave_lds_order();
-                }
-            }
-            if (active && do_pruning) {
-                const float a = __fmul_rn(oma, g.inter_dists[(size_t)c * nsubc + subc]);
-                const float b = __fsub_rn(a, qn);
-                v = __fsub_rn(term1, __fmul_rn(alpha, b)); // Grouping.cpp:251-252
-            }
+            const unsigned long long am = __ballot(direct);
+            if (am)
+                qn = gather_quads<true>(direct, am, nn, qn, gr.vectors, s_q, t.d, s_dist, lane);
+            if (active && do_pruning)
+                v = group_pass1_value(gt, g.inter_dists[(size_t)c * nsubc + subc], qn);
             if (subc < nsubc) {
                 if (do_pruning)
                     qsd[(size_t)r * nsubc + subc] = v; // value-initialised 0.0 where inactive (:228)
@@ -488,14 +360,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             for (int s0 = 0; s0 < nsubc; s0 += 64) {
                 const int subc = s0 + lane;
                 const bool active = subc < nsubc && g.sub_sizes[(size_t)c * nsubc + subc] != 0;
-                const float v = active ? qsd[(size_t)r * nsubc + subc] : 0.f;
-                unsigned long long m = __ballot(active);
-                nsubgroups += __popcll(m);
-                while (m) {
-                    const int j = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    threshold = __fadd_rn(threshold, __shfl(v, j, 64));
-                }
+                threshold_add_active(threshold, nsubgroups, active, active ? qsd[(size_t)r * nsubc + subc] : 0.f);
             }
         }
         threshold = __fdiv_rn(threshold, (float)nsubgroups); // :261, 0/0 = NaN when nothing was seen
@@ -507,8 +372,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
     // one row ahead.  Written per row in the order of the loop further down, which it replaces: there, each row walked
     // five dependent global round trips -- 224 k cycles of a query's 550 k (stamps).
     if (nsubc <= 64) {
-        unsigned long long ncode = 0;
-        uint32_t ns = 0, nl = 0;
+        PlanCursor pc;
         Seg *sq = segs + (size_t)q * max_seg;
         uint32_t *lq = lpos + (size_t)q * max_seg;
         const bool inl = lane < nsubc;
@@ -533,11 +397,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             for (int r = 0; r < nrows; r++) {
                 const RowLoads nx2 = load_row(r + 2);
                 const float cn_nxt = t.centroid_norms[(inl && nxt.sz != 0) ? nxt.nn : 0u];
-                const float alpha = s_ral[r];
-                const float oma = __fsub_rn(1.0f, alpha);
-                const float term1 = __fmul_rn(oma, __fsub_rn(s_rqd[r], s_rcn[r]));
-                const uint32_t lo_c = s_rlo[r];
-                const bool owned = lo_c != kNotOwned;
+                const GroupTerms gt = group_terms(s_ral[r], ivf_cterm(s_rqd[r], s_rcn[r]));
                 const bool have = r < ra; // this row's distances are in the scratch
                 const uint32_t sz = inl ? cur.sz : 0u;
                 bool scanned = false;
@@ -548,60 +408,21 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
                 float qn2 = (scanned && have) ? cur.qn : 0.f;
                 const bool need = scanned && !have;
                 const unsigned long long am = __ballot(need);
-                if (am) { // rows beyond what the sizes promised (pass 2 ran further than pass 1): evaluated here
-                    const int na = __popcll(am);
-                    for (int base = 0; base < na; base += 16) {
-                        const int rr = base + (lane >> 2);
-                        const int src = rr < na ? nth_set_bit(am, rr) : 0;
-                        const uint32_t nnq = (uint32_t)__shfl((int)cur.nn, src, 64);
-                        float dq = 0.f;
-                        if (rr < na)
-                            dq = l2_ref_order_quad_batched(gr.vectors + (size_t)nnq * t.d, s_q, t.d, lane & 3);
-                        if (rr < na && (lane & 3) == 0)
-                            s_dist[src] = dq;
-                    }
-                    wave_lds_order();
-                    if (need)
-                        qn2 = s_dist[lane];
-                    wave_lds_order();
-                }
+                if (am) // rows beyond what the sizes promised (pass 2 ran further than pass 1): evaluated here
+                    qn2 = gather_quads<true>(need, am, cur.nn, qn2, gr.vectors, s_q, t.d, s_dist, lane);
                 float cterm = 0.f;
-                if (scanned) {
-                    const float term2 = __fmul_rn(alpha, __fsub_rn(qn2, cn_cur)); // :318
-                    cterm = __fadd_rn(term1, term2);
-                }
-                const uint32_t in_sz = wave_incl_scan(sz, lane);
-                const uint32_t in_sc = wave_incl_scan(scanned ? sz : 0u, lane);
-                const unsigned long long m = __ballot(scanned);
-                const uint32_t rank_sc = __popcll(m & ((1ull << lane) - 1ull));
-                if (scanned && owned) {
-                    Seg sg;
-                    sg.start = lo_c + (in_sz - sz);
-                    sg.len = sz;
-                    sg.vpos = (uint32_t)ncode + (in_sc - sz);
-                    sg.cterm = cterm;
-                    sq[ns + rank_sc] = sg;
-                    lq[ns + rank_sc] = nl + (in_sc - sz);
-                }
-                const uint32_t tot_sc = __shfl(in_sc, 63, 64);
-                ncode += tot_sc;
-                if (owned) {
-                    ns += (uint32_t)__popcll(m);
-                    nl += tot_sc;
-                }
-                if (ncode >= max_codes)
+                if (scanned)
+                    cterm = group_cterm(gt, qn2, cn_cur);
+                emit_segments(pc, scanned, sz, cterm, s_rlo[r], 0u, sq, lq, lane);
+                if (plan_pass2_ends(pc.ncode, max_codes))
                     break;
                 cur = nxt;
                 cn_cur = cn_nxt;
                 nxt = nx2;
             }
         }
-        if (lane == 0) {
-            PlanHdr h;
-            h.nseg = ns;
-            h.total = nl;
-            hdr[q] = h;
-        }
+        if (lane == 0)
+            store_plan_hdr(&hdr[q], pc.ns, pc.nl);
         stamp(3);
         if (stamps && threadIdx.x == 0)
             atomicAdd(&stamps[4], 1ull);
@@ -609,8 +430,7 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
     }
 
     // ---- phase C (wavefront 0): pass 2 (Grouping.cpp:283-353), distances from the scratch for the rows phase A covered
-    unsigned long long ncode = 0; // codes scored so far == scan position of the next one
-    uint32_t ns = 0, nl = 0;
+    PlanCursor cur;
     int row = 0;
     Seg *sq = segs + (size_t)q * max_seg;
     uint32_t *lq = lpos + (size_t)q * max_seg;
@@ -621,11 +441,8 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
         const unsigned long long gs = t.goff[c + 1] - t.goff[c];
         if (gs == 0)
             continue;
-        const float alpha = g.alphas[c];
-        const float oma = __fsub_rn(1.0f, alpha);
-        const float term1 = __fmul_rn(oma, __fsub_rn(qd[i], t.centroid_norms[c]));
+        const GroupTerms gt = group_terms(g.alphas[c], ivf_cterm(qd[i], t.centroid_norms[c]));
         const uint32_t lo_c = t.loff[c];
-        const bool owned = lo_c != kNotOwned;
         const bool have = row < ra; // this row's distances are in the scratch
         uint32_t list_off = 0;      // codes of this list before the current chunk of sub-groups
         for (int s0 = 0; s0 < nsubc; s0 += 64) {
@@ -645,65 +462,30 @@ __global__ __launch_bounds__(256) void plan_grouping4_kernel(IvfTables t, GroupT
             const bool need = scanned && !have;
             if (scanned && have)
                 qn2 = qnv[(size_t)row * nsubc + subc];
-            {
-                const uint32_t nn = scanned ? g.nn_idx[(size_t)c * nsubc + subc] : 0u;
-                const unsigned long long am = __ballot(need);
-                const int na = __popcll(am);
-                if (na) { // rows beyond what the sizes promised (pass 2 ran further than pass 1): evaluated here
-                    for (int base = 0; base < na; base += 16) {
-                        const int rr = base + (lane >> 2);
-                        const int src = rr < na ? nth_set_bit(am, rr) : 0;
-                        const uint32_t nnq = (uint32_t)__shfl((int)nn, src, 64);
-                        float dq = 0.f;
-                        if (rr < na)
-                            dq = l2_ref_order_quad_batched(gr.vectors + (size_t)nnq * t.d, s_q, t.d, lane & 3);
-                        if (rr < na && (lane & 3) == 0)
-                            s_dist[src] = dq;
-                    }
-                    wave_lds_order();
-                    if (need)
-                        qn2 = s_dist[lane];
-                    wave_lds_order();
-                }
-                if (scanned) {
-                    const float term2 = __fmul_rn(alpha, __fsub_rn(qn2, t.centroid_norms[nn])); // :318
-                    cterm = __fadd_rn(term1, term2);
-                }
-            }
-            const uint32_t in_sz = wave_incl_scan(sz, lane);
-            const uint32_t in_sc = wave_incl_scan(scanned ? sz : 0u, lane);
-            const unsigned long long m = __ballot(scanned);
-            const uint32_t rank_sc = __popcll(m & ((1ull << lane) - 1ull));
-            if (scanned && owned) {
-                Seg sg;
-                sg.start = lo_c + list_off + (in_sz - sz);
-                sg.len = sz;
-                sg.vpos = (uint32_t)ncode + (in_sc - sz);
-                sg.cterm = cterm;
-                sq[ns + rank_sc] = sg;
-                lq[ns + rank_sc] = nl + (in_sc - sz);
-            }
-            const uint32_t tot_sz = __shfl(in_sz, 63, 64), tot_sc = __shfl(in_sc, 63, 64);
-            list_off += tot_sz;
-            ncode += tot_sc;
-            if (owned) {
-                ns += (uint32_t)__popcll(m);
-                nl += tot_sc;
-            }
+            const uint32_t nn = scanned ? g.nn_idx[(size_t)c * nsubc + subc] : 0u;
+            const unsigned long long am = __ballot(need);
+            if (am) // rows beyond what the sizes promised (pass 2 ran further than pass 1): evaluated here
+                qn2 = gather_quads<true>(need, am, nn, qn2, gr.vectors, s_q, t.d, s_dist, lane);
+            if (scanned)
+                cterm = group_cterm(gt, qn2, t.centroid_norms[nn]);
+            list_off += emit_segments(cur, scanned, sz, cterm, lo_c, list_off, sq, lq, lane);
         }
-        if (ncode >= max_codes)
+        if (plan_pass2_ends(cur.ncode, max_codes))
             break;
         row++;
     }
-    if (lane == 0) {
-        PlanHdr h;
-        h.nseg = ns;
-        h.total = nl;
-        hdr[q] = h;
-    }
+    if (lane == 0)
+        store_plan_hdr(&hdr[q], cur.ns, cur.nl);
     stamp(3);
     if (stamps && threadIdx.x == 0)
         atomicAdd(&stamps[4], 1ull);
+}
+
+// a knob of the environment, or null where it is unset or empty
+static const char *env_knob(const char *name)
+{
+    const char *e = getenv(name);
+    return (e && *e) ? e : nullptr;
 }
 
 hipError_t launch_plan_grouping(hipStream_t s, const IvfTables &t, const GroupTables &g, const GraphTables &gr,
@@ -711,16 +493,15 @@ hipError_t launch_plan_grouping(hipStream_t s, const IvfTables &t, const GroupTa
                                 uint64_t max_codes, int do_pruning, const PlanView &p, uint64_t *keys, int k,
                                 float *scratch)
 {
-    const auto [segs, lpos, hdr, max_seg, nq] = p;
-    if (nq == 0)
+    if (p.nq == 0)
         return hipSuccess;
-    // IVFHNSW_PLAN_GROUP4=0: the one-wavefront-per-query form (A/B runs)
+    // the knobs are read once per process.  IVFHNSW_PLAN_GROUP4=0: the one-wavefront-per-query form (A/B runs)
     static const bool four = [] {
-        const char *e = getenv("IVFHNSW_PLAN_GROUP4");
-        return !(e && *e && atoi(e) == 0);
+        const char *e = env_knob("IVFHNSW_PLAN_GROUP4");
+        return !(e && atoi(e) == 0);
     }();
     static unsigned long long *d_st = [] {
-        const char *e = getenv("IVFHNSW_PLAN_STAMPS");
+        const char *e = env_knob("IVFHNSW_PLAN_STAMPS");
         unsigned long long *p = nullptr;
         if (e && atoi(e) == 1 && hipMalloc(&p, 8 * sizeof(unsigned long long)) == hipSuccess) {
             (void)hipMemset(p, 0, 8 * sizeof(unsigned long long));
@@ -737,23 +518,25 @@ hipError_t launch_plan_grouping(hipStream_t s, const IvfTables &t, const GroupTa
     }();
     // IVFHNSW_PLAN_DEDUPE=0 / 1 overrides what upload_grouping measured on the index's neighbour lists (g.dedupe)
     static const int dedupe_knob = [] {
-        const char *e = getenv("IVFHNSW_PLAN_DEDUPE");
-        return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1;
+        const char *e = env_knob("IVFHNSW_PLAN_DEDUPE");
+        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
     }();
     const bool dedupe = dedupe_knob < 0 ? g.dedupe != 0 : dedupe_knob == 1;
-    const size_t shm4 = (size_t)(t.d + 256) * sizeof(float) + (size_t)nprobe * 8 * sizeof(int);
-    if (four && dedupe)
-        hipLaunchKernelGGL(plan_grouping4_kernel<true>, dim3(nq), dim3(256), shm4, s, t, g, gr, xq, coarse_ids,
-                           coarse_dists, nq, nprobe, (unsigned long long)max_codes, do_pruning, segs, lpos, hdr, max_seg,
-                           reinterpret_cast<unsigned long long *>(keys), k, scratch, d_st);
-    else if (four)
-        hipLaunchKernelGGL(plan_grouping4_kernel<false>, dim3(nq), dim3(256), shm4, s, t, g, gr, xq, coarse_ids,
-                           coarse_dists, nq, nprobe, (unsigned long long)max_codes, do_pruning, segs, lpos, hdr, max_seg,
-                           reinterpret_cast<unsigned long long *>(keys), k, scratch, d_st);
+    auto *k64 = reinterpret_cast<unsigned long long *>(keys);
+    const auto launch4 = [&](auto dedupe_c) {
+        hipLaunchKernelGGL(plan_grouping4_kernel<decltype(dedupe_c)::value>, dim3(p.nq), dim3(256),
+                           plan4_lds(t.d, nprobe).bytes(), s, t, g, gr, xq, coarse_ids, coarse_dists, p.nq, nprobe,
+                           (unsigned long long)max_codes, do_pruning, p.segs, p.lpos, p.hdr, p.max_seg, k64, k, scratch,
+                           d_st);
+    };
+    if (!four)
+        hipLaunchKernelGGL(plan_grouping_kernel, dim3(p.nq), dim3(64), (t.d + 64) * sizeof(float), s, t, g, gr, xq,
+                           coarse_ids, coarse_dists, p.nq, nprobe, (unsigned long long)max_codes, do_pruning, p.segs,
+                           p.lpos, p.hdr, p.max_seg, k64, k, scratch);
+    else if (dedupe)
+        launch4(std::true_type());
     else
-        hipLaunchKernelGGL(plan_grouping_kernel, dim3(nq), dim3(64), (t.d + 64) * sizeof(float), s, t, g, gr, xq,
-                           coarse_ids, coarse_dists, nq, nprobe, (unsigned long long)max_codes, do_pruning, segs, lpos, hdr,
-                           max_seg, reinterpret_cast<unsigned long long *>(keys), k, scratch);
+        launch4(std::false_type());
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // Float contract (see DESIGN.md "Numerics"): every arithmetic step is an explicit round-to-nearest
 // intrinsic in the order the reference's source evaluates it; this file is built with
 // -ffp-contract=off so nothing else gets fused either.
+#include "plan_steps.h"
 #include "scan_steps.h"
 #include "sweep_steps.h"
 
@@ -178,8 +179,8 @@ hipError_t launch_lut(hipStream_t s, const IvfTables &t, const float *xq, float 
 // the list that makes ncode >= max_codes.  Depends only on coarse results and list sizes, never on
 // codes, so it is computed up front and the scan itself is order-free.
 // ---------------------------------------------------------------------------------------------
-// One wavefront per query, lanes over the probes (chunks of 64): list sizes in parallel, the max_codes prefix
-// rule by a wave scan -- list i is scored iff fewer than max_codes codes precede it in probe order.
+// One wavefront per query, lanes over the probes (chunks of 64, ivf_plan_chunk in plan_steps.h): list sizes in parallel,
+// the max_codes prefix rule by a wave scan -- list i is scored iff fewer than max_codes codes precede it in probe order.
 __device__ __forceinline__ void plan_ivf_body(int bid, const IvfTables &t, const uint32_t *__restrict__ cid,
                                               const float *__restrict__ cd, int nq, int nprobe,
                                               unsigned long long max_codes, Seg *__restrict__ segs,
@@ -192,50 +193,12 @@ __device__ __forceinline__ void plan_ivf_body(int bid, const IvfTables &t, const
         return;
     for (int j = lane; j < k; j += 64)
         keys[(size_t)q * k + j] = kKeyInit;
-    unsigned long long ncode = 0; // codes of the lists visited so far (wave-uniform)
-    uint32_t nl = 0, ns = 0;
-    Seg *sq = segs + (size_t)q * max_seg;
-    uint32_t *lq = lpos + (size_t)q * max_seg;
-    for (int base = 0; base < nprobe && (ncode < max_codes || ncode == 0); base += 64) {
-        const int i = base + lane;
-        uint32_t c = 0xffffffffu;
-        if (i < nprobe)
-            c = cid[(size_t)q * nprobe + i];
-        const bool ok = c < t.nc; // padding slots (fewer than nprobe coarse results) hold 0xffffffff
-        unsigned long long n = 0;
-        if (ok)
-            n = t.goff[c + 1] - t.goff[c];
-        const unsigned long long incl = wave_incl_scan_u64(n, lane) + ncode;
-        const unsigned long long excl = incl - n;
-        // the check follows the scoring (IndexIVF_HNSW.cpp:290-292): the first non-empty list is always scored
-        const bool take = n != 0 && (excl < max_codes || excl == 0);
-        const uint32_t lo_c = take ? t.loff[c] : kNotOwned;
-        const bool owned = lo_c != kNotOwned;
-        const unsigned long long om = __ballot(owned);
-        const unsigned long long own_incl = wave_incl_scan_u64(owned ? n : 0ull, lane);
-        if (owned) {
-            const uint32_t r = ns + (uint32_t)__popcll(om & ((1ull << lane) - 1ull));
-            Seg sg;
-            sg.start = lo_c;
-            sg.len = (uint32_t)n;
-            sg.vpos = (uint32_t)excl;
-            sg.cterm = __fsub_rn(cd[(size_t)q * nprobe + i], t.centroid_norms[c]);
-            sq[r] = sg;
-            lq[r] = nl + (uint32_t)(own_incl - n);
-        }
-        ns += (uint32_t)__popcll(om);
-        nl += (uint32_t)__shfl(own_incl, 63, 64);
-        // codes visited: everything up to and including the list that reached max_codes
-        const unsigned long long stop = __ballot(take && incl >= max_codes);
-        const int last = stop ? __ffsll((long long)stop) - 1 : 63;
-        ncode = __shfl(incl, last, 64);
-    }
-    if (lane == 0) {
-        PlanHdr h;
-        h.nseg = ns;
-        h.total = nl;
-        hdr[q] = h;
-    }
+    PlanCursor cur;
+    for (int base = 0; base < nprobe && plan_budget_open(cur.ncode, max_codes); base += 64)
+        ivf_plan_chunk(cur, t, cid + (size_t)q * nprobe, cd + (size_t)q * nprobe, base, nprobe, max_codes,
+                       segs + (size_t)q * max_seg, lpos + (size_t)q * max_seg, lane);
+    if (lane == 0)
+        store_plan_hdr(&hdr[q], cur.ns, cur.nl);
 }
 
 __global__ __launch_bounds__(256) void plan_ivf_kernel(IvfTables t, const uint32_t *__restrict__ cid,

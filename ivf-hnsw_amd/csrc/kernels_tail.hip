@@ -11,6 +11,7 @@
 //
 // keys_inv[q] holds the bitwise complement of the best key (atomicMax; 0 = nothing yet, so a plain memset initialises
 // it), done[q] counts finished workgroups of query q.
+#include "plan_steps.h"
 #include "scan_steps.h"
 
 #include <float.h>
@@ -47,42 +48,14 @@ __global__ __launch_bounds__(256) void ivf_tail_kernel(IvfTables t, const float 
         s_x[tid] = xq[(size_t)q * D + tid];
     s_norm[tid] = t.norm_table[tid];
     if (wave == 0) {
-        uint32_t c = 0xffffffffu;
-        if (lane < nprobe)
-            c = cid[(size_t)q * nprobe + lane];
-        const bool ok = c < t.nc;
-        unsigned long long n = 0;
-        if (ok)
-            n = t.goff[c + 1] - t.goff[c];
-        const unsigned long long incl = wave_incl_scan_u64(n, lane);
-        const unsigned long long excl = incl - n;
-        // the check follows the scoring (IndexIVF_HNSW.cpp:290-292): the first non-empty list is always scored
-        const bool take = n != 0 && (excl < max_codes || excl == 0);
-        const uint32_t lo_c = take ? t.loff[c] : kNotOwned;
-        const bool owned = lo_c != kNotOwned;
-        const unsigned long long om = __ballot(owned);
-        const unsigned long long own_incl = wave_incl_scan_u64(owned ? n : 0ull, lane);
-        if (owned) {
-            const uint32_t r = (uint32_t)__popcll(om & ((1ull << lane) - 1ull));
-            Seg sg;
-            sg.start = lo_c;
-            sg.len = (uint32_t)n;
-            sg.vpos = (uint32_t)excl;
-            sg.cterm = __fsub_rn(cd[(size_t)q * nprobe + lane], t.centroid_norms[c]);
-            s_seg[r] = sg;
-            s_lpos[r] = (uint32_t)(own_incl - n);
-        }
-        const uint32_t ns = (uint32_t)__popcll(om);
-        const uint32_t nl = (uint32_t)__shfl(own_incl, 63, 64);
+        PlanCursor cur;
+        ivf_plan_chunk(cur, t, cid + (size_t)q * nprobe, cd + (size_t)q * nprobe, 0, nprobe, max_codes, s_seg, s_lpos, lane);
+        const uint32_t ns = cur.ns, nl = cur.nl;
         if (lane == 0) {
             s_nseg = ns;
             s_lpos[ns] = nl;
-            if (split == 0 && hdr_out) { // the accounting of ivfhnsw_gpu_last_scan_counts
-                PlanHdr h;
-                h.nseg = ns;
-                h.total = nl;
-                hdr_out[q] = h;
-            }
+            if (split == 0 && hdr_out) // the accounting of ivfhnsw_gpu_last_scan_counts
+                store_plan_hdr(&hdr_out[q], ns, nl);
         }
     }
     __syncthreads();
