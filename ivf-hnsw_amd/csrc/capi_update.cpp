@@ -2,6 +2,49 @@
 #include "capi_internal.h"
 
 // ---------------------------------------------------------------------------------------------------------------
+// what the three cores share
+
+// One device word as a kernel's answer: the word is set to `init` bytes, `launch(word)` puts its work on the handle's
+// stream, and the word comes back in *out.  Returns with the stream drained.
+template <class Launch> static int run_with_word(ivfhnsw_gpu *h, DevBuf &word, int init, Launch &&launch, uint32_t *out)
+{
+    int rc;
+    if ((rc = word.ensure(sizeof(uint32_t))))
+        return rc;
+    HIP_TRY(hipMemsetAsync(word.p, init, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch(word.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(out, word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+// The tail of an update, behind the last launch that fills `fresh` (e = the launches' status): the stream is drained,
+// the handle's filter is judged over the new ids, and only then do the new arrays replace the old ones -- every error up
+// to that point leaves the handle's tables the ones it had.  new_sizes (Grouping handles; null otherwise) = the staging
+// that holds the new sub-group sizes: the choice upload_grouping derives from the sizes and the neighbour rows follows
+// them (its workspace was reserved by the caller, grouping_dedupe_reserve, before the first new byte was written), and
+// the staging becomes the table, the old table the next call's staging.
+static int commit_lists(ivfhnsw_gpu *h, const char *who, hipError_t e, ListArrays &fresh, uint64_t n_local2, DevBuf *new_sizes)
+{
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    int rc, dedupe = h->g.dedupe;
+    if (new_sizes && (rc = grouping_dedupe_dev(h, new_sizes->as<uint32_t>(), h->g.nn_idx, &dedupe)))
+        return rc;
+    if ((rc = fresh.mark_filter(h, n_local2)))
+        return rc;
+    fresh.install(h, n_local2);
+    if (new_sizes) {
+        std::swap(h->g_sizes, *new_sizes);
+        h->g.sub_sizes = h->g_sizes.as<uint32_t>();
+        h->g.dedupe = dedupe;
+    }
+    return IVFHNSW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // appends to the lists the handle holds: the new CSR is built beside the old one and swapped in
 static int append_state(ivfhnsw_gpu *h, const char *who)
 {
@@ -31,41 +74,51 @@ static int append_stage(ivfhnsw_gpu *h, size_t n)
     return IVFHNSW_OK;
 }
 
-static int bits_of(size_t top) // key bits of a radix sort over 0..top
+// a host batch into the staging (sub_idx null: IVFADC lists)
+static int stage_batch(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *sub_idx, const uint32_t *ids,
+                       const uint8_t *codes, const uint8_t *norm_codes)
 {
-    int b = 1;
-    while (b < 32 && top >> b)
-        b++;
-    return b;
+    int rc;
+    if ((rc = append_stage(h, n)) || (sub_idx && (rc = h->gp_sub.ensure(n * sizeof(uint32_t)))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->ap_idx.p, list_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (sub_idx)
+        HIP_TRY(hipMemcpyAsync(h->gp_sub.p, sub_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_codes.p, codes, n * h->t.M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ap_ncodes.p, norm_codes, n, hipMemcpyHostToDevice, h->stream));
+    return IVFHNSW_OK;
 }
 
-// The first step of both append cores.  The batch's rows are counted per list (d_sub null: launch_append_count) or per
-// list and sub-group (launch_grouping_count; sizes2 starts as a copy of the handle's sizes), launch_append_tables scans
-// the counts into the new lists' starts (ap_cnt, ap_own), and the id check's flag and the new total come to the host.
-// Returns with the stream drained and the handle's tables untouched.
+// The first step of both append cores.  The batch's rows are counted per list, with d_sub per list and sub-group too
+// (sizes2 starts as a copy of the handle's sizes), launch_append_tables scans the counts into the new lists' starts
+// (ap_cnt, ap_own), and the id check's flag and the new total come to the host.  Returns with the stream drained and the
+// handle's tables untouched.
 static int append_count(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list, const uint32_t *d_sub, uint32_t *sizes2,
                         bool *bad_id, uint64_t *n_local2)
 {
     const size_t nc = h->t.nc, len = nc + 1;
+    const uint32_t nsubc = d_sub ? (uint32_t)h->g.nsubc : 0u;
     int rc;
     if ((rc = h->ap_cnt.ensure(len * sizeof(uint32_t))) || (rc = h->ap_own.ensure(len * sizeof(uint32_t))) ||
-        (rc = h->ap_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) || (rc = h->ap_status.ensure(sizeof(uint32_t))))
+        (rc = h->ap_part.ensure(append_scan_parts(len) * sizeof(uint32_t))))
         return rc;
-    uint32_t *cnt = h->ap_cnt.as<uint32_t>(), *own = h->ap_own.as<uint32_t>(), *status = h->ap_status.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(cnt, 0, len * sizeof(uint32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), h->stream));
-    if (d_sub) {
-        const uint32_t nsubc = (uint32_t)h->g.nsubc;
-        HIP_TRY(hipMemcpyAsync(sizes2, h->g.sub_sizes, nc * nsubc * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(launch_grouping_count(h->stream, d_list, d_sub, n, (uint32_t)nc, nsubc, cnt, sizes2, status));
-    } else {
-        HIP_TRY(launch_append_count(h->stream, d_list, n, (uint32_t)nc, cnt, status));
-    }
-    HIP_TRY(launch_append_tables(h->stream, h->t, cnt, own, h->ap_part.as<uint32_t>()));
+    uint32_t *cnt = h->ap_cnt.as<uint32_t>(), *own = h->ap_own.as<uint32_t>();
     uint32_t st = 0, total = 0;
-    HIP_TRY(hipMemcpyAsync(&st, status, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(&total, own + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    rc = run_with_word(h, h->ap_status, 0, [&](uint32_t *status) -> hipError_t {
+        hipError_t e = hipMemsetAsync(cnt, 0, len * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess && d_sub)
+            e = hipMemcpyAsync(sizes2, h->g.sub_sizes, nc * nsubc * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess)
+            e = launch_append_count(h->stream, d_list, d_sub, n, (uint32_t)nc, nsubc, cnt, d_sub ? sizes2 : nullptr, status);
+        if (e == hipSuccess)
+            e = launch_append_tables(h->stream, h->t, cnt, own, h->ap_part.as<uint32_t>());
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&total, own + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+        return e;
+    }, &st);
+    if (rc)
+        return rc;
     *bad_id = st != 0;
     *n_local2 = total;
     return IVFHNSW_OK;
@@ -78,7 +131,7 @@ static int append_workspace(ivfhnsw_gpu *h, size_t n, uint64_t n_local2)
     int rc;
     if ((rc = h->ap_perm.ensure(n * sizeof(uint32_t))) || (rc = h->ap_perm2.ensure(n * sizeof(uint32_t))) ||
         (rc = h->ap_hist.ensure(256 * nblocks * sizeof(uint32_t))) ||
-        (rc = h->ap_tiles.ensure((n_local2 / kAppendTileRows + 2) * sizeof(uint32_t))))
+        (rc = h->ap_tiles.ensure(append_tile_words(n_local2, kAppendTileRows) * sizeof(uint32_t))))
         return rc;
     return IVFHNSW_OK;
 }
@@ -103,23 +156,18 @@ static int append_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const ui
     ListArrays fresh;
     if ((rc = fresh.allocate(nc, n_local2, h->t.M)))
         return rc;
-    uint32_t *perm = nullptr;
+    const NewLists nl = fresh.view(n_local2);
+    uint32_t *perm = nullptr, *tiles = h->ap_tiles.as<uint32_t>();
     const uint32_t *nstart = h->ap_cnt.as<uint32_t>(), *lstart = h->ap_own.as<uint32_t>(); // scanned in place by launch_append_tables
     hipError_t e = launch_sort_by_key(h->stream, d_idx, n, bits_of(nc - 1), h->ap_perm.as<uint32_t>(),
                                       h->ap_perm2.as<uint32_t>(), h->ap_hist.as<uint32_t>(), &perm);
     if (e == hipSuccess)
-        e = launch_append_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), fresh.view(n_local2));
+        e = launch_append_layout(h->stream, h->t, nstart, lstart, tiles, nl);
     if (e == hipSuccess)
-        e = launch_append_scatter(h->stream, h->t, perm, d_idx, n, nstart, lstart, d_codes, d_ncodes, d_ids,
-                                  fresh.view(n_local2));
+        e = launch_append_merge(h->stream, h->t, nstart, lstart, tiles, nullptr, nl);
     if (e == hipSuccess)
-        e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append: %s", hipGetErrorString(e));
-    if ((rc = fresh.mark_filter(h, n_local2)))
-        return rc;
-    fresh.install(h, n_local2);
-    return IVFHNSW_OK;
+        e = launch_append_scatter(h->stream, h->t, perm, d_idx, n, nstart, lstart, nullptr, d_codes, d_ncodes, d_ids, nl);
+    return commit_lists(h, "append", e, fresh, n_local2, nullptr);
 }
 
 int ivfhnsw_gpu_append_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *ids, const uint8_t *codes,
@@ -135,12 +183,8 @@ int ivfhnsw_gpu_append_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, c
     for (size_t i = 0; i < n; i++)
         if (list_idx[i] >= h->t.nc)
             return fail(IVFHNSW_ERR_INVALID, "append_ivf: list_idx[%zu] = %u, nc = %u", i, list_idx[i], h->t.nc);
-    if ((rc = append_stage(h, n)))
+    if ((rc = stage_batch(h, n, list_idx, nullptr, ids, codes, norm_codes)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(h->ap_idx.p, list_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_codes.p, codes, n * h->t.M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_ncodes.p, norm_codes, n, hipMemcpyHostToDevice, h->stream));
     return append_core(h, n, h->ap_idx.as<uint32_t>(), h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(),
                        h->ap_ncodes.as<uint8_t>());
 }
@@ -203,13 +247,11 @@ static int add_impl(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *pi
         }
         HIP_TRY(hipMemcpyAsync(sidx, pidx, n * sizeof(uint32_t), in, h->stream));
         if (dev) { // before the encoder reads a centroid row by it
-            if ((rc = h->ap_status.ensure(sizeof(uint32_t))))
-                return rc;
             uint32_t st = 0;
-            HIP_TRY(hipMemsetAsync(h->ap_status.p, 0, sizeof(uint32_t), h->stream));
-            HIP_TRY(launch_append_count(h->stream, sidx, n, h->t.nc, nullptr, h->ap_status.as<uint32_t>()));
-            HIP_TRY(hipMemcpyAsync(&st, h->ap_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
+            if ((rc = run_with_word(h, h->ap_status, 0, [&](uint32_t *status) {
+                     return launch_append_count(h->stream, sidx, nullptr, n, h->t.nc, 0u, nullptr, nullptr, status);
+                 }, &st)))
+                return rc;
             if (st)
                 return fail(IVFHNSW_ERR_INVALID, "%s: a precomputed_idx is >= nc = %u", who, h->t.nc);
         }
@@ -320,38 +362,25 @@ try {
         return rc;
     const NewLists nl = fresh.view(n_local2);
     // stable order by (list, sub-group): by sub-group first, then from that order by list
-    uint32_t *perm = nullptr;
+    uint32_t *perm = nullptr, *tiles = h->ap_tiles.as<uint32_t>();
     const uint32_t *nstart = h->ap_cnt.as<uint32_t>(), *lstart = h->ap_own.as<uint32_t>(); // scanned in place by launch_append_tables
-    const uint32_t *pre_old = h->gp_pre_old.as<uint32_t>(), *pre_new = h->gp_pre_new.as<uint32_t>();
     uint32_t *pa = h->ap_perm.as<uint32_t>(), *pb = h->ap_perm2.as<uint32_t>(), *hist = h->ap_hist.as<uint32_t>();
+    const SubGroups sg{(uint32_t)nsubc, d_sub, h->g.sub_sizes, h->gp_pre_old.as<uint32_t>(), h->gp_pre_new.as<uint32_t>()};
     hipError_t e = write_rows();
     if (e == hipSuccess)
         e = launch_sort_by_key(h->stream, d_sub, n, bits_of(nsubc - 1), pa, pb, hist, &perm);
     if (e == hipSuccess)
         e = launch_sort_by_key_from(h->stream, d_list, n, bits_of(nc - 1), perm, pa, pb, hist, &perm);
     if (e == hipSuccess)
-        e = launch_append_layout(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), nl);
+        e = launch_append_layout(h->stream, h->t, nstart, lstart, tiles, nl);
     if (e == hipSuccess)
-        e = launch_grouping_prefix(h->stream, nstart, h->g.sub_sizes, sizes2, h->gp_pre_old.as<uint32_t>(),
-                                   h->gp_pre_new.as<uint32_t>(), (uint32_t)nc, (uint32_t)nsubc);
+        e = launch_grouping_prefix(h->stream, nstart, sg.sizes, sizes2, h->gp_pre_old.as<uint32_t>(),
+                                   h->gp_pre_new.as<uint32_t>(), (uint32_t)nc, sg.nsubc);
     if (e == hipSuccess)
-        e = launch_grouping_merge(h->stream, h->t, nstart, lstart, h->ap_tiles.as<uint32_t>(), pre_old, pre_new,
-                                  (uint32_t)nsubc, nl);
+        e = launch_append_merge(h->stream, h->t, nstart, lstart, tiles, &sg, nl);
     if (e == hipSuccess)
-        e = launch_grouping_scatter(h->stream, h->t, perm, d_list, d_sub, n, nstart, lstart, h->g.sub_sizes, pre_old,
-                                    (uint32_t)nsubc, d_codes, d_ncodes, d_ids, nl);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "append_grouping: %s", hipGetErrorString(e));
-    // the choice upload_grouping derives from the sizes and the neighbour rows follows the new ones
-    if ((rc = grouping_dedupe_dev(h, sizes2, h->g.nn_idx, &dedupe)) || (rc = fresh.mark_filter(h, n_local2)))
-        return rc;
-    fresh.install(h, n_local2);
-    std::swap(h->g_sizes, h->gp_sizes); // the staging that holds the new sizes becomes the table
-    h->g.sub_sizes = h->g_sizes.as<uint32_t>();
-    h->g.dedupe = dedupe;
-    return IVFHNSW_OK;
+        e = launch_append_scatter(h->stream, h->t, perm, d_list, n, nstart, lstart, &sg, d_codes, d_ncodes, d_ids, nl);
+    return commit_lists(h, "append_grouping", e, fresh, n_local2, &h->gp_sizes);
 } catch (const std::bad_alloc &) {
     return fail(IVFHNSW_ERR_NOMEM, "append_grouping: host allocation failed");
 }
@@ -370,13 +399,8 @@ int ivfhnsw_gpu_append_grouping(ivfhnsw_gpu *h, size_t n, const uint32_t *list_i
         if (list_idx[i] >= h->t.nc || sub_idx[i] >= (uint32_t)h->g.nsubc)
             return fail(IVFHNSW_ERR_INVALID, "append_grouping: (list_idx, sub_idx)[%zu] = (%u, %u), nc = %u, nsubc = %d", i,
                         list_idx[i], sub_idx[i], h->t.nc, h->g.nsubc);
-    if ((rc = append_stage(h, n)) || (rc = h->gp_sub.ensure(n * sizeof(uint32_t))))
+    if ((rc = stage_batch(h, n, list_idx, sub_idx, ids, codes, norm_codes)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(h->ap_idx.p, list_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->gp_sub.p, sub_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_codes.p, codes, n * h->t.M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ap_ncodes.p, norm_codes, n, hipMemcpyHostToDevice, h->stream));
     return grouping_append_core(h, n, h->ap_idx.as<uint32_t>(), h->gp_sub.as<uint32_t>(), h->ap_ids.as<uint32_t>(),
                                 h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>(), nullptr);
 }
@@ -456,10 +480,10 @@ try {
     HIP_TRY(hipMemcpyAsync(h->ga_off.p, offsets, (ngroups + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     // a group that holds codes cannot be added to: its alpha and neighbours would be overwritten under them
     uint32_t first = 0xffffffffu;
-    HIP_TRY(hipMemsetAsync(h->ga_status.p, 0xff, sizeof(uint32_t), h->stream));
-    HIP_TRY(launch_groups_empty(h->stream, h->t.goff, h->ga_cidx.as<uint32_t>(), ngroups, (uint32_t)nc, h->ga_status.as<uint32_t>()));
-    HIP_TRY(hipMemcpyAsync(&first, h->ga_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = run_with_word(h, h->ga_status, 0xff, [&](uint32_t *status) {
+             return launch_groups_empty(h->stream, h->t.goff, h->ga_cidx.as<uint32_t>(), ngroups, (uint32_t)nc, status);
+         }, &first)))
+        return rc;
     if (first != 0xffffffffu)
         return fail(IVFHNSW_ERR_STATE, "%s: list %u (group %u of the call) already holds codes; a second add_group on a "
                     "centroid has no counterpart in a search (remove its ids first)", who, centroid_idx[first], first);
@@ -523,12 +547,12 @@ static int remove_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint3
 try {
     const size_t nc = h->t.nc, len = nc + 1;
     const uint64_t n_local = h->n_local;
-    const size_t ntiles = (size_t)((n_local + kRemoveTileRows - 1) / kRemoveTileRows);
+    const size_t ntiles = update_tiles(n_local, kRemoveTileRows);
     const bool grp = h->has_group;
     const size_t nsub = grp ? nc * (size_t)h->g.nsubc : 0;
     int rc;
     if ((rc = h->rm_bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))) ||
-        (rc = h->rm_mask.ensure(std::max<size_t>(ntiles, 1) * (kRemoveTileRows / 64) * sizeof(uint64_t))) ||
+        (rc = h->rm_mask.ensure(remove_mask_words(ntiles, kRemoveTileRows) * sizeof(uint64_t))) ||
         (rc = h->rm_keep.ensure((ntiles + 1) * sizeof(uint32_t))) || (rc = h->rm_rem.ensure(len * sizeof(uint32_t))) ||
         (rc = h->rm_part.ensure(append_scan_parts(std::max(len, ntiles + 1)) * sizeof(uint32_t))) ||
         (rc = h->rm_sizes.ensure(nsub * sizeof(uint32_t))))
@@ -557,24 +581,8 @@ try {
     ListArrays fresh;
     if ((rc = fresh.allocate(nc, n_local2, h->t.M)) || (grp && (rc = grouping_dedupe_reserve(h))))
         return rc;
-    hipError_t e = launch_remove_compact(h->stream, h->t, n_local, mask, rem, keep, fresh.view(n_local2));
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? IVFHNSW_ERR_NOMEM : IVFHNSW_ERR_HIP, "remove_ids: %s", hipGetErrorString(e));
-    // Grouping: the choice upload_grouping derives from the sizes follows the new ones
-    int dedupe = h->g.dedupe;
-    if (grp && (rc = grouping_dedupe_dev(h, h->rm_sizes.as<uint32_t>(), h->g.nn_idx, &dedupe)))
-        return rc;
-    if ((rc = fresh.mark_filter(h, n_local2)))
-        return rc;
-    fresh.install(h, n_local2);
-    if (grp) { // the staging that holds the new sizes becomes the table; the old table the next call's staging
-        std::swap(h->g_sizes, h->rm_sizes);
-        h->g.sub_sizes = h->g_sizes.as<uint32_t>();
-        h->g.dedupe = dedupe;
-    }
-    return IVFHNSW_OK;
+    const hipError_t e = launch_remove_compact(h->stream, h->t, n_local, mask, rem, keep, fresh.view(n_local2));
+    return commit_lists(h, "remove_ids", e, fresh, n_local2, grp ? &h->rm_sizes : nullptr);
 } catch (const std::bad_alloc &) {
     return fail(IVFHNSW_ERR_NOMEM, "remove_ids: host allocation failed");
 }
@@ -626,13 +634,10 @@ int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
         }
         return IVFHNSW_OK;
     }
-    if ((rc = h->rm_status.ensure(sizeof(uint32_t))))
-        return rc;
     uint32_t mx = 0;
-    HIP_TRY(hipMemsetAsync(h->rm_status.p, 0, sizeof(uint32_t), h->stream));
-    HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->rm_status.as<uint32_t>()));
-    HIP_TRY(hipMemcpyAsync(&mx, h->rm_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = run_with_word(h, h->rm_status, 0, [&](uint32_t *out) { return launch_remove_max(h->stream, d_labels, n, out); },
+                            &mx)))
+        return rc;
     uint64_t removed = 0;
     if ((rc = remove_core(h, n, d_labels, mx, &removed, d_removed_per_list)))
         return rc;

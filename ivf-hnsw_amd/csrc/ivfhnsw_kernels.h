@@ -8,6 +8,7 @@
 
 #include "scan_dispatch.h"
 #include "sweep_plan_math.h"
+#include "update_math.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -352,23 +353,36 @@ inline int exact_range_map_words(size_t nx, int nsplit, int map_shift) { return 
 hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
                               int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
                               int map_shift, float *dist, int64_t *labels, size_t out_cap);
-// appends to the inverted lists (kernels_append.hip).  count: cnt[idx[i]] += 1 (cnt may be null: check
-// only), an id >= nc raises *status.  tables: own[c] = old length + cnt[c] of the owned lists, then cnt and own ([nc + 1]
-// each, slot nc zero) become their exclusive scans nstart / lstart in place; part: append_scan_parts(nc + 1) words.
-// merge: nl.goff / nl.loff and the old rows into the new arrays nl (tile_first: nl.n_local / kAppendTileRows + 2 words).
-// scatter: the batch's rows (perm = the ids sorted by list, stably) to the ends of their lists; runs after merge.
+// appends to the inverted lists (kernels_append.hip) and to the sub-groups of Grouping lists (3.12); the
+// arithmetic and the workspace sizes are update_math.h's.  count: cnt[list_idx[i]] += 1 and, with sub_idx, sizes2[list][sub]
+// += 1 (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  tables: own[c] = old length +
+// cnt[c] of the owned lists, then cnt and own ([nc + 1] each, slot nc zero) become their exclusive scans nstart / lstart in
+// place; part: append_scan_parts(nc + 1) words.  layout: nl.goff / nl.loff and tile_first (append_tile_words words).
+// merge, after layout: the old rows into the new arrays nl.  scatter, after merge: the batch's rows (perm = the ids sorted
+// stably by list, or by (list, sub-group)) behind the old rows of their lists or sub-groups.  sg null: IVFADC lists.
 constexpr int kAppendTileRows = 2048;
-size_t append_scan_parts(size_t len);
-hipError_t launch_append_count(hipStream_t s, const uint32_t *idx, size_t n, uint32_t nc, uint32_t *cnt, uint32_t *status);
+struct SubGroups { // a Grouping append: the batch's sub-group ids, the old sizes table, and launch_grouping_prefix's sums
+    uint32_t nsubc;
+    const uint32_t *sub_idx, *sizes, *pre_old, *pre_new;
+};
+hipError_t launch_append_count(hipStream_t s, const uint32_t *list_idx, const uint32_t *sub_idx, size_t n, uint32_t nc,
+                               uint32_t nsubc, uint32_t *cnt, uint32_t *sizes2, uint32_t *status);
 hipError_t launch_append_tables(hipStream_t s, const IvfTables &t, uint32_t *cnt, uint32_t *own, uint32_t *part);
-hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                               uint32_t *tile_first, const NewLists &nl);
-hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *idx, size_t n,
-                                 const uint32_t *nstart, const uint32_t *lstart, const uint8_t *codes, const uint8_t *norm_codes,
-                                 const uint32_t *ids, const NewLists &nl);
-// the first half of merge alone (nl.goff / nl.loff and tile_first), for a caller with a merge kernel of its own
 hipError_t launch_append_layout(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
                                 uint32_t *tile_first, const NewLists &nl);
+hipError_t launch_append_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
+                               const uint32_t *tile_first, const SubGroups *sg, const NewLists &nl);
+hipError_t launch_append_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx, size_t n,
+                                 const uint32_t *nstart, const uint32_t *lstart, const SubGroups *sg, const uint8_t *codes,
+                                 const uint8_t *norm_codes, const uint32_t *ids, const NewLists &nl);
+// prefix, after tables: pre_old / pre_new [nc * nsubc] = exclusive prefix sums of sizes / sizes2 inside every list the
+// batch touches (kernels_add_groups.hip)
+hipError_t launch_grouping_prefix(hipStream_t s, const uint32_t *nstart, const uint32_t *sizes, const uint32_t *sizes2,
+                                  uint32_t *pre_old, uint32_t *pre_new, uint32_t nc, uint32_t nsubc);
+// nl.goff / nl.loff from the exclusive scan delta of the rows each list gains (grow) or loses; lstart: the new local starts
+// of an append, null = they move by delta too (a removal)
+hipError_t launch_update_offsets(hipStream_t s, const IvfTables &t, const uint32_t *delta, const uint32_t *lstart, bool grow,
+                                 const NewLists &nl);
 // exclusive scan of a [len] in place with the scan above; part: append_scan_parts(len) words
 hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part);
 // removal by label from an unsharded handle (kernels_remove.hip).  max: atomicMax of the labels into
@@ -393,22 +407,7 @@ hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, u
 // rows that pass.
 hipError_t launch_filter_mark(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
                               int deny, unsigned long long *mask, unsigned long long *count);
-// additions to a Grouping index (kernels_add_groups.hip).  count: cnt[list] += 1 and sizes2[list][sub] += 1
-// (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  prefix, after launch_append_tables:
-// pre_old / pre_new [nc * nsubc] = exclusive prefix sums of sizes / sizes2 inside every list the batch touches.  merge,
-// after launch_append_layout: the old rows into the new arrays.  scatter: the batch's rows (perm = the ids sorted stably by
-// (list, sub-group)) behind the old rows of their sub-groups; runs after merge.
-hipError_t launch_grouping_count(hipStream_t s, const uint32_t *list_idx, const uint32_t *sub_idx, size_t n, uint32_t nc,
-                                 uint32_t nsubc, uint32_t *cnt, uint32_t *sizes2, uint32_t *status);
-hipError_t launch_grouping_prefix(hipStream_t s, const uint32_t *nstart, const uint32_t *sizes, const uint32_t *sizes2,
-                                  uint32_t *pre_old, uint32_t *pre_new, uint32_t nc, uint32_t nsubc);
-hipError_t launch_grouping_merge(hipStream_t s, const IvfTables &t, const uint32_t *nstart, const uint32_t *lstart,
-                                 const uint32_t *tile_first, const uint32_t *pre_old, const uint32_t *pre_new,
-                                 uint32_t nsubc, const NewLists &nl);
-hipError_t launch_grouping_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx,
-                                   const uint32_t *sub_idx, size_t n, const uint32_t *nstart, const uint32_t *lstart,
-                                   const uint32_t *sizes, const uint32_t *pre_old, uint32_t nsubc, const uint8_t *codes,
-                                   const uint8_t *norm_codes, const uint32_t *ids, const NewLists &nl);
+// additions to a Grouping index (kernels_add_groups.hip): its codes go in with the append launchers above.
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --
 // for groups with points); out[i] = table[rows[i]] for rows of nsubc words

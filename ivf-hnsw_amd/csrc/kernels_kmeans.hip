@@ -12,7 +12,7 @@
 //            S = ((0 + x0) + x1) + ...   (__fadd_rn), mean = S / (float)cnt (__fdiv_rn); an empty cluster keeps its row
 //   split    the (ci, cj) pairs the host picked (faiss's split_clusters, deterministic), applied strictly in order
 #include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "update_steps.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -57,34 +57,15 @@ __global__ __launch_bounds__(256) void kmeans_count_kernel(const uint32_t *__res
 __global__ __launch_bounds__(1024) void scan_u32_kernel(const uint32_t *in, uint32_t *out, size_t len)
 {
     __shared__ uint32_t s_w[16];
-    __shared__ uint32_t s_carry;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0)
-        s_carry = 0;
-    __syncthreads();
-    for (size_t c0 = 0; c0 < len; c0 += 1024) {
-        const size_t i = c0 + t;
+    uint32_t carry = 0; // the sum of the chunks before, kept by every thread
+    for (size_t c0 = 0; c0 < len; c0 += 1024) { // every thread walks every chunk: block_excl_scan sees whole wavefronts
+        const size_t i = c0 + threadIdx.x;
         const uint32_t v = i < len ? in[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o)
-                inc += y;
-        }
-        if (lane == 63)
-            s_w[wave] = inc;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < wave; w++)
-            wbase += s_w[w];
-        const uint32_t carry = s_carry;
+        uint32_t total;
+        const uint32_t excl = block_excl_scan<16>(v, s_w, total);
         if (i < len)
-            out[i] = carry + wbase + inc - v;
-        __syncthreads(); // every thread has read s_w and s_carry
-        if (t == 1023)
-            s_carry = carry + wbase + inc;
-        __syncthreads();
+            out[i] = carry + excl;
+        carry += total;
     }
 }
 

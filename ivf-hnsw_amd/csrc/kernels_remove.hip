@@ -8,14 +8,14 @@
 //   counts   one wavefront per list: popcounts of the mask over the list's rows give rem[c]; on Grouping handles over
 //            each sub-group's rows too, which gives the new sub-group sizes
 //   scans    rem and keep become their exclusive scans (append's three-phase scan, kernels_append.hip)
-//   offsets  goff'[c] = goff[c] - rem_scan[c], loff'[c] = loff[c] - rem_scan[c]
+//   offsets  goff'[c] = goff[c] - rem_scan[c], loff'[c] = loff[c] - rem_scan[c] (launch_update_offsets, kernels_append.hip)
 //   compact  one workgroup per source tile: the ranks of its surviving rows from the mask, then the rows to the
-//            contiguous range that starts at keep_scan[tile].  Destination dwords are written in 16-byte aligned groups;
-//            a group the tile only partly owns gets dword stores (codes, ids) or byte stores (norm codes) of its own
-//            part, so neighbouring tiles never write the same bytes.
+//            contiguous range that starts at keep_scan[tile] (copy_gathered_rows, update_steps.h).  Destination dwords are
+//            written in 16-byte aligned groups; a group the tile only partly owns gets dword stores (codes, ids) or byte
+//            stores (norm codes) of its own part, so neighbouring tiles never write the same bytes.
 // code_size is any multiple of 4, so a row is a whole number q of dwords: every address is dword aligned.
 #include "ivfhnsw_kernels.h"
-#include "device_common.h"
+#include "update_steps.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -23,16 +23,6 @@ namespace {
 
 constexpr int kTileWords = kRemoveTileRows / 64; // mask words (64 rows each) per tile
 static_assert(kTileWords <= 64 && kRemoveTileRows % 256 == 0, "one wavefront scans a tile's mask words");
-
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes, dword aligned
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-        v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void remove_max_kernel(const uint32_t *__restrict__ labels, size_t n, uint32_t *__restrict__ out)
 {
@@ -149,55 +139,7 @@ __global__ __launch_bounds__(256) void remove_counts_kernel(const uint64_t *__re
     }
 }
 
-__global__ __launch_bounds__(256) void remove_offsets_kernel(const uint64_t *__restrict__ goff, const uint32_t *__restrict__ loff,
-                                                             const uint32_t *__restrict__ rscan, uint64_t *__restrict__ goff2,
-                                                             uint32_t *__restrict__ loff2, uint32_t nc)
-{
-    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > nc)
-        return;
-    goff2[c] = goff[c] - rscan[c];
-    if (c < nc)
-        loff2[c] = loff[c] - rscan[c];
-}
-
-// dst dwords [d0, d0 + rows * q) from source dwords s_src[j] * q + k (element e = j * q + k), in 16-byte aligned
-// destination groups; a group the range covers only in part is written dword by dword, its own dwords only
-__device__ __forceinline__ void compact_dwords(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, const uint32_t *s_src,
-                                               uint32_t rows, uint32_t q, uint64_t d0)
-{
-    const uint32_t ndw = rows * q;
-    const uint32_t head = (uint32_t)(d0 & 3);
-    const uint32_t ngroups = (head + ndw + 3) / 4;
-    uint32_t *dbase = dst + (d0 - head);
-    for (uint32_t gi = threadIdx.x; gi < ngroups; gi += 256) {
-        const int64_t e0 = (int64_t)gi * 4 - head;
-        const uint32_t ef = (uint32_t)(e0 < 0 ? 0 : e0);
-        uint32_t j = ef / q, k = ef - j * q;
-        size_t s[4];
-        bool ok[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int64_t e = e0 + u;
-            ok[u] = e >= 0 && e < (int64_t)ndw;
-            s[u] = ok[u] ? (size_t)s_src[j] * q + k : 0;
-            if (ok[u] && ++k == q) {
-                k = 0;
-                j++;
-            }
-        }
-        if (ok[0] && ok[3] && s[1] == s[0] + 1 && s[2] == s[0] + 2 && s[3] == s[0] + 3) {
-            const u32x4_a4 w = *reinterpret_cast<const u32x4_a4 *>(src + s[0]);
-            *reinterpret_cast<uint4 *>(dbase + (size_t)gi * 4) = make_uint4(w.x, w.y, w.z, w.w);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (ok[u])
-                    dbase[(size_t)gi * 4 + u] = src[s[u]];
-        }
-    }
-}
-
+// one workgroup per source tile; every lane of wavefront 0 takes part in the scan of the tile's mask words
 __global__ __launch_bounds__(256) void remove_compact_kernel(const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ kscan,
                                                              uint64_t n_local, const uint32_t *__restrict__ codes,
                                                              const uint8_t *__restrict__ ncodes, const uint32_t *__restrict__ ids,
@@ -218,13 +160,7 @@ __global__ __launch_bounds__(256) void remove_compact_kernel(const unsigned long
                 kb &= (1ull << (n_local - rw)) - 1ull;
         }
         const uint32_t cnt = (uint32_t)__popcll(kb);
-        uint32_t inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o)
-                inc += y;
-        }
+        const uint32_t inc = wave_incl_scan(cnt, lane);
         if (lane < kTileWords) {
             s_keep[lane] = kb;
             s_pre[lane] = inc - cnt;
@@ -240,35 +176,11 @@ __global__ __launch_bounds__(256) void remove_compact_kernel(const unsigned long
         const uint32_t w = j >> 6, b = j & 63;
         const unsigned long long kb = s_keep[w];
         if ((kb >> b) & 1ull)
-            s_src[s_pre[w] + (uint32_t)__popcll(kb & ((1ull << b) - 1ull))] = (uint32_t)(r0 + j);
+            s_src[kept_rank(s_pre[w], kb, b)] = (uint32_t)(r0 + j);
     }
     __syncthreads();
-    const uint64_t d0 = kscan[blockIdx.x];
-    compact_dwords(codes, codes2, s_src, rows, q, d0 * q);
-    compact_dwords(ids, ids2, s_src, rows, 1u, d0);
-    // norm codes: one byte per row; dword stores where the tile owns the whole dword, byte stores at its two ends
-    const uint32_t head = (uint32_t)(d0 & 3);
-    const uint32_t ngroups = (head + rows + 3) / 4;
-    uint8_t *nbase = ncodes2 + (d0 - head);
-    for (uint32_t gi = threadIdx.x; gi < ngroups; gi += 256) {
-        const int64_t e0 = (int64_t)gi * 4 - head;
-        if (e0 >= 0 && e0 + 4 <= (int64_t)rows) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                w |= (uint32_t)ncodes[s_src[e0 + u]] << (8 * u);
-            *reinterpret_cast<uint32_t *>(nbase + (size_t)gi * 4) = w;
-        } else {
-            for (int u = 0; u < 4; u++) {
-                const int64_t e = e0 + u;
-                if (e >= 0 && e < (int64_t)rows)
-                    nbase[(size_t)gi * 4 + u] = ncodes[s_src[e]];
-            }
-        }
-    }
+    copy_gathered_rows<false>(codes, ncodes, ids, codes2, ncodes2, ids2, s_src, rows, q, kscan[blockIdx.x]);
 }
-
-inline unsigned blocks_of(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
 
 } // namespace
 
@@ -314,9 +226,7 @@ hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigne
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
                                  const uint32_t *rscan, const uint32_t *kscan, const NewLists &nl)
 {
-    hipLaunchKernelGGL(remove_offsets_kernel, dim3(blocks_of((size_t)t.nc + 1, 256)), dim3(256), 0, s, t.goff, t.loff, rscan,
-                       nl.goff, nl.loff, t.nc);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+    if (hipError_t e = launch_update_offsets(s, t, rscan, nullptr, false, nl); e != hipSuccess)
         return e;
     if (nl.n_local == 0)
         return hipSuccess;
