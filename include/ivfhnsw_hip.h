@@ -302,7 +302,11 @@ int ivfhnsw_gpu_last_batch_parts(ivfhnsw_gpu *h, uint64_t *first, uint64_t *seco
  *                exact_range_search cuts the store the same way (its slices of a query follow each other in label order).
  *   "exact_range_map"  -1 (default) or 1: exact_range_search's first pass leaves a map of the tiles in which anything
  *                passed and its second pass visits only those; 0: the second pass sweeps the whole store again.  The
- *                results are the same; the key exists so that both can be measured and compared. */
+ *                results are the same; the key exists so that both can be measured and compared.
+ *   "exact_filter_form"  -1 (default) the rule: under a base filter (below) the exact calls sweep the list of passing
+ *                rows when at most n / 8 rows pass, else the store behind its pass bits; 0: always the pass bits; 1: always
+ *                the list (built on demand whatever the number of passing rows).  The results are the same; the key exists
+ *                so that both forms can be exercised on a small store and measured.  Other values: IVFHNSW_ERR_INVALID. */
 int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value);
 
 /* The search-time knobs the drivers set as public members (IndexIVF_HNSW.h:61-62, hnswalg.h:69,
@@ -569,7 +573,8 @@ int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_que
  *   Row j is returned for query q iff (float)dist(q, j) < radius, dist the integer sum (q[i] - x[i])^2 -- strict, as
  *   range_search and faiss compare for L2.  The distance written is that integer as a float, bit for bit what exact_search
  *   and rerank write for the pair (d <= 256: below 2^24, exact).  Every row of the store is a candidate, the zero rows of
- *   a chunk that was never uploaded included.  The radius becomes an int32 threshold on the host, dist < thr: thr = 0 when
+ *   a chunk that was never uploaded included; the index's label filter (set_filter) does not apply, the base filter
+ *   (set_base_filter, below) does.  The radius becomes an int32 threshold on the host, dist < thr: thr = 0 when
  *   !(radius > 0) (0, negatives, -inf: all-zero lims without a sweep), INT_MAX when radius > 2^24 (+inf), else
  *   (int)ceilf(radius) -- for integer dist < 2^24 exactly the float comparison.
  *   The results of one query stand in ASCENDING LABEL.  lims [nq + 1]: lims[0] = 0, query q owns entries
@@ -602,6 +607,46 @@ int ivfhnsw_gpu_exact_range_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t 
                                        uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_exact_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_exact_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
+
+/* ---- base filter: the exact calls under an allow or deny set of row numbers ---------------------------
+ *
+ * faiss's IDSelector for the flat search: the ground truth of a filtered search.  The handle that holds the store
+ * (upload_base) holds no base filter or one: a set of uint32 labels and a mode (IVFHNSW_FILTER_ALLOW / IVFHNSW_FILTER_DENY).
+ * A label is a ROW NUMBER of the store, the label exact_search returns.  Allow: a row passes iff its number is in the set;
+ * deny: iff it is not.  Any uint32 value is accepted; labels >= n match nothing; repeats count once; an empty allow set
+ * passes nothing, an empty deny set everything.
+ * While a base filter is installed ivfhnsw_gpu_exact_search[_dev] and ivfhnsw_gpu_exact_range_search[_dev] answer as the
+ * unfiltered call would on a store that held only the passing rows, the labels being the ORIGINAL row numbers: the same
+ * distance bits, exact_search ascending by (distance, label) and padded with FLT_MAX / -1 when fewer than k rows pass, the
+ * range search in ascending label per query with exact lims.  When no row passes neither call sweeps anything (padding;
+ * all-zero lims and a total of 0).  Limits and errors of the unfiltered calls hold unchanged.  ivfhnsw_gpu_rerank* is not
+ * touched: its candidates come from a search that was filtered already.  The index filter (ivfhnsw_gpu_set_filter, labels =
+ * ids) and the base filter are independent: neither call sets, clears or reads the other, and the index filter never
+ * applies to the exact calls.  Without a base filter nothing changes: the same kernels, the same bits.
+ * The work follows the rows that pass.  The filter is kept as one pass bit per row (n / 8 bytes) and, when at most n / 8
+ * rows pass, as the ascending list of the passing row numbers as well (4 bytes each, at most n / 2 bytes); the sweeps then
+ * run over the list alone (cost in proportion to the passing rows), otherwise over the store, skipping every tile of 32
+ * rows in which no row passes.  The option "exact_filter_form" (ivfhnsw_gpu_set_option) forces either form; results
+ * never depend on it.  ivfhnsw_gpu_memory_bytes counts what the filter holds.
+ *
+ * ivfhnsw_gpu_set_base_filter replaces an earlier base filter; the new one is built on the device beside it and swapped
+ *   in when complete, so any error leaves the earlier filter in force.  Synchronous on the handle's stream; needs a store
+ *   (before upload_base: IVFHNSW_ERR_STATE) but no index; sharded handles are fine (the store is not sharded).  While
+ *   it is built ~1 bit per label value up to the largest label (<= 512 MB) is allocated beside it.  n > 0 with NULL
+ *   labels or an unknown mode: IVFHNSW_ERR_INVALID; a failed allocation: IVFHNSW_ERR_NOMEM.
+ *   ivfhnsw_gpu_set_base_filter_dev: d_labels in device memory (4-byte aligned, else IVFHNSW_ERR_INVALID), read on the
+ *   handle's stream.
+ * ivfhnsw_gpu_clear_base_filter: no base filter afterwards; succeeds on a handle that has none.
+ * ivfhnsw_gpu_upload_base[_dev] with first == 0 (a new store) or n == 0 (no store) drops the base filter; a later chunk
+ *   (first > 0) keeps it.
+ * Views: set / clear on a view -> IVFHNSW_ERR_STATE.  A view reads its parent's store at the call, and its parent's base
+ *   filter the same way; replacing the filter (or uploading) while a view's exact call is in flight is the caller's to avoid.
+ * ivfhnsw_gpu_base_filter_info: *mode = the installed mode or -1; *rows_passing = rows of the store that pass (all of them
+ *   without a filter); *rows_total = rows of the store.  Each pointer nullable; a view reports its parent's. */
+int ivfhnsw_gpu_set_base_filter(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int mode);
+int ivfhnsw_gpu_set_base_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int mode);
+int ivfhnsw_gpu_clear_base_filter(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_base_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_search_reconstruct_dev",
     "ivfhnsw_gpu_exact_range_search", "ivfhnsw_gpu_exact_range_search_dev", "ivfhnsw_gpu_exact_range_results",
     "ivfhnsw_gpu_exact_range_results_dev",
+    "ivfhnsw_gpu_set_base_filter", "ivfhnsw_gpu_set_base_filter_dev", "ivfhnsw_gpu_clear_base_filter",
+    "ivfhnsw_gpu_base_filter_info",
 )
 
 
@@ -175,6 +177,10 @@ def lib():
         L.ivfhnsw_gpu_set_filter_dev.argtypes = L.ivfhnsw_gpu_set_filter.argtypes
         L.ivfhnsw_gpu_clear_filter.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_set_base_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
+        L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_base_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
@@ -956,6 +962,27 @@ class GpuIndex:
         pd, pl, total = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
         _check(lib().ivfhnsw_gpu_exact_range_results_dev(self._h, C.byref(pd), C.byref(pl), C.byref(total)))
         return pd.value or 0, pl.value or 0, int(total.value)
+
+    # ---- base filter of the exact calls (ivfhnsw_gpu_set_base_filter) ------------------------------
+    def set_base_filter(self, labels, deny=False):
+        """exact_search and exact_range_search consider only the rows of the base store whose row number is in `labels`
+        (deny=True: is not in them); replaces an earlier base filter.  Independent of set_filter."""
+        lab = _np(labels, np.uint32).ravel()
+        _check(lib().ivfhnsw_gpu_set_base_filter(self._h, lab.size, _ptr(lab) if lab.size else None,
+                                                 FILTER_DENY if deny else FILTER_ALLOW))
+
+    def set_base_filter_dev(self, n, d_labels, deny=False):
+        """The same on a device buffer (torch CUDA tensor or raw address)."""
+        _check(lib().ivfhnsw_gpu_set_base_filter_dev(self._h, n, _devptr(d_labels), FILTER_DENY if deny else FILTER_ALLOW))
+
+    def clear_base_filter(self):
+        _check(lib().ivfhnsw_gpu_clear_base_filter(self._h))
+
+    def base_filter_info(self):
+        """(mode or -1, rows_passing, rows_total) of the base store."""
+        m, a, b = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_filter_info(self._h, C.byref(m), C.byref(a), C.byref(b)))
+        return int(m.value), int(a.value), int(b.value)
 
     # ---- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on):

@@ -48,7 +48,12 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
     int rc = exact_guard(h, "exact_search", nq, row_stride, !queries || !distances || !labels, "null query/result buffer", k_check, &b);
     if (rc || nq == 0)
         return rc;
-    const size_t d = b->base_d, n = b->base_n;
+    const size_t d = b->base_d;
+    // under a base filter the columns of the sweep: every row behind the pass words, or the list of passing rows
+    SweepCols cols;
+    size_t n;
+    if ((rc = base_filter_cols(h, b, &cols, &n)))
+        return rc;
 
     const size_t first = std::min(nq, kExactChunk);
     const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_splits_for(first, n, (int)k);
@@ -74,7 +79,7 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
         float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
         int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
         HIP_TRY(launch_exact_search(h->stream, h->ex_q.as<uint8_t>(), b->base_rows.as<uint8_t>(), m, n, (int)d, (int)k, nsplit,
-                                    h->ex_part.as<unsigned long long>(), od, ol));
+                                    h->ex_part.as<unsigned long long>(), od, ol, cols));
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -143,16 +148,16 @@ int exact_range_map_shift(size_t nq, size_t n, size_t d, int nsplit, size_t *byt
 }
 
 // the sweep of one form over every chunk of the call's queries (h->ex_q: all of them, permuted)
-int exact_range_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, bool fill, size_t nq, int thr, int nsplit, int map_shift, float *dist,
-                     int64_t *labels, size_t out_cap)
+int exact_range_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const SweepCols &cols, size_t nx, bool fill, size_t nq, int thr,
+                     int nsplit, int map_shift, float *dist, int64_t *labels, size_t out_cap)
 {
     const size_t d = b->base_d;
     StageScope sc(h, fill ? IVFHNSW_STAGE_SELECT : IVFHNSW_STAGE_SCAN); // accounted as range_search accounts its passes
     for (size_t q0 = 0; q0 < nq; q0 += kExactChunk) // (kExactChunk % 128 == 0: a chunk starts a workgroup's strip)
         HIP_TRY(launch_exact_range(h->stream, fill, h->ex_q.as<uint8_t>() + q0 * d, b->base_rows.as<uint8_t>(),
-                                   std::min(kExactChunk, nq - q0), q0, b->base_n, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
+                                   std::min(kExactChunk, nq - q0), q0, nx, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
                                    h->xr_tot.as<unsigned long long>(), h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr,
-                                   map_shift, dist, labels, out_cap));
+                                   map_shift, dist, labels, out_cap, cols));
     return IVFHNSW_OK;
 }
 
@@ -161,10 +166,14 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
                     uint64_t *total)
 {
     const ivfhnsw_gpu *b = h->parent ? h->parent : h;
-    const size_t d = b->base_d, n = b->base_n;
+    const size_t d = b->base_d;
     const int thr = exact_range_threshold(radius);
     int rc;
-    if (thr == 0) { // nothing is below it: no sweep
+    SweepCols cols; // the columns of the sweep under a base filter, as in exact_impl
+    size_t n;
+    if ((rc = base_filter_cols(h, b, &cols, &n)))
+        return rc;
+    if (thr == 0 || n == 0) { // nothing is below it, or no row passes the base filter: no sweep
         HIP_TRY(hipMemsetAsync(d_lims, 0, (nq + 1) * sizeof(uint64_t), h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->xr_valid = true;
@@ -183,7 +192,7 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     HIP_TRY(launch_rerank_permute(h->stream, d_queries, row_stride, h->ex_q.as<uint8_t>(), nq, (int)d));
     HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
-    if ((rc = exact_range_pass(h, b, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0)))
+    if ((rc = exact_range_pass(h, b, cols, n, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0)))
         return rc;
     HIP_TRY(launch_scan_excl_u32(h->stream, h->xr_slices.as<uint32_t>(), len, h->xr_part.as<uint32_t>()));
     // the one synchronisation between the passes: the host sizes the results from the count
@@ -204,7 +213,7 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     auto fill = [&]() -> int {
         HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
         if (tot)
-            if (int e = exact_range_pass(h, b, true, nq, thr, nsplit, map_shift, grow ? nd.as<float>() : h->xr_dist.as<float>(),
+            if (int e = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, grow ? nd.as<float>() : h->xr_dist.as<float>(),
                                          grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), (size_t)tot))
                 return e;
         HIP_TRY(hipStreamSynchronize(h->stream));

@@ -299,6 +299,12 @@ int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value)
         h->opt_exact_range_map = (int)value;
         return IVFHNSW_OK;
     }
+    if (!strcmp(key, "exact_filter_form")) {
+        if (value < -1 || value > 1)
+            return fail(IVFHNSW_ERR_INVALID, "set_option exact_filter_form: %ld outside -1..1", value);
+        h->opt_exact_filter_form = (int)value;
+        return IVFHNSW_OK;
+    }
     return fail(IVFHNSW_ERR_INVALID, "set_option: unknown key '%s'", key);
 }
 

@@ -137,6 +137,7 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
+    X(bf_words) X(bf_rows) X(bf_own) X(bf_labels) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
@@ -184,6 +185,17 @@ struct ivfhnsw_gpu {
     uint32_t f_max_label = 0;
     uint64_t f_pass = 0;
 
+    // the base filter of the exact calls (capi_base_filter.cpp), on the handle that holds the store: a view
+    // reads its parent's at the call.  bf_mode -1 = none.  bf_words: one pass bit per row; bf_rows (bf_has_rows): the
+    // bf_pass passing row numbers ascending.  bf_gen counts the changes, so that the list a handle built for itself because
+    // "exact_filter_form" 1 asked for one the holder does not keep (bf_own, of holder bf_own_of at bf_own_gen) is not
+    // used for a later filter.
+    int bf_mode = -1;
+    uint64_t bf_pass = 0;
+    bool bf_has_rows = false;
+    uint64_t bf_gen = 0, bf_own_gen = 0;
+    const ivfhnsw_gpu *bf_own_of = nullptr;
+
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
     hipEvent_t split_fork = nullptr, split_join = nullptr;
@@ -200,6 +212,7 @@ struct ivfhnsw_gpu {
     int opt_scan_pipe = -1;    // ivfhnsw_gpu_set_option "scan_pipe"
     int opt_exact_splits = -1; // ... "exact_splits"
     int opt_exact_range_map = -1; // ... "exact_range_map"
+    int opt_exact_filter_form = -1; // ... "exact_filter_form"
 
     // the plan the last search_dev chunk left (remember_plan, capi_search.cpp)
     int last_nq = 0, last_max_seg = 0;
@@ -410,6 +423,12 @@ int chunk_checks(ivfhnsw_gpu *h, const Chunk &c, bool results = true);
 int chunk_workspace(ivfhnsw_gpu *h, Chunk &c);
 int chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call);
 int chunk_plan_table(ivfhnsw_gpu *h, Chunk &c);
+
+// ---- capi_base_filter.cpp
+void base_filter_drop(ivfhnsw_gpu *h); // the handle holds no base filter afterwards (buffers released)
+// The column map of an exact call of h on holder b's store and the columns it sweeps (*nx; 0 = nothing passes, no sweep):
+// Dense without a base filter, else the form sweep_filter_form picks.  May build h's own list (bf_own) on h's stream.
+int base_filter_cols(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, SweepCols *cols, size_t *nx);
 
 // ---- capi_range.cpp
 void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)

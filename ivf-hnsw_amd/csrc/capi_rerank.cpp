@@ -15,6 +15,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->base_rows.release();
         h->base_stage.release();
+        base_filter_drop(h); // its rows are gone
         h->base_n = 0;
         h->base_d = 0;
         return IVFHNSW_OK;
@@ -30,6 +31,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
     if (first == 0) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->base_rows.release();
+        base_filter_drop(h); // a new store: its row numbers mean other rows
         h->base_n = 0;
         h->base_d = 0;
         if ((rc = h->base_rows.ensure(n * d)))

@@ -339,8 +339,10 @@ hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, 
 // workspace; writes the k nearest rows of every query ascending by (distance, label), padded with FLT_MAX / -1
 inline int exact_rows_per_block(int k) { return k <= 32 ? 128 : 64; }
 inline int exact_splits_for(size_t nq, size_t nx, int k) { return sweep_splits_for(nq, nx, exact_rows_per_block(k)); }
+// cols: the column map of a base filter (sweep_plan_math.h SweepCols).  Masked: data = the pass words of
+// the nx rows; Indirect: data = the passing row numbers ascending and nx = their number (nx == 0: only padding is written)
 hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
-                               int nsplit, unsigned long long *part, float *dists, int64_t *labels);
+                               int nsplit, unsigned long long *part, float *dists, int64_t *labels, const SweepCols &cols = {});
 // exact range search (kernels_exact.hip): the same sweep with the fixed gate dist < thr (int32, thr >= 0),
 // one launch for the nq queries Qp [nq][d] (permuted) that are queries [q_off, q_off + nq) of the call, q_off % 32 == 0.
 // count (fill = false): slices[(q_off + q) * nsplit + split] = the rows of the split that pass, *total (device) += their
@@ -352,7 +354,14 @@ constexpr int kExactRangeMaxShift = 20;
 inline int exact_range_map_words(size_t nx, int nsplit, int map_shift) { return sweep_map_words(nx, nsplit, map_shift); }
 hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
                               int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
-                              int map_shift, float *dist, int64_t *labels, size_t out_cap);
+                              int map_shift, float *dist, int64_t *labels, size_t out_cap, const SweepCols &cols = {});
+// the base filter of the exact calls (kernels_exact_filter.hip).  words: [sweep_pass_words(n)] = the label
+// bitmap bits [bit_words] (null = the empty set) cut or zero-extended to n rows, inverted with deny, bits at or beyond n
+// zero; *count (zeroed here) = the rows that pass.  rows: the passing row numbers ascending, [*count]; cnt: workspace of
+// sweep_pass_words(n) + 1 words, part: append_scan_parts of that.
+hipError_t launch_pass_words(hipStream_t s, const uint32_t *bits, size_t bit_words, uint64_t n, int deny, uint32_t *words,
+                             unsigned long long *count);
+hipError_t launch_pass_rows(hipStream_t s, const uint32_t *words, uint64_t n, uint32_t *cnt, uint32_t *part, uint32_t *rows);
 // appends to the inverted lists (kernels_append.hip) and to the sub-groups of Grouping lists (3.12); the
 // arithmetic and the workspace sizes are update_math.h's.  count: cnt[list_idx[i]] += 1 and, with sub_idx, sizes2[list][sub]
 // += 1 (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  tables: own[c] = old length +

@@ -20,6 +20,10 @@
 //
 // The exact range search (ivfhnsw_gpu_exact_range_search) is the same strip with a fixed gate and no
 // selection: exact_range_kernel, below the k-search.
+//
+// Under a base filter (ivfhnsw_gpu_set_base_filter) both kernels sweep through a column map, a template
+// parameter (sweep_steps.h): ColsDense is the sweep described above and the only one without a filter; ColsMasked skips
+// every tile of 32 rows in which no row passes; ColsIndirect sweeps the ascending list of passing rows instead of the store.
 #include "sweep_steps.h"
 
 #include <float.h>
@@ -32,10 +36,12 @@ namespace {
 // NS = ceil(d / 32), the steps of 32 bytes a row is read in, CAP = keys of a row's candidate buffer (a row is
 // compacted when it holds more than CAP - 32), WAVES = 32-row strips per workgroup.
 // Qp: the queries in the store's byte order, [nq][d]; X: the store, [nx][d]; both 16-byte aligned, d % 16 == 0.
-template <int NS, int CAP, int WAVES>
+// CM: the column map (sweep_steps.h): ColsDense is the unfiltered sweep; under a base filter ColsMasked
+// skips the tiles without a passing row, ColsIndirect sweeps the list of passing rows, nx = their number.
+template <int NS, int CAP, int WAVES, class CM>
 __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *__restrict__ Qp, const uint8_t *__restrict__ X,
                                                                 int nq, size_t nx, int d, int k, size_t cols_per_split,
-                                                                unsigned long long *__restrict__ out_keys)
+                                                                unsigned long long *__restrict__ out_keys, CM cm)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long *s_buf = reinterpret_cast<unsigned long long *>(smem); // [WAVES][32][CAP]
@@ -64,26 +70,41 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
     }
     __builtin_amdgcn_wave_barrier();
 
-    if (c_begin < c_end)
-        st.fetch(X, c_begin, c_begin, c_end, d);
-    for (size_t c0 = c_begin; c0 < c_end; c0 += 32) {
+    // The tiles of the split in turn -- under a column map the ones it visits: the prefetch goes to the next tile that will
+    // be visited (ColsDense: c0 + 32, the loop as it was before there were column maps).
+    ColCursor<CM> cc;
+    cc.setup(cm, c_begin, c_end, (uint32_t)((c_end - c_begin + 31) >> 5), lane);
+    size_t cn = cc.next_col(c_begin);
+    if (cn < c_end) {
+        cc.ids(cn);
+        cc.shift();
+        cc.fetch(st, X, cn, c_begin, c_end, d);
+        if (CM::kIndirect && cn + 32 < c_end)
+            cc.ids(cn + 32);
+    }
+    for (size_t c0 = cn; c0 < c_end; c0 = cn) {
         const size_t col = c0 + m;
-        const bool col_ok = col < c_end;
+        const bool col_ok = col < c_end && cc.lane_pass(m);
         st.take(); // a lane without a column scores a row it drops below
-        if (c0 + 32 < c_end)
-            st.fetch(X, c0 + 32, c_begin, c_end, d); // in flight behind this tile's MFMAs
+        cc.shift();
+        cn = cc.next_col(c0 + 32);
+        if (cn < c_end)
+            cc.fetch(st, X, cn, c_begin, c_end, d); // in flight behind this tile's MFMAs
+        if (CM::kIndirect && cn + 32 < c_end)
+            cc.ids(cn + 32); // (Indirect visits every tile: the one after the next begins at cn + 32)
         i32x16 acc;
         int xn;
         st.product(acc, xn);
         if (!__ballot(st.any_pass(acc, xn, gate) && col_ok))
             continue; // wave-uniform: the common tile once the thresholds have settled
+        const uint32_t label = (uint32_t)cc.label(col);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int dist = st.dist(acc, xn, r);
             const bool pass = col_ok && dist < st.qn_r[r] - gate[r];
             const unsigned long long mask = __ballot(pass);
             if (mask)
-                row_append<CAP>(buf, cnt, mfma32_row(r, kk), pass, mask, dist, (uint32_t)col, m, kk);
+                row_append<CAP>(buf, cnt, mfma32_row(r, kk), pass, mask, dist, label, m, kk);
         }
         rows_compact<CAP>(buf, cnt, thr_s, k, lane);
 #pragma unroll
@@ -110,18 +131,29 @@ __global__ __launch_bounds__(64) void exact_merge_kernel(const unsigned long lon
         });
 }
 
-template <int NS, int CAP, int WAVES>
+template <int NS, int CAP, int WAVES, class CM>
 hipError_t launch_exact_t(hipStream_t s, const uint8_t *Qp, const uint8_t *X, int nq, size_t nx, int d, int k, int nsplit,
-                          size_t cols_per_split, unsigned long long *part)
+                          size_t cols_per_split, unsigned long long *part, CM cm)
 {
     const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(int));
-    constexpr auto kern = exact_mfma_kernel<NS, CAP, WAVES>;
+    constexpr auto kern = exact_mfma_kernel<NS, CAP, WAVES, CM>;
     if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
         return e;
     // query tile is the fast index, column split the slow one: the tiles that run together stream the same columns
     hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 32 * WAVES - 1) / (32 * WAVES)), (unsigned)nsplit), dim3(64 * WAVES), shm,
-                       s, Qp, X, nq, nx, d, k, cols_per_split, part);
+                       s, Qp, X, nq, nx, d, k, cols_per_split, part, cm);
     return hipGetLastError();
+}
+
+// f(the column map of `cols` as its kernel argument): the one dispatch on the form
+template <class F> hipError_t by_col_map(const SweepCols &cols, F &&f)
+{
+    switch (cols.form) {
+    case kSweepColsDense: return f(ColsDense{});
+    case kSweepColsMasked: return f(ColsMasked{cols.data});
+    case kSweepColsIndirect: return f(ColsIndirect{cols.data});
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // Exact range search (ivfhnsw_gpu_exact_range_search): the sweep above with a fixed gate, dist < thr, in
@@ -138,13 +170,16 @@ hipError_t launch_exact_t(hipStream_t s, const uint8_t *Qp, const uint8_t *X, in
 // pass in them -- 32 bits to a word, stored by one lane when the word is complete; map[((q_off + r0) / 32 * nsplit + split)
 // * map_words + word].  The fill form visits only tiles whose bit is set, still in order, so the cursors stay right; a
 // tile it skips is neither loaded nor multiplied.  Every word the fill form reads the count form wrote (the same tiles).
-template <int NS, bool FILL>
+// Under a column map (CM, as in exact_mfma_kernel) the tile map and the pass words compose: the count form visits the
+// tiles with a passing row and sets map bits only for those, the fill form visits a tile iff its map bit is set and its
+// pass word is not zero (a bit of a coarser map covers 2^map_shift tiles, some of which may be empty).
+template <int NS, bool FILL, class CM>
 __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restrict__ Qp, const uint8_t *__restrict__ X, int nq,
                                                           size_t nx, int d, int thr, size_t cols_per_split, size_t q_off,
                                                           uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
                                                           uint32_t *__restrict__ map, int map_shift, int map_words,
                                                           float *__restrict__ out_d, long long *__restrict__ out_l,
-                                                          size_t out_cap)
+                                                          size_t out_cap, CM cm)
 {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int m = lane & 31, kk = lane >> 5;
@@ -169,29 +204,46 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
     }
 
     uint32_t *mw = map ? map + ((((q_off + r0) >> 5) * nsplit + split) * (size_t)map_words) : nullptr;
-    // the first tile at or after t that is to be visited (ntiles: none)
+    ColCursor<CM> cc;
+    cc.setup(cm, c_begin, c_end, ntiles, lane);
+    // the first tile at or after t that is to be visited (ntiles: none): one with a passing row (cc.next) whose map bit is
+    // set.  The map is read only at tiles with a passing row: those the count form visited, whose words it wrote.
     auto next_tile = [&](uint32_t t) -> uint32_t {
-        if (!FILL || !mw)
-            return t < ntiles ? t : ntiles;
-        while (t < ntiles) {
+        for (;;) {
+            t = cc.next(t, ntiles);
+            if (!FILL || !mw || t >= ntiles)
+                return t;
             const uint32_t g = t >> map_shift;
             const uint32_t w = __builtin_amdgcn_readfirstlane(mw[g >> 5]) >> (g & 31);
             if (w & 1u)
                 return t;
             t = (w ? g + (uint32_t)__ffs((int)w) - 1u : (g | 31u) + 1u) << map_shift; // the next set bit, or the next word
         }
-        return ntiles;
     };
     uint32_t t = next_tile(0), bits = 0;
-    if (t < ntiles)
-        st.fetch(X, c_begin + ((size_t)t << 5), c_begin, c_end, d);
+    if (t < ntiles) {
+        cc.ids(c_begin + ((size_t)t << 5));
+        cc.shift();
+        cc.fetch(st, X, c_begin + ((size_t)t << 5), c_begin, c_end, d);
+        if constexpr (CM::kIndirect) {
+            const uint32_t t1 = next_tile(t + 1);
+            if (t1 < ntiles)
+                cc.ids(c_begin + ((size_t)t1 << 5));
+        }
+    }
     while (t < ntiles) {
         const size_t col = c_begin + ((size_t)t << 5) + m;
-        const bool col_ok = col < c_end;
+        const bool col_ok = col < c_end && cc.lane_pass(m);
         st.take();
+        cc.shift();
         const uint32_t tn = next_tile(t + 1);
         if (tn < ntiles)
-            st.fetch(X, c_begin + ((size_t)tn << 5), c_begin, c_end, d); // in flight behind this tile's MFMAs
+            cc.fetch(st, X, c_begin + ((size_t)tn << 5), c_begin, c_end, d); // in flight behind this tile's MFMAs
+        if constexpr (CM::kIndirect) { // the row numbers of the tile after the next
+            const uint32_t tnn = tn < ntiles ? next_tile(tn + 1) : ntiles;
+            if (tnn < ntiles)
+                cc.ids(c_begin + ((size_t)tnn << 5));
+        }
         i32x16 acc;
         int xn;
         st.product(acc, xn);
@@ -206,7 +258,7 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
                     const size_t o = (size_t)cnt[r] + __popc(half & ((1u << m) - 1u));
                     if (pass && o < out_cap) { // (o < out_cap always: the count form counted this very lane)
                         out_d[o] = (float)st.dist(acc, xn, r);
-                        out_l[o] = (long long)col;
+                        out_l[o] = (long long)cc.label(col);
                     }
                 }
                 cnt[r] += __popc(half);
@@ -244,12 +296,12 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
 
 hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
                               int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
-                              int map_shift, float *dist, int64_t *labels, size_t out_cap)
+                              int map_shift, float *dist, int64_t *labels, size_t out_cap, const SweepCols &cols)
 {
     if (nq == 0)
         return hipSuccess;
     if (d < 16 || d > 256 || (d & 15) || thr < 0 || nq > 0x7fffffffull || nx >= 0xffffffffull || nsplit < 1 || nsplit > 64 ||
-        (q_off & 31) || map_shift < 0 || map_shift > kExactRangeMaxShift)
+        (q_off & 31) || map_shift < 0 || map_shift > kExactRangeMaxShift || (cols.form != kSweepColsDense && nx && !cols.data))
         return hipErrorInvalidValue;
     const size_t cps = sweep_cols_per_split(nx, nsplit);
     const int words = sweep_map_words(nx, nsplit, map_shift);
@@ -257,28 +309,35 @@ hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const
     const dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nsplit);
     long long *lab = reinterpret_cast<long long *>(labels);
     return by_row_steps(d, [&](auto ns) {
-        const auto kern = fill ? exact_range_kernel<decltype(ns)::value, true> : exact_range_kernel<decltype(ns)::value, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, Qp, X, (int)nq, nx, d, thr, cps, q_off, slices, total, map, map_shift, words,
-                           dist, lab, out_cap);
-        return hipGetLastError();
+        return by_col_map(cols, [&](auto cm) {
+            using CM = decltype(cm);
+            const auto kern = fill ? exact_range_kernel<decltype(ns)::value, true, CM> : exact_range_kernel<decltype(ns)::value, false, CM>;
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, Qp, X, (int)nq, nx, d, thr, cps, q_off, slices, total, map, map_shift,
+                               words, dist, lab, out_cap, cm);
+            return hipGetLastError();
+        });
     });
 }
 
 // Qp: [nq][d] queries in the store's byte order (launch_rerank_permute); part: [nsplit][nq][k] u64 workspace
 hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
-                               int nsplit, unsigned long long *part, float *dists, int64_t *labels)
+                               int nsplit, unsigned long long *part, float *dists, int64_t *labels, const SweepCols &cols)
 {
     if (nq == 0)
         return hipSuccess;
     if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || nq > 0x7fffffffull || nx >= 0xffffffffull || nsplit < 1 ||
-        nsplit > 64)
+        nsplit > 64 || (cols.form != kSweepColsDense && nx && !cols.data))
         return hipErrorInvalidValue;
-    const size_t cps = sweep_cols_per_split(nx, nsplit);
-    const hipError_t e = by_row_steps(d, [&](auto ns) {
+    if (nx == 0) // no column at all (a filter nothing passes): no sweep, the merge of no tables writes the padding
+        nsplit = 0;
+    const size_t cps = sweep_cols_per_split(nx, nsplit ? nsplit : 1);
+    const hipError_t e = nsplit == 0 ? hipSuccess : by_row_steps(d, [&](auto ns) {
         constexpr int NS = decltype(ns)::value;
-        return k <= 16   ? launch_exact_t<NS, 48, 4>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part)
-               : k <= 32 ? launch_exact_t<NS, 64, 4>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part)
-                         : launch_exact_t<NS, 136, 2>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part);
+        return by_col_map(cols, [&](auto cm) {
+            return k <= 16   ? launch_exact_t<NS, 48, 4>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part, cm)
+                   : k <= 32 ? launch_exact_t<NS, 64, 4>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part, cm)
+                             : launch_exact_t<NS, 136, 2>(s, Qp, X, (int)nq, nx, d, k, nsplit, cps, part, cm);
+        });
     });
     if (e != hipSuccess)
         return e;

@@ -41,6 +41,37 @@ inline int sweep_map_words(size_t nx, int nsplit, int map_shift)
     return (int)((bits + 31) / 32);
 }
 
+// ---- the exact sweeps under a base filter
+// The column map of a sweep: Dense = column c is row c; Masked = the same columns, data = one pass bit per row, 32 to a
+// word; Indirect = the columns are the entries of data, the passing row numbers ascending.
+enum { kSweepColsDense = 0, kSweepColsMasked = 1, kSweepColsIndirect = 2 };
+struct SweepCols {
+    int form = kSweepColsDense;
+    const uint32_t *data = nullptr;
+};
+
+// Pass words of a store of n rows: word w covers rows [32 w, 32 w + 32).
+inline size_t sweep_pass_words(size_t n) { return (n + 31) / 32; }
+
+// The pass word of tile t of a split that begins at column c_begin.  Splits begin at multiples of 32
+// (sweep_cols_per_split), so the tile's 32 columns are exactly the word's 32 rows.
+inline size_t sweep_tile_word(size_t c_begin, size_t t) { return (c_begin >> 5) + t; }
+
+// Is the list of passing rows kept beside the pass words: when at most an eighth of the rows pass.  It is then at most
+// n / 2 bytes, while the list of a deny filter with few labels would be 4 bytes per row of the store.
+inline bool sweep_pass_list_kept(size_t npass, size_t n) { return npass <= n / 8; }
+
+// The form a filtered sweep takes: Indirect when the list is kept, else Masked; opt (set_option "exact_filter_form")
+// 0 / 1 forces Masked / Indirect, -1 is the rule.
+inline int sweep_filter_form(size_t npass, size_t n, int opt)
+{
+    if (opt == 0)
+        return kSweepColsMasked;
+    if (opt == 1)
+        return kSweepColsIndirect;
+    return sweep_pass_list_kept(npass, n) ? kSweepColsIndirect : kSweepColsMasked;
+}
+
 // f(int_c<NS>()) for NS = ceil(d / 32) = 1 .. 8, the steps of 32 bytes a row of the uint8 store is read in (d <= 256)
 template <class F> auto by_row_steps(int d, F &&f)
 {

@@ -1,6 +1,7 @@
 // The steps the brute-force MFMA sweeps share, one copy each: the C/D row map, the selection of a row's k
 // smallest keys through its LDS buffer (knn_mfma_kernel, exact_mfma_kernel), the int8 strip that reads the uint8 store
-// (exact_mfma_kernel, exact_range_kernel) and the merge of the splits' partial tables.  Control flow -- which tile comes
+// (exact_mfma_kernel, exact_range_kernel), the column maps those two sweep under when the store has a base filter
+// (ColsDense / ColsMasked / ColsIndirect, ColCursor) and the merge of the splits' partial tables.  Control flow -- which tile comes
 // next, what a tile without a candidate costs, what is done with a distance that passes -- stays in the kernels.  Host
 // arithmetic (columns per split, split count): sweep_plan_math.h.
 #pragma once
@@ -180,8 +181,10 @@ template <int NS> struct I8Strip {
     __device__ __forceinline__ void fetch(const uint8_t *X, size_t c0, size_t c_begin, size_t c_end, int d)
     {
         const size_t c = c0 + m;
-        load_row(X + (c < c_end ? c : c_begin) * (size_t)d, nxt);
+        fetch_row(X, c < c_end ? c : c_begin, d);
     }
+    // ... of the tile in which this lane's column is row `row` of X (a gathered tile: ColCursor below)
+    __device__ __forceinline__ void fetch_row(const uint8_t *X, size_t row, int d) { load_row(X + row * (size_t)d, nxt); }
     // the fetched tile becomes the current one; call before the next fetch
     __device__ __forceinline__ void take() { to_i8(nxt, cur); }
 
@@ -207,6 +210,133 @@ template <int NS> struct I8Strip {
         return any;
     }
     __device__ __forceinline__ int dist(const i32x16 &acc, int xn, int r) const { return qn_r[r] + xn - 2 * acc[r]; }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Column maps of the int8 sweeps: which store row a column of the sweep is, and which tiles of a split are
+// visited at all.  A kernel takes the map as a template parameter and its last argument.
+//   ColsDense     column c is row c, every tile is visited: the unfiltered sweep.
+//   ColsMasked    column c is row c; words[w] has one pass bit per row of [32 w, 32 w + 32), bits at or beyond the store's
+//                 end zero.  Splits begin at multiples of 32, so tile t of a split is word (c_begin >> 5) + t: a tile
+//                 whose word is zero is neither fetched nor multiplied, in any other a lane counts only if its bit is set.
+//   ColsIndirect  the sweep runs over the columns [0, npass) of rows[], the passing row numbers ascending: column c is
+//                 row rows[c], which is also the label.  Ascending, so column order is still label order.
+struct ColsDense {
+    static constexpr bool kMasked = false, kIndirect = false;
+};
+struct ColsMasked {
+    static constexpr bool kMasked = true, kIndirect = false;
+    const uint32_t *words;
+};
+struct ColsIndirect {
+    static constexpr bool kMasked = false, kIndirect = true;
+    const uint32_t *rows;
+};
+
+// A wave's place in its split's columns [c_begin, c_end) under a column map.  Everything below is wave-uniform except
+// the row numbers; the members a map does not use are never live.
+//   Masked: lane i holds the pass word of tile tbase + i (zero at or beyond ntiles), one load per 64 tiles; next() finds
+//   the next tile with a set bit by a ballot and leaves its word in `word`.
+//   Indirect: the row numbers of the lane's column are fetched one tile further ahead than the rows, so that the row
+//   loads go out without waiting for them: `cur` belongs to the tile being multiplied (the label), `nxt` to the tile
+//   whose rows are in flight, `ahead` to the one after it.  A lane at or beyond c_end takes the row of c_begin.
+template <class CM> struct ColCursor {
+    const uint32_t *p = nullptr; // Masked: the word of the split's tile 0; Indirect: the list
+    size_t c_begin = 0, c_end = 0;
+    uint32_t ntiles = 0;
+    uint32_t tbase = 0, win = 0, word = 0;
+    uint32_t cur = 0, nxt = 0, ahead = 0;
+    int lane = 0;
+
+    __device__ __forceinline__ void setup(const CM &cm, size_t c_begin_, size_t c_end_, uint32_t ntiles_, int lane_)
+    {
+        if constexpr (CM::kMasked) {
+            lane = lane_;
+            ntiles = ntiles_;
+            c_begin = c_begin_;
+            p = cm.words + (c_begin_ >> 5);
+            win = (uint32_t)lane < ntiles ? p[lane] : 0u;
+        }
+        if constexpr (CM::kIndirect) {
+            lane = lane_;
+            c_begin = c_begin_;
+            c_end = c_end_;
+            p = cm.rows;
+        }
+    }
+    // Masked: the first tile at or after t with a passing row (ntiles: none), its word left in `word`; else t itself
+    __device__ __forceinline__ uint32_t next(uint32_t t, uint32_t ntiles_)
+    {
+        if constexpr (!CM::kMasked) {
+            return t < ntiles_ ? t : ntiles_;
+        } else {
+            while (t < ntiles) {
+                if (t - tbase >= 64u) {
+                    tbase = t;
+                    win = t + (uint32_t)lane < ntiles ? p[t + lane] : 0u;
+                }
+                const unsigned long long nz = __ballot(win != 0u) >> (t - tbase);
+                if (nz) {
+                    const uint32_t i = __builtin_amdgcn_readfirstlane(t - tbase + (uint32_t)__ffsll((long long)nz) - 1u);
+                    word = __builtin_amdgcn_readlane(win, i);
+                    return tbase + i;
+                }
+                t = tbase + 64u;
+            }
+            return ntiles;
+        }
+    }
+    // the same in columns: the first column of the first tile at or after the one that begins at column c0 (c0 - c_begin a
+    // multiple of 32) that is visited; at or beyond c_end: none
+    __device__ __forceinline__ size_t next_col(size_t c0)
+    {
+        if constexpr (!CM::kMasked)
+            return c0;
+        else
+            return c_begin + ((size_t)next((uint32_t)((c0 - c_begin) >> 5), ntiles) << 5);
+    }
+    // does the lane's column m of the tile next() returned last pass
+    __device__ __forceinline__ bool lane_pass(int m) const
+    {
+        if constexpr (CM::kMasked)
+            return (word >> m) & 1u;
+        else
+            return true;
+    }
+    // Indirect: start the load of the row numbers of the tile that begins at column c0 (c0 < c_end)
+    __device__ __forceinline__ void ids(size_t c0)
+    {
+        if constexpr (CM::kIndirect) {
+            const size_t c = c0 + (lane & 31);
+            ahead = p[c < c_end ? c : c_begin];
+        }
+    }
+    // Indirect: the row numbers move up one tile; call with the strip's take(), and once before the first fetch
+    __device__ __forceinline__ void shift()
+    {
+        if constexpr (CM::kIndirect) {
+            cur = nxt;
+            nxt = ahead;
+        }
+    }
+    // start the row loads of the tile that begins at column c0 of the split [cb, ce) (Indirect: its ids() and a shift()
+    // came before)
+    template <int NS>
+    __device__ __forceinline__ void fetch(I8Strip<NS> &st, const uint8_t *X, size_t c0, size_t cb, size_t ce, int d) const
+    {
+        if constexpr (CM::kIndirect)
+            st.fetch_row(X, nxt, d);
+        else
+            st.fetch(X, c0, cb, ce, d);
+    }
+    // the label of the lane's column col of the tile being multiplied
+    __device__ __forceinline__ size_t label(size_t col) const
+    {
+        if constexpr (CM::kIndirect)
+            return cur;
+        else
+            return col;
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

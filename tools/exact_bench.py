@@ -12,11 +12,17 @@
      1 000), and on the small store the median distance with --dense-nq queries (the total stays below 2^32).  Every
      radius with the tile map and without it ("exact_range_map" 1 / 0): seconds of the whole call, of the count pass
      and of the fill pass (HIP events, set_profiling), results, and the ratios to the k = 1 sweep.
+  4. With --filter, on both stores, exact_search under a base filter (ivfhnsw_gpu_set_base_filter_dev):
+     an allow set of random rows at pass fractions 1, 1/2, 1/8, 1/32 and 1/1024 (on the large store 1/32 and 1/1024
+     only), k = 1 and k = 100, in the form the rule picks -- at 1/8 and 1/32 in both forms ("exact_filter_form" 0 = pass
+     words, 1 = list of passing rows) -- each beside the unfiltered call of the same run, and the time of
+     set_base_filter_dev itself.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
-                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--dense-nq 512] [--out result.json]"""
+                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--dense-nq 512]
+                                   [--out result.json]"""
 import argparse
 import json
 import os
@@ -87,6 +93,7 @@ def main():
     ap.add_argument("--no-small", action="store_true")
     ap.add_argument("--no-knn", action="store_true", help="skip the float knn comparison on the small store")
     ap.add_argument("--no-range", action="store_true", help="skip the exact range search legs")
+    ap.add_argument("--filter", action="store_true", help="add the base-filter legs (DESIGN.md 3.18)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -149,10 +156,60 @@ def main():
         g.set_profiling(False)
         g.set_option("exact_range_map", -1)
 
-    def yardstick_and_range(n, dense_radius=None):
+    def random_rows(n, fraction, seed):
+        """About fraction * n distinct random row numbers ascending, as an int32 tensor on the device (n < 2^31)."""
+        if fraction >= 1:
+            return torch.arange(n, dtype=torch.int32, device=dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(seed)
+        parts, chunk = [], 1 << 26
+        for first in range(0, n, chunk):
+            m = min(chunk, n - first)
+            hit = torch.rand(m, device=dev, generator=gen) < fraction
+            parts.append((hit.nonzero().flatten() + first).to(torch.int32))
+        return torch.cat(parts)
+
+    def filter_legs(n, name, plain_seconds, fractions):
+        """exact_search under an allow set of random rows, per fraction, k and form, beside the unfiltered call."""
+        for den in fractions:
+            labels = random_rows(n, 1.0 / den, 1000 + den)
+            torch.cuda.synchronize(dev)
+            t_set, ts_set = timed(torch, dev, lambda: g.set_base_filter_dev(labels.numel(), labels), args.warmup, args.reps,
+                                  "%s set_base_filter 1/%d" % (name, den))
+            mode, npass, total = g.base_filter_info()
+            assert npass == labels.numel() and total == n
+            r = {"what": "set_base_filter_dev", "rows": n, "fraction": "1/%d" % den, "rows_passing": npass,
+                 "seconds": round(t_set, 5), "reps": [round(x, 5) for x in ts_set]}
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+            rule_is_list = npass <= n // 8
+            forms = (0, 1) if den in (8, 32) else (-1,)
+            for k in (1, 100):
+                od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+                for form in forms:
+                    g.set_option("exact_filter_form", form)
+                    if form == 1 and not rule_is_list:
+                        g.set_base_filter_dev(labels.numel(), labels)  # the set keeps the list when the option asks for it
+                    t, ts = timed(torch, dev, lambda: g.exact_search_dev(nq, q, d, k, od, ol), args.warmup, args.reps,
+                                  "%s filtered 1/%d k=%d form=%d" % (name, den, k, form))
+                    used = "list" if (form == 1 or (form == -1 and rule_is_list)) else "words"
+                    r = {"what": "exact_search_dev filtered", "rows": n, "d": d, "nq": nq, "k": k, "fraction": "1/%d" % den,
+                         "rows_passing": npass, "form": used, "forced": form != -1, "rule_picks": "list" if rule_is_list else "words",
+                         "seconds": round(t, 5), "reps": [round(x, 5) for x in ts], "unfiltered_s": round(plain_seconds[k], 5),
+                         "over_unfiltered": round(t / plain_seconds[k], 4)}
+                    result["rows"].append(r)
+                    print(json.dumps(r), flush=True)
+            g.set_option("exact_filter_form", -1)
+            del labels
+        g.clear_base_filter()
+
+    def yardstick_and_range(n, dense_radius=None, fractions=(1, 2, 8, 32, 1024)):
         name = "%d rows" % n
         r1, _, _ = exact(n, 1, name)
-        _, _, od100 = exact(n, 100, name)
+        r100, _, od100 = exact(n, 100, name)
+        if args.filter:
+            filter_legs(n, name, {1: r1["seconds"], 100: r100["seconds"]}, fractions)
         if not args.no_range:
             range_legs(n, name, r1["seconds"], od100[:, 9], od100[:, 99], dense_radius)
 
@@ -185,7 +242,7 @@ def main():
     if not args.no_big:
         n = args.rows
         fill_store(g, torch, dev, n, d, 99)
-        yardstick_and_range(n)
+        yardstick_and_range(n, fractions=(32, 1024))
     g.close()
     if args.out:
         with open(args.out, "w") as f:

@@ -10,8 +10,13 @@ With --radius R the exact RANGE search runs instead (ivfhnsw_gpu_exact_range_sea
 (uint64 [nq + 1]), labels (int64) and distances (float32) -- query q owns entries [lims[q], lims[q + 1]), every base row
 with distance < R in ascending label -- and radius; --k is ignored.  read_range reads it back.
 
-usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N]
-       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N]"""
+With --allow FILE or --deny FILE (one of them; an .ivecs or .npy file of labels = row numbers of the base) the truth of a
+FILTERED workload is written: the base filter (ivfhnsw_gpu_set_base_filter) is installed before either
+search, so only rows in the allow set (not in the deny set) are returned.  The .npz of the range form then also holds
+filter_mode (0 allow, 1 deny; -1 without a filter) and rows_passing; read_range_filter reads them.
+
+usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]"""
 import argparse
 import os
 import sys
@@ -50,11 +55,36 @@ def read_ivecs(path):
     return rec[:, 1:].astype(np.int64)
 
 
-def write_range(path, lims, distances, labels, radius):
-    """The result of an exact range search as an .npz (written to exactly `path`)."""
+def write_range(path, lims, distances, labels, radius, filter_mode=-1, rows_passing=None):
+    """The result of an exact range search as an .npz (written to exactly `path`); under a base filter its mode (0 allow,
+    1 deny) and the rows of the base that pass."""
+    extra = {} if rows_passing is None else {"rows_passing": np.uint64(rows_passing)}
     with open(path, "wb") as f:
         np.savez(f, lims=np.asarray(lims, np.uint64), labels=np.asarray(labels, np.int64),
-                 distances=np.asarray(distances, np.float32), radius=np.float32(radius))
+                 distances=np.asarray(distances, np.float32), radius=np.float32(radius), filter_mode=np.int32(filter_mode),
+                 **extra)
+
+
+def read_range_filter(path):
+    """(filter_mode, rows_passing) of a file --radius wrote: (-1, None) when it was written without a base filter."""
+    with np.load(path) as z:
+        mode = int(z["filter_mode"]) if "filter_mode" in z else -1
+        return mode, (int(z["rows_passing"]) if "rows_passing" in z else None)
+
+
+def read_labels(path):
+    """The labels of an --allow / --deny file as uint32 [n]: every value of an .ivecs file (records of any length), or
+    the integers of an .npy array of any shape."""
+    if path.endswith(".npy"):
+        lab = np.load(path)
+        if lab.dtype.kind not in "iu":
+            raise ValueError("%s: labels must be integers, not %s" % (path, lab.dtype))
+        lab = lab.ravel().astype(np.int64)
+    else:
+        lab = read_ivecs(path).ravel()
+    if lab.size and (lab.min() < 0 or lab.max() >= 1 << 32):
+        raise ValueError("%s: labels must fit 32 bits unsigned" % path)
+    return lab.astype(np.uint32)
 
 
 def read_range(path):
@@ -87,28 +117,37 @@ def read_bvecs_image(path):
     return img, d
 
 
-def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20):
-    """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query."""
+def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False):
+    """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query; with `labels`
+    only of the rows whose number is in them (deny: is not)."""
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
         n, d = g.upload_base_bvecs(base_path, chunk_rows=chunk_rows, rows=rows)
         if d != dq:
             raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        if labels is not None:
+            g.set_base_filter(labels, deny=deny)
         _, lab = g.exact_search(img[:, 4:], k)
     finally:
         g.close()
     return lab
 
 
-def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20):
-    """(lims, distances, labels) of every base row within the radius of every query, ascending label per query."""
+def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False,
+                       info=None):
+    """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
+    `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing."""
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
         n, d = g.upload_base_bvecs(base_path, chunk_rows=chunk_rows, rows=rows)
         if d != dq:
             raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        if labels is not None:
+            g.set_base_filter(labels, deny=deny)
+            if info is not None:
+                info["rows_passing"] = g.base_filter_info()[1]
         return g.exact_range_search(img[:, 4:], radius)
     finally:
         g.close()
@@ -124,16 +163,24 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--rows", type=int, default=None, help="only the base file's first N records")
     ap.add_argument("--device", type=int, default=0)
+    flt = ap.add_mutually_exclusive_group()
+    flt.add_argument("--allow", default=None, help="an .ivecs or .npy file of labels: only these rows of the base are returned")
+    flt.add_argument("--deny", default=None, help="an .ivecs or .npy file of labels: these rows of the base are never returned")
     args = ap.parse_args(argv)
+    labels = read_labels(args.allow or args.deny) if (args.allow or args.deny) else None
+    deny = args.deny is not None
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
     if args.radius is not None:
-        lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device)
-        write_range(args.out, lims, dist, lab, args.radius)
+        info = {}
+        lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device,
+                                             labels=labels, deny=deny, info=info)
+        write_range(args.out, lims, dist, lab, args.radius, filter_mode=-1 if labels is None else int(deny),
+                    rows_passing=info.get("rows_passing"))
         print("%s: %d queries, %d rows within %g" % (args.out, lims.size - 1, lab.size, args.radius))
         return
-    lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device)
+    lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device, labels=labels, deny=deny)
     write_ivecs(args.out, lab)
     print("%s: %d queries x %d labels" % (args.out, lab.shape[0], lab.shape[1]))
 

@@ -11,7 +11,10 @@
   against the exact one (ivfhnsw_gpu_exact_range_search) at radii taken as quantiles of the exact 10th
   neighbour's distance: recall |IVF range & exact range| / |exact range| and precision |IVF range & exact range| /
   |IVF range| of the label sets (the ADC distance is an approximation: neither is 1), and the mean results per query.
-usage: python tools/range_bench.py [--workload NAME] [--nq 10000] [--reps 10] [--recall]"""
+  --recall --allow-fraction F: the same under a filter -- a random allow set of F * n rows is installed as the index's
+  label filter and as the base filter (ids are row numbers on this corpus), so the filtered IVF range
+  search is scored against the filtered exact one.
+usage: python tools/range_bench.py [--workload NAME] [--nq 10000] [--reps 10] [--recall [--allow-fraction F]]"""
 import argparse
 import json
 import os
@@ -29,7 +32,7 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def recall(pkg, quantiles=(0.1, 0.5, 0.9)):
+def recall(pkg, quantiles=(0.1, 0.5, 0.9), allow_fraction=None):
     import rerank_ref
     c = rerank_ref.uint8_recall_corpus(pkg, seed=77)
     g = pkg.GpuIndex(0)
@@ -40,6 +43,13 @@ def recall(pkg, quantiles=(0.1, 0.5, 0.9)):
     qf = c["queries"]
     q8 = qf.astype(np.uint8)  # integer-valued, 0..255
     nq, n = len(q8), len(c["base"])
+    npass = n
+    if allow_fraction is not None:  # the same rows pass the IVF search and the exact one
+        npass = max(1, int(allow_fraction * n))
+        allow = np.sort(np.random.default_rng(78).choice(n, npass, replace=False)).astype(np.uint32)
+        g.set_filter(allow)
+        g.set_base_filter(allow)
+        assert g.filter_info()[1] == g.base_filter_info()[1] == npass
     kd, _ = g.exact_search(q8, 10)
     rows = []
     for x in quantiles:
@@ -57,7 +67,8 @@ def recall(pkg, quantiles=(0.1, 0.5, 0.9)):
             log("[range_bench] radius %.0f (q%.2f) nprobe %d: exact %.2f / query, ivf %.2f / query, recall %.4f, precision %.4f"
                 % (r, x, nprobe, row["exact_per_query"], row["ivf_per_query"], row["recall"], row["precision"]))
     g.close()
-    return {"corpus": "uint8_recall_corpus(seed=77)", "rows": n, "nq": nq, "range_recall": rows}
+    return {"corpus": "uint8_recall_corpus(seed=77)", "rows": n, "rows_passing": npass, "allow_fraction": allow_fraction, "nq": nq,
+            "range_recall": rows}
 
 
 def main():
@@ -66,12 +77,16 @@ def main():
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--recall", action="store_true", help="recall and precision against the exact range search instead")
+    ap.add_argument("--allow-fraction", type=float, default=None,
+                    help="with --recall: score under a random allow set of this fraction of the rows")
     args = ap.parse_args()
+    if args.allow_fraction is not None and (not args.recall or not 0 < args.allow_fraction <= 1):
+        ap.error("--allow-fraction F goes with --recall, 0 < F <= 1")
     import torch
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
     if args.recall:
-        print(json.dumps(recall(pkg)))
+        print(json.dumps(recall(pkg, allow_fraction=args.allow_fraction)))
         return
     import bench
     import synth
