@@ -6,7 +6,8 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), range_search(),
+// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
+// clear_id_filter_slot(), search_batch_slots(), range_search_slots(), range_search(),
 // reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
@@ -125,6 +126,18 @@ public:
     /// Throws with IVFHNSW_SHARDS > 1 (sharded handles have no filter).
     void set_id_filter(size_t n, const idx_t *xids, bool deny = false);
     void clear_id_filter();
+    /// Extension: an IDSelector PER QUERY (ivfhnsw_gpu_set_filter_slot).  An index holds up to 32 id sets
+    /// ("slots"), each allow or deny as set_id_filter's; search_batch_slots / range_search_slots take one byte per query
+    /// naming the slot that query is filtered by (0xff: by none), and answer each query as search_batch / range_search
+    /// would with that slot's set installed by set_id_filter.  A slot that was never set, or was cleared (slot -1: every
+    /// slot), passes nothing.  Independent of set_id_filter, and not combined with it: the _slots calls throw while a
+    /// set_id_filter filter is installed.  The sets are kept on the host beside the object and installed on the device
+    /// copy whenever that is made or remade, at once if it is current.  Non-virtual.  All throw with IVFHNSW_SHARDS > 1.
+    void set_id_filter_slot(unsigned slot, size_t n, const idx_t *xids, bool deny = false);
+    void clear_id_filter_slot(int slot = -1);
+    void search_batch_slots(size_t nq, size_t k, const float *x, const uint8_t *slots, float *distances, long *labels);
+    void range_search_slots(size_t nq, const float *x, const uint8_t *slots, float radius, std::vector<size_t> &lims,
+                            std::vector<float> &distances, std::vector<long> &labels);
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

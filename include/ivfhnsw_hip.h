@@ -255,6 +255,48 @@ int ivfhnsw_gpu_set_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
 int ivfhnsw_gpu_clear_filter(ivfhnsw_gpu *h);
 int ivfhnsw_gpu_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
 
+/* Filter slots: a label filter PER QUERY.  Beside its one filter a handle holds up to
+ * IVFHNSW_FILTER_SLOTS label sets, each a set of uint32 labels and a mode exactly as ivfhnsw_gpu_set_filter takes them
+ * (any label value, repeats count once, an empty allow set passes nothing, an empty deny set everything).  A slot that
+ * was never set, or was cleared, passes nothing.  The _slots forms of search and range search take one byte per query:
+ * query q with query_slots[q] == s answers, bit for bit, what the plain call answers on the same handle with
+ * ivfhnsw_gpu_set_filter(labels of s, mode of s) installed -- labels, distance bits, unfilled places FLT_MAX / -1, the
+ * heap array of heap_order = 1 (any k), out_keys, candidate streams, resolve_keys*, range lims / distances / labels in
+ * scan order -- and with IVFHNSW_SLOT_NONE what it answers with no filter installed.  Everything said above about a
+ * filtered call holds per query: the same lists and sub-groups in the same order, max_codes and pruning count every
+ * stored code, ivfhnsw_gpu_last_scan_counts is the unfiltered call's.  ivfhnsw_gpu_last_scan_kernel reports the
+ * unfiltered name with "+slots" appended; a _slots call runs plan, table and scan (never the one-launch tail or the
+ * pipelined scan), large batches split in two parts as plain ones do.  query_slots == NULL is the plain call.
+ *   Slots and the handle's filter are independent state: plain calls never read slots, and a _slots call on a handle
+ *   that has a set_filter filter installed -> IVFHNSW_ERR_STATE (the two are not combined).
+ * ivfhnsw_gpu_set_filter_slot replaces the slot's earlier set; the new one is built beside the installed state, so any
+ *   error leaves every slot as it was.  Synchronous on the handle's stream.  _dev: d_labels in device memory (4-byte
+ *   aligned).  ivfhnsw_gpu_clear_filter_slot: slot -1 = every slot; succeeds on a slot that is not set.
+ *   ivfhnsw_gpu_upload_ivf clears every slot.  ivfhnsw_gpu_filter_slot_info: *mode = the slot's mode or -1,
+ *   *rows_passing = resident rows that pass it (0 for a slot that is not set), *rows_total = resident rows; each nullable.
+ * Query slot bytes: the host forms check them before anything is launched or written, a byte in 32..254 ->
+ *   IVFHNSW_ERR_INVALID.  The _dev forms read nothing back: any byte other than 0xff that names no installed slot passes
+ *   nothing (the kernels check the byte against the planes the handle holds).
+ * After a successful append_ivf, add, remove_ids, append_grouping or add_groups every installed slot holds for the
+ *   updated lists (all slots are judged again in one pass over the new ids); an update that fails leaves tables and
+ *   slots as they were.  A view reads the slots its parent held when the view was created (the internal view of split
+ *   batches: at every call); set / clear on a view -> IVFHNSW_ERR_STATE.
+ * Memory, all counted by ivfhnsw_gpu_memory_bytes: (highest slot in use + 1) planes of 8 * max(ceil(rows / 64), 1)
+ *   bytes -- one pass bit per resident row and plane -- plus, per slot with a non-empty set, 4 * (max label / 32 + 1)
+ *   bytes of label bitmap (<= 512 MB), kept so that updates can judge new rows.
+ * Errors: slot >= IVFHNSW_FILTER_SLOTS, an unknown mode, null labels with n > 0, a misaligned d_labels ->
+ *   IVFHNSW_ERR_INVALID; set or clear before upload_ivf, on a view, on a handle with shard_world > 1 -> IVFHNSW_ERR_STATE;
+ *   a _slots call on a sharded handle -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM; whatever the plain
+ *   call refuses for the same arguments is refused with its status.
+ * Not built: a slot AND the handle's filter; slots for search_reconstruct, search_sharded, sharded handles and the base
+ *   filter of the exact calls; more than 32 slots. */
+#define IVFHNSW_FILTER_SLOTS 32
+#define IVFHNSW_SLOT_NONE 0xff
+int ivfhnsw_gpu_set_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode);
+int ivfhnsw_gpu_set_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, int mode);
+int ivfhnsw_gpu_clear_filter_slot(ivfhnsw_gpu *h, int slot); /* -1: every slot */
+int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */
@@ -352,6 +394,15 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
                            const ivfhnsw_search_params *params, float *d_distances, int64_t *d_labels,
                            int64_t *d_out_keys);
 
+/* ivfhnsw_gpu_search / ivfhnsw_gpu_search_dev with a filter slot per query (see "Filter slots" above): query_slots [nq]
+ * bytes, host memory for the host form, device memory for the _dev form; NULL = the plain call. */
+int ivfhnsw_gpu_search_slots(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                             const float *coarse_dists, const ivfhnsw_search_params *params, const uint8_t *query_slots,
+                             float *distances, int64_t *labels);
+int ivfhnsw_gpu_search_slots_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                 const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                 const uint8_t *d_query_slots, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
+
 /* Multi-GPU merge helper: given keys already MIN-reduced over the shards, resolve the
  * labels this shard owns ([nq*k]; -1 where the winner lives on another shard) from the scan plan of
  * the last search_dev call, and decode the distances.  The caller then MAX-reduces the labels. */
@@ -435,6 +486,13 @@ int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, co
 int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                                  const float *d_coarse_dists, const ivfhnsw_search_params *params, float radius,
                                  uint64_t *d_lims, uint64_t *total);
+/* ... and with a filter slot per query ("Filter slots" above); results are read with range_results as usual */
+int ivfhnsw_gpu_range_search_slots(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                   const float *coarse_dists, const ivfhnsw_search_params *params, const uint8_t *query_slots,
+                                   float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                       const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                       const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("IVFHNSW_HIP_LIB") or os.path.join(_HERE, "libivfhnsw_
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
 FILTER_ALLOW, FILTER_DENY = 0, 1
+FILTER_SLOTS, SLOT_NONE = 32, 0xff
 RECON_ORIGINAL, RECON_ROTATED = 0, 1
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
@@ -48,6 +49,9 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_range_results_dev",
     "ivfhnsw_gpu_set_base_filter", "ivfhnsw_gpu_set_base_filter_dev", "ivfhnsw_gpu_clear_base_filter",
     "ivfhnsw_gpu_base_filter_info",
+    "ivfhnsw_gpu_set_filter_slot", "ivfhnsw_gpu_set_filter_slot_dev", "ivfhnsw_gpu_clear_filter_slot",
+    "ivfhnsw_gpu_filter_slot_info", "ivfhnsw_gpu_search_slots", "ivfhnsw_gpu_search_slots_dev",
+    "ivfhnsw_gpu_range_search_slots", "ivfhnsw_gpu_range_search_slots_dev",
 )
 
 
@@ -177,6 +181,18 @@ def lib():
         L.ivfhnsw_gpu_set_filter_dev.argtypes = L.ivfhnsw_gpu_set_filter.argtypes
         L.ivfhnsw_gpu_clear_filter.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_set_filter_slot.argtypes = [C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_set_filter_slot_dev.argtypes = L.ivfhnsw_gpu_set_filter_slot.argtypes
+        L.ivfhnsw_gpu_clear_filter_slot.argtypes = [C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_filter_slot_info.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(SearchParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_search_slots_dev.argtypes = L.ivfhnsw_gpu_search_slots.argtypes + [C.c_void_p]
+        L.ivfhnsw_gpu_range_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(SearchParams), C.c_void_p, C.c_float, C.c_void_p,
+                                                     C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_range_search_slots_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
         L.ivfhnsw_gpu_set_base_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
         L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
@@ -405,6 +421,29 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_filter_info(self._h, C.byref(m), C.byref(a), C.byref(b)))
         return int(m.value), int(a.value), int(b.value)
 
+    # ---- filter slots: a label filter per query (ivfhnsw_gpu_set_filter_slot) -----------------------
+    def set_filter_slot(self, slot, labels, deny=False):
+        """Slot `slot` (0..FILTER_SLOTS-1) holds the set `labels`, allow or deny as set_filter; replaces the slot's earlier
+        set.  The _slots searches name a slot per query."""
+        lab = _np(labels, np.uint32).ravel()
+        _check(lib().ivfhnsw_gpu_set_filter_slot(self._h, slot, lab.size, _ptr(lab) if lab.size else None,
+                                                 FILTER_DENY if deny else FILTER_ALLOW))
+
+    def set_filter_slot_dev(self, slot, n, d_labels, deny=False):
+        """The same on a device buffer (torch CUDA tensor or raw address)."""
+        _check(lib().ivfhnsw_gpu_set_filter_slot_dev(self._h, slot, n, _devptr(d_labels),
+                                                     FILTER_DENY if deny else FILTER_ALLOW))
+
+    def clear_filter_slot(self, slot=None):
+        """The slot passes nothing afterwards; None: every slot."""
+        _check(lib().ivfhnsw_gpu_clear_filter_slot(self._h, -1 if slot is None else slot))
+
+    def filter_slot_info(self, slot):
+        """(mode or -1, rows_passing, rows_total) of one slot."""
+        m, a, b = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_filter_slot_info(self._h, slot, C.byref(m), C.byref(a), C.byref(b)))
+        return int(m.value), int(a.value), int(b.value)
+
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)
         n = _np(nn_centroid_idxs, np.uint32)
@@ -540,6 +579,33 @@ class GpuIndex:
                                             _devptr(d_coarse_dists), C.byref(p), _devptr(d_distances),
                                             _devptr(d_labels), _devptr(d_out_keys)))
 
+    def search_slots(self, queries, k, query_slots, nprobe, max_codes, coarse_ids=None, coarse_dists=None, efSearch=0,
+                     do_pruning=False, heap_order=False):
+        """search() with a filter slot per query: query_slots [nq] bytes, each a slot or SLOT_NONE (no filter); None is
+        search() itself (ivfhnsw_gpu_search_slots)."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_slots(self._h, nq, k, _ptr(q), _ptr(cid), _ptr(cd), C.byref(p), _ptr(qs),
+                                              _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def search_slots_dev(self, nq, k, d_queries, d_query_slots, d_distances, d_labels, nprobe, max_codes,
+                         d_coarse_ids=None, d_coarse_dists=None, efSearch=0, do_pruning=False, d_out_keys=None,
+                         heap_order=False):
+        """search_dev() with a filter slot per query (d_query_slots: [nq] bytes in device memory, not checked on the host:
+        a byte that names no installed slot passes nothing)."""
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_slots_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                  _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_slots),
+                                                  _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
+
     # ---- reconstruction of stored vectors (ivfhnsw_gpu_reconstruct*, DESIGN.md 3.16) ---------------------------------
     def locate(self, labels):
         """(rows int64 [n], counts uint32 [n]): the lowest resident row bearing each label (-1 = none) and how many rows
@@ -642,6 +708,33 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_range_search_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
                                                   _devptr(d_coarse_dists), C.byref(p), C.c_float(radius), _devptr(d_lims),
                                                   C.byref(total)))
+        return int(total.value)
+
+    def range_search_slots(self, queries, radius, query_slots, nprobe, max_codes, efSearch=0, do_pruning=False,
+                           coarse_ids=None, coarse_dists=None):
+        """range_search() with a filter slot per query (query_slots as search_slots takes them)."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_slots(self._h, nq, _ptr(q) if nq else None, _ptr(cid), _ptr(cd), C.byref(p),
+                                                    _ptr(qs), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def range_search_slots_dev(self, nq, d_queries, radius, d_query_slots, d_lims, nprobe, max_codes, efSearch=0,
+                               do_pruning=False, d_coarse_ids=None, d_coarse_dists=None):
+        """range_search_dev() with a filter slot per query (d_query_slots in device memory)."""
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_slots_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                        _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_slots),
+                                                        C.c_float(radius), _devptr(d_lims), C.byref(total)))
         return int(total.value)
 
     def range_results(self, first, count):

@@ -87,6 +87,136 @@ static int set_filter_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, u
     return IVFHNSW_OK;
 }
 
+// ---- filter slots: the same label sets, up to IVFHNSW_FILTER_SLOTS of them, each marked into its own
+// plane of fs_planes; a _slots call names a slot per query.
+
+void slots_drop(ivfhnsw_gpu *h)
+{
+    h->fs = SlotMask{nullptr, 0, 0, nullptr};
+    h->fs_planes.release();
+    for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++) {
+        h->fs_bits[s].release();
+        h->fs_mode[s] = -1;
+        h->fs_has_bits[s] = false;
+        h->fs_max_label[s] = 0;
+        h->fs_pass[s] = 0;
+    }
+}
+
+int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &planes, uint64_t *pass)
+{
+    const uint32_t np = h->fs.nplanes;
+    const uint64_t stride = slot_plane_stride(n_local);
+    int rc;
+    if ((rc = planes.ensure((size_t)np * stride * sizeof(uint32_t))) ||
+        (rc = h->fs_count.ensure(kFilterSlots * sizeof(unsigned long long))))
+        return rc;
+    FilterSlotSets sets{};
+    for (uint32_t s = 0; s < np; s++) {
+        sets.bits[s] = h->fs_has_bits[s] ? h->fs_bits[s].as<uint32_t>() : nullptr;
+        sets.max_label[s] = h->fs_max_label[s];
+        sets.set[s] = h->fs_mode[s] >= 0;
+        sets.deny[s] = h->fs_mode[s] == IVFHNSW_FILTER_DENY;
+    }
+    if (n_local == 0) // no kernel runs: the one word of every plane
+        HIP_TRY(hipMemsetAsync(planes.p, 0, (size_t)np * stride * sizeof(uint32_t), h->stream));
+    unsigned long long cnt[kFilterSlots] = {0};
+    HIP_TRY(launch_filter_mark_slots(h->stream, ids, n_local, sets, np, planes.as<unsigned long long>(), stride / 2,
+                                     h->fs_count.as<unsigned long long>()));
+    HIP_TRY(hipMemcpyAsync(cnt, h->fs_count.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++)
+        pass[s] = cnt[s];
+    return IVFHNSW_OK;
+}
+
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who)
+{
+    if (h->t.shard_world > 1)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no filter slots", who,
+                    h->t.shard_rank, h->t.shard_world);
+    if (h->filter_mode >= 0)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle has a set_filter filter installed; a call is filtered by that or by "
+                                       "slots, not both (clear_filter first)", who);
+    return IVFHNSW_OK;
+}
+
+int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who)
+{
+    for (size_t q = 0; q < nq; q++)
+        if (query_slots[q] >= IVFHNSW_FILTER_SLOTS && query_slots[q] != IVFHNSW_SLOT_NONE)
+            return fail(IVFHNSW_ERR_INVALID, "%s: query %zu names slot %u; slots are 0..%d or IVFHNSW_SLOT_NONE", who, q,
+                        (unsigned)query_slots[q], IVFHNSW_FILTER_SLOTS - 1);
+    return IVFHNSW_OK;
+}
+
+// the planes of the handle in a buffer of np planes (np above or below what it holds now), planes the handle lacks zero
+static int planes_resized(ivfhnsw_gpu *h, uint32_t np, DevBuf &out)
+{
+    const size_t pb = (size_t)slot_plane_stride(h->n_local) * sizeof(uint32_t);
+    const uint32_t keep = std::min(np, h->fs.nplanes);
+    int rc = out.ensure((size_t)np * pb);
+    if (rc)
+        return rc;
+    if (keep)
+        HIP_TRY(hipMemcpyAsync(out.p, h->fs_planes.p, keep * pb, hipMemcpyDeviceToDevice, h->stream));
+    if (np > keep)
+        HIP_TRY(hipMemsetAsync(out.as<char>() + keep * pb, 0, (np - keep) * pb, h->stream));
+    return IVFHNSW_OK;
+}
+
+static void planes_install(ivfhnsw_gpu *h, DevBuf &planes, uint32_t np)
+{
+    std::swap(h->fs_planes, planes);
+    planes.release();
+    h->fs = SlotMask{np ? h->fs_planes.as<uint32_t>() : nullptr, np ? (uint32_t)slot_plane_stride(h->n_local) : 0u, np, nullptr};
+}
+
+// As set_filter_core, for one slot.  Label bitmap, the slot's mask and (a slot beyond the planes held) a larger set of
+// planes are all built beside the installed state, which is touched only when nothing can fail any more: every error
+// leaves every slot as it was.
+static int set_slot_core(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, uint32_t max_label, int mode)
+{
+    DevBuf bits, mask, planes;
+    int rc = IVFHNSW_OK;
+    uint64_t pass = 0;
+    const bool grow = slot >= h->fs.nplanes;
+    const size_t pb = (size_t)slot_plane_stride(h->n_local) * sizeof(uint32_t);
+    auto body = [&]() -> int {
+        if (n) {
+            if ((rc = bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))))
+                return rc;
+            HIP_TRY(launch_remove_bits(h->stream, d_labels, n, max_label, bits.as<uint32_t>()));
+        }
+        if ((rc = mark_rows(h, h->t.ids, h->n_local, n ? bits.as<uint32_t>() : nullptr, max_label, mode, mask, &pass)))
+            return rc;
+        if (grow && (rc = planes_resized(h, slot + 1, planes)))
+            return rc;
+        // the last fallible step writes the plane: into the new buffer, or over the slot's own plane, which only this
+        // slot's queries read
+        char *dst = (grow ? planes.as<char>() : h->fs_planes.as<char>()) + (size_t)slot * pb;
+        HIP_TRY(hipMemcpyAsync(dst, mask.p, pb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return IVFHNSW_OK;
+    };
+    rc = body();
+    mask.release();
+    if (rc) {
+        bits.release();
+        planes.release();
+        return rc;
+    }
+    if (grow)
+        planes_install(h, planes, slot + 1);
+    std::swap(h->fs_bits[slot], bits);
+    bits.release(); // the slot's earlier set
+    h->fs_mode[slot] = mode;
+    h->fs_has_bits[slot] = n != 0;
+    h->fs_max_label[slot] = n ? max_label : 0;
+    h->fs_pass[slot] = pass;
+    return IVFHNSW_OK;
+}
+
 static int check_args(size_t n, const uint32_t *labels, int mode, const char *who)
 {
     if (n && !labels)
@@ -157,6 +287,109 @@ int ivfhnsw_gpu_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, u
         *mode = h->filter_mode;
     if (rows_passing)
         *rows_passing = h->filter_mode >= 0 ? h->f_pass : h->n_local;
+    if (rows_total)
+        *rows_total = h->n_local;
+    return IVFHNSW_OK;
+}
+
+// ---- filter slots
+
+static int slot_args(unsigned slot, size_t n, const uint32_t *labels, int mode, const char *who)
+{
+    if (slot >= IVFHNSW_FILTER_SLOTS)
+        return fail(IVFHNSW_ERR_INVALID, "%s: slot %u, a handle has slots 0..%d", who, slot, IVFHNSW_FILTER_SLOTS - 1);
+    return check_args(n, labels, mode, who);
+}
+
+int ivfhnsw_gpu_set_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode)
+{
+    int rc = filter_state(h, "set_filter_slot");
+    if (rc || (rc = slot_args(slot, n, labels, mode, "set_filter_slot")))
+        return rc;
+    uint32_t mx = 0;
+    for (size_t i = 0; i < n; i++)
+        mx = std::max(mx, labels[i]);
+    if (n) {
+        if ((rc = h->fs_labels.ensure(n * sizeof(uint32_t))))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(h->fs_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    }
+    rc = set_slot_core(h, slot, n, h->fs_labels.as<uint32_t>(), mx, mode);
+    h->fs_labels.release(); // staging of this call only
+    return rc;
+}
+
+int ivfhnsw_gpu_set_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, int mode)
+{
+    int rc = filter_state(h, "set_filter_slot_dev");
+    if (rc || (rc = slot_args(slot, n, d_labels, mode, "set_filter_slot_dev")))
+        return rc;
+    if ((uintptr_t)d_labels & 3)
+        return fail(IVFHNSW_ERR_INVALID, "set_filter_slot_dev: labels must be 4-byte aligned");
+    uint32_t mx = 0;
+    if (n) {
+        if ((rc = h->f_count.ensure(sizeof(unsigned long long))))
+            return rc;
+        HIP_TRY(hipMemsetAsync(h->f_count.p, 0, sizeof(uint32_t), h->stream));
+        HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->f_count.as<uint32_t>()));
+        HIP_TRY(hipMemcpyAsync(&mx, h->f_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return set_slot_core(h, slot, n, d_labels, mx, mode);
+}
+
+int ivfhnsw_gpu_clear_filter_slot(ivfhnsw_gpu *h, int slot)
+{
+    int rc = filter_state(h, "clear_filter_slot");
+    if (rc)
+        return rc;
+    if (slot < -1 || slot >= IVFHNSW_FILTER_SLOTS)
+        return fail(IVFHNSW_ERR_INVALID, "clear_filter_slot: slot %d, a handle has slots 0..%d (-1: every slot)", slot,
+                    IVFHNSW_FILTER_SLOTS - 1);
+    if (slot >= 0 && h->fs_mode[slot] < 0)
+        return IVFHNSW_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream)); // searches in flight still read the planes (a split batch joins this stream)
+    if (slot < 0) {
+        slots_drop(h);
+        return IVFHNSW_OK;
+    }
+    // planes reach to the highest slot in use: clearing that one gives the planes above the next back
+    uint32_t np = 0;
+    for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++)
+        if (s != slot && h->fs_mode[s] >= 0)
+            np = (uint32_t)s + 1;
+    const size_t pb = (size_t)slot_plane_stride(h->n_local) * sizeof(uint32_t);
+    if (np < h->fs.nplanes) {
+        DevBuf planes;
+        if (np && (rc = planes_resized(h, np, planes))) {
+            planes.release();
+            return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        planes_install(h, planes, np);
+    } else {
+        HIP_TRY(hipMemsetAsync(h->fs_planes.as<char>() + (size_t)slot * pb, 0, pb, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->fs_bits[slot].release();
+    h->fs_mode[slot] = -1;
+    h->fs_has_bits[slot] = false;
+    h->fs_max_label[slot] = 0;
+    h->fs_pass[slot] = 0;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint64_t *rows_passing, uint64_t *rows_total)
+{
+    if (!h)
+        return fail(IVFHNSW_ERR_INVALID, "null handle");
+    if (slot >= IVFHNSW_FILTER_SLOTS)
+        return fail(IVFHNSW_ERR_INVALID, "filter_slot_info: slot %u, a handle has slots 0..%d", slot, IVFHNSW_FILTER_SLOTS - 1);
+    const ivfhnsw_gpu *holder = h->is_view && h->parent ? h->parent : h;
+    if (mode)
+        *mode = holder->fs_mode[slot];
+    if (rows_passing)
+        *rows_passing = holder->fs_mode[slot] >= 0 ? holder->fs_pass[slot] : 0;
     if (rows_total)
         *rows_total = h->n_local;
     return IVFHNSW_OK;

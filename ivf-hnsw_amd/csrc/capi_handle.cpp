@@ -93,6 +93,7 @@ void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent)
     view->filter_mode = parent->filter_mode; // the view filters as its parent does at this moment
     view->fmask = parent->fmask;
     view->f_pass = parent->f_pass;
+    view->fs = parent->fs; // ... and reads the filter slots its parent holds
 }
 
 int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool need_ivf)

@@ -137,6 +137,7 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
+    X(fs_planes) X(fs_labels) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: fs_bits), staging of labels, counts and a host call's slot bytes */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_labels) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; staging */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
@@ -159,6 +160,8 @@ struct ivfhnsw_gpu {
 #define IVFHNSW_X(name) f(name);
         IVFHNSW_GPU_DEVBUFS(IVFHNSW_X)
 #undef IVFHNSW_X
+        for (DevBuf &b : fs_bits)
+            f(b);
     }
     HostBuf p_in, p_out; // pinned: small batches of the host-pointer entry point
 
@@ -184,6 +187,19 @@ struct ivfhnsw_gpu {
     bool f_has_bits = false;
     uint32_t f_max_label = 0;
     uint64_t f_pass = 0;
+
+    // filter slots (capi_filter.cpp): up to IVFHNSW_FILTER_SLOTS label sets, named per query by the _slots
+    // calls.  fs is what their scans read (its `slots` stays null: the bytes travel with the call): fs.nplanes planes of
+    // fs.stride words in the handle's own fs_planes, on a view the planes its parent held when follow_parent ran.  Per
+    // slot: mode (-1 = not set; its plane, where there is one, is zero), the label set over [0, fs_max_label] in fs_bits
+    // (fs_has_bits false = the empty set), the rows that pass.
+    SlotMask fs{nullptr, 0, 0, nullptr};
+    DevBuf fs_bits[IVFHNSW_FILTER_SLOTS];
+    int fs_mode[IVFHNSW_FILTER_SLOTS];
+    bool fs_has_bits[IVFHNSW_FILTER_SLOTS] = {};
+    uint32_t fs_max_label[IVFHNSW_FILTER_SLOTS] = {};
+    uint64_t fs_pass[IVFHNSW_FILTER_SLOTS] = {};
+    ivfhnsw_gpu() { std::fill(fs_mode, fs_mode + IVFHNSW_FILTER_SLOTS, -1); }
 
     // the base filter of the exact calls (capi_base_filter.cpp), on the handle that holds the store: a view
     // reads its parent's at the call.  bf_mode -1 = none.  bf_words: one pass bit per row; bf_rows (bf_has_rows): the
@@ -271,6 +287,16 @@ void point_at_lists(ivfhnsw_gpu *h, uint64_t n_local);
 // with the stream drained; the handle is not touched.
 int filter_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &mask, uint64_t *pass);
 void filter_drop(ivfhnsw_gpu *h); // the handle holds no filter afterwards (buffers released)
+// Filter slots.  The words between two planes over n_local rows: whole 64-bit words, never zero.
+inline uint64_t slot_plane_stride(uint64_t n_local) { return std::max<uint64_t>((n_local + 63) / 64, 1) * 2; }
+// Every installed slot of h judged over ids [n_local] in one pass: planes (allocated here, h->fs.nplanes of them at
+// slot_plane_stride(n_local)) and the rows that pass each.  Returns with the stream drained; the handle is not touched.
+int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &planes, uint64_t *pass);
+void slots_drop(ivfhnsw_gpu *h); // the handle holds no slot afterwards (buffers released)
+// what a _slots entry point checks first, behind the plain call's own guard
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who);
+// the slot bytes of a host call: each is below IVFHNSW_FILTER_SLOTS or IVFHNSW_SLOT_NONE
+int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who);
 
 // The five arrays that make up the resident lists, built BESIDE the handle's: an in-place update fills a fresh set and
 // installs it when it is complete and the stream has drained, so that on any error the handle's tables are the ones it
@@ -279,6 +305,8 @@ struct ListArrays {
     DevBuf goff, loff, codes, ncodes, ids;
     DevBuf fmask; // the handle's filter judged over the new ids (mark_filter); installed with them
     uint64_t fpass = 0;
+    DevBuf fplanes; // ... and its filter slots, every plane in one pass
+    uint64_t fs_pass[IVFHNSW_FILTER_SLOTS] = {};
     ListArrays() = default;
     ListArrays(const ListArrays &) = delete;
     ListArrays &operator=(const ListArrays &) = delete;
@@ -296,16 +324,20 @@ struct ListArrays {
         return {goff.as<uint64_t>(), loff.as<uint32_t>(), codes.as<uint8_t>(), ncodes.as<uint8_t>(), ids.as<uint32_t>(), n_local};
     }
     // The one place an update re-marks the filter: rows move and new rows must be judged.  Called when the new ids are
-    // complete and BEFORE install, so that a failure here leaves tables and filter as they were.  No filter: nothing.
+    // complete and BEFORE install, so that a failure here leaves tables, filter and slots as they were.  No filter and no
+    // slot: nothing.
     int mark_filter(ivfhnsw_gpu *h, uint64_t n_local)
     {
+        int rc;
+        if (h->fs.nplanes && (rc = slots_mark_rows(h, ids.as<uint32_t>(), n_local, fplanes, fs_pass)))
+            return rc;
         if (h->filter_mode < 0)
             return IVFHNSW_OK;
         return filter_mark_rows(h, ids.as<uint32_t>(), n_local, fmask, &fpass);
     }
     void release()
     {
-        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask})
+        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask, &fplanes})
             b->release();
     }
     void install(ivfhnsw_gpu *h, uint64_t n_local)
@@ -314,6 +346,12 @@ struct ListArrays {
             std::swap(h->f_mask, fmask);
             h->fmask = h->f_mask.as<uint32_t>();
             h->f_pass = fpass;
+        }
+        if (h->fs.nplanes) {
+            std::swap(h->fs_planes, fplanes);
+            h->fs.planes = h->fs_planes.as<uint32_t>();
+            h->fs.stride = (uint32_t)slot_plane_stride(n_local);
+            std::copy(fs_pass, fs_pass + IVFHNSW_FILTER_SLOTS, h->fs_pass);
         }
         std::swap(h->goff, goff);
         std::swap(h->loff, loff);
@@ -392,11 +430,12 @@ struct SearchArgs {
     const ivfhnsw_search_params *p;
     float *d_distances;
     int64_t *d_labels, *d_out_keys;
+    const uint8_t *d_query_slots = nullptr; // a _slots call: the filter slot of every query, else null
     SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
     {
         return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
                 d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k, d_labels + q0 * k,
-                d_out_keys};
+                d_out_keys, d_query_slots ? d_query_slots + q0 : nullptr};
     }
 };
 
@@ -404,7 +443,7 @@ struct SearchArgs {
 struct Chunk : SearchArgs {
     int nprobe, max_seg, plan_k;    // chunk_workspace
     bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
-    const uint32_t *fmask;          // a label filter
+    ScanFilter fmask;               // a label filter, or the call's filter slots (3.19)
     const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
     const uint32_t *cid;
     const float *cd;

@@ -49,12 +49,13 @@ static int range_fill_pass(ivfhnsw_gpu *h, const Chunk &c, int seg_hint, float r
     return check_status(h);
 }
 
-int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
-                                 const float *d_coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *d_lims,
-                                 uint64_t *total)
+// ivfhnsw_gpu_range_search_dev, and with d_query_slots (one byte per query, device memory) its _slots form
+static int range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                            const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint8_t *d_query_slots,
+                            float radius, uint64_t *d_lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, radius, d_lims, total);
-    if (rc)
+    if (rc || (d_query_slots && (rc = slots_call_guard(h, "range_search_slots_dev"))))
         return rc;
     if (nq == 0) {
         if (d_lims) {
@@ -67,7 +68,7 @@ int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queri
         h->rg_total = 0;
         return IVFHNSW_OK;
     }
-    Chunk c{SearchArgs{nq, 1, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, nullptr, nullptr}};
+    Chunk c{SearchArgs{nq, 1, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, nullptr, nullptr, d_query_slots}};
     if ((rc = chunk_checks(h, c, false)))
         return rc;
     // the workspace is about to hold this call's plan: whatever the last search left there is gone
@@ -142,12 +143,28 @@ int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queri
     return IVFHNSW_OK;
 }
 
-int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
-                             const float *coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *lims,
-                             uint64_t *total)
+int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                 const float *d_coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *d_lims,
+                                 uint64_t *total)
+{
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, radius, d_lims, total);
+}
+
+int ivfhnsw_gpu_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                       const float *d_coarse_dists, const ivfhnsw_search_params *p,
+                                       const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, d_query_slots, radius, d_lims, total);
+}
+
+// ivfhnsw_gpu_range_search, and with query_slots (host memory) ivfhnsw_gpu_range_search_slots
+static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                             const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots, float radius,
+                             uint64_t *lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, queries, coarse_ids, coarse_dists, p, radius, lims, total);
-    if (rc)
+    if (rc || (query_slots && ((rc = slots_call_guard(h, "range_search_slots")) ||
+                               (rc = slots_bytes_guard(nq, query_slots, "range_search_slots")))))
         return rc;
     if (nq == 0) {
         if (lims)
@@ -157,13 +174,28 @@ int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, co
     const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
     if ((rc = h->rg_lims.ensure((nq + 1) * sizeof(uint64_t))) || (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (rc = ivfhnsw_gpu_range_search_dev(h, nq, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                                           coarse_ids ? h->s_cd.as<float>() : nullptr, p, radius, h->rg_lims.as<uint64_t>(),
-                                           total)) ||
+        (query_slots && (rc = stage_in(h, h->fs_qslots, query_slots, nq))) ||
+        (rc = range_search_dev(h, nq, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
+                               coarse_ids ? h->s_cd.as<float>() : nullptr, p, query_slots ? h->fs_qslots.as<uint8_t>() : nullptr,
+                               radius, h->rg_lims.as<uint64_t>(), total)) ||
         (rc = stage_out(h, lims, h->rg_lims, (nq + 1) * sizeof(uint64_t))))
         return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                             const float *coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *lims,
+                             uint64_t *total)
+{
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, nullptr, radius, lims, total);
+}
+
+int ivfhnsw_gpu_range_search_slots(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                   const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots,
+                                   float radius, uint64_t *lims, uint64_t *total)
+{
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, query_slots, radius, lims, total);
 }
 
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels)

@@ -217,12 +217,12 @@ static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params
 // box (profiles/r04_early_tables.md): (32, 10000, 80) 1.652 -> 1.617 ms per step.  Only where the second part's walk leaves
 // such slots, i.e. has fewer queries than the walk has resident wavefronts (search_dev_split): at (64, 30000, 100) its 4096
 // queries take every slot the first walk frees, the table workgroups compete with them, and the step measured 0.6 %
-// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter or a table that the
+// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter, filter slots or a table that the
 // pipelined scan builds itself.
 static bool early_tables_wanted(const ivfhnsw_gpu *h, const SearchArgs &a)
 {
     static const bool on = env_size("IVFHNSW_EARLY_LUT", 1) != 0;
-    if (!on || !plan_lut_shape(h) || h->filter_mode >= 0)
+    if (!on || !plan_lut_shape(h) || h->filter_mode >= 0 || a.d_query_slots)
         return false;
     const bool may_pipe = a.k == 1 && h->opt_scan_pipe != 0 &&
                           scan_pipe_supported(h->t, (int)a.p->nprobe, (int)a.nq, 1, h->n_local > 0, h->opt_scan_pipe == 1);
@@ -354,6 +354,22 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
 }
 
+// The same call with a filter slot per query.  The bytes are not read back: one that names no installed
+// slot passes nothing.  d_query_slots null: the plain call.
+int ivfhnsw_gpu_search_slots_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                 const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint8_t *d_query_slots,
+                                 float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
+{
+    if (!d_query_slots)
+        return ivfhnsw_gpu_search_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
+    int rc = bind(h);
+    if (rc || (rc = search_args_guard(h, p, k)) || (rc = slots_call_guard(h, "search_slots_dev")))
+        return rc;
+    SearchCall call;
+    return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys, d_query_slots},
+                           call);
+}
+
 static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_stream, const char *kernel_name)
 {
     h->last_scan_kernel = kernel_name;
@@ -390,7 +406,6 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
     c.max_seg = h->has_group ? c.nprobe * h->g.nsubc : c.nprobe;
     c.heap_big = c.k > 1024;
     c.plan_k = c.heap_big ? 1 : (int)c.k; // the plan kernels reset one key per query
-    c.fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
     int rc;
     if ((rc = h->w_segs.ensure(c.nq * (size_t)c.max_seg * sizeof(Seg))) ||
         (rc = h->w_lpos.ensure(c.nq * (size_t)c.max_seg * sizeof(uint32_t))) ||
@@ -398,6 +413,11 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
         (rc = h->w_keys.ensure(c.nq * (size_t)c.plan_k * sizeof(uint64_t))) ||
         (rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
+    if (c.d_query_slots) // the planes the handle (a view: its parent) holds -- with none, any readable word: a query
+                         // without a plane reads word 0 and ignores it -- and the bytes of this chunk's queries
+        c.fmask = SlotMask{h->fs.nplanes ? h->fs.planes : h->w_totals.as<uint32_t>(), h->fs.stride, h->fs.nplanes, c.d_query_slots};
+    else
+        c.fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
     return IVFHNSW_OK;
 }
 
@@ -424,7 +444,7 @@ int ivfhnsw_gpu_impl::chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &c
     // meeting words are cleared by the latency walk when that runs, by a memset otherwise.  The one-launch tail and the
     // pipelined scan have no filtered form.
     static const size_t tail_max_nq = env_size("IVFHNSW_TAIL_MAX_NQ", 8);
-    c.use_tail = !h->has_group && nq <= tail_max_nq && !c.d_out_keys && !c.fmask &&
+    c.use_tail = !h->has_group && nq <= tail_max_nq && !c.d_out_keys && !c.fmask.any() &&
                  ivf_tail_supported(h->t, c.nprobe, (int)c.k);
     if (c.use_tail) {
         if ((rc = h->w_tail.ensure(nq * (sizeof(uint64_t) + sizeof(uint32_t)))))
@@ -471,7 +491,7 @@ int ivfhnsw_gpu_impl::chunk_plan_table(ivfhnsw_gpu *h, Chunk &c)
     // small batches: split each query over several workgroups so the chip still fills
     c.nsplit = (c.k == 1 && c.nq < 1024) ? (int)std::min<size_t>(32, (2048 + c.nq - 1) / c.nq) : 1;
     // list shards: table and scan in one software-pipelined kernel, the table never leaves the chip (kernels_scan3.hip)
-    c.pipe = c.k == 1 && !h->has_group && !c.heap && !c.fmask && h->opt_scan_pipe != 0 &&
+    c.pipe = c.k == 1 && !h->has_group && !c.heap && !c.fmask.any() && h->opt_scan_pipe != 0 &&
              scan_pipe_supported(h->t, max_seg, nq, c.nsplit, h->n_local > 0, h->opt_scan_pipe == 1);
     const bool plan_lut = !c.pipe && plan_lut_shape(h);
     if (!c.pipe && (rc = h->w_luts.ensure(c.nq * (size_t)h->t.M * 256 * sizeof(float))))
@@ -544,7 +564,7 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
             HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, nullptr, nullptr, heap_ws, c.d_distances, c.d_labels,
                                      c.fmask));
         }
-        remember_plan(h, c.nq, c.max_seg, false, c.fmask ? "heap_scan_kernel+filter" : "heap_scan_kernel");
+        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots"));
         return IVFHNSW_OK;
     }
     if (heap) {
@@ -674,11 +694,16 @@ int ivfhnsw_gpu_replay_stream_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const uin
     return IVFHNSW_OK;
 }
 
-int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
-                       const float *coarse_dists, const ivfhnsw_search_params *p, float *distances, int64_t *labels)
+// ivfhnsw_gpu_search, and with query_slots (one byte per query, host memory) ivfhnsw_gpu_search_slots: the bytes ride in
+// the pinned input block or a staging buffer beside the queries
+static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                       const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots, float *distances,
+                       int64_t *labels)
 {
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)))
+        return rc;
+    if (query_slots && (rc = slots_call_guard(h, "search_slots")))
         return rc;
     if (nq == 0)
         return IVFHNSW_OK;
@@ -686,14 +711,17 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
     if ((coarse_ids == nullptr) != (coarse_dists == nullptr))
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
+    if (query_slots && (rc = slots_bytes_guard(nq, query_slots, "search_slots")))
+        return rc;
     const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
+    const size_t in_s = query_slots ? nq : 0;
     // Small batches -- the reference's drivers pass ONE query per call (tests/test_ivfhnsw_sift1b.cpp:193-208) -- go
     // through pinned host memory the kernels read and write directly: no staging copies, one synchronisation.  Layout
     // of the two blocks: in = queries | coarse ids | coarse dists; out = distances | labels | status word.
     static const size_t pinned_max_nq = env_size("IVFHNSW_PINNED_MAX_NQ", 256);
     if (nq <= pinned_max_nq) {
         const size_t out_d = (nq * k * sizeof(float) + 7) & ~(size_t)7, out_l = nq * k * sizeof(int64_t);
-        if ((rc = h->p_in.ensure(in_q + 2 * in_c)) || (rc = h->p_out.ensure(out_d + out_l + 8)))
+        if ((rc = h->p_in.ensure(in_q + 2 * in_c + in_s)) || (rc = h->p_out.ensure(out_d + out_l + 8)))
             return rc;
         char *pin = h->p_in.as<char>(), *pout = h->p_out.as<char>();
         memcpy(pin, queries, in_q);
@@ -701,6 +729,8 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
             memcpy(pin + in_q, coarse_ids, in_c);
             memcpy(pin + in_q + in_c, coarse_dists, in_c);
         }
+        if (query_slots)
+            memcpy(pin + in_q + 2 * in_c, query_slots, in_s);
         uint32_t *pst = reinterpret_cast<uint32_t *>(pout + out_d + out_l);
         uint32_t *bits = &status_words(h)->bits;
         // The latency walk keeps at most 64 exact ties at the efSearch boundary.  This call synchronises anyway, so instead
@@ -712,7 +742,8 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
                                  {nq, k, reinterpret_cast<const float *>(pin),
                                   coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
                                   coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
-                                  reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr},
+                                  reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr,
+                                  query_slots ? reinterpret_cast<const uint8_t *>(pin + in_q + 2 * in_c) : nullptr},
                                  call);
             if (rc)
                 return rc;
@@ -733,14 +764,29 @@ int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
         (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (rc = ivfhnsw_gpu_search_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                                     coarse_ids ? h->s_cd.as<float>() : nullptr, p, h->s_dist.as<float>(),
-                                     h->s_lab.as<int64_t>(), nullptr)) ||
+        (query_slots && (rc = stage_in(h, h->fs_qslots, query_slots, in_s))) ||
+        (rc = ivfhnsw_gpu_search_slots_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
+                                           coarse_ids ? h->s_cd.as<float>() : nullptr, p,
+                                           query_slots ? h->fs_qslots.as<uint8_t>() : nullptr, h->s_dist.as<float>(),
+                                           h->s_lab.as<int64_t>(), nullptr)) ||
         (rc = stage_out(h, distances, h->s_dist, nq * k * sizeof(float))) ||
         (rc = stage_out(h, labels, h->s_lab, nq * k * sizeof(int64_t))))
         return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return check_status(h);
+}
+
+int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                       const float *coarse_dists, const ivfhnsw_search_params *p, float *distances, int64_t *labels)
+{
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, nullptr, distances, labels);
+}
+
+int ivfhnsw_gpu_search_slots(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                             const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots,
+                             float *distances, int64_t *labels)
+{
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, query_slots, distances, labels);
 }
 
 int ivfhnsw_gpu_search_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan_dispatch.h"
+
 namespace ivfhnsw_gpu_impl {
 
 // Exact reference distance (hnswlib/hnswalg.cpp:326-357 == utils.cpp:22-52, AVX branch): 8 accumulators
@@ -503,5 +505,34 @@ __device__ __forceinline__ void heap_replace_top(int k, float *val, ID *ids, flo
 // row's norm code, so both waits fall together; the lanes of a wavefront read consecutive rows and share one or two words.
 __device__ __forceinline__ const uint32_t *filter_mask() { return nullptr; }
 __device__ __forceinline__ const uint32_t *filter_mask(const uint32_t *m) { return m; }
+
+// The same for a kernel that knows its query q: the third form of the pack (SlotMask, scan_dispatch.h)
+// names a filter slot per query, and the mask is that slot's plane.  Resolved once per workgroup (once per query where a
+// workgroup walks several); the slot byte goes through readfirstlane, so the plane's base is a scalar like the single
+// mask's.  Two cases have no plane, both wave-uniform: IVFHNSW_SLOT_NONE (0xff) passes every row and a slot at or beyond
+// the planes the handle holds passes none.  They are no per-row test and no branch in the scan's load loop either (a
+// branch there, like any use of the loaded word, keeps the unrolled loads of a lane from being issued together): the
+// mask word a row uses is (word & keep) | all with two scalars, applied where the word is consumed (filter_pass,
+// scan_steps.h), keep = ~0 / all = 0 for a plane, and keep = 0 for the other two, which then read word 0 of `planes`
+// whatever the row (the launcher passes a readable word even where the handle holds no plane) and ignore it.  The first
+// two forms leave the scalars alone.
+struct FilterFill {
+    uint32_t keep = ~0u, all = 0u;
+};
+template <class T> struct is_slot_mask : std::false_type {};
+template <> struct is_slot_mask<SlotMask> : std::true_type {};
+// 0 = no filter, 1 = one mask, 2 = a plane per query
+template <class... Mask> constexpr int filter_kind = sizeof...(Mask) == 0 ? 0 : (is_slot_mask<Mask>::value || ...) ? 2 : 1;
+
+__device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &) { return nullptr; }
+__device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &, const uint32_t *m) { return m; }
+__device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, const SlotMask &m)
+{
+    const uint32_t s = __builtin_amdgcn_readfirstlane((uint32_t)m.slots[q]);
+    const bool plane = s < m.nplanes;
+    fill.keep = plane ? ~0u : 0u;
+    fill.all = s == 0xffu ? ~0u : 0u;
+    return m.planes + (plane ? (size_t)s * m.stride : (size_t)0);
+}
 
 } // namespace ivfhnsw_gpu_impl

@@ -61,6 +61,12 @@ struct DeviceSide {
     // set_id_filter: the label set, installed on the handle whenever the device copy is made or remade
     bool has_filter = false, filter_deny = false;
     std::vector<uint32_t> filter_labels;
+    // set_id_filter_slot: the label set of every slot in use (empty, or IVFHNSW_FILTER_SLOTS entries), installed likewise
+    struct SlotSet {
+        bool set = false, deny = false;
+        std::vector<uint32_t> labels;
+    };
+    std::vector<SlotSet> slots;
 };
 std::mutex g_side_mu;
 std::unordered_map<const void *, DeviceSide> g_side;
@@ -91,6 +97,23 @@ void install_id_filter(const void *ix, ivfhnsw_gpu *h)
     }
     if (has && ivfhnsw_gpu_set_filter(h, labels.size(), labels.data(), deny ? IVFHNSW_FILTER_DENY : IVFHNSW_FILTER_ALLOW))
         gpu_fail("ivfhnsw_gpu_set_filter");
+}
+
+// one slot's set, or with slot < 0 every slot's, onto the handle
+void install_id_filter_slots(const void *ix, ivfhnsw_gpu *h, int slot = -1)
+{
+    std::vector<DeviceSide::SlotSet> slots;
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(ix);
+        if (it != g_side.end())
+            slots = it->second.slots;
+    }
+    for (size_t s = 0; s < slots.size(); s++)
+        if (slots[s].set && (slot < 0 || (size_t)slot == s) &&
+            ivfhnsw_gpu_set_filter_slot(h, (unsigned)s, slots[s].labels.size(), slots[s].labels.data(),
+                                        slots[s].deny ? IVFHNSW_FILTER_DENY : IVFHNSW_FILTER_ALLOW))
+            gpu_fail("ivfhnsw_gpu_set_filter_slot");
 }
 
 } // namespace
@@ -124,6 +147,86 @@ void IndexIVF_HNSW::clear_id_filter()
     }
     if (gpu_ && ivfhnsw_gpu_clear_filter(gpu_))
         gpu_fail("ivfhnsw_gpu_clear_filter");
+}
+
+void IndexIVF_HNSW::set_id_filter_slot(unsigned slot, size_t n, const idx_t *xids, bool deny)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_filter_slot: IVFHNSW_SHARDS > 1, and sharded handles have no filter slots");
+    if (slot >= IVFHNSW_FILTER_SLOTS)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_filter_slot: slot " + std::to_string(slot) + ", an index has slots 0.." +
+                                 std::to_string(IVFHNSW_FILTER_SLOTS - 1));
+    if (n && !xids)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_filter_slot: null ids");
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        DeviceSide &side = g_side[this];
+        side.slots.resize(IVFHNSW_FILTER_SLOTS);
+        side.slots[slot].set = true;
+        side.slots[slot].deny = deny;
+        side.slots[slot].labels.assign(xids, xids + n);
+    }
+    if (gpu_ && device_current()) // otherwise the next search's upload installs it
+        install_id_filter_slots(this, gpu_, (int)slot);
+}
+
+void IndexIVF_HNSW::clear_id_filter_slot(int slot)
+{
+    if (slot < -1 || slot >= IVFHNSW_FILTER_SLOTS)
+        throw std::runtime_error("IndexIVF_HNSW::clear_id_filter_slot: slot " + std::to_string(slot));
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(this);
+        if (it != g_side.end())
+            for (size_t s = 0; s < it->second.slots.size(); s++)
+                if (slot < 0 || (size_t)slot == s)
+                    it->second.slots[s] = DeviceSide::SlotSet();
+    }
+    // (a handle without lists holds no slot, and says so)
+    if (gpu_ && device_current() && shards_wanted() == 1 && ivfhnsw_gpu_clear_filter_slot(gpu_, slot))
+        gpu_fail("ivfhnsw_gpu_clear_filter_slot");
+}
+
+void IndexIVF_HNSW::search_batch_slots(size_t nq, size_t k, const float *x, const uint8_t *slots, float *distances,
+                                       long *labels)
+{
+    static_assert(sizeof(long) == sizeof(int64_t), "LP64 expected");
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::search_batch_slots: IVFHNSW_SHARDS > 1, and sharded handles have no filter slots");
+    ensure_device();
+    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
+    ivfhnsw_search_params p;
+    p.nprobe = nprobe;
+    p.max_codes = max_codes;
+    p.efSearch = quantizer->efSearch;
+    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
+    p.heap_order = 1; // as search_batch
+    if (ivfhnsw_gpu_search_slots(gpu_, nq, k, x, nullptr, nullptr, &p, slots, distances, reinterpret_cast<int64_t *>(labels)))
+        gpu_fail("ivfhnsw_gpu_search_slots");
+}
+
+void IndexIVF_HNSW::range_search_slots(size_t nq, const float *x, const uint8_t *slots, float radius, std::vector<size_t> &lims,
+                                       std::vector<float> &distances, std::vector<long> &labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::range_search_slots: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
+    ensure_device();
+    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
+    ivfhnsw_search_params p;
+    p.nprobe = nprobe;
+    p.max_codes = max_codes;
+    p.efSearch = quantizer->efSearch;
+    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
+    p.heap_order = 0;
+    lims.assign(nq + 1, 0);
+    uint64_t total = 0;
+    if (ivfhnsw_gpu_range_search_slots(gpu_, nq, x, nullptr, nullptr, &p, slots, radius,
+                                       reinterpret_cast<uint64_t *>(lims.data()), &total))
+        gpu_fail("ivfhnsw_gpu_range_search_slots");
+    distances.resize(total);
+    labels.resize(total);
+    if (ivfhnsw_gpu_range_results(gpu_, 0, total, distances.data(), reinterpret_cast<int64_t *>(labels.data())))
+        gpu_fail("ivfhnsw_gpu_range_results");
 }
 
 unsigned IndexIVF_HNSW::tables_dirty() const
@@ -370,8 +473,10 @@ void IndexIVF_HNSW::device_upload_common()
     up_quantizer_ = quantizer;
     up_total_ = total;
     up_do_opq_ = do_opq;
-    if (world == 1)
+    if (world == 1) {
         install_id_filter(this, gpu_); // upload_ivf dropped the handle's
+        install_id_filter_slots(this, gpu_);
+    }
     std::lock_guard<std::mutex> lk(g_side_mu);
     DeviceSide &side = g_side[this];
     side.tables_dirty = 0;

@@ -186,11 +186,12 @@ struct ScanOut {
 };
 // the ADC loop (IndexIVF_HNSW.cpp:282-289 / IndexIVF_HNSW_Grouping.cpp:321-333)
 // seg_len_hint: expected codes per plan segment (0 = unknown), picks the scan form
-// fmask non-null: the filtered form of the chosen kernel; bit r = local row r passes (launch_filter_mark)
+// fmask (ScanFilter, scan_dispatch.h): a mask = the filtered form of the chosen kernel, bit r = local row r passes
+// (launch_filter_mark); filter slots = its per-query form, a plane per slot and a slot byte per query
 // *did_select: the scan wrote out.sel_dist / sel_labels (else launch_select has to run); *kernel_name: the form that ran,
 // "" when nothing was launched; either may be null
 hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, int nsplit,
-                       uint64_t *keys, int seg_len_hint, const uint32_t *fmask, const ScanOut &out, bool *did_select,
+                       uint64_t *keys, int seg_len_hint, const ScanFilter &fmask, const ScanOut &out, bool *did_select,
                        const char **kernel_name);
 // table + scan pipelined over queries, for list shards (kernels_scan3.hip)
 bool scan_pipe_supported(const IvfTables &t, int max_seg, int nq, int nsplit, bool has_codes, bool forced = false);
@@ -215,18 +216,18 @@ bool heap_scan_lds_tier(int code_size, int k);
 size_t heap_scan_ws_bytes(int code_size, int k, int nq);
 hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k,
                             uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
-                            const uint32_t *fmask = nullptr); // non-null: the filtered form, as launch_scan
+                            const ScanFilter &fmask = ScanFilter()); // a filter: the filtered form, as launch_scan
 // range search (kernels_range.hip): the scan's plan, table and filter mask as launch_scan takes them, every
 // query cut into nsplit slices.  count: slices [nq * nsplit + 1] (zeroed here) = the codes with dist < radius in every
 // slice, *total (device, zeroed here) their 64-bit sum, *kernel_name the form that ran.  After launch_scan_excl_u32 over
 // slices: lims [nq + 1] = every query's first place, and fill writes hit r of a slice at bases[slice] + r, in scan order.
 hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
                               int seg_len_hint, float radius, uint32_t *slices, unsigned long long *total,
-                              const uint32_t *fmask, const char **kernel_name);
+                              const ScanFilter &fmask, const char **kernel_name);
 hipError_t launch_range_lims(hipStream_t s, const uint32_t *bases, int nq, int nsplit, uint64_t *lims);
 hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
                              int seg_len_hint, float radius, const uint32_t *bases, float *dist, int64_t *labels,
-                             const uint32_t *fmask);
+                             const ScanFilter &fmask);
 // keys -> (distance, label) through the plan; also emits signed-orderable keys when out_keys != null
 hipError_t launch_select(hipStream_t s, const IvfTables &t, const PlanView &p, const uint64_t *keys, int k, float *dist,
                          int64_t *labels, int64_t *out_keys);
@@ -416,6 +417,18 @@ hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, u
 // rows that pass.
 hipError_t launch_filter_mark(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
                               int deny, unsigned long long *mask, unsigned long long *count);
+// the same for every filter slot of a handle in ONE pass over the ids: plane s < nplanes of planes, stride64
+// 64-bit words apart, is the mask of slot s -- all zero where the slot is not set (set[s] 0) -- and counts[s] (the first
+// kFilterSlots words zeroed here) the rows that pass it.
+constexpr int kFilterSlots = 32;
+struct FilterSlotSets {
+    const uint32_t *bits[kFilterSlots]; // the slot's label bitmap, null = the empty set
+    uint32_t max_label[kFilterSlots];
+    uint8_t set[kFilterSlots], deny[kFilterSlots];
+};
+hipError_t launch_filter_mark_slots(hipStream_t s, const uint32_t *ids, uint64_t n_local, const FilterSlotSets &sets,
+                                    uint32_t nplanes, unsigned long long *planes, uint64_t stride64,
+                                    unsigned long long *counts);
 // additions to a Grouping index (kernels_add_groups.hip): its codes go in with the append launchers above.
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --

@@ -28,7 +28,8 @@ constexpr size_t HS_LDS = 160 * 1024;      // LDS of one workgroup on gfx950
 // static LDS of the kernel (norm table, segments, chunk buffer, counts) with room for alignment
 constexpr size_t HS_STATIC_LDS = 256 * 4 + HS_SEGCAP * sizeof(Seg) + (HS_SEGCAP + 1) * 4 + HS_CHUNK * 8 + HS_U * 4 * 4 + 512;
 
-// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear never reaches
+// Mask: empty, the pass mask of a label filter, or filter slots per query -- the plane is resolved for every query the
+// workgroup walks (device_common.h filter_mask): a row whose bit is clear never reaches
 // the heap.
 template <int CS, bool LDS_HEAP, class... Mask>
 __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float *__restrict__ luts,
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                                                         Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     // dynamic LDS: the query's table [csz][256], then (LDS tier) the heap's values [k] and scan positions [k]
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     __shared__ float s_norm[256];
@@ -61,6 +62,8 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
 
     for (uint32_t item = blockIdx.x; item < n; item += gridDim.x) {
         const int q = redo_list ? (int)redo_list[item] : (int)item;
+        [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+        [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
         const PlanHdr h = hdr[q];
         __syncthreads(); // the previous query's label pass is done with the heap
         for (int j = tid; j < k; j += 256) { // maxheap_heapify
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                         const uint32_t off = p - c.seg_lo;
                         const uint32_t gi = c.seg_start + off;
                         code_fetch<CS>(t.codes, gi, t.M, s_lut, w[u]);
-                        load_norm_filter<FILT>(t.norm_codes, fmask, gi, nbv[u], fw[u]);
+                        load_norm_filter<FK>(t.norm_codes, fmask, gi, nbv[u], fw[u], ffill);
                         if constexpr (FILT)
                             fb[u] = gi & 31u;
                         vp[u] = c.seg_vpos + off;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                     pass[u] = false;
                     dn[u] = 0.f;
                     if constexpr (FILT)
-                        ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
+                        ok[u] = ok[u] && filter_pass<FK>(fw[u], fb[u], ffill);
                     if (ok[u]) {
                         const float sum = code_sum<CS>(s_lut, w[u]);
                         const float d = adc_distance(ct[u], s_norm[nbv[u]], sum);
@@ -216,7 +219,7 @@ size_t heap_scan_ws_bytes(int code_size, int k, int nq)
 
 hipError_t launch_heap_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k,
                             uint32_t *redo_hdr, const uint32_t *redo_list, float *heap_ws, float *dist, int64_t *labels,
-                            const uint32_t *fmask)
+                            const ScanFilter &fmask)
 {
     if (p.nq == 0)
         return hipSuccess;

@@ -84,7 +84,8 @@ __device__ __forceinline__ void range_finish(uint32_t *slices, uint32_t run, int
 }
 
 // Position form (whole inverted lists): scan_slice, stage_plan_chunk and a SegCursor, as scan_k1_kernel.
-// CS == 0: run-time code size cs_rt, table in dynamic LDS.  Mask: empty, or the pass mask of a label filter.
+// CS == 0: run-time code size cs_rt, table in dynamic LDS.  Mask: empty, the pass mask of a label filter, or filter slots
+// per query (device_common.h filter_mask).
 template <int CS, int U, bool FILL, class... Mask>
 __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *__restrict__ codes,
                                                                 const uint8_t *__restrict__ norm_codes,
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
                                                                 Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     __shared__ __attribute__((aligned(16))) float s_lut_fixed[(CS > 0 ? CS : 1) * 256];
     extern __shared__ __attribute__((aligned(16))) float s_lut_dyn[];
     float *s_lut = CS > 0 ? s_lut_fixed : s_lut_dyn;
@@ -109,6 +110,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / nsplit;
+    [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
     const int split = blockIdx.x - q * nsplit;
     const PlanHdr h = hdr[q];
     if (h.total == 0)
@@ -158,14 +161,14 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
                     c.seek<SeekStep2Halves>(p, s_lpos, s_seg, cn);
                     gi[u] = c.seg_start + (p - c.seg_lo);
                     code_fetch<CS>(codes, gi[u], cs_rt, s_lut, w[u]);
-                    load_norm_filter<FILT>(norm_codes, fmask, gi[u], nb[u], fw[u]);
+                    load_norm_filter<FK>(norm_codes, fmask, gi[u], nb[u], fw[u], ffill);
                     ct[u] = c.seg_ct;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if constexpr (FILT)
-                    ok[u] = ok[u] && filter_pass(fw[u], gi[u] & 31u);
+                    ok[u] = ok[u] && filter_pass<FK>(fw[u], gi[u] & 31u, ffill);
                 hit[u] = false;
                 dv[u] = 0.f;
                 if (ok[u]) {
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
                                                                        RangeOut out, Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     __shared__ __attribute__((aligned(16))) float s_lut[CS * 256];
     __shared__ float s_norm[256];
     __shared__ __attribute__((aligned(16))) Seg s_seg[kBmSegCap];
@@ -208,6 +211,8 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / nsplit;
+    [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
     const int split = blockIdx.x - q * nsplit;
     const PlanHdr h = hdr[q];
     if (h.total == 0)
@@ -257,7 +262,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
                             const Seg sg = s_seg[sgi];
                             gi[u] = sg.start + (p - s_lpos[sgi]);
                             code_fetch<CS>(codes, gi[u], CS, s_lut, w[u]);
-                            load_norm_filter<FILT>(norm_codes, fmask, gi[u], nb[u], fw[u]);
+                            load_norm_filter<FK>(norm_codes, fmask, gi[u], nb[u], fw[u], ffill);
                             ct[u] = sg.cterm;
                         }
                     }
@@ -265,7 +270,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     if constexpr (FILT)
-                        ok[u] = ok[u] && filter_pass(fw[u], gi[u] & 31u);
+                        ok[u] = ok[u] && filter_pass<FK>(fw[u], gi[u] & 31u, ffill);
                     hit[u] = false;
                     dv[u] = 0.f;
                     if (ok[u]) {
@@ -305,17 +310,16 @@ __global__ void range_total_kernel(const uint32_t *__restrict__ counts, size_t l
 
 template <bool FILL>
 hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit, int seg_len_hint,
-                        float radius, uint32_t *slices, RangeOut out, const uint32_t *fmask, const char **name)
+                        float radius, uint32_t *slices, RangeOut out, const ScanFilter &fmask, const char **name)
 {
     const dim3 grid((unsigned)p.nq * nsplit), block(RG_THREADS);
     return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
         return with_mask(fmask, [&](auto... m) -> hipError_t {
             constexpr int CS = decltype(cs)::value;
-            constexpr bool FILT = sizeof...(m) != 0;
             if constexpr (CS > 0) {
                 // plans of short segments (Grouping sub-groups): the bitmap form; whole lists: the position form
                 if (seg_len_hint > 0 && seg_len_hint <= 48) {
-                    *name = FILT ? "range_scan_bitmap_kernel+filter" : "range_scan_bitmap_kernel";
+                    *name = fmask.name("range_scan_bitmap_kernel", "range_scan_bitmap_kernel+filter", "range_scan_bitmap_kernel+slots");
                     hipLaunchKernelGGL((range_scan_bitmap_kernel<CS, 4, FILL, decltype(m)...>), grid, block, 0, s, t.codes,
                                        t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, radius, slices,
                                        out, m...);
@@ -327,8 +331,9 @@ hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, co
             size_t shm;
             if (hipError_t e = scan_table_lds<CS, kern>(t.M, &shm); e != hipSuccess)
                 return e;
-            *name = CS > 0 ? (FILT ? "range_scan_kernel+filter" : "range_scan_kernel")
-                           : (FILT ? "range_scan_kernel (run-time code size)+filter" : "range_scan_kernel (run-time code size)");
+            *name = CS > 0 ? fmask.name("range_scan_kernel", "range_scan_kernel+filter", "range_scan_kernel+slots")
+                           : fmask.name("range_scan_kernel (run-time code size)", "range_scan_kernel (run-time code size)+filter",
+                                        "range_scan_kernel (run-time code size)+slots");
             hipLaunchKernelGGL(kern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr,
                                p.max_seg, nsplit, t.M, radius, slices, out, m...);
             return hipGetLastError();
@@ -340,7 +345,7 @@ hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, co
 
 hipError_t launch_range_count(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
                               int seg_len_hint, float radius, uint32_t *slices, unsigned long long *total,
-                              const uint32_t *fmask, const char **kernel_name)
+                              const ScanFilter &fmask, const char **kernel_name)
 {
     const char *unused_name;
     kernel_name = kernel_name ? kernel_name : &unused_name; // may be null
@@ -369,7 +374,7 @@ hipError_t launch_range_lims(hipStream_t s, const uint32_t *bases, int nq, int n
 
 hipError_t launch_range_fill(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int nsplit,
                              int seg_len_hint, float radius, const uint32_t *bases, float *dist, int64_t *labels,
-                             const uint32_t *fmask)
+                             const ScanFilter &fmask)
 {
     if (p.nq == 0)
         return hipSuccess;

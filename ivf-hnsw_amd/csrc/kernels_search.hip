@@ -316,7 +316,8 @@ __device__ __forceinline__ void sel_write(const SelOut &so, int q, unsigned long
     so.labels[q] = lb;
 }
 
-// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear forms no key.
+// Mask: empty, the pass mask of a label filter, or filter slots per query (device_common.h filter_mask; DESIGN.md 3.14,
+// 3.19): a row whose bit is clear forms no key.
 template <int CS, int SEGCAP, int U, int THREADS, class... Mask>
 __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restrict__ codes,
                                                           const uint8_t *__restrict__ norm_codes,
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
                                                           Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     // CS == 0: run-time code size cs_rt, table in dynamic LDS (code sizes without an instantiation of their own)
     __shared__ __attribute__((aligned(16))) float s_lut_fixed[(CS > 0 ? CS : 1) * 256];
     extern __shared__ __attribute__((aligned(16))) float s_lut_dyn[];
@@ -342,6 +343,8 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
 
     const int tid = threadIdx.x;
     const int q = blockIdx.x / nsplit;
+    [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
     const int split = blockIdx.x - q * nsplit;
     const PlanHdr h = hdr[q];
     if (h.total == 0) {
@@ -387,7 +390,7 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
                     const uint32_t off = p - c.seg_lo;
                     const uint32_t gi = c.seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
-                    load_norm_filter<FILT>(norm_codes, fmask, gi, nb[u], fw[u]);
+                    load_norm_filter<FK>(norm_codes, fmask, gi, nb[u], fw[u], ffill);
                     if constexpr (FILT)
                         fb[u] = gi & 31u;
                     vp[u] = c.seg_vpos + off;
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if constexpr (FILT)
-                    ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
+                    ok[u] = ok[u] && filter_pass<FK>(fw[u], fb[u], ffill);
                 if (ok[u]) {
                     const float sum = code_sum_lds<CS>(s_lut, w[u]);
                     const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
@@ -448,7 +451,7 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                                                              Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     __shared__ __attribute__((aligned(16))) float s_lut[CS * 256];
     __shared__ float s_norm[256];
     __shared__ __attribute__((aligned(16))) Seg s_seg[kBmSegCap];
@@ -460,6 +463,8 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / nsplit;
+    [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
     const int split = blockIdx.x - q * nsplit;
     const PlanHdr h = hdr[q];
     if (h.total == 0) {
@@ -503,7 +508,7 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
                             const uint32_t off = p - s_lpos[sgi];
                             const uint32_t gi = sg.start + off;
                             code_fetch<CS>(codes, gi, CS, s_lut, w[u]);
-                            load_norm_filter<FILT>(norm_codes, fmask, gi, nb[u], fw[u]);
+                            load_norm_filter<FK>(norm_codes, fmask, gi, nb[u], fw[u], ffill);
                             if constexpr (FILT)
                                 fb[u] = gi & 31u;
                             vp[u] = sg.vpos + off;
@@ -514,7 +519,7 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     if constexpr (FILT)
-                        ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
+                        ok[u] = ok[u] && filter_pass<FK>(fw[u], fb[u], ffill);
                     if (ok[u]) {
                         const float sum = code_sum<CS>(s_lut, w[u]);
                         const float dist = adc_distance(ct[u], s_norm[nb[u]], sum);
@@ -548,10 +553,10 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
 }
 
 hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, uint64_t *keys,
-                            const ScanOut &out, const uint32_t *fmask);
+                            const ScanOut &out, const ScanFilter &fmask);
 
 hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, int nsplit,
-                       uint64_t *keys, int seg_len_hint, const uint32_t *fmask, const ScanOut &out, bool *did_select,
+                       uint64_t *keys, int seg_len_hint, const ScanFilter &fmask, const ScanOut &out, bool *did_select,
                        const char **kernel_name)
 {
     bool unused_sel;
@@ -563,7 +568,7 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
     if (p.nq == 0)
         return hipSuccess;
     if (k != 1) {
-        *kernel_name = fmask ? "scan_topk_kernel+filter" : "scan_topk_kernel";
+        *kernel_name = fmask.name("scan_topk_kernel", "scan_topk_kernel+filter", "scan_topk_kernel+slots");
         return launch_scan_topk(s, t, luts, p, k, keys, out, fmask);
     }
     // several workgroups per query meet in an atomic: nobody knows the winner
@@ -574,7 +579,6 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
     return by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {
         return with_mask(fmask, [&](auto... m) -> hipError_t {
             constexpr int CS = decltype(cs)::value;
-            constexpr bool FILT = sizeof...(m) != 0;
             // the position form: a compiled size unrolls by 4 and stages as many segments as the plan's width asks for
             auto position = [&](auto segcap, auto unroll, const SelOut &so_) -> hipError_t {
                 constexpr auto kern = scan_k1_kernel<CS, decltype(segcap)::value, decltype(unroll)::value, 256, decltype(m)...>;
@@ -588,17 +592,18 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
             };
             if constexpr (CS == 0) {
                 // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS, keys only
-                *kernel_name = FILT ? "scan_k1_kernel (run-time code size)+filter" : "scan_k1_kernel (run-time code size)";
+                *kernel_name = fmask.name("scan_k1_kernel (run-time code size)", "scan_k1_kernel (run-time code size)+filter",
+                                          "scan_k1_kernel (run-time code size)+slots");
                 return position(int_c<256>(), int_c<2>(), SelOut{nullptr, nullptr, nullptr});
             } else if (seg_len_hint > 0 && seg_len_hint <= 48) {
                 // plans of short segments (Grouping sub-groups, ~16 codes): the bitmap form; whole lists: the position form
-                *kernel_name = FILT ? "scan_k1_bitmap_kernel+filter" : "scan_k1_bitmap_kernel";
+                *kernel_name = fmask.name("scan_k1_bitmap_kernel", "scan_k1_bitmap_kernel+filter", "scan_k1_bitmap_kernel+slots");
                 hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4, decltype(m)...>), grid, block, 0, s, t.codes, t.norm_codes, luts,
                                    t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, k64, so, m...);
                 *did_select = so.ids != nullptr;
                 return hipGetLastError();
             } else {
-                *kernel_name = FILT ? "scan_k1_kernel+filter" : "scan_k1_kernel";
+                *kernel_name = fmask.name("scan_k1_kernel", "scan_k1_kernel+filter", "scan_k1_kernel+slots");
                 if (p.max_seg <= 64)
                     return position(int_c<64>(), int_c<4>(), so);
                 // nprobe 65..256 (the DEEP1B preset probes 128 lists): a 5 KB plan instead of 20 KB keeps 7 workgroups

@@ -41,7 +41,7 @@ __device__ __forceinline__ void bitonic_sort_n(unsigned long long *buf, int n, i
     }
 }
 
-// Mask: empty, or the pass mask of a label filter (device_common.h filter_mask): a row whose bit is clear forms no key, so
+// Mask: empty, the pass mask of a label filter, or filter slots per query (device_common.h filter_mask): a row whose bit is clear forms no key, so
 // it enters neither the sort buffer nor the candidate stream.
 template <int CS, class... Mask>
 __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restrict__ codes,
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                                                         int cs_rt, Mask... fmask_arg)
 {
     constexpr bool FILT = sizeof...(Mask) != 0;
-    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(fmask_arg...);
+    constexpr int FK = filter_kind<Mask...>;
     // CS == 0: run-time code size cs_rt, table in dynamic LDS (see scan_k1_kernel)
     __shared__ __attribute__((aligned(16))) float s_lut_fixed[(CS > 0 ? CS : 1) * 256];
     extern __shared__ __attribute__((aligned(16))) float s_lut_dyn[];
@@ -71,6 +71,8 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
 
     const int tid = threadIdx.x;
     const int q = blockIdx.x;
+    [[maybe_unused]] FilterFill ffill; // filter slots: what a query without a plane reads instead (filter_mask)
+    [[maybe_unused]] const uint32_t *__restrict__ fmask = filter_mask(q, ffill, fmask_arg...);
     const PlanHdr h = hdr[q];
     if (h.total == 0) {
         if (stream_len && tid == 0)
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                     const uint32_t off = p - c.seg_lo;
                     const uint32_t gi = c.seg_start + off;
                     code_fetch<CS>(codes, gi, cs_rt, s_lut, w[u]);
-                    load_norm_filter<FILT>(norm_codes, fmask, gi, nbv[u], fw[u]);
+                    load_norm_filter<FK>(norm_codes, fmask, gi, nbv[u], fw[u], ffill);
                     if constexpr (FILT)
                         fb[u] = gi & 31u;
                     vp[u] = c.seg_vpos + off;
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
                 pass[u] = false;
                 key[u] = 0;
                 if constexpr (FILT)
-                    ok[u] = ok[u] && filter_pass(fw[u], fb[u]);
+                    ok[u] = ok[u] && filter_pass<FK>(fw[u], fb[u], ffill);
                 if (ok[u]) {
                     const float sum = code_sum<CS>(s_lut, w[u]);
                     const float dist = adc_distance(ct[u], s_norm[nbv[u]], sum);
@@ -350,7 +352,7 @@ hipError_t launch_heap_replay(hipStream_t s, const IvfTables &t, const PlanView 
 }
 
 hipError_t launch_scan_topk(hipStream_t s, const IvfTables &t, const float *luts, const PlanView &p, int k, uint64_t *keys,
-                            const ScanOut &out, const uint32_t *fmask)
+                            const ScanOut &out, const ScanFilter &fmask)
 {
     if (k < 1 || k > TK_KCAP)
         return hipErrorInvalidValue;

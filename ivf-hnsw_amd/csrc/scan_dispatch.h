@@ -1,13 +1,14 @@
-// How a scan launcher turns two run-time facts -- the code size and whether a label filter is set -- into the template
-// arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
+// How a scan launcher turns two run-time facts -- the code size and how the call is filtered (not at all, by the handle's
+// label filter, by a filter slot per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
 //
 //     by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {          // decltype(cs)::value: 4, 8, 16, 32, or 0 = run-time form
-//         return with_mask(fmask, [&](auto... m) {            // m: the mask, or nothing
+//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, or a SlotMask
 //             launch kernel<decltype(cs)::value, ..., decltype(m)...> with the arguments (..., m...)
 //         });
 //     });
 #pragma once
 
+#include <cstddef>
 #include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
@@ -34,5 +35,45 @@ inline bool runtime_code_size_ok(int M) { return M % 4 == 0 && (size_t)M * 1024 
 
 // f(fmask) with a label filter's pass mask, f() without: the kernels take the mask as an optional trailing argument
 template <class F> auto with_mask(const uint32_t *fmask, F &&f) { return fmask ? f(fmask) : f(); }
+
+// The third form of that argument: every query of the batch names the filter slot it is judged by.
+// planes: one pass mask per slot, plane s at planes + s * stride words, bit r = local row r passes slot s; slots: one
+// byte per query of the launch.  A byte of 0xff (IVFHNSW_SLOT_NONE) passes every row, any other byte at or beyond
+// nplanes passes none (filter_mask, device_common.h); planes points at one readable word at least, also when nplanes
+// is 0 (queries without a plane read word 0 and ignore it).
+struct SlotMask {
+    const uint32_t *planes;
+    uint32_t stride, nplanes;
+    const uint8_t *slots;
+};
+
+// What a scan launcher is told about the filter of its call: nothing, the pass mask of the handle's filter, or filter
+// slots per query (slots.slots non-null).  A bare mask pointer converts, so a caller with one filter passes it as before.
+struct ScanFilter {
+    const uint32_t *fmask = nullptr;
+    SlotMask slots{nullptr, 0, 0, nullptr};
+    ScanFilter() = default;
+    ScanFilter(const uint32_t *m) : fmask(m) {}
+    ScanFilter(std::nullptr_t) {}
+    ScanFilter(const SlotMask &s) : slots(s) {}
+    bool by_slot() const { return slots.slots != nullptr; }
+    bool any() const { return fmask || by_slot(); }
+    // the name a launcher reports: the plain kernel's, "+filter" or "+slots" behind it
+    const char *name(const char *plain, const char *filtered, const char *slotted) const
+    {
+        return by_slot() ? slotted : fmask ? filtered : plain;
+    }
+    // the queries [q0, ...) of the same call
+    ScanFilter from(size_t q0) const
+    {
+        ScanFilter r = *this;
+        if (r.by_slot())
+            r.slots.slots += q0;
+        return r;
+    }
+};
+
+// f(slots) with filter slots, else as above
+template <class F> auto with_mask(const ScanFilter &flt, F &&f) { return flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f); }
 
 } // namespace ivfhnsw_gpu_impl

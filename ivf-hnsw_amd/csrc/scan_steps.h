@@ -46,16 +46,28 @@ template <int CS> __device__ __forceinline__ float code_sum_lds(const float *s_l
 
 // A row's norm code and, under a label filter (device_common.h filter_mask), the 32-bit mask word that holds the row's
 // bit: loaded side by side, so both waits fall together.
-template <bool FILT>
+// KIND: filter_kind (device_common.h).  Under filter slots (2) a query without a plane (FilterFill: keep = 0) reads word 0
+// whatever the row, so that no branch stands here; nothing is done to the loaded word before filter_pass, because a use
+// of it here makes the compiler wait for each unrolled step's loads before it issues the next step's.
+template <int KIND>
 __device__ __forceinline__ void load_norm_filter(const uint8_t *norm_codes, const uint32_t *fmask, uint32_t row, uint32_t &nb,
-                                                 uint32_t &fw)
+                                                 uint32_t &fw, [[maybe_unused]] const FilterFill &fill = FilterFill())
 {
     nb = norm_codes[row];
-    if constexpr (FILT)
+    if constexpr (KIND == 1)
         fw = fmask[row >> 5];
+    if constexpr (KIND == 2)
+        fw = fmask[(row >> 5) & fill.keep];
 }
 // fb = row & 31: the row's bit in that word
 __device__ __forceinline__ bool filter_pass(uint32_t fw, uint32_t fb) { return (fw >> fb) & 1u; }
+// ... under filter slots through the query's two scalars: the plane's word, all ones (NONE) or zero (no such slot)
+template <int KIND> __device__ __forceinline__ bool filter_pass(uint32_t fw, uint32_t fb, [[maybe_unused]] const FilterFill &fill)
+{
+    if constexpr (KIND == 2)
+        fw = (fw & fill.keep) | fill.all;
+    return (fw >> fb) & 1u;
+}
 
 // The table of query q into LDS, global -> LDS directly (global_load_lds_dwordx4: wave-uniform LDS base + lane * 16): the
 // table never passes through VGPRs, and a ds_write_b128 costs the LDS pipe 13 cycles where the DMA's write costs 4 -- the

@@ -9,7 +9,16 @@ index):
   2. search_dev queries/s (10 k queries, k = 1) of ONE handle in one run, in this order: unfiltered; deny nothing (every
      row passes: the cost of the filtered kernels alone); allow 50 %; allow 10 %; allow 1 %; unfiltered again.  The
      reference point of every filtered figure is the unfiltered pair of the same run.
-usage: python tools/filter_bench.py [--workload NAME] [--sizes 1000,10000000,500000000] [--fractions 0.5,0.1,0.01]"""
+With --slots, filter slots (ivfhnsw_gpu_search_slots) instead, on the same corpus and ONE handle:
+  3. --reps (>= 5) alternating repetitions of: (a) unfiltered; (b) set_filter allow 10 %; (c) _slots, every query on one slot
+     holding that same set; (d) _slots, 32 installed 10 % sets dealt round-robin; (e) _slots, every query NONE.  Per form and
+     repetition the step time (wall, 10 steps behind 5 warm-up steps) and the scan stage's time per step (profiling level 2).
+     The yardstick of (c) is (b) of the same run: its min-max spread over the repetitions is reported beside the difference.
+  4. set_filter_slot_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev with no filter, with the single filter
+     installed, and with 1, 8 and 32 slots installed (wall ms, each twice; what the append costs beyond the unfiltered one
+     is the re-mark).
+usage: python tools/filter_bench.py [--workload NAME] [--sizes 1000,10000000,500000000] [--fractions 0.5,0.1,0.01]
+       python tools/filter_bench.py --slots [--reps 5] [--append 10000000]"""
 import argparse
 import json
 import os
@@ -25,11 +34,124 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def slots_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, labels_of, out):
+    n10 = c.n_total // 10
+    same = labels_of(n10, 30)
+    t = time.perf_counter()
+    g.set_filter_slot_dev(0, n10, same)
+    out["first_set_filter_slot_dev_ms"] = (time.perf_counter() - t) * 1e3
+    for s in range(1, pkg.FILTER_SLOTS):
+        g.set_filter_slot_dev(s, n10, labels_of(n10, 100 + s))
+    assert all(g.filter_slot_info(s) == (0, n10, c.n_total) for s in range(pkg.FILTER_SLOTS))
+    out["memory_GB_with_32_slots"] = g.memory_bytes() / 1e9
+    one = torch.zeros(nq, dtype=torch.uint8, device=dev)
+    dealt = (torch.arange(nq, device=dev) % pkg.FILTER_SLOTS).to(torch.uint8)
+    none = torch.full((nq,), pkg.SLOT_NONE, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    forms = [("a unfiltered", None, False), ("b set_filter 10 %", None, True), ("c slots, one slot", one, False),
+             ("d slots, 32 dealt", dealt, False), ("e slots, all NONE", none, False)]
+
+    def step(qs):
+        if qs is None:
+            g.search_dev(nq, 1, q, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        else:
+            g.search_slots_dev(nq, 1, q, qs, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+
+    def measure(qs, steps=10):
+        for _ in range(5):
+            step(qs)
+        g.sync()
+        t = time.perf_counter()
+        for _ in range(steps):
+            step(qs)
+        g.sync()
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        g.set_profiling(2)
+        g.reset_stage_ms()
+        for _ in range(steps):
+            step(qs)
+        g.sync()
+        scan = g.stage_ms()["scan"][0] / steps
+        g.set_profiling(0)
+        return wall, scan, g.last_scan_kernel()
+
+    runs = {name: {"step_ms": [], "scan_ms": []} for name, _, _ in forms}
+    for _ in range(max(5, args.reps)):
+        for name, qs, single in forms:
+            if single:
+                g.set_filter_dev(n10, same)
+            wall, scan, kernel = measure(qs)
+            if single:
+                g.clear_filter()
+            runs[name]["step_ms"].append(wall)
+            runs[name]["scan_ms"].append(scan)
+            runs[name]["kernel"] = kernel
+    for name, r in runs.items():
+        for key in ("step_ms", "scan_ms"):
+            v = r[key]
+            r[key + "_min_mean_max"] = [min(v), sum(v) / len(v), max(v)]
+        log("[filter_bench] %-20s step %.4f ms, scan %.4f ms  (%s)" %
+            (name, r["step_ms_min_mean_max"][1], r["scan_ms_min_mean_max"][1], r["kernel"]))
+    out["slots_search"] = runs
+    b, cc = runs["b set_filter 10 %"], runs["c slots, one slot"]
+    out["c_minus_b_scan_ms"] = cc["scan_ms_min_mean_max"][1] - b["scan_ms_min_mean_max"][1]
+    out["b_scan_spread_ms"] = b["scan_ms_min_mean_max"][2] - b["scan_ms_min_mean_max"][0]
+    out["c_minus_b_step_ms"] = cc["step_ms_min_mean_max"][1] - b["step_ms_min_mean_max"][1]
+    out["b_step_spread_ms"] = b["step_ms_min_mean_max"][2] - b["step_ms_min_mean_max"][0]
+
+    # 4. install and re-mark
+    n10m = min(10 ** 7, c.n_total)
+    lab = labels_of(n10m, 31)
+    t = time.perf_counter()
+    g.set_filter_slot_dev(0, n10m, lab)
+    out["set_filter_slot_dev_10M_ms"] = (time.perf_counter() - t) * 1e3
+    n = args.append
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(5)
+    li = torch.randint(0, c.nc, (n,), device=dev, generator=gen, dtype=torch.int32)
+    codes = torch.randint(0, 256, (n, c.M), device=dev, generator=gen, dtype=torch.uint8)
+    ncodes = torch.randint(0, 255, (n,), device=dev, generator=gen, dtype=torch.uint8)
+    torch.cuda.synchronize(dev)
+    appends = []
+    first_id = c.n_total
+
+    def timed_append(what):
+        nonlocal first_id
+        ids = (torch.arange(n, device=dev, dtype=torch.int64) + first_id).to(torch.int32)
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        g.append_ivf_dev(n, li, ids, codes, ncodes)
+        g.sync()
+        ms = (time.perf_counter() - t) * 1e3
+        first_id += n
+        appends.append({"installed": what, "append_ms": ms})
+        log("[filter_bench] append_ivf_dev of %d codes, %s: %.1f ms" % (n, what, ms))
+
+    g.clear_filter_slot()
+    timed_append("nothing (warm-up: allocations)")
+    timed_append("nothing")
+    timed_append("nothing")
+    g.set_filter_dev(n10, same)
+    timed_append("the single filter")
+    timed_append("the single filter")
+    g.clear_filter()
+    for count in (1, 8, 32):
+        for s in range(count):
+            if g.filter_slot_info(s)[0] < 0:
+                g.set_filter_slot_dev(s, n10, labels_of(n10, 100 + s))
+        timed_append("%d slots" % count)  # the first append after an install also allocates the larger planes anew
+        timed_append("%d slots" % count)
+    out["append"] = appends
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="synthetic-1B-pq16-nc993127-nprobe32")
     ap.add_argument("--sizes", default="1000,10000000,500000000")
     ap.add_argument("--fractions", default="0.5,0.1,0.01")
+    ap.add_argument("--slots", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--append", type=int, default=10 ** 7)
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -76,6 +198,12 @@ def main():
         mode, passing, total = g.filter_info()
         assert total == c.n_total and passing == (total - n if deny else n), (mode, passing, total, n)
         return ms, passing
+
+    if args.slots:
+        slots_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, labels_of, out)
+        g.close()
+        print(json.dumps(out))
+        return
 
     # 1. installing
     ms, _ = timed_set(1, False, 1)
