@@ -22,19 +22,17 @@ void base_filter_drop(ivfhnsw_gpu *h)
 // the passing rows of words [n rows, npass of them passing > 0] into rows (allocated here), on h's stream; workspace freed
 static int build_pass_rows(ivfhnsw_gpu *h, const uint32_t *words, uint64_t n, uint64_t npass, DevBuf &rows)
 {
-    DevBuf cnt, part;
+    ScopedBuf cnt, part;
     const size_t len = sweep_pass_words(n) + 1;
     int rc;
     if ((rc = rows.ensure(npass * sizeof(uint32_t))) == IVFHNSW_OK && (rc = cnt.ensure(len * sizeof(uint32_t))) == IVFHNSW_OK &&
         (rc = part.ensure(append_scan_parts(len) * sizeof(uint32_t))) == IVFHNSW_OK) {
         hipError_t e = launch_pass_rows(h->stream, words, n, cnt.as<uint32_t>(), part.as<uint32_t>(), rows.as<uint32_t>());
         if (e == hipSuccess)
-            e = hipStreamSynchronize(h->stream); // the workspace goes below
+            e = hipStreamSynchronize(h->stream); // the workspace goes with this scope
         if (e != hipSuccess)
             rc = fail(IVFHNSW_ERR_HIP, "base filter, pass rows: %s", hipGetErrorString(e));
     }
-    cnt.release();
-    part.release();
     return rc;
 }
 
@@ -69,64 +67,37 @@ int base_filter_cols(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, SweepCols *cols, size
     return IVFHNSW_OK;
 }
 
-static int base_filter_state(ivfhnsw_gpu *h, const char *who)
+// what both forms of set_base_filter check first
+static int set_base_filter_guard(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int mode, const char *who)
 {
-    if (h && h->is_view)
-        return fail(IVFHNSW_ERR_STATE, "%s: a base filter goes to the handle that holds the store, not to a view of it", who);
-    int rc = bind(h);
-    if (rc)
-        return rc;
-    if (!h->base_n)
-        return fail(IVFHNSW_ERR_STATE, "%s before upload_base", who);
-    return IVFHNSW_OK;
-}
-
-static int check_args(size_t n, const uint32_t *labels, int mode, const char *who)
-{
-    if (n && !labels)
-        return fail(IVFHNSW_ERR_INVALID, "%s: null labels", who);
-    if (mode != IVFHNSW_FILTER_ALLOW && mode != IVFHNSW_FILTER_DENY)
-        return fail(IVFHNSW_ERR_INVALID, "%s: mode %d is neither IVFHNSW_FILTER_ALLOW nor IVFHNSW_FILTER_DENY", who, mode);
-    return IVFHNSW_OK;
+    int rc = filter_holder_guard(h, kBaseFilter, who, true);
+    return rc ? rc : label_args_guard(n, labels, who, &mode);
 }
 
 // d_labels [n] in device memory (n > 0: max_label = their maximum), read on the handle's stream.  Words and rows are built
 // beside the installed ones and swapped in when complete: any error leaves the earlier filter in force.
 static int set_base_filter_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t max_label, int mode)
 {
-    DevBuf bits, words, rows;
+    ScopedBuf words, rows;
     const uint64_t rows_n = h->base_n;
     unsigned long long pass = 0;
-    bool has_rows = false;
-    auto build = [&]() -> int {
-        int rc;
-        const size_t bit_words = n ? (size_t)max_label / 32 + 1 : 0;
-        if (n) {
-            if ((rc = bits.ensure(bit_words * sizeof(uint32_t))))
-                return rc;
-            HIP_TRY(launch_remove_bits(h->stream, d_labels, n, max_label, bits.as<uint32_t>()));
-        }
-        if ((rc = words.ensure(sweep_pass_words(rows_n) * sizeof(uint32_t))) || (rc = h->bf_count.ensure(sizeof(unsigned long long))))
+    int rc;
+    {
+        ScopedBuf bits; // gone before the rows are built
+        if ((rc = labels_bitmap(h, n, d_labels, max_label, bits)) || (rc = words.ensure(sweep_pass_words(rows_n) * sizeof(uint32_t))) ||
+            (rc = h->bf_count.ensure(sizeof(unsigned long long))))
             return rc;
-        HIP_TRY(launch_pass_words(h->stream, n ? bits.as<uint32_t>() : nullptr, bit_words, rows_n, mode == IVFHNSW_FILTER_DENY,
-                                  words.as<uint32_t>(), h->bf_count.as<unsigned long long>()));
+        HIP_TRY(launch_pass_words(h->stream, bits.as<uint32_t>(), n ? label_bitmap_words(max_label) : 0, rows_n,
+                                  mode == IVFHNSW_FILTER_DENY, words.as<uint32_t>(), h->bf_count.as<unsigned long long>()));
         // the one word that comes back: base_filter_info's count and the choice of form
         HIP_TRY(hipMemcpyAsync(&pass, h->bf_count.p, sizeof(pass), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        bits.release();
-        has_rows = pass > 0 && (sweep_pass_list_kept(pass, rows_n) || h->opt_exact_filter_form == 1);
-        return has_rows ? build_pass_rows(h, words.as<uint32_t>(), rows_n, pass, rows) : IVFHNSW_OK;
-    };
-    if (int rc = build()) {
-        bits.release();
-        words.release();
-        rows.release();
-        return rc;
     }
-    std::swap(h->bf_words, words);
-    std::swap(h->bf_rows, rows);
-    words.release(); // the earlier filter's
-    rows.release();
+    const bool has_rows = pass > 0 && (sweep_pass_list_kept(pass, rows_n) || h->opt_exact_filter_form == 1);
+    if (has_rows && (rc = build_pass_rows(h, words.as<uint32_t>(), rows_n, pass, rows)))
+        return rc;
+    words.install(h->bf_words); // the earlier filter's go with this scope
+    rows.install(h->bf_rows);
     h->bf_mode = mode;
     h->bf_pass = pass;
     h->bf_has_rows = has_rows;
@@ -138,46 +109,33 @@ static int set_base_filter_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labe
 
 int ivfhnsw_gpu_set_base_filter(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int mode)
 {
-    int rc = base_filter_state(h, "set_base_filter");
-    if (rc || (rc = check_args(n, labels, mode, "set_base_filter")))
+    int rc = set_base_filter_guard(h, n, labels, mode, "set_base_filter");
+    if (rc)
         return rc;
+    ScopedBuf stage; // of this call only
     uint32_t mx = 0;
-    for (size_t i = 0; i < n; i++)
-        mx = std::max(mx, labels[i]);
-    if (n) {
-        if ((rc = h->bf_labels.ensure(n * sizeof(uint32_t))))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(h->bf_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    }
-    rc = set_base_filter_core(h, n, h->bf_labels.as<uint32_t>(), mx, mode);
-    h->bf_labels.release(); // staging of this call only
-    return rc;
+    if ((rc = labels_from_host(h, n, labels, stage, &mx)))
+        return rc;
+    return set_base_filter_core(h, n, stage.as<uint32_t>(), mx, mode);
 }
 
 int ivfhnsw_gpu_set_base_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int mode)
 {
-    int rc = base_filter_state(h, "set_base_filter_dev");
-    if (rc || (rc = check_args(n, d_labels, mode, "set_base_filter_dev")))
+    int rc = set_base_filter_guard(h, n, d_labels, mode, "set_base_filter_dev");
+    if (rc)
         return rc;
     if ((uintptr_t)d_labels & 3)
         return fail(IVFHNSW_ERR_INVALID, "set_base_filter_dev: labels must be 4-byte aligned");
     uint32_t mx = 0;
-    if (n) {
-        if ((rc = h->bf_count.ensure(sizeof(unsigned long long))))
-            return rc;
-        HIP_TRY(hipMemsetAsync(h->bf_count.p, 0, sizeof(uint32_t), h->stream));
-        HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->bf_count.as<uint32_t>()));
-        HIP_TRY(hipMemcpyAsync(&mx, h->bf_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+    // the count's buffer at the size the mark wants it (not grown a second time there); the maximum comes through its first word
+    if ((n && (rc = h->bf_count.ensure(sizeof(unsigned long long)))) || (rc = labels_max_dev(h, h->bf_count, n, d_labels, &mx)))
+        return rc;
     return set_base_filter_core(h, n, d_labels, mx, mode);
 }
 
 int ivfhnsw_gpu_clear_base_filter(ivfhnsw_gpu *h)
 {
-    if (h && h->is_view)
-        return fail(IVFHNSW_ERR_STATE, "clear_base_filter: a base filter goes to the handle that holds the store, not to a view of it");
-    int rc = bind(h);
+    int rc = filter_holder_guard(h, kBaseFilter, "clear_base_filter", false);
     if (rc)
         return rc;
     if (h->bf_mode < 0)
@@ -194,11 +152,5 @@ int ivfhnsw_gpu_base_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passi
     if (!h)
         return fail(IVFHNSW_ERR_INVALID, "null handle");
     const ivfhnsw_gpu *b = h->parent ? h->parent : h;
-    if (mode)
-        *mode = b->bf_mode;
-    if (rows_passing)
-        *rows_passing = b->bf_mode >= 0 ? b->bf_pass : b->base_n;
-    if (rows_total)
-        *rows_total = b->base_n;
-    return IVFHNSW_OK;
+    return label_set_info(b->bf_mode, b->bf_pass, b->base_n, b->base_n, mode, rows_passing, rows_total);
 }

@@ -26,30 +26,21 @@ static int mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, cons
 
 int filter_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &mask, uint64_t *pass)
 {
-    return mark_rows(h, ids, n_local, h->f_has_bits ? h->f_bits.as<uint32_t>() : nullptr, h->f_max_label, h->filter_mode, mask,
-                     pass);
+    return mark_rows(h, ids, n_local, h->filter.bitmap(), h->filter.max_label, h->filter.mode, mask, pass);
 }
 
 void filter_drop(ivfhnsw_gpu *h)
 {
-    h->filter_mode = -1;
+    h->filter.drop();
     h->fmask = nullptr;
-    h->f_has_bits = false;
-    h->f_max_label = 0;
-    h->f_pass = 0;
     h->f_mask.release();
-    h->f_bits.release();
 }
 
 static int filter_state(ivfhnsw_gpu *h, const char *who)
 {
-    if (h && h->is_view)
-        return fail(IVFHNSW_ERR_STATE, "%s: a filter goes to the handle that holds the tables, not to a view of it", who);
-    int rc = bind(h);
+    int rc = filter_holder_guard(h, kIndexFilter, who, true);
     if (rc)
         return rc;
-    if (!h->has_ivf)
-        return fail(IVFHNSW_ERR_STATE, "%s before upload_ivf", who);
     if (h->t.shard_world > 1)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no label filter", who,
                     h->t.shard_rank, h->t.shard_world);
@@ -60,30 +51,15 @@ static int filter_state(ivfhnsw_gpu *h, const char *who)
 // are built beside the installed ones and swapped in when complete: any error leaves the earlier filter in force.
 static int set_filter_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t max_label, int mode)
 {
-    DevBuf bits, mask;
-    int rc = IVFHNSW_OK;
+    ScopedBuf bits, mask;
+    int rc;
     uint64_t pass = 0;
-    if (n && (rc = bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))) == IVFHNSW_OK) {
-        hipError_t e = launch_remove_bits(h->stream, d_labels, n, max_label, bits.as<uint32_t>());
-        if (e != hipSuccess)
-            rc = fail(IVFHNSW_ERR_HIP, "set_filter: %s", hipGetErrorString(e));
-    }
-    if (rc == IVFHNSW_OK)
-        rc = mark_rows(h, h->t.ids, h->n_local, n ? bits.as<uint32_t>() : nullptr, max_label, mode, mask, &pass);
-    if (rc) {
-        bits.release();
-        mask.release();
+    if ((rc = labels_bitmap(h, n, d_labels, max_label, bits)) ||
+        (rc = mark_rows(h, h->t.ids, h->n_local, bits.as<uint32_t>(), max_label, mode, mask, &pass)))
         return rc;
-    }
-    std::swap(h->f_bits, bits);
-    std::swap(h->f_mask, mask);
-    bits.release(); // the earlier filter's
-    mask.release();
-    h->filter_mode = mode;
+    h->filter.install(bits, n, max_label, mode, pass); // the earlier filter's bitmap and mask go with this scope
+    mask.install(h->f_mask);
     h->fmask = h->f_mask.as<uint32_t>();
-    h->f_has_bits = n != 0;
-    h->f_max_label = n ? max_label : 0;
-    h->f_pass = pass;
     return IVFHNSW_OK;
 }
 
@@ -94,13 +70,8 @@ void slots_drop(ivfhnsw_gpu *h)
 {
     h->fs = SlotMask{nullptr, 0, 0, nullptr};
     h->fs_planes.release();
-    for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++) {
-        h->fs_bits[s].release();
-        h->fs_mode[s] = -1;
-        h->fs_has_bits[s] = false;
-        h->fs_max_label[s] = 0;
-        h->fs_pass[s] = 0;
-    }
+    for (LabelSet &s : h->slots)
+        s.drop();
 }
 
 int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &planes, uint64_t *pass)
@@ -113,10 +84,10 @@ int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBu
         return rc;
     FilterSlotSets sets{};
     for (uint32_t s = 0; s < np; s++) {
-        sets.bits[s] = h->fs_has_bits[s] ? h->fs_bits[s].as<uint32_t>() : nullptr;
-        sets.max_label[s] = h->fs_max_label[s];
-        sets.set[s] = h->fs_mode[s] >= 0;
-        sets.deny[s] = h->fs_mode[s] == IVFHNSW_FILTER_DENY;
+        sets.bits[s] = h->slots[s].bitmap();
+        sets.max_label[s] = h->slots[s].max_label;
+        sets.set[s] = h->slots[s].mode >= 0;
+        sets.deny[s] = h->slots[s].mode == IVFHNSW_FILTER_DENY;
     }
     if (n_local == 0) // no kernel runs: the one word of every plane
         HIP_TRY(hipMemsetAsync(planes.p, 0, (size_t)np * stride * sizeof(uint32_t), h->stream));
@@ -135,7 +106,7 @@ int slots_call_guard(const ivfhnsw_gpu *h, const char *who)
     if (h->t.shard_world > 1)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no filter slots", who,
                     h->t.shard_rank, h->t.shard_world);
-    if (h->filter_mode >= 0)
+    if (h->filter.mode >= 0)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle has a set_filter filter installed; a call is filtered by that or by "
                                        "slots, not both (clear_filter first)", who);
     return IVFHNSW_OK;
@@ -165,10 +136,10 @@ static int planes_resized(ivfhnsw_gpu *h, uint32_t np, DevBuf &out)
     return IVFHNSW_OK;
 }
 
-static void planes_install(ivfhnsw_gpu *h, DevBuf &planes, uint32_t np)
+// ... installed; the earlier planes go with the scope of `planes`
+static void planes_install(ivfhnsw_gpu *h, ScopedBuf &planes, uint32_t np)
 {
-    std::swap(h->fs_planes, planes);
-    planes.release();
+    planes.install(h->fs_planes);
     h->fs = SlotMask{np ? h->fs_planes.as<uint32_t>() : nullptr, np ? (uint32_t)slot_plane_stride(h->n_local) : 0u, np, nullptr};
 }
 
@@ -177,52 +148,23 @@ static void planes_install(ivfhnsw_gpu *h, DevBuf &planes, uint32_t np)
 // leaves every slot as it was.
 static int set_slot_core(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, uint32_t max_label, int mode)
 {
-    DevBuf bits, mask, planes;
-    int rc = IVFHNSW_OK;
+    ScopedBuf bits, mask, planes;
+    int rc;
     uint64_t pass = 0;
     const bool grow = slot >= h->fs.nplanes;
     const size_t pb = (size_t)slot_plane_stride(h->n_local) * sizeof(uint32_t);
-    auto body = [&]() -> int {
-        if (n) {
-            if ((rc = bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))))
-                return rc;
-            HIP_TRY(launch_remove_bits(h->stream, d_labels, n, max_label, bits.as<uint32_t>()));
-        }
-        if ((rc = mark_rows(h, h->t.ids, h->n_local, n ? bits.as<uint32_t>() : nullptr, max_label, mode, mask, &pass)))
-            return rc;
-        if (grow && (rc = planes_resized(h, slot + 1, planes)))
-            return rc;
-        // the last fallible step writes the plane: into the new buffer, or over the slot's own plane, which only this
-        // slot's queries read
-        char *dst = (grow ? planes.as<char>() : h->fs_planes.as<char>()) + (size_t)slot * pb;
-        HIP_TRY(hipMemcpyAsync(dst, mask.p, pb, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        return IVFHNSW_OK;
-    };
-    rc = body();
-    mask.release();
-    if (rc) {
-        bits.release();
-        planes.release();
+    if ((rc = labels_bitmap(h, n, d_labels, max_label, bits)) ||
+        (rc = mark_rows(h, h->t.ids, h->n_local, bits.as<uint32_t>(), max_label, mode, mask, &pass)) ||
+        (grow && (rc = planes_resized(h, slot + 1, planes))))
         return rc;
-    }
+    // the last fallible step writes the plane: into the new buffer, or over the slot's own plane, which only this
+    // slot's queries read
+    char *dst = (grow ? planes.as<char>() : h->fs_planes.as<char>()) + (size_t)slot * pb;
+    HIP_TRY(hipMemcpyAsync(dst, mask.p, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     if (grow)
         planes_install(h, planes, slot + 1);
-    std::swap(h->fs_bits[slot], bits);
-    bits.release(); // the slot's earlier set
-    h->fs_mode[slot] = mode;
-    h->fs_has_bits[slot] = n != 0;
-    h->fs_max_label[slot] = n ? max_label : 0;
-    h->fs_pass[slot] = pass;
-    return IVFHNSW_OK;
-}
-
-static int check_args(size_t n, const uint32_t *labels, int mode, const char *who)
-{
-    if (n && !labels)
-        return fail(IVFHNSW_ERR_INVALID, "%s: null labels", who);
-    if (mode != IVFHNSW_FILTER_ALLOW && mode != IVFHNSW_FILTER_DENY)
-        return fail(IVFHNSW_ERR_INVALID, "%s: mode %d is neither IVFHNSW_FILTER_ALLOW nor IVFHNSW_FILTER_DENY", who, mode);
+    h->slots[slot].install(bits, n, max_label, mode, pass); // the slot's earlier set goes with this scope
     return IVFHNSW_OK;
 }
 
@@ -231,48 +173,35 @@ static int check_args(size_t n, const uint32_t *labels, int mode, const char *wh
 int ivfhnsw_gpu_set_filter(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int mode)
 {
     int rc = filter_state(h, "set_filter");
-    if (rc || (rc = check_args(n, labels, mode, "set_filter")))
+    if (rc || (rc = label_args_guard(n, labels, "set_filter", &mode)))
         return rc;
+    ScopedBuf stage; // of this call only
     uint32_t mx = 0;
-    for (size_t i = 0; i < n; i++)
-        mx = std::max(mx, labels[i]);
-    if (n) {
-        if ((rc = h->f_labels.ensure(n * sizeof(uint32_t))))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(h->f_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    }
-    rc = set_filter_core(h, n, h->f_labels.as<uint32_t>(), mx, mode);
-    h->f_labels.release(); // staging of this call only
-    return rc;
+    if ((rc = labels_from_host(h, n, labels, stage, &mx)))
+        return rc;
+    return set_filter_core(h, n, stage.as<uint32_t>(), mx, mode);
 }
 
 int ivfhnsw_gpu_set_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int mode)
 {
     int rc = filter_state(h, "set_filter_dev");
-    if (rc || (rc = check_args(n, d_labels, mode, "set_filter_dev")))
+    if (rc || (rc = label_args_guard(n, d_labels, "set_filter_dev", &mode)))
         return rc;
     if ((uintptr_t)d_labels & 3)
         return fail(IVFHNSW_ERR_INVALID, "set_filter_dev: labels must be 4-byte aligned");
     uint32_t mx = 0;
-    if (n) {
-        if ((rc = h->f_count.ensure(sizeof(unsigned long long))))
-            return rc;
-        HIP_TRY(hipMemsetAsync(h->f_count.p, 0, sizeof(uint32_t), h->stream));
-        HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->f_count.as<uint32_t>()));
-        HIP_TRY(hipMemcpyAsync(&mx, h->f_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+    // the count's buffer at the size the mark wants it (not grown a second time there); the maximum comes through its first word
+    if ((n && (rc = h->f_count.ensure(sizeof(unsigned long long)))) || (rc = labels_max_dev(h, h->f_count, n, d_labels, &mx)))
+        return rc;
     return set_filter_core(h, n, d_labels, mx, mode);
 }
 
 int ivfhnsw_gpu_clear_filter(ivfhnsw_gpu *h)
 {
-    if (h && h->is_view)
-        return fail(IVFHNSW_ERR_STATE, "clear_filter: a filter goes to the handle that holds the tables, not to a view of it");
-    int rc = bind(h);
+    int rc = filter_holder_guard(h, kIndexFilter, "clear_filter", false);
     if (rc)
         return rc;
-    if (h->filter_mode < 0)
+    if (h->filter.mode < 0)
         return IVFHNSW_OK;
     HIP_TRY(hipStreamSynchronize(h->stream)); // searches in flight still read the mask (a split batch joins this stream)
     filter_drop(h);
@@ -283,13 +212,7 @@ int ivfhnsw_gpu_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, u
 {
     if (!h)
         return fail(IVFHNSW_ERR_INVALID, "null handle");
-    if (mode)
-        *mode = h->filter_mode;
-    if (rows_passing)
-        *rows_passing = h->filter_mode >= 0 ? h->f_pass : h->n_local;
-    if (rows_total)
-        *rows_total = h->n_local;
-    return IVFHNSW_OK;
+    return label_set_info(h->filter.mode, h->filter.pass, h->n_local, h->n_local, mode, rows_passing, rows_total);
 }
 
 // ---- filter slots
@@ -298,7 +221,7 @@ static int slot_args(unsigned slot, size_t n, const uint32_t *labels, int mode, 
 {
     if (slot >= IVFHNSW_FILTER_SLOTS)
         return fail(IVFHNSW_ERR_INVALID, "%s: slot %u, a handle has slots 0..%d", who, slot, IVFHNSW_FILTER_SLOTS - 1);
-    return check_args(n, labels, mode, who);
+    return label_args_guard(n, labels, who, &mode);
 }
 
 int ivfhnsw_gpu_set_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode)
@@ -306,17 +229,11 @@ int ivfhnsw_gpu_set_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const u
     int rc = filter_state(h, "set_filter_slot");
     if (rc || (rc = slot_args(slot, n, labels, mode, "set_filter_slot")))
         return rc;
+    ScopedBuf stage; // of this call only
     uint32_t mx = 0;
-    for (size_t i = 0; i < n; i++)
-        mx = std::max(mx, labels[i]);
-    if (n) {
-        if ((rc = h->fs_labels.ensure(n * sizeof(uint32_t))))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(h->fs_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    }
-    rc = set_slot_core(h, slot, n, h->fs_labels.as<uint32_t>(), mx, mode);
-    h->fs_labels.release(); // staging of this call only
-    return rc;
+    if ((rc = labels_from_host(h, n, labels, stage, &mx)))
+        return rc;
+    return set_slot_core(h, slot, n, stage.as<uint32_t>(), mx, mode);
 }
 
 int ivfhnsw_gpu_set_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, int mode)
@@ -327,14 +244,9 @@ int ivfhnsw_gpu_set_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, con
     if ((uintptr_t)d_labels & 3)
         return fail(IVFHNSW_ERR_INVALID, "set_filter_slot_dev: labels must be 4-byte aligned");
     uint32_t mx = 0;
-    if (n) {
-        if ((rc = h->f_count.ensure(sizeof(unsigned long long))))
-            return rc;
-        HIP_TRY(hipMemsetAsync(h->f_count.p, 0, sizeof(uint32_t), h->stream));
-        HIP_TRY(launch_remove_max(h->stream, d_labels, n, h->f_count.as<uint32_t>()));
-        HIP_TRY(hipMemcpyAsync(&mx, h->f_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+    // the count's buffer at the size the mark wants it (not grown a second time there); the maximum comes through its first word
+    if ((n && (rc = h->f_count.ensure(sizeof(unsigned long long)))) || (rc = labels_max_dev(h, h->f_count, n, d_labels, &mx)))
+        return rc;
     return set_slot_core(h, slot, n, d_labels, mx, mode);
 }
 
@@ -346,7 +258,7 @@ int ivfhnsw_gpu_clear_filter_slot(ivfhnsw_gpu *h, int slot)
     if (slot < -1 || slot >= IVFHNSW_FILTER_SLOTS)
         return fail(IVFHNSW_ERR_INVALID, "clear_filter_slot: slot %d, a handle has slots 0..%d (-1: every slot)", slot,
                     IVFHNSW_FILTER_SLOTS - 1);
-    if (slot >= 0 && h->fs_mode[slot] < 0)
+    if (slot >= 0 && h->slots[slot].mode < 0)
         return IVFHNSW_OK;
     HIP_TRY(hipStreamSynchronize(h->stream)); // searches in flight still read the planes (a split batch joins this stream)
     if (slot < 0) {
@@ -356,26 +268,20 @@ int ivfhnsw_gpu_clear_filter_slot(ivfhnsw_gpu *h, int slot)
     // planes reach to the highest slot in use: clearing that one gives the planes above the next back
     uint32_t np = 0;
     for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++)
-        if (s != slot && h->fs_mode[s] >= 0)
+        if (s != slot && h->slots[s].mode >= 0)
             np = (uint32_t)s + 1;
     const size_t pb = (size_t)slot_plane_stride(h->n_local) * sizeof(uint32_t);
     if (np < h->fs.nplanes) {
-        DevBuf planes;
-        if (np && (rc = planes_resized(h, np, planes))) {
-            planes.release();
+        ScopedBuf planes;
+        if (np && (rc = planes_resized(h, np, planes)))
             return rc;
-        }
         HIP_TRY(hipStreamSynchronize(h->stream));
         planes_install(h, planes, np);
     } else {
         HIP_TRY(hipMemsetAsync(h->fs_planes.as<char>() + (size_t)slot * pb, 0, pb, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    h->fs_bits[slot].release();
-    h->fs_mode[slot] = -1;
-    h->fs_has_bits[slot] = false;
-    h->fs_max_label[slot] = 0;
-    h->fs_pass[slot] = 0;
+    h->slots[slot].drop();
     return IVFHNSW_OK;
 }
 
@@ -385,12 +291,6 @@ int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint6
         return fail(IVFHNSW_ERR_INVALID, "null handle");
     if (slot >= IVFHNSW_FILTER_SLOTS)
         return fail(IVFHNSW_ERR_INVALID, "filter_slot_info: slot %u, a handle has slots 0..%d", slot, IVFHNSW_FILTER_SLOTS - 1);
-    const ivfhnsw_gpu *holder = h->is_view && h->parent ? h->parent : h;
-    if (mode)
-        *mode = holder->fs_mode[slot];
-    if (rows_passing)
-        *rows_passing = holder->fs_mode[slot] >= 0 ? holder->fs_pass[slot] : 0;
-    if (rows_total)
-        *rows_total = h->n_local;
-    return IVFHNSW_OK;
+    const LabelSet &s = (h->is_view && h->parent ? h->parent : h)->slots[slot];
+    return label_set_info(s.mode, s.pass, 0, h->n_local, mode, rows_passing, rows_total);
 }

@@ -90,9 +90,9 @@ void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent)
     view->has_group = parent->has_group;
     view->gr = parent->gr;
     view->has_graph = parent->has_graph;
-    view->filter_mode = parent->filter_mode; // the view filters as its parent does at this moment
+    view->filter.mode = parent->filter.mode; // the view filters as its parent does at this moment
     view->fmask = parent->fmask;
-    view->f_pass = parent->f_pass;
+    view->filter.pass = parent->filter.pass; // (mode and count only: the bitmap stays the parent's)
     view->fs = parent->fs; // ... and reads the filter slots its parent holds
 }
 

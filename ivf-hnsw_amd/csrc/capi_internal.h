@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -53,6 +54,49 @@ struct DevBuf {
         bytes = 0;
     }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// A DevBuf of one scope: whatever it holds when the scope ends is freed.  A function that builds new state beside what
+// the handle has installed keeps it in these, and when nothing can fail any more gives each to its handle member; the
+// member's earlier allocation is then this scope's to free.  Every early return frees what was built so far.
+struct ScopedBuf : DevBuf {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf &) = delete;
+    ScopedBuf &operator=(const ScopedBuf &) = delete;
+    ~ScopedBuf() { release(); }
+    void install(DevBuf &member) { std::swap(static_cast<DevBuf &>(*this), member); }
+};
+
+// A label set a handle keeps (the filter, each filter slot): its bitmap over [0, max_label], so that an update can judge
+// the rows of its new arrays, and what the set's own calls report.  mode -1 = no set.  Not copied: a view takes the
+// fields it reads (follow_parent), never the buffer.
+struct LabelSet {
+    DevBuf bits;
+    uint32_t max_label = 0;
+    bool has_bits = false; // false = the empty set (bits unallocated)
+    int mode = -1;
+    uint64_t pass = 0; // rows of the resident lists that pass
+    LabelSet() = default;
+    LabelSet(const LabelSet &) = delete;
+    LabelSet &operator=(const LabelSet &) = delete;
+    const uint32_t *bitmap() const { return has_bits ? bits.as<uint32_t>() : nullptr; }
+    // the set of n labels whose bitmap was built in fresh (capi_labels.cpp labels_bitmap); fresh leaves with the earlier one
+    void install(ScopedBuf &fresh, size_t n, uint32_t max_label_, int mode_, uint64_t pass_)
+    {
+        fresh.install(bits);
+        max_label = n ? max_label_ : 0;
+        has_bits = n != 0;
+        mode = mode_;
+        pass = pass_;
+    }
+    void drop() // no label set
+    {
+        bits.release();
+        max_label = 0;
+        has_bits = false;
+        mode = -1;
+        pass = 0;
+    }
 };
 
 // Pinned, device-visible host memory that only ever grows (the small-batch entry point reads queries and writes
@@ -136,9 +180,9 @@ using namespace ivfhnsw_gpu_impl;
     X(ap_idx) X(ap_ids) X(ap_codes) X(ap_ncodes) X(ap_cnt) X(ap_own) X(ap_part) X(ap_status) X(ap_perm) X(ap_perm2) X(ap_hist) X(ap_tiles) /* append_ivf, add */ \
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
-    X(f_mask) X(f_bits) X(f_labels) X(f_count) /* set_filter: the pass mask, the kept label bitmap, staging */ \
-    X(fs_planes) X(fs_labels) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: fs_bits), staging of labels, counts and a host call's slot bytes */ \
-    X(bf_words) X(bf_rows) X(bf_own) X(bf_labels) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; staging */ \
+    X(f_mask) X(f_count) /* set_filter: the pass mask, the count's word (the kept label bitmap: filter.bits) */ \
+    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes */ \
+    X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
@@ -160,8 +204,9 @@ struct ivfhnsw_gpu {
 #define IVFHNSW_X(name) f(name);
         IVFHNSW_GPU_DEVBUFS(IVFHNSW_X)
 #undef IVFHNSW_X
-        for (DevBuf &b : fs_bits)
-            f(b);
+        f(filter.bits);
+        for (LabelSet &s : slots)
+            f(s.bits);
     }
     HostBuf p_in, p_out; // pinned: small batches of the host-pointer entry point
 
@@ -179,27 +224,17 @@ struct ivfhnsw_gpu {
     size_t base_d = 0;
     ivfhnsw_gpu *parent = nullptr;
 
-    // the label filter (capi_filter.cpp).  filter_mode -1 = none.  fmask is what the scans read: the
-    // handle's own f_mask, on a view the mask its parent held when follow_parent ran.  f_bits holds the label set over
-    // [0, f_max_label] (f_has_bits false = the empty set) so that an update can judge the rows of its new arrays.
-    int filter_mode = -1;
+    // the label filter (capi_filter.cpp).  filter.mode -1 = none.  fmask is what the scans read: the
+    // handle's own f_mask, on a view the mask its parent held when follow_parent ran (with the parent's mode and pass).
+    LabelSet filter;
     const uint32_t *fmask = nullptr;
-    bool f_has_bits = false;
-    uint32_t f_max_label = 0;
-    uint64_t f_pass = 0;
 
     // filter slots (capi_filter.cpp): up to IVFHNSW_FILTER_SLOTS label sets, named per query by the _slots
     // calls.  fs is what their scans read (its `slots` stays null: the bytes travel with the call): fs.nplanes planes of
-    // fs.stride words in the handle's own fs_planes, on a view the planes its parent held when follow_parent ran.  Per
-    // slot: mode (-1 = not set; its plane, where there is one, is zero), the label set over [0, fs_max_label] in fs_bits
-    // (fs_has_bits false = the empty set), the rows that pass.
+    // fs.stride words in the handle's own fs_planes, on a view the planes its parent held when follow_parent ran.  A slot
+    // that is not set has, where it has a plane, a zero one.
     SlotMask fs{nullptr, 0, 0, nullptr};
-    DevBuf fs_bits[IVFHNSW_FILTER_SLOTS];
-    int fs_mode[IVFHNSW_FILTER_SLOTS];
-    bool fs_has_bits[IVFHNSW_FILTER_SLOTS] = {};
-    uint32_t fs_max_label[IVFHNSW_FILTER_SLOTS] = {};
-    uint64_t fs_pass[IVFHNSW_FILTER_SLOTS] = {};
-    ivfhnsw_gpu() { std::fill(fs_mode, fs_mode + IVFHNSW_FILTER_SLOTS, -1); }
+    LabelSet slots[IVFHNSW_FILTER_SLOTS];
 
     // the base filter of the exact calls (capi_base_filter.cpp), on the handle that holds the store: a view
     // reads its parent's at the call.  bf_mode -1 = none.  bf_words: one pass bit per row; bf_rows (bf_has_rows): the
@@ -282,6 +317,32 @@ int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool n
 // h->t's pointers to the five list arrays and n_local follow the handle's buffers
 void point_at_lists(ivfhnsw_gpu *h, uint64_t n_local);
 
+// ---- capi_labels.cpp: what the calls that take a set of uint32 labels share
+// One device word as a kernel's answer: the word is set to `init` bytes, `launch(word)` puts its work on the handle's
+// stream, and the word comes back in *out.  Returns with the stream drained.
+int run_with_word(ivfhnsw_gpu *h, DevBuf &word, int init, const std::function<hipError_t(uint32_t *)> &launch, uint32_t *out);
+// "<who>: null labels" for n > 0 labels without a pointer and, of a call that takes a mode, one that is neither allow
+// nor deny
+int label_args_guard(size_t n, const uint32_t *labels, const char *who, const int *mode = nullptr);
+// Host labels [n] on their way to the device: copied into stage (grown here; n = 0: untouched) on the handle's stream,
+// and their maximum (0 for none) into *max_label where the caller wants it.
+int labels_from_host(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, DevBuf &stage, uint32_t *max_label);
+// The maximum of device labels [n] (0 for none), through `word` (grown to one word here).  n > 0: drains the stream.
+int labels_max_dev(ivfhnsw_gpu *h, DevBuf &word, size_t n, const uint32_t *d_labels, uint32_t *max_label);
+// the words of a bitmap over [0, max_label]
+inline size_t label_bitmap_words(uint32_t max_label) { return (size_t)max_label / 32 + 1; }
+// The bitmap of device labels [n] over [0, max_label] into bits (grown here), on the handle's stream.  n = 0, the empty
+// set, has no bitmap: bits is left alone.
+int labels_bitmap(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t max_label, DevBuf &bits);
+// The opening of the calls that set or clear a filter: on the handle that holds what the filter is marked over, not on
+// a view of it, the device bound and, with need_upload, that upload made ("<who> before upload_ivf" / "... upload_base").
+enum FilterKind { kIndexFilter, kBaseFilter };
+int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool need_upload);
+// what filter_info, filter_slot_info and base_filter_info answer (each pointer nullable): a set's mode and its passing
+// rows, or -1 and unset_pass where there is none
+int label_set_info(int set_mode, uint64_t pass, uint64_t unset_pass, uint64_t total, int *mode, uint64_t *rows_passing,
+                   uint64_t *rows_total);
+
 // ---- capi_filter.cpp
 // The pass mask of h's filter over ids [n_local] into mask (allocated here) and the rows that pass into *pass.  Returns
 // with the stream drained; the handle is not touched.
@@ -331,7 +392,7 @@ struct ListArrays {
         int rc;
         if (h->fs.nplanes && (rc = slots_mark_rows(h, ids.as<uint32_t>(), n_local, fplanes, fs_pass)))
             return rc;
-        if (h->filter_mode < 0)
+        if (h->filter.mode < 0)
             return IVFHNSW_OK;
         return filter_mark_rows(h, ids.as<uint32_t>(), n_local, fmask, &fpass);
     }
@@ -342,16 +403,17 @@ struct ListArrays {
     }
     void install(ivfhnsw_gpu *h, uint64_t n_local)
     {
-        if (h->filter_mode >= 0) {
+        if (h->filter.mode >= 0) {
             std::swap(h->f_mask, fmask);
             h->fmask = h->f_mask.as<uint32_t>();
-            h->f_pass = fpass;
+            h->filter.pass = fpass;
         }
         if (h->fs.nplanes) {
             std::swap(h->fs_planes, fplanes);
             h->fs.planes = h->fs_planes.as<uint32_t>();
             h->fs.stride = (uint32_t)slot_plane_stride(n_local);
-            std::copy(fs_pass, fs_pass + IVFHNSW_FILTER_SLOTS, h->fs_pass);
+            for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++)
+                h->slots[s].pass = fs_pass[s];
         }
         std::swap(h->goff, goff);
         std::swap(h->loff, loff);

@@ -78,11 +78,12 @@ static int recon_rows_to_host(ivfhnsw_gpu *h, size_t n, const int64_t *d_rows, i
     return IVFHNSW_OK;
 }
 
-// The words locate keeps in lc_scalar.
+// The words locate keeps in lc_scalar; the first is the word labels_max_dev answers through.
 struct LocateScalars {
     uint32_t max_label, pad;
     unsigned long long missing;
 };
+static_assert(offsetof(LocateScalars, max_label) == 0, "labels_max_dev writes the buffer's first word");
 
 // d_labels [n] -> d_rows [n], d_counts [n] (nullable), device pointers on the handle's stream; the requests without a row
 // are counted in lc_scalar's `missing`.  Synchronises once (the bitmap is sized by the largest label).
@@ -100,12 +101,8 @@ static int locate_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int64
     LocateScalars *sc = h->lc_scalar.as<LocateScalars>();
     uint32_t mx = 0;
     HIP_TRY(hipMemsetAsync(sc, 0, sizeof(LocateScalars), h->stream));
-    HIP_TRY(launch_remove_max(h->stream, d_labels, n, &sc->max_label));
-    HIP_TRY(hipMemcpyAsync(&mx, &sc->max_label, sizeof(mx), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if ((rc = h->lc_bits.ensure(((size_t)mx / 32 + 1) * sizeof(uint32_t))))
+    if ((rc = labels_max_dev(h, h->lc_scalar, n, d_labels, &mx)) || (rc = labels_bitmap(h, n, d_labels, mx, h->lc_bits)))
         return rc;
-    HIP_TRY(launch_remove_bits(h->stream, d_labels, n, mx, h->lc_bits.as<uint32_t>()));
     int key_bits = 1;
     while (key_bits < 32 && (mx >> key_bits))
         key_bits++;
@@ -141,7 +138,7 @@ int ivfhnsw_gpu_locate(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, int64_t
     if (!labels || !rows)
         return fail(IVFHNSW_ERR_INVALID, "locate: null labels or rows");
     if ((rc = h->lc_rows.ensure(n * sizeof(int64_t))) || (counts && (rc = h->lc_counts.ensure(n * sizeof(uint32_t)))) ||
-        (rc = stage_in(h, h->lc_labels, labels, n * sizeof(uint32_t))) ||
+        (rc = labels_from_host(h, n, labels, h->lc_labels, nullptr)) ||
         (rc = locate_core(h, n, h->lc_labels.as<uint32_t>(), h->lc_rows.as<int64_t>(), counts ? h->lc_counts.as<uint32_t>() : nullptr)) ||
         (rc = stage_out(h, rows, h->lc_rows, n * sizeof(int64_t))) ||
         (counts && (rc = stage_out(h, counts, h->lc_counts, n * sizeof(uint32_t)))))
@@ -206,7 +203,7 @@ int ivfhnsw_gpu_reconstruct(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, in
     if (!labels || !out)
         return fail(IVFHNSW_ERR_INVALID, "reconstruct: null labels or out");
     uint64_t miss = 0;
-    if ((rc = h->lc_rows.ensure(n * sizeof(int64_t))) || (rc = stage_in(h, h->lc_labels, labels, n * sizeof(uint32_t))) ||
+    if ((rc = h->lc_rows.ensure(n * sizeof(int64_t))) || (rc = labels_from_host(h, n, labels, h->lc_labels, nullptr)) ||
         (rc = locate_core(h, n, h->lc_labels.as<uint32_t>(), h->lc_rows.as<int64_t>(), nullptr)) || (rc = read_missing(h, &miss)) ||
         (rc = recon_rows_to_host(h, n, h->lc_rows.as<int64_t>(), space, out)))
         return rc;

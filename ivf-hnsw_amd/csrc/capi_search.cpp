@@ -222,7 +222,7 @@ static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params
 static bool early_tables_wanted(const ivfhnsw_gpu *h, const SearchArgs &a)
 {
     static const bool on = env_size("IVFHNSW_EARLY_LUT", 1) != 0;
-    if (!on || !plan_lut_shape(h) || h->filter_mode >= 0 || a.d_query_slots)
+    if (!on || !plan_lut_shape(h) || h->filter.mode >= 0 || a.d_query_slots)
         return false;
     const bool may_pipe = a.k == 1 && h->opt_scan_pipe != 0 &&
                           scan_pipe_supported(h->t, (int)a.p->nprobe, (int)a.nq, 1, h->n_local > 0, h->opt_scan_pipe == 1);
@@ -417,7 +417,7 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
                          // without a plane reads word 0 and ignores it -- and the bytes of this chunk's queries
         c.fmask = SlotMask{h->fs.nplanes ? h->fs.planes : h->w_totals.as<uint32_t>(), h->fs.stride, h->fs.nplanes, c.d_query_slots};
     else
-        c.fmask = h->filter_mode >= 0 ? h->fmask : nullptr;
+        c.fmask = h->filter.mode >= 0 ? h->fmask : nullptr;
     return IVFHNSW_OK;
 }
 

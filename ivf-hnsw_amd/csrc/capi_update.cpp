@@ -4,19 +4,7 @@
 // ---------------------------------------------------------------------------------------------------------------
 // what the three cores share
 
-// One device word as a kernel's answer: the word is set to `init` bytes, `launch(word)` puts its work on the handle's
-// stream, and the word comes back in *out.  Returns with the stream drained.
-template <class Launch> static int run_with_word(ivfhnsw_gpu *h, DevBuf &word, int init, Launch &&launch, uint32_t *out)
-{
-    int rc;
-    if ((rc = word.ensure(sizeof(uint32_t))))
-        return rc;
-    HIP_TRY(hipMemsetAsync(word.p, init, sizeof(uint32_t), h->stream));
-    HIP_TRY(launch(word.as<uint32_t>()));
-    HIP_TRY(hipMemcpyAsync(out, word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return IVFHNSW_OK;
-}
+// (run_with_word, one device word as a kernel's answer: capi_labels.cpp)
 
 // The tail of an update, behind the last launch that fills `fresh` (e = the launches' status): the stream is drained,
 // the handle's filter is judged over the new ids, and only then do the new arrays replace the old ones -- every error up
@@ -551,8 +539,7 @@ try {
     const bool grp = h->has_group;
     const size_t nsub = grp ? nc * (size_t)h->g.nsubc : 0;
     int rc;
-    if ((rc = h->rm_bits.ensure(((size_t)max_label / 32 + 1) * sizeof(uint32_t))) ||
-        (rc = h->rm_mask.ensure(remove_mask_words(ntiles, kRemoveTileRows) * sizeof(uint64_t))) ||
+    if ((rc = h->rm_mask.ensure(remove_mask_words(ntiles, kRemoveTileRows) * sizeof(uint64_t))) ||
         (rc = h->rm_keep.ensure((ntiles + 1) * sizeof(uint32_t))) || (rc = h->rm_rem.ensure(len * sizeof(uint32_t))) ||
         (rc = h->rm_part.ensure(append_scan_parts(std::max(len, ntiles + 1)) * sizeof(uint32_t))) ||
         (rc = h->rm_sizes.ensure(nsub * sizeof(uint32_t))))
@@ -560,7 +547,9 @@ try {
     uint32_t *keep = h->rm_keep.as<uint32_t>(), *rem = h->rm_rem.as<uint32_t>(), *part = h->rm_part.as<uint32_t>();
     unsigned long long *mask = h->rm_mask.as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(keep + ntiles, 0, sizeof(uint32_t), h->stream));
-    HIP_TRY(launch_remove_mark(h->stream, h->t, n_local, d_labels, n, max_label, h->rm_bits.as<uint32_t>(), mask, keep));
+    if ((rc = labels_bitmap(h, n, d_labels, max_label, h->rm_bits)))
+        return rc;
+    HIP_TRY(launch_remove_mark(h->stream, h->t, n_local, h->rm_bits.as<uint32_t>(), max_label, mask, keep));
     HIP_TRY(launch_remove_counts(h->stream, h->t, mask, grp ? h->g.sub_sizes : nullptr, h->rm_sizes.as<uint32_t>(),
                                  grp ? h->g.nsubc : 0, rem, rem_out));
     HIP_TRY(launch_scan_excl_u32(h->stream, rem, len, part));
@@ -592,8 +581,8 @@ int ivfhnsw_gpu_remove_ids(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, uin
     int rc = remove_state(h, "remove_ids");
     if (rc)
         return rc;
-    if (n && !labels)
-        return fail(IVFHNSW_ERR_INVALID, "remove_ids: null labels");
+    if ((rc = label_args_guard(n, labels, "remove_ids")))
+        return rc;
     if (n_removed)
         *n_removed = 0;
     if (removed_per_list)
@@ -601,12 +590,9 @@ int ivfhnsw_gpu_remove_ids(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, uin
     if (n == 0 || h->n_local == 0)
         return IVFHNSW_OK;
     uint32_t mx = 0;
-    for (size_t i = 0; i < n; i++)
-        mx = std::max(mx, labels[i]);
-    if ((rc = h->rm_labels.ensure(n * sizeof(uint32_t))) ||
-        (removed_per_list && (rc = h->rm_out.ensure((size_t)h->t.nc * sizeof(uint32_t)))))
+    if ((removed_per_list && (rc = h->rm_out.ensure((size_t)h->t.nc * sizeof(uint32_t)))) ||
+        (rc = labels_from_host(h, n, labels, h->rm_labels, &mx)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(h->rm_labels.p, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     uint64_t removed = 0;
     if ((rc = remove_core(h, n, h->rm_labels.as<uint32_t>(), mx, &removed, removed_per_list ? h->rm_out.as<uint32_t>() : nullptr)))
         return rc;
@@ -623,8 +609,8 @@ int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
     int rc = remove_state(h, "remove_ids_dev");
     if (rc)
         return rc;
-    if (n && !d_labels)
-        return fail(IVFHNSW_ERR_INVALID, "remove_ids_dev: null labels");
+    if ((rc = label_args_guard(n, d_labels, "remove_ids_dev")))
+        return rc;
     if (n_removed)
         *n_removed = 0;
     if (n == 0 || h->n_local == 0) {
@@ -635,8 +621,7 @@ int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
         return IVFHNSW_OK;
     }
     uint32_t mx = 0;
-    if ((rc = run_with_word(h, h->rm_status, 0, [&](uint32_t *out) { return launch_remove_max(h->stream, d_labels, n, out); },
-                            &mx)))
+    if ((rc = labels_max_dev(h, h->rm_status, n, d_labels, &mx)))
         return rc;
     uint64_t removed = 0;
     if ((rc = remove_core(h, n, d_labels, mx, &removed, d_removed_per_list)))

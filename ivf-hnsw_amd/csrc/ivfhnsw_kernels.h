@@ -396,20 +396,20 @@ hipError_t launch_update_offsets(hipStream_t s, const IvfTables &t, const uint32
 // exclusive scan of a [len] in place with the scan above; part: append_scan_parts(len) words
 hipError_t launch_scan_excl_u32(hipStream_t s, uint32_t *a, size_t len, uint32_t *part);
 // removal by label from an unsharded handle (kernels_remove.hip).  max: atomicMax of the labels into
-// *out.  mark: bits ((max_label / 32 + 1) words) = the label set, then mask [ceil(n_local / kRemoveTileRows) *
+// *out.  mark: from bits, the label set (launch_remove_bits below), mask [ceil(n_local / kRemoveTileRows) *
 // kRemoveTileRows / 64] (bit r = row r is removed) and keep [one per tile] = rows each tile keeps.  counts: rem [nc + 1]
 // (slot nc zero) = codes removed per list, also into rem_out when non-null; sizes != null (Grouping): sizes2 [nc * nsubc]
 // = the sub-group sizes after the removal.  compact, after rem and keep are scanned (rscan, kscan): nl.goff / nl.loff and the
 // surviving rows, in order, into the new arrays nl.
 constexpr int kRemoveTileRows = 2048;
 hipError_t launch_remove_max(hipStream_t s, const uint32_t *labels, size_t n, uint32_t *out);
-hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *labels, size_t n,
-                              uint32_t max_label, uint32_t *bits, unsigned long long *mask, uint32_t *keep);
+hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
+                              unsigned long long *mask, uint32_t *keep);
 hipError_t launch_remove_counts(hipStream_t s, const IvfTables &t, const unsigned long long *mask, const uint32_t *sizes,
                                 uint32_t *sizes2, int nsubc, uint32_t *rem, uint32_t *rem_out);
 hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
                                  const uint32_t *rscan, const uint32_t *kscan, const NewLists &nl);
-// the label bitmap alone, for a caller that keeps it (the search filter below): bits [max_label / 32 + 1 words] zeroed, then
+// the label bitmap of every call that takes a label set (capi_labels.cpp): bits [max_label / 32 + 1 words] zeroed, then
 // the bit of every label set
 hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits);
 // search filter (kernels_filter.hip): mask [ceil(n_local / 64)] words, bit r = row r passes: its id is in the

@@ -203,13 +203,11 @@ hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, u
     return hipGetLastError();
 }
 
-hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *labels, size_t n,
-                              uint32_t max_label, uint32_t *bits, unsigned long long *mask, uint32_t *keep)
+hipError_t launch_remove_mark(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
+                              unsigned long long *mask, uint32_t *keep)
 {
-    if (n == 0 || n_local == 0)
+    if (n_local == 0)
         return hipSuccess;
-    if (hipError_t e = launch_remove_bits(s, labels, n, max_label, bits); e != hipSuccess)
-        return e;
     hipLaunchKernelGGL(remove_mark_kernel, dim3(blocks_of(n_local, kRemoveTileRows)), dim3(256), 0, s, t.ids, n_local, bits,
                        max_label, mask, keep);
     return hipGetLastError();
