@@ -288,8 +288,8 @@ int ivfhnsw_gpu_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, u
  *   IVFHNSW_ERR_INVALID; set or clear before upload_ivf, on a view, on a handle with shard_world > 1 -> IVFHNSW_ERR_STATE;
  *   a _slots call on a sharded handle -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM; whatever the plain
  *   call refuses for the same arguments is refused with its status.
- * Not built: a slot AND the handle's filter; slots for search_reconstruct, search_sharded, sharded handles and the base
- *   filter of the exact calls; more than 32 slots. */
+ * Not built: a slot AND the handle's filter; slots for search_reconstruct, search_sharded, and sharded handles; more than
+ *   32 slots.  (The exact calls have slots of their own: "base filter slots" below.) */
 #define IVFHNSW_FILTER_SLOTS 32
 #define IVFHNSW_SLOT_NONE 0xff
 int ivfhnsw_gpu_set_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode);
@@ -705,6 +705,59 @@ int ivfhnsw_gpu_set_base_filter(ivfhnsw_gpu *h, size_t n, const uint32_t *labels
 int ivfhnsw_gpu_set_base_filter_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, int mode);
 int ivfhnsw_gpu_clear_base_filter(ivfhnsw_gpu *h);
 int ivfhnsw_gpu_base_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
+
+/* ---- base filter slots: a base filter PER QUERY of an exact call --------------------------------------
+ *
+ * The truth of a _slots search ("Filter slots" above).  Beside its one base filter the handle that holds the store holds up
+ * to IVFHNSW_FILTER_SLOTS (32) slots, each a set of uint32 ROW NUMBERS and a mode exactly as ivfhnsw_gpu_set_base_filter
+ * takes them (any value, labels >= n match nothing, repeats count once, an empty allow set passes nothing, an empty deny
+ * set everything).  A slot that was never set, or was cleared, passes nothing.  The _slots forms of both exact calls take
+ * one byte per query: query q with query_slots[q] == s gets, bit for bit, what the plain call returns on the same handle
+ * with set_base_filter(set of s, mode of s) installed -- exact_search: the original row numbers with the same distance
+ * bits, ascending by (distance, label), padded with FLT_MAX / -1 when fewer than k rows pass; the range search: results per
+ * query in ascending label, exact lims IN THE CALLER'S QUERY ORDER, held in the handle's exact-range buffers and read with
+ * ivfhnsw_gpu_exact_range_results[_dev].  With IVFHNSW_SLOT_NONE (0xff) the query gets what the plain call returns with
+ * no base filter.  query_slots == NULL is the plain call: same path, same kernels.
+ *   Slots and the handle's base filter are independent state: plain calls never read slots, and a _slots call on a store
+ * with a set_base_filter filter installed -> IVFHNSW_ERR_STATE (the two are not combined).
+ *   The work follows each query's own passing rows: the queries of a call are grouped by slot into strips of 32 on the
+ * device, every strip sweeps its own slot's rows in the form that slot is kept in (below), and one call takes at most
+ * three sweep launches per chunk whatever the bytes are.  A group's last strip is padded to 32 rows.
+ * ivfhnsw_gpu_set_base_filter_slot replaces the slot's earlier set; the new one is built beside the installed state and
+ *   swapped in, so any error leaves every slot as it was.  Synchronous on the handle's stream.  _dev: d_labels in device
+ *   memory (4-byte aligned).  ivfhnsw_gpu_clear_base_filter_slot: slot -1 = every slot; succeeds on a slot that is not set.
+ *   ivfhnsw_gpu_upload_base[_dev] with first == 0 or n == 0 drops every slot; a later chunk (first > 0) keeps them.
+ *   ivfhnsw_gpu_base_filter_slot_info: *mode = the slot's mode or -1, *rows_passing = rows of the store that pass it (0
+ *   for a slot that is not set), *rows_total = rows of the store; each nullable; a view reports its parent's.
+ * Query slot bytes: the host forms check them before anything is launched or written, a byte in 32..254 ->
+ *   IVFHNSW_ERR_INVALID.  The _dev forms read nothing back: any byte other than 0xff that names no installed slot passes
+ *   nothing.
+ * Views: set / clear on a view -> IVFHNSW_ERR_STATE.  A view reads its parent's slots at the call.
+ * Memory, all counted by ivfhnsw_gpu_memory_bytes: per installed slot its pass words, 4 * ceil(n / 32) bytes, and, when at
+ *   most n / 8 of its rows pass, the ascending list of the passing rows as well (4 bytes each); once per store a table of 33
+ *   entries of 16 bytes (allocated by the first set or the first _slots call) and the 8 bytes of the count's word the base
+ *   filter shares; per calling handle the strip plans of its last _slots call (about 132 bytes per 32 queries) and a host
+ *   form's staged bytes.  The option "exact_filter_form" applies per slot: 0 sweeps every slot behind its pass words, 1
+ *   keeps and sweeps the list of every slot set while it is in force; the form a slot is swept in is the HOLDER's choice
+ *   (a view's own option does not change it).  Results never depend on it.
+ * Errors: slot >= IVFHNSW_FILTER_SLOTS, an unknown mode, NULL labels with n > 0, a misaligned d_labels ->
+ *   IVFHNSW_ERR_INVALID; set or a _slots call before upload_base -> IVFHNSW_ERR_STATE; a failed allocation ->
+ *   IVFHNSW_ERR_NOMEM; limits and errors of the plain calls hold unchanged, and whatever they refuse is refused with
+ *   their status.
+ * Not built: a slot AND the handle's base filter; more than 32 slots; filtering the re-rank's candidates; one bitmap
+ *   shared between the index's filter slots and these. */
+int ivfhnsw_gpu_set_base_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode);
+int ivfhnsw_gpu_set_base_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, int mode);
+int ivfhnsw_gpu_clear_base_filter_slot(ivfhnsw_gpu *h, int slot); /* -1: every slot */
+int ivfhnsw_gpu_base_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
+int ivfhnsw_gpu_exact_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                                   const uint8_t *query_slots, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                       const uint8_t *d_query_slots, float *d_distances, int64_t *d_labels);
+int ivfhnsw_gpu_exact_range_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride,
+                                         const uint8_t *query_slots, float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
+                                             const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

@@ -49,6 +49,10 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_range_results_dev",
     "ivfhnsw_gpu_set_base_filter", "ivfhnsw_gpu_set_base_filter_dev", "ivfhnsw_gpu_clear_base_filter",
     "ivfhnsw_gpu_base_filter_info",
+    "ivfhnsw_gpu_set_base_filter_slot", "ivfhnsw_gpu_set_base_filter_slot_dev", "ivfhnsw_gpu_clear_base_filter_slot",
+    "ivfhnsw_gpu_base_filter_slot_info",
+    "ivfhnsw_gpu_exact_search_slots", "ivfhnsw_gpu_exact_search_slots_dev",
+    "ivfhnsw_gpu_exact_range_search_slots", "ivfhnsw_gpu_exact_range_search_slots_dev",
     "ivfhnsw_gpu_set_filter_slot", "ivfhnsw_gpu_set_filter_slot_dev", "ivfhnsw_gpu_clear_filter_slot",
     "ivfhnsw_gpu_filter_slot_info", "ivfhnsw_gpu_search_slots", "ivfhnsw_gpu_search_slots_dev",
     "ivfhnsw_gpu_range_search_slots", "ivfhnsw_gpu_range_search_slots_dev",
@@ -197,6 +201,17 @@ def lib():
         L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
         L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
         L.ivfhnsw_gpu_base_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_set_base_filter_slot.argtypes = [C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_set_base_filter_slot_dev.argtypes = L.ivfhnsw_gpu_set_base_filter_slot.argtypes
+        L.ivfhnsw_gpu_clear_base_filter_slot.argtypes = [C.c_void_p, C.c_int]
+        L.ivfhnsw_gpu_base_filter_slot_info.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                                        C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_exact_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_exact_search_slots_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float,
+                                                           C.c_void_p, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_exact_range_search_slots_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
@@ -1076,6 +1091,74 @@ class GpuIndex:
         m, a, b = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
         _check(lib().ivfhnsw_gpu_base_filter_info(self._h, C.byref(m), C.byref(a), C.byref(b)))
         return int(m.value), int(a.value), int(b.value)
+
+    # ---- base filter slots: a base filter per query (ivfhnsw_gpu_set_base_filter_slot) --------------
+    def set_base_filter_slot(self, slot, labels, deny=False):
+        """Base filter slot `slot` (0..FILTER_SLOTS-1) holds the row numbers `labels`, allow or deny as set_base_filter;
+        replaces the slot's earlier set.  The exact _slots calls name a slot per query."""
+        lab = _np(labels, np.uint32).ravel()
+        _check(lib().ivfhnsw_gpu_set_base_filter_slot(self._h, slot, lab.size, _ptr(lab) if lab.size else None,
+                                                      FILTER_DENY if deny else FILTER_ALLOW))
+
+    def set_base_filter_slot_dev(self, slot, n, d_labels, deny=False):
+        """The same on a device buffer (torch CUDA tensor or raw address)."""
+        _check(lib().ivfhnsw_gpu_set_base_filter_slot_dev(self._h, slot, n, _devptr(d_labels),
+                                                          FILTER_DENY if deny else FILTER_ALLOW))
+
+    def clear_base_filter_slot(self, slot=None):
+        """The slot passes nothing afterwards; None: every slot."""
+        _check(lib().ivfhnsw_gpu_clear_base_filter_slot(self._h, -1 if slot is None else slot))
+
+    def base_filter_slot_info(self, slot):
+        """(mode or -1, rows_passing, rows_total) of one base filter slot."""
+        m, a, b = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_filter_slot_info(self._h, slot, C.byref(m), C.byref(a), C.byref(b)))
+        return int(m.value), int(a.value), int(b.value)
+
+    @staticmethod
+    def _exact_queries(queries_u8):
+        a = np.asarray(queries_u8)
+        assert a.dtype == np.uint8 and a.ndim == 2, "queries_u8: a 2-D uint8 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 1 and (nq == 1 or a.strides[0] >= d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        return a, nq, (a.strides[0] if nq > 1 else d)
+
+    def exact_search_slots(self, queries_u8, k, query_slots):
+        """exact_search() with a base filter slot per query: query_slots [nq] bytes, each a slot or SLOT_NONE (no
+        filter); None is exact_search() itself (ivfhnsw_gpu_exact_search_slots)."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_slots(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                    _ptr(qs), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_slots_dev(self, nq, d_queries, row_stride, k, d_query_slots, d_distances, d_labels):
+        """The same on device buffers (d_query_slots: [nq] bytes in device memory, not checked on the host: a byte that
+        names no installed slot passes nothing), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_slots_dev(self._h, nq, _devptr(d_queries), row_stride, k,
+                                                        _devptr(d_query_slots), _devptr(d_distances), _devptr(d_labels)))
+
+    def exact_range_search_slots(self, queries_u8, radius, query_slots):
+        """exact_range_search() with a base filter slot per query; lims in the caller's query order."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_slots(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                          _ptr(qs), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_slots_dev(self, nq, d_queries, row_stride, d_query_slots, radius, d_lims):
+        """The same on device buffers; returns the number of results, which stay in the handle's memory."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_slots_dev(self._h, nq, _devptr(d_queries), row_stride,
+                                                              _devptr(d_query_slots), C.c_float(radius), _devptr(d_lims),
+                                                              C.byref(total)))
+        return int(total.value)
 
     # ---- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on):

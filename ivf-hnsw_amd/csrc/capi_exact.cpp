@@ -40,8 +40,28 @@ int exact_guard(ivfhnsw_gpu *h, const char *name, size_t nq, size_t row_stride, 
     return IVFHNSW_OK;
 }
 
+// A _slots call: the slot byte of every query (device memory once staged), the holder's table and the
+// forms its entries take.  d_slots null: the plain call.
+struct SlotsArg {
+    const uint8_t *d_slots = nullptr;
+    const StripCols *table = nullptr;
+    unsigned forms = 0;
+};
+
+// what a _slots entry point checks behind the plain call's guard, before anything is launched or written: no base filter
+// installed, and the bytes of a host form
+int exact_slots_guard(ivfhnsw_gpu *h, const char *who, size_t nq, const uint8_t *query_slots, bool on_device, SlotsArg *sl)
+{
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    int rc = base_slots_call(h, b, who, &sl->table, &sl->forms);
+    if (rc == IVFHNSW_OK && !on_device)
+        rc = slots_bytes_guard(nq, query_slots, who);
+    return rc;
+}
+
+// query_slots (null: the plain call): one slot byte per query, where the queries are
 int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k, float *distances,
-               int64_t *labels, bool on_device)
+               int64_t *labels, bool on_device, const uint8_t *query_slots = nullptr)
 {
     const ivfhnsw_gpu *b;
     auto k_check = [&] { return k < 1 || k > 100 ? fail(IVFHNSW_ERR_INVALID, "exact_search needs 1 <= k <= 100 (k %zu)", k) : 0; };
@@ -52,7 +72,12 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
     // under a base filter the columns of the sweep: every row behind the pass words, or the list of passing rows
     SweepCols cols;
     size_t n;
-    if ((rc = base_filter_cols(h, b, &cols, &n)))
+    SlotsArg sl;
+    if (query_slots) { // ... and with a slot per query (3.20) each strip's own, from the holder's table
+        if ((rc = exact_slots_guard(h, "exact_search_slots", nq, query_slots, on_device, &sl)))
+            return rc;
+        n = b->base_n;
+    } else if ((rc = base_filter_cols(h, b, &cols, &n)))
         return rc;
 
     const size_t first = std::min(nq, kExactChunk);
@@ -60,7 +85,12 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
     size_t chunk = kExactPartBytes / ((size_t)nsplit * k * sizeof(uint64_t));
     chunk = std::max<size_t>(128, std::min(kExactChunk, chunk / 128 * 128));
     chunk = std::min(chunk, nq);
-    if ((rc = h->ex_q.ensure(chunk * d)) || (rc = h->ex_part.ensure((size_t)nsplit * chunk * k * sizeof(uint64_t))))
+    // the rows a chunk is swept as: its queries, or under a strip plan the 32 rows of every strip it can have
+    const size_t bound = query_slots ? sweep_strip_bound(chunk) : 0;
+    const size_t rows = query_slots ? bound * 32 : chunk;
+    if ((rc = h->ex_q.ensure(rows * d)) || (rc = h->ex_part.ensure((size_t)nsplit * rows * k * sizeof(uint64_t))))
+        return rc;
+    if (query_slots && ((rc = h->bs_plan.ensure(sweep_strip_plan_bytes(bound))) || (!on_device && (rc = h->bs_qslots.ensure(chunk)))))
         return rc;
     if (!on_device && ((rc = h->ex_raw.ensure(chunk * d)) || (rc = h->ex_dist.ensure(chunk * k * sizeof(float))) ||
                        (rc = h->ex_lab.ensure(chunk * k * sizeof(int64_t)))))
@@ -74,12 +104,26 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
             src = h->ex_raw.as<uint8_t>();
             src_stride = d;
         }
-        // the queries in the store's byte order: an integer sum does not care which order, only that it is the same
-        HIP_TRY(launch_rerank_permute(h->stream, src, src_stride, h->ex_q.as<uint8_t>(), m, (int)d));
         float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
         int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
-        HIP_TRY(launch_exact_search(h->stream, h->ex_q.as<uint8_t>(), b->base_rows.as<uint8_t>(), m, n, (int)d, (int)k, nsplit,
-                                    h->ex_part.as<unsigned long long>(), od, ol, cols));
+        if (query_slots) {
+            const uint8_t *ds = query_slots + q0;
+            if (!on_device) {
+                HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, ds, m, hipMemcpyHostToDevice, h->stream));
+                ds = h->bs_qslots.as<uint8_t>();
+            }
+            // the chunk's strips, its queries gathered into them in the pass that permutes them, one sweep per form
+            StripPlan sp;
+            HIP_TRY(launch_strip_plan(h->stream, ds, m, sl.table, h->bs_plan.p, bound, &sp));
+            HIP_TRY(launch_rerank_permute_rows(h->stream, src, src_stride, h->ex_q.as<uint8_t>(), rows, (int)d, sp.strip_rows));
+            HIP_TRY(launch_exact_search_strips(h->stream, h->ex_q.as<uint8_t>(), b->base_rows.as<uint8_t>(), m, bound, (int)d, (int)k,
+                                               nsplit, h->ex_part.as<unsigned long long>(), od, ol, sp, sl.forms));
+        } else {
+            // the queries in the store's byte order: an integer sum does not care which order, only that it is the same
+            HIP_TRY(launch_rerank_permute(h->stream, src, src_stride, h->ex_q.as<uint8_t>(), m, (int)d));
+            HIP_TRY(launch_exact_search(h->stream, h->ex_q.as<uint8_t>(), b->base_rows.as<uint8_t>(), m, n, (int)d, (int)k, nsplit,
+                                        h->ex_part.as<unsigned long long>(), od, ol, cols));
+        }
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -148,30 +192,45 @@ int exact_range_map_shift(size_t nq, size_t n, size_t d, int nsplit, size_t *byt
 }
 
 // the sweep of one form over every chunk of the call's queries (h->ex_q: all of them, permuted)
+// The strip plans of a _slots call, kept for both passes: one per chunk, each of `bound` strips, chunk i's
+// gathered queries at row i * bound * 32 of h->ex_q.
+struct RangeStrips {
+    size_t bound = 0;
+    unsigned forms = 0;
+    std::vector<StripPlan> plans;
+};
+
 int exact_range_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const SweepCols &cols, size_t nx, bool fill, size_t nq, int thr,
-                     int nsplit, int map_shift, float *dist, int64_t *labels, size_t out_cap)
+                     int nsplit, int map_shift, float *dist, int64_t *labels, size_t out_cap, const RangeStrips *rs = nullptr)
 {
     const size_t d = b->base_d;
     StageScope sc(h, fill ? IVFHNSW_STAGE_SELECT : IVFHNSW_STAGE_SCAN); // accounted as range_search accounts its passes
-    for (size_t q0 = 0; q0 < nq; q0 += kExactChunk) // (kExactChunk % 128 == 0: a chunk starts a workgroup's strip)
-        HIP_TRY(launch_exact_range(h->stream, fill, h->ex_q.as<uint8_t>() + q0 * d, b->base_rows.as<uint8_t>(),
-                                   std::min(kExactChunk, nq - q0), q0, nx, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
-                                   h->xr_tot.as<unsigned long long>(), h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr,
-                                   map_shift, dist, labels, out_cap, cols));
+    uint32_t *map = h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr;
+    for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++) { // (kExactChunk % 128 == 0: a chunk starts a workgroup's strip)
+        if (rs)
+            HIP_TRY(launch_exact_range_strips(h->stream, fill, h->ex_q.as<uint8_t>() + i * rs->bound * 32 * d, b->base_rows.as<uint8_t>(),
+                                              rs->bound, q0, nx, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
+                                              h->xr_tot.as<unsigned long long>(), map, map_shift, dist, labels, out_cap, rs->plans[i],
+                                              rs->forms));
+        else
+            HIP_TRY(launch_exact_range(h->stream, fill, h->ex_q.as<uint8_t>() + q0 * d, b->base_rows.as<uint8_t>(),
+                                       std::min(kExactChunk, nq - q0), q0, nx, (int)d, thr, nsplit, h->xr_slices.as<uint32_t>(),
+                                       h->xr_tot.as<unsigned long long>(), map, map_shift, dist, labels, out_cap, cols));
+    }
     return IVFHNSW_OK;
 }
 
 // device pointers, the arguments checked (nq > 0)
 int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, float radius, uint64_t *d_lims,
-                    uint64_t *total)
+                    uint64_t *total, const SlotsArg &sl = {})
 {
     const ivfhnsw_gpu *b = h->parent ? h->parent : h;
     const size_t d = b->base_d;
     const int thr = exact_range_threshold(radius);
     int rc;
     SweepCols cols; // the columns of the sweep under a base filter, as in exact_impl
-    size_t n;
-    if ((rc = base_filter_cols(h, b, &cols, &n)))
+    size_t n = b->base_n;
+    if (!sl.d_slots && (rc = base_filter_cols(h, b, &cols, &n)))
         return rc;
     if (thr == 0 || n == 0) { // nothing is below it, or no row passes the base filter: no sweep
         HIP_TRY(hipMemsetAsync(d_lims, 0, (nq + 1) * sizeof(uint64_t), h->stream));
@@ -183,16 +242,40 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     }
     const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_splits_for(std::min(nq, kExactChunk), n, 1);
     const size_t len = nq * (size_t)nsplit + 1;
+    // under a strip plan the rows swept are those of every strip a chunk can have, chunk after chunk
+    RangeStrips strips;
+    const size_t nchunks = (nq + kExactChunk - 1) / kExactChunk;
+    if (sl.d_slots) {
+        strips.bound = sweep_strip_bound(std::min(nq, kExactChunk));
+        strips.forms = sl.forms;
+        strips.plans.resize(nchunks);
+    }
+    const size_t rows = sl.d_slots ? nchunks * strips.bound * 32 : nq;
+    const size_t plan_bytes = sweep_strip_plan_bytes(strips.bound);
     size_t map_bytes = 0;
-    const int map_shift = exact_range_map_shift(nq, n, d, nsplit, &map_bytes);
-    if ((rc = h->ex_q.ensure(nq * d)) || (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) ||
+    const int map_shift = exact_range_map_shift(rows, n, d, nsplit, &map_bytes);
+    if ((rc = h->ex_q.ensure(rows * d)) || (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) ||
         (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
-        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))))
+        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))) ||
+        (sl.d_slots && (rc = h->bs_plan.ensure(nchunks * plan_bytes))))
         return rc;
-    HIP_TRY(launch_rerank_permute(h->stream, d_queries, row_stride, h->ex_q.as<uint8_t>(), nq, (int)d));
+    if (sl.d_slots) {
+        // per chunk: its strips, and its queries gathered into them in the pass that permutes them
+        for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++) {
+            StripPlan &sp = strips.plans[i];
+            HIP_TRY(launch_strip_plan(h->stream, sl.d_slots + q0, std::min(kExactChunk, nq - q0), sl.table,
+                                      h->bs_plan.as<unsigned char>() + i * plan_bytes, strips.bound, &sp));
+            sp.map_strip0 = (uint32_t)(i * strips.bound);
+            HIP_TRY(launch_rerank_permute_rows(h->stream, d_queries + q0 * row_stride, row_stride,
+                                               h->ex_q.as<uint8_t>() + i * strips.bound * 32 * d, strips.bound * 32, (int)d, sp.strip_rows));
+        }
+    } else {
+        HIP_TRY(launch_rerank_permute(h->stream, d_queries, row_stride, h->ex_q.as<uint8_t>(), nq, (int)d));
+    }
+    const RangeStrips *rs = sl.d_slots ? &strips : nullptr;
     HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
-    if ((rc = exact_range_pass(h, b, cols, n, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0)))
+    if ((rc = exact_range_pass(h, b, cols, n, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0, rs)))
         return rc;
     HIP_TRY(launch_scan_excl_u32(h->stream, h->xr_slices.as<uint32_t>(), len, h->xr_part.as<uint32_t>()));
     // the one synchronisation between the passes: the host sizes the results from the count
@@ -214,7 +297,7 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
         HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
         if (tot)
             if (int e = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, grow ? nd.as<float>() : h->xr_dist.as<float>(),
-                                         grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), (size_t)tot))
+                                         grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), (size_t)tot, rs))
                 return e;
         HIP_TRY(hipStreamSynchronize(h->stream));
         return IVFHNSW_OK;
@@ -315,4 +398,61 @@ int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_que
                                  float *d_distances, int64_t *d_labels)
 {
     return exact_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true);
+}
+
+// ---- with a base filter slot per query; query_slots == NULL is the plain call
+
+int ivfhnsw_gpu_exact_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                                   const uint8_t *query_slots, float *distances, int64_t *labels)
+{
+    return exact_impl(h, nq, queries, row_stride, k, distances, labels, false, query_slots);
+}
+
+int ivfhnsw_gpu_exact_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                       const uint8_t *d_query_slots, float *d_distances, int64_t *d_labels)
+{
+    return exact_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true, d_query_slots);
+}
+
+int ivfhnsw_gpu_exact_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
+                                             const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    if (!d_query_slots)
+        return ivfhnsw_gpu_exact_range_search_dev(h, nq, d_queries, row_stride, radius, d_lims, total);
+    int rc = exact_range_guard(h, nq, d_queries, row_stride, radius, d_lims, total);
+    if (rc)
+        return rc;
+    SlotsArg sl;
+    if ((rc = exact_slots_guard(h, "exact_range_search_slots_dev", nq, d_query_slots, true, &sl)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, nullptr, d_lims, total);
+    sl.d_slots = d_query_slots;
+    return exact_range_dev(h, nq, d_queries, row_stride, radius, d_lims, total, sl);
+}
+
+int ivfhnsw_gpu_exact_range_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride,
+                                         const uint8_t *query_slots, float radius, uint64_t *lims, uint64_t *total)
+{
+    if (!query_slots)
+        return ivfhnsw_gpu_exact_range_search(h, nq, queries, row_stride, radius, lims, total);
+    int rc = exact_range_guard(h, nq, queries, row_stride, radius, lims, total);
+    if (rc)
+        return rc;
+    SlotsArg sl;
+    if ((rc = exact_slots_guard(h, "exact_range_search_slots", nq, query_slots, false, &sl)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, lims, nullptr, total);
+    const size_t d = (h->parent ? h->parent : h)->base_d;
+    if ((rc = h->ex_raw.ensure(nq * d)) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))) || (rc = h->bs_qslots.ensure(nq)))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d, queries, row_stride, d, nq, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, query_slots, nq, hipMemcpyHostToDevice, h->stream));
+    sl.d_slots = h->bs_qslots.as<uint8_t>();
+    if ((rc = exact_range_dev(h, nq, h->ex_raw.as<uint8_t>(), d, radius, h->xr_lims.as<uint64_t>(), total, sl)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
 }

@@ -304,7 +304,7 @@ int ivfhnsw_gpu_set_option(ivfhnsw_gpu *h, const char *key, long value)
         if (value < -1 || value > 1)
             return fail(IVFHNSW_ERR_INVALID, "set_option exact_filter_form: %ld outside -1..1", value);
         h->opt_exact_filter_form = (int)value;
-        return IVFHNSW_OK;
+        return base_slots_table_write(h, false); // the form of a base filter slot is the holder's choice
     }
     return fail(IVFHNSW_ERR_INVALID, "set_option: unknown key '%s'", key);
 }

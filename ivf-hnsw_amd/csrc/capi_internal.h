@@ -99,6 +99,18 @@ struct LabelSet {
     }
 };
 
+// A base filter slot (capi_base_filter.cpp): a set of row numbers of the store as set_base_filter keeps
+// its one -- pass words, and where few rows pass (has_rows) their ascending list.  mode -1 = not set.
+struct BaseSlot {
+    DevBuf words, rows;
+    int mode = -1;
+    uint64_t pass = 0;
+    bool has_rows = false;
+    BaseSlot() = default;
+    BaseSlot(const BaseSlot &) = delete;
+    BaseSlot &operator=(const BaseSlot &) = delete;
+};
+
 // Pinned, device-visible host memory that only ever grows (the small-batch entry point reads queries and writes
 // results through it: no staging copies on the latency path).
 struct HostBuf {
@@ -183,6 +195,7 @@ using namespace ivfhnsw_gpu_impl;
     X(f_mask) X(f_count) /* set_filter: the pass mask, the count's word (the kept label bitmap: filter.bits) */ \
     X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
+    X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans, a host call's slot bytes */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
@@ -207,6 +220,10 @@ struct ivfhnsw_gpu {
         f(filter.bits);
         for (LabelSet &s : slots)
             f(s.bits);
+        for (BaseSlot &s : bslots) {
+            f(s.words);
+            f(s.rows);
+        }
     }
     HostBuf p_in, p_out; // pinned: small batches of the host-pointer entry point
 
@@ -246,6 +263,12 @@ struct ivfhnsw_gpu {
     bool bf_has_rows = false;
     uint64_t bf_gen = 0, bf_own_gen = 0;
     const ivfhnsw_gpu *bf_own_of = nullptr;
+
+    // base filter slots (capi_base_filter.cpp), on the handle that holds the store, beside and independent
+    // of its one base filter: a view reads its parent's at the call.  bs_table: the kStripNone + 1 entries the strips of an
+    // exact _slots call read (form, words or rows, columns), rewritten whenever a slot or the option "exact_filter_form"
+    // changes; gone with the store, written again by the first call that needs it.
+    BaseSlot bslots[IVFHNSW_FILTER_SLOTS];
 
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
@@ -530,6 +553,14 @@ void base_filter_drop(ivfhnsw_gpu *h); // the handle holds no base filter afterw
 // The column map of an exact call of h on holder b's store and the columns it sweeps (*nx; 0 = nothing passes, no sweep):
 // Dense without a base filter, else the form sweep_filter_form picks.  May build h's own list (bf_own) on h's stream.
 int base_filter_cols(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, SweepCols *cols, size_t *nx);
+
+// Base filter slots.
+void base_slots_drop(ivfhnsw_gpu *h); // the handle holds no base filter slot afterwards (buffers and table released)
+// the holder's table from its slots, on its stream, which is drained; nothing to do on a handle without store or table
+int base_slots_table_write(ivfhnsw_gpu *h, bool create);
+// What an exact _slots call of h on holder b's store sweeps: the table (written here if the holder has none yet) and the
+// forms its entries take (bit kSweepCols*; Dense always: "none" may be named).  ERR_STATE with a base filter installed.
+int base_slots_call(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const char *who, const StripCols **table, unsigned *forms);
 
 // ---- capi_range.cpp
 void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)

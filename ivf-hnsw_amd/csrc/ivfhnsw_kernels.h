@@ -363,6 +363,23 @@ hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const
 hipError_t launch_pass_words(hipStream_t s, const uint32_t *bits, size_t bit_words, uint64_t n, int deny, uint32_t *words,
                              unsigned long long *count);
 hipError_t launch_pass_rows(hipStream_t s, const uint32_t *words, uint64_t n, uint32_t *cnt, uint32_t *part, uint32_t *rows);
+// Base filter slots: the exact sweeps with a row set per query, resolved per 32-row strip.
+// launch_strip_plan: the strip plan of a chunk of m queries from their slot bytes d_slots [m] and the holder's table
+// [kStripNone + 1] into plan (sweep_strip_plan_bytes(bound) bytes, bound >= sweep_strip_bound(m)); *sp = its views.
+// launch_rerank_permute_rows: launch_rerank_permute whose row r comes from row row_src[r] of src (negative: row 0).
+// launch_exact_search_strips / launch_exact_range_strips: the sweeps over the gathered queries Qp [bound * 32][d], one
+// launch per form in `forms` (bit kSweepCols*), results at the queries' own places; part: [nsplit][bound * 32][k].
+hipError_t launch_strip_plan(hipStream_t s, const uint8_t *d_slots, size_t m, const StripCols *table, void *plan, size_t bound,
+                             StripPlan *sp);
+hipError_t launch_rerank_permute_rows(hipStream_t s, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t count, int d,
+                                      const int32_t *row_src);
+hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t bound, int d, int k,
+                                      int nsplit, unsigned long long *part, float *dists, int64_t *labels, const StripPlan &sp,
+                                      unsigned forms);
+hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t bound, size_t q_off,
+                                     size_t nx, int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total,
+                                     uint32_t *map, int map_shift, float *dist, int64_t *labels, size_t out_cap,
+                                     const StripPlan &sp, unsigned forms);
 // appends to the inverted lists (kernels_append.hip) and to the sub-groups of Grouping lists (3.12); the
 // arithmetic and the workspace sizes are update_math.h's.  count: cnt[list_idx[i]] += 1 and, with sub_idx, sizes2[list][sub]
 // += 1 (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  tables: own[c] = old length +

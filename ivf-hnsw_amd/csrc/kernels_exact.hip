@@ -24,6 +24,10 @@
 // Under a base filter (ivfhnsw_gpu_set_base_filter) both kernels sweep through a column map, a template
 // parameter (sweep_steps.h): ColsDense is the sweep described above and the only one without a filter; ColsMasked skips
 // every tile of 32 rows in which no row passes; ColsIndirect sweeps the ascending list of passing rows instead of the store.
+//
+// With a base filter slot per query (ivfhnsw_gpu_exact_search_slots) the same two kernels run under
+// ColsStrips<map>: the queries are laid out in slot-uniform strips of 32 rows (the plan: kernels_exact_filter.hip), a wave
+// takes its strip's words or rows and column count from the holder's table (sweep_steps.h strip_open), one launch per form.
 #include "sweep_steps.h"
 
 #include <float.h>
@@ -50,9 +54,12 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int m = lane & 31, kk = lane >> 5;
-    const int r0 = blockIdx.x * (32 * WAVES) + wave * 32;
-    const size_t c_begin = (size_t)blockIdx.y * cols_per_split < nx ? (size_t)blockIdx.y * cols_per_split : nx;
-    const size_t c_end = c_begin + cols_per_split < nx ? c_begin + cols_per_split : nx;
+    // the wave's rows, map and columns: the call's, or under a strip plan its strip's
+    int r0 = blockIdx.x * (32 * WAVES) + wave * 32;
+    size_t c_begin, c_end;
+    typename CM::Base bcm;
+    if (!strip_open(cm, (int)gridDim.y, (int)blockIdx.y, nx, cols_per_split, r0, c_begin, c_end, bcm))
+        return;
     unsigned long long *buf = s_buf + (size_t)wave * 32 * CAP;
     uint32_t *cnt = s_cnt + wave * 32;
     int *thr_s = s_thr + wave * 32;
@@ -72,8 +79,8 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
 
     // The tiles of the split in turn -- under a column map the ones it visits: the prefetch goes to the next tile that will
     // be visited (ColsDense: c0 + 32, the loop as it was before there were column maps).
-    ColCursor<CM> cc;
-    cc.setup(cm, c_begin, c_end, (uint32_t)((c_end - c_begin + 31) >> 5), lane);
+    ColCursor<typename CM::Base> cc;
+    cc.setup(bcm, c_begin, c_end, (uint32_t)((c_end - c_begin + 31) >> 5), lane);
     size_t cn = cc.next_col(c_begin);
     if (cn < c_end) {
         cc.ids(cn);
@@ -156,6 +163,54 @@ template <class F> hipError_t by_col_map(const SweepCols &cols, F &&f)
     }
 }
 
+// ... and under a strip plan: one launch per form in `forms` (bit f = form f), each over the plan's strips
+// of that form
+template <class F> hipError_t by_strip_maps(const StripPlan &sp, unsigned forms, F &&f)
+{
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess && (forms >> kSweepColsDense & 1u))
+        e = f(ColsStrips<ColsDense>{sp});
+    if (e == hipSuccess && (forms >> kSweepColsMasked & 1u))
+        e = f(ColsStrips<ColsMasked>{sp});
+    if (e == hipSuccess && (forms >> kSweepColsIndirect & 1u))
+        e = f(ColsStrips<ColsIndirect>{sp});
+    return e;
+}
+
+// the merge under a strip plan, one wavefront per strip row: the row of a query goes to the query's place in the caller's
+// order, padding rows and strips beyond the plan's are dropped
+__global__ __launch_bounds__(64) void exact_merge_strips_kernel(const unsigned long long *__restrict__ part, int nsplit, int nrows,
+                                                                int k, float *__restrict__ dists, long long *__restrict__ labels,
+                                                                StripPlan sp)
+{
+    const uint32_t row = blockIdx.x;
+    if ((row >> 5) >= sp.hdr->lay.nstrips)
+        return;
+    const int q = sp.strip_rows[row];
+    if (q < 0)
+        return;
+    sweep_merge_row(
+        part, nsplit, nrows, k, (int)row, q,
+        [&](size_t o, unsigned long long key) {
+            labels[o] = (long long)(uint32_t)key;
+            dists[o] = (float)(uint32_t)(key >> 32);
+        },
+        [&](size_t o) { // fewer than k rows pass the query's slot
+            labels[o] = -1ll;
+            dists[o] = FLT_MAX;
+        });
+}
+
+// every result "nothing": what a query without a strip keeps
+__global__ __launch_bounds__(256) void exact_pad_kernel(float *__restrict__ dists, long long *__restrict__ labels, size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) {
+        labels[i] = -1ll;
+        dists[i] = FLT_MAX;
+    }
+}
+
 // Exact range search (ivfhnsw_gpu_exact_range_search): the sweep above with a fixed gate, dist < thr, in
 // two forms.  Nothing is selected, so there is no LDS at all: a lane keeps the counters of its 16 accumulator rows in
 // registers (the 32 lanes of a half hold the same values, a half's ballot is uniform across it), and the strip is always
@@ -183,12 +238,16 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
 {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int m = lane & 31, kk = lane >> 5;
-    const int r0 = blockIdx.x * 128 + wave * 32;
+    int r0 = blockIdx.x * 128 + wave * 32;
     if (r0 >= nq)
         return; // no barrier anywhere below
     const int nsplit = gridDim.y, split = blockIdx.y;
-    const size_t c_begin = (size_t)split * cols_per_split < nx ? (size_t)split * cols_per_split : nx;
-    const size_t c_end = c_begin + cols_per_split < nx ? c_begin + cols_per_split : nx;
+    // the wave's rows, map and columns: the call's, or under a strip plan its strip's, whose rows are
+    // queries of the call in any order (strip_row_query) -- slices and cursors are the QUERY's, the tile map the strip's
+    size_t c_begin, c_end;
+    typename CM::Base bcm;
+    if (!strip_open(cm, nsplit, split, nx, cols_per_split, r0, c_begin, c_end, bcm))
+        return;
     const uint32_t ntiles = (uint32_t)((c_end - c_begin + 31) >> 5);
 
     I8Strip<NS> st;
@@ -198,14 +257,18 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
     uint32_t cnt[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = mfma32_row(r, kk);
-        gate[r] = r0 + row < nq ? st.qn_r[r] - thr : INT_MAX;
-        cnt[r] = FILL && r0 + row < nq ? slices[(q_off + r0 + row) * nsplit + split] : 0u;
+        size_t qi;
+        const bool in = strip_row_query(cm, r0, mfma32_row(r, kk), nq, q_off, &qi);
+        gate[r] = in ? st.qn_r[r] - thr : INT_MAX;
+        cnt[r] = FILL && in ? slices[qi * nsplit + split] : 0u;
     }
 
-    uint32_t *mw = map ? map + ((((q_off + r0) >> 5) * nsplit + split) * (size_t)map_words) : nullptr;
-    ColCursor<CM> cc;
-    cc.setup(cm, c_begin, c_end, ntiles, lane);
+    size_t map_strip = (q_off + r0) >> 5;
+    if constexpr (CM::kStrips)
+        map_strip = cm.sp.map_strip0 + (size_t)(r0 >> 5);
+    uint32_t *mw = map ? map + ((map_strip * nsplit + split) * (size_t)map_words) : nullptr;
+    ColCursor<typename CM::Base> cc;
+    cc.setup(bcm, c_begin, c_end, ntiles, lane);
     // the first tile at or after t that is to be visited (ntiles: none): one with a passing row (cc.next) whose map bit is
     // set.  The map is read only at tiles with a passing row: those the count form visited, whose words it wrote.
     auto next_tile = [&](uint32_t t) -> uint32_t {
@@ -280,9 +343,9 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
         if (m == 0) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = mfma32_row(r, kk);
-                if (r0 + row < nq)
-                    slices[(q_off + r0 + row) * nsplit + split] = cnt[r];
+                size_t qi;
+                if (strip_row_query(cm, r0, mfma32_row(r, kk), nq, q_off, &qi))
+                    slices[qi * nsplit + split] = cnt[r];
                 sum += cnt[r];
             }
         }
@@ -319,6 +382,31 @@ hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const
     });
 }
 
+// ... under a strip plan: Qp [bound * 32][d] = the chunk's queries gathered by the plan, the chunk being
+// queries [q_off, ...) of the call; nx = the rows of the store (the most columns any strip has: the tile map's stride).
+// One launch per form in `forms`, each sized by the bound: waves beyond the plan's strips of the form exit at once.
+hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t bound, size_t q_off,
+                                     size_t nx, int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total,
+                                     uint32_t *map, int map_shift, float *dist, int64_t *labels, size_t out_cap,
+                                     const StripPlan &sp, unsigned forms)
+{
+    if (d < 16 || d > 256 || (d & 15) || thr < 0 || bound == 0 || bound > (0x7fffffffull >> 5) || nx >= 0xffffffffull || nsplit < 1 ||
+        nsplit > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.table || !sp.hdr || !sp.strip_slot || !sp.strip_rows)
+        return hipErrorInvalidValue;
+    const int words = sweep_map_words(nx, nsplit, map_shift);
+    const dim3 grid((unsigned)((bound + 3) / 4), (unsigned)nsplit);
+    long long *lab = reinterpret_cast<long long *>(labels);
+    return by_row_steps(d, [&](auto ns) {
+        return by_strip_maps(sp, forms, [&](auto cm) {
+            using CM = decltype(cm);
+            const auto kern = fill ? exact_range_kernel<decltype(ns)::value, true, CM> : exact_range_kernel<decltype(ns)::value, false, CM>;
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, Qp, X, (int)(bound * 32), (size_t)0, d, thr, (size_t)0, q_off, slices, total,
+                               map, map_shift, words, dist, lab, out_cap, cm);
+            return hipGetLastError();
+        });
+    });
+}
+
 // Qp: [nq][d] queries in the store's byte order (launch_rerank_permute); part: [nsplit][nq][k] u64 workspace
 hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t nx, int d, int k,
                                int nsplit, unsigned long long *part, float *dists, int64_t *labels, const SweepCols &cols)
@@ -343,6 +431,36 @@ hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *
         return e;
     hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)nq), dim3(64), 0, s, part, nsplit, (int)nq, k, dists,
                        reinterpret_cast<long long *>(labels));
+    return hipGetLastError();
+}
+
+// ... under a strip plan: Qp [bound * 32][d] = the chunk's nq queries gathered by the plan, part
+// [nsplit][bound * 32][k]; results in the caller's order, FLT_MAX / -1 for a query without a strip
+hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t bound, int d, int k,
+                                      int nsplit, unsigned long long *part, float *dists, int64_t *labels, const StripPlan &sp,
+                                      unsigned forms)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || bound == 0 || bound > (0x7fffffffull >> 5) || nsplit < 1 || nsplit > 64 ||
+        !sp.table || !sp.hdr || !sp.strip_slot || !sp.strip_rows)
+        return hipErrorInvalidValue;
+    const int rows = (int)(bound * 32);
+    long long *lab = reinterpret_cast<long long *>(labels);
+    hipLaunchKernelGGL(exact_pad_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, s, dists, lab, nq * (size_t)k);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    const hipError_t e = by_row_steps(d, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        return by_strip_maps(sp, forms, [&](auto cm) {
+            return k <= 16   ? launch_exact_t<NS, 48, 4>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm)
+                   : k <= 32 ? launch_exact_t<NS, 64, 4>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm)
+                             : launch_exact_t<NS, 136, 2>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm);
+        });
+    });
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(exact_merge_strips_kernel, dim3((unsigned)rows), dim3(64), 0, s, part, nsplit, rows, k, dists, lab, sp);
     return hipGetLastError();
 }
 

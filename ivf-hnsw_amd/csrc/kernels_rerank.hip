@@ -23,8 +23,11 @@ constexpr unsigned long long RR_EMPTY = ~0ull; // sorts after every real key (no
 
 // ---- upload: rows in file order -> the store's per-quad layout --------------------------------------------------------
 // One dword of the stored row per thread: stored byte p of a row (lane t = p / (d/4), i = p % (d/4)) holds dim 8(i/2)+2t+(i%2).
+// GATHER: row r of dst is row row_src[r] of src (a negative entry: row 0, a row nobody reads the result of) -- the
+// queries of an exact call laid out by its strip plan in the pass that permutes them.
+template <bool GATHER>
 __global__ void rerank_permute_kernel(const uint8_t *__restrict__ src, size_t src_stride, uint8_t *__restrict__ dst,
-                                      size_t count, int d)
+                                      size_t count, int d, const int32_t *__restrict__ row_src)
 {
     const int S = d >> 2;       // bytes of one lane's slice
     const int wpr = d >> 2;     // dwords per row
@@ -33,7 +36,10 @@ __global__ void rerank_permute_kernel(const uint8_t *__restrict__ src, size_t sr
         const size_t r = w / wpr;
         const int p = (int)(w - r * wpr) * 4;
         const int t = p / S, i = p - t * S; // i even, and i, i+1, i+2, i+3 lie in the same slice (S % 4 == 0)
-        const uint8_t *row = src + r * src_stride;
+        size_t rs = r;
+        if constexpr (GATHER)
+            rs = (size_t)max(row_src[r], 0);
+        const uint8_t *row = src + rs * src_stride;
         const int j = i >> 1;
         const uint32_t b0 = row[8 * j + 2 * t], b1 = row[8 * j + 2 * t + 1];
         const uint32_t b2 = row[8 * (j + 1) + 2 * t], b3 = row[8 * (j + 1) + 2 * t + 1];
@@ -47,7 +53,18 @@ hipError_t launch_rerank_permute(hipStream_t s, const uint8_t *src, size_t src_s
         return hipSuccess;
     const size_t words = count * (size_t)(d / 4);
     const unsigned grid = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 64);
-    hipLaunchKernelGGL(rerank_permute_kernel, dim3(grid), dim3(256), 0, s, src, src_stride, dst, count, d);
+    hipLaunchKernelGGL(rerank_permute_kernel<false>, dim3(grid), dim3(256), 0, s, src, src_stride, dst, count, d, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_rerank_permute_rows(hipStream_t s, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t count, int d,
+                                      const int32_t *row_src)
+{
+    if (count == 0)
+        return hipSuccess;
+    const size_t words = count * (size_t)(d / 4);
+    const unsigned grid = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 64);
+    hipLaunchKernelGGL(rerank_permute_kernel<true>, dim3(grid), dim3(256), 0, s, src, src_stride, dst, count, d, row_src);
     return hipGetLastError();
 }
 

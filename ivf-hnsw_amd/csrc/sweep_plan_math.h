@@ -9,11 +9,18 @@
 
 #include "scan_dispatch.h"
 
+// the functions a sweep kernel calls as well (the split cut, the strip layout): the same text for both compilers
+#ifdef __HIPCC__
+#define SWEEP_HD __host__ __device__
+#else
+#define SWEEP_HD
+#endif
+
 namespace ivfhnsw_gpu_impl {
 
 // Columns per split: equal shares rounded up to the 32 columns of a tile, never none (an empty store still gets a
 // split, whose kernels find c_begin >= c_end and read nothing).
-inline size_t sweep_cols_per_split(size_t nx, int nsplit)
+SWEEP_HD inline size_t sweep_cols_per_split(size_t nx, int nsplit)
 {
     size_t cps = (nx + nsplit - 1) / nsplit;
     cps = (cps + 31) & ~(size_t)31;
@@ -71,6 +78,78 @@ inline int sweep_filter_form(size_t npass, size_t n, int opt)
         return kSweepColsIndirect;
     return sweep_pass_list_kept(npass, n) ? kSweepColsIndirect : kSweepColsMasked;
 }
+
+// ---- base filter slots: the exact sweeps with a row set per query
+// The columns [*c_begin, *c_end) of split `split` of nsplit over nx columns: what the sweep kernels compute from
+// cols_per_split, as one function, because under a strip plan every strip cuts ITS OWN nx (an Indirect slot's columns are
+// its list).  The cuts tile [0, nx) in whole tiles of 32; a split beyond the columns is empty at nx.
+SWEEP_HD inline void sweep_split_cut(size_t nx, int nsplit, int split, size_t *c_begin, size_t *c_end)
+{
+    const size_t cps = sweep_cols_per_split(nx, nsplit);
+    *c_begin = (size_t)split * cps < nx ? (size_t)split * cps : nx;
+    *c_end = *c_begin + cps < nx ? *c_begin + cps : nx;
+}
+
+// What a strip sweeps, one entry per slot and one for "none" (kStripNone): the form, its words or rows, its columns.
+// kSweepColsNothing: the slot is not set, or no row passes it -- its queries get no strip.
+enum { kSweepColsNothing = 3 };
+constexpr int kStripSlots = 32;               // = IVFHNSW_FILTER_SLOTS
+constexpr int kStripNone = kStripSlots;       // the bucket and table entry of IVFHNSW_SLOT_NONE
+constexpr int kStripInvalid = kStripSlots + 1; // the bucket of a byte that names nothing
+constexpr int kStripBuckets = kStripSlots + 2;
+struct StripCols {
+    const uint32_t *data;
+    uint32_t nx, form;
+};
+
+SWEEP_HD inline int sweep_strip_bucket(uint8_t byte) { return byte < kStripSlots ? byte : byte == 0xff ? kStripNone : kStripInvalid; }
+
+// Strips of 32 queries, each of one bucket: at most this many for m queries.  Sum over the 33 buckets that get strips of
+// ceil(c / 32) <= sum of floor(c / 32) + 33 <= m / 32 + 33.
+SWEEP_HD inline size_t sweep_strip_bound(size_t m) { return m / 32 + 33; }
+
+// The strips of a chunk from its counts per bucket.  Ordered by form -- Dense, Masked, Indirect -- so that the sweep of a
+// form takes the contiguous range [range[form][0], range[form][1]); inside a form by bucket.  first[b]: the first strip of
+// bucket b, ~0 where it gets none (no query, the invalid bucket, a form of kSweepColsNothing).
+struct StripLayout {
+    uint32_t first[kStripBuckets];
+    uint32_t range[3][2];
+    uint32_t nstrips;
+};
+SWEEP_HD inline void sweep_strip_layout(const uint32_t *counts, const uint32_t *forms, StripLayout *out)
+{
+    uint32_t s = 0;
+    for (int b = 0; b < kStripBuckets; b++)
+        out->first[b] = ~0u;
+    for (uint32_t f = 0; f < 3; f++) {
+        out->range[f][0] = s;
+        for (int b = 0; b <= kStripNone; b++)
+            if (forms[b] == f && counts[b]) {
+                out->first[b] = s;
+                s += (counts[b] + 31) / 32;
+            }
+        out->range[f][1] = s;
+    }
+    out->nstrips = s;
+}
+
+// The strip plan of one chunk in device memory, as the kernels take it.  hdr: counts per bucket, the cursors the scatter
+// advances, the layout.  strip_slot [bound]: the table entry of every strip.  strip_rows [bound * 32]: per strip row the
+// chunk's query it holds, -1 = padding.  map_strip0: the chunk's first strip in the call's tile map (range search).
+struct StripHdr {
+    uint32_t counts[kStripBuckets], cursor[kStripBuckets];
+    StripLayout lay;
+};
+struct StripPlan {
+    const StripCols *table = nullptr;
+    const StripHdr *hdr = nullptr;
+    const uint8_t *strip_slot = nullptr;
+    const int32_t *strip_rows = nullptr;
+    uint32_t map_strip0 = 0;
+};
+// bytes of a chunk's plan of `bound` strips: header, rows, slots (each part 16-byte aligned)
+inline size_t sweep_strip_hdr_bytes() { return (sizeof(StripHdr) + 15) & ~(size_t)15; }
+inline size_t sweep_strip_plan_bytes(size_t bound) { return sweep_strip_hdr_bytes() + bound * 32 * sizeof(int32_t) + ((bound + 15) & ~(size_t)15); }
 
 // f(int_c<NS>()) for NS = ceil(d / 32) = 1 .. 8, the steps of 32 bytes a row of the uint8 store is read in (d <= 256)
 template <class F> auto by_row_steps(int d, F &&f)

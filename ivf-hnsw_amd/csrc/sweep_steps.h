@@ -1,7 +1,7 @@
 // The steps the brute-force MFMA sweeps share, one copy each: the C/D row map, the selection of a row's k
 // smallest keys through its LDS buffer (knn_mfma_kernel, exact_mfma_kernel), the int8 strip that reads the uint8 store
 // (exact_mfma_kernel, exact_range_kernel), the column maps those two sweep under when the store has a base filter
-// (ColsDense / ColsMasked / ColsIndirect, ColCursor) and the merge of the splits' partial tables.  Control flow -- which tile comes
+// (ColsDense / ColsMasked / ColsIndirect, ColCursor; per 32-row strip under base filter slots: ColsStrips, strip_open) and the merge of the splits' partial tables.  Control flow -- which tile comes
 // next, what a tile without a candidate costs, what is done with a distance that passes -- stays in the kernels.  Host
 // arithmetic (columns per split, split count): sweep_plan_math.h.
 #pragma once
@@ -221,17 +221,74 @@ template <int NS> struct I8Strip {
 //                 whose word is zero is neither fetched nor multiplied, in any other a lane counts only if its bit is set.
 //   ColsIndirect  the sweep runs over the columns [0, npass) of rows[], the passing row numbers ascending: column c is
 //                 row rows[c], which is also the label.  Ascending, so column order is still label order.
+// Under a strip plan (base filter slots) the three take their words or rows and their nx per 32-row strip
+// from the strip's table entry instead of the kernel's arguments: ColsStrips<map>, below.
 struct ColsDense {
-    static constexpr bool kMasked = false, kIndirect = false;
+    static constexpr bool kMasked = false, kIndirect = false, kStrips = false;
+    using Base = ColsDense;
+    __device__ __forceinline__ void take(const uint32_t *) {}
 };
 struct ColsMasked {
-    static constexpr bool kMasked = true, kIndirect = false;
+    static constexpr bool kMasked = true, kIndirect = false, kStrips = false;
+    using Base = ColsMasked;
     const uint32_t *words;
+    __device__ __forceinline__ void take(const uint32_t *data) { words = data; }
 };
 struct ColsIndirect {
-    static constexpr bool kMasked = false, kIndirect = true;
+    static constexpr bool kMasked = false, kIndirect = true, kStrips = false;
+    using Base = ColsIndirect;
     const uint32_t *rows;
+    __device__ __forceinline__ void take(const uint32_t *data) { rows = data; }
 };
+
+// A column map per 32-row strip.  The launch of form B covers the strips [range[B][0], range[B][1]) of the chunk's plan
+// (sweep_plan_math.h StripPlan): the wave whose strip of the launch is i owns strip range[B][0] + i, reads that strip's
+// table entry once -- everything in it is wave-uniform -- and sweeps the entry's columns under B.  The rows of the strip
+// are rows [32 strip, + 32) of the gathered queries; strip_rows says which of the call's queries each is.
+template <class B> struct ColsStrips {
+    static constexpr bool kMasked = B::kMasked, kIndirect = B::kIndirect, kStrips = true;
+    using Base = B;
+    StripPlan sp;
+};
+
+// What the wave whose first row is r0 sweeps in split `split` of nsplit: the map, the first row and the columns
+// [c_begin, c_end).  Without strips they are the kernel's own (cps = its columns per split); with strips r0 counts the
+// launch's strips and everything comes from the strip's table entry -- false: the launch has no such strip, the wave exits
+// (no barrier anywhere in these kernels).
+template <class CM>
+__device__ __forceinline__ bool strip_open(const CM &cm, int nsplit, int split, size_t nx, size_t cps, int &r0, size_t &c_begin,
+                                           size_t &c_end, typename CM::Base &base)
+{
+    if constexpr (!CM::kStrips) {
+        base = cm;
+        c_begin = (size_t)split * cps < nx ? (size_t)split * cps : nx;
+        c_end = c_begin + cps < nx ? c_begin + cps : nx;
+        return true;
+    } else {
+        constexpr int f = CM::kMasked ? kSweepColsMasked : CM::kIndirect ? kSweepColsIndirect : kSweepColsDense;
+        const uint32_t strip = __builtin_amdgcn_readfirstlane(cm.sp.hdr->lay.range[f][0] + (uint32_t)(r0 >> 5));
+        if (strip >= cm.sp.hdr->lay.range[f][1])
+            return false;
+        const StripCols e = cm.sp.table[cm.sp.strip_slot[strip]];
+        base.take(e.data);
+        sweep_split_cut(e.nx, nsplit, split, &c_begin, &c_end);
+        r0 = (int)(strip << 5);
+        return true;
+    }
+}
+// Is row `row` of the wave's strip a query (not: beyond nq; a padding row), and *qi = which of the call's, the chunk being
+// queries [q_off, ...) of the call
+template <class CM> __device__ __forceinline__ bool strip_row_query(const CM &cm, int r0, int row, int nq, size_t q_off, size_t *qi)
+{
+    if constexpr (CM::kStrips) {
+        const int q = cm.sp.strip_rows[r0 + row];
+        *qi = q_off + (size_t)max(q, 0);
+        return q >= 0;
+    } else {
+        *qi = q_off + r0 + row;
+        return r0 + row < nq;
+    }
+}
 
 // A wave's place in its split's columns [c_begin, c_end) under a column map.  Everything below is wave-uniform except
 // the row numbers; the members a map does not use are never live.
@@ -343,11 +400,13 @@ template <class CM> struct ColCursor {
 // The merge of a split call, one wavefront per query: the k smallest of the splits' sorted partial tables part
 // [nsplit][nq][k] (keys distinct: the low words differ).  A key's rank is the number of keys below it, summed over the
 // tables; put(slot, key) stores a result, pad(slot) fills a slot nothing reached.
+// sweep_merge_row: the same for the tables' row q whose results are the caller's row q_out (a strip plan's rows are not in
+// the caller's order).
 template <class Put, class Pad>
-__device__ __forceinline__ void sweep_merge(const unsigned long long *__restrict__ part, int nsplit, int nq, int k, Put put,
-                                            Pad pad)
+__device__ __forceinline__ void sweep_merge_row(const unsigned long long *__restrict__ part, int nsplit, int nq, int k, int q,
+                                                int q_out, Put put, Pad pad)
 {
-    const int q = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     const int total = nsplit * k;
     int found = 0;
     for (int i = lane; i < total; i += 64) {
@@ -371,14 +430,20 @@ __device__ __forceinline__ void sweep_merge(const unsigned long long *__restrict
             rank += lo;
         }
         if (rank < k)
-            put((size_t)q * k + rank, key);
+            put((size_t)q_out * k + rank, key);
     }
     // slots nothing reached: fewer than k candidates exist
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1)
         found += __shfl_xor(found, o);
     for (int i = min(found, k) + lane; i < k; i += 64)
-        pad((size_t)q * k + i);
+        pad((size_t)q_out * k + i);
+}
+template <class Put, class Pad>
+__device__ __forceinline__ void sweep_merge(const unsigned long long *__restrict__ part, int nsplit, int nq, int k, Put put,
+                                            Pad pad)
+{
+    sweep_merge_row(part, nsplit, nq, k, (int)blockIdx.x, (int)blockIdx.x, put, pad);
 }
 
 } // namespace ivfhnsw_gpu_impl

@@ -17,11 +17,17 @@
      only), k = 1 and k = 100, in the form the rule picks -- at 1/8 and 1/32 in both forms ("exact_filter_form" 0 = pass
      words, 1 = list of passing rows) -- each beside the unfiltered call of the same run, and the time of
      set_base_filter_dev itself.
+  5. With --filter-slots, on both stores, base filter slots (ivfhnsw_gpu_exact_search_slots_dev): 32 slots
+     of a random 1/32 of the rows each, the queries spread over the 32 slots and NONE.  Timed alternating in one run:
+     (a) one exact_search_slots_dev call, (b) the loop that answers the same batch without slots -- per slot
+     set_base_filter_dev then exact_search_dev on that slot's queries, NONE's unfiltered -- with and without the installs,
+     (c) the plain unfiltered call on the whole batch; k = 1 and k = 100; and the range form against its per-slot loop.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
-                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--dense-nq 512]
+                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots]
+                                   [--dense-nq 512]
                                    [--out result.json]"""
 import argparse
 import json
@@ -94,6 +100,7 @@ def main():
     ap.add_argument("--no-knn", action="store_true", help="skip the float knn comparison on the small store")
     ap.add_argument("--no-range", action="store_true", help="skip the exact range search legs")
     ap.add_argument("--filter", action="store_true", help="add the base-filter legs (DESIGN.md 3.18)")
+    ap.add_argument("--filter-slots", action="store_true", help="add the base-filter-slot legs (DESIGN.md 3.20)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -204,12 +211,85 @@ def main():
             del labels
         g.clear_base_filter()
 
+    def slots_legs(n, name, d10):
+        """One _slots call against the per-slot loop of single-filter calls and the plain call, alternating."""
+        nslots, none_share = 32, 33  # queries cycle over the 32 slots and NONE: 1/33 of them unfiltered
+        sets = [random_rows(n, 1.0 / 32, 5000 + s) for s in range(nslots)]
+        qs = (torch.arange(nq, device=dev) % none_share).to(torch.uint8)
+        qs[qs == nslots] = 0xff
+        perm = torch.randperm(nq, device=dev, generator=torch.Generator(device=dev).manual_seed(9))
+        qs = qs[perm].contiguous()
+        groups = [(s, (qs == (0xff if s == nslots else s)).nonzero().flatten()) for s in range(nslots + 1)]
+        sub = [(s, q[idx].contiguous(), idx) for s, idx in groups]
+        for s in range(nslots):
+            g.set_base_filter_slot_dev(s, sets[s].numel(), sets[s])
+        torch.cuda.synchronize(dev)
+        radius = float(d10.median())
+
+        def loop(k, od, ol, installs):
+            """the parent commit's way; installs False: only the searches are timed"""
+            t = 0.0
+            for s, qsub, idx in sub:
+                t0 = time.perf_counter()
+                if s == nslots:
+                    g.clear_base_filter()
+                else:
+                    g.set_base_filter_dev(sets[s].numel(), sets[s])
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                if k:
+                    g.exact_search_dev(qsub.shape[0], qsub, d, k, od[:qsub.shape[0]], ol[:qsub.shape[0]])
+                else:
+                    g.exact_range_search_dev(qsub.shape[0], qsub, d, radius, lims)
+                torch.cuda.synchronize(dev)
+                t += time.perf_counter() - (t0 if installs else t1)
+            g.clear_base_filter()
+            return t
+
+        for k in (1, 100, 0):  # 0: the range form
+            od = torch.empty((nq, max(k, 1)), dtype=torch.float32, device=dev)
+            ol = torch.empty((nq, max(k, 1)), dtype=torch.int64, device=dev)
+            ta, tb, tbi, tc = [], [], [], []
+            for rep in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                if k:
+                    g.exact_search_slots_dev(nq, q, d, k, qs, od, ol)
+                else:
+                    g.exact_range_search_slots_dev(nq, q, d, qs, radius, lims)
+                torch.cuda.synchronize(dev)
+                a = time.perf_counter() - t0
+                full = loop(k, od, ol, True)
+                only = loop(k, od, ol, False)
+                t0 = time.perf_counter()
+                if k:
+                    g.exact_search_dev(nq, q, d, k, od, ol)
+                else:
+                    g.exact_range_search_dev(nq, q, d, radius, lims)
+                torch.cuda.synchronize(dev)
+                c = time.perf_counter() - t0
+                log("[exact_bench] %s slots k=%d rep %d: slots call %.4f s, loop %.4f s (searches alone %.4f s), plain %.4f s"
+                    % (name, k, rep, a, full, only, c))
+                if rep >= args.warmup:
+                    ta.append(a), tbi.append(full), tb.append(only), tc.append(c)
+            ma, mbi, mb, mc = (statistics.median(x) for x in (ta, tbi, tb, tc))
+            r = {"what": "exact_search_slots_dev" if k else "exact_range_search_slots_dev", "rows": n, "d": d, "nq": nq,
+                 "k": k if k else None, "radius_value": None if k else radius, "slots": nslots, "fraction": "1/32",
+                 "unfiltered_share": "1/%d" % none_share, "slots_call_s": round(ma, 5), "loop_with_installs_s": round(mbi, 5),
+                 "loop_searches_only_s": round(mb, 5), "plain_unfiltered_s": round(mc, 5),
+                 "loop_with_installs_over_slots": round(mbi / ma, 3), "loop_searches_only_over_slots": round(mb / ma, 3),
+                 "slots_over_plain": round(ma / mc, 4), "reps_slots": [round(x, 5) for x in ta]}
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+        g.clear_base_filter_slot()
+
     def yardstick_and_range(n, dense_radius=None, fractions=(1, 2, 8, 32, 1024)):
         name = "%d rows" % n
         r1, _, _ = exact(n, 1, name)
         r100, _, od100 = exact(n, 100, name)
         if args.filter:
             filter_legs(n, name, {1: r1["seconds"], 100: r100["seconds"]}, fractions)
+        if args.filter_slots:
+            slots_legs(n, name, od100[:, 9])
         if not args.no_range:
             range_legs(n, name, r1["seconds"], od100[:, 9], od100[:, 99], dense_radius)
 

@@ -7,7 +7,10 @@ fractions 1, 1/2, 1/8 and 1/32: the same random allow set is installed as the in
 the exact search returns the true nearest allowed rows).  Reported per fraction and per (nprobe, max_codes, efSearch)
 setting: Recall@1 = share of queries whose true nearest allowed row is the IVF search's first result, and Recall@10 =
 share of the true 10 nearest allowed rows among the IVF search's 10 results.
-usage: python tools/filter_recall.py [--seed 77] [--out result.json]"""
+With --slots: 32 seeded random allow sets, pass fractions cycling 1/2, 1/8 and 1/32, are installed as
+filter slots and as base filter slots; the queries are spread over the 32 slots and NONE; ONE search_slots call is scored
+against ONE exact_search_slots call, Recall@1 and Recall@10 per pass fraction.
+usage: python tools/filter_recall.py [--seed 77] [--slots] [--out result.json]"""
 import argparse
 import json
 import os
@@ -27,48 +30,117 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def filtered_recall(pkg, seed=77):
-    import rerank_ref
-    c = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+def recall_pair(lab, truth):
+    """(Recall@1, Recall@10) of search labels [m, 10] against true labels [m, 10] (-1 = no such row)."""
+    r1 = float((lab[:, 0] == truth[:, 0]).mean())
+    hits = sum(np.intersect1d(lab[i][lab[i] >= 0], truth[i][truth[i] >= 0]).size for i in range(len(lab)))
+    return r1, hits / max(1, int((truth >= 0).sum()))
+
+
+def upload(pkg, c):
     g = pkg.GpuIndex(0)
     g.upload_ivf(c["d"], c["code_size"], c["offsets"], c["ids"], c["codes"], c["norm_codes"], c["centroid_norms"],
                  c["pq_centroids"], c["norm_table"])
-    g.upload_quantizer(c["counts"], c["links"], c["centroids"], 0)
+    g.upload_quantizer(c["counts"], c["links"], c["centroids"], c.get("enterpoint", 0))
     g.upload_base(c["base"])
-    qf = c["queries"]
+    return g
+
+
+def filtered_recall(pkg, seed=77, corpus=None, allow_sets=None, query_idx=None, settings=SETTINGS):
+    """corpus: a dict as rerank_ref.uint8_recall_corpus returns it (default: that corpus); allow_sets: [(name, row numbers)]
+    in place of the random sets of FRACTIONS; query_idx: only these queries."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"] if query_idx is None else c["queries"][query_idx]
     q8 = qf.astype(np.uint8)  # integer-valued, 0..255
     nq, n = len(q8), len(c["base"])
     rng = np.random.default_rng(seed + 1)
+    if allow_sets is None:
+        allow_sets = [("1/%d" % den, np.arange(n, dtype=np.uint32) if den == 1 else
+                       np.sort(rng.choice(n, n // den, replace=False)).astype(np.uint32)) for den in FRACTIONS]
     rows = []
-    for den in FRACTIONS:
-        allow = np.arange(n, dtype=np.uint32) if den == 1 else \
-            np.sort(rng.choice(n, n // den, replace=False)).astype(np.uint32)
+    for name, allow in allow_sets:
         g.set_filter(allow)
         g.set_base_filter(allow)
         assert g.filter_info()[1] == g.base_filter_info()[1] == allow.size
         _, truth = g.exact_search(q8, 10)
-        for nprobe, max_codes, ef in SETTINGS:
+        for nprobe, max_codes, ef in settings:
             _, lab = g.search(qf, 10, nprobe, max_codes, efSearch=ef)
-            r1 = float((lab[:, 0] == truth[:, 0]).mean())
-            hits = sum(np.intersect1d(lab[i][lab[i] >= 0], truth[i][truth[i] >= 0]).size for i in range(nq))
-            r10 = hits / max(1, int((truth >= 0).sum()))
-            row = {"pass_fraction": "1/%d" % den, "rows_passing": int(allow.size), "nprobe": nprobe, "max_codes": max_codes,
+            r1, r10 = recall_pair(lab, truth)
+            row = {"pass_fraction": name, "rows_passing": int(allow.size), "nprobe": nprobe, "max_codes": max_codes,
                    "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10}
             rows.append(row)
-            log("[filter_recall] 1/%d of %d rows, nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
-                % (den, n, nprobe, max_codes, r1, r10))
+            log("[filter_recall] %s of %d rows, nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, n, nprobe, max_codes, r1, r10))
     g.close()
     return {"corpus": "uint8_recall_corpus(seed=%d)" % seed, "rows": n, "nq": nq, "filtered_recall": rows}
+
+
+SLOT_FRACTIONS = (2, 8, 32)
+SLOT_NONE = 0xff
+
+
+def slot_allow_sets(n, seed):
+    """The 32 allow sets of the --slots run: slot s holds a random n / SLOT_FRACTIONS[s % 3] of the row numbers."""
+    rng = np.random.default_rng(seed + 2)
+    return [np.sort(rng.choice(n, n // SLOT_FRACTIONS[s % 3], replace=False)).astype(np.uint32) for s in range(32)]
+
+
+def slots_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
+    """Recall of one search_slots call against one exact_search_slots call, per pass fraction.  corpus: a dict as
+    rerank_ref.uint8_recall_corpus returns it (ids = row numbers of the base); default: that corpus itself.  Returns the
+    report; its "truth" / "query_slots" / "sets" entries are the arrays themselves, for a test to compare."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    sets = slot_allow_sets(n, seed)
+    for s, allow in enumerate(sets):
+        g.set_filter_slot(s, allow)
+        g.set_base_filter_slot(s, allow)
+        assert g.filter_slot_info(s)[1] == g.base_filter_slot_info(s)[1] == allow.size
+    qs = (np.arange(nq) % 33).astype(np.uint8)  # the 32 slots and NONE in turn
+    qs[qs == 32] = SLOT_NONE
+    _, truth = g.exact_search_slots(q8, 10, qs)
+    rows = []
+    den_of = np.array([1 if b == SLOT_NONE else SLOT_FRACTIONS[b % 3] for b in qs])
+    per_slot = []
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_slots(qf, 10, qs, nprobe, max_codes, efSearch=ef)
+        per_slot.append([recall_pair(lab[qs == b], truth[qs == b]) for b in range(32)])
+        for den in (1,) + SLOT_FRACTIONS:
+            idx = np.flatnonzero(den_of == den)
+            r1, r10 = recall_pair(lab[idx], truth[idx])
+            rows.append({"pass_fraction": "1/%d" % den, "queries": int(idx.size), "nprobe": nprobe, "max_codes": max_codes,
+                         "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] slots, 1/%d (%d queries), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (den, idx.size, nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "slots": 32, "slots_recall": rows, "truth": truth, "query_slots": qs, "sets": sets,
+            "per_slot": per_slot}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
+    ap.add_argument("--slots", action="store_true", help="one search_slots call against one exact_search_slots call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
-    out = filtered_recall(pkg, args.seed)
+    if args.slots:
+        out = slots_recall(pkg, args.seed)
+        out = {k: v for k, v in out.items() if k not in ("truth", "query_slots", "sets", "per_slot")}
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    else:
+        out = filtered_recall(pkg, args.seed)
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:
