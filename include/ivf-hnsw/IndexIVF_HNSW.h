@@ -7,7 +7,8 @@
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
 // release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
-// clear_id_filter_slot(), search_batch_slots(), range_search_slots(), range_search(),
+// clear_id_filter_slot(), search_batch_slots(), range_search_slots(), set_id_tags(), clear_id_tags(),
+// search_batch_tags(), range_search_tags(), range_search(),
 // reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
@@ -138,6 +139,19 @@ public:
     void search_batch_slots(size_t nq, size_t k, const float *x, const uint8_t *slots, float *distances, long *labels);
     void range_search_slots(size_t nq, const float *x, const uint8_t *slots, float radius, std::vector<size_t> &lims,
                             std::vector<float> &distances, std::vector<long> &labels);
+    /// Extension: DISJOINT id sets -- tenant, shard key, collection -- as one 16-bit tag per id (ivfhnsw_gpu_set_tags,
+    /// DESIGN.md 3.21).  set_id_tags is incremental: it (over)writes the tags of the ids given (0xffff untags one) and
+    /// leaves every other id's alone; an id given two different tags in one call throws.  search_batch_tags /
+    /// range_search_tags take one tag per query and answer each query as search_batch / range_search would with
+    /// set_id_filter(ids carrying that tag) installed, a query tagged 0xffff as they would with no filter.  Independent of
+    /// set_id_filter and the slots, and not combined with them: the _tags calls throw while a set_id_filter filter is
+    /// installed.  The tags are kept on the host beside the object and installed on the device copy whenever that is made
+    /// or remade, at once if it is current.  Non-virtual.  All throw with IVFHNSW_SHARDS > 1.
+    void set_id_tags(size_t n, const idx_t *xids, const uint16_t *tags);
+    void clear_id_tags();
+    void search_batch_tags(size_t nq, size_t k, const float *x, const uint16_t *tags, float *distances, long *labels);
+    void range_search_tags(size_t nq, const float *x, const uint16_t *tags, float radius, std::vector<size_t> &lims,
+                           std::vector<float> &distances, std::vector<long> &labels);
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

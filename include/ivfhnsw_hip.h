@@ -297,6 +297,49 @@ int ivfhnsw_gpu_set_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, con
 int ivfhnsw_gpu_clear_filter_slot(ivfhnsw_gpu *h, int slot); /* -1: every slot */
 int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint64_t *rows_passing, uint64_t *rows_total);
 
+/* Row tags: DISJOINT sets -- tenant, shard key, collection -- as one 16-bit number per row rather than
+ * a bit plane per set: 2 bytes per resident row serve 65 535 sets.  A handle holds at most one tag table, a uint16 per
+ * label value over [0, largest label ever tagged]; a label that was never tagged reads as IVFHNSW_TAG_NONE.  The _tags
+ * forms of search and range search take one uint16 per query: query q with query_tags[q] == t, t != IVFHNSW_TAG_NONE,
+ * answers, bit for bit, what the plain call answers on the same handle with set_filter({labels tagged t}, ALLOW)
+ * installed -- labels, distance bits, unfilled places, the heap array of heap_order = 1 for any k, out_keys, candidate
+ * streams, resolve_keys*, and range lims / distances / labels in scan order -- and with IVFHNSW_TAG_NONE what it answers
+ * with no filter.  Everything said of a filtered call above holds per query (the same lists in the same order,
+ * max_codes counts every stored code, last_scan_counts is the unfiltered call's).  A tag that no row carries returns
+ * padding / empty lims.  A _tags launch reports the unfiltered kernel's name with "+tags" appended and runs plan, table
+ * and scan as a _slots launch does.  query_tags == NULL is the plain call.
+ *   Tags, slots and the handle's filter are independent state: plain and _slots calls never read tags, a _tags call
+ * ignores slots, and a _tags call on a handle with a set_filter filter installed -> IVFHNSW_ERR_STATE.  A _tags call on a
+ * handle without a tag table is legal: every row is IVFHNSW_TAG_NONE.
+ * ivfhnsw_gpu_set_tags is INCREMENTAL: it (over)writes the tags of the n labels given and leaves every other label's
+ *   alone.  Any uint32 label, resident or not; a repeated label with the same tag counts once; a label given two
+ *   different tags in one call -> IVFHNSW_ERR_INVALID; the tag IVFHNSW_TAG_NONE untags a label.  The new table and row
+ *   tags are built beside the installed ones and swapped in: any error leaves the state as it was.  Synchronous on the
+ *   handle's stream.  _dev: d_labels (4-byte aligned) and d_tags (2-byte aligned) in device memory.
+ *   ivfhnsw_gpu_clear_tags drops table and row tags (succeeds without any); ivfhnsw_gpu_upload_ivf does the same.
+ *   ivfhnsw_gpu_tags_info: *rows_tagged = resident rows whose tag is not IVFHNSW_TAG_NONE, *rows_total = resident rows,
+ *   *table_labels = label values the table spans (largest tagged label + 1; 0 without a table); each nullable.
+ *   ivfhnsw_gpu_tag_rows: *rows = resident rows that carry `tag` (tag <= 0xffff; IVFHNSW_TAG_NONE counts the untagged).
+ * After a successful append_ivf, add, remove_ids, append_grouping or add_groups (host and _dev forms) the row tags hold
+ *   for the updated lists (one gather over the new ids, before they are installed); an update that fails leaves tables and
+ *   tags as they were.  A label held by several rows tags all of them.  A view reads the tags its parent held when the view
+ *   was created (the internal view of a split batch follows the handle at every call); set / clear on a view ->
+ *   IVFHNSW_ERR_STATE.
+ * Memory, counted by ivfhnsw_gpu_memory_bytes: 2 * (largest tagged label + 1) bytes of table and 2 * max(rows, 1) bytes of
+ *   row tags; a host _tags call stages its 2 bytes per query.
+ * Errors: null labels or tags with n > 0, a misaligned device pointer, conflicting repeats, tag > 0xffff ->
+ *   IVFHNSW_ERR_INVALID; set before upload_ivf, set or clear on a view, set / clear / a _tags call on a handle with
+ *   shard_world > 1 -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM.
+ * Not built: tags for the exact calls (the truth of a tagged search is the per-tag base-filter loop), for
+ *   search_reconstruct, search_sharded and sharded handles; a tag AND the handle's filter or a slot; tags wider than 16
+ *   bits or several tags per row. */
+#define IVFHNSW_TAG_NONE 0xffffu
+int ivfhnsw_gpu_set_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint16_t *tags);
+int ivfhnsw_gpu_set_tags_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint16_t *d_tags);
+int ivfhnsw_gpu_clear_tags(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_tags_info(ivfhnsw_gpu *h, uint64_t *rows_tagged, uint64_t *rows_total, uint64_t *table_labels);
+int ivfhnsw_gpu_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */
@@ -403,6 +446,15 @@ int ivfhnsw_gpu_search_slots_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const floa
                                  const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                  const uint8_t *d_query_slots, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
 
+/* ... and with a row tag per query (see "Row tags" above): query_tags [nq] uint16, host memory for the host form, device
+ * memory (2-byte aligned) for the _dev form; NULL = the plain call. */
+int ivfhnsw_gpu_search_tags(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                            const float *coarse_dists, const ivfhnsw_search_params *params, const uint16_t *query_tags,
+                            float *distances, int64_t *labels);
+int ivfhnsw_gpu_search_tags_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
+
 /* Multi-GPU merge helper: given keys already MIN-reduced over the shards, resolve the
  * labels this shard owns ([nq*k]; -1 where the winner lives on another shard) from the scan plan of
  * the last search_dev call, and decode the distances.  The caller then MAX-reduces the labels. */
@@ -493,6 +545,13 @@ int ivfhnsw_gpu_range_search_slots(ivfhnsw_gpu *h, size_t nq, const float *queri
 int ivfhnsw_gpu_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                                        const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                        const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total);
+/* ... and with a row tag per query ("Row tags" above) */
+int ivfhnsw_gpu_range_search_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                  const float *coarse_dists, const ivfhnsw_search_params *params, const uint16_t *query_tags,
+                                  float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                      const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                      const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("IVFHNSW_HIP_LIB") or os.path.join(_HERE, "libivfhnsw_
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
 FILTER_ALLOW, FILTER_DENY = 0, 1
 FILTER_SLOTS, SLOT_NONE = 32, 0xff
+TAG_NONE = 0xffff
 RECON_ORIGINAL, RECON_ROTATED = 0, 1
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
@@ -56,6 +57,9 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_set_filter_slot", "ivfhnsw_gpu_set_filter_slot_dev", "ivfhnsw_gpu_clear_filter_slot",
     "ivfhnsw_gpu_filter_slot_info", "ivfhnsw_gpu_search_slots", "ivfhnsw_gpu_search_slots_dev",
     "ivfhnsw_gpu_range_search_slots", "ivfhnsw_gpu_range_search_slots_dev",
+    "ivfhnsw_gpu_set_tags", "ivfhnsw_gpu_set_tags_dev", "ivfhnsw_gpu_clear_tags", "ivfhnsw_gpu_tags_info",
+    "ivfhnsw_gpu_tag_rows", "ivfhnsw_gpu_search_tags", "ivfhnsw_gpu_search_tags_dev",
+    "ivfhnsw_gpu_range_search_tags", "ivfhnsw_gpu_range_search_tags_dev",
 )
 
 
@@ -197,6 +201,15 @@ def lib():
                                                      C.POINTER(SearchParams), C.c_void_p, C.c_float, C.c_void_p,
                                                      C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_slots_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
+        L.ivfhnsw_gpu_set_tags.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_set_tags_dev.argtypes = L.ivfhnsw_gpu_set_tags.argtypes
+        L.ivfhnsw_gpu_clear_tags.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_tags_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_tag_rows.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_search_tags.argtypes = L.ivfhnsw_gpu_search_slots.argtypes
+        L.ivfhnsw_gpu_search_tags_dev.argtypes = L.ivfhnsw_gpu_search_slots_dev.argtypes
+        L.ivfhnsw_gpu_range_search_tags.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
+        L.ivfhnsw_gpu_range_search_tags_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
         L.ivfhnsw_gpu_set_base_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
         L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
@@ -459,6 +472,36 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_filter_slot_info(self._h, slot, C.byref(m), C.byref(a), C.byref(b)))
         return int(m.value), int(a.value), int(b.value)
 
+    # ---- row tags: disjoint sets as a 16-bit tag per row (ivfhnsw_gpu_set_tags) -------------------------
+    def set_tags(self, labels, tags):
+        """The labels given carry the tags given (uint16; TAG_NONE untags) from now on; every other label keeps its tag.
+        The _tags searches name a tag per query."""
+        lab = _np(labels, np.uint32).ravel()
+        tg = _np(tags, np.uint16).ravel()
+        if tg.size != lab.size:
+            raise ValueError("set_tags: %d labels, %d tags" % (lab.size, tg.size))
+        _check(lib().ivfhnsw_gpu_set_tags(self._h, lab.size, _ptr(lab) if lab.size else None, _ptr(tg) if tg.size else None))
+
+    def set_tags_dev(self, n, d_labels, d_tags):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_set_tags_dev(self._h, n, _devptr(d_labels), _devptr(d_tags)))
+
+    def clear_tags(self):
+        """No label is tagged afterwards."""
+        _check(lib().ivfhnsw_gpu_clear_tags(self._h))
+
+    def tags_info(self):
+        """(rows_tagged, rows_total, table_labels): resident rows with a tag, resident rows, label values the table spans."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_tags_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def tag_rows(self, tag):
+        """Resident rows that carry `tag`."""
+        n = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_tag_rows(self._h, tag, C.byref(n)))
+        return int(n.value)
+
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)
         n = _np(nn_centroid_idxs, np.uint32)
@@ -598,17 +641,28 @@ class GpuIndex:
                      do_pruning=False, heap_order=False):
         """search() with a filter slot per query: query_slots [nq] bytes, each a slot or SLOT_NONE (no filter); None is
         search() itself (ivfhnsw_gpu_search_slots)."""
+        return self._search_picked(lib().ivfhnsw_gpu_search_slots, np.uint8, queries, k, query_slots, nprobe, max_codes,
+                                   coarse_ids, coarse_dists, efSearch, do_pruning, heap_order)
+
+    def search_tags(self, queries, k, query_tags, nprobe, max_codes, coarse_ids=None, coarse_dists=None, efSearch=0,
+                    do_pruning=False, heap_order=False):
+        """search() with a row tag per query: query_tags [nq] uint16, each a tag or TAG_NONE (no filter); None is
+        search() itself (ivfhnsw_gpu_search_tags)."""
+        return self._search_picked(lib().ivfhnsw_gpu_search_tags, np.uint16, queries, k, query_tags, nprobe, max_codes,
+                                   coarse_ids, coarse_dists, efSearch, do_pruning, heap_order)
+
+    def _search_picked(self, fn, pick_dtype, queries, k, query_slots, nprobe, max_codes, coarse_ids, coarse_dists, efSearch,
+                       do_pruning, heap_order):
         q = _np(queries, np.float32)
         q = q.reshape(-1, self.d or q.shape[-1])
         nq = q.shape[0]
         cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
         cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
-        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq)
         dist = np.empty((nq, k), np.float32)
         lab = np.empty((nq, k), np.int64)
         p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
-        _check(lib().ivfhnsw_gpu_search_slots(self._h, nq, k, _ptr(q), _ptr(cid), _ptr(cd), C.byref(p), _ptr(qs),
-                                              _ptr(dist), _ptr(lab)))
+        _check(fn(self._h, nq, k, _ptr(q), _ptr(cid), _ptr(cd), C.byref(p), _ptr(qs), _ptr(dist), _ptr(lab)))
         return dist, lab
 
     def search_slots_dev(self, nq, k, d_queries, d_query_slots, d_distances, d_labels, nprobe, max_codes,
@@ -620,6 +674,15 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_search_slots_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
                                                   _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_slots),
                                                   _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
+
+    def search_tags_dev(self, nq, k, d_queries, d_query_tags, d_distances, d_labels, nprobe, max_codes,
+                        d_coarse_ids=None, d_coarse_dists=None, efSearch=0, do_pruning=False, d_out_keys=None,
+                        heap_order=False):
+        """search_dev() with a row tag per query (d_query_tags: [nq] uint16 in device memory, not read back)."""
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_tags_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                 _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
+                                                 _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
 
     # ---- reconstruction of stored vectors (ivfhnsw_gpu_reconstruct*, DESIGN.md 3.16) ---------------------------------
     def locate(self, labels):
@@ -728,17 +791,28 @@ class GpuIndex:
     def range_search_slots(self, queries, radius, query_slots, nprobe, max_codes, efSearch=0, do_pruning=False,
                            coarse_ids=None, coarse_dists=None):
         """range_search() with a filter slot per query (query_slots as search_slots takes them)."""
+        return self._range_search_picked(lib().ivfhnsw_gpu_range_search_slots, np.uint8, queries, radius, query_slots, nprobe,
+                                         max_codes, efSearch, do_pruning, coarse_ids, coarse_dists)
+
+    def range_search_tags(self, queries, radius, query_tags, nprobe, max_codes, efSearch=0, do_pruning=False,
+                          coarse_ids=None, coarse_dists=None):
+        """range_search() with a row tag per query (query_tags as search_tags takes them)."""
+        return self._range_search_picked(lib().ivfhnsw_gpu_range_search_tags, np.uint16, queries, radius, query_tags, nprobe,
+                                         max_codes, efSearch, do_pruning, coarse_ids, coarse_dists)
+
+    def _range_search_picked(self, fn, pick_dtype, queries, radius, query_slots, nprobe, max_codes, efSearch, do_pruning,
+                             coarse_ids, coarse_dists):
         q = _np(queries, np.float32)
         q = q.reshape(-1, self.d or q.shape[-1])
         nq = q.shape[0]
         cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
         cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
-        qs = None if query_slots is None else _np(query_slots, np.uint8).reshape(nq)
+        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq)
         lims = np.zeros(nq + 1, np.uint64)
         total = C.c_uint64(0)
         p = self._params(nprobe, max_codes, efSearch, do_pruning)
-        _check(lib().ivfhnsw_gpu_range_search_slots(self._h, nq, _ptr(q) if nq else None, _ptr(cid), _ptr(cd), C.byref(p),
-                                                    _ptr(qs), C.c_float(radius), _ptr(lims), C.byref(total)))
+        _check(fn(self._h, nq, _ptr(q) if nq else None, _ptr(cid), _ptr(cd), C.byref(p), _ptr(qs), C.c_float(radius),
+                  _ptr(lims), C.byref(total)))
         dist, lab = self.range_results(0, int(total.value))
         return lims, dist, lab
 
@@ -750,6 +824,16 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_range_search_slots_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
                                                         _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_slots),
                                                         C.c_float(radius), _devptr(d_lims), C.byref(total)))
+        return int(total.value)
+
+    def range_search_tags_dev(self, nq, d_queries, radius, d_query_tags, d_lims, nprobe, max_codes, efSearch=0,
+                              do_pruning=False, d_coarse_ids=None, d_coarse_dists=None):
+        """range_search_dev() with a row tag per query (d_query_tags in device memory)."""
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_tags_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                       _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
+                                                       C.c_float(radius), _devptr(d_lims), C.byref(total)))
         return int(total.value)
 
     def range_results(self, first, count):

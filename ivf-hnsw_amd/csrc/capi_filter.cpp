@@ -1,7 +1,8 @@
 // The label filter of a handle: searches return only rows whose id is in an allowed set, or is not in a
 // denied one.  The set becomes a bitmap over [0, max label], the bitmap one PASS bit per resident row, and the filtered
 // forms of the scan kernels read that bit beside the row's norm code.  The bitmap stays with the handle so that in-place
-// updates can judge the rows of their new arrays (ListArrays::mark_filter, capi_internal.h).
+// updates can judge the rows of their new arrays (ListArrays::mark_filter, capi_internal.h).  Filter slots (3.19) and
+// row tags (3.21), the two per-query forms, live here too.
 #include "capi_internal.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -36,14 +37,15 @@ void filter_drop(ivfhnsw_gpu *h)
     h->f_mask.release();
 }
 
-static int filter_state(ivfhnsw_gpu *h, const char *who)
+// the opening of the calls that set or clear a filter, a slot or the tags (what: "label filter" unless said)
+static int filter_state(ivfhnsw_gpu *h, const char *who, bool need_upload = true, const char *what = "label filter")
 {
-    int rc = filter_holder_guard(h, kIndexFilter, who, true);
+    int rc = filter_holder_guard(h, kIndexFilter, who, need_upload);
     if (rc)
         return rc;
     if (h->t.shard_world > 1)
-        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no label filter", who,
-                    h->t.shard_rank, h->t.shard_world);
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no %s", who,
+                    h->t.shard_rank, h->t.shard_world, what);
     return IVFHNSW_OK;
 }
 
@@ -101,16 +103,17 @@ int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBu
     return IVFHNSW_OK;
 }
 
-int slots_call_guard(const ivfhnsw_gpu *h, const char *who)
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags)
 {
     if (h->t.shard_world > 1)
-        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no filter slots", who,
-                    h->t.shard_rank, h->t.shard_world);
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no %s", who,
+                    h->t.shard_rank, h->t.shard_world, tags ? "row tags" : "filter slots");
     if (h->filter.mode >= 0)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle has a set_filter filter installed; a call is filtered by that or by "
-                                       "slots, not both (clear_filter first)", who);
+                                       "%s, not both (clear_filter first)", who, tags ? "tags" : "slots");
     return IVFHNSW_OK;
 }
+
 
 int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who)
 {
@@ -165,6 +168,94 @@ static int set_slot_core(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t
     if (grow)
         planes_install(h, planes, slot + 1);
     h->slots[slot].install(bits, n, max_label, mode, pass); // the slot's earlier set goes with this scope
+    return IVFHNSW_OK;
+}
+
+// ---- row tags: disjoint sets as one uint16 per label value (tg_table, tg_labels entries), gathered into
+// one uint16 per resident row (tg_rows), which the _tags scans compare with the query's tag.
+
+void tags_drop(ivfhnsw_gpu *h)
+{
+    h->tg_labels = 0;
+    h->row_tags = nullptr;
+    h->tg_table.release();
+    h->tg_rows.release();
+}
+
+// the tags of ids [n_local] from a table of table_n labels into out (grown here; never empty).  Returns with the stream drained.
+static int gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, const uint16_t *table, uint64_t table_n, DevBuf &out)
+{
+    int rc = out.ensure((size_t)std::max<uint64_t>(n_local, 1) * sizeof(uint16_t));
+    if (rc)
+        return rc;
+    HIP_TRY(launch_tags_gather(h->stream, ids, n_local, table, table_n, out.as<uint16_t>()));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+int tags_gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &row_tags)
+{
+    return gather_rows(h, ids, n_local, h->tg_table.as<uint16_t>(), h->tg_labels, row_tags);
+}
+
+// d_labels / d_tags [n] in device memory, max_label their largest label.  As set_filter_core: the new table (the old one's
+// entries, untagged beyond them, then the n tags scattered in) and the new row tags are built beside the installed ones
+// and swapped in when nothing can fail any more.  A label given two different tags keeps one of them, which the check
+// behind the scatter finds.
+static int set_tags_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint16_t *d_tags, uint32_t max_label)
+{
+    if (n == 0)
+        return IVFHNSW_OK;
+    const uint64_t held = h->tg_labels, span = std::max<uint64_t>(held, (uint64_t)max_label + 1);
+    ScopedBuf table, rows, word; // word: of this call only
+    int rc;
+    if ((rc = table.ensure((size_t)span * sizeof(uint16_t))) || (rc = word.ensure(sizeof(uint32_t))))
+        return rc;
+    if (held)
+        HIP_TRY(hipMemcpyAsync(table.p, h->tg_table.p, (size_t)held * sizeof(uint16_t), hipMemcpyDeviceToDevice, h->stream));
+    if (span > held) // 0xffff: IVFHNSW_TAG_NONE
+        HIP_TRY(hipMemsetAsync(table.as<uint16_t>() + held, 0xff, (size_t)(span - held) * sizeof(uint16_t), h->stream));
+    uint32_t conflict = 0;
+    HIP_TRY(launch_tags_scatter(h->stream, d_labels, d_tags, n, table.as<uint16_t>(), word.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(&conflict, word.p, sizeof(conflict), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (conflict)
+        return fail(IVFHNSW_ERR_INVALID, "set_tags: a label is given two different tags in one call");
+    if ((rc = gather_rows(h, h->t.ids, h->n_local, table.as<uint16_t>(), span, rows)))
+        return rc;
+    table.install(h->tg_table); // the earlier table and row tags go with this scope
+    rows.install(h->tg_rows);
+    h->tg_labels = span;
+    h->row_tags = h->tg_rows.as<uint16_t>();
+    return IVFHNSW_OK;
+}
+
+static int tags_args(size_t n, const uint32_t *labels, const uint16_t *tags, const char *who)
+{
+    int rc = label_args_guard(n, labels, who);
+    if (rc)
+        return rc;
+    if (n && !tags)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null tags", who);
+    return IVFHNSW_OK;
+}
+
+// one counting pass over the row tags h reads: rows whose tag equals `tag`, or differs from it
+static int tags_count(ivfhnsw_gpu *h, uint32_t tag, bool equal, uint64_t *out)
+{
+    if (!h->row_tags) { // no table: every row is untagged
+        *out = (tag == IVFHNSW_TAG_NONE) == equal ? h->n_local : 0;
+        return IVFHNSW_OK;
+    }
+    ScopedBuf word;
+    int rc = word.ensure(sizeof(unsigned long long));
+    if (rc)
+        return rc;
+    unsigned long long cnt = 0;
+    HIP_TRY(launch_tags_count(h->stream, h->row_tags, h->n_local, tag, equal, word.as<unsigned long long>()));
+    HIP_TRY(hipMemcpyAsync(&cnt, word.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *out = cnt;
     return IVFHNSW_OK;
 }
 
@@ -293,4 +384,68 @@ int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint6
         return fail(IVFHNSW_ERR_INVALID, "filter_slot_info: slot %u, a handle has slots 0..%d", slot, IVFHNSW_FILTER_SLOTS - 1);
     const LabelSet &s = (h->is_view && h->parent ? h->parent : h)->slots[slot];
     return label_set_info(s.mode, s.pass, 0, h->n_local, mode, rows_passing, rows_total);
+}
+
+// ---- row tags
+
+int ivfhnsw_gpu_set_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint16_t *tags)
+{
+    int rc = filter_state(h, "set_tags", true, "row tags");
+    if (rc || (rc = tags_args(n, labels, tags, "set_tags")))
+        return rc;
+    ScopedBuf stage_l, stage_t; // of this call only
+    uint32_t mx = 0;
+    if ((rc = labels_from_host(h, n, labels, stage_l, &mx)) || (n && (rc = stage_in(h, stage_t, tags, n * sizeof(uint16_t)))))
+        return rc;
+    return set_tags_core(h, n, stage_l.as<uint32_t>(), stage_t.as<uint16_t>(), mx);
+}
+
+int ivfhnsw_gpu_set_tags_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint16_t *d_tags)
+{
+    int rc = filter_state(h, "set_tags_dev", true, "row tags");
+    if (rc || (rc = tags_args(n, d_labels, d_tags, "set_tags_dev")))
+        return rc;
+    if (((uintptr_t)d_labels & 3) || ((uintptr_t)d_tags & 1))
+        return fail(IVFHNSW_ERR_INVALID, "set_tags_dev: labels must be 4-byte aligned and tags 2-byte aligned");
+    ScopedBuf word; // of this call only
+    uint32_t mx = 0;
+    if ((rc = labels_max_dev(h, word, n, d_labels, &mx)))
+        return rc;
+    return set_tags_core(h, n, d_labels, d_tags, mx);
+}
+
+int ivfhnsw_gpu_clear_tags(ivfhnsw_gpu *h)
+{
+    int rc = filter_state(h, "clear_tags", false, "row tags");
+    if (rc)
+        return rc;
+    if (!h->tg_labels)
+        return IVFHNSW_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream)); // searches in flight still read the row tags (a split batch joins this stream)
+    tags_drop(h);
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_tags_info(ivfhnsw_gpu *h, uint64_t *rows_tagged, uint64_t *rows_total, uint64_t *table_labels)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (rows_tagged && (rc = tags_count(h, IVFHNSW_TAG_NONE, false, rows_tagged)))
+        return rc;
+    if (rows_total)
+        *rows_total = h->n_local;
+    if (table_labels)
+        *table_labels = h->tg_labels;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (tag > IVFHNSW_TAG_NONE || !rows)
+        return fail(IVFHNSW_ERR_INVALID, "tag_rows: tag %u (tags are 0..0xffff) or a null result", tag);
+    return tags_count(h, tag, true, rows);
 }

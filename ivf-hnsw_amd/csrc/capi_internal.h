@@ -193,7 +193,8 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_count) /* set_filter: the pass mask, the count's word (the kept label bitmap: filter.bits) */ \
-    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes */ \
+    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts) */ \
+    X(tg_table) X(tg_rows) /* row tags: a uint16 per label value, a uint16 per resident row */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
     X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans, a host call's slot bytes */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
@@ -252,6 +253,13 @@ struct ivfhnsw_gpu {
     // that is not set has, where it has a plane, a zero one.
     SlotMask fs{nullptr, 0, 0, nullptr};
     LabelSet slots[IVFHNSW_FILTER_SLOTS];
+
+    // row tags (capi_filter.cpp): tg_table holds a uint16 per label value below tg_labels (0 = no table),
+    // tg_rows the tag of every resident row, re-derived by every set_tags and every in-place update.  row_tags is what the
+    // _tags scans read: the handle's own tg_rows, on a view what its parent held when follow_parent ran; null = no table,
+    // every row untagged.
+    uint64_t tg_labels = 0;
+    const uint16_t *row_tags = nullptr;
 
     // the base filter of the exact calls (capi_base_filter.cpp), on the handle that holds the store: a view
     // reads its parent's at the call.  bf_mode -1 = none.  bf_words: one pass bit per row; bf_rows (bf_has_rows): the
@@ -378,9 +386,14 @@ inline uint64_t slot_plane_stride(uint64_t n_local) { return std::max<uint64_t>(
 int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &planes, uint64_t *pass);
 void slots_drop(ivfhnsw_gpu *h); // the handle holds no slot afterwards (buffers released)
 // what a _slots entry point checks first, behind the plain call's own guard
-int slots_call_guard(const ivfhnsw_gpu *h, const char *who);
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags = false); // tags: the same for a _tags entry point
 // the slot bytes of a host call: each is below IVFHNSW_FILTER_SLOTS or IVFHNSW_SLOT_NONE
 int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who);
+// (every uint16 is a tag: the host form of a _tags call has nothing to check there)
+// Row tags.  The tag of ids [n_local] from h's table into row_tags (allocated here, max(n_local, 1)
+// elements).  Returns with the stream drained; the handle is not touched.
+int tags_gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &row_tags);
+void tags_drop(ivfhnsw_gpu *h); // the handle holds no tags afterwards (buffers released)
 
 // The five arrays that make up the resident lists, built BESIDE the handle's: an in-place update fills a fresh set and
 // installs it when it is complete and the stream has drained, so that on any error the handle's tables are the ones it
@@ -391,6 +404,7 @@ struct ListArrays {
     uint64_t fpass = 0;
     DevBuf fplanes; // ... and its filter slots, every plane in one pass
     uint64_t fs_pass[IVFHNSW_FILTER_SLOTS] = {};
+    DevBuf ftags; // ... and its row tags, gathered from the tag table
     ListArrays() = default;
     ListArrays(const ListArrays &) = delete;
     ListArrays &operator=(const ListArrays &) = delete;
@@ -408,11 +422,13 @@ struct ListArrays {
         return {goff.as<uint64_t>(), loff.as<uint32_t>(), codes.as<uint8_t>(), ncodes.as<uint8_t>(), ids.as<uint32_t>(), n_local};
     }
     // The one place an update re-marks the filter: rows move and new rows must be judged.  Called when the new ids are
-    // complete and BEFORE install, so that a failure here leaves tables, filter and slots as they were.  No filter and no
-    // slot: nothing.
+    // complete and BEFORE install, so that a failure here leaves tables, filter, slots and tags as they were.  No filter,
+    // no slot and no tag table: nothing.
     int mark_filter(ivfhnsw_gpu *h, uint64_t n_local)
     {
         int rc;
+        if (h->tg_labels && (rc = tags_gather_rows(h, ids.as<uint32_t>(), n_local, ftags)))
+            return rc;
         if (h->fs.nplanes && (rc = slots_mark_rows(h, ids.as<uint32_t>(), n_local, fplanes, fs_pass)))
             return rc;
         if (h->filter.mode < 0)
@@ -421,7 +437,7 @@ struct ListArrays {
     }
     void release()
     {
-        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask, &fplanes})
+        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask, &fplanes, &ftags})
             b->release();
     }
     void install(ivfhnsw_gpu *h, uint64_t n_local)
@@ -437,6 +453,10 @@ struct ListArrays {
             h->fs.stride = (uint32_t)slot_plane_stride(n_local);
             for (int s = 0; s < IVFHNSW_FILTER_SLOTS; s++)
                 h->slots[s].pass = fs_pass[s];
+        }
+        if (h->tg_labels) {
+            std::swap(h->tg_rows, ftags);
+            h->row_tags = h->tg_rows.as<uint16_t>();
         }
         std::swap(h->goff, goff);
         std::swap(h->loff, loff);
@@ -506,6 +526,24 @@ struct WalkClear {
     bool cleared = false;     // out
 };
 
+// What a _slots or a _tags entry point carries beside the plain call's arguments: a filter slot
+// byte or a tag per query, one of the two at most, in host or device memory as the call's other arrays are.
+struct QueryPick {
+    const uint8_t *slots = nullptr;
+    const uint16_t *tags = nullptr;
+    explicit operator bool() const { return slots || tags; }
+    const void *data() const { return slots ? static_cast<const void *>(slots) : tags; }
+    size_t bytes(size_t nq) const { return slots ? nq : tags ? nq * sizeof(uint16_t) : 0; }
+    // the same kind of pick with its array at p / for the queries from q0 on
+    QueryPick at(const void *p) const
+    {
+        return {slots ? static_cast<const uint8_t *>(p) : nullptr, tags ? static_cast<const uint16_t *>(p) : nullptr};
+    }
+    QueryPick from(size_t q0) const { return {slots ? slots + q0 : nullptr, tags ? tags + q0 : nullptr}; }
+    // the entry point's name: "<call>_slots" or "<call>_tags"
+    const char *who(const char *slotted, const char *tagged) const { return tags ? tagged : slotted; }
+};
+
 // The arguments of ivfhnsw_gpu_search_dev, handed down as one.
 struct SearchArgs {
     size_t nq, k;
@@ -515,12 +553,12 @@ struct SearchArgs {
     const ivfhnsw_search_params *p;
     float *d_distances;
     int64_t *d_labels, *d_out_keys;
-    const uint8_t *d_query_slots = nullptr; // a _slots call: the filter slot of every query, else null
+    QueryPick pick{}; // a _slots / _tags call: the filter slot or the tag of every query (device memory), else empty
     SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
     {
         return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
                 d_coarse_dists ? d_coarse_dists + q0 * p->nprobe : nullptr, p, d_distances + q0 * k, d_labels + q0 * k,
-                d_out_keys, d_query_slots ? d_query_slots + q0 : nullptr};
+                d_out_keys, pick.from(q0)};
     }
 };
 
@@ -528,7 +566,7 @@ struct SearchArgs {
 struct Chunk : SearchArgs {
     int nprobe, max_seg, plan_k;    // chunk_workspace
     bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
-    ScanFilter fmask;               // a label filter, or the call's filter slots (3.19)
+    ScanFilter fmask;               // a label filter, the call's filter slots (3.19) or its tags (3.21)
     const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
     const uint32_t *cid;
     const float *cd;

@@ -49,14 +49,16 @@ static int range_fill_pass(ivfhnsw_gpu *h, const Chunk &c, int seg_hint, float r
     return check_status(h);
 }
 
-// ivfhnsw_gpu_range_search_dev, and with d_query_slots (one byte per query, device memory) its _slots form
+// ivfhnsw_gpu_range_search_dev, and with a pick (a slot byte or a tag per query, device memory) its _slots / _tags form
 static int range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
-                            const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint8_t *d_query_slots,
+                            const float *d_coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick,
                             float radius, uint64_t *d_lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, radius, d_lims, total);
-    if (rc || (d_query_slots && (rc = slots_call_guard(h, "range_search_slots_dev"))))
+    if (rc || (pick && (rc = slots_call_guard(h, pick.who("range_search_slots_dev", "range_search_tags_dev"), pick.tags != nullptr))))
         return rc;
+    if ((uintptr_t)pick.tags & 1)
+        return fail(IVFHNSW_ERR_INVALID, "range_search_tags_dev: query tags must be 2-byte aligned");
     if (nq == 0) {
         if (d_lims) {
             HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
@@ -68,7 +70,7 @@ static int range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, c
         h->rg_total = 0;
         return IVFHNSW_OK;
     }
-    Chunk c{SearchArgs{nq, 1, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, nullptr, nullptr, d_query_slots}};
+    Chunk c{SearchArgs{nq, 1, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, nullptr, nullptr, pick}};
     if ((rc = chunk_checks(h, c, false)))
         return rc;
     // the workspace is about to hold this call's plan: whatever the last search left there is gone
@@ -147,24 +149,34 @@ int ivfhnsw_gpu_range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queri
                                  const float *d_coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *d_lims,
                                  uint64_t *total)
 {
-    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, nullptr, radius, d_lims, total);
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{}, radius, d_lims, total);
 }
 
 int ivfhnsw_gpu_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                                        const float *d_coarse_dists, const ivfhnsw_search_params *p,
                                        const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total)
 {
-    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, d_query_slots, radius, d_lims, total);
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{d_query_slots, nullptr}, radius, d_lims,
+                            total);
 }
 
-// ivfhnsw_gpu_range_search, and with query_slots (host memory) ivfhnsw_gpu_range_search_slots
+int ivfhnsw_gpu_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                      const float *d_coarse_dists, const ivfhnsw_search_params *p,
+                                      const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, d_query_tags}, radius, d_lims,
+                            total);
+}
+
+// ivfhnsw_gpu_range_search, and with a pick (host memory) ivfhnsw_gpu_range_search_slots / _tags
 static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
-                             const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots, float radius,
+                             const float *coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick, float radius,
                              uint64_t *lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, queries, coarse_ids, coarse_dists, p, radius, lims, total);
-    if (rc || (query_slots && ((rc = slots_call_guard(h, "range_search_slots")) ||
-                               (rc = slots_bytes_guard(nq, query_slots, "range_search_slots")))))
+    const char *who = pick.who("range_search_slots", "range_search_tags");
+    if (rc || (pick && ((rc = slots_call_guard(h, who, pick.tags != nullptr)) ||
+                        (pick.slots && (rc = slots_bytes_guard(nq, pick.slots, who))))))
         return rc;
     if (nq == 0) {
         if (lims)
@@ -174,9 +186,9 @@ static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, co
     const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
     if ((rc = h->rg_lims.ensure((nq + 1) * sizeof(uint64_t))) || (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (query_slots && (rc = stage_in(h, h->fs_qslots, query_slots, nq))) ||
+        (pick && (rc = stage_in(h, h->fs_qslots, pick.data(), pick.bytes(nq)))) ||
         (rc = range_search_dev(h, nq, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                               coarse_ids ? h->s_cd.as<float>() : nullptr, p, query_slots ? h->fs_qslots.as<uint8_t>() : nullptr,
+                               coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p),
                                radius, h->rg_lims.as<uint64_t>(), total)) ||
         (rc = stage_out(h, lims, h->rg_lims, (nq + 1) * sizeof(uint64_t))))
         return rc;
@@ -188,14 +200,21 @@ int ivfhnsw_gpu_range_search(ivfhnsw_gpu *h, size_t nq, const float *queries, co
                              const float *coarse_dists, const ivfhnsw_search_params *p, float radius, uint64_t *lims,
                              uint64_t *total)
 {
-    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, nullptr, radius, lims, total);
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{}, radius, lims, total);
 }
 
 int ivfhnsw_gpu_range_search_slots(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
                                    const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots,
                                    float radius, uint64_t *lims, uint64_t *total)
 {
-    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, query_slots, radius, lims, total);
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{query_slots, nullptr}, radius, lims, total);
+}
+
+int ivfhnsw_gpu_range_search_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                  const float *coarse_dists, const ivfhnsw_search_params *p, const uint16_t *query_tags,
+                                  float radius, uint64_t *lims, uint64_t *total)
+{
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags}, radius, lims, total);
 }
 
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels)

@@ -217,12 +217,12 @@ static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params
 // box (profiles/r04_early_tables.md): (32, 10000, 80) 1.652 -> 1.617 ms per step.  Only where the second part's walk leaves
 // such slots, i.e. has fewer queries than the walk has resident wavefronts (search_dev_split): at (64, 30000, 100) its 4096
 // queries take every slot the first walk frees, the table workgroups compete with them, and the step measured 0.6 %
-// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter, filter slots or a table that the
+// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter, filter slots, tags or a table that the
 // pipelined scan builds itself.
 static bool early_tables_wanted(const ivfhnsw_gpu *h, const SearchArgs &a)
 {
     static const bool on = env_size("IVFHNSW_EARLY_LUT", 1) != 0;
-    if (!on || !plan_lut_shape(h) || h->filter.mode >= 0 || a.d_query_slots)
+    if (!on || !plan_lut_shape(h) || h->filter.mode >= 0 || a.pick)
         return false;
     const bool may_pipe = a.k == 1 && h->opt_scan_pipe != 0 &&
                           scan_pipe_supported(h->t, (int)a.p->nprobe, (int)a.nq, 1, h->n_local > 0, h->opt_scan_pipe == 1);
@@ -354,20 +354,38 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
 }
 
-// The same call with a filter slot per query.  The bytes are not read back: one that names no installed
-// slot passes nothing.  d_query_slots null: the plain call.
+// The same call with a filter slot or a tag (3.21) per query.  Neither is read back: a byte that names
+// no installed slot, like a tag no row carries, passes nothing.  An empty pick: the plain call.
+static int search_pick_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                           const float *d_coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick,
+                           float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
+{
+    if (!pick)
+        return ivfhnsw_gpu_search_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
+    int rc = bind(h);
+    if (rc || (rc = search_args_guard(h, p, k)) ||
+        (rc = slots_call_guard(h, pick.who("search_slots_dev", "search_tags_dev"), pick.tags != nullptr)))
+        return rc;
+    if ((uintptr_t)pick.tags & 1)
+        return fail(IVFHNSW_ERR_INVALID, "search_tags_dev: query tags must be 2-byte aligned");
+    SearchCall call;
+    return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys, pick}, call);
+}
+
 int ivfhnsw_gpu_search_slots_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
                                  const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint8_t *d_query_slots,
                                  float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
 {
-    if (!d_query_slots)
-        return ivfhnsw_gpu_search_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
-    int rc = bind(h);
-    if (rc || (rc = search_args_guard(h, p, k)) || (rc = slots_call_guard(h, "search_slots_dev")))
-        return rc;
-    SearchCall call;
-    return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys, d_query_slots},
-                           call);
+    return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{d_query_slots, nullptr}, d_distances,
+                           d_labels, d_out_keys);
+}
+
+int ivfhnsw_gpu_search_tags_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint16_t *d_query_tags,
+                                float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
+{
+    return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, d_query_tags}, d_distances,
+                           d_labels, d_out_keys);
 }
 
 static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_stream, const char *kernel_name)
@@ -413,9 +431,11 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
         (rc = h->w_keys.ensure(c.nq * (size_t)c.plan_k * sizeof(uint64_t))) ||
         (rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
-    if (c.d_query_slots) // the planes the handle (a view: its parent) holds -- with none, any readable word: a query
-                         // without a plane reads word 0 and ignores it -- and the bytes of this chunk's queries
-        c.fmask = SlotMask{h->fs.nplanes ? h->fs.planes : h->w_totals.as<uint32_t>(), h->fs.stride, h->fs.nplanes, c.d_query_slots};
+    if (c.pick.tags) // the row tags the handle (a view: its parent) holds, null without a tag table, and this chunk's tags
+        c.fmask = TagMask{h->row_tags, c.pick.tags};
+    else if (c.pick.slots) // the planes the handle (a view: its parent) holds -- with none, any readable word: a query
+                           // without a plane reads word 0 and ignores it -- and the bytes of this chunk's queries
+        c.fmask = SlotMask{h->fs.nplanes ? h->fs.planes : h->w_totals.as<uint32_t>(), h->fs.stride, h->fs.nplanes, c.pick.slots};
     else
         c.fmask = h->filter.mode >= 0 ? h->fmask : nullptr;
     return IVFHNSW_OK;
@@ -564,7 +584,7 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
             HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, nullptr, nullptr, heap_ws, c.d_distances, c.d_labels,
                                      c.fmask));
         }
-        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots"));
+        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots", "heap_scan_kernel+tags"));
         return IVFHNSW_OK;
     }
     if (heap) {
@@ -694,16 +714,17 @@ int ivfhnsw_gpu_replay_stream_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const uin
     return IVFHNSW_OK;
 }
 
-// ivfhnsw_gpu_search, and with query_slots (one byte per query, host memory) ivfhnsw_gpu_search_slots: the bytes ride in
-// the pinned input block or a staging buffer beside the queries
+// ivfhnsw_gpu_search, and with a pick (a slot byte or a tag per query, host memory) ivfhnsw_gpu_search_slots / _tags: the
+// bytes ride in the pinned input block or a staging buffer beside the queries
 static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
-                       const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots, float *distances,
+                       const float *coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick, float *distances,
                        int64_t *labels)
 {
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)))
         return rc;
-    if (query_slots && (rc = slots_call_guard(h, "search_slots")))
+    const char *who = pick.who("search_slots", "search_tags");
+    if (pick && (rc = slots_call_guard(h, who, pick.tags != nullptr)))
         return rc;
     if (nq == 0)
         return IVFHNSW_OK;
@@ -711,10 +732,10 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
         return fail(IVFHNSW_ERR_INVALID, "null query/result buffer");
     if ((coarse_ids == nullptr) != (coarse_dists == nullptr))
         return fail(IVFHNSW_ERR_INVALID, "coarse_ids and coarse_dists must both be given or both be NULL");
-    if (query_slots && (rc = slots_bytes_guard(nq, query_slots, "search_slots")))
+    if (pick.slots && (rc = slots_bytes_guard(nq, pick.slots, who)))
         return rc;
     const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
-    const size_t in_s = query_slots ? nq : 0;
+    const size_t in_s = pick.bytes(nq);
     // Small batches -- the reference's drivers pass ONE query per call (tests/test_ivfhnsw_sift1b.cpp:193-208) -- go
     // through pinned host memory the kernels read and write directly: no staging copies, one synchronisation.  Layout
     // of the two blocks: in = queries | coarse ids | coarse dists; out = distances | labels | status word.
@@ -729,8 +750,8 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
             memcpy(pin + in_q, coarse_ids, in_c);
             memcpy(pin + in_q + in_c, coarse_dists, in_c);
         }
-        if (query_slots)
-            memcpy(pin + in_q + 2 * in_c, query_slots, in_s);
+        if (pick)
+            memcpy(pin + in_q + 2 * in_c, pick.data(), in_s); // (4-byte aligned: what precedes it is floats and words)
         uint32_t *pst = reinterpret_cast<uint32_t *>(pout + out_d + out_l);
         uint32_t *bits = &status_words(h)->bits;
         // The latency walk keeps at most 64 exact ties at the efSearch boundary.  This call synchronises anyway, so instead
@@ -743,7 +764,7 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
                                   coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
                                   coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
                                   reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr,
-                                  query_slots ? reinterpret_cast<const uint8_t *>(pin + in_q + 2 * in_c) : nullptr},
+                                  pick.at(pin + in_q + 2 * in_c)},
                                  call);
             if (rc)
                 return rc;
@@ -764,11 +785,10 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
         (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (query_slots && (rc = stage_in(h, h->fs_qslots, query_slots, in_s))) ||
-        (rc = ivfhnsw_gpu_search_slots_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                                           coarse_ids ? h->s_cd.as<float>() : nullptr, p,
-                                           query_slots ? h->fs_qslots.as<uint8_t>() : nullptr, h->s_dist.as<float>(),
-                                           h->s_lab.as<int64_t>(), nullptr)) ||
+        (pick && (rc = stage_in(h, h->fs_qslots, pick.data(), in_s))) ||
+        (rc = search_pick_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
+                              coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p), h->s_dist.as<float>(),
+                              h->s_lab.as<int64_t>(), nullptr)) ||
         (rc = stage_out(h, distances, h->s_dist, nq * k * sizeof(float))) ||
         (rc = stage_out(h, labels, h->s_lab, nq * k * sizeof(int64_t))))
         return rc;
@@ -779,14 +799,21 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
 int ivfhnsw_gpu_search(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
                        const float *coarse_dists, const ivfhnsw_search_params *p, float *distances, int64_t *labels)
 {
-    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, nullptr, distances, labels);
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{}, distances, labels);
 }
 
 int ivfhnsw_gpu_search_slots(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
                              const float *coarse_dists, const ivfhnsw_search_params *p, const uint8_t *query_slots,
                              float *distances, int64_t *labels)
 {
-    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, query_slots, distances, labels);
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{query_slots, nullptr}, distances, labels);
+}
+
+int ivfhnsw_gpu_search_tags(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                            const float *coarse_dists, const ivfhnsw_search_params *p, const uint16_t *query_tags,
+                            float *distances, int64_t *labels)
+{
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags}, distances, labels);
 }
 
 int ivfhnsw_gpu_search_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,

@@ -521,8 +521,11 @@ struct FilterFill {
 };
 template <class T> struct is_slot_mask : std::false_type {};
 template <> struct is_slot_mask<SlotMask> : std::true_type {};
-// 0 = no filter, 1 = one mask, 2 = a plane per query
-template <class... Mask> constexpr int filter_kind = sizeof...(Mask) == 0 ? 0 : (is_slot_mask<Mask>::value || ...) ? 2 : 1;
+template <class T> struct is_tag_mask : std::false_type {};
+template <> struct is_tag_mask<TagMask> : std::true_type {};
+// 0 = no filter, 1 = one mask, 2 = a plane per query, 3 = a 16-bit tag per row and per query
+template <class... Mask>
+constexpr int filter_kind = sizeof...(Mask) == 0 ? 0 : (is_tag_mask<Mask>::value || ...) ? 3 : (is_slot_mask<Mask>::value || ...) ? 2 : 1;
 
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &) { return nullptr; }
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &, const uint32_t *m) { return m; }
@@ -533,6 +536,20 @@ __device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, 
     fill.keep = plane ? ~0u : 0u;
     fill.all = s == 0xffu ? ~0u : 0u;
     return m.planes + (plane ? (size_t)s * m.stride : (size_t)0);
+}
+// The fourth form (TagMask, scan_dispatch.h): no bit per row but a 16-bit tag, which a lane loads beside the
+// norm code as it loads a mask word (load_norm_filter<3>: the returned pointer is the row tags', read as uint16).  The
+// query's tag goes through readfirstlane into fill.all, and a row passes iff its tag equals that scalar, or the scalar is
+// 0xffff (IVFHNSW_TAG_NONE: every row passes), both wave-uniform operands of one compare (filter_pass<3>).  A handle
+// without tags has no row array and every row counts as 0xffff: keep = 0 then makes every lane read element 0 of the
+// query tags (readable, and ignored), and a tag other than 0xffff gets bit 16 set, which no zero-extended 16-bit load equals.
+__device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, const TagMask &m)
+{
+    const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)m.query_tags[q]);
+    const bool rows = m.row_tags != nullptr;
+    fill.keep = rows ? ~0u : 0u;
+    fill.all = rows || t == 0xffffu ? t : t | 0x10000u;
+    return reinterpret_cast<const uint32_t *>(rows ? m.row_tags : m.query_tags);
 }
 
 } // namespace ivfhnsw_gpu_impl

@@ -67,6 +67,8 @@ struct DeviceSide {
         std::vector<uint32_t> labels;
     };
     std::vector<SlotSet> slots;
+    // set_id_tags: the tag of every label that carries one, installed likewise
+    std::unordered_map<uint32_t, uint16_t> tags;
 };
 std::mutex g_side_mu;
 std::unordered_map<const void *, DeviceSide> g_side;
@@ -114,6 +116,46 @@ void install_id_filter_slots(const void *ix, ivfhnsw_gpu *h, int slot = -1)
             ivfhnsw_gpu_set_filter_slot(h, (unsigned)s, slots[s].labels.size(), slots[s].labels.data(),
                                         slots[s].deny ? IVFHNSW_FILTER_DENY : IVFHNSW_FILTER_ALLOW))
             gpu_fail("ivfhnsw_gpu_set_filter_slot");
+}
+
+// the index's row tags onto its handle, all of them in one call
+void install_id_tags(const void *ix, ivfhnsw_gpu *h)
+{
+    std::vector<uint32_t> labels;
+    std::vector<uint16_t> tags;
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(ix);
+        if (it != g_side.end())
+            for (const auto &lt : it->second.tags) {
+                labels.push_back(lt.first);
+                tags.push_back(lt.second);
+            }
+    }
+    if (!labels.empty() && ivfhnsw_gpu_set_tags(h, labels.size(), labels.data(), tags.data()))
+        gpu_fail("ivfhnsw_gpu_set_tags");
+}
+
+// what search_batch (heap_order 1) and range_search (0) ask of the device, for the _slots and _tags forms alike
+ivfhnsw_search_params per_query_params(const IndexIVF_HNSW *ix, int heap_order)
+{
+    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(ix);
+    ivfhnsw_search_params p;
+    p.nprobe = ix->nprobe;
+    p.max_codes = ix->max_codes;
+    p.efSearch = ix->quantizer->efSearch;
+    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
+    p.heap_order = heap_order;
+    return p;
+}
+
+// the results of the range search that just ran on h
+void fetch_range_results(ivfhnsw_gpu *h, uint64_t total, std::vector<float> &distances, std::vector<long> &labels)
+{
+    distances.resize(total);
+    labels.resize(total);
+    if (ivfhnsw_gpu_range_results(h, 0, total, distances.data(), reinterpret_cast<int64_t *>(labels.data())))
+        gpu_fail("ivfhnsw_gpu_range_results");
 }
 
 } // namespace
@@ -194,13 +236,7 @@ void IndexIVF_HNSW::search_batch_slots(size_t nq, size_t k, const float *x, cons
     if (shards_wanted() > 1)
         throw std::runtime_error("IndexIVF_HNSW::search_batch_slots: IVFHNSW_SHARDS > 1, and sharded handles have no filter slots");
     ensure_device();
-    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
-    ivfhnsw_search_params p;
-    p.nprobe = nprobe;
-    p.max_codes = max_codes;
-    p.efSearch = quantizer->efSearch;
-    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
-    p.heap_order = 1; // as search_batch
+    const ivfhnsw_search_params p = per_query_params(this, 1); // heap order, as search_batch
     if (ivfhnsw_gpu_search_slots(gpu_, nq, k, x, nullptr, nullptr, &p, slots, distances, reinterpret_cast<int64_t *>(labels)))
         gpu_fail("ivfhnsw_gpu_search_slots");
 }
@@ -211,22 +247,73 @@ void IndexIVF_HNSW::range_search_slots(size_t nq, const float *x, const uint8_t 
     if (shards_wanted() > 1)
         throw std::runtime_error("IndexIVF_HNSW::range_search_slots: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
     ensure_device();
-    const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(this);
-    ivfhnsw_search_params p;
-    p.nprobe = nprobe;
-    p.max_codes = max_codes;
-    p.efSearch = quantizer->efSearch;
-    p.do_pruning = grouping && grouping->do_pruning ? 1 : 0;
-    p.heap_order = 0;
+    const ivfhnsw_search_params p = per_query_params(this, 0);
     lims.assign(nq + 1, 0);
     uint64_t total = 0;
     if (ivfhnsw_gpu_range_search_slots(gpu_, nq, x, nullptr, nullptr, &p, slots, radius,
                                        reinterpret_cast<uint64_t *>(lims.data()), &total))
         gpu_fail("ivfhnsw_gpu_range_search_slots");
-    distances.resize(total);
-    labels.resize(total);
-    if (ivfhnsw_gpu_range_results(gpu_, 0, total, distances.data(), reinterpret_cast<int64_t *>(labels.data())))
-        gpu_fail("ivfhnsw_gpu_range_results");
+    fetch_range_results(gpu_, total, distances, labels);
+}
+
+void IndexIVF_HNSW::set_id_tags(size_t n, const idx_t *xids, const uint16_t *tags)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_tags: IVFHNSW_SHARDS > 1, and sharded handles have no row tags");
+    if (n && (!xids || !tags))
+        throw std::runtime_error("IndexIVF_HNSW::set_id_tags: null ids or tags");
+    // an id given two different tags is refused whether or not there is a device copy to refuse it
+    std::unordered_map<uint32_t, uint16_t> given;
+    for (size_t i = 0; i < n; i++)
+        if (!given.emplace(xids[i], tags[i]).second && given[xids[i]] != tags[i])
+            throw std::runtime_error("IndexIVF_HNSW::set_id_tags: id " + std::to_string(xids[i]) + " is given two different tags");
+    if (gpu_ && device_current() && ivfhnsw_gpu_set_tags(gpu_, n, xids, tags)) // otherwise the next search's upload installs them
+        gpu_fail("ivfhnsw_gpu_set_tags");
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    DeviceSide &side = g_side[this];
+    for (const auto &lt : given) {
+        if (lt.second == IVFHNSW_TAG_NONE)
+            side.tags.erase(lt.first);
+        else
+            side.tags[lt.first] = lt.second;
+    }
+}
+
+void IndexIVF_HNSW::clear_id_tags()
+{
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(this);
+        if (it != g_side.end())
+            std::unordered_map<uint32_t, uint16_t>().swap(it->second.tags);
+    }
+    if (gpu_ && shards_wanted() == 1 && ivfhnsw_gpu_clear_tags(gpu_))
+        gpu_fail("ivfhnsw_gpu_clear_tags");
+}
+
+void IndexIVF_HNSW::search_batch_tags(size_t nq, size_t k, const float *x, const uint16_t *tags, float *distances, long *labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::search_batch_tags: IVFHNSW_SHARDS > 1, and sharded handles have no row tags");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 1); // heap order, as search_batch
+    if (ivfhnsw_gpu_search_tags(gpu_, nq, k, x, nullptr, nullptr, &p, tags, distances, reinterpret_cast<int64_t *>(labels)))
+        gpu_fail("ivfhnsw_gpu_search_tags");
+}
+
+void IndexIVF_HNSW::range_search_tags(size_t nq, const float *x, const uint16_t *tags, float radius, std::vector<size_t> &lims,
+                                      std::vector<float> &distances, std::vector<long> &labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::range_search_tags: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 0);
+    lims.assign(nq + 1, 0);
+    uint64_t total = 0;
+    if (ivfhnsw_gpu_range_search_tags(gpu_, nq, x, nullptr, nullptr, &p, tags, radius,
+                                      reinterpret_cast<uint64_t *>(lims.data()), &total))
+        gpu_fail("ivfhnsw_gpu_range_search_tags");
+    fetch_range_results(gpu_, total, distances, labels);
 }
 
 unsigned IndexIVF_HNSW::tables_dirty() const
@@ -476,6 +563,7 @@ void IndexIVF_HNSW::device_upload_common()
     if (world == 1) {
         install_id_filter(this, gpu_); // upload_ivf dropped the handle's
         install_id_filter_slots(this, gpu_);
+        install_id_tags(this, gpu_);
     }
     std::lock_guard<std::mutex> lk(g_side_mu);
     DeviceSide &side = g_side[this];

@@ -446,6 +446,16 @@ struct FilterSlotSets {
 hipError_t launch_filter_mark_slots(hipStream_t s, const uint32_t *ids, uint64_t n_local, const FilterSlotSets &sets,
                                     uint32_t nplanes, unsigned long long *planes, uint64_t stride64,
                                     unsigned long long *counts);
+// Row tags (kernels_filter.hip).  scatter: table[labels[i]] = tags[i], i < n, into a table that spans every
+// label given; *conflict (zeroed here) is non-zero afterwards iff a label was given two different tags.  gather:
+// row_tags[r] = ids[r] < table_n ? table[ids[r]] : 0xffff for r < n_local (n_local = 0: the one element it always has).
+// count: *count (zeroed here) = rows whose tag equals `tag` (equal), or differs from it.
+hipError_t launch_tags_scatter(hipStream_t s, const uint32_t *labels, const uint16_t *tags, size_t n, uint16_t *table,
+                               uint32_t *conflict);
+hipError_t launch_tags_gather(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint16_t *table, uint64_t table_n,
+                              uint16_t *row_tags);
+hipError_t launch_tags_count(hipStream_t s, const uint16_t *row_tags, uint64_t n_local, uint32_t tag, bool equal,
+                             unsigned long long *count);
 // additions to a Grouping index (kernels_add_groups.hip): its codes go in with the append launchers above.
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --

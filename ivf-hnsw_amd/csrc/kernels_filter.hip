@@ -3,6 +3,8 @@
 // tests every local row's id against it and writes the PASS mask the filtered scans read: bit r = row r passes, one
 // __ballot per 64 rows, bits at or beyond n_local zero.  Allow: a row passes iff its id is in the set; deny: iff it is
 // not.  One workgroup per kFilterTileRows rows, one atomic per workgroup for the count of passing rows.
+// Below them the kernels of the row tags: the scatter of (label, tag) pairs into the tag table with its
+// conflict check, the gather of the table into one tag per resident row, and the counting pass.
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 
@@ -99,7 +101,109 @@ __global__ __launch_bounds__(256) void filter_mark_slots_kernel(const uint32_t *
     }
 }
 
+// ---- row tags: a uint16 per label value (the table), gathered into a uint16 per resident row
+
+// table[labels[i]] = tags[i].  The table spans every label given (the host sized it by their maximum).  Two rows of the
+// table share a 32-bit word; a 16-bit store touches its own half only, so threads that write neighbours do not meet.
+__global__ __launch_bounds__(256) void tags_scatter_kernel(const uint32_t *__restrict__ labels, const uint16_t *__restrict__ tags,
+                                                           size_t n, uint16_t *__restrict__ table)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        table[labels[i]] = tags[i];
+}
+
+// ... and the check behind it: a label given two different tags kept one of them, so the other entry does not read back
+__global__ __launch_bounds__(256) void tags_verify_kernel(const uint32_t *__restrict__ labels, const uint16_t *__restrict__ tags,
+                                                          size_t n, const uint16_t *__restrict__ table, uint32_t *__restrict__ conflict)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        bad |= table[labels[i]] != tags[i];
+    if (bad)
+        atomicOr(conflict, 1u);
+}
+
+// row_tags[r] = ids[r] < table_n ? table[ids[r]] : none.  A thread owns one 32-bit word of row_tags, rows 2w and 2w + 1;
+// the last word of an odd n_local is stored as a half, the array ends there.
+__global__ __launch_bounds__(256) void tags_gather_kernel(const uint32_t *__restrict__ ids, uint64_t n_local,
+                                                          const uint16_t *__restrict__ table, uint64_t table_n,
+                                                          uint16_t *__restrict__ row_tags)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x, r = 2 * w;
+    if (r >= n_local)
+        return;
+    const bool two = r + 1 < n_local;
+    const uint32_t i0 = ids[r], i1 = two ? ids[r + 1] : 0u;
+    const uint32_t t0 = i0 < table_n ? table[i0] : 0xffffu;
+    const uint32_t t1 = two && i1 < table_n ? table[i1] : 0xffffu;
+    if (two)
+        reinterpret_cast<uint32_t *>(row_tags)[w] = t0 | (t1 << 16);
+    else
+        row_tags[r] = (uint16_t)t0;
+}
+
+// *count += rows whose tag equals `tag` (equal) or differs from it (!equal): a ballot per wavefront, one atomic per workgroup
+__global__ __launch_bounds__(256) void tags_count_kernel(const uint16_t *__restrict__ row_tags, uint64_t n_local, uint32_t tag,
+                                                         int equal, unsigned long long *__restrict__ count)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    uint32_t c = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 256; r0 < n_local; r0 += stride) { // workgroup-uniform bound: every lane ballots
+        const uint64_t r = r0 + threadIdx.x;
+        const bool hit = r < n_local && ((row_tags[r] == tag) == (equal != 0));
+        c += (uint32_t)__popcll(__ballot(hit));
+    }
+    if (lane == 0)
+        s_cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (t)
+            atomicAdd(count, (unsigned long long)t);
+    }
+}
+
 } // namespace
+
+static unsigned tags_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
+
+hipError_t launch_tags_scatter(hipStream_t s, const uint32_t *labels, const uint16_t *tags, size_t n, uint16_t *table,
+                               uint32_t *conflict)
+{
+    if (hipError_t e = hipMemsetAsync(conflict, 0, sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(tags_scatter_kernel, dim3(tags_grid(n)), dim3(256), 0, s, labels, tags, n, table);
+    hipLaunchKernelGGL(tags_verify_kernel, dim3(tags_grid(n)), dim3(256), 0, s, labels, tags, n, table, conflict);
+    return hipGetLastError();
+}
+
+hipError_t launch_tags_gather(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint16_t *table, uint64_t table_n,
+                              uint16_t *row_tags)
+{
+    if (n_local == 0) // the one element the array always has
+        return hipMemsetAsync(row_tags, 0xff, sizeof(uint16_t), s);
+    const uint64_t words = (n_local + 1) / 2;
+    hipLaunchKernelGGL(tags_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, ids, n_local, table, table_n,
+                       row_tags);
+    return hipGetLastError();
+}
+
+hipError_t launch_tags_count(hipStream_t s, const uint16_t *row_tags, uint64_t n_local, uint32_t tag, bool equal,
+                             unsigned long long *count)
+{
+    if (hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), s); e != hipSuccess)
+        return e;
+    if (n_local == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(tags_count_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, row_tags, n_local, tag, equal ? 1 : 0, count);
+    return hipGetLastError();
+}
 
 hipError_t launch_filter_mark(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *bits, uint32_t max_label,
                               int deny, unsigned long long *mask, unsigned long long *count)

@@ -1,8 +1,8 @@
 // How a scan launcher turns two run-time facts -- the code size and how the call is filtered (not at all, by the handle's
-// label filter, by a filter slot per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
+// label filter, by a filter slot per query, by a row tag per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
 //
 //     by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {          // decltype(cs)::value: 4, 8, 16, 32, or 0 = run-time form
-//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, or a SlotMask
+//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, a SlotMask or a TagMask
 //             launch kernel<decltype(cs)::value, ..., decltype(m)...> with the arguments (..., m...)
 //         });
 //     });
@@ -47,21 +47,34 @@ struct SlotMask {
     const uint8_t *slots;
 };
 
-// What a scan launcher is told about the filter of its call: nothing, the pass mask of the handle's filter, or filter
-// slots per query (slots.slots non-null).  A bare mask pointer converts, so a caller with one filter passes it as before.
+// The fourth form: disjoint sets as one 16-bit tag per row.  row_tags: the tag of every local row;
+// query_tags: one tag per query of the launch.  A row passes a query iff the two are equal; a query tagged 0xffff
+// (IVFHNSW_TAG_NONE) passes every row.  A handle without tags has no row array: row_tags is then null and every row
+// reads as 0xffff (filter_mask, device_common.h, points such a launch at one readable element instead).
+struct TagMask {
+    const uint16_t *row_tags;
+    const uint16_t *query_tags;
+};
+
+// What a scan launcher is told about the filter of its call: nothing, the pass mask of the handle's filter, filter
+// slots per query (slots.slots non-null) or a tag per query (tags.query_tags non-null).  A bare mask pointer converts, so
+// a caller with one filter passes it as before.
 struct ScanFilter {
     const uint32_t *fmask = nullptr;
     SlotMask slots{nullptr, 0, 0, nullptr};
+    TagMask tags{nullptr, nullptr};
     ScanFilter() = default;
     ScanFilter(const uint32_t *m) : fmask(m) {}
     ScanFilter(std::nullptr_t) {}
     ScanFilter(const SlotMask &s) : slots(s) {}
+    ScanFilter(const TagMask &t) : tags(t) {}
     bool by_slot() const { return slots.slots != nullptr; }
-    bool any() const { return fmask || by_slot(); }
-    // the name a launcher reports: the plain kernel's, "+filter" or "+slots" behind it
-    const char *name(const char *plain, const char *filtered, const char *slotted) const
+    bool by_tag() const { return tags.query_tags != nullptr; }
+    bool any() const { return fmask || by_slot() || by_tag(); }
+    // the name a launcher reports: the plain kernel's, "+filter", "+slots" or "+tags" behind it
+    const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged) const
     {
-        return by_slot() ? slotted : fmask ? filtered : plain;
+        return by_tag() ? tagged : by_slot() ? slotted : fmask ? filtered : plain;
     }
     // the queries [q0, ...) of the same call
     ScanFilter from(size_t q0) const
@@ -69,11 +82,16 @@ struct ScanFilter {
         ScanFilter r = *this;
         if (r.by_slot())
             r.slots.slots += q0;
+        if (r.by_tag())
+            r.tags.query_tags += q0;
         return r;
     }
 };
 
-// f(slots) with filter slots, else as above
-template <class F> auto with_mask(const ScanFilter &flt, F &&f) { return flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f); }
+// f(tags) with a tag per query, f(slots) with filter slots, else as above
+template <class F> auto with_mask(const ScanFilter &flt, F &&f)
+{
+    return flt.by_tag() ? f(flt.tags) : flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f);
+}
 
 } // namespace ivfhnsw_gpu_impl

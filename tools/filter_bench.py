@@ -17,8 +17,18 @@ With --slots, filter slots (ivfhnsw_gpu_search_slots) instead, o
   4. set_filter_slot_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev with no filter, with the single filter
      installed, and with 1, 8 and 32 slots installed (wall ms, each twice; what the append costs beyond the unfiltered one
      is the re-mark).
+With --tags, row tags (ivfhnsw_gpu_search_tags), on the same corpus and ONE handle (row r carries tag
+r % 1024, so tags and the slots' sets below partition the same rows):
+  5. --reps (>= 5) alternating repetitions of: (a) unfiltered; (b) _slots, the rows dealt into 32 slots (row r in slot
+     r % 32) and the queries dealt over them; (c) _tags, the same partition as 32 tags (a query of slot s names tag s of
+     a second table, r % 32); (d) _tags with 1 024 tags, the queries dealt over them.  Step and scan time as in 3.
+  6. the loop (d) replaces: per tag set_filter_dev(rows of the tag) + search_dev of that tag's queries, for a sample of
+     --loop-tags tags, wall ms per tag, extrapolated to the 1 024 tags of one batch.
+  7. set_tags_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev without and with the tag table (wall ms, each
+     twice: what the append costs beyond the untagged one is the gather).
 usage: python tools/filter_bench.py [--workload NAME] [--sizes 1000,10000000,500000000] [--fractions 0.5,0.1,0.01]
-       python tools/filter_bench.py --slots [--reps 5] [--append 10000000]"""
+       python tools/filter_bench.py --slots [--reps 5] [--append 10000000]
+       python tools/filter_bench.py --tags [--reps 5] [--append 10000000] [--loop-tags 8]"""
 import argparse
 import json
 import os
@@ -144,12 +154,160 @@ def slots_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, labels_of, out):
     out["append"] = appends
 
 
+def tags_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out):
+    n = c.n_total
+    ids = torch.arange(n, device=dev, dtype=torch.int64)
+
+    def install(modulus):
+        lab = ids.to(torch.int32)
+        tg = (ids % modulus).to(torch.int16)
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        g.set_tags_dev(n, lab, tg)
+        ms = (time.perf_counter() - t) * 1e3
+        del lab, tg
+        return ms
+
+    # the slots' partition: row r in slot r % 32
+    for s in range(pkg.FILTER_SLOTS):
+        lab = (torch.arange(n // 32 + (1 if s < n % 32 else 0), device=dev, dtype=torch.int64) * 32 + s).to(torch.int32)
+        torch.cuda.synchronize(dev)
+        g.set_filter_slot_dev(s, lab.numel(), lab)
+        del lab
+    out["memory_GB_with_32_slots"] = g.memory_bytes() / 1e9
+    qslots = (torch.arange(nq, device=dev) % 32).to(torch.uint8)
+    qtags32 = (torch.arange(nq, device=dev) % 32).to(torch.int16)
+    qtags1k = (torch.arange(nq, device=dev) % 1024).to(torch.int16)
+    torch.cuda.synchronize(dev)
+
+    def step(form):
+        kind, pick = form
+        if kind == "plain":
+            g.search_dev(nq, 1, q, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        elif kind == "slots":
+            g.search_slots_dev(nq, 1, q, pick, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        else:
+            g.search_tags_dev(nq, 1, q, pick, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+
+    def measure(form, steps=10):
+        for _ in range(5):
+            step(form)
+        g.sync()
+        t = time.perf_counter()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        g.set_profiling(2)
+        g.reset_stage_ms()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        scan = g.stage_ms()["scan"][0] / steps
+        g.set_profiling(0)
+        return wall, scan, g.last_scan_kernel()
+
+    runs = {}
+
+    def series(name, form):
+        wall, scan, kernel = measure(form)
+        r = runs.setdefault(name, {"step_ms": [], "scan_ms": []})
+        r["step_ms"].append(wall)
+        r["scan_ms"].append(scan)
+        r["kernel"] = kernel
+
+    # 32 tags and 1 024 tags are two tables: each is measured with its own installed, alternating with (a) and (b)
+    out["set_tags_dev_all_rows_ms"] = []
+    for modulus, name, qt in ((32, "c tags, 32 dealt", qtags32), (1024, "d tags, 1024 dealt", qtags1k)):
+        out["set_tags_dev_all_rows_ms"].append(install(modulus))
+        for _ in range(max(5, args.reps)):
+            series("a unfiltered (beside %d tags)" % modulus, ("plain", None))
+            series("b slots, 32 dealt (beside %d tags)" % modulus, ("slots", qslots))
+            series(name, ("tags", qt))
+    out["memory_GB_with_32_slots_and_tags"] = g.memory_bytes() / 1e9
+    for name, r in runs.items():
+        for key in ("step_ms", "scan_ms"):
+            v = r[key]
+            r[key + "_min_mean_max"] = [min(v), sum(v) / len(v), max(v)]
+        log("[filter_bench] %-36s step %.4f ms, scan %.4f ms  (%s)" %
+            (name, r["step_ms_min_mean_max"][1], r["scan_ms_min_mean_max"][1], r["kernel"]))
+    out["tags_search"] = runs
+    b, cc = runs["b slots, 32 dealt (beside 32 tags)"], runs["c tags, 32 dealt"]
+    out["c_minus_b_scan_ms"] = cc["scan_ms_min_mean_max"][1] - b["scan_ms_min_mean_max"][1]
+    out["b_scan_spread_ms"] = b["scan_ms_min_mean_max"][2] - b["scan_ms_min_mean_max"][0]
+    out["c_minus_b_step_ms"] = cc["step_ms_min_mean_max"][1] - b["step_ms_min_mean_max"][1]
+    out["b_step_spread_ms"] = b["step_ms_min_mean_max"][2] - b["step_ms_min_mean_max"][0]
+
+    # 6. the loop one search_tags call with 1 024 tags replaces
+    g.clear_filter_slot()
+    per_tag_q = max(1, nq // 1024)
+    loop = []
+    for t_ in range(args.loop_tags):
+        lab = (torch.arange(n // 1024 + (1 if t_ < n % 1024 else 0), device=dev, dtype=torch.int64) * 1024 + t_).to(torch.int32)
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        g.set_filter_dev(lab.numel(), lab)
+        g.search_dev(per_tag_q, 1, q[t_ * per_tag_q:(t_ + 1) * per_tag_q], dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        g.sync()
+        loop.append((time.perf_counter() - t) * 1e3)
+        del lab
+    g.clear_filter()
+    out["loop_ms_per_tag"] = loop
+    out["loop_ms_1024_tags_extrapolated"] = sum(loop[1:]) / max(1, len(loop) - 1) * 1024  # the first call allocates
+    log("[filter_bench] set_filter_dev + search_dev per tag: %s ms; x 1024 = %.0f ms against one search_tags step of %.3f ms"
+        % (", ".join("%.2f" % v for v in loop), out["loop_ms_1024_tags_extrapolated"],
+           runs["d tags, 1024 dealt"]["step_ms_min_mean_max"][1]))
+
+    # 7. install and re-derivation
+    n10m = min(10 ** 7, n)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(31)
+    lab = (torch.arange(n10m, device=dev, dtype=torch.int64) * max(1, n // n10m))[torch.randperm(n10m, device=dev, generator=gen)]
+    lab = lab.to(torch.int32)  # the same bits as uint32: every K-th id, in random order
+    tg = (torch.arange(n10m, device=dev) % 1024).to(torch.int16)
+    torch.cuda.synchronize(dev)
+    t = time.perf_counter()
+    g.set_tags_dev(n10m, lab, tg)
+    out["set_tags_dev_10M_ms"] = (time.perf_counter() - t) * 1e3
+    log("[filter_bench] set_tags_dev of %d labels on %d rows: %.1f ms" % (n10m, n, out["set_tags_dev_10M_ms"]))
+    del lab, tg
+    na = args.append
+    li = torch.randint(0, c.nc, (na,), device=dev, generator=gen, dtype=torch.int32)
+    codes = torch.randint(0, 256, (na, c.M), device=dev, generator=gen, dtype=torch.uint8)
+    ncodes = torch.randint(0, 255, (na,), device=dev, generator=gen, dtype=torch.uint8)
+    torch.cuda.synchronize(dev)
+    appends = []
+    first_id = n
+
+    def timed_append(what):
+        nonlocal first_id
+        new = (torch.arange(na, device=dev, dtype=torch.int64) + first_id).to(torch.int32)
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        g.append_ivf_dev(na, li, new, codes, ncodes)
+        g.sync()
+        ms = (time.perf_counter() - t) * 1e3
+        first_id += na
+        appends.append({"installed": what, "append_ms": ms})
+        log("[filter_bench] append_ivf_dev of %d codes, %s: %.1f ms" % (na, what, ms))
+
+    timed_append("the tag table (warm-up: allocations)")
+    timed_append("the tag table")
+    timed_append("the tag table")
+    g.clear_tags()
+    timed_append("nothing")
+    timed_append("nothing")
+    out["append"] = appends
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="synthetic-1B-pq16-nc993127-nprobe32")
     ap.add_argument("--sizes", default="1000,10000000,500000000")
     ap.add_argument("--fractions", default="0.5,0.1,0.01")
     ap.add_argument("--slots", action="store_true")
+    ap.add_argument("--tags", action="store_true")
+    ap.add_argument("--loop-tags", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--append", type=int, default=10 ** 7)
     args = ap.parse_args()
@@ -199,6 +357,11 @@ def main():
         assert total == c.n_total and passing == (total - n if deny else n), (mode, passing, total, n)
         return ms, passing
 
+    if args.tags:
+        tags_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out)
+        g.close()
+        print(json.dumps(out))
+        return
     if args.slots:
         slots_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, labels_of, out)
         g.close()

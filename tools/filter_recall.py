@@ -10,7 +10,10 @@ share of the true 10 nearest allowed rows among the IVF search's 10 results.
 With --slots: 32 seeded random allow sets, pass fractions cycling 1/2, 1/8 and 1/32, are installed as
 filter slots and as base filter slots; the queries are spread over the 32 slots and NONE; ONE search_slots call is scored
 against ONE exact_search_slots call, Recall@1 and Recall@10 per pass fraction.
-usage: python tools/filter_recall.py [--seed 77] [--slots] [--out result.json]"""
+With --tags: every row gets one of 1 024 tags -- tag t < 4 holds 1/8 of the rows each, the other half is
+spread evenly over the tags 4..1023 -- and the queries are dealt over a sample of tags and NONE; ONE search_tags call is
+scored against the truth of a tagged search, the per-tag loop of set_base_filter + exact_search.
+usage: python tools/filter_recall.py [--seed 77] [--slots | --tags] [--out result.json]"""
 import argparse
 import json
 import os
@@ -127,15 +130,77 @@ def slots_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
             "per_slot": per_slot}
 
 
+TAG_NONE = 0xffff
+TAG_SAMPLE = (0, 1, 2, 3, 4, 5, 100, 511, 1023, TAG_NONE)  # four large tags, five small ones, no tag
+
+
+def tag_assignment(n, seed):
+    """uint16 [n]: the tag of row (= id) i.  Tags 0..3 hold n / 8 rows each, tags 4..1023 share the other half."""
+    rng = np.random.default_rng(seed + 3)
+    tags = np.empty(n, np.uint16)
+    order = rng.permutation(n)
+    big = n // 8
+    for t in range(4):
+        tags[order[t * big:(t + 1) * big]] = t
+    rest = order[4 * big:]
+    tags[rest] = 4 + np.arange(len(rest)) % 1020
+    return tags
+
+
+def tags_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
+    """Recall of one search_tags call against the per-tag loop of set_base_filter + exact_search, per tag of TAG_SAMPLE."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    tags = tag_assignment(n, seed)
+    g.set_tags(np.arange(n, dtype=np.uint32), tags)
+    assert g.tags_info() == (n, n, n)
+    qt = np.array([TAG_SAMPLE[i % len(TAG_SAMPLE)] for i in range(nq)], np.uint16)
+    truth = np.empty((nq, 10), np.int64)
+    for t in TAG_SAMPLE:
+        mine = np.flatnonzero(qt == t)
+        if t == TAG_NONE:
+            g.clear_base_filter()
+        else:
+            rows = np.flatnonzero(tags == t).astype(np.uint32)
+            assert g.tag_rows(t) == rows.size
+            g.set_base_filter(rows)
+        truth[mine] = g.exact_search(q8[mine], 10)[1]
+    g.clear_base_filter()
+    rows_out = []
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_tags(qf, 10, qt, nprobe, max_codes, efSearch=ef)
+        assert g.last_scan_kernel().endswith("+tags")
+        for name, sel in (("1/8 (tags 0..3)", qt < 4), ("~1/2040 (small tags)", (qt >= 4) & (qt != TAG_NONE)),
+                          ("1 (no tag)", qt == TAG_NONE)):
+            idx = np.flatnonzero(sel)
+            r1, r10 = recall_pair(lab[idx], truth[idx])
+            rows_out.append({"pass_fraction": name, "queries": int(idx.size), "nprobe": nprobe, "max_codes": max_codes,
+                             "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] tags, %s (%d queries), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, idx.size, nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "tags": 1024, "tags_recall": rows_out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
+    ap.add_argument("--tags", action="store_true", help="one search_tags call against the per-tag base-filter loop")
     ap.add_argument("--slots", action="store_true", help="one search_slots call against one exact_search_slots call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
-    if args.slots:
+    if args.tags:
+        out = tags_recall(pkg, args.seed)
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    elif args.slots:
         out = slots_recall(pkg, args.seed)
         out = {k: v for k, v in out.items() if k not in ("truth", "query_slots", "sets", "per_slot")}
         out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
