@@ -469,7 +469,6 @@ try {
             return (e && atoi(e) == 0) ? 0 : 1;
         }();
         h->gr.merge_admissions = merge;
-        h->gr.skip_padding = 1;
     }
     {
         // IVFHNSW_WALK_LATE_VISIT: 1 always, 0 never, unset = where it pays -- graphs whose ids need more than 8 tag

@@ -152,8 +152,9 @@ struct GraphTables {
     // NULL until ivfhnsw_gpu_prepare_latency builds it.
     const float *fat;
     int visited_clean;    // walk (set by its launcher): the global visited bitmaps are zero on entry and left zero
-    int skip_padding;     // walk: the filter skips the arithmetic of rows beyond the link count (always on since round 3)
-    int merge_admissions; // walk: insert a pass's admitted rows in one step (A/B knob IVFHNSW_WALK_MERGE=0)
+    // walk: insert a pass's admitted rows in one step (A/B knob IVFHNSW_WALK_MERGE=0); the generic form reads it, the
+    // shaped forms are picked by it (hnsw_walk_kernel's MERGE)
+    int merge_admissions;
     int links_unique;     // no id twice in a link list: survivors of the filter may enter the visited set late
 };
 

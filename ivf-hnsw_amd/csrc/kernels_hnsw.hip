@@ -26,10 +26,12 @@
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 #include "walk_set.h"
+#include "walk_shape.h"
 
 #include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace ivfhnsw_gpu_impl {
 
@@ -206,24 +208,63 @@ __device__ __forceinline__ unsigned long long walk_stamp()
 // compiled into them it cost 17 % of the walk (1.365 -> 1.60 ms per 10 k queries, same box) in registers and scratch.
 // redo_hdr: [0] number of listed queries, [1] the redo launch's own query counter (both zeroed with next_query); redo_list:
 // the queries.
-template <int NCH, int MINW, int TAGW, int FMODE, bool STAMPS = false, bool SPILL = false>
-__global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, const float *__restrict__ xq, int nq, int nprobe,
-                                                       int ef, uint32_t *__restrict__ coarse_ids,
-                                                       float *__restrict__ coarse_dists,
-                                                       uint32_t *__restrict__ visited, size_t vwords,
-                                                       uint32_t *__restrict__ status, uint32_t *__restrict__ next_query,
-                                                       uint32_t *__restrict__ redo_hdr, uint32_t *__restrict__ redo_list,
-                                                       uint32_t *__restrict__ tail_bitmaps = nullptr, // SPILL: [grid][vwords]
-                                                       unsigned long long *__restrict__ stamp_out = nullptr)
+
+// WalkArgs: the kernel's one argument, so that the kernarg segment IS this struct (late_kernarg).
+struct WalkArgs {
+    GraphTables g;
+    const float *xq;
+    int nq, nprobe, ef;
+    uint32_t *coarse_ids;
+    float *coarse_dists;
+    uint32_t *visited;
+    size_t vwords;
+    uint32_t *status, *next_query, *redo_hdr, *redo_list;
+    uint32_t *tail_bitmaps;        // SPILL: [grid][vwords]
+    unsigned long long *stamp_out; // STAMPS
+};
+
+// The kernel's argument read again from the kernarg segment, through an empty asm the compiler cannot look through: a
+// field loaded through this pointer is loaded where the load is written (a scalar load from constant memory), not in the
+// kernel's prologue, and is dead after its use -- the way to keep an argument that is needed once per query out of the
+// scalar registers (and out of the spill lanes) while sixty expansions run.
+template <class T> __device__ __forceinline__ const __attribute__((address_space(4))) T *late_kernarg()
 {
+    auto p = (const __attribute__((address_space(4))) T *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+// D, MAXM, MERGE: the SHAPE as constants (neighbour-row forms only; the rule is walk_shape_for, walk_shape.h).  D != 0
+// stands for GraphTables::d, MAXM != 0 for GraphTables::maxM with nb_rows = MAXM rounded up to 32, and MERGE for
+// GraphTables::merge_admissions; 0 / 0 is the generic form, which reads all of them at run time.  With both set the
+// float-row step is l2_ref_order_oct_regs<D / 8> alone, record addresses are shifts, and the loop over a query's
+// expansions is peeled by phase (see `expand` below).
+template <int NCH, int MINW, int TAGW, int FMODE, bool STAMPS = false, bool SPILL = false, int D = 0, int MAXM = 0,
+          bool MERGE = true>
+__global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
+{
+    constexpr bool SHAPED = D != 0 && MAXM != 0;
+    const GraphTables &g = a.g;
+    const int ef = a.ef;
+    uint32_t *__restrict__ const visited = a.visited;
+    const size_t vwords = a.vwords;
+    // What only a query's prologue and epilogue read.  The generic form takes them from the arguments, as before; in the
+    // shaped forms they are read where they are used, so none of them holds a scalar register across the expansions.
+#define WALK_COLD(f) (SHAPED ? late_kernarg<WalkArgs>()->f : a.f)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *s_q = reinterpret_cast<float *>(smem);
+    static_assert(!SHAPED || (FMODE >= 2 && !SPILL && MINW <= 4 && D % 16 == 0 && D <= 128 && MAXM <= 64),
+                  "shape constants go with the neighbour-row forms");
+    static_assert(SHAPED || MERGE, "the generic form reads merge_admissions at run time");
+    const int dim = D ? D : g.d;
+    const int maxm = MAXM ? MAXM : g.maxM;
+    const int nbr_rows = MAXM ? (MAXM + 31) / 32 * 32 : g.nb_rows;
     // gather form of the filter only: the query in byte-row units, (q - q_lo) / q_step
-    float *s_qp = s_q + g.d;
-    const int dp = FMODE == 1 ? g.d : 0;
+    float *s_qp = s_q + dim;
+    const int dp = FMODE == 1 ? dim : 0;
     // neighbour-row form: the same in 1/256 steps, four byte planes of 32 words (hi, lo, XL, XH)
     uint32_t *s_q8 = reinterpret_cast<uint32_t *>(s_qp + dp);
-    unsigned long long *tail = reinterpret_cast<unsigned long long *>(smem + (size_t)(g.d + dp) * sizeof(float) + 512);
+    unsigned long long *tail = reinterpret_cast<unsigned long long *>(smem + (size_t)(dim + dp) * sizeof(float) + 512);
     constexpr int NB = vis_buckets(MINW, TAGW);
     unsigned long long st_acc[9] = {0, 0, 0, 0, 0, 0}, st_t = 0;
     // the tail doubles as the merge buffer of a pass's admissions (ef + 8 entries; only used while the tail is empty)
@@ -234,7 +275,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
     const int lane = threadIdx.x;
     // the row of a 32-row batch whose bound this lane evaluates in the filter (oct_sum4's layout)
     const int judged_row = 8 * (((lane >> 2) & 1) * 2 + (lane & 1)) + (lane >> 3);
-    const bool merge_on = g.merge_admissions != 0;
+    const bool merge_on = SHAPED ? MERGE : g.merge_admissions != 0;
     constexpr bool prefilter = FMODE != 0;
     constexpr bool inline_rows = FMODE >= 2;
     // The rows' squared norms from a table built at upload (one more dword load per expansion) instead of sixteen
@@ -253,7 +294,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
     auto dec_id = [](uint32_t e) { return CK ? e >> 7 : e; };
     uint32_t *bm = visited + (size_t)blockIdx.x * vwords;
     TailSpill spill;
-    spill.bm = SPILL ? tail_bitmaps + (size_t)blockIdx.x * vwords : nullptr;
+    spill.bm = SPILL ? a.tail_bitmaps + (size_t)blockIdx.x * vwords : nullptr;
     spill.hi = -1;
     spill.count = 0;
     // The bitmap must be clean before a query uses it.  With the LDS set it is only the overflow store (rarely touched):
@@ -268,15 +309,15 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
         if constexpr (SPILL) {
             // the queries the fast forms could not finish
             if (lane == 0) {
-                const uint32_t i = atomicAdd(&redo_hdr[1], 1u);
-                q = i < redo_hdr[0] ? (int)redo_list[i] : nq;
+                const uint32_t i = atomicAdd(&a.redo_hdr[1], 1u);
+                q = i < a.redo_hdr[0] ? (int)a.redo_list[i] : a.nq;
             }
         } else {
             if (lane == 0)
-                q = (int)atomicAdd(next_query, 1u);
+                q = (int)atomicAdd(WALK_COLD(next_query), 1u);
         }
         q = __builtin_amdgcn_readfirstlane(q);
-        if (q >= nq)
+        if (q >= WALK_COLD(nq))
             break;
         redo_ran = true;
         if (STAMPS)
@@ -295,11 +336,11 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                 vt[w] = 0ull;
         __syncthreads(); // the previous query's readers of s_q are done
         float qp_sq = 0.f;
-        for (int i = lane; i < g.d; i += 64) {
-            const float v = xq[(size_t)q * g.d + i];
+        for (int i = lane; i < dim; i += 64) {
+            const float v = WALK_COLD(xq)[(size_t)q * dim + i];
             s_q[i] = v;
             if (prefilter) {
-                const float vp = __fdiv_rn(__fsub_rn(v, g.q_lo), g.q_step);
+                const float vp = __fdiv_rn(__fsub_rn(v, WALK_COLD(g.q_lo)), g.q_step);
                 if (!inline_rows)
                     s_qp[i] = vp;
                 qp_sq = fmaf(vp, vp, qp_sq);
@@ -314,7 +355,10 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
         if constexpr (QREG) {
 #pragma unroll
             for (int i = 0; i < 16; i++)
-                q_reg[i] = (g.d == 128 || g.d == 96) && 8 * i < g.d ? s_q[8 * i + (lane & 7)] : 0.f;
+                if constexpr (D != 0)
+                    q_reg[i] = 8 * i < D ? s_q[8 * i + (lane & 7)] : 0.f;
+                else
+                    q_reg[i] = (g.d == 128 || g.d == 96) && 8 * i < g.d ? s_q[8 * i + (lane & 7)] : 0.f;
         }
         // slack of the rejection test in byte-row units: quantisation error of the worst row, plus what the
         // rounding of s_qp can move a distance by (<= 2^-22 ||q'||; 2^-18 leaves a factor 16)
@@ -328,7 +372,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1)
                 qp_sq += __shfl_xor(qp_sq, off, 64);
-            pf_slack = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(g.q_errc + 3.9e-6f * sqrtf(qp_sq))));
+            pf_slack = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(WALK_COLD(g.q_errc) + 3.9e-6f * sqrtf(qp_sq))));
             if (inline_rows) {
                 // The integer form of the filter.  q' = q_in + q_out: q_in is q' clamped to the byte range and
                 // rounded to 1/256 steps, Q = 256 * hi + lo (two byte planes in LDS); q_out is what the clamp cut
@@ -346,7 +390,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
 #pragma unroll
                     for (int b = 0; b < 4; b++) {
                         const int comp = 4 * lane + b; // rows are zero beyond d: so is the query
-                        const float vp = comp < g.d ? __fdiv_rn(__fsub_rn(s_q[comp], g.q_lo), g.q_step) : 0.f;
+                        const float vp = comp < dim ? __fdiv_rn(__fsub_rn(s_q[comp], WALK_COLD(g.q_lo)), g.q_step) : 0.f;
                         const float fh = fminf(255.f, fmaxf(0.f, floorf(vp))); // NaN -> 0, and the slack turns NaN: no rejections
                         const float fl = fminf(255.f, fmaxf(0.f, rintf((vp - fh) * 256.f)));
                         const float qin = fh + fl * 0.00390625f;
@@ -410,11 +454,12 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
         uint32_t tail_db = 0; // SPILL: that distance's bits
         {
             // hnswalg.cpp:56-62: seed with the enter point
-            const float d0 = l2_ref_order_quad(g.vectors + (size_t)g.enterpoint * g.d, s_q, g.d, lane & 3);
+            const uint32_t ep = WALK_COLD(g.enterpoint);
+            const float d0 = l2_ref_order_quad(g.vectors + (size_t)ep * dim, s_q, dim, lane & 3);
             bool ub = false;
             if (lane == 0) {
-                R.r[0] = mk_key(d0, enc_id(g.enterpoint, CK ? (uint32_t)g.counts[g.enterpoint] : 0u));
-                (void)visit_test_and_set<TAGW, NB>(g.enterpoint, vt, bm, ub);
+                R.r[0] = mk_key(d0, enc_id(ep, CK ? (uint32_t)WALK_COLD(g.counts)[ep] : 0u));
+                (void)visit_test_and_set<TAGW, NB>(ep, vt, bm, ub);
             }
             __syncthreads();
         }
@@ -428,9 +473,17 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
             st_t = t;
         }
 
-        for (;;) {
+        // One expansion; false = the walk of this query is over.  PHASE 0 is the whole walk of the generic form.  The
+        // shaped forms peel the loop: the set fills during a query's first three or four expansions and never
+        // shrinks, so PHASE 1 (n < ef on entry: no filter yet) runs until n == ef and PHASE 2 runs the rest with
+        // n == ef, filter_now, filter_first and `full` as constants -- it keeps only the late-entry membership test and
+        // drops n++, the n < ef arms and the unfiltered path.  Same statements, same order, same ties.
+        auto expand = [&](auto phase_c) __attribute__((always_inline)) -> bool {
+            constexpr int PHASE = decltype(phase_c)::value;
+            constexpr bool STEADY = PHASE == 2;
+            auto set_n = [&] { return STEADY ? ef : n; }; // entries in R
             // ---- candidateSet.top(): first unexpanded entry of R, ties -> largest id; tail joins at dist == max
-            const int first = R.first_unexpanded(n, lane);
+            const int first = R.first_unexpanded(set_n(), lane);
             int pick = -1;      // index in R, or
             int pick_tail = -1; // index in tail
             uint32_t pick_id = 0;
@@ -441,11 +494,11 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                 // can a larger id with the same distance exist (the full search is the rare path)
                 pick = first;
                 pick_id = key_id(kfirst);
-                if (first + 1 < n && key_dist_bits(R.get(first + 1)) == db) {
-                    pick = R.last_unexpanded_with(db, first, n, lane);
+                if (first + 1 < set_n() && key_dist_bits(R.get(first + 1)) == db) {
+                    pick = R.last_unexpanded_with(db, first, set_n(), lane);
                     pick_id = key_id(R.get(pick));
                 }
-                if (ntail > 0 && db == key_dist_bits(R.get(n - 1))) {
+                if (ntail > 0 && db == key_dist_bits(R.get(set_n() - 1))) {
                     // tail entries share this distance; the larger id pops first
                     if (SPILL && spill.count > 0) {
                         const uint32_t sid = spill.peek_max(lane);
@@ -477,7 +530,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                         pick_tail = t;
                     }
             } else {
-                break; // candidateSet exhausted (hnswalg.cpp:64) or only entries beyond lowerBound left (:67)
+                return false; // candidateSet exhausted (hnswalg.cpp:64) or only entries beyond lowerBound left (:67)
             }
             if (pick >= 0) {
                 R.mark_expanded(pick, lane);
@@ -504,40 +557,40 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
             uint32_t nb = 0, nb_enc = 0; // neighbour id, and the "id" its key will carry
             if constexpr (CK) {
                 cnt = (int)(pick_id & 127u); // scalar: known before anything of the record is read
-                if (lane < g.maxM) {
-                    const uint32_t raw = g.links_c[(size_t)node * g.maxM + lane];
+                if (lane < maxm) {
+                    const uint32_t raw = g.links_c[(size_t)node * maxm + lane];
                     nb = raw & 0xffffffu;
                     nb_enc = (nb << 7) | (raw >> 24);
                 }
             } else {
                 cnt = g.counts[node];
-                if (lane < g.maxM)
-                    nb = g.links[(size_t)node * g.maxM + lane]; // issued together with the count
+                if (lane < maxm)
+                    nb = g.links[(size_t)node * maxm + lane]; // issued together with the count
                 nb_enc = nb;
             }
             // neighbour byte rows of this node (exact rejection filter, below): rows 8i + (lane >> 3), 16-byte
             // chunk lane & 7 -- four 1 KiB wave reads, in flight together with the link list
-            const bool filter_now = prefilter && n == ef;
+            const bool filter_now = PHASE == 0 ? prefilter && n == ef : prefilter && STEADY;
             uint4 nw[4] = {};
             uint32_t row_rr = 0; // sum of bytes^2 of the row this lane will judge (row 8 * (2 bit2 + bit0) + group)
             if (filter_now && inline_rows) {
                 if constexpr (CK) {
                     // rows below the count only: a lane whose row is padding re-reads the last real row's chunk (same
                     // cache lines, no branch; nobody reads its verdict), an 8-row group wholly beyond it is skipped
-                    const uint4 *nbr = reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * g.nb_rows * 128) + (lane & 7);
+                    const uint4 *nbr = reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * nbr_rows * 128) + (lane & 7);
                     const int last = max(cnt - 1, 0);
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                         if (8 * i < cnt)
                             nw[i] = nbr[min(8 * i + (lane >> 3), last) * 8];
                 } else {
-                    const uint4 *nbr = reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * g.nb_rows * 128) + lane;
+                    const uint4 *nbr = reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * nbr_rows * 128) + lane;
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                         nw[i] = nbr[i * 64];
                 }
                 if constexpr (ROWNORMS)
-                    row_rr = g.nbnorms[(size_t)node * g.nb_rows + judged_row];
+                    row_rr = g.nbnorms[(size_t)node * nbr_rows + judged_row];
             }
             // With the neighbour-row filter on (and the LDS set), only the rows the filter lets through are ENTERED
             // into the visited set: a row it rejects has dist >= bound > max(topResults), the maximum never grows
@@ -551,7 +604,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
             const bool filter_first = LATE && filter_now;
             bool fresh = false, seen = false, full_now = false;
             if constexpr (LATE) {
-                if (pend_any) {
+                if (PHASE != 1 && pend_any) { // (a filling set has no filter: nothing is pending)
                     if (pend)
                         visit_insert_absent<TAGW, NB>(pend_id, pend_full, vt, bm, used_bitmap);
                     pend_any = false;
@@ -570,7 +623,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
             int nfresh = __popcll(mask);
             // the set's last entry: read once per expansion, for the filter and for the first pass below (the set
             // does not change in between)
-            const unsigned long long last_now = R.get(n - 1);
+            const unsigned long long last_now = R.get(set_n() - 1);
             if (filter_now && inline_rows) {
                 if (filter_first)
                     fresh = lane < cnt && !seen;
@@ -591,8 +644,8 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
                         // rows at and beyond the link count are zero padding whose verdicts nobody reads (mean degree
-                        // 21 of 32 slots): a scalar branch over their arithmetic (IVFHNSW_WALK_SKIPPAD, A/B knob)
-                        if ((CK || g.skip_padding) && rb + 8 * i >= cnt_s) {
+                        // 21 of 32 slots): a scalar branch over their arithmetic
+                        if (rb + 8 * i >= cnt_s) {
                             S[i] = 0;
                             X[i] = 0;
                             continue;
@@ -655,7 +708,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                         break;
                     if constexpr (CK) {
                         const uint4 *nbr =
-                            reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * g.nb_rows * 128) + (lane & 7);
+                            reinterpret_cast<const uint4 *>(g.nbrows + (size_t)node * nbr_rows * 128) + (lane & 7);
                         const int last = max(cnt - 1, 0);
 #pragma unroll
                         for (int i = 0; i < 4; i++)
@@ -663,13 +716,13 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                                 nw[i] = nbr[min(rb + 8 * i + (lane >> 3), last) * 8];
                     } else {
                         const uint4 *nbr =
-                            reinterpret_cast<const uint4 *>(g.nbrows + ((size_t)node * g.nb_rows + rb) * 128) + lane;
+                            reinterpret_cast<const uint4 *>(g.nbrows + ((size_t)node * nbr_rows + rb) * 128) + lane;
 #pragma unroll
                         for (int i = 0; i < 4; i++)
                             nw[i] = nbr[i * 64];
                     }
                     if constexpr (ROWNORMS)
-                        row_rr = g.nbnorms[(size_t)node * g.nb_rows + rb + judged_row];
+                        row_rr = g.nbnorms[(size_t)node * nbr_rows + rb + judged_row];
                 }
                 mask = __ballot(fresh);
                 nfresh = __popcll(mask);
@@ -696,7 +749,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                     const uint32_t nbq = (uint32_t)__shfl((int)nb, src, 64);
                     float S = 0.f;
                     if (active)
-                        S = byte_row_dist_half(g.qrows + (size_t)nbq * g.d, s_qp, g.d, lane & 1);
+                        S = byte_row_dist_half(g.qrows + (size_t)nbq * dim, s_qp, dim, lane & 1);
                     S += __shfl_xor(S, 1, 64);
                     const float m = fmaxf(0.f, __builtin_amdgcn_sqrtf(S) * 0.9990234375f - pf_slack) * g.q_step;
                     const float lb = m * m * 0.9990234375f;
@@ -724,7 +777,9 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                 const uint32_t nbq = dec_id(nbe);
                 float dq = 0.f;
                 if (active) {
-                    if constexpr (QREG)
+                    if constexpr (D != 0)
+                        dq = l2_ref_order_oct_regs<D / 8>(g.vectors + (size_t)nbq * D, q_reg, lane & 7);
+                    else if constexpr (QREG)
                         dq = g.d == 128  ? l2_ref_order_oct_regs<16>(g.vectors + (size_t)nbq * 128, q_reg, lane & 7)
                              : g.d == 96 ? l2_ref_order_oct_regs<12>(g.vectors + (size_t)nbq * 96, q_reg, lane & 7)
                                          : l2_ref_order_oct(g.vectors + (size_t)nbq * g.d, s_q, g.d, lane & 7);
@@ -740,16 +795,16 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                 // Rows that cannot be admitted are dropped wave-wide before the sequential part: once the
                 // set is full its maximum only decreases, so a row failing 'top > dist' (hnswalg.cpp:93)
                 // against the current maximum fails against every later one too.
-                unsigned long long topk = base == 0 ? last_now : R.get(n - 1); // the set's last entry, carried through the loop
+                unsigned long long topk = base == 0 ? last_now : R.get(set_n() - 1); // the set's last entry, carried through the loop
                 const float top0 = __uint_as_float(key_dist_bits(topk));
                 // (first lane of each row's group, rows that exist: constant and scalar masks instead of per-lane tests)
-                unsigned long long cand = (n < ef ? ~0ull : __ballot(top0 > dq)) & 0x0101010101010101ull &
+                unsigned long long cand = (!STEADY && n < ef ? ~0ull : __ballot(top0 > dq)) & 0x0101010101010101ull &
                                           lanes_below(8 * (nfresh - base), 0);
                 if (STAMPS) {
                     st_acc[6] += (unsigned long long)__popcll(__ballot(active && (lane & 7) == 0));
                     st_acc[7] += (unsigned long long)__popcll(cand);
                 }
-                if (NCH <= 4 && merge_on && n == ef && ntail == 0 && cand) {
+                if (NCH <= 4 && merge_on && (STEADY || n == ef) && ntail == 0 && cand) {
                     // ---- all admissions of the pass in one step.  With the set full, inserting the pass's
                     // candidates one by one in link order (below) leaves the ef smallest keys of set + candidates,
                     // PROVIDED the ef-th and (ef+1)-th of the merged order differ in distance: then every loser has
@@ -811,16 +866,16 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                     const float dj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(dq), b));
                     const uint32_t idj = (uint32_t)__builtin_amdgcn_readlane((int)nbe, b);
                     const unsigned long long oldtop = topk;
-                    if (!(__uint_as_float(key_dist_bits(oldtop)) > dj || n < ef))
+                    if (!(__uint_as_float(key_dist_bits(oldtop)) > dj || (!STEADY && n < ef)))
                         continue;
                     const unsigned long long K = mk_key(dj, idj);
-                    const bool full = n == ef;
+                    const bool full = STEADY || n == ef;
                     if (STAMPS)
                         st_acc[8] += 1;
                     R.insert_sorted(K, lane);
                     if (!full)
                         n++;
-                    topk = R.get(n - 1);
+                    topk = R.get(set_n() - 1);
                     // bookkeeping of candidates that left topResults but may still be popped
                     const uint32_t newmax = key_dist_bits(topk);
                     if (ntail > 0 && (SPILL ? tail_db : key_dist_bits(tail[0])) != newmax) {
@@ -851,7 +906,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                             // more than kTailCap exact distance ties at the boundary: this form cannot finish the query --
                             // it goes on the redo list (the SPILL form walks it again, results written there)
                             if (lane == 0)
-                                redo_list[atomicAdd(&redo_hdr[0], 1u)] = (uint32_t)q;
+                                WALK_COLD(redo_list)[atomicAdd(&WALK_COLD(redo_hdr)[0], 1u)] = (uint32_t)q;
                             ntail = -1;
                             break;
                         }
@@ -863,8 +918,17 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
                     st_t = t;
                 }
             }
-            if (ntail < 0)
-                break;
+            return ntail >= 0;
+        };
+        if constexpr (SHAPED) {
+            bool live = true;
+            while (live && n < ef)
+                live = expand(std::integral_constant<int, 1>{});
+            while (live)
+                live = expand(std::integral_constant<int, 2>{});
+        } else {
+            while (expand(std::integral_constant<int, 0>{})) {
+            }
         }
 
         if (SPILL && spill.count > 0)
@@ -876,10 +940,11 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
 #pragma unroll
             for (int cc = 0; cc < NCH; cc++) {
                 const int i = cc * 64 + lane;
+                const int nprobe = WALK_COLD(nprobe);
                 if (i < nprobe) {
                     const bool have = i < n;
-                    coarse_ids[(size_t)q * nprobe + i] = have ? dec_id(key_id(R.r[cc])) : 0xffffffffu;
-                    coarse_dists[(size_t)q * nprobe + i] = have ? __uint_as_float(key_dist_bits(R.r[cc])) : 0.f;
+                    WALK_COLD(coarse_ids)[(size_t)q * nprobe + i] = have ? dec_id(key_id(R.r[cc])) : 0xffffffffu;
+                    WALK_COLD(coarse_dists)[(size_t)q * nprobe + i] = have ? __uint_as_float(key_dist_bits(R.r[cc])) : 0.f;
                 }
             }
         }
@@ -890,11 +955,11 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
         // so that launches need no memset between them (it was ~8 us of every step's critical path).
         if (lane == 0) {
             __threadfence();
-            if (atomicAdd(&redo_hdr[2], 1u) == gridDim.x - 1) {
-                redo_hdr[-1] = 0;
-                redo_hdr[0] = 0;
-                redo_hdr[1] = 0;
-                redo_hdr[2] = 0;
+            if (atomicAdd(&a.redo_hdr[2], 1u) == gridDim.x - 1) {
+                a.redo_hdr[-1] = 0;
+                a.redo_hdr[0] = 0;
+                a.redo_hdr[1] = 0;
+                a.redo_hdr[2] = 0;
             }
         }
     }
@@ -908,9 +973,10 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(GraphTables g, cons
         for (size_t w = lane; w < vwords / 4; w += 64)
             bm4[w] = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (STAMPS && stamp_out && lane == 0)
+    if (STAMPS && a.stamp_out && lane == 0)
         for (int i = 0; i < 9; i++)
-            atomicAdd(&stamp_out[i], st_acc[i]);
+            atomicAdd(&a.stamp_out[i], st_acc[i]);
+#undef WALK_COLD
 }
 
 // one 64-thread block per (node, 8 rows): lane -> row (lane >> 3), 16-byte chunk (lane & 7)
@@ -1041,9 +1107,9 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
     } else if (visited_zero) {
         *visited_zero = false;
     }
-#define IVFHNSW_WALK_F(N, W, T, F)                                                                                    \
-    hipLaunchKernelGGL((hnsw_walk_kernel<N, W, T, F>), dim3(nslots), dim3(64), shm, s, g, xq, nq, nprobe, ef,         \
-                       coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot, status, next_query, redo_hdr, redo_list)
+    WalkArgs wa = {g,      xq,         nq,       nprobe,    ef,      coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot,
+                   status, next_query, redo_hdr, redo_list, nullptr, nullptr};
+#define IVFHNSW_WALK_F(N, W, T, F) hipLaunchKernelGGL((hnsw_walk_kernel<N, W, T, F>), dim3(nslots), dim3(64), shm, s, wa)
 #define IVFHNSW_WALK_T(N, W, T)          \
     do {                                 \
         if (fmode == 3)                  \
@@ -1073,6 +1139,13 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
         const char *e = getenv("IVFHNSW_WALK_STAMPS");
         return e && atoi(e) == 1;
     }();
+    // IVFHNSW_WALK_SHAPE=0 forces the generic instantiation (A/B runs); read once per process
+    static const bool shape_on = [] {
+        const char *e = getenv("IVFHNSW_WALK_SHAPE");
+        return !(e && atoi(e) == 0);
+    }();
+    const WalkShape shape = walk_shape_for(g.d, g.maxM, g.nb_rows, fmode, tagw, nch, shape_on);
+    const bool merge = g.merge_admissions != 0;
     if (stamps && nch == 2 && ((tagw == 8 && fmode == 2) || (tagw == 10 && fmode == 3)) && occ == 4) {
         // diagnostic build: per-segment cycle sums, printed when the process exits (never used for timing claims)
         static unsigned long long *d_st = nullptr;
@@ -1092,16 +1165,52 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
                 }
             });
         }
+        wa.stamp_out = d_st;
         if (tagw == 8)
-            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 8, 2, true>), dim3(nslots), dim3(64), shm, s, g, xq, nq, nprobe, ef,
-                               coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot, status, next_query, redo_hdr,
-                               redo_list, nullptr, d_st);
+            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 8, 2, true>), dim3(nslots), dim3(64), shm, s, wa);
+        else if (shape.d == 128 && merge) // ... with the shape compiled in, so the stamps describe the code that is timed
+            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 10, 3, true, false, 128, 32, true>), dim3(nslots), dim3(64), shm, s, wa);
         else // the form graphs of about a million nodes take (10-bit tags, late visited entry): round 3
-            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 10, 3, true>), dim3(nslots), dim3(64), shm, s, g, xq, nq, nprobe, ef,
-                               coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot, status, next_query, redo_hdr,
-                               redo_list, nullptr, d_st);
+            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 10, 3, true>), dim3(nslots), dim3(64), shm, s, wa);
         return hipGetLastError();
     }
+    // the shaped forms (walk_shape.h): nch 1 and 2, LDS visited set, neighbour rows, d 128 / 96 with 32 links per node
+#define IVFHNSW_WALK_S(N, T, F, DD, MG) \
+    hipLaunchKernelGGL((hnsw_walk_kernel<N, 4, T, F, false, false, DD, 32, MG>), dim3(nslots), dim3(64), shm, s, wa)
+#define IVFHNSW_WALK_SD(N, T, F)                   \
+    do {                                           \
+        if (shape.d == 128 && merge)               \
+            IVFHNSW_WALK_S(N, T, F, 128, true);    \
+        else if (shape.d == 128)                   \
+            IVFHNSW_WALK_S(N, T, F, 128, false);   \
+        else if (merge)                            \
+            IVFHNSW_WALK_S(N, T, F, 96, true);     \
+        else                                       \
+            IVFHNSW_WALK_S(N, T, F, 96, false);    \
+    } while (0)
+#define IVFHNSW_WALK_ST(N, T)            \
+    do {                                 \
+        if (fmode == 3)                  \
+            IVFHNSW_WALK_SD(N, T, 3);    \
+        else                             \
+            IVFHNSW_WALK_SD(N, T, 2);    \
+    } while (0)
+#define IVFHNSW_WALK_SN(N)               \
+    do {                                 \
+        if (tagw == 8)                   \
+            IVFHNSW_WALK_ST(N, 8);       \
+        else if (tagw == 10)             \
+            IVFHNSW_WALK_ST(N, 10);      \
+        else if (tagw == 12)             \
+            IVFHNSW_WALK_ST(N, 12);      \
+        else                             \
+            IVFHNSW_WALK_ST(N, 16);      \
+    } while (0)
+    if (shape.d != 0 && nch <= 1) {
+        IVFHNSW_WALK_SN(1);
+    } else if (shape.d != 0) {
+        IVFHNSW_WALK_SN(2);
+    } else
     if (nch <= 1) {
         IVFHNSW_WALK_N(1);
     } else if (nch <= 2) {
@@ -1115,6 +1224,10 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
     } else {
         IVFHNSW_WALK(16, 4);
     }
+#undef IVFHNSW_WALK_SN
+#undef IVFHNSW_WALK_ST
+#undef IVFHNSW_WALK_SD
+#undef IVFHNSW_WALK_S
 #undef IVFHNSW_WALK_N
 #undef IVFHNSW_WALK
 #undef IVFHNSW_WALK_T
@@ -1144,10 +1257,10 @@ hipError_t launch_coarse_redo(hipStream_t s, const GraphTables &g_in, const floa
     const int slots = std::min(std::min(nq, tail_slots), 64);
     const size_t shm = (size_t)g.d * sizeof(float) + 512 +
                        (size_t)(kTailCap + ((ef <= 256 && ef + 8 > kTailCap) ? ef + 8 - kTailCap : 0)) * sizeof(unsigned long long);
-#define IVFHNSW_REDO(N)                                                                                               \
-    hipLaunchKernelGGL((hnsw_walk_kernel<N, 4, 0, 0, false, true>), dim3(slots), dim3(64), shm, s, g, xq, nq, nprobe, ef, \
-                       coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot, status, redo_hdr + 1, redo_hdr, \
-                       redo_list, tail_bitmaps)
+    // (the redo launch's own query counter, redo_hdr[1], stands where the fast forms have next_query)
+    const WalkArgs wa = {g,      xq,           nq,       nprobe,    ef,           coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot,
+                         status, redo_hdr + 1, redo_hdr, redo_list, tail_bitmaps, nullptr};
+#define IVFHNSW_REDO(N) hipLaunchKernelGGL((hnsw_walk_kernel<N, 4, 0, 0, false, true>), dim3(slots), dim3(64), shm, s, wa)
     if (nch <= 1)
         IVFHNSW_REDO(1);
     else if (nch <= 2)
