@@ -1,5 +1,6 @@
 // The batched search pipeline (rotate -> coarse -> table -> plan -> scan -> select) and its host-pointer entry points.
 #include "capi_internal.h"
+#include "walk_form.h"
 
 // a size from the environment, def when unset or empty; every caller reads its knob once per process
 static size_t env_size(const char *name, size_t def)

@@ -9,6 +9,7 @@
 #include "scan_dispatch.h"
 #include "sweep_plan_math.h"
 #include "update_math.h"
+#include "walk_form.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -252,7 +253,7 @@ hipError_t launch_coarse_redo(hipStream_t s, const GraphTables &g, const float *
                               uint32_t *coarse_ids, float *coarse_dists, uint32_t *visited_scratch,
                               size_t visited_words_per_slot, uint32_t *status, uint32_t *redo_hdr, uint32_t *redo_list,
                               uint32_t *tail_bitmaps, int tail_slots);
-int coarse_slots_for(int ef);
+// (coarse_slots_for, the wavefront slots the walk keeps resident for a given ef: walk_form.h)
 // one workgroup per query on the fat graph (small batches: the reference's one-query-per-call drivers)
 bool coarse_latency_supported(const GraphTables &g, int ef);
 size_t coarse_latency_fat_bytes(const GraphTables &g);

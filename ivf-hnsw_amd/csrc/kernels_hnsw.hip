@@ -26,7 +26,7 @@
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 #include "walk_set.h"
-#include "walk_shape.h"
+#include "walk_form.h"
 
 #include <float.h>
 #include <stdio.h>
@@ -43,17 +43,7 @@ namespace ivfhnsw_gpu_impl {
 // bitmap instead (a few percent of the ids), and is looked up there from then on because a full bucket never empties.
 // Why: one returning global atomicOr per neighbour on bitmaps that do not fit L2 was the walk's largest cost
 // (19.6 M scattered atomics per 10 k queries, ~1 ms; MI355X guide: scattered atomics run ~17x below the
-// coalesced rate).
-// The bucket count follows the occupancy the kernel is built for (MINW waves per SIMD, 4 * MINW per CU sharing
-// 160 KB of LDS): 1008 buckets = 7.9 KB at 4 (with query, planes, tail and merge buffer 9.8 KB per wave at efSearch 80:
-// sixteen waves fill 157 of a CU's 160 KB), 6 KB at 5, 5 KB at 6.
-constexpr int vis_buckets(int minw, int tagw = 8)
-{
-    // 10-bit tags (six per bucket) exist for graphs of about a million nodes -- the reference's 993 127 centroids,
-    // the 2^20 of the 8-GPU bench: with 12-bit tags (five per bucket) 896 buckets ran 56 % full and every
-    // expansion paid a global atomic for an overflowing neighbour.  1040 buckets x 6 = 6240 slots, 8320 bytes.
-    return minw <= 4 ? (tagw == 10 ? 1040 : 1008) : minw == 5 ? 768 : minw <= 7 ? 640 : 384;
-}
+// coalesced rate).  The bucket count is walk_vis_buckets (walk_form.h): sixteen waves share a CU's 160 KB of LDS.
 
 // TAGW = bits per tag; a 64-bit bucket holds `slots` tags and, in its top bits, the number of ids that claimed a
 // field:  8 -> 7 tags + 8-bit count (graphs up to 255 * buckets nodes), 10 -> 5 + 14, 12 -> 4 + 16, 16 -> 3 + 16;
@@ -234,14 +224,17 @@ template <class T> __device__ __forceinline__ const __attribute__((address_space
     return p;
 }
 
-// D, MAXM, MERGE: the SHAPE as constants (neighbour-row forms only; the rule is walk_shape_for, walk_shape.h).  D != 0
+// Built for 4 waves per SIMD: register budget and visited-set size follow from it (2, 3, 4 waves resident: 2.61, 1.90,
+// 1.54 ms per 10 k queries at 2^17 nodes, ef 80).  Builds for 5 and 6 waves, with smaller visited sets and no query
+// share in registers, measured no better -- 1.52 / 1.50 against 1.50 ms, 1.51 / 1.68 against 1.37 at 993 127 nodes -- and
+// were removed in round 3 with their IVFHNSW_WALK_OCC knob.
+// D, MAXM, MERGE: the SHAPE as constants (neighbour-row forms only; the rule is walk_form_for, walk_form.h).  D != 0
 // stands for GraphTables::d, MAXM != 0 for GraphTables::maxM with nb_rows = MAXM rounded up to 32, and MERGE for
 // GraphTables::merge_admissions; 0 / 0 is the generic form, which reads all of them at run time.  With both set the
 // float-row step is l2_ref_order_oct_regs<D / 8> alone, record addresses are shifts, and the loop over a query's
 // expansions is peeled by phase (see `expand` below).
-template <int NCH, int MINW, int TAGW, int FMODE, bool STAMPS = false, bool SPILL = false, int D = 0, int MAXM = 0,
-          bool MERGE = true>
-__global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
+template <int NCH, int TAGW, int FMODE, bool STAMPS = false, bool SPILL = false, int D = 0, int MAXM = 0, bool MERGE = true>
+__global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
 {
     constexpr bool SHAPED = D != 0 && MAXM != 0;
     const GraphTables &g = a.g;
@@ -253,7 +246,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
 #define WALK_COLD(f) (SHAPED ? late_kernarg<WalkArgs>()->f : a.f)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *s_q = reinterpret_cast<float *>(smem);
-    static_assert(!SHAPED || (FMODE >= 2 && !SPILL && MINW <= 4 && D % 16 == 0 && D <= 128 && MAXM <= 64),
+    static_assert(!SHAPED || (FMODE >= 2 && !SPILL && D % 16 == 0 && D <= 128 && MAXM <= 64),
                   "shape constants go with the neighbour-row forms");
     static_assert(SHAPED || MERGE, "the generic form reads merge_admissions at run time");
     const int dim = D ? D : g.d;
@@ -265,7 +258,7 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
     // neighbour-row form: the same in 1/256 steps, four byte planes of 32 words (hi, lo, XL, XH)
     uint32_t *s_q8 = reinterpret_cast<uint32_t *>(s_qp + dp);
     unsigned long long *tail = reinterpret_cast<unsigned long long *>(smem + (size_t)(dim + dp) * sizeof(float) + 512);
-    constexpr int NB = vis_buckets(MINW, TAGW);
+    constexpr int NB = walk_vis_buckets(TAGW);
     unsigned long long st_acc[9] = {0, 0, 0, 0, 0, 0}, st_t = 0;
     // the tail doubles as the merge buffer of a pass's admissions (ef + 8 entries; only used while the tail is empty)
     const int merge_extra = (NCH <= 4 && ef + 8 > kTailCap) ? ef + 8 - kTailCap : 0;
@@ -349,17 +342,13 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
         __syncthreads(); // also orders the bitmap reset before the atomics below
         // d = 128 (SIFT) and 96 (DEEP): the lane's share of the query for the 8-lanes-per-row distance stays in
         // registers (one LDS round trip less in every expansion's dependent chain)
-        // (builds for more than 4 waves per SIMD have no registers to spare for it)
-        constexpr bool QREG = MINW <= 4;
-        float q_reg[QREG ? 16 : 1];
-        if constexpr (QREG) {
+        float q_reg[16];
 #pragma unroll
-            for (int i = 0; i < 16; i++)
-                if constexpr (D != 0)
-                    q_reg[i] = 8 * i < D ? s_q[8 * i + (lane & 7)] : 0.f;
-                else
-                    q_reg[i] = (g.d == 128 || g.d == 96) && 8 * i < g.d ? s_q[8 * i + (lane & 7)] : 0.f;
-        }
+        for (int i = 0; i < 16; i++)
+            if constexpr (D != 0)
+                q_reg[i] = 8 * i < D ? s_q[8 * i + (lane & 7)] : 0.f;
+            else
+                q_reg[i] = (g.d == 128 || g.d == 96) && 8 * i < g.d ? s_q[8 * i + (lane & 7)] : 0.f;
         // slack of the rejection test in byte-row units: quantisation error of the worst row, plus what the
         // rounding of s_qp can move a distance by (<= 2^-22 ||q'||; 2^-18 leaves a factor 16)
         float pf_slack = 0.f, pf_slack_q = 0.f, pf_bonus = 0.f;
@@ -779,12 +768,10 @@ __global__ __launch_bounds__(64, MINW) void hnsw_walk_kernel(WalkArgs a)
                 if (active) {
                     if constexpr (D != 0)
                         dq = l2_ref_order_oct_regs<D / 8>(g.vectors + (size_t)nbq * D, q_reg, lane & 7);
-                    else if constexpr (QREG)
+                    else
                         dq = g.d == 128  ? l2_ref_order_oct_regs<16>(g.vectors + (size_t)nbq * 128, q_reg, lane & 7)
                              : g.d == 96 ? l2_ref_order_oct_regs<12>(g.vectors + (size_t)nbq * 96, q_reg, lane & 7)
                                          : l2_ref_order_oct(g.vectors + (size_t)nbq * g.d, s_q, g.d, lane & 7);
-                    else
-                        dq = l2_ref_order_oct(g.vectors + (size_t)nbq * g.d, s_q, g.d, lane & 7);
                 }
                 if (STAMPS) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1024,17 +1011,22 @@ hipError_t launch_build_nbrows(hipStream_t s, const GraphTables &g, uint8_t *nbr
     return hipGetLastError();
 }
 
-// how many wavefront slots the walk keeps resident for a given ef (sizes the visited bitmaps)
-int coarse_slots_for(int ef)
+// the knobs of walk_form.h, read once per process
+static const WalkKnobs &walk_knobs()
 {
-    const int nch = (ef + 63) / 64;
-    // Exactly the wavefronts that can be resident (256 CUs x 4 SIMDs x the waves per SIMD the kernel is built for;
-    // its registers allow no more): blocks beyond that only start when a slot frees up, find the queue empty and
-    // cost their prologue -- 1.205 vs 1.189 ms per 10 k queries with 8192 instead of 4096 blocks.
-    // (builds for 5 and 6 waves per SIMD were measured -- 1.52 / 1.50 ms against 1.50 at 2^17 nodes, 1.51 / 1.68 against
-    // 1.37 at 993 127 -- and removed in round 3 with their IVFHNSW_WALK_OCC knob)
-    const int waves_per_simd = nch <= 8 ? 4 : 3;
-    return 256 * 4 * waves_per_simd;
+    static const WalkKnobs knobs = [] {
+        auto num = [](const char *knob, int unset) { return getenv(knob) ? atoi(getenv(knob)) : unset; };
+        const char *vis = getenv("IVFHNSW_WALK_VIS");
+        const int w = num("IVFHNSW_WALK_TAGW", 0);
+        return WalkKnobs{vis && vis[0] == 'b', (w == 10 || w == 12 || w == 16) ? w : 0, num("IVFHNSW_WALK_SHAPE", 1) != 0,
+                         num("IVFHNSW_WALK_STAMPS", 0) == 1};
+    }();
+    return knobs;
+}
+
+static WalkGraph walk_graph_of(const GraphTables &g)
+{
+    return {g.n, g.d, g.maxM, g.nb_rows, g.qrows != nullptr, g.nbrows != nullptr, g.links_unique != 0, g.merge_admissions != 0};
 }
 
 hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq, int nq, int nprobe, int ef,
@@ -1061,42 +1053,11 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
     }
     if (counters_clean)
         *counters_clean = false;
-    // Waves per SIMD the kernel is built for (register budget and visited-set size follow from it).  Measured
-    // on MI355X (100M / 2^17-centroid workload, ef 80) with the LDS padded to hold 2, 3, 4 waves per SIMD
-    // resident: 2.61, 1.90, 1.54 ms per 10 k queries = 0.48 + 4.26 / waves -- the walk is latency bound per wave.
-    constexpr int occ = 4;
-    const int nch = (ef + 63) / 64;
-    const int occ_eff = 4;
-    uint32_t nbk = (uint32_t)vis_buckets(occ_eff);
-    // the LDS visited set needs 16-bit tags at most; IVFHNSW_WALK_VIS=bitmap forces the global bitmap (A/B runs)
-    static const bool force_bitmap = [] {
-        const char *e = getenv("IVFHNSW_WALK_VIS");
-        return e && e[0] == 'b';
-    }();
-    int tagw = force_bitmap ? 0 : g.n <= 255u * nbk ? 8 : g.n <= 4095u * nbk ? 12 : g.n <= 65535u * nbk ? 16 : 0;
-    // IVFHNSW_WALK_TAGW=10|12|16 forces a wider tag than the graph needs (tests: small graphs reach every form)
-    static const int force_tagw = [] {
-        const char *e = getenv("IVFHNSW_WALK_TAGW");
-        const int v = e ? atoi(e) : 0;
-        return (v == 10 || v == 12 || v == 16) ? v : 0;
-    }();
-    if (tagw && force_tagw > tagw)
-        tagw = force_tagw;
-    if ((tagw == 12 || tagw == 10) && occ_eff == 4 && g.n <= 1023u * (uint32_t)vis_buckets(4, 10) && force_tagw != 12) {
-        tagw = 10;
-        nbk = (uint32_t)vis_buckets(4, 10);
-    } else if (tagw == 10) {
-        tagw = 12; // the 10-bit form exists for 4 waves per SIMD only
-    }
-    const size_t shm = (size_t)(g.d + ((g.qrows && !g.nbrows) ? g.d : 0)) * sizeof(float) + 512 +
-                       (size_t)(kTailCap + ((ef <= 256 && ef + 8 > kTailCap) ? ef + 8 - kTailCap : 0)) *
-                           sizeof(unsigned long long) +
-                       (tagw ? (size_t)nbk * sizeof(unsigned long long) : 0);
-    const int fmode = g.nbrows ? (g.links_unique && tagw ? 3 : 2) : g.qrows ? 1 : 0;
+    const WalkForm form = walk_form_for(walk_graph_of(g), ef, walk_knobs());
     // the global bitmaps: with the LDS set (tagw != 0) they are the overflow store, zero between launches -- cleared
     // here once if the caller cannot vouch for them; the bitmap-only forms wipe per query and leave them used
     g.visited_clean = 0;
-    if (tagw && visited_zero) {
+    if (form.tagw && visited_zero) {
         if (!*visited_zero) {
             e = hipMemsetAsync(visited_scratch, 0, visited_bytes, s);
             if (e != hipSuccess)
@@ -1109,44 +1070,7 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
     }
     WalkArgs wa = {g,      xq,         nq,       nprobe,    ef,      coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot,
                    status, next_query, redo_hdr, redo_list, nullptr, nullptr};
-#define IVFHNSW_WALK_F(N, W, T, F) hipLaunchKernelGGL((hnsw_walk_kernel<N, W, T, F>), dim3(nslots), dim3(64), shm, s, wa)
-#define IVFHNSW_WALK_T(N, W, T)          \
-    do {                                 \
-        if (fmode == 3)                  \
-            IVFHNSW_WALK_F(N, W, T, 3);  \
-        else if (fmode == 2)             \
-            IVFHNSW_WALK_F(N, W, T, 2);  \
-        else if (fmode == 1)             \
-            IVFHNSW_WALK_F(N, 4, T, 1);  \
-        else                             \
-            IVFHNSW_WALK_F(N, 4, T, 0);  \
-    } while (0)
-#define IVFHNSW_WALK(N, W)             \
-    do {                               \
-        if (tagw == 8)                 \
-            IVFHNSW_WALK_T(N, W, 8);   \
-        else if (tagw == 10)           \
-            IVFHNSW_WALK_T(N, 4, 10);  \
-        else if (tagw == 12)           \
-            IVFHNSW_WALK_T(N, W, 12);  \
-        else if (tagw == 16)           \
-            IVFHNSW_WALK_T(N, W, 16);  \
-        else                           \
-            IVFHNSW_WALK_T(N, W, 0);   \
-    } while (0)
-#define IVFHNSW_WALK_N(N) IVFHNSW_WALK(N, 4)
-    static const bool stamps = [] {
-        const char *e = getenv("IVFHNSW_WALK_STAMPS");
-        return e && atoi(e) == 1;
-    }();
-    // IVFHNSW_WALK_SHAPE=0 forces the generic instantiation (A/B runs); read once per process
-    static const bool shape_on = [] {
-        const char *e = getenv("IVFHNSW_WALK_SHAPE");
-        return !(e && atoi(e) == 0);
-    }();
-    const WalkShape shape = walk_shape_for(g.d, g.maxM, g.nb_rows, fmode, tagw, nch, shape_on);
-    const bool merge = g.merge_admissions != 0;
-    if (stamps && nch == 2 && ((tagw == 8 && fmode == 2) || (tagw == 10 && fmode == 3)) && occ == 4) {
+    if (form.stamps) {
         // diagnostic build: per-segment cycle sums, printed when the process exits (never used for timing claims)
         static unsigned long long *d_st = nullptr;
         if (!d_st) {
@@ -1166,74 +1090,16 @@ hipError_t launch_coarse(hipStream_t s, const GraphTables &g_in, const float *xq
             });
         }
         wa.stamp_out = d_st;
-        if (tagw == 8)
-            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 8, 2, true>), dim3(nslots), dim3(64), shm, s, wa);
-        else if (shape.d == 128 && merge) // ... with the shape compiled in, so the stamps describe the code that is timed
-            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 10, 3, true, false, 128, 32, true>), dim3(nslots), dim3(64), shm, s, wa);
-        else // the form graphs of about a million nodes take (10-bit tags, late visited entry): round 3
-            hipLaunchKernelGGL((hnsw_walk_kernel<2, 4, 10, 3, true>), dim3(nslots), dim3(64), shm, s, wa);
-        return hipGetLastError();
     }
-    // the shaped forms (walk_shape.h): nch 1 and 2, LDS visited set, neighbour rows, d 128 / 96 with 32 links per node
-#define IVFHNSW_WALK_S(N, T, F, DD, MG) \
-    hipLaunchKernelGGL((hnsw_walk_kernel<N, 4, T, F, false, false, DD, 32, MG>), dim3(nslots), dim3(64), shm, s, wa)
-#define IVFHNSW_WALK_SD(N, T, F)                   \
-    do {                                           \
-        if (shape.d == 128 && merge)               \
-            IVFHNSW_WALK_S(N, T, F, 128, true);    \
-        else if (shape.d == 128)                   \
-            IVFHNSW_WALK_S(N, T, F, 128, false);   \
-        else if (merge)                            \
-            IVFHNSW_WALK_S(N, T, F, 96, true);     \
-        else                                       \
-            IVFHNSW_WALK_S(N, T, F, 96, false);    \
-    } while (0)
-#define IVFHNSW_WALK_ST(N, T)            \
-    do {                                 \
-        if (fmode == 3)                  \
-            IVFHNSW_WALK_SD(N, T, 3);    \
-        else                             \
-            IVFHNSW_WALK_SD(N, T, 2);    \
-    } while (0)
-#define IVFHNSW_WALK_SN(N)               \
-    do {                                 \
-        if (tagw == 8)                   \
-            IVFHNSW_WALK_ST(N, 8);       \
-        else if (tagw == 10)             \
-            IVFHNSW_WALK_ST(N, 10);      \
-        else if (tagw == 12)             \
-            IVFHNSW_WALK_ST(N, 12);      \
-        else                             \
-            IVFHNSW_WALK_ST(N, 16);      \
-    } while (0)
-    if (shape.d != 0 && nch <= 1) {
-        IVFHNSW_WALK_SN(1);
-    } else if (shape.d != 0) {
-        IVFHNSW_WALK_SN(2);
-    } else
-    if (nch <= 1) {
-        IVFHNSW_WALK_N(1);
-    } else if (nch <= 2) {
-        IVFHNSW_WALK_N(2);
-    } else if (nch == 3) { // efSearch 129..192 (the reference's DEEP1B presets use 130)
-        IVFHNSW_WALK_N(3);
-    } else if (nch <= 4) {
-        IVFHNSW_WALK_N(4);
-    } else if (nch <= 8) {
-        IVFHNSW_WALK(8, 4);
-    } else {
-        IVFHNSW_WALK(16, 4);
-    }
-#undef IVFHNSW_WALK_SN
-#undef IVFHNSW_WALK_ST
-#undef IVFHNSW_WALK_SD
-#undef IVFHNSW_WALK_S
-#undef IVFHNSW_WALK_N
-#undef IVFHNSW_WALK
-#undef IVFHNSW_WALK_T
-#undef IVFHNSW_WALK_F
+    if (!with_walk_form(form, [&](auto nch, auto tagw, auto fmode, auto stamps, auto d, auto maxm, auto merge) {
+            hipLaunchKernelGGL((hnsw_walk_kernel<decltype(nch)::value, decltype(tagw)::value, decltype(fmode)::value,
+                                                 decltype(stamps)::value, false, decltype(d)::value, decltype(maxm)::value,
+                                                 decltype(merge)::value>),
+                               dim3(nslots), dim3(64), form.lds_bytes, s, wa);
+        }))
+        return hipErrorInvalidValue;
     e = hipGetLastError();
-    if (e != hipSuccess)
+    if (e != hipSuccess || form.stamps) // (the diagnostic build walks no redo list)
         return e;
     e = launch_coarse_redo(s, g, xq, nq, nprobe, ef, coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot,
                            status, redo_hdr, redo_list, tail_bitmaps, tail_slots);
@@ -1253,27 +1119,15 @@ hipError_t launch_coarse_redo(hipStream_t s, const GraphTables &g_in, const floa
 {
     GraphTables g = g_in;
     g.visited_clean = 0;
-    const int nch = (ef + 63) / 64;
+    const WalkForm form = walk_redo_form(walk_graph_of(g), ef);
     const int slots = std::min(std::min(nq, tail_slots), 64);
-    const size_t shm = (size_t)g.d * sizeof(float) + 512 +
-                       (size_t)(kTailCap + ((ef <= 256 && ef + 8 > kTailCap) ? ef + 8 - kTailCap : 0)) * sizeof(unsigned long long);
     // (the redo launch's own query counter, redo_hdr[1], stands where the fast forms have next_query)
     const WalkArgs wa = {g,      xq,           nq,       nprobe,    ef,           coarse_ids, coarse_dists, visited_scratch, visited_words_per_slot,
                          status, redo_hdr + 1, redo_hdr, redo_list, tail_bitmaps, nullptr};
-#define IVFHNSW_REDO(N) hipLaunchKernelGGL((hnsw_walk_kernel<N, 4, 0, 0, false, true>), dim3(slots), dim3(64), shm, s, wa)
-    if (nch <= 1)
-        IVFHNSW_REDO(1);
-    else if (nch <= 2)
-        IVFHNSW_REDO(2);
-    else if (nch == 3)
-        IVFHNSW_REDO(3);
-    else if (nch <= 4)
-        IVFHNSW_REDO(4);
-    else if (nch <= 8)
-        IVFHNSW_REDO(8);
-    else
-        IVFHNSW_REDO(16);
-#undef IVFHNSW_REDO
+    if (!with_walk_nch(form.nch, [&](auto nch) {
+            hipLaunchKernelGGL((hnsw_walk_kernel<decltype(nch)::value, 0, 0, false, true>), dim3(slots), dim3(64), form.lds_bytes, s, wa);
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -588,7 +588,6 @@ hipError_t launch_coarse_latency(hipStream_t s, const GraphTables &g, const floa
     if (!coarse_latency_supported(g, ef) || nprobe > ef)
         return hipErrorInvalidValue;
     const size_t shm = ((sizeof(LatShared) + 15) & ~(size_t)15) + (size_t)((g.n + 127u) / 128u) * 16;
-    const int nch = (ef + 63) / 64;
     static const bool stamps = [] {
         const char *e = getenv("IVFHNSW_LAT_STAMPS");
         return e && atoi(e) == 1;
@@ -597,34 +596,24 @@ hipError_t launch_coarse_latency(hipStream_t s, const GraphTables &g, const floa
         const char *e = getenv("IVFHNSW_LAT_DIAG");
         return (e && atoi(e) == 1) ? 1 : 0;
     }();
-#define IVFHNSW_LAT(N, J)                                                                                             \
-    do {                                                                                                              \
-        auto *kern = stamps ? hnsw_walk_lat_kernel<N, J, true> : hnsw_walk_lat_kernel<N, J, false>;                   \
-        if (hipError_t e = stamps ? dyn_lds<hnsw_walk_lat_kernel<N, J, true>>(shm)                                    \
-                                  : dyn_lds<hnsw_walk_lat_kernel<N, J, false>>(shm);                                  \
-            e != hipSuccess)                                                                                          \
-            return e;                                                                                                 \
-        hipLaunchKernelGGL(kern, dim3(nq), dim3(LAT_THREADS), shm, s, g, xq, nq, nprobe, ef, coarse_ids, coarse_dists, \
-                           status, diag, zero_keys, zero_done, redo_hdr, redo_list);                                                                                   \
-    } while (0)
-#define IVFHNSW_LAT_J(N)       \
-    do {                       \
-        if (g.d == 128)        \
-            IVFHNSW_LAT(N, 16); \
-        else                   \
-            IVFHNSW_LAT(N, 12); \
-    } while (0)
-    if (nch <= 1)
-        IVFHNSW_LAT_J(1);
-    else if (nch == 2)
-        IVFHNSW_LAT_J(2);
-    else if (nch == 3)
-        IVFHNSW_LAT_J(3);
-    else
-        IVFHNSW_LAT_J(4);
-#undef IVFHNSW_LAT_J
-#undef IVFHNSW_LAT
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    // one instantiation per nch class (ef <= 256: up to 4), row length (NJ = d / 8) and stamps build
+    auto launch = [&](auto nch, auto nj) {
+        constexpr int N = decltype(nch)::value, J = decltype(nj)::value;
+        auto *kern = stamps ? hnsw_walk_lat_kernel<N, J, true> : hnsw_walk_lat_kernel<N, J, false>;
+        e = stamps ? dyn_lds<hnsw_walk_lat_kernel<N, J, true>>(shm) : dyn_lds<hnsw_walk_lat_kernel<N, J, false>>(shm);
+        if (e == hipSuccess)
+            hipLaunchKernelGGL(kern, dim3(nq), dim3(LAT_THREADS), shm, s, g, xq, nq, nprobe, ef, coarse_ids, coarse_dists,
+                               status, diag, zero_keys, zero_done, redo_hdr, redo_list);
+    };
+    if (!with_walk_nch<4>(walk_nch_for(ef), [&](auto nch) {
+            if (g.d == 128)
+                launch(nch, walk_int<16>());
+            else
+                launch(nch, walk_int<12>());
+        }))
+        return hipErrorInvalidValue;
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 } // namespace ivfhnsw_gpu_impl

@@ -5,9 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace ivfhnsw_gpu_impl {
+#include "walk_form.h" // kTailCap
 
-constexpr int kTailCap = 64;
+namespace ivfhnsw_gpu_impl {
 
 // key = dist bits (non-negative float: bit order == value order) : id : expanded flag
 __device__ __forceinline__ unsigned long long mk_key(float dist, uint32_t id)

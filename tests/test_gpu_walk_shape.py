@@ -1,5 +1,5 @@
 """The walk's shaped instantiations (kernels_hnsw.hip: D / MAXM / MERGE as template constants, the loop over a query's
-expansions peeled into a fill and a steady phase; the rule that picks them is csrc/walk_shape.h) against the oracle's walk.
+expansions peeled into a fill and a steady phase; the rule that picks them is csrc/walk_form.h) against the oracle's walk.
 
 Every case is 512 queries at nprobe 32 and is walked twice on the device, once with the shaped form and once with
 IVFHNSW_WALK_SHAPE=0 (the generic instantiation).  Both must equal the oracle -- ids, their order and the distance bits of
@@ -101,7 +101,7 @@ def _make_cases():
     cases["redo"] = (orc.Hnsw.from_arrays(counts, links, vec, 16, ep), ties.queries(NQ, 7), (80,))
     few = synth.sift_like(rng, 60, 128)                              # fewer than ef nodes: the steady loop is never entered
     cases["few"] = (orc.Hnsw.build(few, M=16, efConstruction=60), _queries(rng, few, 10.0), (80,))
-    # shapes that must take the generic form (tests/test_walk_shape_cpu.py has the rule) and stay equal
+    # shapes that must take the generic form (tests/test_walk_form_cpu.py has the rule) and stay equal
     m16 = orc.Hnsw.build(cents, M=8, efConstruction=60)
     assert m16.maxM == 16
     cases["maxm16"] = (m16, q, (80,))

@@ -18,7 +18,7 @@ rows.sort()
 # the last 3 steps: find the last 6 scan_k1 launches
 scans = [i for i, r in enumerate(rows) if r[2].startswith('scan_k1_kernel')]
 first = None
-walks = [i for i, r in enumerate(rows) if r[2].startswith('hnsw_walk_kernel<2, 4, 10')]
+walks = [i for i, r in enumerate(rows) if r[2].startswith('hnsw_walk_kernel<2, 10')]
 i0 = walks[-4]   # first walk of the second-to-last step
 t0 = rows[i0][0]
 for r in rows[i0:]:
