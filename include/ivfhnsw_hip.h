@@ -330,9 +330,10 @@ int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint6
  * Errors: null labels or tags with n > 0, a misaligned device pointer, conflicting repeats, tag > 0xffff ->
  *   IVFHNSW_ERR_INVALID; set before upload_ivf, set or clear on a view, set / clear / a _tags call on a handle with
  *   shard_world > 1 -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM.
- * Not built: tags for the exact calls (the truth of a tagged search is the per-tag base-filter loop), for
- *   search_reconstruct, search_sharded and sharded handles; a tag AND the handle's filter or a slot; tags wider than 16
- *   bits or several tags per row. */
+ * The truth of a _tags search: ivfhnsw_gpu_exact_search_tags on a store tagged with ivfhnsw_gpu_set_base_tags ("Base
+ *   tags" below), one call for any number of tags.
+ * Not built: tags for search_reconstruct, search_sharded and sharded handles; a tag AND the handle's filter or a slot;
+ *   tags wider than 16 bits or several tags per row. */
 #define IVFHNSW_TAG_NONE 0xffffu
 int ivfhnsw_gpu_set_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint16_t *tags);
 int ivfhnsw_gpu_set_tags_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint16_t *d_tags);
@@ -803,8 +804,8 @@ int ivfhnsw_gpu_base_filter_info(ivfhnsw_gpu *h, int *mode, uint64_t *rows_passi
  *   IVFHNSW_ERR_INVALID; set or a _slots call before upload_base -> IVFHNSW_ERR_STATE; a failed allocation ->
  *   IVFHNSW_ERR_NOMEM; limits and errors of the plain calls hold unchanged, and whatever they refuse is refused with
  *   their status.
- * Not built: a slot AND the handle's base filter; more than 32 slots; filtering the re-rank's candidates; one bitmap
- *   shared between the index's filter slots and these. */
+ * Not built: a slot AND the handle's base filter; more than 32 slots (disjoint sets beyond 32: "Base tags" below);
+ *   filtering the re-rank's candidates; one bitmap shared between the index's filter slots and these. */
 int ivfhnsw_gpu_set_base_filter_slot(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *labels, int mode);
 int ivfhnsw_gpu_set_base_filter_slot_dev(ivfhnsw_gpu *h, unsigned slot, size_t n, const uint32_t *d_labels, int mode);
 int ivfhnsw_gpu_clear_base_filter_slot(ivfhnsw_gpu *h, int slot); /* -1: every slot */
@@ -817,6 +818,66 @@ int ivfhnsw_gpu_exact_range_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_
                                          const uint8_t *query_slots, float radius, uint64_t *lims, uint64_t *total);
 int ivfhnsw_gpu_exact_range_search_slots_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
                                              const uint8_t *d_query_slots, float radius, uint64_t *d_lims, uint64_t *total);
+
+/* ---- base tags: a 16-bit tag per ROW OF THE STORE, a tag per query of an exact call --------------------
+ *
+ * The truth of a _tags search ("Row tags" above) in one call.  The handle that holds the store holds at most one base tag
+ * array, one uint16 per store row; a row never tagged reads as IVFHNSW_TAG_NONE (0xffff).  The _tags forms of both exact
+ * calls take one uint16 per query: query q with query_tags[q] == t, t != IVFHNSW_TAG_NONE, gets, bit for bit, what the
+ * plain call returns on the same handle with set_base_filter({rows tagged t}, IVFHNSW_FILTER_ALLOW) installed --
+ * exact_search: the original row numbers with the same distance bits, ascending by (distance, label), padded with FLT_MAX /
+ * -1 when fewer than k rows carry t; the range search: results per query in ascending label, exact lims IN THE CALLER'S
+ * QUERY ORDER, held in the handle's exact-range buffers and read with ivfhnsw_gpu_exact_range_results[_dev].  With
+ * IVFHNSW_TAG_NONE the query gets what the plain call returns with no base filter.  A tag no row carries returns padding,
+ * or an empty range.  query_tags == NULL is the plain call: same path, same kernels.  A _tags call on a store without a
+ * tag array is legal: every row is IVFHNSW_TAG_NONE.
+ *   Independent state: plain and _slots calls never read tags, a _tags call ignores base filter slots, and a _tags call on
+ * a store with a set_base_filter filter installed -> IVFHNSW_ERR_STATE (the two are not combined).  The index's row tags
+ * (ivfhnsw_gpu_set_tags) and the base tags never read each other.
+ *   The work follows each query's own tag: the queries of a chunk are grouped by tag into strips of 32 on the device (a
+ * stable sort of the chunk's query numbers by tag), the strips of the untagged queries sweep the whole store, every other
+ * strip sweeps the ascending list of its tag's rows, and one call takes at most two sweep launches per chunk however
+ * many tags its queries name.  A group's last strip is padded to 32 rows, so a chunk of m queries can take up to
+ * m / 32 + min(m, tags in use + 1) strips: with many tags the padded rows, not the queries, size the workspace, and the
+ * k-search shortens its chunk so that the partial tables stay within 256 MB.  One split count per call, from what the host
+ * knows (the store's rows and the queries); every tagged strip sweeps in the list form, however many rows its tag holds.
+ * ivfhnsw_gpu_set_base_tags mirrors ivfhnsw_gpu_set_tags with a ROW NUMBER of the store where that call has a label:
+ *   incremental -- it (over)writes the tags of the rows given and leaves every other row alone; a row number >= n matches
+ *   nothing; a repeat with the same tag counts once, one row given two different tags in one call -> IVFHNSW_ERR_INVALID;
+ *   the tag IVFHNSW_TAG_NONE untags a row.  The new state is built beside the installed one and swapped in, so any error
+ *   leaves the state as it was.  Synchronous on the handle's stream.  _dev: d_rows 4-byte and d_tags 2-byte aligned device
+ *   memory, else IVFHNSW_ERR_INVALID (d_query_tags of the _dev calls: 2-byte aligned).
+ *   ivfhnsw_gpu_clear_base_tags succeeds when there are none.  ivfhnsw_gpu_upload_base[_dev] with first == 0 or n == 0
+ *   drops the tags; a later chunk (first > 0) keeps them.
+ *   ivfhnsw_gpu_base_tags_info: *rows_tagged = rows whose tag is not IVFHNSW_TAG_NONE, *rows_total = rows of the store,
+ *   *tags_in_use = tags at least one row carries; each nullable.  ivfhnsw_gpu_base_tag_rows: *rows = rows of the store that
+ *   carry `tag` (tag <= 0xffff; IVFHNSW_TAG_NONE counts the untagged).
+ * Views: set / clear on a view -> IVFHNSW_ERR_STATE.  A view reads its parent's tags at the call, and both info calls
+ *   report the parent's.
+ * Memory, all counted by ivfhnsw_gpu_memory_bytes: 2 n bytes of tags, 4 bytes per tagged row (the row numbers ordered by
+ *   tag, then row) and 4 * 65537 bytes (256 KB) of their starts per tag: up to 6 n bytes, 6 GB on a store of 10^9 rows.  A
+ *   set call takes 12 n bytes more while it runs (the sort) and frees them.  Per calling handle the strip plans of its last
+ *   _tags call (144 bytes per strip), about 0.8 MB of plan workspace and a host form's staged 2 bytes per query.
+ * Errors: NULL rows or tags with n > 0, a misaligned device pointer, conflicting repeats, tag > 0xffff in base_tag_rows ->
+ *   IVFHNSW_ERR_INVALID; set, base_tag_rows or a _tags call before upload_base -> IVFHNSW_ERR_STATE; a failed allocation ->
+ *   IVFHNSW_ERR_NOMEM; limits and errors of the plain calls hold unchanged, and whatever they refuse is refused with
+ *   their status.
+ * Not built: a tag AND the base filter or a slot; several tags per row or tags wider than 16 bits; a pass-word (masked)
+ *   sweep for tags that hold a large share of the store; a split count per form; tags on the re-rank's candidates; one
+ *   tag array shared between the index and the store. */
+int ivfhnsw_gpu_set_base_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, const uint16_t *tags);
+int ivfhnsw_gpu_set_base_tags_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows, const uint16_t *d_tags);
+int ivfhnsw_gpu_clear_base_tags(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_base_tags_info(ivfhnsw_gpu *h, uint64_t *rows_tagged, uint64_t *rows_total, uint64_t *tags_in_use);
+int ivfhnsw_gpu_base_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows);
+int ivfhnsw_gpu_exact_search_tags(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                                  const uint16_t *query_tags, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                      const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels);
+int ivfhnsw_gpu_exact_range_search_tags(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride,
+                                        const uint16_t *query_tags, float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
+                                            const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

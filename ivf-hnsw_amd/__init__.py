@@ -60,6 +60,10 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_set_tags", "ivfhnsw_gpu_set_tags_dev", "ivfhnsw_gpu_clear_tags", "ivfhnsw_gpu_tags_info",
     "ivfhnsw_gpu_tag_rows", "ivfhnsw_gpu_search_tags", "ivfhnsw_gpu_search_tags_dev",
     "ivfhnsw_gpu_range_search_tags", "ivfhnsw_gpu_range_search_tags_dev",
+    "ivfhnsw_gpu_set_base_tags", "ivfhnsw_gpu_set_base_tags_dev", "ivfhnsw_gpu_clear_base_tags",
+    "ivfhnsw_gpu_base_tags_info", "ivfhnsw_gpu_base_tag_rows",
+    "ivfhnsw_gpu_exact_search_tags", "ivfhnsw_gpu_exact_search_tags_dev",
+    "ivfhnsw_gpu_exact_range_search_tags", "ivfhnsw_gpu_exact_range_search_tags_dev",
 )
 
 
@@ -225,6 +229,15 @@ def lib():
         L.ivfhnsw_gpu_exact_range_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float,
                                                            C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_exact_range_search_slots_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_set_base_tags.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_set_base_tags_dev.argtypes = L.ivfhnsw_gpu_set_base_tags.argtypes
+        L.ivfhnsw_gpu_clear_base_tags.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_base_tags_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_base_tag_rows.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_exact_search_tags.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_tags.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
@@ -1242,6 +1255,71 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_exact_range_search_slots_dev(self._h, nq, _devptr(d_queries), row_stride,
                                                               _devptr(d_query_slots), C.c_float(radius), _devptr(d_lims),
                                                               C.byref(total)))
+        return int(total.value)
+
+    # ---- base tags: a 16-bit tag per store row, a tag per query (ivfhnsw_gpu_set_base_tags) ---------
+    def set_base_tags(self, rows, tags):
+        """The rows of the base store given carry the tags given (uint16; TAG_NONE untags) from now on; every other row
+        keeps its tag.  The exact _tags calls name a tag per query."""
+        r = _np(rows, np.uint32).ravel()
+        tg = _np(tags, np.uint16).ravel()
+        if tg.size != r.size:
+            raise ValueError("set_base_tags: %d rows, %d tags" % (r.size, tg.size))
+        _check(lib().ivfhnsw_gpu_set_base_tags(self._h, r.size, _ptr(r) if r.size else None, _ptr(tg) if tg.size else None))
+
+    def set_base_tags_dev(self, n, d_rows, d_tags):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_set_base_tags_dev(self._h, n, _devptr(d_rows), _devptr(d_tags)))
+
+    def clear_base_tags(self):
+        """No row of the base store is tagged afterwards."""
+        _check(lib().ivfhnsw_gpu_clear_base_tags(self._h))
+
+    def base_tags_info(self):
+        """(rows_tagged, rows_total, tags_in_use) of the base store."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_tags_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def base_tag_rows(self, tag):
+        """Rows of the base store that carry `tag`."""
+        n = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_tag_rows(self._h, tag, C.byref(n)))
+        return int(n.value)
+
+    def exact_search_tags(self, queries_u8, k, query_tags):
+        """exact_search() with a tag per query: query_tags [nq] uint16, each a tag or TAG_NONE (no restriction); None is
+        exact_search() itself (ivfhnsw_gpu_exact_search_tags)."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_tags(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                   _ptr(qt), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_tags_dev(self, nq, d_queries, row_stride, k, d_query_tags, d_distances, d_labels):
+        """The same on device buffers (d_query_tags: [nq] uint16 in device memory), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_tags_dev(self._h, nq, _devptr(d_queries), row_stride, k,
+                                                       _devptr(d_query_tags), _devptr(d_distances), _devptr(d_labels)))
+
+    def exact_range_search_tags(self, queries_u8, radius, query_tags):
+        """exact_range_search() with a tag per query; lims in the caller's query order."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_tags(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                         _ptr(qt), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_tags_dev(self, nq, d_queries, row_stride, d_query_tags, radius, d_lims):
+        """The same on device buffers; returns the number of results, which stay in the handle's memory."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_tags_dev(self._h, nq, _devptr(d_queries), row_stride,
+                                                             _devptr(d_query_tags), C.c_float(radius), _devptr(d_lims),
+                                                             C.byref(total)))
         return int(total.value)
 
     # ---- measurement ---------------------------------------------------------------------------

@@ -8,9 +8,8 @@
 
 namespace {
 
-// queries per pass of the kernel: bounds the permuted queries and, with the splits, the partial tables (<= 256 MB)
-constexpr size_t kExactChunk = 16384;
-constexpr size_t kExactPartBytes = (size_t)256 << 20;
+// queries per pass of the kernel (kExactChunk: bounds the permuted queries and, with the splits, the partial tables,
+// <= kExactPartBytes = 256 MB): sweep_plan_math.h, with the chunk rule of the _tags calls
 
 // What every exact call checks before it touches anything, in this order: the handle; the store (*b: a view searches its
 // parent's); the call's own arguments (arg_check() returns their error, or 0); and, when there are queries, the buffers
@@ -41,12 +40,41 @@ int exact_guard(ivfhnsw_gpu *h, const char *name, size_t nq, size_t row_stride, 
 }
 
 // A _slots call: the slot byte of every query (device memory once staged), the holder's table and the
-// forms its entries take.  d_slots null: the plain call.
+// forms its entries take.  A _tags call (3.22): the tag of every query, the holder's row lists and its tags in use; its
+// strips are Dense (untagged queries) and Indirect.  Both null: the plain call.
 struct SlotsArg {
     const uint8_t *d_slots = nullptr;
     const StripCols *table = nullptr;
     unsigned forms = 0;
+    const uint16_t *d_tags = nullptr;
+    TagRows tr;
+    size_t tags_in_use = 0;
+    explicit operator bool() const { return d_slots || d_tags; }
+    // the strips a chunk of m queries can have, and the bytes of its plan
+    size_t bound(size_t m) const { return d_tags ? sweep_tag_strip_bound(m, tags_in_use) : sweep_strip_bound(m); }
+    size_t plan_bytes(size_t bound) const { return d_tags ? sweep_tag_plan_bytes(bound) : sweep_strip_plan_bytes(bound); }
 };
+
+// the plan of the chunk of m queries from q0 on (ds / dt: the chunk's slot bytes or tags in device memory)
+int exact_strip_plan(ivfhnsw_gpu *h, const SlotsArg &sl, const uint8_t *ds, const uint16_t *dt, size_t m, void *plan, size_t bound,
+                     StripPlan *sp)
+{
+    if (dt)
+        HIP_TRY(launch_tag_strip_plan(h->stream, dt, m, sl.tr, plan, bound, h->bt_work.as<uint32_t>(), sp));
+    else
+        HIP_TRY(launch_strip_plan(h->stream, ds, m, sl.table, plan, bound, sp));
+    return IVFHNSW_OK;
+}
+
+// what a _tags entry point checks behind the plain call's guard: no base filter installed; the Indirect sweep only where
+// a row is tagged
+int exact_tags_guard(ivfhnsw_gpu *h, const char *who, SlotsArg *sl)
+{
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    const int rc = base_tags_call(b, who, &sl->tr, &sl->tags_in_use);
+    sl->forms = 1u << kSweepColsDense | (b->bt_tagged ? 1u << kSweepColsIndirect : 0u);
+    return rc;
+}
 
 // what a _slots entry point checks behind the plain call's guard, before anything is launched or written: no base filter
 // installed, and the bytes of a host form
@@ -59,9 +87,10 @@ int exact_slots_guard(ivfhnsw_gpu *h, const char *who, size_t nq, const uint8_t 
     return rc;
 }
 
-// query_slots (null: the plain call): one slot byte per query, where the queries are
+// query_slots / query_tags (one of them at most; both null: the plain call): one slot byte or one tag per query, where the
+// queries are
 int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k, float *distances,
-               int64_t *labels, bool on_device, const uint8_t *query_slots = nullptr)
+               int64_t *labels, bool on_device, const uint8_t *query_slots = nullptr, const uint16_t *query_tags = nullptr)
 {
     const ivfhnsw_gpu *b;
     auto k_check = [&] { return k < 1 || k > 100 ? fail(IVFHNSW_ERR_INVALID, "exact_search needs 1 <= k <= 100 (k %zu)", k) : 0; };
@@ -77,20 +106,32 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
         if ((rc = exact_slots_guard(h, "exact_search_slots", nq, query_slots, on_device, &sl)))
             return rc;
         n = b->base_n;
+    } else if (query_tags) { // ... or a tag per query (3.22): each strip's own entry, a tag's row list
+        if ((rc = exact_tags_guard(h, "exact_search_tags", &sl)))
+            return rc;
+        n = b->base_n;
     } else if ((rc = base_filter_cols(h, b, &cols, &n)))
         return rc;
+    const bool strips = query_slots || query_tags;
 
     const size_t first = std::min(nq, kExactChunk);
     const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_splits_for(first, n, (int)k);
     size_t chunk = kExactPartBytes / ((size_t)nsplit * k * sizeof(uint64_t));
     chunk = std::max<size_t>(128, std::min(kExactChunk, chunk / 128 * 128));
+    if (query_tags) { // with many tags the padded rows, not the queries, size the partial tables
+        sl.d_tags = query_tags;
+        chunk = sweep_tag_chunk(nsplit, k, sl.tags_in_use);
+    }
     chunk = std::min(chunk, nq);
     // the rows a chunk is swept as: its queries, or under a strip plan the 32 rows of every strip it can have
-    const size_t bound = query_slots ? sweep_strip_bound(chunk) : 0;
-    const size_t rows = query_slots ? bound * 32 : chunk;
+    const size_t bound = strips ? sl.bound(chunk) : 0;
+    const size_t rows = strips ? bound * 32 : chunk;
     if ((rc = h->ex_q.ensure(rows * d)) || (rc = h->ex_part.ensure((size_t)nsplit * rows * k * sizeof(uint64_t))))
         return rc;
-    if (query_slots && ((rc = h->bs_plan.ensure(sweep_strip_plan_bytes(bound))) || (!on_device && (rc = h->bs_qslots.ensure(chunk)))))
+    if (strips && ((rc = h->bs_plan.ensure(sl.plan_bytes(bound))) ||
+                   (!on_device && (rc = h->bs_qslots.ensure(chunk * (query_tags ? sizeof(uint16_t) : 1))))))
+        return rc;
+    if (query_tags && (rc = h->bt_work.ensure(tag_plan_work_words(chunk) * sizeof(uint32_t))))
         return rc;
     if (!on_device && ((rc = h->ex_raw.ensure(chunk * d)) || (rc = h->ex_dist.ensure(chunk * k * sizeof(float))) ||
                        (rc = h->ex_lab.ensure(chunk * k * sizeof(int64_t)))))
@@ -106,15 +147,19 @@ int exact_impl(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_str
         }
         float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
         int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
-        if (query_slots) {
-            const uint8_t *ds = query_slots + q0;
+        if (strips) {
+            const uint8_t *ds = query_slots ? query_slots + q0 : nullptr;
+            const uint16_t *dt = query_tags ? query_tags + q0 : nullptr;
             if (!on_device) {
-                HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, ds, m, hipMemcpyHostToDevice, h->stream));
-                ds = h->bs_qslots.as<uint8_t>();
+                HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, ds ? (const void *)ds : dt, ds ? m : m * sizeof(uint16_t), hipMemcpyHostToDevice,
+                                       h->stream));
+                ds = ds ? h->bs_qslots.as<uint8_t>() : nullptr;
+                dt = dt ? h->bs_qslots.as<uint16_t>() : nullptr;
             }
             // the chunk's strips, its queries gathered into them in the pass that permutes them, one sweep per form
             StripPlan sp;
-            HIP_TRY(launch_strip_plan(h->stream, ds, m, sl.table, h->bs_plan.p, bound, &sp));
+            if ((rc = exact_strip_plan(h, sl, ds, dt, m, h->bs_plan.p, bound, &sp)))
+                return rc;
             HIP_TRY(launch_rerank_permute_rows(h->stream, src, src_stride, h->ex_q.as<uint8_t>(), rows, (int)d, sp.strip_rows));
             HIP_TRY(launch_exact_search_strips(h->stream, h->ex_q.as<uint8_t>(), b->base_rows.as<uint8_t>(), m, bound, (int)d, (int)k,
                                                nsplit, h->ex_part.as<unsigned long long>(), od, ol, sp, sl.forms));
@@ -230,7 +275,7 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     int rc;
     SweepCols cols; // the columns of the sweep under a base filter, as in exact_impl
     size_t n = b->base_n;
-    if (!sl.d_slots && (rc = base_filter_cols(h, b, &cols, &n)))
+    if (!sl && (rc = base_filter_cols(h, b, &cols, &n)))
         return rc;
     if (thr == 0 || n == 0) { // nothing is below it, or no row passes the base filter: no sweep
         HIP_TRY(hipMemsetAsync(d_lims, 0, (nq + 1) * sizeof(uint64_t), h->stream));
@@ -245,26 +290,28 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     // under a strip plan the rows swept are those of every strip a chunk can have, chunk after chunk
     RangeStrips strips;
     const size_t nchunks = (nq + kExactChunk - 1) / kExactChunk;
-    if (sl.d_slots) {
-        strips.bound = sweep_strip_bound(std::min(nq, kExactChunk));
+    if (sl) {
+        strips.bound = sl.bound(std::min(nq, kExactChunk));
         strips.forms = sl.forms;
         strips.plans.resize(nchunks);
     }
-    const size_t rows = sl.d_slots ? nchunks * strips.bound * 32 : nq;
-    const size_t plan_bytes = sweep_strip_plan_bytes(strips.bound);
+    const size_t rows = sl ? nchunks * strips.bound * 32 : nq;
+    const size_t plan_bytes = sl.plan_bytes(strips.bound);
     size_t map_bytes = 0;
     const int map_shift = exact_range_map_shift(rows, n, d, nsplit, &map_bytes);
     if ((rc = h->ex_q.ensure(rows * d)) || (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) ||
         (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
         (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))) ||
-        (sl.d_slots && (rc = h->bs_plan.ensure(nchunks * plan_bytes))))
+        (sl && (rc = h->bs_plan.ensure(nchunks * plan_bytes))) ||
+        (sl.d_tags && (rc = h->bt_work.ensure(tag_plan_work_words(std::min(nq, kExactChunk)) * sizeof(uint32_t)))))
         return rc;
-    if (sl.d_slots) {
+    if (sl) {
         // per chunk: its strips, and its queries gathered into them in the pass that permutes them
         for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++) {
             StripPlan &sp = strips.plans[i];
-            HIP_TRY(launch_strip_plan(h->stream, sl.d_slots + q0, std::min(kExactChunk, nq - q0), sl.table,
-                                      h->bs_plan.as<unsigned char>() + i * plan_bytes, strips.bound, &sp));
+            if ((rc = exact_strip_plan(h, sl, sl.d_slots ? sl.d_slots + q0 : nullptr, sl.d_tags ? sl.d_tags + q0 : nullptr,
+                                       std::min(kExactChunk, nq - q0), h->bs_plan.as<unsigned char>() + i * plan_bytes, strips.bound, &sp)))
+                return rc;
             sp.map_strip0 = (uint32_t)(i * strips.bound);
             HIP_TRY(launch_rerank_permute_rows(h->stream, d_queries + q0 * row_stride, row_stride,
                                                h->ex_q.as<uint8_t>() + i * strips.bound * 32 * d, strips.bound * 32, (int)d, sp.strip_rows));
@@ -272,7 +319,7 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     } else {
         HIP_TRY(launch_rerank_permute(h->stream, d_queries, row_stride, h->ex_q.as<uint8_t>(), nq, (int)d));
     }
-    const RangeStrips *rs = sl.d_slots ? &strips : nullptr;
+    const RangeStrips *rs = sl ? &strips : nullptr;
     HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
     if ((rc = exact_range_pass(h, b, cols, n, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0, rs)))
@@ -450,6 +497,68 @@ int ivfhnsw_gpu_exact_range_search_slots(ivfhnsw_gpu *h, size_t nq, const uint8_
     HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d, queries, row_stride, d, nq, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, query_slots, nq, hipMemcpyHostToDevice, h->stream));
     sl.d_slots = h->bs_qslots.as<uint8_t>();
+    if ((rc = exact_range_dev(h, nq, h->ex_raw.as<uint8_t>(), d, radius, h->xr_lims.as<uint64_t>(), total, sl)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+// ---- with a base tag per query; query_tags == NULL is the plain call
+
+int ivfhnsw_gpu_exact_search_tags(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                                  const uint16_t *query_tags, float *distances, int64_t *labels)
+{
+    return exact_impl(h, nq, queries, row_stride, k, distances, labels, false, nullptr, query_tags);
+}
+
+int ivfhnsw_gpu_exact_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                      const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels)
+{
+    if (d_query_tags && ((uintptr_t)d_query_tags & 1))
+        return fail(IVFHNSW_ERR_INVALID, "exact_search_tags_dev: query tags must be 2-byte aligned");
+    return exact_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true, nullptr, d_query_tags);
+}
+
+int ivfhnsw_gpu_exact_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
+                                            const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    if (!d_query_tags)
+        return ivfhnsw_gpu_exact_range_search_dev(h, nq, d_queries, row_stride, radius, d_lims, total);
+    int rc = exact_range_guard(h, nq, d_queries, row_stride, radius, d_lims, total);
+    if (rc)
+        return rc;
+    if ((uintptr_t)d_query_tags & 1)
+        return fail(IVFHNSW_ERR_INVALID, "exact_range_search_tags_dev: query tags must be 2-byte aligned");
+    SlotsArg sl;
+    if ((rc = exact_tags_guard(h, "exact_range_search_tags_dev", &sl)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, nullptr, d_lims, total);
+    sl.d_tags = d_query_tags;
+    return exact_range_dev(h, nq, d_queries, row_stride, radius, d_lims, total, sl);
+}
+
+int ivfhnsw_gpu_exact_range_search_tags(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride,
+                                        const uint16_t *query_tags, float radius, uint64_t *lims, uint64_t *total)
+{
+    if (!query_tags)
+        return ivfhnsw_gpu_exact_range_search(h, nq, queries, row_stride, radius, lims, total);
+    int rc = exact_range_guard(h, nq, queries, row_stride, radius, lims, total);
+    if (rc)
+        return rc;
+    SlotsArg sl;
+    if ((rc = exact_tags_guard(h, "exact_range_search_tags", &sl)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, lims, nullptr, total);
+    const size_t d = (h->parent ? h->parent : h)->base_d;
+    if ((rc = h->ex_raw.ensure(nq * d)) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))) ||
+        (rc = h->bs_qslots.ensure(nq * sizeof(uint16_t))))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d, queries, row_stride, d, nq, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, query_tags, nq * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    sl.d_tags = h->bs_qslots.as<uint16_t>();
     if ((rc = exact_range_dev(h, nq, h->ex_raw.as<uint8_t>(), d, radius, h->xr_lims.as<uint64_t>(), total, sl)))
         return rc;
     HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));

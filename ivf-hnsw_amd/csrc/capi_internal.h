@@ -196,7 +196,8 @@ using namespace ivfhnsw_gpu_impl;
     X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts) */ \
     X(tg_table) X(tg_rows) /* row tags: a uint16 per label value, a uint16 per resident row */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
-    X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans, a host call's slot bytes */ \
+    X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans (a _tags call's too), a host call's slot bytes (a _tags call's shorts) */ \
+    X(bt_tags) X(bt_rows) X(bt_off) X(bt_work) /* base tags: a uint16 per store row, the tagged rows by (tag, row), their starts per tag; a call's plan workspace */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
@@ -277,6 +278,13 @@ struct ivfhnsw_gpu {
     // exact _slots call read (form, words or rows, columns), rewritten whenever a slot or the option "exact_filter_form"
     // changes; gone with the store, written again by the first call that needs it.
     BaseSlot bslots[IVFHNSW_FILTER_SLOTS];
+
+    // base tags (capi_base_tags.cpp), on the handle that holds the store, independent of the base filter, of
+    // its slots and of the index's row tags: a view reads its parent's at the call.  bt_tags (null = no tag array, every row
+    // untagged): a uint16 per store row; bt_rows: the bt_tagged tagged row numbers ordered by (tag, row); bt_off
+    // [kTagValues + 1]: tag t's rows are bt_rows [bt_off[t], bt_off[t + 1]).  All three rebuilt by every set_base_tags.
+    uint64_t bt_tagged = 0;
+    uint32_t bt_in_use = 0, bt_max_rows = 0; // tags that have rows; the most rows of one tag
 
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
@@ -599,6 +607,12 @@ int base_slots_table_write(ivfhnsw_gpu *h, bool create);
 // What an exact _slots call of h on holder b's store sweeps: the table (written here if the holder has none yet) and the
 // forms its entries take (bit kSweepCols*; Dense always: "none" may be named).  ERR_STATE with a base filter installed.
 int base_slots_call(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const char *who, const StripCols **table, unsigned *forms);
+
+// ---- capi_base_tags.cpp: base tags
+void base_tags_drop(ivfhnsw_gpu *h); // the handle holds no base tags afterwards (buffers released)
+// What an exact _tags call of h on holder b's store sweeps: the holder's row lists and the tags in use (the strip bound's
+// argument).  ERR_STATE with a base filter installed.
+int base_tags_call(const ivfhnsw_gpu *b, const char *who, TagRows *tr, size_t *tags_in_use);
 
 // ---- capi_range.cpp
 void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)

@@ -17,6 +17,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
         h->base_stage.release();
         base_filter_drop(h); // its rows are gone
         base_slots_drop(h);
+        base_tags_drop(h);
         h->base_n = 0;
         h->base_d = 0;
         return IVFHNSW_OK;
@@ -34,6 +35,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
         h->base_rows.release();
         base_filter_drop(h); // a new store: its row numbers mean other rows
         base_slots_drop(h);
+        base_tags_drop(h);
         h->base_n = 0;
         h->base_d = 0;
         if ((rc = h->base_rows.ensure(n * d)))

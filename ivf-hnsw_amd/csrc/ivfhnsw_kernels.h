@@ -382,6 +382,20 @@ hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp
                                      size_t nx, int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total,
                                      uint32_t *map, int map_shift, float *dist, int64_t *labels, size_t out_cap,
                                      const StripPlan &sp, unsigned forms);
+// Base tags (kernels_exact_filter.hip): a uint16 per row of the store, and the exact sweeps with a tag per query.
+// launch_base_tags_apply: tags[rows[i]] = vals[i] for rows[i] < n; *conflict (zeroed here) != 0 when a row was given two
+// different tags.  launch_base_tags_index: the rows sorted stably by tag (*sorted = ids_a or ids_b [n]; keys [n], hist as
+// launch_sort_by_key's), off [kTagValues + 1] their starts per tag, stats[0] = the tags with rows, stats[1] = the most
+// rows of one tag.  launch_tag_strip_plan: the strip plan of a chunk of m <= kExactChunk queries from their tags d_tags [m]
+// into plan (sweep_tag_plan_bytes(bound) bytes, bound >= sweep_tag_strip_bound(m, tags in use)): every strip carries its
+// own entry, the Dense strips of the untagged queries first, then the Indirect ones; work: tag_plan_work_words(m) words.
+hipError_t launch_base_tags_apply(hipStream_t s, const uint32_t *rows, const uint16_t *vals, size_t cnt, uint64_t n, uint16_t *tags,
+                                  uint32_t *conflict);
+hipError_t launch_base_tags_index(hipStream_t s, const uint16_t *tags, uint64_t n, uint32_t *keys, uint32_t *ids_a, uint32_t *ids_b,
+                                  uint32_t *hist, uint32_t *off, uint32_t *stats, uint32_t **sorted);
+size_t tag_plan_work_words(size_t m);
+hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
+                                 uint32_t *work, StripPlan *sp);
 // appends to the inverted lists (kernels_append.hip) and to the sub-groups of Grouping lists (3.12); the
 // arithmetic and the workspace sizes are update_math.h's.  count: cnt[list_idx[i]] += 1 and, with sub_idx, sizes2[list][sub]
 // += 1 (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  tables: own[c] = old length +

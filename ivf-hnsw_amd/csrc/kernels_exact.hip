@@ -28,6 +28,9 @@
 // With a base filter slot per query (ivfhnsw_gpu_exact_search_slots) the same two kernels run under
 // ColsStrips<map>: the queries are laid out in slot-uniform strips of 32 rows (the plan: kernels_exact_filter.hip), a wave
 // takes its strip's words or rows and column count from the holder's table (sweep_steps.h strip_open), one launch per form.
+//
+// With a base tag per query (ivfhnsw_gpu_exact_search_tags) the strips are tag-uniform and each carries its
+// own entry (ColsStrips<map, true>): Dense for the untagged queries, Indirect over the tag's row list for the others.
 #include "sweep_steps.h"
 
 #include <float.h>
@@ -164,17 +167,24 @@ template <class F> hipError_t by_col_map(const SweepCols &cols, F &&f)
 }
 
 // ... and under a strip plan: one launch per form in `forms` (bit f = form f), each over the plan's strips
-// of that form
-template <class F> hipError_t by_strip_maps(const StripPlan &sp, unsigned forms, F &&f)
+// of that form.  A plan whose strips carry their own entries (base tags) has Dense and Indirect strips only.
+template <bool OWN, class F> hipError_t by_strip_maps_of(const StripPlan &sp, unsigned forms, F &&f)
 {
     hipError_t e = hipSuccess;
     if (e == hipSuccess && (forms >> kSweepColsDense & 1u))
-        e = f(ColsStrips<ColsDense>{sp});
-    if (e == hipSuccess && (forms >> kSweepColsMasked & 1u))
-        e = f(ColsStrips<ColsMasked>{sp});
+        e = f(ColsStrips<ColsDense, OWN>{sp});
+    if constexpr (!OWN)
+        if (e == hipSuccess && (forms >> kSweepColsMasked & 1u))
+            e = f(ColsStrips<ColsMasked>{sp});
     if (e == hipSuccess && (forms >> kSweepColsIndirect & 1u))
-        e = f(ColsStrips<ColsIndirect>{sp});
+        e = f(ColsStrips<ColsIndirect, OWN>{sp});
     return e;
+}
+template <class F> hipError_t by_strip_maps(const StripPlan &sp, unsigned forms, F &&f)
+{
+    if (sp.strip_cols)
+        return (forms >> kSweepColsMasked & 1u) ? hipErrorInvalidValue : by_strip_maps_of<true>(sp, forms, f);
+    return by_strip_maps_of<false>(sp, forms, f);
 }
 
 // the merge under a strip plan, one wavefront per strip row: the row of a query goes to the query's place in the caller's
@@ -391,7 +401,7 @@ hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp
                                      const StripPlan &sp, unsigned forms)
 {
     if (d < 16 || d > 256 || (d & 15) || thr < 0 || bound == 0 || bound > (0x7fffffffull >> 5) || nx >= 0xffffffffull || nsplit < 1 ||
-        nsplit > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.table || !sp.hdr || !sp.strip_slot || !sp.strip_rows)
+        nsplit > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.hdr || !sp.strip_rows || (!sp.strip_cols && (!sp.table || !sp.strip_slot)))
         return hipErrorInvalidValue;
     const int words = sweep_map_words(nx, nsplit, map_shift);
     const dim3 grid((unsigned)((bound + 3) / 4), (unsigned)nsplit);
@@ -443,7 +453,7 @@ hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const ui
     if (nq == 0)
         return hipSuccess;
     if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || bound == 0 || bound > (0x7fffffffull >> 5) || nsplit < 1 || nsplit > 64 ||
-        !sp.table || !sp.hdr || !sp.strip_slot || !sp.strip_rows)
+        !sp.hdr || !sp.strip_rows || (!sp.strip_cols && (!sp.table || !sp.strip_slot)))
         return hipErrorInvalidValue;
     const int rows = (int)(bound * 32);
     long long *lab = reinterpret_cast<long long *>(labels);

@@ -5,8 +5,13 @@
 //   pass rows    the passing row numbers ascending, from the words: a popcount per word, the exclusive scan of the
 //                counts (launch_scan_excl_u32) and a scatter in which every row finds its place by the bits below it.
 // Below them the strip plan of a call with a base filter slot per query: count, layout, scatter.
+// Then base tags: the holder's tag per row with the row lists per tag behind it (a stable sort of the row
+// numbers by tag, launch_sort_by_key), and the strip plan of a call with a tag per query -- one bucket per tag among the
+// chunk's queries, found with the same sort.
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
+
+#include <algorithm>
 
 namespace ivfhnsw_gpu_impl {
 
@@ -121,7 +126,214 @@ __global__ __launch_bounds__(256) void strip_scatter_kernel(const uint8_t *__res
         strip_rows[(size_t)first * 32 + pos] = (int32_t)q;
 }
 
+// ---- base tags: the holder's arrays -------------------------------------------------------------------
+// tags[rows[i]] = vals[i] for the rows inside the store (a row number >= n matches nothing).  Two entries share a 32-bit
+// word; a 16-bit store touches its own half only (as tags_scatter_kernel, kernels_filter.hip).
+__global__ __launch_bounds__(256) void base_tags_scatter_kernel(const uint32_t *__restrict__ rows, const uint16_t *__restrict__ vals,
+                                                                size_t cnt, uint64_t n, uint16_t *__restrict__ tags)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += stride)
+        if (rows[i] < n)
+            tags[rows[i]] = vals[i];
+}
+
+// ... and the check behind it: a row given two different tags kept one of them, so the other entry does not read back
+__global__ __launch_bounds__(256) void base_tags_verify_kernel(const uint32_t *__restrict__ rows, const uint16_t *__restrict__ vals,
+                                                               size_t cnt, uint64_t n, const uint16_t *__restrict__ tags,
+                                                               uint32_t *__restrict__ conflict)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += stride)
+        bad |= rows[i] < n && tags[rows[i]] != vals[i];
+    if (bad)
+        atomicOr(conflict, 1u);
+}
+
+// the sort's keys: a row's tag as 32 bits
+__global__ __launch_bounds__(256) void base_tags_keys_kernel(const uint16_t *__restrict__ tags, uint64_t n, uint32_t *__restrict__ keys)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < n)
+        keys[r] = tags[r];
+}
+
+// off[t] = the rows whose tag is below t, t = 0 .. kTagValues: the first place of the rows sorted by tag whose tag is not
+// below t (a binary search per thread).  Tag t's rows are sorted [off[t], off[t + 1]); off[kTagNone] = the tagged rows.
+__global__ __launch_bounds__(256) void base_tags_offsets_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ sorted,
+                                                                uint32_t n, uint32_t *__restrict__ off)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t > kTagValues)
+        return;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[sorted[mid]] < t)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    off[t] = lo;
+}
+
+// stats (zeroed before): [0] = the tags that have rows, [1] = the most rows of one tag
+__global__ __launch_bounds__(256) void base_tags_stats_kernel(const uint32_t *__restrict__ off, uint32_t *__restrict__ stats)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t c = t < kTagNone ? off[t + 1] - off[t] : 0u;
+    const uint32_t used = (uint32_t)__popcll(__ballot(c != 0));
+    if ((threadIdx.x & 63) == 0 && used)
+        atomicAdd(&stats[0], used);
+    if (c)
+        atomicMax(&stats[1], c);
+}
+
+// ---- base tags: the strip plan of one chunk of an exact _tags call ----------------------------------------------------
+// A query's bucket: 0 for "none" -- so that its strips, the Dense ones, come first -- else its tag + 1.
+__device__ __forceinline__ uint32_t tag_bucket(uint16_t tag) { return ((uint32_t)tag + 1u) & 0xffffu; }
+
+// keys[q] = the bucket of query q; qcnt[bucket] (zeroed before) counts them
+__global__ __launch_bounds__(256) void tag_query_keys_kernel(const uint16_t *__restrict__ qtags, size_t m, uint32_t *__restrict__ keys,
+                                                             uint32_t *__restrict__ qcnt)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= m)
+        return;
+    const uint32_t b = tag_bucket(qtags[q]);
+    keys[q] = b;
+    atomicAdd(&qcnt[b], 1u);
+}
+
+// nstr[b] = the strips of bucket b, b = 0 .. kTagValues (the last: none, the scan's total): ceil(queries / 32) where the
+// bucket sweeps something -- "none" the store, a tag its rows -- else 0, its queries keep the padding
+__global__ __launch_bounds__(256) void tag_bucket_strips_kernel(const uint32_t *__restrict__ qcnt, TagRows tr, uint32_t *__restrict__ nstr)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b > kTagValues)
+        return;
+    uint32_t s = 0;
+    if (b < kTagValues && qcnt[b]) {
+        const bool rows = b == 0 ? tr.n != 0 : tr.off != nullptr && tr.off[b] > tr.off[b - 1];
+        s = rows ? (qcnt[b] + 31) / 32 : 0u;
+    }
+    nstr[b] = s;
+}
+
+// Query sorted[i], the i-th of the chunk's queries in the stable order by bucket, takes row (i - qoff[b]) of its bucket's
+// strips (strip_rows filled with -1 before); the query in a strip's row 0 writes the strip's entry, the first thread the
+// layout.  qoff / sfirst: the exclusive scans of qcnt / nstr.
+__global__ __launch_bounds__(256) void tag_scatter_kernel(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ keys, size_t m,
+                                                          const uint32_t *__restrict__ qoff, const uint32_t *__restrict__ sfirst, TagRows tr,
+                                                          uint32_t bound, StripHdr *__restrict__ hdr, int32_t *__restrict__ strip_rows,
+                                                          StripCols *__restrict__ strip_cols)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) {
+        const uint32_t dense = min(sfirst[1], bound), all = min(sfirst[kTagValues], bound); // (never above: sweep_tag_strip_bound)
+        hdr->lay.range[kSweepColsDense][0] = 0;
+        hdr->lay.range[kSweepColsDense][1] = dense;
+        hdr->lay.range[kSweepColsMasked][0] = hdr->lay.range[kSweepColsMasked][1] = dense;
+        hdr->lay.range[kSweepColsIndirect][0] = dense;
+        hdr->lay.range[kSweepColsIndirect][1] = all;
+        hdr->lay.nstrips = all;
+    }
+    if (i >= m)
+        return;
+    const uint32_t q = sorted[i], b = keys[q];
+    const uint32_t first = sfirst[b], pos = (uint32_t)i - qoff[b];
+    if (sfirst[b + 1] == first)
+        return;
+    const uint32_t strip = first + (pos >> 5);
+    if (strip >= bound)
+        return;
+    strip_rows[(size_t)strip * 32 + (pos & 31)] = (int32_t)q;
+    if ((pos & 31) == 0) {
+        StripCols e;
+        if (b == 0)
+            e = {nullptr, tr.n, (uint32_t)kSweepColsDense};
+        else
+            e = {tr.rows + tr.off[b - 1], tr.off[b] - tr.off[b - 1], (uint32_t)kSweepColsIndirect};
+        strip_cols[strip] = e;
+    }
+}
+
 } // namespace
+
+hipError_t launch_base_tags_apply(hipStream_t s, const uint32_t *rows, const uint16_t *vals, size_t cnt, uint64_t n, uint16_t *tags,
+                                  uint32_t *conflict)
+{
+    if (hipError_t e = hipMemsetAsync(conflict, 0, sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    if (cnt == 0)
+        return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)1 << 16);
+    hipLaunchKernelGGL(base_tags_scatter_kernel, dim3(grid), dim3(256), 0, s, rows, vals, cnt, n, tags);
+    hipLaunchKernelGGL(base_tags_verify_kernel, dim3(grid), dim3(256), 0, s, rows, vals, cnt, n, tags, conflict);
+    return hipGetLastError();
+}
+
+hipError_t launch_base_tags_index(hipStream_t s, const uint16_t *tags, uint64_t n, uint32_t *keys, uint32_t *ids_a, uint32_t *ids_b,
+                                  uint32_t *hist, uint32_t *off, uint32_t *stats, uint32_t **sorted)
+{
+    if (n == 0 || n >= 0xffffffffull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(base_tags_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tags, n, keys);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_sort_by_key(s, keys, n, 16, ids_a, ids_b, hist, sorted); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(base_tags_offsets_kernel, dim3((unsigned)(kTagValues / 256 + 1)), dim3(256), 0, s, keys, *sorted, (uint32_t)n, off);
+    hipLaunchKernelGGL(base_tags_stats_kernel, dim3((unsigned)(kTagValues / 256)), dim3(256), 0, s, off, stats);
+    return hipGetLastError();
+}
+
+size_t tag_plan_work_words(size_t m)
+{
+    return 3 * m + 256 * ((m + kKmeansTile - 1) / kKmeansTile) + 2 * (kTagValues + 1) + append_scan_parts(kTagValues + 1);
+}
+
+hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
+                                 uint32_t *work, StripPlan *sp)
+{
+    if (m == 0 || m > kExactChunk || bound < m / 32 + 1 || bound > 0x7fffffffull / 32 || !d_tags || !plan || !work)
+        return hipErrorInvalidValue;
+    StripHdr *hdr = reinterpret_cast<StripHdr *>(plan);
+    int32_t *rows = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(plan) + sweep_strip_hdr_bytes());
+    StripCols *cols = reinterpret_cast<StripCols *>(rows + bound * 32);
+    uint32_t *keys = work, *ids_a = keys + m, *ids_b = ids_a + m, *hist = ids_b + m;
+    uint32_t *qcnt = hist + 256 * ((m + kKmeansTile - 1) / kKmeansTile), *nstr = qcnt + kTagValues + 1, *part = nstr + kTagValues + 1;
+    if (hipError_t e = hipMemsetAsync(hdr, 0, sweep_strip_hdr_bytes(), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(rows, 0xff, bound * 32 * sizeof(int32_t), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(cols, 0, bound * sizeof(StripCols), s); e != hipSuccess) // (Dense over no column)
+        return e;
+    if (hipError_t e = hipMemsetAsync(qcnt, 0, (kTagValues + 1) * sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    const dim3 grid((unsigned)((m + 255) / 256)), tgrid((unsigned)(kTagValues / 256 + 1));
+    hipLaunchKernelGGL(tag_query_keys_kernel, grid, dim3(256), 0, s, d_tags, m, keys, qcnt);
+    hipLaunchKernelGGL(tag_bucket_strips_kernel, tgrid, dim3(256), 0, s, qcnt, tr, nstr);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    uint32_t *sorted = nullptr;
+    if (hipError_t e = launch_sort_by_key(s, keys, m, 16, ids_a, ids_b, hist, &sorted); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_scan_excl_u32(s, qcnt, kTagValues + 1, part); e != hipSuccess)
+        return e;
+    if (hipError_t e = launch_scan_excl_u32(s, nstr, kTagValues + 1, part); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(tag_scatter_kernel, grid, dim3(256), 0, s, sorted, keys, m, qcnt, nstr, tr, (uint32_t)bound, hdr, rows, cols);
+    sp->table = nullptr;
+    sp->hdr = hdr;
+    sp->strip_slot = nullptr;
+    sp->strip_rows = rows;
+    sp->strip_cols = cols;
+    return hipGetLastError();
+}
 
 hipError_t launch_strip_plan(hipStream_t s, const uint8_t *d_slots, size_t m, const StripCols *table, void *plan, size_t bound,
                              StripPlan *sp)

@@ -140,16 +140,59 @@ struct StripHdr {
     uint32_t counts[kStripBuckets], cursor[kStripBuckets];
     StripLayout lay;
 };
+// A strip's entry comes from the slot table (table[strip_slot[strip]], base filter slots) or, under base tags (DESIGN.md
+// 3.22), from an entry of its own (strip_cols[strip]): which of the two is the column map's to say (ColsStrips), at
+// compile time.
 struct StripPlan {
     const StripCols *table = nullptr;
     const StripHdr *hdr = nullptr;
     const uint8_t *strip_slot = nullptr;
     const int32_t *strip_rows = nullptr;
     uint32_t map_strip0 = 0;
+    const StripCols *strip_cols = nullptr;
 };
 // bytes of a chunk's plan of `bound` strips: header, rows, slots (each part 16-byte aligned)
 inline size_t sweep_strip_hdr_bytes() { return (sizeof(StripHdr) + 15) & ~(size_t)15; }
 inline size_t sweep_strip_plan_bytes(size_t bound) { return sweep_strip_hdr_bytes() + bound * 32 * sizeof(int32_t) + ((bound + 15) & ~(size_t)15); }
+
+// ---- base tags: the exact sweeps with a 16-bit tag per store row and per query
+// queries per pass of the exact k-search, and the bytes its partial tables [nsplit][rows][k] may take
+constexpr size_t kExactChunk = 16384;
+constexpr size_t kExactPartBytes = (size_t)256 << 20;
+constexpr uint32_t kTagNone = 0xffffu;  // = IVFHNSW_TAG_NONE
+constexpr size_t kTagValues = 65536;    // tag_off has kTagValues + 1 entries: tag t's rows are [tag_off[t], tag_off[t + 1])
+
+// Strips of 32 queries, each of one tag: at most this many for m queries on a store with tags_in_use tags.  A bucket is a
+// tag with rows, or "none"; there are at most min(m, tags_in_use + 1) non-empty ones, and the sum over them of
+// ceil(c / 32) <= sum of floor(c / 32) + their number <= m / 32 + min(m, tags_in_use + 1).
+SWEEP_HD inline size_t sweep_tag_strip_bound(size_t m, size_t tags_in_use)
+{
+    const size_t buckets = tags_in_use + 1;
+    return m / 32 + (m < buckets ? m : buckets);
+}
+
+// Queries per pass of a _tags k-search: the most, in multiples of 128 up to kExactChunk, whose partial tables over the
+// PADDED rows stay within kExactPartBytes -- nsplit * bound(chunk) * 32 * k * 8 bytes.  At 128 it always fits (nsplit <= 64,
+// k <= 100: 64 * 132 * 32 * 100 * 8 = 216 MB), so the answer is never below 128.
+inline size_t sweep_tag_chunk(int nsplit, size_t k, size_t tags_in_use)
+{
+    const size_t per_strip = (size_t)nsplit * 32 * k * sizeof(uint64_t);
+    size_t chunk = kExactChunk;
+    while (chunk > 128 && per_strip * sweep_tag_strip_bound(chunk, tags_in_use) > kExactPartBytes)
+        chunk -= 128;
+    return chunk;
+}
+
+// What the holder keeps for the plan: rows = the tagged row numbers ordered by (tag, row), off [kTagValues + 1] their
+// starts per tag, n = the rows of the store.  off null: no tag array, every row is untagged.
+struct TagRows {
+    const uint32_t *off = nullptr;
+    const uint32_t *rows = nullptr;
+    uint32_t n = 0;
+};
+
+// bytes of a chunk's tag plan of `bound` strips: header, rows, one entry per strip
+inline size_t sweep_tag_plan_bytes(size_t bound) { return sweep_strip_hdr_bytes() + bound * 32 * sizeof(int32_t) + bound * sizeof(StripCols); }
 
 // f(int_c<NS>()) for NS = ceil(d / 32) = 1 .. 8, the steps of 32 bytes a row of the uint8 store is read in (d <= 256)
 template <class F> auto by_row_steps(int d, F &&f)

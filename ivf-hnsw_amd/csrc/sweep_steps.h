@@ -1,7 +1,7 @@
 // The steps the brute-force MFMA sweeps share, one copy each: the C/D row map, the selection of a row's k
 // smallest keys through its LDS buffer (knn_mfma_kernel, exact_mfma_kernel), the int8 strip that reads the uint8 store
 // (exact_mfma_kernel, exact_range_kernel), the column maps those two sweep under when the store has a base filter
-// (ColsDense / ColsMasked / ColsIndirect, ColCursor; per 32-row strip under base filter slots: ColsStrips, strip_open) and the merge of the splits' partial tables.  Control flow -- which tile comes
+// (ColsDense / ColsMasked / ColsIndirect, ColCursor; per 32-row strip under base filter slots and base tags: ColsStrips, strip_open) and the merge of the splits' partial tables.  Control flow -- which tile comes
 // next, what a tile without a candidate costs, what is done with a distance that passes -- stays in the kernels.  Host
 // arithmetic (columns per split, split count): sweep_plan_math.h.
 #pragma once
@@ -245,8 +245,10 @@ struct ColsIndirect {
 // (sweep_plan_math.h StripPlan): the wave whose strip of the launch is i owns strip range[B][0] + i, reads that strip's
 // table entry once -- everything in it is wave-uniform -- and sweeps the entry's columns under B.  The rows of the strip
 // are rows [32 strip, + 32) of the gathered queries; strip_rows says which of the call's queries each is.
-template <class B> struct ColsStrips {
-    static constexpr bool kMasked = B::kMasked, kIndirect = B::kIndirect, kStrips = true;
+// OWN: the strip's entry is its own, strip_cols[strip] (base tags, DESIGN.md 3.22: one bucket per tag among the chunk's
+// queries, far more than a table of slots holds); else it is the slot table's, table[strip_slot[strip]].
+template <class B, bool OWN = false> struct ColsStrips {
+    static constexpr bool kMasked = B::kMasked, kIndirect = B::kIndirect, kStrips = true, kOwnEntries = OWN;
     using Base = B;
     StripPlan sp;
 };
@@ -269,7 +271,11 @@ __device__ __forceinline__ bool strip_open(const CM &cm, int nsplit, int split, 
         const uint32_t strip = __builtin_amdgcn_readfirstlane(cm.sp.hdr->lay.range[f][0] + (uint32_t)(r0 >> 5));
         if (strip >= cm.sp.hdr->lay.range[f][1])
             return false;
-        const StripCols e = cm.sp.table[cm.sp.strip_slot[strip]];
+        StripCols e;
+        if constexpr (CM::kOwnEntries)
+            e = cm.sp.strip_cols[strip];
+        else
+            e = cm.sp.table[cm.sp.strip_slot[strip]];
         base.take(e.data);
         sweep_split_cut(e.nx, nsplit, split, &c_begin, &c_end);
         r0 = (int)(strip << 5);

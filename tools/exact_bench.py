@@ -22,11 +22,17 @@
      (a) one exact_search_slots_dev call, (b) the loop that answers the same batch without slots -- per slot
      set_base_filter_dev then exact_search_dev on that slot's queries, NONE's unfiltered -- with and without the installs,
      (c) the plain unfiltered call on the whole batch; k = 1 and k = 100; and the range form against its per-slot loop.
+  6. With --tags, on both stores, base tags (ivfhnsw_gpu_exact_search_tags_dev), run twice: with 32 tags of
+     1/32 of the rows each and with 1 024 tags in the distribution of tools/filter_recall.py --tags, 1/33 of the queries
+     untagged.  Timed alternating in one run: (a) one exact_search_tags_dev call, (b) the loop it replaces -- per tag
+     present set_base_filter_dev then exact_search_dev on that tag's queries -- with and without the installs, (c) at 32
+     tags one exact_search_slots_dev call over the same partition; k = 1 and k = 100; the range form at the median k = 10
+     distance; and the time of set_base_tags_dev over every row.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
-                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots]
+                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags]
                                    [--dense-nq 512]
                                    [--out result.json]"""
 import argparse
@@ -101,6 +107,7 @@ def main():
     ap.add_argument("--no-range", action="store_true", help="skip the exact range search legs")
     ap.add_argument("--filter", action="store_true", help="add the base-filter legs (DESIGN.md 3.18)")
     ap.add_argument("--filter-slots", action="store_true", help="add the base-filter-slot legs (DESIGN.md 3.20)")
+    ap.add_argument("--tags", action="store_true", help="add the base-tag legs (DESIGN.md 3.22)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -282,6 +289,115 @@ def main():
             print(json.dumps(r), flush=True)
         g.clear_base_filter_slot()
 
+    def tags_legs(n, name, d10, ntags):
+        """One _tags call against the per-tag loop of single-filter calls (and, at 32 tags, one _slots call), alternating."""
+        none_share, none = 33, 0xffff  # 1/33 of the queries untagged
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(7000 + ntags)
+        order = torch.randperm(n, device=dev, generator=gen)
+        tags = torch.empty(n, dtype=torch.int16, device=dev)
+        if ntags == 32:  # 1/32 of the rows each
+            tags[order] = (torch.arange(n, device=dev) % 32).to(torch.int16)
+        else:            # the distribution of tools/filter_recall.py: tags 0..3 hold 1/8 each, the others share the rest
+            big = n // 8
+            for t in range(4):
+                tags[order[t * big:(t + 1) * big]] = t
+            rest = order[4 * big:]
+            tags[rest] = (4 + torch.arange(rest.numel(), device=dev) % (ntags - 4)).to(torch.int16)
+        del order
+        all_rows = torch.arange(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        t_set, ts_set = timed(torch, dev, lambda: g.set_base_tags_dev(n, all_rows, tags), args.warmup, args.reps,
+                              "%s set_base_tags %d tags" % (name, ntags))
+        tagged, total, in_use = g.base_tags_info()
+        assert (tagged, total, in_use) == (n, n, ntags)
+        r = {"what": "set_base_tags_dev", "rows": n, "tags": ntags, "seconds": round(t_set, 5), "reps": [round(x, 5) for x in ts_set],
+             "memory_GB": round(g.memory_bytes() / 1e9, 3)}
+        result["rows"].append(r)
+        print(json.dumps(r), flush=True)
+        del all_rows
+        qt = (torch.arange(nq, device=dev) % ntags).to(torch.int32)
+        qt[torch.arange(nq, device=dev) % none_share == none_share - 1] = none
+        qt = qt[torch.randperm(nq, device=dev, generator=gen)].contiguous()
+        qtags = qt.to(torch.int16).contiguous()  # the bit pattern of the uint16
+        # the rows of every tag, ascending: one stable sort
+        by_tag = torch.sort(tags.to(torch.int32), stable=True)
+        counts = torch.bincount(by_tag.values, minlength=ntags).cpu().tolist()
+        row_lists, at = [], 0
+        for t in range(ntags):
+            row_lists.append(by_tag.indices[at:at + counts[t]].to(torch.int32).contiguous())
+            at += counts[t]
+        del by_tag
+        present = sorted(set(qt.cpu().tolist()))
+        sub = [(t, q[(qt == t).nonzero().flatten()].contiguous()) for t in present]
+        if ntags == 32:
+            for s in range(32):
+                g.set_base_filter_slot_dev(s, row_lists[s].numel(), row_lists[s])
+            qs = qt.to(torch.uint8).contiguous()  # 0xffff -> 0xff: NONE in both
+        torch.cuda.synchronize(dev)
+        radius = float(d10.median())
+
+        def loop(k, od, ol):
+            """the parent commit's way, per tag present: (seconds with the installs, seconds of the searches alone)"""
+            t_all = t_search = 0.0
+            for t, qsub in sub:
+                t0 = time.perf_counter()
+                if t == none:
+                    g.clear_base_filter()
+                else:
+                    g.set_base_filter_dev(row_lists[t].numel(), row_lists[t])
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                if k:
+                    g.exact_search_dev(qsub.shape[0], qsub, d, k, od[:qsub.shape[0]], ol[:qsub.shape[0]])
+                else:
+                    g.exact_range_search_dev(qsub.shape[0], qsub, d, radius, lims)
+                torch.cuda.synchronize(dev)
+                t2 = time.perf_counter()
+                t_all += t2 - t0
+                t_search += t2 - t1
+            g.clear_base_filter()
+            return t_all, t_search
+
+        for k in (1, 100, 0):  # 0: the range form
+            od = torch.empty((nq, max(k, 1)), dtype=torch.float32, device=dev)
+            ol = torch.empty((nq, max(k, 1)), dtype=torch.int64, device=dev)
+            ta, tb, tbi, tc = [], [], [], []
+            for rep in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                if k:
+                    g.exact_search_tags_dev(nq, q, d, k, qtags, od, ol)
+                else:
+                    g.exact_range_search_tags_dev(nq, q, d, qtags, radius, lims)
+                torch.cuda.synchronize(dev)
+                a = time.perf_counter() - t0
+                full, only = loop(k, od, ol)
+                c = float("nan")
+                if ntags == 32:
+                    t0 = time.perf_counter()
+                    if k:
+                        g.exact_search_slots_dev(nq, q, d, k, qs, od, ol)
+                    else:
+                        g.exact_range_search_slots_dev(nq, q, d, qs, radius, lims)
+                    torch.cuda.synchronize(dev)
+                    c = time.perf_counter() - t0
+                log("[exact_bench] %s %d tags k=%d rep %d: tags call %.4f s, loop %.4f s (searches alone %.4f s), slots call %.4f s"
+                    % (name, ntags, k, rep, a, full, only, c))
+                if rep >= args.warmup:
+                    ta.append(a), tbi.append(full), tb.append(only), tc.append(c)
+            ma, mbi, mb, mc = (statistics.median(x) for x in (ta, tbi, tb, tc))
+            r = {"what": "exact_search_tags_dev" if k else "exact_range_search_tags_dev", "rows": n, "d": d, "nq": nq,
+                 "k": k if k else None, "radius_value": None if k else radius, "tags": ntags, "tags_present": len(present),
+                 "unfiltered_share": "1/%d" % none_share, "tags_call_s": round(ma, 5), "loop_with_installs_s": round(mbi, 5),
+                 "loop_searches_only_s": round(mb, 5), "slots_call_s": round(mc, 5) if ntags == 32 else None,
+                 "loop_with_installs_over_tags": round(mbi / ma, 3), "loop_searches_only_over_tags": round(mb / ma, 3),
+                 "reps_tags": [round(x, 5) for x in ta]}
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+        if ntags == 32:
+            g.clear_base_filter_slot()
+        g.clear_base_tags()
+
     def yardstick_and_range(n, dense_radius=None, fractions=(1, 2, 8, 32, 1024)):
         name = "%d rows" % n
         r1, _, _ = exact(n, 1, name)
@@ -290,6 +406,9 @@ def main():
             filter_legs(n, name, {1: r1["seconds"], 100: r100["seconds"]}, fractions)
         if args.filter_slots:
             slots_legs(n, name, od100[:, 9])
+        if args.tags:
+            for ntags in (32, 1024):
+                tags_legs(n, name, od100[:, 9], ntags)
         if not args.no_range:
             range_legs(n, name, r1["seconds"], od100[:, 9], od100[:, 99], dense_radius)
 

@@ -13,7 +13,9 @@ against ONE exact_search_slots call, Recall@1 and Recall@10 per pass fraction.
 With --tags: every row gets one of 1 024 tags -- tag t < 4 holds 1/8 of the rows each, the other half is
 spread evenly over the tags 4..1023 -- and the queries are dealt over a sample of tags and NONE; ONE search_tags call is
 scored against the truth of a tagged search, the per-tag loop of set_base_filter + exact_search.
-usage: python tools/filter_recall.py [--seed 77] [--slots | --tags] [--out result.json]"""
+With --base-tags: the same corpus and tags, installed on the store as well (ivfhnsw_gpu_set_base_tags); the
+queries are dealt over ALL 1 024 tags and NONE, and ONE search_tags call is scored against ONE exact_search_tags call.
+usage: python tools/filter_recall.py [--seed 77] [--slots | --tags | --base-tags] [--out result.json]"""
 import argparse
 import json
 import os
@@ -188,16 +190,60 @@ def tags_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
     return {"rows": n, "nq": nq, "tags": 1024, "tags_recall": rows_out}
 
 
+def base_tags_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
+    """Recall of one search_tags call against ONE exact_search_tags call, the queries dealt over ALL 1 024 tags and NONE
+    (the --tags corpus and tag assignment).  Returns the report; its "truth" / "query_tags" / "tags" entries are the arrays
+    themselves, for a test to compare."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    tags = tag_assignment(n, seed)
+    rows = np.arange(n, dtype=np.uint32)
+    g.set_tags(rows, tags)      # ids = row numbers of the base: the index and the store carry the same tags
+    g.set_base_tags(rows, tags)
+    assert g.tags_info() == (n, n, n) and g.base_tags_info() == (n, n, np.unique(tags).size)
+    # the tags of TAG_SAMPLE first (what --tags scores), then every other tag in a seeded order, dealt in turn
+    others = np.setdiff1d(np.arange(1024), TAG_SAMPLE)
+    every = np.concatenate([TAG_SAMPLE, np.random.default_rng(seed + 4).permutation(others)]).astype(np.uint16)
+    qt = every[np.arange(nq) % every.size]
+    _, truth = g.exact_search_tags(q8, 10, qt)
+    rows_out = []
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_tags(qf, 10, qt, nprobe, max_codes, efSearch=ef)
+        assert g.last_scan_kernel().endswith("+tags")
+        for name, sel in (("1/8 (tags 0..3)", qt < 4), ("~1/2040 (small tags)", (qt >= 4) & (qt != TAG_NONE)),
+                          ("1 (no tag)", qt == TAG_NONE)):
+            idx = np.flatnonzero(sel)
+            r1, r10 = recall_pair(lab[idx], truth[idx]) if idx.size else (float("nan"), float("nan"))
+            rows_out.append({"pass_fraction": name, "queries": int(idx.size), "tags_named": int(np.unique(qt[idx]).size),
+                             "nprobe": nprobe, "max_codes": max_codes, "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] base tags, %s (%d queries on %d tags), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, idx.size, np.unique(qt[idx]).size, nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "tags": 1024, "base_tags_recall": rows_out, "truth": truth, "query_tags": qt, "tags_of_rows": tags}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
     ap.add_argument("--tags", action="store_true", help="one search_tags call against the per-tag base-filter loop")
+    ap.add_argument("--base-tags", action="store_true", help="one search_tags call against one exact_search_tags call, "
+                                                              "the queries over all 1 024 tags")
     ap.add_argument("--slots", action="store_true", help="one search_slots call against one exact_search_slots call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
-    if args.tags:
+    if args.base_tags:
+        out = base_tags_recall(pkg, args.seed)
+        out = {k: v for k, v in out.items() if k not in ("truth", "query_tags", "tags_of_rows")}
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    elif args.tags:
         out = tags_recall(pkg, args.seed)
         out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
     elif args.slots:

@@ -15,8 +15,13 @@ FILTERED workload is written: the base filter (ivfhnsw_gpu_set_base_filter, DESI
 search, so only rows in the allow set (not in the deny set) are returned.  The .npz of the range form then also holds
 filter_mode (0 allow, 1 deny; -1 without a filter) and rows_passing; read_range_filter reads them.
 
+With --tags FILE --query-tags FILE (both .npy files of uint16: one tag per row of the base, one per query; 0xffff = no tag)
+the truth of a TAGGED workload is written: the base tags (ivfhnsw_gpu_set_base_tags) are installed and the
+_tags form of either search runs, so query q gets only rows whose tag is query_tags[q] (every row when it is 0xffff).
+
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
-       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]"""
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy"""
 import argparse
 import os
 import sys
@@ -87,6 +92,24 @@ def read_labels(path):
     return lab.astype(np.uint32)
 
 
+def read_tags(path):
+    """The tags of a --tags / --query-tags file as uint16 [n]: an .npy array of integers in 0..0xffff, of any shape."""
+    t = np.load(path)
+    if t.dtype.kind not in "iu":
+        raise ValueError("%s: tags must be integers, not %s" % (path, t.dtype))
+    t = t.ravel().astype(np.int64)
+    if t.size and (t.min() < 0 or t.max() > 0xffff):
+        raise ValueError("%s: tags must fit 16 bits unsigned" % path)
+    return t.astype(np.uint16)
+
+
+def install_tags(g, n, nq, tags, query_tags):
+    """The base tags of a tagged workload on g's store of n rows, the two arrays checked against the store and the queries."""
+    if tags.size != n or query_tags.size != nq:
+        raise ValueError("%d tags for %d rows, %d query tags for %d queries" % (tags.size, n, query_tags.size, nq))
+    g.set_base_tags(np.arange(n, dtype=np.uint32), tags)
+
+
 def read_range(path):
     """(lims uint64 [nq + 1], distances float32 [total], labels int64 [total], radius) of a file --radius wrote; lims is
     checked against the arrays."""
@@ -117,9 +140,11 @@ def read_bvecs_image(path):
     return img, d
 
 
-def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False):
+def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False, tags=None,
+                 query_tags=None):
     """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query; with `labels`
-    only of the rows whose number is in them (deny: is not)."""
+    only of the rows whose number is in them (deny: is not); with `tags` and `query_tags` only of the rows that carry the
+    query's tag."""
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
@@ -128,14 +153,18 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
             raise ValueError("base dimension %d, query dimension %d" % (d, dq))
         if labels is not None:
             g.set_base_filter(labels, deny=deny)
-        _, lab = g.exact_search(img[:, 4:], k)
+        if tags is not None:
+            install_tags(g, n, img.shape[0], tags, query_tags)
+            _, lab = g.exact_search_tags(img[:, 4:], k, query_tags)
+        else:
+            _, lab = g.exact_search(img[:, 4:], k)
     finally:
         g.close()
     return lab
 
 
 def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False,
-                       info=None):
+                       info=None, tags=None, query_tags=None):
     """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
     `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing."""
     img, dq = read_bvecs_image(query_path)
@@ -148,6 +177,11 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
             g.set_base_filter(labels, deny=deny)
             if info is not None:
                 info["rows_passing"] = g.base_filter_info()[1]
+        if tags is not None:
+            install_tags(g, n, img.shape[0], tags, query_tags)
+            if info is not None:
+                info["rows_passing"] = g.base_tags_info()[0]  # the tagged rows
+            return g.exact_range_search_tags(img[:, 4:], radius, query_tags)
         return g.exact_range_search(img[:, 4:], radius)
     finally:
         g.close()
@@ -166,7 +200,13 @@ def main(argv=None):
     flt = ap.add_mutually_exclusive_group()
     flt.add_argument("--allow", default=None, help="an .ivecs or .npy file of labels: only these rows of the base are returned")
     flt.add_argument("--deny", default=None, help="an .ivecs or .npy file of labels: these rows of the base are never returned")
+    ap.add_argument("--tags", default=None, help="an .npy file of uint16: the tag of every row of the base (0xffff: none)")
+    ap.add_argument("--query-tags", default=None, help="an .npy file of uint16: the tag of every query (0xffff: every row)")
     args = ap.parse_args(argv)
+    if (args.tags is None) != (args.query_tags is None) or (args.tags and (args.allow or args.deny)):
+        ap.error("--tags and --query-tags go together, and not with --allow / --deny")
+    tags = read_tags(args.tags) if args.tags else None
+    query_tags = read_tags(args.query_tags) if args.tags else None
     labels = read_labels(args.allow or args.deny) if (args.allow or args.deny) else None
     deny = args.deny is not None
     sys.path.insert(0, ROOT)
@@ -175,12 +215,13 @@ def main(argv=None):
     if args.radius is not None:
         info = {}
         lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device,
-                                             labels=labels, deny=deny, info=info)
+                                             labels=labels, deny=deny, info=info, tags=tags, query_tags=query_tags)
         write_range(args.out, lims, dist, lab, args.radius, filter_mode=-1 if labels is None else int(deny),
                     rows_passing=info.get("rows_passing"))
         print("%s: %d queries, %d rows within %g" % (args.out, lims.size - 1, lab.size, args.radius))
         return
-    lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device, labels=labels, deny=deny)
+    lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device, labels=labels, deny=deny,
+                       tags=tags, query_tags=query_tags)
     write_ivecs(args.out, lab)
     print("%s: %d queries x %d labels" % (args.out, lab.shape[0], lab.shape[1]))
 
