@@ -179,7 +179,7 @@ using namespace ivfhnsw_gpu_impl;
 #define IVFHNSW_GPU_DEVBUFS(X) \
     X(goff) X(loff) X(cnorm) X(pqc) X(ntab) X(opq_at) X(opq_a) X(codes) X(ncodes) X(ids) /* index tables */ \
     X(g_alpha) X(g_nn) X(g_sizes) X(g_inter) /* Grouping tables */ \
-    X(q_counts) X(q_links) X(q_vectors) X(q_qrows) X(q_nbrows) X(q_nbnorms) X(q_fat) X(q_links_c) /* quantizer */ \
+    X(q_counts) X(q_links) X(q_vectors) X(q_qrows) X(q_nbrows) X(q_nbnorms) X(q_fat) X(q_links_c) X(q_rowerr) /* quantizer */ \
     X(e_pqc) X(e_ntab) X(e_a) X(e_at) X(e_x) X(e_idx) X(e_dist) X(e_res) X(e_tmp) X(e_codes) X(e_ncodes) /* code books, encode */ \
     X(t_x) X(t_y) X(t_cb) X(t_assign) X(t_part) X(t_c) /* pq_train, xty */ \
     X(k_q) X(k_x) X(k_qn) X(k_xn) X(k_part) X(k_ids) X(k_dists) /* knn */ \

@@ -1,5 +1,6 @@
 // Uploads and downloads of the index tables: IVF lists, Grouping tables, the HNSW quantizer and its derived rows.
 #include "capi_internal.h"
+#include "walk_bound.h"
 #include "walk_form.h"
 
 namespace {
@@ -313,8 +314,9 @@ try {
 
 // The walk's exact rejection filter (kernels_hnsw.hip): one byte per component, x ~ lo + step * byte with one
 // (lo, step) for the whole table, and the largest row error ||x - (lo + step*byte)|| in units of step, rounded
-// up.  Tables with non-finite values, a single value or d > 2048 run without the filter (always exact, only
-// slower); IVFHNSW_WALK_PREFILTER=0 turns it off for A/B runs.
+// up -- and every row's own error as a 9-bit code in steps of 1/511 of the largest (walk_bound.h), which the
+// neighbour rows' norm table carries to the walk.  Tables with non-finite values, a single value or d > 2048 run
+// without the filter (always exact, only slower); IVFHNSW_WALK_PREFILTER=0 turns it off for A/B runs.
 static int build_byte_rows(ivfhnsw_gpu *h, size_t n, size_t d, const float *vectors)
 {
     static const bool off = [] {
@@ -336,6 +338,7 @@ static int build_byte_rows(ivfhnsw_gpu *h, size_t n, size_t d, const float *vect
         return IVFHNSW_OK;
     std::vector<uint8_t> rows(n * d);
     double worst = 0.0;
+    std::vector<double> row_e2(n);
     for (size_t r = 0; r < n; r++) {
         double e2 = 0.0;
         for (size_t j = 0; j < d; j++) {
@@ -346,19 +349,27 @@ static int build_byte_rows(ivfhnsw_gpu *h, size_t n, size_t d, const float *vect
             const double e = x - ((double)lo + (double)step * c);
             e2 += e * e;
         }
+        row_e2[r] = e2;
         worst = std::max(worst, e2);
     }
-    const double errc = std::sqrt(worst) / (double)step * (1.0 + 1e-6) + 1e-6;
+    const double errc = walk_err_round_up(worst, (double)step);
     float errc_f = (float)errc;
     if ((double)errc_f < errc)
         errc_f = std::nextafter(errc_f, INFINITY);
+    const float unit = walk_err_unit(errc_f);
+    std::vector<uint16_t> codes(n);
+    for (size_t r = 0; r < n; r++)
+        codes[r] = (uint16_t)walk_err_code(walk_err_round_up(row_e2[r], (double)step), unit);
     int rc = upload(h->q_qrows, rows.data(), n * d);
     if (rc)
+        return rc;
+    if ((rc = upload(h->q_rowerr, codes.data(), n * sizeof(uint16_t))))
         return rc;
     h->gr.qrows = h->q_qrows.as<uint8_t>();
     h->gr.q_lo = lo;
     h->gr.q_step = step;
     h->gr.q_errc = errc_f;
+    h->gr.q_errunit = unit;
     return IVFHNSW_OK;
 }
 
@@ -389,7 +400,7 @@ static int build_neighbour_rows(ivfhnsw_gpu *h)
     if ((rc = h->q_links_c.ensure((size_t)h->gr.n * h->gr.maxM * sizeof(uint32_t))))
         return rc;
     HIP_TRY(launch_build_nbrows(h->stream, h->gr, h->q_nbrows.as<uint8_t>(), h->q_nbnorms.as<uint32_t>(), nb_rows,
-                                h->q_links_c.as<uint32_t>()));
+                                h->q_links_c.as<uint32_t>(), h->q_rowerr.as<uint16_t>()));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->gr.nbrows = h->q_nbrows.as<uint8_t>();
     h->gr.nbnorms = h->q_nbnorms.as<uint32_t>();
@@ -492,6 +503,7 @@ try {
     h->gr.q_lo = 0.f;
     h->gr.q_step = 1.f;
     h->gr.q_errc = 0.f;
+    h->gr.q_errunit = 0.f;
     if ((rc = build_byte_rows(h, n, d, vectors)))
         return rc;
     if ((rc = build_neighbour_rows(h)))

@@ -141,11 +141,14 @@ struct GraphTables {
     // x ~ q_lo + q_step * byte, with q_errc >= max_row ||x - (q_lo + q_step*byte)|| / q_step.  NULL = filter off.
     const uint8_t *qrows;    // [n][d]
     float q_lo, q_step, q_errc;
+    float q_errunit;         // q_errc / 511 rounded up: what one step of a row's error code is worth (walk_bound.h)
     // The same bytes once more, laid out for the walk (d <= 128): node i carries the byte rows of its own
     // neighbours, [n][nb_rows][128] with nb_rows = maxM rounded up to 32, zero padded.  One contiguous
     // nb_rows*128-byte read per expansion, issued together with the link list.  NULL = gather from qrows.
     const uint8_t *nbrows;
-    const uint32_t *nbnorms; // [n][nb_rows] sum of bytes^2 of every neighbour row (the filter's ||c||^2 term)
+    // [n][nb_rows] sum of bytes^2 of every neighbour row (the filter's ||c||^2 term, 23 bits), and above it the row's own
+    // error ||x - (q_lo + q_step*byte)|| / q_step in steps of q_errunit, rounded up (9 bits)
+    const uint32_t *nbnorms;
     const uint32_t *links_c; // [n][maxM] id | (link count of id) << 24; goes with nbrows: the walk's keys carry the count
     int nb_rows;
     // Latency form of the walk (kernels_hnsw_lat.hip): node i carries the FLOAT rows of its own neighbours,
@@ -325,8 +328,9 @@ hipError_t launch_group_alpha(hipStream_t s, const unsigned long long *offsets, 
 hipError_t launch_group_rows(hipStream_t s, const unsigned long long *offsets, const uint32_t *sub, uint32_t *rows,
                              size_t ngroups, int nsubc);
 // nbrows[i][j] = qrows[links[i][j]] for j < counts[i], zero otherwise (GraphTables::nbrows)
+// row_err: [n] every row's error code (walk_err_code)
 hipError_t launch_build_nbrows(hipStream_t s, const GraphTables &g, uint8_t *nbrows, uint32_t *nbnorms, int nb_rows,
-                               uint32_t *links_c);
+                               uint32_t *links_c, const uint16_t *row_err);
 hipError_t launch_fill_bytes(hipStream_t s, uint8_t *dst, size_t nbytes, uint64_t seed);
 hipError_t launch_fill_iota(hipStream_t s, uint32_t *dst, size_t n, uint32_t first);
 hipError_t launch_fill_lists(hipStream_t s, const IvfTables &t, uint8_t *codes, uint8_t *norm_codes, uint32_t *ids,

@@ -27,6 +27,7 @@
 #include "device_common.h"
 #include "walk_set.h"
 #include "walk_form.h"
+#include "walk_bound.h"
 
 #include <float.h>
 #include <stdio.h>
@@ -199,6 +200,11 @@ __device__ __forceinline__ unsigned long long walk_stamp()
 // redo_hdr: [0] number of listed queries, [1] the redo launch's own query counter (both zeroed with next_query); redo_list:
 // the queries.
 
+// the square root walk_bound.h's margins are sized for: v_sqrt_f32, 1 ulp
+struct HwSqrt {
+    __device__ __forceinline__ float operator()(float v) const { return __builtin_amdgcn_sqrtf(v); }
+};
+
 // WalkArgs: the kernel's one argument, so that the kernarg segment IS this struct (late_kernarg).
 struct WalkArgs {
     GraphTables g;
@@ -276,6 +282,8 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
     // 1.085 -> 1.103 ms at 2^17 nodes, where the load's wait costs more than the instructions -- so it goes with
     // the form large graphs take.
     constexpr bool ROWNORMS = FMODE == 3;
+    // the tight margins of walk_bound.h: the integer form on rows whose d <= 128 is a constant of the instantiation
+    constexpr bool TIGHT = FMODE >= 2 && D != 0;
     // Neighbour-row forms: a node's LINK COUNT travels with its id.  A node's record is nb_rows byte rows but the mean
     // degree is ~21 of 32: a third of the 4-KB read is zero padding, and the walk moves ~63 % of the HBM peak, so those
     // bytes are time.  The count only used to arrive together with the record.  Here the "id" of every key is
@@ -349,9 +357,10 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
                 q_reg[i] = 8 * i < D ? s_q[8 * i + (lane & 7)] : 0.f;
             else
                 q_reg[i] = (g.d == 128 || g.d == 96) && 8 * i < g.d ? s_q[8 * i + (lane & 7)] : 0.f;
-        // slack of the rejection test in byte-row units: quantisation error of the worst row, plus what the
-        // rounding of s_qp can move a distance by (<= 2^-22 ||q'||; 2^-18 leaves a factor 16)
-        float pf_slack = 0.f, pf_slack_q = 0.f, pf_bonus = 0.f;
+        // slack of the rejection test in byte-row units: quantisation error of the row -- its own, decoded from its
+        // norm-table entry with pf_unit (ROWNORMS), or the table's worst -- plus what the rounding of s_qp can move a
+        // distance by (walk_bound.h)
+        float pf_slack = 0.f, pf_unit = 0.f, pf_slack_q = 0.f, pf_bonus = 0.f;
         int q16_w = 0; // 128 * ||Q / 256||^2 of the two-byte query Q below (floor)
         int x_const = 0;    // 255 * sum XH
         bool x_any = false; // some component of this query lies outside the byte range
@@ -361,7 +370,10 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1)
                 qp_sq += __shfl_xor(qp_sq, off, 64);
-            pf_slack = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(WALK_COLD(g.q_errc) + 3.9e-6f * sqrtf(qp_sq))));
+            pf_slack = __uint_as_float(__builtin_amdgcn_readfirstlane(
+                __float_as_uint((ROWNORMS ? 0.f : WALK_COLD(g.q_errc)) + 3.9e-6f * sqrtf(qp_sq))));
+            if constexpr (ROWNORMS)
+                pf_unit = WALK_COLD(g.q_errunit);
             if (inline_rows) {
                 // The integer form of the filter.  q' = q_in + q_out: q_in is q' clamped to the byte range and
                 // rounded to 1/256 steps, Q = 256 * hi + lo (two byte planes in LDS); q_out is what the clamp cut
@@ -561,7 +573,8 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
             // chunk lane & 7 -- four 1 KiB wave reads, in flight together with the link list
             const bool filter_now = PHASE == 0 ? prefilter && n == ef : prefilter && STEADY;
             uint4 nw[4] = {};
-            uint32_t row_rr = 0; // sum of bytes^2 of the row this lane will judge (row 8 * (2 bit2 + bit0) + group)
+            // sum of bytes^2 of the row this lane will judge (row 8 * (2 bit2 + bit0) + group), under its error code
+            uint32_t row_rr = 0;
             if (filter_now && inline_rows) {
                 if constexpr (CK) {
                     // rows below the count only: a lane whose row is padding re-reads the last real row's chunk (same
@@ -680,13 +693,11 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
                         oct_sum4x2(S, X, lane, mine, minex);
                     else
                         mine = oct_sum4(S, lane);
-                    // v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence: the factors 1 - 2^-10 cover it
-                    mine += (int)(128u * row_rr);
-                    const float m1 = fmaxf(
-                        0.f, __builtin_amdgcn_sqrtf((float)(mine + q16_w) * 0.0078125f) * 0.9990234375f - pf_slack_q);
-                    const float m2 = fmaf(m1, m1, fmaf((float)(minex + x_const), 0.9990234375f, pf_bonus));
-                    const float m = fmaxf(0.f, __builtin_amdgcn_sqrtf(m2) * 0.9990234375f - pf_slack) * g.q_step;
-                    const float lb = m * m * 0.9990234375f;
+                    // v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence: the margins cover it
+                    mine += (int)(128u * walk_norm_of(row_rr));
+                    const float slack = ROWNORMS ? walk_row_slack(row_rr, pf_unit, pf_slack) : pf_slack;
+                    const float lb = walk_lb_int<TIGHT>(mine + q16_w, minex + x_const, pf_slack_q, pf_bonus, slack, g.q_step,
+                                                        HwSqrt());
                     const unsigned long long dropm = __ballot(lb > worst) & 0x3333333333333333ull; // lanes with bit 1 clear
                     const int rel = lane - rb; // this link lane's row within the batch
                     const int ri = rel >> 3;
@@ -726,8 +737,8 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
                 // below the current maximum (hnswalg.cpp:93), and the maximum never grows.  A lower bound of
                 // the row's float distance that already exceeds it settles the row without reading its d floats:
                 //   ||q - x|| >= q_step * (||q' - bytes|| - errc),
-                // shrunk by 2^-10 twice, which covers every rounding on either side (d <= 2048: the float sums
-                // are within (d+2) * 2^-24 of the real ones).  Rejected rows stay marked visited, as in the
+                // shrunk by 2^-10 twice (walk_lb_of_root), which covers every rounding on either side (d <= 2048: the
+                // float sums are within (d+2) * 2^-24 of the real ones).  Rejected rows stay marked visited, as in the
                 // reference; everything else takes the float path below unchanged.
                 const float worst = __uint_as_float(key_dist_bits(last_now));
                 const int myrow = __popcll(mask & ((1ull << lane) - 1ull)); // row index of this link lane
@@ -740,8 +751,7 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
                     if (active)
                         S = byte_row_dist_half(g.qrows + (size_t)nbq * dim, s_qp, dim, lane & 1);
                     S += __shfl_xor(S, 1, 64);
-                    const float m = fmaxf(0.f, __builtin_amdgcn_sqrtf(S) * 0.9990234375f - pf_slack) * g.q_step;
-                    const float lb = m * m * 0.9990234375f;
+                    const float lb = walk_lb_of_root<false>(__builtin_amdgcn_sqrtf(S), pf_slack, g.q_step);
                     const unsigned long long drop = __ballot(active && lb > worst);
                     const int rel = myrow - base;
                     if (fresh && rel >= 0 && rel < 32 && ((drop >> (2 * rel)) & 1ull))
@@ -971,7 +981,8 @@ __global__ __launch_bounds__(64, 4) void hnsw_walk_kernel(WalkArgs a)
 // dword load per row is cheaper there than sixteen v_dot4 of the row with itself
 __global__ __launch_bounds__(64) void build_nbrows_kernel(GraphTables g, uint8_t *__restrict__ nbrows,
                                                           uint32_t *__restrict__ nbnorms, int nb_rows,
-                                                          uint32_t *__restrict__ links_c)
+                                                          uint32_t *__restrict__ links_c,
+                                                          const uint16_t *__restrict__ row_err)
 {
     const size_t node = blockIdx.x;
     const int cnt = g.counts[node];
@@ -997,17 +1008,18 @@ __global__ __launch_bounds__(64) void build_nbrows_kernel(GraphTables g, uint8_t
         rr = __builtin_amdgcn_udot4(v.z, v.z, rr, false);
         rr = __builtin_amdgcn_udot4(v.w, v.w, rr, false);
         rr = (uint32_t)oct_sum((int)rr);
+        // ... under the row's own error code (walk_bound.h; zero rows beyond the count carry none)
         if (c == 0)
-            nbnorms[node * nb_rows + r] = rr;
+            nbnorms[node * nb_rows + r] = walk_norm_pack(rr, r < cnt ? (uint32_t)row_err[g.links[node * g.maxM + r]] : 0u);
     }
 }
 
 hipError_t launch_build_nbrows(hipStream_t s, const GraphTables &g, uint8_t *nbrows, uint32_t *nbnorms, int nb_rows,
-                               uint32_t *links_c)
+                               uint32_t *links_c, const uint16_t *row_err)
 {
-    if (!g.qrows || g.d > 128 || (g.d & 15) || nb_rows < g.maxM || (nb_rows & 31) || g.n >= (1u << 24) || g.maxM > 64)
+    if (!g.qrows || !row_err || g.d > 128 || (g.d & 15) || nb_rows < g.maxM || (nb_rows & 31) || g.n >= (1u << 24) || g.maxM > 64)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(build_nbrows_kernel, dim3(g.n), dim3(64), 0, s, g, nbrows, nbnorms, nb_rows, links_c);
+    hipLaunchKernelGGL(build_nbrows_kernel, dim3(g.n), dim3(64), 0, s, g, nbrows, nbnorms, nb_rows, links_c, row_err);
     return hipGetLastError();
 }
 
