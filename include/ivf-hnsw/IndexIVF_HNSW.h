@@ -6,7 +6,7 @@
 // path: without a gfx950 device search() throws.
 //
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
-// release_base(), searchDisk_batch(), remove_ids(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
+// release_base(), searchDisk_batch(), remove_ids(), update_batch(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
 // clear_id_filter_slot(), search_batch_slots(), range_search_slots(), set_id_tags(), clear_id_tags(),
 // search_batch_tags(), range_search_tags(), range_search(),
 // reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
@@ -119,6 +119,13 @@ public:
     /// With the device copy current (one handle) the lists shrink in HBM as well (ivfhnsw_gpu_remove_ids); otherwise the
     /// next search uploads them again.
     size_t remove_ids(size_t n, const idx_t *xids);
+    /// Extension: the labels xids[0..n) have the new vectors x (faiss update_vectors): the lists change as by
+    /// remove_ids(n, xids) followed by add_batch(n, x, xids, precomputed_idx); returns how many codes left.  With the
+    /// device copy current (one handle) the device lists change by ONE ivfhnsw_gpu_upsert_ivf with the codes computed here;
+    /// otherwise the next search uploads them again.  A label twice in xids throws std::invalid_argument before anything
+    /// changes.  Non-virtual; an IndexIVF_HNSW_Grouping throws (a code's sub-group and its group's alpha would have to be
+    /// derived again).
+    size_t update_batch(size_t n, const float *x, const idx_t *xids, const idx_t *precomputed_idx = nullptr);
     /// Extension: faiss's IDSelector.  Every search entry point (search, search_batch, search2, searchDisk,
     /// searchDisk_batch) returns only codes whose id is one of xids[0..n) -- with deny, only codes whose id is none of
     /// them -- as if every other code failed `dist < distances[0]`; unfilled slots hold FLT_MAX / -1.  The set is kept

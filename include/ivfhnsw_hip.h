@@ -162,6 +162,47 @@ int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
                                uint32_t *d_removed_per_list);
 int ivfhnsw_gpu_download_grouping(ivfhnsw_gpu *h, uint32_t *subgroup_sizes);
 
+/* ---- upserts: replace vectors by label in the device lists -------------------------------------
+ *
+ * "This label has a new vector" (faiss's IndexIVF::update_vectors) for the lists the handle holds, in HBM, as ONE
+ * atomic call.  ivfhnsw_gpu_upsert_ivf removes every code whose id equals one of ids[0..n) from every list that holds
+ * one and puts batch code i (ids[i], codes[i*code_size ..], norm_codes[i]) at the end of list list_idx[i]; the codes
+ * that remain keep their order, and the batch codes of one list keep ascending i.  After the call the handle's arrays
+ * (offsets, local offsets, codes, norm codes, ids, n_local) are byte for byte what ivfhnsw_gpu_remove_ids(h, n, ids)
+ * followed by ivfhnsw_gpu_append_ivf(h, n, list_idx, ids, codes, norm_codes) leaves, so searches (labels, distance bits,
+ * the max_codes cut, last_scan_counts) are those of upload_ivf of the updated lists.  A label no row bears is a plain
+ * insert; a label several rows bear loses all of them and gains one.  Filter, filter slots and row tags are keyed by
+ * label and hold for the new rows as after an append or a removal.
+ *   n_removed (nullable) receives the number of codes removed, removed_per_list (nullable, [nc]) the number per list.
+ *   Unlike the pair of calls it replaces, the call is atomic: every error leaves tables, filter, slots, tags and range
+ *   results exactly as they were, and all of them are found before the first byte of a new array is written.
+ *   list_idx[i] >= nc, a null buffer with n > 0, n_local + n >= 2^32 - 1 (counted before the removal), or THE SAME
+ *   LABEL TWICE IN ONE BATCH (found on the device while the label bitmap is built) -> IVFHNSW_ERR_INVALID; allocation
+ *   failure -> IVFHNSW_ERR_NOMEM; before upload_ivf, on a view, on a handle with grouping tables or on a sharded handle
+ *   (shard_world > 1) -> IVFHNSW_ERR_STATE.  n = 0 does nothing.
+ *   Synchronous on the handle's stream.  No views of the handle may exist during the call.  An upsert ends the validity
+ *   of the last search's plan and candidate stream (resolve_keys*, last_stream*).  The graph and the latency walk's
+ *   records are not touched.
+ *   Memory: ONE set of new arrays is built beside the old ones and swapped in (the peak is twice the list bytes, once,
+ *   where the pair of calls reaches it twice), plus removal's bitmap and mask and append's staging and sort workspace,
+ *   in the buffers the handle keeps for those calls.  Every old row is read once and every new row written once.
+ * ivfhnsw_gpu_upsert_ivf_dev: the same on device pointers (list_idx, ids, codes and removed_per_list 4-byte aligned) on
+ *   the handle's stream; list ids and labels are checked on the device before anything changes.  Returns when the new
+ *   arrays are in place.
+ * ivfhnsw_gpu_upsert: ivfhnsw_gpu_encode followed by the upsert, the codes never leaving HBM; to upsert_ivf what
+ *   ivfhnsw_gpu_add is to append_ivf, with add's requirements and out_* arrays.  ivfhnsw_gpu_upsert_dev: on device pointers.
+ * Not built: upserts on Grouping handles (a code's sub-group and the group's alpha would have to be re-derived) and on
+ *   sharded handles; "last one wins" for a label that comes twice; a count of the batch labels that were new. */
+int ivfhnsw_gpu_upsert_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *ids, const uint8_t *codes,
+                           const uint8_t *norm_codes, uint64_t *n_removed, uint32_t *removed_per_list);
+int ivfhnsw_gpu_upsert_ivf_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_ids, const uint8_t *d_codes,
+                               const uint8_t *d_norm_codes, uint64_t *n_removed, uint32_t *d_removed_per_list);
+int ivfhnsw_gpu_upsert(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *precomputed_idx, size_t efSearch,
+                       const uint32_t *ids, uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes, uint64_t *n_removed);
+int ivfhnsw_gpu_upsert_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32_t *d_precomputed_idx, size_t efSearch,
+                           const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes,
+                           uint64_t *n_removed);
+
 /* ---- additions to a Grouping index on the device -----------------------------------------------
  *
  * IndexIVF_HNSW_Grouping::add_group lays a group out as nsubc sub-groups end to end (IndexIVF_HNSW_Grouping.cpp:

@@ -64,6 +64,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_base_tags_info", "ivfhnsw_gpu_base_tag_rows",
     "ivfhnsw_gpu_exact_search_tags", "ivfhnsw_gpu_exact_search_tags_dev",
     "ivfhnsw_gpu_exact_range_search_tags", "ivfhnsw_gpu_exact_range_search_tags_dev",
+    "ivfhnsw_gpu_upsert_ivf", "ivfhnsw_gpu_upsert_ivf_dev", "ivfhnsw_gpu_upsert", "ivfhnsw_gpu_upsert_dev",
 )
 
 
@@ -152,6 +153,10 @@ def lib():
         L.ivfhnsw_gpu_download_ivf.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.ivfhnsw_gpu_remove_ids.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
         L.ivfhnsw_gpu_remove_ids_dev.argtypes = L.ivfhnsw_gpu_remove_ids.argtypes
+        L.ivfhnsw_gpu_upsert_ivf.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
+        L.ivfhnsw_gpu_upsert_ivf_dev.argtypes = L.ivfhnsw_gpu_upsert_ivf.argtypes
+        L.ivfhnsw_gpu_upsert.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+        L.ivfhnsw_gpu_upsert_dev.argtypes = L.ivfhnsw_gpu_upsert.argtypes
         L.ivfhnsw_gpu_download_grouping.argtypes = [C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_append_grouping.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
         L.ivfhnsw_gpu_append_grouping_dev.argtypes = L.ivfhnsw_gpu_append_grouping.argtypes
@@ -440,6 +445,53 @@ class GpuIndex:
         """The same on device buffers (torch CUDA tensors or raw addresses); returns n_removed."""
         nr = C.c_uint64(0)
         _check(lib().ivfhnsw_gpu_remove_ids_dev(self._h, n, _devptr(d_labels), C.byref(nr), _devptr(d_removed_per_list)))
+        return int(nr.value)
+
+    # ---- upserts (ivfhnsw_gpu_upsert_ivf / ivfhnsw_gpu_upsert, DESIGN.md 3.23) -----------------------------------
+    def upsert_ivf(self, list_idx, ids, codes, norm_codes):
+        """remove_ids(ids) + append_ivf(list_idx, ids, codes, norm_codes) as one atomic call that moves the lists once;
+        a label twice in `ids` is an error.  Returns (n_removed, removed_per_list uint32 [nc])."""
+        li = _np(list_idx, np.uint32).ravel()
+        n = li.size
+        i = _np(ids, np.uint32).ravel()
+        c = _np(codes, np.uint8).reshape(n, -1) if n else np.zeros((0, self.code_size), np.uint8)
+        nc = _np(norm_codes, np.uint8).ravel()
+        assert i.size == n and nc.size == n and (not self.code_size or c.shape[1] == self.code_size)
+        nr = C.c_uint64(0)
+        per = np.zeros(self.nc, np.uint32)
+        _check(lib().ivfhnsw_gpu_upsert_ivf(self._h, n, _ptr(li), _ptr(i), _ptr(c), _ptr(nc), C.byref(nr), _ptr(per)))
+        return int(nr.value), per
+
+    def upsert_ivf_dev(self, n, d_list_idx, d_ids, d_codes, d_norm_codes, d_removed_per_list=None):
+        """The same on device buffers (torch CUDA tensors or raw addresses); returns n_removed."""
+        nr = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_upsert_ivf_dev(self._h, n, _devptr(d_list_idx), _devptr(d_ids), _devptr(d_codes),
+                                                _devptr(d_norm_codes), C.byref(nr), _devptr(d_removed_per_list)))
+        return int(nr.value)
+
+    def upsert(self, x, ids, precomputed_idx=None, efSearch=0):
+        """encode + upsert_ivf without the codes leaving HBM: returns (idx, codes, norm_codes, n_removed)."""
+        x = _np(x, np.float32)
+        x = x.reshape(-1, x.shape[-1])
+        n = x.shape[0]
+        i = _np(ids, np.uint32).ravel()
+        assert i.size == n
+        pidx = None if precomputed_idx is None else _np(precomputed_idx, np.uint32)
+        idx = np.empty(n, np.uint32)
+        codes = np.empty((n, self.code_size), np.uint8)
+        ncodes = np.empty(n, np.uint8)
+        nr = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_upsert(self._h, n, _ptr(x), _ptr(pidx), efSearch, _ptr(i), _ptr(idx), _ptr(codes),
+                                        _ptr(ncodes), C.byref(nr)))
+        return idx, codes, ncodes, int(nr.value)
+
+    def upsert_dev(self, n, d_x, d_ids, d_precomputed_idx=None, efSearch=0, d_out_idx=None, d_out_codes=None,
+                   d_out_norm_codes=None):
+        """upsert on device buffers (outputs optional); returns n_removed."""
+        nr = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_upsert_dev(self._h, n, _devptr(d_x), _devptr(d_precomputed_idx), efSearch, _devptr(d_ids),
+                                            _devptr(d_out_idx), _devptr(d_out_codes), _devptr(d_out_norm_codes),
+                                            C.byref(nr)))
         return int(nr.value)
 
     # ---- label filter (ivfhnsw_gpu_set_filter, DESIGN.md 3.14) ---------------------------------------------------

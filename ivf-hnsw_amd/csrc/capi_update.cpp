@@ -1,4 +1,5 @@
-// In-place updates of the resident lists: appends, additions to a Grouping index (3.12), removals (3.11).
+// In-place updates of the resident lists: appends, additions to a Grouping index (3.12), removals (3.11),
+// upserts (3.23).
 #include "capi_internal.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -207,11 +208,17 @@ static int check_add_ready(ivfhnsw_gpu *h, const char *who)
     return IVFHNSW_OK;
 }
 
-// encode (as ivfhnsw_gpu_encode, chunk by chunk) into the staging, then one append
+static int upsert_state(ivfhnsw_gpu *h, const char *who);
+static int upsert_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const uint32_t *d_ids, const uint8_t *d_codes,
+                       const uint8_t *d_ncodes, uint64_t *n_removed, uint32_t *rem_out);
+
+// encode (as ivfhnsw_gpu_encode, chunk by chunk) into the staging, then one append -- or, with n_removed (upsert: the
+// codes that bore one of ids leave first, 3.23), one upsert
 static int add_impl(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *pidx, size_t efSearch, const uint32_t *ids,
-                    uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes, bool dev, const char *who)
+                    uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes, bool dev, const char *who,
+                    uint64_t *n_removed = nullptr)
 {
-    int rc = append_state(h, who);
+    int rc = n_removed ? upsert_state(h, who) : append_state(h, who);
     if (rc || (rc = check_add_ready(h, who)))
         return rc;
     if (n == 0)
@@ -271,6 +278,9 @@ static int add_impl(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *pi
         HIP_TRY(hipMemcpyAsync(out_norm_codes, h->ap_ncodes.p, n, out, h->stream));
     if (out_idx)
         HIP_TRY(hipMemcpyAsync(out_idx, sidx, n * sizeof(uint32_t), out, h->stream));
+    if (n_removed)
+        return upsert_core(h, n, sidx, h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>(), n_removed,
+                           nullptr);
     return append_core(h, n, sidx, h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(), h->ap_ncodes.as<uint8_t>());
 }
 
@@ -629,4 +639,177 @@ int ivfhnsw_gpu_remove_ids_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_label
     if (n_removed)
         *n_removed = removed;
     return IVFHNSW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// upserts: the codes that bear one of the batch's labels leave and the batch's codes go to the ends of
+// their lists, as remove_ids followed by append_ivf would leave them -- in one rebuild and one commit
+static int upsert_state(ivfhnsw_gpu *h, const char *who)
+{
+    int rc = append_state(h, who);
+    if (rc)
+        return rc;
+    if (h->t.shard_world > 1)
+        return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no removal, so no upsert", who,
+                    h->t.shard_rank, h->t.shard_world);
+    return IVFHNSW_OK;
+}
+
+// d_idx [n] and d_ids [n] (both checked here, on the device, before anything changes: every list id < nc, no label twice),
+// d_codes [n][M] (dword aligned), d_ncodes [n]: device memory, n > 0, read on the handle's stream.  rem_out [nc] (device,
+// nullable) receives the codes removed per list.  Returns with the stream drained; on any error the handle's tables are
+// the ones it had.  The steps are removal's (mask, keep, rem) and append's (cnt, the sort); the layout and the two copies
+// are kernels_upsert.hip's.
+static int upsert_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_idx, const uint32_t *d_ids, const uint8_t *d_codes,
+                       const uint8_t *d_ncodes, uint64_t *n_removed, uint32_t *rem_out)
+try {
+    const size_t nc = h->t.nc, len = nc + 1;
+    const uint64_t n_local = h->n_local;
+    const size_t ntiles = update_tiles(n_local, kRemoveTileRows);
+    int rc;
+    bool bad_id = false;
+    uint64_t grown = 0;
+    if ((rc = append_count(h, n, d_idx, nullptr, nullptr, &bad_id, &grown)))
+        return rc;
+    if (bad_id)
+        return fail(IVFHNSW_ERR_INVALID, "upsert: a list id is >= nc = %zu", nc);
+    uint32_t max_label = 0, twice = 0;
+    if ((rc = labels_max_dev(h, h->rm_status, n, d_ids, &max_label)) ||
+        (rc = h->rm_bits.ensure(label_bitmap_words(max_label) * sizeof(uint32_t))) ||
+        (rc = run_with_word(h, h->rm_status, 0, [&](uint32_t *status) {
+             return launch_upsert_bits(h->stream, d_ids, n, max_label, h->rm_bits.as<uint32_t>(), status);
+         }, &twice)))
+        return rc;
+    if (twice)
+        return fail(IVFHNSW_ERR_INVALID, "upsert: a label comes twice in one batch (after an upsert one row bears each label)");
+    if ((rc = h->rm_mask.ensure(remove_mask_words(ntiles, kRemoveTileRows) * sizeof(uint64_t))) ||
+        (rc = h->rm_keep.ensure((ntiles + 1) * sizeof(uint32_t))) || (rc = h->rm_rem.ensure(len * sizeof(uint32_t))) ||
+        (rc = h->rm_part.ensure(append_scan_parts(std::max(len, ntiles + 1)) * sizeof(uint32_t))))
+        return rc;
+    uint32_t *keep = h->rm_keep.as<uint32_t>(), *rem = h->rm_rem.as<uint32_t>(), *part = h->rm_part.as<uint32_t>();
+    unsigned long long *mask = h->rm_mask.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(keep + ntiles, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(launch_remove_mark(h->stream, h->t, n_local, h->rm_bits.as<uint32_t>(), max_label, mask, keep));
+    HIP_TRY(launch_remove_counts(h->stream, h->t, mask, nullptr, nullptr, 0, rem, rem_out));
+    HIP_TRY(launch_scan_excl_u32(h->stream, rem, len, part));
+    HIP_TRY(launch_scan_excl_u32(h->stream, keep, ntiles + 1, part));
+    uint32_t removed = 0, kept = 0;
+    HIP_TRY(hipMemcpyAsync(&removed, rem + nc, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&kept, keep + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((uint64_t)removed + kept != n_local || grown != n_local + n)
+        return fail(IVFHNSW_ERR_HIP, "upsert: %u removed + %u kept != %llu codes, or %llu != %llu + %zu", removed, kept,
+                    (unsigned long long)n_local, (unsigned long long)grown, (unsigned long long)n_local, n);
+    const uint64_t n_local2 = (uint64_t)kept + n;
+    const size_t nblocks = (n + kKmeansTile - 1) / kKmeansTile;
+    if ((rc = h->ap_perm.ensure(n * sizeof(uint32_t))) || (rc = h->ap_perm2.ensure(n * sizeof(uint32_t))) ||
+        (rc = h->ap_hist.ensure(256 * nblocks * sizeof(uint32_t))) || (rc = h->ap_tiles.ensure((ntiles + 1) * sizeof(uint32_t))))
+        return rc;
+    // the new arrays, one set: the old ones stay the handle's until the new ones are complete
+    ListArrays fresh;
+    if ((rc = fresh.allocate(nc, n_local2, h->t.M)))
+        return rc;
+    const NewLists nl = fresh.view(n_local2);
+    uint32_t *perm = nullptr, *tiles = h->ap_tiles.as<uint32_t>();
+    const uint32_t *nstart = h->ap_cnt.as<uint32_t>(); // scanned in place by launch_append_tables
+    hipError_t e = launch_sort_by_key(h->stream, d_idx, n, bits_of(nc - 1), h->ap_perm.as<uint32_t>(), h->ap_perm2.as<uint32_t>(),
+                                      h->ap_hist.as<uint32_t>(), &perm);
+    if (e == hipSuccess)
+        e = launch_upsert_layout(h->stream, h->t, n_local, rem, nstart, tiles, nl);
+    if (e == hipSuccess)
+        e = launch_upsert_compact(h->stream, h->t, n_local, mask, keep, nstart, tiles, nl);
+    if (e == hipSuccess)
+        e = launch_upsert_scatter(h->stream, h->t, perm, d_idx, n, nstart, rem, d_codes, d_ncodes, d_ids, nl);
+    if ((rc = commit_lists(h, "upsert", e, fresh, n_local2, nullptr)))
+        return rc;
+    h->last_nq = 0; // the last search's plan and candidate stream described the old rows
+    h->last_stream = false;
+    *n_removed = removed;
+    return IVFHNSW_OK;
+} catch (const std::bad_alloc &) {
+    return fail(IVFHNSW_ERR_NOMEM, "upsert: host allocation failed");
+}
+
+int ivfhnsw_gpu_upsert_ivf(ivfhnsw_gpu *h, size_t n, const uint32_t *list_idx, const uint32_t *ids, const uint8_t *codes,
+                           const uint8_t *norm_codes, uint64_t *n_removed, uint32_t *removed_per_list)
+{
+    int rc = upsert_state(h, "upsert_ivf");
+    if (rc)
+        return rc;
+    if (n && (!list_idx || !ids || !codes || !norm_codes))
+        return fail(IVFHNSW_ERR_INVALID, "upsert_ivf: null buffer");
+    if (n && (rc = append_size(h, n, "upsert_ivf")))
+        return rc;
+    for (size_t i = 0; i < n; i++)
+        if (list_idx[i] >= h->t.nc)
+            return fail(IVFHNSW_ERR_INVALID, "upsert_ivf: list_idx[%zu] = %u, nc = %u", i, list_idx[i], h->t.nc);
+    if (n_removed)
+        *n_removed = 0;
+    if (removed_per_list)
+        memset(removed_per_list, 0, (size_t)h->t.nc * sizeof(uint32_t));
+    if (n == 0)
+        return IVFHNSW_OK;
+    if ((removed_per_list && (rc = h->rm_out.ensure((size_t)h->t.nc * sizeof(uint32_t)))) ||
+        (rc = stage_batch(h, n, list_idx, nullptr, ids, codes, norm_codes)))
+        return rc;
+    uint64_t removed = 0;
+    if ((rc = upsert_core(h, n, h->ap_idx.as<uint32_t>(), h->ap_ids.as<uint32_t>(), h->ap_codes.as<uint8_t>(),
+                          h->ap_ncodes.as<uint8_t>(), &removed, removed_per_list ? h->rm_out.as<uint32_t>() : nullptr)))
+        return rc;
+    if (removed_per_list)
+        HIP_TRY(hipMemcpy(removed_per_list, h->rm_out.p, (size_t)h->t.nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_removed)
+        *n_removed = removed;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_upsert_ivf_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_list_idx, const uint32_t *d_ids, const uint8_t *d_codes,
+                               const uint8_t *d_norm_codes, uint64_t *n_removed, uint32_t *d_removed_per_list)
+{
+    int rc = upsert_state(h, "upsert_ivf_dev");
+    if (rc)
+        return rc;
+    if (n && (!d_list_idx || !d_ids || !d_codes || !d_norm_codes))
+        return fail(IVFHNSW_ERR_INVALID, "upsert_ivf_dev: null buffer");
+    if (((uintptr_t)d_list_idx | (uintptr_t)d_ids | (uintptr_t)d_codes | (uintptr_t)d_removed_per_list) & 3)
+        return fail(IVFHNSW_ERR_INVALID, "upsert_ivf_dev: list_idx, ids, codes and removed_per_list must be 4-byte aligned");
+    if (n && (rc = append_size(h, n, "upsert_ivf_dev")))
+        return rc;
+    if (n_removed)
+        *n_removed = 0;
+    if (n == 0) {
+        if (d_removed_per_list) {
+            HIP_TRY(hipMemsetAsync(d_removed_per_list, 0, (size_t)h->t.nc * sizeof(uint32_t), h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        return IVFHNSW_OK;
+    }
+    uint64_t removed = 0;
+    if ((rc = upsert_core(h, n, d_list_idx, d_ids, d_codes, d_norm_codes, &removed, d_removed_per_list)))
+        return rc;
+    if (n_removed)
+        *n_removed = removed;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_upsert(ivfhnsw_gpu *h, size_t n, const float *x, const uint32_t *precomputed_idx, size_t efSearch,
+                       const uint32_t *ids, uint32_t *out_idx, uint8_t *out_codes, uint8_t *out_norm_codes, uint64_t *n_removed)
+{
+    uint64_t removed = 0;
+    const int rc = add_impl(h, n, x, precomputed_idx, efSearch, ids, out_idx, out_codes, out_norm_codes, false, "upsert", &removed);
+    if (n_removed)
+        *n_removed = rc ? 0 : removed;
+    return rc;
+}
+
+int ivfhnsw_gpu_upsert_dev(ivfhnsw_gpu *h, size_t n, const float *d_x, const uint32_t *d_precomputed_idx, size_t efSearch,
+                           const uint32_t *d_ids, uint32_t *d_out_idx, uint8_t *d_out_codes, uint8_t *d_out_norm_codes,
+                           uint64_t *n_removed)
+{
+    uint64_t removed = 0;
+    const int rc = add_impl(h, n, d_x, d_precomputed_idx, efSearch, d_ids, d_out_idx, d_out_codes, d_out_norm_codes, true,
+                            "upsert_dev", &removed);
+    if (n_removed)
+        *n_removed = rc ? 0 : removed;
+    return rc;
 }

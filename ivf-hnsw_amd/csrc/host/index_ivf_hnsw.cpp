@@ -1191,6 +1191,73 @@ size_t IndexIVF_HNSW::remove_ids(size_t n, const idx_t *xids)
     return removed;
 }
 
+size_t IndexIVF_HNSW::update_batch(size_t n, const float *x, const idx_t *xids, const idx_t *precomputed_idx)
+{
+    // remove_ids + add_batch on the host lists; a current device copy (one handle) follows by ONE ivfhnsw_gpu_upsert_ivf
+    // with the codes computed here, every other case marks the copy stale.
+    if (dynamic_cast<IndexIVF_HNSW_Grouping *>(this))
+        throw std::runtime_error("IndexIVF_HNSW_Grouping::update_batch: a Grouping index has no update (the code's sub-group "
+                                 "and its group's alpha would have to be derived again); remove_ids, then add_group");
+    if (n == 0)
+        return 0;
+    std::vector<idx_t> labels(xids, xids + n);
+    std::sort(labels.begin(), labels.end());
+    const auto twice = std::adjacent_find(labels.begin(), labels.end());
+    if (twice != labels.end())
+        throw std::invalid_argument("IndexIVF_HNSW::update_batch: label " + std::to_string(*twice) + " comes twice in one batch");
+    ensure_encoder();
+    std::vector<idx_t> idx(n);
+    std::vector<uint8_t> xcodes(n * code_size), ncodes(n);
+    if (ivfhnsw_gpu_encode(gpu_, n, x, precomputed_idx, quantizer->efSearch, idx.data(), xcodes.data(), ncodes.data()))
+        gpu_fail("ivfhnsw_gpu_encode");
+    const bool in_place = nshards() == 1 && device_current();
+    std::vector<uint32_t> per_list;
+    uint64_t dev_removed = 0;
+    if (in_place) {
+        per_list.assign(nc, 0);
+        if (ivfhnsw_gpu_upsert_ivf(gpu_, n, idx.data(), xids, xcodes.data(), ncodes.data(), &dev_removed, per_list.data()))
+            gpu_fail("ivfhnsw_gpu_upsert_ivf");
+    }
+    size_t removed = 0;
+    for (size_t c = 0; c < nc; c++) {
+        if (in_place && per_list[c] == 0)
+            continue;
+        std::vector<idx_t> &lid = ids[c];
+        std::vector<uint8_t> &lcode = codes[c], &lnorm = norm_codes[c];
+        size_t w = 0;
+        for (size_t r = 0; r < lid.size(); r++) {
+            if (std::binary_search(labels.begin(), labels.end(), lid[r]))
+                continue;
+            lid[w] = lid[r];
+            std::copy(lcode.begin() + r * code_size, lcode.begin() + (r + 1) * code_size, lcode.begin() + w * code_size);
+            lnorm[w] = lnorm[r];
+            w++;
+        }
+        const size_t gone = lid.size() - w;
+        if (in_place && gone != per_list[c])
+            throw std::runtime_error("IndexIVF_HNSW::update_batch: list " + std::to_string(c) + " lost " + std::to_string(gone) +
+                                     " codes on the host, " + std::to_string(per_list[c]) + " on the device");
+        lid.resize(w);
+        lcode.resize(w * code_size);
+        lnorm.resize(w);
+        removed += gone;
+    }
+    if (in_place && removed != dev_removed)
+        throw std::runtime_error("IndexIVF_HNSW::update_batch: " + std::to_string(removed) + " codes removed on the host, " +
+                                 std::to_string(dev_removed) + " on the device");
+    for (size_t i = 0; i < n; i++) {
+        const idx_t key = idx[i];
+        ids[key].push_back(xids[i]);
+        codes[key].insert(codes[key].end(), xcodes.begin() + i * code_size, xcodes.begin() + (i + 1) * code_size);
+        norm_codes[key].push_back(ncodes[i]);
+    }
+    if (in_place)
+        up_total_ = up_total_ - removed + n;
+    else
+        device_dirty_ = true;
+    return removed;
+}
+
 void IndexIVF_HNSW::add_batch2(size_t, const float *, const idx_t *, const idx_t *, uint64_t *, char *)
 {
     throw std::runtime_error("IndexIVF_HNSW::add_batch2: the ORCV vendor format is out of scope (SURVEY.md 2, row 9)");

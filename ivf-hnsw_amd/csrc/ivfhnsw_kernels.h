@@ -449,6 +449,19 @@ hipError_t launch_remove_compact(hipStream_t s, const IvfTables &t, uint64_t n_l
 // the label bitmap of every call that takes a label set (capi_labels.cpp): bits [max_label / 32 + 1 words] zeroed, then
 // the bit of every label set
 hipError_t launch_remove_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits);
+// upsert (kernels_upsert.hip): a removal and an append of an unsharded IVFADC handle in one rebuild, from
+// removal's mask / kscan / rscan and append's nstart / perm.  bits: launch_remove_bits that raises *status when a label
+// comes twice.  layout: nl.goff / nl.loff and tile_first [ceil(n_local / kRemoveTileRows) + 1] = the old list of every
+// source tile's first row.  compact, after layout: the surviving rows, one contiguous range per (source tile, list)
+// segment.  scatter: the batch's rows behind the surviving rows of their lists; it writes no byte compact writes.
+hipError_t launch_upsert_bits(hipStream_t s, const uint32_t *labels, size_t n, uint32_t max_label, uint32_t *bits, uint32_t *status);
+hipError_t launch_upsert_layout(hipStream_t s, const IvfTables &t, uint64_t n_local, const uint32_t *rscan, const uint32_t *nstart,
+                                uint32_t *tile_first, const NewLists &nl);
+hipError_t launch_upsert_compact(hipStream_t s, const IvfTables &t, uint64_t n_local, const unsigned long long *mask,
+                                 const uint32_t *kscan, const uint32_t *nstart, const uint32_t *tile_first, const NewLists &nl);
+hipError_t launch_upsert_scatter(hipStream_t s, const IvfTables &t, const uint32_t *perm, const uint32_t *list_idx, size_t n,
+                                 const uint32_t *nstart, const uint32_t *rscan, const uint8_t *codes, const uint8_t *norm_codes,
+                                 const uint32_t *ids, const NewLists &nl);
 // search filter (kernels_filter.hip): mask [ceil(n_local / 64)] words, bit r = row r passes: its id is in the
 // label bitmap (bits null = the empty set), or with deny is not; rows at or beyond n_local are 0.  *count (zeroed here) = the
 // rows that pass.

@@ -184,6 +184,50 @@ IVFHNSW_UPDATE_FN uint32_t kept_rank(uint32_t pre_w, unsigned long long kept, ui
     return pre_w + (uint32_t)__builtin_popcountll(kept & ((1ull << b) - 1ull));
 }
 
+// ---- the upsert: a removal and an append in one rebuild.  rscan / nstart = the exclusive scans of the
+// rows each list loses / gains, kscan = that of the rows each source tile keeps.  The new list c is its surviving old rows,
+// in order, then its batch rows: it starts at start[c] - rscan[c] + nstart[c].
+// The kept rows of a tile in front of its row x (0 <= x <= the tile's rows): pre / kept as the compaction holds them
+// (words of 1 << wshift rows; 64 on the device), so kept row x has this rank inside the tile.
+IVFHNSW_UPDATE_FN uint32_t kept_before(const uint32_t *pre, const unsigned long long *kept, uint32_t x, uint32_t wshift, uint32_t words)
+{
+    const uint32_t w = x >> wshift;
+    return w >= words ? pre[words] : kept_rank(pre[w], kept[w], x & ((1u << wshift) - 1u));
+}
+
+// The piece of a source tile that lies in one list: from old row a (a < r_end, the tile's end) to the end of the list
+// that holds a, or the tile's.  lo .. hi = the lists the search looks at (start[lo] <= a; hi = the list of the next
+// tile's first row).  The kept rows of one segment are contiguous in the new arrays; between two segments lie the batch
+// rows of the first one's list and whatever the lists in between gain.
+struct TileSegment {
+    uint32_t list, end;
+};
+template <class P, class G>
+IVFHNSW_UPDATE_FN TileSegment tile_segment(P start, G goff, uint32_t lo, uint32_t hi, uint32_t a, uint32_t r_end)
+{
+    const uint32_t c = list_of_row(start, lo, hi, a);
+    const uint64_t e = (uint64_t)start[c] + (uint64_t)(goff[c + 1] - goff[c]);
+    return {c, e < r_end ? (uint32_t)e : r_end};
+}
+
+// the new local row of the kept row with rank j inside its source tile (kscan_t kept rows lie in tiles in front of it)
+// and list c: every kept row in front of it stays in front, and so do the batch rows of the lists in front of c
+IVFHNSW_UPDATE_FN size_t upsert_kept_dest(uint32_t kscan_t, uint32_t j, uint32_t nstart_c)
+{
+    return (size_t)kscan_t + j + nstart_c;
+}
+// the new start of list c, and the new local row of row p of the batch sorted stably by list: behind the list's kept rows
+// and the batch rows sorted before it
+IVFHNSW_UPDATE_FN uint32_t upsert_list_start(uint32_t start_c, uint32_t rscan_c, uint32_t nstart_c)
+{
+    return start_c - rscan_c + nstart_c;
+}
+IVFHNSW_UPDATE_FN size_t upsert_batch_dest(uint32_t start_c, uint32_t old_len, uint32_t rscan_c, uint32_t rscan_c1, size_t p,
+                                           uint32_t nstart_c)
+{
+    return (size_t)upsert_list_start(start_c, rscan_c, nstart_c) + (old_len - (rscan_c1 - rscan_c)) + (p - nstart_c);
+}
+
 // ---- workspace sizes, in elements
 constexpr int kScanChunk = 4096; // elements per workgroup of the three-phase scan (launch_append_tables, launch_scan_excl_u32)
 
