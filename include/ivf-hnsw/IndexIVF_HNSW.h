@@ -8,7 +8,8 @@
 // Extensions (not in the reference): search_batch(), sync_to_device(), invalidate_device(), upload_base(),
 // release_base(), searchDisk_batch(), remove_ids(), update_batch(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
 // clear_id_filter_slot(), search_batch_slots(), range_search_slots(), set_id_tags(), clear_id_tags(),
-// search_batch_tags(), range_search_tags(), range_search(),
+// search_batch_tags(), range_search_tags(), set_id_values(), clear_id_values(), search_batch_values(),
+// range_search_values(), range_search(),
 // reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
@@ -159,6 +160,21 @@ public:
     void search_batch_tags(size_t nq, size_t k, const float *x, const uint16_t *tags, float *distances, long *labels);
     void range_search_tags(size_t nq, const float *x, const uint16_t *tags, float radius, std::vector<size_t> &lims,
                            std::vector<float> &distances, std::vector<long> &labels);
+    /// Extension: the INTERVAL predicate -- timestamp, price, version, sequence number between a and b -- as one uint32
+    /// value per id (ivfhnsw_gpu_set_values).  set_id_values is incremental as set_id_tags is (0xffffffff
+    /// un-values an id; an id given two different values in one call throws).  search_batch_values / range_search_values
+    /// take one pair per query, ranges[2q] = lo and ranges[2q + 1] = hi, and answer each query as search_batch /
+    /// range_search would with set_id_filter(ids whose value lies in [lo, hi]) installed: unsigned, inclusive at both ends,
+    /// an id without a value counting as 0xffffffff, so that (0, 0xffffffff) is the unfiltered query and lo > hi finds
+    /// nothing.  Independent of set_id_filter, the slots and the tags, and not combined with them: the _values calls throw
+    /// while a set_id_filter filter is installed.  The values are kept on the host beside the object and installed on the
+    /// device copy whenever that is made or remade, at once if it is current; add_batch, update_batch and remove_ids keep
+    /// them.  Non-virtual.  All throw with IVFHNSW_SHARDS > 1.
+    void set_id_values(size_t n, const idx_t *xids, const uint32_t *values);
+    void clear_id_values();
+    void search_batch_values(size_t nq, size_t k, const float *x, const uint32_t *ranges, float *distances, long *labels);
+    void range_search_values(size_t nq, const float *x, const uint32_t *ranges, float radius, std::vector<size_t> &lims,
+                             std::vector<float> &distances, std::vector<long> &labels);
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

@@ -171,10 +171,10 @@ int ivfhnsw_gpu_download_grouping(ivfhnsw_gpu *h, uint32_t *subgroup_sizes);
  * (offsets, local offsets, codes, norm codes, ids, n_local) are byte for byte what ivfhnsw_gpu_remove_ids(h, n, ids)
  * followed by ivfhnsw_gpu_append_ivf(h, n, list_idx, ids, codes, norm_codes) leaves, so searches (labels, distance bits,
  * the max_codes cut, last_scan_counts) are those of upload_ivf of the updated lists.  A label no row bears is a plain
- * insert; a label several rows bear loses all of them and gains one.  Filter, filter slots and row tags are keyed by
+ * insert; a label several rows bear loses all of them and gains one.  Filter, filter slots, row tags and row values are keyed by
  * label and hold for the new rows as after an append or a removal.
  *   n_removed (nullable) receives the number of codes removed, removed_per_list (nullable, [nc]) the number per list.
- *   Unlike the pair of calls it replaces, the call is atomic: every error leaves tables, filter, slots, tags and range
+ *   Unlike the pair of calls it replaces, the call is atomic: every error leaves tables, filter, slots, tags, values and range
  *   results exactly as they were, and all of them are found before the first byte of a new array is written.
  *   list_idx[i] >= nc, a null buffer with n > 0, n_local + n >= 2^32 - 1 (counted before the removal), or THE SAME
  *   LABEL TWICE IN ONE BATCH (found on the device while the label bitmap is built) -> IVFHNSW_ERR_INVALID; allocation
@@ -382,6 +382,55 @@ int ivfhnsw_gpu_clear_tags(ivfhnsw_gpu *h);
 int ivfhnsw_gpu_tags_info(ivfhnsw_gpu *h, uint64_t *rows_tagged, uint64_t *rows_total, uint64_t *table_labels);
 int ivfhnsw_gpu_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows);
 
+/* Row values: the INTERVAL predicate -- timestamp, price, version, sequence number between a and b --
+ * beside the set-membership ones above.  A handle holds at most one value table, a uint32 per label value over [0, largest
+ * label ever given a value]; a label that was never given one reads as IVFHNSW_VALUE_NONE.  The _values forms of search
+ * and range search take one pair per query: query_ranges [2 * nq] uint32, query q carrying (lo, hi) = (query_ranges[2q],
+ * query_ranges[2q + 1]).
+ *   The rule: a row passes query q iff lo <= value(row) <= hi, UNSIGNED and INCLUSIVE at both ends.  A row without a value
+ * has the value 0xffffffff.  There is deliberately no special case: (0, 0xffffffff) passes every row and is the unfiltered
+ * query; (x, 0xfffffffe) is "at least x, among the rows that have a value", (x, 0xffffffff) also admits the rows without
+ * one; lo > hi is legal and passes no row -- the query returns padding (FLT_MAX / -1) or an empty range.
+ *   Query q answers, bit for bit, what the plain call answers on the same handle with set_filter({labels whose value lies
+ * in [lo, hi]}, ALLOW) installed -- labels, distance bits, unfilled places, the heap array of heap_order = 1 for any k
+ * (k > 1024 included), out_keys, candidate streams, resolve_keys*, and range lims / distances / labels in scan order --
+ * and with (0, 0xffffffff) what it answers with no filter.  Everything said of a filtered call above holds per query (the
+ * same lists in the same order, max_codes and Grouping's pruning count every stored code, last_scan_counts is the
+ * unfiltered call's).  A _values launch reports the unfiltered kernel's name with "+values" appended and runs plan, table
+ * and scan as a _tags launch does.  query_ranges == NULL is the plain call.
+ *   Values are a fourth independent state beside filter, slots and tags: plain, _slots and _tags calls never read them, a
+ * _values call ignores slots and tags, and a _values call on a handle with a set_filter filter installed ->
+ * IVFHNSW_ERR_STATE.  A _values call on a handle without a value table is legal: every row is IVFHNSW_VALUE_NONE.
+ * ivfhnsw_gpu_set_values is INCREMENTAL, exactly as set_tags is: it (over)writes the values of the n labels given and
+ *   leaves every other label's alone.  Any uint32 label, resident or not; a repeated label with the same value counts
+ *   once; a label given two different values in one call -> IVFHNSW_ERR_INVALID; the value IVFHNSW_VALUE_NONE un-values a
+ *   label.  The new table and row values are built beside the installed ones and swapped in: any error leaves the state
+ *   as it was.  Synchronous on the handle's stream.  _dev: d_labels and d_values in device memory, 4-byte aligned.
+ *   ivfhnsw_gpu_clear_values drops table and row values (succeeds without any); ivfhnsw_gpu_upload_ivf does the same.
+ *   ivfhnsw_gpu_values_info: *rows_valued = resident rows whose value is not IVFHNSW_VALUE_NONE, *rows_total = resident
+ *   rows, *table_labels = label values the table spans (largest valued label + 1; 0 without a table); each nullable.
+ *   ivfhnsw_gpu_value_rows: *rows = resident rows an interval passes under the rule above (size max_codes from it).
+ * After a successful append_ivf, add, remove_ids, upsert_ivf, upsert, append_grouping or add_groups (host and _dev forms)
+ *   the row values hold for the updated lists (one gather over the new ids, before they are installed); an update that
+ *   fails leaves lists, filter, slots, tags and values as they were.  A label held by several rows gives all of them its
+ *   value.  A view reads the values its parent held when the view was created (the internal view of a split batch follows
+ *   the handle at every call); set / clear on a view -> IVFHNSW_ERR_STATE.
+ * Memory, counted by ivfhnsw_gpu_memory_bytes: 4 * (largest valued label + 1) bytes of table and 4 * max(rows, 1) bytes
+ *   of row values; a host _values call stages its 8 bytes per query.
+ * Errors: null labels or values with n > 0, a misaligned device pointer, conflicting repeats, a null result of value_rows
+ *   -> IVFHNSW_ERR_INVALID; set before upload_ivf, set or clear on a view, set / clear / a _values call on a handle with
+ *   shard_world > 1 -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM; whatever search_dev /
+ *   range_search_dev refuses for the same params -> that status.  An error leaves earlier range results and the
+ *   installed state as they were.
+ * Not built: values for the exact calls, for search_reconstruct, search_sharded and sharded handles; an interval AND a
+ *   tag, a slot or the handle's filter; 64-bit or float values, or several values per row. */
+#define IVFHNSW_VALUE_NONE 0xffffffffu
+int ivfhnsw_gpu_set_values(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint32_t *values);
+int ivfhnsw_gpu_set_values_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint32_t *d_values);
+int ivfhnsw_gpu_clear_values(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_values_info(ivfhnsw_gpu *h, uint64_t *rows_valued, uint64_t *rows_total, uint64_t *table_labels);
+int ivfhnsw_gpu_value_rows(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *rows);
+
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
  * groups are zero.  Requires upload_ivf first and upload_quantizer before searching. */
@@ -497,6 +546,15 @@ int ivfhnsw_gpu_search_tags_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float
                                 const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                 const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
 
+/* ... and with a value interval per query (see "Row values" above): query_ranges [2 * nq] uint32, host memory for the
+ * host form, device memory (8-byte aligned) for the _dev form; NULL = the plain call. */
+int ivfhnsw_gpu_search_values(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                              const float *coarse_dists, const ivfhnsw_search_params *params, const uint32_t *query_ranges,
+                              float *distances, int64_t *labels);
+int ivfhnsw_gpu_search_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                  const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                  const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
+
 /* Multi-GPU merge helper: given keys already MIN-reduced over the shards, resolve the
  * labels this shard owns ([nq*k]; -1 where the winner lives on another shard) from the scan plan of
  * the last search_dev call, and decode the distances.  The caller then MAX-reduces the labels. */
@@ -594,6 +652,13 @@ int ivfhnsw_gpu_range_search_tags(ivfhnsw_gpu *h, size_t nq, const float *querie
 int ivfhnsw_gpu_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                                       const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                       const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
+/* ... and with a value interval per query ("Row values" above) */
+int ivfhnsw_gpu_range_search_values(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                    const float *coarse_dists, const ivfhnsw_search_params *params, const uint32_t *query_ranges,
+                                    float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_range_search_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                        const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                        const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 

@@ -18,6 +18,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
 FILTER_ALLOW, FILTER_DENY = 0, 1
 FILTER_SLOTS, SLOT_NONE = 32, 0xff
 TAG_NONE = 0xffff
+VALUE_NONE = 0xffffffff
 RECON_ORIGINAL, RECON_ROTATED = 0, 1
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
@@ -60,6 +61,9 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_set_tags", "ivfhnsw_gpu_set_tags_dev", "ivfhnsw_gpu_clear_tags", "ivfhnsw_gpu_tags_info",
     "ivfhnsw_gpu_tag_rows", "ivfhnsw_gpu_search_tags", "ivfhnsw_gpu_search_tags_dev",
     "ivfhnsw_gpu_range_search_tags", "ivfhnsw_gpu_range_search_tags_dev",
+    "ivfhnsw_gpu_set_values", "ivfhnsw_gpu_set_values_dev", "ivfhnsw_gpu_clear_values", "ivfhnsw_gpu_values_info",
+    "ivfhnsw_gpu_value_rows", "ivfhnsw_gpu_search_values", "ivfhnsw_gpu_search_values_dev",
+    "ivfhnsw_gpu_range_search_values", "ivfhnsw_gpu_range_search_values_dev",
     "ivfhnsw_gpu_set_base_tags", "ivfhnsw_gpu_set_base_tags_dev", "ivfhnsw_gpu_clear_base_tags",
     "ivfhnsw_gpu_base_tags_info", "ivfhnsw_gpu_base_tag_rows",
     "ivfhnsw_gpu_exact_search_tags", "ivfhnsw_gpu_exact_search_tags_dev",
@@ -219,6 +223,15 @@ def lib():
         L.ivfhnsw_gpu_search_tags_dev.argtypes = L.ivfhnsw_gpu_search_slots_dev.argtypes
         L.ivfhnsw_gpu_range_search_tags.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search_tags_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
+        L.ivfhnsw_gpu_set_values.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_set_values_dev.argtypes = L.ivfhnsw_gpu_set_values.argtypes
+        L.ivfhnsw_gpu_clear_values.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_value_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_search_values.argtypes = L.ivfhnsw_gpu_search_slots.argtypes
+        L.ivfhnsw_gpu_search_values_dev.argtypes = L.ivfhnsw_gpu_search_slots_dev.argtypes
+        L.ivfhnsw_gpu_range_search_values.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
+        L.ivfhnsw_gpu_range_search_values_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
         L.ivfhnsw_gpu_set_base_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
         L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
@@ -567,6 +580,36 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_tag_rows(self._h, tag, C.byref(n)))
         return int(n.value)
 
+    # ---- row values: a uint32 per row, an interval per query (ivfhnsw_gpu_set_values) ------------------
+    def set_values(self, labels, values):
+        """The labels given carry the values given (uint32; VALUE_NONE un-values) from now on; every other label keeps
+        its value.  The _values searches name an interval per query."""
+        lab = _np(labels, np.uint32).ravel()
+        vl = _np(values, np.uint32).ravel()
+        if vl.size != lab.size:
+            raise ValueError("set_values: %d labels, %d values" % (lab.size, vl.size))
+        _check(lib().ivfhnsw_gpu_set_values(self._h, lab.size, _ptr(lab) if lab.size else None, _ptr(vl) if vl.size else None))
+
+    def set_values_dev(self, n, d_labels, d_values):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_set_values_dev(self._h, n, _devptr(d_labels), _devptr(d_values)))
+
+    def clear_values(self):
+        """No label has a value afterwards."""
+        _check(lib().ivfhnsw_gpu_clear_values(self._h))
+
+    def values_info(self):
+        """(rows_valued, rows_total, table_labels): resident rows with a value, resident rows, label values the table spans."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_values_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def value_rows(self, lo, hi):
+        """Resident rows whose value lies in [lo, hi], unsigned and inclusive; a row without a value holds VALUE_NONE."""
+        n = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_value_rows(self._h, lo, hi, C.byref(n)))
+        return int(n.value)
+
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)
         n = _np(nn_centroid_idxs, np.uint32)
@@ -716,14 +759,21 @@ class GpuIndex:
         return self._search_picked(lib().ivfhnsw_gpu_search_tags, np.uint16, queries, k, query_tags, nprobe, max_codes,
                                    coarse_ids, coarse_dists, efSearch, do_pruning, heap_order)
 
+    def search_values(self, queries, k, query_ranges, nprobe, max_codes, coarse_ids=None, coarse_dists=None, efSearch=0,
+                      do_pruning=False, heap_order=False):
+        """search() with a value interval per query: query_ranges [nq, 2] uint32, (lo, hi) inclusive, (0, VALUE_NONE) =
+        no filter; None is search() itself (ivfhnsw_gpu_search_values)."""
+        return self._search_picked(lib().ivfhnsw_gpu_search_values, np.uint32, queries, k, query_ranges, nprobe, max_codes,
+                                   coarse_ids, coarse_dists, efSearch, do_pruning, heap_order, per=2)
+
     def _search_picked(self, fn, pick_dtype, queries, k, query_slots, nprobe, max_codes, coarse_ids, coarse_dists, efSearch,
-                       do_pruning, heap_order):
+                       do_pruning, heap_order, per=1):
         q = _np(queries, np.float32)
         q = q.reshape(-1, self.d or q.shape[-1])
         nq = q.shape[0]
         cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
         cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
-        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq)
+        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq * per)
         dist = np.empty((nq, k), np.float32)
         lab = np.empty((nq, k), np.int64)
         p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
@@ -748,6 +798,16 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_search_tags_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
                                                  _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
                                                  _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
+
+    def search_values_dev(self, nq, k, d_queries, d_query_ranges, d_distances, d_labels, nprobe, max_codes,
+                          d_coarse_ids=None, d_coarse_dists=None, efSearch=0, do_pruning=False, d_out_keys=None,
+                          heap_order=False):
+        """search_dev() with a value interval per query (d_query_ranges: [nq, 2] uint32 in device memory, 8-byte aligned,
+        not read back)."""
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_values_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                   _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_ranges),
+                                                   _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
 
     # ---- reconstruction of stored vectors (ivfhnsw_gpu_reconstruct*, DESIGN.md 3.16) ---------------------------------
     def locate(self, labels):
@@ -865,14 +925,20 @@ class GpuIndex:
         return self._range_search_picked(lib().ivfhnsw_gpu_range_search_tags, np.uint16, queries, radius, query_tags, nprobe,
                                          max_codes, efSearch, do_pruning, coarse_ids, coarse_dists)
 
+    def range_search_values(self, queries, radius, query_ranges, nprobe, max_codes, efSearch=0, do_pruning=False,
+                            coarse_ids=None, coarse_dists=None):
+        """range_search() with a value interval per query (query_ranges as search_values takes them)."""
+        return self._range_search_picked(lib().ivfhnsw_gpu_range_search_values, np.uint32, queries, radius, query_ranges, nprobe,
+                                         max_codes, efSearch, do_pruning, coarse_ids, coarse_dists, per=2)
+
     def _range_search_picked(self, fn, pick_dtype, queries, radius, query_slots, nprobe, max_codes, efSearch, do_pruning,
-                             coarse_ids, coarse_dists):
+                             coarse_ids, coarse_dists, per=1):
         q = _np(queries, np.float32)
         q = q.reshape(-1, self.d or q.shape[-1])
         nq = q.shape[0]
         cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
         cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
-        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq)
+        qs = None if query_slots is None else _np(query_slots, pick_dtype).reshape(nq * per)
         lims = np.zeros(nq + 1, np.uint64)
         total = C.c_uint64(0)
         p = self._params(nprobe, max_codes, efSearch, do_pruning)
@@ -899,6 +965,16 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_range_search_tags_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
                                                        _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
                                                        C.c_float(radius), _devptr(d_lims), C.byref(total)))
+        return int(total.value)
+
+    def range_search_values_dev(self, nq, d_queries, radius, d_query_ranges, d_lims, nprobe, max_codes, efSearch=0,
+                                do_pruning=False, d_coarse_ids=None, d_coarse_dists=None):
+        """range_search_dev() with a value interval per query (d_query_ranges in device memory)."""
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_values_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                         _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_ranges),
+                                                         C.c_float(radius), _devptr(d_lims), C.byref(total)))
         return int(total.value)
 
     def range_results(self, first, count):

@@ -2,7 +2,7 @@
 // denied one.  The set becomes a bitmap over [0, max label], the bitmap one PASS bit per resident row, and the filtered
 // forms of the scan kernels read that bit beside the row's norm code.  The bitmap stays with the handle so that in-place
 // updates can judge the rows of their new arrays (ListArrays::mark_filter, capi_internal.h).  Filter slots (3.19) and
-// row tags (3.21), the two per-query forms, live here too.
+// row tags (3.21) and row values (3.24), the three per-query forms, live here too.
 #include "capi_internal.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -103,14 +103,16 @@ int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBu
     return IVFHNSW_OK;
 }
 
-int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags)
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags) { return slots_call_guard(h, who, tags ? 1 : 0); }
+
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, int kind)
 {
     if (h->t.shard_world > 1)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no %s", who,
-                    h->t.shard_rank, h->t.shard_world, tags ? "row tags" : "filter slots");
+                    h->t.shard_rank, h->t.shard_world, kind == 2 ? "row values" : kind == 1 ? "row tags" : "filter slots");
     if (h->filter.mode >= 0)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle has a set_filter filter installed; a call is filtered by that or by "
-                                       "%s, not both (clear_filter first)", who, tags ? "tags" : "slots");
+                                       "%s, not both (clear_filter first)", who, kind == 2 ? "values" : kind == 1 ? "tags" : "slots");
     return IVFHNSW_OK;
 }
 
@@ -253,6 +255,94 @@ static int tags_count(ivfhnsw_gpu *h, uint32_t tag, bool equal, uint64_t *out)
         return rc;
     unsigned long long cnt = 0;
     HIP_TRY(launch_tags_count(h->stream, h->row_tags, h->n_local, tag, equal, word.as<unsigned long long>()));
+    HIP_TRY(hipMemcpyAsync(&cnt, word.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *out = cnt;
+    return IVFHNSW_OK;
+}
+
+// ---- row values: a uint32 per label value (vl_table, vl_labels entries), gathered into one uint32 per
+// resident row (vl_rows), which the _values scans judge against the query's interval.  Built as the tags are.
+
+void values_drop(ivfhnsw_gpu *h)
+{
+    h->vl_labels = 0;
+    h->row_values = nullptr;
+    h->vl_table.release();
+    h->vl_rows.release();
+}
+
+// the values of ids [n_local] from a table of table_n labels into out (grown here; never empty).  Returns with the stream drained.
+static int gather_value_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, const uint32_t *table, uint64_t table_n,
+                             DevBuf &out)
+{
+    int rc = out.ensure((size_t)std::max<uint64_t>(n_local, 1) * sizeof(uint32_t));
+    if (rc)
+        return rc;
+    HIP_TRY(launch_values_gather(h->stream, ids, n_local, table, table_n, out.as<uint32_t>()));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+int values_gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &row_values)
+{
+    return gather_value_rows(h, ids, n_local, h->vl_table.as<uint32_t>(), h->vl_labels, row_values);
+}
+
+// d_labels / d_values [n] in device memory, max_label their largest label.  As set_tags_core: the new table (the old
+// one's entries, IVFHNSW_VALUE_NONE beyond them, then the n values scattered in) and the new row values are built beside
+// the installed ones and swapped in when nothing can fail any more.
+static int set_values_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint32_t *d_values, uint32_t max_label)
+{
+    if (n == 0)
+        return IVFHNSW_OK;
+    const uint64_t held = h->vl_labels, span = std::max<uint64_t>(held, (uint64_t)max_label + 1);
+    ScopedBuf table, rows, word; // word: of this call only
+    int rc;
+    if ((rc = table.ensure((size_t)span * sizeof(uint32_t))) || (rc = word.ensure(sizeof(uint32_t))))
+        return rc;
+    if (held)
+        HIP_TRY(hipMemcpyAsync(table.p, h->vl_table.p, (size_t)held * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    if (span > held) // 0xffffffff: IVFHNSW_VALUE_NONE
+        HIP_TRY(hipMemsetAsync(table.as<uint32_t>() + held, 0xff, (size_t)(span - held) * sizeof(uint32_t), h->stream));
+    uint32_t conflict = 0;
+    HIP_TRY(launch_values_scatter(h->stream, d_labels, d_values, n, table.as<uint32_t>(), word.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(&conflict, word.p, sizeof(conflict), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (conflict)
+        return fail(IVFHNSW_ERR_INVALID, "set_values: a label is given two different values in one call");
+    if ((rc = gather_value_rows(h, h->t.ids, h->n_local, table.as<uint32_t>(), span, rows)))
+        return rc;
+    table.install(h->vl_table); // the earlier table and row values go with this scope
+    rows.install(h->vl_rows);
+    h->vl_labels = span;
+    h->row_values = h->vl_rows.as<uint32_t>();
+    return IVFHNSW_OK;
+}
+
+static int values_args(size_t n, const uint32_t *labels, const uint32_t *values, const char *who)
+{
+    int rc = label_args_guard(n, labels, who);
+    if (rc)
+        return rc;
+    if (n && !values)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null values", who);
+    return IVFHNSW_OK;
+}
+
+// one counting pass over the row values h reads: rows whose value lies in [lo, hi]
+static int values_count(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *out)
+{
+    if (!h->row_values) { // no table: every row holds IVFHNSW_VALUE_NONE
+        *out = lo <= hi && hi == IVFHNSW_VALUE_NONE ? h->n_local : 0;
+        return IVFHNSW_OK;
+    }
+    ScopedBuf word;
+    int rc = word.ensure(sizeof(unsigned long long));
+    if (rc)
+        return rc;
+    unsigned long long cnt = 0;
+    HIP_TRY(launch_values_count(h->stream, h->row_values, h->n_local, lo, hi, word.as<unsigned long long>()));
     HIP_TRY(hipMemcpyAsync(&cnt, word.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *out = cnt;
@@ -448,4 +538,68 @@ int ivfhnsw_gpu_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows)
     if (tag > IVFHNSW_TAG_NONE || !rows)
         return fail(IVFHNSW_ERR_INVALID, "tag_rows: tag %u (tags are 0..0xffff) or a null result", tag);
     return tags_count(h, tag, true, rows);
+}
+
+// ---- row values
+
+int ivfhnsw_gpu_set_values(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint32_t *values)
+{
+    int rc = filter_state(h, "set_values", true, "row values");
+    if (rc || (rc = values_args(n, labels, values, "set_values")))
+        return rc;
+    ScopedBuf stage_l, stage_v; // of this call only
+    uint32_t mx = 0;
+    if ((rc = labels_from_host(h, n, labels, stage_l, &mx)) || (n && (rc = stage_in(h, stage_v, values, n * sizeof(uint32_t)))))
+        return rc;
+    return set_values_core(h, n, stage_l.as<uint32_t>(), stage_v.as<uint32_t>(), mx);
+}
+
+int ivfhnsw_gpu_set_values_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint32_t *d_values)
+{
+    int rc = filter_state(h, "set_values_dev", true, "row values");
+    if (rc || (rc = values_args(n, d_labels, d_values, "set_values_dev")))
+        return rc;
+    if (((uintptr_t)d_labels & 3) || ((uintptr_t)d_values & 3))
+        return fail(IVFHNSW_ERR_INVALID, "set_values_dev: labels and values must be 4-byte aligned");
+    ScopedBuf word; // of this call only
+    uint32_t mx = 0;
+    if ((rc = labels_max_dev(h, word, n, d_labels, &mx)))
+        return rc;
+    return set_values_core(h, n, d_labels, d_values, mx);
+}
+
+int ivfhnsw_gpu_clear_values(ivfhnsw_gpu *h)
+{
+    int rc = filter_state(h, "clear_values", false, "row values");
+    if (rc)
+        return rc;
+    if (!h->vl_labels)
+        return IVFHNSW_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream)); // searches in flight still read the row values (a split batch joins this stream)
+    values_drop(h);
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_values_info(ivfhnsw_gpu *h, uint64_t *rows_valued, uint64_t *rows_total, uint64_t *table_labels)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (rows_valued && (rc = values_count(h, 0, IVFHNSW_VALUE_NONE - 1, rows_valued)))
+        return rc;
+    if (rows_total)
+        *rows_total = h->n_local;
+    if (table_labels)
+        *table_labels = h->vl_labels;
+    return IVFHNSW_OK;
+}
+
+int ivfhnsw_gpu_value_rows(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *rows)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (!rows)
+        return fail(IVFHNSW_ERR_INVALID, "value_rows: a null result");
+    return values_count(h, lo, hi, rows);
 }

@@ -96,6 +96,8 @@ void follow_parent(ivfhnsw_gpu *view, const ivfhnsw_gpu *parent)
     view->fs = parent->fs; // ... and reads the filter slots its parent holds
     view->row_tags = parent->row_tags; // ... and its row tags (3.21)
     view->tg_labels = parent->tg_labels;
+    view->row_values = parent->row_values; // ... and its row values (3.24)
+    view->vl_labels = parent->vl_labels;
 }
 
 int table_change_guard(ivfhnsw_gpu *h, TableChange what, const char *who, bool need_ivf)

@@ -193,8 +193,9 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_count) /* set_filter: the pass mask, the count's word (the kept label bitmap: filter.bits) */ \
-    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts) */ \
+    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts, a _values call's pairs) */ \
     X(tg_table) X(tg_rows) /* row tags: a uint16 per label value, a uint16 per resident row */ \
+    X(vl_table) X(vl_rows) /* row values: a uint32 per label value, a uint32 per resident row */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
     X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans (a _tags call's too), a host call's slot bytes (a _tags call's shorts) */ \
     X(bt_tags) X(bt_rows) X(bt_off) X(bt_work) /* base tags: a uint16 per store row, the tagged rows by (tag, row), their starts per tag; a call's plan workspace */ \
@@ -261,6 +262,12 @@ struct ivfhnsw_gpu {
     // every row untagged.
     uint64_t tg_labels = 0;
     const uint16_t *row_tags = nullptr;
+
+    // row values (capi_filter.cpp), the same with a uint32: vl_table holds one per label value below
+    // vl_labels (0 = no table), vl_rows the value of every resident row; row_values is what the _values scans read, null =
+    // no table, every row without a value.
+    uint64_t vl_labels = 0;
+    const uint32_t *row_values = nullptr;
 
     // the base filter of the exact calls (capi_base_filter.cpp), on the handle that holds the store: a view
     // reads its parent's at the call.  bf_mode -1 = none.  bf_words: one pass bit per row; bf_rows (bf_has_rows): the
@@ -395,6 +402,7 @@ int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBu
 void slots_drop(ivfhnsw_gpu *h); // the handle holds no slot afterwards (buffers released)
 // what a _slots entry point checks first, behind the plain call's own guard
 int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags = false); // tags: the same for a _tags entry point
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, int kind); // ... by QueryPick::kind(): 0 _slots, 1 _tags, 2 _values
 // the slot bytes of a host call: each is below IVFHNSW_FILTER_SLOTS or IVFHNSW_SLOT_NONE
 int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who);
 // (every uint16 is a tag: the host form of a _tags call has nothing to check there)
@@ -402,6 +410,9 @@ int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who);
 // elements).  Returns with the stream drained; the handle is not touched.
 int tags_gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &row_tags);
 void tags_drop(ivfhnsw_gpu *h); // the handle holds no tags afterwards (buffers released)
+// Row values: the same two for the uint32 of every row.
+int values_gather_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBuf &row_values);
+void values_drop(ivfhnsw_gpu *h);
 
 // The five arrays that make up the resident lists, built BESIDE the handle's: an in-place update fills a fresh set and
 // installs it when it is complete and the stream has drained, so that on any error the handle's tables are the ones it
@@ -413,6 +424,7 @@ struct ListArrays {
     DevBuf fplanes; // ... and its filter slots, every plane in one pass
     uint64_t fs_pass[IVFHNSW_FILTER_SLOTS] = {};
     DevBuf ftags; // ... and its row tags, gathered from the tag table
+    DevBuf fvalues; // ... and its row values, gathered from the value table
     ListArrays() = default;
     ListArrays(const ListArrays &) = delete;
     ListArrays &operator=(const ListArrays &) = delete;
@@ -430,12 +442,14 @@ struct ListArrays {
         return {goff.as<uint64_t>(), loff.as<uint32_t>(), codes.as<uint8_t>(), ncodes.as<uint8_t>(), ids.as<uint32_t>(), n_local};
     }
     // The one place an update re-marks the filter: rows move and new rows must be judged.  Called when the new ids are
-    // complete and BEFORE install, so that a failure here leaves tables, filter, slots and tags as they were.  No filter,
-    // no slot and no tag table: nothing.
+    // complete and BEFORE install, so that a failure here leaves tables, filter, slots, tags and values as they were.
+    // No filter, no slot, no tag table and no value table: nothing.
     int mark_filter(ivfhnsw_gpu *h, uint64_t n_local)
     {
         int rc;
         if (h->tg_labels && (rc = tags_gather_rows(h, ids.as<uint32_t>(), n_local, ftags)))
+            return rc;
+        if (h->vl_labels && (rc = values_gather_rows(h, ids.as<uint32_t>(), n_local, fvalues)))
             return rc;
         if (h->fs.nplanes && (rc = slots_mark_rows(h, ids.as<uint32_t>(), n_local, fplanes, fs_pass)))
             return rc;
@@ -445,7 +459,7 @@ struct ListArrays {
     }
     void release()
     {
-        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask, &fplanes, &ftags})
+        for (DevBuf *b : {&goff, &loff, &codes, &ncodes, &ids, &fmask, &fplanes, &ftags, &fvalues})
             b->release();
     }
     void install(ivfhnsw_gpu *h, uint64_t n_local)
@@ -465,6 +479,10 @@ struct ListArrays {
         if (h->tg_labels) {
             std::swap(h->tg_rows, ftags);
             h->row_tags = h->tg_rows.as<uint16_t>();
+        }
+        if (h->vl_labels) {
+            std::swap(h->vl_rows, fvalues);
+            h->row_values = h->vl_rows.as<uint32_t>();
         }
         std::swap(h->goff, goff);
         std::swap(h->loff, loff);
@@ -534,22 +552,32 @@ struct WalkClear {
     bool cleared = false;     // out
 };
 
-// What a _slots or a _tags entry point carries beside the plain call's arguments: a filter slot
-// byte or a tag per query, one of the two at most, in host or device memory as the call's other arrays are.
+// What a _slots, a _tags or a _values entry point carries beside the plain call's arguments:
+// a filter slot byte, a tag or an interval (two uint32: lo, hi) per query, one of the three at most, in host or device
+// memory as the call's other arrays are.
 struct QueryPick {
     const uint8_t *slots = nullptr;
     const uint16_t *tags = nullptr;
-    explicit operator bool() const { return slots || tags; }
-    const void *data() const { return slots ? static_cast<const void *>(slots) : tags; }
-    size_t bytes(size_t nq) const { return slots ? nq : tags ? nq * sizeof(uint16_t) : 0; }
+    const uint32_t *ranges = nullptr;
+    explicit operator bool() const { return slots || tags || ranges; }
+    int kind() const { return ranges ? 2 : tags ? 1 : 0; } // what slots_call_guard is told
+    const void *data() const { return slots ? static_cast<const void *>(slots) : tags ? static_cast<const void *>(tags) : ranges; }
+    size_t bytes(size_t nq) const { return slots ? nq : tags ? nq * sizeof(uint16_t) : ranges ? nq * 2 * sizeof(uint32_t) : 0; }
     // the same kind of pick with its array at p / for the queries from q0 on
     QueryPick at(const void *p) const
     {
-        return {slots ? static_cast<const uint8_t *>(p) : nullptr, tags ? static_cast<const uint16_t *>(p) : nullptr};
+        return {slots ? static_cast<const uint8_t *>(p) : nullptr, tags ? static_cast<const uint16_t *>(p) : nullptr,
+                ranges ? static_cast<const uint32_t *>(p) : nullptr};
     }
-    QueryPick from(size_t q0) const { return {slots ? slots + q0 : nullptr, tags ? tags + q0 : nullptr}; }
-    // the entry point's name: "<call>_slots" or "<call>_tags"
-    const char *who(const char *slotted, const char *tagged) const { return tags ? tagged : slotted; }
+    QueryPick from(size_t q0) const
+    {
+        return {slots ? slots + q0 : nullptr, tags ? tags + q0 : nullptr, ranges ? ranges + 2 * q0 : nullptr};
+    }
+    // the entry point's name: "<call>_slots", "<call>_tags" or "<call>_values"
+    const char *who(const char *slotted, const char *tagged, const char *valued) const
+    {
+        return ranges ? valued : tags ? tagged : slotted;
+    }
 };
 
 // The arguments of ivfhnsw_gpu_search_dev, handed down as one.
@@ -561,7 +589,7 @@ struct SearchArgs {
     const ivfhnsw_search_params *p;
     float *d_distances;
     int64_t *d_labels, *d_out_keys;
-    QueryPick pick{}; // a _slots / _tags call: the filter slot or the tag of every query (device memory), else empty
+    QueryPick pick{}; // a _slots / _tags / _values call: the slot, tag or interval of every query (device memory), else empty
     SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
     {
         return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
@@ -574,7 +602,7 @@ struct SearchArgs {
 struct Chunk : SearchArgs {
     int nprobe, max_seg, plan_k;    // chunk_workspace
     bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
-    ScanFilter fmask;               // a label filter, the call's filter slots (3.19) or its tags (3.21)
+    ScanFilter fmask;               // a label filter, the call's filter slots (3.19), tags (3.21) or values (3.24)
     const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
     const uint32_t *cid;
     const float *cd;

@@ -49,16 +49,18 @@ static int range_fill_pass(ivfhnsw_gpu *h, const Chunk &c, int seg_hint, float r
     return check_status(h);
 }
 
-// ivfhnsw_gpu_range_search_dev, and with a pick (a slot byte or a tag per query, device memory) its _slots / _tags form
+// ivfhnsw_gpu_range_search_dev, and with a pick (a slot byte, a tag or an interval per query, device memory) its _slots / _tags / _values form
 static int range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                             const float *d_coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick,
                             float radius, uint64_t *d_lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, radius, d_lims, total);
-    if (rc || (pick && (rc = slots_call_guard(h, pick.who("range_search_slots_dev", "range_search_tags_dev"), pick.tags != nullptr))))
+    if (rc || (pick && (rc = slots_call_guard(h, pick.who("range_search_slots_dev", "range_search_tags_dev", "range_search_values_dev"), pick.kind()))))
         return rc;
     if ((uintptr_t)pick.tags & 1)
         return fail(IVFHNSW_ERR_INVALID, "range_search_tags_dev: query tags must be 2-byte aligned");
+    if ((uintptr_t)pick.ranges & 7)
+        return fail(IVFHNSW_ERR_INVALID, "range_search_values_dev: query ranges must be 8-byte aligned");
     if (nq == 0) {
         if (d_lims) {
             HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
@@ -168,14 +170,22 @@ int ivfhnsw_gpu_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_
                             total);
 }
 
-// ivfhnsw_gpu_range_search, and with a pick (host memory) ivfhnsw_gpu_range_search_slots / _tags
+int ivfhnsw_gpu_range_search_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                        const float *d_coarse_dists, const ivfhnsw_search_params *p,
+                                        const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, nullptr, d_query_ranges}, radius,
+                            d_lims, total);
+}
+
+// ivfhnsw_gpu_range_search, and with a pick (host memory) ivfhnsw_gpu_range_search_slots / _tags / _values
 static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
                              const float *coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick, float radius,
                              uint64_t *lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, queries, coarse_ids, coarse_dists, p, radius, lims, total);
-    const char *who = pick.who("range_search_slots", "range_search_tags");
-    if (rc || (pick && ((rc = slots_call_guard(h, who, pick.tags != nullptr)) ||
+    const char *who = pick.who("range_search_slots", "range_search_tags", "range_search_values");
+    if (rc || (pick && ((rc = slots_call_guard(h, who, pick.kind())) ||
                         (pick.slots && (rc = slots_bytes_guard(nq, pick.slots, who))))))
         return rc;
     if (nq == 0) {
@@ -215,6 +225,13 @@ int ivfhnsw_gpu_range_search_tags(ivfhnsw_gpu *h, size_t nq, const float *querie
                                   float radius, uint64_t *lims, uint64_t *total)
 {
     return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags}, radius, lims, total);
+}
+
+int ivfhnsw_gpu_range_search_values(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                    const float *coarse_dists, const ivfhnsw_search_params *p, const uint32_t *query_ranges,
+                                    float radius, uint64_t *lims, uint64_t *total)
+{
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, nullptr, query_ranges}, radius, lims, total);
 }
 
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels)

@@ -218,7 +218,7 @@ static int auto_split_permille(const ivfhnsw_gpu *h, const ivfhnsw_search_params
 // box (profiles/r04_early_tables.md): (32, 10000, 80) 1.652 -> 1.617 ms per step.  Only where the second part's walk leaves
 // such slots, i.e. has fewer queries than the walk has resident wavefronts (search_dev_split): at (64, 30000, 100) its 4096
 // queries take every slot the first walk frees, the table workgroups compete with them, and the step measured 0.6 %
-// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter, filter slots, tags or a table that the
+// SLOWER (2.377 -> 2.390 ms; no other cut gained either).  Not for Grouping, shards, a filter, filter slots, tags, values or a table that the
 // pipelined scan builds itself.
 static bool early_tables_wanted(const ivfhnsw_gpu *h, const SearchArgs &a)
 {
@@ -355,8 +355,9 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
 }
 
-// The same call with a filter slot or a tag (3.21) per query.  Neither is read back: a byte that names
-// no installed slot, like a tag no row carries, passes nothing.  An empty pick: the plain call.
+// The same call with a filter slot, a tag (3.21) or a value interval (3.24) per query.  None is read
+// back: a byte that names no installed slot, like a tag no row carries or an interval no row's value lies in, passes
+// nothing.  An empty pick: the plain call.
 static int search_pick_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
                            const float *d_coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick,
                            float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
@@ -365,10 +366,12 @@ static int search_pick_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
         return ivfhnsw_gpu_search_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)) ||
-        (rc = slots_call_guard(h, pick.who("search_slots_dev", "search_tags_dev"), pick.tags != nullptr)))
+        (rc = slots_call_guard(h, pick.who("search_slots_dev", "search_tags_dev", "search_values_dev"), pick.kind())))
         return rc;
     if ((uintptr_t)pick.tags & 1)
         return fail(IVFHNSW_ERR_INVALID, "search_tags_dev: query tags must be 2-byte aligned");
+    if ((uintptr_t)pick.ranges & 7)
+        return fail(IVFHNSW_ERR_INVALID, "search_values_dev: query ranges must be 8-byte aligned");
     SearchCall call;
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys, pick}, call);
 }
@@ -387,6 +390,14 @@ int ivfhnsw_gpu_search_tags_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float
 {
     return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, d_query_tags}, d_distances,
                            d_labels, d_out_keys);
+}
+
+int ivfhnsw_gpu_search_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                  const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint32_t *d_query_ranges,
+                                  float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
+{
+    return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, nullptr, d_query_ranges},
+                           d_distances, d_labels, d_out_keys);
 }
 
 static void remember_plan(ivfhnsw_gpu *h, size_t nq, int max_seg, bool has_stream, const char *kernel_name)
@@ -432,7 +443,9 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
         (rc = h->w_keys.ensure(c.nq * (size_t)c.plan_k * sizeof(uint64_t))) ||
         (rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
-    if (c.pick.tags) // the row tags the handle (a view: its parent) holds, null without a tag table, and this chunk's tags
+    if (c.pick.ranges) // the row values the handle (a view: its parent) holds, null without a table, and this chunk's pairs
+        c.fmask = ValueMask{h->row_values, c.pick.ranges};
+    else if (c.pick.tags) // the row tags the handle (a view: its parent) holds, null without a tag table, and this chunk's tags
         c.fmask = TagMask{h->row_tags, c.pick.tags};
     else if (c.pick.slots) // the planes the handle (a view: its parent) holds -- with none, any readable word: a query
                            // without a plane reads word 0 and ignores it -- and the bytes of this chunk's queries
@@ -585,7 +598,7 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
             HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, nullptr, nullptr, heap_ws, c.d_distances, c.d_labels,
                                      c.fmask));
         }
-        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots", "heap_scan_kernel+tags"));
+        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots", "heap_scan_kernel+tags", "heap_scan_kernel+values"));
         return IVFHNSW_OK;
     }
     if (heap) {
@@ -715,8 +728,8 @@ int ivfhnsw_gpu_replay_stream_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const uin
     return IVFHNSW_OK;
 }
 
-// ivfhnsw_gpu_search, and with a pick (a slot byte or a tag per query, host memory) ivfhnsw_gpu_search_slots / _tags: the
-// bytes ride in the pinned input block or a staging buffer beside the queries
+// ivfhnsw_gpu_search, and with a pick (a slot byte, a tag or an interval per query, host memory) ivfhnsw_gpu_search_slots /
+// _tags / _values: the bytes ride in the pinned input block or a staging buffer beside the queries
 static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
                        const float *coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick, float *distances,
                        int64_t *labels)
@@ -724,8 +737,8 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)))
         return rc;
-    const char *who = pick.who("search_slots", "search_tags");
-    if (pick && (rc = slots_call_guard(h, who, pick.tags != nullptr)))
+    const char *who = pick.who("search_slots", "search_tags", "search_values");
+    if (pick && (rc = slots_call_guard(h, who, pick.kind())))
         return rc;
     if (nq == 0)
         return IVFHNSW_OK;
@@ -739,11 +752,13 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     const size_t in_s = pick.bytes(nq);
     // Small batches -- the reference's drivers pass ONE query per call (tests/test_ivfhnsw_sift1b.cpp:193-208) -- go
     // through pinned host memory the kernels read and write directly: no staging copies, one synchronisation.  Layout
-    // of the two blocks: in = queries | coarse ids | coarse dists; out = distances | labels | status word.
+    // of the two blocks: in = queries | coarse ids | coarse dists | the pick's array, at the next multiple of 8 (a _values
+    // call's pairs are 8-byte aligned wherever they come from); out = distances | labels | status word.
     static const size_t pinned_max_nq = env_size("IVFHNSW_PINNED_MAX_NQ", 256);
     if (nq <= pinned_max_nq) {
         const size_t out_d = (nq * k * sizeof(float) + 7) & ~(size_t)7, out_l = nq * k * sizeof(int64_t);
-        if ((rc = h->p_in.ensure(in_q + 2 * in_c + in_s)) || (rc = h->p_out.ensure(out_d + out_l + 8)))
+        const size_t at_s = (in_q + 2 * in_c + 7) & ~(size_t)7;
+        if ((rc = h->p_in.ensure(at_s + in_s)) || (rc = h->p_out.ensure(out_d + out_l + 8)))
             return rc;
         char *pin = h->p_in.as<char>(), *pout = h->p_out.as<char>();
         memcpy(pin, queries, in_q);
@@ -752,7 +767,7 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
             memcpy(pin + in_q + in_c, coarse_dists, in_c);
         }
         if (pick)
-            memcpy(pin + in_q + 2 * in_c, pick.data(), in_s); // (4-byte aligned: what precedes it is floats and words)
+            memcpy(pin + at_s, pick.data(), in_s);
         uint32_t *pst = reinterpret_cast<uint32_t *>(pout + out_d + out_l);
         uint32_t *bits = &status_words(h)->bits;
         // The latency walk keeps at most 64 exact ties at the efSearch boundary.  This call synchronises anyway, so instead
@@ -765,7 +780,7 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
                                   coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
                                   coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
                                   reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr,
-                                  pick.at(pin + in_q + 2 * in_c)},
+                                  pick.at(pin + at_s)},
                                  call);
             if (rc)
                 return rc;
@@ -815,6 +830,13 @@ int ivfhnsw_gpu_search_tags(ivfhnsw_gpu *h, size_t nq, size_t k, const float *qu
                             float *distances, int64_t *labels)
 {
     return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags}, distances, labels);
+}
+
+int ivfhnsw_gpu_search_values(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                              const float *coarse_dists, const ivfhnsw_search_params *p, const uint32_t *query_ranges,
+                              float *distances, int64_t *labels)
+{
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, nullptr, query_ranges}, distances, labels);
 }
 
 int ivfhnsw_gpu_search_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,

@@ -47,6 +47,7 @@ int upload_tables(ivfhnsw_gpu *h, const ivfhnsw_ivf_desc *d, bool need_lists, ui
     filter_drop(h); // a filter belongs to the lists it was marked over
     slots_drop(h);  // ... and so do the filter slots
     tags_drop(h);   // ... and the row tags
+    values_drop(h); // ... and the row values
     range_drop(h);  // ... and range results to the lists they were found in
     std::vector<uint32_t> loff(d->nc, kNotOwned);
     n_local = 0;

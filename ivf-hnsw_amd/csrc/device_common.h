@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "scan_dispatch.h"
+#include "value_math.h"
 
 namespace ivfhnsw_gpu_impl {
 
@@ -518,14 +519,22 @@ __device__ __forceinline__ const uint32_t *filter_mask(const uint32_t *m) { retu
 // two forms leave the scalars alone.
 struct FilterFill {
     uint32_t keep = ~0u, all = 0u;
+    uint32_t span = 0u, live = 0u; // the fifth form only (ValueMask below): all = lo, span = hi - lo, live = ~0 iff lo <= hi
 };
 template <class T> struct is_slot_mask : std::false_type {};
 template <> struct is_slot_mask<SlotMask> : std::true_type {};
 template <class T> struct is_tag_mask : std::false_type {};
 template <> struct is_tag_mask<TagMask> : std::true_type {};
-// 0 = no filter, 1 = one mask, 2 = a plane per query, 3 = a 16-bit tag per row and per query
+template <class T> struct is_value_mask : std::false_type {};
+template <> struct is_value_mask<ValueMask> : std::true_type {};
+// 0 = no filter, 1 = one mask, 2 = a plane per query, 3 = a 16-bit tag per row and per query, 4 = a uint32 value per row
+// and an interval per query
 template <class... Mask>
-constexpr int filter_kind = sizeof...(Mask) == 0 ? 0 : (is_tag_mask<Mask>::value || ...) ? 3 : (is_slot_mask<Mask>::value || ...) ? 2 : 1;
+constexpr int filter_kind = sizeof...(Mask) == 0                     ? 0
+                            : (is_value_mask<Mask>::value || ...) ? 4
+                            : (is_tag_mask<Mask>::value || ...)   ? 3
+                            : (is_slot_mask<Mask>::value || ...)  ? 2
+                                                                  : 1;
 
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &) { return nullptr; }
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &, const uint32_t *m) { return m; }
@@ -550,6 +559,24 @@ __device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, 
     fill.keep = rows ? ~0u : 0u;
     fill.all = rows || t == 0xffffu ? t : t | 0x10000u;
     return reinterpret_cast<const uint32_t *>(rows ? m.row_tags : m.query_tags);
+}
+// The fifth form (ValueMask, scan_dispatch.h): a uint32 per row, which a lane loads beside the norm code
+// (load_norm_filter<4>: the returned pointer is the row values').  The query's pair goes through readfirstlane, and
+// value_fill (value_math.h) turns it into the scalars of one subtract and one compare (filter_pass<4>): all = lo,
+// span = hi - lo, live = the interval is not empty.  A handle without a table has no row array and every row counts as
+// 0xffffffff: keep = 0 then makes every lane read element 0 of the query ranges (readable, and ignored), and ~keep is
+// OR-ed into the word where it is consumed.
+__device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, const ValueMask &m)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(m.query_ranges[2 * (size_t)q]);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(m.query_ranges[2 * (size_t)q + 1]);
+    const bool rows = m.row_values != nullptr;
+    const ValueFill f = value_fill(lo, hi, rows);
+    fill.keep = f.keep;
+    fill.all = f.lo;
+    fill.span = f.span;
+    fill.live = f.live;
+    return rows ? m.row_values : m.query_ranges;
 }
 
 } // namespace ivfhnsw_gpu_impl

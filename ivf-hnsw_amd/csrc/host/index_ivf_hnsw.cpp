@@ -69,6 +69,8 @@ struct DeviceSide {
     std::vector<SlotSet> slots;
     // set_id_tags: the tag of every label that carries one, installed likewise
     std::unordered_map<uint32_t, uint16_t> tags;
+    // set_id_values: the value of every label that has one, installed likewise
+    std::unordered_map<uint32_t, uint32_t> values;
 };
 std::mutex g_side_mu;
 std::unordered_map<const void *, DeviceSide> g_side;
@@ -136,7 +138,24 @@ void install_id_tags(const void *ix, ivfhnsw_gpu *h)
         gpu_fail("ivfhnsw_gpu_set_tags");
 }
 
-// what search_batch (heap_order 1) and range_search (0) ask of the device, for the _slots and _tags forms alike
+// the index's row values onto its handle, all of them in one call
+void install_id_values(const void *ix, ivfhnsw_gpu *h)
+{
+    std::vector<uint32_t> labels, values;
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(ix);
+        if (it != g_side.end())
+            for (const auto &lv : it->second.values) {
+                labels.push_back(lv.first);
+                values.push_back(lv.second);
+            }
+    }
+    if (!labels.empty() && ivfhnsw_gpu_set_values(h, labels.size(), labels.data(), values.data()))
+        gpu_fail("ivfhnsw_gpu_set_values");
+}
+
+// what search_batch (heap_order 1) and range_search (0) ask of the device, for the _slots, _tags and _values forms alike
 ivfhnsw_search_params per_query_params(const IndexIVF_HNSW *ix, int heap_order)
 {
     const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(ix);
@@ -313,6 +332,66 @@ void IndexIVF_HNSW::range_search_tags(size_t nq, const float *x, const uint16_t 
     if (ivfhnsw_gpu_range_search_tags(gpu_, nq, x, nullptr, nullptr, &p, tags, radius,
                                       reinterpret_cast<uint64_t *>(lims.data()), &total))
         gpu_fail("ivfhnsw_gpu_range_search_tags");
+    fetch_range_results(gpu_, total, distances, labels);
+}
+
+void IndexIVF_HNSW::set_id_values(size_t n, const idx_t *xids, const uint32_t *values)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::set_id_values: IVFHNSW_SHARDS > 1, and sharded handles have no row values");
+    if (n && (!xids || !values))
+        throw std::runtime_error("IndexIVF_HNSW::set_id_values: null ids or values");
+    // an id given two different values is refused whether or not there is a device copy to refuse it
+    std::unordered_map<uint32_t, uint32_t> given;
+    for (size_t i = 0; i < n; i++)
+        if (!given.emplace(xids[i], values[i]).second && given[xids[i]] != values[i])
+            throw std::runtime_error("IndexIVF_HNSW::set_id_values: id " + std::to_string(xids[i]) + " is given two different values");
+    if (gpu_ && device_current() && ivfhnsw_gpu_set_values(gpu_, n, xids, values)) // otherwise the next search's upload installs them
+        gpu_fail("ivfhnsw_gpu_set_values");
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    DeviceSide &side = g_side[this];
+    for (const auto &lv : given) {
+        if (lv.second == IVFHNSW_VALUE_NONE)
+            side.values.erase(lv.first);
+        else
+            side.values[lv.first] = lv.second;
+    }
+}
+
+void IndexIVF_HNSW::clear_id_values()
+{
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(this);
+        if (it != g_side.end())
+            std::unordered_map<uint32_t, uint32_t>().swap(it->second.values);
+    }
+    if (gpu_ && shards_wanted() == 1 && ivfhnsw_gpu_clear_values(gpu_))
+        gpu_fail("ivfhnsw_gpu_clear_values");
+}
+
+void IndexIVF_HNSW::search_batch_values(size_t nq, size_t k, const float *x, const uint32_t *ranges, float *distances, long *labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::search_batch_values: IVFHNSW_SHARDS > 1, and sharded handles have no row values");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 1); // heap order, as search_batch
+    if (ivfhnsw_gpu_search_values(gpu_, nq, k, x, nullptr, nullptr, &p, ranges, distances, reinterpret_cast<int64_t *>(labels)))
+        gpu_fail("ivfhnsw_gpu_search_values");
+}
+
+void IndexIVF_HNSW::range_search_values(size_t nq, const float *x, const uint32_t *ranges, float radius, std::vector<size_t> &lims,
+                                        std::vector<float> &distances, std::vector<long> &labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::range_search_values: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 0);
+    lims.assign(nq + 1, 0);
+    uint64_t total = 0;
+    if (ivfhnsw_gpu_range_search_values(gpu_, nq, x, nullptr, nullptr, &p, ranges, radius,
+                                        reinterpret_cast<uint64_t *>(lims.data()), &total))
+        gpu_fail("ivfhnsw_gpu_range_search_values");
     fetch_range_results(gpu_, total, distances, labels);
 }
 
@@ -564,6 +643,7 @@ void IndexIVF_HNSW::device_upload_common()
         install_id_filter(this, gpu_); // upload_ivf dropped the handle's
         install_id_filter_slots(this, gpu_);
         install_id_tags(this, gpu_);
+        install_id_values(this, gpu_);
     }
     std::lock_guard<std::mutex> lk(g_side_mu);
     DeviceSide &side = g_side[this];

@@ -489,6 +489,14 @@ hipError_t launch_tags_gather(hipStream_t s, const uint32_t *ids, uint64_t n_loc
                               uint16_t *row_tags);
 hipError_t launch_tags_count(hipStream_t s, const uint16_t *row_tags, uint64_t n_local, uint32_t tag, bool equal,
                              unsigned long long *count);
+// Row values (kernels_filter.hip), as the three above with a uint32 per label and per row: none is
+// 0xffffffff, and count: *count (zeroed here) = rows whose value lies in [lo, hi], unsigned and inclusive (lo > hi: none).
+hipError_t launch_values_scatter(hipStream_t s, const uint32_t *labels, const uint32_t *values, size_t n, uint32_t *table,
+                                 uint32_t *conflict);
+hipError_t launch_values_gather(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *table, uint64_t table_n,
+                                uint32_t *row_values);
+hipError_t launch_values_count(hipStream_t s, const uint32_t *row_values, uint64_t n_local, uint32_t lo, uint32_t hi,
+                               unsigned long long *count);
 // additions to a Grouping index (kernels_add_groups.hip): its codes go in with the append launchers above.
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --

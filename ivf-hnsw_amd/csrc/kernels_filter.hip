@@ -167,6 +167,69 @@ __global__ __launch_bounds__(256) void tags_count_kernel(const uint16_t *__restr
     }
 }
 
+// ---- row values: a uint32 per label value (the table), gathered into a uint32 per resident row.  The
+// tag kernels above are not generalised over the element type: the tag gather packs two rows into one 32-bit store and the
+// tag count compares for equality, where a value row is a word of its own and is judged against an interval; the scatter
+// and the verify differ in the element type alone, but as templates they would change the names the tag forms are compiled
+// under, and the kernels that existed keep theirs.
+
+// table[labels[i]] = values[i]; the table spans every label given
+__global__ __launch_bounds__(256) void values_scatter_kernel(const uint32_t *__restrict__ labels, const uint32_t *__restrict__ values,
+                                                             size_t n, uint32_t *__restrict__ table)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        table[labels[i]] = values[i];
+}
+
+// ... and the check behind it: a label given two different values kept one of them, so the other entry does not read back
+__global__ __launch_bounds__(256) void values_verify_kernel(const uint32_t *__restrict__ labels, const uint32_t *__restrict__ values,
+                                                            size_t n, const uint32_t *__restrict__ table, uint32_t *__restrict__ conflict)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        bad |= table[labels[i]] != values[i];
+    if (bad)
+        atomicOr(conflict, 1u);
+}
+
+// row_values[r] = ids[r] < table_n ? table[ids[r]] : none
+__global__ __launch_bounds__(256) void values_gather_kernel(const uint32_t *__restrict__ ids, uint64_t n_local,
+                                                            const uint32_t *__restrict__ table, uint64_t table_n,
+                                                            uint32_t *__restrict__ row_values)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_local; r += stride) {
+        const uint32_t id = ids[r];
+        row_values[r] = id < table_n ? table[id] : kValueNone;
+    }
+}
+
+// *count += rows whose value lies in [lo, hi] (value_math.h): a ballot per wavefront, one atomic per workgroup
+__global__ __launch_bounds__(256) void values_count_kernel(const uint32_t *__restrict__ row_values, uint64_t n_local, uint32_t lo,
+                                                           uint32_t hi, unsigned long long *__restrict__ count)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const ValueFill f = value_fill(lo, hi, true);
+    uint32_t c = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 256; r0 < n_local; r0 += stride) { // workgroup-uniform bound: every lane ballots
+        const uint64_t r = r0 + threadIdx.x;
+        const bool hit = r < n_local && value_pass(row_values[r], f);
+        c += (uint32_t)__popcll(__ballot(hit));
+    }
+    if (lane == 0)
+        s_cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (t)
+            atomicAdd(count, (unsigned long long)t);
+    }
+}
+
 } // namespace
 
 static unsigned tags_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
@@ -202,6 +265,38 @@ hipError_t launch_tags_count(hipStream_t s, const uint16_t *row_tags, uint64_t n
     if (n_local == 0)
         return hipSuccess;
     hipLaunchKernelGGL(tags_count_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, row_tags, n_local, tag, equal ? 1 : 0, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_values_scatter(hipStream_t s, const uint32_t *labels, const uint32_t *values, size_t n, uint32_t *table,
+                                 uint32_t *conflict)
+{
+    if (hipError_t e = hipMemsetAsync(conflict, 0, sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(values_scatter_kernel, dim3(tags_grid(n)), dim3(256), 0, s, labels, values, n, table);
+    hipLaunchKernelGGL(values_verify_kernel, dim3(tags_grid(n)), dim3(256), 0, s, labels, values, n, table, conflict);
+    return hipGetLastError();
+}
+
+hipError_t launch_values_gather(hipStream_t s, const uint32_t *ids, uint64_t n_local, const uint32_t *table, uint64_t table_n,
+                                uint32_t *row_values)
+{
+    if (n_local == 0) // the one element the array always has
+        return hipMemsetAsync(row_values, 0xff, sizeof(uint32_t), s);
+    hipLaunchKernelGGL(values_gather_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, ids, n_local, table, table_n, row_values);
+    return hipGetLastError();
+}
+
+hipError_t launch_values_count(hipStream_t s, const uint32_t *row_values, uint64_t n_local, uint32_t lo, uint32_t hi,
+                               unsigned long long *count)
+{
+    if (hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), s); e != hipSuccess)
+        return e;
+    if (n_local == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(values_count_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, row_values, n_local, lo, hi, count);
     return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 // How a scan launcher turns two run-time facts -- the code size and how the call is filtered (not at all, by the handle's
-// label filter, by a filter slot per query, by a row tag per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
+// label filter, by a filter slot per query, by a row tag per query, by a value interval per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
 //
 //     by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {          // decltype(cs)::value: 4, 8, 16, 32, or 0 = run-time form
-//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, a SlotMask or a TagMask
+//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, a SlotMask, a TagMask or a ValueMask
 //             launch kernel<decltype(cs)::value, ..., decltype(m)...> with the arguments (..., m...)
 //         });
 //     });
@@ -56,25 +56,42 @@ struct TagMask {
     const uint16_t *query_tags;
 };
 
+// The fifth form: a uint32 value per row, an interval per query.  row_values: the value of every local
+// row; query_ranges: the pair (lo, hi) of query q at [2q], [2q + 1].  A row passes iff lo <= value <= hi, unsigned and
+// inclusive (value_math.h); a row without a value holds 0xffffffff.  A handle without a table has no row array:
+// row_values is then null and every row reads as 0xffffffff (filter_mask points such a launch at one readable element).
+struct ValueMask {
+    const uint32_t *row_values;
+    const uint32_t *query_ranges;
+};
+
 // What a scan launcher is told about the filter of its call: nothing, the pass mask of the handle's filter, filter
-// slots per query (slots.slots non-null) or a tag per query (tags.query_tags non-null).  A bare mask pointer converts, so
-// a caller with one filter passes it as before.
+// slots per query (slots.slots non-null), a tag per query (tags.query_tags non-null) or an interval per query
+// (values.query_ranges non-null).  A bare mask pointer converts, so a caller with one filter passes it as before.
 struct ScanFilter {
     const uint32_t *fmask = nullptr;
     SlotMask slots{nullptr, 0, 0, nullptr};
     TagMask tags{nullptr, nullptr};
+    ValueMask values{nullptr, nullptr};
     ScanFilter() = default;
     ScanFilter(const uint32_t *m) : fmask(m) {}
     ScanFilter(std::nullptr_t) {}
     ScanFilter(const SlotMask &s) : slots(s) {}
     ScanFilter(const TagMask &t) : tags(t) {}
+    ScanFilter(const ValueMask &v) : values(v) {}
     bool by_slot() const { return slots.slots != nullptr; }
     bool by_tag() const { return tags.query_tags != nullptr; }
-    bool any() const { return fmask || by_slot() || by_tag(); }
+    bool by_value() const { return values.query_ranges != nullptr; }
+    bool any() const { return fmask || by_slot() || by_tag() || by_value(); }
     // the name a launcher reports: the plain kernel's, "+filter", "+slots" or "+tags" behind it
     const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged) const
     {
         return by_tag() ? tagged : by_slot() ? slotted : fmask ? filtered : plain;
+    }
+    // ... and of a launcher that has a value form too: "+values" behind it
+    const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged, const char *valued) const
+    {
+        return by_value() ? valued : name(plain, filtered, slotted, tagged);
     }
     // the queries [q0, ...) of the same call
     ScanFilter from(size_t q0) const
@@ -84,14 +101,16 @@ struct ScanFilter {
             r.slots.slots += q0;
         if (r.by_tag())
             r.tags.query_tags += q0;
+        if (r.by_value())
+            r.values.query_ranges += 2 * q0;
         return r;
     }
 };
 
-// f(tags) with a tag per query, f(slots) with filter slots, else as above
+// f(values) with an interval per query, f(tags) with a tag per query, f(slots) with filter slots, else as above
 template <class F> auto with_mask(const ScanFilter &flt, F &&f)
 {
-    return flt.by_tag() ? f(flt.tags) : flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f);
+    return flt.by_value() ? f(flt.values) : flt.by_tag() ? f(flt.tags) : flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f);
 }
 
 } // namespace ivfhnsw_gpu_impl

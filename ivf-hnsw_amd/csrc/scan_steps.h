@@ -49,7 +49,8 @@ template <int CS> __device__ __forceinline__ float code_sum_lds(const float *s_l
 // KIND: filter_kind (device_common.h).  Under filter slots (2) a query without a plane (FilterFill: keep = 0) reads word 0
 // whatever the row, so that no branch stands here; nothing is done to the loaded word before filter_pass, because a use
 // of it here makes the compiler wait for each unrolled step's loads before it issues the next step's.  Under row tags (3,
-// DESIGN.md 3.21) the word is the row's tag and a handle without tags (keep = 0) reads element 0 the same way.
+// DESIGN.md 3.21) the word is the row's tag and a handle without tags (keep = 0) reads element 0 the same way.  Under row
+// values (4) it is the row's uint32, read the same way.
 template <int KIND>
 __device__ __forceinline__ void load_norm_filter(const uint8_t *norm_codes, const uint32_t *fmask, uint32_t row, uint32_t &nb,
                                                  uint32_t &fw, [[maybe_unused]] const FilterFill &fill = FilterFill())
@@ -61,6 +62,8 @@ __device__ __forceinline__ void load_norm_filter(const uint8_t *norm_codes, cons
         fw = fmask[(row >> 5) & fill.keep];
     if constexpr (KIND == 3) // the row's 16-bit tag, zero-extended: the 64 lanes of a wavefront read 128 contiguous bytes
         fw = reinterpret_cast<const uint16_t *>(fmask)[row & fill.keep];
+    if constexpr (KIND == 4) // the row's value: one dword, the 64 lanes of a wavefront read 256 contiguous bytes
+        fw = fmask[value_index(row, fill.keep)];
 }
 // fb = row & 31: the row's bit in that word
 __device__ __forceinline__ bool filter_pass(uint32_t fw, uint32_t fb) { return (fw >> fb) & 1u; }
@@ -71,6 +74,8 @@ template <int KIND> __device__ __forceinline__ bool filter_pass(uint32_t fw, uin
         fw = (fw & fill.keep) | fill.all;
     if constexpr (KIND == 3) // a tag per row: equal to the query's scalar, or the query is untagged (wave-uniform); no branch
         return (fw == fill.all) | (fill.all == 0xffffu);
+    if constexpr (KIND == 4) // a value per row: inside the query's interval (value_math.h); no branch
+        return value_pass(fw, fill.keep, fill.all, fill.span, fill.live);
     return (fw >> fb) & 1u;
 }
 

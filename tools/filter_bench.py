@@ -26,9 +26,20 @@ r % 1024, so tags and the slots' sets below partition the same rows):
      --loop-tags tags, wall ms per tag, extrapolated to the 1 024 tags of one batch.
   7. set_tags_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev without and with the tag table (wall ms, each
      twice: what the append costs beyond the untagged one is the gather).
+With --values, row values (ivfhnsw_gpu_search_values), on the same corpus and ONE handle (row r carries
+tag r % 1024 and value r % 1024: value = tag, so both forms pass the same rows):
+  8. --reps (>= 5) alternating repetitions of: (a) unfiltered; (b) _tags with 1 024 tags, the queries dealt over them;
+     (c) _values with the same 1 024 points (t, t); (d) _values with intervals of 128 consecutive values (pass fraction
+     1/8, overlapping from query to query: what tags cannot express); (e) _values, every query (0, 0xffffffff).  Step and
+     scan time as in 3.
+  9. the loop (d) replaces: per distinct interval set_filter_dev(rows whose value lies in it) + search_dev of that
+     interval's queries, for a sample of --loop-tags intervals, wall ms per interval.
+ 10. set_values_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev with and without the value table (wall ms,
+     each twice: what the append costs beyond the plain one is the gather).
 usage: python tools/filter_bench.py [--workload NAME] [--sizes 1000,10000000,500000000] [--fractions 0.5,0.1,0.01]
        python tools/filter_bench.py --slots [--reps 5] [--append 10000000]
-       python tools/filter_bench.py --tags [--reps 5] [--append 10000000] [--loop-tags 8]"""
+       python tools/filter_bench.py --tags [--reps 5] [--append 10000000] [--loop-tags 8]
+       python tools/filter_bench.py --values [--reps 5] [--append 10000000] [--loop-tags 8]"""
 import argparse
 import json
 import os
@@ -300,6 +311,159 @@ def tags_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out):
     out["append"] = appends
 
 
+def values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out):
+    n = c.n_total
+    ids = torch.arange(n, device=dev, dtype=torch.int64)
+    lab = ids.to(torch.int32)
+    tg = (ids % 1024).to(torch.int16)
+    vl = (ids % 1024).to(torch.int32)
+    del ids
+    torch.cuda.synchronize(dev)
+    mem0 = g.memory_bytes()
+    g.set_tags_dev(n, lab, tg)
+    t = time.perf_counter()
+    g.set_values_dev(n, lab, vl)
+    out["set_values_dev_all_rows_ms"] = (time.perf_counter() - t) * 1e3
+    del lab, tg, vl
+    out["memory_GB_tags_and_values"] = (g.memory_bytes() - mem0) / 1e9
+    assert g.values_info() == (n, n, n) and g.value_rows(0, 127) == 128 * (n // 1024) + min(n % 1024, 128)
+    qi = torch.arange(nq, device=dev) % 1024
+    qtags = qi.to(torch.int16)
+    points = torch.stack([qi, qi], 1).to(torch.int32).contiguous()
+    lo = (qi * 7) % 897  # 897 = 1024 - 127: every interval lies inside the values, and neighbours overlap
+    eighth = torch.stack([lo, lo + 127], 1).to(torch.int32).contiguous()
+    full = torch.stack([torch.zeros_like(qi), torch.full_like(qi, -1)], 1).to(torch.int32).contiguous()  # (0, 0xffffffff)
+    torch.cuda.synchronize(dev)
+
+    def step(form):
+        kind, pick = form
+        if kind == "plain":
+            g.search_dev(nq, 1, q, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        elif kind == "tags":
+            g.search_tags_dev(nq, 1, q, pick, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        else:
+            g.search_values_dev(nq, 1, q, pick, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+
+    def measure(form, steps=10):
+        for _ in range(5):
+            step(form)
+        g.sync()
+        t = time.perf_counter()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        g.set_profiling(2)
+        g.reset_stage_ms()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        scan = g.stage_ms()["scan"][0] / steps
+        g.set_profiling(0)
+        return wall, scan, g.last_scan_kernel()
+
+    forms = [("a unfiltered", ("plain", None)), ("b tags, 1024 dealt", ("tags", qtags)),
+             ("c values, 1024 points", ("values", points)), ("d values, 1/8 intervals", ("values", eighth)),
+             ("e values, all (0, 0xffffffff)", ("values", full))]
+    runs = {name: {"step_ms": [], "scan_ms": []} for name, _ in forms}
+    for _ in range(max(5, args.reps)):
+        for name, form in forms:
+            wall, scan, kernel = measure(form)
+            runs[name]["step_ms"].append(wall)
+            runs[name]["scan_ms"].append(scan)
+            runs[name]["kernel"] = kernel
+    # the same rows pass (b) and (c): the same answers
+    step(("tags", qtags))
+    g.sync()
+    want = ll.clone()
+    step(("values", points))
+    g.sync()
+    out["points_equal_tags"] = bool(torch.equal(want, ll))
+    for name, r in runs.items():
+        for key in ("step_ms", "scan_ms"):
+            v = r[key]
+            r[key + "_min_mean_max"] = [min(v), sum(v) / len(v), max(v)]
+        log("[filter_bench] %-32s step %.4f ms, scan %.4f ms  (%s)" %
+            (name, r["step_ms_min_mean_max"][1], r["scan_ms_min_mean_max"][1], r["kernel"]))
+    out["values_search"] = runs
+    b, cc = runs["b tags, 1024 dealt"], runs["c values, 1024 points"]
+    out["c_minus_b_scan_ms"] = cc["scan_ms_min_mean_max"][1] - b["scan_ms_min_mean_max"][1]
+    out["b_scan_spread_ms"] = b["scan_ms_min_mean_max"][2] - b["scan_ms_min_mean_max"][0]
+    out["c_minus_b_step_ms"] = cc["step_ms_min_mean_max"][1] - b["step_ms_min_mean_max"][1]
+    out["b_step_spread_ms"] = b["step_ms_min_mean_max"][2] - b["step_ms_min_mean_max"][0]
+
+    # 9. the loop one search_values call replaces: a filter per distinct interval
+    distinct = torch.unique(eighth, dim=0)
+    out["distinct_intervals"] = int(distinct.shape[0])
+    per_q = max(1, nq // int(distinct.shape[0]))
+    loop = []
+    for i in range(args.loop_tags):
+        a, b_ = int(distinct[i, 0]), int(distinct[i, 1])
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        r = torch.arange(n, device=dev, dtype=torch.int64)
+        m = r % 1024
+        lab = r[(m >= a) & (m <= b_)].to(torch.int32)  # the application's side of the loop: the labels of the interval
+        del r, m
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        g.set_filter_dev(lab.numel(), lab)
+        g.search_dev(per_q, 1, q[i * per_q:(i + 1) * per_q], dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        g.sync()
+        t2 = time.perf_counter()
+        loop.append({"labels_ms": (t1 - t) * 1e3, "set_filter_and_search_ms": (t2 - t1) * 1e3})
+        del lab
+    g.clear_filter()
+    out["loop_per_interval"] = loop
+    tail = [x["set_filter_and_search_ms"] for x in loop[1:]] or [loop[0]["set_filter_and_search_ms"]]  # the first call allocates
+    out["loop_ms_all_intervals_extrapolated"] = sum(tail) / len(tail) * int(distinct.shape[0])
+    log("[filter_bench] set_filter_dev + search_dev per interval: %s ms; x %d = %.0f ms against one search_values step of %.3f ms"
+        % (", ".join("%.2f" % x["set_filter_and_search_ms"] for x in loop), int(distinct.shape[0]),
+           out["loop_ms_all_intervals_extrapolated"], runs["d values, 1/8 intervals"]["step_ms_min_mean_max"][1]))
+
+    # 10. install and re-derivation
+    g.clear_tags()
+    n10m = min(10 ** 7, n)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(31)
+    lab = (torch.arange(n10m, device=dev, dtype=torch.int64) * max(1, n // n10m))[torch.randperm(n10m, device=dev, generator=gen)]
+    lab = lab.to(torch.int32)  # the same bits as uint32: every K-th id, in random order
+    vl = (torch.arange(n10m, device=dev) % 1024).to(torch.int32)
+    torch.cuda.synchronize(dev)
+    t = time.perf_counter()
+    g.set_values_dev(n10m, lab, vl)
+    out["set_values_dev_10M_ms"] = (time.perf_counter() - t) * 1e3
+    log("[filter_bench] set_values_dev of %d labels on %d rows: %.1f ms" % (n10m, n, out["set_values_dev_10M_ms"]))
+    del lab, vl
+    na = args.append
+    li = torch.randint(0, c.nc, (na,), device=dev, generator=gen, dtype=torch.int32)
+    codes = torch.randint(0, 256, (na, c.M), device=dev, generator=gen, dtype=torch.uint8)
+    ncodes = torch.randint(0, 255, (na,), device=dev, generator=gen, dtype=torch.uint8)
+    torch.cuda.synchronize(dev)
+    appends = []
+    first_id = n
+
+    def timed_append(what):
+        nonlocal first_id
+        new = (torch.arange(na, device=dev, dtype=torch.int64) + first_id).to(torch.int32)
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        g.append_ivf_dev(na, li, new, codes, ncodes)
+        g.sync()
+        ms = (time.perf_counter() - t) * 1e3
+        first_id += na
+        appends.append({"installed": what, "append_ms": ms})
+        log("[filter_bench] append_ivf_dev of %d codes, %s: %.1f ms" % (na, what, ms))
+
+    timed_append("the value table (warm-up: allocations)")
+    timed_append("the value table")
+    timed_append("the value table")
+    g.clear_values()
+    timed_append("nothing")
+    timed_append("nothing")
+    out["append"] = appends
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="synthetic-1B-pq16-nc993127-nprobe32")
@@ -307,6 +471,7 @@ def main():
     ap.add_argument("--fractions", default="0.5,0.1,0.01")
     ap.add_argument("--slots", action="store_true")
     ap.add_argument("--tags", action="store_true")
+    ap.add_argument("--values", action="store_true")
     ap.add_argument("--loop-tags", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--append", type=int, default=10 ** 7)
@@ -357,6 +522,11 @@ def main():
         assert total == c.n_total and passing == (total - n if deny else n), (mode, passing, total, n)
         return ms, passing
 
+    if args.values:
+        values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out)
+        g.close()
+        print(json.dumps(out))
+        return
     if args.tags:
         tags_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out)
         g.close()

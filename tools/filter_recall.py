@@ -15,7 +15,10 @@ spread evenly over the tags 4..1023 -- and the queries are dealt over a sample o
 scored against the truth of a tagged search, the per-tag loop of set_base_filter + exact_search.
 With --base-tags: the same corpus and tags, installed on the store as well (ivfhnsw_gpu_set_base_tags); the
 queries are dealt over ALL 1 024 tags and NONE, and ONE search_tags call is scored against ONE exact_search_tags call.
-usage: python tools/filter_recall.py [--seed 77] [--slots | --tags | --base-tags] [--out result.json]"""
+With --values: every row gets a distinct value (a seeded permutation of 0..n-1: a timestamp), and the
+queries are dealt over a handful of sample intervals -- four of pass fraction 1/8 that overlap one another, five of about
+1/2000, and (0, 0xffffffff); ONE search_values call is scored against the per-interval loop of set_base_filter + exact_search.
+usage: python tools/filter_recall.py [--seed 77] [--slots | --tags | --base-tags | --values] [--out result.json]"""
 import argparse
 import json
 import os
@@ -228,6 +231,61 @@ def base_tags_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
     return {"rows": n, "nq": nq, "tags": 1024, "base_tags_recall": rows_out, "truth": truth, "query_tags": qt, "tags_of_rows": tags}
 
 
+VALUE_NONE = 0xffffffff
+
+
+def value_intervals(n):
+    """The sample intervals over values 0..n-1: (name of the pass fraction, lo, hi)."""
+    w8, w2k = n // 8, max(1, n // 2000)
+    out = [("1/8", a, a + w8 - 1) for a in (0, w8 // 2, n // 2 - w8 // 3, n - w8)]  # neighbours overlap: no tag partition
+    out += [("~1/2000", a, a + w2k - 1) for a in (0, n // 7, n // 3, n // 2, n - w2k)]
+    out.append(("1 (0, 0xffffffff)", 0, VALUE_NONE))
+    return out
+
+
+def values_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
+    """Recall of one search_values call against the per-interval loop of set_base_filter + exact_search."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    values = np.random.default_rng(seed + 5).permutation(n).astype(np.uint32)  # the value of row (= id) i
+    g.set_values(np.arange(n, dtype=np.uint32), values)
+    assert g.values_info() == (n, n, n)
+    sample = value_intervals(n)
+    pick = np.arange(nq) % len(sample)
+    qr = np.array([(sample[i][1], sample[i][2]) for i in pick], np.uint32)
+    truth = np.empty((nq, 10), np.int64)
+    for i, (_, lo, hi) in enumerate(sample):
+        mine = np.flatnonzero(pick == i)
+        if hi == VALUE_NONE:
+            g.clear_base_filter()
+        else:
+            rows = np.flatnonzero((values >= lo) & (values <= hi)).astype(np.uint32)
+            assert g.value_rows(lo, hi) == rows.size
+            g.set_base_filter(rows)
+        truth[mine] = g.exact_search(q8[mine], 10)[1]
+    g.clear_base_filter()
+    rows_out = []
+    names = np.array([s_[0] for s_ in sample])
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_values(qf, 10, qr, nprobe, max_codes, efSearch=ef)
+        assert g.last_scan_kernel().endswith("+values")
+        for name in ("1/8", "~1/2000", "1 (0, 0xffffffff)"):
+            idx = np.flatnonzero(names[pick] == name)
+            r1, r10 = recall_pair(lab[idx], truth[idx])
+            rows_out.append({"pass_fraction": name, "queries": int(idx.size), "nprobe": nprobe, "max_codes": max_codes,
+                             "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] values, %s (%d queries), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, idx.size, nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "intervals": len(sample), "values_recall": rows_out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
@@ -235,6 +293,7 @@ def main():
     ap.add_argument("--base-tags", action="store_true", help="one search_tags call against one exact_search_tags call, "
                                                               "the queries over all 1 024 tags")
     ap.add_argument("--slots", action="store_true", help="one search_slots call against one exact_search_slots call")
+    ap.add_argument("--values", action="store_true", help="one search_values call against the per-interval base-filter loop")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -242,6 +301,9 @@ def main():
     if args.base_tags:
         out = base_tags_recall(pkg, args.seed)
         out = {k: v for k, v in out.items() if k not in ("truth", "query_tags", "tags_of_rows")}
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    elif args.values:
+        out = values_recall(pkg, args.seed)
         out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
     elif args.tags:
         out = tags_recall(pkg, args.seed)
