@@ -985,6 +985,69 @@ int ivfhnsw_gpu_exact_range_search_tags(ivfhnsw_gpu *h, size_t nq, const uint8_t
 int ivfhnsw_gpu_exact_range_search_tags_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
                                             const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
 
+/* ---- base values: a uint32 per ROW OF THE STORE, an interval per query of an exact call -----------------
+ *
+ * The truth of a _values search ("Row values" above) in one call.  The handle that holds the store holds at most one base
+ * value array, one uint32 per store row; a row never given a value reads as IVFHNSW_VALUE_NONE (0xffffffff).  The _values
+ * forms of both exact calls take one pair per query, query_ranges[2 q] = lo and query_ranges[2 q + 1] = hi: store row r
+ * passes query q iff lo <= value(r) <= hi, unsigned and inclusive at both ends -- the rule of "Row values", with no special
+ * value.  Query q gets, bit for bit, what the plain call returns on the same handle with set_base_filter({rows whose value
+ * lies in [lo, hi]}, IVFHNSW_FILTER_ALLOW) installed -- exact_search: the original row numbers with the same distance
+ * bits, ascending by (distance, label), padded with FLT_MAX / -1 when fewer than k rows pass; the range search: results
+ * per query in ascending label, exact lims IN THE CALLER'S QUERY ORDER, held in the handle's exact-range buffers and read
+ * with ivfhnsw_gpu_exact_range_results[_dev].  (0, 0xffffffff) is the plain unfiltered call's answer; lo > hi, or an
+ * interval no row falls in, returns padding or an empty range.  query_ranges == NULL is the plain call: same path, same
+ * kernels.  A _values call on a store without a value array is legal: every row is IVFHNSW_VALUE_NONE.
+ *   Independent state: plain, _slots and _tags calls never read values, a _values call ignores base filter slots and base
+ * tags, and a _values call on a store with a set_base_filter filter installed -> IVFHNSW_ERR_STATE (the two are not
+ * combined).  The index's row values (ivfhnsw_gpu_set_values) and the base values never read each other.
+ *   The work follows each query's own interval.  The holder keeps ALL row numbers ordered by (value, row), so an interval
+ * is one window of positions of that order, found on the device by two binary searches per query.  A query whose window
+ * is the whole store sweeps it with the unfiltered kernel; a query whose window is empty is not swept; the others are
+ * sorted by their windows' starts and cut into strips of 32, and a strip sweeps the rows from its first window's start to
+ * its furthest end while every one of its queries counts only the rows of ITS OWN window: at most two sweep launches and
+ * m / 32 + 2 strips per chunk of m queries, however many distinct intervals they name.  Intervals far apart in one strip
+ * sweep the rows between them without scoring them.  One split count per call, as for the _slots and _tags forms.  The
+ * range form ends with a reorder of the held results to (query, label) when a windowed strip ran: 28 bytes and a little
+ * more per result while it runs, freed before the call returns.
+ * ivfhnsw_gpu_set_base_values mirrors ivfhnsw_gpu_set_base_tags with a value in place of a tag: incremental; a row number
+ *   >= n matches nothing; a repeat with the same value counts once, one row given two different values in one call ->
+ *   IVFHNSW_ERR_INVALID, found on the device before anything is swapped; the value IVFHNSW_VALUE_NONE un-values a row.  The
+ *   new state is built beside the installed one and swapped in, so any error leaves the state as it was.  Synchronous on
+ *   the handle's stream.  _dev: d_rows and d_values 4-byte aligned device memory, else IVFHNSW_ERR_INVALID; d_query_ranges
+ *   of the _dev calls: 8-byte aligned, as in "Row values".
+ *   ivfhnsw_gpu_clear_base_values succeeds when there are none.  ivfhnsw_gpu_upload_base[_dev] with first == 0 or n == 0
+ *   drops the values; a later chunk (first > 0) keeps them.
+ *   ivfhnsw_gpu_base_values_info: *rows_valued = rows whose value is not IVFHNSW_VALUE_NONE, *rows_total = rows of the
+ *   store; each nullable.  ivfhnsw_gpu_base_value_rows: *rows = rows of the store whose value lies in [lo, hi] (valueless
+ *   rows count at 0xffffffff), the size of the window the calls sweep.
+ * Views: set / clear on a view -> IVFHNSW_ERR_STATE.  A view reads its parent's values at the call, and both info calls
+ *   report the parent's.
+ * Memory, all counted by ivfhnsw_gpu_memory_bytes: 4 n bytes of values and 4 n bytes of row numbers, 8 GB on a store of
+ *   10^9 rows; no sorted copy of the values is kept (a window's search reads values through the row order).  A set call
+ *   takes 12 n bytes more while it runs (the new values and the sort's two permutations, one of which stays) and frees
+ *   what it replaces.  Per calling handle the strip plans of its last _values call (400 bytes per strip), about 0.4 MB of
+ *   plan workspace and a host form's staged 8 bytes per query.
+ * Errors: NULL rows or values with n > 0, a misaligned device pointer, conflicting repeats, a NULL result ->
+ *   IVFHNSW_ERR_INVALID; set, base_value_rows or a _values call before upload_base -> IVFHNSW_ERR_STATE; a failed
+ *   allocation -> IVFHNSW_ERR_NOMEM; limits and errors of the plain calls hold unchanged, and whatever they refuse is
+ *   refused with their status.
+ * Not built: an interval AND the base filter, a slot or a tag; cost-aware grouping of the queries into strips (a strip
+ *   sweeps from its first window's start to its furthest end); a split count per form; 64-bit values; the class surface. */
+int ivfhnsw_gpu_set_base_values(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, const uint32_t *values);
+int ivfhnsw_gpu_set_base_values_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows, const uint32_t *d_values);
+int ivfhnsw_gpu_clear_base_values(ivfhnsw_gpu *h);
+int ivfhnsw_gpu_base_values_info(ivfhnsw_gpu *h, uint64_t *rows_valued, uint64_t *rows_total);
+int ivfhnsw_gpu_base_value_rows(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *rows);
+int ivfhnsw_gpu_exact_search_values(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride, size_t k,
+                                    const uint32_t *query_ranges, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_values_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
+                                        const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels);
+int ivfhnsw_gpu_exact_range_search_values(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, size_t row_stride,
+                                          const uint32_t *query_ranges, float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_values_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride,
+                                              const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 /* ---- construction side: what IndexIVF_HNSW::add_batch computes before it appends --------

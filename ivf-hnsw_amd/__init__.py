@@ -68,6 +68,10 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_base_tags_info", "ivfhnsw_gpu_base_tag_rows",
     "ivfhnsw_gpu_exact_search_tags", "ivfhnsw_gpu_exact_search_tags_dev",
     "ivfhnsw_gpu_exact_range_search_tags", "ivfhnsw_gpu_exact_range_search_tags_dev",
+    "ivfhnsw_gpu_set_base_values", "ivfhnsw_gpu_set_base_values_dev", "ivfhnsw_gpu_clear_base_values",
+    "ivfhnsw_gpu_base_values_info", "ivfhnsw_gpu_base_value_rows",
+    "ivfhnsw_gpu_exact_search_values", "ivfhnsw_gpu_exact_search_values_dev",
+    "ivfhnsw_gpu_exact_range_search_values", "ivfhnsw_gpu_exact_range_search_values_dev",
     "ivfhnsw_gpu_upsert_ivf", "ivfhnsw_gpu_upsert_ivf_dev", "ivfhnsw_gpu_upsert", "ivfhnsw_gpu_upsert_dev",
 )
 
@@ -256,6 +260,15 @@ def lib():
         L.ivfhnsw_gpu_exact_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_tags.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_set_base_values.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_set_base_values_dev.argtypes = L.ivfhnsw_gpu_set_base_values.argtypes
+        L.ivfhnsw_gpu_clear_base_values.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_base_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_base_value_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.ivfhnsw_gpu_exact_search_values.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
@@ -1448,6 +1461,73 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_exact_range_search_tags_dev(self._h, nq, _devptr(d_queries), row_stride,
                                                              _devptr(d_query_tags), C.c_float(radius), _devptr(d_lims),
                                                              C.byref(total)))
+        return int(total.value)
+
+    # ---- base values: a uint32 per store row, an interval per query (ivfhnsw_gpu_set_base_values) ----
+    def set_base_values(self, rows, values):
+        """The rows of the base store given hold the values given (uint32; VALUE_NONE un-values) from now on; every other
+        row keeps its value.  The exact _values calls name an interval per query."""
+        r = _np(rows, np.uint32).ravel()
+        v = _np(values, np.uint32).ravel()
+        if v.size != r.size:
+            raise ValueError("set_base_values: %d rows, %d values" % (r.size, v.size))
+        _check(lib().ivfhnsw_gpu_set_base_values(self._h, r.size, _ptr(r) if r.size else None, _ptr(v) if v.size else None))
+
+    def set_base_values_dev(self, n, d_rows, d_values):
+        """The same on device buffers (torch CUDA tensors or raw addresses)."""
+        _check(lib().ivfhnsw_gpu_set_base_values_dev(self._h, n, _devptr(d_rows), _devptr(d_values)))
+
+    def clear_base_values(self):
+        """No row of the base store holds a value afterwards."""
+        _check(lib().ivfhnsw_gpu_clear_base_values(self._h))
+
+    def base_values_info(self):
+        """(rows_valued, rows_total) of the base store."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_values_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def base_value_rows(self, lo, hi):
+        """Rows of the base store whose value lies in [lo, hi] (a valueless row holds VALUE_NONE)."""
+        n = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_base_value_rows(self._h, lo, hi, C.byref(n)))
+        return int(n.value)
+
+    def exact_search_values(self, queries_u8, k, query_ranges):
+        """exact_search() with a value interval per query: query_ranges [nq, 2] uint32, (lo, hi) inclusive, (0, VALUE_NONE)
+        = no restriction; None is exact_search() itself (ivfhnsw_gpu_exact_search_values)."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq, 2)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_values(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                     _ptr(qr), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_values_dev(self, nq, d_queries, row_stride, k, d_query_ranges, d_distances, d_labels):
+        """The same on device buffers (d_query_ranges: [nq, 2] uint32 in device memory, 8-byte aligned), asynchronous on
+        the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_values_dev(self._h, nq, _devptr(d_queries), row_stride, k,
+                                                         _devptr(d_query_ranges), _devptr(d_distances), _devptr(d_labels)))
+
+    def exact_range_search_values(self, queries_u8, radius, query_ranges):
+        """exact_range_search() with a value interval per query; lims in the caller's query order, results per query in
+        ascending label."""
+        a, nq, stride = self._exact_queries(queries_u8)
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq, 2)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_values(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                           _ptr(qr), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_values_dev(self, nq, d_queries, row_stride, d_query_ranges, radius, d_lims):
+        """The same on device buffers; returns the number of results, which stay in the handle's memory."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_values_dev(self._h, nq, _devptr(d_queries), row_stride,
+                                                               _devptr(d_query_ranges), C.c_float(radius), _devptr(d_lims),
+                                                               C.byref(total)))
         return int(total.value)
 
     # ---- measurement ---------------------------------------------------------------------------

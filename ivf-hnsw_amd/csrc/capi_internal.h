@@ -199,6 +199,7 @@ using namespace ivfhnsw_gpu_impl;
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
     X(bs_table) X(bs_plan) X(bs_qslots) /* base filter slots: the table the strips read (their words and rows: bslots[]); a call's strip plans (a _tags call's too), a host call's slot bytes (a _tags call's shorts) */ \
     X(bt_tags) X(bt_rows) X(bt_off) X(bt_work) /* base tags: a uint16 per store row, the tagged rows by (tag, row), their starts per tag; a call's plan workspace */ \
+    X(bv_vals) X(bv_rows) X(bv_work) /* base values: a uint32 per store row, all rows by (value, row); a call's plan workspace */ \
     X(w_xq) X(w_luts) X(w_segs) X(w_lpos) X(w_hdr) X(w_keys) X(w_cid) X(w_cd) X(w_qsd) X(w_totals) X(w_visited) X(w_status) X(w_stream) X(w_slen) X(w_tail) X(w_redo) X(w_hredo) X(w_heap) /* per-batch workspace */ \
     X(rg_dist) X(rg_lab) X(rg_slices) X(rg_part) X(rg_lims) /* range_search: the results it holds; slice counts, scan partials, lims staging */ \
     X(xr_dist) X(xr_lab) X(xr_slices) X(xr_part) X(xr_map) X(xr_lims) X(xr_tot) /* exact_range_search: the results it holds; slice counts, scan partials, tile map, lims staging, total */ \
@@ -292,6 +293,12 @@ struct ivfhnsw_gpu {
     // [kTagValues + 1]: tag t's rows are bt_rows [bt_off[t], bt_off[t + 1]).  All three rebuilt by every set_base_tags.
     uint64_t bt_tagged = 0;
     uint32_t bt_in_use = 0, bt_max_rows = 0; // tags that have rows; the most rows of one tag
+
+    // base values (capi_base_values.cpp), on the handle that holds the store, independent of the base filter,
+    // of its slots, of the base tags and of the index's row values: a view reads its parent's at the call.  bv_vals (null = no
+    // value array, every row valueless): a uint32 per store row; bv_rows: ALL row numbers ordered by (value, row), the
+    // bv_valued rows that hold a value first.  Both rebuilt by every set_base_values.
+    uint64_t bv_valued = 0;
 
     // one large batch as two uneven parts on two streams (ivfhnsw_gpu_search_dev): the second part runs on this view
     ivfhnsw_gpu *split_view = nullptr;
@@ -641,6 +648,12 @@ void base_tags_drop(ivfhnsw_gpu *h); // the handle holds no base tags afterwards
 // What an exact _tags call of h on holder b's store sweeps: the holder's row lists and the tags in use (the strip bound's
 // argument).  ERR_STATE with a base filter installed.
 int base_tags_call(const ivfhnsw_gpu *b, const char *who, TagRows *tr, size_t *tags_in_use);
+
+// ---- capi_base_values.cpp: base values
+void base_values_drop(ivfhnsw_gpu *h); // the handle holds no base values afterwards (buffers released)
+// What an exact _values call of h on holder b's store sweeps: the holder's values and row order.  ERR_STATE with a base
+// filter installed.
+int base_values_call(const ivfhnsw_gpu *b, const char *who, ValueRows *vr);
 
 // ---- capi_range.cpp
 void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)

@@ -18,6 +18,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
         base_filter_drop(h); // its rows are gone
         base_slots_drop(h);
         base_tags_drop(h);
+        base_values_drop(h);
         h->base_n = 0;
         h->base_d = 0;
         return IVFHNSW_OK;
@@ -36,6 +37,7 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
         base_filter_drop(h); // a new store: its row numbers mean other rows
         base_slots_drop(h);
         base_tags_drop(h);
+        base_values_drop(h);
         h->base_n = 0;
         h->base_d = 0;
         if ((rc = h->base_rows.ensure(n * d)))

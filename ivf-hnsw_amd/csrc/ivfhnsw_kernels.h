@@ -381,11 +381,11 @@ hipError_t launch_rerank_permute_rows(hipStream_t s, const uint8_t *src, size_t 
                                       const int32_t *row_src);
 hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t bound, int d, int k,
                                       int nsplit, unsigned long long *part, float *dists, int64_t *labels, const StripPlan &sp,
-                                      unsigned forms);
+                                      unsigned forms, const StripWin *win = nullptr);
 hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t bound, size_t q_off,
                                      size_t nx, int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total,
                                      uint32_t *map, int map_shift, float *dist, int64_t *labels, size_t out_cap,
-                                     const StripPlan &sp, unsigned forms);
+                                     const StripPlan &sp, unsigned forms, const StripWin *win = nullptr);
 // Base tags (kernels_exact_filter.hip): a uint16 per row of the store, and the exact sweeps with a tag per query.
 // launch_base_tags_apply: tags[rows[i]] = vals[i] for rows[i] < n; *conflict (zeroed here) != 0 when a row was given two
 // different tags.  launch_base_tags_index: the rows sorted stably by tag (*sorted = ids_a or ids_b [n]; keys [n], hist as
@@ -400,6 +400,28 @@ hipError_t launch_base_tags_index(hipStream_t s, const uint16_t *tags, uint64_t 
 size_t tag_plan_work_words(size_t m);
 hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
                                  uint32_t *work, StripPlan *sp);
+// Base values (kernels_exact_filter.hip): a uint32 per row of the store, and the exact sweeps with an
+// interval per query.  launch_base_values_apply: vals[rows[i]] = v[i] for rows[i] < n; *conflict (zeroed here) != 0 when a
+// row was given two different values.  launch_base_values_index: all rows sorted stably by value (*sorted = ids_a or ids_b
+// [n]; hist as launch_sort_by_key's).  launch_value_windows: win[q] = the window of query q's interval qr[2q], qr[2q + 1]
+// in vr's row order (sweep_value_window; no value array: every row holds 0xffffffff).  launch_value_strip_plan: the strip
+// plan of a chunk of m <= kExactChunk queries from their intervals d_ranges [2 m] into plan (sweep_value_plan_bytes(bound)
+// bytes, bound >= sweep_value_strip_bound(m)): the Dense strips of the queries whose window is the whole store first, then
+// the others in the order of their windows' starts, 32 to a strip whose entry spans their windows, *win the windows of its
+// rows (the last arguments of the strip sweeps); work: value_plan_work_words(m) words.
+// launch_range_by_label: the tot results dist / labels of an exact range search whose lims [nq + 1] are in device memory,
+// gathered into out_d / out_l in (query, label) order; work: range_by_label_work_words(tot) words.
+hipError_t launch_base_values_apply(hipStream_t s, const uint32_t *rows, const uint32_t *v, size_t cnt, uint64_t n, uint32_t *vals,
+                                    uint32_t *conflict);
+hipError_t launch_base_values_index(hipStream_t s, const uint32_t *vals, uint64_t n, uint32_t *ids_a, uint32_t *ids_b, uint32_t *hist,
+                                    uint32_t **sorted);
+hipError_t launch_value_windows(hipStream_t s, const uint32_t *d_ranges, size_t m, const ValueRows &vr, StripWin *win);
+size_t value_plan_work_words(size_t m);
+hipError_t launch_value_strip_plan(hipStream_t s, const uint32_t *d_ranges, size_t m, const ValueRows &vr, void *plan, size_t bound,
+                                   uint32_t *work, StripPlan *sp, const StripWin **win);
+size_t range_by_label_work_words(size_t tot);
+hipError_t launch_range_by_label(hipStream_t s, const uint64_t *d_lims, size_t nq, size_t tot, const float *dist, const int64_t *labels,
+                                 float *out_d, int64_t *out_l, uint32_t *work);
 // appends to the inverted lists (kernels_append.hip) and to the sub-groups of Grouping lists (3.12); the
 // arithmetic and the workspace sizes are update_math.h's.  count: cnt[list_idx[i]] += 1 and, with sub_idx, sizes2[list][sub]
 // += 1 (cnt null: check only); a list id >= nc or a sub-group id >= nsubc raises *status.  tables: own[c] = old length +

@@ -31,6 +31,11 @@
 //
 // With a base tag per query (ivfhnsw_gpu_exact_search_tags) the strips are tag-uniform and each carries its
 // own entry (ColsStrips<map, true>): Dense for the untagged queries, Indirect over the tag's row list for the others.
+//
+// With an interval of row values per query (ivfhnsw_gpu_exact_search_values) the Indirect strips sweep a
+// span of the holder's rows in (value, row) order and every strip row counts only its own window of it
+// (ColsStrips<ColsIndirect, true, true>, RowWindows): columns arrive in value order, so the k-search admits ties at the
+// k-th distance and the caller puts the range results in label order.
 #include "sweep_steps.h"
 
 #include <float.h>
@@ -70,13 +75,19 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
     I8Strip<NS> st;
     st.setup(Qp, r0, lane, nq, d);
     // what the common tile compares against: dist < thr  <=>  2 dot - |x'|^2 > |q'|^2 - thr = gate
+    // Under a windowed map columns do not arrive in label order, so a distance EQUAL to the k-th is admitted
+    // too (dist <= thr: the gate one lower) and the keys, (distance, label), decide; the first threshold is then a number
+    // above every distance (<= 256 * 255^2 < 2^24) from which thr + 1 and |q'|^2 - thr - 1 do not overflow.
+    constexpr int kTie = CM::kWindowed ? 1 : 0, kThr0 = CM::kWindowed ? 1 << 30 : INT_MAX;
     int gate[16];
+    RowWindows<CM> rw; // (a row without a window, the padding of a strip that is not full: a gate nothing passes)
+    rw.setup(cm, r0, lane);
 #pragma unroll
     for (int r = 0; r < 16; r++)
-        gate[r] = st.qn_r[r] - INT_MAX;
+        gate[r] = rw.gate_of(r, st.qn_r[r] - kThr0 - kTie);
     if (lane < 32) {
         cnt[lane] = 0;
-        thr_s[lane] = INT_MAX;
+        thr_s[lane] = kThr0;
     }
     __builtin_amdgcn_wave_barrier();
 
@@ -102,16 +113,19 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
             cc.fetch(st, X, cn, c_begin, c_end, d); // in flight behind this tile's MFMAs
         if (CM::kIndirect && cn + 32 < c_end)
             cc.ids(cn + 32); // (Indirect visits every tile: the one after the next begins at cn + 32)
+        if (!rw.tile(c0, kk))
+            continue; // wave-uniform: no row's window meets the tile
         i32x16 acc;
         int xn;
         st.product(acc, xn);
-        if (!__ballot(st.any_pass(acc, xn, gate) && col_ok))
+        if (!__ballot(rw.any_pass(st, acc, xn, gate) && col_ok))
             continue; // wave-uniform: the common tile once the thresholds have settled
         const uint32_t label = (uint32_t)cc.label(col);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int dist = st.dist(acc, xn, r);
-            const bool pass = col_ok && dist < st.qn_r[r] - gate[r];
+            const bool in = rw.row_counts(r, kk, col); // (every lane: a window is read from another lane)
+            const bool pass = col_ok && dist < st.qn_r[r] - gate[r] && in;
             const unsigned long long mask = __ballot(pass);
             if (mask)
                 row_append<CAP>(buf, cnt, mfma32_row(r, kk), pass, mask, dist, label, m, kk);
@@ -119,7 +133,7 @@ __global__ __launch_bounds__(64 * WAVES) void exact_mfma_kernel(const uint8_t *_
         rows_compact<CAP>(buf, cnt, thr_s, k, lane);
 #pragma unroll
         for (int r = 0; r < 16; r++)
-            gate[r] = st.qn_r[r] - thr_s[mfma32_row(r, kk)];
+            gate[r] = rw.gate_of(r, st.qn_r[r] - thr_s[mfma32_row(r, kk)] - kTie);
     }
 
     // out: [split][nq][k] keys
@@ -180,8 +194,19 @@ template <bool OWN, class F> hipError_t by_strip_maps_of(const StripPlan &sp, un
         e = f(ColsStrips<ColsIndirect, OWN>{sp});
     return e;
 }
-template <class F> hipError_t by_strip_maps(const StripPlan &sp, unsigned forms, F &&f)
+// win (base values): the plan's Indirect strips are windowed, each row with its own window
+template <class F> hipError_t by_strip_maps(const StripPlan &sp, unsigned forms, const StripWin *win, F &&f)
 {
+    if (win) {
+        if (!sp.strip_cols || (forms >> kSweepColsMasked & 1u))
+            return hipErrorInvalidValue;
+        hipError_t e = hipSuccess;
+        if (forms >> kSweepColsDense & 1u)
+            e = f(ColsStrips<ColsDense, true>{sp});
+        if (e == hipSuccess && (forms >> kSweepColsIndirect & 1u))
+            e = f(ColsStrips<ColsIndirect, true, true>{sp, win});
+        return e;
+    }
     if (sp.strip_cols)
         return (forms >> kSweepColsMasked & 1u) ? hipErrorInvalidValue : by_strip_maps_of<true>(sp, forms, f);
     return by_strip_maps_of<false>(sp, forms, f);
@@ -279,6 +304,11 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
     uint32_t *mw = map ? map + ((map_strip * nsplit + split) * (size_t)map_words) : nullptr;
     ColCursor<typename CM::Base> cc;
     cc.setup(bcm, c_begin, c_end, ntiles, lane);
+    RowWindows<CM> rw;
+    rw.setup(cm, r0, lane);
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        gate[r] = rw.gate_of(r, gate[r]);
     // the first tile at or after t that is to be visited (ntiles: none): one with a passing row (cc.next) whose map bit is
     // set.  The map is read only at tiles with a passing row: those the count form visited, whose words it wrote.
     auto next_tile = [&](uint32_t t) -> uint32_t {
@@ -319,12 +349,16 @@ __global__ __launch_bounds__(256) void exact_range_kernel(const uint8_t *__restr
         }
         i32x16 acc;
         int xn;
-        st.product(acc, xn);
-        const bool hit = __ballot(st.any_pass(acc, xn, gate) && col_ok) != 0; // wave-uniform
+        bool hit = rw.tile(c_begin + ((size_t)t << 5), kk); // wave-uniform: does any row's window meet the tile
+        if (hit) {
+            st.product(acc, xn);
+            hit = __ballot(rw.any_pass(st, acc, xn, gate) && col_ok) != 0; // wave-uniform
+        }
         if (hit) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const bool pass = col_ok && i8_gate_pass(acc[r], xn, gate[r]);
+                const bool in = rw.row_counts(r, kk, col); // (every lane: a window is read from another lane)
+                const bool pass = col_ok && i8_gate_pass(acc[r], xn, gate[r]) && in;
                 const unsigned long long mask = __ballot(pass);
                 const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
                 if (FILL) {
@@ -398,7 +432,7 @@ hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const
 hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t bound, size_t q_off,
                                      size_t nx, int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total,
                                      uint32_t *map, int map_shift, float *dist, int64_t *labels, size_t out_cap,
-                                     const StripPlan &sp, unsigned forms)
+                                     const StripPlan &sp, unsigned forms, const StripWin *win)
 {
     if (d < 16 || d > 256 || (d & 15) || thr < 0 || bound == 0 || bound > (0x7fffffffull >> 5) || nx >= 0xffffffffull || nsplit < 1 ||
         nsplit > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.hdr || !sp.strip_rows || (!sp.strip_cols && (!sp.table || !sp.strip_slot)))
@@ -407,7 +441,7 @@ hipError_t launch_exact_range_strips(hipStream_t s, bool fill, const uint8_t *Qp
     const dim3 grid((unsigned)((bound + 3) / 4), (unsigned)nsplit);
     long long *lab = reinterpret_cast<long long *>(labels);
     return by_row_steps(d, [&](auto ns) {
-        return by_strip_maps(sp, forms, [&](auto cm) {
+        return by_strip_maps(sp, forms, win, [&](auto cm) {
             using CM = decltype(cm);
             const auto kern = fill ? exact_range_kernel<decltype(ns)::value, true, CM> : exact_range_kernel<decltype(ns)::value, false, CM>;
             hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, Qp, X, (int)(bound * 32), (size_t)0, d, thr, (size_t)0, q_off, slices, total,
@@ -448,7 +482,7 @@ hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *
 // [nsplit][bound * 32][k]; results in the caller's order, FLT_MAX / -1 for a query without a strip
 hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t bound, int d, int k,
                                       int nsplit, unsigned long long *part, float *dists, int64_t *labels, const StripPlan &sp,
-                                      unsigned forms)
+                                      unsigned forms, const StripWin *win)
 {
     if (nq == 0)
         return hipSuccess;
@@ -462,7 +496,7 @@ hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const ui
         return e;
     const hipError_t e = by_row_steps(d, [&](auto ns) {
         constexpr int NS = decltype(ns)::value;
-        return by_strip_maps(sp, forms, [&](auto cm) {
+        return by_strip_maps(sp, forms, win, [&](auto cm) {
             return k <= 16   ? launch_exact_t<NS, 48, 4>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm)
                    : k <= 32 ? launch_exact_t<NS, 64, 4>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm)
                              : launch_exact_t<NS, 136, 2>(s, Qp, X, rows, 0, d, k, nsplit, 0, part, cm);

@@ -8,6 +8,10 @@
 // Then base tags: the holder's tag per row with the row lists per tag behind it (a stable sort of the row
 // numbers by tag, launch_sort_by_key), and the strip plan of a call with a tag per query -- one bucket per tag among the
 // chunk's queries, found with the same sort.
+// Then base values: the holder's value per row with ALL row numbers ordered by (value, row) behind it (the
+// same sort, 32 key bits), the window of an interval in that order, the strip plan of a call with an interval per query --
+// whole-store windows in Dense strips, the others sorted by their start into strips that span their windows -- and the
+// reorder of a range call's results to (query, label).
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 
@@ -259,7 +263,247 @@ __global__ __launch_bounds__(256) void tag_scatter_kernel(const uint32_t *__rest
     }
 }
 
+// ---- base values: the holder's arrays -----------------------------------------------------------------
+// vals[rows[i]] = v[i] for the rows inside the store, and the check behind it, as the tags' pair above
+__global__ __launch_bounds__(256) void base_values_scatter_kernel(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ v,
+                                                                  size_t cnt, uint64_t n, uint32_t *__restrict__ vals)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += stride)
+        if (rows[i] < n)
+            vals[rows[i]] = v[i];
+}
+
+__global__ __launch_bounds__(256) void base_values_verify_kernel(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ v,
+                                                                 size_t cnt, uint64_t n, const uint32_t *__restrict__ vals,
+                                                                 uint32_t *__restrict__ conflict)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += stride)
+        bad |= rows[i] < n && vals[rows[i]] != v[i];
+    if (bad)
+        atomicOr(conflict, 1u);
+}
+
+// the window of the interval (lo, hi) in the holder's row order; without a value array every row holds 0xffffffff
+__device__ __forceinline__ StripWin value_window(const ValueRows &vr, uint32_t lo, uint32_t hi)
+{
+    StripWin w;
+    sweep_value_window([&](uint32_t i) { return vr.vals ? vr.vals[vr.rows[i]] : 0xffffffffu; }, vr.n, lo, hi, &w.a, &w.b);
+    return w;
+}
+
+__global__ __launch_bounds__(256) void value_windows_kernel(const uint32_t *__restrict__ qr, size_t m, ValueRows vr, StripWin *__restrict__ win)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < m)
+        win[q] = value_window(vr, qr[2 * q], qr[2 * q + 1]);
+}
+
+// ---- base values: the strip plan of one chunk of an exact _values call --------------------------------------------------
+// wabs[q] = the window of query q; keys[q] = what the chunk's queries are sorted by: 0 for a window that is the whole store
+// -- its strips, the Dense ones, come first --, the window's start + 1 (<= n < 2^32 - 1) for any other that holds a row,
+// 0xffffffff for an empty one, which gets no strip.  cnt (zeroed before): [0] the whole-store queries, [1] the windowed ones.
+__global__ __launch_bounds__(256) void value_query_keys_kernel(const uint32_t *__restrict__ qr, size_t m, ValueRows vr,
+                                                               StripWin *__restrict__ wabs, uint32_t *__restrict__ keys,
+                                                               uint32_t *__restrict__ cnt)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= m)
+        return;
+    const StripWin w = value_window(vr, qr[2 * q], qr[2 * q + 1]);
+    wabs[q] = w;
+    const bool none = w.a >= w.b, full = !none && w.a == 0 && w.b == vr.n;
+    keys[q] = none ? 0xffffffffu : full ? 0u : w.a + 1u;
+    if (!none)
+        atomicAdd(&cnt[full ? 0 : 1], 1u);
+}
+
+// Query sorted[i], the i-th of the chunk's queries in the stable order by key, takes the next row of the Dense strips
+// (i < cnt[0]) or of the windowed ones (strip_rows filled with -1, strip_win with empty windows before).  A windowed strip
+// spans [A, B): A the start of its first query's window, the smallest of the strip, B the furthest end among its rows,
+// which the thread of the strip's row 0 finds; a row's own window is kept relative to A.  The first thread writes the layout.
+__global__ __launch_bounds__(256) void value_scatter_kernel(const uint32_t *__restrict__ sorted, const StripWin *__restrict__ wabs, size_t m,
+                                                            const uint32_t *__restrict__ cnt, ValueRows vr, uint32_t bound,
+                                                            StripHdr *__restrict__ hdr, int32_t *__restrict__ strip_rows,
+                                                            StripCols *__restrict__ strip_cols, StripWin *__restrict__ strip_win)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t nfull = cnt[0], nwin = cnt[1];
+    const uint32_t dense = min((nfull + 31) / 32, bound), all = min(dense + (nwin + 31) / 32, bound); // (never above: sweep_value_strip_bound)
+    if (i == 0) {
+        hdr->lay.range[kSweepColsDense][0] = 0;
+        hdr->lay.range[kSweepColsDense][1] = dense;
+        hdr->lay.range[kSweepColsMasked][0] = hdr->lay.range[kSweepColsMasked][1] = dense;
+        hdr->lay.range[kSweepColsIndirect][0] = dense;
+        hdr->lay.range[kSweepColsIndirect][1] = all;
+        hdr->lay.nstrips = all;
+    }
+    if (i >= m || i >= (size_t)nfull + nwin)
+        return;
+    const uint32_t q = sorted[i];
+    if (i < nfull) {
+        const uint32_t strip = (uint32_t)i >> 5;
+        if (strip >= dense)
+            return;
+        strip_rows[(size_t)strip * 32 + (i & 31)] = (int32_t)q;
+        if ((i & 31) == 0)
+            strip_cols[strip] = {nullptr, vr.n, (uint32_t)kSweepColsDense};
+        return;
+    }
+    const uint32_t j = (uint32_t)i - nfull, strip = dense + (j >> 5);
+    if (strip >= all)
+        return;
+    const uint32_t j0 = nfull + (j & ~31u), j1 = min(j0 + 32u, nfull + nwin);
+    const uint32_t A = wabs[sorted[j0]].a;
+    const StripWin w = wabs[q];
+    strip_rows[(size_t)strip * 32 + (j & 31)] = (int32_t)q;
+    strip_win[(size_t)strip * 32 + (j & 31)] = {w.a - A, w.b - A};
+    if ((j & 31) == 0) {
+        uint32_t B = w.b;
+        for (uint32_t t = j0 + 1; t < j1; t++)
+            B = max(B, wabs[sorted[t]].b);
+        strip_cols[strip] = {vr.rows + A, B - A, (uint32_t)kSweepColsIndirect};
+    }
+}
+
+// ---- base values: the results of a range call in label order -------------------------------------------------------------
+// keys of result i: the low word of its label (row numbers are below 2^32), and the query whose results [lims[q],
+// lims[q + 1]) hold place i
+__global__ __launch_bounds__(256) void range_label_keys_kernel(const long long *__restrict__ labels, const uint64_t *__restrict__ lims,
+                                                               uint32_t nq, size_t tot, uint32_t *__restrict__ klab, uint32_t *__restrict__ kq)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tot)
+        return;
+    klab[i] = (uint32_t)labels[i];
+    uint32_t lo = 0, hi = nq; // the last q with lims[q] <= i
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (lims[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    kq[i] = lo;
+}
+
+__global__ __launch_bounds__(256) void range_gather_kernel(const uint32_t *__restrict__ order, size_t tot, const float *__restrict__ dist,
+                                                           const long long *__restrict__ labels, float *__restrict__ out_d,
+                                                           long long *__restrict__ out_l)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tot)
+        return;
+    const uint32_t src = order[i];
+    out_d[i] = dist[src];
+    out_l[i] = labels[src];
+}
+
 } // namespace
+
+hipError_t launch_base_values_apply(hipStream_t s, const uint32_t *rows, const uint32_t *v, size_t cnt, uint64_t n, uint32_t *vals,
+                                    uint32_t *conflict)
+{
+    if (hipError_t e = hipMemsetAsync(conflict, 0, sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    if (cnt == 0)
+        return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)1 << 16);
+    hipLaunchKernelGGL(base_values_scatter_kernel, dim3(grid), dim3(256), 0, s, rows, v, cnt, n, vals);
+    hipLaunchKernelGGL(base_values_verify_kernel, dim3(grid), dim3(256), 0, s, rows, v, cnt, n, vals, conflict);
+    return hipGetLastError();
+}
+
+// 32 key bits from the identity: equal values keep ascending row
+hipError_t launch_base_values_index(hipStream_t s, const uint32_t *vals, uint64_t n, uint32_t *ids_a, uint32_t *ids_b, uint32_t *hist,
+                                    uint32_t **sorted)
+{
+    if (n == 0 || n >= 0xffffffffull)
+        return hipErrorInvalidValue;
+    return launch_sort_by_key(s, vals, n, 32, ids_a, ids_b, hist, sorted);
+}
+
+hipError_t launch_value_windows(hipStream_t s, const uint32_t *d_ranges, size_t m, const ValueRows &vr, StripWin *win)
+{
+    if (m == 0)
+        return hipSuccess;
+    if (!d_ranges || !win || (vr.vals && !vr.rows))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(value_windows_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_ranges, m, vr, win);
+    return hipGetLastError();
+}
+
+// keys, the sort's two permutations and its histograms; the windows; the two counts (padded to four words)
+size_t value_plan_work_words(size_t m) { return 3 * m + 256 * ((m + kKmeansTile - 1) / kKmeansTile) + 2 * m + 4; }
+
+hipError_t launch_value_strip_plan(hipStream_t s, const uint32_t *d_ranges, size_t m, const ValueRows &vr, void *plan, size_t bound,
+                                   uint32_t *work, StripPlan *sp, const StripWin **win)
+{
+    if (m == 0 || m > kExactChunk || bound < sweep_value_strip_bound(m) || bound > 0x7fffffffull / 32 || !d_ranges || !plan || !work ||
+        (vr.vals && !vr.rows))
+        return hipErrorInvalidValue;
+    StripHdr *hdr = reinterpret_cast<StripHdr *>(plan);
+    int32_t *rows = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(plan) + sweep_strip_hdr_bytes());
+    StripCols *cols = reinterpret_cast<StripCols *>(rows + bound * 32);
+    StripWin *swin = reinterpret_cast<StripWin *>(cols + bound);
+    uint32_t *keys = work, *ids_a = keys + m, *ids_b = ids_a + m, *hist = ids_b + m;
+    uint32_t *cnt = hist + 256 * ((m + kKmeansTile - 1) / kKmeansTile);
+    StripWin *wabs = reinterpret_cast<StripWin *>(cnt + 4);
+    if (hipError_t e = hipMemsetAsync(hdr, 0, sweep_strip_hdr_bytes(), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(rows, 0xff, bound * 32 * sizeof(int32_t), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(cols, 0, bound * sizeof(StripCols) + bound * 32 * sizeof(StripWin), s); e != hipSuccess)
+        return e; // (Dense over no column; every window empty)
+    if (hipError_t e = hipMemsetAsync(cnt, 0, 4 * sizeof(uint32_t), s); e != hipSuccess)
+        return e;
+    const dim3 grid((unsigned)((m + 255) / 256));
+    hipLaunchKernelGGL(value_query_keys_kernel, grid, dim3(256), 0, s, d_ranges, m, vr, wabs, keys, cnt);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    uint32_t *sorted = nullptr;
+    if (hipError_t e = launch_sort_by_key(s, keys, m, 32, ids_a, ids_b, hist, &sorted); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(value_scatter_kernel, grid, dim3(256), 0, s, sorted, wabs, m, cnt, vr, (uint32_t)bound, hdr, rows, cols, swin);
+    sp->table = nullptr;
+    sp->hdr = hdr;
+    sp->strip_slot = nullptr;
+    sp->strip_rows = rows;
+    sp->strip_cols = cols;
+    *win = swin;
+    return hipGetLastError();
+}
+
+// the label keys and the query keys, the sort's two permutations and its histograms
+size_t range_by_label_work_words(size_t tot) { return 4 * tot + 256 * ((tot + kKmeansTile - 1) / kKmeansTile); }
+
+hipError_t launch_range_by_label(hipStream_t s, const uint64_t *d_lims, size_t nq, size_t tot, const float *dist, const int64_t *labels,
+                                 float *out_d, int64_t *out_l, uint32_t *work)
+{
+    if (tot == 0)
+        return hipSuccess;
+    if (nq == 0 || nq > 0x7fffffffull || tot >= 0xffffffffull || !d_lims || !dist || !labels || !out_d || !out_l || !work)
+        return hipErrorInvalidValue;
+    uint32_t *klab = work, *kq = klab + tot, *ids_a = kq + tot, *ids_b = ids_a + tot, *hist = ids_b + tot;
+    const dim3 grid((unsigned)((tot + 255) / 256));
+    const long long *lab = reinterpret_cast<const long long *>(labels);
+    hipLaunchKernelGGL(range_label_keys_kernel, grid, dim3(256), 0, s, lab, d_lims, (uint32_t)nq, tot, klab, kq);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    // stable by the label, then from that order stable by the query: (query, label)
+    uint32_t *order = nullptr;
+    if (hipError_t e = launch_sort_by_key(s, klab, tot, 32, ids_a, ids_b, hist, &order); e != hipSuccess)
+        return e;
+    int qbits = 1;
+    while (qbits < 32 && ((size_t)1 << qbits) < nq)
+        qbits++;
+    if (hipError_t e = launch_sort_by_key_from(s, kq, tot, qbits, order, ids_a, ids_b, hist, &order); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(range_gather_kernel, grid, dim3(256), 0, s, order, tot, dist, lab, out_d, reinterpret_cast<long long *>(out_l));
+    return hipGetLastError();
+}
 
 hipError_t launch_base_tags_apply(hipStream_t s, const uint32_t *rows, const uint16_t *vals, size_t cnt, uint64_t n, uint16_t *tags,
                                   uint32_t *conflict)

@@ -194,6 +194,69 @@ struct TagRows {
 // bytes of a chunk's tag plan of `bound` strips: header, rows, one entry per strip
 inline size_t sweep_tag_plan_bytes(size_t bound) { return sweep_strip_hdr_bytes() + bound * 32 * sizeof(int32_t) + bound * sizeof(StripCols); }
 
+// ---- base values: the exact sweeps with a uint32 value per store row and an interval per query
+// The holder keeps ALL row numbers ordered by (value, row), a valueless row last at 0xffffffff, so the rows whose value
+// lies in [lo, hi] are one window [*a, *b) of positions of that order: *a the first position whose value is >= lo, *b the
+// first whose value is > hi -- n when hi is the largest value there is.  lo > hi is empty (0, 0).  value_at(i) = the value
+// at position i of the n; two binary searches.  The rule is value_math.h's: lo <= v <= hi, unsigned, inclusive.
+template <class V> SWEEP_HD inline void sweep_value_window(V value_at, uint32_t n, uint32_t lo, uint32_t hi, uint32_t *a, uint32_t *b)
+{
+    *a = *b = 0;
+    if (lo > hi)
+        return;
+    uint32_t l = 0, h = n;
+    while (l < h) {
+        const uint32_t mid = l + ((h - l) >> 1);
+        if (value_at(mid) < lo)
+            l = mid + 1;
+        else
+            h = mid;
+    }
+    *a = l;
+    h = n; // (the second search begins at *a: no position below it holds a value above hi >= lo)
+    if (hi != 0xffffffffu)
+        while (l < h) {
+            const uint32_t mid = l + ((h - l) >> 1);
+            if (value_at(mid) <= hi)
+                l = mid + 1;
+            else
+                h = mid;
+        }
+    *b = h;
+}
+
+// Strips of 32 queries of a chunk of m: the queries whose window is the whole store fill ceil(f / 32) Dense strips, those
+// with any other non-empty window, in the order of their windows' starts, ceil(w / 32) windowed ones; f + w <= m, so
+// ceil(f / 32) + ceil(w / 32) <= (f + w) / 32 + 2 <= m / 32 + 2.
+SWEEP_HD inline size_t sweep_value_strip_bound(size_t m) { return m / 32 + 2; }
+
+// Queries per pass of a _values k-search: as the plain call's rule, over the padded rows of the strip bound --
+// nsplit * bound(chunk) * 32 * k * 8 bytes within kExactPartBytes, in multiples of 128, never below 128
+// (64 * 6 * 32 * 100 * 8 = 9.8 MB).
+inline size_t sweep_value_chunk(int nsplit, size_t k)
+{
+    const size_t per_strip = (size_t)nsplit * 32 * k * sizeof(uint64_t);
+    size_t chunk = kExactChunk;
+    while (chunk > 128 && per_strip * sweep_value_strip_bound(chunk) > kExactPartBytes)
+        chunk -= 128;
+    return chunk;
+}
+
+// What the holder keeps for the plan: vals = the value of every row, rows = all row numbers ordered by (value, row),
+// n = the rows of the store.  Null: no value array, every row is valueless.
+struct ValueRows {
+    const uint32_t *vals = nullptr;
+    const uint32_t *rows = nullptr;
+    uint32_t n = 0;
+};
+// a strip row's own window, relative to its strip's first column: the row counts columns [a, b) only; padding (0, 0)
+struct StripWin {
+    uint32_t a, b;
+};
+
+// bytes of a chunk's value plan of `bound` strips: a tag plan's, then a window per strip row
+inline size_t sweep_value_plan_bytes(size_t bound) { return sweep_tag_plan_bytes(bound) + bound * 32 * sizeof(StripWin); }
+
 // f(int_c<NS>()) for NS = ceil(d / 32) = 1 .. 8, the steps of 32 bytes a row of the uint8 store is read in (d <= 256)
 template <class F> auto by_row_steps(int d, F &&f)
 {

@@ -1,7 +1,7 @@
 // The steps the brute-force MFMA sweeps share, one copy each: the C/D row map, the selection of a row's k
 // smallest keys through its LDS buffer (knn_mfma_kernel, exact_mfma_kernel), the int8 strip that reads the uint8 store
 // (exact_mfma_kernel, exact_range_kernel), the column maps those two sweep under when the store has a base filter
-// (ColsDense / ColsMasked / ColsIndirect, ColCursor; per 32-row strip under base filter slots and base tags: ColsStrips, strip_open) and the merge of the splits' partial tables.  Control flow -- which tile comes
+// (ColsDense / ColsMasked / ColsIndirect, ColCursor; per 32-row strip under base filter slots, base tags and base values: ColsStrips, strip_open, RowWindows) and the merge of the splits' partial tables.  Control flow -- which tile comes
 // next, what a tile without a candidate costs, what is done with a distance that passes -- stays in the kernels.  Host
 // arithmetic (columns per split, split count): sweep_plan_math.h.
 #pragma once
@@ -224,18 +224,18 @@ template <int NS> struct I8Strip {
 // Under a strip plan (base filter slots) the three take their words or rows and their nx per 32-row strip
 // from the strip's table entry instead of the kernel's arguments: ColsStrips<map>, below.
 struct ColsDense {
-    static constexpr bool kMasked = false, kIndirect = false, kStrips = false;
+    static constexpr bool kMasked = false, kIndirect = false, kStrips = false, kWindowed = false;
     using Base = ColsDense;
     __device__ __forceinline__ void take(const uint32_t *) {}
 };
 struct ColsMasked {
-    static constexpr bool kMasked = true, kIndirect = false, kStrips = false;
+    static constexpr bool kMasked = true, kIndirect = false, kStrips = false, kWindowed = false;
     using Base = ColsMasked;
     const uint32_t *words;
     __device__ __forceinline__ void take(const uint32_t *data) { words = data; }
 };
 struct ColsIndirect {
-    static constexpr bool kMasked = false, kIndirect = true, kStrips = false;
+    static constexpr bool kMasked = false, kIndirect = true, kStrips = false, kWindowed = false;
     using Base = ColsIndirect;
     const uint32_t *rows;
     __device__ __forceinline__ void take(const uint32_t *data) { rows = data; }
@@ -247,10 +247,21 @@ struct ColsIndirect {
 // are rows [32 strip, + 32) of the gathered queries; strip_rows says which of the call's queries each is.
 // OWN: the strip's entry is its own, strip_cols[strip] (base tags, DESIGN.md 3.22: one bucket per tag among the chunk's
 // queries, far more than a table of slots holds); else it is the slot table's, table[strip_slot[strip]].
-template <class B, bool OWN = false> struct ColsStrips {
-    static constexpr bool kMasked = B::kMasked, kIndirect = B::kIndirect, kStrips = true, kOwnEntries = OWN;
+// WIN (base values; Indirect, own entries): the strip's columns are a span of the holder's rows in (value,
+// row) order that covers the windows of all its rows, and every strip row counts only the columns of ITS OWN window
+// win[32 strip + row], relative to the span (RowWindows, below).  Columns then arrive in (value, row) order, not in label
+// order: the k-search admits ties at the k-th distance (kTie) and the range results are put in label order afterwards.
+template <class B, bool OWN = false, bool WIN = false> struct ColsStrips {
+    static constexpr bool kMasked = B::kMasked, kIndirect = B::kIndirect, kStrips = true, kOwnEntries = OWN, kWindowed = false;
     using Base = B;
     StripPlan sp;
+};
+template <class B> struct ColsStrips<B, true, true> {
+    static_assert(B::kIndirect, "a windowed strip sweeps a span of the holder's row order");
+    static constexpr bool kMasked = false, kIndirect = true, kStrips = true, kOwnEntries = true, kWindowed = true;
+    using Base = B;
+    StripPlan sp;
+    const StripWin *win;
 };
 
 // What the wave whose first row is r0 sweeps in split `split` of nsplit: the map, the first row and the columns
@@ -295,6 +306,81 @@ template <class CM> __device__ __forceinline__ bool strip_row_query(const CM &cm
         return r0 + row < nq;
     }
 }
+
+// The windows of a wave's 32 strip rows under a windowed map, two registers a lane: lanes m and m + 32 hold row m's window
+// [wa, wb) in the strip's columns.  Per tile of columns [c0, c0 + 32) one ballot gives `live`, bit m = row m's window
+// meets the tile -- wave-uniform, so a tile no window meets (the gap between two windows of a strip) is dropped before it
+// is multiplied, and the tile's cheap test counts a row only where its bit is set; the exact test, column by column, is
+// made behind the cheap test, where a row's window is read from its lane.  A row whose window is empty -- the padding rows
+// of a strip that is not full -- never counts: gate_of() gives it a gate nothing passes, for good.  A tile inside the
+// window of every row that has one (all == true) then takes the unwindowed cheap test.  Without kWindowed nothing here is
+// live.
+template <class CM> struct RowWindows {
+    uint32_t wa = 0, wb = 0; // the window of row lane & 31
+    uint32_t lv = 0;         // the live bits of the rows this lane holds: bit (r & 3) + 8 (r >> 2) = accumulator register r
+    uint32_t dead = 0;       // ... and, in the same places, the rows whose window is empty
+    uint32_t empty = 0;      // bit m = row m's window is empty (wave-uniform)
+    bool all = true;
+
+    __device__ __forceinline__ void setup(const CM &cm, int r0, int lane)
+    {
+        if constexpr (CM::kWindowed) {
+            const StripWin w = cm.win[r0 + (lane & 31)];
+            wa = w.a;
+            wb = w.b;
+            empty = (uint32_t)__ballot(wa >= wb);
+            dead = empty >> (4 * (lane >> 5));
+        }
+    }
+    // the gate of accumulator register r's row: g, or for a row without a window one that no distance passes
+    __device__ __forceinline__ int gate_of(int r, int g) const
+    {
+        if constexpr (CM::kWindowed)
+            return (dead >> ((r & 3) + 8 * (r >> 2))) & 1u ? 0x7fffffff : g;
+        else
+            return g;
+    }
+    // false: no row of the wave counts any column of the tile
+    __device__ __forceinline__ bool tile(size_t c0, int kk)
+    {
+        if constexpr (CM::kWindowed) {
+            const uint32_t t0 = (uint32_t)c0;
+            const bool meets = wa < t0 + 32u && wb > t0; // (an empty window meets nothing; columns are below 2^32 - 32)
+            const uint32_t live = (uint32_t)__ballot(meets);
+            all = ((uint32_t)__ballot(wa <= t0 && wb >= t0 + 32u) | empty) == 0xffffffffu;
+            lv = live >> (4 * kk);
+            return live != 0u;
+        } else {
+            return true;
+        }
+    }
+    // the cheap test of a tile: does any of the lane's 16 distances pass its row's gate, in a row whose window meets the tile
+    template <int NS> __device__ __forceinline__ bool any_pass(const I8Strip<NS> &st, const i32x16 &acc, int xn, const int (&gate)[16]) const
+    {
+        if constexpr (CM::kWindowed) {
+            if (all)
+                return st.any_pass(acc, xn, gate);
+            uint32_t any = 0;
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                any |= i8_gate_pass(acc[r], xn, gate[r]) ? 1u << ((r & 3) + 8 * (r >> 2)) : 0u;
+            return (any & lv) != 0u;
+        } else {
+            return st.any_pass(acc, xn, gate);
+        }
+    }
+    // the exact test: does accumulator register r's row count column col
+    __device__ __forceinline__ bool row_counts(int r, int kk, size_t col) const
+    {
+        if constexpr (CM::kWindowed) {
+            const int row = mfma32_row(r, kk);
+            const uint32_t a = __shfl(wa, row), b = __shfl(wb, row);
+            return (uint32_t)col >= a && (uint32_t)col < b;
+        } else {
+            return true;
+        }
+    }
+};
 
 // A wave's place in its split's columns [c_begin, c_end) under a column map.  Everything below is wave-uniform except
 // the row numbers; the members a map does not use are never live.

@@ -28,11 +28,17 @@
      present set_base_filter_dev then exact_search_dev on that tag's queries -- with and without the installs, (c) at 32
      tags one exact_search_slots_dev call over the same partition; k = 1 and k = 100; the range form at the median k = 10
      distance; and the time of set_base_tags_dev over every row.
+  7. With --values, on both stores, base values (ivfhnsw_gpu_exact_search_values_dev): every row holds a
+     distinct value, and three batches -- 897 intervals of 1/8 of the rows, 1 000 intervals of about 100 rows, the latter
+     with 1/33 of the queries on (0, 0xffffffff) -- are timed alternating in one run: (a) one _values call, (b) the loop it
+     replaces, per distinct interval set_base_filter_dev(the interval's rows) + the plain call on its queries, with and
+     without the installs; k = 1, k = 100 and the range form at the median k = 10 distance with the reorder's share of
+     it; and the time of set_base_values_dev over every row.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
-                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags]
+                                   [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags] [--values]
                                    [--dense-nq 512]
                                    [--out result.json]"""
 import argparse
@@ -108,6 +114,7 @@ def main():
     ap.add_argument("--filter", action="store_true", help="add the base-filter legs (DESIGN.md 3.18)")
     ap.add_argument("--filter-slots", action="store_true", help="add the base-filter-slot legs (DESIGN.md 3.20)")
     ap.add_argument("--tags", action="store_true", help="add the base-tag legs (DESIGN.md 3.22)")
+    ap.add_argument("--values", action="store_true", help="add the base-value legs (DESIGN.md 3.25)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -398,6 +405,109 @@ def main():
             g.clear_base_filter_slot()
         g.clear_base_tags()
 
+    def values_legs(n, name, d10):
+        """One _values call against the per-interval loop of single-filter calls it replaces, alternating, on three
+        workloads over a store whose rows hold a permutation of 0..n-1: 897 intervals of 1/8 of the rows, 1 000 intervals of
+        about 100 rows, and the latter with 1/33 of the queries on (0, 0xffffffff)."""
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(8100)
+        values = torch.randperm(n, device=dev, generator=gen).to(torch.int32)  # the value of row i
+        row_of = torch.argsort(values.to(torch.int64)).to(torch.int32)          # the row that holds value v
+        all_rows = torch.arange(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        t_set, ts_set = timed(torch, dev, lambda: g.set_base_values_dev(n, all_rows, values), args.warmup, args.reps,
+                              "%s set_base_values" % name)
+        assert g.base_values_info() == (n, n)
+        r = {"what": "set_base_values_dev", "rows": n, "seconds": round(t_set, 5), "reps": [round(x, 5) for x in ts_set],
+             "memory_GB": round(g.memory_bytes() / 1e9, 3)}
+        result["rows"].append(r)
+        print(json.dumps(r), flush=True)
+        del all_rows
+        radius = float(d10.median())
+        full = (0, 0xffffffff)
+
+        def spread(count, width):
+            return [(a, a + width - 1) for a in ((i * (n - width)) // max(1, count - 1) for i in range(count))]
+        workloads = [("897 x 1/8", spread(897, n // 8), 0), ("1000 x ~100 rows", spread(1000, min(n, 100)), 0),
+                     ("1000 x ~100 rows, 1/33 full", spread(1000, min(n, 100)), 33)]
+        for wname, ivs, full_share in workloads:
+            pick = torch.arange(nq, device=dev) % len(ivs)
+            pick = pick[torch.randperm(nq, device=dev, generator=gen)]
+            is_full = (torch.arange(nq, device=dev) % full_share == full_share - 1) if full_share else torch.zeros(nq, dtype=torch.bool, device=dev)
+            iv_t = torch.tensor(ivs, dtype=torch.int64, device=dev)
+            qr64 = iv_t[pick]
+            qr64[is_full] = torch.tensor(full, dtype=torch.int64, device=dev)
+            qr = torch.where(qr64 >= 2 ** 31, qr64 - 2 ** 32, qr64).to(torch.int32).contiguous()  # the bit pattern of the uint32
+            # per distinct interval present: its ascending row list and its queries
+            sub = []
+            for i in sorted(set(pick[~is_full].cpu().tolist())):
+                lo, hi = ivs[i]
+                rows_i = torch.sort(row_of[lo:hi + 1]).values.contiguous()
+                sub.append((rows_i, q[((pick == i) & ~is_full).nonzero().flatten()].contiguous()))
+            if full_share:
+                sub.append((None, q[is_full.nonzero().flatten()].contiguous()))
+            torch.cuda.synchronize(dev)
+
+            def loop(k, od, ol):
+                """the parent commit's way, per interval present: (seconds with the installs, seconds of the searches alone)"""
+                t_all = t_search = 0.0
+                for rows_i, qsub in sub:
+                    t0 = time.perf_counter()
+                    if rows_i is None:
+                        g.clear_base_filter()
+                    else:
+                        g.set_base_filter_dev(rows_i.numel(), rows_i)
+                    torch.cuda.synchronize(dev)
+                    t1 = time.perf_counter()
+                    if k:
+                        g.exact_search_dev(qsub.shape[0], qsub, d, k, od[:qsub.shape[0]], ol[:qsub.shape[0]])
+                    else:
+                        g.exact_range_search_dev(qsub.shape[0], qsub, d, radius, lims)
+                    torch.cuda.synchronize(dev)
+                    t2 = time.perf_counter()
+                    t_all += t2 - t0
+                    t_search += t2 - t1
+                g.clear_base_filter()
+                return t_all, t_search
+
+            for k in (1, 100, 0):  # 0: the range form
+                od = torch.empty((nq, max(k, 1)), dtype=torch.float32, device=dev)
+                ol = torch.empty((nq, max(k, 1)), dtype=torch.int64, device=dev)
+                ta, tb, tbi, reorder, results = [], [], [], [], 0
+                for rep in range(args.warmup + args.reps):
+                    if not k:
+                        g.set_profiling(True)
+                        g.reset_stage_ms()
+                    t0 = time.perf_counter()
+                    if k:
+                        g.exact_search_values_dev(nq, q, d, k, qr, od, ol)
+                    else:
+                        results = g.exact_range_search_values_dev(nq, q, d, qr, radius, lims)
+                    torch.cuda.synchronize(dev)
+                    a = time.perf_counter() - t0
+                    if not k:
+                        reorder.append(g.stage_ms()["plan"][0] / 1e3)  # the reorder is accounted as the plan stage of this call
+                        g.set_profiling(False)
+                    full_s, only = loop(k, od, ol)
+                    log("[exact_bench] %s values '%s' k=%d rep %d: values call %.4f s, loop %.4f s (searches alone %.4f s)"
+                        % (name, wname, k, rep, a, full_s, only))
+                    if rep >= args.warmup:
+                        ta.append(a), tbi.append(full_s), tb.append(only)
+                ma, mbi, mb = (statistics.median(x) for x in (ta, tbi, tb))
+                r = {"what": "exact_search_values_dev" if k else "exact_range_search_values_dev", "rows": n, "d": d, "nq": nq,
+                     "k": k if k else None, "radius_value": None if k else radius, "workload": wname, "intervals_present": len(sub),
+                     "values_call_s": round(ma, 5), "loop_with_installs_s": round(mbi, 5), "loop_searches_only_s": round(mb, 5),
+                     "loop_with_installs_over_values": round(mbi / ma, 3), "loop_searches_only_over_values": round(mb / ma, 3),
+                     "reps_values": [round(x, 5) for x in ta]}
+                if not k:
+                    r["results"] = results
+                    r["reorder_s"] = round(statistics.median(reorder[args.warmup:]), 5)
+                    r["reorder_share"] = round(r["reorder_s"] / ma, 4)
+                result["rows"].append(r)
+                print(json.dumps(r), flush=True)
+            del sub
+        g.clear_base_values()
+
     def yardstick_and_range(n, dense_radius=None, fractions=(1, 2, 8, 32, 1024)):
         name = "%d rows" % n
         r1, _, _ = exact(n, 1, name)
@@ -409,6 +519,8 @@ def main():
         if args.tags:
             for ntags in (32, 1024):
                 tags_legs(n, name, od100[:, 9], ntags)
+        if args.values:
+            values_legs(n, name, od100[:, 9])
         if not args.no_range:
             range_legs(n, name, r1["seconds"], od100[:, 9], od100[:, 99], dense_radius)
 

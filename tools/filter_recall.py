@@ -18,7 +18,10 @@ queries are dealt over ALL 1 024 tags and NONE, and ONE search_tags call is scor
 With --values: every row gets a distinct value (a seeded permutation of 0..n-1: a timestamp), and the
 queries are dealt over a handful of sample intervals -- four of pass fraction 1/8 that overlap one another, five of about
 1/2000, and (0, 0xffffffff); ONE search_values call is scored against the per-interval loop of set_base_filter + exact_search.
-usage: python tools/filter_recall.py [--seed 77] [--slots | --tags | --base-tags | --values] [--out result.json]"""
+With --base-values: the same corpus and values, installed on the store as well
+(ivfhnsw_gpu_set_base_values); every query names an interval of its own, and ONE search_values call is scored against ONE
+exact_search_values call.
+usage: python tools/filter_recall.py [--seed 77] [--slots | --tags | --base-tags | --values | --base-values] [--out result.json]"""
 import argparse
 import json
 import os
@@ -286,6 +289,56 @@ def values_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
     return {"rows": n, "nq": nq, "intervals": len(sample), "values_recall": rows_out}
 
 
+def base_values_recall(pkg, seed=77, corpus=None, settings=SETTINGS, sample_only=False):
+    """Recall of one search_values call against ONE exact_search_values call (the --values corpus and value assignment,
+    installed on the store as well).  The queries name a whole batch of distinct intervals: query q takes, in turn, a width
+    of 1/8 of the values, of about 1/2000, or (0, 0xffffffff), at a seeded start of its own.  sample_only: the queries are
+    dealt over the ten sample intervals of --values instead, and the figures are the ones --values prints.  Returns the
+    report; its "truth" / "query_ranges" / "values_of_rows" entries are the arrays themselves, for a test to compare."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    values = np.random.default_rng(seed + 5).permutation(n).astype(np.uint32)  # the value of row (= id) i
+    rows = np.arange(n, dtype=np.uint32)
+    g.set_values(rows, values)       # ids = row numbers of the base: the index and the store hold the same values
+    g.set_base_values(rows, values)
+    assert g.values_info() == (n, n, n) and g.base_values_info() == (n, n)
+    if sample_only:
+        sample = value_intervals(n)
+        pick = np.arange(nq) % len(sample)
+        qr = np.array([(sample[i][1], sample[i][2]) for i in pick], np.uint32)
+        names = np.array([s_[0] for s_ in sample])[pick]
+    else:
+        w8, w2k = n // 8, max(1, n // 2000)
+        start = np.random.default_rng(seed + 6).integers(0, n, nq)
+        kind = np.arange(nq) % 3
+        names = np.array(["1/8", "~1/2000", "1 (0, 0xffffffff)"])[kind]
+        width = np.where(kind == 0, w8, w2k)
+        lo = np.minimum(start, n - width)
+        qr = np.stack([np.where(kind == 2, 0, lo), np.where(kind == 2, VALUE_NONE, lo + width - 1)], 1).astype(np.uint32)
+    distinct = int(np.unique(qr, axis=0).shape[0])
+    _, truth = g.exact_search_values(q8, 10, qr)
+    rows_out = []
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_values(qf, 10, qr, nprobe, max_codes, efSearch=ef)
+        assert g.last_scan_kernel().endswith("+values")
+        for name in ("1/8", "~1/2000", "1 (0, 0xffffffff)"):
+            idx = np.flatnonzero(names == name)
+            r1, r10 = recall_pair(lab[idx], truth[idx]) if idx.size else (float("nan"), float("nan"))
+            rows_out.append({"pass_fraction": name, "queries": int(idx.size), "nprobe": nprobe, "max_codes": max_codes,
+                             "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] base values, %s (%d queries), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, idx.size, nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "intervals": distinct, "base_values_recall": rows_out, "truth": truth, "query_ranges": qr,
+            "values_of_rows": values}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
@@ -294,6 +347,8 @@ def main():
                                                               "the queries over all 1 024 tags")
     ap.add_argument("--slots", action="store_true", help="one search_slots call against one exact_search_slots call")
     ap.add_argument("--values", action="store_true", help="one search_values call against the per-interval base-filter loop")
+    ap.add_argument("--base-values", action="store_true", help="one search_values call against one exact_search_values call, "
+                                                                "every query an interval of its own")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -301,6 +356,10 @@ def main():
     if args.base_tags:
         out = base_tags_recall(pkg, args.seed)
         out = {k: v for k, v in out.items() if k not in ("truth", "query_tags", "tags_of_rows")}
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    elif args.base_values:
+        out = base_values_recall(pkg, args.seed)
+        out = {k: v for k, v in out.items() if k not in ("truth", "query_ranges", "values_of_rows")}
         out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
     elif args.values:
         out = values_recall(pkg, args.seed)

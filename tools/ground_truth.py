@@ -19,9 +19,15 @@ With --tags FILE --query-tags FILE (both .npy files of uint16: one tag per row o
 the truth of a TAGGED workload is written: the base tags (ivfhnsw_gpu_set_base_tags) are installed and the
 _tags form of either search runs, so query q gets only rows whose tag is query_tags[q] (every row when it is 0xffff).
 
+With --values FILE --query-ranges FILE (both .npy files of uint32: one value per row of the base, 0xffffffff = no value;
+one pair (lo, hi) per query, shape [nq, 2]) the truth of a workload with a value interval per query is written: the base
+values (ivfhnsw_gpu_set_base_values) are installed and the _values form of either search runs, so query q
+gets only rows whose value lies in [lo, hi], inclusive ((0, 0xffffffff): every row).
+
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
-       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy"""
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
+       python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --values v.npy --query-ranges qr.npy"""
 import argparse
 import os
 import sys
@@ -103,6 +109,24 @@ def read_tags(path):
     return t.astype(np.uint16)
 
 
+def read_values(path):
+    """The values of a --values / --query-ranges file as uint32, flat: an .npy array of integers in 0..0xffffffff."""
+    v = np.load(path)
+    if v.dtype.kind not in "iu":
+        raise ValueError("%s: values must be integers, not %s" % (path, v.dtype))
+    v = v.ravel()
+    if v.size and (int(v.min()) < 0 or int(v.max()) > 0xffffffff):
+        raise ValueError("%s: values must fit 32 bits unsigned" % path)
+    return v.astype(np.uint32)
+
+
+def install_values(g, n, nq, values, query_ranges):
+    """The base values of a workload on g's store of n rows, the two arrays checked against the store and the queries."""
+    if values.size != n or query_ranges.size != 2 * nq:
+        raise ValueError("%d values for %d rows, %d interval ends for %d queries" % (values.size, n, query_ranges.size, nq))
+    g.set_base_values(np.arange(n, dtype=np.uint32), values)
+
+
 def install_tags(g, n, nq, tags, query_tags):
     """The base tags of a tagged workload on g's store of n rows, the two arrays checked against the store and the queries."""
     if tags.size != n or query_tags.size != nq:
@@ -141,10 +165,10 @@ def read_bvecs_image(path):
 
 
 def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False, tags=None,
-                 query_tags=None):
+                 query_tags=None, values=None, query_ranges=None):
     """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query; with `labels`
     only of the rows whose number is in them (deny: is not); with `tags` and `query_tags` only of the rows that carry the
-    query's tag."""
+    query's tag; with `values` and `query_ranges` only of the rows whose value lies in the query's interval."""
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
@@ -156,6 +180,9 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
         if tags is not None:
             install_tags(g, n, img.shape[0], tags, query_tags)
             _, lab = g.exact_search_tags(img[:, 4:], k, query_tags)
+        elif values is not None:
+            install_values(g, n, img.shape[0], values, query_ranges)
+            _, lab = g.exact_search_values(img[:, 4:], k, query_ranges)
         else:
             _, lab = g.exact_search(img[:, 4:], k)
     finally:
@@ -164,7 +191,7 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
 
 
 def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False,
-                       info=None, tags=None, query_tags=None):
+                       info=None, tags=None, query_tags=None, values=None, query_ranges=None):
     """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
     `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing."""
     img, dq = read_bvecs_image(query_path)
@@ -182,6 +209,11 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
             if info is not None:
                 info["rows_passing"] = g.base_tags_info()[0]  # the tagged rows
             return g.exact_range_search_tags(img[:, 4:], radius, query_tags)
+        if values is not None:
+            install_values(g, n, img.shape[0], values, query_ranges)
+            if info is not None:
+                info["rows_passing"] = g.base_values_info()[0]  # the rows that hold a value
+            return g.exact_range_search_values(img[:, 4:], radius, query_ranges)
         return g.exact_range_search(img[:, 4:], radius)
     finally:
         g.close()
@@ -202,7 +234,14 @@ def main(argv=None):
     flt.add_argument("--deny", default=None, help="an .ivecs or .npy file of labels: these rows of the base are never returned")
     ap.add_argument("--tags", default=None, help="an .npy file of uint16: the tag of every row of the base (0xffff: none)")
     ap.add_argument("--query-tags", default=None, help="an .npy file of uint16: the tag of every query (0xffff: every row)")
+    ap.add_argument("--values", default=None, help="an .npy file of uint32: the value of every row of the base (0xffffffff: none)")
+    ap.add_argument("--query-ranges", default=None, help="an .npy file of uint32 [nq, 2]: the interval (lo, hi) of every query, "
+                                                         "inclusive ((0, 0xffffffff): every row)")
     args = ap.parse_args(argv)
+    if (args.values is None) != (args.query_ranges is None) or (args.values and (args.allow or args.deny or args.tags)):
+        ap.error("--values and --query-ranges go together, and not with --allow / --deny / --tags")
+    values = read_values(args.values) if args.values else None
+    query_ranges = read_values(args.query_ranges) if args.values else None
     if (args.tags is None) != (args.query_tags is None) or (args.tags and (args.allow or args.deny)):
         ap.error("--tags and --query-tags go together, and not with --allow / --deny")
     tags = read_tags(args.tags) if args.tags else None
@@ -215,13 +254,14 @@ def main(argv=None):
     if args.radius is not None:
         info = {}
         lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device,
-                                             labels=labels, deny=deny, info=info, tags=tags, query_tags=query_tags)
+                                             labels=labels, deny=deny, info=info, tags=tags, query_tags=query_tags,
+                                             values=values, query_ranges=query_ranges)
         write_range(args.out, lims, dist, lab, args.radius, filter_mode=-1 if labels is None else int(deny),
                     rows_passing=info.get("rows_passing"))
         print("%s: %d queries, %d rows within %g" % (args.out, lims.size - 1, lab.size, args.radius))
         return
     lab = ground_truth(pkg, args.base, args.queries, args.k, rows=args.rows, device=args.device, labels=labels, deny=deny,
-                       tags=tags, query_tags=query_tags)
+                       tags=tags, query_tags=query_tags, values=values, query_ranges=query_ranges)
     write_ivecs(args.out, lab)
     print("%s: %d queries x %d labels" % (args.out, lab.shape[0], lab.shape[1]))
 
