@@ -9,7 +9,7 @@
 // release_base(), searchDisk_batch(), remove_ids(), update_batch(), set_id_filter(), clear_id_filter(), set_id_filter_slot(),
 // clear_id_filter_slot(), search_batch_slots(), range_search_slots(), set_id_tags(), clear_id_tags(),
 // search_batch_tags(), range_search_tags(), set_id_values(), clear_id_values(), search_batch_values(),
-// range_search_values(), range_search(),
+// range_search_values(), search_batch_tags_values(), range_search_tags_values(), range_search(),
 // reconstruct_labels(), search_and_reconstruct(), search_and_reconstruct_batch().
 #ifndef IVFHNSW_AMD_INDEX_IVF_HNSW_H
 #define IVFHNSW_AMD_INDEX_IVF_HNSW_H
@@ -175,6 +175,16 @@ public:
     void search_batch_values(size_t nq, size_t k, const float *x, const uint32_t *ranges, float *distances, long *labels);
     void range_search_values(size_t nq, const float *x, const uint32_t *ranges, float radius, std::vector<size_t> &lims,
                              std::vector<float> &distances, std::vector<long> &labels);
+    /// Extension: a tag AND an interval per query (ivfhnsw_gpu_search_tags_values), on the tags of
+    /// set_id_tags and the values of set_id_values the object already keeps: nothing is added to it.  Query q carries
+    /// tags[q] and (ranges[2q], ranges[2q + 1]) and is answered as search_batch / range_search would with
+    /// set_id_filter(ids tagged tags[q] whose value lies in the interval) installed; tag 0xffff and (0, 0xffffffff) are the
+    /// wildcards of the two sides, a null array makes the call the other side's.  Throws while a set_id_filter filter is
+    /// installed, and with IVFHNSW_SHARDS > 1.  Non-virtual.
+    void search_batch_tags_values(size_t nq, size_t k, const float *x, const uint16_t *tags, const uint32_t *ranges,
+                                  float *distances, long *labels);
+    void range_search_tags_values(size_t nq, const float *x, const uint16_t *tags, const uint32_t *ranges, float radius,
+                                  std::vector<size_t> &lims, std::vector<float> &distances, std::vector<long> &labels);
     virtual void add_batch2(size_t n, const float *x, const idx_t *xids, const idx_t *idx, uint64_t *eids, char *obuf);
     virtual void train_pq(size_t n, const float *x);
 

@@ -373,6 +373,7 @@ int ivfhnsw_gpu_filter_slot_info(ivfhnsw_gpu *h, unsigned slot, int *mode, uint6
  *   shard_world > 1 -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM.
  * The truth of a _tags search: ivfhnsw_gpu_exact_search_tags on a store tagged with ivfhnsw_gpu_set_base_tags ("Base
  *   tags" below), one call for any number of tags.
+ * A tag AND a value interval per query: the _tags_values calls ("Row tags AND row values" below).
  * Not built: tags for search_reconstruct, search_sharded and sharded handles; a tag AND the handle's filter or a slot;
  *   tags wider than 16 bits or several tags per row. */
 #define IVFHNSW_TAG_NONE 0xffffu
@@ -422,14 +423,39 @@ int ivfhnsw_gpu_tag_rows(ivfhnsw_gpu *h, unsigned tag, uint64_t *rows);
  *   shard_world > 1 -> IVFHNSW_ERR_STATE; a failed allocation -> IVFHNSW_ERR_NOMEM; whatever search_dev /
  *   range_search_dev refuses for the same params -> that status.  An error leaves earlier range results and the
  *   installed state as they were.
- * Not built: values for the exact calls, for search_reconstruct, search_sharded and sharded handles; an interval AND a
- *   tag, a slot or the handle's filter; 64-bit or float values, or several values per row. */
+ * An interval AND a tag per query: the _tags_values calls ("Row tags AND row values" below).
+ * Not built: values for search_reconstruct, search_sharded and sharded handles; an interval AND a slot or the handle's
+ *   filter; 64-bit or float values, or several values per row. */
 #define IVFHNSW_VALUE_NONE 0xffffffffu
 int ivfhnsw_gpu_set_values(ivfhnsw_gpu *h, size_t n, const uint32_t *labels, const uint32_t *values);
 int ivfhnsw_gpu_set_values_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, const uint32_t *d_values);
 int ivfhnsw_gpu_clear_values(ivfhnsw_gpu *h);
 int ivfhnsw_gpu_values_info(ivfhnsw_gpu *h, uint64_t *rows_valued, uint64_t *rows_total, uint64_t *table_labels);
 int ivfhnsw_gpu_value_rows(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *rows);
+
+/* Row tags AND row values: "the nearest neighbours among THIS tenant's vectors of the LAST HOUR" in one
+ * call.  The _tags_values forms of search and range search take both per-query arrays of the two sections above:
+ * query_tags [nq] uint16 and query_ranges [2 * nq] uint32, (lo, hi) of query q at [2q], [2q + 1].
+ *   The rule: a row passes query q iff (t == IVFHNSW_TAG_NONE || tag(row) == t) && lo <= value(row) <= hi -- exactly the
+ * AND of the two rules above, both wildcards kept: (NONE, (0, 0xffffffff)) is the unfiltered query, (t, (0, 0xffffffff))
+ * the _tags query, (NONE, (lo, hi)) the _values query, and lo > hi passes nothing.
+ *   Query q answers, bit for bit, what the plain call answers on the same handle with set_filter({labels tagged t whose
+ * value lies in [lo, hi]}, ALLOW) installed, in everything the two sections above list; max_codes and Grouping's pruning
+ * count every stored code and last_scan_counts is the unfiltered call's.  A launch reports the unfiltered kernel's name
+ * with "+tags+values" appended and runs plan, table and scan as a _values launch does.  query_tags == NULL makes the call
+ * the _values call ("+values"), query_ranges == NULL the _tags call, both NULL the plain call.
+ *   No new state: the calls read the tags and the values the handle (a view: its parent) already holds and that every
+ * update re-derives.  They ignore slots; with a set_filter filter installed -> IVFHNSW_ERR_STATE; on a handle that lacks
+ * the tag table, the value table or both they are legal and the missing one reads as NONE for every row; on a handle with
+ * shard_world > 1 -> IVFHNSW_ERR_STATE.  Host memory for the host forms; device memory for _dev, the tags 2-byte and the
+ * ranges 8-byte aligned (else IVFHNSW_ERR_INVALID).  A host call stages 2 + 8 bytes per query.  Other errors are the
+ * twins'; an error leaves earlier range results and all installed state as they were.
+ *   ivfhnsw_gpu_tag_value_rows: *rows = resident rows the rule passes (size max_codes from it); tag > 0xffff or a null
+ * result -> IVFHNSW_ERR_INVALID.
+ * Not built: the exact calls under tag AND interval (the store would need a (tag, value, row) order); a slot or the
+ *   handle's filter AND-ed with either; search_reconstruct, search_sharded and sharded handles; several tags or values
+ *   per row. */
+int ivfhnsw_gpu_tag_value_rows(ivfhnsw_gpu *h, unsigned tag, uint32_t lo, uint32_t hi, uint64_t *rows);
 
 /* The extra members of IndexIVF_HNSW_Grouping (IndexIVF_HNSW_Grouping.h:17-22,61) after read()
  * (IndexIVF_HNSW_Grouping.cpp:445-483).  All [nc*nsubc] row major; subgroup_sizes rows of empty
@@ -555,6 +581,15 @@ int ivfhnsw_gpu_search_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const flo
                                   const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                   const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels, int64_t *d_out_keys);
 
+/* ... and with both (see "Row tags AND row values" above); either array NULL = the other's call. */
+int ivfhnsw_gpu_search_tags_values(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                                   const float *coarse_dists, const ivfhnsw_search_params *params, const uint16_t *query_tags,
+                                   const uint32_t *query_ranges, float *distances, int64_t *labels);
+int ivfhnsw_gpu_search_tags_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                       const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                       const uint16_t *d_query_tags, const uint32_t *d_query_ranges, float *d_distances,
+                                       int64_t *d_labels, int64_t *d_out_keys);
+
 /* Multi-GPU merge helper: given keys already MIN-reduced over the shards, resolve the
  * labels this shard owns ([nq*k]; -1 where the winner lives on another shard) from the scan plan of
  * the last search_dev call, and decode the distances.  The caller then MAX-reduces the labels. */
@@ -659,6 +694,15 @@ int ivfhnsw_gpu_range_search_values(ivfhnsw_gpu *h, size_t nq, const float *quer
 int ivfhnsw_gpu_range_search_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
                                         const float *d_coarse_dists, const ivfhnsw_search_params *params,
                                         const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total);
+/* ... and with both ("Row tags AND row values" above) */
+int ivfhnsw_gpu_range_search_tags_values(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                         const float *coarse_dists, const ivfhnsw_search_params *params,
+                                         const uint16_t *query_tags, const uint32_t *query_ranges, float radius, uint64_t *lims,
+                                         uint64_t *total);
+int ivfhnsw_gpu_range_search_tags_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                             const float *d_coarse_dists, const ivfhnsw_search_params *params,
+                                             const uint16_t *d_query_tags, const uint32_t *d_query_ranges, float radius,
+                                             uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
 

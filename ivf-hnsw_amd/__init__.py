@@ -64,6 +64,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_set_values", "ivfhnsw_gpu_set_values_dev", "ivfhnsw_gpu_clear_values", "ivfhnsw_gpu_values_info",
     "ivfhnsw_gpu_value_rows", "ivfhnsw_gpu_search_values", "ivfhnsw_gpu_search_values_dev",
     "ivfhnsw_gpu_range_search_values", "ivfhnsw_gpu_range_search_values_dev",
+    "ivfhnsw_gpu_search_tags_values", "ivfhnsw_gpu_search_tags_values_dev",
+    "ivfhnsw_gpu_range_search_tags_values", "ivfhnsw_gpu_range_search_tags_values_dev", "ivfhnsw_gpu_tag_value_rows",
     "ivfhnsw_gpu_set_base_tags", "ivfhnsw_gpu_set_base_tags_dev", "ivfhnsw_gpu_clear_base_tags",
     "ivfhnsw_gpu_base_tags_info", "ivfhnsw_gpu_base_tag_rows",
     "ivfhnsw_gpu_exact_search_tags", "ivfhnsw_gpu_exact_search_tags_dev",
@@ -236,6 +238,14 @@ def lib():
         L.ivfhnsw_gpu_search_values_dev.argtypes = L.ivfhnsw_gpu_search_slots_dev.argtypes
         L.ivfhnsw_gpu_range_search_values.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search_values_dev.argtypes = L.ivfhnsw_gpu_range_search_slots.argtypes
+        # ... and with both arrays: the second pick pointer follows the first
+        a = L.ivfhnsw_gpu_search_slots.argtypes
+        L.ivfhnsw_gpu_search_tags_values.argtypes = a[:8] + [C.c_void_p] + a[8:]
+        L.ivfhnsw_gpu_search_tags_values_dev.argtypes = L.ivfhnsw_gpu_search_tags_values.argtypes + [C.c_void_p]
+        a = L.ivfhnsw_gpu_range_search_slots.argtypes
+        L.ivfhnsw_gpu_range_search_tags_values.argtypes = a[:7] + [C.c_void_p] + a[7:]
+        L.ivfhnsw_gpu_range_search_tags_values_dev.argtypes = L.ivfhnsw_gpu_range_search_tags_values.argtypes
+        L.ivfhnsw_gpu_tag_value_rows.argtypes = [C.c_void_p, C.c_uint, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_set_base_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         L.ivfhnsw_gpu_set_base_filter_dev.argtypes = L.ivfhnsw_gpu_set_base_filter.argtypes
         L.ivfhnsw_gpu_clear_base_filter.argtypes = [C.c_void_p]
@@ -623,6 +633,13 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_value_rows(self._h, lo, hi, C.byref(n)))
         return int(n.value)
 
+    # ---- row tags AND row values: both per query (ivfhnsw_gpu_search_tags_values) -----------------------
+    def tag_value_rows(self, tag, lo, hi):
+        """Resident rows whose tag passes `tag` (TAG_NONE: every row) AND whose value lies in [lo, hi]."""
+        n = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_tag_value_rows(self._h, tag, lo, hi, C.byref(n)))
+        return int(n.value)
+
     def upload_grouping(self, nsubc, alphas, nn_centroid_idxs, subgroup_sizes, inter_centroid_dists):
         a = _np(alphas, np.float32)
         n = _np(nn_centroid_idxs, np.uint32)
@@ -779,6 +796,25 @@ class GpuIndex:
         return self._search_picked(lib().ivfhnsw_gpu_search_values, np.uint32, queries, k, query_ranges, nprobe, max_codes,
                                    coarse_ids, coarse_dists, efSearch, do_pruning, heap_order, per=2)
 
+    def search_tags_values(self, queries, k, query_tags, query_ranges, nprobe, max_codes, coarse_ids=None, coarse_dists=None,
+                           efSearch=0, do_pruning=False, heap_order=False):
+        """search() with a row tag AND a value interval per query (query_tags as search_tags, query_ranges as
+        search_values take them): a row passes iff it passes both.  query_tags None is search_values, query_ranges None
+        search_tags, both None search() itself (ivfhnsw_gpu_search_tags_values)."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq * 2)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_tags_values(self._h, nq, k, _ptr(q), _ptr(cid), _ptr(cd), C.byref(p), _ptr(qt), _ptr(qr),
+                                                    _ptr(dist), _ptr(lab)))
+        return dist, lab
+
     def _search_picked(self, fn, pick_dtype, queries, k, query_slots, nprobe, max_codes, coarse_ids, coarse_dists, efSearch,
                        do_pruning, heap_order, per=1):
         q = _np(queries, np.float32)
@@ -821,6 +857,17 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_search_values_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
                                                    _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_ranges),
                                                    _devptr(d_distances), _devptr(d_labels), _devptr(d_out_keys)))
+
+    def search_tags_values_dev(self, nq, k, d_queries, d_query_tags, d_query_ranges, d_distances, d_labels, nprobe, max_codes,
+                               d_coarse_ids=None, d_coarse_dists=None, efSearch=0, do_pruning=False, d_out_keys=None,
+                               heap_order=False):
+        """search_dev() with a row tag AND a value interval per query (d_query_tags: [nq] uint16, d_query_ranges: [nq, 2]
+        uint32 8-byte aligned, both in device memory, not read back); either None gives the other's call."""
+        p = self._params(nprobe, max_codes, efSearch, do_pruning, heap_order)
+        _check(lib().ivfhnsw_gpu_search_tags_values_dev(self._h, nq, k, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                        _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
+                                                        _devptr(d_query_ranges), _devptr(d_distances), _devptr(d_labels),
+                                                        _devptr(d_out_keys)))
 
     # ---- reconstruction of stored vectors (ivfhnsw_gpu_reconstruct*, DESIGN.md 3.16) ---------------------------------
     def locate(self, labels):
@@ -944,6 +991,24 @@ class GpuIndex:
         return self._range_search_picked(lib().ivfhnsw_gpu_range_search_values, np.uint32, queries, radius, query_ranges, nprobe,
                                          max_codes, efSearch, do_pruning, coarse_ids, coarse_dists, per=2)
 
+    def range_search_tags_values(self, queries, radius, query_tags, query_ranges, nprobe, max_codes, efSearch=0,
+                                 do_pruning=False, coarse_ids=None, coarse_dists=None):
+        """range_search() with a row tag AND a value interval per query (as search_tags_values takes them)."""
+        q = _np(queries, np.float32)
+        q = q.reshape(-1, self.d or q.shape[-1])
+        nq = q.shape[0]
+        cid = None if coarse_ids is None else _np(coarse_ids, np.uint32).reshape(nq, nprobe)
+        cd = None if coarse_dists is None else _np(coarse_dists, np.float32).reshape(nq, nprobe)
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq * 2)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_tags_values(self._h, nq, _ptr(q) if nq else None, _ptr(cid), _ptr(cd), C.byref(p),
+                                                          _ptr(qt), _ptr(qr), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.range_results(0, int(total.value))
+        return lims, dist, lab
+
     def _range_search_picked(self, fn, pick_dtype, queries, radius, query_slots, nprobe, max_codes, efSearch, do_pruning,
                              coarse_ids, coarse_dists, per=1):
         q = _np(queries, np.float32)
@@ -988,6 +1053,17 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_range_search_values_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
                                                          _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_ranges),
                                                          C.c_float(radius), _devptr(d_lims), C.byref(total)))
+        return int(total.value)
+
+    def range_search_tags_values_dev(self, nq, d_queries, radius, d_query_tags, d_query_ranges, d_lims, nprobe, max_codes,
+                                     efSearch=0, do_pruning=False, d_coarse_ids=None, d_coarse_dists=None):
+        """range_search_dev() with a row tag AND a value interval per query (both arrays in device memory)."""
+        total = C.c_uint64(0)
+        p = self._params(nprobe, max_codes, efSearch, do_pruning)
+        _check(lib().ivfhnsw_gpu_range_search_tags_values_dev(self._h, nq, _devptr(d_queries), _devptr(d_coarse_ids),
+                                                              _devptr(d_coarse_dists), C.byref(p), _devptr(d_query_tags),
+                                                              _devptr(d_query_ranges), C.c_float(radius), _devptr(d_lims),
+                                                              C.byref(total)))
         return int(total.value)
 
     def range_results(self, first, count):

@@ -2,7 +2,8 @@
 // denied one.  The set becomes a bitmap over [0, max label], the bitmap one PASS bit per resident row, and the filtered
 // forms of the scan kernels read that bit beside the row's norm code.  The bitmap stays with the handle so that in-place
 // updates can judge the rows of their new arrays (ListArrays::mark_filter, capi_internal.h).  Filter slots (3.19) and
-// row tags (3.21) and row values (3.24), the three per-query forms, live here too.
+// row tags (3.21) and row values (3.24), the three per-query forms, and the call that reads tags AND values (3.26)
+// live here too.
 #include "capi_internal.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -109,13 +110,25 @@ int slots_call_guard(const ivfhnsw_gpu *h, const char *who, int kind)
 {
     if (h->t.shard_world > 1)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle is shard %u of %u; sharded handles have no %s", who,
-                    h->t.shard_rank, h->t.shard_world, kind == 2 ? "row values" : kind == 1 ? "row tags" : "filter slots");
+                    h->t.shard_rank, h->t.shard_world,
+                    kind == 3 ? "row tags and values" : kind == 2 ? "row values" : kind == 1 ? "row tags" : "filter slots");
     if (h->filter.mode >= 0)
         return fail(IVFHNSW_ERR_STATE, "%s: the handle has a set_filter filter installed; a call is filtered by that or by "
-                                       "%s, not both (clear_filter first)", who, kind == 2 ? "values" : kind == 1 ? "tags" : "slots");
+                                       "%s, not both (clear_filter first)", who,
+                    kind == 3 ? "tags and values" : kind == 2 ? "values" : kind == 1 ? "tags" : "slots");
     return IVFHNSW_OK;
 }
 
+int pick_stage_in(ivfhnsw_gpu *h, const QueryPick &pick, size_t nq)
+{
+    int rc = h->fs_qslots.ensure(pick.bytes(nq));
+    if (rc)
+        return rc;
+    return pick.each_array(nq, [&](const void *src, size_t at, size_t bytes) -> int {
+        HIP_TRY(hipMemcpyAsync(h->fs_qslots.as<char>() + at, src, bytes, hipMemcpyHostToDevice, h->stream));
+        return IVFHNSW_OK;
+    });
+}
 
 int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who)
 {
@@ -343,6 +356,21 @@ static int values_count(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *out)
         return rc;
     unsigned long long cnt = 0;
     HIP_TRY(launch_values_count(h->stream, h->row_values, h->n_local, lo, hi, word.as<unsigned long long>()));
+    HIP_TRY(hipMemcpyAsync(&cnt, word.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *out = cnt;
+    return IVFHNSW_OK;
+}
+
+// ... and over both: rows the conjunction of DESIGN.md 3.26 passes.  A missing table reads as NONE for every row.
+static int tag_values_count(ivfhnsw_gpu *h, uint32_t tag, uint32_t lo, uint32_t hi, uint64_t *out)
+{
+    ScopedBuf word;
+    int rc = word.ensure(sizeof(unsigned long long));
+    if (rc)
+        return rc;
+    unsigned long long cnt = 0;
+    HIP_TRY(launch_tag_values_count(h->stream, h->row_tags, h->row_values, h->n_local, tag, lo, hi, word.as<unsigned long long>()));
     HIP_TRY(hipMemcpyAsync(&cnt, word.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *out = cnt;
@@ -602,4 +630,16 @@ int ivfhnsw_gpu_value_rows(ivfhnsw_gpu *h, uint32_t lo, uint32_t hi, uint64_t *r
     if (!rows)
         return fail(IVFHNSW_ERR_INVALID, "value_rows: a null result");
     return values_count(h, lo, hi, rows);
+}
+
+// ---- row tags AND row values
+
+int ivfhnsw_gpu_tag_value_rows(ivfhnsw_gpu *h, unsigned tag, uint32_t lo, uint32_t hi, uint64_t *rows)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (tag > IVFHNSW_TAG_NONE || !rows)
+        return fail(IVFHNSW_ERR_INVALID, "tag_value_rows: tag %u (tags are 0..0xffff) or a null result", tag);
+    return tag_values_count(h, tag, lo, hi, rows);
 }

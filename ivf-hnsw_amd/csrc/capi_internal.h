@@ -193,7 +193,7 @@ using namespace ivfhnsw_gpu_impl;
     X(gp_sub) X(gp_sizes) X(gp_pre_old) X(gp_pre_new) X(gp_rows) X(gp_gather) X(ga_cidx) X(ga_off) X(ga_nn) X(ga_alpha) X(ga_inter) X(ga_status) /* append_grouping, add_groups */ \
     X(rm_labels) X(rm_bits) X(rm_mask) X(rm_keep) X(rm_rem) X(rm_out) X(rm_part) X(rm_status) X(rm_sizes) /* remove_ids */ \
     X(f_mask) X(f_count) /* set_filter: the pass mask, the count's word (the kept label bitmap: filter.bits) */ \
-    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts, a _values call's pairs) */ \
+    X(fs_planes) X(fs_count) X(fs_qslots) /* filter slots: the planes (their label bitmaps: slots[].bits), staging of counts and a host call's slot bytes (a _tags call's shorts, a _values call's pairs, a _tags_values call's both) */ \
     X(tg_table) X(tg_rows) /* row tags: a uint16 per label value, a uint16 per resident row */ \
     X(vl_table) X(vl_rows) /* row values: a uint32 per label value, a uint32 per resident row */ \
     X(bf_words) X(bf_rows) X(bf_own) X(bf_count) /* set_base_filter: pass words, pass rows; a list this handle was forced to build; the count's word */ \
@@ -409,7 +409,7 @@ int slots_mark_rows(ivfhnsw_gpu *h, const uint32_t *ids, uint64_t n_local, DevBu
 void slots_drop(ivfhnsw_gpu *h); // the handle holds no slot afterwards (buffers released)
 // what a _slots entry point checks first, behind the plain call's own guard
 int slots_call_guard(const ivfhnsw_gpu *h, const char *who, bool tags = false); // tags: the same for a _tags entry point
-int slots_call_guard(const ivfhnsw_gpu *h, const char *who, int kind); // ... by QueryPick::kind(): 0 _slots, 1 _tags, 2 _values
+int slots_call_guard(const ivfhnsw_gpu *h, const char *who, int kind); // ... by QueryPick::kind(): 0 _slots, 1 _tags, 2 _values, 3 _tags_values
 // the slot bytes of a host call: each is below IVFHNSW_FILTER_SLOTS or IVFHNSW_SLOT_NONE
 int slots_bytes_guard(size_t nq, const uint8_t *query_slots, const char *who);
 // (every uint16 is a tag: the host form of a _tags call has nothing to check there)
@@ -559,33 +559,54 @@ struct WalkClear {
     bool cleared = false;     // out
 };
 
-// What a _slots, a _tags or a _values entry point carries beside the plain call's arguments:
-// a filter slot byte, a tag or an interval (two uint32: lo, hi) per query, one of the three at most, in host or device
-// memory as the call's other arrays are.
+// What a _slots, a _tags, a _values or a _tags_values entry point carries beside the plain call's arguments (DESIGN.md
+// 3.19, 3.21, 3.24, 3.26): a filter slot byte, a tag or an interval (two uint32: lo, hi) per query, in host or device
+// memory as the call's other arrays are.  One of the three at most, except that a tag AND an interval go together.
 struct QueryPick {
     const uint8_t *slots = nullptr;
     const uint16_t *tags = nullptr;
     const uint32_t *ranges = nullptr;
     explicit operator bool() const { return slots || tags || ranges; }
-    int kind() const { return ranges ? 2 : tags ? 1 : 0; } // what slots_call_guard is told
-    const void *data() const { return slots ? static_cast<const void *>(slots) : tags ? static_cast<const void *>(tags) : ranges; }
-    size_t bytes(size_t nq) const { return slots ? nq : tags ? nq * sizeof(uint16_t) : ranges ? nq * 2 * sizeof(uint32_t) : 0; }
-    // the same kind of pick with its array at p / for the queries from q0 on
-    QueryPick at(const void *p) const
+    bool both() const { return tags && ranges; }
+    int kind() const { return both() ? 3 : ranges ? 2 : tags ? 1 : 0; } // what slots_call_guard is told
+    // The arrays of nq queries as they ride in ONE block (the pinned input block, the staging buffer): the pairs first, so
+    // that they are 8-byte aligned wherever the block is, the tags of a _tags_values call behind them.
+    size_t tags_at(size_t nq) const { return both() ? nq * 2 * sizeof(uint32_t) : 0; }
+    size_t bytes(size_t nq) const
     {
-        return {slots ? static_cast<const uint8_t *>(p) : nullptr, tags ? static_cast<const uint16_t *>(p) : nullptr,
+        return slots ? nq : (tags ? nq * sizeof(uint16_t) : 0) + (ranges ? nq * 2 * sizeof(uint32_t) : 0);
+    }
+    // f(source, offset in the block, bytes) for every array the pick holds; stops at the first non-zero result
+    template <class F> int each_array(size_t nq, F &&f) const
+    {
+        int rc = 0;
+        if (slots)
+            rc = f(static_cast<const void *>(slots), (size_t)0, nq);
+        if (!rc && ranges)
+            rc = f(static_cast<const void *>(ranges), (size_t)0, nq * 2 * sizeof(uint32_t));
+        if (!rc && tags)
+            rc = f(static_cast<const void *>(tags), tags_at(nq), nq * sizeof(uint16_t));
+        return rc;
+    }
+    // the same kind of pick with its nq queries' arrays in the block at p / for the queries from q0 on
+    QueryPick at(const void *p, size_t nq) const
+    {
+        return {slots ? static_cast<const uint8_t *>(p) : nullptr,
+                tags ? reinterpret_cast<const uint16_t *>(static_cast<const char *>(p) + tags_at(nq)) : nullptr,
                 ranges ? static_cast<const uint32_t *>(p) : nullptr};
     }
     QueryPick from(size_t q0) const
     {
         return {slots ? slots + q0 : nullptr, tags ? tags + q0 : nullptr, ranges ? ranges + 2 * q0 : nullptr};
     }
-    // the entry point's name: "<call>_slots", "<call>_tags" or "<call>_values"
-    const char *who(const char *slotted, const char *tagged, const char *valued) const
+    // the entry point's name: "<call>_slots", "<call>_tags", "<call>_values" or "<call>_tags_values"
+    const char *who(const char *slotted, const char *tagged, const char *valued, const char *tag_valued) const
     {
-        return ranges ? valued : tags ? tagged : slotted;
+        return both() ? tag_valued : ranges ? valued : tags ? tagged : slotted;
     }
 };
+// a host call's pick into the handle's staging buffer (fs_qslots), laid out as above; at(h->fs_qslots.p, nq) reads it
+int pick_stage_in(ivfhnsw_gpu *h, const QueryPick &pick, size_t nq);
 
 // The arguments of ivfhnsw_gpu_search_dev, handed down as one.
 struct SearchArgs {
@@ -596,7 +617,7 @@ struct SearchArgs {
     const ivfhnsw_search_params *p;
     float *d_distances;
     int64_t *d_labels, *d_out_keys;
-    QueryPick pick{}; // a _slots / _tags / _values call: the slot, tag or interval of every query (device memory), else empty
+    QueryPick pick{}; // a _slots / _tags / _values / _tags_values call: the slot, tag, interval or both of every query (device memory), else empty
     SearchArgs slice(size_t q0, size_t n, size_t d) const // the same call for queries [q0, q0 + n)
     {
         return {n, k, d_queries + q0 * d, d_coarse_ids ? d_coarse_ids + q0 * p->nprobe : nullptr,
@@ -609,7 +630,7 @@ struct SearchArgs {
 struct Chunk : SearchArgs {
     int nprobe, max_seg, plan_k;    // chunk_workspace
     bool heap_big;                  // k > 1024: the heap-order scan only (no top-k keys, no stream)
-    ScanFilter fmask;               // a label filter, the call's filter slots (3.19), tags (3.21) or values (3.24)
+    ScanFilter fmask;               // a label filter, the call's filter slots (3.19), tags (3.21), values (3.24) or both (3.26)
     const float *xq;                // chunk_coarse: the rotated queries, the coarse results,
     const uint32_t *cid;
     const float *cd;

@@ -55,12 +55,12 @@ static int range_search_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, c
                             float radius, uint64_t *d_lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, radius, d_lims, total);
-    if (rc || (pick && (rc = slots_call_guard(h, pick.who("range_search_slots_dev", "range_search_tags_dev", "range_search_values_dev"), pick.kind()))))
+    if (rc || (pick && (rc = slots_call_guard(h, pick.who("range_search_slots_dev", "range_search_tags_dev", "range_search_values_dev", "range_search_tags_values_dev"), pick.kind()))))
         return rc;
     if ((uintptr_t)pick.tags & 1)
-        return fail(IVFHNSW_ERR_INVALID, "range_search_tags_dev: query tags must be 2-byte aligned");
+        return fail(IVFHNSW_ERR_INVALID, "%s: query tags must be 2-byte aligned", pick.who("", "range_search_tags_dev", "", "range_search_tags_values_dev"));
     if ((uintptr_t)pick.ranges & 7)
-        return fail(IVFHNSW_ERR_INVALID, "range_search_values_dev: query ranges must be 8-byte aligned");
+        return fail(IVFHNSW_ERR_INVALID, "%s: query ranges must be 8-byte aligned", pick.who("", "", "range_search_values_dev", "range_search_tags_values_dev"));
     if (nq == 0) {
         if (d_lims) {
             HIP_TRY(hipMemsetAsync(d_lims, 0, sizeof(uint64_t), h->stream));
@@ -178,13 +178,22 @@ int ivfhnsw_gpu_range_search_values_dev(ivfhnsw_gpu *h, size_t nq, const float *
                             d_lims, total);
 }
 
+int ivfhnsw_gpu_range_search_tags_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, const uint32_t *d_coarse_ids,
+                                             const float *d_coarse_dists, const ivfhnsw_search_params *p,
+                                             const uint16_t *d_query_tags, const uint32_t *d_query_ranges, float radius,
+                                             uint64_t *d_lims, uint64_t *total)
+{
+    return range_search_dev(h, nq, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, d_query_tags, d_query_ranges},
+                            radius, d_lims, total);
+}
+
 // ivfhnsw_gpu_range_search, and with a pick (host memory) ivfhnsw_gpu_range_search_slots / _tags / _values
 static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
                              const float *coarse_dists, const ivfhnsw_search_params *p, const QueryPick &pick, float radius,
                              uint64_t *lims, uint64_t *total)
 {
     int rc = range_args_guard(h, nq, queries, coarse_ids, coarse_dists, p, radius, lims, total);
-    const char *who = pick.who("range_search_slots", "range_search_tags", "range_search_values");
+    const char *who = pick.who("range_search_slots", "range_search_tags", "range_search_values", "range_search_tags_values");
     if (rc || (pick && ((rc = slots_call_guard(h, who, pick.kind())) ||
                         (pick.slots && (rc = slots_bytes_guard(nq, pick.slots, who))))))
         return rc;
@@ -196,9 +205,9 @@ static int range_search_host(ivfhnsw_gpu *h, size_t nq, const float *queries, co
     const size_t in_q = nq * h->t.d * sizeof(float), in_c = coarse_ids ? nq * p->nprobe * sizeof(uint32_t) : 0;
     if ((rc = h->rg_lims.ensure((nq + 1) * sizeof(uint64_t))) || (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (pick && (rc = stage_in(h, h->fs_qslots, pick.data(), pick.bytes(nq)))) ||
+        (pick && (rc = pick_stage_in(h, pick, nq))) ||
         (rc = range_search_dev(h, nq, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                               coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p),
+                               coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p, nq),
                                radius, h->rg_lims.as<uint64_t>(), total)) ||
         (rc = stage_out(h, lims, h->rg_lims, (nq + 1) * sizeof(uint64_t))))
         return rc;
@@ -232,6 +241,14 @@ int ivfhnsw_gpu_range_search_values(ivfhnsw_gpu *h, size_t nq, const float *quer
                                     float radius, uint64_t *lims, uint64_t *total)
 {
     return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, nullptr, query_ranges}, radius, lims, total);
+}
+
+int ivfhnsw_gpu_range_search_tags_values(ivfhnsw_gpu *h, size_t nq, const float *queries, const uint32_t *coarse_ids,
+                                         const float *coarse_dists, const ivfhnsw_search_params *p, const uint16_t *query_tags,
+                                         const uint32_t *query_ranges, float radius, uint64_t *lims, uint64_t *total)
+{
+    return range_search_host(h, nq, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags, query_ranges}, radius, lims,
+                             total);
 }
 
 int ivfhnsw_gpu_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels)

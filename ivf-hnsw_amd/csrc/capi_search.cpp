@@ -355,7 +355,7 @@ int ivfhnsw_gpu_search_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys}, call);
 }
 
-// The same call with a filter slot, a tag (3.21) or a value interval (3.24) per query.  None is read
+// The same call with a filter slot, a tag (3.21), a value interval (3.24) or both (3.26) per query.  None is read
 // back: a byte that names no installed slot, like a tag no row carries or an interval no row's value lies in, passes
 // nothing.  An empty pick: the plain call.
 static int search_pick_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
@@ -366,12 +366,12 @@ static int search_pick_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_q
         return ivfhnsw_gpu_search_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys);
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)) ||
-        (rc = slots_call_guard(h, pick.who("search_slots_dev", "search_tags_dev", "search_values_dev"), pick.kind())))
+        (rc = slots_call_guard(h, pick.who("search_slots_dev", "search_tags_dev", "search_values_dev", "search_tags_values_dev"), pick.kind())))
         return rc;
     if ((uintptr_t)pick.tags & 1)
-        return fail(IVFHNSW_ERR_INVALID, "search_tags_dev: query tags must be 2-byte aligned");
+        return fail(IVFHNSW_ERR_INVALID, "%s: query tags must be 2-byte aligned", pick.who("", "search_tags_dev", "", "search_tags_values_dev"));
     if ((uintptr_t)pick.ranges & 7)
-        return fail(IVFHNSW_ERR_INVALID, "search_values_dev: query ranges must be 8-byte aligned");
+        return fail(IVFHNSW_ERR_INVALID, "%s: query ranges must be 8-byte aligned", pick.who("", "", "search_values_dev", "search_tags_values_dev"));
     SearchCall call;
     return search_dev_impl(h, {nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, d_distances, d_labels, d_out_keys, pick}, call);
 }
@@ -397,6 +397,14 @@ int ivfhnsw_gpu_search_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const flo
                                   float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
 {
     return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, nullptr, d_query_ranges},
+                           d_distances, d_labels, d_out_keys);
+}
+
+int ivfhnsw_gpu_search_tags_values_dev(ivfhnsw_gpu *h, size_t nq, size_t k, const float *d_queries, const uint32_t *d_coarse_ids,
+                                       const float *d_coarse_dists, const ivfhnsw_search_params *p, const uint16_t *d_query_tags,
+                                       const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels, int64_t *d_out_keys)
+{
+    return search_pick_dev(h, nq, k, d_queries, d_coarse_ids, d_coarse_dists, p, QueryPick{nullptr, d_query_tags, d_query_ranges},
                            d_distances, d_labels, d_out_keys);
 }
 
@@ -443,7 +451,9 @@ int ivfhnsw_gpu_impl::chunk_workspace(ivfhnsw_gpu *h, Chunk &c)
         (rc = h->w_keys.ensure(c.nq * (size_t)c.plan_k * sizeof(uint64_t))) ||
         (rc = h->w_totals.ensure(2 * sizeof(unsigned long long))))
         return rc;
-    if (c.pick.ranges) // the row values the handle (a view: its parent) holds, null without a table, and this chunk's pairs
+    if (c.pick.both()) // both row arrays, either null without its table, and this chunk's tags and pairs
+        c.fmask = TagValueMask{h->row_tags, h->row_values, c.pick.tags, c.pick.ranges};
+    else if (c.pick.ranges) // the row values the handle (a view: its parent) holds, null without a table, and this chunk's pairs
         c.fmask = ValueMask{h->row_values, c.pick.ranges};
     else if (c.pick.tags) // the row tags the handle (a view: its parent) holds, null without a tag table, and this chunk's tags
         c.fmask = TagMask{h->row_tags, c.pick.tags};
@@ -598,7 +608,7 @@ static int chunk_scan_select(ivfhnsw_gpu *h, const Chunk &c)
             HIP_TRY(launch_heap_scan(h->stream, h->t, luts, plan, k, nullptr, nullptr, heap_ws, c.d_distances, c.d_labels,
                                      c.fmask));
         }
-        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots", "heap_scan_kernel+tags", "heap_scan_kernel+values"));
+        remember_plan(h, c.nq, c.max_seg, false, c.fmask.name("heap_scan_kernel", "heap_scan_kernel+filter", "heap_scan_kernel+slots", "heap_scan_kernel+tags", "heap_scan_kernel+values", "heap_scan_kernel+tags+values"));
         return IVFHNSW_OK;
     }
     if (heap) {
@@ -737,7 +747,7 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     int rc = bind(h);
     if (rc || (rc = search_args_guard(h, p, k)))
         return rc;
-    const char *who = pick.who("search_slots", "search_tags", "search_values");
+    const char *who = pick.who("search_slots", "search_tags", "search_values", "search_tags_values");
     if (pick && (rc = slots_call_guard(h, who, pick.kind())))
         return rc;
     if (nq == 0)
@@ -752,8 +762,8 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     const size_t in_s = pick.bytes(nq);
     // Small batches -- the reference's drivers pass ONE query per call (tests/test_ivfhnsw_sift1b.cpp:193-208) -- go
     // through pinned host memory the kernels read and write directly: no staging copies, one synchronisation.  Layout
-    // of the two blocks: in = queries | coarse ids | coarse dists | the pick's array, at the next multiple of 8 (a _values
-    // call's pairs are 8-byte aligned wherever they come from); out = distances | labels | status word.
+    // of the two blocks: in = queries | coarse ids | coarse dists | the pick's arrays, at the next multiple of 8 (a _values
+    // call's pairs are 8-byte aligned wherever they come from; a _tags_values call's tags follow its pairs); out = distances | labels | status word.
     static const size_t pinned_max_nq = env_size("IVFHNSW_PINNED_MAX_NQ", 256);
     if (nq <= pinned_max_nq) {
         const size_t out_d = (nq * k * sizeof(float) + 7) & ~(size_t)7, out_l = nq * k * sizeof(int64_t);
@@ -766,8 +776,10 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
             memcpy(pin + in_q, coarse_ids, in_c);
             memcpy(pin + in_q + in_c, coarse_dists, in_c);
         }
-        if (pick)
-            memcpy(pin + at_s, pick.data(), in_s);
+        pick.each_array(nq, [&](const void *src, size_t at, size_t bytes) {
+            memcpy(pin + at_s + at, src, bytes);
+            return 0;
+        });
         uint32_t *pst = reinterpret_cast<uint32_t *>(pout + out_d + out_l);
         uint32_t *bits = &status_words(h)->bits;
         // The latency walk keeps at most 64 exact ties at the efSearch boundary.  This call synchronises anyway, so instead
@@ -780,7 +792,7 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
                                   coarse_ids ? reinterpret_cast<const uint32_t *>(pin + in_q) : nullptr,
                                   coarse_ids ? reinterpret_cast<const float *>(pin + in_q + in_c) : nullptr, p,
                                   reinterpret_cast<float *>(pout), reinterpret_cast<int64_t *>(pout + out_d), nullptr,
-                                  pick.at(pin + at_s)},
+                                  pick.at(pin + at_s, nq)},
                                  call);
             if (rc)
                 return rc;
@@ -801,9 +813,9 @@ static int search_host(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries
     if ((rc = h->s_dist.ensure(nq * k * sizeof(float))) || (rc = h->s_lab.ensure(nq * k * sizeof(int64_t))) ||
         (rc = stage_in(h, h->s_q, queries, in_q)) ||
         (coarse_ids && ((rc = stage_in(h, h->s_cid, coarse_ids, in_c)) || (rc = stage_in(h, h->s_cd, coarse_dists, in_c)))) ||
-        (pick && (rc = stage_in(h, h->fs_qslots, pick.data(), in_s))) ||
+        (pick && (rc = pick_stage_in(h, pick, nq))) ||
         (rc = search_pick_dev(h, nq, k, h->s_q.as<float>(), coarse_ids ? h->s_cid.as<uint32_t>() : nullptr,
-                              coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p), h->s_dist.as<float>(),
+                              coarse_ids ? h->s_cd.as<float>() : nullptr, p, pick.at(h->fs_qslots.p, nq), h->s_dist.as<float>(),
                               h->s_lab.as<int64_t>(), nullptr)) ||
         (rc = stage_out(h, distances, h->s_dist, nq * k * sizeof(float))) ||
         (rc = stage_out(h, labels, h->s_lab, nq * k * sizeof(int64_t))))
@@ -837,6 +849,13 @@ int ivfhnsw_gpu_search_values(ivfhnsw_gpu *h, size_t nq, size_t k, const float *
                               float *distances, int64_t *labels)
 {
     return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, nullptr, query_ranges}, distances, labels);
+}
+
+int ivfhnsw_gpu_search_tags_values(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,
+                                   const float *coarse_dists, const ivfhnsw_search_params *p, const uint16_t *query_tags,
+                                   const uint32_t *query_ranges, float *distances, int64_t *labels)
+{
+    return search_host(h, nq, k, queries, coarse_ids, coarse_dists, p, QueryPick{nullptr, query_tags, query_ranges}, distances, labels);
 }
 
 int ivfhnsw_gpu_search_keys(ivfhnsw_gpu *h, size_t nq, size_t k, const float *queries, const uint32_t *coarse_ids,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "scan_dispatch.h"
+#include "tag_value_math.h"
 #include "value_math.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -520,6 +521,10 @@ __device__ __forceinline__ const uint32_t *filter_mask(const uint32_t *m) { retu
 struct FilterFill {
     uint32_t keep = ~0u, all = 0u;
     uint32_t span = 0u, live = 0u; // the fifth form only (ValueMask below): all = lo, span = hi - lo, live = ~0 iff lo <= hi
+    // the sixth form only (TagValueMask below): the value side as in the fifth, and beside it the row tags, the keep
+    // of their index and the scalar a row's tag is compared with
+    const uint16_t *rtags = nullptr;
+    uint32_t tkeep = 0u, tag = 0u;
 };
 template <class T> struct is_slot_mask : std::false_type {};
 template <> struct is_slot_mask<SlotMask> : std::true_type {};
@@ -527,14 +532,23 @@ template <class T> struct is_tag_mask : std::false_type {};
 template <> struct is_tag_mask<TagMask> : std::true_type {};
 template <class T> struct is_value_mask : std::false_type {};
 template <> struct is_value_mask<ValueMask> : std::true_type {};
+template <class T> struct is_tag_value_mask : std::false_type {};
+template <> struct is_tag_value_mask<TagValueMask> : std::true_type {};
 // 0 = no filter, 1 = one mask, 2 = a plane per query, 3 = a 16-bit tag per row and per query, 4 = a uint32 value per row
-// and an interval per query
+// and an interval per query, 5 = both of these
 template <class... Mask>
-constexpr int filter_kind = sizeof...(Mask) == 0                     ? 0
-                            : (is_value_mask<Mask>::value || ...) ? 4
-                            : (is_tag_mask<Mask>::value || ...)   ? 3
-                            : (is_slot_mask<Mask>::value || ...)  ? 2
-                                                                  : 1;
+constexpr int filter_kind = sizeof...(Mask) == 0                         ? 0
+                            : (is_tag_value_mask<Mask>::value || ...) ? 5
+                            : (is_value_mask<Mask>::value || ...)     ? 4
+                            : (is_tag_mask<Mask>::value || ...)       ? 3
+                            : (is_slot_mask<Mask>::value || ...)      ? 2
+                                                                      : 1;
+// What a kernel carries per row from its load loop (load_norm_filter) to filter_pass: one word, and under kind 5 two --
+// the row's tag (zero-extended) and its value.  Kinds 0 to 4 keep the bare uint32_t they always had.
+struct TagValueWord {
+    uint32_t t, v;
+};
+template <int KIND> using FilterWord = std::conditional_t<KIND == 5, TagValueWord, uint32_t>;
 
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &) { return nullptr; }
 __device__ __forceinline__ const uint32_t *filter_mask(int, FilterFill &, const uint32_t *m) { return m; }
@@ -577,6 +591,27 @@ __device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, 
     fill.span = f.span;
     fill.live = f.live;
     return rows ? m.row_values : m.query_ranges;
+}
+// The sixth form (TagValueMask, scan_dispatch.h): the fourth AND the fifth.  A lane loads the row's tag
+// and the row's value beside the norm code (load_norm_filter<5>: the returned pointer is the row values', fill.rtags the
+// row tags').  The query's tag and pair go through readfirstlane, and tag_value_fill (tag_value_math.h) turns them into
+// the scalars of filter_pass<5>.  Either row array may be missing; its keep = 0 then makes every lane read element 0 of
+// the matching query array (readable, and ignored), exactly as the two forms above do it.
+__device__ __forceinline__ const uint32_t *filter_mask(int q, FilterFill &fill, const TagValueMask &m)
+{
+    const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)m.query_tags[q]);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(m.query_ranges[2 * (size_t)q]);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(m.query_ranges[2 * (size_t)q + 1]);
+    const bool trows = m.row_tags != nullptr, vrows = m.row_values != nullptr;
+    const TagValueFill f = tag_value_fill(t, lo, hi, trows, vrows);
+    fill.rtags = trows ? m.row_tags : m.query_tags;
+    fill.tkeep = f.tkeep;
+    fill.tag = f.tag;
+    fill.keep = f.value.keep;
+    fill.all = f.value.lo;
+    fill.span = f.value.span;
+    fill.live = f.value.live;
+    return vrows ? m.row_values : m.query_ranges;
 }
 
 } // namespace ivfhnsw_gpu_impl

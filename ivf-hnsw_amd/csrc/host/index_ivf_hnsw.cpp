@@ -155,7 +155,7 @@ void install_id_values(const void *ix, ivfhnsw_gpu *h)
         gpu_fail("ivfhnsw_gpu_set_values");
 }
 
-// what search_batch (heap_order 1) and range_search (0) ask of the device, for the _slots, _tags and _values forms alike
+// what search_batch (heap_order 1) and range_search (0) ask of the device, for the _slots, _tags, _values and _tags_values forms alike
 ivfhnsw_search_params per_query_params(const IndexIVF_HNSW *ix, int heap_order)
 {
     const IndexIVF_HNSW_Grouping *grouping = dynamic_cast<const IndexIVF_HNSW_Grouping *>(ix);
@@ -392,6 +392,33 @@ void IndexIVF_HNSW::range_search_values(size_t nq, const float *x, const uint32_
     if (ivfhnsw_gpu_range_search_values(gpu_, nq, x, nullptr, nullptr, &p, ranges, radius,
                                         reinterpret_cast<uint64_t *>(lims.data()), &total))
         gpu_fail("ivfhnsw_gpu_range_search_values");
+    fetch_range_results(gpu_, total, distances, labels);
+}
+
+void IndexIVF_HNSW::search_batch_tags_values(size_t nq, size_t k, const float *x, const uint16_t *tags, const uint32_t *ranges,
+                                             float *distances, long *labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::search_batch_tags_values: IVFHNSW_SHARDS > 1, and sharded handles have no row tags or values");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 1); // heap order, as search_batch
+    if (ivfhnsw_gpu_search_tags_values(gpu_, nq, k, x, nullptr, nullptr, &p, tags, ranges, distances,
+                                       reinterpret_cast<int64_t *>(labels)))
+        gpu_fail("ivfhnsw_gpu_search_tags_values");
+}
+
+void IndexIVF_HNSW::range_search_tags_values(size_t nq, const float *x, const uint16_t *tags, const uint32_t *ranges, float radius,
+                                             std::vector<size_t> &lims, std::vector<float> &distances, std::vector<long> &labels)
+{
+    if (shards_wanted() > 1)
+        throw std::runtime_error("IndexIVF_HNSW::range_search_tags_values: IVFHNSW_SHARDS > 1, and sharded handles have no range search");
+    ensure_device();
+    const ivfhnsw_search_params p = per_query_params(this, 0);
+    lims.assign(nq + 1, 0);
+    uint64_t total = 0;
+    if (ivfhnsw_gpu_range_search_tags_values(gpu_, nq, x, nullptr, nullptr, &p, tags, ranges, radius,
+                                             reinterpret_cast<uint64_t *>(lims.data()), &total))
+        gpu_fail("ivfhnsw_gpu_range_search_tags_values");
     fetch_range_results(gpu_, total, distances, labels);
 }
 

@@ -519,6 +519,10 @@ hipError_t launch_values_gather(hipStream_t s, const uint32_t *ids, uint64_t n_l
                                 uint32_t *row_values);
 hipError_t launch_values_count(hipStream_t s, const uint32_t *row_values, uint64_t n_local, uint32_t lo, uint32_t hi,
                                unsigned long long *count);
+// Tag AND value: *count (zeroed here) = rows whose tag passes `tag` (0xffff: every row) and whose value
+// lies in [lo, hi].  A null row array: every row untagged / without a value.
+hipError_t launch_tag_values_count(hipStream_t s, const uint16_t *row_tags, const uint32_t *row_values, uint64_t n_local,
+                                   uint32_t tag, uint32_t lo, uint32_t hi, unsigned long long *count);
 // additions to a Grouping index (kernels_add_groups.hip): its codes go in with the append launchers above.
 // add_groups: *status (0xffffffff before) = the lowest g whose list holds codes; list_idx[p] = cidx[group of point p];
 // the table rows of G groups (nn always; alpha and the inter-centroid row -- inter_src, or computed when it is null --

@@ -230,6 +230,38 @@ __global__ __launch_bounds__(256) void values_count_kernel(const uint32_t *__res
     }
 }
 
+// *count += rows the conjunction of DESIGN.md 3.26 passes (tag_value_math.h), built as values_count_kernel is.  Either row
+// array may be null: the lanes then read nothing of it and every row counts as untagged / without a value.
+__global__ __launch_bounds__(256) void tag_values_count_kernel(const uint16_t *__restrict__ row_tags,
+                                                               const uint32_t *__restrict__ row_values, uint64_t n_local,
+                                                               uint32_t tag, uint32_t lo, uint32_t hi,
+                                                               unsigned long long *__restrict__ count)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const TagValueFill f = tag_value_fill(tag, lo, hi, row_tags != nullptr, row_values != nullptr);
+    uint32_t c = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 256; r0 < n_local; r0 += stride) { // workgroup-uniform bound: every lane ballots
+        const uint64_t r = r0 + threadIdx.x;
+        bool hit = false;
+        if (r < n_local) {
+            const uint32_t wt = row_tags ? (uint32_t)row_tags[r] : 0u; // without the array the word is ignored: f.tag has bit 16 set or is the wildcard
+            const uint32_t wv = row_values ? row_values[r] : 0u;       // ... and f.value.keep = 0 makes it 0xffffffff
+            hit = tag_value_pass(wt, wv, f);
+        }
+        c += (uint32_t)__popcll(__ballot(hit));
+    }
+    if (lane == 0)
+        s_cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (t)
+            atomicAdd(count, (unsigned long long)t);
+    }
+}
+
 } // namespace
 
 static unsigned tags_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
@@ -297,6 +329,18 @@ hipError_t launch_values_count(hipStream_t s, const uint32_t *row_values, uint64
     if (n_local == 0)
         return hipSuccess;
     hipLaunchKernelGGL(values_count_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, row_values, n_local, lo, hi, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_tag_values_count(hipStream_t s, const uint16_t *row_tags, const uint32_t *row_values, uint64_t n_local,
+                                   uint32_t tag, uint32_t lo, uint32_t hi, unsigned long long *count)
+{
+    if (hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), s); e != hipSuccess)
+        return e;
+    if (n_local == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(tag_values_count_kernel, dim3(tags_grid(n_local)), dim3(256), 0, s, row_tags, row_values, n_local, tag, lo,
+                       hi, count);
     return hipGetLastError();
 }
 

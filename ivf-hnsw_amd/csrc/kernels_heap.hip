@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(IvfTables t, const float
                 const float root = val[0]; // the heap is at rest here (barrier behind the last replay)
                 CodeRegs<CS> w[HS_U];
                 uint32_t nbv[HS_U], vp[HS_U];
-                [[maybe_unused]] uint32_t fw[HS_U], fb[HS_U];
+                [[maybe_unused]] FilterWord<FK> fw[HS_U];
+                [[maybe_unused]] uint32_t fb[HS_U];
                 float ct[HS_U], dn[HS_U];
                 bool ok[HS_U], pass[HS_U];
 #pragma unroll

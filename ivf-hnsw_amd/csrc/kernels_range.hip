@@ -149,7 +149,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_kernel(const uint8_t *_
         for (uint32_t base = b0; base < b1; base += RG_THREADS * U) {
             CodeRegs<CS> w[U];
             uint32_t nb[U], gi[U];
-            [[maybe_unused]] uint32_t fw[U];
+            [[maybe_unused]] FilterWord<FK> fw[U];
             float ct[U], dv[U];
             bool ok[U], hit[U];
 #pragma unroll
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_scan_bitmap_kernel(const uin
             for (uint32_t rbase = (b0 - cl) & ~63u; rbase < b1 - cl; rbase += RG_THREADS * U) {
                 CodeRegs<CS> w[U];
                 uint32_t nb[U], gi[U];
-                [[maybe_unused]] uint32_t fw[U];
+                [[maybe_unused]] FilterWord<FK> fw[U];
                 float ct[U], dv[U];
                 bool ok[U], hit[U];
 #pragma unroll
@@ -319,7 +319,7 @@ hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, co
             if constexpr (CS > 0) {
                 // plans of short segments (Grouping sub-groups): the bitmap form; whole lists: the position form
                 if (seg_len_hint > 0 && seg_len_hint <= 48) {
-                    *name = fmask.name("range_scan_bitmap_kernel", "range_scan_bitmap_kernel+filter", "range_scan_bitmap_kernel+slots", "range_scan_bitmap_kernel+tags", "range_scan_bitmap_kernel+values");
+                    *name = fmask.name("range_scan_bitmap_kernel", "range_scan_bitmap_kernel+filter", "range_scan_bitmap_kernel+slots", "range_scan_bitmap_kernel+tags", "range_scan_bitmap_kernel+values", "range_scan_bitmap_kernel+tags+values");
                     hipLaunchKernelGGL((range_scan_bitmap_kernel<CS, 4, FILL, decltype(m)...>), grid, block, 0, s, t.codes,
                                        t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, radius, slices,
                                        out, m...);
@@ -331,9 +331,9 @@ hipError_t range_launch(hipStream_t s, const IvfTables &t, const float *luts, co
             size_t shm;
             if (hipError_t e = scan_table_lds<CS, kern>(t.M, &shm); e != hipSuccess)
                 return e;
-            *name = CS > 0 ? fmask.name("range_scan_kernel", "range_scan_kernel+filter", "range_scan_kernel+slots", "range_scan_kernel+tags", "range_scan_kernel+values")
+            *name = CS > 0 ? fmask.name("range_scan_kernel", "range_scan_kernel+filter", "range_scan_kernel+slots", "range_scan_kernel+tags", "range_scan_kernel+values", "range_scan_kernel+tags+values")
                            : fmask.name("range_scan_kernel (run-time code size)", "range_scan_kernel (run-time code size)+filter",
-                                        "range_scan_kernel (run-time code size)+slots", "range_scan_kernel (run-time code size)+tags", "range_scan_kernel (run-time code size)+values");
+                                        "range_scan_kernel (run-time code size)+slots", "range_scan_kernel (run-time code size)+tags", "range_scan_kernel (run-time code size)+values", "range_scan_kernel (run-time code size)+tags+values");
             hipLaunchKernelGGL(kern, grid, block, shm, s, t.codes, t.norm_codes, luts, t.norm_table, p.segs, p.lpos, p.hdr,
                                p.max_seg, nsplit, t.M, radius, slices, out, m...);
             return hipGetLastError();

@@ -378,7 +378,8 @@ __global__ __launch_bounds__(THREADS) void scan_k1_kernel(const uint8_t *__restr
         for (uint32_t base = b0; base < b1; base += THREADS * U) {
             CodeRegs<CS> w[U];
             uint32_t nb[U], vp[U];
-            [[maybe_unused]] uint32_t fw[U], fb[U];
+            [[maybe_unused]] FilterWord<FK> fw[U];
+            [[maybe_unused]] uint32_t fb[U];
             float ct[U];
             bool ok[U];
 #pragma unroll
@@ -492,7 +493,8 @@ __global__ __launch_bounds__(256) void scan_k1_bitmap_kernel(const uint8_t *__re
             for (uint32_t rbase = (b0 - cl) & ~63u; rbase < b1 - cl; rbase += 256 * U) {
                 CodeRegs<CS> w[U];
                 uint32_t nb[U], vp[U];
-                [[maybe_unused]] uint32_t fw[U], fb[U];
+                [[maybe_unused]] FilterWord<FK> fw[U];
+                [[maybe_unused]] uint32_t fb[U];
                 float ct[U];
                 bool ok[U];
 #pragma unroll
@@ -568,7 +570,7 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
     if (p.nq == 0)
         return hipSuccess;
     if (k != 1) {
-        *kernel_name = fmask.name("scan_topk_kernel", "scan_topk_kernel+filter", "scan_topk_kernel+slots", "scan_topk_kernel+tags", "scan_topk_kernel+values");
+        *kernel_name = fmask.name("scan_topk_kernel", "scan_topk_kernel+filter", "scan_topk_kernel+slots", "scan_topk_kernel+tags", "scan_topk_kernel+values", "scan_topk_kernel+tags+values");
         return launch_scan_topk(s, t, luts, p, k, keys, out, fmask);
     }
     // several workgroups per query meet in an atomic: nobody knows the winner
@@ -593,17 +595,17 @@ hipError_t launch_scan(hipStream_t s, const IvfTables &t, const float *luts, con
             if constexpr (CS == 0) {
                 // any other multiple of 4 (IndexIVF_HNSW.cpp:805): the run-time form, table in dynamic LDS, keys only
                 *kernel_name = fmask.name("scan_k1_kernel (run-time code size)", "scan_k1_kernel (run-time code size)+filter",
-                                          "scan_k1_kernel (run-time code size)+slots", "scan_k1_kernel (run-time code size)+tags", "scan_k1_kernel (run-time code size)+values");
+                                          "scan_k1_kernel (run-time code size)+slots", "scan_k1_kernel (run-time code size)+tags", "scan_k1_kernel (run-time code size)+values", "scan_k1_kernel (run-time code size)+tags+values");
                 return position(int_c<256>(), int_c<2>(), SelOut{nullptr, nullptr, nullptr});
             } else if (seg_len_hint > 0 && seg_len_hint <= 48) {
                 // plans of short segments (Grouping sub-groups, ~16 codes): the bitmap form; whole lists: the position form
-                *kernel_name = fmask.name("scan_k1_bitmap_kernel", "scan_k1_bitmap_kernel+filter", "scan_k1_bitmap_kernel+slots", "scan_k1_bitmap_kernel+tags", "scan_k1_bitmap_kernel+values");
+                *kernel_name = fmask.name("scan_k1_bitmap_kernel", "scan_k1_bitmap_kernel+filter", "scan_k1_bitmap_kernel+slots", "scan_k1_bitmap_kernel+tags", "scan_k1_bitmap_kernel+values", "scan_k1_bitmap_kernel+tags+values");
                 hipLaunchKernelGGL((scan_k1_bitmap_kernel<CS, 4, decltype(m)...>), grid, block, 0, s, t.codes, t.norm_codes, luts,
                                    t.norm_table, p.segs, p.lpos, p.hdr, p.max_seg, nsplit, k64, so, m...);
                 *did_select = so.ids != nullptr;
                 return hipGetLastError();
             } else {
-                *kernel_name = fmask.name("scan_k1_kernel", "scan_k1_kernel+filter", "scan_k1_kernel+slots", "scan_k1_kernel+tags", "scan_k1_kernel+values");
+                *kernel_name = fmask.name("scan_k1_kernel", "scan_k1_kernel+filter", "scan_k1_kernel+slots", "scan_k1_kernel+tags", "scan_k1_kernel+values", "scan_k1_kernel+tags+values");
                 if (p.max_seg <= 64)
                     return position(int_c<64>(), int_c<4>(), so);
                 // nprobe 65..256 (the DEEP1B preset probes 128 lists): a 5 KB plan instead of 20 KB keeps 7 workgroups

@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const uint8_t *__restric
             bool pass[TK_U];
             CodeRegs<CS> w[TK_U];
             uint32_t nbv[TK_U], vp[TK_U];
-            [[maybe_unused]] uint32_t fw[TK_U], fb[TK_U];
+            [[maybe_unused]] FilterWord<FK> fw[TK_U];
+            [[maybe_unused]] uint32_t fb[TK_U];
             float ct[TK_U];
             bool ok[TK_U];
 #pragma unroll

@@ -1,8 +1,8 @@
 // How a scan launcher turns two run-time facts -- the code size and how the call is filtered (not at all, by the handle's
-// label filter, by a filter slot per query, by a row tag per query, by a value interval per query) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
+// label filter, by a filter slot per query, by a row tag per query, by a value interval per query, by both) -- into the template arguments of its kernel.  No HIP in here: tests/cpp/dispatch_tool.cpp checks it on the host.
 //
 //     by_code_size<4, 8, 16, 32>(t.M, [&](auto cs) {          // decltype(cs)::value: 4, 8, 16, 32, or 0 = run-time form
-//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, a SlotMask, a TagMask or a ValueMask
+//         return with_mask(fmask, [&](auto... m) {            // m: nothing, the mask, a SlotMask, a TagMask, a ValueMask or a TagValueMask
 //             launch kernel<decltype(cs)::value, ..., decltype(m)...> with the arguments (..., m...)
 //         });
 //     });
@@ -65,24 +65,38 @@ struct ValueMask {
     const uint32_t *query_ranges;
 };
 
+// The sixth form: the fourth AND the fifth.  A row passes query q iff its tag passes query_tags[q] as
+// under a TagMask and its value passes the pair at query_ranges[2q] as under a ValueMask (tag_value_math.h).  Either row
+// array may be null (the handle lacks that table: every row reads as 0xffff / 0xffffffff); both query arrays are given.
+struct TagValueMask {
+    const uint16_t *row_tags;
+    const uint32_t *row_values;
+    const uint16_t *query_tags;
+    const uint32_t *query_ranges;
+};
+
 // What a scan launcher is told about the filter of its call: nothing, the pass mask of the handle's filter, filter
-// slots per query (slots.slots non-null), a tag per query (tags.query_tags non-null) or an interval per query
-// (values.query_ranges non-null).  A bare mask pointer converts, so a caller with one filter passes it as before.
+// slots per query (slots.slots non-null), a tag per query (tags.query_tags non-null), an interval per query
+// (values.query_ranges non-null) or both (tag_values.query_tags non-null).  A bare mask pointer converts, so a caller
+// with one filter passes it as before.
 struct ScanFilter {
     const uint32_t *fmask = nullptr;
     SlotMask slots{nullptr, 0, 0, nullptr};
     TagMask tags{nullptr, nullptr};
     ValueMask values{nullptr, nullptr};
+    TagValueMask tag_values{nullptr, nullptr, nullptr, nullptr};
     ScanFilter() = default;
     ScanFilter(const uint32_t *m) : fmask(m) {}
     ScanFilter(std::nullptr_t) {}
     ScanFilter(const SlotMask &s) : slots(s) {}
     ScanFilter(const TagMask &t) : tags(t) {}
     ScanFilter(const ValueMask &v) : values(v) {}
+    ScanFilter(const TagValueMask &tv) : tag_values(tv) {}
     bool by_slot() const { return slots.slots != nullptr; }
     bool by_tag() const { return tags.query_tags != nullptr; }
     bool by_value() const { return values.query_ranges != nullptr; }
-    bool any() const { return fmask || by_slot() || by_tag() || by_value(); }
+    bool by_tag_value() const { return tag_values.query_tags != nullptr; }
+    bool any() const { return fmask || by_slot() || by_tag() || by_value() || by_tag_value(); }
     // the name a launcher reports: the plain kernel's, "+filter", "+slots" or "+tags" behind it
     const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged) const
     {
@@ -92,6 +106,12 @@ struct ScanFilter {
     const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged, const char *valued) const
     {
         return by_value() ? valued : name(plain, filtered, slotted, tagged);
+    }
+    // ... and a tag-and-value form: "+tags+values" behind it
+    const char *name(const char *plain, const char *filtered, const char *slotted, const char *tagged, const char *valued,
+                     const char *tag_valued) const
+    {
+        return by_tag_value() ? tag_valued : name(plain, filtered, slotted, tagged, valued);
     }
     // the queries [q0, ...) of the same call
     ScanFilter from(size_t q0) const
@@ -103,14 +123,23 @@ struct ScanFilter {
             r.tags.query_tags += q0;
         if (r.by_value())
             r.values.query_ranges += 2 * q0;
+        if (r.by_tag_value()) {
+            r.tag_values.query_tags += q0;
+            r.tag_values.query_ranges += 2 * q0;
+        }
         return r;
     }
 };
 
-// f(values) with an interval per query, f(tags) with a tag per query, f(slots) with filter slots, else as above
+// f(tag_values) with a tag and an interval per query, f(values) with an interval per query, f(tags) with a tag per query,
+// f(slots) with filter slots, else as above
 template <class F> auto with_mask(const ScanFilter &flt, F &&f)
 {
-    return flt.by_value() ? f(flt.values) : flt.by_tag() ? f(flt.tags) : flt.by_slot() ? f(flt.slots) : with_mask(flt.fmask, f);
+    return flt.by_tag_value() ? f(flt.tag_values)
+           : flt.by_value()   ? f(flt.values)
+           : flt.by_tag()     ? f(flt.tags)
+           : flt.by_slot()    ? f(flt.slots)
+                              : with_mask(flt.fmask, f);
 }
 
 } // namespace ivfhnsw_gpu_impl

@@ -50,10 +50,12 @@ template <int CS> __device__ __forceinline__ float code_sum_lds(const float *s_l
 // whatever the row, so that no branch stands here; nothing is done to the loaded word before filter_pass, because a use
 // of it here makes the compiler wait for each unrolled step's loads before it issues the next step's.  Under row tags (3,
 // DESIGN.md 3.21) the word is the row's tag and a handle without tags (keep = 0) reads element 0 the same way.  Under row
-// values (4) it is the row's uint32, read the same way.
+// values (4) it is the row's uint32, read the same way.  Under tag AND value (5) a row
+// brings both, so the word a kernel carries from its load loop to filter_pass is a pair there (FilterWord) and a bare
+// uint32_t in every other kind; the values come from fmask, the tags from fill.rtags, each masked by its own keep.
 template <int KIND>
 __device__ __forceinline__ void load_norm_filter(const uint8_t *norm_codes, const uint32_t *fmask, uint32_t row, uint32_t &nb,
-                                                 uint32_t &fw, [[maybe_unused]] const FilterFill &fill = FilterFill())
+                                                 FilterWord<KIND> &fw, [[maybe_unused]] const FilterFill &fill = FilterFill())
 {
     nb = norm_codes[row];
     if constexpr (KIND == 1)
@@ -64,6 +66,10 @@ __device__ __forceinline__ void load_norm_filter(const uint8_t *norm_codes, cons
         fw = reinterpret_cast<const uint16_t *>(fmask)[row & fill.keep];
     if constexpr (KIND == 4) // the row's value: one dword, the 64 lanes of a wavefront read 256 contiguous bytes
         fw = fmask[value_index(row, fill.keep)];
+    if constexpr (KIND == 5) { // both: 128 + 256 contiguous bytes per wavefront, issued side by side
+        fw.t = fill.rtags[tag_index(row, fill.tkeep)];
+        fw.v = fmask[value_index(row, fill.keep)];
+    }
 }
 // fb = row & 31: the row's bit in that word
 __device__ __forceinline__ bool filter_pass(uint32_t fw, uint32_t fb) { return (fw >> fb) & 1u; }
@@ -77,6 +83,12 @@ template <int KIND> __device__ __forceinline__ bool filter_pass(uint32_t fw, uin
     if constexpr (KIND == 4) // a value per row: inside the query's interval (value_math.h); no branch
         return value_pass(fw, fill.keep, fill.all, fill.span, fill.live);
     return (fw >> fb) & 1u;
+}
+// ... and under tag AND value (5) with the row's pair of words: the AND of the two rules above (tag_value_math.h); no branch
+template <int KIND> __device__ __forceinline__ bool filter_pass(const TagValueWord &fw, uint32_t, const FilterFill &fill)
+{
+    static_assert(KIND == 5, "a pair of words is the sixth form's");
+    return tag_value_pass(fw.t, fw.v, fill.tag, fill.keep, fill.all, fill.span, fill.live);
 }
 
 // The table of query q into LDS, global -> LDS directly (global_load_lds_dwordx4: wave-uniform LDS base + lane * 16): the

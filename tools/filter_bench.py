@@ -36,10 +36,22 @@ tag r % 1024 and value r % 1024: value = tag, so both forms pass the same rows):
      interval's queries, for a sample of --loop-tags intervals, wall ms per interval.
  10. set_values_dev of 10 M labels (wall ms), and a 10 M-code append_ivf_dev with and without the value table (wall ms,
      each twice: what the append costs beyond the plain one is the gather).
+With --tags-values, tag AND value (ivfhnsw_gpu_search_tags_values), on the same corpus and ONE handle
+that holds both tables (row r carries tag r % 1024 and value r % 1024, so (t, (t, t)), (t, FULL) and (NONE, (t, t)) pass the
+same rows):
+ 11. --reps (>= 5) alternating repetitions of: (a) unfiltered; (b) _tags with 1 024 tags; (c) _values with the 1 024
+     points (t, t); the new call with (d) (t, (t, t)), (e) (t, FULL), (f) (NONE, (t, t)) -- the same rows as (b) and (c), and
+     the answers must compare equal; (h) the new call, every query (NONE, FULL), which must answer as (a).  Then, with the
+     columns made independent (tag r % 8, value (r // 8) % 1024): (a), _tags over the 8 tags, _values over intervals of 128
+     consecutive values, and (g) the new call over the pairs of both, about 1/8 x 1/8 of the rows.  Step and scan time as
+     in 3.
+ 12. the loop (g) replaces: per distinct pair set_filter_dev(rows tagged t whose value lies in the interval) + search_dev of
+     that pair's queries, for a sample of --loop-tags pairs, wall ms per pair, extrapolated to all pairs of the batch.
 usage: python tools/filter_bench.py [--workload NAME] [--sizes 1000,10000000,500000000] [--fractions 0.5,0.1,0.01]
        python tools/filter_bench.py --slots [--reps 5] [--append 10000000]
        python tools/filter_bench.py --tags [--reps 5] [--append 10000000] [--loop-tags 8]
-       python tools/filter_bench.py --values [--reps 5] [--append 10000000] [--loop-tags 8]"""
+       python tools/filter_bench.py --values [--reps 5] [--append 10000000] [--loop-tags 8]
+       python tools/filter_bench.py --tags-values [--reps 5] [--loop-tags 8]"""
 import argparse
 import json
 import os
@@ -464,6 +476,142 @@ def values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out):
     out["append"] = appends
 
 
+def tags_values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out):
+    """Two installs on one handle.  First row r carries tag r % 1024 and value r % 1024, so that the tag t, the point
+    (t, t) and their conjunction pass the same rows and the five filtered forms must give the same answers.  Then the two
+    columns are made independent -- tag r % 8 (eight tenants), value (r // 8) % 1024 (a clock that ticks once per eight
+    rows) -- and each query carries one tenant and an interval of 128 consecutive values: about 1/8 x 1/8 of the rows."""
+    n = c.n_total
+    ids = torch.arange(n, device=dev, dtype=torch.int64)
+    lab = ids.to(torch.int32)
+    tg = (ids % 1024).to(torch.int16)
+    vl = (ids % 1024).to(torch.int32)
+    torch.cuda.synchronize(dev)  # the handle's stream is not torch's
+    mem0 = g.memory_bytes()
+    g.set_tags_dev(n, lab, tg)
+    g.set_values_dev(n, lab, vl)
+    out["memory_GB_tags_and_values"] = (g.memory_bytes() - mem0) / 1e9
+    assert g.tag_value_rows(5, 5, 5) == g.tag_rows(5) == g.value_rows(5, 5) == g.tag_value_rows(0xffff, 5, 5)
+    qi = torch.arange(nq, device=dev) % 1024
+    qtags = qi.to(torch.int16)
+    none = torch.full_like(qi, -1).to(torch.int16)  # 0xffff
+    points = torch.stack([qi, qi], 1).to(torch.int32).contiguous()
+    full = torch.stack([torch.zeros_like(qi), torch.full_like(qi, -1)], 1).to(torch.int32).contiguous()  # (0, 0xffffffff)
+    torch.cuda.synchronize(dev)
+
+    def step(form):
+        kind, t, r = form
+        if kind == "plain":
+            g.search_dev(nq, 1, q, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        elif kind == "tags":
+            g.search_tags_dev(nq, 1, q, t, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        elif kind == "values":
+            g.search_values_dev(nq, 1, q, r, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        else:
+            g.search_tags_values_dev(nq, 1, q, t, r, dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+
+    def measure(form, steps=10):
+        for _ in range(5):
+            step(form)
+        g.sync()
+        t = time.perf_counter()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        g.set_profiling(2)
+        g.reset_stage_ms()
+        for _ in range(steps):
+            step(form)
+        g.sync()
+        scan = g.stage_ms()["scan"][0] / steps
+        g.set_profiling(0)
+        return wall, scan, g.last_scan_kernel()
+
+    def run(forms):
+        runs = {name: {"step_ms": [], "scan_ms": []} for name, _ in forms}
+        for _ in range(max(5, args.reps)):
+            for name, form in forms:
+                wall, scan, kernel = measure(form)
+                runs[name]["step_ms"].append(wall)
+                runs[name]["scan_ms"].append(scan)
+                runs[name]["kernel"] = kernel
+        for name, r in runs.items():
+            for key in ("step_ms", "scan_ms"):
+                v = r[key]
+                r[key + "_min_mean_max"] = [min(v), sum(v) / len(v), max(v)]
+            log("[filter_bench] %-40s step %.4f (%.4f-%.4f) ms, scan %.4f (%.4f-%.4f) ms  (%s)" %
+                (name, r["step_ms_min_mean_max"][1], r["step_ms_min_mean_max"][0], r["step_ms_min_mean_max"][2],
+                 r["scan_ms_min_mean_max"][1], r["scan_ms_min_mean_max"][0], r["scan_ms_min_mean_max"][2], r["kernel"]))
+        return runs
+
+    same = [("a unfiltered", ("plain", None, None)), ("b tags, 1024 dealt", ("tags", qtags, None)),
+            ("c values, 1024 points", ("values", None, points)), ("d tags+values (t, (t, t))", ("both", qtags, points)),
+            ("e tags+values (t, FULL)", ("both", qtags, full)), ("f tags+values (NONE, (t, t))", ("both", none, points)),
+            ("h tags+values, all (NONE, FULL)", ("both", none, full))]
+    out["same_rows"] = run(same)
+    # the same rows pass (b) to (f): the same answers; (h) answers as (a)
+    answers = {}
+    for name, form in same:
+        step(form)
+        g.sync()
+        answers[name] = ll.clone()
+    out["same_rows_answers_equal"] = bool(all(torch.equal(answers["b tags, 1024 dealt"], answers[k]) for k in
+                                            ("c values, 1024 points", "d tags+values (t, (t, t))", "e tags+values (t, FULL)",
+                                             "f tags+values (NONE, (t, t))")))
+    out["none_full_equals_unfiltered"] = bool(torch.equal(answers["a unfiltered"], answers["h tags+values, all (NONE, FULL)"]))
+    assert out["same_rows_answers_equal"] and out["none_full_equals_unfiltered"], out
+
+    # (g) distinct tag and interval pairs of about 1/8 x 1/8: the columns made independent -- tag r % 8 (8 tenants),
+    # value (r // 8) % 1024 (a clock that ticks once per 8 rows), the interval 128 consecutive values
+    tg = (ids % 8).to(torch.int16)
+    vl = ((ids // 8) % 1024).to(torch.int32)
+    del ids
+    torch.cuda.synchronize(dev)
+    g.set_tags_dev(n, lab, tg)
+    g.set_values_dev(n, lab, vl)
+    del tg, vl
+    gtags = (qi % 8).to(torch.int16)
+    lo = (qi * 7) % 897  # 897 = 1024 - 127: every interval lies inside the values, and neighbours overlap
+    eighth = torch.stack([lo, lo + 127], 1).to(torch.int32).contiguous()
+    torch.cuda.synchronize(dev)
+    t0, lo0 = int(gtags[3]), int(lo[3])
+    assert abs(g.tag_value_rows(t0, lo0, lo0 + 127) - n / 64) < n / 640
+    out["eighth_eighth"] = run([("a unfiltered", ("plain", None, None)), ("b tags, 8 tenants", ("tags", gtags, None)),
+                                ("c values, 1/8 intervals", ("values", None, eighth)),
+                                ("g tags+values, 1/8 x 1/8 pairs", ("both", gtags, eighth))])
+
+    # 12. the loop one call replaces: a filter per distinct (tag, interval) pair
+    pairs = torch.unique(torch.cat([gtags.to(torch.int32).unsqueeze(1), eighth], 1), dim=0)
+    npairs = int(pairs.shape[0])
+    out["distinct_pairs"] = npairs
+    per_q = max(1, nq // npairs)
+    loop = []
+    for i in range(args.loop_tags):
+        t_, a, b_ = int(pairs[i, 0]), int(pairs[i, 1]), int(pairs[i, 2])
+        torch.cuda.synchronize(dev)
+        t = time.perf_counter()
+        r = torch.arange(n, device=dev, dtype=torch.int64)
+        v = (r // 8) % 1024
+        labs = r[(r % 8 == t_) & (v >= a) & (v <= b_)].to(torch.int32)  # the application's side: the labels of the pair
+        del r, v
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        g.set_filter_dev(labs.numel(), labs)
+        g.search_dev(per_q, 1, q[i * per_q:(i + 1) * per_q], dd, ll, c.nprobe, c.max_codes, efSearch=c.ef)
+        g.sync()
+        t2 = time.perf_counter()
+        loop.append({"labels_ms": (t1 - t) * 1e3, "set_filter_and_search_ms": (t2 - t1) * 1e3})
+        del labs
+    g.clear_filter()
+    out["loop_per_pair"] = loop
+    tail = [x["set_filter_and_search_ms"] for x in loop[1:]] or [loop[0]["set_filter_and_search_ms"]]  # the first call allocates
+    out["loop_ms_all_pairs_extrapolated"] = sum(tail) / len(tail) * npairs
+    log("[filter_bench] set_filter_dev + search_dev per pair: %s ms; x %d = %.0f ms against one search_tags_values step of %.3f ms"
+        % (", ".join("%.2f" % x["set_filter_and_search_ms"] for x in loop), npairs, out["loop_ms_all_pairs_extrapolated"],
+           out["eighth_eighth"]["g tags+values, 1/8 x 1/8 pairs"]["step_ms_min_mean_max"][1]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="synthetic-1B-pq16-nc993127-nprobe32")
@@ -472,6 +620,7 @@ def main():
     ap.add_argument("--slots", action="store_true")
     ap.add_argument("--tags", action="store_true")
     ap.add_argument("--values", action="store_true")
+    ap.add_argument("--tags-values", action="store_true")
     ap.add_argument("--loop-tags", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--append", type=int, default=10 ** 7)
@@ -522,6 +671,11 @@ def main():
         assert total == c.n_total and passing == (total - n if deny else n), (mode, passing, total, n)
         return ms, passing
 
+    if args.tags_values:
+        tags_values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out)
+        g.close()
+        print(json.dumps(out))
+        return
     if args.values:
         values_bench(args, pkg, torch, dev, c, g, q, dd, ll, nq, out)
         g.close()

@@ -339,6 +339,68 @@ def base_values_recall(pkg, seed=77, corpus=None, settings=SETTINGS, sample_only
             "values_of_rows": values}
 
 
+def tag_value_pairs(n):
+    """The sample pairs: (name of the pass fraction, tag, lo, hi)."""
+    iv = value_intervals(n)
+    eighths = [x for x in iv if x[0] == "1/8"]
+    small = [x for x in iv if x[0] == "~1/2000"]
+    out = [("1/64 (1/8 x 1/8)", t, lo, hi) for t in range(4) for _, lo, hi in eighths]
+    out += [("1/8 (tag, FULL)", t, 0, VALUE_NONE) for t in range(4)]
+    out += [("1/8 (NONE, interval)", TAG_NONE, lo, hi) for _, lo, hi in eighths]
+    out += [("~1/2040 (small tag, FULL)", t, 0, VALUE_NONE) for t in (4, 5, 100, 511, 1023)]
+    out += [("~1/2000 (NONE, small interval)", TAG_NONE, lo, hi) for _, lo, hi in small]
+    out.append(("1 (NONE, FULL)", TAG_NONE, 0, VALUE_NONE))
+    return out
+
+
+def tags_values_recall(pkg, seed=77, corpus=None, settings=SETTINGS):
+    """Recall of one search_tags_values call against the per-pair loop of set_base_filter + exact_search."""
+    if corpus is None:
+        import rerank_ref
+        corpus = rerank_ref.uint8_recall_corpus(pkg, seed=seed)
+    c = corpus
+    g = upload(pkg, c)
+    qf = c["queries"]
+    q8 = qf.astype(np.uint8)
+    nq, n = len(q8), len(c["base"])
+    tags = tag_assignment(n, seed)
+    values = np.random.default_rng(seed + 5).permutation(n).astype(np.uint32)  # the value of row (= id) i
+    g.set_tags(np.arange(n, dtype=np.uint32), tags)
+    g.set_values(np.arange(n, dtype=np.uint32), values)
+    sample = tag_value_pairs(n)
+    pick = np.arange(nq) % len(sample)
+    qt = np.array([sample[i][1] for i in pick], np.uint16)
+    qr = np.array([(sample[i][2], sample[i][3]) for i in pick], np.uint32)
+    truth = np.empty((nq, 10), np.int64)
+    passing = {}
+    for i, (name, t, lo, hi) in enumerate(sample):
+        mine = np.flatnonzero(pick == i)
+        if t == TAG_NONE and hi == VALUE_NONE:
+            g.clear_base_filter()
+            passing.setdefault(name, []).append(n)
+        else:
+            rows = np.flatnonzero(((tags == t) | (t == TAG_NONE)) & (values >= lo) & (values <= hi)).astype(np.uint32)
+            assert g.tag_value_rows(t, lo, hi) == rows.size
+            passing.setdefault(name, []).append(int(rows.size))
+            g.set_base_filter(rows)
+        truth[mine] = g.exact_search(q8[mine], 10)[1]
+    g.clear_base_filter()
+    rows_out = []
+    names = np.array([s_[0] for s_ in sample])
+    for nprobe, max_codes, ef in settings:
+        _, lab = g.search_tags_values(qf, 10, qt, qr, nprobe, max_codes, efSearch=ef)
+        assert g.last_scan_kernel().endswith("+tags+values")
+        for name in dict.fromkeys(names.tolist()):
+            idx = np.flatnonzero(names[pick] == name)
+            r1, r10 = recall_pair(lab[idx], truth[idx])
+            rows_out.append({"pass_fraction": name, "rows_passing_mean": float(np.mean(passing[name])), "queries": int(idx.size),
+                             "nprobe": nprobe, "max_codes": max_codes, "efSearch": ef, "recall_at_1": r1, "recall_at_10": r10})
+            log("[filter_recall] tags+values, %s (%d queries, %.0f rows pass), nprobe %d max_codes %d: Recall@1 %.4f, Recall@10 %.4f"
+                % (name, idx.size, np.mean(passing[name]), nprobe, max_codes, r1, r10))
+    g.close()
+    return {"rows": n, "nq": nq, "pairs": len(sample), "tags_values_recall": rows_out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=77)
@@ -349,6 +411,7 @@ def main():
     ap.add_argument("--values", action="store_true", help="one search_values call against the per-interval base-filter loop")
     ap.add_argument("--base-values", action="store_true", help="one search_values call against one exact_search_values call, "
                                                                 "every query an interval of its own")
+    ap.add_argument("--tags-values", action="store_true", help="one search_tags_values call against the per-pair base-filter loop")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -360,6 +423,9 @@ def main():
     elif args.base_values:
         out = base_values_recall(pkg, args.seed)
         out = {k: v for k, v in out.items() if k not in ("truth", "query_ranges", "values_of_rows")}
+        out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
+    elif args.tags_values:
+        out = tags_values_recall(pkg, args.seed)
         out["corpus"] = "uint8_recall_corpus(seed=%d)" % args.seed
     elif args.values:
         out = values_recall(pkg, args.seed)
