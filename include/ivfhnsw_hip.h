@@ -799,6 +799,31 @@ int ivfhnsw_gpu_upload_base(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
 int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const uint8_t *d_rows,
                                 size_t row_stride);
 
+/* The base store as float16: for float-valued corpora (DEEP1B: 96-d float; a billion rows are 192 GB as
+ * halves).  A handle holds ONE store, of one kind: allocating either kind (first == 0) releases the other, with whatever
+ * upload_base drops on reallocation (base filter, slots, tags, values).  Rows are float32, row_stride FLOATS apart
+ * (row_stride >= d; d + 1 takes an .fvecs file image as it is, `rows` pointing past the first record's 4-byte header); every
+ * value is rounded to half, round to nearest even, on the device, and beside the rows the store keeps one float32 per row,
+ * the squared norm of the rounded row (4 bytes per row).  first, count, n == 0, views, synchrony: as upload_base.  Needs
+ * d % 16 == 0, 16 <= d <= 256 and n < 2^32, else IVFHNSW_ERR_INVALID.  A chunk that holds a NaN or a value that does not
+ * round to a finite half (|v| >= 65520) is refused with IVFHNSW_ERR_INVALID before anything of it is written: the store --
+ * with first == 0 the previous one -- answers as before the call (a host chunk above 512 MB is therefore copied to the
+ * device twice, once to be checked and once to be stored; smaller chunks once).  A later chunk (first > 0) of the other kind of store ->
+ * IVFHNSW_ERR_STATE.  upload_base_f16_dev: rows in HBM, 4-byte aligned.
+ * ivfhnsw_gpu_rerank[_dev] serves whichever store the handle holds; against a float16 store its distance is
+ * fvec_L2sqr(q, float(x^)) bit for bit -- the unrounded float32 query, the stored half widened exactly, the eight
+ * accumulators and the order of utils.cpp:22-52.  On a float16 store every uint8 exact call (exact_search*,
+ * exact_range_search*) and every set_base_* installer returns IVFHNSW_ERR_STATE: it takes no filter of any kind.
+ * ivfhnsw_gpu_base_kind: what the handle (a view: its parent) holds. */
+#define IVFHNSW_BASE_NONE 0
+#define IVFHNSW_BASE_U8 1
+#define IVFHNSW_BASE_F16 2
+int ivfhnsw_gpu_upload_base_f16(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows,
+                                size_t row_stride);
+int ivfhnsw_gpu_upload_base_f16_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *d_rows,
+                                    size_t row_stride);
+int ivfhnsw_gpu_base_kind(const ivfhnsw_gpu *h);
+
 /* searchDisk's exact re-rank for nq queries (IndexIVF_HNSW_Grouping.cpp:365-395): d_cand[nq*kc] are labels a search
  * returned (-1 = empty), queries are unrotated (getL2Distance compares the raw query with the raw base row,
  * utils.cpp:98-137); writes the k best by (exact distance, label) ascending, [nq*k], padded with FLT_MAX / -1 when fewer
@@ -832,6 +857,28 @@ int ivfhnsw_gpu_exact_search(ivfhnsw_gpu *h, size_t nq, const uint8_t *queries, 
                              float *distances, int64_t *labels);
 int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t row_stride, size_t k,
                                  float *d_distances, int64_t *d_labels);
+
+/* The same question of a float16 store (upload_base_f16), on the f16 matrix cores.  Queries are float32, d
+ * each, row_stride FLOATS apart (d + 1 takes an .fvecs image), and are rounded to half as the rows were: q^, x^ below are
+ * the rounded vectors.  The value returned is
+ *     (|q^|^2 + |x^|^2) - 2 q^.x^
+ * with the norms and the dot product accumulated in float32 (the dot product by v_mfma_f32_32x32x16_f16, whose order of
+ * summation is not defined): it lies within (d + 3) * 2^-23 * (|q^| + |x^|)^2 of the real-number squared distance between the
+ * two rounded vectors, and may therefore be marginally NEGATIVE for near-identical rows.  Rows whose returned values differ
+ * by less than twice that bound may come in either order; equal values come in ascending label.  Where every value is an
+ * integer (or one power of two times an integer) small enough that every partial sum stays below 2^24 times that power's
+ * square -- 0..127 at d <= 256 -- every operation is exact and the result is the exact distance.  A query holding a value
+ * that does not round to a finite half gets padding.
+ * Results ascending by (distance, label), [nq*k], padded with FLT_MAX / -1; 1 <= k <= 100, null buffers with nq > 0,
+ * row_stride < d, a misaligned device pointer: IVFHNSW_ERR_INVALID; no store, a uint8 store, or a base filter, slot, tags
+ * or values installed on the holder: IVFHNSW_ERR_STATE (it takes no filter, and does not ignore one).  nq is unbounded
+ * (chunks, as exact_search); the option "exact_splits" applies; a view searches its parent's store.
+ * exact_search_f16: host pointers, synchronous.  exact_search_f16_dev: device pointers (queries 4-byte aligned),
+ * asynchronous on the handle's stream. */
+int ivfhnsw_gpu_exact_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                 float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                     float *d_distances, int64_t *d_labels);
 
 /* ---- exact range search of the base store ----------------------------------------------------------
  *

@@ -20,6 +20,7 @@ FILTER_SLOTS, SLOT_NONE = 32, 0xff
 TAG_NONE = 0xffff
 VALUE_NONE = 0xffffffff
 RECON_ORIGINAL, RECON_ROTATED = 0, 1
+BASE_NONE, BASE_U8, BASE_F16 = 0, 1, 2
 STAGES = ("opq", "coarse", "lut", "plan", "scan", "select")
 
 # every symbol include/ivfhnsw_hip.h declares
@@ -75,6 +76,8 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_search_values", "ivfhnsw_gpu_exact_search_values_dev",
     "ivfhnsw_gpu_exact_range_search_values", "ivfhnsw_gpu_exact_range_search_values_dev",
     "ivfhnsw_gpu_upsert_ivf", "ivfhnsw_gpu_upsert_ivf_dev", "ivfhnsw_gpu_upsert", "ivfhnsw_gpu_upsert_dev",
+    "ivfhnsw_gpu_upload_base_f16", "ivfhnsw_gpu_upload_base_f16_dev", "ivfhnsw_gpu_base_kind",
+    "ivfhnsw_gpu_exact_search_f16", "ivfhnsw_gpu_exact_search_f16_dev",
 )
 
 
@@ -198,6 +201,11 @@ def lib():
         L.ivfhnsw_gpu_exact_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                C.c_void_p]
         L.ivfhnsw_gpu_exact_search_dev.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
+        L.ivfhnsw_gpu_upload_base_f16.argtypes = L.ivfhnsw_gpu_upload_base.argtypes
+        L.ivfhnsw_gpu_upload_base_f16_dev.argtypes = L.ivfhnsw_gpu_upload_base.argtypes
+        L.ivfhnsw_gpu_base_kind.argtypes = [C.c_void_p]
+        L.ivfhnsw_gpu_exact_search_f16.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_dev.argtypes = L.ivfhnsw_gpu_exact_search.argtypes
         L.ivfhnsw_gpu_exact_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p,
                                                      C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_exact_range_search_dev.argtypes = L.ivfhnsw_gpu_exact_range_search.argtypes
@@ -1282,6 +1290,75 @@ class GpuIndex:
                 _check_dims(path, raw[:, :4].copy().view(np.int32)[:, 0], d, first)
                 self.upload_base(raw[:, 4:], n=n, first=first, row_stride=rec)
         return n, d
+
+    # ---- the float16 base store (ivfhnsw_gpu_upload_base_f16) ----------------------------------------
+    def upload_base_f16(self, rows_f32, n=None, first=0, row_stride=None):
+        """Rows [first, first + count) of the float16 base store: rows_f32 [count, d] float32, rounded to half on the
+        device, whose rows may lie row_stride FLOATS apart (default: its own; raw[:, 1:] of a [count, d + 1] .fvecs image
+        is taken as it is).  n: rows of the whole store (default first + count); first == 0 (re)allocates it and releases
+        a uint8 store.  rerank serves it; exact_search_f16 searches it."""
+        a = np.asarray(rows_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "rows_f32: a 2-D float32 array [count, d]"
+        count, d = a.shape
+        stride = a.strides[0] // 4 if row_stride is None else row_stride
+        assert count == 0 or (a.strides[1] == 4 and (count == 1 or a.strides[0] == 4 * stride)), \
+            "rows must be contiguous inside a row and row_stride floats apart"
+        n = first + count if n is None else n
+        _check(lib().ivfhnsw_gpu_upload_base_f16(self._h, n, d, first, count, C.c_void_p(a.ctypes.data) if count else None,
+                                                 max(stride, d)))
+        self.base_n, self.base_d = n, d
+
+    def upload_base_f16_dev(self, n, d, first, count, d_rows, row_stride=None):
+        """The same from HBM (a torch CUDA float32 tensor or a device address); synchronous."""
+        _check(lib().ivfhnsw_gpu_upload_base_f16_dev(self._h, n, d, first, count, _devptr(d_rows),
+                                                     d if row_stride is None else row_stride))
+        self.base_n, self.base_d = n, d
+
+    def upload_base_fvecs(self, path, chunk_rows=None, rows=None):
+        """Stream an .fvecs file (records: int32 dim + dim float32) into the float16 base store in chunks of chunk_rows
+        records (default: 2^20, fewer where that would exceed the 512 MB the library stages at once -- a larger chunk is
+        copied to the device twice; rows: only the file's first `rows` records); every record's dim header is checked."""
+        n, d = xvecs_shape(path, 4)
+        if chunk_rows is None:
+            chunk_rows = min(1 << 20, (512 << 20) // (4 * d))
+        if rows is not None:
+            if not 1 <= rows <= n:
+                raise ValueError("%s holds %d records, asked for the first %d" % (path, n, rows))
+            n = rows
+        rec = d + 1
+        with open(path, "rb") as f:
+            for first in range(0, n, chunk_rows):
+                m = min(chunk_rows, n - first)
+                raw = np.frombuffer(f.read(m * rec * 4), np.float32).reshape(m, rec)
+                _check_dims(path, raw[:, :1].copy().view(np.int32)[:, 0], d, first)
+                self.upload_base_f16(raw[:, 1:], n=n, first=first, row_stride=rec)
+        return n, d
+
+    def base_kind(self):
+        """What base store the handle (a view: its parent) holds: BASE_NONE, BASE_U8 or BASE_F16."""
+        return lib().ivfhnsw_gpu_base_kind(self._h)
+
+    def exact_search_f16(self, queries_f32, k):
+        """The k rows of the float16 base store nearest to every query (ivfhnsw_gpu_exact_search_f16): queries_f32 [nq, d]
+        float32, rounded to half as the rows were, whose rows may lie a row stride apart (raw[:, 1:] of an .fvecs image is
+        taken as it is).  Returns (distances f32 [nq, k], labels i64 [nq, k]) ascending by (distance, label), padded
+        FLT_MAX / -1; a distance is (|q|^2 + |x|^2) - 2 q.x of the rounded vectors in float32."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_f16(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                  _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_f16_dev(self, nq, d_queries, row_stride, k, d_distances, d_labels):
+        """The same on device buffers (torch CUDA tensors or raw addresses), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_f16_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_distances),
+                                                      _devptr(d_labels)))
 
     def rerank(self, queries, cand, k):
         """Host arrays: the k best of every query's candidate labels ([nq, kc] int64, -1 = empty) by (exact L2 against

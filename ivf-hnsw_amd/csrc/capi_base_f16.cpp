@@ -1,0 +1,200 @@
+#include "capi_internal.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The float16 base store: float-valued corpora (DEEP1B: 96-d float) kept as halves in HBM, with the exact
+// search on the f16 matrix cores that writes their ground truth (kernels_exact_f16.hip).  The re-rank against it is
+// capi_rerank.cpp's, which serves whichever store the handle holds.
+
+namespace {
+
+// Pieces of at most 512 MB of float32 rows on their way through the device staging buffer.  A host chunk of one piece --
+// upload_base_fvecs' default chunks are -- crosses the bus once and serves both passes from the buffer; a larger chunk is
+// copied twice, once per pass, because the whole chunk is checked before any of it is written.
+size_t stage_rows(size_t d) { return std::max<size_t>(1, ((size_t)512 << 20) / (d * sizeof(float))); }
+
+// rows [r0, r0 + m) of host `rows` packed into the staging buffer, on the handle's stream
+int stage_piece(ivfhnsw_gpu *h, const float *rows, size_t row_stride, size_t d, size_t r0, size_t m)
+{
+    HIP_TRY(hipMemcpy2DAsync(h->base_stage.p, d * sizeof(float), rows + r0 * row_stride, row_stride * sizeof(float),
+                             d * sizeof(float), m, hipMemcpyHostToDevice, h->stream));
+    return IVFHNSW_OK;
+}
+
+// rows [first, first + count) of the store from float32 `rows` at row_stride floats (device memory when on_device).  The
+// whole chunk is checked before anything changes: a value that is NaN or does not round to a finite half refuses the call
+// with the store -- on first == 0 the previous one -- as it was.
+int upload_base_f16_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows, size_t row_stride,
+                         bool on_device)
+{
+    const char *who = on_device ? "upload_base_f16_dev" : "upload_base_f16";
+    int rc = table_change_guard(h, kUploads, who, false);
+    if (rc)
+        return rc;
+    if (n == 0)
+        return base_store_free(h);
+    if ((rc = base_store_args(n, d, 256, first, count, rows, row_stride)))
+        return rc;
+    if (on_device && ((uintptr_t)rows & 3))
+        return fail(IVFHNSW_ERR_INVALID, "%s: rows must be 4-byte aligned", who);
+    const size_t piece = stage_rows(d);
+    const bool one_piece = count <= piece; // a host chunk of one piece is staged once for both passes
+    if (count) {
+        if (!on_device && (rc = h->base_stage.ensure(std::min(piece, count) * d * sizeof(float))))
+            return rc;
+        if ((rc = h->base_flag.ensure(sizeof(uint32_t))))
+            return rc;
+        uint32_t bad = 0, *flag = h->base_flag.as<uint32_t>();
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), h->stream));
+        if (on_device)
+            HIP_TRY(launch_f16_check(h->stream, rows, row_stride, count, (int)d, flag));
+        for (size_t r0 = 0; !on_device && r0 < count; r0 += piece) {
+            const size_t m = std::min(piece, count - r0);
+            if ((rc = stage_piece(h, rows, row_stride, d, r0, m)))
+                return rc;
+            HIP_TRY(launch_f16_check(h->stream, h->base_stage.as<float>(), d, m, (int)d, flag));
+        }
+        HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (bad)
+            return fail(IVFHNSW_ERR_INVALID, "%s: rows [%zu, %zu) hold a NaN or a value that does not round to a finite half", who,
+                        first, first + count);
+    }
+    if ((rc = base_store_open(h, IVFHNSW_BASE_F16, who, n, d, first)))
+        return rc;
+    unsigned char *dst = h->base_rows.as<unsigned char>() + first * d * 2;
+    float *norms = h->base_norms.as<float>() + first;
+    if (on_device) {
+        HIP_TRY(launch_f16_store(h->stream, rows, row_stride, dst, norms, count, (int)d));
+    } else {
+        for (size_t r0 = 0; r0 < count; r0 += piece) {
+            const size_t m = std::min(piece, count - r0);
+            if (!one_piece && (rc = stage_piece(h, rows, row_stride, d, r0, m)))
+                return rc;
+            HIP_TRY(launch_f16_store(h->stream, h->base_stage.as<float>(), d, dst + r0 * d * 2, norms + r0, m, (int)d));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
+// Splits of a call.  The sweep's workgroups hold 64 to 100 KB of LDS, so one or two are resident per CU and a grid that is
+// a little larger than what is resident runs a second, nearly empty round: with s splits the call takes
+// ceil(row_blocks * s / resident) rounds of 1 / s of the columns each.  The fewest splits within 5 % of the best such
+// product (every split warms its thresholds up anew, and the merge reads them all); a split never shorter than 4096
+// columns.  256 CUs, as sweep_splits_for counts them, and 160 KB of LDS each; what a workgroup holds is
+// exact_f16_lds_bytes', the one place that knows the kernel's CAP and WAVES per k, so this rule follows any change of
+// them as long as that function does.  Above k = 32 the sweep is bound by the selection, whose warm-up every
+// split repeats, not by the rounds: there the rule of the uint8 sweep stays (measured).
+int exact_f16_splits_for(size_t nq, size_t nx, size_t d, int k)
+{
+    if (k > 32)
+        return exact_splits_for(nq, nx, k);
+    const size_t rpb = (size_t)exact_rows_per_block(k), row_blocks = (nq + rpb - 1) / rpb;
+    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 << 10) / exact_f16_lds_bytes((int)d, k)));
+    const size_t resident = 256 * per_cu, max_s = std::min<size_t>(64, std::max<size_t>(1, (nx + 4095) / 4096));
+    auto cost = [&](size_t s) { return (double)((row_blocks * s + resident - 1) / resident) / (double)s; };
+    double best = cost(1);
+    for (size_t s = 2; s <= max_s; s++)
+        best = std::min(best, cost(s));
+    for (size_t s = 1; s <= max_s; s++)
+        if (cost(s) <= 1.05 * best)
+            return (int)s;
+    return 1;
+}
+
+// as exact_impl of the uint8 store (capi_exact.cpp) without a column map: the chunks, the splits and the staging of a host call
+int exact_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k, float *distances, int64_t *labels,
+                   bool on_device)
+{
+    const char *who = on_device ? "exact_search_f16_dev" : "exact_search_f16";
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    if (!b->base_n)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_base_f16", who);
+    if (b->base_kind != IVFHNSW_BASE_F16)
+        return fail(IVFHNSW_ERR_STATE, "%s on a uint8 store: exact_search serves it", who);
+    const bool slot_set = std::any_of(std::begin(b->bslots), std::end(b->bslots), [](const BaseSlot &s) { return s.mode >= 0; });
+    if (b->bf_mode >= 0 || slot_set || b->bt_tags.p || b->bv_vals.p)
+        return fail(IVFHNSW_ERR_STATE, "%s: the holder has a base filter, slots, tags or values installed, which it does not take", who);
+    if (k < 1 || k > 100)
+        return fail(IVFHNSW_ERR_INVALID, "%s needs 1 <= k <= 100 (k %zu)", who, k);
+    if (nq == 0)
+        return IVFHNSW_OK;
+    const size_t d = b->base_d, n = b->base_n;
+    if (!queries || !distances || !labels)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null query/result buffer", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (on_device && ((uintptr_t)queries & 3))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries must be 4-byte aligned", who);
+
+    const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_f16_splits_for(std::min(nq, kExactChunk), n, d, (int)k);
+    size_t chunk = kExactPartBytes / ((size_t)nsplit * k * sizeof(uint64_t));
+    chunk = std::min(nq, std::max<size_t>(128, std::min(kExactChunk, chunk / 128 * 128)));
+    if ((rc = h->ex_q.ensure(chunk * d * 2)) || (rc = h->ex_qn.ensure(chunk * sizeof(float))) ||
+        (rc = h->ex_part.ensure((size_t)nsplit * chunk * k * sizeof(uint64_t))))
+        return rc;
+    if (!on_device && ((rc = h->ex_raw.ensure(chunk * d * sizeof(float))) || (rc = h->ex_dist.ensure(chunk * k * sizeof(float))) ||
+                       (rc = h->ex_lab.ensure(chunk * k * sizeof(int64_t)))))
+        return rc;
+    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
+        const size_t m = std::min(chunk, nq - q0);
+        const float *src = queries + q0 * row_stride;
+        size_t src_stride = row_stride;
+        if (!on_device) {
+            HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), src, row_stride * sizeof(float), d * sizeof(float), m,
+                                     hipMemcpyHostToDevice, h->stream));
+            src = h->ex_raw.as<float>();
+            src_stride = d;
+        }
+        float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
+        int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
+        // the queries rounded, permuted and normed as the store's rows were
+        HIP_TRY(launch_f16_store(h->stream, src, src_stride, h->ex_q.p, h->ex_qn.as<float>(), m, (int)d));
+        HIP_TRY(launch_exact_search_f16(h->stream, h->ex_q.p, h->ex_qn.as<float>(), b->base_rows.p, b->base_norms.as<float>(), m, n,
+                                        (int)d, (int)k, nsplit, h->ex_part.as<unsigned long long>(), od, ol));
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+            // the next chunk reuses the pageable source and the staging buffers
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+    }
+    return IVFHNSW_OK;
+}
+
+} // namespace
+
+int ivfhnsw_gpu_upload_base_f16(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows,
+                                size_t row_stride)
+{
+    return upload_base_f16_impl(h, n, d, first, count, rows, row_stride, false);
+}
+
+int ivfhnsw_gpu_upload_base_f16_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *d_rows,
+                                    size_t row_stride)
+{
+    return upload_base_f16_impl(h, n, d, first, count, d_rows, row_stride, true);
+}
+
+int ivfhnsw_gpu_base_kind(const ivfhnsw_gpu *h)
+{
+    if (!h)
+        return IVFHNSW_BASE_NONE;
+    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
+    return b->base_n ? b->base_kind : IVFHNSW_BASE_NONE;
+}
+
+int ivfhnsw_gpu_exact_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k, float *distances,
+                                 int64_t *labels)
+{
+    return exact_f16_impl(h, nq, queries, row_stride, k, distances, labels, false);
+}
+
+int ivfhnsw_gpu_exact_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                     float *d_distances, int64_t *d_labels)
+{
+    return exact_f16_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true);
+}

@@ -24,6 +24,8 @@ int exact_guard(ivfhnsw_gpu *h, const char *name, size_t nq, size_t row_stride, 
     *b = h->parent ? h->parent : h;
     if (!(*b)->base_n)
         return fail(IVFHNSW_ERR_STATE, "%s before upload_base", name);
+    if ((*b)->base_kind != IVFHNSW_BASE_U8)
+        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: exact_search_f16 serves it", name);
     const size_t d = (*b)->base_d;
     if (d > 256)
         return fail(IVFHNSW_ERR_INVALID,

@@ -187,6 +187,7 @@ using namespace ivfhnsw_gpu_impl;
     X(gb_table) X(gb_fwd) X(gb_fcnt) X(gb_deg) X(gb_roff) X(gb_ids) X(gb_ids2) X(gb_hist) X(gb_stat) X(gb_counts) X(gb_links) /* build_graph */ \
     X(cg_q) X(cg_cidx) X(cg_ids) X(cg_dists) X(gc_nn) X(cg_cvn) X(cg_tab) X(cg_tab2) X(cg_off) X(cg_alpha2) X(cg_sub) /* add_group */ \
     X(base_rows) X(base_stage) /* uint8 base of the re-rank, rows permuted (kernels_rerank.hip); a view reads its parent's */ \
+    X(base_norms) X(base_flag) X(ex_qn) /* the float16 store (base_rows holds its halves): a float32 squared norm per row; the upload check's word; the norms of exact_search_f16's queries */ \
     X(r_q) X(r_cand) X(r_dist) X(r_lab) /* staging of the host-pointer re-rank */ \
     X(ex_q) X(ex_part) X(ex_raw) X(ex_dist) X(ex_lab) /* exact_search: permuted queries, per-split partial tables; staging of the host form */ \
     X(ap_idx) X(ap_ids) X(ap_codes) X(ap_ncodes) X(ap_cnt) X(ap_own) X(ap_part) X(ap_status) X(ap_perm) X(ap_perm2) X(ap_hist) X(ap_tiles) /* append_ivf, add */ \
@@ -243,6 +244,7 @@ struct ivfhnsw_gpu {
     bool e_opq = false, has_codebooks = false;
     uint64_t base_n = 0;
     size_t base_d = 0;
+    int base_kind = IVFHNSW_BASE_NONE; // what base_rows holds: IVFHNSW_BASE_U8 bytes or IVFHNSW_BASE_F16 halves (with base_norms)
     ivfhnsw_gpu *parent = nullptr;
 
     // the label filter (capi_filter.cpp).  filter.mode -1 = none.  fmask is what the scans read: the
@@ -649,6 +651,16 @@ int chunk_checks(ivfhnsw_gpu *h, const Chunk &c, bool results = true);
 int chunk_workspace(ivfhnsw_gpu *h, Chunk &c);
 int chunk_coarse(ivfhnsw_gpu *h, Chunk &c, const SearchCall &call);
 int chunk_plan_table(ivfhnsw_gpu *h, Chunk &c);
+
+// ---- capi_rerank.cpp: what the uploads of both kinds of base store share
+// The arguments of an upload of rows [first, first + count) of a store of n x d (n > 0), d a multiple of 16 in 16..d_max,
+// rows row_stride elements apart.
+int base_store_args(size_t n, size_t d, size_t d_max, size_t first, size_t count, const void *rows, size_t row_stride);
+// The handle holds no store afterwards: rows, norms, base filter, slots, tags and values released.  Drains the stream.
+int base_store_free(ivfhnsw_gpu *h);
+// The store the upload writes to: first == 0 frees whatever the handle holds and allocates n x d elements of `kind`,
+// zero-filled (a float16 store: its norms too); a later chunk must name the store there is.  `who`: the call's name.
+int base_store_open(ivfhnsw_gpu *h, int kind, const char *who, size_t n, size_t d, size_t first);
 
 // ---- capi_base_filter.cpp
 void base_filter_drop(ivfhnsw_gpu *h); // the handle holds no base filter afterwards (buffers released)

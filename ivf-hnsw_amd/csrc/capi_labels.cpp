@@ -67,6 +67,8 @@ int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool n
         return rc;
     if (need_upload && !(base ? h->base_n != 0 : h->has_ivf))
         return fail(IVFHNSW_ERR_STATE, "%s before %s", who, base ? "upload_base" : "upload_ivf");
+    if (need_upload && base && h->base_kind != IVFHNSW_BASE_U8)
+        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: it takes no filter, slots, tags or values", who);
     return IVFHNSW_OK;
 }
 

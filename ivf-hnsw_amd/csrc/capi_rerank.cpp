@@ -3,6 +3,74 @@
 // ---------------------------------------------------------------------------------------------------------------------
 // searchDisk's exact re-rank on the device (IndexIVF_HNSW_Grouping.cpp:365-395): the base store and the re-rank itself.
 
+namespace ivfhnsw_gpu_impl {
+
+int base_store_args(size_t n, size_t d, size_t d_max, size_t first, size_t count, const void *rows, size_t row_stride)
+{
+    if (d % 16 || d < 16 || d > d_max)
+        return fail(IVFHNSW_ERR_INVALID, "base dimension %zu: must be a multiple of 16 in 16..%zu", d, d_max);
+    if (n >= 0xffffffffull)
+        return fail(IVFHNSW_ERR_INVALID, "base of %zu rows: labels must fit 32 bits", n);
+    if (first > n || count > n - first)
+        return fail(IVFHNSW_ERR_INVALID, "rows [%zu, %zu) outside a base of %zu rows", first, first + count, n);
+    if (count && (!rows || row_stride < d))
+        return fail(IVFHNSW_ERR_INVALID, "null rows or row_stride %zu < d %zu", row_stride, d);
+    return IVFHNSW_OK;
+}
+
+// the store and everything that names its rows go; base_stage stays
+static int base_store_release(ivfhnsw_gpu *h)
+{
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->base_rows.release();
+    h->base_norms.release();
+    base_filter_drop(h); // its rows are gone, or a new store's row numbers mean other rows
+    base_slots_drop(h);
+    base_tags_drop(h);
+    base_values_drop(h);
+    h->base_n = 0;
+    h->base_d = 0;
+    h->base_kind = IVFHNSW_BASE_NONE;
+    return IVFHNSW_OK;
+}
+
+int base_store_free(ivfhnsw_gpu *h)
+{
+    h->base_stage.release();
+    return base_store_release(h);
+}
+
+int base_store_open(ivfhnsw_gpu *h, int kind, const char *who, size_t n, size_t d, size_t first)
+{
+    if (first == 0) {
+        int rc = base_store_release(h);
+        if (rc)
+            return rc;
+        const size_t bytes = n * d * (kind == IVFHNSW_BASE_F16 ? 2 : 1);
+        if ((rc = h->base_rows.ensure(bytes)) || (kind == IVFHNSW_BASE_F16 && (rc = h->base_norms.ensure(n * sizeof(float))))) {
+            h->base_rows.release();
+            return fail(rc, "base store of %zu x %zu, %zu bytes: %s", n, d, bytes, ivfhnsw_gpu_last_error());
+        }
+        HIP_TRY(hipMemsetAsync(h->base_rows.p, 0, bytes, h->stream));
+        if (kind == IVFHNSW_BASE_F16)
+            HIP_TRY(hipMemsetAsync(h->base_norms.p, 0, n * sizeof(float), h->stream));
+        h->base_n = n;
+        h->base_d = d;
+        h->base_kind = kind;
+    } else if (!h->base_n) {
+        return fail(IVFHNSW_ERR_STATE, "%s with first = %zu: no store (the first call has first = 0)", who, first);
+    } else if (h->base_kind != kind) {
+        return fail(IVFHNSW_ERR_STATE, "%s with first = %zu: the store holds %s", who, first,
+                    h->base_kind == IVFHNSW_BASE_F16 ? "float16 rows (upload_base_f16 fills it)" : "uint8 rows (upload_base fills it)");
+    } else if (h->base_n != n || h->base_d != d) {
+        return fail(IVFHNSW_ERR_INVALID, "%s: store holds %llu x %zu, call says %zu x %zu", who, (unsigned long long)h->base_n,
+                    h->base_d, n, d);
+    }
+    return IVFHNSW_OK;
+}
+
+} // namespace ivfhnsw_gpu_impl
+
 // rows [first, first + count) of the store from `rows` at row_stride (device memory when on_device); first == 0
 // (re)allocates the store, n == 0 frees it.  Synchronous: the caller may reuse `rows` when it returns.
 static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const uint8_t *rows,
@@ -11,46 +79,11 @@ static int upload_base_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, si
     int rc = table_change_guard(h, kUploads, "upload_base", false);
     if (rc)
         return rc;
-    if (n == 0) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->base_rows.release();
-        h->base_stage.release();
-        base_filter_drop(h); // its rows are gone
-        base_slots_drop(h);
-        base_tags_drop(h);
-        base_values_drop(h);
-        h->base_n = 0;
-        h->base_d = 0;
-        return IVFHNSW_OK;
-    }
-    if (d % 16 || d < 16 || d > 512)
-        return fail(IVFHNSW_ERR_INVALID, "base dimension %zu: must be a multiple of 16 in 16..512", d);
-    if (n >= 0xffffffffull)
-        return fail(IVFHNSW_ERR_INVALID, "base of %zu rows: labels must fit 32 bits", n);
-    if (first > n || count > n - first)
-        return fail(IVFHNSW_ERR_INVALID, "rows [%zu, %zu) outside a base of %zu rows", first, first + count, n);
-    if (count && (!rows || row_stride < d))
-        return fail(IVFHNSW_ERR_INVALID, "null rows or row_stride %zu < d %zu", row_stride, d);
-    if (first == 0) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->base_rows.release();
-        base_filter_drop(h); // a new store: its row numbers mean other rows
-        base_slots_drop(h);
-        base_tags_drop(h);
-        base_values_drop(h);
-        h->base_n = 0;
-        h->base_d = 0;
-        if ((rc = h->base_rows.ensure(n * d)))
-            return fail(rc, "base store of %zu x %zu bytes: %s", n, d, ivfhnsw_gpu_last_error());
-        HIP_TRY(hipMemsetAsync(h->base_rows.p, 0, n * d, h->stream));
-        h->base_n = n;
-        h->base_d = d;
-    } else if (!h->base_n) {
-        return fail(IVFHNSW_ERR_STATE, "upload_base with first = %zu: no store (the first call has first = 0)", first);
-    } else if (h->base_n != n || h->base_d != d) {
-        return fail(IVFHNSW_ERR_INVALID, "upload_base: store holds %llu x %zu, call says %zu x %zu",
-                    (unsigned long long)h->base_n, h->base_d, n, d);
-    }
+    if (n == 0)
+        return base_store_free(h);
+    if ((rc = base_store_args(n, d, 512, first, count, rows, row_stride)) ||
+        (rc = base_store_open(h, IVFHNSW_BASE_U8, "upload_base", n, d, first)))
+        return rc;
     uint8_t *dst = h->base_rows.as<uint8_t>() + first * d;
     if (on_device) {
         HIP_TRY(launch_rerank_permute(h->stream, rows, row_stride, dst, count, (int)d));
@@ -85,6 +118,15 @@ int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first
 // the handle that holds the store: a view reads its parent's
 static const ivfhnsw_gpu *base_holder(const ivfhnsw_gpu *h) { return h->parent ? h->parent : h; }
 
+// the re-rank of whichever store holder b has
+static hipError_t launch_rerank_of(hipStream_t s, const ivfhnsw_gpu *b, const float *q, const int64_t *cand, size_t nq, size_t kc,
+                                   size_t k, float *dist, int64_t *labels)
+{
+    if (b->base_kind == IVFHNSW_BASE_F16)
+        return launch_rerank_f16(s, b->base_rows.p, b->base_n, (int)b->base_d, q, cand, nq, (int)kc, (int)k, dist, labels);
+    return launch_rerank(s, b->base_rows.as<uint8_t>(), b->base_n, (int)b->base_d, q, cand, nq, (int)kc, (int)k, dist, labels);
+}
+
 static int check_rerank(ivfhnsw_gpu *h, size_t kc, size_t k)
 {
     int rc = bind(h);
@@ -108,8 +150,7 @@ int ivfhnsw_gpu_rerank_dev(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *d_
     if (!d_queries || !d_cand || !d_distances || !d_labels)
         return fail(IVFHNSW_ERR_INVALID, "null query/candidate/result buffer");
     const ivfhnsw_gpu *b = base_holder(h);
-    HIP_TRY(launch_rerank(h->stream, b->base_rows.as<uint8_t>(), b->base_n, (int)b->base_d, d_queries, d_cand, nq, (int)kc,
-                          (int)k, d_distances, d_labels));
+    HIP_TRY(launch_rerank_of(h->stream, b, d_queries, d_cand, nq, kc, k, d_distances, d_labels));
     return IVFHNSW_OK;
 }
 
@@ -135,8 +176,8 @@ int ivfhnsw_gpu_rerank(ivfhnsw_gpu *h, size_t nq, size_t kc, const float *querie
         return rc;
     HIP_TRY(hipMemcpyAsync(h->r_q.p, queries, nq * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->r_cand.p, cand, nq * kc * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(launch_rerank(h->stream, b->base_rows.as<uint8_t>(), b->base_n, (int)d, h->r_q.as<float>(),
-                          h->r_cand.as<int64_t>(), nq, (int)kc, (int)k, h->r_dist.as<float>(), h->r_lab.as<int64_t>()));
+    HIP_TRY(launch_rerank_of(h->stream, b, h->r_q.as<float>(), h->r_cand.as<int64_t>(), nq, kc, k, h->r_dist.as<float>(),
+                             h->r_lab.as<int64_t>()));
     HIP_TRY(hipMemcpyAsync(distances, h->r_dist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(labels, h->r_lab.p, nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

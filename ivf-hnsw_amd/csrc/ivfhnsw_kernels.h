@@ -341,6 +341,21 @@ hipError_t launch_rerank_permute(hipStream_t s, const uint8_t *src, size_t src_s
 size_t rerank_lds_bytes(int kc, int d);
 hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
                          const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels);
+// ... against the float16 store (launch_f16_store's layout, d <= 256): fvec_L2sqr of the float32 query and the halves widened
+hipError_t launch_rerank_f16(hipStream_t s, const void *base, uint64_t n, int d, const float *queries, const int64_t *cand,
+                             size_t nq, int kc, int k, float *dist, int64_t *labels);
+// The float16 base store and its exact search on the f16 matrix cores (kernels_exact_f16.hip); d % 16 == 0,
+// 16 <= d <= 256.  launch_f16_check: *flag (not zeroed here) |= 1 where a value of rows [count] at src_stride floats is NaN
+// or does not round to a finite half.  launch_f16_store: the rows rounded to half and permuted as the uint8 store's are at
+// dst [count][d], norms [count] = the float32 squared norms of the rounded rows.  launch_exact_search_f16: Qh, qn = the
+// queries as launch_f16_store leaves rows, X, xn = the store; 1 <= k <= 100; part: [nsplit][nq][k] u64 workspace; writes
+// the k nearest rows of every query ascending by (distance, label), padded with FLT_MAX / -1.  Workgroups own
+// exact_rows_per_block(k) query rows.  exact_f16_lds_bytes: the sweep's LDS per workgroup.
+hipError_t launch_f16_check(hipStream_t s, const float *src, size_t src_stride, size_t count, int d, uint32_t *flag);
+hipError_t launch_f16_store(hipStream_t s, const float *src, size_t src_stride, void *dst, float *norms, size_t count, int d);
+size_t exact_f16_lds_bytes(int d, int k);
+hipError_t launch_exact_search_f16(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                   size_t nx, int d, int k, int nsplit, unsigned long long *part, float *dists, int64_t *labels);
 // exact brute-force search of the store on the int8 matrix cores (kernels_exact.hip).  Qp: [nq][d] queries
 // in the store's byte order (launch_rerank_permute), d % 16 == 0, d <= 256, 1 <= k <= 100; part: [nsplit][nq][k] u64
 // workspace; writes the k nearest rows of every query ascending by (distance, label), padded with FLT_MAX / -1

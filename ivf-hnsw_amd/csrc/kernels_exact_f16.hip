@@ -1,0 +1,319 @@
+// The float16 base store (ivfhnsw_gpu_upload_base_f16) and its exact brute-force search on the f16 matrix cores
+// (ivfhnsw_gpu_exact_search_f16).
+//
+// The store: every float32 value rounded to half (round to nearest even), rows permuted as the uint8 store's are
+// (kernels_rerank.hip: lane t of a quad owns dims 8j + 2t, 8j + 2t + 1 as the d/4 contiguous halves [t d/4, (t + 1) d/4)), and
+// beside the rows one float32 per row: the squared norm of the ROUNDED row.
+//
+// Arithmetic of the search, q^ and x^ the rounded vectors:
+//     dist(q, x) = (|q^|^2 + |x^|^2) - 2 q^.x^        two rounded float32 operations, 2 * dot is exact
+//     q^.x^      = a chain of v_mfma_f32_32x32x16_f16 over the d/16 steps of a row, float32 accumulation
+// The queries go through the store's permutation once per call, so whatever contraction order the instruction gives the
+// eight halves of a lane, it gives the same one to both operands; only the C/D map is relied on (sweep_steps.h mfma32_row).
+// Where every value is an integer (or the same power of two times one) and every partial sum stays below 2^24 each
+// operation is exact in any order and the result is the integer distance.
+//
+// Shape: wave w of a workgroup owns the 32 query rows [32w, 32w + 32) of the workgroup's strip for the whole sweep, operand
+// A resident in d/16 x 4 registers.  Operand B is staged ONCE PER WORKGROUP: a tile of 32 columns is 32 rows of 2d bytes,
+// contiguous in the store; the workgroup's threads copy it in 16-byte pieces into one of TWO LDS tiles while the waves
+// multiply the other, the global loads of tile t + 1 in flight in registers behind the MFMAs of tile t, one barrier per
+// tile.  An LDS row is padded by 16 bytes: its stride in words is 4 (d/8 + 1), four times an odd number, so the sixteen
+// lanes of a ds_read_b128 pass fall on sixteen distinct groups of four banks.  A column's norm comes from the table, one
+// float per column lane per tile.  The common tile (none of the wave's 32 x 32 distances is a candidate) costs one
+// multiply-subtract and one compare per accumulator register against a per-row gate; selection and merge are
+// sweep_steps.h's with float keys, as in kernels_knn.hip: columns arrive in increasing order, so ties go to the lower label
+// by the strict '<' alone.
+#include "sweep_steps.h"
+
+#include <float.h>
+#include <math.h>
+
+namespace ivfhnsw_gpu_impl {
+
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ---- upload -------------------------------------------------------------------------------------------------------------
+// *flag |= 1 where a value of rows [count] at src_stride floats is NaN or does not round to a finite half: 65520 is the
+// midpoint between the largest half, 65504, and 2^16, and rounds to even -- to infinity.
+__global__ __launch_bounds__(256) void f16_check_kernel(const float *__restrict__ src, size_t src_stride, size_t count, int d,
+                                                        uint32_t *__restrict__ flag)
+{
+    const size_t total = count * (size_t)d;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / (size_t)d;
+        bad |= !(fabsf(src[r * src_stride + (i - r * (size_t)d)]) < 65520.f);
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0)
+        atomicOr(flag, 1u);
+}
+
+// One lane per (row, quad lane t): the lane's d/4 halves, two to a word, and its share of the norm; the quad adds the four
+// shares.  The norm is that of the rounded values: fmaf chains of d/8 terms, then three additions.
+__global__ __launch_bounds__(256) void f16_store_kernel(const float *__restrict__ src, size_t src_stride, _Float16 *__restrict__ dst,
+                                                        float *__restrict__ norms, size_t count, int d)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t r = i >> 2;
+    const int t = (int)(i & 3);
+    const bool ok = r < count; // (the four lanes of a quad agree)
+    const float *row = src + (ok ? r : 0) * src_stride + 2 * t;
+    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (ok ? r : 0) * (size_t)d + t * (d >> 2));
+    float alo = 0.f, ahi = 0.f;
+    for (int j = 0; j < (d >> 3); j++) {
+        const _Float16 h0 = (_Float16)row[8 * j], h1 = (_Float16)row[8 * j + 1];
+        if (ok)
+            out[j] = (uint32_t)__builtin_bit_cast(unsigned short, h0) | ((uint32_t)__builtin_bit_cast(unsigned short, h1) << 16);
+        const float f0 = (float)h0, f1 = (float)h1;
+        alo = __fmaf_rn(f0, f0, alo);
+        ahi = __fmaf_rn(f1, f1, ahi);
+    }
+    float s = __fadd_rn(alo, ahi);
+    s = __fadd_rn(s, __shfl_xor(s, 1));
+    s = __fadd_rn(s, __shfl_xor(s, 2));
+    if (ok && t == 0)
+        norms[r] = s;
+}
+
+// ---- the sweep ----------------------------------------------------------------------------------------------------------
+// What the common tile compares against.  A distance is a candidate when
+//     dist = fl(fl(qn + xn) - 2 dot) < thr,
+// and the tile's cheap test is fl(2 dot - xn) > gate with gate = qn - thr lowered by a margin that covers the three
+// roundings: each is at most 2^-24 of its result.  For a candidate the results are bounded by the row's own numbers --
+// |dist| <= |thr| or so, and xn <= (sqrt(qn) + sqrt(dist))^2 <= 2 (qn + dist) by Cauchy-Schwarz, so qn + xn and |2 dot - xn|
+// stay below 3 (qn + |thr|) -- which makes the sum of the three at most 2^-22 (qn + |thr|).  The margin is sixteen times
+// that: the dot product's own rounding bends the Cauchy-Schwarz step a little, and a tile that passes the cheap test in
+// vain costs only the exact test behind it.  thr = FLT_MAX (fewer than k keys yet) gives -inf: every tile passes.
+// thr = -inf marks a row that is no query (beyond nq): nothing passes, ever.
+__device__ __forceinline__ float f16_gate(float qn, float thr)
+{
+    if (thr == -INFINITY)
+        return INFINITY;
+    return __fsub_rn(__fsub_rn(qn, thr), __fmul_rn(0x1p-18f, __fadd_rn(qn, fabsf(thr))));
+}
+
+// ND = d / 16, the MFMA steps of a row; CAP = keys of a row's candidate buffer (a row is compacted when it holds more than
+// CAP - 32); WAVES = 32-row strips per workgroup.  Qh [nq][d] the queries as the store holds its rows, qn [nq] their norms;
+// X [nx][d], xn [nx] the store.
+template <int ND, int CAP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                               const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                               int nq, size_t nx, int k, size_t cols_per_split,
+                                                               unsigned long long *__restrict__ out_keys)
+{
+    constexpr int D = 16 * ND, T = 64 * WAVES;
+    constexpr int ROWB = 2 * D + 16;        // bytes of a tile's row in LDS: the row and its padding
+    constexpr int TILEB = 32 * ROWB;
+    constexpr int PPR = D / 8;              // 16-byte pieces of a row,
+    constexpr int NPIECE = 32 * PPR;        // ... of a tile,
+    constexpr int NP = (NPIECE + T - 1) / T; // ... of a thread
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char *s_tile = smem;                                                              // [2][TILEB]
+    unsigned long long *s_buf = reinterpret_cast<unsigned long long *>(smem + 2 * TILEB);       // [WAVES][32][CAP]
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_buf + WAVES * 32 * CAP);                   // [WAVES][32]
+    float *s_thr = reinterpret_cast<float *>(s_cnt + WAVES * 32);                               // [WAVES][32]
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const int r0 = blockIdx.x * (32 * WAVES) + wave * 32;
+    // (the same for every wave of the workgroup: all of them meet at every barrier below)
+    const size_t c_begin = (size_t)blockIdx.y * cols_per_split < nx ? (size_t)blockIdx.y * cols_per_split : nx;
+    const size_t c_end = c_begin + cols_per_split < nx ? c_begin + cols_per_split : nx;
+    unsigned long long *buf = s_buf + (size_t)wave * 32 * CAP;
+    uint32_t *cnt = s_cnt + wave * 32;
+    float *thr_s = s_thr + wave * 32;
+
+    // operand A: lane (m, kk) holds for step s the stored halves [16 s + 8 kk, + 8) of query row r0 + m (a row beyond nq
+    // repeats the last one and is never a candidate)
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)min(r0 + m, nq - 1) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    if (lane < 32) {
+        cnt[lane] = 0;
+        thr_s[lane] = r0 + lane < nq ? FLT_MAX : -INFINITY;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float qn_r[16], gate[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        qn_r[r] = qn[min(r0 + row, nq - 1)];
+        gate[r] = f16_gate(qn_r[r], thr_s[row]);
+    }
+
+    // staging: thread tid takes the pieces tid, tid + T, ... of a tile, piece p = 16 bytes at byte 16 p of the tile in the
+    // store, which is byte 16 (p % PPR) of tile row p / PPR.  A row at or beyond c_end is not read: its pieces are zeros.
+    uint4 pre[NP];
+    float pre_n = 0.f;
+    auto fetch = [&](size_t c0) {
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(X) + c0 * (size_t)(2 * D);
+        const int rows_in = c_end - c0 < 32 ? (int)(c_end - c0) : 32;
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int p = tid + i * T;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if ((NPIECE % T == 0 || p < NPIECE) && p / PPR < rows_in)
+                v = *reinterpret_cast<const uint4 *>(src + 16 * (size_t)p);
+            pre[i] = v;
+        }
+        pre_n = c0 + m < c_end ? xn[c0 + m] : 0.f;
+    };
+    auto stash = [&](int b) {
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int p = tid + i * T;
+            if (NPIECE % T == 0 || p < NPIECE)
+                *reinterpret_cast<uint4 *>(s_tile + b * TILEB + (p / PPR) * ROWB + 16 * (p % PPR)) = pre[i];
+        }
+    };
+
+    float xn_cur = 0.f;
+    if (c_begin < c_end) {
+        fetch(c_begin);
+        stash(0);
+        xn_cur = pre_n;
+    }
+    __syncthreads();
+    int b = 0;
+    for (size_t c0 = c_begin; c0 < c_end; c0 += 32, b ^= 1) {
+        const bool more = c0 + 32 < c_end;
+        if (more)
+            fetch(c0 + 32); // in flight behind this tile's MFMAs
+        const unsigned char *bt = s_tile + b * TILEB + m * ROWB + 16 * kk;
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], *reinterpret_cast<const f16x8 *>(bt + 32 * s), acc, 0, 0, 0);
+        const size_t col = c0 + m;
+        const bool col_ok = col < c_end;
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_cur) > gate[r];
+        if (__ballot(any && col_ok)) { // wave-uniform: rare once the thresholds have settled
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_cur), __fmul_rn(2.0f, acc[r]));
+                const int row = mfma32_row(r, kk);
+                const bool pass = col_ok && dist < thr_s[row];
+                const unsigned long long mask = __ballot(pass);
+                if (mask)
+                    row_append<CAP>(buf, cnt, row, pass, mask, dist, (uint32_t)col, m, kk);
+            }
+            rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+        }
+        if (more)
+            stash(b ^ 1); // the tile every wave left at the last barrier
+        xn_cur = pre_n;
+        __syncthreads();
+    }
+
+    // out: [split][nq][k] keys
+    rows_write_out<CAP>(buf, cnt, k, lane, nq - r0, out_keys, (size_t)blockIdx.y * nq + r0);
+}
+
+__global__ __launch_bounds__(64) void exact_f16_merge_kernel(const unsigned long long *__restrict__ part, int nsplit, int nq, int k,
+                                                             float *__restrict__ dists, long long *__restrict__ labels)
+{
+    sweep_merge(
+        part, nsplit, nq, k,
+        [&](size_t o, unsigned long long key) {
+            labels[o] = (long long)(uint32_t)key;
+            dists[o] = orderable_f32((uint32_t)(key >> 32));
+        },
+        [&](size_t o) { // the store has fewer than k rows
+            labels[o] = -1ll;
+            dists[o] = FLT_MAX;
+        });
+}
+
+template <int ND, int CAP, int WAVES>
+hipError_t launch_exact_f16_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn, int nq,
+                              size_t nx, int k, int nsplit, size_t cols_per_split, unsigned long long *part)
+{
+    const size_t shm = exact_f16_lds_bytes(16 * ND, k);
+    constexpr auto kern = exact_f16_kernel<ND, CAP, WAVES>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
+        return e;
+    // query tile is the fast index, column split the slow one: the workgroups that run together stream the same columns
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 32 * WAVES - 1) / (32 * WAVES)), (unsigned)nsplit), dim3(64 * WAVES), shm, s,
+                       Qh, qn, X, xn, nq, nx, k, cols_per_split, part);
+    return hipGetLastError();
+}
+
+// f(int_c<ND>()) for ND = d / 16 = 1 .. 16; any other d is refused
+template <class F> hipError_t by_f16_steps(int d, F &&f)
+{
+    switch (d / 16) {
+#define IVFHNSW_F16_STEP(N) case N: return f(int_c<N>());
+        IVFHNSW_F16_STEP(1) IVFHNSW_F16_STEP(2) IVFHNSW_F16_STEP(3) IVFHNSW_F16_STEP(4) IVFHNSW_F16_STEP(5) IVFHNSW_F16_STEP(6)
+        IVFHNSW_F16_STEP(7) IVFHNSW_F16_STEP(8) IVFHNSW_F16_STEP(9) IVFHNSW_F16_STEP(10) IVFHNSW_F16_STEP(11) IVFHNSW_F16_STEP(12)
+        IVFHNSW_F16_STEP(13) IVFHNSW_F16_STEP(14) IVFHNSW_F16_STEP(15) IVFHNSW_F16_STEP(16)
+#undef IVFHNSW_F16_STEP
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace
+
+size_t exact_f16_lds_bytes(int d, int k)
+{
+    const size_t waves = k <= 32 ? 4 : 2, cap = k <= 16 ? 48 : k <= 32 ? 64 : 136;
+    return (size_t)2 * 32 * (2 * d + 16) + waves * 32 * cap * sizeof(unsigned long long) + waves * 32 * (sizeof(uint32_t) + sizeof(float));
+}
+
+hipError_t launch_f16_check(hipStream_t s, const float *src, size_t src_stride, size_t count, int d, uint32_t *flag)
+{
+    if (count == 0)
+        return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((count * (size_t)d + 255) / 256, 256 * 64);
+    hipLaunchKernelGGL(f16_check_kernel, dim3(grid), dim3(256), 0, s, src, src_stride, count, d, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_f16_store(hipStream_t s, const float *src, size_t src_stride, void *dst, float *norms, size_t count, int d)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || count > ((size_t)1 << 36))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(f16_store_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, s, src, src_stride,
+                       reinterpret_cast<_Float16 *>(dst), norms, count, d);
+    return hipGetLastError();
+}
+
+// Qh, qn: the queries as launch_f16_store leaves rows; part: [nsplit][nq][k] u64 workspace
+hipError_t launch_exact_search_f16(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                   size_t nx, int d, int k, int nsplit, unsigned long long *part, float *dists, int64_t *labels)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || nq > 0x7fffffffull || nx == 0 || nx >= 0xffffffffull || nsplit < 1 ||
+        nsplit > 64)
+        return hipErrorInvalidValue;
+    const size_t cps = sweep_cols_per_split(nx, nsplit);
+    const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
+    const hipError_t e = by_f16_steps(d, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        return k <= 16   ? launch_exact_f16_t<ND, 48, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part)
+               : k <= 32 ? launch_exact_f16_t<ND, 64, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part)
+                         : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part);
+    });
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(exact_f16_merge_kernel, dim3((unsigned)nq), dim3(64), 0, s, part, nsplit, (int)nq, k, dists,
+                       reinterpret_cast<long long *>(labels));
+    return hipGetLastError();
+}
+
+} // namespace ivfhnsw_gpu_impl

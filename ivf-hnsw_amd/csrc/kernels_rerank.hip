@@ -11,6 +11,13 @@
 // One workgroup per query: the quads gather its kc candidate rows (several per quad in flight), the packed keys
 // (distance bits << 32 | label) go to LDS, a bitonic sort orders them (unsigned order = (distance, label) because
 // distances are non-negative), and the first k are written out.  Labels outside [0, n) are empty slots: never read.
+//
+// Against the float16 store (kernels_exact_f16.hip) the same kernel with HALF: the rows hold halves in the
+// same permutation, a lane's slice is d/4 halves, one dword = the lane's two dims of one block of eight, and the distance
+// is fvec_L2sqr of the unrounded float32 query and the stored halves widened -- exactly -- to float32, in the same order.
+// The HALF instantiations are compiled in a translation unit of their own, kernels_rerank_f16.hip, which includes this
+// file with IVFHNSW_RERANK_F16_UNIT defined and takes launch_rerank_f16 from it; this unit is the uint8 store's, compiled
+// as it always was.
 #include "ivfhnsw_kernels.h"
 #include "device_common.h"
 
@@ -21,6 +28,7 @@ namespace ivfhnsw_gpu_impl {
 constexpr int RR_THREADS_MAX = 256;
 constexpr unsigned long long RR_EMPTY = ~0ull; // sorts after every real key (no distance has the bits 0xffffffff: NaN)
 
+#ifndef IVFHNSW_RERANK_F16_UNIT
 // ---- upload: rows in file order -> the store's per-quad layout --------------------------------------------------------
 // One dword of the stored row per thread: stored byte p of a row (lane t = p / (d/4), i = p % (d/4)) holds dim 8(i/2)+2t+(i%2).
 // GATHER: row r of dst is row row_src[r] of src (a negative entry: row 0, a row nobody reads the result of) -- the
@@ -68,6 +76,8 @@ hipError_t launch_rerank_permute_rows(hipStream_t s, const uint8_t *src, size_t 
     return hipGetLastError();
 }
 
+#endif // !IVFHNSW_RERANK_F16_UNIT
+
 // ---- the re-rank -----------------------------------------------------------------------------------------------------
 // One lane's contribution to a row: its NW dwords (NW = d/16; template form for the common d, runtime otherwise).
 template <int NW>
@@ -109,6 +119,23 @@ __device__ __forceinline__ void rr_acc_word(uint32_t w, const float *qs, float &
     ahi = __fadd_rn(ahi, __fmul_rn(t1, t1));
 }
 
+// ... of the float16 store = stored halves 2i, 2i+1 of the slice = dim 8i+2t, +1: one block
+__device__ __forceinline__ void rr_acc_half(uint32_t w, const float *qs, float &alo, float &ahi)
+{
+    const float2 q = *reinterpret_cast<const float2 *>(qs);
+    const float t0 = __fsub_rn(q.x, (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)));
+    const float t1 = __fsub_rn(q.y, (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)));
+    alo = __fadd_rn(alo, __fmul_rn(t0, t0));
+    ahi = __fadd_rn(ahi, __fmul_rn(t1, t1));
+}
+template <bool HALF> __device__ __forceinline__ void rr_acc(uint32_t w, const float *qs, int x, float &alo, float &ahi)
+{
+    if constexpr (HALF)
+        rr_acc_half(w, qs + 2 * x, alo, ahi);
+    else
+        rr_acc_word(w, qs + 4 * x, alo, ahi);
+}
+
 __device__ __forceinline__ float rr_quad_total(float alo, float ahi)
 {
     float r = __fadd_rn(quad_bcast<0>(alo), quad_bcast<0>(ahi));
@@ -124,16 +151,18 @@ __device__ __forceinline__ float rr_quad_total(float alo, float ahi)
 // the keys' LDS, rounded up so that the query slices behind it are 16-byte aligned
 __host__ __device__ inline size_t rr_keys_bytes(int P) { return ((size_t)P * 8 + 15) & ~(size_t)15; }
 
-// NW > 0: compile-time d = 16 * NW, R rows per quad in flight.  NW == 0: any d (runtime loop, one row at a time).
-template <int NW, int R>
+// NW > 0: NW dwords per lane and row at compile time (d = 16 * NW; HALF: d = 8 * NW), R rows per quad in flight.
+// NW == 0: any d (runtime loop, one row at a time).  HALF: base is the float16 store.
+template <bool HALF, int NW, int R>
 __global__ __launch_bounds__(RR_THREADS_MAX) void rerank_kernel(const uint8_t *__restrict__ base, uint64_t n, int d_rt,
                                                                 const float *__restrict__ queries,
                                                                 const long long *__restrict__ cand, int kc, int k, int P,
                                                                 float *__restrict__ out_dist, long long *__restrict__ out_lab)
 {
     extern __shared__ __align__(16) unsigned char rr_lds[];
-    const int d = NW > 0 ? 16 * NW : d_rt;
-    const int S = d >> 2;  // bytes (= floats of the permuted query) per lane slice
+    const int d = NW > 0 ? (HALF ? 8 : 16) * NW : d_rt;
+    const int S = d >> 2;  // elements (= floats of the permuted query) per lane slice
+    const int SB = HALF ? 2 * S : S, RB = HALF ? 2 * d : d; // ... its bytes, and a row's
     const int QS = S + 4;  // LDS stride of a slice: lanes t and t+2 of a quad land on different banks
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(rr_lds);
     float *qp = reinterpret_cast<float *>(rr_lds + rr_keys_bytes(P));
@@ -164,7 +193,7 @@ __global__ __launch_bounds__(RR_THREADS_MAX) void rerank_kernel(const uint8_t *_
                 lab[u] = i < kc ? qc[i] : -1;
                 ok[u] = lab[u] >= 0 && (unsigned long long)lab[u] < n;
                 if (ok[u])
-                    rr_load<NW>(base + (size_t)lab[u] * d + t * S, w[u]);
+                    rr_load<NW>(base + (size_t)lab[u] * RB + t * SB, w[u]);
                 else
 #pragma unroll
                     for (int x = 0; x < NW; x++)
@@ -175,7 +204,7 @@ __global__ __launch_bounds__(RR_THREADS_MAX) void rerank_kernel(const uint8_t *_
                 float alo = 0.f, ahi = 0.f;
 #pragma unroll
                 for (int x = 0; x < NW; x++)
-                    rr_acc_word(w[u][x], qs + 4 * x, alo, ahi);
+                    rr_acc<HALF>(w[u][x], qs, x, alo, ahi);
                 const float dist = rr_quad_total(alo, ahi);
                 const int i = r0 + u * nquads + quad;
                 if (t == 0 && i < kc)
@@ -186,10 +215,10 @@ __global__ __launch_bounds__(RR_THREADS_MAX) void rerank_kernel(const uint8_t *_
             const int i = r0 + quad;
             const long long lab = i < kc ? qc[i] : -1;
             const bool ok = lab >= 0 && (unsigned long long)lab < n;
-            const uint32_t *row = reinterpret_cast<const uint32_t *>(base + (size_t)(ok ? lab : 0) * d + t * S);
+            const uint32_t *row = reinterpret_cast<const uint32_t *>(base + (size_t)(ok ? lab : 0) * RB + t * SB);
             float alo = 0.f, ahi = 0.f;
-            for (int x = 0; x < (S >> 2); x++)
-                rr_acc_word(ok ? row[x] : 0u, qs + 4 * x, alo, ahi);
+            for (int x = 0; x < (SB >> 2); x++)
+                rr_acc<HALF>(ok ? row[x] : 0u, qs, x, alo, ahi);
             const float dist = rr_quad_total(alo, ahi);
             if (t == 0 && i < kc)
                 keys[i] = ok ? ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned long long)lab : RR_EMPTY;
@@ -221,6 +250,7 @@ __global__ __launch_bounds__(RR_THREADS_MAX) void rerank_kernel(const uint8_t *_
     }
 }
 
+#ifndef IVFHNSW_RERANK_F16_UNIT
 size_t rerank_lds_bytes(int kc, int d)
 {
     int P = 1;
@@ -229,8 +259,12 @@ size_t rerank_lds_bytes(int kc, int d)
     return rr_keys_bytes(P) + (size_t)4 * (d / 4 + 4) * sizeof(float);
 }
 
-hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
-                         const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels)
+#endif
+
+// HALF: base is the float16 store
+template <bool HALF>
+static hipError_t launch_rerank_t(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
+                                  const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels)
 {
     if (nq == 0)
         return hipSuccess;
@@ -250,14 +284,19 @@ hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, 
         float *od = dist + q0 * (size_t)k;
         long long *ol = l + q0 * (size_t)k;
 #define RR_LAUNCH(NW, R)                                                                                                 \
-    hipLaunchKernelGGL((rerank_kernel<NW, R>), dim3((unsigned)m), dim3(thr), lds, s, base, (unsigned long long)n, d, xq, \
-                       cq, kc, k, P, od, ol)
+    hipLaunchKernelGGL((rerank_kernel<HALF, (HALF ? 2 : 1) * (NW), R>), dim3((unsigned)m), dim3(thr), lds, s, base,          \
+                       (unsigned long long)n, d, xq, cq, kc, k, P, od, ol)
         switch (d) {
         case 128: RR_LAUNCH(8, 2); break;
         case 96: RR_LAUNCH(6, 2); break;
         case 64: RR_LAUNCH(4, 4); break;
         case 256: RR_LAUNCH(16, 1); break;
-        case 512: RR_LAUNCH(32, 1); break;
+        case 512:
+            if constexpr (!HALF) { // (the float16 store ends at d = 256)
+                RR_LAUNCH(32, 1);
+                break;
+            }
+            [[fallthrough]];
         default: RR_LAUNCH(0, 1); break;
         }
 #undef RR_LAUNCH
@@ -267,5 +306,22 @@ hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, 
     }
     return hipSuccess;
 }
+
+#ifndef IVFHNSW_RERANK_F16_UNIT
+hipError_t launch_rerank(hipStream_t s, const uint8_t *base, uint64_t n, int d, const float *queries,
+                         const int64_t *cand, size_t nq, int kc, int k, float *dist, int64_t *labels)
+{
+    return launch_rerank_t<false>(s, base, n, d, queries, cand, nq, kc, k, dist, labels);
+}
+#else
+
+hipError_t launch_rerank_f16(hipStream_t s, const void *base, uint64_t n, int d, const float *queries, const int64_t *cand,
+                             size_t nq, int kc, int k, float *dist, int64_t *labels)
+{
+    if (d < 16 || d > 256 || (d & 15))
+        return hipErrorInvalidValue;
+    return launch_rerank_t<true>(s, static_cast<const uint8_t *>(base), n, d, queries, cand, nq, kc, k, dist, labels);
+}
+#endif
 
 } // namespace ivfhnsw_gpu_impl

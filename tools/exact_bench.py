@@ -34,6 +34,10 @@
      replaces, per distinct interval set_base_filter_dev(the interval's rows) + the plain call on its queries, with and
      without the installs; k = 1, k = 100 and the range form at the median k = 10 distance with the reorder's share of
      it; and the time of set_base_values_dev over every row.
+  8. With --f16 ONLY the float16 store (ivfhnsw_gpu_exact_search_f16_dev): --small-rows x 128 and x 96 rows
+     of random bytes as float32, k = 1, 10 and 100, alternating in one process with ivfhnsw_gpu_knn_dev on the same rows as
+     float32 (k <= 80) and exact_search_dev on a uint8 store of the same rows; all three are exact on such rows and must
+     agree.  Store bytes per second are those of each call's own rows (2, 4 and 1 bytes a value).
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
@@ -115,6 +119,7 @@ def main():
     ap.add_argument("--filter-slots", action="store_true", help="add the base-filter-slot legs (DESIGN.md 3.20)")
     ap.add_argument("--tags", action="store_true", help="add the base-tag legs (DESIGN.md 3.22)")
     ap.add_argument("--values", action="store_true", help="add the base-value legs (DESIGN.md 3.25)")
+    ap.add_argument("--f16", action="store_true", help="only the float16 store's legs (DESIGN.md 3.27), at d = 128 and d = 96 on --small-rows rows")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -507,6 +512,72 @@ def main():
                 print(json.dumps(r), flush=True)
             del sub
         g.clear_base_values()
+
+    def f16_legs(n, dd):
+        """The float16 store's sweep (exact_search_f16_dev) beside knn_dev on the same rows as float32 and
+        exact_search_dev on a uint8 store of the same rows, alternating in one process.  The rows are random bytes, so all
+        three are exact and must return the same labels."""
+        g8 = pkg.GpuIndex(0)
+        g8.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(77 + dd)
+        rows = torch.empty((n, dd), dtype=torch.uint8, device=dev).random_(0, 256, generator=gen)
+        qb = torch.empty((nq, dd), dtype=torch.uint8, device=dev).random_(0, 256, generator=gen)
+        xf, qf = rows.to(torch.float32), qb.to(torch.float32)
+        torch.cuda.synchronize(dev)
+        g8.upload_base_dev(n, dd, 0, n, rows)
+        t0 = time.perf_counter()
+        g.upload_base_f16_dev(n, dd, 0, n, xf)
+        t_up = time.perf_counter() - t0
+        r = {"what": "upload_base_f16_dev", "rows": n, "d": dd, "seconds": round(t_up, 4), "memory_GB": round(g.memory_bytes() / 1e9, 3)}
+        result["rows"].append(r)
+        print(json.dumps(r), flush=True)
+        for k in (1, 10, 100):
+            od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            od8, ol8 = torch.empty_like(od), torch.empty_like(ol)
+            ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+            kd = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            calls = [("exact_search_f16_dev", lambda: g.exact_search_f16_dev(nq, qf, dd, k, od, ol)),
+                     ("exact_search_dev (uint8 store)", lambda: g8.exact_search_dev(nq, qb, dd, k, od8, ol8))]
+            if k <= 80 and not args.no_knn:  # knn_dev's limit
+                calls.append(("knn_dev (f32 MFMA)", lambda: g.knn_dev(nq, n, dd, qf, xf, k, ids, kd)))
+            ts = {name: [] for name, _ in calls}
+            for rep in range(args.warmup + args.reps):
+                for name, fn in calls:
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize(dev)
+                    if rep >= args.warmup:
+                        ts[name].append(time.perf_counter() - t0)
+                    log("[exact_bench] f16 legs d=%d k=%d rep %d %s: %.4f s" % (dd, k, rep, name, time.perf_counter() - t0))
+            assert torch.equal(ol, ol8) and torch.equal(od, od8), "the float16 and the uint8 sweep disagree on integer rows"
+            base_t = statistics.median(ts["exact_search_f16_dev"])
+            for name, _ in calls:
+                t = statistics.median(ts[name])
+                r = figures(name, n, dd, nq, k, t, ts[name], 128 if k <= 32 else 64)
+                elem = {"exact_search_f16_dev": 2, "knn_dev (f32 MFMA)": 4}.get(name, 1)
+                r["store_TB_per_s_per_pass"] = round(n * dd * elem / t / 1e12, 4)  # bytes of THIS call's rows
+                r["streamed_TB_per_s"] = round(r["query_tiles"] * n * dd * elem / t / 1e12, 3)
+                r["over_f16"] = round(t / base_t, 3)
+                if name.startswith("knn"):
+                    r["labels_equal"] = bool(torch.equal(ids.to(torch.int64) & 0xffffffff, ol))
+                result["rows"].append(r)
+                print(json.dumps(r), flush=True)
+        g8.close()
+        g.upload_base_f16_dev(0, dd, 0, 0, None)
+        del rows, xf, qf, qb
+        torch.cuda.empty_cache()
+
+    if args.f16:
+        for dd in (128, 96):
+            f16_legs(args.small_rows, dd)
+        g.close()
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+        return
 
     def yardstick_and_range(n, dense_radius=None, fractions=(1, 2, 8, 32, 1024)):
         name = "%d rows" % n

@@ -24,7 +24,11 @@ one pair (lo, hi) per query, shape [nq, 2]) the truth of a workload with a value
 values (ivfhnsw_gpu_set_base_values) are installed and the _values form of either search runs, so query q
 gets only rows whose value lies in [lo, hi], inclusive ((0, 0xffffffff): every row).
 
+With an .fvecs base and .fvecs queries (float corpora: DEEP1B) the same .ivecs is written from the float16 base store
+(upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; no filter, no --radius.
+
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
+       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --values v.npy --query-ranges qr.npy"""
@@ -164,11 +168,48 @@ def read_bvecs_image(path):
     return img, d
 
 
+def read_fvecs_image(path):
+    """(image float32 [n, d + 1], d) of an .fvecs file, every record's dim header checked; image[:, 1:] are the rows, d + 1
+    floats apart, as exact_search_f16 and upload_base_f16 take them."""
+    raw = np.fromfile(path, "<f4")
+    if raw.size < 1:
+        raise ValueError("%s is empty" % path)
+    d = int(raw[:1].view("<i4")[0])
+    if d <= 0 or raw.size % (d + 1):
+        raise ValueError("%s: not an .fvecs file of dimension %d" % (path, d))
+    img = raw.reshape(-1, d + 1)
+    dims = np.ascontiguousarray(img[:, :1]).view("<i4")[:, 0]
+    if (dims != d).any():
+        bad = int(np.nonzero(dims != d)[0][0])
+        raise ValueError("%s: record %d has dimension %d, expected %d" % (path, bad, dims[bad], d))
+    return img, d
+
+
+def ground_truth_f16(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=None):
+    """The same for an .fvecs base and .fvecs queries, through the float16 base store: both are rounded to
+    half, and the order is that of ivfhnsw_gpu_exact_search_f16's float32 distances between the rounded vectors."""
+    img, dq = read_fvecs_image(query_path)
+    g = pkg.GpuIndex(device)
+    try:
+        n, d = g.upload_base_fvecs(base_path, chunk_rows=chunk_rows, rows=rows)
+        if d != dq:
+            raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        _, lab = g.exact_search_f16(img[:, 1:], k)
+    finally:
+        g.close()
+    return lab
+
+
 def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False, tags=None,
                  query_tags=None, values=None, query_ranges=None):
     """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query; with `labels`
     only of the rows whose number is in them (deny: is not); with `tags` and `query_tags` only of the rows that carry the
-    query's tag; with `values` and `query_ranges` only of the rows whose value lies in the query's interval."""
+    query's tag; with `values` and `query_ranges` only of the rows whose value lies in the query's interval.  An .fvecs
+    base goes to the float16 store (ground_truth_f16), which takes none of the filters."""
+    if base_path.endswith(".fvecs"):
+        if labels is not None or tags is not None or values is not None:
+            raise ValueError("an .fvecs base goes to the float16 store, which takes no filter, tags or values")
+        return ground_truth_f16(pkg, base_path, query_path, k, rows=rows, device=device)  # (upload_base_fvecs sizes its chunks)
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
@@ -251,6 +292,8 @@ def main(argv=None):
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
+    if args.radius is not None and args.base.endswith(".fvecs"):
+        ap.error("--radius needs a .bvecs base: the float16 store has no exact range search")
     if args.radius is not None:
         info = {}
         lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device,

@@ -7,7 +7,10 @@
      one stream, rows/s and TB/s of gathered row bytes, and the whole step against search_dev at k = 1 and k = 10.
   2. A small SIFT-like uint8 corpus (tests/rerank_ref.uint8_recall_corpus): Recall@1 / Recall@10 with and without the
      re-rank.
-usage: python tools/rerank_bench.py [--workload NAME] [--reps 10] [--kcs 10,20,100,1000] [--no-recall] [--no-speed]"""
+  3. With --f16 only: the re-rank against a float16 store beside the re-rank against a uint8 store of the
+     same --f16-rows x --f16-d random rows, random candidates, alternating in one process.
+usage: python tools/rerank_bench.py [--workload NAME] [--reps 10] [--kcs 10,20,100,1000] [--no-recall] [--no-speed]
+       python tools/rerank_bench.py --f16 [--f16-rows 50000000] [--f16-d 128] [--kcs 100] [--reps 10]"""
 import argparse
 import json
 import os
@@ -92,6 +95,54 @@ def speed(args, pkg, torch):
     return out
 
 
+def speed_f16(args, pkg, torch):
+    """The re-rank against a float16 store beside the re-rank against a uint8 store of the same rows (random bytes), random
+    candidate labels, alternating in one process: milliseconds from HIP events, rows/s and TB/s of gathered row bytes."""
+    dev = torch.device("cuda", 0)
+    n, d, nq, k = args.f16_rows, args.f16_d, 10000, 10
+    stream = torch.cuda.current_stream(dev)
+    g8, g16 = pkg.GpuIndex(0), pkg.GpuIndex(0)
+    g8.set_stream(stream.cuda_stream)
+    g16.set_stream(stream.cuda_stream)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(99)
+    chunk_rows = min(n, (1 << 28) // d)
+    buf = torch.empty((chunk_rows, d), dtype=torch.uint8, device=dev)
+    for first in range(0, n, chunk_rows):
+        m = min(chunk_rows, n - first)
+        buf.random_(0, 256, generator=gen)
+        bf = buf.to(torch.float32)
+        torch.cuda.synchronize(dev)
+        g8.upload_base_dev(n, d, first, m, buf)
+        g16.upload_base_f16_dev(n, d, first, m, bf)
+    del buf, bf
+    q = torch.empty((nq, d), dtype=torch.float32, device=dev).uniform_(0, 255, generator=gen)
+    out = {"nq": nq, "k": k, "base_rows": n, "d": d, "rows": []}
+    for kc in [int(x) for x in args.kcs.split(",")]:
+        cl = torch.randint(0, n, (nq, kc), dtype=torch.int64, device=dev, generator=gen)
+        od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        ms = {"uint8": [], "float16": []}
+        for rep in range(2 + args.reps):
+            for name, g in (("uint8", g8), ("float16", g16)):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                e[0].record(stream)
+                g.rerank_dev(nq, kc, q, cl, min(k, kc), od, ol)
+                e[1].record(stream)
+                g.sync()
+                if rep >= 2:
+                    ms[name].append(e[0].elapsed_time(e[1]))
+        for name, elem in (("uint8", 1), ("float16", 2)):
+            t = float(np.median(ms[name]))
+            r = {"store": name, "kc": kc, "rerank_dev_ms": round(t, 4), "rows_per_s": nq * kc / (t * 1e-3),
+                 "row_TBps": nq * kc * d * elem / (t * 1e-3) / 1e12, "reps_ms": [round(x, 4) for x in ms[name]]}
+            out["rows"].append(r)
+            print(json.dumps(r), flush=True)
+    g8.close()
+    g16.close()
+    return out
+
+
 def recall(pkg):
     import rerank_ref
     c = rerank_ref.uint8_recall_corpus(pkg, seed=77)
@@ -123,11 +174,17 @@ def main():
     ap.add_argument("--no-recall", action="store_true")
     ap.add_argument("--no-speed", action="store_true")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
+    ap.add_argument("--f16", action="store_true", help="only the float16 store's re-rank beside the uint8 store's (DESIGN.md 3.27)")
+    ap.add_argument("--f16-rows", type=int, default=50_000_000)
+    ap.add_argument("--f16-d", type=int, default=128)
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
     result = {}
+    if args.f16:
+        result["speed_f16"] = speed_f16(args, pkg, torch)
+        args.no_recall = args.no_speed = True
     if not args.no_recall:
         result["recall"] = recall(pkg)
     if not args.no_speed:
