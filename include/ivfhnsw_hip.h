@@ -812,8 +812,9 @@ int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first
  * IVFHNSW_ERR_STATE.  upload_base_f16_dev: rows in HBM, 4-byte aligned.
  * ivfhnsw_gpu_rerank[_dev] serves whichever store the handle holds; against a float16 store its distance is
  * fvec_L2sqr(q, float(x^)) bit for bit -- the unrounded float32 query, the stored half widened exactly, the eight
- * accumulators and the order of utils.cpp:22-52.  On a float16 store every uint8 exact call (exact_search*,
- * exact_range_search*) and every set_base_* installer returns IVFHNSW_ERR_STATE: it takes no filter of any kind.
+ * accumulators and the order of utils.cpp:22-52.  ivfhnsw_gpu_exact_search_f16 and ivfhnsw_gpu_exact_range_search_f16 (below)
+ * search it.  On a float16 store every uint8 exact call (exact_search*, exact_range_search*) and every set_base_* installer
+ * returns IVFHNSW_ERR_STATE: it takes no filter of any kind.
  * ivfhnsw_gpu_base_kind: what the handle (a view: its parent) holds. */
 #define IVFHNSW_BASE_NONE 0
 #define IVFHNSW_BASE_U8 1
@@ -922,6 +923,36 @@ int ivfhnsw_gpu_exact_range_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t 
                                        uint64_t *d_lims, uint64_t *total);
 int ivfhnsw_gpu_exact_range_results(ivfhnsw_gpu *h, uint64_t first, uint64_t count, float *distances, int64_t *labels);
 int ivfhnsw_gpu_exact_range_results_dev(ivfhnsw_gpu *h, const float **d_distances, const int64_t **d_labels, uint64_t *total);
+
+/* The same question of a float16 store (upload_base_f16), on the f16 matrix cores: the truth of a range search
+ * over float-valued data.  Queries as for exact_search_f16: float32, the store's d each, row_stride >= d FLOATS apart (d + 1
+ * takes an .fvecs image), rounded to half as the rows were.
+ *   Row j is returned for query q iff dist(q, j) < radius -- strict -- where dist is THE VALUE exact_search_f16 RETURNS for
+ *   the pair, (|q^|^2 + |x^|^2) - 2 q^.x^ in float32, bit for bit, and that value is the distance written.  It lies within
+ *   (d + 3) * 2^-23 * (|q^| + |x^|)^2 of the real-number squared distance of the rounded vectors: a pair nearer to the radius
+ *   than that may fall on either side of it, and the value may be marginally NEGATIVE, so a radius <= 0 is swept like any
+ *   other (it can return near-identical rows).  Any radius but NaN is taken; +inf returns every row, -inf none.  A query
+ *   holding a value that does not round to a finite half gets no results.  Every row of the store is a candidate.
+ *   The results of one query stand in ASCENDING LABEL; lims, *total, the absence of a cap: as exact_range_search.
+ *   The results land in the SAME buffers as exact_range_search's -- a handle holds one store, of one kind -- so
+ *   ivfhnsw_gpu_exact_range_results[_dev] serve them, and they stay until the handle's next exact range search of either kind.
+ *   Memory (ivfhnsw_gpu_memory_bytes counts all of it): 12 bytes per result; 4 bytes per (query, column split); 2 d + 4 bytes
+ *   per query (all queries of the call are prepared at once) and, for the host form, 4 d more; the tile map, one bit per (32
+ *   queries, 32 rows), coarsened by powers of two until it is at most 1/16 of the store's 2 n d bytes.
+ *   One synchronisation between the two passes; profiling: count = scan stage, fill = select stage.
+ *   Limits: at most 131 072 queries per call; 2^32 or more results -> IVFHNSW_ERR_INVALID after the count pass, before
+ *   anything is allocated.
+ *   Errors leave earlier results as they were: no store, a uint8 store, or a base filter, slot, tags or values installed on
+ *   the holder -> IVFHNSW_ERR_STATE; a NaN radius, NULL queries, lims or total with nq > 0, row_stride < d, more than
+ *   131 072 queries, a misaligned device pointer -> IVFHNSW_ERR_INVALID; a failed allocation -> IVFHNSW_ERR_NOMEM.
+ *   nq = 0: lims[0] = 0 (when lims is given), *total = 0, success.
+ *   The options "exact_splits" and "exact_range_map" apply; the results do not depend on them.
+ * exact_range_search_f16: host pointers.  exact_range_search_f16_dev: device pointers (queries 4-byte, d_lims 8-byte
+ *   aligned), *total on the host.  Both return when the results are complete. */
+int ivfhnsw_gpu_exact_range_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, float radius,
+                                       uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, float radius,
+                                           uint64_t *d_lims, uint64_t *total);
 
 /* ---- base filter: the exact calls under an allow or deny set of row numbers ---------------------------
  *

@@ -78,6 +78,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_upsert_ivf", "ivfhnsw_gpu_upsert_ivf_dev", "ivfhnsw_gpu_upsert", "ivfhnsw_gpu_upsert_dev",
     "ivfhnsw_gpu_upload_base_f16", "ivfhnsw_gpu_upload_base_f16_dev", "ivfhnsw_gpu_base_kind",
     "ivfhnsw_gpu_exact_search_f16", "ivfhnsw_gpu_exact_search_f16_dev",
+    "ivfhnsw_gpu_exact_range_search_f16", "ivfhnsw_gpu_exact_range_search_f16_dev",
 )
 
 
@@ -209,6 +210,8 @@ def lib():
         L.ivfhnsw_gpu_exact_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p,
                                                      C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_exact_range_search_dev.argtypes = L.ivfhnsw_gpu_exact_range_search.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16.argtypes = L.ivfhnsw_gpu_exact_range_search.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16_dev.argtypes = L.ivfhnsw_gpu_exact_range_search.argtypes
         L.ivfhnsw_gpu_exact_range_results.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_exact_range_results_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                           C.POINTER(C.c_uint64)]
@@ -1359,6 +1362,32 @@ class GpuIndex:
         """The same on device buffers (torch CUDA tensors or raw addresses), asynchronous on the handle's stream."""
         _check(lib().ivfhnsw_gpu_exact_search_f16_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_distances),
                                                       _devptr(d_labels)))
+
+    def exact_range_search_f16(self, queries_f32, radius):
+        """Every row of the float16 base store whose distance -- the value exact_search_f16 returns for the pair -- is
+        < radius (strict), per query in ascending label (ivfhnsw_gpu_exact_range_search_f16): (lims u64 [nq + 1],
+        distances f32 [total], labels i64 [total]); query q owns [lims[q], lims[q + 1]).  queries_f32 as exact_search_f16
+        takes them."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                        C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_f16_dev(self, nq, d_queries, row_stride, radius, d_lims):
+        """The same on device buffers (float32 queries, d_lims: [nq + 1] 64-bit words); returns when the results are
+        complete, with their number.  They stay in the handle's memory: exact_range_results_dev() / exact_range_results()."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16_dev(self._h, nq, _devptr(d_queries), row_stride, C.c_float(radius),
+                                                            _devptr(d_lims), C.byref(total)))
+        return int(total.value)
 
     def rerank(self, queries, cand, k):
         """Host arrays: the k best of every query's candidate labels ([nq, kc] int64, -1 = empty) by (exact L2 against

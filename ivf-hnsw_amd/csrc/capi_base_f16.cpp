@@ -85,12 +85,13 @@ int upload_base_f16_impl(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_
 // exact_f16_lds_bytes', the one place that knows the kernel's CAP and WAVES per k, so this rule follows any change of
 // them as long as that function does.  Above k = 32 the sweep is bound by the selection, whose warm-up every
 // split repeats, not by the rounds: there the rule of the uint8 sweep stays (measured).
-int exact_f16_splits_for(size_t nq, size_t nx, size_t d, int k)
+// The rule itself takes the kernel's shape -- rpb query rows and lds bytes per workgroup -- so that the range sweep
+// (DESIGN.md 3.28), whose workgroups hold the two tiles only, is cut by the same rule with its own numbers.  More than two
+// workgroups per CU are not counted on for either kernel: whether they help has not been measured.
+int f16_splits_rule(size_t nq, size_t nx, size_t rpb, size_t lds)
 {
-    if (k > 32)
-        return exact_splits_for(nq, nx, k);
-    const size_t rpb = (size_t)exact_rows_per_block(k), row_blocks = (nq + rpb - 1) / rpb;
-    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 << 10) / exact_f16_lds_bytes((int)d, k)));
+    const size_t row_blocks = (nq + rpb - 1) / rpb;
+    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 << 10) / lds));
     const size_t resident = 256 * per_cu, max_s = std::min<size_t>(64, std::max<size_t>(1, (nx + 4095) / 4096));
     auto cost = [&](size_t s) { return (double)((row_blocks * s + resident - 1) / resident) / (double)s; };
     double best = cost(1);
@@ -102,22 +103,42 @@ int exact_f16_splits_for(size_t nq, size_t nx, size_t d, int k)
     return 1;
 }
 
+int exact_f16_splits_for(size_t nq, size_t nx, size_t d, int k)
+{
+    if (k > 32)
+        return exact_splits_for(nq, nx, k);
+    return f16_splits_rule(nq, nx, (size_t)exact_rows_per_block(k), exact_f16_lds_bytes((int)d, k));
+}
+
+int exact_range_f16_splits_for(size_t nq, size_t nx, size_t d) { return f16_splits_rule(nq, nx, 128, exact_range_f16_lds_bytes((int)d)); }
+
+// what every exact call on the half store checks first: the handle; the store (*b: a view searches its parent's), its
+// kind, and that the holder has nothing installed that the call would have to ignore
+int exact_f16_guard(ivfhnsw_gpu *h, const char *who, const char *u8_call, const ivfhnsw_gpu **b)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    *b = h->parent ? h->parent : h;
+    if (!(*b)->base_n)
+        return fail(IVFHNSW_ERR_STATE, "%s before upload_base_f16", who);
+    if ((*b)->base_kind != IVFHNSW_BASE_F16)
+        return fail(IVFHNSW_ERR_STATE, "%s on a uint8 store: %s serves it", who, u8_call);
+    const bool slot_set = std::any_of(std::begin((*b)->bslots), std::end((*b)->bslots), [](const BaseSlot &s) { return s.mode >= 0; });
+    if ((*b)->bf_mode >= 0 || slot_set || (*b)->bt_tags.p || (*b)->bv_vals.p)
+        return fail(IVFHNSW_ERR_STATE, "%s: the holder has a base filter, slots, tags or values installed, which it does not take", who);
+    return IVFHNSW_OK;
+}
+
 // as exact_impl of the uint8 store (capi_exact.cpp) without a column map: the chunks, the splits and the staging of a host call
 int exact_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k, float *distances, int64_t *labels,
                    bool on_device)
 {
     const char *who = on_device ? "exact_search_f16_dev" : "exact_search_f16";
-    int rc = bind(h);
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "exact_search", &b);
     if (rc)
         return rc;
-    const ivfhnsw_gpu *b = h->parent ? h->parent : h;
-    if (!b->base_n)
-        return fail(IVFHNSW_ERR_STATE, "%s before upload_base_f16", who);
-    if (b->base_kind != IVFHNSW_BASE_F16)
-        return fail(IVFHNSW_ERR_STATE, "%s on a uint8 store: exact_search serves it", who);
-    const bool slot_set = std::any_of(std::begin(b->bslots), std::end(b->bslots), [](const BaseSlot &s) { return s.mode >= 0; });
-    if (b->bf_mode >= 0 || slot_set || b->bt_tags.p || b->bv_vals.p)
-        return fail(IVFHNSW_ERR_STATE, "%s: the holder has a base filter, slots, tags or values installed, which it does not take", who);
     if (k < 1 || k > 100)
         return fail(IVFHNSW_ERR_INVALID, "%s needs 1 <= k <= 100 (k %zu)", who, k);
     if (nq == 0)
@@ -165,6 +186,94 @@ int exact_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_s
     return IVFHNSW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Exact range search of the half store: the sequence of the uint8 call (capi_exact.cpp, 3.17) -- count ->
+// prefix -> (one synchronisation: the host sizes the results) -> fill -- around exact_range_f16_kernel.
+
+// one form of the sweep over every chunk of the call's queries (h->ex_q, h->ex_qn: all of them, as the store holds rows)
+int exact_range_f16_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, bool fill, size_t nq, float radius, int nsplit, int map_shift,
+                         float *dist, int64_t *labels, size_t out_cap)
+{
+    const size_t d = b->base_d;
+    StageScope sc(h, fill ? IVFHNSW_STAGE_SELECT : IVFHNSW_STAGE_SCAN); // accounted as exact_range_search accounts its passes
+    uint32_t *map = h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr;
+    for (size_t q0 = 0; q0 < nq; q0 += kExactChunk) // (kExactChunk % 128 == 0: a chunk starts a workgroup's strip)
+        HIP_TRY(launch_exact_range_f16(h->stream, fill, h->ex_q.as<unsigned char>() + q0 * d * 2, h->ex_qn.as<float>() + q0,
+                                       b->base_rows.p, b->base_norms.as<float>(), std::min(kExactChunk, nq - q0), q0, b->base_n, (int)d,
+                                       radius, nsplit, h->xr_slices.as<uint32_t>(), h->xr_tot.as<unsigned long long>(), map, map_shift,
+                                       dist, labels, out_cap));
+    return IVFHNSW_OK;
+}
+
+// device pointers, the arguments checked (nq > 0)
+int exact_range_f16_dev(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const char *who, size_t nq, const float *d_queries, size_t row_stride,
+                        float radius, uint64_t *d_lims, uint64_t *total)
+{
+    const size_t d = b->base_d, n = b->base_n;
+    const int nsplit = h->opt_exact_splits > 0 ? h->opt_exact_splits : exact_range_f16_splits_for(std::min(nq, kExactChunk), n, d);
+    const size_t len = nq * (size_t)nsplit + 1;
+    size_t map_bytes = 0;
+    const int map_shift = exact_range_map_shift(nq, n, 2 * d, nsplit, &map_bytes);
+    int rc;
+    if ((rc = h->ex_q.ensure(nq * d * 2)) || (rc = h->ex_qn.ensure(nq * sizeof(float))) ||
+        (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) || (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
+        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))))
+        return rc;
+    // every query of the call rounded, permuted and normed as the store's rows were, once for both passes
+    HIP_TRY(launch_f16_store(h->stream, d_queries, row_stride, h->ex_q.p, h->ex_qn.as<float>(), nq, (int)d));
+    HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
+    if ((rc = exact_range_f16_pass(h, b, false, nq, radius, nsplit, map_shift, nullptr, nullptr, 0)))
+        return rc;
+    unsigned long long tot = 0;
+    if ((rc = exact_range_total(h, who, len, &tot)))
+        return rc;
+    RangeOut out;
+    if ((rc = out.reserve(h, tot)))
+        return rc;
+    HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
+    if (tot && (rc = exact_range_f16_pass(h, b, true, nq, radius, nsplit, map_shift, out.dist(h), out.lab(h), (size_t)tot)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    out.commit(h, tot);
+    *total = tot;
+    return IVFHNSW_OK;
+}
+
+int exact_range_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, float radius, uint64_t *lims,
+                         uint64_t *total, bool on_device)
+{
+    const char *who = on_device ? "exact_range_search_f16_dev" : "exact_range_search_f16";
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "exact_range_search", &b);
+    if (rc)
+        return rc;
+    if (std::isnan(radius))
+        return fail(IVFHNSW_ERR_INVALID, "%s: the radius is NaN", who);
+    if (nq == 0)
+        return exact_range_none(h, on_device ? nullptr : lims, on_device ? lims : nullptr, total);
+    const size_t d = b->base_d;
+    if (!queries || !lims || !total)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null queries, lims or total", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (nq > kMaxBatchAll)
+        return fail(IVFHNSW_ERR_INVALID, "%s is limited to %zu queries per call", who, kMaxBatchAll);
+    if (on_device && (((uintptr_t)queries & 3) || ((uintptr_t)lims & 7)))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries must be 4-byte and lims 8-byte aligned", who);
+    if (on_device)
+        return exact_range_f16_dev(h, b, who, nq, queries, row_stride, radius, lims, total);
+    if ((rc = h->ex_raw.ensure(nq * d * sizeof(float))) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), queries, row_stride * sizeof(float), d * sizeof(float), nq,
+                             hipMemcpyHostToDevice, h->stream));
+    if ((rc = exact_range_f16_dev(h, b, who, nq, h->ex_raw.as<float>(), d, radius, h->xr_lims.as<uint64_t>(), total)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
 } // namespace
 
 int ivfhnsw_gpu_upload_base_f16(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows,
@@ -197,4 +306,16 @@ int ivfhnsw_gpu_exact_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_q
                                      float *d_distances, int64_t *d_labels)
 {
     return exact_f16_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true);
+}
+
+int ivfhnsw_gpu_exact_range_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, float radius,
+                                       uint64_t *lims, uint64_t *total)
+{
+    return exact_range_f16_impl(h, nq, queries, row_stride, radius, lims, total, false);
+}
+
+int ivfhnsw_gpu_exact_range_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, float radius,
+                                           uint64_t *d_lims, uint64_t *total)
+{
+    return exact_range_f16_impl(h, nq, d_queries, row_stride, radius, d_lims, total, true);
 }

@@ -245,7 +245,10 @@ int exact_range_guard(ivfhnsw_gpu *h, size_t nq, const void *queries, size_t row
     return rc;
 }
 
-// a call without queries: lims is the one entry 0 (on the host or on the device), and no results are held
+} // namespace
+
+namespace ivfhnsw_gpu_impl {
+
 int exact_range_none(ivfhnsw_gpu *h, uint64_t *lims, uint64_t *d_lims, uint64_t *total)
 {
     if (lims)
@@ -261,19 +264,34 @@ int exact_range_none(ivfhnsw_gpu *h, uint64_t *lims, uint64_t *d_lims, uint64_t 
     return IVFHNSW_OK;
 }
 
-// The tile map's granularity: one bit per 2^shift tiles of (32 queries, 32 rows), the finest whose map stays within a
-// sixteenth of the store -- or, on a store too small for that, the one word per (32 queries, split) that is the least.
-int exact_range_map_shift(size_t nq, size_t n, size_t d, int nsplit, size_t *bytes)
+int exact_range_map_shift(size_t nq, size_t n, size_t row_bytes, int nsplit, size_t *bytes)
 {
     const size_t strips = (nq + 31) / 32;
     int shift = 0;
     for (;; shift++) {
         const size_t words = (size_t)exact_range_map_words(n, nsplit, shift);
         *bytes = strips * nsplit * words * sizeof(uint32_t);
-        if (*bytes <= n * d / 16 || words == 1 || shift == kExactRangeMaxShift)
+        if (*bytes <= n * row_bytes / 16 || words == 1 || shift == kExactRangeMaxShift)
             return shift;
     }
 }
+
+int exact_range_total(ivfhnsw_gpu *h, const char *who, size_t len, unsigned long long *tot)
+{
+    HIP_TRY(launch_scan_excl_u32(h->stream, h->xr_slices.as<uint32_t>(), len, h->xr_part.as<uint32_t>()));
+    // the one synchronisation between the passes: the host sizes the results from the count
+    *tot = 0;
+    HIP_TRY(hipMemcpyAsync(tot, h->xr_tot.p, sizeof(*tot), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (*tot >= (1ull << 32))
+        return fail(IVFHNSW_ERR_INVALID, "%s: %llu results in one call, the limit is 2^32 - 1 (use a smaller "
+                                         "radius or fewer queries per call)", who, *tot);
+    return IVFHNSW_OK;
+}
+
+} // namespace ivfhnsw_gpu_impl
+
+namespace {
 
 // the sweep of one form over every chunk of the call's queries (h->ex_q: all of them, permuted)
 // The strip plans of a _slots call, kept for both passes: one per chunk, each of `bound` strips, chunk i's
@@ -372,33 +390,24 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
     if ((rc = exact_range_pass(h, b, cols, n, false, nq, thr, nsplit, map_shift, nullptr, nullptr, 0, rs)))
         return rc;
-    HIP_TRY(launch_scan_excl_u32(h->stream, h->xr_slices.as<uint32_t>(), len, h->xr_part.as<uint32_t>()));
-    // the one synchronisation between the passes: the host sizes the results from the count
     unsigned long long tot = 0;
-    HIP_TRY(hipMemcpyAsync(&tot, h->xr_tot.p, sizeof(tot), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (tot >= (1ull << 32))
-        return fail(IVFHNSW_ERR_INVALID, "exact_range_search: %llu results in one call, the limit is 2^32 - 1 (use a smaller "
-                                         "radius or fewer queries per call)", tot);
+    if ((rc = exact_range_total(h, "exact_range_search", len, &tot)))
+        return rc;
     // Under a windowed strip the fill pass writes a query's results in (value, row) order: they are then
     // gathered in (query, label) order into a second pair of arrays that replaces the first.
     bool windowed = false;
     for (size_t i = 0; i < win_range.size(); i += 2)
         windowed |= win_range[i + 1] > win_range[i];
     // results: in the buffers the handle holds when they are large enough, else in new ones swapped in when they are full
-    DevBuf nd, nl, rd, rl, rwork; // rd, rl: the reordered pair; rwork: the keys and permutations of its two sorts
+    RangeOut out;
+    DevBuf rd, rl, rwork; // rd, rl: the reordered pair; rwork: the keys and permutations of its two sorts
     auto release = [&] {
-        nd.release();
-        nl.release();
         rd.release();
         rl.release();
         rwork.release();
     };
-    const bool grow = tot * sizeof(float) > h->xr_dist.bytes || tot * sizeof(int64_t) > h->xr_lab.bytes;
-    if (grow && ((rc = nd.ensure(tot * sizeof(float))) || (rc = nl.ensure(tot * sizeof(int64_t))))) {
-        release();
+    if ((rc = out.reserve(h, tot)))
         return rc;
-    }
     // ... and the reordered pair with its workspace, before the fill pass writes anything: a failed allocation leaves the
     // results the handle holds as they were
     if (tot && windowed && ((rc = rd.ensure(tot * sizeof(float))) || (rc = rl.ensure(tot * sizeof(int64_t))) ||
@@ -409,13 +418,11 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
     auto fill = [&]() -> int {
         HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
         if (tot)
-            if (int e = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, grow ? nd.as<float>() : h->xr_dist.as<float>(),
-                                         grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), (size_t)tot, rs))
+            if (int e = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, out.dist(h), out.lab(h), (size_t)tot, rs))
                 return e;
         if (tot && windowed) {
             StageScope sc(h, IVFHNSW_STAGE_PLAN); // accounted apart from the two passes: the order of the results
-            HIP_TRY(launch_range_by_label(h->stream, d_lims, nq, tot, grow ? nd.as<float>() : h->xr_dist.as<float>(),
-                                          grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(), rd.as<float>(), rl.as<int64_t>(),
+            HIP_TRY(launch_range_by_label(h->stream, d_lims, nq, tot, out.dist(h), out.lab(h), rd.as<float>(), rl.as<int64_t>(),
                                           rwork.as<uint32_t>()));
         }
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -425,16 +432,13 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
         release();
         return rc;
     }
-    if (rd.p) {
+    if (rd.p) { // (the pair the fill pass wrote, where it is new, goes with `out`)
         std::swap(h->xr_dist, rd);
         std::swap(h->xr_lab, rl);
-    } else if (grow) {
-        std::swap(h->xr_dist, nd);
-        std::swap(h->xr_lab, nl);
+        out.grow = false;
     }
+    out.commit(h, tot);
     release();
-    h->xr_valid = true;
-    h->xr_total = tot;
     *total = tot;
     return IVFHNSW_OK;
 }

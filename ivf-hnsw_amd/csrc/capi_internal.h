@@ -691,6 +691,42 @@ int base_values_call(const ivfhnsw_gpu *b, const char *who, ValueRows *vr);
 // ---- capi_range.cpp
 void range_drop(ivfhnsw_gpu *h); // the handle holds no range results afterwards (buffers released)
 
+// ---- capi_exact.cpp: what the exact range searches of both kinds of store share
+// a call without queries: lims is the one entry 0 (on the host or on the device), and no results are held
+int exact_range_none(ivfhnsw_gpu *h, uint64_t *lims, uint64_t *d_lims, uint64_t *total);
+// The tile map's granularity: one bit per 2^shift tiles of (32 queries, 32 rows), the finest whose map stays within a
+// sixteenth of the store's n rows of row_bytes -- or, on a store too small for that, the one word per (32 queries, split)
+// that is the least.  *bytes: the map's.
+int exact_range_map_shift(size_t nq, size_t n, size_t row_bytes, int nsplit, size_t *bytes);
+// Between the passes: the slice counts xr_slices [len] become their exclusive prefix, and *tot the count pass's total --
+// the call's one synchronisation.  2^32 results or more: IVFHNSW_ERR_INVALID in `who`'s name, before anything is allocated.
+int exact_range_total(ivfhnsw_gpu *h, const char *who, size_t len, unsigned long long *tot);
+// Where the fill pass writes: the buffers the handle holds when they are large enough, else new ones that commit() swaps
+// in when they are full -- so an error in between leaves the earlier results as they were, and frees the new ones.
+struct RangeOut {
+    ScopedBuf nd, nl;
+    bool grow = false;
+    int reserve(ivfhnsw_gpu *h, unsigned long long tot)
+    {
+        int rc = IVFHNSW_OK;
+        grow = tot * sizeof(float) > h->xr_dist.bytes || tot * sizeof(int64_t) > h->xr_lab.bytes;
+        if (grow && !(rc = nd.ensure(tot * sizeof(float))))
+            rc = nl.ensure(tot * sizeof(int64_t));
+        return rc;
+    }
+    float *dist(const ivfhnsw_gpu *h) const { return grow ? nd.as<float>() : h->xr_dist.as<float>(); }
+    int64_t *lab(const ivfhnsw_gpu *h) const { return grow ? nl.as<int64_t>() : h->xr_lab.as<int64_t>(); }
+    void commit(ivfhnsw_gpu *h, unsigned long long tot)
+    {
+        if (grow) {
+            nd.install(h->xr_dist);
+            nl.install(h->xr_lab);
+        }
+        h->xr_valid = true;
+        h->xr_total = tot;
+    }
+};
+
 // ---- capi_upload.cpp
 int grouping_dedupe_reserve(ivfhnsw_gpu *h);
 int grouping_dedupe_dev(ivfhnsw_gpu *h, const uint32_t *d_sizes, const uint32_t *d_nn, int *dedupe);

@@ -377,6 +377,16 @@ inline int exact_range_map_words(size_t nx, int nsplit, int map_shift) { return 
 hipError_t launch_exact_range(hipStream_t s, bool fill, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t q_off, size_t nx,
                               int d, int thr, int nsplit, uint32_t *slices, unsigned long long *total, uint32_t *map,
                               int map_shift, float *dist, int64_t *labels, size_t out_cap, const SweepCols &cols = {});
+// ... of the float16 store on the f16 matrix cores (kernels_exact_f16.hip): Qh, qn = the nq queries as
+// launch_f16_store leaves rows, X, xn = the store; a row passes iff fl(fl(qn + xn) - 2 dot) < radius (any float but NaN),
+// the value launch_exact_search_f16 writes for the pair.  slices, total, map, dist, labels, out_cap, q_off: as above, the
+// map in the same words and layout -- but the fill form visits a tile iff the bit of ANY wave of the workgroup (128 queries)
+// is set, because its B tiles are staged per workgroup.  exact_range_f16_lds_bytes: the sweep's LDS per workgroup.
+size_t exact_range_f16_lds_bytes(int d);
+hipError_t launch_exact_range_f16(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                  size_t q_off, size_t nx, int d, float radius, int nsplit, uint32_t *slices,
+                                  unsigned long long *total, uint32_t *map, int map_shift, float *dist, int64_t *labels,
+                                  size_t out_cap);
 // the base filter of the exact calls (kernels_exact_filter.hip).  words: [sweep_pass_words(n)] = the label
 // bitmap bits [bit_words] (null = the empty set) cut or zero-extended to n rows, inverted with deny, bits at or beyond n
 // zero; *count (zeroed here) = the rows that pass.  rows: the passing row numbers ascending, [*count]; cnt: workspace of

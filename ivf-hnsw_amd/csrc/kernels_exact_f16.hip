@@ -88,6 +88,13 @@ __global__ __launch_bounds__(256) void f16_store_kernel(const float *__restrict_
 // that: the dot product's own rounding bends the Cauchy-Schwarz step a little, and a tile that passes the cheap test in
 // vain costs only the exact test behind it.  thr = FLT_MAX (fewer than k keys yet) gives -inf: every tile passes.
 // thr = -inf marks a row that is no query (beyond nq): nothing passes, ever.
+// The range search (exact_range_f16_kernel) sets the gate ONCE from a thr that is the caller's radius: any float, small,
+// zero or negative.  The argument holds as it stands.  A returned distance is never far below zero -- it is within
+// (d + 3) 2^-23 (|q^| + |x^|)^2 of a real squared distance, and where it is negative x^ is nearly q^, so |dist| < 2^-12 qn --
+// hence |dist| <= |thr| + 2^-12 qn whatever the sign of thr, which is the "or so" above.  The gate's own two subtractions
+// round as well, each by at most 2^-24 (qn + |thr|): with them the roundings sum to less than 1.6 * 2^-22 (qn + |thr|), a
+// tenth of the margin, so it is not widened.  thr = +inf gives -inf as FLT_MAX does; a query whose norm is not finite
+// gives a NaN gate, which nothing passes, and its distances are inf or NaN, which are below no radius.
 __device__ __forceinline__ float f16_gate(float qn, float thr)
 {
     if (thr == -INFINITY)
@@ -264,6 +271,199 @@ template <class F> hipError_t by_f16_steps(int d, F &&f)
     }
 }
 
+// ---- the range search (ivfhnsw_gpu_exact_range_search_f16) -------------------------------------------------
+// The strip and the staging of exact_f16_kernel -- 4 waves of 32 query rows, operand A resident, operand B copied once per
+// workgroup into two padded LDS tiles, the next tile's global loads in flight behind this tile's MFMAs, one barrier per
+// tile -- with the fixed gate and the two forms of exact_range_kernel (kernels_exact.hip): nothing is selected, so the two
+// tiles are all the LDS there is, and a lane keeps the counters or cursors of its 16 accumulator rows in registers.
+//   dist = fl(fl(qn + xn) - 2 acc), the k-search's; a row passes iff dist < radius; the cheap test is f16_gate(qn, radius).
+//   count (FILL = false): slices[(q_off + row) * nsplit + split] = the columns of the split that pass, *total += their sum.
+//   fill (FILL = true): the cursor of a row starts at its slice's prefix; a passing lane writes (dist, col) at the cursor +
+//       the passing lanes of its half below it.  Tiles come in increasing order: ascending label within and across splits.
+// The tile map.  The count form records, as exact_range_kernel does and in its layout, per WAVE one bit per 2^map_shift
+// tiles: did any of the wave's rows pass in them.  The int8 fill form lets each wave skip by its own bits, because each
+// wave loads its own B.  Here B is staged by the workgroup behind a barrier, so a tile is skipped by all four waves or by
+// none: the fill form visits a tile iff the OR of the bit over the workgroup's waves is set.  Every thread forms that OR
+// itself from the (at most four) waves' words, which are the same addresses for the whole workgroup, so the decision is
+// uniform without any exchange, and it is made before the tile is fetched: a skipped tile is neither loaded, staged nor
+// multiplied and costs no barrier.  The prefetch asks for the next VISITED tile (next_tile), one step ahead.
+// A wave whose 32 rows all lie beyond nq stages and meets every barrier, multiplies nothing, writes no map word, slice or
+// total -- and its map words, which need not even exist (the map has ceil(nq / 32) strips), are never read: the OR runs
+// over the waves with a row below nq only.
+template <int ND, bool FILL>
+__global__ __launch_bounds__(256) void exact_range_f16_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                              const _Float16 *__restrict__ X, const float *__restrict__ xn, int nq,
+                                                              size_t nx, float radius, size_t q_off,
+                                                              uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
+                                                              uint32_t *__restrict__ map, int map_shift, int map_words,
+                                                              float *__restrict__ out_d, long long *__restrict__ out_l, size_t out_cap)
+{
+    constexpr int D = 16 * ND, T = 256;
+    constexpr int ROWB = 2 * D + 16; // bytes of a tile's row in LDS: the row and its padding
+    constexpr int TILEB = 32 * ROWB;
+    constexpr int PPR = D / 8;               // 16-byte pieces of a row,
+    constexpr int NPIECE = 32 * PPR;         // ... of a tile,
+    constexpr int NP = (NPIECE + T - 1) / T; // ... of a thread
+    __shared__ __attribute__((aligned(16))) unsigned char s_tile[2 * TILEB];
+
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const int wg_r0 = blockIdx.x * 128, r0 = wg_r0 + wave * 32;
+    const bool active = r0 < nq; // wave-uniform; the workgroup's first wave always is
+    const int nsplit = gridDim.y, split = blockIdx.y;
+    // (the same for every wave of the workgroup: all of them meet at every barrier below)
+    size_t c_begin, c_end;
+    sweep_split_cut(nx, nsplit, split, &c_begin, &c_end);
+    const uint32_t ntiles = (uint32_t)((c_end - c_begin + 31) >> 5);
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)min(r0 + m, nq - 1) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    float qn_r[16], gate[16];
+    uint32_t cnt[16], in_rows = 0; // bit r: accumulator row r is a query
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = r0 + mfma32_row(r, kk);
+        const bool in = row < nq;
+        in_rows |= in ? 1u << r : 0u;
+        qn_r[r] = qn[min(row, nq - 1)];
+        gate[r] = f16_gate(qn_r[r], in ? radius : -INFINITY);
+        cnt[r] = FILL && in ? slices[(q_off + row) * nsplit + split] : 0u;
+    }
+
+    // The map words: this wave's own (count), and the OR over the workgroup's waves with a row below nq (fill).
+    const size_t wg_strip = (q_off + wg_r0) >> 5;
+    const int wg_waves = nq - wg_r0 >= 128 ? 4 : (nq - wg_r0 + 31) >> 5;
+    uint32_t *mw = map ? map + ((wg_strip + wave) * nsplit + split) * (size_t)map_words : nullptr;
+    uint32_t or_at = ~0u, or_word = 0; // the last word formed: a word covers 32 << map_shift tiles
+    auto wg_word = [&](uint32_t w) -> uint32_t {
+        if (w != or_at) {
+            or_at = w;
+            or_word = 0;
+            for (int v = 0; v < wg_waves; v++)
+                or_word |= map[((wg_strip + v) * nsplit + split) * (size_t)map_words + w];
+        }
+        return or_word;
+    };
+    // the first tile at or after t that is visited (ntiles or beyond: none); workgroup-uniform
+    auto next_tile = [&](uint32_t t) -> uint32_t {
+        if (!FILL || !map)
+            return t;
+        while (t < ntiles) {
+            const uint32_t g = t >> map_shift;
+            const uint32_t w = wg_word(g >> 5) >> (g & 31);
+            if (w & 1u)
+                return t;
+            t = (w ? g + (uint32_t)__ffs((int)w) - 1u : (g | 31u) + 1u) << map_shift; // the next set bit, or the next word
+        }
+        return ntiles;
+    };
+
+    // staging, as in exact_f16_kernel: thread tid takes the pieces tid, tid + T, ... of a tile; a row at or beyond c_end is
+    // not read, its pieces are zeros
+    uint4 pre[NP];
+    float pre_n = 0.f;
+    auto fetch = [&](size_t c0) {
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(X) + c0 * (size_t)(2 * D);
+        const int rows_in = c_end - c0 < 32 ? (int)(c_end - c0) : 32;
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int p = tid + i * T;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if ((NPIECE % T == 0 || p < NPIECE) && p / PPR < rows_in)
+                v = *reinterpret_cast<const uint4 *>(src + 16 * (size_t)p);
+            pre[i] = v;
+        }
+        pre_n = c0 + m < c_end ? xn[c0 + m] : 0.f;
+    };
+    auto stash = [&](int b) {
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int p = tid + i * T;
+            if (NPIECE % T == 0 || p < NPIECE)
+                *reinterpret_cast<uint4 *>(s_tile + b * TILEB + (p / PPR) * ROWB + 16 * (p % PPR)) = pre[i];
+        }
+    };
+
+    uint32_t t = next_tile(0), bits = 0;
+    float xn_cur = 0.f;
+    if (t < ntiles) {
+        fetch(c_begin + ((size_t)t << 5));
+        stash(0);
+        xn_cur = pre_n;
+    }
+    __syncthreads();
+    for (int b = 0; t < ntiles; b ^= 1) {
+        const uint32_t tn = next_tile(t + 1);
+        if (tn < ntiles)
+            fetch(c_begin + ((size_t)tn << 5)); // in flight behind this tile's MFMAs
+        bool hit = false;
+        if (active) {
+            const unsigned char *bt = s_tile + b * TILEB + m * ROWB + 16 * kk;
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int s = 0; s < ND; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], *reinterpret_cast<const f16x8 *>(bt + 32 * s), acc, 0, 0, 0);
+            const size_t col = c_begin + ((size_t)t << 5) + m;
+            const bool col_ok = col < c_end;
+            bool any = false;
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_cur) > gate[r];
+            if (__ballot(any && col_ok)) { // wave-uniform
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_cur), __fmul_rn(2.0f, acc[r]));
+                    const bool pass = col_ok && (in_rows >> r & 1u) && dist < radius;
+                    const unsigned long long mask = __ballot(pass);
+                    const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
+                    hit |= mask != 0;
+                    if (FILL) {
+                        const size_t o = (size_t)cnt[r] + __popc(half & ((1u << m) - 1u));
+                        if (pass && o < out_cap) { // (o < out_cap always: the count form counted this very lane)
+                            out_d[o] = dist;
+                            out_l[o] = (long long)col;
+                        }
+                    }
+                    cnt[r] += __popc(half);
+                }
+            }
+        }
+        if (!FILL && mw && active) {
+            const uint32_t g = t >> map_shift;
+            bits |= hit ? 1u << (g & 31) : 0u;
+            if (tn >= ntiles || (tn >> map_shift) >> 5 != g >> 5) { // the word is complete
+                if (lane == 0)
+                    mw[g >> 5] = bits;
+                bits = 0;
+            }
+        }
+        if (tn < ntiles)
+            stash(b ^ 1); // the tile every wave left at the last barrier
+        xn_cur = pre_n;
+        __syncthreads();
+        t = tn;
+    }
+    if (!FILL && active) {
+        unsigned long long sum = 0;
+        if (m == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                if (in_rows >> r & 1u)
+                    slices[(q_off + r0 + mfma32_row(r, kk)) * nsplit + split] = cnt[r];
+                sum += cnt[r];
+            }
+        }
+        sum += __shfl_xor(sum, 32);
+        if (lane == 0 && sum)
+            atomicAdd(total, sum);
+    }
+}
+
 } // namespace
 
 size_t exact_f16_lds_bytes(int d, int k)
@@ -314,6 +514,33 @@ hipError_t launch_exact_search_f16(hipStream_t s, const void *Qh, const float *q
     hipLaunchKernelGGL(exact_f16_merge_kernel, dim3((unsigned)nq), dim3(64), 0, s, part, nsplit, (int)nq, k, dists,
                        reinterpret_cast<long long *>(labels));
     return hipGetLastError();
+}
+
+size_t exact_range_f16_lds_bytes(int d) { return (size_t)2 * 32 * (2 * d + 16); }
+
+// the argument checks of launch_exact_range (kernels_exact.hip); the radius is any float but NaN
+hipError_t launch_exact_range_f16(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                  size_t q_off, size_t nx, int d, float radius, int nsplit, uint32_t *slices,
+                                  unsigned long long *total, uint32_t *map, int map_shift, float *dist, int64_t *labels,
+                                  size_t out_cap)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || radius != radius || nq > 0x7fffffffull || nx >= 0xffffffffull || nsplit < 1 ||
+        nsplit > 64 || (q_off & 31) || map_shift < 0 || map_shift > kExactRangeMaxShift)
+        return hipErrorInvalidValue;
+    const int words = sweep_map_words(nx, nsplit, map_shift);
+    // query tile is the fast index, column split the slow one, as in launch_exact_f16_t
+    const dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nsplit);
+    const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
+    long long *lab = reinterpret_cast<long long *>(labels);
+    return by_f16_steps(d, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        const auto kern = fill ? exact_range_f16_kernel<ND, true> : exact_range_f16_kernel<ND, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, qn, x, xn, (int)nq, nx, radius, q_off, slices, total, map, map_shift, words,
+                           dist, lab, out_cap);
+        return hipGetLastError();
+    });
 }
 
 } // namespace ivfhnsw_gpu_impl

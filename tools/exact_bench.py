@@ -38,12 +38,17 @@
      of random bytes as float32, k = 1, 10 and 100, alternating in one process with ivfhnsw_gpu_knn_dev on the same rows as
      float32 (k <= 80) and exact_search_dev on a uint8 store of the same rows; all three are exact on such rows and must
      agree.  Store bytes per second are those of each call's own rows (2, 4 and 1 bytes a value).
+     With --f16 --range the float16 store's exact RANGE search (ivfhnsw_gpu_exact_range_search_f16_dev) as
+     well, as 3. does for the uint8 one: at the median k = 10 and k = 100 distances and one step beyond, the call with the
+     tile map and without it ALTERNATING with the k = 1 f16 sweep, the yardstick, in one process (whole call, count pass
+     and fill pass, and the ratios to the sweep); and at the k = 100 radius the split count the rule picks beside one
+     neighbour on each side ("exact_splits").
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
                                    [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags] [--values]
-                                   [--dense-nq 512]
+                                   [--dense-nq 512] [--f16 [--range]]
                                    [--out result.json]"""
 import argparse
 import json
@@ -120,6 +125,7 @@ def main():
     ap.add_argument("--tags", action="store_true", help="add the base-tag legs (DESIGN.md 3.22)")
     ap.add_argument("--values", action="store_true", help="add the base-value legs (DESIGN.md 3.25)")
     ap.add_argument("--f16", action="store_true", help="only the float16 store's legs (DESIGN.md 3.27), at d = 128 and d = 96 on --small-rows rows")
+    ap.add_argument("--range", action="store_true", help="with --f16: add the float16 store's exact range search legs (DESIGN.md 3.28)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
     ap.add_argument("--out", default=None, help="write the whole result as JSON here")
     args = ap.parse_args()
@@ -513,6 +519,56 @@ def main():
             del sub
         g.clear_base_values()
 
+    def f16_range_splits(n, dd):
+        """exact_range_f16_splits_for (capi_base_f16.cpp) restated: the split count an nq-query call gets by the rule."""
+        blocks, resident = -(-min(nq, 16384) // 128), 256 * max(1, min(2, (160 << 10) // (64 * (2 * dd + 16))))
+        cost = [None] + [-(-blocks * s // resident) / s for s in range(1, min(64, max(1, -(-n // 4096))) + 1)]
+        return next(s for s in range(1, len(cost)) if cost[s] <= 1.05 * min(cost[1:]))
+
+    def f16_range_legs(n, dd, qf, d10, d100):
+        """The float16 range search at each radius beside the k = 1 f16 sweep, the three alternating rep by rep."""
+        od, ol = torch.empty((nq, 1), dtype=torch.float32, device=dev), torch.empty((nq, 1), dtype=torch.int64, device=dev)
+        r10, r100 = float(d10.median()), float(d100.median())
+        rule = f16_range_splits(n, dd)
+        legs = [(what, radius, -1) for what, radius in (("k=10 distance", r10), ("k=100 distance", r100), ("one step beyond", 2 * r100 - r10))]
+        legs += [("k=100 distance", r100, s) for s in (rule - 1, rule, rule + 1) if 1 <= s <= 64]
+        for what, radius, splits in legs:
+            ts, st, total = {"sweep": [], 1: [], 0: []}, {}, 0
+            for rep_i in range(args.warmup + args.reps):
+                for which in ("sweep", 1, 0):
+                    g.set_option("exact_splits", -1 if which == "sweep" else splits)
+                    g.set_option("exact_range_map", -1 if which == "sweep" else which)
+                    g.set_profiling(which != "sweep" and rep_i >= args.warmup)
+                    g.reset_stage_ms()
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    if which == "sweep":
+                        g.exact_search_f16_dev(nq, qf, dd, 1, od, ol)
+                    else:
+                        total = g.exact_range_search_f16_dev(nq, qf, dd, radius, lims)
+                    torch.cuda.synchronize(dev)
+                    if rep_i >= args.warmup:
+                        ts[which].append(time.perf_counter() - t0)
+                        if which != "sweep":
+                            ms = g.stage_ms()
+                            st.setdefault(which, []).append((ms["scan"][0] / 1e3, ms["select"][0] / 1e3))
+            g.set_profiling(False)
+            k1 = statistics.median(ts["sweep"])
+            for use_map in (1, 0):
+                t = statistics.median(ts[use_map])
+                r = {"what": "exact_range_search_f16_dev", "rows": n, "d": dd, "nq": nq, "radius": what, "radius_value": radius,
+                     "splits": splits if splits > 0 else rule, "splits_by_rule": splits < 0, "tile_map": bool(use_map), "results": total,
+                     "results_per_query": round(total / nq, 2), "seconds": round(t, 5), "reps": [round(x, 5) for x in ts[use_map]],
+                     "count_pass_s": round(statistics.median(a for a, _ in st[use_map]), 5),
+                     "fill_pass_s": round(statistics.median(b for _, b in st[use_map]), 5), "k1_sweep_s": round(k1, 5),
+                     "k1_sweep_reps": [round(x, 5) for x in ts["sweep"]]}
+                for key in ("seconds", "count_pass_s", "fill_pass_s"):
+                    r[key.replace("_s", "").replace("seconds", "total") + "_over_k1"] = round(r[key] / k1, 3)
+                result["rows"].append(r)
+                print(json.dumps(r), flush=True)
+        g.set_option("exact_splits", -1)
+        g.set_option("exact_range_map", -1)
+
     def f16_legs(n, dd):
         """The float16 store's sweep (exact_search_f16_dev) beside knn_dev on the same rows as float32 and
         exact_search_dev on a uint8 store of the same rows, alternating in one process.  The rows are random bytes, so all
@@ -532,6 +588,7 @@ def main():
         r = {"what": "upload_base_f16_dev", "rows": n, "d": dd, "seconds": round(t_up, 4), "memory_GB": round(g.memory_bytes() / 1e9, 3)}
         result["rows"].append(r)
         print(json.dumps(r), flush=True)
+        kth = {}
         for k in (1, 10, 100):
             od = torch.empty((nq, k), dtype=torch.float32, device=dev)
             ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
@@ -565,7 +622,10 @@ def main():
                     r["labels_equal"] = bool(torch.equal(ids.to(torch.int64) & 0xffffffff, ol))
                 result["rows"].append(r)
                 print(json.dumps(r), flush=True)
+            kth[k] = od[:, k - 1].clone()
         g8.close()
+        if args.range:
+            f16_range_legs(n, dd, qf, kth[10], kth[100])
         g.upload_base_f16_dev(0, dd, 0, 0, None)
         del rows, xf, qf, qb
         torch.cuda.empty_cache()

@@ -25,11 +25,14 @@ values (ivfhnsw_gpu_set_base_values) are installed and the _valu
 gets only rows whose value lies in [lo, hi], inclusive ((0, 0xffffffff): every row).
 
 With an .fvecs base and .fvecs queries (float corpora: DEEP1B) the same .ivecs is written from the float16 base store
-(upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; no filter, no --radius.
+(upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; no filter.  With
+--radius the .npz comes from ivfhnsw_gpu_exact_range_search_f16 (3.28): the rows whose float32 distance between the rounded
+vectors, the value the k-search returns, is < R.
 
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
+       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --values v.npy --query-ranges qr.npy"""
 import argparse
@@ -234,7 +237,20 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
 def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, chunk_rows=1 << 20, labels=None, deny=False,
                        info=None, tags=None, query_tags=None, values=None, query_ranges=None):
     """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
-    `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing."""
+    `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing.  An .fvecs
+    base goes to the float16 store (ivfhnsw_gpu_exact_range_search_f16), which takes none of the filters."""
+    if base_path.endswith(".fvecs"):
+        if labels is not None or tags is not None or values is not None:
+            raise ValueError("an .fvecs base goes to the float16 store, which takes no filter, tags or values")
+        img, dq = read_fvecs_image(query_path)
+        g = pkg.GpuIndex(device)
+        try:
+            n, d = g.upload_base_fvecs(base_path, rows=rows)
+            if d != dq:
+                raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+            return g.exact_range_search_f16(img[:, 1:], radius)
+        finally:
+            g.close()
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
@@ -292,8 +308,6 @@ def main(argv=None):
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
-    if args.radius is not None and args.base.endswith(".fvecs"):
-        ap.error("--radius needs a .bvecs base: the float16 store has no exact range search")
     if args.radius is not None:
         info = {}
         lims, dist, lab = ground_truth_range(pkg, args.base, args.queries, args.radius, rows=args.rows, device=args.device,
