@@ -813,8 +813,9 @@ int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first
  * ivfhnsw_gpu_rerank[_dev] serves whichever store the handle holds; against a float16 store its distance is
  * fvec_L2sqr(q, float(x^)) bit for bit -- the unrounded float32 query, the stored half widened exactly, the eight
  * accumulators and the order of utils.cpp:22-52.  ivfhnsw_gpu_exact_search_f16 and ivfhnsw_gpu_exact_range_search_f16 (below)
- * search it.  On a float16 store every uint8 exact call (exact_search*, exact_range_search*) and every set_base_* installer
- * returns IVFHNSW_ERR_STATE: it takes no filter of any kind.
+ * search it.  On a float16 store every uint8 exact call (exact_search*, exact_range_search*) returns IVFHNSW_ERR_STATE, and
+ * so do set_base_filter, set_base_filter_slot and set_base_values: of the base filters it takes tags only (set_base_tags,
+ * clear_base_tags, base_tags_info, base_tag_rows as on a uint8 store; ivfhnsw_gpu_exact_search_f16_tags searches under them).
  * ivfhnsw_gpu_base_kind: what the handle (a view: its parent) holds. */
 #define IVFHNSW_BASE_NONE 0
 #define IVFHNSW_BASE_U8 1
@@ -871,8 +872,9 @@ int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_que
  * square -- 0..127 at d <= 256 -- every operation is exact and the result is the exact distance.  A query holding a value
  * that does not round to a finite half gets padding.
  * Results ascending by (distance, label), [nq*k], padded with FLT_MAX / -1; 1 <= k <= 100, null buffers with nq > 0,
- * row_stride < d, a misaligned device pointer: IVFHNSW_ERR_INVALID; no store, a uint8 store, or a base filter, slot, tags
- * or values installed on the holder: IVFHNSW_ERR_STATE (it takes no filter, and does not ignore one).  nq is unbounded
+ * row_stride < d, a misaligned device pointer: IVFHNSW_ERR_INVALID; no store, a uint8 store, or a base filter, slot or
+ * values installed on the holder (none can be, on a float16 store): IVFHNSW_ERR_STATE.  Base tags the holder carries are
+ * ignored, as exact_search ignores them.  nq is unbounded
  * (chunks, as exact_search); the option "exact_splits" applies; a view searches its parent's store.
  * exact_search_f16: host pointers, synchronous.  exact_search_f16_dev: device pointers (queries 4-byte aligned),
  * asynchronous on the handle's stream. */
@@ -880,6 +882,17 @@ int ivfhnsw_gpu_exact_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries
                                  float *distances, int64_t *labels);
 int ivfhnsw_gpu_exact_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
                                      float *d_distances, int64_t *d_labels);
+
+/* ... with a base tag per query (set_base_tags on the float16 store): the truth of search_tags for a float
+ * corpus, with the semantics of ivfhnsw_gpu_exact_search_tags.  query_tags [nq] uint16: a query with tag t is answered as
+ * exact_search_f16 would answer it on a store holding only the rows whose base tag is t -- the same values, the labels the
+ * original row numbers; IVFHNSW_TAG_NONE searches the whole store; a tag no row carries returns -1 / FLT_MAX in every
+ * place.  query_tags == NULL is exact_search_f16 itself.  Limits, errors, chunks, views (the parent's store and tags) and
+ * "exact_splits" as exact_search_f16; _dev: d_query_tags in device memory, 2-byte aligned. */
+int ivfhnsw_gpu_exact_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                      const uint16_t *query_tags, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                          const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels);
 
 /* ---- exact range search of the base store ----------------------------------------------------------
  *

@@ -79,6 +79,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_upload_base_f16", "ivfhnsw_gpu_upload_base_f16_dev", "ivfhnsw_gpu_base_kind",
     "ivfhnsw_gpu_exact_search_f16", "ivfhnsw_gpu_exact_search_f16_dev",
     "ivfhnsw_gpu_exact_range_search_f16", "ivfhnsw_gpu_exact_range_search_f16_dev",
+    "ivfhnsw_gpu_exact_search_f16_tags", "ivfhnsw_gpu_exact_search_f16_tags_dev",
 )
 
 
@@ -269,6 +270,8 @@ def lib():
         L.ivfhnsw_gpu_exact_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_exact_search_slots_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_tags.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_tags_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_slots.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float,
                                                            C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_exact_range_search_slots_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
@@ -1362,6 +1365,27 @@ class GpuIndex:
         """The same on device buffers (torch CUDA tensors or raw addresses), asynchronous on the handle's stream."""
         _check(lib().ivfhnsw_gpu_exact_search_f16_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_distances),
                                                       _devptr(d_labels)))
+
+    def exact_search_f16_tags(self, queries_f32, k, query_tags):
+        """exact_search_f16() with a base tag per query (set_base_tags on the float16 store; ivfhnsw_gpu_exact_search_f16_tags):
+        query_tags [nq] uint16, each a tag or TAG_NONE (the whole store); None is exact_search_f16() itself."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_f16_tags(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                       _ptr(qt), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_f16_tags_dev(self, nq, d_queries, row_stride, k, d_query_tags, d_distances, d_labels):
+        """The same on device buffers (d_query_tags: [nq] uint16 in device memory), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_f16_tags_dev(self._h, nq, _devptr(d_queries), row_stride, k,
+                                                           _devptr(d_query_tags), _devptr(d_distances), _devptr(d_labels)))
 
     def exact_range_search_f16(self, queries_f32, radius):
         """Every row of the float16 base store whose distance -- the value exact_search_f16 returns for the pair -- is

@@ -113,7 +113,8 @@ int exact_f16_splits_for(size_t nq, size_t nx, size_t d, int k)
 int exact_range_f16_splits_for(size_t nq, size_t nx, size_t d) { return f16_splits_rule(nq, nx, 128, exact_range_f16_lds_bytes((int)d)); }
 
 // what every exact call on the half store checks first: the handle; the store (*b: a view searches its parent's), its
-// kind, and that the holder has nothing installed that the call would have to ignore
+// kind, and that the holder has no base filter, slots or values installed (none of them can be, on a half store: the
+// check stands for the day one can).  Base tags can; the plain calls ignore them as the uint8 store's do.
 int exact_f16_guard(ivfhnsw_gpu *h, const char *who, const char *u8_call, const ivfhnsw_gpu **b)
 {
     int rc = bind(h);
@@ -125,9 +126,21 @@ int exact_f16_guard(ivfhnsw_gpu *h, const char *who, const char *u8_call, const 
     if ((*b)->base_kind != IVFHNSW_BASE_F16)
         return fail(IVFHNSW_ERR_STATE, "%s on a uint8 store: %s serves it", who, u8_call);
     const bool slot_set = std::any_of(std::begin((*b)->bslots), std::end((*b)->bslots), [](const BaseSlot &s) { return s.mode >= 0; });
-    if ((*b)->bf_mode >= 0 || slot_set || (*b)->bt_tags.p || (*b)->bv_vals.p)
-        return fail(IVFHNSW_ERR_STATE, "%s: the holder has a base filter, slots, tags or values installed, which it does not take", who);
+    if ((*b)->bf_mode >= 0 || slot_set || (*b)->bv_vals.p)
+        return fail(IVFHNSW_ERR_STATE, "%s: the holder has a base filter, slots or values installed, which it does not take", who);
     return IVFHNSW_OK;
+}
+
+// The splits of a _tags call's two launches, for a chunk of m queries on a store of n rows.  Dense: the
+// plain call's rule fed with the most rows the Dense launch can have, the chunk's queries padded to a strip -- not with the
+// rows of every strip the plan can have, most of which are other tags': an all-NONE batch is then cut as the plain call
+// is.  Indirect: the uint8 sweep's rule (its workgroups hold the candidate buffers only, as that sweep's do) over the rows
+// of every strip and the columns of the longest row list; a shorter list cuts its own columns and leaves the splits it
+// does not reach empty.
+void exact_f16_tag_splits(const ivfhnsw_gpu *b, size_t m, int k, int *ns_dense, int *ns_ind)
+{
+    *ns_dense = exact_f16_splits_for((m + 31) / 32 * 32, b->base_n, b->base_d, k);
+    *ns_ind = b->bt_tagged ? exact_splits_for(sweep_tag_strip_bound(m, b->bt_in_use) * 32, b->bt_max_rows, k) : 1;
 }
 
 // as exact_impl of the uint8 store (capi_exact.cpp) without a column map: the chunks, the splits and the staging of a host call
@@ -176,6 +189,87 @@ int exact_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_s
         HIP_TRY(launch_f16_store(h->stream, src, src_stride, h->ex_q.p, h->ex_qn.as<float>(), m, (int)d));
         HIP_TRY(launch_exact_search_f16(h->stream, h->ex_q.p, h->ex_qn.as<float>(), b->base_rows.p, b->base_norms.as<float>(), m, n,
                                         (int)d, (int)k, nsplit, h->ex_part.as<unsigned long long>(), od, ol));
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+            // the next chunk reuses the pageable source and the staging buffers
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+    }
+    return IVFHNSW_OK;
+}
+
+// With a base tag per query: exact_impl's _tags path (capi_exact.cpp, 3.22) around the half store's two
+// kernels.  Per chunk: the tag plan (launch_tag_strip_plan, which never looks at the rows' type), the queries rounded,
+// permuted and normed into the plan's strip order in one pass, the Dense strips by the staged kernel and the Indirect ones
+// by the per-wave kernel, each under its own split count, and the merge that scatters every strip row to its query.
+int exact_f16_tags_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k, const uint16_t *query_tags,
+                        float *distances, int64_t *labels, bool on_device)
+{
+    if (!query_tags)
+        return exact_f16_impl(h, nq, queries, row_stride, k, distances, labels, on_device);
+    const char *who = on_device ? "exact_search_f16_tags_dev" : "exact_search_f16_tags";
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "exact_search_tags", &b);
+    if (rc)
+        return rc;
+    if (k < 1 || k > 100)
+        return fail(IVFHNSW_ERR_INVALID, "%s needs 1 <= k <= 100 (k %zu)", who, k);
+    if (nq == 0)
+        return IVFHNSW_OK;
+    const size_t d = b->base_d, n = b->base_n;
+    if (!queries || !distances || !labels)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null query/result buffer", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (on_device && (((uintptr_t)queries & 3) || ((uintptr_t)query_tags & 1)))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries must be 4-byte and query tags 2-byte aligned", who);
+    TagRows tr;
+    size_t in_use = 0;
+    if ((rc = base_tags_call(b, who, &tr, &in_use)))
+        return rc;
+    const unsigned forms = 1u << kSweepColsDense | (b->bt_tagged ? 1u << kSweepColsIndirect : 0u);
+
+    int ns_dense, ns_ind;
+    exact_f16_tag_splits(b, std::min(nq, kExactChunk), (int)k, &ns_dense, &ns_ind);
+    if (h->opt_exact_splits > 0)
+        ns_dense = ns_ind = h->opt_exact_splits;
+    const int nsplit = std::max(ns_dense, ns_ind);
+    // with many tags the padded rows, not the queries, size the partial tables
+    const size_t chunk = std::min(nq, sweep_tag_chunk(nsplit, k, in_use));
+    const size_t bound = sweep_tag_strip_bound(chunk, in_use), rows = bound * 32;
+    if ((rc = h->ex_q.ensure(rows * d * 2)) || (rc = h->ex_qn.ensure(rows * sizeof(float))) ||
+        (rc = h->ex_part.ensure((size_t)nsplit * rows * k * sizeof(uint64_t))) || (rc = h->bs_plan.ensure(sweep_tag_plan_bytes(bound))) ||
+        (rc = h->bt_work.ensure(tag_plan_work_words(chunk) * sizeof(uint32_t))))
+        return rc;
+    if (!on_device && ((rc = h->ex_raw.ensure(chunk * d * sizeof(float))) || (rc = h->bs_qslots.ensure(chunk * sizeof(uint16_t))) ||
+                       (rc = h->ex_dist.ensure(chunk * k * sizeof(float))) || (rc = h->ex_lab.ensure(chunk * k * sizeof(int64_t)))))
+        return rc;
+    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
+        const size_t m = std::min(chunk, nq - q0);
+        const float *src = queries + q0 * row_stride;
+        const uint16_t *dt = query_tags + q0;
+        size_t src_stride = row_stride;
+        if (!on_device) {
+            HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), src, row_stride * sizeof(float), d * sizeof(float), m,
+                                     hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, dt, m * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+            src = h->ex_raw.as<float>();
+            src_stride = d;
+            dt = h->bs_qslots.as<uint16_t>();
+        }
+        float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
+        int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
+        StripPlan sp;
+        {
+            StageScope sc(h, IVFHNSW_STAGE_PLAN); // the plan and the gather, accounted apart from the sweep
+            HIP_TRY(launch_tag_strip_plan(h->stream, dt, m, tr, h->bs_plan.p, bound, h->bt_work.as<uint32_t>(), &sp));
+            // the queries as the store holds its rows, in strip order; a padding row repeats the chunk's first query
+            HIP_TRY(launch_f16_store_rows(h->stream, src, src_stride, h->ex_q.p, h->ex_qn.as<float>(), rows, (int)d, sp.strip_rows));
+        }
+        HIP_TRY(launch_exact_search_f16_strips(h->stream, h->ex_q.p, h->ex_qn.as<float>(), b->base_rows.p, b->base_norms.as<float>(), m,
+                                               bound, n, (int)d, (int)k, ns_dense, ns_ind, h->ex_part.as<unsigned long long>(), od, ol, sp,
+                                               forms));
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -306,6 +400,20 @@ int ivfhnsw_gpu_exact_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const float *d_q
                                      float *d_distances, int64_t *d_labels)
 {
     return exact_f16_impl(h, nq, d_queries, row_stride, k, d_distances, d_labels, true);
+}
+
+// ---- with a base tag per query; query_tags == NULL is the plain call
+
+int ivfhnsw_gpu_exact_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                      const uint16_t *query_tags, float *distances, int64_t *labels)
+{
+    return exact_f16_tags_impl(h, nq, queries, row_stride, k, query_tags, distances, labels, false);
+}
+
+int ivfhnsw_gpu_exact_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                          const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels)
+{
+    return exact_f16_tags_impl(h, nq, d_queries, row_stride, k, d_query_tags, d_distances, d_labels, true);
 }
 
 int ivfhnsw_gpu_exact_range_search_f16(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, float radius,

@@ -3,7 +3,8 @@
 // query's tag}, ALLOW) installed.  The holder keeps the tag of every row and, behind it, the tagged row numbers ordered
 // by (tag, row) with their starts per tag: a tag's rows are an ascending list, which is what the Indirect column map
 // sweeps (sweep_steps.h).  Both are rebuilt by every set call -- a stable sort of the row numbers by tag.  Independent of
-// the base filter, of its slots and of the index's row tags (capi_filter.cpp), whose labels are ids.
+// the base filter, of its slots and of the index's row tags (capi_filter.cpp), whose labels are ids.  Nothing here looks at
+// the rows' type: a float16 store takes tags as a uint8 store does (capi_base_f16.cpp searches under them).
 #include "capi_internal.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -93,7 +94,7 @@ static int set_base_tags_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows, 
 
 int ivfhnsw_gpu_set_base_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, const uint16_t *tags)
 {
-    int rc = filter_holder_guard(h, kBaseFilter, "set_base_tags", true);
+    int rc = filter_holder_guard(h, kBaseFilter, "set_base_tags", true, true);
     if (rc || (rc = base_tags_args(n, rows, tags, "set_base_tags")))
         return rc;
     ScopedBuf stage_r, stage_t; // of this call only
@@ -104,7 +105,7 @@ int ivfhnsw_gpu_set_base_tags(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, co
 
 int ivfhnsw_gpu_set_base_tags_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows, const uint16_t *d_tags)
 {
-    int rc = filter_holder_guard(h, kBaseFilter, "set_base_tags_dev", true);
+    int rc = filter_holder_guard(h, kBaseFilter, "set_base_tags_dev", true, true);
     if (rc || (rc = base_tags_args(n, d_rows, d_tags, "set_base_tags_dev")))
         return rc;
     if (((uintptr_t)d_rows & 3) || ((uintptr_t)d_tags & 1))

@@ -56,7 +56,7 @@ int labels_bitmap(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t m
     return IVFHNSW_OK;
 }
 
-int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool need_upload)
+int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool need_upload, bool half_store_ok)
 {
     const bool base = kind == kBaseFilter;
     if (h && h->is_view)
@@ -67,8 +67,8 @@ int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool n
         return rc;
     if (need_upload && !(base ? h->base_n != 0 : h->has_ivf))
         return fail(IVFHNSW_ERR_STATE, "%s before %s", who, base ? "upload_base" : "upload_ivf");
-    if (need_upload && base && h->base_kind != IVFHNSW_BASE_U8)
-        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: it takes no filter, slots, tags or values", who);
+    if (need_upload && base && h->base_kind != IVFHNSW_BASE_U8 && !half_store_ok)
+        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: it takes tags, but no filter, slots or values", who);
     return IVFHNSW_OK;
 }
 

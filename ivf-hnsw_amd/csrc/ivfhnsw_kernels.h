@@ -425,6 +425,18 @@ hipError_t launch_base_tags_index(hipStream_t s, const uint16_t *tags, uint64_t 
 size_t tag_plan_work_words(size_t m);
 hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
                                  uint32_t *work, StripPlan *sp);
+// launch_exact_pad: dists / labels [total] = FLT_MAX / -1, what a query without a strip keeps.
+hipError_t launch_exact_pad(hipStream_t s, float *dists, int64_t *labels, size_t total);
+// Base tags on the float16 store (kernels_exact_f16.hip).  launch_f16_store_rows: launch_f16_store whose row
+// r comes from row row_src[r] of src (negative: row 0), the same arithmetic.  launch_exact_search_f16_strips: the sweep
+// over the queries Qh, qn [bound * 32] gathered by a tag plan sp of the chunk's nq queries; X, xn = the store of nx rows;
+// the plan's Dense strips by the staged kernel under ns_dense splits, its Indirect strips (forms bit kSweepColsIndirect) by
+// the per-wave kernel under ns_ind; part: [max(ns_dense, ns_ind)][bound * 32][k]; results at the queries' own places.
+hipError_t launch_f16_store_rows(hipStream_t s, const float *src, size_t src_stride, void *dst, float *norms, size_t count, int d,
+                                 const int32_t *row_src);
+hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                          size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
+                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms);
 // Base values (kernels_exact_filter.hip): a uint32 per row of the store, and the exact sweeps with an
 // interval per query.  launch_base_values_apply: vals[rows[i]] = v[i] for rows[i] < n; *conflict (zeroed here) != 0 when a
 // row was given two different values.  launch_base_values_index: all rows sorted stably by value (*sorted = ids_a or ids_b

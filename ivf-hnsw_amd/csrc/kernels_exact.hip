@@ -478,6 +478,15 @@ hipError_t launch_exact_search(hipStream_t s, const uint8_t *Qp, const uint8_t *
     return hipGetLastError();
 }
 
+hipError_t launch_exact_pad(hipStream_t s, float *dists, int64_t *labels, size_t total)
+{
+    if (total == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(exact_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dists, reinterpret_cast<long long *>(labels),
+                       total);
+    return hipGetLastError();
+}
+
 // ... under a strip plan: Qp [bound * 32][d] = the chunk's nq queries gathered by the plan, part
 // [nsplit][bound * 32][k]; results in the caller's order, FLT_MAX / -1 for a query without a strip
 hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const uint8_t *X, size_t nq, size_t bound, int d, int k,
@@ -491,8 +500,7 @@ hipError_t launch_exact_search_strips(hipStream_t s, const uint8_t *Qp, const ui
         return hipErrorInvalidValue;
     const int rows = (int)(bound * 32);
     long long *lab = reinterpret_cast<long long *>(labels);
-    hipLaunchKernelGGL(exact_pad_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, s, dists, lab, nq * (size_t)k);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+    if (hipError_t e = launch_exact_pad(s, dists, labels, nq * (size_t)k); e != hipSuccess)
         return e;
     const hipError_t e = by_row_steps(d, [&](auto ns) {
         constexpr int NS = decltype(ns)::value;

@@ -53,14 +53,21 @@ __global__ __launch_bounds__(256) void f16_check_kernel(const float *__restrict_
 
 // One lane per (row, quad lane t): the lane's d/4 halves, two to a word, and its share of the norm; the quad adds the four
 // shares.  The norm is that of the rounded values: fmaf chains of d/8 terms, then three additions.
+// GATHER (the queries of a strip plan): row r comes from row row_src[r] of src, a negative entry -- the
+// padding of a strip -- from row 0; the arithmetic is the same text, so a gathered row is the row the plain form makes.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void f16_store_kernel(const float *__restrict__ src, size_t src_stride, _Float16 *__restrict__ dst,
-                                                        float *__restrict__ norms, size_t count, int d)
+                                                        float *__restrict__ norms, size_t count, int d,
+                                                        const int32_t *__restrict__ row_src)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t r = i >> 2;
     const int t = (int)(i & 3);
     const bool ok = r < count; // (the four lanes of a quad agree)
-    const float *row = src + (ok ? r : 0) * src_stride + 2 * t;
+    size_t from = ok ? r : 0;
+    if constexpr (GATHER)
+        from = (size_t)max(row_src[from], 0);
+    const float *row = src + from * src_stride + 2 * t;
     uint32_t *out = reinterpret_cast<uint32_t *>(dst + (ok ? r : 0) * (size_t)d + t * (d >> 2));
     float alo = 0.f, ahi = 0.f;
     for (int j = 0; j < (d >> 3); j++) {
@@ -102,14 +109,59 @@ __device__ __forceinline__ float f16_gate(float qn, float thr)
     return __fsub_rn(__fsub_rn(qn, thr), __fmul_rn(0x1p-18f, __fadd_rn(qn, fabsf(thr))));
 }
 
+// What a wave of the per-wave sweep (exact_f16_rows_kernel) does with a multiplied tile: acc[r] = q^.x^ of row
+// mfma32_row(r, kk) and the lane's column, whose norm is xn_col and whose label is `label`; col_ok: the lane has a column.
+// The common tile costs the cheap test; behind it the exact test, the append, the compaction of the rows that could
+// overflow and the new gates -- the steps of exact_f16_kernel's loop in its arithmetic, operation for operation.  That
+// kernel keeps them in its own body: called from there, this function costs its plain instantiations 6 to 17 registers
+// and, at d = 96 and d = 192, a wave of occupancy (the compiler's report).
+template <int CAP>
+__device__ __forceinline__ void f16_select(const f32x16 &acc, float xn_col, bool col_ok, uint32_t label, const float (&qn_r)[16],
+                                           float (&gate)[16], unsigned long long *buf, uint32_t *cnt, float *thr_s, int k, int lane)
+{
+    const int m = lane & 31, kk = lane >> 5;
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_col) > gate[r];
+    if (__ballot(any && col_ok)) { // wave-uniform: rare once the thresholds have settled
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_col), __fmul_rn(2.0f, acc[r]));
+            const int row = mfma32_row(r, kk);
+            const bool pass = col_ok && dist < thr_s[row];
+            const unsigned long long mask = __ballot(pass);
+            if (mask)
+                row_append<CAP>(buf, cnt, row, pass, mask, dist, label, m, kk);
+        }
+        rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+    }
+}
+
 // ND = d / 16, the MFMA steps of a row; CAP = keys of a row's candidate buffer (a row is compacted when it holds more than
 // CAP - 32); WAVES = 32-row strips per workgroup.  Qh [nq][d] the queries as the store holds its rows, qn [nq] their norms;
 // X [nx][d], xn [nx] the store.
-template <int ND, int CAP, int WAVES>
+// SP: F16Rows is the plain call.  F16DenseStrips (base tags): Qh, qn are the nq = 32 * bound rows of a strip
+// plan, and workgroup i owns the strips [WAVES i, WAVES i + WAVES) of the plan's Dense range -- the untagged queries, which
+// sweep the whole store and so share its staging.  A workgroup beyond the range leaves before the first barrier; a wave
+// beyond it in a workgroup that stays stages and meets every barrier, multiplies nothing and writes nothing
+// (exact_range_f16_kernel's `active`); a padding row of a strip holds the threshold of a row beyond nq.
+struct F16Rows {
+    static constexpr bool kStrips = false;
+};
+struct F16DenseStrips {
+    static constexpr bool kStrips = true;
+    StripPlan sp;
+};
+
+template <int ND, int CAP, int WAVES, class SP>
 __global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
                                                                const _Float16 *__restrict__ X, const float *__restrict__ xn,
                                                                int nq, size_t nx, int k, size_t cols_per_split,
-                                                               unsigned long long *__restrict__ out_keys)
+                                                               unsigned long long *__restrict__ out_keys, SP sp)
 {
     constexpr int D = 16 * ND, T = 64 * WAVES;
     constexpr int ROWB = 2 * D + 16;        // bytes of a tile's row in LDS: the row and its padding
@@ -125,7 +177,15 @@ __global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *_
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int m = lane & 31, kk = lane >> 5;
-    const int r0 = blockIdx.x * (32 * WAVES) + wave * 32;
+    int r0 = blockIdx.x * (32 * WAVES) + wave * 32;
+    bool active = true; // wave-uniform
+    if constexpr (SP::kStrips) {
+        const uint32_t s0 = sp.sp.hdr->lay.range[kSweepColsDense][0] + blockIdx.x * WAVES, s1 = sp.sp.hdr->lay.range[kSweepColsDense][1];
+        if (s0 >= s1)
+            return;
+        active = s0 + wave < s1;
+        r0 = (int)((active ? s0 + wave : s0) << 5);
+    }
     // (the same for every wave of the workgroup: all of them meet at every barrier below)
     const size_t c_begin = (size_t)blockIdx.y * cols_per_split < nx ? (size_t)blockIdx.y * cols_per_split : nx;
     const size_t c_end = c_begin + cols_per_split < nx ? c_begin + cols_per_split : nx;
@@ -143,8 +203,11 @@ __global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *_
             a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
     }
     if (lane < 32) {
+        bool is_query = r0 + lane < nq;
+        if constexpr (SP::kStrips)
+            is_query = active && sp.sp.strip_rows[r0 + lane] >= 0;
         cnt[lane] = 0;
-        thr_s[lane] = r0 + lane < nq ? FLT_MAX : -INFINITY;
+        thr_s[lane] = is_query ? FLT_MAX : -INFINITY;
     }
     __builtin_amdgcn_wave_barrier();
     float qn_r[16], gate[16];
@@ -193,31 +256,33 @@ __global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *_
         const bool more = c0 + 32 < c_end;
         if (more)
             fetch(c0 + 32); // in flight behind this tile's MFMAs
-        const unsigned char *bt = s_tile + b * TILEB + m * ROWB + 16 * kk;
-        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (active) {
+            const unsigned char *bt = s_tile + b * TILEB + m * ROWB + 16 * kk;
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < ND; s++)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], *reinterpret_cast<const f16x8 *>(bt + 32 * s), acc, 0, 0, 0);
-        const size_t col = c0 + m;
-        const bool col_ok = col < c_end;
-        bool any = false;
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-            any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_cur) > gate[r];
-        if (__ballot(any && col_ok)) { // wave-uniform: rare once the thresholds have settled
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_cur), __fmul_rn(2.0f, acc[r]));
-                const int row = mfma32_row(r, kk);
-                const bool pass = col_ok && dist < thr_s[row];
-                const unsigned long long mask = __ballot(pass);
-                if (mask)
-                    row_append<CAP>(buf, cnt, row, pass, mask, dist, (uint32_t)col, m, kk);
-            }
-            rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+            for (int s = 0; s < ND; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], *reinterpret_cast<const f16x8 *>(bt + 32 * s), acc, 0, 0, 0);
+            const size_t col = c0 + m;
+            const bool col_ok = col < c_end;
+            bool any = false;
 #pragma unroll
             for (int r = 0; r < 16; r++)
-                gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+                any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_cur) > gate[r];
+            if (__ballot(any && col_ok)) { // wave-uniform: rare once the thresholds have settled
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_cur), __fmul_rn(2.0f, acc[r]));
+                    const int row = mfma32_row(r, kk);
+                    const bool pass = col_ok && dist < thr_s[row];
+                    const unsigned long long mask = __ballot(pass);
+                    if (mask)
+                        row_append<CAP>(buf, cnt, row, pass, mask, dist, (uint32_t)col, m, kk);
+                }
+                rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+            }
         }
         if (more)
             stash(b ^ 1); // the tile every wave left at the last barrier
@@ -226,7 +291,8 @@ __global__ __launch_bounds__(64 * WAVES) void exact_f16_kernel(const _Float16 *_
     }
 
     // out: [split][nq][k] keys
-    rows_write_out<CAP>(buf, cnt, k, lane, nq - r0, out_keys, (size_t)blockIdx.y * nq + r0);
+    if (active)
+        rows_write_out<CAP>(buf, cnt, k, lane, nq - r0, out_keys, (size_t)blockIdx.y * nq + r0);
 }
 
 __global__ __launch_bounds__(64) void exact_f16_merge_kernel(const unsigned long long *__restrict__ part, int nsplit, int nq, int k,
@@ -244,17 +310,190 @@ __global__ __launch_bounds__(64) void exact_f16_merge_kernel(const unsigned long
         });
 }
 
-template <int ND, int CAP, int WAVES>
+// sp: F16Rows{} -- the nq queries in their order -- or F16DenseStrips{plan}: nq = the plan's rows, the grid covers every strip
+// the plan can have and the workgroups beyond its Dense range leave at once
+template <int ND, int CAP, int WAVES, class SP>
 hipError_t launch_exact_f16_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn, int nq,
-                              size_t nx, int k, int nsplit, size_t cols_per_split, unsigned long long *part)
+                              size_t nx, int k, int nsplit, size_t cols_per_split, unsigned long long *part, SP sp)
 {
     const size_t shm = exact_f16_lds_bytes(16 * ND, k);
-    constexpr auto kern = exact_f16_kernel<ND, CAP, WAVES>;
+    constexpr auto kern = exact_f16_kernel<ND, CAP, WAVES, SP>;
     if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
         return e;
     // query tile is the fast index, column split the slow one: the workgroups that run together stream the same columns
     hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 32 * WAVES - 1) / (32 * WAVES)), (unsigned)nsplit), dim3(64 * WAVES), shm, s,
-                       Qh, qn, X, xn, nq, nx, k, cols_per_split, part);
+                       Qh, qn, X, xn, nq, nx, k, cols_per_split, part, sp);
+    return hipGetLastError();
+}
+
+// ---- the tagged strips (ivfhnsw_gpu_exact_search_f16_tags) -----------------------------------------------
+// An Indirect strip of a tag plan sweeps its tag's row list, and the strips of a workgroup sweep different lists: there is no
+// tile to share, so a strip is a wave, there is no barrier and no LDS tile, and a wave without a strip, or whose split of a
+// short list is empty, leaves at once (the merge reads only the splits that have columns).  Operand A is resident as in
+// exact_f16_kernel.  For a tile of 32 columns lane (m, kk) reads rows[c0 + m] -- ascending, so the row number is the
+// column's label -- and takes its operand B straight from the store: piece s is the 16 bytes at row * 2d + 32 s + 16 kk,
+// the address pattern exact_f16_kernel reads from its LDS row; the store's quad permutation lays a row out in MFMA order,
+// and over the ND steps the two lanes of a column consume the row's 2d contiguous bytes whole.  The column's norm is
+// xn[row].  In flight behind the MFMAs of tile t: the row numbers of tile t + 2, the norms and the first NPRE pieces of
+// tile t + 1 (two register buffers, the loop unrolled by two so that nothing is copied).  NPRE = ND up to d = 128; beyond
+// it half the pieces, the other half loaded when their tile begins and in flight behind the MFMAs of its first half: 1.5 ND
+// pieces live instead of 2 ND, which is what keeps ND = 16 within the registers of two waves per SIMD.
+// A column at or beyond c_end is not read -- its pieces are zeros -- and never passes.
+template <int ND, int CAP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void exact_f16_rows_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                                    const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                                    int nrows, int k, unsigned long long *__restrict__ out_keys,
+                                                                    StripPlan sp)
+{
+    constexpr int D = 16 * ND;
+    constexpr int NPRE = ND <= 8 ? ND : (ND + 1) / 2, NLATE = ND - NPRE;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *s_buf = reinterpret_cast<unsigned long long *>(smem); // [WAVES][32][CAP]
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_buf + WAVES * 32 * CAP);  // [WAVES][32]
+    float *s_thr = reinterpret_cast<float *>(s_cnt + WAVES * 32);             // [WAVES][32]
+
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const uint32_t strip = sp.hdr->lay.range[kSweepColsIndirect][0] + blockIdx.x * WAVES + wave;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][1])
+        return;
+    const StripCols e = sp.strip_cols[strip];
+    size_t c_begin, c_end;
+    sweep_split_cut(e.nx, (int)gridDim.y, (int)blockIdx.y, &c_begin, &c_end);
+    if (c_begin >= c_end)
+        return;
+    const uint32_t *__restrict__ rows = e.data;
+    const int r0 = (int)(strip << 5); // (strip < the plan's bound: every row of it exists in Qh, qn and strip_rows)
+    unsigned long long *buf = s_buf + (size_t)wave * 32 * CAP;
+    uint32_t *cnt = s_cnt + wave * 32;
+    float *thr_s = s_thr + wave * 32;
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)(r0 + m) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    if (lane < 32) {
+        cnt[lane] = 0;
+        thr_s[lane] = sp.strip_rows[r0 + lane] >= 0 ? FLT_MAX : -INFINITY;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float qn_r[16], gate[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        qn_r[r] = qn[r0 + row];
+        gate[r] = f16_gate(qn_r[r], thr_s[row]);
+    }
+
+    const unsigned char *xb = reinterpret_cast<const unsigned char *>(X) + 16 * kk;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the row number of the lane's column of the tile that begins at c0
+    auto ids = [&](size_t c0) -> uint32_t { return c0 + m < c_end ? rows[c0 + m] : 0u; };
+    // pieces [first, first + N) of store row `row` into w; ok: the lane has a column
+    auto pieces = [&](uint32_t row, bool ok, int first, auto &w) {
+        constexpr int N = (int)(sizeof(w) / sizeof(w[0]));
+        const unsigned char *p = xb + (size_t)row * (2 * D) + 32 * first;
+#pragma unroll
+        for (int s = 0; s < N; s++)
+            w[s] = zero;
+        if (ok) {
+#pragma unroll
+            for (int s = 0; s < N; s++)
+                w[s] = *reinterpret_cast<const f16x8 *>(p + 32 * s);
+        }
+    };
+    // The tile at c0: `cur`, n_cur = its first NPRE pieces and its norms, id_cur its row numbers.  Starts the loads of tile
+    // c0 + 32 (row numbers id_nxt) into nxt, n_nxt and of the row numbers of tile c0 + 64 into id_ahead.
+    auto tile = [&](size_t c0, const f16x8 (&cur)[NPRE], float n_cur, uint32_t id_cur, f16x8 (&nxt)[NPRE], float &n_nxt, uint32_t id_nxt,
+                    uint32_t &id_ahead) {
+        const bool col_ok = c0 + m < c_end;
+        f16x8 late[NLATE > 0 ? NLATE : 1];
+        if constexpr (NLATE > 0)
+            pieces(id_cur, col_ok, NPRE, late);
+        if (c0 + 32 < c_end) { // in flight behind this tile's MFMAs
+            const bool ok = c0 + 32 + m < c_end;
+            pieces(id_nxt, ok, 0, nxt);
+            n_nxt = ok ? xn[id_nxt] : 0.f;
+        }
+        if (c0 + 64 < c_end)
+            id_ahead = ids(c0 + 64);
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < NPRE; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], cur[s], acc, 0, 0, 0);
+        if constexpr (NLATE > 0) {
+#pragma unroll
+            for (int s = 0; s < NLATE; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPRE + s], late[s], acc, 0, 0, 0);
+        }
+        f16_select<CAP>(acc, n_cur, col_ok, id_cur, qn_r, gate, buf, cnt, thr_s, k, lane);
+    };
+
+    f16x8 b0[NPRE], b1[NPRE];
+    float n0, n1 = 0.f;
+    uint32_t id0 = ids(c_begin), id1 = 0, id_ahead = 0;
+    pieces(id0, c_begin + m < c_end, 0, b0);
+    n0 = c_begin + m < c_end ? xn[id0] : 0.f;
+    if (c_begin + 32 < c_end)
+        id1 = ids(c_begin + 32);
+    for (size_t c0 = c_begin;;) {
+        tile(c0, b0, n0, id0, b1, n1, id1, id_ahead);
+        if ((c0 += 32) >= c_end)
+            break;
+        id0 = id_ahead;
+        tile(c0, b1, n1, id1, b0, n0, id0, id_ahead);
+        if ((c0 += 32) >= c_end)
+            break;
+        id1 = id_ahead;
+    }
+
+    // out: [split][plan row][k] keys, every row of the strip (a padding row holds nothing)
+    rows_write_out<CAP>(buf, cnt, k, lane, 32, out_keys, (size_t)blockIdx.y * nrows + r0);
+}
+
+// The merge under a tag plan, one wavefront per plan row (exact_merge_strips_kernel with float keys): the row of a query
+// goes to the query's place in the caller's order, padding rows and strips beyond the plan's are dropped.  part
+// [split][nrows][k]; a Dense strip wrote ns_dense splits, an Indirect one the splits of ns_ind that have columns of its list.
+__global__ __launch_bounds__(64) void exact_f16_merge_strips_kernel(const unsigned long long *__restrict__ part, int ns_dense,
+                                                                    int ns_ind, int nrows, int k, float *__restrict__ dists,
+                                                                    long long *__restrict__ labels, StripPlan sp)
+{
+    const uint32_t row = blockIdx.x, strip = row >> 5;
+    if (strip >= sp.hdr->lay.nstrips)
+        return;
+    const int q = sp.strip_rows[row];
+    if (q < 0)
+        return;
+    int ns = ns_dense;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][0]) {
+        const size_t nx = sp.strip_cols[strip].nx, cps = sweep_cols_per_split(nx, ns_ind);
+        ns = (int)min((size_t)ns_ind, (nx + cps - 1) / cps);
+    }
+    sweep_merge_row(
+        part, ns, nrows, k, (int)row, q,
+        [&](size_t o, unsigned long long key) {
+            labels[o] = (long long)(uint32_t)key;
+            dists[o] = orderable_f32((uint32_t)(key >> 32));
+        },
+        [&](size_t o) { // fewer than k rows carry the query's tag
+            labels[o] = -1ll;
+            dists[o] = FLT_MAX;
+        });
+}
+
+template <int ND, int CAP, int WAVES>
+hipError_t launch_exact_f16_rows_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn, size_t bound,
+                                   int k, int nsplit, unsigned long long *part, const StripPlan &sp)
+{
+    const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(float));
+    constexpr auto kern = exact_f16_rows_kernel<ND, CAP, WAVES>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((bound + WAVES - 1) / WAVES), (unsigned)nsplit), dim3(64 * WAVES), shm, s, Qh, qn, X, xn,
+                       (int)(bound * 32), k, part, sp);
     return hipGetLastError();
 }
 
@@ -487,8 +726,20 @@ hipError_t launch_f16_store(hipStream_t s, const float *src, size_t src_stride, 
         return hipSuccess;
     if (d < 16 || d > 256 || (d & 15) || count > ((size_t)1 << 36))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(f16_store_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, s, src, src_stride,
-                       reinterpret_cast<_Float16 *>(dst), norms, count, d);
+    hipLaunchKernelGGL(f16_store_kernel<false>, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, s, src, src_stride,
+                       reinterpret_cast<_Float16 *>(dst), norms, count, d, (const int32_t *)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_f16_store_rows(hipStream_t s, const float *src, size_t src_stride, void *dst, float *norms, size_t count, int d,
+                                 const int32_t *row_src)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || count > ((size_t)1 << 36) || !row_src)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(f16_store_kernel<true>, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, s, src, src_stride,
+                       reinterpret_cast<_Float16 *>(dst), norms, count, d, row_src);
     return hipGetLastError();
 }
 
@@ -505,14 +756,52 @@ hipError_t launch_exact_search_f16(hipStream_t s, const void *Qh, const float *q
     const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
     const hipError_t e = by_f16_steps(d, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        return k <= 16   ? launch_exact_f16_t<ND, 48, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part)
-               : k <= 32 ? launch_exact_f16_t<ND, 64, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part)
-                         : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part);
+        return k <= 16   ? launch_exact_f16_t<ND, 48, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part, F16Rows{})
+               : k <= 32 ? launch_exact_f16_t<ND, 64, 4>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part, F16Rows{})
+                         : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, (int)nq, nx, k, nsplit, cps, part, F16Rows{});
     });
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(exact_f16_merge_kernel, dim3((unsigned)nq), dim3(64), 0, s, part, nsplit, (int)nq, k, dists,
                        reinterpret_cast<long long *>(labels));
+    return hipGetLastError();
+}
+
+// ... under a tag plan: Qh, qn [bound * 32] = the chunk's nq queries gathered by the plan
+// (launch_f16_store_rows), part [max(ns_dense, ns_ind)][bound * 32][k]; the Dense strips by the staged kernel under ns_dense
+// splits, the Indirect ones (forms bit kSweepColsIndirect) by the per-wave kernel under ns_ind; results in the caller's
+// order, FLT_MAX / -1 for a query without a strip
+hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                          size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
+                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms)
+{
+    if (nq == 0)
+        return hipSuccess;
+    if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || bound == 0 || bound > (0x7fffffffull >> 5) || nx == 0 || nx >= 0xffffffffull ||
+        ns_dense < 1 || ns_dense > 64 || ns_ind < 1 || ns_ind > 64 || !sp.hdr || !sp.strip_rows || !sp.strip_cols)
+        return hipErrorInvalidValue;
+    const int rows = (int)(bound * 32);
+    if (hipError_t e = launch_exact_pad(s, dists, labels, nq * (size_t)k); e != hipSuccess)
+        return e;
+    const size_t cps = sweep_cols_per_split(nx, ns_dense);
+    const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
+    const bool indirect = forms >> kSweepColsIndirect & 1u;
+    const hipError_t e = by_f16_steps(d, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        const F16DenseStrips ds{sp};
+        hipError_t e = k <= 16   ? launch_exact_f16_t<ND, 48, 4>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds)
+                       : k <= 32 ? launch_exact_f16_t<ND, 64, 4>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds)
+                                 : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds);
+        if (e != hipSuccess || !indirect)
+            return e;
+        return k <= 16   ? launch_exact_f16_rows_t<ND, 48, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp)
+               : k <= 32 ? launch_exact_f16_rows_t<ND, 64, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp)
+                         : launch_exact_f16_rows_t<ND, 136, 2>(s, q, qn, x, xn, bound, k, ns_ind, part, sp);
+    });
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(exact_f16_merge_strips_kernel, dim3((unsigned)rows), dim3(64), 0, s, part, ns_dense, ns_ind, rows, k, dists,
+                       reinterpret_cast<long long *>(labels), sp);
     return hipGetLastError();
 }
 

@@ -43,12 +43,16 @@
      tile map and without it ALTERNATING with the k = 1 f16 sweep, the yardstick, in one process (whole call, count pass
      and fill pass, and the ratios to the sweep); and at the k = 100 radius the split count the rule picks beside one
      neighbour on each side ("exact_splits").
+     With --f16 --tags base tags on the float16 store (ivfhnsw_gpu_exact_search_f16_tags_dev) at d = 128:
+     with 32 and with 1 024 tags, k = 1 and 100, the tagged call under the rule's split count and under its two neighbours
+     ALTERNATING with exact_search_tags_dev on the uint8 store of the same rows (the two must agree); and the all-NONE batch
+     alternating with the plain exact_search_f16_dev, its plan stage (plan and gather) from the stage profiler.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
                                    [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags] [--values]
-                                   [--dense-nq 512] [--f16 [--range]]
+                                   [--dense-nq 512] [--f16 [--range] [--tags]]
                                    [--out result.json]"""
 import argparse
 import json
@@ -569,6 +573,87 @@ def main():
         g.set_option("exact_splits", -1)
         g.set_option("exact_range_map", -1)
 
+    def f16_tags_legs(n, dd, g8, qf, qb):
+        """Base tags on the float16 store (exact_search_f16_tags_dev) on the rows f16_legs uploaded to both
+        stores, the calls of a leg alternating rep by rep in one process.  Per tag count (row i carries tag i % ntags, query
+        q asks for q % ntags) and k: the tagged call under the rule's split count and under its neighbours beside
+        exact_search_tags_dev on the uint8 store; then the all-NONE batch beside the plain exact_search_f16_dev, with the
+        plan stage (the plan and the gather) timed by the stage profiler."""
+        def alternate(calls, what):
+            ts = {name: [] for name, _ in calls}
+            for rep in range(args.warmup + args.reps):
+                for name, fn in calls:
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize(dev)
+                    if rep >= args.warmup:
+                        ts[name].append(time.perf_counter() - t0)
+                    log("[exact_bench] f16 tags %s rep %d %s: %.4f s" % (what, rep, name, time.perf_counter() - t0))
+            return ts
+
+        def with_splits(s, fn):
+            g.set_option("exact_splits", s)
+            fn()
+            g.set_option("exact_splits", -1)
+
+        for ntags in (32, 1024):
+            btags = (torch.arange(n, device=dev, dtype=torch.int32) % ntags).to(torch.int16)
+            rows_i = torch.arange(n, device=dev, dtype=torch.int32)
+            qt = (torch.arange(nq, device=dev, dtype=torch.int32) % ntags).to(torch.int16)
+            torch.cuda.synchronize(dev)
+            g.set_base_tags_dev(n, rows_i, btags)
+            g8.set_base_tags_dev(n, rows_i, btags)
+            for k in (1, 100):
+                od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+                od8, ol8 = torch.empty_like(od), torch.empty_like(ol)
+                # the rule of the Indirect launch (capi_base_f16.cpp exact_f16_tag_splits), restated
+                bound, rpb = nq // 32 + min(nq, ntags + 1), 128 if k <= 32 else 64
+                blocks, longest = -(-bound * 32 // rpb), -(-n // ntags)
+                rule = max(1, min(64, -(-512 // blocks), -(-longest // 4096)))
+                tagged = lambda: g.exact_search_f16_tags_dev(nq, qf, dd, k, qt, od, ol)
+                calls = [("exact_search_f16_tags_dev", tagged),
+                         ("exact_search_tags_dev (uint8 store)", lambda: g8.exact_search_tags_dev(nq, qb, dd, k, qt, od8, ol8))]
+                calls += [("exact_search_f16_tags_dev, %d splits" % s, lambda s=s: with_splits(s, tagged))
+                          for s in (rule - 1, rule + 1) if 1 <= s <= 64]
+                ts = alternate(calls, "%d tags k=%d" % (ntags, k))
+                tagged()
+                torch.cuda.synchronize(dev)
+                assert torch.equal(ol, ol8) and torch.equal(od, od8), "the float16 and the uint8 tagged sweep disagree on integer rows"
+                base_t = statistics.median(ts["exact_search_f16_tags_dev"])
+                for name, _ in calls:
+                    t = statistics.median(ts[name])
+                    r = {"what": name, "rows": n, "d": dd, "nq": nq, "k": k, "tags": ntags, "rule_splits": rule, "seconds": round(t, 5),
+                         "reps": [round(x, 5) for x in ts[name]], "over_f16_tags": round(t / base_t, 3)}
+                    result["rows"].append(r)
+                    print(json.dumps(r), flush=True)
+        none = torch.full((nq,), -1, dtype=torch.int16, device=dev)  # 0xffff: every query untagged
+        for k in (1, 100):
+            od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            odp, olp = torch.empty_like(od), torch.empty_like(ol)
+            plan_ms = []
+
+            def all_none():
+                g.set_profiling(True)
+                g.reset_stage_ms()
+                g.exact_search_f16_tags_dev(nq, qf, dd, k, none, od, ol)
+                torch.cuda.synchronize(dev)
+                plan_ms.append(g.stage_ms()["plan"][0])
+                g.set_profiling(False)
+
+            ts = alternate([("exact_search_f16_tags_dev, all NONE", all_none),
+                            ("exact_search_f16_dev", lambda: g.exact_search_f16_dev(nq, qf, dd, k, odp, olp))], "all NONE k=%d" % k)
+            assert torch.equal(ol, olp) and torch.equal(od, odp), "the all-NONE batch and the plain call disagree"
+            a, b = ts["exact_search_f16_tags_dev, all NONE"], ts["exact_search_f16_dev"]
+            r = {"what": "all NONE beside the plain call", "rows": n, "d": dd, "nq": nq, "k": k, "all_none_seconds": round(statistics.median(a), 5),
+                 "plain_seconds": round(statistics.median(b), 5), "plain_span": [round(min(b), 5), round(max(b), 5)],
+                 "all_none_reps": [round(x, 5) for x in a], "plan_and_gather_ms": round(statistics.median(plan_ms[args.warmup:]), 4)}
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+        g.clear_base_tags()
+
     def f16_legs(n, dd):
         """The float16 store's sweep (exact_search_f16_dev) beside knn_dev on the same rows as float32 and
         exact_search_dev on a uint8 store of the same rows, alternating in one process.  The rows are random bytes, so all
@@ -623,6 +708,8 @@ def main():
                 result["rows"].append(r)
                 print(json.dumps(r), flush=True)
             kth[k] = od[:, k - 1].clone()
+        if args.tags and dd == 128:
+            f16_tags_legs(n, dd, g8, qf, qb)
         g8.close()
         if args.range:
             f16_range_legs(n, dd, qf, kth[10], kth[100])
