@@ -894,6 +894,21 @@ int ivfhnsw_gpu_exact_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *qu
 int ivfhnsw_gpu_exact_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
                                           const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels);
 
+/* ... and the range form under them: the truth of range_search_tags for a float corpus, with the semantics
+ * of ivfhnsw_gpu_exact_range_search_tags.  A query with tag t gets every row whose base tag is t and whose distance -- the
+ * value exact_search_f16_tags and exact_range_search_f16 (below) write for the pair, bit for bit -- is < radius (strict), in
+ * ascending label; IVFHNSW_TAG_NONE searches the whole store; a tag no row carries returns nothing.  lims [nq + 1] and the
+ * results stand in the caller's query order and are read through ivfhnsw_gpu_exact_range_results[_dev].  query_tags == NULL
+ * is exact_range_search_f16 itself.  Radius, limits (131 072 queries a call), errors, memory, the one synchronisation and the
+ * options "exact_splits" and "exact_range_map" as exact_range_search_f16 -- but base tags on the holder are what this call
+ * is for, and a set_base_filter filter -> IVFHNSW_ERR_STATE; the queries are kept in strips of 32 of one tag (at most nq / 32
+ * + the tags in use + 1 strips per 16 384 queries), which is what the query memory and the tile map count.  A view searches
+ * its parent's store under its parent's tags.  _dev: d_query_tags in device memory, 2-byte aligned. */
+int ivfhnsw_gpu_exact_range_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride,
+                                            const uint16_t *query_tags, float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride,
+                                                const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
+
 /* ---- exact range search of the base store ----------------------------------------------------------
  *
  * Every row of the base store (upload_base) within a radius of each of nq queries: the true answer to the question

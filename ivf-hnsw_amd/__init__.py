@@ -80,6 +80,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_search_f16", "ivfhnsw_gpu_exact_search_f16_dev",
     "ivfhnsw_gpu_exact_range_search_f16", "ivfhnsw_gpu_exact_range_search_f16_dev",
     "ivfhnsw_gpu_exact_search_f16_tags", "ivfhnsw_gpu_exact_search_f16_tags_dev",
+    "ivfhnsw_gpu_exact_range_search_f16_tags", "ivfhnsw_gpu_exact_range_search_f16_tags_dev",
 )
 
 
@@ -284,6 +285,8 @@ def lib():
         L.ivfhnsw_gpu_exact_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_tags.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_tags_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16_tags.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16_tags_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_set_base_values.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ivfhnsw_gpu_set_base_values_dev.argtypes = L.ivfhnsw_gpu_set_base_values.argtypes
         L.ivfhnsw_gpu_clear_base_values.argtypes = [C.c_void_p]
@@ -1411,6 +1414,33 @@ class GpuIndex:
         total = C.c_uint64(0)
         _check(lib().ivfhnsw_gpu_exact_range_search_f16_dev(self._h, nq, _devptr(d_queries), row_stride, C.c_float(radius),
                                                             _devptr(d_lims), C.byref(total)))
+        return int(total.value)
+
+    def exact_range_search_f16_tags(self, queries_f32, radius, query_tags):
+        """exact_range_search_f16() with a base tag per query (set_base_tags on the float16 store;
+        ivfhnsw_gpu_exact_range_search_f16_tags): query_tags [nq] uint16, each a tag or TAG_NONE (the whole store); None is
+        exact_range_search_f16() itself.  lims in the caller's query order."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16_tags(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                             _ptr(qt), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_f16_tags_dev(self, nq, d_queries, row_stride, d_query_tags, radius, d_lims):
+        """The same on device buffers (d_query_tags: [nq] uint16 in device memory); returns the number of results, which
+        stay in the handle's memory."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16_tags_dev(self._h, nq, _devptr(d_queries), row_stride,
+                                                                 _devptr(d_query_tags), C.c_float(radius), _devptr(d_lims),
+                                                                 C.byref(total)))
         return int(total.value)
 
     def rerank(self, queries, cand, k):

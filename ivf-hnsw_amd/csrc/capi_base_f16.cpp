@@ -368,6 +368,132 @@ int exact_range_f16_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t
     return IVFHNSW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// ... with a base tag per query: the same sequence around the two kernels a tag plan takes, the way
+// exact_range_dev of the uint8 store carries its RangeStrips.  Per chunk of kExactChunk queries the tag plan is made once
+// and kept for both passes, chunk i's gathered queries at row i * bound * 32 of h->ex_q / h->ex_qn and its strips from
+// strip i * bound of the tile map.
+struct F16RangeStrips {
+    size_t bound = 0;
+    unsigned forms = 0;
+    int ns_dense = 1, ns_ind = 1;
+    std::vector<StripPlan> plans;
+};
+
+int exact_range_f16_strips_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const F16RangeStrips &rs, bool fill, size_t nq, float radius,
+                                int map_shift, float *dist, int64_t *labels, size_t out_cap)
+{
+    const size_t d = b->base_d, rows = rs.bound * 32;
+    StageScope sc(h, fill ? IVFHNSW_STAGE_SELECT : IVFHNSW_STAGE_SCAN);
+    uint32_t *map = h->opt_exact_range_map ? h->xr_map.as<uint32_t>() : nullptr;
+    for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++)
+        HIP_TRY(launch_exact_range_f16_strips(h->stream, fill, h->ex_q.as<unsigned char>() + i * rows * d * 2, h->ex_qn.as<float>() + i * rows,
+                                              b->base_rows.p, b->base_norms.as<float>(), rs.bound, q0, b->base_n, (int)d, radius, rs.ns_dense,
+                                              rs.ns_ind, h->xr_slices.as<uint32_t>(), h->xr_tot.as<unsigned long long>(), map, map_shift,
+                                              dist, labels, out_cap, rs.plans[i], rs.forms));
+    return IVFHNSW_OK;
+}
+
+// device pointers, the arguments checked (nq > 0)
+int exact_range_f16_tags_dev(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const char *who, size_t nq, const float *d_queries, size_t row_stride,
+                             const uint16_t *d_tags, const TagRows &tr, size_t in_use, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    const size_t d = b->base_d, n = b->base_n, first = std::min(nq, kExactChunk), nchunks = (nq + kExactChunk - 1) / kExactChunk;
+    F16RangeStrips rs;
+    rs.bound = sweep_tag_strip_bound(first, in_use);
+    rs.forms = 1u << kSweepColsDense | (b->bt_tagged ? 1u << kSweepColsIndirect : 0u);
+    // Dense: the plain call's rule over the chunk's queries padded to a strip; Indirect: the uint8 sweep's rule (k = 1: a
+    // workgroup of four strips) over the rows of every strip and the longest row list
+    rs.ns_dense = exact_range_f16_splits_for((first + 31) / 32 * 32, n, d);
+    rs.ns_ind = b->bt_tagged ? exact_splits_for(rs.bound * 32, b->bt_max_rows, 1) : 1;
+    if (h->opt_exact_splits > 0)
+        rs.ns_dense = rs.ns_ind = h->opt_exact_splits;
+    rs.plans.resize(nchunks);
+    const int nsplit = std::max(rs.ns_dense, rs.ns_ind); // the one width of the slices table
+    const size_t len = nq * (size_t)nsplit + 1, rows = nchunks * rs.bound * 32, plan_bytes = sweep_tag_plan_bytes(rs.bound);
+    size_t map_bytes = 0;
+    const int map_shift = exact_range_map_shift(rows, n, 2 * d, nsplit, &map_bytes);
+    map_bytes = rows / 32 * exact_range_f16_strips_map_words(n, rs.ns_dense, rs.ns_ind, map_shift) * sizeof(uint32_t);
+    int rc;
+    if ((rc = h->ex_q.ensure(rows * d * 2)) || (rc = h->ex_qn.ensure(rows * sizeof(float))) ||
+        (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) || (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
+        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))) ||
+        (rc = h->bs_plan.ensure(nchunks * plan_bytes)) || (rc = h->bt_work.ensure(tag_plan_work_words(first) * sizeof(uint32_t))))
+        return rc;
+    {
+        StageScope sc(h, IVFHNSW_STAGE_PLAN); // the plans and the gathers, accounted apart from the sweeps
+        for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++) {
+            StripPlan &sp = rs.plans[i];
+            HIP_TRY(launch_tag_strip_plan(h->stream, d_tags + q0, std::min(kExactChunk, nq - q0), tr, h->bs_plan.as<unsigned char>() + i * plan_bytes,
+                                          rs.bound, h->bt_work.as<uint32_t>(), &sp));
+            sp.map_strip0 = (uint32_t)(i * rs.bound);
+            // the queries as the store holds its rows, in strip order; a padding row repeats the chunk's first query
+            HIP_TRY(launch_f16_store_rows(h->stream, d_queries + q0 * row_stride, row_stride, h->ex_q.as<unsigned char>() + i * rs.bound * 32 * d * 2,
+                                          h->ex_qn.as<float>() + i * rs.bound * 32, rs.bound * 32, (int)d, sp.strip_rows));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
+    if ((rc = exact_range_f16_strips_pass(h, b, rs, false, nq, radius, map_shift, nullptr, nullptr, 0)))
+        return rc;
+    unsigned long long tot = 0;
+    if ((rc = exact_range_total(h, who, len, &tot)))
+        return rc;
+    RangeOut out;
+    if ((rc = out.reserve(h, tot)))
+        return rc;
+    HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
+    if (tot && (rc = exact_range_f16_strips_pass(h, b, rs, true, nq, radius, map_shift, out.dist(h), out.lab(h), (size_t)tot)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    out.commit(h, tot);
+    *total = tot;
+    return IVFHNSW_OK;
+}
+
+int exact_range_f16_tags_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, const uint16_t *query_tags, float radius,
+                              uint64_t *lims, uint64_t *total, bool on_device)
+{
+    if (!query_tags)
+        return exact_range_f16_impl(h, nq, queries, row_stride, radius, lims, total, on_device);
+    const char *who = on_device ? "exact_range_search_f16_tags_dev" : "exact_range_search_f16_tags";
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "exact_range_search_tags", &b);
+    if (rc)
+        return rc;
+    if (std::isnan(radius))
+        return fail(IVFHNSW_ERR_INVALID, "%s: the radius is NaN", who);
+    TagRows tr;
+    size_t in_use = 0;
+    if ((rc = base_tags_call(b, who, &tr, &in_use)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, on_device ? nullptr : lims, on_device ? lims : nullptr, total);
+    const size_t d = b->base_d;
+    if (!queries || !lims || !total)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null queries, lims or total", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (nq > kMaxBatchAll)
+        return fail(IVFHNSW_ERR_INVALID, "%s is limited to %zu queries per call", who, kMaxBatchAll);
+    if (on_device && (((uintptr_t)queries & 3) || ((uintptr_t)lims & 7) || ((uintptr_t)query_tags & 1)))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries must be 4-byte, lims 8-byte and query tags 2-byte aligned", who);
+    if (on_device)
+        return exact_range_f16_tags_dev(h, b, who, nq, queries, row_stride, query_tags, tr, in_use, radius, lims, total);
+    if ((rc = h->ex_raw.ensure(nq * d * sizeof(float))) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))) ||
+        (rc = h->bs_qslots.ensure(nq * sizeof(uint16_t))))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), queries, row_stride * sizeof(float), d * sizeof(float), nq,
+                             hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, query_tags, nq * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = exact_range_f16_tags_dev(h, b, who, nq, h->ex_raw.as<float>(), d, h->bs_qslots.as<uint16_t>(), tr, in_use, radius,
+                                       h->xr_lims.as<uint64_t>(), total)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
 } // namespace
 
 int ivfhnsw_gpu_upload_base_f16(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows,
@@ -426,4 +552,18 @@ int ivfhnsw_gpu_exact_range_search_f16_dev(ivfhnsw_gpu *h, size_t nq, const floa
                                            uint64_t *d_lims, uint64_t *total)
 {
     return exact_range_f16_impl(h, nq, d_queries, row_stride, radius, d_lims, total, true);
+}
+
+// ---- with a base tag per query; query_tags == NULL is the plain call
+
+int ivfhnsw_gpu_exact_range_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride,
+                                            const uint16_t *query_tags, float radius, uint64_t *lims, uint64_t *total)
+{
+    return exact_range_f16_tags_impl(h, nq, queries, row_stride, query_tags, radius, lims, total, false);
+}
+
+int ivfhnsw_gpu_exact_range_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride,
+                                                const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    return exact_range_f16_tags_impl(h, nq, d_queries, row_stride, d_query_tags, radius, d_lims, total, true);
 }

@@ -437,6 +437,19 @@ hipError_t launch_f16_store_rows(hipStream_t s, const float *src, size_t src_str
 hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
                                           size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
                                           float *dists, int64_t *labels, const StripPlan &sp, unsigned forms);
+// ... and the range search under them: launch_exact_range_f16 over a tag plan of the chunk that begins at
+// query q_off of the call, one form per call as there.  slices: [queries of the call][max(ns_dense, ns_ind)], keyed by the
+// caller's query; map (nullable): [strips of the call][exact_range_f16_strips_map_words], keyed by sp.map_strip0 + plan
+// strip, each launch's splits at its own exact_range_map_words apart -- the Dense launch skips by the OR over a workgroup's
+// strips, the Indirect one per strip.
+inline size_t exact_range_f16_strips_map_words(size_t nx, int ns_dense, int ns_ind, int map_shift)
+{
+    return std::max((size_t)ns_dense * sweep_map_words(nx, ns_dense, map_shift), (size_t)ns_ind * sweep_map_words(nx, ns_ind, map_shift));
+}
+hipError_t launch_exact_range_f16_strips(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn,
+                                         size_t bound, size_t q_off, size_t nx, int d, float radius, int ns_dense, int ns_ind,
+                                         uint32_t *slices, unsigned long long *total, uint32_t *map, int map_shift, float *dist,
+                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms);
 // Base values (kernels_exact_filter.hip): a uint32 per row of the store, and the exact sweeps with an
 // interval per query.  launch_base_values_apply: vals[rows[i]] = v[i] for rows[i] < n; *conflict (zeroed here) != 0 when a
 // row was given two different values.  launch_base_values_index: all rows sorted stably by value (*sorted = ids_a or ids_b

@@ -529,13 +529,26 @@ template <class F> hipError_t by_f16_steps(int d, F &&f)
 // A wave whose 32 rows all lie beyond nq stages and meets every barrier, multiplies nothing, writes no map word, slice or
 // total -- and its map words, which need not even exist (the map has ceil(nq / 32) strips), are never read: the OR runs
 // over the waves with a row below nq only.
-template <int ND, bool FILL>
+// SP: F16Rows is the plain call.  F16RangeDenseStrips (base tags): Qh, qn are the nq = 32 * bound rows of a
+// strip plan and workgroup i owns the strips [4 i, 4 i + 4) of the plan's Dense range, as in exact_f16_kernel: a workgroup
+// beyond the range leaves before the first barrier, a wave beyond it in a workgroup that stays is not `active`, and the OR
+// of the map runs over the waves that own a strip.  Slices and cursors are the QUERY's (strip_rows), in a table slice_w
+// splits wide; the map words the plan strip's, map_stride words a strip.
+struct F16RangeDenseStrips {
+    static constexpr bool kStrips = true;
+    StripPlan sp;
+    int slice_w;
+    uint32_t map_stride;
+};
+
+template <int ND, bool FILL, class SP>
 __global__ __launch_bounds__(256) void exact_range_f16_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
                                                               const _Float16 *__restrict__ X, const float *__restrict__ xn, int nq,
                                                               size_t nx, float radius, size_t q_off,
                                                               uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
                                                               uint32_t *__restrict__ map, int map_shift, int map_words,
-                                                              float *__restrict__ out_d, long long *__restrict__ out_l, size_t out_cap)
+                                                              float *__restrict__ out_d, long long *__restrict__ out_l, size_t out_cap,
+                                                              SP sp)
 {
     constexpr int D = 16 * ND, T = 256;
     constexpr int ROWB = 2 * D + 16; // bytes of a tile's row in LDS: the row and its padding
@@ -547,9 +560,24 @@ __global__ __launch_bounds__(256) void exact_range_f16_kernel(const _Float16 *__
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int m = lane & 31, kk = lane >> 5;
-    const int wg_r0 = blockIdx.x * 128, r0 = wg_r0 + wave * 32;
-    const bool active = r0 < nq; // wave-uniform; the workgroup's first wave always is
+    // the workgroup's first strip and the strips it owns: of the call's rows, or of the plan's Dense range
+    uint32_t s0 = blockIdx.x * 4, s1 = (uint32_t)((nq + 31) >> 5);
+    if constexpr (SP::kStrips) {
+        s0 += sp.sp.hdr->lay.range[kSweepColsDense][0];
+        s1 = sp.sp.hdr->lay.range[kSweepColsDense][1];
+        if (s0 >= s1)
+            return;
+    }
+    const int wg_r0 = (int)(s0 << 5), r0 = SP::kStrips ? wg_r0 + (s0 + wave < s1 ? wave : 0) * 32 : wg_r0 + wave * 32;
+    const bool active = SP::kStrips ? s0 + wave < s1 : r0 < nq; // wave-uniform; the workgroup's first wave always is
     const int nsplit = gridDim.y, split = blockIdx.y;
+    // the slice of row `row` of the plan or of the call (under a plan: of the query the row holds, padding rows of query 0)
+    auto slice_of = [&](int row) -> size_t {
+        if constexpr (SP::kStrips)
+            return (q_off + (size_t)max(sp.sp.strip_rows[row], 0)) * sp.slice_w + split;
+        else
+            return (q_off + row) * nsplit + split;
+    };
     // (the same for every wave of the workgroup: all of them meet at every barrier below)
     size_t c_begin, c_end;
     sweep_split_cut(nx, nsplit, split, &c_begin, &c_end);
@@ -567,24 +595,33 @@ __global__ __launch_bounds__(256) void exact_range_f16_kernel(const _Float16 *__
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int row = r0 + mfma32_row(r, kk);
-        const bool in = row < nq;
+        bool in = row < nq;
+        if constexpr (SP::kStrips)
+            in = active && sp.sp.strip_rows[row] >= 0;
         in_rows |= in ? 1u << r : 0u;
         qn_r[r] = qn[min(row, nq - 1)];
         gate[r] = f16_gate(qn_r[r], in ? radius : -INFINITY);
-        cnt[r] = FILL && in ? slices[(q_off + row) * nsplit + split] : 0u;
+        cnt[r] = FILL && in ? slices[slice_of(row)] : 0u;
     }
 
     // The map words: this wave's own (count), and the OR over the workgroup's waves with a row below nq (fill).
-    const size_t wg_strip = (q_off + wg_r0) >> 5;
-    const int wg_waves = nq - wg_r0 >= 128 ? 4 : (nq - wg_r0 + 31) >> 5;
-    uint32_t *mw = map ? map + ((wg_strip + wave) * nsplit + split) * (size_t)map_words : nullptr;
+    const size_t wg_strip = SP::kStrips ? (size_t)(wg_r0 >> 5) : (q_off + wg_r0) >> 5;
+    const int wg_waves = SP::kStrips ? (int)min(s1 - s0, 4u) : nq - wg_r0 >= 128 ? 4 : (nq - wg_r0 + 31) >> 5;
+    // the words of wave v of the workgroup in this split
+    auto words_of = [&](int v) -> uint32_t * {
+        if constexpr (SP::kStrips)
+            return map + (sp.sp.map_strip0 + wg_strip + v) * (size_t)sp.map_stride + (size_t)split * map_words;
+        else
+            return map + ((wg_strip + v) * nsplit + split) * (size_t)map_words;
+    };
+    uint32_t *mw = map ? words_of(wave) : nullptr;
     uint32_t or_at = ~0u, or_word = 0; // the last word formed: a word covers 32 << map_shift tiles
     auto wg_word = [&](uint32_t w) -> uint32_t {
         if (w != or_at) {
             or_at = w;
             or_word = 0;
             for (int v = 0; v < wg_waves; v++)
-                or_word |= map[((wg_strip + v) * nsplit + split) * (size_t)map_words + w];
+                or_word |= words_of(v)[w];
         }
         return or_word;
     };
@@ -692,8 +729,206 @@ __global__ __launch_bounds__(256) void exact_range_f16_kernel(const _Float16 *__
         if (m == 0) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
+                if (in_rows >> r & 1u) {
+                    // (the plain call's index in its own words: through slice_of it costs the count form 10 to 25 VGPRs
+                    // in this unit's build, which the Makefile compiles without packed float32 operations)
+                    if constexpr (SP::kStrips)
+                        slices[slice_of(r0 + mfma32_row(r, kk))] = cnt[r];
+                    else
+                        slices[(q_off + r0 + mfma32_row(r, kk)) * nsplit + split] = cnt[r];
+                }
+                sum += cnt[r];
+            }
+        }
+        sum += __shfl_xor(sum, 32);
+        if (lane == 0 && sum)
+            atomicAdd(total, sum);
+    }
+}
+
+// ---- the tagged strips of the range search (ivfhnsw_gpu_exact_range_search_f16_tags) -------------------------
+// exact_f16_rows_kernel's sweep of a row list -- a strip is a wave, operand A resident, operand B straight from the store in
+// MFMA order, row numbers two tiles ahead, norms and the first NPRE pieces one tile ahead, the late pieces behind the first
+// MFMAs of their own tile -- with the fixed gate and the two forms of exact_range_f16_kernel, whose arithmetic it repeats
+// operation for operation.  Nothing is selected: no candidate buffers, no LDS, no barrier; occupancy is the registers'.
+// Slices and cursors are the QUERY's (strip_rows) in a table slice_w splits wide, so lims and results come out in the
+// caller's order; the label is the row number, the list ascends, so results ascend within and across splits.
+// The tile map, per WAVE: each wave loads its own B, so the fill form skips by the strip's OWN bits (as the int8 fill form
+// does), words map + (map_strip0 + strip) * map_stride + split * map_words.  The pipeline aims at VISITED tiles: t is the
+// tile being multiplied, tn the next visited one (its pieces and norms are requested now), ta the one after (its row
+// numbers are).  next_tile decides before anything of a tile is requested; a skipped tile is neither loaded nor
+// multiplied.  In the count form, and without a map, next_tile(t) == t: the loop is exact_f16_rows_kernel's.
+// A wave without a strip, or whose split of a short list is empty, leaves at once in both forms: no slice (the memset left
+// it zero), no map word (the fill form's wave leaves too), no total.
+template <int ND, bool FILL>
+__global__ __launch_bounds__(256) void exact_range_f16_rows_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                                   const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                                   float radius, size_t q_off, int slice_w,
+                                                                   uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
+                                                                   uint32_t *__restrict__ map, int map_shift, int map_words,
+                                                                   uint32_t map_stride, float *__restrict__ out_d,
+                                                                   long long *__restrict__ out_l, size_t out_cap, StripPlan sp)
+{
+    constexpr int D = 16 * ND;
+    constexpr int NPRE = ND <= 8 ? ND : (ND + 1) / 2, NLATE = ND - NPRE;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const uint32_t strip = sp.hdr->lay.range[kSweepColsIndirect][0] + blockIdx.x * 4 + wave;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][1])
+        return;
+    const StripCols e = sp.strip_cols[strip];
+    const int split = blockIdx.y;
+    size_t c_begin, c_end;
+    sweep_split_cut(e.nx, (int)gridDim.y, split, &c_begin, &c_end);
+    if (c_begin >= c_end)
+        return;
+    const uint32_t ntiles = (uint32_t)((c_end - c_begin + 31) >> 5);
+    const uint32_t *__restrict__ rows = e.data;
+    const int r0 = (int)(strip << 5); // (strip < the plan's bound: every row of it exists in Qh, qn and strip_rows)
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)(r0 + m) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    // the slice of strip row `row`: its query's (a padding row: query 0's, never touched)
+    auto slice_of = [&](int row) -> size_t { return (q_off + (size_t)max(sp.strip_rows[r0 + row], 0)) * slice_w + split; };
+    float qn_r[16], gate[16];
+    uint32_t cnt[16], in_rows = 0; // bit r: accumulator row r is a query
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        const bool in = sp.strip_rows[r0 + row] >= 0;
+        in_rows |= in ? 1u << r : 0u;
+        qn_r[r] = qn[r0 + row];
+        gate[r] = f16_gate(qn_r[r], in ? radius : -INFINITY);
+        cnt[r] = FILL && in ? slices[slice_of(row)] : 0u;
+    }
+
+    uint32_t *mw = map ? map + (size_t)(sp.map_strip0 + strip) * map_stride + (size_t)split * map_words : nullptr;
+    // the first tile at or after t that is visited (ntiles or beyond: none); wave-uniform
+    auto next_tile = [&](uint32_t t) -> uint32_t {
+        if (!FILL || !mw)
+            return t;
+        while (t < ntiles) {
+            const uint32_t g = t >> map_shift;
+            const uint32_t w = __builtin_amdgcn_readfirstlane(mw[g >> 5]) >> (g & 31);
+            if (w & 1u)
+                return t;
+            t = (w ? g + (uint32_t)__ffs((int)w) - 1u : (g | 31u) + 1u) << map_shift; // the next set bit, or the next word
+        }
+        return ntiles;
+    };
+
+    const unsigned char *xb = reinterpret_cast<const unsigned char *>(X) + 16 * kk;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the lane's column of tile t, whether it has one, and its row number
+    auto col_of = [&](uint32_t t) -> size_t { return c_begin + ((size_t)t << 5) + m; };
+    auto ids = [&](uint32_t t) -> uint32_t { return col_of(t) < c_end ? rows[col_of(t)] : 0u; };
+    // pieces [first, first + N) of store row `row` into w; ok: the lane has a column
+    auto pieces = [&](uint32_t row, bool ok, int first, auto &w) {
+        constexpr int N = (int)(sizeof(w) / sizeof(w[0]));
+        const unsigned char *p = xb + (size_t)row * (2 * D) + 32 * first;
+#pragma unroll
+        for (int s = 0; s < N; s++)
+            w[s] = zero;
+        if (ok) {
+#pragma unroll
+            for (int s = 0; s < N; s++)
+                w[s] = *reinterpret_cast<const f16x8 *>(p + 32 * s);
+        }
+    };
+    uint32_t bits = 0;
+    // Tile t: `cur`, n_cur = its first NPRE pieces and its norms, id_cur its row numbers.  Starts the loads of tile tn (row
+    // numbers id_nxt) into nxt, n_nxt and of the row numbers of tile ta into id_ahead.
+    auto tile = [&](uint32_t t, const f16x8 (&cur)[NPRE], float n_cur, uint32_t id_cur, uint32_t tn, f16x8 (&nxt)[NPRE], float &n_nxt,
+                    uint32_t id_nxt, uint32_t ta, uint32_t &id_ahead) {
+        const bool col_ok = col_of(t) < c_end;
+        f16x8 late[NLATE > 0 ? NLATE : 1];
+        if constexpr (NLATE > 0)
+            pieces(id_cur, col_ok, NPRE, late);
+        if (tn < ntiles) { // in flight behind this tile's MFMAs
+            const bool ok = col_of(tn) < c_end;
+            pieces(id_nxt, ok, 0, nxt);
+            n_nxt = ok ? xn[id_nxt] : 0.f;
+        }
+        if (ta < ntiles)
+            id_ahead = ids(ta);
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < NPRE; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], cur[s], acc, 0, 0, 0);
+        if constexpr (NLATE > 0) {
+#pragma unroll
+            for (int s = 0; s < NLATE; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPRE + s], late[s], acc, 0, 0, 0);
+        }
+        bool any = false, hit = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), n_cur) > gate[r];
+        if (__ballot(any && col_ok)) { // wave-uniform
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float dist = __fsub_rn(__fadd_rn(qn_r[r], n_cur), __fmul_rn(2.0f, acc[r]));
+                const bool pass = col_ok && (in_rows >> r & 1u) && dist < radius;
+                const unsigned long long mask = __ballot(pass);
+                const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
+                hit |= mask != 0;
+                if (FILL) {
+                    const size_t o = (size_t)cnt[r] + __popc(half & ((1u << m) - 1u));
+                    if (pass && o < out_cap) { // (o < out_cap always: the count form counted this very lane)
+                        out_d[o] = dist;
+                        out_l[o] = (long long)id_cur;
+                    }
+                }
+                cnt[r] += __popc(half);
+            }
+        }
+        if (!FILL && mw) {
+            const uint32_t g = t >> map_shift;
+            bits |= hit ? 1u << (g & 31) : 0u;
+            if (tn >= ntiles || (tn >> map_shift) >> 5 != g >> 5) { // the word is complete
+                if (lane == 0)
+                    mw[g >> 5] = bits;
+                bits = 0;
+            }
+        }
+    };
+
+    uint32_t t = next_tile(0);
+    if (t >= ntiles)
+        return; // (fill: no tile of the split has a hit)
+    uint32_t tn = next_tile(t + 1), ta;
+    f16x8 b0[NPRE], b1[NPRE];
+    float n0, n1 = 0.f;
+    uint32_t id0 = ids(t), id1 = 0, id_ahead = 0;
+    pieces(id0, col_of(t) < c_end, 0, b0);
+    n0 = col_of(t) < c_end ? xn[id0] : 0.f;
+    if (tn < ntiles)
+        id1 = ids(tn);
+    for (;;) {
+        ta = tn < ntiles ? next_tile(tn + 1) : tn;
+        tile(t, b0, n0, id0, tn, b1, n1, id1, ta, id_ahead);
+        if (tn >= ntiles)
+            break;
+        t = tn, tn = ta, id0 = id_ahead;
+        ta = tn < ntiles ? next_tile(tn + 1) : tn;
+        tile(t, b1, n1, id1, tn, b0, n0, id0, ta, id_ahead);
+        if (tn >= ntiles)
+            break;
+        t = tn, tn = ta, id1 = id_ahead;
+    }
+
+    if (!FILL) {
+        unsigned long long sum = 0;
+        if (m == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
                 if (in_rows >> r & 1u)
-                    slices[(q_off + r0 + mfma32_row(r, kk)) * nsplit + split] = cnt[r];
+                    slices[slice_of(mfma32_row(r, kk))] = cnt[r];
                 sum += cnt[r];
             }
         }
@@ -825,9 +1060,44 @@ hipError_t launch_exact_range_f16(hipStream_t s, bool fill, const void *Qh, cons
     long long *lab = reinterpret_cast<long long *>(labels);
     return by_f16_steps(d, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        const auto kern = fill ? exact_range_f16_kernel<ND, true> : exact_range_f16_kernel<ND, false>;
+        const auto kern = fill ? exact_range_f16_kernel<ND, true, F16Rows> : exact_range_f16_kernel<ND, false, F16Rows>;
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, qn, x, xn, (int)nq, nx, radius, q_off, slices, total, map, map_shift, words,
-                           dist, lab, out_cap);
+                           dist, lab, out_cap, F16Rows{});
+        return hipGetLastError();
+    });
+}
+
+// ... under a tag plan: Qh, qn [bound * 32] = the chunk's queries gathered by the plan, the chunk being
+// queries [q_off, ...) of the call; nx = the rows of the store (the most columns any strip has).  The Dense strips by the
+// staged kernel under ns_dense splits, the Indirect ones (forms bit kSweepColsIndirect) by the per-wave kernel under ns_ind;
+// both grids cover every strip the plan can have, and what lies beyond a form's range leaves at once.  slices: one table
+// max(ns_dense, ns_ind) splits wide, each form writes the splits it has.  map: exact_range_f16_strips_map_words words a strip.
+hipError_t launch_exact_range_f16_strips(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn,
+                                         size_t bound, size_t q_off, size_t nx, int d, float radius, int ns_dense, int ns_ind,
+                                         uint32_t *slices, unsigned long long *total, uint32_t *map, int map_shift, float *dist,
+                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms)
+{
+    if (d < 16 || d > 256 || (d & 15) || radius != radius || bound == 0 || bound > (0x7fffffffull >> 5) || nx == 0 || nx >= 0xffffffffull ||
+        ns_dense < 1 || ns_dense > 64 || ns_ind < 1 || ns_ind > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.hdr ||
+        !sp.strip_rows || !sp.strip_cols)
+        return hipErrorInvalidValue;
+    const int slice_w = std::max(ns_dense, ns_ind);
+    const uint32_t stride = (uint32_t)exact_range_f16_strips_map_words(nx, ns_dense, ns_ind, map_shift);
+    const int w_dense = sweep_map_words(nx, ns_dense, map_shift), w_ind = sweep_map_words(nx, ns_ind, map_shift);
+    const unsigned wgs = (unsigned)((bound + 3) / 4);
+    const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
+    long long *lab = reinterpret_cast<long long *>(labels);
+    return by_f16_steps(d, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        const F16RangeDenseStrips ds{sp, slice_w, stride};
+        const auto dense = fill ? exact_range_f16_kernel<ND, true, F16RangeDenseStrips> : exact_range_f16_kernel<ND, false, F16RangeDenseStrips>;
+        hipLaunchKernelGGL(dense, dim3(wgs, (unsigned)ns_dense), dim3(256), 0, s, q, qn, x, xn, (int)(bound * 32), nx, radius, q_off, slices,
+                           total, map, map_shift, w_dense, dist, lab, out_cap, ds);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess || !(forms >> kSweepColsIndirect & 1u))
+            return e;
+        const auto rows = fill ? exact_range_f16_rows_kernel<ND, true> : exact_range_f16_rows_kernel<ND, false>;
+        hipLaunchKernelGGL(rows, dim3(wgs, (unsigned)ns_ind), dim3(256), 0, s, q, qn, x, xn, radius, q_off, slice_w, slices, total, map,
+                           map_shift, w_ind, stride, dist, lab, out_cap, sp);
         return hipGetLastError();
     });
 }

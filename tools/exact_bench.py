@@ -47,6 +47,10 @@
      with 32 and with 1 024 tags, k = 1 and 100, the tagged call under the rule's split count and under its two neighbours
      ALTERNATING with exact_search_tags_dev on the uint8 store of the same rows (the two must agree); and the all-NONE batch
      alternating with the plain exact_search_f16_dev, its plan stage (plan and gather) from the stage profiler.
+     Per tag count also the range form under the tags (ivfhnsw_gpu_exact_range_search_f16_tags_dev) at the
+     radius of the tagged 10th neighbour, alternating with exact_range_search_tags_dev on the uint8 store (the two must
+     agree), the tagged k = 1 sweep, the call without the tile map and the call under the neighbouring split counts; and
+     its all-NONE batch alternating with the plain exact_range_search_f16_dev.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
@@ -573,6 +577,62 @@ def main():
         g.set_option("exact_splits", -1)
         g.set_option("exact_range_map", -1)
 
+    def f16_tags_range_leg(n, dd, g8, qf, qb, qt, ntags, radius, alternate, with_splits):
+        """The range form under base tags (exact_range_search_f16_tags_dev) at the radius of the tagged 10th
+        neighbour: beside exact_range_search_tags_dev of the uint8 store (equal results required), the tagged k = 1 sweep,
+        the call without the tile map and under the neighbours of the Indirect launch's split count; the count and the fill
+        pass by the stage profiler.  qt None: the all-NONE batch beside the plain exact_range_search_f16_dev."""
+        od, ol = torch.empty((nq, 1), dtype=torch.float32, device=dev), torch.empty((nq, 1), dtype=torch.int64, device=dev)
+        lims8, passes = torch.zeros_like(lims), []
+        tags = qt if qt is not None else torch.full((nq,), -1, dtype=torch.int16, device=dev)
+
+        def tagged():
+            g.set_profiling(True)
+            g.reset_stage_ms()
+            tagged.total = g.exact_range_search_f16_tags_dev(nq, qf, dd, tags, radius, lims)
+            ms = g.stage_ms()
+            passes.append((ms["plan"][0], ms["scan"][0], ms["select"][0]))
+            g.set_profiling(False)
+
+        def no_map():
+            g.set_option("exact_range_map", 0)
+            g.exact_range_search_f16_tags_dev(nq, qf, dd, tags, radius, lims)
+            g.set_option("exact_range_map", -1)
+
+        if qt is None:
+            calls = [("exact_range_search_f16_tags_dev, all NONE", tagged),
+                     ("exact_range_search_f16_dev", lambda: g.exact_range_search_f16_dev(nq, qf, dd, radius, lims8))]
+        else:
+            # the rule of the Indirect launch (capi_base_f16.cpp exact_range_f16_tags_dev), restated
+            blocks, longest = -(-(nq // 32 + min(nq, ntags + 1)) * 32 // 128), -(-n // ntags)
+            rule = max(1, min(64, -(-512 // blocks), -(-longest // 4096)))
+            calls = [("exact_range_search_f16_tags_dev", tagged),
+                     ("exact_range_search_tags_dev (uint8 store)", lambda: g8.exact_range_search_tags_dev(nq, qb, dd, tags, radius, lims8)),
+                     ("exact_search_f16_tags_dev k=1", lambda: g.exact_search_f16_tags_dev(nq, qf, dd, 1, tags, od, ol)),
+                     ("exact_range_search_f16_tags_dev, no tile map", no_map)]
+            calls += [("exact_range_search_f16_tags_dev, %d splits" % s, lambda s=s: with_splits(s, tagged))
+                      for s in (rule - 1, rule + 1) if 1 <= s <= 64]
+        ts = alternate(calls, "range %s" % (ntags if qt is not None else "all NONE"))
+        other = g8 if qt is not None else g
+        calls[1][1]()
+        want = other.exact_range_results(0, int(lims8[-1]))
+        tagged()
+        got = g.exact_range_results(0, tagged.total)
+        assert torch.equal(lims, lims8) and (got[1] == want[1]).all() and (got[0] == want[0]).all(), \
+            "the tagged float16 range search and %s disagree" % calls[1][0]
+        base_t = statistics.median(ts[calls[0][0]])
+        for name, _ in calls:
+            t = statistics.median(ts[name])
+            r = {"what": name, "rows": n, "d": dd, "nq": nq, "tags": ntags, "radius_value": radius, "results": tagged.total,
+                 "seconds": round(t, 5), "reps": [round(x, 5) for x in ts[name]], "over_f16_range_tags": round(t / base_t, 3)}
+            if name == calls[0][0]:
+                per_rep = sum(1 for other, fn in calls if fn is tagged or "splits" in other)  # the profiled calls of a rep
+                mine = passes[args.warmup * per_rep:][::per_rep][:args.reps]
+                for i, key in enumerate(("plan_and_gather_ms", "count_pass_ms", "fill_pass_ms")):
+                    r[key] = round(statistics.median(x[i] for x in mine), 4)
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+
     def f16_tags_legs(n, dd, g8, qf, qb):
         """Base tags on the float16 store (exact_search_f16_tags_dev) on the rows f16_legs uploaded to both
         stores, the calls of a leg alternating rep by rep in one process.  Per tag count (row i carries tag i % ntags, query
@@ -628,6 +688,7 @@ def main():
                          "reps": [round(x, 5) for x in ts[name]], "over_f16_tags": round(t / base_t, 3)}
                     result["rows"].append(r)
                     print(json.dumps(r), flush=True)
+            f16_tags_range_leg(n, dd, g8, qf, qb, qt, ntags, float(od[:, 9].median()), alternate, with_splits)
         none = torch.full((nq,), -1, dtype=torch.int16, device=dev)  # 0xffff: every query untagged
         for k in (1, 100):
             od = torch.empty((nq, k), dtype=torch.float32, device=dev)
@@ -652,6 +713,7 @@ def main():
                  "all_none_reps": [round(x, 5) for x in a], "plan_and_gather_ms": round(statistics.median(plan_ms[args.warmup:]), 4)}
             result["rows"].append(r)
             print(json.dumps(r), flush=True)
+        f16_tags_range_leg(n, dd, g8, qf, qb, None, 0, float(odp[:, 9].median()), alternate, with_splits)
         g.clear_base_tags()
 
     def f16_legs(n, dd):

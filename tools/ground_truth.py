@@ -28,12 +28,13 @@ With an .fvecs base and .fvecs queries (float corpora: DEEP1B) the same .ivecs i
 (upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; of the filters the k-search
 takes --tags with --query-tags (ivfhnsw_gpu_exact_search_f16_tags, 3.29), nothing else.  With
 --radius the .npz comes from ivfhnsw_gpu_exact_range_search_f16 (3.28): the rows whose float32 distance between the rounded
-vectors, the value the k-search returns, is < R.
+vectors, the value the k-search returns, is < R -- and with --tags and --query-tags from
+ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag.
 
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N] [--tags t.npy --query-tags qt.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
-       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N]
+       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N] [--tags t.npy --query-tags qt.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --values v.npy --query-ranges qr.npy"""
 import argparse
@@ -243,16 +244,22 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
                        info=None, tags=None, query_tags=None, values=None, query_ranges=None):
     """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
     `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing.  An .fvecs
-    base goes to the float16 store (ivfhnsw_gpu_exact_range_search_f16), which takes none of the filters."""
+    base goes to the float16 store (ivfhnsw_gpu_exact_range_search_f16), which takes `tags` with `query_tags`
+    (ivfhnsw_gpu_exact_range_search_f16_tags, 3.30) and none of the other filters."""
     if base_path.endswith(".fvecs"):
-        if labels is not None or tags is not None or values is not None:
-            raise ValueError("an .fvecs base goes to the float16 store, which takes no filter, tags or values")
+        if labels is not None or values is not None:
+            raise ValueError("an .fvecs base goes to the float16 store, which takes tags but no filter or values")
         img, dq = read_fvecs_image(query_path)
         g = pkg.GpuIndex(device)
         try:
             n, d = g.upload_base_fvecs(base_path, rows=rows)
             if d != dq:
                 raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+            if tags is not None:
+                install_tags(g, n, img.shape[0], tags, query_tags)
+                if info is not None:
+                    info["rows_passing"] = g.base_tags_info()[0]  # the tagged rows
+                return g.exact_range_search_f16_tags(img[:, 1:], radius, query_tags)
             return g.exact_range_search_f16(img[:, 1:], radius)
         finally:
             g.close()
