@@ -814,8 +814,10 @@ int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first
  * fvec_L2sqr(q, float(x^)) bit for bit -- the unrounded float32 query, the stored half widened exactly, the eight
  * accumulators and the order of utils.cpp:22-52.  ivfhnsw_gpu_exact_search_f16 and ivfhnsw_gpu_exact_range_search_f16 (below)
  * search it.  On a float16 store every uint8 exact call (exact_search*, exact_range_search*) returns IVFHNSW_ERR_STATE, and
- * so do set_base_filter, set_base_filter_slot and set_base_values: of the base filters it takes tags only (set_base_tags,
- * clear_base_tags, base_tags_info, base_tag_rows as on a uint8 store; ivfhnsw_gpu_exact_search_f16_tags searches under them).
+ * so do set_base_filter and set_base_filter_slot: of the base filters it takes tags (set_base_tags, clear_base_tags,
+ * base_tags_info, base_tag_rows as on a uint8 store; ivfhnsw_gpu_exact_search_f16_tags searches under them) and values
+ * (set_base_values, clear_base_values, base_values_info, base_value_rows as on a uint8 store;
+ * ivfhnsw_gpu_exact_search_f16_values searches under them).
  * ivfhnsw_gpu_base_kind: what the handle (a view: its parent) holds. */
 #define IVFHNSW_BASE_NONE 0
 #define IVFHNSW_BASE_U8 1
@@ -872,9 +874,9 @@ int ivfhnsw_gpu_exact_search_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_que
  * square -- 0..127 at d <= 256 -- every operation is exact and the result is the exact distance.  A query holding a value
  * that does not round to a finite half gets padding.
  * Results ascending by (distance, label), [nq*k], padded with FLT_MAX / -1; 1 <= k <= 100, null buffers with nq > 0,
- * row_stride < d, a misaligned device pointer: IVFHNSW_ERR_INVALID; no store, a uint8 store, or a base filter, slot or
- * values installed on the holder (none can be, on a float16 store): IVFHNSW_ERR_STATE.  Base tags the holder carries are
- * ignored, as exact_search ignores them.  nq is unbounded
+ * row_stride < d, a misaligned device pointer: IVFHNSW_ERR_INVALID; no store, a uint8 store, or a base filter or slot
+ * installed on the holder (neither can be, on a float16 store): IVFHNSW_ERR_STATE.  Base tags and base values the holder
+ * carries are ignored, as exact_search ignores them.  nq is unbounded
  * (chunks, as exact_search); the option "exact_splits" applies; a view searches its parent's store.
  * exact_search_f16: host pointers, synchronous.  exact_search_f16_dev: device pointers (queries 4-byte aligned),
  * asynchronous on the handle's stream. */
@@ -894,7 +896,21 @@ int ivfhnsw_gpu_exact_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const float *qu
 int ivfhnsw_gpu_exact_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
                                           const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels);
 
-/* ... and the range form under them: the truth of range_search_tags for a float corpus, with the semantics
+/* ... with an interval of base values per query (set_base_values on the float16 store): the truth of
+ * search_values for a float corpus, with the semantics of ivfhnsw_gpu_exact_search_values.  query_ranges [2 nq] uint32,
+ * (lo, hi) per query: the query is answered as exact_search_f16 would answer it on a store holding only the rows whose base
+ * value v has lo <= v <= hi, unsigned and inclusive, a row without a value holding 0xffffffff -- every distance bit for bit
+ * the value exact_search_f16 writes for the pair, the labels the original row numbers, equal distances in ascending label.
+ * (0, 0xffffffff) searches the whole store; an interval no row's value lies in, lo > hi included, returns -1 / FLT_MAX in
+ * every place.  query_ranges == NULL is exact_search_f16 itself.  Limits, errors, chunks, views (the parent's store and
+ * values) and "exact_splits" as exact_search_f16; base tags on the holder are ignored.  _dev: d_query_ranges in device
+ * memory, 8-byte aligned. */
+int ivfhnsw_gpu_exact_search_f16_values(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                        const uint32_t *query_ranges, float *distances, int64_t *labels);
+int ivfhnsw_gpu_exact_search_f16_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                            const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels);
+
+/* ... and the range form under base tags: the truth of range_search_tags for a float corpus, with the semantics
  * of ivfhnsw_gpu_exact_range_search_tags.  A query with tag t gets every row whose base tag is t and whose distance -- the
  * value exact_search_f16_tags and exact_range_search_f16 (below) write for the pair, bit for bit -- is < radius (strict), in
  * ascending label; IVFHNSW_TAG_NONE searches the whole store; a tag no row carries returns nothing.  lims [nq + 1] and the

@@ -81,6 +81,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_range_search_f16", "ivfhnsw_gpu_exact_range_search_f16_dev",
     "ivfhnsw_gpu_exact_search_f16_tags", "ivfhnsw_gpu_exact_search_f16_tags_dev",
     "ivfhnsw_gpu_exact_range_search_f16_tags", "ivfhnsw_gpu_exact_range_search_f16_tags_dev",
+    "ivfhnsw_gpu_exact_search_f16_values", "ivfhnsw_gpu_exact_search_f16_values_dev",
 )
 
 
@@ -294,6 +295,8 @@ def lib():
         L.ivfhnsw_gpu_base_value_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_exact_search_values.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_values.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1389,6 +1392,29 @@ class GpuIndex:
         """The same on device buffers (d_query_tags: [nq] uint16 in device memory), asynchronous on the handle's stream."""
         _check(lib().ivfhnsw_gpu_exact_search_f16_tags_dev(self._h, nq, _devptr(d_queries), row_stride, k,
                                                            _devptr(d_query_tags), _devptr(d_distances), _devptr(d_labels)))
+
+    def exact_search_f16_values(self, queries_f32, k, query_ranges):
+        """exact_search_f16() with a value interval per query (set_base_values on the float16 store;
+        ivfhnsw_gpu_exact_search_f16_values): query_ranges [nq, 2] uint32, (lo, hi) inclusive, (0, VALUE_NONE) = no
+        restriction; None is exact_search_f16() itself."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq, 2)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_f16_values(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                         _ptr(qr), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_f16_values_dev(self, nq, d_queries, row_stride, k, d_query_ranges, d_distances, d_labels):
+        """The same on device buffers (d_query_ranges: [nq, 2] uint32 in device memory, 8-byte aligned), asynchronous on
+        the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_f16_values_dev(self._h, nq, _devptr(d_queries), row_stride, k,
+                                                             _devptr(d_query_ranges), _devptr(d_distances), _devptr(d_labels)))
 
     def exact_range_search_f16(self, queries_f32, radius):
         """Every row of the float16 base store whose distance -- the value exact_search_f16 returns for the pair -- is

@@ -4,7 +4,8 @@
 // ordered by (value, row), a valueless row last at 0xffffffff: an interval is then one window of positions of that order
 // (sweep_plan_math.h sweep_value_window), which the windowed column map sweeps (sweep_steps.h).  Both arrays are rebuilt by
 // every set call -- a stable sort of the row numbers by value.  Independent of the base filter, of its slots, of the base
-// tags and of the index's row values (capi_filter.cpp), whose labels are ids.
+// tags and of the index's row values (capi_filter.cpp), whose labels are ids.  None of it looks at the rows' type: a float16
+// store takes values as a uint8 store does (ivfhnsw_gpu_exact_search_f16_values searches under them).
 #include "capi_internal.h"
 
 namespace ivfhnsw_gpu_impl {
@@ -98,7 +99,7 @@ static int set_base_values_core(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows
 
 int ivfhnsw_gpu_set_base_values(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, const uint32_t *values)
 {
-    int rc = filter_holder_guard(h, kBaseFilter, "set_base_values", true);
+    int rc = filter_holder_guard(h, kBaseFilter, "set_base_values", true, true);
     if (rc || (rc = base_values_args(n, rows, values, "set_base_values")))
         return rc;
     ScopedBuf stage_r, stage_v; // of this call only
@@ -109,7 +110,7 @@ int ivfhnsw_gpu_set_base_values(ivfhnsw_gpu *h, size_t n, const uint32_t *rows, 
 
 int ivfhnsw_gpu_set_base_values_dev(ivfhnsw_gpu *h, size_t n, const uint32_t *d_rows, const uint32_t *d_values)
 {
-    int rc = filter_holder_guard(h, kBaseFilter, "set_base_values_dev", true);
+    int rc = filter_holder_guard(h, kBaseFilter, "set_base_values_dev", true, true);
     if (rc || (rc = base_values_args(n, d_rows, d_values, "set_base_values_dev")))
         return rc;
     if (((uintptr_t)d_rows & 3) || ((uintptr_t)d_values & 3))

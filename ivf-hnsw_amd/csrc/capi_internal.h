@@ -391,7 +391,8 @@ inline size_t label_bitmap_words(uint32_t max_label) { return (size_t)max_label 
 int labels_bitmap(ivfhnsw_gpu *h, size_t n, const uint32_t *d_labels, uint32_t max_label, DevBuf &bits);
 // The opening of the calls that set or clear a filter: on the handle that holds what the filter is marked over, not on
 // a view of it, the device bound and, with need_upload, that upload made ("<who> before upload_ivf" / "... upload_base").
-// A float16 store takes base tags only: their calls pass half_store_ok, every other base call is refused there.
+// A float16 store takes base tags and base values (3.31): their calls pass half_store_ok, the base filter's
+// and its slots' are refused there.
 enum FilterKind { kIndexFilter, kBaseFilter };
 int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool need_upload, bool half_store_ok = false);
 // what filter_info, filter_slot_info and base_filter_info answer (each pointer nullable): a set's mode and its passing

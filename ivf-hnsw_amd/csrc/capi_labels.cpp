@@ -68,7 +68,7 @@ int filter_holder_guard(ivfhnsw_gpu *h, FilterKind kind, const char *who, bool n
     if (need_upload && !(base ? h->base_n != 0 : h->has_ivf))
         return fail(IVFHNSW_ERR_STATE, "%s before %s", who, base ? "upload_base" : "upload_ivf");
     if (need_upload && base && h->base_kind != IVFHNSW_BASE_U8 && !half_store_ok)
-        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: it takes tags, but no filter, slots or values", who);
+        return fail(IVFHNSW_ERR_STATE, "%s on a float16 store: it takes tags and values, but no filter or slots", who);
     return IVFHNSW_OK;
 }
 

@@ -432,11 +432,14 @@ hipError_t launch_exact_pad(hipStream_t s, float *dists, int64_t *labels, size_t
 // over the queries Qh, qn [bound * 32] gathered by a tag plan sp of the chunk's nq queries; X, xn = the store of nx rows;
 // the plan's Dense strips by the staged kernel under ns_dense splits, its Indirect strips (forms bit kSweepColsIndirect) by
 // the per-wave kernel under ns_ind; part: [max(ns_dense, ns_ind)][bound * 32][k]; results at the queries' own places.
+// win (base values on the float16 store): sp and win are launch_value_strip_plan's, and the Indirect strips
+// -- spans of the holder's row order, each row with its own window -- go to the windowed per-wave kernel.
 hipError_t launch_f16_store_rows(hipStream_t s, const float *src, size_t src_stride, void *dst, float *norms, size_t count, int d,
                                  const int32_t *row_src);
 hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
                                           size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
-                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms);
+                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms,
+                                          const StripWin *win = nullptr);
 // ... and the range search under them: launch_exact_range_f16 over a tag plan of the chunk that begins at
 // query q_off of the call, one form per call as there.  slices: [queries of the call][max(ns_dense, ns_ind)], keyed by the
 // caller's query; map (nullable): [strips of the call][exact_range_f16_strips_map_words], keyed by sp.map_strip0 + plan

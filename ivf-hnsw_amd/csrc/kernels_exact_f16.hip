@@ -497,6 +497,221 @@ hipError_t launch_exact_f16_rows_t(hipStream_t s, const _Float16 *Qh, const floa
     return hipGetLastError();
 }
 
+// ---- the windowed strips (ivfhnsw_gpu_exact_search_f16_values) -------------------------------------------
+// A windowed strip of a value plan sweeps a span of the holder's rows in (value, row) order, and every strip row counts only
+// the columns of ITS OWN window win[32 strip + row] = [wa, wb) of the span.  The sweep is exact_f16_rows_kernel's -- a strip a
+// wave, no barrier, no LDS tile, operand A resident, operand B straight from the store through the span's row numbers in
+// MFMA order, the same prefetch depths -- with three things of its own.
+//   Windows in lanes.  Lanes m and m + 32 hold row m's window.  Whether a tile of 32 columns is LIVE -- some window meets
+//   it -- is one ballot over (c0, wa, wb): it depends on nothing that is loaded.  The pipeline therefore aims at live tiles
+//   only, as exact_range_f16_rows_kernel's aims at visited ones: t is the tile being multiplied, tn the next live one (its
+//   norms and pieces are requested now), ta the live one after it (its row numbers are).  next_tile decides before anything
+//   of a tile is requested: a dead tile costs no row number, norm, piece or MFMA.  It steps while tiles are live -- one
+//   ballot -- and at the first dead tile JUMPS: every lane whose window ends beyond the tile offers the tile its window
+//   starts in, a wave minimum (five exchanges) takes the nearest.  A gap costs one reduction however long it is.
+//   The two tests.  The cheap test counts an accumulator register only where its row's live bit is set; a tile inside
+//   every non-empty window (`all`, a second ballot) takes the unwindowed test.  A padding row and a row whose window is
+//   empty hold the threshold -inf and so the gate +inf, for good.  The exact test, behind the cheap one, reads the row's
+//   window from its lane and rejects the columns of an edge tile outside it.
+//   Arrival order.  Columns come in (value, row) order, not label order, so `<` alone no longer sends a tie to the lower
+//   label.  Admission is dist <= thr; compaction, write-out and merge rank whole (distance bits, label) keys, which are
+//   distinct, so of equal distances the lower label stays.  The cheap test is `>=`: f16_gate's margin is 2^-18 (qn + |thr|),
+//   which is zero for a zero query whose k-th distance is zero, and 2 dot - xn > qn - thr would then drop dist == thr.
+//   The buffer bound is unchanged by `<=`: a row enters a tile with at most CAP - 32 keys (one with more was compacted to
+//   min(n, k) <= CAP - 32 keys behind the tile before: k <= 16 / 32 / 100 against CAP - 32 = 16 / 32 / 104), and a tile
+//   appends at most its 32 columns.
+// A split of the span without a live tile still writes its (empty) rows: the merge reads every split that has columns.
+template <int ND, int CAP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void exact_f16_windows_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                                       const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                                       int nrows, int k, unsigned long long *__restrict__ out_keys,
+                                                                       StripPlan sp, const StripWin *__restrict__ win)
+{
+    constexpr int D = 16 * ND;
+    constexpr int NPRE = ND <= 8 ? ND : (ND + 1) / 2, NLATE = ND - NPRE;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *s_buf = reinterpret_cast<unsigned long long *>(smem); // [WAVES][32][CAP]
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_buf + WAVES * 32 * CAP);  // [WAVES][32]
+    float *s_thr = reinterpret_cast<float *>(s_cnt + WAVES * 32);             // [WAVES][32]
+
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const uint32_t strip = sp.hdr->lay.range[kSweepColsIndirect][0] + blockIdx.x * WAVES + wave;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][1])
+        return;
+    const StripCols e = sp.strip_cols[strip];
+    size_t cb, ce;
+    sweep_split_cut(e.nx, (int)gridDim.y, (int)blockIdx.y, &cb, &ce);
+    if (cb >= ce)
+        return;
+    const uint32_t c_begin = (uint32_t)cb, c_end = (uint32_t)ce; // (columns of a span: below the rows of the store)
+    const uint32_t ntiles = (c_end - c_begin + 31u) >> 5;
+    const uint32_t *__restrict__ rows = e.data;
+    const int r0 = (int)(strip << 5); // (strip < the plan's bound: every row of it exists in Qh, qn, strip_rows and win)
+    unsigned long long *buf = s_buf + (size_t)wave * 32 * CAP;
+    uint32_t *cnt = s_cnt + wave * 32;
+    float *thr_s = s_thr + wave * 32;
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)(r0 + m) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    // the window of row m, in the span's columns; bit m of `empty`: row m has none
+    const StripWin w = win[r0 + m];
+    const uint32_t wa = w.a, wb = w.b;
+    const uint32_t empty = (uint32_t)__ballot(wa >= wb);
+    if (lane < 32) {
+        cnt[lane] = 0;
+        thr_s[lane] = sp.strip_rows[r0 + lane] >= 0 && wa < wb ? FLT_MAX : -INFINITY;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float qn_r[16], gate[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        qn_r[r] = qn[r0 + row];
+        gate[r] = f16_gate(qn_r[r], thr_s[row]);
+    }
+
+    // the first column of tile t; does the lane's window meet the tile that begins at c0 (an empty window meets none; the
+    // launch keeps columns below 2^32 - 64)
+    auto col0 = [&](uint32_t t) -> uint32_t { return c_begin + (t << 5); };
+    auto meets = [&](uint32_t c0) -> bool { return wa < c0 + 32u && wb > c0; };
+    // the first live tile at or after t (ntiles: none); wave-uniform, from the windows alone
+    auto next_tile = [&](uint32_t t) -> uint32_t {
+        if (t >= ntiles)
+            return ntiles;
+        const uint32_t c0 = col0(t);
+        if (__ballot(meets(c0)))
+            return t;
+        // dead: the tile in which the nearest window that ends beyond c0 begins (it begins beyond the tile, or it would meet it)
+        uint32_t tt = wa < wb && wb > c0 ? ((wa > c0 ? wa : c0) - c_begin) >> 5 : ~0u;
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) // (lanes m and m + 32 hold the same window: each half finds the minimum)
+            tt = min(tt, (uint32_t)__shfl_xor((int)tt, o));
+        tt = __builtin_amdgcn_readfirstlane(tt);
+        return tt < ntiles ? tt : ntiles;
+    };
+
+    const unsigned char *xb = reinterpret_cast<const unsigned char *>(X) + 16 * kk;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the row number of the lane's column of tile t
+    auto ids = [&](uint32_t t) -> uint32_t { return col0(t) + m < c_end ? rows[col0(t) + m] : 0u; };
+    // pieces [first, first + N) of store row `row` into w; ok: the lane has a column
+    auto pieces = [&](uint32_t row, bool ok, int first, auto &w) {
+        constexpr int N = (int)(sizeof(w) / sizeof(w[0]));
+        const unsigned char *p = xb + (size_t)row * (2 * D) + 32 * first;
+#pragma unroll
+        for (int s = 0; s < N; s++)
+            w[s] = zero;
+        if (ok) {
+#pragma unroll
+            for (int s = 0; s < N; s++)
+                w[s] = *reinterpret_cast<const f16x8 *>(p + 32 * s);
+        }
+    };
+    // Tile t: `cur`, n_cur = its first NPRE pieces and its norms, id_cur its row numbers.  Starts the loads of tile tn (row
+    // numbers id_nxt) into nxt, n_nxt and of the row numbers of tile ta into id_ahead.
+    auto tile = [&](uint32_t t, const f16x8 (&cur)[NPRE], float n_cur, uint32_t id_cur, uint32_t tn, f16x8 (&nxt)[NPRE], float &n_nxt,
+                    uint32_t id_nxt, uint32_t ta, uint32_t &id_ahead) {
+        const uint32_t c0 = col0(t), col = c0 + m;
+        const bool col_ok = col < c_end;
+        f16x8 late[NLATE > 0 ? NLATE : 1];
+        if constexpr (NLATE > 0)
+            pieces(id_cur, col_ok, NPRE, late);
+        if (tn < ntiles) { // in flight behind this tile's MFMAs
+            const bool ok = col0(tn) + m < c_end;
+            pieces(id_nxt, ok, 0, nxt);
+            n_nxt = ok ? xn[id_nxt] : 0.f;
+        }
+        if (ta < ntiles)
+            id_ahead = ids(ta);
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < NPRE; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], cur[s], acc, 0, 0, 0);
+        if constexpr (NLATE > 0) {
+#pragma unroll
+            for (int s = 0; s < NLATE; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPRE + s], late[s], acc, 0, 0, 0);
+        }
+        // the cheap test: inside every non-empty window the unwindowed one, else a register counts where its row is live
+        const bool all = ((uint32_t)__ballot(wa <= c0 && wb >= c0 + 32u) | empty) == ~0u; // wave-uniform
+        bool any = false;
+        if (all) {
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), n_cur) >= gate[r];
+        } else {
+            const uint32_t lv = (uint32_t)__ballot(meets(c0)) >> (4 * kk); // bit (r & 3) + 8 (r >> 2): register r's row is live
+            uint32_t bits = 0;
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                bits |= __fsub_rn(__fmul_rn(2.0f, acc[r]), n_cur) >= gate[r] ? 1u << ((r & 3) + 8 * (r >> 2)) : 0u;
+            any = (bits & lv) != 0u;
+        }
+        if (__ballot(any && col_ok)) { // wave-uniform: rare once the thresholds have settled
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float dist = __fsub_rn(__fadd_rn(qn_r[r], n_cur), __fmul_rn(2.0f, acc[r]));
+                const int row = mfma32_row(r, kk);
+                const uint32_t ra = (uint32_t)__shfl((int)wa, row), rb = (uint32_t)__shfl((int)wb, row); // (every lane: read from another)
+                const bool pass = col_ok && col >= ra && col < rb && dist <= thr_s[row];
+                const unsigned long long mask = __ballot(pass);
+                if (mask)
+                    row_append<CAP>(buf, cnt, row, pass, mask, dist, id_cur, m, kk);
+            }
+            rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+        }
+    };
+
+    uint32_t t = next_tile(0);
+    if (t < ntiles) {
+        uint32_t tn = next_tile(t + 1), ta;
+        f16x8 b0[NPRE], b1[NPRE];
+        float n0, n1 = 0.f;
+        uint32_t id0 = ids(t), id1 = 0, id_ahead = 0;
+        pieces(id0, col0(t) + m < c_end, 0, b0);
+        n0 = col0(t) + m < c_end ? xn[id0] : 0.f;
+        if (tn < ntiles)
+            id1 = ids(tn);
+        for (;;) {
+            ta = next_tile(tn + 1);
+            tile(t, b0, n0, id0, tn, b1, n1, id1, ta, id_ahead);
+            if (tn >= ntiles)
+                break;
+            t = tn, tn = ta, id0 = id_ahead;
+            ta = next_tile(tn + 1);
+            tile(t, b1, n1, id1, tn, b0, n0, id0, ta, id_ahead);
+            if (tn >= ntiles)
+                break;
+            t = tn, tn = ta, id1 = id_ahead;
+        }
+    }
+
+    // out: [split][plan row][k] keys, every row of the strip (a padding row holds nothing)
+    rows_write_out<CAP>(buf, cnt, k, lane, 32, out_keys, (size_t)blockIdx.y * nrows + r0);
+}
+
+template <int ND, int CAP, int WAVES>
+hipError_t launch_exact_f16_windows_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn,
+                                      size_t bound, int k, int nsplit, unsigned long long *part, const StripPlan &sp, const StripWin *win)
+{
+    const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(float));
+    constexpr auto kern = exact_f16_windows_kernel<ND, CAP, WAVES>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((bound + WAVES - 1) / WAVES), (unsigned)nsplit), dim3(64 * WAVES), shm, s, Qh, qn, X, xn,
+                       (int)(bound * 32), k, part, sp, win);
+    return hipGetLastError();
+}
+
 // f(int_c<ND>()) for ND = d / 16 = 1 .. 16; any other d is refused
 template <class F> hipError_t by_f16_steps(int d, F &&f)
 {
@@ -1005,15 +1220,18 @@ hipError_t launch_exact_search_f16(hipStream_t s, const void *Qh, const float *q
 // ... under a tag plan: Qh, qn [bound * 32] = the chunk's nq queries gathered by the plan
 // (launch_f16_store_rows), part [max(ns_dense, ns_ind)][bound * 32][k]; the Dense strips by the staged kernel under ns_dense
 // splits, the Indirect ones (forms bit kSweepColsIndirect) by the per-wave kernel under ns_ind; results in the caller's
-// order, FLT_MAX / -1 for a query without a strip
+// order, FLT_MAX / -1 for a query without a strip.  win (base values): sp is a value plan, its Indirect strips
+// are windowed -- each row with its own window win[32 strip + row] of the strip's span -- and go to the windowed kernel
 hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
                                           size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
-                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms)
+                                          float *dists, int64_t *labels, const StripPlan &sp, unsigned forms, const StripWin *win)
 {
     if (nq == 0)
         return hipSuccess;
     if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || bound == 0 || bound > (0x7fffffffull >> 5) || nx == 0 || nx >= 0xffffffffull ||
         ns_dense < 1 || ns_dense > 64 || ns_ind < 1 || ns_ind > 64 || !sp.hdr || !sp.strip_rows || !sp.strip_cols)
+        return hipErrorInvalidValue;
+    if (win && nx > 0xffffffffull - 64) // (the windowed kernel adds a tile's 32 columns to a column in 32 bits)
         return hipErrorInvalidValue;
     const int rows = (int)(bound * 32);
     if (hipError_t e = launch_exact_pad(s, dists, labels, nq * (size_t)k); e != hipSuccess)
@@ -1029,6 +1247,10 @@ hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const f
                                  : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds);
         if (e != hipSuccess || !indirect)
             return e;
+        if (win)
+            return k <= 16   ? launch_exact_f16_windows_t<ND, 48, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp, win)
+                   : k <= 32 ? launch_exact_f16_windows_t<ND, 64, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp, win)
+                             : launch_exact_f16_windows_t<ND, 136, 2>(s, q, qn, x, xn, bound, k, ns_ind, part, sp, win);
         return k <= 16   ? launch_exact_f16_rows_t<ND, 48, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp)
                : k <= 32 ? launch_exact_f16_rows_t<ND, 64, 4>(s, q, qn, x, xn, bound, k, ns_ind, part, sp)
                          : launch_exact_f16_rows_t<ND, 136, 2>(s, q, qn, x, xn, bound, k, ns_ind, part, sp);

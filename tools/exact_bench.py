@@ -51,12 +51,16 @@
      radius of the tagged 10th neighbour, alternating with exact_range_search_tags_dev on the uint8 store (the two must
      agree), the tagged k = 1 sweep, the call without the tile map and the call under the neighbouring split counts; and
      its all-NONE batch alternating with the plain exact_range_search_f16_dev.
+     With --f16 --values base values on the float16 store (ivfhnsw_gpu_exact_search_f16_values_dev) at
+     d = 128: the three workloads of 7., k = 1 and 100, ALTERNATING with exact_search_values_dev on the uint8 store of the
+     same rows (the two must agree); and the all-FULL batch alternating with the plain exact_search_f16_dev, with the plan
+     stage (plan and gather) from the stage profiler.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
 usage: python tools/exact_bench.py [--rows 1000000000] [--small-rows 10000000] [--nq 10000] [--reps 3] [--warmup 1]
                                    [--no-big] [--no-small] [--no-knn] [--no-range] [--filter] [--filter-slots] [--tags] [--values]
-                                   [--dense-nq 512] [--f16 [--range] [--tags]]
+                                   [--dense-nq 512] [--f16 [--range] [--tags] [--values]]
                                    [--out result.json]"""
 import argparse
 import json
@@ -577,6 +581,73 @@ def main():
         g.set_option("exact_splits", -1)
         g.set_option("exact_range_map", -1)
 
+    def alternate(calls, what):
+        """{name: seconds of every timed rep} of calls [(name, fn)] run in turn, rep by rep"""
+        ts = {name: [] for name, _ in calls}
+        for rep in range(args.warmup + args.reps):
+            for name, fn in calls:
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize(dev)
+                if rep >= args.warmup:
+                    ts[name].append(time.perf_counter() - t0)
+                log("[exact_bench] f16 %s rep %d %s: %.4f s" % (what, rep, name, time.perf_counter() - t0))
+        return ts
+
+    def f16_values_legs(n, dd, g8, qf, qb):
+        """Base values on the float16 store (exact_search_f16_values_dev) on the rows f16_legs uploaded to both
+        stores: values_legs' three workloads over a permutation of 0..n-1, k = 1 and 100, the call ALTERNATING with
+        exact_search_values_dev on the uint8 store (the two must agree); then the all-FULL batch beside the plain
+        exact_search_f16_dev, its plan stage (plan and gather) from the stage profiler."""
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(8100)
+        values = torch.randperm(n, device=dev, generator=gen).to(torch.int32)
+        rows_i = torch.arange(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        g.set_base_values_dev(n, rows_i, values)
+        g8.set_base_values_dev(n, rows_i, values)
+
+        def spread(count, width):
+            return [(a, a + width - 1) for a in ((i * (n - width)) // max(1, count - 1) for i in range(count))]
+        workloads = [("897 x 1/8", spread(897, n // 8), 0), ("1000 x ~100 rows", spread(1000, min(n, 100)), 0),
+                     ("1000 x ~100 rows, 1/33 full", spread(1000, min(n, 100)), 33), ("all full", [(0, 0xffffffff)], 0)]
+        for wname, ivs, full_share in workloads:
+            pick = (torch.arange(nq, device=dev) % len(ivs))[torch.randperm(nq, device=dev, generator=gen)]
+            qr64 = torch.tensor(ivs, dtype=torch.int64, device=dev)[pick]
+            if full_share:
+                qr64[torch.arange(nq, device=dev) % full_share == full_share - 1] = torch.tensor((0, 0xffffffff), dtype=torch.int64, device=dev)
+            qr = torch.where(qr64 >= 2 ** 31, qr64 - 2 ** 32, qr64).to(torch.int32).contiguous()  # the bit pattern of the uint32
+            for k in (1, 100):
+                od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                ol = torch.empty((nq, k), dtype=torch.int64, device=dev)
+                od8, ol8 = torch.empty_like(od), torch.empty_like(ol)
+                plan_ms = []
+
+                def valued():
+                    g.set_profiling(True)
+                    g.reset_stage_ms()
+                    g.exact_search_f16_values_dev(nq, qf, dd, k, qr, od, ol)
+                    torch.cuda.synchronize(dev)
+                    plan_ms.append(g.stage_ms()["plan"][0])
+                    g.set_profiling(False)
+
+                if wname == "all full":
+                    other = ("exact_search_f16_dev", lambda: g.exact_search_f16_dev(nq, qf, dd, k, od8, ol8))
+                else:
+                    other = ("exact_search_values_dev (uint8 store)", lambda: g8.exact_search_values_dev(nq, qb, dd, k, qr, od8, ol8))
+                ts = alternate([("exact_search_f16_values_dev", valued), other], "values '%s' k=%d" % (wname, k))
+                assert torch.equal(ol, ol8) and torch.equal(od, od8), "exact_search_f16_values_dev and %s disagree" % other[0]
+                a, b = ts["exact_search_f16_values_dev"], ts[other[0]]
+                r = {"what": "exact_search_f16_values_dev", "beside": other[0], "rows": n, "d": dd, "nq": nq, "k": k, "workload": wname,
+                     "seconds": round(statistics.median(a), 5), "reps": [round(x, 5) for x in a],
+                     "beside_seconds": round(statistics.median(b), 5), "beside_reps": [round(x, 5) for x in b],
+                     "plan_and_gather_ms": round(statistics.median(plan_ms[args.warmup:]), 4)}
+                result["rows"].append(r)
+                print(json.dumps(r), flush=True)
+        g.clear_base_values()
+        g8.clear_base_values()
+
     def f16_tags_range_leg(n, dd, g8, qf, qb, qt, ntags, radius, alternate, with_splits):
         """The range form under base tags (exact_range_search_f16_tags_dev) at the radius of the tagged 10th
         neighbour: beside exact_range_search_tags_dev of the uint8 store (equal results required), the tagged k = 1 sweep,
@@ -639,19 +710,6 @@ def main():
         q asks for q % ntags) and k: the tagged call under the rule's split count and under its neighbours beside
         exact_search_tags_dev on the uint8 store; then the all-NONE batch beside the plain exact_search_f16_dev, with the
         plan stage (the plan and the gather) timed by the stage profiler."""
-        def alternate(calls, what):
-            ts = {name: [] for name, _ in calls}
-            for rep in range(args.warmup + args.reps):
-                for name, fn in calls:
-                    torch.cuda.synchronize(dev)
-                    t0 = time.perf_counter()
-                    fn()
-                    torch.cuda.synchronize(dev)
-                    if rep >= args.warmup:
-                        ts[name].append(time.perf_counter() - t0)
-                    log("[exact_bench] f16 tags %s rep %d %s: %.4f s" % (what, rep, name, time.perf_counter() - t0))
-            return ts
-
         def with_splits(s, fn):
             g.set_option("exact_splits", s)
             fn()
@@ -772,6 +830,8 @@ def main():
             kth[k] = od[:, k - 1].clone()
         if args.tags and dd == 128:
             f16_tags_legs(n, dd, g8, qf, qb)
+        if args.values and dd == 128:
+            f16_values_legs(n, dd, g8, qf, qb)
         g8.close()
         if args.range:
             f16_range_legs(n, dd, qf, kth[10], kth[100])

@@ -26,13 +26,14 @@ gets only rows whose value lies in [lo, hi], inclusive ((0, 0xffffffff): every r
 
 With an .fvecs base and .fvecs queries (float corpora: DEEP1B) the same .ivecs is written from the float16 base store
 (upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; of the filters the k-search
-takes --tags with --query-tags (ivfhnsw_gpu_exact_search_f16_tags, 3.29), nothing else.  With
+takes --tags with --query-tags (ivfhnsw_gpu_exact_search_f16_tags, 3.29) or --values with --query-ranges
+(ivfhnsw_gpu_exact_search_f16_values, 3.31), nothing else.  With
 --radius the .npz comes from ivfhnsw_gpu_exact_range_search_f16 (3.28): the rows whose float32 distance between the rounded
 vectors, the value the k-search returns, is < R -- and with --tags and --query-tags from
-ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag.
+ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag; --values is refused there.
 
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
-       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N] [--tags t.npy --query-tags qt.npy]
+       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N] [--tags t.npy --query-tags qt.npy | --values v.npy --query-ranges qr.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N] [--tags t.npy --query-tags qt.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
@@ -190,16 +191,23 @@ def read_fvecs_image(path):
     return img, d
 
 
-def ground_truth_f16(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=None, tags=None, query_tags=None):
+def ground_truth_f16(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=None, tags=None, query_tags=None, values=None,
+                     query_ranges=None):
     """The same for an .fvecs base and .fvecs queries, through the float16 base store: both are rounded to
     half, and the order is that of ivfhnsw_gpu_exact_search_f16's float32 distances between the rounded vectors.  With
-    `tags` and `query_tags` only of the rows that carry the query's tag (ivfhnsw_gpu_exact_search_f16_tags, 3.29)."""
+    `tags` and `query_tags` only of the rows that carry the query's tag (ivfhnsw_gpu_exact_search_f16_tags, 3.29), with
+    `values` and `query_ranges` only of the rows whose value lies in the query's interval (ivfhnsw_gpu_exact_search_f16_values,
+    3.31)."""
     img, dq = read_fvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
         n, d = g.upload_base_fvecs(base_path, chunk_rows=chunk_rows, rows=rows)
         if d != dq:
             raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        if values is not None:
+            install_values(g, n, img.shape[0], values, query_ranges)
+            _, lab = g.exact_search_f16_values(img[:, 1:], k, query_ranges)
+            return lab
         if tags is not None:
             install_tags(g, n, img.shape[0], tags, query_tags)
         _, lab = g.exact_search_f16_tags(img[:, 1:], k, query_tags if tags is not None else None)
@@ -213,12 +221,12 @@ def ground_truth(pkg, base_path, query_path, k, rows=None, device=0, chunk_rows=
     """labels int64 [nq, k] (-1 beyond the base's rows) of the exact k nearest base rows of every query; with `labels`
     only of the rows whose number is in them (deny: is not); with `tags` and `query_tags` only of the rows that carry the
     query's tag; with `values` and `query_ranges` only of the rows whose value lies in the query's interval.  An .fvecs
-    base goes to the float16 store (ground_truth_f16), which of the filters takes tags only."""
+    base goes to the float16 store (ground_truth_f16), which of the filters takes tags or values."""
     if base_path.endswith(".fvecs"):
-        if labels is not None or values is not None:
-            raise ValueError("an .fvecs base goes to the float16 store, which takes tags but no filter or values")
+        if labels is not None:
+            raise ValueError("an .fvecs base goes to the float16 store, which takes tags or values but no filter")
         return ground_truth_f16(pkg, base_path, query_path, k, rows=rows, device=device,  # (upload_base_fvecs sizes its chunks)
-                                tags=tags, query_tags=query_tags)
+                                tags=tags, query_tags=query_tags, values=values, query_ranges=query_ranges)
     img, dq = read_bvecs_image(query_path)
     g = pkg.GpuIndex(device)
     try:
@@ -248,7 +256,7 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
     (ivfhnsw_gpu_exact_range_search_f16_tags, 3.30) and none of the other filters."""
     if base_path.endswith(".fvecs"):
         if labels is not None or values is not None:
-            raise ValueError("an .fvecs base goes to the float16 store, which takes tags but no filter or values")
+            raise ValueError("an .fvecs base goes to the float16 store, whose range search takes tags but no filter or values")
         img, dq = read_fvecs_image(query_path)
         g = pkg.GpuIndex(device)
         try:
