@@ -817,7 +817,8 @@ int ivfhnsw_gpu_upload_base_dev(ivfhnsw_gpu *h, size_t n, size_t d, size_t first
  * so do set_base_filter and set_base_filter_slot: of the base filters it takes tags (set_base_tags, clear_base_tags,
  * base_tags_info, base_tag_rows as on a uint8 store; ivfhnsw_gpu_exact_search_f16_tags searches under them) and values
  * (set_base_values, clear_base_values, base_values_info, base_value_rows as on a uint8 store;
- * ivfhnsw_gpu_exact_search_f16_values searches under them).
+ * ivfhnsw_gpu_exact_search_f16_values and ivfhnsw_gpu_exact_range_search_f16_values search under them).
+ * Not built on a float16 store: an interval AND a tag, the class surface, 64-bit values.
  * ivfhnsw_gpu_base_kind: what the handle (a view: its parent) holds. */
 #define IVFHNSW_BASE_NONE 0
 #define IVFHNSW_BASE_U8 1
@@ -924,6 +925,24 @@ int ivfhnsw_gpu_exact_range_search_f16_tags(ivfhnsw_gpu *h, size_t nq, const flo
                                             const uint16_t *query_tags, float radius, uint64_t *lims, uint64_t *total);
 int ivfhnsw_gpu_exact_range_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride,
                                                 const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total);
+
+/* ... and the range form under base values: the truth of range_search_values for a float corpus, with the
+ * semantics of ivfhnsw_gpu_exact_range_search_values over the float16 store's distances.  query_ranges [2 nq] uint32, (lo, hi)
+ * per query: the query gets every row whose base value v has lo <= v <= hi, unsigned and inclusive, a row without a value
+ * holding 0xffffffff, and whose distance -- the value exact_search_f16_values and exact_range_search_f16 (below) write for
+ * the pair, bit for bit -- is < radius (strict), in ascending label.  (0, 0xffffffff) searches the whole store; an interval
+ * no row's value lies in, lo > hi included, returns nothing.  lims [nq + 1] and the results stand in the caller's query
+ * order and are read through ivfhnsw_gpu_exact_range_results[_dev].  query_ranges == NULL is exact_range_search_f16 itself.
+ * Radius, limits (131 072 queries a call), errors, memory, the one synchronisation and the options "exact_splits" and
+ * "exact_range_map" as exact_range_search_f16 -- but a set_base_filter filter -> IVFHNSW_ERR_STATE, and base tags on the
+ * holder are ignored; the queries are kept in strips of 32 (at most nq / 32 + 2 per 16 384 queries), and where a windowed
+ * strip ran the held results are put in (query, label) order before the call returns: 28 bytes and a little more per
+ * result while that runs.  A view searches its parent's store under its parent's values.  _dev: d_query_ranges in device
+ * memory, 8-byte aligned. */
+int ivfhnsw_gpu_exact_range_search_f16_values(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride,
+                                              const uint32_t *query_ranges, float radius, uint64_t *lims, uint64_t *total);
+int ivfhnsw_gpu_exact_range_search_f16_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride,
+                                                  const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total);
 
 /* ---- exact range search of the base store ----------------------------------------------------------
  *

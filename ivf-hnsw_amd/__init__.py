@@ -82,6 +82,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_search_f16_tags", "ivfhnsw_gpu_exact_search_f16_tags_dev",
     "ivfhnsw_gpu_exact_range_search_f16_tags", "ivfhnsw_gpu_exact_range_search_f16_tags_dev",
     "ivfhnsw_gpu_exact_search_f16_values", "ivfhnsw_gpu_exact_search_f16_values_dev",
+    "ivfhnsw_gpu_exact_range_search_f16_values", "ivfhnsw_gpu_exact_range_search_f16_values_dev",
 )
 
 
@@ -299,6 +300,8 @@ def lib():
         L.ivfhnsw_gpu_exact_search_f16_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_range_search_f16_values_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_range_search.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(SearchParams), C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.ivfhnsw_gpu_range_search_dev.argtypes = L.ivfhnsw_gpu_range_search.argtypes
@@ -1467,6 +1470,34 @@ class GpuIndex:
         _check(lib().ivfhnsw_gpu_exact_range_search_f16_tags_dev(self._h, nq, _devptr(d_queries), row_stride,
                                                                  _devptr(d_query_tags), C.c_float(radius), _devptr(d_lims),
                                                                  C.byref(total)))
+        return int(total.value)
+
+    def exact_range_search_f16_values(self, queries_f32, radius, query_ranges):
+        """exact_range_search_f16() with an interval of base values per query (set_base_values on the float16 store;
+        ivfhnsw_gpu_exact_range_search_f16_values): query_ranges [nq, 2] uint32, (lo, hi) inclusive, (0, VALUE_NONE) = the
+        whole store; None is exact_range_search_f16() itself.  lims in the caller's query order, results per query in
+        ascending label."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq, 2)
+        lims = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16_values(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride,
+                                                               _ptr(qr), C.c_float(radius), _ptr(lims), C.byref(total)))
+        dist, lab = self.exact_range_results(0, int(total.value))
+        return lims, dist, lab
+
+    def exact_range_search_f16_values_dev(self, nq, d_queries, row_stride, d_query_ranges, radius, d_lims):
+        """The same on device buffers (d_query_ranges: [nq, 2] uint32 in device memory); returns the number of results,
+        which stay in the handle's memory."""
+        total = C.c_uint64(0)
+        _check(lib().ivfhnsw_gpu_exact_range_search_f16_values_dev(self._h, nq, _devptr(d_queries), row_stride,
+                                                                   _devptr(d_query_ranges), C.c_float(radius), _devptr(d_lims),
+                                                                   C.byref(total)))
         return int(total.value)
 
     def rerank(self, queries, cand, k):

@@ -472,6 +472,7 @@ struct F16RangeStrips {
     unsigned forms = 0;
     int ns_dense = 1, ns_ind = 1;
     std::vector<StripPlan> plans;
+    std::vector<const StripWin *> wins; // a _values call (3.32): the windows of each plan's strip rows; else empty
 };
 
 int exact_range_f16_strips_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const F16RangeStrips &rs, bool fill, size_t nq, float radius,
@@ -484,7 +485,7 @@ int exact_range_f16_strips_pass(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const F16R
         HIP_TRY(launch_exact_range_f16_strips(h->stream, fill, h->ex_q.as<unsigned char>() + i * rows * d * 2, h->ex_qn.as<float>() + i * rows,
                                               b->base_rows.p, b->base_norms.as<float>(), rs.bound, q0, b->base_n, (int)d, radius, rs.ns_dense,
                                               rs.ns_ind, h->xr_slices.as<uint32_t>(), h->xr_tot.as<unsigned long long>(), map, map_shift,
-                                              dist, labels, out_cap, rs.plans[i], rs.forms));
+                                              dist, labels, out_cap, rs.plans[i], rs.forms, rs.wins.empty() ? nullptr : rs.wins[i]));
     return IVFHNSW_OK;
 }
 
@@ -588,6 +589,137 @@ int exact_range_f16_tags_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, s
     return IVFHNSW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// ... with an interval of base values per query: the same sequence around the two kernels a value plan
+// takes.  Per chunk of kExactChunk queries the value plan is made once and kept for both passes -- the plan, the windows of
+// its strip rows and its place in the tile map -- with chunk i's gathered queries at row i * bound * 32 of h->ex_q /
+// h->ex_qn.  The windowed strips write a query's results in (value, row) order: where any chunk has one and there are
+// results, they are gathered by label behind the fill pass, as exact_range_dev of the uint8 store does (RangeByLabel).
+
+// The splits of the windowed launch over `rows` padded strip rows and a store of nx rows, the longest span a strip can have.
+// exact_splits_for(rows, nx, 1) -- the uint8 sweep's rule, a workgroup of four strips -- asks for enough workgroups for two
+// per CU and rounds UP: 10 000 queries are 79 workgroups, 7 splits, 553 workgroups on 512 places, and the 41 left over run
+// a second round alone.  This rule rounds DOWN, to the most splits whose workgroups all run at once (6 there: measured 23 %
+// faster than 7 on long windows and level with it on short ones); a split never shorter than 4096 columns.
+// Two workgroups per CU is what the registers give up to d = 160; beyond it the count has not been measured.
+int exact_range_f16_window_splits_for(size_t rows, size_t nx)
+{
+    const size_t blocks = (rows + 127) / 128, max_s = std::min<size_t>(64, std::max<size_t>(1, (nx + 4095) / 4096));
+    return (int)std::max<size_t>(1, std::min(max_s, 512 / blocks));
+}
+
+// device pointers, the arguments checked (nq > 0)
+int exact_range_f16_values_dev(ivfhnsw_gpu *h, const ivfhnsw_gpu *b, const char *who, size_t nq, const float *d_queries, size_t row_stride,
+                               const uint32_t *d_ranges, const ValueRows &vr, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    const size_t d = b->base_d, n = b->base_n, first = std::min(nq, kExactChunk), nchunks = (nq + kExactChunk - 1) / kExactChunk;
+    F16RangeStrips rs;
+    rs.bound = sweep_value_strip_bound(first);
+    // the windowed sweep only where a row holds a value
+    rs.forms = 1u << kSweepColsDense | (vr.vals ? 1u << kSweepColsIndirect : 0u);
+    // Dense: the plain call's rule over the chunk's queries padded to a strip; windowed: its own rule over the rows of
+    // every strip the plan can have
+    rs.ns_dense = exact_range_f16_splits_for((first + 31) / 32 * 32, n, d);
+    rs.ns_ind = vr.vals ? exact_range_f16_window_splits_for(rs.bound * 32, n) : 1;
+    if (h->opt_exact_splits > 0)
+        rs.ns_dense = rs.ns_ind = h->opt_exact_splits;
+    rs.plans.resize(nchunks);
+    rs.wins.assign(nchunks, nullptr);
+    std::vector<uint32_t> win_range(2 * nchunks, 0u); // per chunk the strips of its plan that are windowed, read back with the count
+    const int nsplit = std::max(rs.ns_dense, rs.ns_ind); // the one width of the slices table
+    const size_t len = nq * (size_t)nsplit + 1, rows = nchunks * rs.bound * 32, plan_bytes = sweep_value_plan_bytes(rs.bound);
+    size_t map_bytes = 0;
+    const int map_shift = exact_range_map_shift(rows, n, 2 * d, nsplit, &map_bytes);
+    map_bytes = rows / 32 * exact_range_f16_strips_map_words(n, rs.ns_dense, rs.ns_ind, map_shift) * sizeof(uint32_t);
+    int rc;
+    if ((rc = h->ex_q.ensure(rows * d * 2)) || (rc = h->ex_qn.ensure(rows * sizeof(float))) ||
+        (rc = h->xr_slices.ensure(len * sizeof(uint32_t))) || (rc = h->xr_part.ensure(append_scan_parts(len) * sizeof(uint32_t))) ||
+        (rc = h->xr_tot.ensure(sizeof(unsigned long long))) || (h->opt_exact_range_map && (rc = h->xr_map.ensure(map_bytes))) ||
+        (rc = h->bs_plan.ensure(nchunks * plan_bytes)) || (rc = h->bv_work.ensure(value_plan_work_words(first) * sizeof(uint32_t))))
+        return rc;
+    {
+        StageScope sc(h, IVFHNSW_STAGE_PLAN); // the plans and the gathers, accounted apart from the sweeps
+        for (size_t q0 = 0, i = 0; q0 < nq; q0 += kExactChunk, i++) {
+            StripPlan &sp = rs.plans[i];
+            HIP_TRY(launch_value_strip_plan(h->stream, d_ranges + 2 * q0, std::min(kExactChunk, nq - q0), vr,
+                                            h->bs_plan.as<unsigned char>() + i * plan_bytes, rs.bound, h->bv_work.as<uint32_t>(), &sp,
+                                            &rs.wins[i]));
+            HIP_TRY(hipMemcpyAsync(&win_range[2 * i], sp.hdr->lay.range[kSweepColsIndirect], 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   h->stream));
+            sp.map_strip0 = (uint32_t)(i * rs.bound);
+            // the queries as the store holds its rows, in strip order; a padding row repeats the chunk's first query
+            HIP_TRY(launch_f16_store_rows(h->stream, d_queries + q0 * row_stride, row_stride, h->ex_q.as<unsigned char>() + i * rs.bound * 32 * d * 2,
+                                          h->ex_qn.as<float>() + i * rs.bound * 32, rs.bound * 32, (int)d, sp.strip_rows));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(h->xr_slices.p, 0, len * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->xr_tot.p, 0, sizeof(unsigned long long), h->stream));
+    if ((rc = exact_range_f16_strips_pass(h, b, rs, false, nq, radius, map_shift, nullptr, nullptr, 0)))
+        return rc;
+    unsigned long long tot = 0;
+    if ((rc = exact_range_total(h, who, len, &tot))) // (the synchronisation that brings win_range)
+        return rc;
+    bool windowed = false;
+    for (size_t i = 0; i < nchunks; i++)
+        windowed |= (rs.forms >> kSweepColsIndirect & 1u) && win_range[2 * i + 1] > win_range[2 * i];
+    RangeOut out;
+    RangeByLabel by_label;
+    if ((rc = out.reserve(h, tot)) || (tot && windowed && (rc = by_label.reserve(tot))))
+        return rc;
+    HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
+    if (tot && (rc = exact_range_f16_strips_pass(h, b, rs, true, nq, radius, map_shift, out.dist(h), out.lab(h), (size_t)tot)))
+        return rc;
+    if ((rc = by_label.run(h, d_lims, nq, tot, out)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    by_label.commit(h, out);
+    out.commit(h, tot);
+    *total = tot;
+    return IVFHNSW_OK;
+}
+
+int exact_range_f16_values_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, const uint32_t *query_ranges, float radius,
+                                uint64_t *lims, uint64_t *total, bool on_device)
+{
+    if (!query_ranges)
+        return exact_range_f16_impl(h, nq, queries, row_stride, radius, lims, total, on_device);
+    const char *who = on_device ? "exact_range_search_f16_values_dev" : "exact_range_search_f16_values";
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "exact_range_search_values", &b);
+    if (rc)
+        return rc;
+    if (std::isnan(radius))
+        return fail(IVFHNSW_ERR_INVALID, "%s: the radius is NaN", who);
+    ValueRows vr;
+    if ((rc = base_values_call(b, who, &vr)))
+        return rc;
+    if (nq == 0)
+        return exact_range_none(h, on_device ? nullptr : lims, on_device ? lims : nullptr, total);
+    const size_t d = b->base_d;
+    if (!queries || !lims || !total)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null queries, lims or total", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (nq > kMaxBatchAll)
+        return fail(IVFHNSW_ERR_INVALID, "%s is limited to %zu queries per call", who, kMaxBatchAll);
+    if (on_device && (((uintptr_t)queries & 3) || ((uintptr_t)lims & 7) || ((uintptr_t)query_ranges & 7)))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries must be 4-byte, lims 8-byte and query ranges 8-byte aligned", who);
+    if (on_device)
+        return exact_range_f16_values_dev(h, b, who, nq, queries, row_stride, query_ranges, vr, radius, lims, total);
+    if ((rc = h->ex_raw.ensure(nq * d * sizeof(float))) || (rc = h->xr_lims.ensure((nq + 1) * sizeof(uint64_t))) ||
+        (rc = h->bs_qslots.ensure(nq * 2 * sizeof(uint32_t))))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), queries, row_stride * sizeof(float), d * sizeof(float), nq,
+                             hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_qslots.p, query_ranges, nq * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = exact_range_f16_values_dev(h, b, who, nq, h->ex_raw.as<float>(), d, h->bs_qslots.as<uint32_t>(), vr, radius,
+                                         h->xr_lims.as<uint64_t>(), total)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lims, h->xr_lims.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return IVFHNSW_OK;
+}
+
 } // namespace
 
 int ivfhnsw_gpu_upload_base_f16(ivfhnsw_gpu *h, size_t n, size_t d, size_t first, size_t count, const float *rows,
@@ -674,4 +806,18 @@ int ivfhnsw_gpu_exact_range_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const
                                                 const uint16_t *d_query_tags, float radius, uint64_t *d_lims, uint64_t *total)
 {
     return exact_range_f16_tags_impl(h, nq, d_queries, row_stride, d_query_tags, radius, d_lims, total, true);
+}
+
+// ---- with an interval of base values per query; query_ranges == NULL is the plain call
+
+int ivfhnsw_gpu_exact_range_search_f16_values(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride,
+                                              const uint32_t *query_ranges, float radius, uint64_t *lims, uint64_t *total)
+{
+    return exact_range_f16_values_impl(h, nq, queries, row_stride, query_ranges, radius, lims, total, false);
+}
+
+int ivfhnsw_gpu_exact_range_search_f16_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride,
+                                                  const uint32_t *d_query_ranges, float radius, uint64_t *d_lims, uint64_t *total)
+{
+    return exact_range_f16_values_impl(h, nq, d_queries, row_stride, d_query_ranges, radius, d_lims, total, true);
 }

@@ -400,45 +400,17 @@ int exact_range_dev(ivfhnsw_gpu *h, size_t nq, const uint8_t *d_queries, size_t 
         windowed |= win_range[i + 1] > win_range[i];
     // results: in the buffers the handle holds when they are large enough, else in new ones swapped in when they are full
     RangeOut out;
-    DevBuf rd, rl, rwork; // rd, rl: the reordered pair; rwork: the keys and permutations of its two sorts
-    auto release = [&] {
-        rd.release();
-        rl.release();
-        rwork.release();
-    };
-    if ((rc = out.reserve(h, tot)))
+    RangeByLabel by_label; // the reordered pair and the workspace of its two sorts (capi_internal.h)
+    if ((rc = out.reserve(h, tot)) || (tot && windowed && (rc = by_label.reserve(tot))))
         return rc;
-    // ... and the reordered pair with its workspace, before the fill pass writes anything: a failed allocation leaves the
-    // results the handle holds as they were
-    if (tot && windowed && ((rc = rd.ensure(tot * sizeof(float))) || (rc = rl.ensure(tot * sizeof(int64_t))) ||
-                            (rc = rwork.ensure(range_by_label_work_words(tot) * sizeof(uint32_t))))) {
-        release();
+    HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
+    if (tot && (rc = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, out.dist(h), out.lab(h), (size_t)tot, rs)))
         return rc;
-    }
-    auto fill = [&]() -> int {
-        HIP_TRY(launch_range_lims(h->stream, h->xr_slices.as<uint32_t>(), (int)nq, nsplit, d_lims));
-        if (tot)
-            if (int e = exact_range_pass(h, b, cols, n, true, nq, thr, nsplit, map_shift, out.dist(h), out.lab(h), (size_t)tot, rs))
-                return e;
-        if (tot && windowed) {
-            StageScope sc(h, IVFHNSW_STAGE_PLAN); // accounted apart from the two passes: the order of the results
-            HIP_TRY(launch_range_by_label(h->stream, d_lims, nq, tot, out.dist(h), out.lab(h), rd.as<float>(), rl.as<int64_t>(),
-                                          rwork.as<uint32_t>()));
-        }
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        return IVFHNSW_OK;
-    };
-    if ((rc = fill())) {
-        release();
+    if ((rc = by_label.run(h, d_lims, nq, tot, out)))
         return rc;
-    }
-    if (rd.p) { // (the pair the fill pass wrote, where it is new, goes with `out`)
-        std::swap(h->xr_dist, rd);
-        std::swap(h->xr_lab, rl);
-        out.grow = false;
-    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    by_label.commit(h, out);
     out.commit(h, tot);
-    release();
     *total = tot;
     return IVFHNSW_OK;
 }

@@ -728,6 +728,39 @@ struct RangeOut {
         h->xr_total = tot;
     }
 };
+// Under a windowed strip the fill pass writes a query's results in (value, row) order: they are then
+// gathered in (query, label) order into a second pair of arrays that replaces the first.  reserve(): that pair and the
+// workspace of its two sorts, before the fill pass writes anything -- a failed allocation leaves the results the handle
+// holds as they were.  run(): behind the fill pass on the handle's stream, accounted as the plan stage, apart from the two
+// passes.  commit(): before out.commit(), when nothing can fail any more; the pair the fill pass wrote goes with `out`.
+// A call that never reserves (no windowed strip, or no result) does nothing in any of them.
+struct RangeByLabel {
+    ScopedBuf rd, rl, work;
+    int reserve(unsigned long long tot)
+    {
+        int rc;
+        if ((rc = rd.ensure(tot * sizeof(float))) || (rc = rl.ensure(tot * sizeof(int64_t))))
+            return rc;
+        return work.ensure(range_by_label_work_words(tot) * sizeof(uint32_t));
+    }
+    int run(ivfhnsw_gpu *h, const uint64_t *d_lims, size_t nq, unsigned long long tot, const RangeOut &out)
+    {
+        if (!rd.p)
+            return IVFHNSW_OK;
+        StageScope sc(h, IVFHNSW_STAGE_PLAN);
+        HIP_TRY(launch_range_by_label(h->stream, d_lims, nq, tot, out.dist(h), out.lab(h), rd.as<float>(), rl.as<int64_t>(),
+                                      work.as<uint32_t>()));
+        return IVFHNSW_OK;
+    }
+    void commit(ivfhnsw_gpu *h, RangeOut &out)
+    {
+        if (!rd.p)
+            return;
+        rd.install(h->xr_dist);
+        rl.install(h->xr_lab);
+        out.grow = false;
+    }
+};
 
 // ---- capi_upload.cpp
 int grouping_dedupe_reserve(ivfhnsw_gpu *h);

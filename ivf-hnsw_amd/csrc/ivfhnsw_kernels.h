@@ -445,6 +445,8 @@ hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const f
 // caller's query; map (nullable): [strips of the call][exact_range_f16_strips_map_words], keyed by sp.map_strip0 + plan
 // strip, each launch's splits at its own exact_range_map_words apart -- the Dense launch skips by the OR over a workgroup's
 // strips, the Indirect one per strip.
+// win (base values): sp and win are launch_value_strip_plan's; the Indirect strips go to the windowed per-wave
+// kernel, whose fill form writes a query's results in (value, row) order (launch_range_by_label puts them in label order).
 inline size_t exact_range_f16_strips_map_words(size_t nx, int ns_dense, int ns_ind, int map_shift)
 {
     return std::max((size_t)ns_dense * sweep_map_words(nx, ns_dense, map_shift), (size_t)ns_ind * sweep_map_words(nx, ns_ind, map_shift));
@@ -452,7 +454,8 @@ inline size_t exact_range_f16_strips_map_words(size_t nx, int ns_dense, int ns_i
 hipError_t launch_exact_range_f16_strips(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn,
                                          size_t bound, size_t q_off, size_t nx, int d, float radius, int ns_dense, int ns_ind,
                                          uint32_t *slices, unsigned long long *total, uint32_t *map, int map_shift, float *dist,
-                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms);
+                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms,
+                                         const StripWin *win = nullptr);
 // Base values (kernels_exact_filter.hip): a uint32 per row of the store, and the exact sweeps with an
 // interval per query.  launch_base_values_apply: vals[rows[i]] = v[i] for rows[i] < n; *conflict (zeroed here) != 0 when a
 // row was given two different values.  launch_base_values_index: all rows sorted stably by value (*sorted = ids_a or ids_b

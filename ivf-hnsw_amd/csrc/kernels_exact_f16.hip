@@ -1153,6 +1153,245 @@ __global__ __launch_bounds__(256) void exact_range_f16_rows_kernel(const _Float1
     }
 }
 
+// ---- the windowed strips of the range search (ivfhnsw_gpu_exact_range_search_f16_values) --------------------
+// A windowed strip of a value plan sweeps a span of the holder's rows in (value, row) order, every strip row counting only the
+// columns of ITS OWN window win[32 strip + row] = [wa, wb) of the span, and returns every pair below the radius.  The sweep
+// is a strip a wave, four strips a workgroup that share nothing: no barrier, no LDS, operand A resident, operand B straight
+// from the store through the span's row numbers in MFMA order with exact_f16_rows_kernel's prefetch depths; the arithmetic,
+// the fixed gate and the two forms are exact_range_f16_rows_kernel's, operation for operation, counters and cursors in
+// registers.  Two skips meet here, and next_tile composes them before anything of a tile is requested:
+//   the windows (exact_f16_windows_kernel's, in lanes m and m + 32): a tile no window meets is dead; next_live steps while
+//   tiles are live -- one ballot -- and jumps a gap with one wave minimum.  Both forms skip by them.
+//   the tile map: the count form records, in the map's layout, one bit per 2^map_shift tiles of the strip's own span by
+//   the strip's OWN hits; the fill form visits a tile iff it is live AND its bit is set.  The count form visits every live
+//   tile and writes a word when it leaves it, so the word of a live tile is always written -- and only such words are
+//   read: the fill form asks the windows first, looks up the live tile's bit, and from an unset bit goes to the word's
+//   next set bit (or the next word) and asks the windows again from there.  A word no live tile lies in is neither
+//   written nor read; the groups of a written word that hold no live tile are zero.
+// The cheap test counts an accumulator register only where its row's live bit is set (a tile inside every non-empty window
+// takes the unwindowed test); the exact test reads the row's window from its lane and rejects the columns of an edge tile
+// outside it.  A padding row and a row with an empty window hold the gate +inf for good and are no query (in_rows).
+// The fill form writes at the cursors in arrival order -- (value, row), not label order: the host gathers the results by
+// label afterwards (launch_range_by_label).  A wave without a strip, whose split of a short span is empty or holds no live
+// tile leaves at once in both forms: no slice (the memset left it zero), no map word, no total.
+template <int ND, bool FILL>
+__global__ __launch_bounds__(256) void exact_range_f16_windows_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                                      const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                                      float radius, size_t q_off, int slice_w,
+                                                                      uint32_t *__restrict__ slices, unsigned long long *__restrict__ total,
+                                                                      uint32_t *__restrict__ map, int map_shift, int map_words,
+                                                                      uint32_t map_stride, float *__restrict__ out_d,
+                                                                      long long *__restrict__ out_l, size_t out_cap, StripPlan sp,
+                                                                      const StripWin *__restrict__ win)
+{
+    constexpr int D = 16 * ND;
+    constexpr int NPRE = ND <= 8 ? ND : (ND + 1) / 2, NLATE = ND - NPRE;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const uint32_t strip = sp.hdr->lay.range[kSweepColsIndirect][0] + blockIdx.x * 4 + wave;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][1])
+        return;
+    const StripCols e = sp.strip_cols[strip];
+    const int split = blockIdx.y;
+    size_t cb, ce;
+    sweep_split_cut(e.nx, (int)gridDim.y, split, &cb, &ce);
+    if (cb >= ce)
+        return;
+    const uint32_t c_begin = (uint32_t)cb, c_end = (uint32_t)ce; // (columns of a span: below the rows of the store)
+    const uint32_t ntiles = (c_end - c_begin + 31u) >> 5;
+    const uint32_t *__restrict__ rows = e.data;
+    const int r0 = (int)(strip << 5); // (strip < the plan's bound: every row of it exists in Qh, qn, strip_rows and win)
+
+    // the window of row m, in the span's columns; bit m of `empty`: row m has none
+    const StripWin w = win[r0 + m];
+    const uint32_t wa = w.a, wb = w.b;
+    const uint32_t empty = (uint32_t)__ballot(wa >= wb);
+    // the first column of tile t; does the lane's window meet the tile that begins at c0 (an empty window meets none; the
+    // launch keeps columns below 2^32 - 64)
+    auto col0 = [&](uint32_t t) -> uint32_t { return c_begin + (t << 5); };
+    auto meets = [&](uint32_t c0) -> bool { return wa < c0 + 32u && wb > c0; };
+    // the first live tile at or after t (ntiles: none); wave-uniform, from the windows alone
+    auto next_live = [&](uint32_t t) -> uint32_t {
+        if (t >= ntiles)
+            return ntiles;
+        const uint32_t c0 = col0(t);
+        if (__ballot(meets(c0)))
+            return t;
+        // dead: the tile in which the nearest window that ends beyond c0 begins (it begins beyond the tile, or it would meet it)
+        uint32_t tt = wa < wb && wb > c0 ? ((wa > c0 ? wa : c0) - c_begin) >> 5 : ~0u;
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) // (lanes m and m + 32 hold the same window: each half finds the minimum)
+            tt = min(tt, (uint32_t)__shfl_xor((int)tt, o));
+        tt = __builtin_amdgcn_readfirstlane(tt);
+        return tt < ntiles ? tt : ntiles;
+    };
+    uint32_t *mw = map ? map + (size_t)(sp.map_strip0 + strip) * map_stride + (size_t)split * map_words : nullptr;
+    // the first tile at or after t that is visited: live, and in the fill form under a map with its bit set (ntiles: none)
+    auto next_tile = [&](uint32_t t) -> uint32_t {
+        t = next_live(t);
+        if (!FILL || !mw)
+            return t;
+        while (t < ntiles) {
+            const uint32_t g = t >> map_shift;
+            const uint32_t bw = __builtin_amdgcn_readfirstlane(mw[g >> 5]) >> (g & 31);
+            if (bw & 1u)
+                return t;
+            // the next set bit of the word, or the next word; then the windows again
+            t = next_live((bw ? g + (uint32_t)__ffs((int)bw) - 1u : (g | 31u) + 1u) << map_shift);
+        }
+        return ntiles;
+    };
+    uint32_t t = next_tile(0);
+    if (t >= ntiles)
+        return; // no window meets the split, or (fill) no live tile of it has a hit
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)(r0 + m) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    // the slice of strip row `row`: its query's (a padding row: query 0's, never touched)
+    auto slice_of = [&](int row) -> size_t { return (q_off + (size_t)max(sp.strip_rows[r0 + row], 0)) * slice_w + split; };
+    float qn_r[16], gate[16];
+    uint32_t cnt[16], in_rows = 0; // bit r: accumulator row r is a query with a window
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        const bool in = sp.strip_rows[r0 + row] >= 0 && !(empty >> row & 1u);
+        in_rows |= in ? 1u << r : 0u;
+        qn_r[r] = qn[r0 + row];
+        gate[r] = f16_gate(qn_r[r], in ? radius : -INFINITY);
+        cnt[r] = FILL && in ? slices[slice_of(row)] : 0u;
+    }
+
+    const unsigned char *xb = reinterpret_cast<const unsigned char *>(X) + 16 * kk;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the row number of the lane's column of tile t
+    auto ids = [&](uint32_t t) -> uint32_t { return col0(t) + m < c_end ? rows[col0(t) + m] : 0u; };
+    // pieces [first, first + N) of store row `row` into w; ok: the lane has a column
+    auto pieces = [&](uint32_t row, bool ok, int first, auto &w) {
+        constexpr int N = (int)(sizeof(w) / sizeof(w[0]));
+        const unsigned char *p = xb + (size_t)row * (2 * D) + 32 * first;
+#pragma unroll
+        for (int s = 0; s < N; s++)
+            w[s] = zero;
+        if (ok) {
+#pragma unroll
+            for (int s = 0; s < N; s++)
+                w[s] = *reinterpret_cast<const f16x8 *>(p + 32 * s);
+        }
+    };
+    uint32_t bits = 0;
+    // Tile t: `cur`, n_cur = its first NPRE pieces and its norms, id_cur its row numbers.  Starts the loads of tile tn (row
+    // numbers id_nxt) into nxt, n_nxt and of the row numbers of tile ta into id_ahead.
+    auto tile = [&](uint32_t t, const f16x8 (&cur)[NPRE], float n_cur, uint32_t id_cur, uint32_t tn, f16x8 (&nxt)[NPRE], float &n_nxt,
+                    uint32_t id_nxt, uint32_t ta, uint32_t &id_ahead) {
+        const uint32_t c0 = col0(t), col = c0 + m;
+        const bool col_ok = col < c_end;
+        f16x8 late[NLATE > 0 ? NLATE : 1];
+        if constexpr (NLATE > 0)
+            pieces(id_cur, col_ok, NPRE, late);
+        if (tn < ntiles) { // in flight behind this tile's MFMAs
+            const bool ok = col0(tn) + m < c_end;
+            pieces(id_nxt, ok, 0, nxt);
+            n_nxt = ok ? xn[id_nxt] : 0.f;
+        }
+        if (ta < ntiles)
+            id_ahead = ids(ta);
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < NPRE; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], cur[s], acc, 0, 0, 0);
+        if constexpr (NLATE > 0) {
+#pragma unroll
+            for (int s = 0; s < NLATE; s++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPRE + s], late[s], acc, 0, 0, 0);
+        }
+        // the cheap test: inside every non-empty window the unwindowed one, else a register counts where its row is live
+        const bool all = ((uint32_t)__ballot(wa <= c0 && wb >= c0 + 32u) | empty) == ~0u; // wave-uniform
+        bool any = false, hit = false;
+        if (all) {
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), n_cur) > gate[r];
+        } else {
+            const uint32_t lv = (uint32_t)__ballot(meets(c0)) >> (4 * kk); // bit (r & 3) + 8 (r >> 2): register r's row is live
+            uint32_t pb = 0;
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                pb |= __fsub_rn(__fmul_rn(2.0f, acc[r]), n_cur) > gate[r] ? 1u << ((r & 3) + 8 * (r >> 2)) : 0u;
+            any = (pb & lv) != 0u;
+        }
+        if (__ballot(any && col_ok)) { // wave-uniform
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float dist = __fsub_rn(__fadd_rn(qn_r[r], n_cur), __fmul_rn(2.0f, acc[r]));
+                const int row = mfma32_row(r, kk);
+                const uint32_t ra = (uint32_t)__shfl((int)wa, row), rb = (uint32_t)__shfl((int)wb, row); // (every lane: read from another)
+                const bool pass = col_ok && (in_rows >> r & 1u) && col >= ra && col < rb && dist < radius;
+                const unsigned long long mask = __ballot(pass);
+                const uint32_t half = kk ? (uint32_t)(mask >> 32) : (uint32_t)mask;
+                hit |= mask != 0;
+                if (FILL) {
+                    const size_t o = (size_t)cnt[r] + __popc(half & ((1u << m) - 1u));
+                    if (pass && o < out_cap) { // (o < out_cap always: the count form counted this very lane)
+                        out_d[o] = dist;
+                        out_l[o] = (long long)id_cur;
+                    }
+                }
+                cnt[r] += __popc(half);
+            }
+        }
+        if (!FILL && mw) {
+            const uint32_t g = t >> map_shift;
+            bits |= hit ? 1u << (g & 31) : 0u;
+            if (tn >= ntiles || (tn >> map_shift) >> 5 != g >> 5) { // the word is complete: no live tile of it is left
+                if (lane == 0)
+                    mw[g >> 5] = bits;
+                bits = 0;
+            }
+        }
+    };
+
+    uint32_t tn = next_tile(t + 1), ta;
+    f16x8 b0[NPRE], b1[NPRE];
+    float n0, n1 = 0.f;
+    uint32_t id0 = ids(t), id1 = 0, id_ahead = 0;
+    pieces(id0, col0(t) + m < c_end, 0, b0);
+    n0 = col0(t) + m < c_end ? xn[id0] : 0.f;
+    if (tn < ntiles)
+        id1 = ids(tn);
+    for (;;) {
+        ta = next_tile(tn + 1);
+        tile(t, b0, n0, id0, tn, b1, n1, id1, ta, id_ahead);
+        if (tn >= ntiles)
+            break;
+        t = tn, tn = ta, id0 = id_ahead;
+        ta = next_tile(tn + 1);
+        tile(t, b1, n1, id1, tn, b0, n0, id0, ta, id_ahead);
+        if (tn >= ntiles)
+            break;
+        t = tn, tn = ta, id1 = id_ahead;
+    }
+
+    if (!FILL) {
+        unsigned long long sum = 0;
+        if (m == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                if (in_rows >> r & 1u)
+                    slices[slice_of(mfma32_row(r, kk))] = cnt[r];
+                sum += cnt[r];
+            }
+        }
+        sum += __shfl_xor(sum, 32);
+        if (lane == 0 && sum)
+            atomicAdd(total, sum);
+    }
+}
+
 } // namespace
 
 size_t exact_f16_lds_bytes(int d, int k)
@@ -1294,14 +1533,18 @@ hipError_t launch_exact_range_f16(hipStream_t s, bool fill, const void *Qh, cons
 // staged kernel under ns_dense splits, the Indirect ones (forms bit kSweepColsIndirect) by the per-wave kernel under ns_ind;
 // both grids cover every strip the plan can have, and what lies beyond a form's range leaves at once.  slices: one table
 // max(ns_dense, ns_ind) splits wide, each form writes the splits it has.  map: exact_range_f16_strips_map_words words a strip.
+// win (base values): sp is a value plan, its Indirect strips are windowed -- each row with its own window
+// win[32 strip + row] of the strip's span -- and go to the windowed kernel, whose fill form writes in (value, row) order.
 hipError_t launch_exact_range_f16_strips(hipStream_t s, bool fill, const void *Qh, const float *qn, const void *X, const float *xn,
                                          size_t bound, size_t q_off, size_t nx, int d, float radius, int ns_dense, int ns_ind,
                                          uint32_t *slices, unsigned long long *total, uint32_t *map, int map_shift, float *dist,
-                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms)
+                                         int64_t *labels, size_t out_cap, const StripPlan &sp, unsigned forms, const StripWin *win)
 {
     if (d < 16 || d > 256 || (d & 15) || radius != radius || bound == 0 || bound > (0x7fffffffull >> 5) || nx == 0 || nx >= 0xffffffffull ||
         ns_dense < 1 || ns_dense > 64 || ns_ind < 1 || ns_ind > 64 || map_shift < 0 || map_shift > kExactRangeMaxShift || !sp.hdr ||
         !sp.strip_rows || !sp.strip_cols)
+        return hipErrorInvalidValue;
+    if (win && nx > 0xffffffffull - 64) // (the windowed kernel adds a tile's 32 columns to a column in 32 bits)
         return hipErrorInvalidValue;
     const int slice_w = std::max(ns_dense, ns_ind);
     const uint32_t stride = (uint32_t)exact_range_f16_strips_map_words(nx, ns_dense, ns_ind, map_shift);
@@ -1317,6 +1560,12 @@ hipError_t launch_exact_range_f16_strips(hipStream_t s, bool fill, const void *Q
                            total, map, map_shift, w_dense, dist, lab, out_cap, ds);
         if (hipError_t e = hipGetLastError(); e != hipSuccess || !(forms >> kSweepColsIndirect & 1u))
             return e;
+        if (win) {
+            const auto wins = fill ? exact_range_f16_windows_kernel<ND, true> : exact_range_f16_windows_kernel<ND, false>;
+            hipLaunchKernelGGL(wins, dim3(wgs, (unsigned)ns_ind), dim3(256), 0, s, q, qn, x, xn, radius, q_off, slice_w, slices, total, map,
+                               map_shift, w_ind, stride, dist, lab, out_cap, sp, win);
+            return hipGetLastError();
+        }
         const auto rows = fill ? exact_range_f16_rows_kernel<ND, true> : exact_range_f16_rows_kernel<ND, false>;
         hipLaunchKernelGGL(rows, dim3(wgs, (unsigned)ns_ind), dim3(256), 0, s, q, qn, x, xn, radius, q_off, slice_w, slices, total, map,
                            map_shift, w_ind, stride, dist, lab, out_cap, sp);

@@ -54,7 +54,11 @@
      With --f16 --values base values on the float16 store (ivfhnsw_gpu_exact_search_f16_values_dev) at
      d = 128: the three workloads of 7., k = 1 and 100, ALTERNATING with exact_search_values_dev on the uint8 store of the
      same rows (the two must agree); and the all-FULL batch alternating with the plain exact_search_f16_dev, with the plan
-     stage (plan and gather) from the stage profiler.
+     stage (plan and gather) from the stage profiler.  Per workload also the range form under the intervals
+     (ivfhnsw_gpu_exact_range_search_f16_values_dev) at the radius of the 30th neighbour inside the interval,
+     alternating with exact_range_search_values_dev on the uint8 store (equal lims, labels and distances required), the
+     k = 1 search under the intervals, the call without the tile map and under the neighbouring split counts; the all-FULL
+     batch alternating with the plain exact_range_search_f16_dev.
 Each figure: warm-up runs, then the median of several repetitions, each timed from the call to the end of the stream's
 work.  Reported: seconds, 2 nq n d / t in TOP/s, store bytes per second per pass (n d / t) and, with one pass per query
 tile, the bytes per second all tiles stream together.
@@ -645,8 +649,65 @@ def main():
                      "plan_and_gather_ms": round(statistics.median(plan_ms[args.warmup:]), 4)}
                 result["rows"].append(r)
                 print(json.dumps(r), flush=True)
+            # (od: the k = 100 distances under the intervals) a radius that gives some tens of hits per query
+            f16_values_range_leg(n, dd, g8, qf, qb, qr, wname, float(od[:, 29][od[:, 29] < 3e38].median()))
         g.clear_base_values()
         g8.clear_base_values()
+
+    def f16_values_range_leg(n, dd, g8, qf, qb, qr, wname, radius):
+        """The range form under base values (exact_range_search_f16_values_dev) on one workload of
+        f16_values_legs: beside exact_range_search_values_dev of the uint8 store (equal lims, labels and distances required),
+        the k = 1 search under the same intervals, the call without the tile map and under the neighbours of the windowed
+        launch's split count; plan (with the reorder), count and fill by the stage profiler.  "all full": beside the plain
+        exact_range_search_f16_dev."""
+        od, ol = torch.empty((nq, 1), dtype=torch.float32, device=dev), torch.empty((nq, 1), dtype=torch.int64, device=dev)
+        lims8, passes = torch.zeros_like(lims), []
+        name = "exact_range_search_f16_values_dev"
+
+        def valued():
+            g.set_profiling(True)
+            g.reset_stage_ms()
+            valued.total = g.exact_range_search_f16_values_dev(nq, qf, dd, qr, radius, lims)
+            ms = g.stage_ms()
+            passes.append((ms["plan"][0], ms["scan"][0], ms["select"][0]))
+            g.set_profiling(False)
+
+        def with_option(key, value):
+            g.set_option(key, value)
+            g.exact_range_search_f16_values_dev(nq, qf, dd, qr, radius, lims)
+            g.set_option(key, -1)
+
+        if wname == "all full":
+            calls = [(name, valued), ("exact_range_search_f16_dev", lambda: g.exact_range_search_f16_dev(nq, qf, dd, radius, lims8))]
+        else:
+            # the rule of the windowed launch (capi_base_f16.cpp exact_range_f16_window_splits_for), restated
+            blocks = -(-(min(nq, 16384) // 32 + 2) * 32 // 128)
+            rule = max(1, min(64, 512 // blocks, -(-n // 4096)))
+            calls = [(name, valued),
+                     ("exact_range_search_values_dev (uint8 store)", lambda: g8.exact_range_search_values_dev(nq, qb, dd, qr, radius, lims8)),
+                     ("exact_search_f16_values_dev k=1", lambda: g.exact_search_f16_values_dev(nq, qf, dd, 1, qr, od, ol)),
+                     (name + ", no tile map", lambda: with_option("exact_range_map", 0))]
+            calls += [(name + ", %d splits" % s, lambda s=s: with_option("exact_splits", s)) for s in (rule - 1, rule + 1) if 1 <= s <= 64]
+        ts = alternate(calls, "range values '%s'" % wname)
+        other = g if wname == "all full" else g8
+        calls[1][1]()
+        want = other.exact_range_results(0, int(lims8[-1]))
+        valued()
+        got = g.exact_range_results(0, valued.total)
+        assert torch.equal(lims, lims8) and (got[1] == want[1]).all() and (got[0] == want[0]).all(), \
+            "the float16 range search under values and %s disagree" % calls[1][0]
+        base_t = statistics.median(ts[name])
+        for what, _ in calls:
+            t = statistics.median(ts[what])
+            r = {"what": what, "rows": n, "d": dd, "nq": nq, "workload": wname, "radius_value": radius, "results": valued.total,
+                 "results_per_query": round(valued.total / nq, 2), "seconds": round(t, 5), "reps": [round(x, 5) for x in ts[what]],
+                 "over_f16_range_values": round(t / base_t, 3)}
+            if what == name:
+                mine = passes[args.warmup:][:args.reps]
+                for i, key in enumerate(("plan_gather_reorder_ms", "count_pass_ms", "fill_pass_ms")):
+                    r[key] = round(statistics.median(x[i] for x in mine), 4)
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
 
     def f16_tags_range_leg(n, dd, g8, qf, qb, qt, ntags, radius, alternate, with_splits):
         """The range form under base tags (exact_range_search_f16_tags_dev) at the radius of the tagged 10th

@@ -30,12 +30,13 @@ takes --tags with --query-tags (ivfhnsw_gpu_exact_search_f16_tags, 3.29) or --va
 (ivfhnsw_gpu_exact_search_f16_values, 3.31), nothing else.  With
 --radius the .npz comes from ivfhnsw_gpu_exact_range_search_f16 (3.28): the rows whose float32 distance between the rounded
 vectors, the value the k-search returns, is < R -- and with --tags and --query-tags from
-ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag; --values is refused there.
+ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag; with --values and --query-ranges
+from ivfhnsw_gpu_exact_range_search_f16_values (3.32): only the rows whose value lies in the query's interval.
 
 usage: python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs [--rows N] [--allow F | --deny F]
        python tools/ground_truth.py --base x.fvecs --queries q.fvecs --k 100 --out gt.ivecs [--rows N] [--tags t.npy --query-tags qt.npy | --values v.npy --query-ranges qr.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --radius R --out gt.npz [--rows N] [--allow F | --deny F]
-       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N] [--tags t.npy --query-tags qt.npy]
+       python tools/ground_truth.py --base x.fvecs --queries q.fvecs --radius R --out gt.npz [--rows N] [--tags t.npy --query-tags qt.npy | --values v.npy --query-ranges qr.npy]
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --tags t.npy --query-tags qt.npy
        python tools/ground_truth.py --base x.bvecs --queries q.bvecs --k 100 --out gt.ivecs --values v.npy --query-ranges qr.npy"""
 import argparse
@@ -253,10 +254,11 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
     """(lims, distances, labels) of every base row within the radius of every query, ascending label per query; with
     `labels` only of the rows whose number is in them (deny: is not), info (a dict) then receives rows_passing.  An .fvecs
     base goes to the float16 store (ivfhnsw_gpu_exact_range_search_f16), which takes `tags` with `query_tags`
-    (ivfhnsw_gpu_exact_range_search_f16_tags, 3.30) and none of the other filters."""
+    (ivfhnsw_gpu_exact_range_search_f16_tags, 3.30) or `values` with `query_ranges` (ivfhnsw_gpu_exact_range_search_f16_values,
+    3.32) and no label filter."""
     if base_path.endswith(".fvecs"):
-        if labels is not None or values is not None:
-            raise ValueError("an .fvecs base goes to the float16 store, whose range search takes tags but no filter or values")
+        if labels is not None:
+            raise ValueError("an .fvecs base goes to the float16 store, whose range search takes tags or values but no filter")
         img, dq = read_fvecs_image(query_path)
         g = pkg.GpuIndex(device)
         try:
@@ -268,6 +270,11 @@ def ground_truth_range(pkg, base_path, query_path, radius, rows=None, device=0, 
                 if info is not None:
                     info["rows_passing"] = g.base_tags_info()[0]  # the tagged rows
                 return g.exact_range_search_f16_tags(img[:, 1:], radius, query_tags)
+            if values is not None:
+                install_values(g, n, img.shape[0], values, query_ranges)
+                if info is not None:
+                    info["rows_passing"] = g.base_values_info()[0]  # the rows that hold a value
+                return g.exact_range_search_f16_values(img[:, 1:], radius, query_ranges)
             return g.exact_range_search_f16(img[:, 1:], radius)
         finally:
             g.close()
