@@ -911,6 +911,22 @@ int ivfhnsw_gpu_exact_search_f16_values(ivfhnsw_gpu *h, size_t nq, const float *
 int ivfhnsw_gpu_exact_search_f16_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
                                             const uint32_t *d_query_ranges, float *d_distances, int64_t *d_labels);
 
+/* ... with a base tag AND an interval of base values per query: the truth of search_tags_values for a float
+ * corpus.  query_tags [nq] and query_ranges [2 nq] as the two calls above take them; a row passes for a query iff
+ * (tag == IVFHNSW_TAG_NONE || the row's base tag == tag) && lo <= the row's base value <= hi, a row without a value holding
+ * 0xffffffff and a row without a tag matching no named tag.  The query is answered as exact_search_f16 would answer it on a
+ * store holding only its passing rows: every distance bit for bit the value exact_search_f16 writes for the pair, the labels
+ * the original row numbers, equal distances in ascending label, -1 / FLT_MAX where fewer than k rows pass (lo > hi, a tag no
+ * row carries).  query_ranges == NULL is exact_search_f16_tags itself, query_tags == NULL exact_search_f16_values, both NULL
+ * exact_search_f16.  Limits, errors, chunks, views and "exact_splits" as those calls; IVFHNSW_ERR_STATE on a uint8 store,
+ * which has no such call.  _dev: d_query_tags 2-byte and d_query_ranges 4-byte aligned in device memory. */
+int ivfhnsw_gpu_exact_search_f16_tags_values(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                             const uint16_t *query_tags, const uint32_t *query_ranges, float *distances,
+                                             int64_t *labels);
+int ivfhnsw_gpu_exact_search_f16_tags_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                                 const uint16_t *d_query_tags, const uint32_t *d_query_ranges, float *d_distances,
+                                                 int64_t *d_labels);
+
 /* ... and the range form under base tags: the truth of range_search_tags for a float corpus, with the semantics
  * of ivfhnsw_gpu_exact_range_search_tags.  A query with tag t gets every row whose base tag is t and whose distance -- the
  * value exact_search_f16_tags and exact_range_search_f16 (below) write for the pair, bit for bit -- is < radius (strict), in

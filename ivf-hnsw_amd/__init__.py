@@ -83,6 +83,7 @@ ABI_SYMBOLS = (
     "ivfhnsw_gpu_exact_range_search_f16_tags", "ivfhnsw_gpu_exact_range_search_f16_tags_dev",
     "ivfhnsw_gpu_exact_search_f16_values", "ivfhnsw_gpu_exact_search_f16_values_dev",
     "ivfhnsw_gpu_exact_range_search_f16_values", "ivfhnsw_gpu_exact_range_search_f16_values_dev",
+    "ivfhnsw_gpu_exact_search_f16_tags_values", "ivfhnsw_gpu_exact_search_f16_tags_values_dev",
 )
 
 
@@ -298,6 +299,9 @@ def lib():
         L.ivfhnsw_gpu_exact_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_search_f16_values.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
         L.ivfhnsw_gpu_exact_search_f16_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_slots.argtypes
+        L.ivfhnsw_gpu_exact_search_f16_tags_values.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ivfhnsw_gpu_exact_search_f16_tags_values_dev.argtypes = L.ivfhnsw_gpu_exact_search_f16_tags_values.argtypes
         L.ivfhnsw_gpu_exact_range_search_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_values_dev.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
         L.ivfhnsw_gpu_exact_range_search_f16_values.argtypes = L.ivfhnsw_gpu_exact_range_search_slots.argtypes
@@ -1418,6 +1422,31 @@ class GpuIndex:
         the handle's stream."""
         _check(lib().ivfhnsw_gpu_exact_search_f16_values_dev(self._h, nq, _devptr(d_queries), row_stride, k,
                                                              _devptr(d_query_ranges), _devptr(d_distances), _devptr(d_labels)))
+
+    def exact_search_f16_tags_values(self, queries_f32, k, query_tags, query_ranges):
+        """exact_search_f16() with a base tag AND a value interval per query (ivfhnsw_gpu_exact_search_f16_tags_values): a
+        row passes for a query iff it passes exact_search_f16_tags()'s rule for query_tags [nq] uint16 and
+        exact_search_f16_values()'s for query_ranges [nq, 2] uint32.  query_ranges None is exact_search_f16_tags() itself,
+        query_tags None exact_search_f16_values()."""
+        a = np.asarray(queries_f32)
+        assert a.dtype == np.float32 and a.ndim == 2, "queries_f32: a 2-D float32 array [nq, d]"
+        nq, d = a.shape
+        assert nq == 0 or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and (nq == 1 or a.strides[0] >= 4 * d)), \
+            "queries must be contiguous inside a row and a fixed stride apart"
+        stride = a.strides[0] // 4 if nq > 1 else d
+        qt = None if query_tags is None else _np(query_tags, np.uint16).reshape(nq)
+        qr = None if query_ranges is None else _np(query_ranges, np.uint32).reshape(nq, 2)
+        dist = np.empty((nq, k), np.float32)
+        lab = np.empty((nq, k), np.int64)
+        _check(lib().ivfhnsw_gpu_exact_search_f16_tags_values(self._h, nq, C.c_void_p(a.ctypes.data) if nq else None, stride, k,
+                                                              _ptr(qt), _ptr(qr), _ptr(dist), _ptr(lab)))
+        return dist, lab
+
+    def exact_search_f16_tags_values_dev(self, nq, d_queries, row_stride, k, d_query_tags, d_query_ranges, d_distances, d_labels):
+        """The same on device buffers (d_query_tags: [nq] uint16, d_query_ranges: [nq, 2] uint32 in device memory, 4-byte
+        aligned), asynchronous on the handle's stream."""
+        _check(lib().ivfhnsw_gpu_exact_search_f16_tags_values_dev(self._h, nq, _devptr(d_queries), row_stride, k, _devptr(d_query_tags),
+                                                                  _devptr(d_query_ranges), _devptr(d_distances), _devptr(d_labels)))
 
     def exact_range_search_f16(self, queries_f32, radius):
         """Every row of the float16 base store whose distance -- the value exact_search_f16 returns for the pair -- is

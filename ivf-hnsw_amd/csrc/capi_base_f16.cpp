@@ -374,6 +374,132 @@ int exact_f16_values_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_
     return IVFHNSW_OK;
 }
 
+// Queries per pass of a _tags_values k-search: as sweep_tag_chunk, the partial tables over the padded rows of BOTH plans.
+// At 128 it always fits (64 * (132 + 6) * 32 * 100 * 8 = 226 MB).
+size_t exact_f16_tags_values_chunk(int nsplit, size_t k, size_t tags_in_use)
+{
+    const size_t per_strip = (size_t)nsplit * 32 * k * sizeof(uint64_t);
+    size_t chunk = kExactChunk;
+    while (chunk > 128 && per_strip * (sweep_tag_strip_bound(chunk, tags_in_use) + sweep_value_strip_bound(chunk)) > kExactPartBytes)
+        chunk -= 128;
+    return chunk;
+}
+
+// With a base tag AND an interval of base values per query.  Per chunk the queries are parted on the
+// device by tag == NONE, without moving them: one small kernel writes the value plan's intervals -- a tagged query's is
+// empty, so it gets no strip there -- and the tag plan's minor keys, a tagged query's lo.  The untagged side is the _values
+// call's: the value plan, its Dense strips by the staged kernel and its windowed ones by exact_f16_windows_kernel.  The
+// tagged side is the tag plan, a tag's queries ordered by lo, whose Indirect strips go to exact_f16_gated_kernel (its Dense
+// strips, the untagged queries, are swept by nobody).  Each sweep under its own split count; one merge scatters every
+// strip row of both plans to its query's place.  The host form knows the chunk's tags and plans and launches only the sides
+// that have queries; the device form launches both -- the workgroups of a side without strips leave at once.
+int exact_f16_tags_values_impl(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k, const uint16_t *query_tags,
+                               const uint32_t *query_ranges, float *distances, int64_t *labels, bool on_device)
+{
+    if (!query_ranges)
+        return exact_f16_tags_impl(h, nq, queries, row_stride, k, query_tags, distances, labels, on_device);
+    if (!query_tags)
+        return exact_f16_values_impl(h, nq, queries, row_stride, k, query_ranges, distances, labels, on_device);
+    const char *who = on_device ? "exact_search_f16_tags_values_dev" : "exact_search_f16_tags_values";
+    const ivfhnsw_gpu *b;
+    int rc = exact_f16_guard(h, who, "no call", &b); // (the uint8 store has no counterpart)
+    if (rc)
+        return rc;
+    if (k < 1 || k > 100)
+        return fail(IVFHNSW_ERR_INVALID, "%s needs 1 <= k <= 100 (k %zu)", who, k);
+    if (nq == 0)
+        return IVFHNSW_OK;
+    const size_t d = b->base_d, n = b->base_n;
+    if (!queries || !distances || !labels)
+        return fail(IVFHNSW_ERR_INVALID, "%s: null query/result buffer", who);
+    if (row_stride < d)
+        return fail(IVFHNSW_ERR_INVALID, "row_stride %zu < d %zu", row_stride, d);
+    if (on_device && (((uintptr_t)queries & 3) || ((uintptr_t)query_tags & 1) || ((uintptr_t)query_ranges & 3)))
+        return fail(IVFHNSW_ERR_INVALID, "%s: queries and query ranges must be 4-byte and query tags 2-byte aligned", who);
+    TagRows tr;
+    ValueRows vr;
+    size_t in_use = 0;
+    if ((rc = base_tags_call(b, who, &tr, &in_use)) || (rc = base_values_call(b, who, &vr)))
+        return rc;
+
+    int ns_dense, ns_win, ns_tag; // (both rules cut the Dense strips alike)
+    exact_f16_value_splits(b, std::min(nq, kExactChunk), (int)k, &ns_dense, &ns_win);
+    exact_f16_tag_splits(b, std::min(nq, kExactChunk), (int)k, &ns_dense, &ns_tag);
+    if (h->opt_exact_splits > 0)
+        ns_dense = ns_win = ns_tag = h->opt_exact_splits;
+    const int nsplit = std::max(ns_dense, std::max(ns_win, ns_tag));
+    const size_t chunk = std::min(nq, exact_f16_tags_values_chunk(nsplit, k, in_use));
+    const size_t bound_v = sweep_value_strip_bound(chunk), bound_t = sweep_tag_strip_bound(chunk, in_use);
+    const size_t rows_v = bound_v * 32, rows = (bound_v + bound_t) * 32;
+    const size_t plan_v = (sweep_value_plan_bytes(bound_v) + 15) & ~(size_t)15, vwork = value_plan_work_words(chunk);
+    // behind the value plan's work words: the tag plan's minor keys [chunk] and the value plan's intervals [2 chunk]
+    if ((rc = h->ex_q.ensure(rows * d * 2)) || (rc = h->ex_qn.ensure(rows * sizeof(float))) ||
+        (rc = h->ex_part.ensure((size_t)nsplit * rows * k * sizeof(uint64_t))) ||
+        (rc = h->bs_plan.ensure(plan_v + sweep_tag_plan_bytes(bound_t))) ||
+        (rc = h->bt_work.ensure(tag_plan_work_words(chunk) * sizeof(uint32_t))) ||
+        (rc = h->bv_work.ensure((vwork + 3 * chunk) * sizeof(uint32_t))))
+        return rc;
+    // the host form stages a chunk's intervals and, behind them, its tags
+    if (!on_device && ((rc = h->ex_raw.ensure(chunk * d * sizeof(float))) ||
+                       (rc = h->bs_qslots.ensure(chunk * (2 * sizeof(uint32_t) + sizeof(uint16_t)))) ||
+                       (rc = h->ex_dist.ensure(chunk * k * sizeof(float))) || (rc = h->ex_lab.ensure(chunk * k * sizeof(int64_t)))))
+        return rc;
+    uint32_t *lo_keys = h->bv_work.as<uint32_t>() + vwork, *vranges = lo_keys + chunk;
+    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
+        const size_t m = std::min(chunk, nq - q0);
+        const float *src = queries + q0 * row_stride;
+        const uint16_t *dt = query_tags + q0;
+        const uint32_t *dr = query_ranges + 2 * q0;
+        size_t src_stride = row_stride;
+        bool side_v = true, side_t = b->bt_tagged; // (a holder without tagged rows has no row list to sweep)
+        if (!on_device) {
+            side_v = std::any_of(dt, dt + m, [](uint16_t t) { return t == kTagNone; });
+            side_t = side_t && std::any_of(dt, dt + m, [](uint16_t t) { return t != kTagNone; });
+            uint32_t *sr = h->bs_qslots.as<uint32_t>();
+            uint16_t *st = reinterpret_cast<uint16_t *>(sr + 2 * chunk);
+            HIP_TRY(hipMemcpy2DAsync(h->ex_raw.p, d * sizeof(float), src, row_stride * sizeof(float), d * sizeof(float), m,
+                                     hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(sr, dr, m * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(st, dt, m * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+            src = h->ex_raw.as<float>();
+            src_stride = d;
+            dr = sr;
+            dt = st;
+        }
+        float *od = on_device ? distances + q0 * k : h->ex_dist.as<float>();
+        int64_t *ol = on_device ? labels + q0 * k : h->ex_lab.as<int64_t>();
+        StripPlan spv, spt;
+        const StripWin *win = nullptr;
+        unsigned char *qh = h->ex_q.as<unsigned char>();
+        {
+            StageScope sc(h, IVFHNSW_STAGE_PLAN); // the plans and the gathers, accounted apart from the sweeps
+            HIP_TRY(launch_f16_tags_values_split(h->stream, dt, dr, m, lo_keys, vranges));
+            // the queries as the store holds its rows, in each plan's strip order; a padding row repeats the chunk's first query
+            if (side_v) {
+                HIP_TRY(launch_value_strip_plan(h->stream, vranges, m, vr, h->bs_plan.p, bound_v, h->bv_work.as<uint32_t>(), &spv, &win));
+                HIP_TRY(launch_f16_store_rows(h->stream, src, src_stride, qh, h->ex_qn.as<float>(), rows_v, (int)d, spv.strip_rows));
+            }
+            if (side_t) {
+                HIP_TRY(launch_tag_strip_plan(h->stream, dt, m, tr, h->bs_plan.as<unsigned char>() + plan_v, bound_t, h->bt_work.as<uint32_t>(),
+                                              &spt, lo_keys));
+                HIP_TRY(launch_f16_store_rows(h->stream, src, src_stride, qh + rows_v * d * 2, h->ex_qn.as<float>() + rows_v, bound_t * 32,
+                                              (int)d, spt.strip_rows));
+            }
+        }
+        HIP_TRY(launch_exact_search_f16_tags_values(h->stream, qh, h->ex_qn.as<float>(), b->base_rows.p, b->base_norms.as<float>(), m, bound_v,
+                                                    bound_t, n, (int)d, (int)k, ns_dense, ns_win, ns_tag, h->ex_part.as<unsigned long long>(), od,
+                                                    ol, side_v ? &spv : nullptr, win, vr.vals != nullptr, side_t ? &spt : nullptr, dt, dr,
+                                                    vr.vals));
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(distances + q0 * k, od, m * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(labels + q0 * k, ol, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+            // the next chunk reuses the pageable source and the staging buffers
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+    }
+    return IVFHNSW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Exact range search of the half store: the sequence of the uint8 call (capi_exact.cpp, 3.17) -- count ->
 // prefix -> (one synchronisation: the host sizes the results) -> fill -- around exact_range_f16_kernel.
@@ -766,6 +892,21 @@ int ivfhnsw_gpu_exact_search_f16_tags_dev(ivfhnsw_gpu *h, size_t nq, const float
                                           const uint16_t *d_query_tags, float *d_distances, int64_t *d_labels)
 {
     return exact_f16_tags_impl(h, nq, d_queries, row_stride, k, d_query_tags, d_distances, d_labels, true);
+}
+
+// ---- with a base tag and an interval of base values per query; a NULL array leaves the other's call
+
+int ivfhnsw_gpu_exact_search_f16_tags_values(ivfhnsw_gpu *h, size_t nq, const float *queries, size_t row_stride, size_t k,
+                                             const uint16_t *query_tags, const uint32_t *query_ranges, float *distances, int64_t *labels)
+{
+    return exact_f16_tags_values_impl(h, nq, queries, row_stride, k, query_tags, query_ranges, distances, labels, false);
+}
+
+int ivfhnsw_gpu_exact_search_f16_tags_values_dev(ivfhnsw_gpu *h, size_t nq, const float *d_queries, size_t row_stride, size_t k,
+                                                 const uint16_t *d_query_tags, const uint32_t *d_query_ranges, float *d_distances,
+                                                 int64_t *d_labels)
+{
+    return exact_f16_tags_values_impl(h, nq, d_queries, row_stride, k, d_query_tags, d_query_ranges, d_distances, d_labels, true);
 }
 
 // ---- with an interval of base values per query; query_ranges == NULL is the plain call

@@ -423,8 +423,9 @@ hipError_t launch_base_tags_apply(hipStream_t s, const uint32_t *rows, const uin
 hipError_t launch_base_tags_index(hipStream_t s, const uint16_t *tags, uint64_t n, uint32_t *keys, uint32_t *ids_a, uint32_t *ids_b,
                                   uint32_t *hist, uint32_t *off, uint32_t *stats, uint32_t **sorted);
 size_t tag_plan_work_words(size_t m);
+// minor_keys [m] (null: none): the queries of a bucket in the order of their minor key, then of position.
 hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
-                                 uint32_t *work, StripPlan *sp);
+                                 uint32_t *work, StripPlan *sp, const uint32_t *minor_keys = nullptr);
 // launch_exact_pad: dists / labels [total] = FLT_MAX / -1, what a query without a strip keeps.
 hipError_t launch_exact_pad(hipStream_t s, float *dists, int64_t *labels, size_t total);
 // Base tags on the float16 store (kernels_exact_f16.hip).  launch_f16_store_rows: launch_f16_store whose row
@@ -440,6 +441,21 @@ hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const f
                                           size_t bound, size_t nx, int d, int k, int ns_dense, int ns_ind, unsigned long long *part,
                                           float *dists, int64_t *labels, const StripPlan &sp, unsigned forms,
                                           const StripWin *win = nullptr);
+// A tag AND an interval of base values per query on the float16 store (kernels_exact_f16.hip).
+// launch_f16_tags_values_split: from a chunk's tags and intervals lo_keys [m] -- launch_tag_strip_plan's minor keys, a tagged
+// query's lo -- and vranges [2 m] -- launch_value_strip_plan's intervals, empty for a tagged query.
+// launch_exact_search_f16_tags_values: the sweeps over the queries Qh, qn [(bound_v + bound_t) * 32] gathered by the value
+// plan spv (the untagged queries; win its windows, `windowed`: the holder has values) and behind them by the tag plan spt,
+// whose Indirect strips go to the gated per-wave kernel with the chunk's d_tags, d_ranges and the holder's values vals
+// (null: none); a null plan is not swept.  part: [max of the splits][(bound_v + bound_t) * 32][k]; one merge, results at
+// the queries' own places.
+hipError_t launch_f16_tags_values_split(hipStream_t s, const uint16_t *d_tags, const uint32_t *d_ranges, size_t m, uint32_t *lo_keys,
+                                        uint32_t *vranges);
+hipError_t launch_exact_search_f16_tags_values(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                               size_t bound_v, size_t bound_t, size_t nx, int d, int k, int ns_dense, int ns_win, int ns_tag,
+                                               unsigned long long *part, float *dists, int64_t *labels, const StripPlan *spv,
+                                               const StripWin *win, bool windowed, const StripPlan *spt, const uint16_t *d_tags,
+                                               const uint32_t *d_ranges, const uint32_t *vals);
 // ... and the range search under them: launch_exact_range_f16 over a tag plan of the chunk that begins at
 // query q_off of the call, one form per call as there.  slices: [queries of the call][max(ns_dense, ns_ind)], keyed by the
 // caller's query; map (nullable): [strips of the call][exact_range_f16_strips_map_words], keyed by sp.map_strip0 + plan

@@ -699,17 +699,301 @@ __global__ __launch_bounds__(64 * WAVES) void exact_f16_windows_kernel(const _Fl
     rows_write_out<CAP>(buf, cnt, k, lane, 32, out_keys, (size_t)blockIdx.y * nrows + r0);
 }
 
+// part_rows: the rows of a split of `part` where the table holds more than this plan's; 0 = bound * 32
 template <int ND, int CAP, int WAVES>
 hipError_t launch_exact_f16_windows_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn,
-                                      size_t bound, int k, int nsplit, unsigned long long *part, const StripPlan &sp, const StripWin *win)
+                                      size_t bound, int k, int nsplit, unsigned long long *part, const StripPlan &sp, const StripWin *win,
+                                      size_t part_rows = 0)
 {
     const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(float));
     constexpr auto kern = exact_f16_windows_kernel<ND, CAP, WAVES>;
     if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)((bound + WAVES - 1) / WAVES), (unsigned)nsplit), dim3(64 * WAVES), shm, s, Qh, qn, X, xn,
-                       (int)(bound * 32), k, part, sp, win);
+                       (int)(part_rows ? part_rows : bound * 32), k, part, sp, win);
     return hipGetLastError();
+}
+
+// ---- the gated strips (ivfhnsw_gpu_exact_search_f16_tags_values) -----------------------------------------
+// A tagged query with an interval of base values sweeps its tag's row list, as exact_f16_rows_kernel does, and counts only the
+// columns whose VALUE lies in its interval.  The sweep is that kernel's -- a strip a wave, no barrier, no LDS tile, operand A
+// resident, operand B straight from the store through the list in MFMA order, the NPRE / NLATE piece split -- with four
+// things of its own.
+//   Intervals in lanes, envelope in scalars.  Lanes m and m + 32 hold strip row m's interval as value_math.h's (lo, span,
+//   live).  Once per strip two wave reductions give the envelope [LO, HI] over the rows that are queries and have lo <= hi;
+//   a padding row and a row with lo > hi hold the threshold -inf and so the gate +inf, for good.  The tag plan orders a
+//   tag's queries by lo (launch_tag_strip_plan's minor keys), so that the envelope of a strip is tight.
+//   A value stage.  Whether a tile is LIVE -- some column's value lies in the envelope -- depends on loaded data: 4 bytes of
+//   row number and 4 bytes of value per column.  The pipeline is three deep: behind the MFMAs of tile t are in flight the
+//   row numbers of tile t + 3, the values of tile t + 2 (through the row numbers requested a tile ago) and, decided by one
+//   ballot over the values requested a tile ago, the norms and the first NPRE pieces of tile t + 1 -- only if it is live.
+//   A dead tile costs its row numbers and values: no norm, no piece, no MFMA.  There is nothing to jump over, as the
+//   windows kernel does: the sweep steps tile by tile over 8 bytes per column.  In a live tile a column outside the
+//   envelope is not read either: its pieces are zeros and it never passes, so under shuffled values the sweep moves the
+//   rows of the envelope only.  The registers in flight alternate between two sets with the loop unrolled by two, so that
+//   none is copied before it has arrived.
+//   The two tests.  The cheap test is the rows kernel's over the columns inside the envelope.  The exact test, behind the
+//   wave-uniform ballot, judges every (row, column) by tag_value_math.h's rule with the row's interval read from its lane.
+//   The list ascends in row number, so `<` alone keeps ties on the lower label.
+// vals null: the holder has no values, every row reads as 0xffffffff (value_math.h's keep).  A split of a list without a
+// live tile still writes its (empty) rows: the merge reads every split that has columns.
+template <int CAP>
+__device__ __forceinline__ void f16_select_gated(const f32x16 &acc, float xn_col, bool col_in, uint32_t label, uint32_t wv, uint32_t wt,
+                                                 uint32_t keep, uint32_t lo, uint32_t span, uint32_t live, const float (&qn_r)[16],
+                                                 float (&gate)[16], unsigned long long *buf, uint32_t *cnt, float *thr_s, int k, int lane)
+{
+    const int m = lane & 31, kk = lane >> 5;
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        any |= __fsub_rn(__fmul_rn(2.0f, acc[r]), xn_col) > gate[r];
+    if (__ballot(any && col_in)) { // wave-uniform: rare once the thresholds have settled
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float dist = __fsub_rn(__fadd_rn(qn_r[r], xn_col), __fmul_rn(2.0f, acc[r]));
+            const int row = mfma32_row(r, kk);
+            // (every lane: read from another.)  The column carries the list's tag wt, which is the tag of every query of the strip.
+            const uint32_t rlo = (uint32_t)__shfl((int)lo, row), rspan = (uint32_t)__shfl((int)span, row), rlive = (uint32_t)__shfl((int)live, row);
+            const bool pass = col_in && tag_value_pass(wt, wv, wt, keep, rlo, rspan, rlive) && dist < thr_s[row];
+            const unsigned long long mask = __ballot(pass);
+            if (mask)
+                row_append<CAP>(buf, cnt, row, pass, mask, dist, label, m, kk);
+        }
+        rows_compact<CAP>(buf, cnt, thr_s, k, lane);
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            gate[r] = f16_gate(qn_r[r], thr_s[mfma32_row(r, kk)]);
+    }
+}
+
+// Qh, qn, out_keys: at the tag plan's first row; nrows: the rows of a split of the partial table.  qtags, qranges: the
+// chunk's tags and intervals in the caller's order, read through the plan's strip_rows.
+template <int ND, int CAP, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void exact_f16_gated_kernel(const _Float16 *__restrict__ Qh, const float *__restrict__ qn,
+                                                                     const _Float16 *__restrict__ X, const float *__restrict__ xn,
+                                                                     int nrows, int k, unsigned long long *__restrict__ out_keys,
+                                                                     StripPlan sp, const uint16_t *__restrict__ qtags,
+                                                                     const uint32_t *__restrict__ qranges, const uint32_t *__restrict__ vals)
+{
+    constexpr int D = 16 * ND;
+    constexpr int NPRE = ND <= 8 ? ND : (ND + 1) / 2, NLATE = ND - NPRE;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *s_buf = reinterpret_cast<unsigned long long *>(smem); // [WAVES][32][CAP]
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_buf + WAVES * 32 * CAP);  // [WAVES][32]
+    float *s_thr = reinterpret_cast<float *>(s_cnt + WAVES * 32);             // [WAVES][32]
+
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int m = lane & 31, kk = lane >> 5;
+    const uint32_t strip = sp.hdr->lay.range[kSweepColsIndirect][0] + blockIdx.x * WAVES + wave;
+    if (strip >= sp.hdr->lay.range[kSweepColsIndirect][1])
+        return;
+    const StripCols e = sp.strip_cols[strip];
+    size_t c_begin, c_end;
+    sweep_split_cut(e.nx, (int)gridDim.y, (int)blockIdx.y, &c_begin, &c_end);
+    if (c_begin >= c_end)
+        return;
+    const uint32_t *__restrict__ rows = e.data;
+    const int r0 = (int)(strip << 5); // (strip < the plan's bound: every row of it exists in Qh, qn and strip_rows)
+    unsigned long long *buf = s_buf + (size_t)wave * 32 * CAP;
+    uint32_t *cnt = s_cnt + wave * 32;
+    float *thr_s = s_thr + wave * 32;
+
+    f16x8 a[ND];
+    {
+        const _Float16 *qr = Qh + (size_t)(r0 + m) * D + 8 * kk;
+#pragma unroll
+        for (int s = 0; s < ND; s++)
+            a[s] = *reinterpret_cast<const f16x8 *>(qr + 16 * s);
+    }
+    // the interval of row m; valid: the row is a query and its interval is not empty.  The envelope of the valid rows.
+    const int q_m = sp.strip_rows[r0 + m];
+    const ValueFill f = value_fill(q_m >= 0 ? qranges[2 * (size_t)q_m] : 1u, q_m >= 0 ? qranges[2 * (size_t)q_m + 1] : 0u, vals != nullptr);
+    const bool valid = q_m >= 0 && f.live;
+    uint32_t elo = valid ? f.lo : ~0u, ehi = valid ? f.lo + f.span : 0u;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) { // (lanes m and m + 32 hold the same interval: each half finds the envelope)
+        elo = min(elo, (uint32_t)__shfl_xor((int)elo, o));
+        ehi = max(ehi, (uint32_t)__shfl_xor((int)ehi, o));
+    }
+    const uint32_t LO = __builtin_amdgcn_readfirstlane(elo), HI = __builtin_amdgcn_readfirstlane(ehi);
+    const uint32_t wt = qtags[sp.strip_rows[r0]]; // the list's tag (row 0 of a strip is a query)
+    if (lane < 32) {
+        cnt[lane] = 0;
+        thr_s[lane] = valid ? FLT_MAX : -INFINITY;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float qn_r[16], gate[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = mfma32_row(r, kk);
+        qn_r[r] = qn[r0 + row];
+        gate[r] = f16_gate(qn_r[r], thr_s[row]);
+    }
+
+    if (LO <= HI) { // (else no row of the strip can find anything)
+        const unsigned char *xb = reinterpret_cast<const unsigned char *>(X) + 16 * kk;
+        const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        const uint32_t *__restrict__ vp = vals ? vals : rows; // (without values: element 0 of a readable array, ignored)
+        // the row number of the lane's column of the tile that begins at c0; the value word of that row; is it in the envelope
+        auto ids = [&](size_t c0) -> uint32_t { return c0 + m < c_end ? rows[c0 + m] : 0u; };
+        auto val = [&](size_t c0, uint32_t id) -> uint32_t { return c0 + m < c_end ? vp[value_index(id, f.keep)] : 0u; };
+        auto in_env = [&](size_t c0, uint32_t w) -> bool {
+            const uint32_t v = w | ~f.keep;
+            return c0 + m < c_end && LO <= v && v <= HI;
+        };
+        // pieces [first, first + N) of store row `row` into w; ok: the lane has a column that is read
+        auto pieces = [&](uint32_t row, bool ok, int first, auto &w) {
+            constexpr int N = (int)(sizeof(w) / sizeof(w[0]));
+            const unsigned char *p = xb + (size_t)row * (2 * D) + 32 * first;
+#pragma unroll
+            for (int s = 0; s < N; s++)
+                w[s] = zero;
+            if (ok) {
+#pragma unroll
+                for (int s = 0; s < N; s++)
+                    w[s] = *reinterpret_cast<const f16x8 *>(p + 32 * s);
+            }
+        };
+        // The tile at c0: id_c its row numbers, w_c its values, live_c whether it is live, and if so `cur`, n_cur its first NPRE
+        // pieces and its norms; id_n the row numbers of tile c0 + 32.  w_in: the values of tile c0 + 32, id_in: the row numbers
+        // of tile c0 + 64, both requested a tile ago.  Starts the loads of tile c0 + 32 into nxt, n_nxt if that tile is live, of
+        // the values of tile c0 + 64 into w_out and of the row numbers of tile c0 + 96 into id_out.
+        uint32_t id_c = ids(c_begin), id_n = 0, w_c;
+        bool live_c; // wave-uniform
+        auto tile = [&](size_t c0, const f16x8 (&cur)[NPRE], float n_cur, f16x8 (&nxt)[NPRE], float &n_nxt, uint32_t w_in, uint32_t id_in,
+                        uint32_t &w_out, uint32_t &id_out) {
+            const bool in_c = in_env(c0, w_c);
+            f16x8 late[NLATE > 0 ? NLATE : 1];
+            if constexpr (NLATE > 0) {
+                if (live_c)
+                    pieces(id_c, in_c, NPRE, late);
+            }
+            bool live_n = false;
+            if (c0 + 32 < c_end) { // in flight behind this tile's MFMAs
+                const bool in_n = in_env(c0 + 32, w_in);
+                live_n = __ballot(in_n) != 0;
+                if (live_n) {
+                    pieces(id_n, in_n, 0, nxt);
+                    n_nxt = in_n ? xn[id_n] : 0.f;
+                }
+            }
+            if (c0 + 64 < c_end)
+                w_out = val(c0 + 64, id_in);
+            if (c0 + 96 < c_end)
+                id_out = ids(c0 + 96);
+            if (live_c) {
+                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int s = 0; s < NPRE; s++)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], cur[s], acc, 0, 0, 0);
+                if constexpr (NLATE > 0) {
+#pragma unroll
+                    for (int s = 0; s < NLATE; s++)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPRE + s], late[s], acc, 0, 0, 0);
+                }
+                f16_select_gated<CAP>(acc, n_cur, in_c, id_c, w_c, wt, f.keep, f.lo, f.span, f.live, qn_r, gate, buf, cnt, thr_s, k, lane);
+            }
+            id_c = id_n, w_c = w_in, live_c = live_n, id_n = id_in; // (all arrived: none was requested in this tile)
+        };
+
+        f16x8 b0[NPRE], b1[NPRE];
+        float n0 = 0.f, n1 = 0.f;
+        uint32_t id_a = 0, id_b = 0, w_a = 0, w_b = 0;
+        if (c_begin + 32 < c_end)
+            id_n = ids(c_begin + 32);
+        if (c_begin + 64 < c_end)
+            id_b = ids(c_begin + 64);
+        w_c = val(c_begin, id_c);
+        if (c_begin + 32 < c_end)
+            w_b = val(c_begin + 32, id_n);
+        {
+            const bool in0 = in_env(c_begin, w_c);
+            live_c = __ballot(in0) != 0;
+            if (live_c) {
+                pieces(id_c, in0, 0, b0);
+                n0 = in0 ? xn[id_c] : 0.f;
+            }
+        }
+        for (size_t c0 = c_begin;;) {
+            tile(c0, b0, n0, b1, n1, w_b, id_b, w_a, id_a);
+            if ((c0 += 32) >= c_end)
+                break;
+            tile(c0, b1, n1, b0, n0, w_a, id_a, w_b, id_b);
+            if ((c0 += 32) >= c_end)
+                break;
+        }
+    }
+
+    // out: [split][row of the table][k] keys, every row of the strip (a padding row holds nothing)
+    rows_write_out<CAP>(buf, cnt, k, lane, 32, out_keys, (size_t)blockIdx.y * nrows + r0);
+}
+
+template <int ND, int CAP, int WAVES>
+hipError_t launch_exact_f16_gated_t(hipStream_t s, const _Float16 *Qh, const float *qn, const _Float16 *X, const float *xn, size_t bound,
+                                    size_t part_rows, int k, int nsplit, unsigned long long *part, const StripPlan &sp, const uint16_t *qtags,
+                                    const uint32_t *qranges, const uint32_t *vals)
+{
+    const size_t shm = (size_t)WAVES * 32 * CAP * sizeof(unsigned long long) + (size_t)WAVES * 32 * (sizeof(uint32_t) + sizeof(float));
+    constexpr auto kern = exact_f16_gated_kernel<ND, CAP, WAVES>;
+    if (hipError_t e = dyn_lds<kern>(shm); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((bound + WAVES - 1) / WAVES), (unsigned)nsplit), dim3(64 * WAVES), shm, s, Qh, qn, X, xn,
+                       (int)part_rows, k, part, sp, qtags, qranges, vals);
+    return hipGetLastError();
+}
+
+// the minor keys of the tag plan and the intervals of the value plan of a chunk of a _tags_values call: a tagged query is
+// ordered inside its tag by its lo and gets the empty interval (1, 0) -- no strip of the value plan; an untagged one keeps
+// its interval there
+__global__ __launch_bounds__(256) void f16_tags_values_split_kernel(const uint16_t *__restrict__ qtags, const uint32_t *__restrict__ qr, size_t m,
+                                                                    uint32_t *__restrict__ lo_keys, uint32_t *__restrict__ vranges)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= m)
+        return;
+    const bool untagged = qtags[q] == kRowTagNone;
+    lo_keys[q] = untagged ? 0u : qr[2 * q];
+    vranges[2 * q] = untagged ? qr[2 * q] : 1u;
+    vranges[2 * q + 1] = untagged ? qr[2 * q + 1] : 0u;
+}
+
+// The merge of a _tags_values chunk, one wavefront per row of the partial table [split][rows_v + rows_t][k]: rows [0, rows_v)
+// are the value plan's (spv: the untagged queries, Dense under ns_dense, windowed under ns_win), the rest the tag plan's
+// (spt), of which only the Indirect strips count (under ns_tag) -- its Dense strips hold the untagged queries, which the
+// value plan answers.  sides: bit 0 the value plan was swept, bit 1 the tag plan.
+__global__ __launch_bounds__(64) void exact_f16_merge_two_kernel(const unsigned long long *__restrict__ part, int ns_dense, int ns_win,
+                                                                 int ns_tag, int rows_v, int nrows, int k, float *__restrict__ dists,
+                                                                 long long *__restrict__ labels, StripPlan spv, StripPlan spt, unsigned sides)
+{
+    const bool tagside = (int)blockIdx.x >= rows_v;
+    if (!(sides >> (tagside ? 1 : 0) & 1u))
+        return;
+    const StripPlan &sp = tagside ? spt : spv;
+    const uint32_t row = tagside ? blockIdx.x - rows_v : blockIdx.x, strip = row >> 5;
+    if (strip >= sp.hdr->lay.nstrips)
+        return;
+    const bool indirect = strip >= sp.hdr->lay.range[kSweepColsIndirect][0];
+    if (tagside && !indirect)
+        return;
+    const int q = sp.strip_rows[row];
+    if (q < 0)
+        return;
+    int ns = ns_dense;
+    if (indirect) {
+        const int nsi = tagside ? ns_tag : ns_win;
+        const size_t nx = sp.strip_cols[strip].nx, cps = sweep_cols_per_split(nx, nsi);
+        ns = (int)min((size_t)nsi, (nx + cps - 1) / cps);
+    }
+    sweep_merge_row(
+        part, ns, nrows, k, (int)blockIdx.x, q,
+        [&](size_t o, unsigned long long key) {
+            labels[o] = (long long)(uint32_t)key;
+            dists[o] = orderable_f32((uint32_t)(key >> 32));
+        },
+        [&](size_t o) { // fewer than k rows pass for the query
+            labels[o] = -1ll;
+            dists[o] = FLT_MAX;
+        });
 }
 
 // f(int_c<ND>()) for ND = d / 16 = 1 .. 16; any other d is refused
@@ -1498,6 +1782,75 @@ hipError_t launch_exact_search_f16_strips(hipStream_t s, const void *Qh, const f
         return e;
     hipLaunchKernelGGL(exact_f16_merge_strips_kernel, dim3((unsigned)rows), dim3(64), 0, s, part, ns_dense, ns_ind, rows, k, dists,
                        reinterpret_cast<long long *>(labels), sp);
+    return hipGetLastError();
+}
+
+hipError_t launch_f16_tags_values_split(hipStream_t s, const uint16_t *d_tags, const uint32_t *d_ranges, size_t m, uint32_t *lo_keys,
+                                        uint32_t *vranges)
+{
+    if (m == 0)
+        return hipSuccess;
+    if (!d_tags || !d_ranges || !lo_keys || !vranges)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(f16_tags_values_split_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_tags, d_ranges, m, lo_keys, vranges);
+    return hipGetLastError();
+}
+
+// ... under a tag AND an interval per query.  Qh, qn [(bound_v + bound_t) * 32]: the chunk's nq queries
+// gathered by the value plan spv (its rows first) and by the tag plan spt; part [max of the splits][(bound_v + bound_t) * 32][k].
+// spv (null: no untagged query, nothing of it is launched): the plan of the untagged queries' intervals with its windows
+// win, Dense strips by the staged kernel under ns_dense, windowed ones (`windowed`: the holder has values) under ns_win.
+// spt (null: nothing of it is launched): the tag plan, whose Indirect strips go to the gated kernel under ns_tag with the
+// chunk's tags and intervals d_tags, d_ranges and the holder's values (null: none).  One merge; FLT_MAX / -1 for a query
+// without a strip.
+hipError_t launch_exact_search_f16_tags_values(hipStream_t s, const void *Qh, const float *qn, const void *X, const float *xn, size_t nq,
+                                               size_t bound_v, size_t bound_t, size_t nx, int d, int k, int ns_dense, int ns_win, int ns_tag,
+                                               unsigned long long *part, float *dists, int64_t *labels, const StripPlan *spv,
+                                               const StripWin *win, bool windowed, const StripPlan *spt, const uint16_t *d_tags,
+                                               const uint32_t *d_ranges, const uint32_t *vals)
+{
+    if (nq == 0)
+        return hipSuccess;
+    const size_t bound = bound_v + bound_t;
+    if (d < 16 || d > 256 || (d & 15) || k < 1 || k > 100 || bound_v == 0 || bound_t == 0 || bound > (0x7fffffffull >> 5) || nx == 0 ||
+        nx > 0xffffffffull - 64 || ns_dense < 1 || ns_dense > 64 || ns_win < 1 || ns_win > 64 || ns_tag < 1 || ns_tag > 64 ||
+        (spv && (!spv->hdr || !spv->strip_rows || !spv->strip_cols || !win)) ||
+        (spt && (!spt->hdr || !spt->strip_rows || !spt->strip_cols || !d_tags || !d_ranges)))
+        return hipErrorInvalidValue;
+    const int rows = (int)(bound * 32), rows_v = (int)(bound_v * 32);
+    if (hipError_t e = launch_exact_pad(s, dists, labels, nq * (size_t)k); e != hipSuccess)
+        return e;
+    if (!spv && !spt)
+        return hipSuccess;
+    const size_t cps = sweep_cols_per_split(nx, ns_dense);
+    const _Float16 *q = reinterpret_cast<const _Float16 *>(Qh), *x = reinterpret_cast<const _Float16 *>(X);
+    const hipError_t e = by_f16_steps(d, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        hipError_t e = hipSuccess;
+        if (spv) {
+            const F16DenseStrips ds{*spv};
+            e = k <= 16   ? launch_exact_f16_t<ND, 48, 4>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds)
+                : k <= 32 ? launch_exact_f16_t<ND, 64, 4>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds)
+                          : launch_exact_f16_t<ND, 136, 2>(s, q, qn, x, xn, rows, nx, k, ns_dense, cps, part, ds);
+            if (e == hipSuccess && windowed)
+                e = k <= 16   ? launch_exact_f16_windows_t<ND, 48, 4>(s, q, qn, x, xn, bound_v, k, ns_win, part, *spv, win, rows)
+                    : k <= 32 ? launch_exact_f16_windows_t<ND, 64, 4>(s, q, qn, x, xn, bound_v, k, ns_win, part, *spv, win, rows)
+                              : launch_exact_f16_windows_t<ND, 136, 2>(s, q, qn, x, xn, bound_v, k, ns_win, part, *spv, win, rows);
+        }
+        if (e != hipSuccess || !spt)
+            return e;
+        const _Float16 *qt = q + (size_t)rows_v * d;
+        const float *qnt = qn + rows_v;
+        unsigned long long *pt = part + (size_t)rows_v * k;
+        return k <= 16   ? launch_exact_f16_gated_t<ND, 48, 4>(s, qt, qnt, x, xn, bound_t, rows, k, ns_tag, pt, *spt, d_tags, d_ranges, vals)
+               : k <= 32 ? launch_exact_f16_gated_t<ND, 64, 4>(s, qt, qnt, x, xn, bound_t, rows, k, ns_tag, pt, *spt, d_tags, d_ranges, vals)
+                         : launch_exact_f16_gated_t<ND, 136, 2>(s, qt, qnt, x, xn, bound_t, rows, k, ns_tag, pt, *spt, d_tags, d_ranges, vals);
+    });
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(exact_f16_merge_two_kernel, dim3((unsigned)rows), dim3(64), 0, s, part, ns_dense, ns_win, ns_tag, rows_v, rows, k,
+                       dists, reinterpret_cast<long long *>(labels), spv ? *spv : StripPlan{}, spt ? *spt : StripPlan{},
+                       (spv ? 1u : 0u) | (spt ? 2u : 0u));
     return hipGetLastError();
 }
 

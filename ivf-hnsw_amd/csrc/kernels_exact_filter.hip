@@ -541,7 +541,7 @@ size_t tag_plan_work_words(size_t m)
 }
 
 hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m, const TagRows &tr, void *plan, size_t bound,
-                                 uint32_t *work, StripPlan *sp)
+                                 uint32_t *work, StripPlan *sp, const uint32_t *minor_keys)
 {
     if (m == 0 || m > kExactChunk || bound < m / 32 + 1 || bound > 0x7fffffffull / 32 || !d_tags || !plan || !work)
         return hipErrorInvalidValue;
@@ -563,8 +563,12 @@ hipError_t launch_tag_strip_plan(hipStream_t s, const uint16_t *d_tags, size_t m
     hipLaunchKernelGGL(tag_bucket_strips_kernel, tgrid, dim3(256), 0, s, qcnt, tr, nstr);
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
+    // stable by the minor key, then from that order stable by the bucket: (bucket, minor key, position)
     uint32_t *sorted = nullptr;
-    if (hipError_t e = launch_sort_by_key(s, keys, m, 16, ids_a, ids_b, hist, &sorted); e != hipSuccess)
+    if (minor_keys)
+        if (hipError_t e = launch_sort_by_key(s, minor_keys, m, 32, ids_a, ids_b, hist, &sorted); e != hipSuccess)
+            return e;
+    if (hipError_t e = launch_sort_by_key_from(s, keys, m, 16, sorted, ids_a, ids_b, hist, &sorted); e != hipSuccess)
         return e;
     if (hipError_t e = launch_scan_excl_u32(s, qcnt, kTagValues + 1, part); e != hipSuccess)
         return e;

@@ -34,6 +34,9 @@
      replaces, per distinct interval set_base_filter_dev(the interval's rows) + the plain call on its queries, with and
      without the installs; k = 1, k = 100 and the range form at the median k = 10 distance with the reorder's share of
      it; and the time of set_base_values_dev over every row.
+     With --f16 --tags-values a tag AND an interval per query on the float16 store (ivfhnsw_gpu_exact_search_f16_tags_values_dev,
+     DESIGN.md 3.33) at d = 128: intervals of an eighth of each tag's rows under ascending and under shuffled values beside
+     exact_search_f16_tags_dev, the all-whole batch beside it and the all-(NONE, whole) batch beside the plain call.
   8. With --f16 ONLY the float16 store (ivfhnsw_gpu_exact_search_f16_dev): --small-rows x 128 and x 96 rows
      of random bytes as float32, k = 1, 10 and 100, alternating in one process with ivfhnsw_gpu_knn_dev on the same rows as
      float32 (k <= 80) and exact_search_dev on a uint8 store of the same rows; all three are exact on such rows and must
@@ -140,6 +143,7 @@ def main():
     ap.add_argument("--filter-slots", action="store_true", help="add the base-filter-slot legs (DESIGN.md 3.20)")
     ap.add_argument("--tags", action="store_true", help="add the base-tag legs (DESIGN.md 3.22)")
     ap.add_argument("--values", action="store_true", help="add the base-value legs (DESIGN.md 3.25)")
+    ap.add_argument("--tags-values", action="store_true", help="with --f16: add the tag-and-interval legs (DESIGN.md 3.33)")
     ap.add_argument("--f16", action="store_true", help="only the float16 store's legs (DESIGN.md 3.27), at d = 128 and d = 96 on --small-rows rows")
     ap.add_argument("--range", action="store_true", help="with --f16: add the float16 store's exact range search legs (DESIGN.md 3.28)")
     ap.add_argument("--dense-nq", type=int, default=512, help="queries of the dense (median distance) range leg")
@@ -835,6 +839,58 @@ def main():
         f16_tags_range_leg(n, dd, g8, qf, qb, None, 0, float(odp[:, 9].median()), alternate, with_splits)
         g.clear_base_tags()
 
+    def f16_tags_values_legs(n, dd, qf):
+        """A tag AND an interval per query on the float16 store (exact_search_f16_tags_values_dev), the calls
+        of a leg alternating rep by rep in one process.  Per tag count (row i carries tag i % ntags, query q asks for
+        q % ntags) and k: intervals of 1/8 of each tag's rows under values that ascend with the row number (timestamps: most
+        tiles of a list are dead) and under the same values shuffled (none is), each beside exact_search_f16_tags_dev on the
+        same tags -- the same sweep without the gate; then the all-whole tagged batch beside that call, and the
+        all-(NONE, whole) batch beside the plain one."""
+        rows_i = torch.arange(n, device=dev, dtype=torch.int32)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(5)
+        layouts = {"ascending": rows_i.clone(), "shuffled": torch.randperm(n, device=dev, generator=gen).to(torch.int32)}
+        whole = torch.tensor([0, -1], dtype=torch.int32, device=dev).repeat(nq, 1)  # (0, 0xffffffff)
+        lo = ((torch.arange(nq, device=dev, dtype=torch.int64) * 7919) % (n - n // 8)).to(torch.int32)
+        eighth = torch.stack([lo, lo + n // 8 - 1], 1).contiguous()  # values are 0 .. n - 1: an eighth of every tag's rows
+        for ntags in (32, 1024):
+            g.set_base_tags_dev(n, rows_i, (rows_i % ntags).to(torch.int16))
+            qt = (torch.arange(nq, device=dev, dtype=torch.int32) % ntags).to(torch.int16)
+            for k in (1, 100):
+                od, ol = torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev)
+                odt, olt = torch.empty_like(od), torch.empty_like(ol)
+                tags_only = ("exact_search_f16_tags_dev", lambda: g.exact_search_f16_tags_dev(nq, qf, dd, k, qt, odt, olt))
+                for lname, values in layouts.items():
+                    g.set_base_values_dev(n, rows_i, values)
+                    for wname, qr in (("an eighth", eighth), ("whole", whole)):
+                        if wname == "whole" and lname == "shuffled":
+                            continue
+                        both = ("exact_search_f16_tags_values_dev", lambda: g.exact_search_f16_tags_values_dev(nq, qf, dd, k, qt, qr, od, ol))
+                        ts = alternate([both, tags_only], "%d tags k=%d %s %s" % (ntags, k, lname, wname))
+                        if wname == "whole":
+                            assert torch.equal(ol, olt) and torch.equal(od, odt), "the all-whole batch and the _tags call disagree"
+                        a, b = ts[both[0]], ts[tags_only[0]]
+                        r = {"what": both[0], "beside": tags_only[0], "rows": n, "d": dd, "nq": nq, "k": k, "tags": ntags, "values": lname,
+                             "intervals": wname, "seconds": round(statistics.median(a), 5), "reps": [round(x, 5) for x in a],
+                             "beside_seconds": round(statistics.median(b), 5), "beside_span": [round(min(b), 5), round(max(b), 5)],
+                             "ratio": round(statistics.median(a) / statistics.median(b), 3)}
+                        result["rows"].append(r)
+                        print(json.dumps(r), flush=True)
+        none = torch.full((nq,), -1, dtype=torch.int16, device=dev)  # 0xffff: every query untagged
+        for k in (1, 100):
+            od, ol = torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev)
+            odp, olp = torch.empty_like(od), torch.empty_like(ol)
+            ts = alternate([("all (NONE, whole)", lambda: g.exact_search_f16_tags_values_dev(nq, qf, dd, k, none, whole, od, ol)),
+                            ("exact_search_f16_dev", lambda: g.exact_search_f16_dev(nq, qf, dd, k, odp, olp))], "all (NONE, whole) k=%d" % k)
+            assert torch.equal(ol, olp) and torch.equal(od, odp), "the all-(NONE, whole) batch and the plain call disagree"
+            a, b = ts["all (NONE, whole)"], ts["exact_search_f16_dev"]
+            r = {"what": "all (NONE, whole) beside the plain call", "rows": n, "d": dd, "nq": nq, "k": k, "seconds": round(statistics.median(a), 5),
+                 "reps": [round(x, 5) for x in a], "plain_seconds": round(statistics.median(b), 5), "plain_span": [round(min(b), 5), round(max(b), 5)]}
+            result["rows"].append(r)
+            print(json.dumps(r), flush=True)
+        g.clear_base_tags()
+        g.clear_base_values()
+
     def f16_legs(n, dd):
         """The float16 store's sweep (exact_search_f16_dev) beside knn_dev on the same rows as float32 and
         exact_search_dev on a uint8 store of the same rows, alternating in one process.  The rows are random bytes, so all
@@ -893,6 +949,8 @@ def main():
             f16_tags_legs(n, dd, g8, qf, qb)
         if args.values and dd == 128:
             f16_values_legs(n, dd, g8, qf, qb)
+        if args.tags_values and dd == 128:
+            f16_tags_values_legs(n, dd, qf)
         g8.close()
         if args.range:
             f16_range_legs(n, dd, qf, kth[10], kth[100])

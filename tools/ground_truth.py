@@ -27,7 +27,8 @@ gets only rows whose value lies in [lo, hi], inclusive ((0, 0xffffffff): every r
 With an .fvecs base and .fvecs queries (float corpora: DEEP1B) the same .ivecs is written from the float16 base store
 (upload_base_fvecs, ivfhnsw_gpu_exact_search_f16): rows and queries rounded to half; of the filters the k-search
 takes --tags with --query-tags (ivfhnsw_gpu_exact_search_f16_tags, 3.29) or --values with --query-ranges
-(ivfhnsw_gpu_exact_search_f16_values, 3.31), nothing else.  With
+(ivfhnsw_gpu_exact_search_f16_values, 3.31), or both pairs together (ivfhnsw_gpu_exact_search_f16_tags_values, 3.33: the rows
+that pass both rules), nothing else.  With
 --radius the .npz comes from ivfhnsw_gpu_exact_range_search_f16 (3.28): the rows whose float32 distance between the rounded
 vectors, the value the k-search returns, is < R -- and with --tags and --query-tags from
 ivfhnsw_gpu_exact_range_search_f16_tags (3.30): only the rows that carry the query's tag; with --values and --query-ranges
@@ -205,6 +206,11 @@ def ground_truth_f16(pkg, base_path, query_path, k, rows=None, device=0, chunk_r
         n, d = g.upload_base_fvecs(base_path, chunk_rows=chunk_rows, rows=rows)
         if d != dq:
             raise ValueError("base dimension %d, query dimension %d" % (d, dq))
+        if values is not None and tags is not None:  # both rules at once (ivfhnsw_gpu_exact_search_f16_tags_values, 3.33)
+            install_values(g, n, img.shape[0], values, query_ranges)
+            install_tags(g, n, img.shape[0], tags, query_tags)
+            _, lab = g.exact_search_f16_tags_values(img[:, 1:], k, query_tags, query_ranges)
+            return lab
         if values is not None:
             install_values(g, n, img.shape[0], values, query_ranges)
             _, lab = g.exact_search_f16_values(img[:, 1:], k, query_ranges)
@@ -322,8 +328,9 @@ def main(argv=None):
     ap.add_argument("--query-ranges", default=None, help="an .npy file of uint32 [nq, 2]: the interval (lo, hi) of every query, "
                                                          "inclusive ((0, 0xffffffff): every row)")
     args = ap.parse_args(argv)
-    if (args.values is None) != (args.query_ranges is None) or (args.values and (args.allow or args.deny or args.tags)):
-        ap.error("--values and --query-ranges go together, and not with --allow / --deny / --tags")
+    both = args.values and args.tags and args.base.endswith(".fvecs") and args.radius is None  # (the float16 k-search takes both, 3.33)
+    if (args.values is None) != (args.query_ranges is None) or (args.values and (args.allow or args.deny or (args.tags and not both))):
+        ap.error("--values and --query-ranges go together, and not with --allow / --deny / --tags (but for an .fvecs k-search)")
     values = read_values(args.values) if args.values else None
     query_ranges = read_values(args.query_ranges) if args.values else None
     if (args.tags is None) != (args.query_tags is None) or (args.tags and (args.allow or args.deny)):
